@@ -5,7 +5,10 @@ A "step" is one pass of the hot path (BiWFA gap-affine-2p alignment, penalties
 5,8,2,24,1; wflign.cpp:136-148) over one batch of synthetic mapping records:
 BASELINE.json configs[2], "synthetic 5%-divergence 64x50kb segment pairs,
 WFA-only (mappings pre-supplied), 1 GPU" (generator: SURVEY.md 8d / wfmash_amd/synth.py).
-The other configs are reported in the same line as `secondary` legs, driver-timed end to end
+A plain run sets up, warms up, times --steps steps, writes the last step's outputs (--dump-outputs DIR)
+and prints the line.  With --full, the line also holds the roofline (from two untimed passes of
+its own), the CPU baseline with the CIGAR-identical rate of its sample, and the other configs
+as `secondary` legs, driver-timed end to end
 through the C ABI and each with a sampled parity check against the oracles: C1 (substitute:
 synth.yeast_like, the data blob is absent), C2 (LPA.subset all-vs-all, the reference's test data,
 a committed fixture), one rank of C4 at two sizes, C5; `value` stays C3, the largest
@@ -59,14 +62,24 @@ def main():
                     help="weak: --pairs records per GPU (the driver's SCALE runs); strong: one file of --total-pairs records "
                          "sharded over the ranks by dist.shard_records, the same file at every N")
     ap.add_argument("--total-pairs", type=int, default=512, help="records of the strong-scaling file (64 x 8)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps, everything else the line can report: the roofline (two untimed passes of their own), the CPU "
+                         "baseline with its CIGAR-identical rate, and the secondary legs; without it a run only sets up, warms up, times the steps, "
+                         "writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-sample", type=int, default=0, help="pairs in the cpu_baseline sample (0 = auto)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary figures (C5, C1 substitute, C4 ranks, C2)")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the secondary figures (C5, C1 substitute, C4 ranks, C2)")
     ap.add_argument("--legs", default="", help="comma-separated subset of the secondary legs to run (C5,C1_substitute,C4_rank_scaled,C4_rank_40mbp,C4_rank_full,C4_all_vs_all,C2,map_parity); default all")
     ap.add_argument("--no-full-c4", action="store_true", help="skip the chr1-sized C4 rank among the secondary legs (2 GB of synthetic haplotypes: ~20 s to make)")
     ap.add_argument("--rank-check", action="store_true",
                     help="launch / join the ranks, print one line per rank and stop (no GPU needed: gloo)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.config == "C4":
+        ap.error("--dump-outputs: --config C3 / C5 (the C4 job's records go to --out-paf)")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # not under a launcher: start one process per GPU ourselves
@@ -140,7 +153,8 @@ def main():
     # this rank's shard of the mapping records (weak: distinct seeds per rank; strong: its share of the one file)
     n_all = args.pairs * world if args.scaling == "weak" else args.total_pairs
     all_pairs = synth.pairs(args.config, n_pairs=n_all)
-    mine = [all_pairs[i] for i in _shard(args, rank, world, all_pairs)]
+    mine_idx = _shard(args, rank, world, all_pairs)
+    mine = [all_pairs[i] for i in mine_idx]
     seqset = h.upload(mine)
     query_bases = sum(len(q) for _, q in mine)  # "total aligned bp" = sum of query spans (computeAlignments.hpp:481,528)
     job_bases = sum(len(q) for _, q in all_pairs)  # of all ranks
@@ -177,22 +191,14 @@ def main():
         tt = torch.tensor([dt], dtype=torch.float64, device=comm_dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if args.dump_outputs:
+        _dump_alignments(args.dump_outputs, capi.Handle._collect(seqset), mine_idx, mine, "" if world == 1 else f".rank{rank}",
+                         DUMP_BUDGET_BYTES // world)
 
     out = None
     if rank == 0:
         value = job_bases * args.steps / dt
         seq_bytes = sum(len(p) + len(q) for p, q in mine) * 2  # forward + reversed copies
-        # one more, untimed, pass with the parts of the batch one after the other on one stream (WFM_OVERLAP=0): every
-        # launch then has the GPU to itself, which is what rocprofv3's per-launch durations of that mode show
-        excl = _StatAcc()
-        os.environ["WFM_OVERLAP"] = "0"
-        try:
-            for _ in range(2):
-                h.align_resident(seqset, collect=False)
-                excl.add(h.stats())
-        finally:
-            del os.environ["WFM_OVERLAP"]
-        roof = _roofline(acc, excl, seq_bytes, args)
         out = {
             "metric": "aligned bases/sec (whole node) + CIGAR-identical rate vs CPU ref",
             "value": value, "unit": "aligned bases/s", "n_gpus": world, "steps": args.steps,
@@ -205,7 +211,6 @@ def main():
                                    f"{'per GPU' if args.scaling == 'weak' else 'in all, sharded over the GPUs'}, WFA-only "
                                    "(BiWFA gap-affine-2p 5,8,2,24,1; mappings pre-supplied)",
                        "pairs_per_gpu": len(mine), "pairs_total": n_all, "parallelism": f"records sharded over {world} GPU(s)"},
-            "roofline": roof,
             # time during which at least one launch of the kernel was running (union of the launch intervals over all
             # streams, HIP events against one origin), and the sum of the individual launch durations
             "kernel_busy_ms_per_step": {"wfa_tile2_kernel": acc.ms_tile_busy / args.steps, "wfa_bp_kernel": acc.ms_bp_busy / args.steps,
@@ -218,8 +223,20 @@ def main():
                            "note": "48 B x unique cells of all kernels / wall time of the step"},
             "device": h.device_name(),
         }
+        if args.full:
+            # two more, untimed, passes with the parts of the batch one after the other on one stream (WFM_OVERLAP=0): every
+            # launch then has the GPU to itself, which is what rocprofv3's per-launch durations of that mode show
+            excl = _StatAcc()
+            os.environ["WFM_OVERLAP"] = "0"
+            try:
+                for _ in range(2):
+                    h.align_resident(seqset, collect=False)
+                    excl.add(h.stats())
+            finally:
+                del os.environ["WFM_OVERLAP"]
+            out["roofline"] = _roofline(acc, excl, seq_bytes, args)
         # ---- CPU baseline (oracle = "port") on a bounded sample of the same workload ----
-        if not args.no_cpu_baseline and world == 1:  # the CPU baseline is timed on rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # the CPU baseline is timed on rank 0 at N = 1 only
             from oracle import pyoracle as O
             cores = os.cpu_count() or 1
             n_s = args.cpu_sample or min(len(mine), max(8, cores))
@@ -240,7 +257,7 @@ def main():
             out["cigar_identical_rate"] = ident / n_s
             out["score_identical_rate"] = score_ident / n_s
             out["cpu_baseline_map"] = _cpu_baseline_map(h)
-        if not args.no_secondary and world == 1:
+        if args.full and not args.no_secondary and world == 1:
             out["secondary"] = _secondary(h, capi, synth, full_c4=not args.no_full_c4, only=set(x for x in args.legs.split(",") if x))
             out["legs"] = _legs_summary(out)  # the last thing in the line: a reader of its tail sees every leg
         print(json.dumps(out), flush=True)
@@ -346,7 +363,7 @@ def _strong_c4(args, h, capi, synth, dist, rank, world, comm_dev, torch):
                                    "note": "48 B x the cells of ALL align kernels / the time any of them was running on rank 0's device"},
                     "note": "launch durations are summed over workers whose launches overlap (an upper bound of the kernel's own time); the yardstick and the VALU floor are "
                             "the C3 line's (DESIGN.md section 5)"}
-            if world == 1 and not args.no_cpu_baseline:
+            if args.full and world == 1 and not args.no_cpu_baseline:
                 # the CPU baseline on a bounded sample of the same records: oracle/wflign_host.py over oracle/wfa2p.c, one record per thread
                 from oracle import wflign_host as W
                 from concurrent.futures import ThreadPoolExecutor
@@ -409,6 +426,34 @@ def _shard(args, rank, world, pairs):
     else:
         weights = [float(len(q)) ** 2 for _, q in pairs]
     return shard_records(weights, world)[rank]
+
+
+DUMP_BUDGET_BYTES = 63 << 20  # 64 MB in all, with room to spare for the .npy headers
+
+
+def _dump_alignments(out_dir, res, idx, pairs, suffix, budget):
+    """--dump-outputs: what a caller of the timed path receives for each record of the last step -- status, score and the CIGAR
+    (its ops over {M,X,I,D} as character codes, the records' ops one after the other) -- as DIR/<name><suffix>.npy.  Past the byte
+    budget, a sample of the records fixed by a seed and the input lengths (never by the outputs): record.npy names them."""
+    import numpy as np
+    bound = [8 * 4 + 4 * (len(p) + len(q)) for p, q in pairs]  # an op string is never longer than pattern + text
+    keep = list(range(len(res)))
+    if sum(bound) > budget:
+        keep, used = [], 0
+        for i in np.random.default_rng(0xD0).permutation(len(res)).tolist():
+            if used + bound[i] <= budget:
+                keep.append(i)
+                used += bound[i]
+        keep.sort()
+    ops = [res[i].ops or b"" for i in keep]
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"record": np.array([idx[i] for i in keep], dtype=np.float64),
+              "status": np.array([res[i].status for i in keep], dtype=np.float64),
+              "score": np.array([res[i].score for i in keep], dtype=np.float64),
+              "cigar_len": np.array([len(o) for o in ops], dtype=np.float64),
+              "cigar_ops": np.frombuffer(b"".join(ops), dtype=np.uint8).astype(np.float32)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
 
 
 class _StatAcc:

@@ -4,7 +4,7 @@
 root=$(cd "$(dirname "$0")/.." && pwd)
 for setting in "$@"; do
   echo "==== setting: [$setting]"
-  env $setting python $root/bench.py --steps 2 --warmup 1 --no-cpu-baseline --legs C4_rank_full,C4_all_vs_all 2>/dev/null | python -c '
+  env $setting python $root/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --legs C4_rank_full,C4_all_vs_all 2>/dev/null | python -c '
 import sys, json
 for line in sys.stdin:
     if line.startswith("{"):

@@ -5,7 +5,7 @@
 root=$(cd "$(dirname "$0")/.." && pwd)
 for setting in "$@"; do
   echo "==== setting: [$setting]"
-  env $setting python $root/bench.py --steps ${STEPS:-10} --warmup 3 --no-secondary --no-cpu-baseline 2>/dev/null | python -c '
+  env $setting python $root/bench.py --steps ${STEPS:-10} --warmup 3 --full --no-secondary --no-cpu-baseline 2>/dev/null | python -c '
 import sys, json
 for line in sys.stdin:
     if line.startswith("{"):

@@ -1,4 +1,4 @@
-for w in 4 6 4 6; do WFM_ALIGN_WORKERS=$w python bench.py --steps 2 --warmup 1 --no-cpu-baseline --legs C4_rank_40mbp,C4_rank_full,C4_all_vs_all 2>/dev/null | W=$w python -c '
+for w in 4 6 4 6; do WFM_ALIGN_WORKERS=$w python bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --legs C4_rank_40mbp,C4_rank_full,C4_all_vs_all 2>/dev/null | W=$w python -c '
 import sys,json,os
 for l in sys.stdin:
     if l.startswith("{"):

@@ -11,7 +11,7 @@ po=$root/gpurun_out/profiles_out
 mkdir -p "$po"
 export TMPDIR=/tmp
 cd /tmp
-B="python $root/bench.py --steps 3 --warmup 1 --no-secondary --no-cpu-baseline"
+B="python $root/bench.py --steps 3 --warmup 1 --full --no-secondary --no-cpu-baseline"
 WFM_OVERLAP=0 rocprofv3 --kernel-trace --stats -d /tmp/p3/t -o t -- $B > /tmp/p3_trace.log 2>&1
 WFM_OVERLAP=0 rocprofv3 --pmc FETCH_SIZE -d /tmp/p3/f -o f -- $B > /tmp/p3_f.log 2>&1
 WFM_OVERLAP=0 rocprofv3 --pmc WRITE_SIZE -d /tmp/p3/w -o w -- $B > /tmp/p3_w.log 2>&1

@@ -11,7 +11,7 @@ mkdir -p "$po"
 export TMPDIR=/tmp
 cd /tmp
 rm -rf /tmp/p5
-B="python $root/bench.py --steps 3 --warmup 1 --no-secondary --no-cpu-baseline"
+B="python $root/bench.py --steps 3 --warmup 1 --full --no-secondary --no-cpu-baseline"
 WFM_OVERLAP=0 rocprofv3 --kernel-trace --stats -d /tmp/p5/t -o t -- $B > /tmp/p5_trace.log 2>&1
 WFM_OVERLAP=0 rocprofv3 --pmc FETCH_SIZE -d /tmp/p5/f -o f -- $B > /tmp/p5_f.log 2>&1
 WFM_OVERLAP=0 rocprofv3 --pmc WRITE_SIZE -d /tmp/p5/w -o w -- $B > /tmp/p5_w.log 2>&1
@@ -57,7 +57,7 @@ cd "$root"
 python scripts/prof_summary.py "$po/r5_map.md" "r5: map phase of one rank of C4 at full size (8 x 249 Mbp, one query haplotype: 249 k fragments; scripts/c4_rank.py)" "$(find /tmp/p5/map -name '*results.db' | head -1)" --bench /tmp/p5_map.log > /dev/null
 # C5
 cd /tmp
-rocprofv3 --kernel-trace --stats -d /tmp/p5/c5 -o t -- python $root/bench.py --config C5 --pairs 8 --steps 2 --warmup 1 --no-secondary --no-cpu-baseline > /tmp/p5_c5.log 2>&1
+rocprofv3 --kernel-trace --stats -d /tmp/p5/c5 -o t -- python $root/bench.py --config C5 --pairs 8 --steps 2 --warmup 1 --full --no-secondary --no-cpu-baseline > /tmp/p5_c5.log 2>&1
 cd "$root"
 python scripts/prof_summary.py "$po/r5_c5.md" "r5: C5 (8 pairs of 100 kb at 15 %), align only (bench.py --config C5 --pairs 8)" "$(find /tmp/p5/c5 -name '*results.db' | head -1)" --bench /tmp/p5_c5.log > /dev/null
 ls -la "$po"

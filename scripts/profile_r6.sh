@@ -11,7 +11,7 @@ mkdir -p "$po"
 export TMPDIR=/tmp
 cd /tmp
 rm -rf /tmp/p6
-B="python $root/bench.py --steps 3 --warmup 1 --no-secondary --no-cpu-baseline"
+B="python $root/bench.py --steps 3 --warmup 1 --full --no-secondary --no-cpu-baseline"
 WFM_OVERLAP=0 rocprofv3 --kernel-trace --stats -d /tmp/p6/t -o t -- $B > /tmp/p6_trace.log 2>&1
 WFM_OVERLAP=0 rocprofv3 --pmc FETCH_SIZE -d /tmp/p6/f -o f -- $B > /tmp/p6_f.log 2>&1
 WFM_OVERLAP=0 rocprofv3 --pmc WRITE_SIZE -d /tmp/p6/w -o w -- $B > /tmp/p6_w.log 2>&1
@@ -72,7 +72,7 @@ cd "$root"
 python scripts/prof_summary.py "$po/r6_map.md" "r6: map phase of one rank of C4 at full size (8 x 249 Mbp, one query haplotype: 249 k fragments; scripts/c4_rank.py)" "$(find /tmp/p6/map -name '*results.db' | head -1)" --bench /tmp/p6_map.log > /dev/null
 # C5
 cd /tmp
-rocprofv3 --kernel-trace --stats -d /tmp/p6/c5 -o t -- python $root/bench.py --config C5 --pairs 8 --steps 2 --warmup 1 --no-secondary --no-cpu-baseline > /tmp/p6_c5.log 2>&1
+rocprofv3 --kernel-trace --stats -d /tmp/p6/c5 -o t -- python $root/bench.py --config C5 --pairs 8 --steps 2 --warmup 1 --full --no-secondary --no-cpu-baseline > /tmp/p6_c5.log 2>&1
 cd "$root"
 python scripts/prof_summary.py "$po/r6_c5.md" "r6: C5 (8 pairs of 100 kb at 15 %), align only (bench.py --config C5 --pairs 8)" "$(find /tmp/p6/c5 -name '*results.db' | head -1)" --bench /tmp/p6_c5.log > /dev/null
 ls -la "$po"

@@ -52,7 +52,7 @@ def test_two_ranks_on_one_gpu_print_one_line_for_the_job():
     """The N>1 path end to end on the one-GPU box: two ranks share the device (gloo instead of RCCL), each aligns its own
     shard, the CIGAR payload is gathered to rank 0, rank 0 prints the one JSON line with n_gpus = 2."""
     env = dict(_clean_env(), WFM_BENCH_SHARE_GPU="1")
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "1", "--warmup", "0", "--pairs", "4", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "1", "--warmup", "0", "--pairs", "4", "--full", "--no-cpu-baseline"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [j for j in _json_lines(r.stdout) if "metric" in j]
@@ -106,3 +106,68 @@ def test_c4_all_vs_all_two_ranks_give_the_records_of_one(tmp_path):
         assert j["roofline"]["bound"] == "valu"
         outs.append(out.read_bytes())
     assert len(outs[0]) > 10000 and outs[0] == outs[1]
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", BENCH)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_dump_sample_stays_in_budget_and_ignores_the_outputs(tmp_path):
+    """--dump-outputs past its byte budget: a sample of the records fixed by the inputs alone, float32 / float64 arrays within the budget."""
+    import numpy as np
+    from wfmash_amd.capi import AlignResult
+    bench = _bench_module()
+    pairs = [(b"A" * (100 + 7 * i), b"C" * (90 + 5 * i)) for i in range(40)]
+    budget = 20_000
+    dumps = []
+    for op in (b"M", b"MX"):  # two runs whose outputs differ, not their inputs
+        res = [AlignResult(0, i, op * (len(p) // len(op)), 1, 0) for i, (p, _) in enumerate(pairs)]
+        d = tmp_path / op.decode()
+        bench._dump_alignments(str(d), res, list(range(100, 140)), pairs, "", budget)
+        arrays = {f.stem: np.load(f) for f in d.iterdir()}
+        assert set(arrays) == {"record", "status", "score", "cigar_len", "cigar_ops"}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(f.stat().st_size for f in d.iterdir()) <= budget
+        assert 0 < len(arrays["record"]) < len(pairs)
+        assert arrays["cigar_len"].sum() == len(arrays["cigar_ops"])
+        dumps.append(arrays)
+    assert list(dumps[0]["record"]) == list(dumps[1]["record"])
+    assert list(dumps[0]["score"]) == [r - 100 for r in dumps[0]["record"]]
+
+
+def test_dump_outputs_refuses_the_c4_job(tmp_path):
+    r = subprocess.run([sys.executable, BENCH, "--config", "C4", "--dump-outputs", str(tmp_path)], cwd=ROOT, env=_clean_env(),
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "--dump-outputs" in r.stderr
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path, oracle):
+    """A plain run prints the headline line alone (no roofline passes, CPU baseline or secondary legs) and --dump-outputs writes the
+    last timed step's status, score and CIGAR of every record: the oracle's, record for record; the same again in a second process."""
+    import numpy as np
+    from wfmash_amd import synth
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"out{run}"
+        r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "3", "--warmup", "1", "--pairs", "4", "--dump-outputs", str(d)],
+                           cwd=ROOT, env=_clean_env(), capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        (j,) = [j for j in _json_lines(r.stdout) if "metric" in j]
+        assert j["steps"] == 3 and j["warmup"] == 1 and j["ms_per_step"] > 0 and j["value"] > 0
+        assert not {"roofline", "cpu_baseline", "secondary", "legs"} & set(j)
+        dumps.append({f.stem: np.load(f) for f in d.iterdir()})
+    a = dumps[0]
+    assert set(a) == {"record", "status", "score", "cigar_len", "cigar_ops"}
+    assert all(np.array_equal(a[k], dumps[1][k]) for k in a)
+    pairs = synth.pairs("C3", n_pairs=4)
+    assert list(a["record"]) == [0, 1, 2, 3] and not a["status"].any()
+    ops, scores, _, failed = oracle.align_batch_biwfa([p for p, _ in pairs], [q for _, q in pairs])
+    assert list(a["score"]) == [int(s) for s in scores]
+    cig = a["cigar_ops"].astype(np.uint8).tobytes()
+    ends = np.cumsum(a["cigar_len"]).astype(np.int64)
+    assert [cig[e - n:e] for e, n in zip(ends, a["cigar_len"].astype(np.int64))] == list(ops)
