@@ -181,6 +181,9 @@ typedef struct {
   int32_t  write_index;               /* 1: -W, build the index of every target subset, write it and stop;
                                          0 with index_file set: -I, read the index instead of building it */
   int32_t  pad_;
+  /* appended: nothing above moves */
+  const char* scaffold_out;           /* --scaffold-out FILE: the scaffold chains the filter used as anchors (parse_args.hpp:105,464-465);
+                                         NULL = none, and nothing of them is kept */
 } wfmh_map_params_t;
 
 void wfmh_map_default_params(wfmh_map_params_t* p);
@@ -213,6 +216,15 @@ int wfmh_map(wfm_handle_t* h, const char* target_fasta, const char* query_fasta,
  * in the reference, computeMap.hpp:527-688), records are written in query order as with one GPU. */
 int wfmh_map_multi(wfm_handle_t* const* handles, int n, const char* target_fasta, const char* query_fasta, const char* out_paf,
                    const wfmh_map_params_t* params, wfmh_map_summary_t* summary);
+
+/* External seeds (-K, parse_args.hpp:78,771-773; skch::ExternalSeeder, src/map/include/externalSeeder.hpp) in place of the
+ * MinHash mapper: the PAF records of another tool (seeds_paf; "-" or "/dev/stdin" = standard input) grouped by query, each query's
+ * through the group plane sweep, sparsification and the scaffold filter, written as a mapping PAF (the -m / -i hand-off file) to
+ * out_paf.  Host only, no device: the stages read nothing the identity estimate sets.  params->scaffold_out is honoured.
+ * Summary: queries = seed groups, targets = target sequences, l2_mappings = seeds read, written = records written; ms_map = reading
+ * the seeds, ms_filter = filters and output, ms_total = ms_wall = the whole call.  Returns 0 or WFM_E_* (message on stderr). */
+int wfmh_seed_paf(const char* target_fasta, const char* query_fasta, const char* seeds_paf, const char* out_paf,
+                  const wfmh_map_params_t* params, wfmh_map_summary_t* summary);
 
 /* Test hook for the host-side post-processing of one query's mappings (CPU tests): runs
  * mappingBoundarySanityCheck + Map::filterSubsetMappings + reportReadMappings

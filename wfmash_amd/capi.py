@@ -624,7 +624,7 @@ class Handle:
 HOST_EXPORTS = ["wfmh_test_packed_lce", "wfmh_test_is_acgt", "wfmh_align_default_params", "wfmh_align_paf", "wfmh_test_cigar", "wfmh_free", "wfmh_test_winnow",
                 "wfmh_map_default_params", "wfmh_test_filter", "wfmh_map", "wfmh_test_winnow_chunked", "wfmh_test_fasta", "wfmh_test_winnow_thinned", "wfmh_test_sort_records", "wfmh_test_index_file",
                 "wfmh_map_multi", "wfmh_align_paf_multi", "wfmh_test_winnow_model", "wfmh_test_sortlike_model", "wfmh_test_finish_records",
-                "wfmh_release_sequences", "wfmh_test_fasta_shared"]
+                "wfmh_release_sequences", "wfmh_test_fasta_shared", "wfmh_seed_paf"]
 
 
 class MapSummary(C.Structure):
@@ -649,6 +649,19 @@ def map_paf_multi(handles, target_fasta: str, out_paf: str, query_fasta: str = N
                           out_paf.encode(), C.byref(params) if params is not None else None, C.byref(s))
     if rc != 0:
         raise WfmError(f"wfmh_map_multi failed ({rc}): {handles[0].last_error()}")
+    return s
+
+
+def seed_paf(target_fasta: str, seeds_paf: str, out_paf: str, query_fasta: str = None, params=None) -> "MapSummary":
+    """wfmh_seed_paf: external seeds (-K) through the group sweep and the scaffold filter into a mapping PAF (host only, no GPU)."""
+    L = load()
+    L.wfmh_seed_paf.restype = C.c_int
+    L.wfmh_seed_paf.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_void_p, C.POINTER(MapSummary)]
+    s = MapSummary()
+    rc = L.wfmh_seed_paf(target_fasta.encode(), query_fasta.encode() if query_fasta else None, seeds_paf.encode(), out_paf.encode(),
+                         C.byref(params) if params is not None else None, C.byref(s))
+    if rc != 0:
+        raise WfmError(f"wfmh_seed_paf failed ({rc})")
     return s
 
 
@@ -705,7 +718,8 @@ class MapHostParams(C.Structure):
                 ("ani_diff_conf", C.c_float), ("hg_numerator", C.c_double), ("threads", C.c_int32),
                 ("auto_pct_identity", C.c_int32), ("ani_percentile", C.c_int32), ("ani_adjustment", C.c_float),
                 ("target_prefix", C.c_char_p), ("target_list", C.c_char_p), ("query_prefix", C.c_char_p), ("query_list", C.c_char_p),
-                ("index_file", C.c_char_p), ("write_index", C.c_int32), ("pad_", C.c_int32)]
+                ("index_file", C.c_char_p), ("write_index", C.c_int32), ("pad_", C.c_int32),
+                ("scaffold_out", C.c_char_p)]
 
 
 def map_default_params(**over) -> MapHostParams:

@@ -95,6 +95,7 @@ void Aligner::parseMashmapRow(const std::string& line, MappingBoundaryRow& row, 
   const auto idv = split(tokens[12], ':');
   const float mm_id = (!idv.empty() && is_a_number(idv.back())) ? std::stof(idv.back()) : 0.70f;  // fixed::percentage_identity
   int64_t chain_id = -1, chain_length = 1, chain_pos = 1;
+  // only tokens 12 and 14 are read (computeAlignments.hpp:203-230): the cg:Z / st:Z tags an -K record carries after ch:Z are passed over
   if (tokens.size() > 14) {
     const auto cv = split(tokens[14], ':');
     if (cv.size() == 3 && cv[0] == "ch" && cv[1] == "Z") {

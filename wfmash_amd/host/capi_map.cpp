@@ -2,6 +2,7 @@
 #include <chrono>
 #include <cstdlib>
 #include <fstream>
+#include <iostream>
 #include <cstdio>
 #include <cstring>
 #include <limits>
@@ -12,6 +13,7 @@
 #include "../csrc/wfa_handle.h"
 #include "ani_estimate.hpp"
 #include "capi_map.hpp"
+#include "external_seeds.hpp"
 #include "fasta.hpp"
 #include "index_file.hpp"
 #include "map_filter.hpp"
@@ -64,6 +66,7 @@ skch::Parameters to_parameters(const wfmh_map_params_t& c) {
   if (c.target_list) p.target_list = c.target_list;
   if (c.query_list) p.query_list = c.query_list;
   if (c.index_file) { p.indexFilename = c.index_file; p.create_index_only = c.write_index != 0; }
+  if (c.scaffold_out) p.scaffold_output_file = c.scaffold_out;
   if (c.query_prefix) {  // CommonFunc::split(args::get(query_prefix), ',') (parse_args.hpp:204)
     std::stringstream ss(c.query_prefix);
     for (std::string tok; std::getline(ss, tok, ',');) p.query_prefix.push_back(tok);
@@ -188,6 +191,59 @@ int wfmh_map_multi(wfm_handle_t* const* handles, int n, const char* target_fasta
     return rc;
   } catch (const std::exception& e) {
     wfm_set_error(h, e.what());
+    return WFM_E_ARG;
+  }
+}
+
+int wfmh_seed_paf(const char* target_fasta, const char* query_fasta, const char* seeds_paf, const char* out_paf, const wfmh_map_params_t* params,
+                  wfmh_map_summary_t* summary) {
+  if (!target_fasta || !seeds_paf || !out_paf) return WFM_E_ARG;
+  const auto t_call = std::chrono::steady_clock::now();
+  try {
+    wfmh_map_params_t def;
+    wfmh_map_default_params(&def);
+    skch::Parameters p = wfmash_host::to_parameters(params ? *params : def);
+    p.refSequences = {std::string(target_fasta)};
+    p.querySequences = {std::string(query_fasta ? query_fasta : target_fasta)};
+    p.outFileName = out_paf;
+    // the id manager the reference's -K branch makes (main.cpp:172-188): names and lengths only, no index
+    std::vector<std::string> target_prefix_vec;
+    if (!p.target_prefix.empty()) target_prefix_vec.push_back(p.target_prefix);
+    const skch::SequenceIdManager ids(p.querySequences, p.refSequences, p.query_prefix, target_prefix_vec, std::string(1, p.prefix_delim),
+                                      p.query_list, p.target_list);
+    const bool to_stdout = p.outFileName == "/dev/stdout" || p.outFileName == "-";
+    std::ofstream file;
+    if (!to_stdout) {
+      file.open(p.outFileName);
+      if (!file.is_open()) throw std::runtime_error("Could not open output file: " + p.outFileName);
+    }
+    std::ofstream scaffolds;
+    if (!p.scaffold_output_file.empty()) {
+      scaffolds.open(p.scaffold_output_file);
+      if (!scaffolds.is_open()) throw std::runtime_error("cannot open scaffold output file " + p.scaffold_output_file);
+    }
+    skch::SeedSummary s;
+    skch::processExternalSeeds(p, seeds_paf, ids, to_stdout ? static_cast<std::ostream&>(std::cout) : file,
+                               scaffolds.is_open() ? &scaffolds : nullptr, &s);
+    if ((!to_stdout && !file) || (scaffolds.is_open() && !scaffolds)) throw std::runtime_error("writing the output failed");
+    if (summary) {
+      std::memset(summary, 0, sizeof(*summary));
+      summary->targets = ids.getTargetSequenceNames().size();
+      summary->queries = s.queries;
+      summary->l2_mappings = s.seeds;
+      summary->written = s.written;
+      summary->percentage_identity = p.percentageIdentity;
+      summary->sketch_size = p.sketchSize;
+      summary->ms_map = s.ms_read;
+      summary->ms_filter = s.ms_filter;
+      summary->ms_total = summary->ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+    }
+    return WFM_OK;
+  } catch (const std::bad_alloc&) {
+    fprintf(stderr, "[wfmash::externalSeeder] ERROR: out of host memory\n");
+    return WFM_E_NOMEM;
+  } catch (const std::exception& e) {
+    fprintf(stderr, "[wfmash::externalSeeder] ERROR: %s\n", e.what());
     return WFM_E_ARG;
   }
 }

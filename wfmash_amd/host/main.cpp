@@ -7,11 +7,16 @@
 //
 //   wfmash-hip -W idx target.fa                build the target index, write it and stop (parse_args.hpp:745-751)
 //   wfmash-hip -I idx target.fa [query.fa]     read the index instead of building it (:752-758)
+//   wfmash-hip -K seeds.paf target.fa [query.fa]     external PAF seeds through the group sweep and the scaffold filter
+//                                              in place of the MinHash mapper, then aligned (:78, :771-773); with -m the
+//                                              filtered seeds are written (host only, no GPU is opened)
+//   --scaffold-out FILE                        the scaffold chains the scaffold filter used as anchors (:105, :464-465),
+//                                              of the map path or of -K
 //
 // Differences: output goes to stdout or --out FILE; --device picks the GPU, --gpus N spreads the
-// queries (map) and the mapping records (align) over N GPUs of the node.  Options of the reference
-// that belong to subsystems outside this build (external seeds -K, wavefront plots -G/-u, scaffold
-// dump --scaffold-out) are not accepted.
+// queries (map) and the mapping records (align) over N GPUs of the node.  -K together with -i, -W or
+// -I is refused (the reference ignores the index flags there).  Options of the reference that belong
+// to subsystems outside this build (wavefront plots -G/-u) are not accepted.
 #include <unistd.h>
 
 #include <cstdio>
@@ -46,7 +51,9 @@ static void usage() {
           "            -N no split   -M no merge   -f no filter   -o one-to-one   -O FLOAT max overlap [0.95]   -x FLOAT sparsify [1.0]\n"
           "            -H INT L1 hits [3]   -F FLOAT high-frequency filter [0.0002]   -b SIZE target batch [all]\n"
           "            -W FILE build the index, write it and stop   -I FILE read the index from FILE\n"
+          "            -K FILE external PAF seeds in place of the mapper ('-' = stdin)\n"
           "            -S INT scaffold mass [10k]   -D INT scaffold dist [100k]   -j INT scaffold jump [100k]   -r INT per scaffold [1]\n"
+          "            --scaffold-out FILE write the scaffold chains\n"
           "            -Y C group delimiter [#]   -X self maps   -L lower triangular   -t INT threads [1]\n"
           "  alignment -g x,o1,e1,o2,e2 [5,8,2,24,1]   -E INT target padding   -U INT query padding   -a SAM   -d MD tag\n"
           "  other     --out FILE [stdout]   --device INT [0]   --gpus N|all [1] GPUs of this node, starting at --device\n");
@@ -58,7 +65,7 @@ int main(int argc, char** argv) {
   ap.threads = 1;  // -t, default 1 as in the reference (parse_args.hpp: thread_count); the C ABI default (0) means all cores
   wfmh_map_params_t mp;
   wfmh_map_default_params(&mp);
-  std::string mapping_in, out = "/dev/stdout", target, query;
+  std::string mapping_in, out = "/dev/stdout", target, query, seeds_in, scaffold_out;
   bool approx_only = false, target_padding_given = false, query_padding_given = false;
   int device = 0, gpus = 1;
   for (int i = 1; i < argc; ++i) {
@@ -74,6 +81,8 @@ int main(int argc, char** argv) {
     };
     if (a == "-m" || a == "--approx-mapping") approx_only = true;
     else if (a == "-i" || a == "--align-paf") mapping_in = next("-i");
+    else if (a == "-K" || a == "--input-seeds") seeds_in = next("-K");
+    else if (a == "--scaffold-out") { scaffold_out = next("--scaffold-out"); mp.scaffold_out = scaffold_out.c_str(); }
     else if (a == "--out") out = next("--out");
     else if (a == "--device") device = atoi(next("--device").c_str());
     else if (a == "--gpus") { const std::string v = next("--gpus"); gpus = v == "all" ? 0 : atoi(v.c_str()); if (gpus < 0) gpus = 1; }
@@ -175,6 +184,8 @@ int main(int argc, char** argv) {
   }
   if (target.empty()) { fprintf(stderr, "[wfmash] ERROR: need a target FASTA\n"); usage(); return 1; }
   if (approx_only && !mapping_in.empty()) { fprintf(stderr, "[wfmash] ERROR: -m and -i exclude each other\n"); return 1; }
+  if (!seeds_in.empty() && !mapping_in.empty()) { fprintf(stderr, "[wfmash] ERROR: -K (external seeds) and -i (align mappings from a file) exclude each other\n"); return 1; }
+  if (!seeds_in.empty() && mp.index_file) { fprintf(stderr, "[wfmash] ERROR: -K (external seeds) does not read or write an index (-W / -I)\n"); return 1; }
   if (!mapping_in.empty() && mp.index_file) { fprintf(stderr, "[wfmash] ERROR: -i (align only) does not read or write an index (-W / -I)\n"); return 1; }
   if (!approx_only && !(mp.index_file && mp.write_index) && mp.window_length > 10000) {  // parse_args.hpp:330-335
     fprintf(stderr, "[wfmash] ERROR: window size (-w) must be <= 10kb when running alignment.\n"
@@ -195,6 +206,16 @@ int main(int argc, char** argv) {
   if (!target_padding_given) ap.target_padding = (uint64_t)std::min<int64_t>(mp.window_length, 5000);
   if (!query_padding_given) ap.query_padding = (uint64_t)std::min<int64_t>(mp.window_length, 5000);
   ap.wflign_max_len_minor = (uint64_t)mp.window_length * 128;
+  const char* q = query.empty() ? nullptr : query.c_str();
+  auto seed = [&](const std::string& to) {  // -K: the seeds through the filters into `to` (host only)
+    wfmh_map_summary_t ms;
+    const int rc = wfmh_seed_paf(target.c_str(), q, seeds_in.c_str(), to.c_str(), &mp, &ms);
+    if (rc == WFM_OK)
+      fprintf(stderr, "[wfmash::seeds] %llu seeds of %llu queries -> %llu records; reading %.0f ms, filtering %.0f ms, total %.0f ms\n",
+              (unsigned long long)ms.l2_mappings, (unsigned long long)ms.queries, (unsigned long long)ms.written, ms.ms_map, ms.ms_filter, ms.ms_total);
+    return rc;
+  };
+  if (!seeds_in.empty() && approx_only) return seed(out) == WFM_OK ? 0 : 3;
   // one handle per GPU; every phase hands its batches to whichever device is free
   if (gpus == 0) { gpus = wfm_device_count() - device; if (gpus < 1) gpus = 1; }
   std::vector<wfm_handle_t*> hs;
@@ -209,7 +230,6 @@ int main(int argc, char** argv) {
   }
   wfm_handle_t* h = hs.front();
   auto destroy_all = [&] { for (wfm_handle_t* o : hs) wfm_destroy(o); };
-  const char* q = query.empty() ? nullptr : query.c_str();
   int rc = WFM_OK;
   std::string mapping = mapping_in;
   std::string temp;
@@ -223,6 +243,10 @@ int main(int argc, char** argv) {
       temp = tmpl;
       mapping = temp;
     }
+  }
+  if (!seeds_in.empty()) {
+    rc = seed(mapping);  // then aligned exactly as the mapper's hand-off file is
+  } else if (mapping_in.empty()) {
     wfmh_map_summary_t ms;
     rc = wfmh_map_multi(hs.data(), (int)hs.size(), target.c_str(), q, mapping.c_str(), &mp, &ms);
     if (rc == WFM_OK)

@@ -746,7 +746,8 @@ class AnchorIndex {
 
 }  // namespace
 
-void MappingFilterUtils::filterByScaffolds(MappingResultsVector_t& readMappings, const Parameters& param, const SequenceIdManager& idManager) {
+void MappingFilterUtils::filterByScaffolds(MappingResultsVector_t& readMappings, const Parameters& param, const SequenceIdManager& idManager,
+                                           MappingResultsVector_t* chains_out) {
   if (param.scaffold_gap <= 0) return;
   // scaffolds: chains formed with the (much larger) scaffold gap, long enough, and surviving a
   // plane sweep of their own
@@ -810,6 +811,7 @@ void MappingFilterUtils::filterByScaffolds(MappingResultsVector_t& readMappings,
   const double ts2 = tnow();
   if (readMappings.empty()) return;
   if (anchors.empty()) { readMappings.clear(); return; }
+  if (chains_out) *chains_out = scaffolds;  // what the reference writes to --scaffold-out, at the point it writes it
   const AnchorIndex index(anchors);
   const float max_dist = static_cast<float>(param.scaffold_max_deviation);
   MappingResultsVector_t keepers;
@@ -839,6 +841,7 @@ FilteredMappingsResult filterSubsetMappings(MappingResultsVector_t& mappings, co
   static const bool tdbg = getenv("WFM_FILTER_TIMES") != nullptr;
   auto tnow = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   const size_t n_in = mappings.size();
+  MappingResultsVector_t* const scaffolds_out = param.scaffold_output_file.empty() ? nullptr : &result.scaffoldChains;
   double tt[8] = {0}; int ti = 0; tt[ti++] = tnow();
   MappingsWithChains chained = MappingFilterUtils::mergeMappingsInRangeWithChains(mappings, (int)param.chain_gap, param);
   tt[ti++] = tnow();
@@ -855,7 +858,7 @@ FilteredMappingsResult filterSubsetMappings(MappingResultsVector_t& mappings, co
     tt[ti++] = tnow();
     if (param.filterLengthMismatches) MappingFilterUtils::filterFalseHighIdentity(merged, param);
     MappingFilterUtils::sparsifyMappings(merged, param);
-    MappingFilterUtils::filterByScaffolds(merged, param, idManager);
+    MappingFilterUtils::filterByScaffolds(merged, param, idManager, scaffolds_out);
     tt[ti++] = tnow();
     if (tdbg && n_in >= 100000)
       fprintf(stderr, "[filter] filterSubsetMappings n=%zu: chains + merge %.1f, weak %.1f, sweep %.1f, scaffolds %.1f ms\n", n_in, tt[1] - tt[0], tt[2] - tt[1], tt[3] - tt[2], tt[4] - tt[3]);
@@ -865,7 +868,7 @@ FilteredMappingsResult filterSubsetMappings(MappingResultsVector_t& mappings, co
       MappingFilterUtils::filterByGroup(mappings, kept, param.numMappingsForSegment - 1, false, idManager, param);
       mappings = std::move(kept);
     }
-    MappingFilterUtils::filterByScaffolds(mappings, param, idManager);
+    MappingFilterUtils::filterByScaffolds(mappings, param, idManager, scaffolds_out);
   }
   result.nonMergedMappings = std::move(mappings);
   result.mergedMappings = std::move(merged);
@@ -908,6 +911,19 @@ inline void put_int(std::string& s, long long v) { char b[24]; const int k = snp
 inline void put_uint(std::string& s, unsigned long long v) { char b[24]; const int k = snprintf(b, sizeof b, "%llu", v); s.append(b, (size_t)k); }
 inline void put_real(std::string& s, double v) { char b[48]; const int k = snprintf(b, sizeof b, "%g", v); s.append(b, (size_t)k); }
 }  // namespace
+
+std::string MappingOutput::scaffoldText(const MappingResultsVector_t& chains, const std::string& queryName, offset_t queryLen,
+                                        const SequenceIdManager& idManager) {
+  std::string o;
+  for (const MappingResult& c : chains) {
+    o += queryName; o += '\t'; put_int(o, (long long)queryLen); o += '\t'; put_uint(o, c.queryStartPos); o += '\t'; put_int(o, (long long)c.queryEndPos());
+    o += '\t'; o += (c.strand() == strnd::FWD ? "+" : "-"); o += '\t'; o += idManager.getSequenceName(c.refSeqId);
+    o += '\t'; put_int(o, (long long)idManager.getSequenceLength(c.refSeqId)); o += '\t'; put_uint(o, c.refStartPos); o += '\t'; put_int(o, (long long)c.refEndPos());
+    o += '\t'; put_uint(o, c.conservedSketches); o += '\t'; put_uint(o, c.blockLength); o += "\t60\ttp:A:S\tid:f:"; put_real(o, (double)c.getNucIdentity());
+    o += "\tkc:f:"; put_real(o, (double)c.getKmerComplexity()); o += '\n';
+  }
+  return o;
+}
 
 void MappingOutput::reportReadMappings(MappingResultsVector_t& readMappings, const ChainInfoVector_t& chainInfo, const std::string& queryName,
                                        std::ostream& outstrm, const SequenceIdManager& idManager, const Parameters& param, offset_t queryLen) {

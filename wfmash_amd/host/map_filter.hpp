@@ -40,12 +40,16 @@ class MappingFilterUtils {
                             bool filter_ref, const SequenceIdManager& idManager, const Parameters& param);
   static MappingsWithChains mergeMappingsInRangeWithChains(MappingResultsVector_t& readMappings, int max_dist, const Parameters& param);
   static MappingResultsVector_t mergeMappingsInRange(MappingResultsVector_t& readMappings, int max_dist, const Parameters& param);
-  static void filterByScaffolds(MappingResultsVector_t& readMappings, const Parameters& param, const SequenceIdManager& idManager);
+  // chains_out (optional): receives the scaffold chains the reference writes to --scaffold-out (mappingFilter.hpp:911-945) --
+  // the chains after the length cut and their own sweep, and only when anchors were found
+  static void filterByScaffolds(MappingResultsVector_t& readMappings, const Parameters& param, const SequenceIdManager& idManager,
+                                MappingResultsVector_t* chains_out = nullptr);
 };
 
 struct FilteredMappingsResult {
   MappingResultsVector_t nonMergedMappings, mergedMappings;
   ChainInfoVector_t nonMergedChainInfo, mergedChainInfo;
+  MappingResultsVector_t scaffoldChains;  // filled only when param.scaffold_output_file is set
 };
 // host threads the CALLING thread may use inside filterSubsetMappings (default 1): a batch with a single long query
 void set_filter_threads(int threads);
@@ -65,6 +69,9 @@ class MappingOutput {
                                  std::ostream& outstrm, const SequenceIdManager& idManager, const Parameters& param, offset_t queryLen);
   static void reportReadMappings(MappingResultsVector_t& readMappings, const std::string& queryName, std::ostream& outstrm,
                                  const SequenceIdManager& idManager, const Parameters& param, offset_t queryLen);
+  // the --scaffold-out lines of one query's scaffold chains (mappingFilter.hpp:925-941)
+  static std::string scaffoldText(const MappingResultsVector_t& chains, const std::string& queryName, offset_t queryLen,
+                                  const SequenceIdManager& idManager);
 };
 
 }  // namespace skch

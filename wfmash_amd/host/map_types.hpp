@@ -128,6 +128,7 @@ struct Parameters {
   std::string target_list, target_prefix, query_list;
   std::vector<std::string> query_prefix;
   std::string outFileName = "/dev/stdout";
+  std::string scaffold_output_file;        // --scaffold-out (:105, :464-465); empty = no scaffold chains are kept or written
 };
 
 }  // namespace skch

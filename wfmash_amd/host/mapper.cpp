@@ -206,6 +206,14 @@ int Map::mapQuery(MapSummary* summary) {
     if (!file.is_open()) { wfm_set_error(h_, "cannot open output file " + P.outFileName); return WFM_E_ARG; }
   }
   std::ostream& out = to_stdout ? static_cast<std::ostream&>(std::cout) : file;
+  // --scaffold-out: one file for the run, every query and every target subset; queries are post-processed on several threads, each
+  // query's lines are written at once under the lock (the reference writes from its worker threads as well: the line order is not fixed)
+  std::ofstream scaffold_file;
+  std::mutex scaffold_mu;
+  if (!P.scaffold_output_file.empty()) {
+    scaffold_file.open(P.scaffold_output_file);
+    if (!scaffold_file.is_open()) { wfm_set_error(h_, "cannot open scaffold output file " + P.scaffold_output_file); return WFM_E_ARG; }
+  }
   std::map<seqno_t, MappingResultsVector_t> combined;  // one-to-one mode: everything is held back
 
   std::ifstream index_in;   // -I: the sub-indexes are read in file order, one per subset
@@ -577,6 +585,11 @@ int Map::mapQuery(MapSummary* summary) {
             if (!orig.empty()) set_presorted_order(orig.data(), orig.size());
             FilteredMappingsResult fr = filterSubsetMappings(results, P, ids, q.len);
             const double tq3 = now_ms();
+            if (!fr.scaffoldChains.empty()) {
+              const std::string st = MappingOutput::scaffoldText(fr.scaffoldChains, q.name, q.len, ids);
+              std::lock_guard<std::mutex> lk(scaffold_mu);
+              scaffold_file << st;
+            }
             const bool merged = P.mergeMappings && P.split;
             MappingResultsVector_t& keep = merged ? fr.mergedMappings : fr.nonMergedMappings;
             const ChainInfoVector_t& chains = merged ? fr.mergedChainInfo : fr.nonMergedChainInfo;
@@ -674,6 +687,7 @@ int Map::mapQuery(MapSummary* summary) {
     out.flush();
     sum.ms_filter += now_ms() - t0;
   }
+  if (scaffold_file.is_open() && !scaffold_file.flush()) { wfm_set_error(h_, "cannot write scaffold output file " + P.scaffold_output_file); return WFM_E_ARG; }
   sum.ms_total = now_ms() - t_begin;
   if (summary) *summary = sum;
   return WFM_OK;
