@@ -448,6 +448,21 @@ int64_t wfm_map_fragments_ordered(wfm_handle_t* h, const wfm_index_t* ix, const 
                                   const wfm_map_params_t* prm, wfm_mapping_t* out, int32_t* out_frag, int64_t cap,
                                   const int32_t* frag_first, uint32_t* out_perm);
 
+/* --streaming-minhash (CommonFunc::sketchSequenceStreaming, commonFunc.hpp:338-430, as Sketch::buildHelper calls it for every
+ * target sequence, winSketch.hpp:467-497): the target sketch taken from a per-sequence bottom-s MinHash instead of winnowed
+ * minmers.  Of sequence i, the min(s, k-mers) smallest canonical hashes, duplicates included, of the k-mers free of non-ACGT bases
+ * whose two strands hash differently; each becomes one record {hash, wpos = the first position of that hash among those k-mers,
+ * wpos_end = wpos + w, seq_ids[i] (NULL: i), strand +1}, and a sequence's records are ordered by wpos.  Hashing and selection run
+ * on the device.  out receives the records grouped by sequence in input order, counts[i] (optional) the number of sequence i.
+ * Returns the total (may exceed cap; only cap are written) or a WFM_E_* code. */
+int64_t wfm_streaming_minmers(wfm_handle_t* h, const char* const* seqs, const int64_t* lens, const int32_t* seq_ids, int64_t nseq,
+                              int k, int w, int s, wfm_minmer_t* out, int64_t cap, int64_t* counts);
+
+/* Sketch::build with --streaming-minhash: wfm_streaming_minmers followed by the index stage (wfm_index_build), the records going to the
+ * device directly.  *n_windows (optional) receives the number of records; when it is 0 no index is made and *out stays NULL. */
+int wfm_index_build_streaming(wfm_handle_t* h, const char* const* seqs, const int64_t* lens, const int32_t* seq_ids, int64_t nseq,
+                              int k, int w, int s, double max_kmer_freq, wfm_index_t** out, int64_t* n_windows);
+
 #ifdef __cplusplus
 }
 #endif

@@ -184,6 +184,8 @@ typedef struct {
   /* appended: nothing above moves */
   const char* scaffold_out;           /* --scaffold-out FILE: the scaffold chains the filter used as anchors (parse_args.hpp:105,464-465);
                                          NULL = none, and nothing of them is kept */
+  int32_t  streaming_minhash;         /* --streaming-minhash (parse_args.hpp:137,177): 1 = target sketches from a per-sequence bottom-s
+                                         MinHash (wfm_streaming_minmers) instead of winnowed minmers; 0 (default) = winnowing */
 } wfmh_map_params_t;
 
 void wfmh_map_default_params(wfmh_map_params_t* p);

@@ -30,6 +30,7 @@ EXPORTS = [
     "wfm_prefilter_kmers", "wfm_index_build_sequences", "wfm_index_upload",
     "wfm_index_replicate", "wfm_device_count", "wfm_finish_records",
     "wfm_align_batch_rle", "wfm_align_resident_rle", "wfm_free_runs", "wfm_score_bounds", "wfm_get_busy_intervals", "wfm_trim_device_cache", "wfm_map_fragments_ordered", "wfm_map_sequence_cache", "wfm_selftest_dpp", "wfm_selftest_arena_growth", "wfm_set_concurrent_calls", "wfm_get_problem_flags",
+    "wfm_streaming_minmers", "wfm_index_build_streaming",
 ]
 
 
@@ -719,7 +720,29 @@ class MapHostParams(C.Structure):
                 ("auto_pct_identity", C.c_int32), ("ani_percentile", C.c_int32), ("ani_adjustment", C.c_float),
                 ("target_prefix", C.c_char_p), ("target_list", C.c_char_p), ("query_prefix", C.c_char_p), ("query_list", C.c_char_p),
                 ("index_file", C.c_char_p), ("write_index", C.c_int32), ("pad_", C.c_int32),
-                ("scaffold_out", C.c_char_p)]
+                ("scaffold_out", C.c_char_p), ("streaming_minhash", C.c_int32)]
+
+
+def streaming_minmers(handle, seqs, k: int, w: int, s: int, seq_ids=None):
+    """wfm_streaming_minmers: the --streaming-minhash target records (sketchSequenceStreaming) of several sequences, grouped by
+    sequence in input order, each group ordered by wpos; one MINMER_DTYPE array."""
+    L = load()
+    n = len(seqs)
+    ids = np.ascontiguousarray(seq_ids if seq_ids is not None else range(n), dtype=np.int32)
+    bufs = [np.frombuffer(x, dtype=np.uint8) for x in seqs]
+    ptrs = (C.c_void_p * max(n, 1))(*[b.ctypes.data for b in bufs])
+    lens = np.array([len(x) for x in seqs], dtype=np.int64)
+    counts = np.zeros(max(n, 1), dtype=np.int64)
+    f = L.wfm_streaming_minmers
+    f.restype = C.c_int64
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
+    cap = n * s + 1
+    out = np.zeros(cap, dtype=MINMER_DTYPE)
+    tot = f(handle._p, ptrs, lens.ctypes.data, ids.ctypes.data, n, k, w, s, out.ctypes.data, cap, counts.ctypes.data)
+    if tot < 0:
+        raise WfmError(f"wfm_streaming_minmers failed ({tot}): {handle.last_error()}")
+    assert tot <= cap, (tot, cap)
+    return out[:tot]
 
 
 def map_default_params(**over) -> MapHostParams:

@@ -45,6 +45,9 @@ int map_l2_device(wfm_handle_t* h, MapScratch& sc, const wfm_index_t* ix, const 
 // The index stage on minmer intervals that are already on the device (map_index.hip); d_minmers stays the caller's.
 int map_index_build_device(wfm_handle_t* h, const wfm_minmer_t* d_minmers, int64_t n, double max_kmer_freq, wfm_index_t** out);
 
+// --streaming-minhash: the records sketchSequenceStreaming makes of one target sequence (map_kernels.hip), ordered by wpos
+int map_streaming_sketch(wfm_handle_t* h, const char* seq, int64_t len, int k, int w, int s, int32_t seq_id, std::vector<wfm_minmer_t>& out);
+
 // One sequence normalised and hashed on the device, left there so that host threads can pull the
 // slices they work on in parallel (each through its own per-thread stream).
 struct MapHashedSeq {

@@ -243,6 +243,47 @@ static void launch_kmer_hash(const uint8_t* d_norm, int64_t nk, int k, uint64_t*
   }
 }
 
+// --streaming-minhash (map_streaming_sketch): kmer_hash_select_kernel with the k-mer's position carried beside its hash.  Every k-mer
+// that holds an N or is palindromic hashes to ~0 and is never at most tau (tau < 2^60 here), which is exactly the reference's skip rule.
+template <int K>
+__global__ void __launch_bounds__(256) kmer_hash_select_pos_kernel(const uint8_t* __restrict__ seq /*normalised, padded*/, int64_t nk, uint64_t tau,
+                                                                   uint64_t* __restrict__ out_hash, uint32_t* __restrict__ out_pos,
+                                                                   unsigned long long* __restrict__ count, unsigned long long cap) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nk; i += (int64_t)gridDim.x * blockDim.x) {
+    uint64_t h; int8_t st;
+    kmer_hash_2w<K>(seq + i, h, st);
+    if (h <= tau) {
+      const unsigned long long at = atomicAdd(count, 1ull);
+      if (at < cap) { out_hash[at] = h; out_pos[at] = (uint32_t)i; }
+    }
+  }
+}
+// false: no fused form for this k
+static bool launch_kmer_hash_select_pos(const uint8_t* d_norm, int64_t nk, int k, uint64_t tau, uint64_t* d_hash, uint32_t* d_pos,
+                                        unsigned long long* d_count, unsigned long long cap, hipStream_t st) {
+  const int blocks = (int)std::min<int64_t>((nk + 255) / 256, 256 * 64);
+  switch (k) {
+#define WFM_K2P(K) case K: hipLaunchKernelGGL(kmer_hash_select_pos_kernel<K>, dim3(blocks), dim3(256), 0, st, d_norm, nk, tau, d_hash, d_pos, d_count, cap); return true;
+    WFM_K2P(15) WFM_K2P(16) WFM_K2P(17) WFM_K2P(19) WFM_K2P(21)
+#undef WFM_K2P
+    default: return false;
+  }
+}
+// the same selection on the hash array of the two-pass form
+__global__ void __launch_bounds__(256) select_below_pos_kernel(const uint64_t* __restrict__ hash, int64_t nk, uint64_t tau, uint64_t* __restrict__ out_hash,
+                                                               uint32_t* __restrict__ out_pos, unsigned long long* __restrict__ count, unsigned long long cap) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nk; i += (int64_t)gridDim.x * blockDim.x) {
+    const uint64_t h = hash[i];
+    if (h <= tau) {
+      const unsigned long long at = atomicAdd(count, 1ull);
+      if (at < cap) { out_hash[at] = h; out_pos[at] = (uint32_t)i; }
+    }
+  }
+}
+__global__ void __launch_bounds__(256) iota_pos_kernel(uint32_t* __restrict__ pos, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) pos[i] = (uint32_t)i;
+}
+
 // One workgroup per fragment.  LDS: key[npow2] (u64) + pv[npow2] (u32: pos<<1 | isRev).
 __global__ __launch_bounds__(256) void sketch_fragments_kernel(const uint8_t* __restrict__ seq, const int64_t* __restrict__ frag_off,
                                                                const int32_t* __restrict__ frag_len, int k, int s, int32_t seq_id,
@@ -940,3 +981,110 @@ int wfm_sketch_fragments(wfm_handle_t* h, const char* seq, int64_t seq_len, cons
 }
 
 }  // extern "C"
+
+namespace {
+template <typename K, typename V>
+hipError_t sort_pairs(Scoped& sc, K* kin, K* kout, V* vin, V* vout, size_t n, unsigned bits, hipStream_t st) {
+  size_t tmp = 0;
+  hipError_t e = rocprim::radix_sort_pairs(nullptr, tmp, kin, kout, vin, vout, n, 0, bits, st);
+  if (e != hipSuccess) return e;
+  char* d_tmp = nullptr;
+  if ((e = sc.alloc(&d_tmp, tmp)) != hipSuccess) return e;
+  return rocprim::radix_sort_pairs(d_tmp, tmp, kin, kout, vin, vout, n, 0, bits, st);
+}
+}  // namespace
+
+// sketchSequenceStreaming (commonFunc.hpp:338-430) of one sequence, the target sketch of --streaming-minhash.  The sketch is what
+// StreamingMinHash keeps: the n = min(s, k-mers) smallest canonical hashes, with multiplicity, of the k-mers free of N whose two
+// strands hash differently.  Each entry becomes one record at the first position its hash has among those k-mers.
+//   fused form: hashing and the selection of the (hash, position) pairs at most tau in one pass (tau as wfm_minhash_sketch sets it);
+//   two-pass form: every k-mer hashed first, then the same selection, or -- for short sequences, or when fewer than n or more than
+//   64 n turn up under tau -- every pair sorted.
+// The selected pairs are put in position order and then stably in hash order, so every run of one hash begins with its first
+// position.  A run that crosses the cut at n begins before it: the first position of every hash of the sketch is among the n.
+int map_streaming_sketch(wfm_handle_t* h, const char* seq, int64_t len, int k, int w, int s, int32_t seq_id, std::vector<wfm_minmer_t>& out) {
+  out.clear();
+  if (!h || len < 0 || (len > 0 && !seq) || s < 1) return WFM_E_ARG;
+  if (k < 1 || k > 32) { wfm_set_error(h, "k must be in 1..32"); return WFM_E_UNSUPPORTED; }
+  const int64_t nk = len - k + 1;
+  if (nk <= 0) return WFM_OK;
+  if (nk > (int64_t)UINT32_MAX) { wfm_set_error(h, "streaming MinHash: a sequence of more than 2^32 k-mers"); return WFM_E_UNSUPPORTED; }
+  HIPCHK(h, hipSetDevice(wfm_device(h)));
+  Scoped sc;
+  uint8_t* d_norm = nullptr;
+  int rc = upload_normalised(h, sc, seq, len, &d_norm);
+  if (rc != WFM_OK) return rc;
+  hipStream_t st = wfm_stream(h);
+  const int64_t n = std::min<int64_t>(s, nk);
+  const bool thresholded = nk > ((int64_t)1 << 20) && n * 64 < nk;
+  const uint64_t tau = thresholded ? (uint64_t)(4.0L * (long double)n / (long double)nk * 18446744073709551616.0L) : 0;
+  const unsigned long long cap = (unsigned long long)n * 64;
+  uint64_t* d_ch = nullptr; uint32_t* d_cp = nullptr; unsigned long long* d_count = nullptr;
+  unsigned long long m = 0;
+  bool selected = false;  // d_ch / d_cp hold m pairs, every pair at most tau, at least n of them
+  auto count_selected = [&]() -> int {
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(&m, d_count, sizeof(m), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    selected = (int64_t)m >= n && m <= cap;
+    return WFM_OK;
+  };
+  if (thresholded) {
+    HIPCHK(h, sc.alloc(&d_ch, (size_t)cap * 8));
+    HIPCHK(h, sc.alloc(&d_cp, (size_t)cap * 4));
+    HIPCHK(h, sc.alloc(&d_count, sizeof(unsigned long long)));
+    HIPCHK(h, hipMemsetAsync(d_count, 0, sizeof(unsigned long long), st));
+    if (launch_kmer_hash_select_pos(d_norm, nk, k, tau, d_ch, d_cp, d_count, cap, st) && (rc = count_selected()) != WFM_OK) return rc;
+  }
+  uint64_t* d_hash = nullptr;
+  if (!selected) {
+    int8_t* d_st = nullptr;
+    HIPCHK(h, sc.alloc(&d_hash, (size_t)nk * 8));
+    HIPCHK(h, sc.alloc(&d_st, (size_t)nk));
+    launch_kmer_hash(d_norm, nk, k, d_hash, d_st, st);
+    HIPCHK(h, hipGetLastError());
+    if (thresholded) {
+      HIPCHK(h, hipMemsetAsync(d_count, 0, sizeof(unsigned long long), st));
+      const int blocks = (int)std::min<int64_t>((nk + 255) / 256, 256 * 64);
+      hipLaunchKernelGGL(select_below_pos_kernel, dim3(blocks), dim3(256), 0, st, d_hash, nk, tau, d_ch, d_cp, d_count, cap);
+      if ((rc = count_selected()) != WFM_OK) return rc;
+    }
+  }
+  uint64_t* d_sh = nullptr; uint32_t* d_sp = nullptr;  // the pairs in (hash, position) order
+  if (selected) {
+    uint64_t* d_h2 = nullptr; uint32_t* d_p2 = nullptr;
+    HIPCHK(h, sc.alloc(&d_h2, (size_t)m * 8));
+    HIPCHK(h, sc.alloc(&d_p2, (size_t)m * 4));
+    HIPCHK(h, sc.alloc(&d_sh, (size_t)m * 8));
+    HIPCHK(h, sc.alloc(&d_sp, (size_t)m * 4));
+    HIPCHK(h, sort_pairs(sc, d_cp, d_p2, d_ch, d_h2, (size_t)m, 32, st));  // (the atomics append in any order)
+    HIPCHK(h, sort_pairs(sc, d_h2, d_sh, d_p2, d_sp, (size_t)m, 64, st));
+  } else {
+    uint32_t* d_pos = nullptr;
+    HIPCHK(h, sc.alloc(&d_pos, (size_t)nk * 4));
+    HIPCHK(h, sc.alloc(&d_sh, (size_t)nk * 8));
+    HIPCHK(h, sc.alloc(&d_sp, (size_t)nk * 4));
+    const int blocks = (int)std::min<int64_t>((nk + 255) / 256, 256 * 8);
+    hipLaunchKernelGGL(iota_pos_kernel, dim3(blocks), dim3(256), 0, st, d_pos, nk);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, sort_pairs(sc, d_hash, d_sh, d_pos, d_sp, (size_t)nk, 64, st));
+  }
+  std::vector<uint64_t> hh((size_t)n);
+  std::vector<uint32_t> hp((size_t)n);
+  HIPCHK(h, hipMemcpyAsync(hh.data(), d_sh, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipMemcpyAsync(hp.data(), d_sp, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipStreamSynchronize(st));
+  int64_t valid = n;
+  while (valid > 0 && hh[(size_t)valid - 1] == ~0ull) --valid;  // k-mers with an N and palindromes sort last (two-pass form)
+  out.reserve((size_t)valid);
+  int64_t first = 0;
+  for (int64_t i = 0; i < valid; ++i) {
+    if (i == 0 || hh[(size_t)i] != hh[(size_t)i - 1]) first = hp[(size_t)i];
+    wfm_minmer_t r;
+    r.hash = hh[(size_t)i]; r.wpos = first; r.wpos_end = first + w; r.seqId = seq_id; r.strand = 1; r.pad_ = 0;  // strnd::FWD
+    out.push_back(r);
+  }
+  // by wpos: distinct hashes have distinct first positions, and the entries of one hash are identical records
+  std::stable_sort(out.begin(), out.end(), [](const wfm_minmer_t& a, const wfm_minmer_t& b) { return a.wpos < b.wpos; });
+  return WFM_OK;
+}

@@ -67,6 +67,7 @@ skch::Parameters to_parameters(const wfmh_map_params_t& c) {
   if (c.query_list) p.query_list = c.query_list;
   if (c.index_file) { p.indexFilename = c.index_file; p.create_index_only = c.write_index != 0; }
   if (c.scaffold_out) p.scaffold_output_file = c.scaffold_out;
+  p.use_streaming_minhash = c.streaming_minhash != 0;
   if (c.query_prefix) {  // CommonFunc::split(args::get(query_prefix), ',') (parse_args.hpp:204)
     std::stringstream ss(c.query_prefix);
     for (std::string tok; std::getline(ss, tok, ',');) p.query_prefix.push_back(tok);
@@ -120,6 +121,7 @@ void wfmh_map_default_params(wfmh_map_params_t* c) {
   c->auto_pct_identity = p.auto_pct_identity;
   c->ani_percentile = p.ani_percentile;
   c->ani_adjustment = p.ani_adjustment;
+  c->streaming_minhash = p.use_streaming_minhash;
 }
 
 int wfmh_map(wfm_handle_t* h, const char* target_fasta, const char* query_fasta, const char* out_paf, const wfmh_map_params_t* params,

@@ -12,11 +12,18 @@
 //                                              filtered seeds are written (host only, no GPU is opened)
 //   --scaffold-out FILE                        the scaffold chains the scaffold filter used as anchors (:105, :464-465),
 //                                              of the map path or of -K
+//   --streaming-minhash                        target sketches from one bottom-s MinHash per sequence instead of winnowed
+//                                              minmers (:137, :177; winSketch.hpp:467-497); no effect with -K or -i
+//   --hg-filter n,D,conf                       numerator, ANI difference and confidence of the L1 / L2 cutoffs (:94, :700-725)
+//   -B DIR / -Z                                directory of the map-to-align hand-off file [cwd] / keep that file (:134-135)
+//   --quiet, --ani-sketch-size INT             accepted and without effect: there is no progress meter, and the identity
+//                                              estimate's sketch size is 4096 in the reference too (map_stats.hpp:330)
 //
 // Differences: output goes to stdout or --out FILE; --device picks the GPU, --gpus N spreads the
 // queries (map) and the mapping records (align) over N GPUs of the node.  -K together with -i, -W or
 // -I is refused (the reference ignores the index flags there).  Options of the reference that belong
 // to subsystems outside this build (wavefront plots -G/-u) are not accepted.
+#include <sys/stat.h>
 #include <unistd.h>
 
 #include <cstdio>
@@ -25,6 +32,7 @@
 #include <algorithm>
 #include <limits>
 #include <regex>
+#include <sstream>
 #include <string>
 #include <vector>
 
@@ -42,6 +50,29 @@ static int64_t handy_parameter(const std::string& v) {  // utils.cpp:13-29 ("50k
   return (int64_t)(atof(t.c_str()) * mult);
 }
 
+// --hg-filter n,D,conf (parse_args.hpp:700-725): false with the message printed when the value is refused
+static bool parse_hg_filter(const std::string& v, wfmh_map_params_t* mp) {
+  std::vector<std::string> params;  // CommonFunc::split: std::getline on ',' (commonFunc.hpp:744-757)
+  std::stringstream ss(v);
+  for (std::string item; std::getline(ss, item, ',');) params.push_back(item);
+  if (params.size() != 3) {
+    fprintf(stderr, "[wfmash] ERROR: hypergeometric filter requires 3 comma-separated values: numerator,ani-diff,confidence\n");
+    return false;
+  }
+  double x[3];
+  for (int j = 0; j < 3; ++j) {  // std::stod: a number at the start of the value, or it throws
+    const char* c = params[(size_t)j].c_str();
+    char* end = nullptr;
+    x[j] = strtod(c, &end);
+    if (end == c) { fprintf(stderr, "[wfmash] ERROR: --hg-filter expects numbers, got: %s\n", c); return false; }
+    if (j == 0 && x[0] < 1.0) { fprintf(stderr, "[wfmash] ERROR: hg-filter numerator must be >= 1.0\n"); return false; }
+  }
+  mp->hg_numerator = x[0];
+  mp->ani_diff = (float)(x[1] / 100.0);
+  mp->ani_diff_conf = (float)(x[2] / 100.0);
+  return true;
+}
+
 static void usage() {
   fprintf(stderr,
           "usage: wfmash-hip [options] target.fa [query.fa]\n"
@@ -50,13 +81,16 @@ static void usage() {
           "            -n INT|inf mappings per segment [inf]   -l INT block length [0]   -c INT chain jump [2k]   -P INT max length [50k]\n"
           "            -N no split   -M no merge   -f no filter   -o one-to-one   -O FLOAT max overlap [0.95]   -x FLOAT sparsify [1.0]\n"
           "            -H INT L1 hits [3]   -F FLOAT high-frequency filter [0.0002]   -b SIZE target batch [all]\n"
+          "            --hg-filter n,D,conf hypergeometric filter [1.0,0.0,99.9]   --ani-sketch-size INT (no effect)\n"
           "            -W FILE build the index, write it and stop   -I FILE read the index from FILE\n"
+          "            --streaming-minhash target sketches from a per-sequence bottom-s MinHash (experimental)\n"
           "            -K FILE external PAF seeds in place of the mapper ('-' = stdin)\n"
           "            -S INT scaffold mass [10k]   -D INT scaffold dist [100k]   -j INT scaffold jump [100k]   -r INT per scaffold [1]\n"
           "            --scaffold-out FILE write the scaffold chains\n"
           "            -Y C group delimiter [#]   -X self maps   -L lower triangular   -t INT threads [1]\n"
           "  alignment -g x,o1,e1,o2,e2 [5,8,2,24,1]   -E INT target padding   -U INT query padding   -a SAM   -d MD tag\n"
-          "  other     --out FILE [stdout]   --device INT [0]   --gpus N|all [1] GPUs of this node, starting at --device\n");
+          "  other     --out FILE [stdout]   --device INT [0]   --gpus N|all [1] GPUs of this node, starting at --device\n"
+          "            -B DIR directory of the hand-off file [cwd]   -Z keep the hand-off file   --quiet (no effect)\n");
 }
 
 int main(int argc, char** argv) {
@@ -65,8 +99,8 @@ int main(int argc, char** argv) {
   ap.threads = 1;  // -t, default 1 as in the reference (parse_args.hpp: thread_count); the C ABI default (0) means all cores
   wfmh_map_params_t mp;
   wfmh_map_default_params(&mp);
-  std::string mapping_in, out = "/dev/stdout", target, query, seeds_in, scaffold_out;
-  bool approx_only = false, target_padding_given = false, query_padding_given = false;
+  std::string mapping_in, out = "/dev/stdout", target, query, seeds_in, scaffold_out, tmp_base;
+  bool approx_only = false, target_padding_given = false, query_padding_given = false, keep_temp = false;
   int device = 0, gpus = 1;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
@@ -87,6 +121,11 @@ int main(int argc, char** argv) {
     else if (a == "--device") device = atoi(next("--device").c_str());
     else if (a == "--gpus") { const std::string v = next("--gpus"); gpus = v == "all" ? 0 : atoi(v.c_str()); if (gpus < 0) gpus = 1; }
     else if (a == "-t" || a == "--threads") { mp.threads = atoi(next("-t").c_str()); ap.threads = mp.threads; }
+    // ---- system (parse_args.hpp:134-137)
+    else if (a == "-B" || a == "--tmp-base") tmp_base = next("-B");
+    else if (a == "-Z" || a == "--keep-temp") keep_temp = true;
+    else if (a == "--quiet") {}  // no progress meter to turn off
+    else if (a == "--streaming-minhash") mp.streaming_minhash = 1;
     // ---- mapping (parse_args.hpp:71-115)
     else if (a == "-k" || a == "--kmer-size") mp.kmer_size = atoi(next("-k").c_str());
     else if (a == "-s" || a == "--sketch-size") mp.sketch_size = atoi(next("-s").c_str());
@@ -143,6 +182,13 @@ int main(int argc, char** argv) {
       mp.sparsity_hash_threshold = f == 1 ? std::numeric_limits<uint64_t>::max() : (uint64_t)(f * (double)std::numeric_limits<uint64_t>::max());
     }
     else if (a == "-H" || a == "--l1-hits") mp.minimum_hits = atoi(next("-H").c_str());
+    else if (a == "--hg-filter") { if (!parse_hg_filter(next("--hg-filter"), &mp)) return 1; }
+    else if (a == "--ani-sketch-size") {  // stored by the reference, never read: the estimate's sketch is 4096 (map_stats.hpp:330)
+      const std::string v = next("--ani-sketch-size");
+      char* end = nullptr;
+      (void)strtol(v.c_str(), &end, 10);
+      if (v.empty() || *end) { fprintf(stderr, "[wfmash] ERROR: --ani-sketch-size expects an integer, got: %s\n", v.c_str()); return 1; }
+    }
     else if (a == "-F" || a == "--filter-freq") mp.max_kmer_freq = atof(next("-F").c_str());
     else if (a == "-b" || a == "--batch") mp.index_by_size = size("-b");
     else if (a == "-W" || a == "--write-index") { mp.index_file = argv[(next("-W"), i)]; mp.write_index = 1; }
@@ -206,6 +252,15 @@ int main(int argc, char** argv) {
   if (!target_padding_given) ap.target_padding = (uint64_t)std::min<int64_t>(mp.window_length, 5000);
   if (!query_padding_given) ap.query_padding = (uint64_t)std::min<int64_t>(mp.window_length, 5000);
   ap.wflign_max_len_minor = (uint64_t)mp.window_length * 128;
+  const bool hand_off = mapping_in.empty() && !approx_only;  // a temporary mapping file between the phases
+  const std::string tmp_dir = tmp_base.empty() ? "." : tmp_base;
+  if (hand_off && !tmp_base.empty()) {  // checked before any device is opened
+    struct stat sb;
+    if (stat(tmp_dir.c_str(), &sb) != 0 || !S_ISDIR(sb.st_mode) || access(tmp_dir.c_str(), W_OK | X_OK) != 0) {
+      fprintf(stderr, "[wfmash] ERROR: the temporary directory (-B) %s does not exist or is not writable\n", tmp_dir.c_str());
+      return 1;
+    }
+  }
   const char* q = query.empty() ? nullptr : query.c_str();
   auto seed = [&](const std::string& to) {  // -K: the seeds through the filters into `to` (host only)
     wfmh_map_summary_t ms;
@@ -235,10 +290,10 @@ int main(int argc, char** argv) {
   std::string temp;
   if (mapping.empty()) {
     if (approx_only) mapping = out;
-    else {  // the hand-off file between the phases (temp_file::create, parse_args.hpp:805-808)
-      char tmpl[] = "./wfmash-XXXXXX";
-      const int fd = mkstemp(tmpl);
-      if (fd < 0) { fprintf(stderr, "[wfmash] ERROR: cannot create a temporary file in the working directory\n"); destroy_all(); return 1; }
+    else {  // the hand-off file between the phases (temp_file::create, parse_args.hpp:805-808; temp_file.hpp:66-105)
+      std::string tmpl = tmp_dir + "/wfmash-XXXXXX";
+      const int fd = mkstemp(&tmpl[0]);
+      if (fd < 0) { fprintf(stderr, "[wfmash] ERROR: cannot create a temporary file in %s\n", tmp_dir.c_str()); destroy_all(); return 1; }
       close(fd);
       temp = tmpl;
       mapping = temp;
@@ -257,8 +312,13 @@ int main(int argc, char** argv) {
               ms.ms_map, ms.ms_filter, ms.ms_total);
     else fprintf(stderr, "[wfmash::map] ERROR: %s\n", wfm_last_error(h));
   }
+  auto release_temp = [&] {  // -Z: kept (temp_file.hpp:42)
+    if (temp.empty()) return;
+    if (keep_temp) fprintf(stderr, "[wfmash] keeping temporary file %s\n", temp.c_str());
+    else unlink(temp.c_str());
+  };
   if (mp.index_file && mp.write_index) {  // -W: "index construction completed", nothing else runs (computeMap.hpp:405-415)
-    if (!temp.empty()) unlink(temp.c_str());
+    release_temp();
     destroy_all();
     return rc == WFM_OK ? 0 : 3;
   }
@@ -270,7 +330,7 @@ int main(int argc, char** argv) {
               (unsigned long long)s.records, (unsigned long long)s.aligned_bp, s.ms_gpu, s.ms_total, s.aligned_bp / (s.ms_total * 1e-3));
     else fprintf(stderr, "[wfmash::align] ERROR: %s\n", wfm_last_error(h));
   }
-  if (!temp.empty()) unlink(temp.c_str());
+  release_temp();
   destroy_all();
   return rc == WFM_OK ? 0 : 3;
 }

@@ -129,6 +129,7 @@ struct Parameters {
   std::vector<std::string> query_prefix;
   std::string outFileName = "/dev/stdout";
   std::string scaffold_output_file;        // --scaffold-out (:105, :464-465); empty = no scaffold chains are kept or written
+  bool use_streaming_minhash = false;      // --streaming-minhash (:137, :177; the true of map_parameters.hpp:101 is never seen from the CLI)
 };
 
 }  // namespace skch

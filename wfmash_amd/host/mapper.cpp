@@ -253,10 +253,12 @@ int Map::mapQuery(MapSummary* summary) {
         sp.push_back(seq.data()); sl.push_back((int64_t)seq.size()); si.push_back(ids.getSequenceId(name));
       }
       // minmer intervals (GPU hashing + thinning, host winnowing) and the index stage; the intervals never
-      // sit in one host array
+      // sit in one host array.  --streaming-minhash: one bottom-S MinHash per sequence instead (winSketch.hpp:474-485)
       int64_t n_windows = 0;
-      const int rc = wfm_index_build_sequences(h_, sp.data(), sl.data(), si.data(), (int64_t)sp.size(), k, (int)w, S, P.threads,
-                                               P.max_kmer_freq, &ix, &n_windows);
+      const int rc = P.use_streaming_minhash && S > 0
+                         ? wfm_index_build_streaming(h_, sp.data(), sl.data(), si.data(), (int64_t)sp.size(), k, (int)w, S, P.max_kmer_freq, &ix, &n_windows)
+                         : wfm_index_build_sequences(h_, sp.data(), sl.data(), si.data(), (int64_t)sp.size(), k, (int)w, S, P.threads,
+                                                     P.max_kmer_freq, &ix, &n_windows);
       if (rc != WFM_OK) return rc;
       sum.index_windows += (uint64_t)n_windows;
     }

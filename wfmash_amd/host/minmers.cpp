@@ -1321,6 +1321,45 @@ extern "C" int wfm_index_build_sequences(wfm_handle_t* h, const char* const* seq
   return rc;
 }
 
+namespace {
+// --streaming-minhash: the records of every sequence (map_streaming_sketch), grouped by sequence in input order, into one sink
+int64_t streaming_core(wfm_handle_t* h, const char* const* seqs, const int64_t* lens, const int32_t* seq_ids, int64_t nseq, int k, int w, int s,
+                       MinmerSink& sink, int64_t* counts) {
+  if (!h || nseq < 0 || (nseq && (!seqs || !lens)) || s < 1 || w < 1) return WFM_E_ARG;
+  std::vector<wfm_minmer_t> all, one;
+  for (int64_t i = 0; i < nseq; ++i) {
+    const int rc = map_streaming_sketch(h, seqs[i], lens[i], k, w, s, seq_ids ? seq_ids[i] : (int32_t)i, one);
+    if (rc != WFM_OK) return rc;
+    if (counts) counts[i] = (int64_t)one.size();
+    all.insert(all.end(), one.begin(), one.end());
+  }
+  if (!all.empty()) {  // (a handful of records per sequence: one copy for the whole list)
+    const int rc = sink.put(all.data(), (int64_t)all.size());
+    if (rc != WFM_OK) return rc;
+  }
+  return (int64_t)all.size();
+}
+}  // namespace
+
+extern "C" int64_t wfm_streaming_minmers(wfm_handle_t* h, const char* const* seqs, const int64_t* lens, const int32_t* seq_ids, int64_t nseq,
+                                         int k, int w, int s, wfm_minmer_t* out, int64_t cap, int64_t* counts) {
+  if (cap && !out) return WFM_E_ARG;
+  HostSink sink(out, cap);
+  return streaming_core(h, seqs, lens, seq_ids, nseq, k, w, s, sink, counts);
+}
+
+// Sketch::build with --streaming-minhash: the streaming records of all sequences, then the unchanged index stage
+extern "C" int wfm_index_build_streaming(wfm_handle_t* h, const char* const* seqs, const int64_t* lens, const int32_t* seq_ids, int64_t nseq,
+                                         int k, int w, int s, double max_kmer_freq, wfm_index_t** out, int64_t* n_windows) {
+  if (!h || !out) return WFM_E_ARG;
+  *out = nullptr;
+  DeviceSink sink(h, nseq * (int64_t)std::max(s, 0));
+  const int64_t n = streaming_core(h, seqs, lens, seq_ids, nseq, k, w, s, sink, nullptr);
+  if (n < 0) return (int)n;
+  if (n_windows) *n_windows = n;
+  return n > 0 ? map_index_build_device(h, sink.d, n, max_kmer_freq, out) : WFM_OK;  // n == 0: no index, *out stays NULL
+}
+
 // Test hook (CPU test-suite): the host winnowing stage on caller-supplied k-mer hashes.
 // chunk_len > 0 runs the speculative chunked form (single thread) and reports replays in *replays.
 extern "C" int64_t wfmh_test_winnow_chunked(const char* seq, int64_t len, int k, int w, int s, int32_t seq_id, const uint64_t* hash,
