@@ -63,6 +63,9 @@ extern "C" {
  * tested at wflign.cpp:150,307,399 */
 #define WFM_ST_OK            0
 #define WFM_ST_UNREACHABLE (-300)
+/* The wavefronts of the problem do not fit the handle's memory budget.  For a BiWFA problem the limit is the alignment's SCORE, not the
+ * record's length: where a ring over all diagonals does not fit, rings grow with the score a job reaches (about 2 x score columns of
+ * 1280 bytes -- 5120 for penalties of a scope beyond 30 -- have to fit the budget). */
 #define WFM_ST_OOM         (-200)
 
 #define WFMASH_HIP_VERSION "wfmash-hip-0.3"   /* SAM @PG VN:, `wfmash-hip --version` */
@@ -207,6 +210,7 @@ void wfm_set_concurrent_calls(wfm_handle_t* h, int other_calls);
 #define WFM_PF_P2_ROUNDS   32u   /* an overlap walk went past the first round of rows computed ahead                  */
 #define WFM_PF_RING_KERNEL 64u   /* a leaf / patch ran on the global-memory ring kernel (other penalties, an N; rows beyond 2048 diagonals until round 6) */
 #define WFM_PF_BASE_TILES 128u   /* a patch with rows beyond 2048 diagonals ran as tiles of the register kernel (its third attempt)   */
+#define WFM_PF_RING_GROWN 256u   /* the full ring of the root or of a child did not fit the budget: it ran on rings grown with its score   */
 size_t wfm_get_problem_flags(const wfm_handle_t* h, uint32_t* out, size_t n);
 
 /* Device blocks of both paths -- the map path's work buffers, the align path's arenas and a batch's sequence buffers, also

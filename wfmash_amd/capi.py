@@ -19,6 +19,7 @@ WFM_MODE_END2END_UNI = 2
 DEFAULT_PEN = (5, 8, 2, 24, 1)  # parse_args.hpp:290-294
 # wfm_get_problem_flags (include/wfmash_hip.h): which of the rarer paths a problem took
 WFM_PF_ROOT_AGAIN, WFM_PF_JOB_AGAIN, WFM_PF_BASE_RETRY, WFM_PF_BASE_RETRY2, WFM_PF_BYTE_KERNEL, WFM_PF_P2_ROUNDS, WFM_PF_RING_KERNEL, WFM_PF_BASE_TILES = 1, 2, 4, 8, 16, 32, 64, 128
+WFM_PF_RING_GROWN = 256
 
 EXPORTS = [
     "wfm_create", "wfm_destroy", "wfm_last_error", "wfm_device_name",

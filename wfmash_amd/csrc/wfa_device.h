@@ -220,6 +220,17 @@ void launch_tile_p2(const uint8_t* seq, int32_t* ring, const TileJob* jobs, cons
 // The state after 2 * P2K tests as a snapshot: the last RING rows of both directions, out of the P2 rows into the job's ring
 // (jobs whose walk ran out of rows go another round from there)
 void launch_p2_to_ring(int32_t* ring, const int32_t* p2, const P2Job* jobs, int njobs, hipStream_t st);
+// A ring moved into another geometry (a job that ran out of its narrow ring goes on from its snapshot on a wider one): every row of
+// both directions and all five components ([dir][comp][ring rows][width], column = k + koff) from src to dst, diagonals klo .. khi;
+// every other column of dst is WF_NULL.  src and dst are the rings' first elements; they may lie in different device blocks.
+struct RingWidenJob {
+  const int32_t* src;
+  int32_t* dst;
+  int32_t src_w, src_koff;
+  int32_t dst_w, dst_koff;             // dst_w: a multiple of 4
+  int32_t klo, khi;
+};
+void launch_ring_widen(const RingWidenJob* jobs, int njobs, int max_dst_w, int ring_rows, hipStream_t st);
 void launch_p2_blockmax(const int32_t* ring, const int32_t* p2, const P2Job* jobs, int32_t* bmax, int32_t* p2max, int njobs, hipStream_t st);
 void launch_p2_overlap(const int32_t* ring, const int32_t* p2, const P2Job* jobs, const int32_t* p2max, const int32_t* bmax, int32_t* pbmax,
                        BpResult* res, int njobs, int threads, int max_nblk, DevPen pen, int scope, hipStream_t st);

@@ -97,6 +97,22 @@ struct Node {
   int32_t sub;        // bialign jobs: upper bound of the score (SUB_NONE: none); the wavefronts are cut to what can stay under it
   int32_t hinted;     // the bound is the caller's guess (a root): the job is run again without it if the guess was too small
   int32_t tries;      // base jobs: how many score budgets the job has overflowed so far
+  int32_t band;       // bialign jobs that are run again: the band (scores a direction) of the attempt that failed, 0: it had a full ring.  Where the
+                      // full ring does not fit the budget the next attempt's band grows from it (the level loop of align_resident_impl)
+  int32_t snap;       // bialign jobs: 1 + the index of the snapshot the job goes on from on its wider ring (GrownSnap), 0: it starts at score 0
+};
+
+// The state of a tiled job that ran out of its narrow ring, kept in a device block of its own until the job has its wider ring: the columns
+// |k| <= s0 + 8 of every row of the snapshot of score s0 (both directions stand there), and the running maxima of the two directions
+struct GrownSnap {
+  int32_t* d = nullptr;
+  int32_t w = 0, koff = 0;
+  int32_t s0 = 0, fmax = 0, rmax = 0;
+};
+struct GrownSnaps {  // (the blocks of a call that ends early go back as well)
+  std::vector<GrownSnap> v;
+  void drop(int32_t id) { if (id > 0 && v[(size_t)id - 1].d) { wfm_dfree(v[(size_t)id - 1].d); v[(size_t)id - 1].d = nullptr; } }
+  ~GrownSnaps() { for (size_t q = 0; q < v.size(); ++q) drop((int32_t)q + 1); }
 };
 
 }  // namespace
@@ -183,6 +199,7 @@ struct wfm_handle {
   DevBuf<int32_t> tilemak;
   DevBuf<int32_t> p2rows, p2max, p2bmax, p2pbmax;  // phase 2 from rows computed ahead (P2Job)
   DevBuf<P2Job> p2jobs;
+  DevBuf<RingWidenJob> widenjobs;
   DevBuf<SeqRev> revjobs;
   DevBuf<BoundJob> bndjobs;   // roots whose score is bounded from above before their wavefronts run (wfa_bound_kernel)
   DevBuf<int32_t> bndres;
@@ -810,7 +827,11 @@ int run_tiled_phase(wfm_handle* h, wfm_seqset* S, const DevPen& dp, int scope, c
     ring2[i] = tj[i].ring_out;
     j.resume_s = tj[i].s0;
     j.resume_sr = -1; j.last_fwd = 0;
-    if (tj[i].mode == 3) { j.resume_s = -3; continue; }  // ran out of its band: wfa_bp_kernel reports WFM_DEV_BAND
+    if (tj[i].mode == 3) {  // ran out of its band: wfa_bp_kernel reports WFM_DEV_BAND
+      // (where it stands, for the host: a job that goes on from this snapshot on a wider ring resumes at resume_sr with these maxima)
+      j.resume_s = -3; j.resume_sr = tj[i].s0; j.fmax0 = fmax[i]; j.rmax0 = rmax[i];
+      continue;
+    }
     if (tj[i].mode == 2) {  // stopped exactly at the meeting point: the step kernel goes straight to phase 2
       j.resume_s = tj[i].s0 + tj[i].tf;
       j.resume_sr = tj[i].s0 + tj[i].tr;
@@ -1097,6 +1118,15 @@ int align_resident_impl(wfm_handle* h, const wfm_penalties_t* pen, wfm_seqset* S
   const int RR = ring_rows_for(scope);  // rows of every ring of this call
   uint64_t tile_cells_level = 0;
   uint64_t band_retries = 0, band_jobs = 0, roots_banded = 0, roots_out = 0, hint_retries = 0, hinted_roots = 0;
+  // Rings that grow with the score: a job whose full ring does not fit the budget runs on bands b, 4 b, 16 b ...
+  uint64_t grown_jobs = 0, grown_widened = 0, grown_restarts = 0;
+  int64_t grown_maxband = 0;
+  size_t ring_peak = 0;  // most elements a chunk's ring arena held
+  GrownSnaps snaps;
+  std::vector<int> tiled_r;        // the chunk's jobs that go on from a snapshot (indices into jobs), their second rings, their fine_s
+  std::vector<int64_t> ring2_r;
+  std::vector<int32_t> fine_r, snap_r;
+  std::vector<char> grown_job, resume_bad;
   bool roots_off = false;
   std::vector<int32_t> node_of;
   std::vector<BpResult> res;
@@ -1133,14 +1163,18 @@ int align_resident_impl(wfm_handle* h, const wfm_penalties_t* pen, wfm_seqset* S
       size_t i = i0;
       int maxw = 0;
       tiled.clear(); ring2.clear(); ring3.clear(); ring_third.clear(); fine_from.clear();
+      tiled_r.clear(); ring2_r.clear(); fine_r.clear(); snap_r.clear(); grown_job.clear();
+      int64_t fine_min_blocks_r = INT64_MAX;
       int64_t fine_min_blocks = INT64_MAX;  // fewest blocks any tiled job of the chunk is expected to run before its directions meet
       for (; i < bp_nodes.size(); ++i) {
         const Node& nd = bp_nodes[i];
         const ProbMeta& pm = S->meta[nd.prob];
         size_t width = ((size_t)nd.pl + nd.tl + 9 + 3) & ~(size_t)3;  // columns 4 .. pl+tl+4, 16-byte chunks
+        const size_t full_width = width;
         int koff = nd.pl + 4;
         bool tile_it = tcfg.enabled && nd.pl + nd.tl >= tcfg.min_len &&
                              (nd.score_rem == INT_MAX || nd.score_rem >= tcfg.min_score);
+        const bool tiles_take_it = tile_it;
         int band = 0;
         // (a root without a bound gets a guessed band only when the level would not fit otherwise: below the budget the
         // guess has nothing to win and a deep record -- 5 % divergence: 6 k scores per direction -- everything to lose)
@@ -1159,7 +1193,39 @@ int align_resident_impl(wfm_handle* h, const wfm_penalties_t* pen, wfm_seqset* S
           }
         }
         if (tile_it && width * 2 * 5 * RR * 2 * 4 > h->mem_budget) tile_it = false;  // two snapshot rings do not fit: step-by-step kernel
-        const size_t need = width * 2 * 5 * RR * (tile_it ? 2 : 1);
+        size_t need = width * 2 * 5 * RR * (tile_it ? 2 : 1);
+        // The ring does not fit the budget (the job's first attempt, without a band it could have had; or its full ring, after a band ran out
+        // or a guess of its score failed): a ring for max(4 x the band it had, WFM_BAND_ROOT) scores a direction -- the cells of a job grow with the
+        // square of the score it reaches, so all the attempts before the one that holds cost a fifteenth of it -- on the tile kernels where they
+        // take the job and two such rings fit, on the step kernel alone otherwise; no wider than the budget holds.  (A child's first band is what its
+        // known score asks for, as above.)  Once the band's ring would be as wide as the full one -- below the budget a band has to halve the ring
+        // to be worth a second attempt, here the full ring is no alternative -- or the job has spent the widest band the budget holds, its score
+        // is beyond the budget: WFM_ST_OOM.
+        bool grown = false;
+        if (need * 4 > h->mem_budget) {
+          const size_t col_bytes = (size_t)2 * 5 * RR * 4;  // one column of a ring
+          const int64_t first = nd.score_rem == INT_MAX ? (int64_t)band_root : (int64_t)nd.score_rem / 2 + 64 + (int64_t)tcfg.chunk * tcfg.T + 16;
+          int64_t nb = nd.band > 0 ? std::max<int64_t>(4 * (int64_t)nd.band, first) : first;
+          size_t gw = 0;
+          int gk = 0;
+          auto band_ring = [&](int64_t b) {  // the geometry of the guessed bands above
+            const int64_t shift = std::max<int64_t>(0, ((int64_t)nd.pl - (b + 8)) & ~(int64_t)3);  // (0: a short pattern, the ring is cut on the right only)
+            const int64_t right = std::min<int64_t>(nd.tl, b + 8);
+            gw = ((size_t)((int64_t)nd.pl - shift + right + 9) + 3) & ~(size_t)3;
+            gk = (int)(nd.pl + 4 - shift);
+            return gw < full_width;
+          };
+          bool fits = band_ring(nb);
+          if (fits && gw * col_bytes > h->mem_budget) {
+            nb = ((int64_t)(h->mem_budget / col_bytes) - 32) / 2;  // (a ring for b scores is at most 2 b + 32 columns wide)
+            fits = nb > (int64_t)nd.band && nb >= 64 && band_ring(nb) && gw * col_bytes <= h->mem_budget;
+          }
+          if (!fits) { prob_status[nd.prob] = WFM_ST_OOM; snaps.drop(nd.snap); continue; }
+          grown = true;
+          band = (int)nb; width = gw; koff = gk;
+          tile_it = tiles_take_it && width * col_bytes * 2 <= h->mem_budget;
+          need = width * 2 * 5 * RR * (tile_it ? 2 : 1);
+        }
         // (a chunk of a level stops at 4 GB of rings even when the budget allows more: hundreds of jobs fill the device
         // long before that, and every GB of a first allocation costs 30 - 70 ms.  C1 substitute, three handles in a fresh
         // process: 8 GB chunks 8.3 s cold / 5.33 s warm, 4 GB 5.67 / 5.52, 2 GB 6.22 / 6.06 -- scripts/c1_cold.sh.  A chunk of
@@ -1167,7 +1233,6 @@ int align_resident_impl(wfm_handle* h, const wfm_penalties_t* pen, wfm_seqset* S
         // Tried and dropped: two launches per block, jobs without a score bound apart from those with one -- the plain kernel form
         // has 7 % fewer instructions, the second launch cost more: C2 0.18 -> 0.21 s, C1 no better)
         if (!jobs.empty() && (ring_elems + need) * 4 > std::min<size_t>(h->mem_budget, jobs.size() >= 128 ? ring_chunk_bytes : std::max(ring_chunk_bytes, (size_t)8 << 30))) break;
-        if (need * 4 > h->mem_budget) { prob_status[nd.prob] = WFM_ST_OOM; continue; }
         BpJob j{};
         j.p_fwd = pm.p_fwd + nd.pb;
         j.t_fwd = pm.t_fwd + nd.tb;
@@ -1189,8 +1254,27 @@ int align_resident_impl(wfm_handle* h, const wfm_penalties_t* pen, wfm_seqset* S
         // bit 1: near-identical sequences -- the job's score is known (a child's, a bounded or hinted root's) to be under a sixteenth of its length; the packed
         // tile kernel then hands a lone long run to the whole wave at once (wfa_tile2.hip, tail_direct).  Whether the bound also CUTS the rows (sub below) is another matter.
         if (j.packed && nd.sub != SUB_NONE && (int64_t)nd.sub * 16 < (int64_t)nd.pl + nd.tl) j.packed |= 2;
-        band_jobs += band > 0;
-        if (tile_it) {
+        band_jobs += band > 0 && !grown;
+        grown_job.push_back((char)grown);
+        const bool resumes = grown && tile_it && nd.snap > 0;  // (a snapshot is the tile kernels' own: no gap rows as deep as the step kernel reads)
+        if (nd.snap > 0 && !resumes) snaps.drop(nd.snap);
+        if (grown) {
+          ++grown_jobs;
+          grown_maxband = std::max<int64_t>(grown_maxband, band);
+          if (resumes) ++grown_widened; else if (nd.noband || nd.band > 0) ++grown_restarts;
+          if (pflags) pflags[nd.prob] |= WFM_PF_RING_GROWN;
+          if (getenv("WFM_DEBUG"))
+            fprintf(stderr, "[wfm] grown ring: problem %d, %s of %d x %d: band %d, %zu columns on the %s%s\n", nd.prob, nd.score_rem == INT_MAX ? "root" : "child", nd.pl, nd.tl, band, width,
+                    tile_it ? "tile kernels" : "step kernel alone", resumes ? ", widened from its snapshot" : ((nd.noband || nd.band > 0) ? ", from score 0 again" : ""));
+        }
+        if (resumes) {
+          // the job's rule for per-score maxima is the one it started with (below); its blocks until the directions meet are counted from the snapshot
+          const GrownSnap& sn = snaps.v[(size_t)nd.snap - 1];
+          tiled_r.push_back((int)jobs.size()); ring2_r.push_back((int64_t)(ring_elems + need / 2)); snap_r.push_back(nd.snap);
+          const int64_t est = nd.score_rem != INT_MAX ? (int64_t)nd.score_rem : (int64_t)nd.pl + nd.tl;
+          fine_min_blocks_r = std::min<int64_t>(fine_min_blocks_r, std::max<int64_t>(0, est / 2 - sn.s0) / tcfg.T);
+          fine_r.push_back(nd.score_rem != INT_MAX ? std::max(0, nd.score_rem / 2 - fine_margin) : INT_MAX);
+        } else if (tile_it) {
           tiled.push_back((int)jobs.size()); ring2.push_back((int64_t)(ring_elems + need / 2)); ring_third.push_back(need / 2);
           // per-score maxima from here on (TileJob::fine_s): a child's directions meet near half its score (the trigger -- the sum of the two largest
           // antidiagonals -- can fire a little earlier, never later); a root's score is anybody's guess: it finds its meeting block with one maximum
@@ -1216,6 +1300,7 @@ int align_resident_impl(wfm_handle* h, const wfm_penalties_t* pen, wfm_seqset* S
       // device time, the scaled C4 rank +3 % (gpurun_out/r6r/ab2.log).  So: only chunks of at most coarse_max_jobs jobs, every one of them
       // at least coarse_min_blocks blocks deep; everybody else keeps the per-score maxima from the first block on (one launch per block, as before).
       if (tiled.size() > (size_t)coarse_max_jobs || fine_min_blocks < (int64_t)coarse_min_blocks) std::fill(fine_from.begin(), fine_from.end(), 0);
+      if (tiled_r.size() > (size_t)coarse_max_jobs || fine_min_blocks_r < (int64_t)coarse_min_blocks) std::fill(fine_r.begin(), fine_r.end(), 0);
       // third rings behind the chunk's rings (TileJob::ring_prev), for all of its tiled jobs or for none: where half as much again still fits the
       // budget (and 12 GB: fresh memory is 30 ms per GB).  The chunk's composition does not depend on it.
       {
@@ -1230,12 +1315,51 @@ int align_resident_impl(wfm_handle* h, const wfm_penalties_t* pen, wfm_seqset* S
         if (h->ring.ensure(ring_elems + 16) || h->bpjobs.ensure(jobs.size()) || h->bpres.ensure(jobs.size())) {
           h->err = "out of device memory (ring arena)"; return WFM_E_NOMEM;
         }
+        ring_peak = std::max(ring_peak, ring_elems);
+        resume_bad.assign(jobs.size(), 0);
+        if (!tiled_r.empty()) {
+          // the snapshots of the jobs that go on where they stood, out of their blocks into the chunk's (wider) rings; the blocks go back
+          std::vector<RingWidenJob> wj;
+          int maxw_dst = 0;
+          for (size_t q = 0; q < tiled_r.size(); ++q) {
+            BpJob& j = jobs[(size_t)tiled_r[q]];
+            const GrownSnap& sn = snaps.v[(size_t)snap_r[q] - 1];
+            wj.push_back(RingWidenJob{sn.d, h->ring.p + j.ring_off, sn.w, sn.koff, j.width, j.koff, -(sn.s0 + 8), sn.s0 + 8});
+            maxw_dst = std::max(maxw_dst, j.width);
+            j.resume_s = sn.s0; j.resume_sr = -1; j.fmax0 = sn.fmax; j.rmax0 = sn.rmax;
+          }
+          if (h->widenjobs.ensure(wj.size())) { h->err = "out of device memory (ring arena)"; return WFM_E_NOMEM; }
+          HIPCHK(h, hipMemcpyAsync(h->widenjobs.p, wj.data(), wj.size() * sizeof(RingWidenJob), hipMemcpyHostToDevice, h->stream));
+          launch_ring_widen(h->widenjobs.p, (int)wj.size(), maxw_dst, RR, h->stream);
+          HIPCHK(h, hipGetLastError());
+          HIPCHK(h, hipStreamSynchronize(h->stream));
+          for (int32_t id : snap_r) snaps.drop(id);
+        }
         {
           double tms = 0; uint64_t tcells = 0;
           const auto tw0 = std::chrono::steady_clock::now();
           rc = run_tiled_phase(h, S, dp, scope, tcfg, tcfg.T, false, jobs, tiled, ring2, tms, tcells, level, &fine_from, &ring3);
           if (rc == WFM_OK && tcfg.T_refine > 0 && tcfg.T_refine < tcfg.T && !(tcfg.reg && tcfg.exact))
             rc = run_tiled_phase(h, S, dp, scope, tcfg, tcfg.T_refine, true, jobs, tiled, ring2, tms, tcells, level);
+          if (rc == WFM_OK && !tiled_r.empty()) {
+            std::vector<int> from_s(tiled_r.size());
+            const int resume_margin = getenv("WFM_RESUME_MARGIN") ? atoi(getenv("WFM_RESUME_MARGIN")) : 26;  // (tests: a large value sends every resumed job back to score 0)
+            for (size_t q = 0; q < tiled_r.size(); ++q) from_s[q] = jobs[(size_t)tiled_r[q]].resume_s;
+            rc = run_tiled_phase(h, S, dp, scope, tcfg, tcfg.T, true, jobs, tiled_r, ring2_r, tms, tcells, level, &fine_r);
+            for (size_t q = 0; rc == WFM_OK && q < tiled_r.size(); ++q) {
+              BpJob& j = jobs[(size_t)tiled_r[q]];
+              // The snapshot a job goes on from was written by a block of the tile kernels for the next block of the tile kernels: with a third ring
+              // in play (TileJob::ring_prev) it holds the gap components two rows and one row deep, not the 26 the overlap phase and the step kernel
+              // read.  A job whose directions meet within 26 scores of that snapshot would hand such rows on: it starts again on this band instead
+              // (26 scores out of the thousands the wider ring was made for).
+              const bool exact_end = j.resume_s >= 0 && j.resume_sr >= 0;
+              if (tcfg.reg && tcfg.exact && ((exact_end && std::min(j.resume_s, j.resume_sr) - from_s[q] < resume_margin) || (j.resume_s >= 0 && j.resume_sr < 0 && j.resume_s == from_s[q]))) {
+                j.resume_s = -3; j.resume_sr = -1;
+                resume_bad[(size_t)tiled_r[q]] = 1;
+              }
+              tiled.push_back(tiled_r[q]); ring2.push_back(ring2_r[q]);  // (from here on a tiled job like the others)
+            }
+          }
           wall_tile += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw0).count();
           if (rc != WFM_OK) return rc;
           tm.bp_ms += tms; tm.tile_ms += tms;
@@ -1342,20 +1466,51 @@ int align_resident_impl(wfm_handle* h, const wfm_penalties_t* pen, wfm_seqset* S
           const BpResult& r = res[q];
           prob_cells[nd.prob] += r.cells;
           h->stats.cells_bp += r.cells;
-          if (nd.score_rem == INT_MAX && jobs[q].band > 0) { ++roots_banded; roots_out += r.status == WFM_DEV_BAND; }
+          if (nd.score_rem == INT_MAX && jobs[q].band > 0 && !grown_job[q]) { ++roots_banded; roots_out += r.status == WFM_DEV_BAND; }
           const bool guessed = nd.hinted && jobs[q].sub != SUB_NONE;  // the job really ran under the caller's guess
           if (r.status == WFM_DEV_BAND || (guessed && (r.status < 0 || (r.status == 0 && r.score > nd.sub)))) {
             // ran out of its narrow ring, or past the caller's guess of its score: once more, at the end of this level, on
             // a full ring and without the guess
             Node again = nd; again.noband = 1; again.sub = SUB_NONE; again.hinted = 0;
+            again.band = jobs[q].band; again.snap = 0;
             if (pflags) pflags[nd.prob] |= nd.score_rem == INT_MAX ? WFM_PF_ROOT_AGAIN : WFM_PF_JOB_AGAIN;
+            // where the full ring does not fit, the job's next ring grows from the band it had (above)
+            const bool full_fits = ((((size_t)nd.pl + nd.tl + 9 + 3) & ~(size_t)3) * 2 * 5 * RR) * 4 <= h->mem_budget;
+            if (!full_fits) {
+              if (pflags) pflags[nd.prob] |= WFM_PF_RING_GROWN;
+              if (resume_bad[q]) again.band = nd.band;  // (the same band once more, from score 0)
+              // A tiled job that simply ran out of its band stands at a block boundary s0 <= band with both directions complete -- a row of score s
+              // spans |k| <= s, nothing was cut by the ring's edge -- and goes on from there: the columns |k| <= s0 + 8 of its snapshot wait in a block of
+              // their own for the job's wider ring (the chunk's arena is the next chunk's).  Not so a job under a bound of its score (rows cut to
+              // |k - (tl - pl)| <= sub - s: no state of the unbounded problem) or one the step kernel stopped: those start again from score 0.
+              const BpJob& j = jobs[q];
+              if (!resume_bad[q] && r.status == WFM_DEV_BAND && j.resume_s == -3 && j.resume_sr >= 0 && j.sub == SUB_NONE && j.band > 0) {
+                GrownSnap sn;
+                sn.s0 = j.resume_sr; sn.fmax = j.fmax0; sn.rmax = j.rmax0;
+                const int reach = sn.s0 + 8;
+                sn.koff = reach + 4;
+                sn.koff += ((j.koff - sn.koff) % 4 + 4) % 4;  // whole 16-byte chunks apart from the ring's columns, and from those of the ring to come
+                sn.w = (sn.koff + reach + 5 + 3) & ~3;
+                if (wfm_dmalloc((void**)&sn.d, (size_t)sn.w * 2 * 5 * RR * sizeof(int32_t)) != hipSuccess) { (void)hipGetLastError(); sn.d = nullptr; }
+                if (sn.d) {  // (no block to be had: the job starts again)
+                  const RingWidenJob wj{h->ring.p + j.ring_off, sn.d, j.width, j.koff, sn.w, sn.koff, -reach, reach};
+                  snaps.v.push_back(sn);
+                  again.snap = (int32_t)snaps.v.size();
+                  if (h->widenjobs.ensure(1)) { h->err = "out of device memory (ring arena)"; return WFM_E_NOMEM; }
+                  HIPCHK(h, hipMemcpyAsync(h->widenjobs.p, &wj, sizeof(wj), hipMemcpyHostToDevice, h->stream));
+                  launch_ring_widen(h->widenjobs.p, 1, sn.w, RR, h->stream);
+                  HIPCHK(h, hipGetLastError());
+                  HIPCHK(h, hipStreamSynchronize(h->stream));
+                }
+              }
+            }
             // (it joins the next level's jobs instead of holding this level up on its own: nodes are independent, only the gather at
             // the end waits for all of them.  Until round 5 a job that ran out of its ring was run again at the end of its own level --
             // three chains of 30 - 40 tile blocks one after the other in the first level of an LPA batch, 19 of its 50 ms of tile time;
             // WFM_RETRY_SAME_LEVEL=1 restores that for A/B runs)
             static const bool same_level = getenv("WFM_RETRY_SAME_LEVEL") && atoi(getenv("WFM_RETRY_SAME_LEVEL")) != 0;
             if (guessed || !same_level) next_bp.push_back(again); else bp_nodes.push_back(again);
-            ++band_retries;
+            band_retries += full_fits;
             hint_retries += guessed;
             continue;
           }
@@ -1442,6 +1597,10 @@ int align_resident_impl(wfm_handle* h, const wfm_penalties_t* pen, wfm_seqset* S
   if (getenv("WFM_DEBUG") && hint_retries) fprintf(stderr, "[wfm] score hints: %llu roots ran past their hint and were run again without it\n", (unsigned long long)hint_retries);
   (void)hinted_roots;
   if (getenv("WFM_DEBUG") && band_jobs) fprintf(stderr, "[wfm] narrow rings: %llu jobs, %llu ran out of their band and were run again on full rings\n", (unsigned long long)band_jobs, (unsigned long long)band_retries);
+  if (getenv("WFM_DEBUG") && grown_jobs)
+    fprintf(stderr, "[wfm] grown rings: %llu jobs, %llu widened and resumed, %llu started again, largest band %lld\n", (unsigned long long)grown_jobs,
+            (unsigned long long)grown_widened, (unsigned long long)grown_restarts, (long long)grown_maxband);
+  if (getenv("WFM_DEBUG") && atoi(getenv("WFM_DEBUG")) > 1) fprintf(stderr, "[wfm] ring arena: at most %.1f MB in a chunk\n", (double)ring_peak * 4.0 / 1048576.0);
   const auto t_levels = std::chrono::steady_clock::now();
 
   // ---- gather RLE pieces ----
@@ -1614,7 +1773,7 @@ void wfm_destroy(wfm_handle_t* h) {
   h->tilejobs.release(); h->tiletasks.release(); h->tilemak.release();
   h->revjobs.release(); h->bndjobs.release(); h->bndres.release();
   if (h->stage) { (void)hipHostFree(h->stage); h->stage = nullptr; h->stage_cap = 0; }
-  h->p2rows.release(); h->p2max.release(); h->p2bmax.release(); h->p2pbmax.release(); h->p2jobs.release();
+  h->p2rows.release(); h->p2max.release(); h->p2bmax.release(); h->p2pbmax.release(); h->p2jobs.release(); h->widenjobs.release();
   h->bpjobs.release(); h->bpres.release(); h->bsjobs.release(); h->bsres.release();
   h->b2tjobs.release(); h->b2ttasks.release(); h->b2tkeys.release(); h->b2toffs.release(); h->b2tactive.release();
   h->i64a.release(); h->i64b.release(); h->i64c.release(); h->i32a.release(); h->seqflags.release(); h->flagjobs.release(); h->total.release();

@@ -1485,6 +1485,41 @@ void launch_p2_to_ring(int32_t* ring, const int32_t* p2, const P2Job* jobs, int 
   static_assert(P2K >= RING, "the snapshot after a round of phase 2 is taken from the P2 rows alone");
   hipLaunchKernelGGL(wfa_p2_to_ring_kernel, dim3((unsigned)njobs * 2 * 5 * RING), dim3(256), 0, st, ring, p2, jobs);
 }
+// One thread per 16-byte chunk of a row of dst (grid: chunks x rows x jobs); a row is (direction, component, ring row), the same in
+// both geometries.  A chunk whose four diagonals all lie inside klo .. khi and inside src's row is one 16-byte load where the two
+// column offsets differ by a multiple of four (the host keeps them so: a narrow ring is cut off in whole chunks); anything else goes
+// element by element.  Off the steady-state path: a job takes it once per band it outgrows.
+__global__ __launch_bounds__(256) void wfa_ring_widen_kernel(const RingWidenJob* __restrict__ jobs) {
+  const RingWidenJob J = jobs[blockIdx.z];
+  const int64_t c0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;  // first column of the chunk in dst
+  if (c0 + 3 >= (int64_t)J.dst_w) return;                                   // (dst_w is a multiple of 4)
+  const int64_t row = blockIdx.y;
+  const int32_t* __restrict__ src = J.src + row * (int64_t)J.src_w;
+  int32_t* __restrict__ dst = J.dst + row * (int64_t)J.dst_w;
+  const int64_t delta = (int64_t)J.src_koff - J.dst_koff;                   // src column = dst column + delta
+  const int64_t k0 = c0 - J.dst_koff, s0 = c0 + delta;
+  int4 v = make_int4(WF_NULL, WF_NULL, WF_NULL, WF_NULL);
+  const bool inside = k0 >= J.klo && k0 + 3 <= J.khi && s0 >= 0 && s0 + 3 < (int64_t)J.src_w;
+  const bool aligned = ((delta & 3) == 0) && ((J.src_w & 3) == 0) && ((reinterpret_cast<uintptr_t>(J.src) & 15) == 0);
+  if (inside && aligned) {
+    v = *reinterpret_cast<const int4*>(src + s0);
+  } else {
+    int32_t e[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int64_t k = k0 + q, sc = s0 + q;
+      e[q] = (k >= J.klo && k <= J.khi && sc >= 0 && sc < (int64_t)J.src_w) ? src[sc] : WF_NULL;
+    }
+    v = make_int4(e[0], e[1], e[2], e[3]);
+  }
+  if ((reinterpret_cast<uintptr_t>(J.dst) & 15) == 0) *reinterpret_cast<int4*>(dst + c0) = v;
+  else { dst[c0] = v.x; dst[c0 + 1] = v.y; dst[c0 + 2] = v.z; dst[c0 + 3] = v.w; }
+}
+void launch_ring_widen(const RingWidenJob* jobs, int njobs, int max_dst_w, int ring_rows, hipStream_t st) {
+  if (njobs <= 0 || max_dst_w <= 0) return;
+  const unsigned chunks = (unsigned)((max_dst_w / 4 + 255) / 256);
+  hipLaunchKernelGGL(wfa_ring_widen_kernel, dim3(chunks, (unsigned)(2 * 5 * ring_rows), (unsigned)njobs), dim3(256), 0, st, jobs);
+}
 void launch_p2_blockmax(const int32_t* ring, const int32_t* p2, const P2Job* jobs, int32_t* bmax, int32_t* p2max, int njobs, hipStream_t st) {
   hipLaunchKernelGGL(wfa_p2_blockmax_kernel, dim3(njobs * 2 * P2ROWS), dim3(256), 0, st, ring, p2, jobs, bmax, p2max);
 }

@@ -78,7 +78,7 @@ static void usage() {
           "usage: wfmash-hip [options] target.fa [query.fa]\n"
           "  phases    -m approximate mappings only | -i FILE align mappings from FILE | (neither) map + align\n"
           "  mapping   -p PCT|aniN[+-X] identity [ani50-2]   -k INT k-mer [15]   -w INT window [1k]   -s INT sketch size [auto]\n"
-          "            -n INT|inf mappings per segment [inf]   -l INT block length [0]   -c INT chain jump [2k]   -P INT max length [50k]\n"
+          "            -n INT|inf mappings per segment [inf]   -l INT block length [0]   -c INT chain jump [2k]   -P INT|inf max length [50k]\n"
           "            -N no split   -M no merge   -f no filter   -o one-to-one   -O FLOAT max overlap [0.95]   -x FLOAT sparsify [1.0]\n"
           "            -H INT L1 hits [3]   -F FLOAT high-frequency filter [0.0002]   -b SIZE target batch [all]\n"
           "            --hg-filter n,D,conf hypergeometric filter [1.0,0.0,99.9]   --ani-sketch-size INT (no effect)\n"
@@ -171,7 +171,11 @@ int main(int argc, char** argv) {
     }
     else if (a == "-l" || a == "--block-length") mp.block_length = size("-l");
     else if (a == "-c" || a == "--chain-jump") mp.chain_gap = size("-c");
-    else if (a == "-P" || a == "--max-length") mp.max_mapping_length = (uint64_t)size("-P");
+    else if (a == "-P" || a == "--max-length") {  // parse_args.hpp:472-483: "inf" = no limit
+      if (i + 1 < argc && std::string(argv[i + 1]) == "inf") { ++i; mp.max_mapping_length = (uint64_t)std::numeric_limits<int64_t>::max(); }
+      else mp.max_mapping_length = (uint64_t)size("-P");
+      if (mp.max_mapping_length == 0) { fprintf(stderr, "[wfmash] ERROR: max mapping length must be greater than 0.\n"); return 1; }
+    }
     else if (a == "-N" || a == "--no-split") mp.split = 0;
     else if (a == "-M" || a == "--no-merge") mp.merge_mappings = 0;
     else if (a == "-f" || a == "--no-filter") mp.filter_mode = 3;

@@ -727,6 +727,7 @@ int do_biwfa_alignment_batch(wfm_handle_t* h, std::vector<BiwfaRecord>& recs, co
     bool tail_later = false;             // the scans overlap: the tail is scanned on the head-patched CIGAR
   };
   std::vector<Work> wk(n);
+  std::vector<char> over_budget(n, 0);  // WFM_ST_OOM: dropped like every record whose main alignment fails, but not silently
   {
     GpuBatch g;
     g.probs.reserve(n);
@@ -743,6 +744,7 @@ int do_biwfa_alignment_batch(wfm_handle_t* h, std::vector<BiwfaRecord>& recs, co
     for_each_record(n, nt, [&](size_t i) {
       BiwfaRecord& r = recs[i];
       r.ok = (g.res[i].status == 0);  // status != 0: the reference drops the record silently (wflign.cpp:150-152)
+      over_budget[i] = g.res[i].status == WFM_ST_OOM;
       r.score = g.res[i].score;
       r.tags = g.flags[i] & 0xffu;
       r.paf.clear();
@@ -757,6 +759,12 @@ int do_biwfa_alignment_batch(wfm_handle_t* h, std::vector<BiwfaRecord>& recs, co
   }
   if (stats)
     for (const auto& r : recs) stats->main_failed += !r.ok;
+  // (the one status the reference does not have: its memory follows the score as well, but has no budget to run out of)
+  for (size_t i = 0; i < n; ++i)
+    if (over_budget[i])
+      fprintf(stderr, "[wfmash] WARNING: %s:%llu-%llu -> %s:%llu-%llu not aligned: its wavefronts do not fit the device memory budget\n", recs[i].query_name.c_str(),
+              (unsigned long long)recs[i].query_offset, (unsigned long long)(recs[i].query_offset + recs[i].query_length), recs[i].target_name.c_str(),
+              (unsigned long long)recs[i].target_offset, (unsigned long long)(recs[i].target_offset + recs[i].target_length));
   const auto ts1 = now();
   size_t later = 0;
   if (!disable_chain_patching) {
