@@ -213,6 +213,22 @@ void wfm_set_concurrent_calls(wfm_handle_t* h, int other_calls);
 #define WFM_PF_RING_GROWN 256u   /* the full ring of the root or of a child did not fit the budget: it ran on rings grown with its score   */
 size_t wfm_get_problem_flags(const wfm_handle_t* h, uint32_t* out, size_t n);
 
+/* Which paths the BiWFA tile phase took in the handle's LAST align call, summed over the call's parts and streams (a
+ * diagnostic channel like the flags above: the block-boundary tests assert from it that the path they aim at ran).  Fills
+ * out[0 .. min(n, WFM_TILE_COUNTERS)) in the order below; out may be NULL; returns WFM_TILE_COUNTERS. */
+enum {
+  WFM_TC_JOBS = 0,          /* jobs that entered the tile phase (a job that goes on from a snapshot on a wider ring enters again) */
+  WFM_TC_EXACT_ENDS = 1,    /* jobs that left it stopped exactly at their meeting point                                          */
+  WFM_TC_FINE_RERUNS = 2,   /* meeting blocks found with one maximum per block and run again with per-score maxima               */
+  WFM_TC_GAP_RERUNS = 3,    /* blocks before a short run up to the meeting point run again for their gap rows                    */
+  WFM_TC_RING3 = 4,         /* jobs that held a third ring                                                                       */
+  WFM_TC_BLOCKS_COARSE = 5, /* blocks launched with the packed tile kernel's instantiation without per-score maxima              */
+  WFM_TC_BLOCKS_FINE = 6,   /* blocks launched with the one that keeps them                                                      */
+  WFM_TC_LEFT_BAND = 7,     /* jobs that left out of their band or out of their score bound                                      */
+  WFM_TILE_COUNTERS = 8
+};
+size_t wfm_get_tile_counters(const wfm_handle_t* h, uint64_t* out, size_t n);
+
 /* Device blocks of both paths -- the map path's work buffers, the align path's arenas and a batch's sequence buffers, also
  * those of a handle that has been destroyed -- come from one heap per device and go back to it (wfmash_amd/csrc/dev_cache.h: an
  * address range reserved at the first wfm_create of the device, 1 GB chunks mapped behind what is there, WFM_POOL_GB -- 24 -- at once;

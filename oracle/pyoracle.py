@@ -66,6 +66,8 @@ def lib():
         L.wfo_find_breakpoint_rounds.argtypes = [cp, ci, cp, ci, PP, ci, ci, ci, ci, C.POINTER(Breakpoint), C.POINTER(ci), SP]
         L.wfo_find_breakpoint_bounded.restype = ci
         L.wfo_find_breakpoint_bounded.argtypes = [cp, ci, cp, ci, PP, ci, ci, ci, C.POINTER(Breakpoint), SP]
+        L.wfo_meet_point.restype = ci
+        L.wfo_meet_point.argtypes = [cp, ci, cp, ci, PP, ci, ci, C.POINTER(C.c_int32)]
         L.wfo_ops_score.restype = C.c_int64
         L.wfo_ops_score.argtypes = [cp, ci, PP]
         L.wfo_ops_check.restype = ci
@@ -146,6 +148,17 @@ def find_breakpoint_rounds(pattern: bytes, text: bytes, tests_per_round: int, su
     rc = lib().wfo_find_breakpoint_rounds(pattern, len(pattern), text, len(text), C.byref(p), comp_begin, comp_end, sub, tests_per_round,
                                           C.byref(bp), C.byref(rounds), C.byref(st))
     return rc, bp, rounds.value
+
+
+def meet_point(pattern: bytes, text: bytes, pen=None, comp_begin=0, comp_end=0):
+    """where the first loop of the breakpoint search ends (the directions' largest antidiagonals have met) -> (sf, sr, last_fwd);
+    (0, 0, 0) where that is before the first step"""
+    p = _pen(pen)
+    m = (C.c_int32 * 3)()
+    rc = lib().wfo_meet_point(pattern, len(pattern), text, len(text), C.byref(p), comp_begin, comp_end, m)
+    if rc < 0:
+        raise RuntimeError("wfo_meet_point: status %d" % rc)
+    return int(m[0]), int(m[1]), int(m[2])
 
 
 def ops_score(ops: bytes, pen=None) -> int:

@@ -591,21 +591,23 @@ static void overlap(const al_t* a0, const al_t* a1, int s0, int s1, int fwd0, wf
 /* wavefront_bialign_find_breakpoint */
 static int find_breakpoint_sub(const char* p, int plen, const char* t, int tlen, const wfo_penalties_t* pen,
                                int comp_begin, int comp_end, wfo_breakpoint_t* bp, wfo_stats_t* st, int bounded, int sub,
-                               int tests_per_round, int* rounds_out);
+                               int tests_per_round, int* rounds_out, int32_t* meet_out);
 static int find_breakpoint(const char* p, int plen, const char* t, int tlen, const wfo_penalties_t* pen,
                            int comp_begin, int comp_end, wfo_breakpoint_t* bp, wfo_stats_t* st) {
-  return find_breakpoint_sub(p, plen, t, tlen, pen, comp_begin, comp_end, bp, st, 0, 0, 0, NULL);
+  return find_breakpoint_sub(p, plen, t, tlen, pen, comp_begin, comp_end, bp, st, 0, 0, 0, NULL, NULL);
 }
 /* bounded != 0: the product's form of the search under an upper bound `sub` of the score -- rows cut as above, and the
  * second loop starts as if a breakpoint of score sub + 1 were in hand.  Returns ST_OK with bp->score <= sub, or
  * ST_UNREACHABLE when nothing lies within the bound. */
+/* meet_out != NULL: the search ends where its first loop does -- the two directions' largest antidiagonals have met -- and
+ * meet_out receives (sf, sr, last_fwd) of that exit; (0, 0, 0) where they meet before the first step.  bp is not filled. */
 /* tests_per_round > 0: the product's phase 2 in rounds (wfa_host.hip, run_p2_phase / wfa_p2_overlap_kernel): after that many
  * tests the walk is cut -- what it has taken so far is set aside, the next round starts "as if a breakpoint of that score
  * were in hand" with an empty record of its own, and when the loop ends in a round that took nothing the one set aside
  * stands (WFM_DEV_P2_NOTHING). */
 static int find_breakpoint_sub(const char* p, int plen, const char* t, int tlen, const wfo_penalties_t* pen,
                                int comp_begin, int comp_end, wfo_breakpoint_t* bp, wfo_stats_t* st, int bounded, int sub,
-                               int tests_per_round, int* rounds_out) {
+                               int tests_per_round, int* rounds_out, int32_t* meet_out) {
   al_t f, r;
   wfo_breakpoint_t carry;
   int have_carry = 0, tests = 0, rounds = 1;
@@ -623,6 +625,7 @@ static int find_breakpoint_sub(const char* p, int plen, const char* t, int tlen,
   int sf = 0, sr = 0, fmax = 0, rmax = 0, mak = 0, fin;
   bp->score = bounded ? sub + 1 : INT_MAX;
   bp->component = -1;
+  if (meet_out) meet_out[0] = meet_out[1] = meet_out[2] = 0;
   fin = extend_step(&f, sf, &fmax, 1);
   if (fin == 1) { al_free(&f); al_free(&r); return ST_END_REACHED; }
   fin = extend_step(&r, sr, &rmax, 1);
@@ -645,6 +648,7 @@ static int find_breakpoint_sub(const char* p, int plen, const char* t, int tlen,
     if ((int64_t)sf + sr > max_steps) { rc = ST_UNREACHABLE; goto done; }
     if (bounded && 2 * sf > sub + 128) { rc = ST_UNREACHABLE; goto done; }  /* the product gives up here too */
   }
+  if (meet_out) { meet_out[0] = sf; meet_out[1] = sr; meet_out[2] = last_fwd; goto done; }
   {
     const int scope = f.scope;
     const int gopen = MAXI(pen->o1, pen->o2);
@@ -752,13 +756,19 @@ int wfo_find_breakpoint(const char* pattern, int plen, const char* text, int tle
 int wfo_find_breakpoint_bounded(const char* pattern, int plen, const char* text, int tlen,
                                 const wfo_penalties_t* pen, int comp_begin, int comp_end, int sub,
                                 wfo_breakpoint_t* bp, wfo_stats_t* stats) {
-  return find_breakpoint_sub(pattern, plen, text, tlen, pen, comp_begin, comp_end, bp, stats, 1, sub, 0, NULL);
+  return find_breakpoint_sub(pattern, plen, text, tlen, pen, comp_begin, comp_end, bp, stats, 1, sub, 0, NULL, NULL);
 }
 
 int wfo_find_breakpoint_rounds(const char* pattern, int plen, const char* text, int tlen,
                                const wfo_penalties_t* pen, int comp_begin, int comp_end, int sub, int tests_per_round,
                                wfo_breakpoint_t* bp, int* rounds, wfo_stats_t* stats) {
-  return find_breakpoint_sub(pattern, plen, text, tlen, pen, comp_begin, comp_end, bp, stats, sub >= 0, sub >= 0 ? sub : 0, tests_per_round, rounds);
+  return find_breakpoint_sub(pattern, plen, text, tlen, pen, comp_begin, comp_end, bp, stats, sub >= 0, sub >= 0 ? sub : 0, tests_per_round, rounds, NULL);
+}
+
+int wfo_meet_point(const char* pattern, int plen, const char* text, int tlen,
+                   const wfo_penalties_t* pen, int comp_begin, int comp_end, int32_t* meet) {
+  wfo_breakpoint_t bp;
+  return find_breakpoint_sub(pattern, plen, text, tlen, pen, comp_begin, comp_end, &bp, NULL, 0, 0, 0, NULL, meet);
 }
 
 int wfo_align_end2end_biwfa(const char* pattern, int plen, const char* text, int tlen,

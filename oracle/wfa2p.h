@@ -115,6 +115,14 @@ int wfo_find_breakpoint_rounds(const char* pattern, int plen, const char* text, 
                                const wfo_penalties_t* pen, int comp_begin, int comp_end, int sub, int tests_per_round,
                                wfo_breakpoint_t* bp, int* rounds, wfo_stats_t* stats);
 
+/* Where the breakpoint search's first loop ends: the loop alternates a forward and a reverse step and leaves as soon as the
+ * two directions' largest antidiagonals sum to plen + tlen - 1 (the condition the product's tile phase replays block by
+ * block).  meet[0..2] = (sf, sr, last_fwd): the scores the two directions stand at and whether the forward step was the
+ * last one; (0, 0, 0) where they meet before any step.  Returns what wfo_find_breakpoint would at that point (0, or 1 if
+ * the end was reached at score 0, < 0 on error). */
+int wfo_meet_point(const char* pattern, int plen, const char* text, int tlen,
+                   const wfo_penalties_t* pen, int comp_begin, int comp_end, int32_t* meet);
+
 /* Score implied by an op string under the reference's cost model
  * (wflign_alignment.cpp:680-722: a gap run of length L costs
  * o1+e1+min(e1*(L-1), o2+e2*(L-1)) ... note this equals min(o1+L*e1,o2+o1... )

@@ -228,3 +228,53 @@ def test_cutting_the_overlap_loop_into_rounds_does_not_change_the_breakpoint(ora
                 multi += rounds > 1
                 checked += 1
     assert checked > 900 and multi > 600, (checked, multi)
+
+
+# ---- the meeting point of the two directions (wfo_meet_point): what the product's tile phase replays block by block
+
+
+def _with_subs(p, K):
+    a = bytearray(p)
+    for i in range(K):
+        pos = (2 * i + 1) * len(p) // (2 * K)
+        a[pos:pos + 1] = a[pos:pos + 1].translate(bytes.maketrans(b"ACGT", b"CGTA"))
+    return bytes(a)
+
+
+def test_meet_point_of_evenly_spaced_substitutions(oracle):
+    """K evenly spaced substitutions in 4000 bases, default penalties: each direction pays 5 per substitution it passes, the forward
+    one steps first, and the loop ends when the two have paid all K between them -- sf = 5 ceil(K / 2), sr = sf - (K odd)."""
+    p = synth.random_dna(0x3E37, 4000)
+    assert oracle.meet_point(p, _with_subs(p, 41)) == (105, 104, 1)
+    assert oracle.meet_point(p, _with_subs(p, 42)) == (105, 105, 0)
+    for K in range(1, 170):
+        sf = 5 * ((K + 1) // 2)
+        assert oracle.meet_point(p, _with_subs(p, K)) == (sf, sf - K % 2, K % 2), K
+    assert oracle.meet_point(p, p) == (0, 0, 0)  # met before the first step
+
+
+def test_meet_point_against_the_breakpoint(oracle):
+    """Any penalties, any begin / end components: sf - sr is 0 or 1, and 1 exactly when the forward step was the last.  The
+    breakpoint is found by the second loop, which goes on from the meeting point: every overlap test pairs the wavefront of the
+    step at hand (a score >= the meeting point's) with wavefronts of the other direction up to scope - 1 scores behind ITS step
+    -- so one of the breakpoint's two scores is at or beyond the meeting point and the other less than a scope short of it."""
+    rng = random.Random(5)
+    n = 0
+    for i in range(200):
+        L = rng.choice([130, 300, 700, 1500])
+        p = synth.random_dna(1000 + i, L)
+        t = synth.mutate(p, rng.choice([0.01, 0.05, 0.15, 0.3]), 77 + i)
+        pen = rng.choice([None, (4, 6, 2, 12, 1), (3, 4, 2, 24, 1)])
+        cb, ce = rng.choice([(0, 0), (0, 0), (1, 0), (0, 3), (2, 4), (4, 1)])
+        sf, sr, last_fwd = oracle.meet_point(p, t, pen, cb, ce)
+        assert sf - sr in (0, 1) and sf - sr == last_fwd
+        rc, bp, _ = oracle.find_breakpoint(p, t, cb, ce, pen)
+        if rc != 0:
+            assert (sf, sr) == (0, 0)
+            continue
+        n += 1
+        x, o1, e1, o2, e2 = pen or oracle.DEFAULT_PEN
+        scope = max(x, o1 + e1, o2 + e2) + 1
+        assert (bp.score_forward >= sf and bp.score_reverse > sr - scope) or (bp.score_reverse >= sr and bp.score_forward > sf - scope), \
+            (sf, sr, bp.score_forward, bp.score_reverse)
+    assert n >= 180

@@ -20,6 +20,8 @@ DEFAULT_PEN = (5, 8, 2, 24, 1)  # parse_args.hpp:290-294
 # wfm_get_problem_flags (include/wfmash_hip.h): which of the rarer paths a problem took
 WFM_PF_ROOT_AGAIN, WFM_PF_JOB_AGAIN, WFM_PF_BASE_RETRY, WFM_PF_BASE_RETRY2, WFM_PF_BYTE_KERNEL, WFM_PF_P2_ROUNDS, WFM_PF_RING_KERNEL, WFM_PF_BASE_TILES = 1, 2, 4, 8, 16, 32, 64, 128
 WFM_PF_RING_GROWN = 256
+# wfm_get_tile_counters (include/wfmash_hip.h): the paths the BiWFA tile phase took in an align call, in the header's order
+TILE_COUNTERS = ("jobs", "exact_ends", "fine_reruns", "gap_reruns", "ring3", "blocks_coarse", "blocks_fine", "left_band")
 
 EXPORTS = [
     "wfm_create", "wfm_destroy", "wfm_last_error", "wfm_device_name",
@@ -31,6 +33,7 @@ EXPORTS = [
     "wfm_prefilter_kmers", "wfm_index_build_sequences", "wfm_index_upload",
     "wfm_index_replicate", "wfm_device_count", "wfm_finish_records",
     "wfm_align_batch_rle", "wfm_align_resident_rle", "wfm_free_runs", "wfm_score_bounds", "wfm_get_busy_intervals", "wfm_trim_device_cache", "wfm_map_fragments_ordered", "wfm_map_sequence_cache", "wfm_selftest_dpp", "wfm_selftest_arena_growth", "wfm_set_concurrent_calls", "wfm_get_problem_flags",
+    "wfm_get_tile_counters",
     "wfm_streaming_minmers", "wfm_index_build_streaming",
 ]
 
@@ -295,6 +298,16 @@ class Handle:
         out = np.zeros(max(n, 1), dtype=np.uint32)
         have = f(self._p, out.ctypes.data, n)
         return out[:min(n, have)]
+
+    def tile_counters(self):
+        """wfm_get_tile_counters: which paths the tile phase took in the handle's last align call, by the names of TILE_COUNTERS."""
+        f = self._L.wfm_get_tile_counters
+        f.restype = C.c_size_t
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        out = np.zeros(len(TILE_COUNTERS), dtype=np.uint64)
+        have = f(self._p, out.ctypes.data, len(out))
+        assert have == len(TILE_COUNTERS), have
+        return {k: int(v) for k, v in zip(TILE_COUNTERS, out)}
 
     def upload(self, items):
         return SeqSet(self, items)

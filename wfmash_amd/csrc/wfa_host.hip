@@ -189,6 +189,7 @@ struct wfm_handle {
   size_t mem_budget = 0;       // arena budget in force for the call at hand
   size_t mem_budget_full = 0;  // the handle's whole budget (40 % of free HBM at creation, or WFM_MEM_BUDGET_MB)
   wfm_stats_t stats{};
+  uint64_t tile_ctr[WFM_TILE_COUNTERS] = {};  // which paths the tile phase took in the last align call (wfm_get_tile_counters)
   DevBuf<int32_t> ring;      // breakpoint rings
   DevBuf<int32_t> base32;    // base: pre + rings
   DevBuf<uint8_t> base8;     // base: bt
@@ -621,7 +622,9 @@ int run_tiled_phase(wfm_handle* h, wfm_seqset* S, const DevPen& dp, int scope, c
     // 26 deep from any snapshot
     t.ring_prev = (ring3 && i < ring3->size() && (*ring3)[i] >= 0 && (j.packed & 1) && cfg.reg && cfg.exact && !refine) ? (*ring3)[i] : -1;
     t.prev_ok = 0; t.reran = 0;
+    h->tile_ctr[WFM_TC_RING3] += t.ring_prev >= 0;
   }
+  if (!refine || T == cfg.T) h->tile_ctr[WFM_TC_JOBS] += n;  // (a WFM_TILE_T_REFINE pass goes on with jobs already counted; a resumed job enters)
   bool any_cut = false;  // the kernel form with the score bounds' bookkeeping is only launched when a job carries one
   for (size_t i = 0; i < n; ++i) any_cut |= tj[i].sub != SUB_NONE;
   if (h->tilejobs.ensure(n) || h->tilemak.ensure(n * 2 * (size_t)std::max(T, 2))) { h->err = "out of device memory (tiles)"; return WFM_E_NOMEM; }
@@ -713,7 +716,7 @@ int run_tiled_phase(wfm_handle* h, wfm_seqset* S, const DevPen& dp, int scope, c
         }
         if (wb[(size_t)chunk - 1] <= cfg.threads * cfg.C) {
           // one tile per job-direction: whole waves, as many as the block's own widest range needs (two diagonals per lane)
-          static const bool fine = !(getenv("WFM_TILE_FINE") && atoi(getenv("WFM_TILE_FINE")) == 0);
+          const bool fine = !(getenv("WFM_TILE_FINE") && atoi(getenv("WFM_TILE_FINE")) == 0);  // (per call, like the score-bound switches: the tests run both forms in one process)
           for (int b = 0; b < chunk; ++b) {
             const int wdt = fine ? wb[(size_t)b] : wb[(size_t)chunk - 1];
             threads_b[(size_t)b] = fine ? std::min(cfg.threads, std::max(64, ((wdt + cfg.C - 1) / cfg.C + 63) / 64 * 64))
@@ -761,7 +764,11 @@ int run_tiled_phase(wfm_handle* h, wfm_seqset* S, const DevPen& dp, int scope, c
       for (int b = 0; b < chunk; ++b) {
         HIPCHK(h, hipEventRecord(h->tile_ev[2 * b], h->stream));
         if (cfg.reg) {
-          if (n_pk) launch_tile2(S->d_pk, h->ring.p, h->tilejobs.p, h->tiletasks.p, h->tilemak.p, (int)n_pk, threads_b[(size_t)b], T, variants_b[(size_t)b], h->stream);
+          if (n_pk) {
+            launch_tile2(S->d_pk, h->ring.p, h->tilejobs.p, h->tiletasks.p, h->tilemak.p, (int)n_pk, threads_b[(size_t)b], T, variants_b[(size_t)b], h->stream);
+            h->tile_ctr[WFM_TC_BLOCKS_COARSE] += (variants_b[(size_t)b] & 1) != 0;
+            h->tile_ctr[WFM_TC_BLOCKS_FINE] += (variants_b[(size_t)b] & 2) != 0;
+          }
           if (tasks.size() > n_pk)
             launch_tile_reg(S->d_seq, h->ring.p, h->tilejobs.p, h->tiletasks.p + n_pk, h->tilemak.p, (int)(tasks.size() - n_pk), threads_b[(size_t)b], T, cfg.C, any_cut, h->stream);
         } else launch_tile(S->d_seq, h->ring.p, h->tilejobs.p, h->tiletasks.p, h->tilemak.p, (int)tasks.size(), cfg.threads, T, cfg.Wt, lds, dp, scope, ring_rows_for(scope), h->stream);
@@ -798,10 +805,14 @@ int run_tiled_phase(wfm_handle* h, wfm_seqset* S, const DevPen& dp, int scope, c
             tile_cells += (uint64_t)h_cells_sum(tj[i].pl, tj[i].tl, tj[i].sub, base + 1, base + steps);
           }
         }
-        if (got[i].fine_s == -1 && tj[i].fine_s != -1)  // the block in which the directions met ran once more, for its per-score maxima (TileJob::fine_s)
+        if (got[i].fine_s == -1 && tj[i].fine_s != -1) {  // the block in which the directions met ran once more, for its per-score maxima (TileJob::fine_s)
           for (int d = 0; d < 2; ++d) tile_cells += (uint64_t)h_cells_sum(tj[i].pl, tj[i].tl, tj[i].sub, got[i].s0 + 1, got[i].s0 + T);
-        if (got[i].reran > tj[i].reran)  // the block before the meeting block ran once more, for its gap rows (TileJob::ring_prev)
+          h->tile_ctr[WFM_TC_FINE_RERUNS] += 1;
+        }
+        if (got[i].reran > tj[i].reran) {  // the block before the meeting block ran once more, for its gap rows (TileJob::ring_prev)
           for (int d = 0; d < 2; ++d) tile_cells += (uint64_t)h_cells_sum(tj[i].pl, tj[i].tl, tj[i].sub, got[i].s0 - T + 1, got[i].s0);
+          h->tile_ctr[WFM_TC_GAP_RERUNS] += (uint64_t)(got[i].reran - tj[i].reran);
+        }
         tj[i] = got[i];
         active[i] = (char)(got[i].active != 0);
         fmax[i] = got[i].fmax; rmax[i] = got[i].rmax;
@@ -827,6 +838,8 @@ int run_tiled_phase(wfm_handle* h, wfm_seqset* S, const DevPen& dp, int scope, c
     ring2[i] = tj[i].ring_out;
     j.resume_s = tj[i].s0;
     j.resume_sr = -1; j.last_fwd = 0;
+    h->tile_ctr[WFM_TC_EXACT_ENDS] += tj[i].mode == 2;
+    h->tile_ctr[WFM_TC_LEFT_BAND] += tj[i].mode == 3;
     if (tj[i].mode == 3) {  // ran out of its band: wfa_bp_kernel reports WFM_DEV_BAND
       // (where it stands, for the host: a job that goes on from this snapshot on a wider ring resumes at resume_sr with these maxima)
       j.resume_s = -3; j.resume_sr = tj[i].s0; j.fmax0 = fmax[i]; j.rmax0 = rmax[i];
@@ -1017,6 +1030,7 @@ int align_resident_impl(wfm_handle* h, const wfm_penalties_t* pen, wfm_seqset* S
   HIPCHK(h, hipSetDevice(h->device));
   const size_t n = last - first;
   h->stats = wfm_stats_t{};
+  std::fill(h->tile_ctr, h->tile_ctr + WFM_TILE_COUNTERS, (uint64_t)0);
   if (n == 0) return 0;
   const DevPen dp{pen->x, pen->o1, pen->e1, pen->o2, pen->e2};
 
@@ -1107,7 +1121,8 @@ int align_resident_impl(wfm_handle* h, const wfm_penalties_t* pen, wfm_seqset* S
   std::vector<int> tiled;
   std::vector<int64_t> ring2, ring3;
   std::vector<size_t> ring_third;  // elements of one ring of every tiled job of the chunk
-  static const bool ring3_on = !(getenv("WFM_TILE_RING3") && atoi(getenv("WFM_TILE_RING3")) == 0);
+  const bool ring3_on = !(getenv("WFM_TILE_RING3") && atoi(getenv("WFM_TILE_RING3")) == 0);  // (these, too, per call: one process runs both forms)
+  const bool p2_on = !(getenv("WFM_P2") && atoi(getenv("WFM_P2")) == 0);
   std::vector<int32_t> fine_from;
   const int fine_margin = getenv("WFM_TILE_FINE_MARGIN") ? atoi(getenv("WFM_TILE_FINE_MARGIN")) : 48;
   const int coarse_min_blocks = getenv("WFM_TILE_COARSE_MIN_BLOCKS") ? atoi(getenv("WFM_TILE_COARSE_MIN_BLOCKS")) : 32;
@@ -1374,7 +1389,6 @@ int align_resident_impl(wfm_handle* h, const wfm_penalties_t* pen, wfm_seqset* S
         std::vector<char> has_carry;
         std::vector<int> more_set;
         {
-          static const bool p2_on = !(getenv("WFM_P2") && atoi(getenv("WFM_P2")) == 0);
           std::vector<int> cand;
           std::vector<int64_t> other;
           std::vector<char> is_cand(jobs.size(), 0);
@@ -1809,6 +1823,12 @@ size_t wfm_get_problem_flags(const wfm_handle_t* h, uint32_t* out, size_t n) {
   return have;
 }
 
+size_t wfm_get_tile_counters(const wfm_handle_t* h, uint64_t* out, size_t n) {
+  if (!h) return 0;
+  if (out) for (size_t i = 0; i < n && i < (size_t)WFM_TILE_COUNTERS; ++i) out[i] = h->tile_ctr[i];
+  return (size_t)WFM_TILE_COUNTERS;
+}
+
 int wfm_device_name(const wfm_handle_t* h, char* buf, size_t buflen) {
   if (!h || !buf || !buflen) return WFM_E_ARG;
   snprintf(buf, buflen, "%s", h->name.c_str());
@@ -2126,6 +2146,7 @@ int align_resident_any(wfm_handle_t* h, const wfm_penalties_t* pen, wfm_seqset_t
     a.p2_launches += b.p2_launches; a.p2_jobs += b.p2_jobs; a.p2_more += b.p2_more;
     a.cells_tile += b.cells_tile; a.ms_tile += b.ms_tile; a.tile_launches += b.tile_launches; a.tile_tasks += b.tile_tasks;
     a.cells_tile_unique += b.cells_tile_unique;
+    for (int c = 0; c < WFM_TILE_COUNTERS; ++c) h->tile_ctr[c] += h->peers[k - 1]->tile_ctr[c];
     iv.insert(iv.end(), h->peers[k - 1]->tile_iv.begin(), h->peers[k - 1]->tile_iv.end());
     ivb.insert(ivb.end(), h->peers[k - 1]->bp_iv.begin(), h->peers[k - 1]->bp_iv.end());
     ivs.insert(ivs.end(), h->peers[k - 1]->base_iv.begin(), h->peers[k - 1]->base_iv.end());
