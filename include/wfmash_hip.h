@@ -26,6 +26,8 @@
  *                              std::sort by (wpos, wpos_end) with the library's tie order, std::unique)
  *     wfm_index_build       <- Sketch::build (index stage), winSketch.hpp:266-429
  *     wfm_index_build_sequences <- Sketch::build as a whole, winSketch.hpp:175-457
+ *     wfm_sketch_part / wfm_index_build_parts <- the same in two steps: buildHelper per sequence (winSketch.hpp:200-239) on
+ *                              the device that holds the sequence, the index stage (:266-429) once on the union
  *     wfm_index_replicate   <- (the one Sketch all mapping threads share, computeMap.hpp:431-484: one copy per GPU)
  *     wfm_index_upload / wfm_index_download <- Sketch::readIndex / writeIndex (device side), winSketch.hpp:569-866
  *     wfm_map_l1            <- getSeedIntervalPoints + computeL1CandidateRegions, mappingCore.hpp:82-301
@@ -341,6 +343,38 @@ int64_t wfm_add_minmers_multi(wfm_handle_t* h, const char* const* seqs, const in
 int wfm_index_build_sequences(wfm_handle_t* h, const char* const* seqs, const int64_t* lens, const int32_t* seq_ids,
                               int64_t nseq, int k, int w, int s, int threads, double max_kmer_freq,
                               wfm_index_t** out, int64_t* n_windows);
+
+/* Sketch::build split at its seam, for a target subset whose sequences are sketched on several GPUs of the node
+ * (wfmh_map_multi): the records of a share of the sequences stay on the device that made them (a part), and the index
+ * stage runs once on the union of all parts.
+ *
+ * wfm_sketch_part: wfm_add_minmers_multi's pipeline with the records left on h's device (one block of the device heap),
+ * grouped by sequence in input order; a sequence shorter than k contributes 0 records.  The part outlives the call's
+ * work buffers and may outlive h; release it with wfm_minmer_part_free. */
+typedef struct wfm_minmer_part wfm_minmer_part_t;
+int  wfm_sketch_part(wfm_handle_t* h, const char* const* seqs, const int64_t* lens, const int32_t* seq_ids, int64_t nseq,
+                     int k, int w, int s, int threads, wfm_minmer_part_t** out);
+/* *n_records (optional) = records of the part; counts (optional) receives min(cap, sequences) per-sequence counts.
+ * Returns the number of sequences or a WFM_E_* code. */
+int64_t wfm_minmer_part_info(const wfm_minmer_part_t* part, int64_t* n_records, int64_t* counts, int64_t cap);
+/* The records on the host (up to cap of them), grouped by sequence in the part's order; h: any handle, it carries the
+ * error message.  Returns the number of records (may exceed cap) or a WFM_E_* code. */
+int64_t wfm_minmer_part_download(wfm_handle_t* h, const wfm_minmer_part_t* part, wfm_minmer_t* out, int64_t cap);
+void wfm_minmer_part_free(wfm_minmer_part_t* part);
+
+/* The index stage on the union of parts: order[i] names the i-th sequence of the union (the reference's minmerIndex
+ * order: subset order), a sequence of a part at most once.  The index equals wfm_index_build_sequences on the sequences
+ * in that order.  Parts on h's own device are read where they lie; a part on another device comes over through a pinned
+ * host buffer (device-to-host on its device, host-to-device on h's stream, in chunks, the two overlapped -- no copy
+ * between the two devices' heaps).  A segmented gather (WFM_GATHER_TILE destination records per workgroup) then lays
+ * the sequences' records end to end; one part on h's device whose named records already lie end to end is read in
+ * place instead.  *n_windows (optional) = records of the union; when it is 0 no index is made and *out stays NULL.
+ * (WFM_INDEX_STAGE_ALL=1, read per call: parts on h's own device take the staging path as well -- a test switch for
+ * nodes with one GPU; WFM_INDEX_STAGE_CHUNK: records per staged chunk, 1024 .. 2^18, the default.) */
+typedef struct { int32_t part; int32_t seq; } wfm_part_seq_t;
+#define WFM_GATHER_TILE 2048
+int  wfm_index_build_parts(wfm_handle_t* h, const wfm_minmer_part_t* const* parts, int nparts, const wfm_part_seq_t* order,
+                           int64_t norder, double max_kmer_freq, wfm_index_t** out, int64_t* n_windows);
 
 /* The k-mers of a sequence that wfm_add_minmers_multi lets its host workers see: valid k-mers whose hash
  * is under the threshold that lets c_factor * s of a window's w-k+1 k-mers through, plus every valid k-mer of a window that may hold

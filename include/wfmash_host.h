@@ -203,6 +203,12 @@ typedef struct {
   double   ms_replicate;    /* copying the finished index to the other GPUs (wfmh_map_multi) */
   double   ms_identity;     /* the identity estimate (-p aniN: reading every sequence once + one MinHash per sequence on the device) */
   double   ms_wall;         /* the whole call: identity estimate, reading the sequences, index, mapping, post-processing, output */
+  int32_t  index_parts;     /* the most handles that sketched one target subset (wfmh_map_multi deals a subset's sequences over its
+                               handles): 1 = every subset on handles[0] alone, 0 = no subset was sketched (-I) */
+  int32_t  pad_;
+  double   ms_index_sketch; /* part of ms_index: the sketching of the subset's parts, the slowest part's wall time, summed over subsets
+                               (0 where handles[0] built alone) */
+  double   ms_index_merge;  /* part of ms_index: bringing the parts to handles[0]'s device and into subset order (staging + gather) */
 } wfmh_map_summary_t;
 
 /* The map phase on files: replaces skch::Map's constructor + mapQuery()
@@ -213,11 +219,20 @@ typedef struct {
 int wfmh_map(wfm_handle_t* h, const char* target_fasta, const char* query_fasta, const char* out_paf,
              const wfmh_map_params_t* params, wfmh_map_summary_t* summary);
 
-/* The same over n GPUs of one node: the index of a target subset is built once (handles[0]) and copied to the other
- * devices (wfm_index_replicate), batches of whole query sequences go to whichever device is free (one task per query
- * in the reference, computeMap.hpp:527-688), records are written in query order as with one GPU. */
+/* The same over n GPUs of one node.  The sequences of a target subset are dealt over the handles (longest first onto the
+ * least loaded, ties to the lower index), every handle sketches its share (wfm_sketch_part), the records meet on
+ * handles[0]'s device where the index stage runs once on the union in subset order (wfm_index_build_parts), and the
+ * finished index is copied to the other devices (wfm_index_replicate): the index, and with it every PAF byte and every
+ * -W index file, is that of one handle.  --streaming-minhash records are made on the host and stay with handles[0], as does
+ * everything with WFM_INDEX_SHARDED=0 (read per call; =1 takes the two-step path with a single handle too, which then reports
+ * ms_index_sketch).  Batches of whole query sequences go to whichever device is free
+ * (one task per query in the reference, computeMap.hpp:527-688), records are written in query order as with one GPU. */
 int wfmh_map_multi(wfm_handle_t* const* handles, int n, const char* target_fasta, const char* query_fasta, const char* out_paf,
                    const wfmh_map_params_t* params, wfmh_map_summary_t* summary);
+
+/* Test hook (no GPU needed): the deal of wfmh_map_multi's index build.  out_part[i] = the part (0 .. n_parts - 1) that item i of
+ * lengths[0 .. n) goes to.  Returns 0 or WFM_E_ARG. */
+int wfmh_test_deal(const int64_t* lengths, int64_t n, int n_parts, int32_t* out_part);
 
 /* External seeds (-K, parse_args.hpp:78,771-773; skch::ExternalSeeder, src/map/include/externalSeeder.hpp) in place of the
  * MinHash mapper: the PAF records of another tool (seeds_paf; "-" or "/dev/stdin" = standard input) grouped by query, each query's

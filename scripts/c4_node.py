@@ -47,7 +47,8 @@ def main():
                 s = capi.map_paf_multi(hs, fa, m, params=capi.map_default_params(threads=threads))
                 map_s = time.time() - t0
                 out = {"gpus": n, "devices": min(n, ndev), "haps": a.haps, "target_bp": int(s.target_bp), "threads": threads, "gen_s": round(gen_s, 1),
-                       "map_wall_s": round(map_s, 3), "ms_index": round(s.ms_index), "ms_replicate": round(s.ms_replicate), "ms_map": round(s.ms_map),
+                       "map_wall_s": round(map_s, 3), "ms_index": round(s.ms_index), "index_parts": int(s.index_parts), "ms_index_sketch": round(s.ms_index_sketch, 1),
+                       "ms_index_merge": round(s.ms_index_merge, 1), "index_windows": int(s.index_windows), "ms_replicate": round(s.ms_replicate), "ms_map": round(s.ms_map),
                        "ms_filter": round(s.ms_filter), "records": int(s.written), "pct": round(float(s.percentage_identity), 4)}
                 digest = hashlib.sha256(open(m, "rb").read()).hexdigest()
                 if a.align:

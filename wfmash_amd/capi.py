@@ -35,6 +35,7 @@ EXPORTS = [
     "wfm_align_batch_rle", "wfm_align_resident_rle", "wfm_free_runs", "wfm_score_bounds", "wfm_get_busy_intervals", "wfm_trim_device_cache", "wfm_map_fragments_ordered", "wfm_map_sequence_cache", "wfm_selftest_dpp", "wfm_selftest_arena_growth", "wfm_set_concurrent_calls", "wfm_get_problem_flags",
     "wfm_get_tile_counters",
     "wfm_streaming_minmers", "wfm_index_build_streaming",
+    "wfm_sketch_part", "wfm_minmer_part_info", "wfm_minmer_part_download", "wfm_minmer_part_free", "wfm_index_build_parts",
 ]
 
 
@@ -254,6 +255,56 @@ class Index:
             pass
 
 
+GATHER_TILE = 2048  # WFM_GATHER_TILE (include/wfmash_hip.h): destination records per workgroup of wfm_index_build_parts' gather
+
+
+class MinmerPart:
+    """wfm_minmer_part_t: the records of some sequences, resident on the device of the handle that sketched them."""
+
+    def __init__(self, handle, ptr):
+        self._h, self._p = handle, ptr
+
+    def info(self):
+        """wfm_minmer_part_info: (number of records, per-sequence counts)."""
+        f = self._h._L.wfm_minmer_part_info
+        f.restype = C.c_int64
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_int64]
+        tot = C.c_int64(0)
+        nseq = f(self._p, C.byref(tot), None, 0)
+        if nseq < 0:
+            raise WfmError(f"wfm_minmer_part_info failed ({nseq})")
+        counts = np.zeros(max(nseq, 1), dtype=np.int64)
+        f(self._p, None, counts.ctypes.data, nseq)
+        return tot.value, counts[:nseq]
+
+    def download(self):
+        """wfm_minmer_part_download: one array of records per sequence, in the part's order."""
+        tot, counts = self.info()
+        out = np.zeros(max(tot, 1), dtype=MINMER_DTYPE)
+        f = self._h._L.wfm_minmer_part_download
+        f.restype = C.c_int64
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+        n = f(self._h._p, self._p, out.ctypes.data, tot)
+        if n != tot:
+            raise WfmError(f"wfm_minmer_part_download failed ({n}): {self._h.last_error()}")
+        offs = np.concatenate([[0], np.cumsum(counts)])
+        return [out[offs[i]:offs[i + 1]] for i in range(len(counts))]
+
+    def free(self):
+        if self._p:
+            f = self._h._L.wfm_minmer_part_free
+            f.restype = None
+            f.argtypes = [C.c_void_p]
+            f(self._p)
+            self._p = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class Handle:
     """One handle per GPU (wfm_create)."""
 
@@ -456,6 +507,42 @@ class Handle:
             raise WfmError(f"wfm_index_build_sequences failed ({rc}): {self.last_error()}")
         return (Index(self, ix) if ix.value else None), nw.value
 
+    def sketch_part(self, seqs, k: int, w: int, s: int, seq_ids=None, threads: int = 1):
+        """wfm_sketch_part: the minmer intervals of the sequences, left on this handle's device; returns a MinmerPart."""
+        n = len(seqs)
+        ids = np.ascontiguousarray(seq_ids if seq_ids is not None else range(n), dtype=np.int32)
+        bufs = [np.frombuffer(x, dtype=np.uint8) for x in seqs]
+        ptrs = (C.c_void_p * max(n, 1))(*[b.ctypes.data for b in bufs])
+        lens = np.array([len(x) for x in seqs], dtype=np.int64)
+        f = self._L.wfm_sketch_part
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+        part = C.c_void_p()
+        rc = f(self._p, ptrs, lens.ctypes.data, ids.ctypes.data, n, k, w, s, threads, C.byref(part))
+        if rc != 0:
+            raise WfmError(f"wfm_sketch_part failed ({rc}): {self.last_error()}")
+        return MinmerPart(self, part)
+
+    def index_build_parts(self, parts, order, max_kmer_freq=0.0002):
+        """wfm_index_build_parts: the index of the union of the parts (MinmerPart objects of any handle), order = one
+        (part, sequence-in-part) pair per sequence of the union; returns (Index or None, number of minmer intervals)."""
+        L = self._L
+        L.wfm_index_free.restype = None
+        L.wfm_index_free.argtypes = [C.c_void_p, C.c_void_p]
+        L.wfm_index_info.argtypes = [C.c_void_p, C.POINTER(IndexInfo)]
+        L.wfm_index_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        arr = (C.c_void_p * max(len(parts), 1))(*[p._p for p in parts])
+        od = np.ascontiguousarray(order, dtype=np.int32).reshape(-1, 2)
+        f = L.wfm_index_build_parts
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_double, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+        ix = C.c_void_p()
+        nw = C.c_int64(0)
+        rc = f(self._p, arr, len(parts), od.ctypes.data, len(od), max_kmer_freq, C.byref(ix), C.byref(nw))
+        if rc != 0:
+            raise WfmError(f"wfm_index_build_parts failed ({rc}): {self.last_error()}")
+        return (Index(self, ix) if ix.value else None), nw.value
+
     def map_l1(self, index, qsketch, qcount, q_seq_id, q_len, q_active, s, params, ref_group):
         """wfm_map_l1: L1 candidate regions of a batch of query fragments.  params: the dict of oracle/map_l1.py."""
         nfrag = len(qcount)
@@ -639,14 +726,15 @@ class Handle:
 HOST_EXPORTS = ["wfmh_test_packed_lce", "wfmh_test_is_acgt", "wfmh_align_default_params", "wfmh_align_paf", "wfmh_test_cigar", "wfmh_free", "wfmh_test_winnow",
                 "wfmh_map_default_params", "wfmh_test_filter", "wfmh_map", "wfmh_test_winnow_chunked", "wfmh_test_fasta", "wfmh_test_winnow_thinned", "wfmh_test_sort_records", "wfmh_test_index_file",
                 "wfmh_map_multi", "wfmh_align_paf_multi", "wfmh_test_winnow_model", "wfmh_test_sortlike_model", "wfmh_test_finish_records",
-                "wfmh_release_sequences", "wfmh_test_fasta_shared", "wfmh_seed_paf"]
+                "wfmh_release_sequences", "wfmh_test_fasta_shared", "wfmh_seed_paf", "wfmh_test_deal"]
 
 
 class MapSummary(C.Structure):
     _fields_ = [("targets", C.c_uint64), ("queries", C.c_uint64), ("subsets", C.c_uint64), ("target_bp", C.c_uint64),
                 ("query_bp", C.c_uint64), ("index_windows", C.c_uint64), ("fragments", C.c_uint64), ("l2_mappings", C.c_uint64),
                 ("written", C.c_uint64), ("percentage_identity", C.c_float), ("sketch_size", C.c_int32), ("ms_index", C.c_double), ("ms_map", C.c_double), ("ms_filter", C.c_double),
-                ("ms_total", C.c_double), ("ms_replicate", C.c_double), ("ms_identity", C.c_double), ("ms_wall", C.c_double)]
+                ("ms_total", C.c_double), ("ms_replicate", C.c_double), ("ms_identity", C.c_double), ("ms_wall", C.c_double),
+                ("index_parts", C.c_int32), ("pad_", C.c_int32), ("ms_index_sketch", C.c_double), ("ms_index_merge", C.c_double)]
 
 
 def _handle_array(handles):
@@ -691,6 +779,19 @@ def map_paf(handle, target_fasta: str, out_paf: str, query_fasta: str = None, pa
     if rc != 0:
         raise WfmError(f"wfmh_map failed ({rc}): {handle.last_error()}")
     return s
+
+
+def host_deal(lengths, n_parts: int):
+    """wfmh_test_deal: the part each of the sequences goes to when wfmh_map_multi deals a target subset over n_parts handles."""
+    L = load()
+    L.wfmh_test_deal.restype = C.c_int
+    L.wfmh_test_deal.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
+    ln = np.ascontiguousarray(lengths, dtype=np.int64)
+    out = np.zeros(max(len(ln), 1), dtype=np.int32)
+    rc = L.wfmh_test_deal(ln.ctypes.data, len(ln), n_parts, out.ctypes.data)
+    if rc != 0:
+        raise WfmError(f"wfmh_test_deal failed ({rc})")
+    return [int(x) for x in out[:len(ln)]]
 
 
 def host_fasta_shared(path: str, name: str) -> str:

@@ -45,6 +45,18 @@ int map_l2_device(wfm_handle_t* h, MapScratch& sc, const wfm_index_t* ix, const 
 // The index stage on minmer intervals that are already on the device (map_index.hip); d_minmers stays the caller's.
 int map_index_build_device(wfm_handle_t* h, const wfm_minmer_t* d_minmers, int64_t n, double max_kmer_freq, wfm_index_t** out);
 
+// The records of some sequences of a target subset, on the device that sketched them (wfm_sketch_part, minmers.cpp).
+struct wfm_minmer_part {
+  int device = 0;
+  wfm_minmer_t* d = nullptr;   // [n] from wfm_dmalloc on `device`, grouped by sequence in input order; NULL when n == 0
+  int64_t n = 0;
+  std::vector<int64_t> offs;   // [sequences + 1] first record of each sequence
+};
+// wfm_index_build_parts; *ms_merge (optional) = staging of the other devices' parts plus the gather, up to the moment the
+// union lies on h's device in order (0 when a single part is read in place)
+int map_index_build_parts(wfm_handle_t* h, const wfm_minmer_part_t* const* parts, int nparts, const wfm_part_seq_t* order, int64_t norder,
+                          double max_kmer_freq, wfm_index_t** out, int64_t* n_windows, double* ms_merge);
+
 // --streaming-minhash: the records sketchSequenceStreaming makes of one target sequence (map_kernels.hip), ordered by wpos
 int map_streaming_sketch(wfm_handle_t* h, const char* seq, int64_t len, int k, int w, int s, int32_t seq_id, std::vector<wfm_minmer_t>& out);
 

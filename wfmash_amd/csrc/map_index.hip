@@ -266,7 +266,245 @@ int map_index_build_device(wfm_handle_t* h, const wfm_minmer_t* d_m, int64_t n, 
   return WFM_OK;
 }
 
+// ---- the index of a subset whose sequences were sketched in parts (wfm_sketch_part), possibly on several devices ----
+namespace {
+
+// one row per sequence of the union, in union order: count records from src[src_off] on go to dst[dst_off]; dst_off is the
+// running sum of the counts, so a sequence without records is a row that shares its dst_off with the next one
+struct GatherRow {
+  const wfm_minmer_t* src;
+  int64_t src_off, dst_off, count;
+};
+constexpr int kGatherTile = WFM_GATHER_TILE;  // destination records per workgroup
+constexpr int kGatherThreads = 256;
+
+// the row that holds destination record p among rows [lo, hi]: the last one with dst_off <= p.  Rows without records never
+// qualify as that: the row after such a row has the same dst_off and lies behind it
+__device__ inline int64_t gather_row_of(const GatherRow* rows, int64_t lo, int64_t hi, int64_t p) {
+  while (lo < hi) {
+    const int64_t mid = lo + (hi - lo + 1) / 2;
+    if (rows[mid].dst_off <= p) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// Segmented gather: workgroup b writes destination records [b * kGatherTile, (b + 1) * kGatherTile) and n bounds the last
+// one.  The tile's first and last row are found once per workgroup (the same search in every lane: uniform loads), a
+// lane's record is then looked up among those rows only.  A record is two 16-byte loads and two 16-byte stores; consecutive
+// lanes write consecutive records.
+__global__ __launch_bounds__(kGatherThreads) void gather_segments(const GatherRow* __restrict__ rows, int64_t nrows,
+                                                                  wfm_minmer_t* __restrict__ dst, int64_t n) {
+  const int64_t t0 = (int64_t)blockIdx.x * kGatherTile;
+  if (t0 >= n || nrows <= 0) return;
+  const int64_t t1 = t0 + kGatherTile < n ? t0 + kGatherTile : n;
+  const int64_t r0 = gather_row_of(rows, 0, nrows - 1, t0);
+  const int64_t r1 = gather_row_of(rows, r0, nrows - 1, t1 - 1);
+  uint4* out = reinterpret_cast<uint4*>(dst);
+  for (int64_t p = t0 + threadIdx.x; p < t1; p += kGatherThreads) {
+    const GatherRow row = rows[gather_row_of(rows, r0, r1, p)];
+    const int64_t at = p - row.dst_off;
+    if (at < 0 || at >= row.count) continue;  // (cannot happen with a table that covers [0, n): the host checks the sums)
+    const uint4* in = reinterpret_cast<const uint4*>(row.src + row.src_off + at);
+    const uint4 a = in[0], b = in[1];
+    out[2 * p] = a;
+    out[2 * p + 1] = b;
+  }
+}
+
+// a part of another device onto h's device: chunks go device-to-host on a stream of the source device and host-to-device
+// on h's stream through two pinned slots, chunk c + 1 on its way down while chunk c goes up.  Every wait is a host wait
+// for an event of the stream's own device; no stream waits for another device's event and nothing is copied peer to peer.
+struct PartStager {
+  static constexpr size_t kMaxChunkRecs = (size_t)1 << 18;  // 8 MB per slot
+  size_t kChunkRecs = kMaxChunkRecs;  // (WFM_INDEX_STAGE_CHUNK, records, 1024 .. 2^18: a test switch, several chunks from a small part)
+  PartStager() {
+    const char* e = getenv("WFM_INDEX_STAGE_CHUNK");
+    if (e) kChunkRecs = (size_t)std::min<long long>((long long)kMaxChunkRecs, std::max<long long>(1024, atoll(e)));
+  }
+  char* pin = nullptr;
+  hipStream_t src_stream = nullptr;
+  hipEvent_t down[2] = {nullptr, nullptr}, up[2] = {nullptr, nullptr};
+  int src_dev = -1, dst_dev = -1;
+  ~PartStager() { release(); }
+  void release() {
+    if (src_dev >= 0) (void)hipSetDevice(src_dev);
+    if (src_stream) { (void)hipStreamSynchronize(src_stream); (void)hipStreamDestroy(src_stream); src_stream = nullptr; }
+    for (auto& e : down) if (e) { (void)hipEventDestroy(e); e = nullptr; }
+    if (dst_dev >= 0) (void)hipSetDevice(dst_dev);
+    for (auto& e : up) if (e) { (void)hipEventDestroy(e); e = nullptr; }
+    if (pin) { (void)hipHostFree(pin); pin = nullptr; }
+  }
+  // the events and the stream belong to one source device: a part of another device begins with fresh ones
+  hipError_t bind(int sdev, int ddev) {
+    hipError_t e = hipSuccess;
+    if (!pin) e = hipHostMalloc((void**)&pin, 2 * kMaxChunkRecs * sizeof(wfm_minmer_t), hipHostMallocPortable);
+    if (e != hipSuccess) return e;
+    if (sdev == src_dev && ddev == dst_dev) return hipSuccess;
+    char* keep = pin;
+    pin = nullptr;
+    release();
+    pin = keep;
+    src_dev = sdev; dst_dev = ddev;
+    if ((e = hipSetDevice(sdev)) != hipSuccess) return e;
+    if ((e = hipStreamCreateWithFlags(&src_stream, hipStreamNonBlocking)) != hipSuccess) return e;
+    for (auto& ev : down) if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return e;
+    if ((e = hipSetDevice(ddev)) != hipSuccess) return e;
+    for (auto& ev : up) if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return e;
+    return hipSuccess;
+  }
+  // d_dst (on ddev, n records) = d_src (on sdev); returns with the last upload queued on st, the downloads all done
+  hipError_t copy(const wfm_minmer_t* d_src, int sdev, wfm_minmer_t* d_dst, int ddev, int64_t n, hipStream_t st) {
+    hipError_t e = bind(sdev, ddev);
+    if (e != hipSuccess) return e;
+    const int64_t nchunks = (n + (int64_t)kChunkRecs - 1) / (int64_t)kChunkRecs;
+    auto recs_of = [&](int64_t c) { return (size_t)std::min<int64_t>((int64_t)kChunkRecs, n - c * (int64_t)kChunkRecs); };
+    auto slot_of = [&](int64_t c) { return pin + (size_t)(c & 1) * kChunkRecs * sizeof(wfm_minmer_t); };
+    auto download = [&](int64_t c) -> hipError_t {
+      hipError_t d = hipSetDevice(sdev);
+      if (d == hipSuccess && c >= 2) d = hipEventSynchronize(up[c & 1]);  // the slot's last upload has read it
+      if (d == hipSuccess) d = hipMemcpyAsync(slot_of(c), d_src + c * (int64_t)kChunkRecs, recs_of(c) * sizeof(wfm_minmer_t), hipMemcpyDeviceToHost, src_stream);
+      if (d == hipSuccess) d = hipEventRecord(down[c & 1], src_stream);
+      return d;
+    };
+    if (nchunks > 0) e = download(0);
+    for (int64_t c = 0; c < nchunks && e == hipSuccess; ++c) {
+      if (c + 1 < nchunks) e = download(c + 1);
+      if (e == hipSuccess) e = hipEventSynchronize(down[c & 1]);
+      if (e == hipSuccess) e = hipSetDevice(ddev);
+      if (e == hipSuccess) e = hipMemcpyAsync(d_dst + c * (int64_t)kChunkRecs, slot_of(c), recs_of(c) * sizeof(wfm_minmer_t), hipMemcpyHostToDevice, st);
+      if (e == hipSuccess) e = hipEventRecord(up[c & 1], st);
+    }
+    (void)hipSetDevice(ddev);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);  // the slots are free again for the next part
+    return e;
+  }
+};
+
+}  // namespace
+
+int map_index_build_parts(wfm_handle_t* h, const wfm_minmer_part_t* const* parts, int nparts, const wfm_part_seq_t* order, int64_t norder,
+                          double max_kmer_freq, wfm_index_t** out, int64_t* n_windows, double* ms_merge) {
+  if (!h || !out || nparts < 0 || norder < 0 || (nparts && !parts) || (norder && !order)) return WFM_E_ARG;
+  *out = nullptr;
+  if (n_windows) *n_windows = 0;
+  if (ms_merge) *ms_merge = 0;
+  for (int p = 0; p < nparts; ++p)
+    if (!parts[p] || parts[p]->offs.empty() || parts[p]->offs.back() != parts[p]->n || (parts[p]->n && !parts[p]->d)) return WFM_E_ARG;
+  // the gather table on the host; every (part, sequence) at most once, so that the union is no larger than the parts together
+  std::vector<GatherRow> rows((size_t)norder);
+  std::vector<std::vector<uint8_t>> seen((size_t)nparts);
+  for (int p = 0; p < nparts; ++p) seen[(size_t)p].assign(parts[p]->offs.size() - 1, 0);
+  int64_t n = 0;
+  for (int64_t i = 0; i < norder; ++i) {
+    const int32_t p = order[i].part, q = order[i].seq;
+    if (p < 0 || p >= nparts || q < 0 || (size_t)q >= seen[(size_t)p].size() || seen[(size_t)p][(size_t)q]) {
+      wfm_set_error(h, "wfm_index_build_parts: order[" + std::to_string(i) + "] names no sequence of a part, or one named before");
+      return WFM_E_ARG;
+    }
+    seen[(size_t)p][(size_t)q] = 1;
+    const wfm_minmer_part& P = *parts[p];
+    rows[(size_t)i] = GatherRow{P.d, P.offs[(size_t)q], n, P.offs[(size_t)q + 1] - P.offs[(size_t)q]};
+    if (rows[(size_t)i].count < 0 || rows[(size_t)i].src_off < 0 || rows[(size_t)i].src_off + rows[(size_t)i].count > P.n) return WFM_E_ARG;
+    n += rows[(size_t)i].count;
+  }
+  if (n_windows) *n_windows = n;
+  if (n == 0) return WFM_OK;
+  if (n >= (int64_t)1 << 31) { wfm_set_error(h, "wfm_index_build_parts: 2^31 records and more"); return WFM_E_ARG; }
+  const int dev = wfm_device(h);
+  HIPCHK(h, hipSetDevice(dev));
+  hipStream_t st = wfm_stream(h);
+  const bool stage_all = getenv("WFM_INDEX_STAGE_ALL") && atoi(getenv("WFM_INDEX_STAGE_ALL")) != 0;
+
+  // one part of this device whose named records lie end to end already: the index stage reads it where it is
+  {
+    bool in_place = !stage_all;
+    const wfm_minmer_t* base = nullptr;
+    int64_t next = 0;
+    int from_part = -1;
+    for (int64_t i = 0; i < norder && in_place; ++i) {
+      const GatherRow& r = rows[(size_t)i];
+      if (r.count == 0) continue;
+      if (!base) { base = r.src + r.src_off; next = r.src_off; from_part = order[i].part; }
+      in_place = order[i].part == from_part && r.src_off == next && parts[from_part]->device == dev;
+      next += r.count;
+    }
+    if (in_place && base) return map_index_build_device(h, base, n, max_kmer_freq, out);
+  }
+
+  auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+  const double t_m = now();
+  Scratch sc;
+  // the parts of other devices, whole, onto this one
+  std::vector<const wfm_minmer_t*> local((size_t)nparts, nullptr);
+  {
+    PartStager stager;
+    for (int p = 0; p < nparts; ++p) {
+      const wfm_minmer_part& P = *parts[p];
+      local[(size_t)p] = P.d;
+      bool used = false;
+      for (uint8_t u : seen[(size_t)p]) used = used || u;
+      if (!used || P.n == 0 || (P.device == dev && !stage_all)) continue;
+      wfm_minmer_t* d_copy = nullptr;
+      if (sc.alloc(&d_copy, (size_t)P.n) != hipSuccess) { (void)hipGetLastError(); wfm_set_error(h, "out of device memory (staged minmer part)"); return WFM_E_NOMEM; }
+      const hipError_t e = stager.copy(P.d, P.device, d_copy, dev, P.n, st);
+      if (e != hipSuccess) {
+        (void)hipSetDevice(dev);
+        wfm_set_error(h, std::string("wfm_index_build_parts: staging a part of device ") + std::to_string(P.device) + ": " + hipGetErrorString(e));
+        return WFM_E_HIP;
+      }
+      local[(size_t)p] = d_copy;
+    }
+  }
+  HIPCHK(h, hipSetDevice(dev));
+  for (int64_t i = 0; i < norder; ++i) rows[(size_t)i].src = local[(size_t)order[i].part];
+  GatherRow* d_rows = nullptr;
+  wfm_minmer_t* d_union = nullptr;
+  if (sc.alloc(&d_rows, (size_t)norder) != hipSuccess || sc.alloc(&d_union, (size_t)n) != hipSuccess) {
+    (void)hipGetLastError();
+    wfm_set_error(h, "out of device memory (union of the minmer parts)");
+    return WFM_E_NOMEM;
+  }
+  HIPCHK(h, hipMemcpyAsync(d_rows, rows.data(), (size_t)norder * sizeof(GatherRow), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(gather_segments, dim3((unsigned)((n + kGatherTile - 1) / kGatherTile)), dim3(kGatherThreads), 0, st, d_rows, norder, d_union, n);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipStreamSynchronize(st));  // (rows is read by the copy until here)
+  if (ms_merge) *ms_merge = now() - t_m;
+  if (getenv("WFM_DEBUG")) fprintf(stderr, "[wfm] index_build_parts: %d parts, %lld sequences, %.1f MB of records staged and gathered in %.1f ms\n", nparts, (long long)norder, (double)n * 32 / 1e6, now() - t_m);
+  return map_index_build_device(h, d_union, n, max_kmer_freq, out);
+}
+
 extern "C" {
+
+int wfm_index_build_parts(wfm_handle_t* h, const wfm_minmer_part_t* const* parts, int nparts, const wfm_part_seq_t* order, int64_t norder,
+                          double max_kmer_freq, wfm_index_t** out, int64_t* n_windows) {
+  return map_index_build_parts(h, parts, nparts, order, norder, max_kmer_freq, out, n_windows, nullptr);
+}
+
+int64_t wfm_minmer_part_info(const wfm_minmer_part_t* part, int64_t* n_records, int64_t* counts, int64_t cap) {
+  if (!part || part->offs.empty() || (cap > 0 && !counts)) return WFM_E_ARG;
+  const int64_t nseq = (int64_t)part->offs.size() - 1;
+  if (n_records) *n_records = part->n;
+  for (int64_t i = 0; i < std::min(nseq, cap); ++i) counts[i] = part->offs[(size_t)i + 1] - part->offs[(size_t)i];
+  return nseq;
+}
+
+int64_t wfm_minmer_part_download(wfm_handle_t* h, const wfm_minmer_part_t* part, wfm_minmer_t* out, int64_t cap) {
+  if (!h || !part || cap < 0 || (cap && !out)) return WFM_E_ARG;
+  const int64_t m = std::min(part->n, cap);
+  if (m > 0) {
+    HIPCHK(h, hipSetDevice(part->device));
+    const hipError_t e = hipMemcpy(out, part->d, (size_t)m * sizeof(wfm_minmer_t), hipMemcpyDeviceToHost);
+    (void)hipSetDevice(wfm_device(h));
+    if (e != hipSuccess) { wfm_set_error(h, std::string("wfm_minmer_part_download: ") + hipGetErrorString(e)); return WFM_E_HIP; }
+  }
+  return part->n;
+}
+
+void wfm_minmer_part_free(wfm_minmer_part_t* part) {
+  if (!part) return;
+  if (part->d) wfm_dfree(part->d);  // (finds the block's device itself and waits for it)
+  delete part;
+}
 
 int wfm_index_upload(wfm_handle_t* h, const uint64_t* uhash, const int64_t* poff, int64_t n_unique, const wfm_interval_point_t* points,
                      const wfm_minmer_t* minmers, int64_t n_kept, wfm_index_t** out) {

@@ -155,11 +155,12 @@ int wfmh_map_multi(wfm_handle_t* const* handles, int n, const char* target_fasta
       double ms_identity = 0;
       // the normalised device copies of the chromosomes stay from the identity estimate's sketches to the index build and the queries' fragments
       // (wfm_map_sequence_cache); the scope ends before the files are let go
+      // -- on every handle: each device sketches its share of the index and finds there what its share of the estimate left
       struct SeqCacheScope {
-        wfm_handle_t* h;
-        explicit SeqCacheScope(wfm_handle_t* hh) : h(hh) { (void)wfm_map_sequence_cache(h, 1); }
-        ~SeqCacheScope() { (void)wfm_map_sequence_cache(h, 0); }
-      } seq_cache_scope(handles[0]);
+        wfm_handle_t* const* hs; int n;
+        SeqCacheScope(wfm_handle_t* const* hh, int nn) : hs(hh), n(nn) { for (int i = 0; i < n; ++i) (void)wfm_map_sequence_cache(hs[i], 1); }
+        ~SeqCacheScope() { for (int i = n - 1; i >= 0; --i) (void)wfm_map_sequence_cache(hs[i], 0); }
+      } seq_cache_scope(handles, n);
       if (p.auto_pct_identity) {
         // main.cpp:72-128: estimate, then derive the sketch size from the estimate unless -s was given
         std::vector<std::string> target_prefix_vec;
@@ -180,6 +181,8 @@ int wfmh_map_multi(wfm_handle_t* const* handles, int n, const char* target_fasta
         summary->sketch_size = mapper.parameters().sketchSize;
         summary->ms_index = s.ms_index; summary->ms_map = s.ms_map; summary->ms_filter = s.ms_filter; summary->ms_total = s.ms_total;
         summary->ms_replicate = s.ms_replicate;
+        summary->index_parts = s.index_parts; summary->pad_ = 0;
+        summary->ms_index_sketch = s.ms_index_sketch; summary->ms_index_merge = s.ms_index_merge;
         summary->ms_identity = ms_identity;
         summary->ms_wall = ms_since(t_call);
       }
@@ -248,6 +251,13 @@ int wfmh_seed_paf(const char* target_fasta, const char* query_fasta, const char*
     fprintf(stderr, "[wfmash::externalSeeder] ERROR: %s\n", e.what());
     return WFM_E_ARG;
   }
+}
+
+int wfmh_test_deal(const int64_t* lengths, int64_t n, int n_parts, int32_t* out_part) {
+  if (n < 0 || n_parts < 1 || (n && (!lengths || !out_part))) return WFM_E_ARG;
+  const std::vector<int> part = skch::deal_longest_first(lengths, n, n_parts);
+  for (int64_t i = 0; i < n; ++i) out_part[i] = part[(size_t)i];
+  return WFM_OK;
 }
 
 char* wfmh_test_filter(const char* stage, const wfm_mapping_t* maps, int64_t n, const char* fasta, const char* query_name,

@@ -20,6 +20,7 @@
 #include <thread>
 #include <unordered_map>
 
+#include "../csrc/map_device.h"
 #include "../csrc/wfa_handle.h"
 #include "fasta.hpp"
 #include "index_file.hpp"
@@ -102,7 +103,81 @@ struct DeviceTables {
   wfm_map_params_t prm;
 };
 
+// Sketch::build of one subset over several handles: the sequences are dealt over hs, one host thread per handle that got
+// any sketches its share (wfm_sketch_part), the index stage runs on hs[0] on the union in the order given (wfm_index_build_parts).
+// Errors are reported on hs[0]; the parts are freed on every way out.
+int build_index_sharded(const std::vector<wfm_handle_t*>& hs, const std::vector<const char*>& sp, const std::vector<int64_t>& sl,
+                        const std::vector<int32_t>& si, int k, int w, int s, int threads, double max_kmer_freq, wfm_index_t** ix,
+                        int64_t* n_windows, int* parts_used, double* ms_sketch, double* ms_merge) {
+  const size_t nh = hs.size(), n = sp.size();
+  const std::vector<int> part_of = deal_longest_first(sl.data(), (int64_t)n, (int)nh);
+  struct Share {
+    std::vector<const char*> sp;
+    std::vector<int64_t> sl;
+    std::vector<int32_t> si;
+    wfm_minmer_part_t* part = nullptr;
+    int rc = WFM_OK;
+    double ms = 0;
+  };
+  std::vector<Share> shares(nh);
+  struct FreeParts {
+    std::vector<Share>& v;
+    ~FreeParts() { for (Share& sh : v) { wfm_minmer_part_free(sh.part); sh.part = nullptr; } }
+  } free_parts{shares};
+  std::vector<wfm_part_seq_t> order(n);
+  for (size_t i = 0; i < n; ++i) {
+    Share& sh = shares[(size_t)part_of[i]];
+    order[i].part = part_of[i];  // (the handle's index for now: the parts are numbered below)
+    order[i].seq = (int32_t)sh.sp.size();
+    sh.sp.push_back(sp[i]); sh.sl.push_back(sl[i]); sh.si.push_back(si[i]);
+  }
+  const int threads_each = std::max(1, threads / (int)nh);
+  {
+    std::vector<std::thread> sketchers;
+    for (size_t g = 0; g < nh; ++g) {
+      if (shares[g].sp.empty()) continue;
+      sketchers.emplace_back([&, g] {
+        Share& sh = shares[g];
+        const double t0 = now_ms();
+        sh.rc = wfm_sketch_part(hs[g], sh.sp.data(), sh.sl.data(), sh.si.data(), (int64_t)sh.sp.size(), k, w, s, threads_each, &sh.part);
+        sh.ms = now_ms() - t0;
+      });
+    }
+    for (auto& t : sketchers) t.join();
+  }
+  std::vector<const wfm_minmer_part_t*> parts;
+  std::vector<int> number(nh, -1);
+  for (size_t g = 0; g < nh; ++g) {
+    if (shares[g].sp.empty()) continue;
+    if (shares[g].rc != WFM_OK) {
+      wfm_set_error(hs[0], "index sketching failed on handle " + std::to_string(g) + ": " + wfm_last_error(hs[g]));
+      return shares[g].rc;
+    }
+    number[g] = (int)parts.size();
+    parts.push_back(shares[g].part);
+    *ms_sketch = std::max(*ms_sketch, shares[g].ms);
+  }
+  for (auto& o : order) o.part = number[(size_t)o.part];
+  *parts_used = (int)parts.size();
+  return map_index_build_parts(hs[0], parts.data(), (int)parts.size(), order.data(), (int64_t)order.size(), max_kmer_freq, ix, n_windows, ms_merge);
+}
+
 }  // namespace
+
+std::vector<int> deal_longest_first(const int64_t* lengths, int64_t n, int n_parts) {
+  std::vector<int> part((size_t)std::max<int64_t>(n, 0), 0);
+  if (n_parts < 1) return part;
+  std::vector<int64_t> by_length(part.size());
+  for (size_t i = 0; i < by_length.size(); ++i) by_length[i] = (int64_t)i;
+  std::stable_sort(by_length.begin(), by_length.end(), [&](int64_t a, int64_t b) { return lengths[a] > lengths[b]; });  // equal lengths: the lower index first
+  std::vector<int64_t> load((size_t)n_parts, 0);
+  for (int64_t i : by_length) {
+    const int p = (int)(std::min_element(load.begin(), load.end()) - load.begin());  // the first of the least loaded
+    part[(size_t)i] = p;
+    load[(size_t)p] += lengths[i];
+  }
+  return part;
+}
 
 Map::Map(const Parameters& p, wfm_handle_t* h) : Map(p, std::vector<wfm_handle_t*>{h}) {}
 
@@ -255,10 +330,24 @@ int Map::mapQuery(MapSummary* summary) {
       // minmer intervals (GPU hashing + thinning, host winnowing) and the index stage; the intervals never
       // sit in one host array.  --streaming-minhash: one bottom-S MinHash per sequence instead (winSketch.hpp:474-485)
       int64_t n_windows = 0;
-      const int rc = P.use_streaming_minhash && S > 0
-                         ? wfm_index_build_streaming(h_, sp.data(), sl.data(), si.data(), (int64_t)sp.size(), k, (int)w, S, P.max_kmer_freq, &ix, &n_windows)
-                         : wfm_index_build_sequences(h_, sp.data(), sl.data(), si.data(), (int64_t)sp.size(), k, (int)w, S, P.threads,
-                                                     P.max_kmer_freq, &ix, &n_windows);
+      const bool streaming = P.use_streaming_minhash && S > 0;
+      const char* env_sharded = getenv("WFM_INDEX_SHARDED");
+      int rc;
+      // (WFM_INDEX_SHARDED=0: handles[0] builds alone as before; =1: the two-step path with a single handle as well, which times its steps)
+      if ((hs_.size() > 1 || (env_sharded && atoi(env_sharded) == 1)) && !streaming && !sp.empty() && !(env_sharded && atoi(env_sharded) == 0)) {
+        // every device sketches its share of the subset; the index stage runs on the first device on the union in subset order
+        int parts_used = 0;
+        double ms_sketch = 0, ms_merge = 0;
+        rc = build_index_sharded(hs_, sp, sl, si, k, (int)w, S, P.threads, P.max_kmer_freq, &ix, &n_windows, &parts_used, &ms_sketch, &ms_merge);
+        sum.index_parts = std::max(sum.index_parts, parts_used);
+        sum.ms_index_sketch += ms_sketch;
+        sum.ms_index_merge += ms_merge;
+      } else {
+        rc = streaming ? wfm_index_build_streaming(h_, sp.data(), sl.data(), si.data(), (int64_t)sp.size(), k, (int)w, S, P.max_kmer_freq, &ix, &n_windows)
+                       : wfm_index_build_sequences(h_, sp.data(), sl.data(), si.data(), (int64_t)sp.size(), k, (int)w, S, P.threads,
+                                                   P.max_kmer_freq, &ix, &n_windows);
+        sum.index_parts = std::max(sum.index_parts, 1);
+      }
       if (rc != WFM_OK) return rc;
       sum.index_windows += (uint64_t)n_windows;
     }

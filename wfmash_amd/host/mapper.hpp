@@ -30,14 +30,21 @@ struct MapSummary {
   uint64_t l2_mappings = 0;         // MappingResults leaving the GPU
   uint64_t written = 0;             // mapping PAF lines written
   double ms_index = 0, ms_replicate = 0, ms_map = 0, ms_filter = 0, ms_total = 0;
+  int index_parts = 0;              // the most handles that sketched one subset (0: none was sketched, -I)
+  double ms_index_sketch = 0, ms_index_merge = 0;  // parts of ms_index: slowest part per subset; staging + gather
 };
+
+// The deal of a subset's sequences over n_parts handles: longest first onto the least-loaded part, ties to the lower index
+// (the rule of wfmash_amd/dist.py:shard_records); part[i] of item i.  Deterministic.
+std::vector<int> deal_longest_first(const int64_t* lengths, int64_t n, int n_parts);
 
 class Map {
  public:
   // p.sketchSize == 0 derives it from the identity (parse_args.hpp:642-644)
   Map(const Parameters& p, wfm_handle_t* h);
-  // one handle per GPU of the node: the index is built on the first and copied to the others (it is read-only while
-  // mapping, computeMap.hpp:431-484), batches of query sequences go to whichever device is free
+  // one handle per GPU of the node: every handle sketches its share of a subset's sequences, the index stage runs on the
+  // first and its result is copied to the others (it is read-only while mapping, computeMap.hpp:431-484), batches of query
+  // sequences go to whichever device is free
   Map(const Parameters& p, const std::vector<wfm_handle_t*>& hs);
   // maps every query against every target subset and writes param.outFileName; returns 0 or WFM_E_*
   int mapQuery(MapSummary* summary = nullptr);

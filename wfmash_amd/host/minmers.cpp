@@ -1321,6 +1321,33 @@ extern "C" int wfm_index_build_sequences(wfm_handle_t* h, const char* const* seq
   return rc;
 }
 
+// The first half of wfm_index_build_sequences on its own: the records stay in the sink's device block, which the part takes over
+// (wfm_index_build_parts, map_index.hip, is the second half)
+extern "C" int wfm_sketch_part(wfm_handle_t* h, const char* const* seqs, const int64_t* lens, const int32_t* seq_ids, int64_t nseq,
+                               int k, int w, int s, int threads, wfm_minmer_part_t** out) {
+  if (!h || !out) return WFM_E_ARG;
+  *out = nullptr;
+  if (hipSetDevice(wfm_device(h)) != hipSuccess) { wfm_set_error(h, "hipSetDevice failed (sketch part)"); return WFM_E_HIP; }
+  int64_t bases = 0;
+  for (int64_t i = 0; i < nseq && lens; ++i) bases += std::max<int64_t>(0, lens[i]);
+  DeviceSink sink(h, bases / std::max(1, w) * (int64_t)s * 5 / 2 + 4096);
+  std::vector<int64_t> counts((size_t)std::max<int64_t>(nseq, 0), 0);
+  std::function<void()> release;
+  const int64_t n = add_minmers_core(h, seqs, lens, seq_ids, nseq, k, w, s, threads, sink, counts.data(), &release);
+  if (release) release();
+  if (n < 0) return (int)n;
+  std::unique_ptr<wfm_minmer_part> part(new wfm_minmer_part());
+  part->device = wfm_device(h);
+  part->offs.assign(counts.size() + 1, 0);
+  for (size_t i = 0; i < counts.size(); ++i) part->offs[i + 1] = part->offs[i] + counts[i];
+  if (part->offs.back() != n || sink.n != n) { wfm_set_error(h, "wfm_sketch_part: the per-sequence counts do not add up"); return WFM_E_HIP; }
+  part->n = n;
+  part->d = sink.d;   // (NULL when no sequence made a record: the sink allocates at its first record)
+  sink.d = nullptr;
+  *out = part.release();
+  return WFM_OK;
+}
+
 namespace {
 // --streaming-minhash: the records of every sequence (map_streaming_sketch), grouped by sequence in input order, into one sink
 int64_t streaming_core(wfm_handle_t* h, const char* const* seqs, const int64_t* lens, const int32_t* seq_ids, int64_t nseq, int k, int w, int s,
