@@ -192,6 +192,52 @@ int  wfm_align_resident(wfm_handle_t* h, const wfm_penalties_t* pen, wfm_seqset_
 int  wfm_align_resident_rle(wfm_handle_t* h, const wfm_penalties_t* pen, wfm_seqset_t* s,
                             wfm_result_t* out, uint32_t** runs, size_t* n_runs_total);
 
+/* ---- sequences resident on the device, problems by reference ----
+ * A store holds whole sequences on one device, normalised as makeUpperCaseAndValidDNA leaves them (commonFunc.hpp:132-142: upper
+ * case, anything but A C G T becomes N), one byte per base -- the form the align driver gives every window it fetches.  A problem
+ * is then named as "bases [off, off + len) of sequence i, this strand" and the device cuts, reverse-complements and lays out the
+ * windows itself; only sides given as host pointers cross PCIe.
+ *
+ * wfm_seqstore_create binds the store to h's DEVICE; every handle of that device may add to it and read from it, also at the same
+ * time (an internal mutex guards the table).  wfm_seqstore_add uploads the raw bytes in chunks through pinned memory, normalises
+ * them on the device and has finished there before it returns the sequence's id (>= 0) or a WFM_E_* code; a sequence lives in a
+ * block of its own from the device heap, with 16 bytes and more of slack on either side, and never moves.  A store of another
+ * device than h's: WFM_E_ARG; out of device memory: WFM_E_NOMEM, and the store stays usable.  wfm_seqstore_free releases the
+ * blocks (no call that reads the store may be in flight). */
+typedef struct wfm_seqstore wfm_seqstore_t;
+int     wfm_seqstore_create(wfm_handle_t* h, wfm_seqstore_t** out);
+void    wfm_seqstore_free(wfm_seqstore_t* s);
+int32_t wfm_seqstore_add(wfm_handle_t* h, wfm_seqstore_t* s, const char* seq, int64_t len);
+int     wfm_seqstore_info(const wfm_seqstore_t* s, int64_t* n_seqs, int64_t* bytes);  /* sequences held, bytes of their device blocks */
+
+typedef struct {
+  const char* pattern; const char* text;   /* host bytes for a side whose *_seq is -1, taken as they are (as wfm_problem_t) */
+  int64_t pattern_off, text_off;           /* window start on the stored (forward) strand */
+  int32_t pattern_seq, text_seq;           /* store id, or -1 = host pointer */
+  int32_t plen, tlen;
+  int32_t mode;
+  int32_t pattern_revcomp, text_revcomp;   /* 1: the side is the reverse complement of the window (N stays N) */
+  int32_t pattern_begin_free, pattern_end_free, text_begin_free, text_end_free;
+  int32_t score_hint;
+} wfm_problem_ref_t;                       /* 80 bytes */
+
+/* Destination bytes one task of the gather kernel covers (seq_gather_kernel, wfmash_amd/csrc/wfa_kernels.hip): a window longer
+ * than this is cut into several tasks, each a workgroup of its own. */
+#define WFM_SEQ_GATHER_CHUNK 16384
+
+/* wfm_upload_sequences for problems by reference: the seqset has exactly the layout wfm_upload_sequences gives the same problems
+ * (forward copies, the reversed copies of the BiWFA problems, pads, 2-bit mirror, ACGT flags), so wfm_align_resident[_rle] and
+ * everything behind them take it as they take any other.  store may be NULL when every side is a host pointer.  WFM_E_ARG (with a
+ * message, the handle stays usable): an unknown id, a window that leaves its sequence, plen + tlen > 2^29, a null host pointer
+ * for a -1 side of non-zero length, a store of another device. */
+int wfm_upload_sequence_refs(wfm_handle_t* h, const wfm_seqstore_t* store, const wfm_problem_ref_t* refs, size_t n, wfm_seqset_t** out);
+/* wfm_upload_sequence_refs + wfm_align_resident_rle + wfm_free_sequences */
+int wfm_align_refs_rle(wfm_handle_t* h, const wfm_penalties_t* pen, const wfm_seqstore_t* store, const wfm_problem_ref_t* refs, size_t n,
+                       wfm_result_t* out, uint32_t** runs, size_t* n_runs_total);
+/* Diagnostic: the seqset's byte buffer (pads, forward and reversed copies) back on the host.  Writes min(cap, its size) bytes to
+ * out (may be NULL); returns the buffer's size or a WFM_E_* code. */
+int64_t wfm_download_sequences(wfm_handle_t* h, const wfm_seqset_t* s, uint8_t* out, int64_t cap);
+
 /* How many other align calls the caller keeps in flight on this handle's DEVICE while a call on this handle runs (the align
  * driver's workers, each on a handle of its own: wfmash_amd/host/aligner.cpp).  0, the default: none -- a batch is then cut
  * into up to three parts that run side by side on streams of their own, because the levels of a batch of near-identical

@@ -32,7 +32,10 @@ typedef struct {
   int32_t  no_seq_in_sam;           /* 0 */
   int32_t  threads;                 /* -t: host threads for fetching sequences and for the CIGAR / PAF work of a
                                        batch (the reference runs one Taskflow worker per record); 0 = all cores */
-  int32_t  pad_;
+  int32_t  resident_sequences;      /* --resident-seqs: 1 = whole sequences stay on the device (one wfm_seqstore_t per device, filled on
+                                       first use up to WFM_SEQSTORE_GB, 32) and the problems name their windows by reference; the host
+                                       fetches a PAF record's bases only where the swizzle reads them.  0 (default): every window is
+                                       fetched on the host and uploaded -- the gain is unmeasured (profiles/resident_sequences.md) */
 } wfmh_align_params_t;
 
 typedef struct {
@@ -57,6 +60,9 @@ typedef struct {
   uint64_t tile_launches;
   double   ms_tile;
   double   ms_tags;      /* WFM_RECORD_TAGS (a diagnostic channel of the parity tests and bench.py): writing the records' tags, summed over the batches */
+  /* resident_sequences (both 0 without it) */
+  uint64_t records_resident;  /* records whose two sides both came from the device's sequence store */
+  uint64_t lazy_fetches;      /* of those, the ones whose bases the host fetched after all (a CIGAR that begins =,D or ends D,=) */
 } wfmh_align_summary_t;
 
 void wfmh_align_default_params(wfmh_align_params_t* p);
@@ -82,6 +88,9 @@ int wfmh_align_paf_multi(wfm_handle_t* const* handles, int n, const char* target
 char* wfmh_test_cigar(const char* fn, const char* a, const char* b, const char* query, const char* target,
                       long long i0, long long i1);
 void  wfmh_free(char* p);
+/* Test hook of the align driver's sub-window translation (resident_sequences): [a, b) of a side that is the window
+ * [win_start, win_end) of a stored sequence -- reverse-complemented when rev -- as the forward window [*out_start, *out_end). */
+void  wfmh_test_subwindow(int64_t win_start, int64_t win_end, int rev, int64_t a, int64_t b, int64_t* out_start, int64_t* out_end);
 /* host winnowing stage of wfm_add_minmers on caller-supplied canonical k-mer hashes (CPU tests) */
 int64_t wfmh_test_winnow(const char* seq, int64_t len, int k, int w, int s, int32_t seq_id,
                          const uint64_t* hash, const int8_t* strand, wfm_minmer_t* out, int64_t cap);

@@ -36,7 +36,10 @@ EXPORTS = [
     "wfm_get_tile_counters",
     "wfm_streaming_minmers", "wfm_index_build_streaming",
     "wfm_sketch_part", "wfm_minmer_part_info", "wfm_minmer_part_download", "wfm_minmer_part_free", "wfm_index_build_parts",
+    "wfm_seqstore_create", "wfm_seqstore_free", "wfm_seqstore_add", "wfm_seqstore_info",
+    "wfm_upload_sequence_refs", "wfm_align_refs_rle", "wfm_download_sequences",
 ]
+SEQ_GATHER_CHUNK = 16384  # WFM_SEQ_GATHER_CHUNK (include/wfmash_hip.h): destination bytes per task of the gather kernel
 
 
 class Penalties(C.Structure):
@@ -51,6 +54,19 @@ class Problem(C.Structure):
                 ("pattern_begin_free", C.c_int32), ("pattern_end_free", C.c_int32),
                 ("text_begin_free", C.c_int32), ("text_end_free", C.c_int32),
                 ("score_hint", C.c_int32), ("pad_", C.c_int32)]
+
+
+class ProblemRef(C.Structure):
+    """wfm_problem_ref_t: a problem whose sides are windows of sequences in a SeqStore (or host bytes where *_seq is -1)."""
+    _fields_ = [("pattern", C.c_char_p), ("text", C.c_char_p),
+                ("pattern_off", C.c_int64), ("text_off", C.c_int64),
+                ("pattern_seq", C.c_int32), ("text_seq", C.c_int32),
+                ("plen", C.c_int32), ("tlen", C.c_int32),
+                ("mode", C.c_int32),
+                ("pattern_revcomp", C.c_int32), ("text_revcomp", C.c_int32),
+                ("pattern_begin_free", C.c_int32), ("pattern_end_free", C.c_int32),
+                ("text_begin_free", C.c_int32), ("text_end_free", C.c_int32),
+                ("score_hint", C.c_int32)]
 
 
 class Result(C.Structure):
@@ -198,18 +214,67 @@ def _make_problems(items):
     return arr, keep, len(items)
 
 
+def _make_refs(refs):
+    """refs: iterable of ProblemRef, or of dicts keyed by its field names.  A side is either a window of the store
+    (pattern_seq / pattern_off / plen[/ pattern_revcomp], likewise text_*) or host bytes (pattern=b"...", text=b"..."; the
+    length is taken from them).  mode defaults to END2END_BIWFA."""
+    refs = list(refs)
+    arr = (ProblemRef * max(len(refs), 1))()
+    keep = []
+    for i, r in enumerate(refs):
+        if isinstance(r, ProblemRef):
+            C.memmove(C.byref(arr[i]), C.byref(r), C.sizeof(ProblemRef))
+            keep.append(r)
+            continue
+        a = arr[i]
+        a.pattern_seq = a.text_seq = -1
+        a.mode = WFM_MODE_END2END_BIWFA
+        for k, v in r.items():
+            if k in ("pattern", "text") and v is not None:
+                v = bytes(v)
+                keep.append(v)
+                setattr(a, "plen" if k == "pattern" else "tlen", len(v))
+            setattr(a, k, v)
+    return arr, keep, len(refs)
+
+
 class SeqSet:
-    def __init__(self, handle, items):
+    def __init__(self, handle, items, refs=False, store=None):
+        """items: problems as for Handle.align or, with refs, problems by reference as for _make_refs (their windows from store)."""
         self._h = handle
-        self.problems, self._keep, self.n = _make_problems(items)
         sp = C.c_void_p()
-        rc = handle._L.wfm_upload_sequences(handle._p, self.problems, self.n, C.byref(sp))
-        if rc != 0:
-            raise WfmError(f"wfm_upload_sequences failed ({rc}): {handle.last_error()}")
+        if refs:
+            self.problems, self._keep, self.n = _make_refs(items)
+            f = handle._L.wfm_upload_sequence_refs
+            f.restype = C.c_int
+            f.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(ProblemRef), C.c_size_t, C.POINTER(C.c_void_p)]
+            rc = f(handle._p, store._p if store is not None else None, self.problems, self.n, C.byref(sp))
+            if rc != 0:
+                raise WfmError(f"wfm_upload_sequence_refs failed ({rc}): {handle.last_error()}")
+            self.arena_bytes = sum(self.problems[i].plen + self.problems[i].tlen + 1 for i in range(self.n))
+        else:
+            self.problems, self._keep, self.n = _make_problems(items)
+            rc = handle._L.wfm_upload_sequences(handle._p, self.problems, self.n, C.byref(sp))
+            if rc != 0:
+                raise WfmError(f"wfm_upload_sequences failed ({rc}): {handle.last_error()}")
+            self.arena_bytes = handle._L.wfm_align_arena_bytes(self.problems, self.n)
         self._p = sp
-        self.arena_bytes = handle._L.wfm_align_arena_bytes(self.problems, self.n)
         self.arena = np.zeros(self.arena_bytes + 8, dtype=np.uint8)
         self.results = (Result * max(self.n, 1))()
+
+    def download(self):
+        """wfm_download_sequences: the seqset's byte buffer (pads, forward and reversed copies) as bytes."""
+        f = self._h._L.wfm_download_sequences
+        f.restype = C.c_int64
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+        n = f(self._h._p, self._p, None, 0)
+        if n < 0:
+            raise WfmError(f"wfm_download_sequences failed ({n}): {self._h.last_error()}")
+        out = np.zeros(max(n, 1), dtype=np.uint8)
+        n2 = f(self._h._p, self._p, out.ctypes.data, n)
+        if n2 != n:
+            raise WfmError(f"wfm_download_sequences failed ({n2}): {self._h.last_error()}")
+        return out[:n].tobytes()
 
     def free(self):
         if self._p:
@@ -305,6 +370,55 @@ class MinmerPart:
             pass
 
 
+class SeqStore:
+    """wfm_seqstore_t: whole sequences resident on a handle's device, normalised there (upper case, non-ACGT -> N)."""
+
+    def __init__(self, handle):
+        self._h = handle
+        L = handle._L
+        L.wfm_seqstore_create.restype = C.c_int
+        L.wfm_seqstore_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+        L.wfm_seqstore_free.restype = None
+        L.wfm_seqstore_free.argtypes = [C.c_void_p]
+        L.wfm_seqstore_add.restype = C.c_int32
+        L.wfm_seqstore_add.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_int64]
+        L.wfm_seqstore_info.restype = C.c_int
+        L.wfm_seqstore_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        p = C.c_void_p()
+        rc = L.wfm_seqstore_create(handle._p, C.byref(p))
+        if rc != 0:
+            raise WfmError(f"wfm_seqstore_create failed ({rc}): {handle.last_error()}")
+        self._p = p
+
+    def add(self, seq: bytes, handle=None) -> int:
+        """wfm_seqstore_add: the sequence's id.  handle: another handle of the store's device to add through."""
+        h = handle or self._h
+        seq = bytes(seq)
+        i = h._L.wfm_seqstore_add(h._p, self._p, seq, len(seq))
+        if i < 0:
+            raise WfmError(f"wfm_seqstore_add failed ({i}): {h.last_error()}")
+        return i
+
+    def info(self):
+        """wfm_seqstore_info: (sequences held, bytes of their device blocks)."""
+        n, b = C.c_int64(0), C.c_int64(0)
+        rc = self._h._L.wfm_seqstore_info(self._p, C.byref(n), C.byref(b))
+        if rc != 0:
+            raise WfmError(f"wfm_seqstore_info failed ({rc})")
+        return n.value, b.value
+
+    def free(self):
+        if self._p:
+            self._h._L.wfm_seqstore_free(self._p)
+            self._p = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class Handle:
     """One handle per GPU (wfm_create)."""
 
@@ -362,6 +476,44 @@ class Handle:
 
     def upload(self, items):
         return SeqSet(self, items)
+
+    def seqstore(self):
+        """wfm_seqstore_create: a store of device-resident sequences on this handle's device."""
+        return SeqStore(self)
+
+    def upload_refs(self, store, refs):
+        """wfm_upload_sequence_refs: a SeqSet from problems by reference (see _make_refs); store may be None when every side is host bytes."""
+        return SeqSet(self, refs, refs=True, store=store)
+
+    def align_refs(self, store, refs, pen=None):
+        """wfm_align_refs_rle: problems by reference; returns the same [AlignResult] as align (the runs spelled out as an op string)."""
+        arr, keep, n = _make_refs(refs)
+        pn = Penalties(*(pen or DEFAULT_PEN))
+        res = (Result * max(n, 1))()
+        runs = C.POINTER(C.c_uint32)()
+        total = C.c_size_t(0)
+        f = self._L.wfm_align_refs_rle
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ProblemRef), C.c_size_t, C.c_void_p, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_size_t)]
+        self._L.wfm_free_runs.restype = None
+        self._L.wfm_free_runs.argtypes = [C.POINTER(C.c_uint32)]
+        rc = f(self._p, C.byref(pn), store._p if store is not None else None, arr, n, res, C.byref(runs), C.byref(total))
+        if rc < 0:
+            raise WfmError(f"wfm_align_refs_rle failed ({rc}): {self.last_error()}")
+        try:
+            a = np.ctypeslib.as_array(runs, shape=(total.value,)).copy() if total.value else np.zeros(0, dtype=np.uint32)
+        finally:
+            self._L.wfm_free_runs(runs)
+        opc = np.frombuffer(b"MXID", dtype=np.uint8)
+        out = []
+        for i in range(n):
+            r = res[i]
+            ops = None
+            if r.status == 0:
+                mine = a[r.ops_off:r.ops_off + r.n_runs]
+                ops = np.repeat(opc[mine & 3], mine >> 2).tobytes()
+            out.append(AlignResult(r.status, r.score, ops, r.n_runs, r.cells))
+        return out
 
     def align_resident(self, seqset, pen=None, collect=True):
         pn = Penalties(*(pen or DEFAULT_PEN))
@@ -726,7 +878,7 @@ class Handle:
 HOST_EXPORTS = ["wfmh_test_packed_lce", "wfmh_test_is_acgt", "wfmh_align_default_params", "wfmh_align_paf", "wfmh_test_cigar", "wfmh_free", "wfmh_test_winnow",
                 "wfmh_map_default_params", "wfmh_test_filter", "wfmh_map", "wfmh_test_winnow_chunked", "wfmh_test_fasta", "wfmh_test_winnow_thinned", "wfmh_test_sort_records", "wfmh_test_index_file",
                 "wfmh_map_multi", "wfmh_align_paf_multi", "wfmh_test_winnow_model", "wfmh_test_sortlike_model", "wfmh_test_finish_records",
-                "wfmh_release_sequences", "wfmh_test_fasta_shared", "wfmh_seed_paf", "wfmh_test_deal"]
+                "wfmh_release_sequences", "wfmh_test_fasta_shared", "wfmh_seed_paf", "wfmh_test_deal", "wfmh_test_subwindow"]
 
 
 class MapSummary(C.Structure):
@@ -916,14 +1068,15 @@ class AlignParams(C.Structure):
                 ("min_block_identity", C.c_float), ("target_padding", C.c_uint64),
                 ("query_padding", C.c_uint64), ("wflign_max_len_minor", C.c_uint64),
                 ("disable_chain_patching", C.c_int32), ("sam_format", C.c_int32),
-                ("emit_md_tag", C.c_int32), ("no_seq_in_sam", C.c_int32), ("threads", C.c_int32), ("pad_", C.c_int32)]
+                ("emit_md_tag", C.c_int32), ("no_seq_in_sam", C.c_int32), ("threads", C.c_int32), ("resident_sequences", C.c_int32)]
 
 
 class AlignSummary(C.Structure):
     _fields_ = [("records", C.c_uint64), ("aligned_bp", C.c_uint64), ("written", C.c_uint64),
                 ("skipped", C.c_uint64), ("cells", C.c_uint64), ("ms_gpu", C.c_double), ("ms_total", C.c_double),
                 ("ms_rows", C.c_double), ("ms_fetch", C.c_double), ("ms_wflign", C.c_double), ("ms_text", C.c_double), ("batches", C.c_uint64),
-                ("cells_tile", C.c_uint64), ("tile_launches", C.c_uint64), ("ms_tile", C.c_double), ("ms_tags", C.c_double)]
+                ("cells_tile", C.c_uint64), ("tile_launches", C.c_uint64), ("ms_tile", C.c_double), ("ms_tags", C.c_double),
+                ("records_resident", C.c_uint64), ("lazy_fetches", C.c_uint64)]
 
 
 def _host():
@@ -950,6 +1103,18 @@ def host_cigar_fn(fn, a=b"", b=b"", query=b"", target=b"", i0=0, i1=0) -> str:
     s = C.string_at(p).decode()
     L.wfmh_free(p)
     return s
+
+
+def host_subwindow(win_start, win_end, rev, a, b):
+    """wfmh_test_subwindow: [a, b) of a side that is the (reverse-complemented when rev) window [win_start, win_end) of a stored
+    sequence, as a forward window (start, end) of that sequence."""
+    L = _host()
+    f = L.wfmh_test_subwindow
+    f.restype = None
+    f.argtypes = [C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    s, e = C.c_int64(0), C.c_int64(0)
+    f(win_start, win_end, 1 if rev else 0, a, b, C.byref(s), C.byref(e))
+    return s.value, e.value
 
 
 def host_plan_batch_bytes(file_bytes, rows, row_bytes, row_bases_sum, batch_records, batch_bases, nworkers, ngpu=1, min_batches=1, level=True) -> int:

@@ -196,6 +196,13 @@ void launch_bound(const uint8_t* seq, const BoundJob* jobs, int32_t* out, int nj
 // reversed copies of the sequences of a BiWFA problem, made on the device (wfm_upload_sequences)
 struct SeqRev { int64_t p_fwd, p_rev, t_fwd, t_rev; int32_t plen, tlen; };
 void launch_reverse(uint8_t* seq, const SeqRev* jobs, int njobs, int pad, hipStream_t st);
+// a window of a device-resident sequence copied into a seqset (wfm_upload_sequence_refs): len bytes from src to dst, read backwards
+// (reverse) and / or with A<->T, C<->G swapped (complement), then pad zero bytes; any alignment of src and dst.  A task covers at
+// most WFM_SEQ_GATHER_CHUNK bytes; the aligned 16-byte words of the source it reads reach at most 15 bytes beyond [src, src + len).
+struct SeqGatherTask { const uint8_t* src; uint8_t* dst; int32_t len, pad; int32_t reverse, complement; };
+void launch_seq_gather(const SeqGatherTask* tasks, int64_t ntasks, hipStream_t st);
+// makeUpperCaseAndValidDNA in place on nbytes (rounded up to 16) from a 16-byte aligned device address (wfm_seqstore_add)
+void launch_seq_normalize(uint8_t* seq, int64_t nbytes, hipStream_t st);
 // the 2-bit mirror of the sequence buffer (word i = bytes 16 i .. 16 i + 15) and, per BiWFA problem, "pure ACGT" (flag stays nonzero)
 void launch_seq_pack(const uint8_t* seq, uint32_t* pk, int64_t nwords, int64_t nbytes, const SeqRev* jobs, int njobs, int32_t* flag, hipStream_t st);
 constexpr int64_t PK_PAD_WORDS = 2048 + 64;  // words of padding behind the mirror: a tile stages a whole window from any origin inside

@@ -127,6 +127,20 @@ struct wfm_seqset {
   uint64_t seq_bases = 0;
 };
 
+// wfm_seqstore_t: whole sequences on one device, normalised, one block of the device heap each.  `mu` guards the table (a block
+// never moves, so a reader copies the entries it needs under the lock and reads the device memory without it); `add_mu` lets one
+// add at a time use the pinned chunks.
+struct wfm_seqstore {
+  int device = 0;
+  struct Seq { uint8_t* block = nullptr; uint8_t* data = nullptr; int64_t len = 0; size_t block_bytes = 0; };
+  mutable std::mutex mu;
+  std::vector<Seq> seqs;
+  int64_t bytes = 0;
+  std::mutex add_mu;
+  uint8_t* pin[2] = {nullptr, nullptr};  // pinned chunks the raw bytes go through
+  hipEvent_t pin_ev[2] = {nullptr, nullptr};
+};
+
 namespace {
 // one time origin per device for the whole process: the busy intervals of calls on different handles of a device (the align
 // driver keeps several batches in flight, each on a handle of its own) are reported against it and can be merged
@@ -217,6 +231,7 @@ struct wfm_handle {
   DevBuf<int32_t> i32a;
   DevBuf<int32_t> seqflags;  // wfm_upload_sequences: per problem, nonzero = pure ACGT
   DevBuf<SeqRev> flagjobs;
+  DevBuf<SeqGatherTask> gathertasks;  // wfm_upload_sequence_refs
   DevBuf<unsigned long long> total;
   void* attachment = nullptr;  // owned by another translation unit (map_kernels.hip: the pinned staging ring)
   void (*attachment_free)(void*) = nullptr;
@@ -1790,7 +1805,7 @@ void wfm_destroy(wfm_handle_t* h) {
   h->p2rows.release(); h->p2max.release(); h->p2bmax.release(); h->p2pbmax.release(); h->p2jobs.release(); h->widenjobs.release();
   h->bpjobs.release(); h->bpres.release(); h->bsjobs.release(); h->bsres.release();
   h->b2tjobs.release(); h->b2ttasks.release(); h->b2tkeys.release(); h->b2toffs.release(); h->b2tactive.release();
-  h->i64a.release(); h->i64b.release(); h->i64c.release(); h->i32a.release(); h->seqflags.release(); h->flagjobs.release(); h->total.release();
+  h->i64a.release(); h->i64b.release(); h->i64c.release(); h->i32a.release(); h->seqflags.release(); h->flagjobs.release(); h->gathertasks.release(); h->total.release();
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->ev2) (void)hipEventDestroy(h->ev2);
@@ -1841,26 +1856,24 @@ size_t wfm_align_arena_bytes(const wfm_problem_t* problems, size_t n) {
   return t;
 }
 
-int wfm_upload_sequences(wfm_handle_t* h, const wfm_problem_t* problems, size_t n, wfm_seqset_t** out) {
-  if (!h || !out || (n && !problems)) return WFM_E_ARG;
-  *out = nullptr;
-  HIPCHK(h, hipSetDevice(h->device));
-  wfm_seqset* S = new wfm_seqset();
+}  // extern "C"
+namespace {
+// The layout of a seqset, shared by wfm_upload_sequences and wfm_upload_sequence_refs (P: wfm_problem_t or wfm_problem_ref_t, lengths
+// validated by the caller): SEQ_PAD zero bytes, the forward copies -- the only part that crosses PCIe where the sides are host
+// pointers -- each followed by SEQ_PAD zero bytes, SEQ_PAD more, then the reversed copies of the BiWFA problems and a last SEQ_PAD.
+template <typename P>
+void layout_seqset(wfm_seqset* S, const P* problems, size_t n, size_t* fwd_bytes_out) {
   S->meta.resize(n);
   size_t bytes = SEQ_PAD, rev_bytes = 0;
   int64_t rle = 0;
   for (size_t i = 0; i < n; ++i) {
-    const wfm_problem_t& p = problems[i];
-    if (p.plen < 0 || p.tlen < 0 || (int64_t)p.plen + p.tlen > (1 << 29) || (p.plen && !p.pattern) || (p.tlen && !p.text)) {
-      delete S; h->err = "bad problem"; return WFM_E_ARG;
-    }
+    const P& p = problems[i];
     ProbMeta& m = S->meta[i];
     m.plen = p.plen; m.tlen = p.tlen; m.mode = p.mode;
     m.hint = (p.mode == WFM_MODE_END2END_BIWFA && p.score_hint > 0) ? p.score_hint : 0;
     m.pbf = std::min(std::max(p.pattern_begin_free, 0), p.plen); m.pef = std::min(std::max(p.pattern_end_free, 0), p.plen);
     m.tbf = std::min(std::max(p.text_begin_free, 0), p.tlen);    m.tef = std::min(std::max(p.text_end_free, 0), p.tlen);
     if (p.mode != WFM_MODE_ENDSFREE) { m.pbf = m.pef = m.tbf = m.tef = 0; }
-    // forward copies first (the only part that crosses PCIe), the reversed copies of the BiWFA problems behind them
     m.p_fwd = (int64_t)bytes; bytes += (size_t)p.plen + SEQ_PAD;
     m.t_fwd = (int64_t)bytes; bytes += (size_t)p.tlen + SEQ_PAD;
     const bool need_rev = (p.mode == WFM_MODE_END2END_BIWFA);
@@ -1878,7 +1891,28 @@ int wfm_upload_sequences(wfm_handle_t* h, const wfm_problem_t* problems, size_t 
     if (m.p_rev < 0) { m.p_rev = m.p_fwd; m.t_rev = m.t_fwd; }
     else { m.p_rev += (int64_t)fwd_bytes; m.t_rev += (int64_t)fwd_bytes; }
   }
-  bytes = fwd_bytes + rev_bytes + SEQ_PAD;
+  S->bytes = fwd_bytes + rev_bytes + SEQ_PAD;
+  S->rle_total = rle;
+  *fwd_bytes_out = fwd_bytes;
+}
+}  // namespace
+extern "C" {
+
+int wfm_upload_sequences(wfm_handle_t* h, const wfm_problem_t* problems, size_t n, wfm_seqset_t** out) {
+  if (!h || !out || (n && !problems)) return WFM_E_ARG;
+  *out = nullptr;
+  HIPCHK(h, hipSetDevice(h->device));
+  for (size_t i = 0; i < n; ++i) {
+    const wfm_problem_t& p = problems[i];
+    if (p.plen < 0 || p.tlen < 0 || (int64_t)p.plen + p.tlen > (1 << 29) || (p.plen && !p.pattern) || (p.tlen && !p.text)) {
+      h->err = "bad problem"; return WFM_E_ARG;
+    }
+  }
+  wfm_seqset* S = new wfm_seqset();
+  size_t fwd_bytes = 0;
+  layout_seqset(S, problems, n, &fwd_bytes);
+  const size_t bytes = S->bytes;
+  const int64_t rle = S->rle_total;
   // Only the forward sequences (with their zero padding) are written on the host and cross PCIe; the reversed copies
   // BiWFA's reverse direction reads are made on the device after the upload (half the bytes, no byte-wise host loop).
   // The forward part is assembled in a pinned staging buffer kept with the handle, by a few threads.
@@ -1974,6 +2008,230 @@ void wfm_free_sequences(wfm_handle_t* h, wfm_seqset_t* s) {
   if (s->d_seq) wfm_dfree_nosync(s->d_seq);
   if (s->d_pk) wfm_dfree_nosync(s->d_pk);
   delete s;
+}
+
+
+// ---- sequences resident on the device, problems by reference (wfmash_hip.h) ----
+namespace {
+constexpr size_t STORE_SLACK = 64;            // bytes before and behind a stored sequence (the gather kernel reads up to 15 beyond a window)
+constexpr size_t STORE_PIN_CHUNK = 8u << 20;  // raw bytes per pinned chunk of wfm_seqstore_add
+}  // namespace
+
+int wfm_seqstore_create(wfm_handle_t* h, wfm_seqstore_t** out) {
+  if (!h || !out) return WFM_E_ARG;
+  wfm_seqstore* s = new wfm_seqstore();
+  s->device = h->device;
+  *out = s;
+  return WFM_OK;
+}
+
+void wfm_seqstore_free(wfm_seqstore_t* s) {
+  if (!s) return;
+  (void)hipSetDevice(s->device);
+  (void)hipDeviceSynchronize();  // one wait serves every block
+  for (auto& q : s->seqs) if (q.block) wfm_dfree_nosync(q.block);
+  for (int k = 0; k < 2; ++k) {
+    if (s->pin[k]) (void)hipHostFree(s->pin[k]);
+    if (s->pin_ev[k]) (void)hipEventDestroy(s->pin_ev[k]);
+  }
+  delete s;
+}
+
+int wfm_seqstore_info(const wfm_seqstore_t* s, int64_t* n_seqs, int64_t* bytes) {
+  if (!s) return WFM_E_ARG;
+  std::lock_guard<std::mutex> lk(s->mu);
+  if (n_seqs) *n_seqs = (int64_t)s->seqs.size();
+  if (bytes) *bytes = s->bytes;
+  return WFM_OK;
+}
+
+int32_t wfm_seqstore_add(wfm_handle_t* h, wfm_seqstore_t* s, const char* seq, int64_t len) {
+  if (!h || !s || len < 0 || (len && !seq)) return WFM_E_ARG;
+  if (s->device != h->device) { h->err = "the sequence store belongs to another device"; return WFM_E_ARG; }
+  HIPCHK(h, hipSetDevice(h->device));
+  std::lock_guard<std::mutex> add_lk(s->add_mu);
+  wfm_seqstore::Seq q;
+  q.len = len;
+  q.block_bytes = (((size_t)len + 15) & ~(size_t)15) + 2 * STORE_SLACK;
+  if (wfm_dmalloc((void**)&q.block, q.block_bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    h->err = "out of device memory (sequence store)";
+    return WFM_E_NOMEM;
+  }
+  q.data = q.block + STORE_SLACK;  // (16-byte aligned as the block is)
+  auto fail = [&](hipError_t e) { (void)hipStreamSynchronize(h->stream); wfm_dfree(q.block); h->err = hipGetErrorString(e); return (int32_t)WFM_E_HIP; };
+  hipError_t e = hipMemsetAsync(q.block, 0, q.block_bytes, h->stream);
+  // the raw bytes in chunks through two pinned buffers (a chromosome in a pageable block must not be one pageable hipMemcpy)
+  for (int k = 0; k < 2 && e == hipSuccess && len > 0; ++k) {
+    if (!s->pin[k]) e = hipHostMalloc((void**)&s->pin[k], STORE_PIN_CHUNK, hipHostMallocDefault);
+    if (e == hipSuccess && !s->pin_ev[k]) e = hipEventCreateWithFlags(&s->pin_ev[k], hipEventDisableTiming);
+  }
+  int turn = 0;
+  for (int64_t at = 0; at < len && e == hipSuccess; at += (int64_t)STORE_PIN_CHUNK, turn ^= 1) {
+    const size_t nb = (size_t)std::min<int64_t>((int64_t)STORE_PIN_CHUNK, len - at);
+    if (at >= 2 * (int64_t)STORE_PIN_CHUNK) e = hipEventSynchronize(s->pin_ev[turn]);  // the copy that last read this buffer
+    if (e != hipSuccess) break;
+    memcpy(s->pin[turn], seq + at, nb);
+    e = hipMemcpyAsync(q.data + at, s->pin[turn], nb, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipEventRecord(s->pin_ev[turn], h->stream);
+  }
+  if (e == hipSuccess && len > 0) { launch_seq_normalize(q.data, len, h->stream); e = hipGetLastError(); }
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e != hipSuccess) return fail(e);
+  std::lock_guard<std::mutex> lk(s->mu);
+  if (s->seqs.size() >= (size_t)INT32_MAX) { wfm_dfree(q.block); h->err = "sequence store is full"; return WFM_E_ARG; }
+  s->seqs.push_back(q);
+  s->bytes += (int64_t)q.block_bytes;
+  return (int32_t)(s->seqs.size() - 1);
+}
+
+int wfm_upload_sequence_refs(wfm_handle_t* h, const wfm_seqstore_t* store, const wfm_problem_ref_t* refs, size_t n, wfm_seqset_t** out) {
+  if (!h || !out || (n && !refs)) return WFM_E_ARG;
+  *out = nullptr;
+  if (store && store->device != h->device) { h->err = "the sequence store belongs to another device"; return WFM_E_ARG; }
+  HIPCHK(h, hipSetDevice(h->device));
+  // the table as it stands (blocks never move: the pointers stay good without the lock)
+  std::vector<wfm_seqstore::Seq> table;
+  if (store) { std::lock_guard<std::mutex> lk(store->mu); table = store->seqs; }
+  size_t host_bytes = 0;
+  auto bad = [&](size_t i, const char* what) { h->err = "problem " + std::to_string(i) + ": " + what; return WFM_E_ARG; };
+  for (size_t i = 0; i < n; ++i) {
+    const wfm_problem_ref_t& p = refs[i];
+    if (p.plen < 0 || p.tlen < 0) return bad(i, "negative length");
+    if ((int64_t)p.plen + p.tlen > (1 << 29)) return bad(i, "plen + tlen exceeds 2^29");
+    const int32_t ids[2] = {p.pattern_seq, p.text_seq};
+    const int64_t offs[2] = {p.pattern_off, p.text_off};
+    const int32_t lens[2] = {p.plen, p.tlen};
+    const char* ptrs[2] = {p.pattern, p.text};
+    for (int side = 0; side < 2; ++side) {
+      if (ids[side] == -1) {
+        if (lens[side] && !ptrs[side]) return bad(i, "null host pointer for a side of non-zero length");
+        host_bytes += (size_t)lens[side];
+      } else {
+        if (ids[side] < 0 || (size_t)ids[side] >= table.size()) return bad(i, "unknown sequence id");
+        if (offs[side] < 0 || offs[side] > table[(size_t)ids[side]].len || (int64_t)lens[side] > table[(size_t)ids[side]].len - offs[side])
+          return bad(i, "window leaves its sequence");
+      }
+    }
+  }
+  wfm_seqset* S = new wfm_seqset();
+  size_t fwd_bytes = 0;
+  layout_seqset(S, refs, n, &fwd_bytes);
+  const size_t bytes = S->bytes;
+  uint8_t* d_host = nullptr;  // the host-pointer sides end to end, STORE_SLACK before and behind them
+  auto drop = [&](int rc, const std::string& msg) {
+    (void)hipStreamSynchronize(h->stream);
+    if (S->d_seq) wfm_dfree_nosync(S->d_seq);
+    if (S->d_pk) wfm_dfree_nosync(S->d_pk);
+    if (d_host) wfm_dfree_nosync(d_host);
+    delete S;
+    h->err = msg;
+    return rc;
+  };
+  // Only the host-pointer sides are assembled in the pinned staging buffer and cross PCIe, end to end into a block of their own;
+  // from there they are laid out by the same tasks as the windows of the store.
+  uint8_t* host = nullptr;
+  std::vector<uint8_t> pageable;
+  if (host_bytes) {
+    if (h->stage_cap < host_bytes) {
+      if (h->stage) (void)hipHostFree(h->stage);
+      h->stage = nullptr; h->stage_cap = 0;
+      const size_t want = host_bytes + host_bytes / 4 + (1 << 20);
+      if (hipHostMalloc((void**)&h->stage, want, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); h->stage = nullptr; }
+      else h->stage_cap = want;
+    }
+    host = h->stage;
+    if (!host) { pageable.resize(host_bytes); host = pageable.data(); }
+    if (wfm_dmalloc((void**)&d_host, host_bytes + 2 * STORE_SLACK) != hipSuccess) { (void)hipGetLastError(); d_host = nullptr; return drop(WFM_E_NOMEM, "out of device memory (staged sequences)"); }
+  }
+  if (wfm_dmalloc((void**)&S->d_seq, bytes) != hipSuccess) { (void)hipGetLastError(); S->d_seq = nullptr; return drop(WFM_E_NOMEM, "out of device memory (sequences)"); }
+  const int64_t pk_words = ((int64_t)bytes + 15) / 16;
+  if (wfm_dmalloc((void**)&S->d_pk, (size_t)(pk_words + PK_PAD_WORDS) * 4) != hipSuccess) { (void)hipGetLastError(); S->d_pk = nullptr; return drop(WFM_E_NOMEM, "out of device memory (packed sequences)"); }
+  // the tasks: per side the forward copy and, for a BiWFA problem, the reversed one, each cut into chunks; the last chunk writes the pad
+  std::vector<SeqGatherTask> tasks;
+  tasks.reserve(4 * n + 16);
+  auto add_copy = [&](const uint8_t* src, int64_t dst_off, int32_t len, bool reverse, bool complement) {
+    int32_t at = 0;
+    do {
+      const int32_t nb = std::min<int32_t>(len - at, WFM_SEQ_GATHER_CHUNK);
+      const bool last = at + nb == len;
+      // (read backwards, chunk [at, at + nb) of the copy comes from the window's bytes [len - at - nb, len - at))
+      tasks.push_back(SeqGatherTask{src + (reverse ? len - at - nb : at), S->d_seq + dst_off + at, nb, last ? SEQ_PAD : 0, reverse ? 1 : 0, complement ? 1 : 0});
+      at += nb;
+    } while (at < len);
+  };
+  size_t host_at = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const wfm_problem_ref_t& p = refs[i];
+    const ProbMeta& m = S->meta[i];
+    const bool biwfa = p.mode == WFM_MODE_END2END_BIWFA;
+    for (int side = 0; side < 2; ++side) {
+      const int32_t id = side ? p.text_seq : p.pattern_seq, len = side ? p.tlen : p.plen;
+      const int64_t fwd = side ? m.t_fwd : m.p_fwd, rev = side ? m.t_rev : m.p_rev;
+      const uint8_t* src;
+      bool rc = false;
+      if (id == -1) {
+        if (len) memcpy(host + host_at, side ? p.text : p.pattern, (size_t)len);
+        src = d_host ? d_host + STORE_SLACK + host_at : nullptr;
+        host_at += (size_t)len;
+      } else {
+        src = table[(size_t)id].data + (side ? p.text_off : p.pattern_off);
+        rc = (side ? p.text_revcomp : p.pattern_revcomp) != 0;
+      }
+      add_copy(src, fwd, len, rc, rc);            // '+': (0, 0), '-': (1, 1)
+      if (biwfa) add_copy(src, rev, len, !rc, rc);  // '+': (1, 0), '-': (0, 1)
+    }
+  }
+  hipError_t e = hipSuccess;
+  if (host_bytes) e = hipMemcpyAsync(d_host + STORE_SLACK, host, host_bytes, hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(S->d_seq, 0, SEQ_PAD, h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(S->d_seq + fwd_bytes - SEQ_PAD, 0, SEQ_PAD, h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(S->d_seq + bytes - SEQ_PAD, 0, SEQ_PAD, h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(S->d_pk + pk_words, 0, (size_t)PK_PAD_WORDS * 4, h->stream);
+  const bool timed = getenv("WFM_DEBUG") != nullptr;
+  if (e == hipSuccess && !tasks.empty()) {
+    if (h->gathertasks.ensure(tasks.size())) e = hipErrorOutOfMemory;
+    if (e == hipSuccess) e = hipMemcpyAsync(h->gathertasks.p, tasks.data(), tasks.size() * sizeof(SeqGatherTask), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess && timed) e = hipEventRecord(h->ev0, h->stream);
+    if (e == hipSuccess) { launch_seq_gather(h->gathertasks.p, (int64_t)tasks.size(), h->stream); e = hipGetLastError(); }
+    if (e == hipSuccess && timed) e = hipEventRecord(h->ev1, h->stream);
+  }
+  // the mirror of everything (forward and reversed copies), and which problems are pure ACGT: as wfm_upload_sequences
+  std::vector<int32_t> flags(n, 1);
+  std::vector<SeqRev> fj(n);
+  for (size_t i = 0; i < n; ++i) { const ProbMeta& m = S->meta[i]; fj[i] = SeqRev{m.p_fwd, m.p_fwd, m.t_fwd, m.t_fwd, m.plen, m.tlen}; }
+  if (e == hipSuccess && n && (h->seqflags.ensure(n) || h->flagjobs.ensure(n))) e = hipErrorOutOfMemory;
+  if (e == hipSuccess && n) e = hipMemsetAsync(h->seqflags.p, 1, n * sizeof(int32_t), h->stream);
+  if (e == hipSuccess && n) e = hipMemcpyAsync(h->flagjobs.p, fj.data(), n * sizeof(SeqRev), hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) {
+    launch_seq_pack(S->d_seq, S->d_pk, pk_words, (int64_t)bytes, h->flagjobs.p, (int)n, n ? h->seqflags.p : nullptr, h->stream);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess && n) e = hipMemcpyAsync(flags.data(), h->seqflags.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e != hipSuccess) return drop(WFM_E_HIP, hipGetErrorString(e));
+  if (d_host) { wfm_dfree_nosync(d_host); d_host = nullptr; }
+  S->acgt.assign(flags.begin(), flags.end());
+  if (timed && !tasks.empty()) {
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess)
+      fprintf(stderr, "[wfm] upload by reference: %zu problems, %zu gather tasks, %zu bytes written (%zu of them from host pointers) in %.3f ms = %.1f GB/s\n", n,
+              tasks.size(), bytes, host_bytes, ms, ms > 0 ? (double)bytes / (ms * 1e6) : 0.0);
+    else (void)hipGetLastError();
+  }
+  *out = S;
+  return WFM_OK;
+}
+
+int64_t wfm_download_sequences(wfm_handle_t* h, const wfm_seqset_t* s, uint8_t* out, int64_t cap) {
+  if (!h || !s || cap < 0) return WFM_E_ARG;
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t nb = std::min<size_t>((size_t)cap, s->bytes);
+  if (out && nb) {
+    HIPCHK(h, hipMemcpyAsync(out, s->d_seq, nb, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+  }
+  return (int64_t)s->bytes;
 }
 
 namespace {
@@ -2176,6 +2434,19 @@ int wfm_align_resident_rle(wfm_handle_t* h, const wfm_penalties_t* pen, wfm_seqs
                            uint32_t** runs, size_t* n_runs_total) {
   if (!runs) return WFM_E_ARG;
   return align_resident_any(h, pen, s, out, nullptr, 0, runs, n_runs_total);
+}
+
+int wfm_align_refs_rle(wfm_handle_t* h, const wfm_penalties_t* pen, const wfm_seqstore_t* store, const wfm_problem_ref_t* refs, size_t n,
+                       wfm_result_t* out, uint32_t** runs, size_t* n_runs_total) {
+  if (!h || !runs) return WFM_E_ARG;
+  *runs = nullptr;
+  if (n_runs_total) *n_runs_total = 0;
+  wfm_seqset_t* S = nullptr;
+  int rc = wfm_upload_sequence_refs(h, store, refs, n, &S);
+  if (rc != WFM_OK) return rc;
+  rc = align_resident_any(h, pen, S, out, nullptr, 0, runs, n_runs_total);
+  wfm_free_sequences(h, S);
+  return rc;
 }
 
 int wfm_align_batch(wfm_handle_t* h, const wfm_penalties_t* pen, const wfm_problem_t* problems, size_t n,

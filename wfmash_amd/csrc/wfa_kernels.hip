@@ -1421,6 +1421,114 @@ void launch_reverse(uint8_t* seq, const SeqRev* jobs, int njobs, int pad, hipStr
   hipLaunchKernelGGL(seq_reverse_kernel, dim3(njobs * 2), dim3(256), 0, st, seq, jobs, pad);
 }
 
+// ---------------------------------------------------------------------------
+// windows of device-resident sequences into a seqset (wfm_upload_sequence_refs)
+// ---------------------------------------------------------------------------
+// One workgroup per task: T.len bytes from T.src to T.dst -- read backwards when T.reverse, A<->T and C<->G swapped when
+// T.complement (every other byte, N among them, stays) -- and T.pad zero bytes behind them.  The four combinations make the
+// forward and the reversed copy of a '+' and of a '-' side from one read of the stored strand.  Source and destination have any
+// alignment: a lane owns one 16-byte aligned slot of the destination, reads the (at most two) aligned 16-byte words of the
+// source that hold its bytes, shifts them into place (v_alignbyte) and, read backwards, turns the slot round (v_perm); a word
+// is only read where it overlaps [src, src + len), so a read goes at most 15 bytes past either end of the window -- the slack
+// a store block keeps.  A slot that is not wholly inside [dst, dst + len) -- the head and the tail of a task, the pad -- is
+// written byte by byte: its other bytes belong to the neighbouring task, which runs at the same time.
+namespace {
+__device__ __forceinline__ uint32_t gather_complement4(uint32_t w) {
+  const uint32_t b1 = (w >> 1) & 0x01010101u, b3 = (w >> 3) & 0x01010101u;  // bit 1: C G N, bit 3: N (of A C G T N)
+  const uint32_t cg = b1 & ~b3, at = ~b1 & ~b3 & 0x01010101u & (w >> 6);   // (w >> 6: nothing below 0x40, the pad's zeros)
+  return w ^ (cg << 2) ^ (at | (at << 2) | (at << 4));                      // C ^ G = 0x04, A ^ T = 0x15
+}
+__device__ __forceinline__ uint32_t gather_pick(const uint32_t (&w)[8], int k) {  // w[k], k uniform over the workgroup
+  uint32_t v = w[0];
+#pragma unroll
+  for (int j = 1; j < 8; ++j) v = k == j ? w[j] : v;
+  return v;
+}
+}  // namespace
+__global__ __launch_bounds__(256) void seq_gather_kernel(const SeqGatherTask* __restrict__ tasks) {
+  const SeqGatherTask T = tasks[blockIdx.x];
+  const int64_t n = (int64_t)T.len + T.pad;
+  const uintptr_t d = (uintptr_t)T.dst, s = (uintptr_t)T.src, s_end = s + (uintptr_t)T.len;
+  const uintptr_t d0 = d & ~(uintptr_t)15;
+  const int64_t nslots = (int64_t)((d + (uintptr_t)n + 15 - d0) >> 4);
+  for (int64_t j = threadIdx.x; j < nslots; j += blockDim.x) {
+    const uintptr_t D = d0 + ((uintptr_t)j << 4);
+    const int64_t qb = (int64_t)D - (int64_t)d;  // the slot holds bytes qb .. qb + 15 of the task (qb < 0: its head)
+    uint32_t o[4] = {0u, 0u, 0u, 0u};
+    if (qb < T.len) {
+      // the 16 source bytes of the slot lie at A .. A + 15, in this order or, read backwards, in the opposite one
+      const int64_t A = T.reverse ? (int64_t)s_end - 16 - qb : (int64_t)s + qb;
+      const int64_t A0 = A & ~(int64_t)15;
+      const int sh = (int)(A & 15);
+      uint32_t w[8];
+#pragma unroll
+      for (int half = 0; half < 2; ++half) {
+        const int64_t W = A0 + 16 * half;
+        uint4 q = make_uint4(0u, 0u, 0u, 0u);
+        if (W < (int64_t)s_end && W + 16 > (int64_t)s && (half == 0 || sh != 0)) q = *reinterpret_cast<const uint4*>((uintptr_t)W);
+        w[4 * half] = q.x; w[4 * half + 1] = q.y; w[4 * half + 2] = q.z; w[4 * half + 3] = q.w;
+      }
+      uint32_t v[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int k = (sh >> 2) + i;  // k + 1 <= 7
+        const uint32_t lo = gather_pick(w, k), hi = k + 1 < 8 ? gather_pick(w, k + 1) : 0u;
+        v[i] = __builtin_amdgcn_alignbyte(hi, lo, (uint32_t)(sh & 3));
+      }
+      if (T.reverse) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) o[i] = __builtin_amdgcn_perm(0u, v[3 - i], 0x00010203u);  // the four bytes turned round
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) o[i] = v[i];
+      }
+      if (T.complement) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) o[i] = gather_complement4(o[i]);
+      }
+    }
+    if (qb >= 0 && qb + 16 <= T.len) {
+      *reinterpret_cast<uint4*>(D) = make_uint4(o[0], o[1], o[2], o[3]);
+    } else {
+      uint8_t* dst = reinterpret_cast<uint8_t*>(D);
+#pragma unroll
+      for (int b = 0; b < 16; ++b) {
+        const int64_t q = qb + b;
+        if (q >= 0 && q < n) dst[b] = q < T.len ? (uint8_t)(o[b >> 2] >> (8 * (b & 3))) : (uint8_t)0;
+      }
+    }
+  }
+}
+void launch_seq_gather(const SeqGatherTask* tasks, int64_t ntasks, hipStream_t st) {
+  if (ntasks > 0) hipLaunchKernelGGL(seq_gather_kernel, dim3((unsigned)ntasks), dim3(256), 0, st, tasks);
+}
+
+// makeUpperCaseAndValidDNA (commonFunc.hpp:132-142) in place on n bytes from a 16-byte aligned address: a..z to upper case, then
+// anything but A C G T becomes N.  16 bytes per lane; the bytes between n and the next multiple of 16 are rewritten too (slack).
+__global__ __launch_bounds__(256) void seq_normalize_kernel(uint8_t* __restrict__ seq, int64_t nwords) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nwords) return;
+  uint4 q = *reinterpret_cast<const uint4*>(seq + i * 16);
+  uint32_t w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    uint32_t out = 0;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      uint32_t c = (w[j] >> (8 * b)) & 0xffu;
+      if (c > 96u && c < 123u) c -= 32u;
+      if (!(c == 'A' || c == 'C' || c == 'G' || c == 'T')) c = 'N';
+      out |= c << (8 * b);
+    }
+    w[j] = out;
+  }
+  *reinterpret_cast<uint4*>(seq + i * 16) = make_uint4(w[0], w[1], w[2], w[3]);
+}
+void launch_seq_normalize(uint8_t* seq, int64_t nbytes, hipStream_t st) {
+  const int64_t nwords = (nbytes + 15) / 16;
+  if (nwords > 0) hipLaunchKernelGGL(seq_normalize_kernel, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, st, seq, nwords);
+}
+
 #ifdef WFM_PROFILE_SECTIONS
 void read_sections(long long* out) { (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_sec), sizeof(long long) * 8); }
 #endif

@@ -72,6 +72,8 @@ struct Fetched {
   std::string qry;    // strand-adjusted query window
   uint64_t ref_start = 0, ref_total = 0, q_total = 0;
   uint64_t row_no = 0;  // the row's number in the mapping file
+  int32_t ref_seq = -1, qry_seq = -1;  // resident_sequences: the sides' ids in the device's store (-1: by host pointer)
+  bool lazy = false;                   // ... both are there and the output is PAF: the bases are fetched only on demand
 };
 
 }  // namespace
@@ -86,6 +88,43 @@ Aligner::Aligner(const Parameters& p, const std::vector<wfm_handle_t*>& g) : par
   ref = wfmash_host::open_shared(param.refSequences.front());
   if (param.querySequences.front() == param.refSequences.front()) query = ref.get();
   else { query_own = wfmash_host::open_shared(param.querySequences.front()); query = query_own.get(); }
+}
+
+Aligner::~Aligner() {
+  for (auto& kv : stores) if (kv.second && kv.second->store) wfm_seqstore_free(kv.second->store);
+}
+
+Aligner::DeviceStore* Aligner::device_store(wfm_handle_t* h) {
+  std::lock_guard<std::mutex> lk(stores_mu);
+  auto& ds = stores[wfm_device(h)];
+  if (!ds) {
+    ds.reset(new DeviceStore());
+    if (wfm_seqstore_create(h, &ds->store) != WFM_OK) throw std::runtime_error("[wfmash::align] cannot create the device sequence store");
+    // (the figure the host side uses for the sequences it keeps, WFM_FASTA_KEEP_GB; a decimal, so that a test can ask for kilobytes)
+    const char* g = getenv("WFM_SEQSTORE_GB");
+    const double gb = g && *g ? atof(g) : 32.0;
+    ds->budget = gb > 0 ? (int64_t)(gb * 1073741824.0) : 0;
+  }
+  return ds.get();
+}
+
+int32_t Aligner::resident_id(wfm_handle_t* h, DeviceStore& ds, const wfmash_host::FastaStore* fa, int idx) {
+  if (idx < 0) return -1;
+  std::lock_guard<std::mutex> lk(ds.mu);
+  const auto key = std::make_pair(fa, idx);
+  auto it = ds.ids.find(key);
+  if (it != ds.ids.end()) return it->second;
+  int32_t id = -1;
+  const int64_t len = fa->length(idx);
+  if (len > 0 && len <= ds.budget - ds.used) {
+    const wfmash_host::SeqView v = fa->sequence(idx);
+    std::lock_guard<std::mutex> hl(wflign::handle_lock(h));
+    id = wfm_seqstore_add(h, ds.store, v.data(), (int64_t)v.size());
+    if (id >= 0) ds.used += len;
+    else { std::cerr << "[wfmash::align] " << fa->name(idx) << " stays on the host: " << wfm_last_error(h) << std::endl; id = -1; }
+  }
+  ds.ids.emplace(key, id);
+  return id;
 }
 
 void Aligner::parseMashmapRow(const std::string& line, MappingBoundaryRow& row, uint64_t target_padding, uint64_t query_padding) {
@@ -193,24 +232,41 @@ std::string Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<std::stri
   std::vector<std::string>().swap(lines);
   const double ms_parse = since(tb0);
   const auto tb1 = std::chrono::steady_clock::now();
+  // resident_sequences: the sides' ids in the device's store, each sequence added on first use.  A record with both sides there
+  // is not fetched up front when the output is PAF (SAM needs the bases for SEQ and MD).
+  DeviceStore* ds = param.resident_sequences ? device_store(gpu_handle) : nullptr;
+  if (ds) {
+    for (Fetched& f : rows) {
+      if (f.row.rStartPos >= 0 && f.row.rEndPos > f.row.rStartPos && (uint64_t)f.row.rEndPos <= f.ref_total)
+        f.ref_seq = resident_id(gpu_handle, *ds, ref.get(), ref->find(f.row.refId));
+      if (f.row.qStartPos >= 0 && f.row.qEndPos > f.row.qStartPos && (uint64_t)f.row.qEndPos <= f.q_total)
+        f.qry_seq = resident_id(gpu_handle, *ds, query, query->find(f.row.qId));
+      f.lazy = f.ref_seq >= 0 && f.qry_seq >= 0 && !param.sam_format;
+    }
+  }
+  // the padded reference window and the strand-adjusted query window of a row, normalised
+  auto fetch_windows = [&](Fetched& f) {
+    const int64_t ref_size = (int64_t)f.ref_total;
+    const uint64_t head_pad = (uint64_t)f.row.rStartPos >= param.wflign_max_len_minor ? param.wflign_max_len_minor : (uint64_t)f.row.rStartPos;
+    const uint64_t tail_pad = (uint64_t)(ref_size - f.row.rEndPos) >= param.wflign_max_len_minor ? param.wflign_max_len_minor : (uint64_t)(ref_size - f.row.rEndPos);
+    f.ref = ref->fetch(f.row.refId, f.row.rStartPos - (int64_t)head_pad, f.row.rEndPos + (int64_t)tail_pad - 1);
+    if (f.ref.empty()) throw std::runtime_error("Failed to fetch reference sequence");
+    std::string q = query->fetch(f.row.qId, f.row.qStartPos, f.row.qEndPos - 1);
+    if (q.empty()) throw std::runtime_error("Failed to fetch query sequence");
+    f.ref_start = (uint64_t)f.row.rStartPos - head_pad;
+    upper_valid_dna(f.ref);
+    upper_valid_dna(q);
+    f.qry = f.row.strand == FWD ? std::move(q) : revcomp(q);
+  };
   std::vector<std::string> fetch_error(rows.size());
   {
     std::atomic<size_t> next{0};
     auto work = [&] {
       for (size_t k; (k = next.fetch_add(1)) < rows.size();) {
         Fetched& f = rows[k];
+        if (f.lazy) continue;
         try {
-          const int64_t ref_size = (int64_t)f.ref_total;
-          const uint64_t head_pad = (uint64_t)f.row.rStartPos >= param.wflign_max_len_minor ? param.wflign_max_len_minor : (uint64_t)f.row.rStartPos;
-          const uint64_t tail_pad = (uint64_t)(ref_size - f.row.rEndPos) >= param.wflign_max_len_minor ? param.wflign_max_len_minor : (uint64_t)(ref_size - f.row.rEndPos);
-          f.ref = ref->fetch(f.row.refId, f.row.rStartPos - (int64_t)head_pad, f.row.rEndPos + (int64_t)tail_pad - 1);
-          if (f.ref.empty()) throw std::runtime_error("Failed to fetch reference sequence");
-          std::string q = query->fetch(f.row.qId, f.row.qStartPos, f.row.qEndPos - 1);
-          if (q.empty()) throw std::runtime_error("Failed to fetch query sequence");
-          f.ref_start = (uint64_t)f.row.rStartPos - head_pad;
-          upper_valid_dna(f.ref);
-          upper_valid_dna(q);
-          f.qry = f.row.strand == FWD ? std::move(q) : revcomp(q);
+          fetch_windows(f);
         } catch (const std::exception& e) {
           fetch_error[k] = e.what();
           if (fetch_error[k].empty()) fetch_error[k] = "error";
@@ -233,24 +289,43 @@ std::string Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<std::stri
   }
   if (fetched.empty()) return out;
   std::vector<wflign::BiwfaRecord> recs(fetched.size());
+  // the host pointers of a record whose windows have been fetched
+  auto point_at = [](wflign::BiwfaRecord& r, const Fetched& f) {
+    const uint64_t skip = (uint64_t)f.row.rStartPos - f.ref_start;
+    r.query = f.qry.data();
+    r.target = f.ref.data() + skip;
+    r.target_avail = f.ref.size() - skip;
+  };
   for (size_t k = 0; k < fetched.size(); ++k) {
     const Fetched& f = fetched[k];
     wflign::BiwfaRecord& r = recs[k];
     r.query_name = f.row.qId;
-    r.query = f.qry.data();
     r.query_total_length = f.q_total;
     r.query_offset = (uint64_t)f.row.qStartPos;
-    r.query_length = f.qry.size();
+    r.query_length = f.lazy ? (uint64_t)(f.row.qEndPos - f.row.qStartPos) : f.qry.size();
     r.query_is_rev = f.row.strand != FWD;
     r.target_name = f.row.refId;
-    const uint64_t skip = (uint64_t)f.row.rStartPos - f.ref_start;
-    r.target = f.ref.data() + skip;
     r.target_total_length = f.ref_total;
     r.target_offset = (uint64_t)f.row.rStartPos;
     r.target_length = (uint64_t)(f.row.rEndPos - f.row.rStartPos);
-    r.target_avail = f.ref.size() - skip;
+    if (!f.lazy) point_at(r, f);
+    r.target_seq = f.ref_seq; r.target_win_off = f.row.rStartPos;
+    r.query_seq = f.qry_seq; r.query_win_off = f.row.qStartPos;
     r.mashmap_estimated_identity = f.row.mashmap_estimated_identity;
     r.chain_id = f.row.chain_id; r.chain_length = f.row.chain_length; r.chain_pos = f.row.chain_pos;
+  }
+  wflign::ResidentSeqs resident;
+  if (ds) {
+    resident.store = ds->store;
+    // (from the pipeline's worker threads, one record each: exactly the eager fetch)
+    resident.fetch = [&](size_t k) {
+      try {
+        fetch_windows(fetched[k]);
+        point_at(recs[k], fetched[k]);
+      } catch (const std::exception& e) {
+        std::cerr << "[wfmash::align] Error fetching the bases of a record: " << e.what() << std::endl;
+      }
+    };
   }
   const double ms_fetch = since(tb1);
   const auto tb2 = std::chrono::steady_clock::now();
@@ -260,8 +335,9 @@ std::string Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<std::stri
   fmt.no_seq_in_sam = param.no_seq_in_sam;
   fmt.emit_md_tag = param.emit_md_tag;
   fmt.threads = threads;
-  const int rc = wflign::do_biwfa_alignment_batch(gpu_handle, recs, pen, param.disable_chain_patching, pp, &st, fmt);
+  const int rc = wflign::do_biwfa_alignment_batch(gpu_handle, recs, pen, param.disable_chain_patching, pp, &st, fmt, ds ? &resident : nullptr);
   if (rc < 0) throw std::runtime_error(std::string("[wfmash::align] GPU alignment failed: ") + st.error);
+  sum.lazy_fetches += resident.lazy_fetches.load();
   sum.cells += st.cells; sum.ms_gpu += st.ms_gpu;
   sum.cells_tile += st.cells_tile; sum.tile_launches += st.tile_launches; sum.ms_tile += st.ms_tile;
   sum.busy.insert(sum.busy.end(), st.busy.begin(), st.busy.end());
@@ -276,6 +352,7 @@ std::string Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<std::stri
   const auto tb3 = std::chrono::steady_clock::now();
   for (size_t k = 0; k < recs.size(); ++k) {
     sum.records++;
+    sum.records_resident += recs[k].target_seq >= 0 && recs[k].query_seq >= 0;
     sum.aligned_bp += (uint64_t)(fetched[k].row.qEndPos - fetched[k].row.qStartPos);
     if (recs[k].paf.empty()) continue;
     // PAF: the record is already in the form processMappingRecord gives it (fields re-joined with single tabs,
@@ -514,6 +591,7 @@ Summary Aligner::compute() {
       const Summary& p = part[wk];
       sum.records += p.records; sum.aligned_bp += p.aligned_bp; sum.written += p.written; sum.skipped += p.skipped;
       sum.cells += p.cells;
+      sum.records_resident += p.records_resident; sum.lazy_fetches += p.lazy_fetches;
       sum.cells_tile += p.cells_tile; sum.tile_launches += p.tile_launches; sum.ms_tile += p.ms_tile; sum.ms_tags += p.ms_tags;
       sum.ms_rows += p.ms_rows; sum.ms_fetch += p.ms_fetch; sum.ms_wflign += p.ms_wflign; sum.ms_text += p.ms_text; sum.batches += p.batches;
       iv[wk % ngpu].insert(iv[wk % ngpu].end(), p.busy.begin(), p.busy.end());

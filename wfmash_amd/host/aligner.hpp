@@ -6,7 +6,9 @@
 #pragma once
 
 #include <cstdint>
+#include <map>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -46,6 +48,9 @@ struct Parameters {
   // records 0.63 s, 6 batches 0.51 s; a 1.2 k-record file is best left whole)
   uint64_t batch_bases = 160ull << 20;
   size_t batch_records = 1536;
+  // (not in the reference) whole sequences stay on the device and the problems name their windows by reference
+  // (wfmh_align_params_t::resident_sequences); off by default
+  bool resident_sequences = false;
 };
 
 // MappingBoundaryRow (align_types.hpp:17)
@@ -69,6 +74,8 @@ struct Summary {
   double ms_rows = 0, ms_fetch = 0, ms_wflign = 0, ms_text = 0;  // host stages, summed over the batches
   double ms_tags = 0;  // WFM_RECORD_TAGS (a diagnostic): writing the records' tags, lock wait included, summed over the batches
   uint64_t batches = 0;
+  uint64_t records_resident = 0;   // resident_sequences: records whose two sides both came from the device's store
+  uint64_t lazy_fetches = 0;       // ... and of those, the ones whose bases the host fetched after all (for the swizzle)
   std::vector<std::pair<double, double>> busy;  // a worker's device-busy intervals (merged per device at the end of compute())
 };
 
@@ -77,6 +84,7 @@ class Aligner {
   Aligner(const Parameters& p, wfm_handle_t* gpu);
   // one handle per GPU of the node: batches of records go to whichever device is free
   Aligner(const Parameters& p, const std::vector<wfm_handle_t*>& gpus);
+  ~Aligner();
   // throws std::runtime_error on malformed rows (computeAlignments.hpp:199-201,292-297)
   static void parseMashmapRow(const std::string& line, MappingBoundaryRow& row, uint64_t target_padding,
                               uint64_t query_padding = 0);
@@ -95,6 +103,19 @@ class Aligner {
   std::vector<wfm_handle_t*> gpus;
   std::shared_ptr<wfmash_host::FastaStore> ref, query_own;
   const wfmash_host::FastaStore* query = nullptr;
+  // resident_sequences: one store per device, shared by all of that device's workers.  A sequence is added on first use; one that
+  // does not fit what is left of the budget (WFM_SEQSTORE_GB, read when the store is made) never is -- there is no eviction -- and
+  // its windows stay host-pointer sides.
+  struct DeviceStore {
+    wfm_seqstore_t* store = nullptr;
+    std::mutex mu;
+    int64_t budget = 0, used = 0;
+    std::map<std::pair<const wfmash_host::FastaStore*, int>, int32_t> ids;  // -1: did not fit
+  };
+  std::mutex stores_mu;
+  std::map<int, std::unique_ptr<DeviceStore>> stores;  // by device
+  DeviceStore* device_store(wfm_handle_t* h);
+  int32_t resident_id(wfm_handle_t* h, DeviceStore& ds, const wfmash_host::FastaStore* fa, int idx);
 };
 
 }  // namespace align

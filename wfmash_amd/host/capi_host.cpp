@@ -39,7 +39,7 @@ void wfmh_align_default_params(wfmh_align_params_t* p) {
   p->target_padding = 1000; p->query_padding = 1000; p->wflign_max_len_minor = 128000;
   p->disable_chain_patching = 0;
   p->sam_format = 0; p->emit_md_tag = 0; p->no_seq_in_sam = 0;
-  p->threads = 0; p->pad_ = 0;
+  p->threads = 0; p->resident_sequences = 0;
 }
 
 int wfmh_align_paf(wfm_handle_t* h, const char* target_fasta, const char* query_fasta, const char* mapping_paf,
@@ -74,6 +74,7 @@ int wfmh_align_paf_multi(wfm_handle_t* const* handles, int n, const char* target
     ap.wflign_max_len_minor = d.wflign_max_len_minor;
     ap.disable_chain_patching = d.disable_chain_patching != 0;
     ap.sam_format = d.sam_format != 0; ap.emit_md_tag = d.emit_md_tag != 0; ap.no_seq_in_sam = d.no_seq_in_sam != 0;
+    ap.resident_sequences = d.resident_sequences != 0;
     ap.threads = d.threads > 0 ? d.threads : (int)std::max(1u, std::thread::hardware_concurrency());
     align::Aligner aligner(ap, std::vector<wfm_handle_t*>(handles, handles + n));
     const align::Summary s = aligner.compute();
@@ -84,6 +85,7 @@ int wfmh_align_paf_multi(wfm_handle_t* const* handles, int n, const char* target
       summary->batches = s.batches;
       summary->cells_tile = s.cells_tile; summary->tile_launches = s.tile_launches; summary->ms_tile = s.ms_tile;
       summary->ms_tags = s.ms_tags;
+      summary->records_resident = s.records_resident; summary->lazy_fetches = s.lazy_fetches;
     }
     return WFM_OK;
   } catch (const std::exception& e) {
@@ -104,6 +106,13 @@ int wfmh_align_paf_multi(wfm_handle_t* const* handles, int n, const char* target
 extern "C" {
 
 void wfmh_free(char* p) { free(p); }
+
+// test hook: the sub-window translation of the problems by reference (wflign::sub_window_off)
+void wfmh_test_subwindow(int64_t win_start, int64_t win_end, int rev, int64_t a, int64_t b, int64_t* out_start, int64_t* out_end) {
+  const int64_t off = wflign::sub_window_off(win_start, win_end - win_start, rev != 0, a, b);
+  if (out_start) *out_start = off;
+  if (out_end) *out_end = off + (b - a);
+}
 
 // test hook: the align driver's batch plan (Aligner::plan_batch_bytes), pure arithmetic
 unsigned long long wfmh_test_plan_batch_bytes(unsigned long long file_bytes, unsigned long long rows, unsigned long long row_bytes,

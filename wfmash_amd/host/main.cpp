@@ -14,6 +14,8 @@
 //                                              of the map path or of -K
 //   --streaming-minhash                        target sketches from one bottom-s MinHash per sequence instead of winnowed
 //                                              minmers (:137, :177; winSketch.hpp:467-497); no effect with -K or -i
+//   --resident-seqs                            whole sequences stay on the device (up to WFM_SEQSTORE_GB, 32) and the align phase names
+//                                              its windows by reference instead of fetching and uploading each; off by default
 //   --hg-filter n,D,conf                       numerator, ANI difference and confidence of the L1 / L2 cutoffs (:94, :700-725)
 //   -B DIR / -Z                                directory of the map-to-align hand-off file [cwd] / keep that file (:134-135)
 //   --quiet, --ani-sketch-size INT             accepted and without effect: there is no progress meter, and the identity
@@ -89,6 +91,7 @@ static void usage() {
           "            --scaffold-out FILE write the scaffold chains\n"
           "            -Y C group delimiter [#]   -X self maps   -L lower triangular   -t INT threads [1]\n"
           "  alignment -g x,o1,e1,o2,e2 [5,8,2,24,1]   -E INT target padding   -U INT query padding   -a SAM   -d MD tag\n"
+          "            --resident-seqs keep whole sequences on the GPU and align windows of them by reference [off]\n"
           "  other     --out FILE [stdout]   --device INT [0]   --gpus N|all [1] GPUs of this node, starting at --device\n"
           "            -B DIR directory of the hand-off file [cwd]   -Z keep the hand-off file   --quiet (no effect)\n");
 }
@@ -227,6 +230,7 @@ int main(int argc, char** argv) {
     else if (a == "--no-patching") ap.disable_chain_patching = 1;
     else if (a == "-a" || a == "--sam") ap.sam_format = 1;
     else if (a == "-d" || a == "--md-tag") ap.emit_md_tag = 1;
+    else if (a == "--resident-seqs") ap.resident_sequences = 1;
     else if (a == "-h" || a == "--help") { usage(); return 0; }
     else if (a == "-v" || a == "--version") { std::printf("%s\n", WFMASH_HIP_VERSION); return 0; }
     else if (a[0] != '-') { if (target.empty()) target = a; else query = a; }

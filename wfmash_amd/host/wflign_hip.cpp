@@ -600,6 +600,7 @@ void for_each_record(size_t n, int threads, F&& fn) {
 // A handle runs one batch at a time; several host threads may feed the same GPU (the align driver keeps up to three
 // batches per device in flight so that the host stages of one overlap the device stages of another): calls are
 // serialised here.
+}  // namespace
 std::mutex& handle_lock(wfm_handle_t* h) {
   static std::mutex reg;
   static std::map<wfm_handle_t*, std::unique_ptr<std::mutex>> locks;
@@ -608,9 +609,13 @@ std::mutex& handle_lock(wfm_handle_t* h) {
   if (!m) m.reset(new std::mutex());
   return *m;
 }
+namespace {
 
+// The problems of one device call, always written by reference (a side without a store id carries its host pointer); without a
+// store they go to the device as plain wfm_problem_t, as they always have.
 struct GpuBatch {
-  std::vector<wfm_problem_t> probs;
+  std::vector<wfm_problem_ref_t> probs;
+  const wfm_seqstore_t* store = nullptr;
   std::vector<wfm_result_t> res;
   std::vector<uint32_t> flags;  // WFM_PF_* per problem (wfm_get_problem_flags), fetched while the handle is still ours
   uint32_t* runs = nullptr;
@@ -622,7 +627,17 @@ struct GpuBatch {
     runs = nullptr;
     if (probs.empty()) return 0;
     std::lock_guard<std::mutex> lk(handle_lock(h));
-    const int rc = wfm_align_batch_rle(h, &pen, probs.data(), probs.size(), res.data(), &runs, nullptr);
+    int rc;
+    if (store) rc = wfm_align_refs_rle(h, &pen, store, probs.data(), probs.size(), res.data(), &runs, nullptr);
+    else {
+      std::vector<wfm_problem_t> plain(probs.size());
+      for (size_t i = 0; i < probs.size(); ++i) {
+        const wfm_problem_ref_t& r = probs[i];
+        plain[i] = wfm_problem_t{r.pattern, r.plen, r.text, r.tlen, r.mode, r.pattern_begin_free, r.pattern_end_free,
+                                 r.text_begin_free, r.text_end_free, r.score_hint, 0};
+      }
+      rc = wfm_align_batch_rle(h, &pen, plain.data(), plain.size(), res.data(), &runs, nullptr);
+    }
     if (rc < 0) err = wfm_last_error(h);
     flags.assign(probs.size(), 0u);
     if (rc >= 0) wfm_get_problem_flags(h, flags.data(), flags.size());
@@ -663,19 +678,30 @@ int32_t score_hint(const BiwfaRecord& r, const wflign_penalties_t& penalties) {
   return hint < 1e9 ? (int32_t)hint : 0;
 }
 
-wfm_problem_t head_problem(const BiwfaRecord& r, const Erosion& e) {  // wflign.cpp:280-305
-  wfm_problem_t p{};
-  p.pattern = r.target; p.plen = (int32_t)e.target_eroded;
-  p.text = r.query; p.tlen = (int32_t)e.query_eroded;
+// bases [ta, ta + plen) of the record's target window against [qa, qa + tlen) of its (strand-adjusted) query window: by host
+// pointer, or -- where the record names its sides in the device's store -- as the sub-windows of the stored sequences
+wfm_problem_ref_t window_problem(const BiwfaRecord& r, uint64_t ta, uint64_t plen, uint64_t qa, uint64_t tlen) {
+  wfm_problem_ref_t p{};
+  p.plen = (int32_t)plen; p.tlen = (int32_t)tlen;
+  p.pattern_seq = r.target_seq; p.text_seq = r.query_seq;
+  if (r.target_seq >= 0) p.pattern_off = sub_window_off(r.target_win_off, (int64_t)r.target_length, false, (int64_t)ta, (int64_t)(ta + plen));
+  else p.pattern = r.target + ta;
+  if (r.query_seq >= 0) {
+    p.text_off = sub_window_off(r.query_win_off, (int64_t)r.query_length, r.query_is_rev, (int64_t)qa, (int64_t)(qa + tlen));
+    p.text_revcomp = r.query_is_rev ? 1 : 0;
+  } else p.text = r.query + qa;
+  return p;
+}
+
+wfm_problem_ref_t head_problem(const BiwfaRecord& r, const Erosion& e) {  // wflign.cpp:280-305
+  wfm_problem_ref_t p = window_problem(r, 0, e.target_eroded, 0, e.query_eroded);
   p.mode = WFM_MODE_ENDSFREE;
   p.pattern_begin_free = (int32_t)e.target_eroded; p.pattern_end_free = 0;
   p.text_begin_free = (int32_t)e.query_eroded; p.text_end_free = 0;
   return p;
 }
-wfm_problem_t tail_problem(const BiwfaRecord& r, const Erosion& e) {  // wflign.cpp:368-397
-  wfm_problem_t p{};
-  p.pattern = r.target + r.target_length - e.target_eroded; p.plen = (int32_t)e.target_eroded;
-  p.text = r.query + r.query_length - e.query_eroded; p.tlen = (int32_t)e.query_eroded;
+wfm_problem_ref_t tail_problem(const BiwfaRecord& r, const Erosion& e) {  // wflign.cpp:368-397
+  wfm_problem_ref_t p = window_problem(r, r.target_length - e.target_eroded, e.target_eroded, r.query_length - e.query_eroded, e.query_eroded);
   p.mode = WFM_MODE_ENDSFREE;
   p.pattern_begin_free = 0; p.pattern_end_free = (int32_t)e.target_eroded;
   p.text_begin_free = 0; p.text_end_free = (int32_t)e.query_eroded;
@@ -708,7 +734,9 @@ Erosion scan_tail(const CigarOps& ops, size_t* looked_from) {
 // the two patches of all records of the batch go to the device in ONE call.  The remaining records (short ones, where
 // the scans overlap) get their tail scanned after their head is in place and share a second, small call.
 int do_biwfa_alignment_batch(wfm_handle_t* h, std::vector<BiwfaRecord>& recs, const wflign_penalties_t& penalties,
-                             bool disable_chain_patching, const PafParams& pp, BiwfaStats* stats, const OutputFormat& fmt) {
+                             bool disable_chain_patching, const PafParams& pp, BiwfaStats* stats, const OutputFormat& fmt,
+                             ResidentSeqs* resident) {
+  const wfm_seqstore_t* store = resident ? resident->store : nullptr;
   const wfm_penalties_t pen{penalties.mismatch, penalties.gap_opening1, penalties.gap_extension1,
                             penalties.gap_opening2, penalties.gap_extension2};
   const bool dbg = getenv("WFM_DEBUG") != nullptr;
@@ -730,11 +758,10 @@ int do_biwfa_alignment_batch(wfm_handle_t* h, std::vector<BiwfaRecord>& recs, co
   std::vector<char> over_budget(n, 0);  // WFM_ST_OOM: dropped like every record whose main alignment fails, but not silently
   {
     GpuBatch g;
+    g.store = store;
     g.probs.reserve(n);
     for (const auto& r : recs) {
-      wfm_problem_t p{};
-      p.pattern = r.target; p.plen = (int32_t)r.target_length;
-      p.text = r.query; p.tlen = (int32_t)r.query_length;
+      wfm_problem_ref_t p = window_problem(r, 0, r.target_length, 0, r.query_length);
       p.mode = WFM_MODE_END2END_BIWFA;
       p.score_hint = score_hint(r, penalties);
       g.probs.push_back(p);
@@ -770,6 +797,7 @@ int do_biwfa_alignment_batch(wfm_handle_t* h, std::vector<BiwfaRecord>& recs, co
   if (!disable_chain_patching) {
     // ---- stages 2 + 3: head patches (wflign.cpp:241-320) and tail patches (wflign.cpp:323-418) ----
     GpuBatch g;
+    g.store = store;
     for (size_t i = 0; i < n; ++i) {
       if (!recs[i].ok) continue;
       Work& w = wk[i];
@@ -813,6 +841,7 @@ int do_biwfa_alignment_batch(wfm_handle_t* h, std::vector<BiwfaRecord>& recs, co
     });
     if (later) {  // short records: the tail scan on the head-patched CIGAR, as the reference runs it
       GpuBatch g2;
+      g2.store = store;
       std::vector<size_t> owner;
       for (size_t i = 0; i < n; ++i) {
         Work& w = wk[i];
@@ -842,9 +871,17 @@ int do_biwfa_alignment_batch(wfm_handle_t* h, std::vector<BiwfaRecord>& recs, co
   for_each_record(n, nt, [&](size_t ri) {
     BiwfaRecord& r = recs[ri];
     if (!r.ok) return;
-    const int64_t qn = (int64_t)r.query_length, tn = (int64_t)(r.target_avail ? r.target_avail : r.target_length);
-    try_swap_start_ops(r.ops, r.query, qn, r.target, tn);
-    try_swap_end_ops(r.ops, r.query, qn, r.target, tn);
+    if (!r.query || !r.target) {
+      // a record that came by reference, without its bases: the two swaps read bases only behind these two patterns
+      const size_t no = r.ops.size();
+      const bool may_swap = no >= 2 && ((r.ops[0].second == '=' && r.ops[1].second == 'D') || (r.ops[no - 2].second == 'D' && r.ops[no - 1].second == '='));
+      if (may_swap && resident && resident->fetch) { resident->fetch(ri); resident->lazy_fetches.fetch_add(1); }
+    }
+    if (r.query && r.target) {
+      const int64_t qn = (int64_t)r.query_length, tn = (int64_t)(r.target_avail ? r.target_avail : r.target_length);
+      try_swap_start_ops(r.ops, r.query, qn, r.target, tn);
+      try_swap_end_ops(r.ops, r.query, qn, r.target, tn);
+    }
     if (fmt.paf_format_else_sam)
       write_alignment_paf_ops(r.paf, r.ops, r.query_name, r.query_total_length, r.query_offset, r.query_length,
                               r.query_is_rev, r.target_name, r.target_total_length, r.target_offset, pp,

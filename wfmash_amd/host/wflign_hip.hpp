@@ -13,7 +13,10 @@
 // and CIGARs are runs (count, op) from the device to the record's text: nothing is expanded to one byte per base.
 #pragma once
 
+#include <atomic>
 #include <cstdint>
+#include <functional>
+#include <mutex>
 #include <string>
 #include <utility>
 #include <vector>
@@ -109,6 +112,11 @@ struct BiwfaRecord {
   uint64_t target_avail = 0;         // bytes readable from `target` (length incl. tail padding)
   float mashmap_estimated_identity = 0;
   int32_t chain_id = -1, chain_length = 1, chain_pos = 1;
+  // The two windows by reference (ResidentSeqs): id in the device's sequence store (-1: the side goes by its host pointer), forward
+  // offset of the window in that sequence; the query's strand is query_is_rev.  With both ids set `query` and `target` may be null
+  // (PAF output): the record's bases are then fetched on the host only if the swizzle asks for them.
+  int32_t target_seq = -1, query_seq = -1;
+  int64_t target_win_off = 0, query_win_off = 0;
   // outputs
   bool ok = false;
   int32_t score = -1;
@@ -127,6 +135,26 @@ struct BiwfaStats {
   std::vector<std::pair<double, double>> busy;  // when kernels of this batch's device calls ran (ms on the device's clock, wfm_get_busy_intervals)
 };
 
+// The sub-window [a, b) of a side that is the window of win_len bases at forward offset win_off of a stored sequence,
+// reverse-complemented when rev: the forward offset of the same bases (their length stays b - a, the strand flag stays rev).
+// For a '-' record the sub-window [a, b) of the reverse-complemented query window [qs, qe) is the forward window [qe - b, qe - a).
+inline int64_t sub_window_off(int64_t win_off, int64_t win_len, bool rev, int64_t a, int64_t b) {
+  (void)a;
+  return rev ? win_off + win_len - b : win_off + a;
+}
+
+// Problems by reference for a batch (wfmh_align_params_t::resident_sequences): the store of the handle's device, and how the host
+// gets at the bases of a record that came without them -- fetch(i) fills recs[i].query / target / target_avail exactly as the
+// eager path does (fetch + makeUpperCaseAndValidDNA + reverse complement); it is called from the batch's worker threads.
+struct ResidentSeqs {
+  const wfm_seqstore_t* store = nullptr;
+  std::function<void(size_t)> fetch;
+  std::atomic<uint64_t> lazy_fetches{0};
+};
+
+// A handle runs one call at a time; the mutex every caller of a handle's device entry points holds meanwhile.
+std::mutex& handle_lock(wfm_handle_t* h);
+
 struct OutputFormat {
   bool paf_format_else_sam = true;   // wflign.cpp:434
   bool no_seq_in_sam = false;
@@ -136,6 +164,6 @@ struct OutputFormat {
 
 int do_biwfa_alignment_batch(wfm_handle_t* h, std::vector<BiwfaRecord>& recs, const wflign_penalties_t& penalties,
                              bool disable_chain_patching, const PafParams& pp, BiwfaStats* stats,
-                             const OutputFormat& fmt = OutputFormat());
+                             const OutputFormat& fmt = OutputFormat(), ResidentSeqs* resident = nullptr);
 
 }  // namespace wflign
