@@ -107,6 +107,31 @@ def test_balanced_root_past_its_band_resumes_on_a_wider_ring(oracle, monkeypatch
     assert g[1] >= 1, g
 
 
+def test_the_rings_the_driver_used_are_the_planner_s(oracle, monkeypatch, capfd):
+    """One pair of the case above: every grown ring the level driver reports -- band, columns, tile kernels or step kernel alone --
+    is what plan_ring (csrc/wfa_plan.h, held on a CPU by tests/test_ring_plan_cpu.py) gives for that job: a root of 80 000 x its
+    text under 128 MiB that has spent the band it had before (the guessed 4312 at first, then the band of its last grown ring;
+    the same input once more where a resumed job is sent back to score 0 on the band it has)."""
+    items = _balanced(0x1001, 80_000, 0.04, 1)
+    h = _handle(monkeypatch, 128)
+    try:
+        _check_batch(h, oracle, items)
+    finally:
+        h.close()
+    err = capfd.readouterr().err
+    lines = re.findall(r"\[wfm\] grown ring: problem (\d+), (\w+) of (\d+) x (\d+): band (\d+), (\d+) columns on the (tile kernels|step kernel alone)", err)
+    assert lines, err[-2000:]
+    had, handed = 4096 + TILE_CHUNK * TILE_T + 16, None  # the band of the job's last ring; the band the planner was last handed
+    for prob, kind, pl, tl, band, cols, kernel in lines:
+        print(f"grown ring: {kind} {pl} x {tl}: band {band}, {cols} columns on the {kernel}; the band it had: {had}")
+        assert (int(prob), kind, int(pl), int(tl)) == (0, "root", 80_000, len(items[0][1]))
+        before = handed if int(band) == had else had
+        p = capi.ring_plan(int(pl), int(tl), 128 << 20, noband=1, band=before, use_band=True, over_budget=True)
+        assert p is not None and p["grown"], (before, p)
+        assert (p["band"], p["width"], p["tile_it"]) == (int(band), int(cols), kernel == "tile kernels"), (before, p)
+        had, handed = int(band), before
+
+
 def test_a_resumed_job_that_meets_next_to_its_snapshot_starts_again(oracle, monkeypatch, capfd):
     """A snapshot holds the gap components only as deep as the next tile block loads them; a resumed job whose directions meet
     within 26 scores of it would hand rows on that are not there, and runs again from score 0 on the same band.  Forced here for

@@ -1125,6 +1125,46 @@ def host_plan_batch_bytes(file_bytes, rows, row_bytes, row_bases_sum, batch_reco
     return int(L.wfmh_test_plan_batch_bytes(file_bytes, rows, row_bytes, row_bases_sum, batch_records, batch_bases, nworkers, ngpu, min_batches, 1 if level else 0))
 
 
+SCORE_NONE, SUB_NONE = 2**31 - 1, 1 << 29  # Node::score_rem of a root; "no bound of the score" (csrc/wfa_device.h)
+
+
+def ring_plan(pl, tl, mem_budget, score_rem=SCORE_NONE, sub=SUB_NONE, noband=0, band=0, tiles=True, min_len=128, min_score=64, chunk=2, T=100,
+              RR=32, use_band=False, over_budget=False, roots_off=False, band_root=4096):
+    """plan_ring of csrc/wfa_plan.h (no GPU): the ring a BiWFA job gets -- dict(width, koff, band, tile_it, grown, need), or None
+    where the job's score is beyond the budget (WFM_ST_OOM)."""
+    L = load()
+    L.wfmh_test_ring_plan.restype = C.c_int
+    L.wfmh_test_ring_plan.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_ulonglong, C.POINTER(C.c_int64)]
+    node = (C.c_int32 * 6)(pl, tl, score_rem, sub, noband, band)
+    rules = (C.c_int32 * 10)(int(tiles), min_len, min_score, chunk, T, RR, int(use_band), int(over_budget), int(roots_off), band_root)
+    out = (C.c_int64 * 6)()
+    rc = L.wfmh_test_ring_plan(node, rules, mem_budget, out)
+    if rc != 0:
+        assert rc == -200, rc
+        return None
+    return dict(width=out[0], koff=out[1], band=out[2], tile_it=bool(out[3]), grown=bool(out[4]), need=out[5])
+
+
+def expand_runs(runs, plen, tlen, pen=DEFAULT_PEN, rle=False, ops_cap=None, before=()):
+    """expand_runs of csrc/wfa_plan.h (no GPU): (code, score, n_runs, ops_len, output) for a problem's runs ((len << 2) | op); the
+    output is the op bytes written, or with rle the run vector afterwards -- it held `before` when the call began."""
+    L = load()
+    L.wfmh_test_expand_runs.restype = C.c_int
+    L.wfmh_test_expand_runs.argtypes = [C.POINTER(C.c_uint32), C.c_int, C.POINTER(Penalties), C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t,
+                                        C.POINTER(C.c_uint32), C.POINTER(C.c_size_t), C.c_size_t, C.POINTER(C.c_int64)]
+    e = (C.c_uint32 * max(1, len(runs)))(*runs)
+    pn = Penalties(*pen)
+    cap = sum(r >> 2 for r in runs) if ops_cap is None else ops_cap
+    ops = C.create_string_buffer(cap + 1)
+    vcap = len(before) + len(runs)
+    vec = (C.c_uint32 * max(1, vcap))(*before)
+    nvec = C.c_size_t(len(before))
+    res = (C.c_int64 * 3)()
+    rc = L.wfmh_test_expand_runs(e, len(runs), C.byref(pn), plen, tlen, 1 if rle else 0, ops, cap, vec, C.byref(nvec), vcap, res)
+    out = list(vec[:nvec.value]) if rle else ops.raw[:res[2]]
+    return rc, int(res[0]), int(res[1]), int(res[2]), out
+
+
 def align_paf(handle, target_fasta, mapping_paf, out_paf, query_fasta=None, params=None):
     """wfmh_align_paf: the align phase on files (mapping PAF in, aligned PAF out)."""
     L = _host()

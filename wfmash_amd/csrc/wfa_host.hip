@@ -23,6 +23,7 @@
 #include "../../include/wfmash_hip.h"
 #include "wfa_device.h"
 #include "dev_cache.h"
+#include "wfa_plan.h"
 
 #ifdef WFM_PROFILE_SECTIONS
 namespace wfm { void read_sections(long long* out); }
@@ -31,6 +32,7 @@ namespace wfm { void p2_counters(unsigned long long* out); }
 namespace {
 
 using namespace wfm;
+static_assert(PLAN_SUB_NONE == SUB_NONE && OP_M == 0 && OP_X == 1 && OP_I == 2 && OP_D == 3, "wfa_plan.h spells these out (it includes no HIP header)");
 
 constexpr int BIALIGN_FALLBACK_MIN_SCORE = 250;   // WFA2-lib WF_BIALIGN_FALLBACK_MIN_SCORE
 constexpr int BIALIGN_FALLBACK_MIN_LENGTH = 100;  // WFA2-lib WF_BIALIGN_FALLBACK_MIN_LENGTH
@@ -84,22 +86,6 @@ struct ProbMeta {
   int32_t mode, pbf, pef, tbf, tef;
   int32_t hint;     // the caller's guess of an upper bound of the score (0: none)
   int64_t rle_off;  // start of this problem's RLE slot range
-};
-
-struct Node {
-  int32_t prob;
-  int32_t pb, pl, tb, tl;
-  int32_t cb, ce;
-  int32_t score_rem;  // INT_MAX at the root
-  int32_t smax;       // base jobs: score budget (0 = derive)
-  int32_t endsfree;
-  int32_t noband;     // bialign jobs: 1 = ran out of a narrow ring once, gets the full one now
-  int32_t sub;        // bialign jobs: upper bound of the score (SUB_NONE: none); the wavefronts are cut to what can stay under it
-  int32_t hinted;     // the bound is the caller's guess (a root): the job is run again without it if the guess was too small
-  int32_t tries;      // base jobs: how many score budgets the job has overflowed so far
-  int32_t band;       // bialign jobs that are run again: the band (scores a direction) of the attempt that failed, 0: it had a full ring.  Where the
-                      // full ring does not fit the budget the next attempt's band grows from it (the level loop of align_resident_impl)
-  int32_t snap;       // bialign jobs: 1 + the index of the snapshot the job goes on from on its wider ring (GrownSnap), 0: it starts at score 0
 };
 
 // The state of a tiled job that ran out of its narrow ring, kept in a device block of its own until the job has its wider ring: the columns
@@ -1032,6 +1018,638 @@ int run_p2_phase(wfm_handle* h, wfm_seqset* S, const DevPen& dp, int scope, cons
   return WFM_OK;
 }
 
+// ---- the BiWFA level driver: align_resident_impl (at the end) is the loop over levels and chunks, the stages before it do the work ----
+
+// The call's switches, read from the environment once per call (not once per process: the tests run both forms of most of them in
+// one process).  tile_cfg() reads the tile kernels' own.
+struct Knobs {
+  static int num(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+  bool use_hints = num("WFM_SCORE_HINT", 1) != 0;
+  bool use_bound = use_hints && num("WFM_BOUND", 1) != 0;
+  int slack_env = num("WFM_SUB_SLACK", -1);  // tests: < 0 default, >= 2^28 none
+  bool ring3_on = num("WFM_TILE_RING3", 1) != 0, p2_on = num("WFM_P2", 1) != 0;
+  int p2_rounds = std::max(1, num("WFM_P2_ROUNDS", 64));
+  int fine_margin = num("WFM_TILE_FINE_MARGIN", 48);
+  int coarse_min_blocks = num("WFM_TILE_COARSE_MIN_BLOCKS", 32), coarse_max_jobs = num("WFM_TILE_COARSE_MAX_JOBS", 128);
+  bool tile_v2 = num("WFM_TILE_V2", 1) != 0;  // 0: every tile on the byte kernel (wfa_tile_reg_kernel) -- the A/B switch of the packed kernel (wfa_tile2.hip)
+  bool band_on = num("WFM_BAND", 1) != 0;
+  int band_root = std::max(64, num("WFM_BAND_ROOT", 4096));
+  int resume_margin = num("WFM_RESUME_MARGIN", 26);  // (tests: a large value sends every resumed job back to score 0)
+  int debug = getenv("WFM_DEBUG") ? std::max(1, num("WFM_DEBUG", 0)) : 0;  // 0: unset
+};
+
+// One chunk of a level: the breakpoint jobs whose rings share the arena, and what the stages hand on about them
+struct Chunk {
+  std::vector<BpJob> jobs;
+  std::vector<int32_t> node_of;    // the job's node in bp_nodes
+  size_t ring_elems = 0, end = 0;  // elements of the chunk's rings; the first node behind the chunk
+  int maxw = 0;
+  std::vector<int> tiled, tiled_r;  // jobs of the tile phase (indices into jobs); _r: those that go on from a snapshot.  Their second and third rings, their fine_s:
+  std::vector<int64_t> ring2, ring3, ring2_r;
+  std::vector<int32_t> fine_from, fine_r, snap_r;
+  std::vector<size_t> ring_third;  // elements of one ring of every tiled job of the chunk
+  std::vector<char> grown_job, resume_bad, has_carry;
+  std::vector<BpResult> res, carry;  // carry: breakpoints found by rounds of phase 2 that did not end the walk
+  std::vector<int> rest, more_set;   // rest: jobs for the step kernel -- not tiled, not exact, or not finished by the rows computed ahead
+  void clear() {
+    jobs.clear(); node_of.clear(); ring_elems = 0; maxw = 0;
+    tiled.clear(); ring2.clear(); ring3.clear(); ring_third.clear(); fine_from.clear();
+    tiled_r.clear(); ring2_r.clear(); fine_r.clear(); snap_r.clear(); grown_job.clear();
+  }
+};
+
+// The state of one align call, handed from stage to stage
+struct AlignCall {
+  wfm_handle* h;
+  const wfm_penalties_t* pen;
+  wfm_seqset* S;
+  size_t first, last;
+  wfm_result_t* out;
+  char* ops_arena;
+  size_t arena_bytes, arena_base;
+  std::vector<uint32_t>* runs_out;
+  uint32_t* pflags;
+  int scope;
+  DevPen dp;
+  const Knobs knobs;
+  TileCfg tcfg;
+  int RR;           // rows of every ring of this call
+  RingRules rules;  // what plan_ring decides by: the call's, the level's (use_band, over_budget) and roots_off
+  std::vector<int32_t> prob_status;  // indexed by problem id
+  std::vector<uint64_t> prob_cells;
+  std::vector<Node> bp_nodes, base_nodes, next_bp;
+  uint32_t level = 0;
+  Chunk ck;
+  LevelTimer tm;
+  double wall_tile = 0, wall_base = 0;
+  uint64_t band_retries = 0, band_jobs = 0, roots_banded = 0, roots_out = 0, hint_retries = 0;
+  // Rings that grow with the score (DESIGN.md section 5): a job whose full ring does not fit the budget runs on bands b, 4 b, 16 b ...
+  uint64_t grown_jobs = 0, grown_widened = 0, grown_restarts = 0;
+  int64_t grown_maxband = 0;
+  size_t ring_peak = 0;  // most elements a chunk's ring arena held
+  GrownSnaps snaps;
+};
+
+void make_roots(AlignCall& c) {
+  for (size_t i = c.first; i < c.last; ++i) {
+    const ProbMeta& pm = c.S->meta[i];
+    Node nd{};
+    nd.prob = (int32_t)i; nd.pb = 0; nd.pl = pm.plen; nd.tb = 0; nd.tl = pm.tlen;
+    nd.cb = C_M; nd.ce = C_M; nd.score_rem = INT_MAX; nd.endsfree = 0;
+    nd.sub = SUB_NONE; nd.hinted = 0;
+    if (c.pflags && pm.mode == WFM_MODE_END2END_BIWFA && !((size_t)i < c.S->acgt.size() && c.S->acgt[i])) c.pflags[i] |= WFM_PF_BYTE_KERNEL;
+    if (c.knobs.use_hints && pm.hint > 0 && pm.mode == WFM_MODE_END2END_BIWFA) { nd.sub = pm.hint; nd.hinted = 1; }
+    const int64_t bound = (int64_t)gapcost(*c.pen, pm.plen) + gapcost(*c.pen, pm.tlen) + 8;
+    if (pm.mode == WFM_MODE_ENDSFREE) {
+      nd.endsfree = 1;
+      // ends-free score is bounded by the cheaper all-gap alignment; start small, double on overflow
+      nd.smax = (int32_t)std::min<int64_t>(bound, 256);
+      c.base_nodes.push_back(nd);
+    } else if (pm.mode == WFM_MODE_END2END_UNI || std::max(pm.plen, pm.tlen) <= BIALIGN_FALLBACK_MIN_LENGTH ||
+               pm.plen == 0 || pm.tlen == 0) {
+      nd.smax = (int32_t)std::min<int64_t>(bound, 256);
+      c.base_nodes.push_back(nd);
+    } else {
+      c.bp_nodes.push_back(nd);
+    }
+  }
+}
+
+// An upper bound of every long root's score, from one greedy walk per root (wfa_bound_kernel): rigorous, so the root's
+// wavefronts are cut to what an alignment of at most that score can touch -- usually a fifth of what the caller's guess
+// leaves.  The guess stays where the walk gives up (divergent records, structural differences).
+int bound_roots(AlignCall& c) {
+  wfm_handle* h = c.h;
+  std::vector<BoundJob> bj;
+  std::vector<size_t> owner;
+  if (c.knobs.use_bound)
+    for (size_t q = 0; q < c.bp_nodes.size(); ++q) {
+      const Node& nd = c.bp_nodes[q];
+      const ProbMeta& pm = c.S->meta[nd.prob];
+      // only where a bound can bind: the end diagonal far from the start diagonal (see BpJob::sub below)
+      if (pm.mode != WFM_MODE_END2END_BIWFA || std::min(nd.pl, nd.tl) < 1024 || std::abs(nd.tl - nd.pl) < 64) continue;
+      bj.push_back(BoundJob{pm.p_fwd, pm.t_fwd, nd.pl, nd.tl});
+      owner.push_back(q);
+    }
+  if (bj.empty()) return WFM_OK;
+  uint64_t bounded_roots = 0, bound_gain = 0;
+  const auto tb0 = std::chrono::steady_clock::now();
+  if (h->bndjobs.ensure(bj.size()) || h->bndres.ensure(bj.size())) { h->err = "out of device memory (score bounds)"; return WFM_E_NOMEM; }
+  HIPCHK(h, hipMemcpyAsync(h->bndjobs.p, bj.data(), bj.size() * sizeof(BoundJob), hipMemcpyHostToDevice, h->stream));
+  launch_bound(c.S->d_seq, h->bndjobs.p, h->bndres.p, (int)bj.size(), c.dp, h->stream);
+  HIPCHK(h, hipGetLastError());
+  std::vector<int32_t> ub(bj.size());
+  HIPCHK(h, hipMemcpyAsync(ub.data(), h->bndres.p, bj.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  for (size_t q = 0; q < bj.size(); ++q) {
+    if (ub[q] < 0) continue;
+    Node& nd = c.bp_nodes[owner[q]];
+    if (nd.sub == SUB_NONE || ub[q] < nd.sub) {
+      if (nd.sub != SUB_NONE) bound_gain += (uint64_t)(nd.sub - ub[q]);
+      nd.sub = ub[q];
+      nd.hinted = 1;  // (cannot fail; the retry of a root that runs past its bound stays as the safety net it is)
+      ++bounded_roots;
+    }
+  }
+  const double bound_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb0).count();
+  if (c.knobs.debug)
+    fprintf(stderr, "[wfm] score bounds: %zu roots walked in %.2f ms, %llu bounded (on average %.0f below the caller's guess)\n", bj.size(), bound_ms,
+            (unsigned long long)bounded_roots, bounded_roots ? (double)bound_gain / (double)bounded_roots : 0.0);
+  return WFM_OK;
+}
+
+// Rings cover every diagonal of a job ((pl + tl) columns of 1280 B, twice for tiled jobs): fine for a batch of
+// few deep problems, wasteful for thousands of long low-divergence records, whose wavefronts stay within a few
+// thousand diagonals and which would otherwise be worked off in many small chunks.  When the level does not fit
+// the budget, jobs get rings for |k| <= band only: a child's total score is known (half of it per direction,
+// plus the overlap phase), a root gets WFM_BAND_ROOT scores; whoever runs out of its band is run again on a
+// full ring.  WFM_BAND=0 switches this off.
+void level_budget(AlignCall& c) {
+  size_t total = 0;
+  for (const Node& nd : c.bp_nodes) total += ring_elems(ring_full_width(nd.pl, nd.tl), c.RR, 2);
+  // (narrow rings whenever full ones would take more than 2 GB, not only when they would not fit: every fresh GB of a
+  // first hipMalloc costs ~30 ms on this driver, scripts/micro/malloc_cost2.hip, and a one-shot run pays it)
+  c.rules.use_band = c.knobs.band_on && total * 4 > std::min<size_t>(c.h->mem_budget, (size_t)2 << 30);
+  c.rules.over_budget = total * 4 > c.h->mem_budget;
+}
+
+// The jobs of the chunk that begins at node i0: a ring for each (plan_ring), until the chunk's byte limit is reached
+void plan_chunk(AlignCall& c, size_t i0) {
+  wfm_handle* h = c.h;
+  Chunk& k = c.ck;
+  const TileCfg& tcfg = c.tcfg;
+  // (once per process)
+  static const size_t ring_chunk_bytes = (size_t)(getenv("WFM_RING_CHUNK_GB") ? std::max(1, atoi(getenv("WFM_RING_CHUNK_GB"))) : 4) << 30;
+  k.clear();
+  size_t i = i0;
+  int64_t fine_min_blocks_r = INT64_MAX;
+  int64_t fine_min_blocks = INT64_MAX;  // fewest blocks any tiled job of the chunk is expected to run before its directions meet
+  for (; i < c.bp_nodes.size(); ++i) {
+    const Node& nd = c.bp_nodes[i];
+    const ProbMeta& pm = c.S->meta[nd.prob];
+    const RingPlan rp = plan_ring(nd, c.rules);
+    if (!rp.fits) { c.prob_status[nd.prob] = WFM_ST_OOM; c.snaps.drop(nd.snap); continue; }
+    const size_t width = rp.width, need = rp.need; const int band = rp.band; const bool tile_it = rp.tile_it, grown = rp.grown;
+    // (a chunk of a level stops at 4 GB of rings even when the budget allows more: hundreds of jobs fill the device
+    // long before that, and every GB of a first allocation costs 30 - 70 ms.  C1 substitute, three handles in a fresh
+    // process: 8 GB chunks 8.3 s cold / 5.33 s warm, 4 GB 5.67 / 5.52, 2 GB 6.22 / 6.06 -- scripts/c1_cold.sh.  A chunk of
+    // fewer than 128 jobs may grow to 8 GB: C3's 21 roots of a part are 5.4 GB of full rings, and cut in two they fill the device worse.
+    // Tried and dropped: two launches per block, jobs without a score bound apart from those with one -- the plain kernel form
+    // has 7 % fewer instructions, the second launch cost more: C2 0.18 -> 0.21 s, C1 no better)
+    if (!k.jobs.empty() && (k.ring_elems + need) * 4 > std::min<size_t>(h->mem_budget, k.jobs.size() >= 128 ? ring_chunk_bytes : std::max(ring_chunk_bytes, (size_t)8 << 30))) break;
+    BpJob j{};
+    j.p_fwd = pm.p_fwd + nd.pb;
+    j.t_fwd = pm.t_fwd + nd.tb;
+    j.p_rev = pm.p_rev + (pm.plen - nd.pb - nd.pl);
+    j.t_rev = pm.t_rev + (pm.tlen - nd.tb - nd.tl);
+    j.ring_off = (int64_t)k.ring_elems;
+    j.pl = nd.pl; j.tl = nd.tl;
+    j.comp_begin = nd.cb; j.comp_end = nd.ce;
+    j.width = (int32_t)width;
+    j.koff = rp.koff;
+    j.resume_s = -1; j.resume_sr = -1; j.last_fwd = 0; j.fmax0 = 0; j.rmax0 = 0;
+    j.band = band;
+    // a bound only earns its keep when the end diagonal is far from the start diagonal relative to the score (padded
+    // records and their children): for a balanced problem it starts to bind where the wavefronts meet, and costs the
+    // tile kernel its bookkeeping all the way there
+    j.sub = (nd.sub != SUB_NONE && (int64_t)std::abs(nd.tl - nd.pl) * 8 >= (int64_t)nd.sub) ? nd.sub : SUB_NONE;
+    j.best0 = 0;
+    j.packed = (c.knobs.tile_v2 && tcfg.reg && tcfg.C == 2 && (size_t)nd.prob < c.S->acgt.size() && c.S->acgt[(size_t)nd.prob]) ? 1 : 0;
+    // bit 1: near-identical sequences -- the job's score is known (a child's, a bounded or hinted root's) to be under a sixteenth of its length; the packed
+    // tile kernel then hands a lone long run to the whole wave at once (wfa_tile2.hip, tail_direct).  Whether the bound also CUTS the rows (sub below) is another matter.
+    if (j.packed && nd.sub != SUB_NONE && (int64_t)nd.sub * 16 < (int64_t)nd.pl + nd.tl) j.packed |= 2;
+    c.band_jobs += band > 0 && !grown;
+    k.grown_job.push_back((char)grown);
+    const bool resumes = grown && tile_it && nd.snap > 0;  // (a snapshot is the tile kernels' own: no gap rows as deep as the step kernel reads)
+    if (nd.snap > 0 && !resumes) c.snaps.drop(nd.snap);
+    if (grown) {
+      ++c.grown_jobs;
+      c.grown_maxband = std::max<int64_t>(c.grown_maxband, band);
+      if (resumes) ++c.grown_widened; else if (nd.noband || nd.band > 0) ++c.grown_restarts;
+      if (c.pflags) c.pflags[nd.prob] |= WFM_PF_RING_GROWN;
+      if (c.knobs.debug)
+        fprintf(stderr, "[wfm] grown ring: problem %d, %s of %d x %d: band %d, %zu columns on the %s%s\n", nd.prob, nd.score_rem == INT_MAX ? "root" : "child", nd.pl, nd.tl, band, width,
+                tile_it ? "tile kernels" : "step kernel alone", resumes ? ", widened from its snapshot" : ((nd.noband || nd.band > 0) ? ", from score 0 again" : ""));
+    }
+    if (resumes) {
+      // the job's rule for per-score maxima is the one it started with (below); its blocks until the directions meet are counted from the snapshot
+      const GrownSnap& sn = c.snaps.v[(size_t)nd.snap - 1];
+      k.tiled_r.push_back((int)k.jobs.size()); k.ring2_r.push_back((int64_t)(k.ring_elems + need / 2)); k.snap_r.push_back(nd.snap);
+      const int64_t est = nd.score_rem != INT_MAX ? (int64_t)nd.score_rem : (int64_t)nd.pl + nd.tl;
+      fine_min_blocks_r = std::min<int64_t>(fine_min_blocks_r, std::max<int64_t>(0, est / 2 - sn.s0) / tcfg.T);
+      k.fine_r.push_back(nd.score_rem != INT_MAX ? std::max(0, nd.score_rem / 2 - c.knobs.fine_margin) : INT_MAX);
+    } else if (tile_it) {
+      k.tiled.push_back((int)k.jobs.size()); k.ring2.push_back((int64_t)(k.ring_elems + need / 2)); k.ring_third.push_back(need / 2);
+      // per-score maxima from here on (TileJob::fine_s): a child's directions meet near half its score (the trigger -- the sum of the two largest
+      // antidiagonals -- can fire a little earlier, never later); a root's score is anybody's guess: it finds its meeting block with one maximum
+      // per block and runs it again (whether the chunk uses any of this is decided below, once its jobs are known)
+      const int64_t est = nd.score_rem != INT_MAX ? (int64_t)nd.score_rem : (nd.sub != SUB_NONE ? (int64_t)nd.sub : (int64_t)nd.pl + nd.tl);  // its score / the guess or bound / the worst case
+      fine_min_blocks = std::min<int64_t>(fine_min_blocks, est / 2 / tcfg.T);
+      k.fine_from.push_back(nd.score_rem != INT_MAX ? std::max(0, nd.score_rem / 2 - c.knobs.fine_margin) : INT_MAX);
+    }
+    k.node_of.push_back((int32_t)i);
+    k.ring_elems += need;
+    // widest wavefront this job can reach: 2 diagonals per score of one direction (~half the total score)
+    const int64_t est_w = nd.score_rem == INT_MAX ? (int64_t)width : std::min<int64_t>((int64_t)width, (int64_t)nd.score_rem + 128);
+    k.maxw = std::max(k.maxw, (int)est_w);
+    k.jobs.push_back(j);
+  }
+  k.end = i;
+  // One maximum per block instead of one per score (TileJob::fine_s) pays where a launch is a few deep jobs that move in step -- C3: 21 roots
+  // of 78 blocks each, -3.7 % per step -- and costs where it is hundreds of jobs of all depths: their blocks need both instantiations of the
+  // kernel side by side (two launches per block), and a root runs its meeting block a third time behind one more look of the host: C2 +10 %
+  // device time, the scaled C4 rank +3 % (gpurun_out/r6r/ab2.log).  So: only chunks of at most coarse_max_jobs jobs, every one of them
+  // at least coarse_min_blocks blocks deep; everybody else keeps the per-score maxima from the first block on (one launch per block, as before).
+  if (k.tiled.size() > (size_t)c.knobs.coarse_max_jobs || fine_min_blocks < (int64_t)c.knobs.coarse_min_blocks) std::fill(k.fine_from.begin(), k.fine_from.end(), 0);
+  if (k.tiled_r.size() > (size_t)c.knobs.coarse_max_jobs || fine_min_blocks_r < (int64_t)c.knobs.coarse_min_blocks) std::fill(k.fine_r.begin(), k.fine_r.end(), 0);
+  // third rings behind the chunk's rings (TileJob::ring_prev), for all of its tiled jobs or for none: where half as much again still fits the
+  // budget (and 12 GB: fresh memory is 30 ms per GB).  The chunk's composition does not depend on it.
+  size_t third = 0;
+  for (size_t x : k.ring_third) third += x;
+  const bool give = c.knobs.ring3_on && tcfg.reg && tcfg.exact && third > 0 && (k.ring_elems + third) * 4 <= std::min<size_t>(h->mem_budget, (size_t)12 << 30);
+  k.ring3.assign(k.tiled.size(), -1);
+  if (give)
+    for (size_t q = 0; q < k.tiled.size(); ++q) { k.ring3[q] = (int64_t)k.ring_elems; k.ring_elems += k.ring_third[q]; }
+}
+
+// The chunk's arena; then the snapshots of the jobs that go on where they stood, out of their blocks into the chunk's (wider)
+// rings; the blocks go back
+int widen_resumed(AlignCall& c) {
+  wfm_handle* h = c.h;
+  Chunk& k = c.ck;
+  if (h->ring.ensure(k.ring_elems + 16) || h->bpjobs.ensure(k.jobs.size()) || h->bpres.ensure(k.jobs.size())) {
+    h->err = "out of device memory (ring arena)"; return WFM_E_NOMEM;
+  }
+  c.ring_peak = std::max(c.ring_peak, k.ring_elems);
+  k.resume_bad.assign(k.jobs.size(), 0);
+  if (k.tiled_r.empty()) return WFM_OK;
+  std::vector<RingWidenJob> wj;
+  int maxw_dst = 0;
+  for (size_t q = 0; q < k.tiled_r.size(); ++q) {
+    BpJob& j = k.jobs[(size_t)k.tiled_r[q]];
+    const GrownSnap& sn = c.snaps.v[(size_t)k.snap_r[q] - 1];
+    wj.push_back(RingWidenJob{sn.d, h->ring.p + j.ring_off, sn.w, sn.koff, j.width, j.koff, -(sn.s0 + 8), sn.s0 + 8});
+    maxw_dst = std::max(maxw_dst, j.width);
+    j.resume_s = sn.s0; j.resume_sr = -1; j.fmax0 = sn.fmax; j.rmax0 = sn.rmax;
+  }
+  if (h->widenjobs.ensure(wj.size())) { h->err = "out of device memory (ring arena)"; return WFM_E_NOMEM; }
+  HIPCHK(h, hipMemcpyAsync(h->widenjobs.p, wj.data(), wj.size() * sizeof(RingWidenJob), hipMemcpyHostToDevice, h->stream));
+  launch_ring_widen(h->widenjobs.p, (int)wj.size(), maxw_dst, c.RR, h->stream);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  for (int32_t id : k.snap_r) c.snaps.drop(id);
+  return WFM_OK;
+}
+
+// The tile phase of the chunk: its tiled jobs, the optional finer pass, then the resumed jobs from their snapshots
+int run_chunk_tiles(AlignCall& c) {
+  wfm_handle* h = c.h;
+  Chunk& k = c.ck;
+  const TileCfg& tcfg = c.tcfg;
+  double tms = 0; uint64_t tcells = 0;
+  const auto tw0 = std::chrono::steady_clock::now();
+  int rc = run_tiled_phase(h, c.S, c.dp, c.scope, tcfg, tcfg.T, false, k.jobs, k.tiled, k.ring2, tms, tcells, c.level, &k.fine_from, &k.ring3);
+  if (rc == WFM_OK && tcfg.T_refine > 0 && tcfg.T_refine < tcfg.T && !(tcfg.reg && tcfg.exact))
+    rc = run_tiled_phase(h, c.S, c.dp, c.scope, tcfg, tcfg.T_refine, true, k.jobs, k.tiled, k.ring2, tms, tcells, c.level);
+  if (rc == WFM_OK && !k.tiled_r.empty()) {
+    std::vector<int> from_s(k.tiled_r.size());
+    for (size_t q = 0; q < k.tiled_r.size(); ++q) from_s[q] = k.jobs[(size_t)k.tiled_r[q]].resume_s;
+    rc = run_tiled_phase(h, c.S, c.dp, c.scope, tcfg, tcfg.T, true, k.jobs, k.tiled_r, k.ring2_r, tms, tcells, c.level, &k.fine_r);
+    for (size_t q = 0; rc == WFM_OK && q < k.tiled_r.size(); ++q) {
+      BpJob& j = k.jobs[(size_t)k.tiled_r[q]];
+      // The snapshot a job goes on from was written by a block of the tile kernels for the next block of the tile kernels: with a third ring
+      // in play (TileJob::ring_prev) it holds the gap components two rows and one row deep, not the 26 the overlap phase and the step kernel
+      // read.  A job whose directions meet within 26 scores of that snapshot would hand such rows on: it starts again on this band instead
+      // (26 scores out of the thousands the wider ring was made for).
+      const bool exact_end = j.resume_s >= 0 && j.resume_sr >= 0;
+      if (tcfg.reg && tcfg.exact && ((exact_end && std::min(j.resume_s, j.resume_sr) - from_s[q] < c.knobs.resume_margin) || (j.resume_s >= 0 && j.resume_sr < 0 && j.resume_s == from_s[q]))) {
+        j.resume_s = -3; j.resume_sr = -1;
+        k.resume_bad[(size_t)k.tiled_r[q]] = 1;
+      }
+      k.tiled.push_back(k.tiled_r[q]); k.ring2.push_back(k.ring2_r[q]);  // (from here on a tiled job like the others)
+    }
+  }
+  c.wall_tile += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw0).count();
+  if (rc != WFM_OK) return rc;
+  c.tm.bp_ms += tms; c.tm.tile_ms += tms;
+  h->stats.cells_bp += tcells; h->stats.cells_tile += tcells;
+  return WFM_OK;
+}
+
+// Phase 2 of the jobs the tile phase left exactly at their meeting point: rows computed ahead + scan + replay.  Leaves the
+// step kernel's jobs in rest.
+int run_chunk_p2(AlignCall& c) {
+  wfm_handle* h = c.h;
+  Chunk& k = c.ck;
+  k.res.assign(k.jobs.size(), BpResult{});
+  k.rest.clear(); k.more_set.clear();
+  std::vector<int> cand;
+  std::vector<int64_t> other;
+  std::vector<char> is_cand(k.jobs.size(), 0);
+  if (c.knobs.p2_on && c.tcfg.reg && c.tcfg.exact)
+    for (size_t q = 0; q < k.tiled.size(); ++q) {
+      const BpJob& j = k.jobs[(size_t)k.tiled[q]];
+      if (j.resume_s >= 0 && j.resume_sr >= 0) { cand.push_back(k.tiled[q]); other.push_back(k.ring2[q]); is_cand[(size_t)k.tiled[q]] = 1; }
+    }
+  double pms = 0;
+  k.carry.assign(k.jobs.size(), BpResult{});
+  k.has_carry.assign(k.jobs.size(), 0);
+  std::vector<int> cand_r = cand, again;
+  std::vector<int64_t> other_r = other;
+  for (int round = 1; !cand_r.empty(); ++round) {
+    again.clear();
+    const int rc = run_p2_phase(h, c.S, c.dp, c.scope, c.tcfg, k.jobs, cand_r, other_r, k.res, pms, k.carry, k.has_carry, round < c.knobs.p2_rounds, again);
+    if (rc != WFM_OK) return rc;
+    std::vector<int> c2; std::vector<int64_t> o2;
+    for (int a : again) {
+      c2.push_back(cand_r[(size_t)a]); o2.push_back(other_r[(size_t)a]);
+      if (c.pflags) c.pflags[c.bp_nodes[(size_t)k.node_of[(size_t)cand_r[(size_t)a]]].prob] |= WFM_PF_P2_ROUNDS;
+    }
+    h->stats.p2_again += (uint32_t)again.size();
+    cand_r.swap(c2); other_r.swap(o2);
+  }
+  c.tm.bp_ms += pms;
+  for (size_t q = 0; q < k.jobs.size(); ++q)
+    if (!is_cand[q] || k.res[q].status == WFM_DEV_P2_MORE) { k.rest.push_back((int)q); h->stats.p2_more += is_cand[q]; if (is_cand[q]) k.more_set.push_back((int)q); }
+  if (c.pflags)  // jobs whose overlap walk went past the first round of rows computed ahead (or was finished by the step kernel)
+    for (size_t q = 0; q < k.jobs.size(); ++q)
+      if (is_cand[q] && k.res[q].status == WFM_DEV_P2_MORE) c.pflags[c.bp_nodes[(size_t)k.node_of[q]].prob] |= WFM_PF_P2_ROUNDS;
+  return WFM_OK;
+}
+
+// The step kernel (wfa_bp_kernel) for the jobs in rest
+int run_chunk_step(AlignCall& c) {
+  wfm_handle* h = c.h;
+  Chunk& k = c.ck;
+  const std::vector<int>& rest = k.rest;
+  if (rest.empty()) return WFM_OK;
+  auto is_more = [&](int q) { return std::find(k.more_set.begin(), k.more_set.end(), q) != k.more_set.end(); };
+  // workgroup size: wide wavefronts want all 16 waves of a CU
+  int threads = 1024;
+  if (k.maxw <= 1024) threads = 256;
+  else if (k.maxw <= 8192) threads = 512;
+  std::vector<BpJob> rj(rest.size());
+  for (size_t q = 0; q < rest.size(); ++q) rj[q] = k.jobs[(size_t)rest[q]];
+  HIPCHK(h, hipMemcpyAsync(h->bpjobs.p, rj.data(), rj.size() * sizeof(BpJob), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+  launch_bp(c.S->d_seq, h->ring.p, h->bpjobs.p, h->bpres.p, (int)rj.size(), threads, c.dp, c.scope, c.RR, h->stream);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+  std::vector<BpResult> rr(rj.size());
+  HIPCHK(h, hipMemcpyAsync(rr.data(), h->bpres.p, rr.size() * sizeof(BpResult), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  float ms = 0;
+  HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+  c.tm.bp_ms += ms;
+  if (h->call_base) {
+    float t0 = 0;
+    HIPCHK(h, hipEventElapsedTime(&t0, h->call_base, h->ev0));
+    h->bp_iv.emplace_back(t0, t0 + ms);
+  }
+  h->stats.bp_launches++;
+  for (size_t q = 0; q < rest.size(); ++q) {
+    if (rr[q].status == WFM_DEV_P2_NOTHING) {  // (only jobs that carry a breakpoint are handed a best0)
+      const uint64_t cl = rr[q].cells; const int32_t st = rr[q].steps;
+      rr[q] = k.carry[(size_t)rest[q]]; rr[q].cells = cl; rr[q].steps = st;
+    }
+    k.res[(size_t)rest[q]] = rr[q];
+  }
+  if (c.knobs.debug) {
+    uint64_t cl = 0; double t1 = 0, t2 = 0; int64_t st1 = 0, st = 0; uint32_t m1 = 0, m2 = 0;
+    for (const BpResult& r : rr) { cl += r.cells; t1 += r.ticks_p1; t2 += r.ticks_p2; st1 += r.steps_p1; st += r.steps; m1 = std::max(m1, r.ticks_p1); m2 = std::max(m2, r.ticks_p2); }
+    fprintf(stderr, "[wfm] level %u: %zu bp jobs (step kernel), %d thr, %.3f ms, cells %.3e, avg steps p1 %.0f p2 %.0f, avg ms p1 %.3f p2 %.3f, max ms p1 %.3f p2 %.3f\n", c.level, rr.size(), threads, ms,
+            (double)cl, (double)st1 / rr.size(), (double)(st - st1) / rr.size(), t1 / rr.size() / 1e5, t2 / rr.size() / 1e5, m1 / 1e5, m2 / 1e5);
+    if (c.knobs.debug > 1) {  // the slowest three
+      std::vector<size_t> ord(rr.size());
+      for (size_t q = 0; q < ord.size(); ++q) ord[q] = q;
+      std::sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return rr[a].ticks_p1 + rr[a].ticks_p2 > rr[b].ticks_p1 + rr[b].ticks_p2; });
+      for (size_t q = 0; q < std::min<size_t>(3, ord.size()); ++q) {
+        const BpResult& r = rr[ord[q]];
+        const BpJob& j = rj[ord[q]];
+        fprintf(stderr, "[wfm]   slow step-kernel job: pl %d tl %d width %d band %d sub %d resume %d/%d (%s), status %d score %d = %d + %d, steps p1 %d p2 %d, ms p1 %.3f p2 %.3f\n", j.pl, j.tl, j.width,
+                j.band, j.sub == SUB_NONE ? -1 : j.sub, j.resume_s, j.resume_sr, is_more(rest[ord[q]]) ? "phase-2 walk ran out of rows" : (j.resume_sr >= 0 ? "exact" : "not exact"), r.status,
+                r.score, r.score_fwd, r.score_rev, r.steps_p1, r.steps - r.steps_p1, r.ticks_p1 / 1e5, r.ticks_p2 / 1e5);
+      }
+    }
+  }
+  return WFM_OK;
+}
+
+// A tiled job that simply ran out of its band stands at a block boundary s0 <= band with both directions complete -- a row of score s
+// spans |k| <= s, nothing was cut by the ring's edge -- and goes on from there: the columns |k| <= s0 + 8 of its snapshot wait in a block of
+// their own for the job's wider ring (the chunk's arena is the next chunk's).  Not so a job under a bound of its score (rows cut to
+// |k - (tl - pl)| <= sub - s: no state of the unbounded problem) or one the step kernel stopped: those start again from score 0.
+int keep_snapshot(AlignCall& c, size_t q, Node& again) {
+  wfm_handle* h = c.h;
+  const BpJob& j = c.ck.jobs[q];
+  if (c.ck.resume_bad[q] || c.ck.res[q].status != WFM_DEV_BAND || j.resume_s != -3 || j.resume_sr < 0 || j.sub != SUB_NONE || j.band <= 0) return WFM_OK;
+  GrownSnap sn;
+  sn.s0 = j.resume_sr; sn.fmax = j.fmax0; sn.rmax = j.rmax0;
+  const int reach = sn.s0 + 8;
+  sn.koff = reach + 4;
+  sn.koff += ((j.koff - sn.koff) % 4 + 4) % 4;  // whole 16-byte chunks apart from the ring's columns, and from those of the ring to come
+  sn.w = (sn.koff + reach + 5 + 3) & ~3;
+  if (wfm_dmalloc((void**)&sn.d, ring_elems((size_t)sn.w, c.RR) * sizeof(int32_t)) != hipSuccess) { (void)hipGetLastError(); sn.d = nullptr; }
+  if (!sn.d) return WFM_OK;  // (no block to be had: the job starts again)
+  const RingWidenJob wj{h->ring.p + j.ring_off, sn.d, j.width, j.koff, sn.w, sn.koff, -reach, reach};
+  c.snaps.v.push_back(sn);
+  again.snap = (int32_t)c.snaps.v.size();
+  if (h->widenjobs.ensure(1)) { h->err = "out of device memory (ring arena)"; return WFM_E_NOMEM; }
+  HIPCHK(h, hipMemcpyAsync(h->widenjobs.p, &wj, sizeof(wj), hipMemcpyHostToDevice, h->stream));
+  launch_ring_widen(h->widenjobs.p, 1, sn.w, c.RR, h->stream);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return WFM_OK;
+}
+
+// The two halves of a job on either side of its breakpoint: leaves to the base aligner, the others to the next level
+void push_children(AlignCall& c, const Node& nd, const BpResult& r, int bp_v, int bp_h) {
+  const wfm_penalties_t* pen = c.pen;
+  Node a{}, b{};
+  a.prob = nd.prob; a.pb = nd.pb; a.pl = bp_v; a.tb = nd.tb; a.tl = bp_h;
+  // what a child can cost: the score its parent found for it, plus the opening of a gap it begins or ends in
+  // (counted on the other side of the breakpoint)
+  const int slack = c.knobs.slack_env >= 0 ? c.knobs.slack_env : 2 * std::max(pen->o1, pen->o2) + 8;
+  a.sub = (int)std::min<int64_t>((int64_t)r.score_fwd + slack, SUB_NONE);
+  b.sub = (int)std::min<int64_t>((int64_t)r.score_rev + slack, SUB_NONE);
+  a.hinted = 0; b.hinted = 0;
+  a.cb = nd.cb; a.ce = r.comp; a.score_rem = r.score_fwd;
+  b.prob = nd.prob; b.pb = nd.pb + bp_v; b.pl = nd.pl - bp_v; b.tb = nd.tb + bp_h; b.tl = nd.tl - bp_h;
+  b.cb = r.comp; b.ce = nd.ce; b.score_rem = r.score_rev;
+  for (Node* ch : {&a, &b}) {
+    if (ch->pl == 0 || ch->tl == 0) { ch->smax = 0; c.base_nodes.push_back(*ch); }
+    else if (ch->score_rem <= BIALIGN_FALLBACK_MIN_SCORE) {
+      // the leaf's own forward score: what the breakpoint credited it with, plus the opening of a gap it has
+      // to end in (counted on the other side of that breakpoint)
+      const int open_end = ch->ce == C_M ? 0 : ((ch->ce == C_I1 || ch->ce == C_D1) ? pen->o1 : pen->o2);
+      ch->smax = std::max(ch->score_rem, 0) + open_end;
+      c.base_nodes.push_back(*ch);
+    }
+    else c.next_bp.push_back(*ch);
+  }
+}
+
+// diagnosis (WFM_DUMP_FAIL): the whole problem's sequences, for a replay
+void dump_failed_problem(AlignCall& c, const Node& nd, const char* dd) {
+  const ProbMeta& pm = c.S->meta[nd.prob];
+  std::vector<char> pb((size_t)pm.plen), tb((size_t)pm.tlen);
+  (void)hipMemcpy(pb.data(), c.S->d_seq + pm.p_fwd, pb.size(), hipMemcpyDeviceToHost);
+  (void)hipMemcpy(tb.data(), c.S->d_seq + pm.t_fwd, tb.size(), hipMemcpyDeviceToHost);
+  static std::atomic<int> nfail{0};
+  const std::string fn = std::string(dd) + "/fail_" + std::to_string(nfail.fetch_add(1)) + ".txt";
+  if (FILE* f = fopen(fn.c_str(), "w")) {
+    fprintf(f, "%d %d %d\n", pm.plen, pm.tlen, pm.hint);
+    fwrite(pb.data(), 1, pb.size(), f); fputc('\n', f);
+    fwrite(tb.data(), 1, tb.size(), f); fputc('\n', f);
+    fclose(f);
+  }
+}
+
+// What became of the chunk's jobs: run again (with a snapshot where one can be kept), children, a leaf, or the problem's failure
+int settle_chunk(AlignCall& c) {
+  wfm_handle* h = c.h;
+  Chunk& k = c.ck;
+  h->stats.bp_jobs += (uint32_t)k.jobs.size();
+  for (size_t q = 0; q < k.jobs.size(); ++q) {
+    const Node nd = c.bp_nodes[(size_t)k.node_of[q]];  // a copy: retries are appended to bp_nodes below
+    const BpResult& r = k.res[q];
+    c.prob_cells[nd.prob] += r.cells;
+    h->stats.cells_bp += r.cells;
+    if (nd.score_rem == INT_MAX && k.jobs[q].band > 0 && !k.grown_job[q]) { ++c.roots_banded; c.roots_out += r.status == WFM_DEV_BAND; }
+    const bool guessed = nd.hinted && k.jobs[q].sub != SUB_NONE;  // the job really ran under the caller's guess
+    if (r.status == WFM_DEV_BAND || (guessed && (r.status < 0 || (r.status == 0 && r.score > nd.sub)))) {
+      // ran out of its narrow ring, or past the caller's guess of its score: once more, at the end of this level, on
+      // a full ring and without the guess
+      Node again = nd; again.noband = 1; again.sub = SUB_NONE; again.hinted = 0;
+      again.band = k.jobs[q].band; again.snap = 0;
+      if (c.pflags) c.pflags[nd.prob] |= nd.score_rem == INT_MAX ? WFM_PF_ROOT_AGAIN : WFM_PF_JOB_AGAIN;
+      // where the full ring does not fit, the job's next ring grows from the band it had (plan_ring)
+      const bool full_fits = ring_elems(ring_full_width(nd.pl, nd.tl), c.RR) * 4 <= h->mem_budget;
+      if (!full_fits) {
+        if (c.pflags) c.pflags[nd.prob] |= WFM_PF_RING_GROWN;
+        if (k.resume_bad[q]) again.band = nd.band;  // (the same band once more, from score 0)
+        const int rc = keep_snapshot(c, q, again);
+        if (rc != WFM_OK) return rc;
+      }
+      // (it joins the next level's jobs instead of holding this level up on its own: nodes are independent, only the gather at
+      // the end waits for all of them.  Until round 5 a job that ran out of its ring was run again at the end of its own level --
+      // three chains of 30 - 40 tile blocks one after the other in the first level of an LPA batch, 19 of its 50 ms of tile time;
+      // WFM_RETRY_SAME_LEVEL=1 restores that for A/B runs; once per process)
+      static const bool same_level = getenv("WFM_RETRY_SAME_LEVEL") && atoi(getenv("WFM_RETRY_SAME_LEVEL")) != 0;
+      if (guessed || !same_level) c.next_bp.push_back(again); else c.bp_nodes.push_back(again);
+      c.band_retries += full_fits;
+      c.hint_retries += guessed;
+      continue;
+    }
+    if (r.status == 1) {  // end reached at score 0 -> base aligner
+      Node b = nd; b.smax = 0; c.base_nodes.push_back(b);
+    } else if (r.status != 0) {
+      if (c.knobs.debug) fprintf(stderr, "[wfm] problem %d: bialign job pl %d tl %d cb %d ce %d score_rem %d status %d (steps %d)\n", nd.prob, nd.pl, nd.tl, nd.cb, nd.ce, nd.score_rem, r.status, r.steps);
+      c.prob_status[nd.prob] = WFM_ST_UNREACHABLE;
+    } else {
+      const int bp_h = r.off_fwd, bp_v = r.off_fwd - r.k_fwd;
+      if (bp_h < 0 || bp_v < 0 || bp_h > nd.tl || bp_v > nd.pl) {
+        if (c.knobs.debug) fprintf(stderr, "[wfm] problem %d: bialign job pl %d tl %d (at %d, %d of the problem; level %u, begin / end components %d %d, bound %d%s): breakpoint (%d, %d) outside, score %d = %d + %d comp %d k %d\n", nd.prob, nd.pl, nd.tl, nd.pb, nd.tb, c.level, nd.cb, nd.ce, k.jobs[q].sub, nd.hinted ? " guessed" : "", bp_v, bp_h, r.score, r.score_fwd, r.score_rev, r.comp, r.k_fwd);
+        if (const char* dd = getenv("WFM_DUMP_FAIL")) dump_failed_problem(c, nd, dd);
+        c.prob_status[nd.prob] = WFM_ST_UNREACHABLE; continue;
+      }
+      if (c.knobs.debug > 1) fprintf(stderr, "[wfm] problem %d level %u: job pl %d tl %d cb %d ce %d rem %d -> bp v %d h %d score %d = %d + %d comp %d\n", nd.prob, c.level, nd.pl, nd.tl, nd.cb, nd.ce, nd.score_rem, bp_v, bp_h, r.score, r.score_fwd, r.score_rev, r.comp);
+      push_children(c, nd, r, bp_v, bp_h);
+    }
+  }
+  return WFM_OK;
+}
+
+// The base jobs collected so far (incl. retries with a larger budget)
+int run_leaves(AlignCall& c) {
+  std::vector<Node> retry;
+  while (!c.base_nodes.empty()) {
+    retry.clear();
+    const auto tb0 = std::chrono::steady_clock::now();
+    const int rc = run_base_jobs(c.h, c.S, *c.pen, c.base_nodes, retry, c.prob_status, c.prob_cells, c.tm, c.pflags);
+    c.wall_base += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb0).count();
+    if (rc != WFM_OK) return rc;
+    c.base_nodes.swap(retry);
+  }
+  return WFM_OK;
+}
+
+void print_level_totals(const AlignCall& c) {
+  if (getenv("WFM_P2_COUNT") && atoi(getenv("WFM_P2_COUNT"))) {
+    unsigned long long n[8];
+    wfm::p2_counters(n);
+    fprintf(stderr, "[wfm] p2 overlap (cumulative): tests %llu, with candidates %llu, pairs listed %llu, blocks tested cell by cell %llu, pairs that met %llu; most pairs in a round %llu, most blocks one wave tested in a round %llu\n",
+            n[0], n[1], n[2], n[3], n[4], n[5], n[6]);
+  }
+  if (!c.knobs.debug) return;
+  if (c.hint_retries) fprintf(stderr, "[wfm] score hints: %llu roots ran past their hint and were run again without it\n", (unsigned long long)c.hint_retries);
+  if (c.band_jobs) fprintf(stderr, "[wfm] narrow rings: %llu jobs, %llu ran out of their band and were run again on full rings\n", (unsigned long long)c.band_jobs, (unsigned long long)c.band_retries);
+  if (c.grown_jobs)
+    fprintf(stderr, "[wfm] grown rings: %llu jobs, %llu widened and resumed, %llu started again, largest band %lld\n", (unsigned long long)c.grown_jobs,
+            (unsigned long long)c.grown_widened, (unsigned long long)c.grown_restarts, (long long)c.grown_maxband);
+  if (c.knobs.debug > 1) fprintf(stderr, "[wfm] ring arena: at most %.1f MB in a chunk\n", (double)c.ring_peak * 4.0 / 1048576.0);
+}
+
+// The RLE pieces of every problem, compacted on the device: the runs, and where each problem's begin and how many they are
+struct GatheredRuns { std::vector<uint32_t> runs; std::vector<int64_t> ostart; std::vector<int32_t> ocount; };
+int gather_runs(AlignCall& c, GatheredRuns& g) {
+  wfm_handle* h = c.h;
+  const size_t n = c.last - c.first;
+  std::vector<int64_t> poff(n), pcap(n);
+  for (size_t i = 0; i < n; ++i) { poff[i] = c.S->meta[c.first + i].rle_off; pcap[i] = (int64_t)c.S->meta[c.first + i].plen + c.S->meta[c.first + i].tlen; }
+  if (h->i64a.ensure(n) || h->i64b.ensure(n) || h->i64c.ensure(n) || h->i32a.ensure(n) || h->total.ensure(1)) {
+    h->err = "out of device memory"; return WFM_E_NOMEM;
+  }
+  HIPCHK(h, hipMemcpyAsync(h->i64a.p, poff.data(), n * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->i64b.p, pcap.data(), n * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemsetAsync(h->total.p, 0, sizeof(unsigned long long), h->stream));
+  launch_compact(h->rle.p, h->i64a.p, h->i64b.p, h->rle_out.p, h->total.p, h->i64c.p, h->i32a.p, (int)n, h->stream);
+  HIPCHK(h, hipGetLastError());
+  g.ostart.resize(n);
+  g.ocount.resize(n);
+  unsigned long long total = 0;
+  HIPCHK(h, hipMemcpyAsync(g.ostart.data(), h->i64c.p, n * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(g.ocount.data(), h->i32a.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(&total, h->total.p, sizeof(total), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  g.runs.resize((size_t)total + 1);
+  if (total) HIPCHK(h, hipMemcpy(g.runs.data(), h->rle_out.p, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return WFM_OK;
+}
+
+// Every problem's result: its runs expanded into the caller's arena (or merged into *runs_out).  Returns the number of problems
+// that failed, or an error.
+int write_results(AlignCall& c, const GatheredRuns& g, uint64_t* cells_total) {
+  std::vector<uint32_t>* runs_out = c.runs_out;
+  size_t arena_pos = runs_out ? runs_out->size() : c.arena_base;
+  if (runs_out) runs_out->reserve(runs_out->size() + g.runs.size() - 1);
+  int failed = 0;
+  for (size_t i = 0; i < c.last - c.first; ++i) {
+    const size_t gi = c.first + i;  // problem id
+    const ProbMeta& pm = c.S->meta[gi];
+    wfm_result_t& r = c.out[gi];
+    r.status = c.prob_status[gi];
+    r.cells = c.prob_cells[gi];
+    *cells_total += c.prob_cells[gi];
+    r.ops_off = arena_pos; r.ops_len = 0; r.n_runs = 0; r.score = -1;
+    if (r.status != WFM_ST_OK) { ++failed; continue; }
+    Expanded ex;
+    const int err = expand_runs(g.runs.data() + g.ostart[i], g.ocount[i], *c.pen, pm.plen, pm.tlen, runs_out ? nullptr : c.ops_arena + arena_pos,
+                                c.arena_bytes > arena_pos ? c.arena_bytes - arena_pos : 0, runs_out, &ex);
+    if (err == EXPAND_RUN_TOO_LONG) { c.h->err = "run too long"; return WFM_E_ARG; }
+    if (err == EXPAND_ARENA) { c.h->err = "ops arena too small"; return WFM_E_ARENA; }
+    if (err == EXPAND_SPANS) {
+      if (c.knobs.debug) fprintf(stderr, "[wfm] problem %zu: CIGAR spans %llu x %llu, sequences %d x %d\n", gi, (unsigned long long)ex.pc, (unsigned long long)ex.tc, pm.plen, pm.tlen);
+      r.status = WFM_ST_UNREACHABLE;  // internal inconsistency: never report a broken CIGAR as ok
+      ++failed;
+      continue;
+    }
+    r.ops_len = ex.ops_len; r.n_runs = ex.n_runs; r.score = ex.score;
+    arena_pos = runs_out ? runs_out->size() : arena_pos + ex.ops_len;
+  }
+  return failed;
+}
+
 // Aligns problems [first, last) of S; their op strings go to ops_arena from byte arena_base on.
 // runs_out != nullptr: run-length output (wfm_align_batch_rle) -- the part's merged runs are appended to *runs_out and
 // ops_off counts from the part's first run (the caller shifts the parts into one buffer); ops_arena is not touched
@@ -1043,693 +1661,70 @@ int align_resident_impl(wfm_handle* h, const wfm_penalties_t* pen, wfm_seqset* S
   if (rc != WFM_OK) { h->err = "unsupported penalties"; return rc; }
   const auto t_start = std::chrono::steady_clock::now();
   HIPCHK(h, hipSetDevice(h->device));
-  const size_t n = last - first;
   h->stats = wfm_stats_t{};
   std::fill(h->tile_ctr, h->tile_ctr + WFM_TILE_COUNTERS, (uint64_t)0);
-  if (n == 0) return 0;
-  const DevPen dp{pen->x, pen->o1, pen->e1, pen->o2, pen->e2};
-
-  // (read per call, not once per process: the tests run the bounded and the unbounded forms in one process)
-  const bool use_hints = !(getenv("WFM_SCORE_HINT") && atoi(getenv("WFM_SCORE_HINT")) == 0);
-  const bool use_bound = use_hints && !(getenv("WFM_BOUND") && atoi(getenv("WFM_BOUND")) == 0);
-  const int slack_env = getenv("WFM_SUB_SLACK") ? atoi(getenv("WFM_SUB_SLACK")) : -1;  // tests: < 0 default, >= 2^28 none
-  std::vector<int32_t> prob_status(S->meta.size(), WFM_ST_OK);  // indexed by problem id
-  std::vector<uint64_t> prob_cells(S->meta.size(), 0);
-
+  if (last == first) return 0;
+  AlignCall c{h, pen, S, first, last, out, ops_arena, arena_bytes, arena_base, runs_out, pflags, scope, DevPen{pen->x, pen->o1, pen->e1, pen->o2, pen->e2}};
+  c.prob_status.assign(S->meta.size(), WFM_ST_OK);
+  c.prob_cells.assign(S->meta.size(), 0);
   // RLE slot buffer (zero = empty)
   if (h->rle.ensure((size_t)S->rle_total + 16) || h->rle_out.ensure((size_t)S->rle_total + 16)) {
     h->err = "out of device memory (rle)"; return WFM_E_NOMEM;
   }
   HIPCHK(h, hipMemsetAsync(h->rle.p, 0, ((size_t)S->rle_total + 16) * sizeof(uint32_t), h->stream));
+  make_roots(c);
+  if ((rc = bound_roots(c)) != WFM_OK) return rc;
+  c.tcfg = tile_cfg(*pen, scope);
+  c.RR = ring_rows_for(scope);
+  c.rules = RingRules{c.tcfg.enabled, c.tcfg.min_len, c.tcfg.min_score, c.tcfg.chunk, c.tcfg.T, c.RR, h->mem_budget, c.knobs.band_root};
 
-  // roots
-  std::vector<Node> bp_nodes, base_nodes, next_bp, retry;
-  for (size_t i = first; i < last; ++i) {
-    const ProbMeta& pm = S->meta[i];
-    Node nd{};
-    nd.prob = (int32_t)i; nd.pb = 0; nd.pl = pm.plen; nd.tb = 0; nd.tl = pm.tlen;
-    nd.cb = C_M; nd.ce = C_M; nd.score_rem = INT_MAX; nd.endsfree = 0;
-    nd.sub = SUB_NONE; nd.hinted = 0;
-    if (pflags && pm.mode == WFM_MODE_END2END_BIWFA && !((size_t)i < S->acgt.size() && S->acgt[i])) pflags[i] |= WFM_PF_BYTE_KERNEL;
-    if (use_hints && pm.hint > 0 && pm.mode == WFM_MODE_END2END_BIWFA) { nd.sub = pm.hint; nd.hinted = 1; }
-    const int64_t bound = (int64_t)gapcost(*pen, pm.plen) + gapcost(*pen, pm.tlen) + 8;
-    if (pm.mode == WFM_MODE_ENDSFREE) {
-      nd.endsfree = 1;
-      // ends-free score is bounded by the cheaper all-gap alignment; start small, double on overflow
-      nd.smax = (int32_t)std::min<int64_t>(bound, 256);
-      base_nodes.push_back(nd);
-    } else if (pm.mode == WFM_MODE_END2END_UNI || std::max(pm.plen, pm.tlen) <= BIALIGN_FALLBACK_MIN_LENGTH ||
-               pm.plen == 0 || pm.tlen == 0) {
-      nd.smax = (int32_t)std::min<int64_t>(bound, 256);
-      base_nodes.push_back(nd);
-    } else {
-      bp_nodes.push_back(nd);
-    }
-  }
-
-  // ---- an upper bound of every long root's score, from one greedy walk per root (wfa_bound_kernel): rigorous, so the root's
-  // wavefronts are cut to what an alignment of at most that score can touch -- usually a fifth of what the caller's guess
-  // leaves.  The guess stays where the walk gives up (divergent records, structural differences).
-  uint64_t bounded_roots = 0, bound_gain = 0;
-  double bound_ms = 0;
-  {
-    std::vector<BoundJob> bj;
-    std::vector<size_t> owner;
-    if (use_bound)
-      for (size_t q = 0; q < bp_nodes.size(); ++q) {
-        const Node& nd = bp_nodes[q];
-        const ProbMeta& pm = S->meta[nd.prob];
-        // only where a bound can bind: the end diagonal far from the start diagonal (see BpJob::sub below)
-        if (pm.mode != WFM_MODE_END2END_BIWFA || std::min(nd.pl, nd.tl) < 1024 || std::abs(nd.tl - nd.pl) < 64) continue;
-        bj.push_back(BoundJob{pm.p_fwd, pm.t_fwd, nd.pl, nd.tl});
-        owner.push_back(q);
-      }
-    if (!bj.empty()) {
-      const auto tb0 = std::chrono::steady_clock::now();
-      if (h->bndjobs.ensure(bj.size()) || h->bndres.ensure(bj.size())) { h->err = "out of device memory (score bounds)"; return WFM_E_NOMEM; }
-      HIPCHK(h, hipMemcpyAsync(h->bndjobs.p, bj.data(), bj.size() * sizeof(BoundJob), hipMemcpyHostToDevice, h->stream));
-      launch_bound(S->d_seq, h->bndjobs.p, h->bndres.p, (int)bj.size(), dp, h->stream);
-      HIPCHK(h, hipGetLastError());
-      std::vector<int32_t> ub(bj.size());
-      HIPCHK(h, hipMemcpyAsync(ub.data(), h->bndres.p, bj.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-      HIPCHK(h, hipStreamSynchronize(h->stream));
-      for (size_t q = 0; q < bj.size(); ++q) {
-        if (ub[q] < 0) continue;
-        Node& nd = bp_nodes[owner[q]];
-        if (nd.sub == SUB_NONE || ub[q] < nd.sub) {
-          if (nd.sub != SUB_NONE) bound_gain += (uint64_t)(nd.sub - ub[q]);
-          nd.sub = ub[q];
-          nd.hinted = 1;  // (cannot fail; the retry of a root that runs past its bound stays as the safety net it is)
-          ++bounded_roots;
-        }
-      }
-      bound_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb0).count();
-      if (getenv("WFM_DEBUG"))
-        fprintf(stderr, "[wfm] score bounds: %zu roots walked in %.2f ms, %llu bounded (on average %.0f below the caller's guess)\n", bj.size(), bound_ms,
-                (unsigned long long)bounded_roots, bounded_roots ? (double)bound_gain / (double)bounded_roots : 0.0);
-    }
-  }
-
-  LevelTimer tm;
-  double wall_tile = 0, wall_base = 0;
-  std::vector<BpJob> jobs;
-  std::vector<int> tiled;
-  std::vector<int64_t> ring2, ring3;
-  std::vector<size_t> ring_third;  // elements of one ring of every tiled job of the chunk
-  const bool ring3_on = !(getenv("WFM_TILE_RING3") && atoi(getenv("WFM_TILE_RING3")) == 0);  // (these, too, per call: one process runs both forms)
-  const bool p2_on = !(getenv("WFM_P2") && atoi(getenv("WFM_P2")) == 0);
-  std::vector<int32_t> fine_from;
-  const int fine_margin = getenv("WFM_TILE_FINE_MARGIN") ? atoi(getenv("WFM_TILE_FINE_MARGIN")) : 48;
-  const int coarse_min_blocks = getenv("WFM_TILE_COARSE_MIN_BLOCKS") ? atoi(getenv("WFM_TILE_COARSE_MIN_BLOCKS")) : 32;
-  const int coarse_max_jobs = getenv("WFM_TILE_COARSE_MAX_JOBS") ? atoi(getenv("WFM_TILE_COARSE_MAX_JOBS")) : 128;
-  const TileCfg tcfg = tile_cfg(*pen, scope);
-  // WFM_TILE_V2=0: every tile on the byte kernel (wfa_tile_reg_kernel) -- the A/B switch of the packed kernel (wfa_tile2.hip)
-  const bool tile_v2 = !(getenv("WFM_TILE_V2") && atoi(getenv("WFM_TILE_V2")) == 0);
-  const int RR = ring_rows_for(scope);  // rows of every ring of this call
-  uint64_t tile_cells_level = 0;
-  uint64_t band_retries = 0, band_jobs = 0, roots_banded = 0, roots_out = 0, hint_retries = 0, hinted_roots = 0;
-  // Rings that grow with the score (DESIGN.md section 5): a job whose full ring does not fit the budget runs on bands b, 4 b, 16 b ...
-  uint64_t grown_jobs = 0, grown_widened = 0, grown_restarts = 0;
-  int64_t grown_maxband = 0;
-  size_t ring_peak = 0;  // most elements a chunk's ring arena held
-  GrownSnaps snaps;
-  std::vector<int> tiled_r;        // the chunk's jobs that go on from a snapshot (indices into jobs), their second rings, their fine_s
-  std::vector<int64_t> ring2_r;
-  std::vector<int32_t> fine_r, snap_r;
-  std::vector<char> grown_job, resume_bad;
-  bool roots_off = false;
-  std::vector<int32_t> node_of;
-  std::vector<BpResult> res;
-  uint32_t level = 0;
-  while (!bp_nodes.empty() || !base_nodes.empty()) {
-    ++level;
+  while (!c.bp_nodes.empty() || !c.base_nodes.empty()) {
+    ++c.level;
     // ---- breakpoint jobs of this level (chunked to the memory budget) ----
-    next_bp.clear();
-    // Rings cover every diagonal of a job ((pl + tl) columns of 1280 B, twice for tiled jobs): fine for a batch of
-    // few deep problems, wasteful for thousands of long low-divergence records, whose wavefronts stay within a few
-    // thousand diagonals and which would otherwise be worked off in many small chunks.  When the level does not fit
-    // the budget, jobs get rings for |k| <= band only: a child's total score is known (half of it per direction,
-    // plus the overlap phase), a root gets WFM_BAND_ROOT scores; whoever runs out of its band is run again on a
-    // full ring.  WFM_BAND=0 switches this off.
-    bool use_band = false, over_budget = false;
-    {
-      const char* be = getenv("WFM_BAND");
-      const int band_on = be ? atoi(be) : 1;
-      size_t total = 0;
-      for (const Node& nd : bp_nodes) total += (((size_t)nd.pl + nd.tl + 9 + 3) & ~(size_t)3) * 2 * 5 * RR * 2;
-      // (narrow rings whenever full ones would take more than 2 GB, not only when they would not fit: every fresh GB of a
-      // first hipMalloc costs ~30 ms on this driver, scripts/micro/malloc_cost2.hip, and a one-shot run pays it)
-      use_band = band_on && total * 4 > std::min<size_t>(h->mem_budget, (size_t)2 << 30);
-      over_budget = total * 4 > h->mem_budget;
-    }
-    static const size_t ring_chunk_bytes = (size_t)(getenv("WFM_RING_CHUNK_GB") ? std::max(1, atoi(getenv("WFM_RING_CHUNK_GB"))) : 4) << 30;
-    const char* bre = getenv("WFM_BAND_ROOT");
-    const int band_root = bre ? std::max(64, atoi(bre)) : 4096;
-    size_t i0 = 0;
-    while (i0 < bp_nodes.size()) {
-      jobs.clear();
-      node_of.clear();
-      size_t ring_elems = 0;
-      size_t i = i0;
-      int maxw = 0;
-      tiled.clear(); ring2.clear(); ring3.clear(); ring_third.clear(); fine_from.clear();
-      tiled_r.clear(); ring2_r.clear(); fine_r.clear(); snap_r.clear(); grown_job.clear();
-      int64_t fine_min_blocks_r = INT64_MAX;
-      int64_t fine_min_blocks = INT64_MAX;  // fewest blocks any tiled job of the chunk is expected to run before its directions meet
-      for (; i < bp_nodes.size(); ++i) {
-        const Node& nd = bp_nodes[i];
-        const ProbMeta& pm = S->meta[nd.prob];
-        size_t width = ((size_t)nd.pl + nd.tl + 9 + 3) & ~(size_t)3;  // columns 4 .. pl+tl+4, 16-byte chunks
-        const size_t full_width = width;
-        int koff = nd.pl + 4;
-        bool tile_it = tcfg.enabled && nd.pl + nd.tl >= tcfg.min_len &&
-                             (nd.score_rem == INT_MAX || nd.score_rem >= tcfg.min_score);
-        const bool tiles_take_it = tile_it;
-        int band = 0;
-        // (a root without a bound gets a guessed band only when the level would not fit otherwise: below the budget the
-        // guess has nothing to win and a deep record -- 5 % divergence: 6 k scores per direction -- everything to lose)
-        const bool known = nd.score_rem != INT_MAX || nd.sub != SUB_NONE;
-        if (use_band && (known || over_budget) && tile_it && !nd.noband && !(roots_off && nd.score_rem == INT_MAX)) {
-          // scores one direction is allowed to reach; the ring holds |k| <= band + 8, its left margin stays 4 columns
-          // (a root under a bound of its score leaves the tile phase once a direction passes (bound + 128) / 2)
-          int64_t dir_scores = nd.score_rem == INT_MAX ? (int64_t)band_root : (int64_t)nd.score_rem / 2 + 64;
-          if (nd.score_rem == INT_MAX && nd.sub != SUB_NONE) dir_scores = std::min<int64_t>(dir_scores, ((int64_t)nd.sub + 128) / 2 + 64);
-          const int64_t b = dir_scores + (int64_t)tcfg.chunk * tcfg.T + 16;
-          const int64_t shift = ((int64_t)nd.pl - (b + 8)) & ~(int64_t)3;  // columns cut off on the left, whole 16-byte chunks
-          const int64_t right = std::min<int64_t>(nd.tl, b + 8);           // largest diagonal kept
-          if (shift > 0) {
-            const size_t w = ((size_t)((int64_t)nd.pl - shift + right + 9) + 3) & ~(size_t)3;
-            if (w * 2 <= width) { band = (int)b; width = w; koff = (int)(nd.pl + 4 - shift); }
-          }
-        }
-        if (tile_it && width * 2 * 5 * RR * 2 * 4 > h->mem_budget) tile_it = false;  // two snapshot rings do not fit: step-by-step kernel
-        size_t need = width * 2 * 5 * RR * (tile_it ? 2 : 1);
-        // The ring does not fit the budget (the job's first attempt, without a band it could have had; or its full ring, after a band ran out
-        // or a guess of its score failed): a ring for max(4 x the band it had, WFM_BAND_ROOT) scores a direction -- the cells of a job grow with the
-        // square of the score it reaches, so all the attempts before the one that holds cost a fifteenth of it -- on the tile kernels where they
-        // take the job and two such rings fit, on the step kernel alone otherwise; no wider than the budget holds.  (A child's first band is what its
-        // known score asks for, as above.)  Once the band's ring would be as wide as the full one -- below the budget a band has to halve the ring
-        // to be worth a second attempt, here the full ring is no alternative -- or the job has spent the widest band the budget holds, its score
-        // is beyond the budget: WFM_ST_OOM.
-        bool grown = false;
-        if (need * 4 > h->mem_budget) {
-          const size_t col_bytes = (size_t)2 * 5 * RR * 4;  // one column of a ring
-          const int64_t first = nd.score_rem == INT_MAX ? (int64_t)band_root : (int64_t)nd.score_rem / 2 + 64 + (int64_t)tcfg.chunk * tcfg.T + 16;
-          int64_t nb = nd.band > 0 ? std::max<int64_t>(4 * (int64_t)nd.band, first) : first;
-          size_t gw = 0;
-          int gk = 0;
-          auto band_ring = [&](int64_t b) {  // the geometry of the guessed bands above
-            const int64_t shift = std::max<int64_t>(0, ((int64_t)nd.pl - (b + 8)) & ~(int64_t)3);  // (0: a short pattern, the ring is cut on the right only)
-            const int64_t right = std::min<int64_t>(nd.tl, b + 8);
-            gw = ((size_t)((int64_t)nd.pl - shift + right + 9) + 3) & ~(size_t)3;
-            gk = (int)(nd.pl + 4 - shift);
-            return gw < full_width;
-          };
-          bool fits = band_ring(nb);
-          if (fits && gw * col_bytes > h->mem_budget) {
-            nb = ((int64_t)(h->mem_budget / col_bytes) - 32) / 2;  // (a ring for b scores is at most 2 b + 32 columns wide)
-            fits = nb > (int64_t)nd.band && nb >= 64 && band_ring(nb) && gw * col_bytes <= h->mem_budget;
-          }
-          if (!fits) { prob_status[nd.prob] = WFM_ST_OOM; snaps.drop(nd.snap); continue; }
-          grown = true;
-          band = (int)nb; width = gw; koff = gk;
-          tile_it = tiles_take_it && width * col_bytes * 2 <= h->mem_budget;
-          need = width * 2 * 5 * RR * (tile_it ? 2 : 1);
-        }
-        // (a chunk of a level stops at 4 GB of rings even when the budget allows more: hundreds of jobs fill the device
-        // long before that, and every GB of a first allocation costs 30 - 70 ms.  C1 substitute, three handles in a fresh
-        // process: 8 GB chunks 8.3 s cold / 5.33 s warm, 4 GB 5.67 / 5.52, 2 GB 6.22 / 6.06 -- scripts/c1_cold.sh.  A chunk of
-        // fewer than 128 jobs may grow to 8 GB: C3's 21 roots of a part are 5.4 GB of full rings, and cut in two they fill the device worse.
-        // Tried and dropped: two launches per block, jobs without a score bound apart from those with one -- the plain kernel form
-        // has 7 % fewer instructions, the second launch cost more: C2 0.18 -> 0.21 s, C1 no better)
-        if (!jobs.empty() && (ring_elems + need) * 4 > std::min<size_t>(h->mem_budget, jobs.size() >= 128 ? ring_chunk_bytes : std::max(ring_chunk_bytes, (size_t)8 << 30))) break;
-        BpJob j{};
-        j.p_fwd = pm.p_fwd + nd.pb;
-        j.t_fwd = pm.t_fwd + nd.tb;
-        j.p_rev = pm.p_rev + (pm.plen - nd.pb - nd.pl);
-        j.t_rev = pm.t_rev + (pm.tlen - nd.tb - nd.tl);
-        j.ring_off = (int64_t)ring_elems;
-        j.pl = nd.pl; j.tl = nd.tl;
-        j.comp_begin = nd.cb; j.comp_end = nd.ce;
-        j.width = (int32_t)width;
-        j.koff = koff;
-        j.resume_s = -1; j.resume_sr = -1; j.last_fwd = 0; j.fmax0 = 0; j.rmax0 = 0;
-        j.band = band;
-        // a bound only earns its keep when the end diagonal is far from the start diagonal relative to the score (padded
-        // records and their children): for a balanced problem it starts to bind where the wavefronts meet, and costs the
-        // tile kernel its bookkeeping all the way there
-        j.sub = (nd.sub != SUB_NONE && (int64_t)std::abs(nd.tl - nd.pl) * 8 >= (int64_t)nd.sub) ? nd.sub : SUB_NONE;
-        j.best0 = 0;
-        j.packed = (tile_v2 && tcfg.reg && tcfg.C == 2 && (size_t)nd.prob < S->acgt.size() && S->acgt[(size_t)nd.prob]) ? 1 : 0;
-        // bit 1: near-identical sequences -- the job's score is known (a child's, a bounded or hinted root's) to be under a sixteenth of its length; the packed
-        // tile kernel then hands a lone long run to the whole wave at once (wfa_tile2.hip, tail_direct).  Whether the bound also CUTS the rows (sub below) is another matter.
-        if (j.packed && nd.sub != SUB_NONE && (int64_t)nd.sub * 16 < (int64_t)nd.pl + nd.tl) j.packed |= 2;
-        band_jobs += band > 0 && !grown;
-        grown_job.push_back((char)grown);
-        const bool resumes = grown && tile_it && nd.snap > 0;  // (a snapshot is the tile kernels' own: no gap rows as deep as the step kernel reads)
-        if (nd.snap > 0 && !resumes) snaps.drop(nd.snap);
-        if (grown) {
-          ++grown_jobs;
-          grown_maxband = std::max<int64_t>(grown_maxband, band);
-          if (resumes) ++grown_widened; else if (nd.noband || nd.band > 0) ++grown_restarts;
-          if (pflags) pflags[nd.prob] |= WFM_PF_RING_GROWN;
-          if (getenv("WFM_DEBUG"))
-            fprintf(stderr, "[wfm] grown ring: problem %d, %s of %d x %d: band %d, %zu columns on the %s%s\n", nd.prob, nd.score_rem == INT_MAX ? "root" : "child", nd.pl, nd.tl, band, width,
-                    tile_it ? "tile kernels" : "step kernel alone", resumes ? ", widened from its snapshot" : ((nd.noband || nd.band > 0) ? ", from score 0 again" : ""));
-        }
-        if (resumes) {
-          // the job's rule for per-score maxima is the one it started with (below); its blocks until the directions meet are counted from the snapshot
-          const GrownSnap& sn = snaps.v[(size_t)nd.snap - 1];
-          tiled_r.push_back((int)jobs.size()); ring2_r.push_back((int64_t)(ring_elems + need / 2)); snap_r.push_back(nd.snap);
-          const int64_t est = nd.score_rem != INT_MAX ? (int64_t)nd.score_rem : (int64_t)nd.pl + nd.tl;
-          fine_min_blocks_r = std::min<int64_t>(fine_min_blocks_r, std::max<int64_t>(0, est / 2 - sn.s0) / tcfg.T);
-          fine_r.push_back(nd.score_rem != INT_MAX ? std::max(0, nd.score_rem / 2 - fine_margin) : INT_MAX);
-        } else if (tile_it) {
-          tiled.push_back((int)jobs.size()); ring2.push_back((int64_t)(ring_elems + need / 2)); ring_third.push_back(need / 2);
-          // per-score maxima from here on (TileJob::fine_s): a child's directions meet near half its score (the trigger -- the sum of the two largest
-          // antidiagonals -- can fire a little earlier, never later); a root's score is anybody's guess: it finds its meeting block with one maximum
-          // per block and runs it again (whether the chunk uses any of this is decided below, once its jobs are known)
-          int ff;
-          const int64_t est = nd.score_rem != INT_MAX ? (int64_t)nd.score_rem : (nd.sub != SUB_NONE ? (int64_t)nd.sub : (int64_t)nd.pl + nd.tl);  // its score / the guess or bound / the worst case
-          fine_min_blocks = std::min<int64_t>(fine_min_blocks, est / 2 / tcfg.T);
-          if (nd.score_rem != INT_MAX) ff = std::max(0, nd.score_rem / 2 - fine_margin);
-          else ff = INT_MAX;
-          fine_from.push_back(ff);
-        }
-        node_of.push_back((int32_t)i);
-        ring_elems += need;
-        // widest wavefront this job can reach: 2 diagonals per score of one direction (~half the total score)
-        const int64_t est_w = nd.score_rem == INT_MAX ? (int64_t)width : std::min<int64_t>((int64_t)width, (int64_t)nd.score_rem + 128);
-        maxw = std::max(maxw, (int)est_w);
-        jobs.push_back(j);
-      }
-      const size_t chunk_end = i;
-      // One maximum per block instead of one per score (TileJob::fine_s) pays where a launch is a few deep jobs that move in step -- C3: 21 roots
-      // of 78 blocks each, -3.7 % per step -- and costs where it is hundreds of jobs of all depths: their blocks need both instantiations of the
-      // kernel side by side (two launches per block), and a root runs its meeting block a third time behind one more look of the host: C2 +10 %
-      // device time, the scaled C4 rank +3 % (gpurun_out/r6r/ab2.log).  So: only chunks of at most coarse_max_jobs jobs, every one of them
-      // at least coarse_min_blocks blocks deep; everybody else keeps the per-score maxima from the first block on (one launch per block, as before).
-      if (tiled.size() > (size_t)coarse_max_jobs || fine_min_blocks < (int64_t)coarse_min_blocks) std::fill(fine_from.begin(), fine_from.end(), 0);
-      if (tiled_r.size() > (size_t)coarse_max_jobs || fine_min_blocks_r < (int64_t)coarse_min_blocks) std::fill(fine_r.begin(), fine_r.end(), 0);
-      // third rings behind the chunk's rings (TileJob::ring_prev), for all of its tiled jobs or for none: where half as much again still fits the
-      // budget (and 12 GB: fresh memory is 30 ms per GB).  The chunk's composition does not depend on it.
-      {
-        size_t third = 0;
-        for (size_t x : ring_third) third += x;
-        const bool give = ring3_on && tcfg.reg && tcfg.exact && third > 0 && (ring_elems + third) * 4 <= std::min<size_t>(h->mem_budget, (size_t)12 << 30);
-        ring3.assign(tiled.size(), -1);
-        if (give)
-          for (size_t q = 0; q < tiled.size(); ++q) { ring3[q] = (int64_t)ring_elems; ring_elems += ring_third[q]; }
-      }
-      if (!jobs.empty()) {
-        if (h->ring.ensure(ring_elems + 16) || h->bpjobs.ensure(jobs.size()) || h->bpres.ensure(jobs.size())) {
-          h->err = "out of device memory (ring arena)"; return WFM_E_NOMEM;
-        }
-        ring_peak = std::max(ring_peak, ring_elems);
-        resume_bad.assign(jobs.size(), 0);
-        if (!tiled_r.empty()) {
-          // the snapshots of the jobs that go on where they stood, out of their blocks into the chunk's (wider) rings; the blocks go back
-          std::vector<RingWidenJob> wj;
-          int maxw_dst = 0;
-          for (size_t q = 0; q < tiled_r.size(); ++q) {
-            BpJob& j = jobs[(size_t)tiled_r[q]];
-            const GrownSnap& sn = snaps.v[(size_t)snap_r[q] - 1];
-            wj.push_back(RingWidenJob{sn.d, h->ring.p + j.ring_off, sn.w, sn.koff, j.width, j.koff, -(sn.s0 + 8), sn.s0 + 8});
-            maxw_dst = std::max(maxw_dst, j.width);
-            j.resume_s = sn.s0; j.resume_sr = -1; j.fmax0 = sn.fmax; j.rmax0 = sn.rmax;
-          }
-          if (h->widenjobs.ensure(wj.size())) { h->err = "out of device memory (ring arena)"; return WFM_E_NOMEM; }
-          HIPCHK(h, hipMemcpyAsync(h->widenjobs.p, wj.data(), wj.size() * sizeof(RingWidenJob), hipMemcpyHostToDevice, h->stream));
-          launch_ring_widen(h->widenjobs.p, (int)wj.size(), maxw_dst, RR, h->stream);
-          HIPCHK(h, hipGetLastError());
-          HIPCHK(h, hipStreamSynchronize(h->stream));
-          for (int32_t id : snap_r) snaps.drop(id);
-        }
-        {
-          double tms = 0; uint64_t tcells = 0;
-          const auto tw0 = std::chrono::steady_clock::now();
-          rc = run_tiled_phase(h, S, dp, scope, tcfg, tcfg.T, false, jobs, tiled, ring2, tms, tcells, level, &fine_from, &ring3);
-          if (rc == WFM_OK && tcfg.T_refine > 0 && tcfg.T_refine < tcfg.T && !(tcfg.reg && tcfg.exact))
-            rc = run_tiled_phase(h, S, dp, scope, tcfg, tcfg.T_refine, true, jobs, tiled, ring2, tms, tcells, level);
-          if (rc == WFM_OK && !tiled_r.empty()) {
-            std::vector<int> from_s(tiled_r.size());
-            const int resume_margin = getenv("WFM_RESUME_MARGIN") ? atoi(getenv("WFM_RESUME_MARGIN")) : 26;  // (tests: a large value sends every resumed job back to score 0)
-            for (size_t q = 0; q < tiled_r.size(); ++q) from_s[q] = jobs[(size_t)tiled_r[q]].resume_s;
-            rc = run_tiled_phase(h, S, dp, scope, tcfg, tcfg.T, true, jobs, tiled_r, ring2_r, tms, tcells, level, &fine_r);
-            for (size_t q = 0; rc == WFM_OK && q < tiled_r.size(); ++q) {
-              BpJob& j = jobs[(size_t)tiled_r[q]];
-              // The snapshot a job goes on from was written by a block of the tile kernels for the next block of the tile kernels: with a third ring
-              // in play (TileJob::ring_prev) it holds the gap components two rows and one row deep, not the 26 the overlap phase and the step kernel
-              // read.  A job whose directions meet within 26 scores of that snapshot would hand such rows on: it starts again on this band instead
-              // (26 scores out of the thousands the wider ring was made for).
-              const bool exact_end = j.resume_s >= 0 && j.resume_sr >= 0;
-              if (tcfg.reg && tcfg.exact && ((exact_end && std::min(j.resume_s, j.resume_sr) - from_s[q] < resume_margin) || (j.resume_s >= 0 && j.resume_sr < 0 && j.resume_s == from_s[q]))) {
-                j.resume_s = -3; j.resume_sr = -1;
-                resume_bad[(size_t)tiled_r[q]] = 1;
-              }
-              tiled.push_back(tiled_r[q]); ring2.push_back(ring2_r[q]);  // (from here on a tiled job like the others)
-            }
-          }
-          wall_tile += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw0).count();
-          if (rc != WFM_OK) return rc;
-          tm.bp_ms += tms; tm.tile_ms += tms;
-          h->stats.cells_bp += tcells; h->stats.cells_tile += tcells;
-          for (size_t q = 0; q < tiled.size(); ++q) (void)q;
-          tile_cells_level = tcells;
-        }
-        res.assign(jobs.size(), BpResult{});
-        // ---- phase 2 of the jobs the tile phase left exactly at their meeting point: rows computed ahead + scan + replay
-        std::vector<int> rest;  // jobs for the step kernel: not tiled, not exact, or not finished by the rows computed ahead
-        std::vector<BpResult> carry;  // breakpoints found by rounds of phase 2 that did not end the walk
-        std::vector<char> has_carry;
-        std::vector<int> more_set;
-        {
-          std::vector<int> cand;
-          std::vector<int64_t> other;
-          std::vector<char> is_cand(jobs.size(), 0);
-          if (p2_on && tcfg.reg && tcfg.exact)
-            for (size_t q = 0; q < tiled.size(); ++q) {
-              const BpJob& j = jobs[(size_t)tiled[q]];
-              if (j.resume_s >= 0 && j.resume_sr >= 0) { cand.push_back(tiled[q]); other.push_back(ring2[q]); is_cand[(size_t)tiled[q]] = 1; }
-            }
-          double pms = 0;
-          carry.assign(jobs.size(), BpResult{});
-          has_carry.assign(jobs.size(), 0);
-          const int p2_rounds = getenv("WFM_P2_ROUNDS") ? std::max(1, atoi(getenv("WFM_P2_ROUNDS"))) : 64;
-          std::vector<int> cand_r = cand, again;
-          std::vector<int64_t> other_r = other;
-          for (int round = 1; !cand_r.empty(); ++round) {
-            again.clear();
-            rc = run_p2_phase(h, S, dp, scope, tcfg, jobs, cand_r, other_r, res, pms, carry, has_carry, round < p2_rounds, again);
-            if (rc != WFM_OK) return rc;
-            std::vector<int> c2; std::vector<int64_t> o2;
-            for (int a : again) {
-              c2.push_back(cand_r[(size_t)a]); o2.push_back(other_r[(size_t)a]);
-              if (pflags) pflags[bp_nodes[(size_t)node_of[(size_t)cand_r[(size_t)a]]].prob] |= WFM_PF_P2_ROUNDS;
-            }
-            h->stats.p2_again += (uint32_t)again.size();
-            cand_r.swap(c2); other_r.swap(o2);
-          }
-          tm.bp_ms += pms;
-          for (size_t q = 0; q < jobs.size(); ++q)
-            if (!is_cand[q] || res[q].status == WFM_DEV_P2_MORE) { rest.push_back((int)q); h->stats.p2_more += is_cand[q]; if (is_cand[q]) more_set.push_back((int)q); }
-          if (pflags)  // jobs whose overlap walk went past the first round of rows computed ahead (or was finished by the step kernel)
-            for (size_t q = 0; q < jobs.size(); ++q)
-              if (is_cand[q] && res[q].status == WFM_DEV_P2_MORE) pflags[bp_nodes[(size_t)node_of[q]].prob] |= WFM_PF_P2_ROUNDS;
-        }
-        auto is_more = [&](int q) { return std::find(more_set.begin(), more_set.end(), q) != more_set.end(); };
-        if (!rest.empty()) {
-          // workgroup size: wide wavefronts want all 16 waves of a CU
-          int threads = 1024;
-          if (maxw <= 1024) threads = 256;
-          else if (maxw <= 8192) threads = 512;
-          std::vector<BpJob> rj(rest.size());
-          for (size_t q = 0; q < rest.size(); ++q) rj[q] = jobs[(size_t)rest[q]];
-          HIPCHK(h, hipMemcpyAsync(h->bpjobs.p, rj.data(), rj.size() * sizeof(BpJob), hipMemcpyHostToDevice, h->stream));
-          HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-          launch_bp(S->d_seq, h->ring.p, h->bpjobs.p, h->bpres.p, (int)rj.size(), threads, dp, scope, RR, h->stream);
-          HIPCHK(h, hipGetLastError());
-          HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-          std::vector<BpResult> rr(rj.size());
-          HIPCHK(h, hipMemcpyAsync(rr.data(), h->bpres.p, rr.size() * sizeof(BpResult), hipMemcpyDeviceToHost, h->stream));
-          HIPCHK(h, hipStreamSynchronize(h->stream));
-          float ms = 0;
-          HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-          tm.bp_ms += ms;
-          if (h->call_base) {
-            float t0 = 0;
-            HIPCHK(h, hipEventElapsedTime(&t0, h->call_base, h->ev0));
-            h->bp_iv.emplace_back(t0, t0 + ms);
-          }
-          h->stats.bp_launches++;
-          for (size_t q = 0; q < rest.size(); ++q) {
-            if (rr[q].status == WFM_DEV_P2_NOTHING) {  // (only jobs that carry a breakpoint are handed a best0)
-              const uint64_t c = rr[q].cells; const int32_t st = rr[q].steps;
-              rr[q] = carry[(size_t)rest[q]]; rr[q].cells = c; rr[q].steps = st;
-            }
-            res[(size_t)rest[q]] = rr[q];
-          }
-          if (getenv("WFM_DEBUG")) {
-            uint64_t c = 0; double t1 = 0, t2 = 0; int64_t st1 = 0, st = 0; uint32_t m1 = 0, m2 = 0;
-            for (const BpResult& r : rr) { c += r.cells; t1 += r.ticks_p1; t2 += r.ticks_p2; st1 += r.steps_p1; st += r.steps; m1 = std::max(m1, r.ticks_p1); m2 = std::max(m2, r.ticks_p2); }
-            fprintf(stderr, "[wfm] level %u: %zu bp jobs (step kernel), %d thr, %.3f ms, cells %.3e, avg steps p1 %.0f p2 %.0f, avg ms p1 %.3f p2 %.3f, max ms p1 %.3f p2 %.3f\n", level, rr.size(), threads, ms,
-                    (double)c, (double)st1 / rr.size(), (double)(st - st1) / rr.size(), t1 / rr.size() / 1e5, t2 / rr.size() / 1e5, m1 / 1e5, m2 / 1e5);
-            if (atoi(getenv("WFM_DEBUG")) > 1) {  // the slowest three
-              std::vector<size_t> ord(rr.size());
-              for (size_t q = 0; q < ord.size(); ++q) ord[q] = q;
-              std::sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return rr[a].ticks_p1 + rr[a].ticks_p2 > rr[b].ticks_p1 + rr[b].ticks_p2; });
-              for (size_t q = 0; q < std::min<size_t>(3, ord.size()); ++q) {
-                const BpResult& r = rr[ord[q]];
-                const BpJob& j = rj[ord[q]];
-                fprintf(stderr, "[wfm]   slow step-kernel job: pl %d tl %d width %d band %d sub %d resume %d/%d (%s), status %d score %d = %d + %d, steps p1 %d p2 %d, ms p1 %.3f p2 %.3f\n", j.pl, j.tl, j.width,
-                        j.band, j.sub == SUB_NONE ? -1 : j.sub, j.resume_s, j.resume_sr, is_more(rest[ord[q]]) ? "phase-2 walk ran out of rows" : (j.resume_sr >= 0 ? "exact" : "not exact"), r.status,
-                        r.score, r.score_fwd, r.score_rev, r.steps_p1, r.steps - r.steps_p1, r.ticks_p1 / 1e5, r.ticks_p2 / 1e5);
-              }
-            }
-          }
-        }
-        h->stats.bp_jobs += (uint32_t)jobs.size();
-        const int dbg_lvl = getenv("WFM_DEBUG") ? std::max(1, atoi(getenv("WFM_DEBUG"))) : 0;  // (once per chunk, not once per job)
-        for (size_t q = 0; q < jobs.size(); ++q) {
-          const Node nd = bp_nodes[(size_t)node_of[q]];  // a copy: retries are appended to bp_nodes below
-          const BpResult& r = res[q];
-          prob_cells[nd.prob] += r.cells;
-          h->stats.cells_bp += r.cells;
-          if (nd.score_rem == INT_MAX && jobs[q].band > 0 && !grown_job[q]) { ++roots_banded; roots_out += r.status == WFM_DEV_BAND; }
-          const bool guessed = nd.hinted && jobs[q].sub != SUB_NONE;  // the job really ran under the caller's guess
-          if (r.status == WFM_DEV_BAND || (guessed && (r.status < 0 || (r.status == 0 && r.score > nd.sub)))) {
-            // ran out of its narrow ring, or past the caller's guess of its score: once more, at the end of this level, on
-            // a full ring and without the guess
-            Node again = nd; again.noband = 1; again.sub = SUB_NONE; again.hinted = 0;
-            again.band = jobs[q].band; again.snap = 0;
-            if (pflags) pflags[nd.prob] |= nd.score_rem == INT_MAX ? WFM_PF_ROOT_AGAIN : WFM_PF_JOB_AGAIN;
-            // where the full ring does not fit, the job's next ring grows from the band it had (above)
-            const bool full_fits = ((((size_t)nd.pl + nd.tl + 9 + 3) & ~(size_t)3) * 2 * 5 * RR) * 4 <= h->mem_budget;
-            if (!full_fits) {
-              if (pflags) pflags[nd.prob] |= WFM_PF_RING_GROWN;
-              if (resume_bad[q]) again.band = nd.band;  // (the same band once more, from score 0)
-              // A tiled job that simply ran out of its band stands at a block boundary s0 <= band with both directions complete -- a row of score s
-              // spans |k| <= s, nothing was cut by the ring's edge -- and goes on from there: the columns |k| <= s0 + 8 of its snapshot wait in a block of
-              // their own for the job's wider ring (the chunk's arena is the next chunk's).  Not so a job under a bound of its score (rows cut to
-              // |k - (tl - pl)| <= sub - s: no state of the unbounded problem) or one the step kernel stopped: those start again from score 0.
-              const BpJob& j = jobs[q];
-              if (!resume_bad[q] && r.status == WFM_DEV_BAND && j.resume_s == -3 && j.resume_sr >= 0 && j.sub == SUB_NONE && j.band > 0) {
-                GrownSnap sn;
-                sn.s0 = j.resume_sr; sn.fmax = j.fmax0; sn.rmax = j.rmax0;
-                const int reach = sn.s0 + 8;
-                sn.koff = reach + 4;
-                sn.koff += ((j.koff - sn.koff) % 4 + 4) % 4;  // whole 16-byte chunks apart from the ring's columns, and from those of the ring to come
-                sn.w = (sn.koff + reach + 5 + 3) & ~3;
-                if (wfm_dmalloc((void**)&sn.d, (size_t)sn.w * 2 * 5 * RR * sizeof(int32_t)) != hipSuccess) { (void)hipGetLastError(); sn.d = nullptr; }
-                if (sn.d) {  // (no block to be had: the job starts again)
-                  const RingWidenJob wj{h->ring.p + j.ring_off, sn.d, j.width, j.koff, sn.w, sn.koff, -reach, reach};
-                  snaps.v.push_back(sn);
-                  again.snap = (int32_t)snaps.v.size();
-                  if (h->widenjobs.ensure(1)) { h->err = "out of device memory (ring arena)"; return WFM_E_NOMEM; }
-                  HIPCHK(h, hipMemcpyAsync(h->widenjobs.p, &wj, sizeof(wj), hipMemcpyHostToDevice, h->stream));
-                  launch_ring_widen(h->widenjobs.p, 1, sn.w, RR, h->stream);
-                  HIPCHK(h, hipGetLastError());
-                  HIPCHK(h, hipStreamSynchronize(h->stream));
-                }
-              }
-            }
-            // (it joins the next level's jobs instead of holding this level up on its own: nodes are independent, only the gather at
-            // the end waits for all of them.  Until round 5 a job that ran out of its ring was run again at the end of its own level --
-            // three chains of 30 - 40 tile blocks one after the other in the first level of an LPA batch, 19 of its 50 ms of tile time;
-            // WFM_RETRY_SAME_LEVEL=1 restores that for A/B runs)
-            static const bool same_level = getenv("WFM_RETRY_SAME_LEVEL") && atoi(getenv("WFM_RETRY_SAME_LEVEL")) != 0;
-            if (guessed || !same_level) next_bp.push_back(again); else bp_nodes.push_back(again);
-            band_retries += full_fits;
-            hint_retries += guessed;
-            continue;
-          }
-          if (r.status == 1) {  // end reached at score 0 -> base aligner
-            Node b = nd; b.smax = 0; base_nodes.push_back(b);
-          } else if (r.status != 0) {
-            if (getenv("WFM_DEBUG")) fprintf(stderr, "[wfm] problem %d: bialign job pl %d tl %d cb %d ce %d score_rem %d status %d (steps %d)\n", nd.prob, nd.pl, nd.tl, nd.cb, nd.ce, nd.score_rem, r.status, r.steps);
-            prob_status[nd.prob] = WFM_ST_UNREACHABLE;
-          } else {
-            const int bp_h = r.off_fwd, bp_v = r.off_fwd - r.k_fwd;
-            if (bp_h < 0 || bp_v < 0 || bp_h > nd.tl || bp_v > nd.pl) {
-              if (getenv("WFM_DEBUG")) fprintf(stderr, "[wfm] problem %d: bialign job pl %d tl %d (at %d, %d of the problem; level %u, begin / end components %d %d, bound %d%s): breakpoint (%d, %d) outside, score %d = %d + %d comp %d k %d\n", nd.prob, nd.pl, nd.tl, nd.pb, nd.tb, level, nd.cb, nd.ce, jobs[q].sub, nd.hinted ? " guessed" : "", bp_v, bp_h, r.score, r.score_fwd, r.score_rev, r.comp, r.k_fwd);
-              if (const char* dd = getenv("WFM_DUMP_FAIL")) {  // diagnosis: the whole problem's sequences, for a replay
-                const ProbMeta& pm = S->meta[nd.prob];
-                std::vector<char> pb((size_t)pm.plen), tb((size_t)pm.tlen);
-                (void)hipMemcpy(pb.data(), S->d_seq + pm.p_fwd, pb.size(), hipMemcpyDeviceToHost);
-                (void)hipMemcpy(tb.data(), S->d_seq + pm.t_fwd, tb.size(), hipMemcpyDeviceToHost);
-                static std::atomic<int> nfail{0};
-                const std::string fn = std::string(dd) + "/fail_" + std::to_string(nfail.fetch_add(1)) + ".txt";
-                if (FILE* f = fopen(fn.c_str(), "w")) {
-                  fprintf(f, "%d %d %d\n", pm.plen, pm.tlen, pm.hint);
-                  fwrite(pb.data(), 1, pb.size(), f); fputc('\n', f);
-                  fwrite(tb.data(), 1, tb.size(), f); fputc('\n', f);
-                  fclose(f);
-                }
-              }
-              prob_status[nd.prob] = WFM_ST_UNREACHABLE; continue;
-            }
-            if (dbg_lvl > 1) fprintf(stderr, "[wfm] problem %d level %u: job pl %d tl %d cb %d ce %d rem %d -> bp v %d h %d score %d = %d + %d comp %d\n", nd.prob, level, nd.pl, nd.tl, nd.cb, nd.ce, nd.score_rem, bp_v, bp_h, r.score, r.score_fwd, r.score_rev, r.comp);
-            Node a{}, b{};
-            a.prob = nd.prob; a.pb = nd.pb; a.pl = bp_v; a.tb = nd.tb; a.tl = bp_h;
-            // what a child can cost: the score its parent found for it, plus the opening of a gap it begins or ends in
-            // (counted on the other side of the breakpoint)
-            const int slack = slack_env >= 0 ? slack_env : 2 * std::max(pen->o1, pen->o2) + 8;
-            a.sub = (int)std::min<int64_t>((int64_t)r.score_fwd + slack, SUB_NONE);
-            b.sub = (int)std::min<int64_t>((int64_t)r.score_rev + slack, SUB_NONE);
-            a.hinted = 0; b.hinted = 0;
-            a.cb = nd.cb; a.ce = r.comp; a.score_rem = r.score_fwd;
-            b.prob = nd.prob; b.pb = nd.pb + bp_v; b.pl = nd.pl - bp_v; b.tb = nd.tb + bp_h; b.tl = nd.tl - bp_h;
-            b.cb = r.comp; b.ce = nd.ce; b.score_rem = r.score_rev;
-            for (Node* c : {&a, &b}) {
-              if (c->pl == 0 || c->tl == 0) { c->smax = 0; base_nodes.push_back(*c); }
-              else if (c->score_rem <= BIALIGN_FALLBACK_MIN_SCORE) {
-                // the leaf's own forward score: what the breakpoint credited it with, plus the opening of a gap it has
-                // to end in (counted on the other side of that breakpoint)
-                const int open_end = c->ce == C_M ? 0 : ((c->ce == C_I1 || c->ce == C_D1) ? pen->o1 : pen->o2);
-                c->smax = std::max(c->score_rem, 0) + open_end;
-                base_nodes.push_back(*c);
-              }
-              else next_bp.push_back(*c);
-            }
-          }
-        }
+    c.next_bp.clear();
+    level_budget(c);
+    for (size_t i0 = 0; i0 < c.bp_nodes.size(); i0 = c.ck.end) {
+      plan_chunk(c, i0);
+      if (!c.ck.jobs.empty()) {
+        if ((rc = widen_resumed(c)) != WFM_OK || (rc = run_chunk_tiles(c)) != WFM_OK || (rc = run_chunk_p2(c)) != WFM_OK ||
+            (rc = run_chunk_step(c)) != WFM_OK || (rc = settle_chunk(c)) != WFM_OK) return rc;
       }
       // a root's band is a guess (its score is not known): when the guess keeps failing -- a batch of divergent
       // records -- the remaining roots get full rings right away instead of paying for the attempt
-      if (!roots_off && roots_banded >= 16 && roots_out * 4 > roots_banded) roots_off = true;
-      i0 = chunk_end;
+      if (!c.rules.roots_off && c.roots_banded >= 16 && c.roots_out * 4 > c.roots_banded) c.rules.roots_off = true;
     }
-    bp_nodes.swap(next_bp);
-    // ---- base jobs collected so far (incl. retries with a larger budget) ----
+    c.bp_nodes.swap(c.next_bp);
     // Leaves do not feed the recursion: while bialign jobs are left they wait (round 5), and all levels' leaves go out together behind the
     // last level -- two launches of thousands of leaves instead of two of hundreds per level, each with its wait for the device in the chain of
     // the batch's launches (C2: 12 launches + waits per part -> 3).  WFM_LEAVES_PER_LEVEL=1: the round-4 order; a quarter of a million leaves
-    // waiting are run anyway (their arenas are chunked to the budget either way).
+    // waiting are run anyway (their arenas are chunked to the budget either way).  (Once per process.)
     static const bool leaves_per_level = getenv("WFM_LEAVES_PER_LEVEL") && atoi(getenv("WFM_LEAVES_PER_LEVEL")) != 0;
-    if (!leaves_per_level && !bp_nodes.empty() && base_nodes.size() < ((size_t)1 << 18)) continue;
-    while (!base_nodes.empty()) {
-      retry.clear();
-      const auto tb0 = std::chrono::steady_clock::now();
-      rc = run_base_jobs(h, S, *pen, base_nodes, retry, prob_status, prob_cells, tm, pflags);
-      wall_base += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb0).count();
-      if (rc != WFM_OK) return rc;
-      base_nodes.swap(retry);
-    }
+    if (!leaves_per_level && !c.bp_nodes.empty() && c.base_nodes.size() < ((size_t)1 << 18)) continue;
+    if ((rc = run_leaves(c)) != WFM_OK) return rc;
   }
-  h->stats.levels = level;
-  if (getenv("WFM_P2_COUNT") && atoi(getenv("WFM_P2_COUNT"))) {
-    unsigned long long c[8];
-    wfm::p2_counters(c);
-    fprintf(stderr, "[wfm] p2 overlap (cumulative): tests %llu, with candidates %llu, pairs listed %llu, blocks tested cell by cell %llu, pairs that met %llu; most pairs in a round %llu, most blocks one wave tested in a round %llu\n",
-            c[0], c[1], c[2], c[3], c[4], c[5], c[6]);
-  }
-  if (getenv("WFM_DEBUG") && hint_retries) fprintf(stderr, "[wfm] score hints: %llu roots ran past their hint and were run again without it\n", (unsigned long long)hint_retries);
-  (void)hinted_roots;
-  if (getenv("WFM_DEBUG") && band_jobs) fprintf(stderr, "[wfm] narrow rings: %llu jobs, %llu ran out of their band and were run again on full rings\n", (unsigned long long)band_jobs, (unsigned long long)band_retries);
-  if (getenv("WFM_DEBUG") && grown_jobs)
-    fprintf(stderr, "[wfm] grown rings: %llu jobs, %llu widened and resumed, %llu started again, largest band %lld\n", (unsigned long long)grown_jobs,
-            (unsigned long long)grown_widened, (unsigned long long)grown_restarts, (long long)grown_maxband);
-  if (getenv("WFM_DEBUG") && atoi(getenv("WFM_DEBUG")) > 1) fprintf(stderr, "[wfm] ring arena: at most %.1f MB in a chunk\n", (double)ring_peak * 4.0 / 1048576.0);
+  h->stats.levels = c.level;
+  print_level_totals(c);
   const auto t_levels = std::chrono::steady_clock::now();
 
-  // ---- gather RLE pieces ----
-  std::vector<int64_t> poff(n), pcap(n);
-  for (size_t i = 0; i < n; ++i) { poff[i] = S->meta[first + i].rle_off; pcap[i] = (int64_t)S->meta[first + i].plen + S->meta[first + i].tlen; }
-  if (h->i64a.ensure(n) || h->i64b.ensure(n) || h->i64c.ensure(n) || h->i32a.ensure(n) || h->total.ensure(1)) {
-    h->err = "out of device memory"; return WFM_E_NOMEM;
-  }
-  HIPCHK(h, hipMemcpyAsync(h->i64a.p, poff.data(), n * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(h->i64b.p, pcap.data(), n * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemsetAsync(h->total.p, 0, sizeof(unsigned long long), h->stream));
-  launch_compact(h->rle.p, h->i64a.p, h->i64b.p, h->rle_out.p, h->total.p, h->i64c.p, h->i32a.p, (int)n, h->stream);
-  HIPCHK(h, hipGetLastError());
-  std::vector<int64_t> ostart(n);
-  std::vector<int32_t> ocount(n);
-  unsigned long long total = 0;
-  HIPCHK(h, hipMemcpyAsync(ostart.data(), h->i64c.p, n * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(ocount.data(), h->i32a.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(&total, h->total.p, sizeof(total), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  std::vector<uint32_t> runs((size_t)total + 1);
-  if (total) HIPCHK(h, hipMemcpy(runs.data(), h->rle_out.p, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost));
-
-  // ---- expand to op strings ----
-  static const char opc[4] = {'M', 'X', 'I', 'D'};
-  size_t arena_pos = runs_out ? runs_out->size() : arena_base;
-  if (runs_out) runs_out->reserve(runs_out->size() + (size_t)total);
-  int failed = 0;
+  GatheredRuns g;
+  if ((rc = gather_runs(c, g)) != WFM_OK) return rc;
   uint64_t cells_total = 0;
-  for (size_t i = 0; i < n; ++i) {
-    const size_t gi = first + i;  // problem id
-    wfm_result_t& r = out[gi];
-    r.status = prob_status[gi];
-    r.cells = prob_cells[gi];
-    cells_total += prob_cells[gi];
-    r.ops_off = arena_pos; r.ops_len = 0; r.n_runs = 0; r.score = -1;
-    if (r.status != WFM_ST_OK) { ++failed; continue; }
-    const uint32_t* e = runs.data() + ostart[i];
-    const int cnt = ocount[i];
-    int64_t score = 0;
-    uint64_t pc = 0, tc = 0;
-    uint32_t nruns = 0;
-    size_t pos = arena_pos;
-    int k = 0;
-    while (k < cnt) {
-      const int op = (int)(e[k] & 3u);
-      uint64_t len = e[k] >> 2;
-      int k2 = k + 1;
-      while (k2 < cnt && (int)(e[k2] & 3u) == op) { len += e[k2] >> 2; ++k2; }
-      if (runs_out) {
-        if (len >= (1u << 30)) { h->err = "run too long"; return WFM_E_ARG; }
-        runs_out->push_back((uint32_t)(len << 2) | (uint32_t)op);
-      } else {
-        if (pos + len > arena_bytes) { h->err = "ops arena too small"; return WFM_E_ARENA; }
-        memset(ops_arena + pos, opc[op], (size_t)len);
-        pos += (size_t)len;
-      }
-      ++nruns;
-      if (op == OP_X) { score += (int64_t)len * pen->x; pc += len; tc += len; }
-      else if (op == OP_M) { pc += len; tc += len; }
-      else {
-        score += std::min<int64_t>(pen->o1 + (int64_t)len * pen->e1, pen->o2 + (int64_t)len * pen->e2);
-        if (op == OP_I) tc += len; else pc += len;
-      }
-      k = k2;
-    }
-    if (pc != (uint64_t)S->meta[gi].plen || tc != (uint64_t)S->meta[gi].tlen) {
-      if (getenv("WFM_DEBUG")) fprintf(stderr, "[wfm] problem %zu: CIGAR spans %llu x %llu, sequences %d x %d\n", gi, (unsigned long long)pc, (unsigned long long)tc, S->meta[gi].plen, S->meta[gi].tlen);
-      r.status = WFM_ST_UNREACHABLE;  // internal inconsistency: never report a broken CIGAR as ok
-      ++failed;
-      if (runs_out) runs_out->resize(arena_pos);
-      continue;
-    }
-    if (runs_out) {
-      // ops spelled: every M / X op advances both sequences, I the text, D the pattern
-      uint64_t both = 0;
-      for (size_t q = arena_pos; q < runs_out->size(); ++q) if (((*runs_out)[q] & 3u) <= (uint32_t)OP_X) both += (*runs_out)[q] >> 2;
-      r.ops_len = (uint32_t)(pc + tc - both);
-      pos = runs_out->size();
-    } else {
-      r.ops_len = (uint32_t)(pos - arena_pos);
-    }
-    r.n_runs = nruns;
-    r.score = (int32_t)score;
-    arena_pos = pos;
-  }
+  const int failed = write_results(c, g, &cells_total);
+  if (failed < 0) return failed;
   cells_total += h->stats.cells_tile;
   h->stats.cells = cells_total;
   uint64_t range_bases = 0;
   for (size_t i = first; i < last; ++i) range_bases += (uint64_t)S->meta[i].plen + (uint64_t)S->meta[i].tlen;
   h->stats.bytes_algorithmic = 48ull * cells_total + range_bases;
-  h->stats.ms_breakpoint = tm.bp_ms;
-  h->stats.ms_tile = tm.tile_ms;
-  h->stats.ms_base = tm.base_ms;
-  h->stats.ms_kernels = tm.bp_ms + tm.base_ms;
+  h->stats.ms_breakpoint = c.tm.bp_ms;
+  h->stats.ms_tile = c.tm.tile_ms;
+  h->stats.ms_base = c.tm.base_ms;
+  h->stats.ms_kernels = c.tm.bp_ms + c.tm.base_ms;
   h->stats.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
-  if (getenv("WFM_DEBUG"))
+  if (c.knobs.debug)
     fprintf(stderr, "[wfm] wall: total %.2f ms | levels %.2f (tile phase %.2f incl. kernels %.2f; base phase %.2f incl. kernels %.2f; bp kernels %.2f) | gather+expand %.2f\n",
-            h->stats.ms_total, std::chrono::duration<double, std::milli>(t_levels - t_start).count(), wall_tile, tm.tile_ms, wall_base, tm.base_ms,
-            tm.bp_ms - tm.tile_ms, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_levels).count());
+            h->stats.ms_total, std::chrono::duration<double, std::milli>(t_levels - t_start).count(), c.wall_tile, c.tm.tile_ms, c.wall_base, c.tm.base_ms,
+            c.tm.bp_ms - c.tm.tile_ms, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_levels).count());
   return failed;
 }
 
@@ -2342,6 +2337,7 @@ int align_resident_any(wfm_handle_t* h, const wfm_penalties_t* pen, wfm_seqset_t
     // (C4-like records, 60 Mbp of queries: 2 -> 2.6 s, 3 -> 3.5 s)
     size_t ring_bytes = 0;
     for (size_t i = 0; i < n && ring_bytes <= h->mem_budget_full; ++i)
+      // (an estimate of its own, not ring_elems of wfa_plan.h: the default depth whatever the penalties, no rounding to 16-byte chunks)
       ring_bytes += ((size_t)s->meta[i].plen + (size_t)s->meta[i].tlen + 9) * 2 * 5 * RING * 2 * 4;
     if (ring_bytes > h->mem_budget_full) parts = 2;
   }

@@ -9,6 +9,7 @@
 #include "../../include/wfmash_host.h"
 #include "../csrc/wfa_handle.h"
 #include "../csrc/wfa_pack.h"
+#include "../csrc/wfa_plan.h"
 #include "aligner.hpp"
 #include "fasta.hpp"
 #include "map_stats.hpp"
@@ -119,6 +120,34 @@ unsigned long long wfmh_test_plan_batch_bytes(unsigned long long file_bytes, uns
                                               unsigned long long row_bases_sum, unsigned long long batch_records, unsigned long long batch_bases,
                                               unsigned long long nworkers, unsigned long long ngpu, unsigned long long min_batches, int level) {
   return align::Aligner::plan_batch_bytes(file_bytes, rows, row_bytes, row_bases_sum, batch_records, batch_bases, nworkers, ngpu, min_batches, level != 0);
+}
+
+// test hook: which ring a BiWFA job gets (csrc/wfa_plan.h, plan_ring), pure arithmetic.  node: pl, tl, score_rem, sub, noband, band;
+// rules: tiles enabled, min_len, min_score, chunk, T, RR, use_band, over_budget, roots_off, band_root.  Returns 0 and
+// out = {width, koff, band, tile_it, grown, need}, or WFM_ST_OOM.
+int wfmh_test_ring_plan(const int32_t* node, const int32_t* rules, unsigned long long mem_budget, int64_t* out) {
+  wfm::Node nd{};
+  nd.pl = node[0]; nd.tl = node[1]; nd.score_rem = node[2]; nd.sub = node[3]; nd.noband = node[4]; nd.band = node[5];
+  wfm::RingRules r{rules[0] != 0, rules[1], rules[2], rules[3], rules[4], rules[5], (size_t)mem_budget, rules[9], rules[6] != 0, rules[7] != 0, rules[8] != 0};
+  const wfm::RingPlan p = wfm::plan_ring(nd, r);
+  if (!p.fits) return WFM_ST_OOM;
+  const int64_t v[6] = {(int64_t)p.width, p.koff, p.band, p.tile_it, p.grown, (int64_t)p.need};
+  std::copy(v, v + 6, out);
+  return 0;
+}
+
+// test hook: a problem's runs into its op string (csrc/wfa_plan.h, expand_runs).  rle == 0: op bytes into ops[0 .. ops_cap); else the
+// merged runs go behind the *n_runs_io entries runs_io already holds (room for runs_cap), *n_runs_io = what it holds afterwards.
+// res = {score, n_runs, ops_len}.  Returns expand_runs' code: 0, 1 spans do not match, 2 arena too small, 3 run too long.
+int wfmh_test_expand_runs(const uint32_t* runs, int n, const wfm_penalties_t* pen, int plen, int tlen, int rle, char* ops, size_t ops_cap,
+                          uint32_t* runs_io, size_t* n_runs_io, size_t runs_cap, int64_t* res) {
+  std::vector<uint32_t> v;
+  if (rle) v.assign(runs_io, runs_io + *n_runs_io);
+  wfm::Expanded ex;
+  const int rc = wfm::expand_runs(runs, n, *pen, plen, tlen, ops, ops_cap, rle ? &v : nullptr, &ex);
+  if (rle) { std::copy(v.begin(), v.begin() + std::min(v.size(), runs_cap), runs_io); *n_runs_io = v.size(); }
+  res[0] = ex.score; res[1] = ex.n_runs; res[2] = ex.ops_len;
+  return rc;
 }
 
 char* wfmh_test_cigar(const char* fn, const char* a, const char* b, const char* query, const char* target,
