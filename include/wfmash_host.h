@@ -91,6 +91,13 @@ void  wfmh_free(char* p);
 /* Test hook of the align driver's sub-window translation (resident_sequences): [a, b) of a side that is the window
  * [win_start, win_end) of a stored sequence -- reverse-complemented when rev -- as the forward window [*out_start, *out_end). */
 void  wfmh_test_subwindow(int64_t win_start, int64_t win_end, int rev, int64_t a, int64_t b, int64_t* out_start, int64_t* out_end);
+/* Test hooks of the tile phase's, phase 2's and the base jobs' planning (csrc/wfa_rows.h, csrc/wfa_plan.h; pure arithmetic, no GPU):
+ * the layouts of their arguments are described at their definitions (host/capi_host.cpp) and wrapped by tests/test_tile_plan_cpu.py. */
+int wfmh_test_rows(const int32_t* q, int64_t n, int64_t* out);
+int wfmh_test_tile_plan(const int32_t* jobs, int64_t n, const int32_t* rules, int32_t* per_block, int32_t* tasks, int64_t tasks_cap, int64_t* scalars);
+int wfmh_test_p2_plan(const int32_t* cand, int64_t n, int64_t i0, int rows, int rows_bm, unsigned long long budget, int threads, int core, int64_t* geo,
+                      int32_t* tasks, int64_t tasks_cap, int64_t* scalars);
+int wfmh_test_base_plan(int op, const int32_t* in, int64_t n, int32_t* out);
 /* host winnowing stage of wfm_add_minmers on caller-supplied canonical k-mer hashes (CPU tests) */
 int64_t wfmh_test_winnow(const char* seq, int64_t len, int k, int w, int s, int32_t seq_id,
                          const uint64_t* hash, const int8_t* strand, wfm_minmer_t* out, int64_t cap);

@@ -16,6 +16,11 @@ The battery (small shapes, a few seconds):
   d  sixteen pairs of 5 kbp under penalties (5, 8, 2, 100, 1): scope 102, rings of 128 rows, no tiles
   e  sixteen ends-free patch problems
   f  the pairs of a through the run-length entry point
+  g  twelve pairs of tests/tile_path_cases (4000 bases) with their N twins in one call, at WFM_TILE_T 100 (g) and 32 (g32): tiles of
+     the packed kernel and of the byte kernel in one task list
+  h  four pairs of 3 kbp at 15 - 25 % whose phase 2 takes further rounds (more launches of phase 2 than levels)
+  i  four ends-free patches of tests/test_align_gpu.py's wide set: base jobs on tiles (wfa_base2t_kernel)
+A case of g, h, i that does not show its path in build A's dump ends the run: it is to be replaced, not kept.
 """
 import argparse
 import json
@@ -62,8 +67,57 @@ def _balanced(seed, length, rate, n):
     return out
 
 
+# (seed, length, mutation rate) of the pairs of case h
+H_PAIRS = ((0x3BBA, 3000, 0.17), (0x3BBC, 3000, 0.19), (0x3BBE, 3000, 0.21), (0x3BC0, 3000, 0.23))
+
+
+def _diverged(seed, length, rate):
+    from wfmash_amd import synth
+    p = synth.random_dna(seed, length)
+    return p, synth.mutate(p, rate, seed + 0x20000)
+
+
+def _tile_pairs():
+    """twelve members of the tile-path family, each followed by its twin with one N"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import tile_path_cases as tp
+    out = []
+    for K, dels, side in [(10, (0, 0, 0, 0), 0), (13, (1, 0, 0, 2), 1), (20, (0, 2, 2, 0), 0), (41, (0, 0, 0, 0), 0), (42, (3, 0, 0, 1), 1), (50, (4, 1, 0, 4), 0),
+                          (64, (2, 0, 0, 0), 1), (77, (0, 0, 0, 3), 0), (90, (1, 3, 3, 1), 1), (120, (0, 0, 0, 0), 0), (141, (2, 0, 0, 2), 0), (158, (4, 0, 0, 0), 1)]:
+        p, t = tp.make_pair(K, dels, side)
+        out += [(p, t), tp.n_twin(tp.Case(K, dels, side, p, t, 0, 0, 0))]
+    return out
+
+
+def _wide_patches():
+    """the head and the tail form of the first two shapes of test_wide_patches_on_tiles_match_oracle"""
+    from wfmash_amd import capi, synth
+    out = []
+    for i, (L, div, pre) in enumerate([(3400, 0.10, 0), (3000, 0.14, 0)]):
+        p = synth.random_dna(5100 + i, L)
+        t = synth.random_dna(5200 + i, pre) + synth.mutate(p, div, 5300 + i)
+        out += [(p, t, capi.WFM_MODE_ENDSFREE, len(p), 0, len(t), 0), (p, t, capi.WFM_MODE_ENDSFREE, 0, len(p), 0, len(t))]
+    return out
+
+
+def shows_its_path(dump):
+    """-> the cases of g, h, i whose path the dump does not show"""
+    from wfmash_amd import capi
+    flags = lambda case: [p["flags"] for p in dump[case]["problems"]]
+    bad = []
+    for g in ("g", "g32"):
+        byte = [bool(f & capi.WFM_PF_BYTE_KERNEL) for f in flags(g)]
+        if not (any(byte) and not all(byte) and dump[g]["tile"]["jobs"] > 0):
+            bad.append(g)
+    if not dump["h"]["stats"]["p2_launches"] > dump["h"]["stats"]["levels"]:
+        bad.append("h")
+    if not all(f & capi.WFM_PF_BASE_TILES for f in flags("i")):
+        bad.append("i")
+    return bad
+
+
 def battery():
-    """(name, WFM_MEM_BUDGET_MB or None, penalties or None, run-length?, items)"""
+    """(name, WFM_MEM_BUDGET_MB or None, penalties or None, run-length?, items, further switches of the environment)"""
     from wfmash_amd import capi, synth
     small = _pairs(5, 64, [0, 100, 700, 1500, 3000], [0.0, 0.01, 0.05, 0.15])
     hinted = []
@@ -76,22 +130,27 @@ def battery():
     for p, t in _pairs(9, 16, [300, 600, 1200], [0.02, 0.08]):
         p, t = p or b"ACGT", t or b"ACG"
         patches.append((p, t, capi.WFM_MODE_ENDSFREE, len(p), 0, len(t), 0))
-    return [("a", None, None, False, small),
-            ("b", 128, None, False, _balanced(0x1001, 80_000, 0.04, 3)),
-            ("c", 128, None, False, hinted),
-            ("d", None, (5, 8, 2, 100, 1), False, _pairs(7, 16, [5000], [0.01, 0.04])),
-            ("e", None, None, False, patches),
-            ("f", None, None, True, small)]
+    return [("a", None, None, False, small, {}),
+            ("b", 128, None, False, _balanced(0x1001, 80_000, 0.04, 3), {}),
+            ("c", 128, None, False, hinted, {}),
+            ("d", None, (5, 8, 2, 100, 1), False, _pairs(7, 16, [5000], [0.01, 0.04]), {}),
+            ("e", None, None, False, patches, {}),
+            ("f", None, None, True, small, {}),
+            ("g", None, None, False, _tile_pairs(), {"WFM_TILE_T": "100"}),
+            ("g32", None, None, False, _tile_pairs(), {"WFM_TILE_T": "32"}),
+            ("h", None, None, False, [_diverged(*spec) for spec in H_PAIRS], {}),
+            ("i", None, None, False, _wide_patches(), {})]
 
 
 def child(dump_path):
     from wfmash_amd import capi
     dump = {"library": capi.LIB_PATH}
-    for name, budget_mb, pen, rle, items in battery():
+    for name, budget_mb, pen, rle, items, env in battery():
         if budget_mb is None:
             os.environ.pop("WFM_MEM_BUDGET_MB", None)
         else:
             os.environ["WFM_MEM_BUDGET_MB"] = str(budget_mb)
+        os.environ.update(env)
         h = capi.Handle(0)
         try:
             if rle:
@@ -107,6 +166,8 @@ def child(dump_path):
             dump[name] = dict(problems=res, stats=stats, tile=h.tile_counters())
         finally:
             h.close()
+            for k in env:
+                del os.environ[k]
         print(f"case {name}: {len(items)} problems, statuses {sorted(set(r['status'] for r in res))}", flush=True)
     with open(dump_path, "w") as f:
         json.dump(dump, f, sort_keys=True)
@@ -145,7 +206,10 @@ def main():
     if a.child:
         return child(a.child)
     os.makedirs(a.out, exist_ok=True)
-    a1 = _fields(run_child(a.lib_a, os.path.join(a.out, "a1.json"), a.limit))
+    first = run_child(a.lib_a, os.path.join(a.out, "a1.json"), a.limit)
+    if shows_its_path(first):
+        sys.exit("build A does not show the path of: " + ", ".join(shows_its_path(first)))
+    a1 = _fields(first)
     a2 = _fields(run_child(a.lib_a, os.path.join(a.out, "a2.json"), a.limit))
     unstable = sorted({k[1] for k in a1 if a1[k] != a2.get(k)})
     print("unstable between two runs of A (left out):", unstable or "none")

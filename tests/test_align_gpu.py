@@ -649,7 +649,7 @@ def test_phase2_work_list_overflow_path(oracle, tmp_path):
 
 def test_cells_the_rooflines_count_against_the_oracles_own_count(oracle, monkeypatch):
     """The numerator of every roofline figure is a count of (score, diagonal) cells made by the host in closed form
-    (wfa_host.hip: h_cells_sum over the rows' ranges [max(-pl, -s), min(tl, s)] cut by the score bounds).  Held here against
+    (wfa_plan.h: cells_sum over the rows' ranges [max(-pl, -s), min(tl, s)] cut by the score bounds).  Held here against
     the oracle's own count (wfo_stats_t.cells: the width of every wavefront WFA2-lib's recursion computes, after trimming):
     with the bounds switched off -- no hints, no walk, children without their parents' scores -- the device computes the
     reference's rows, and its UNIQUE cells (the block in which a job's wavefronts meet is computed twice and counted once)

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "wfa_rows.h"
+
 namespace wfm {
 
 constexpr int WF_NULL = -(1 << 30);
@@ -22,7 +24,6 @@ enum { BT_I1_EXT = 8, BT_I2_EXT = 16, BT_D1_EXT = 32, BT_D2_EXT = 64 };
 constexpr int WFM_DEV_UNREACHABLE = -300;
 constexpr int WFM_DEV_OVERFLOW = -2;  // base job exceeded its score budget (smax)
 constexpr int WFM_DEV_BAND = -4;      // bialign job ran out of its diagonal band (BpJob::band)
-constexpr int SUB_NONE = 1 << 29;     // "no upper bound of the score is known" (BpJob::sub, TileJob::sub, P2Job::sub)
 constexpr int WFM_DEV_P2_NOTHING = -6; // phase 2 ended without improving on the breakpoint it was handed (BpJob / P2Job::best0): that one stands
 constexpr int WFM_DEV_P2_MORE = -5;   // phase 2 did not end within the P2K rows computed ahead: the step kernel takes the job
 
@@ -110,7 +111,7 @@ struct TileJob {
 // 2 * P2K tests (WFM_DEV_P2_MORE) is finished by wfa_bp_kernel from the same snapshot.
 constexpr int P2K = 32;            // (48 until jobs could take further rounds: most walks end within 2 x 26 tests, and the rows of the
                                     // others are computed when they are asked for -- C3 109 -> 106 ms per step, C1 substitute 5.5 -> 5.4 s)
-constexpr int P2ROWS = 26 + P2K;   // row maxima per direction: the snapshot's rows sd-25 .. sd, then sd+1 .. sd+P2K
+constexpr int P2ROWS = SNAP_ROWS + P2K;  // row maxima per direction: the snapshot's rows sd-25 .. sd, then sd+1 .. sd+P2K
 constexpr int P2TESTS = 2 * P2K;
 constexpr int P2ENT = RING * 5;    // (row of the other direction, component) slots of a test; scope <= RING rows are used
 struct P2Job {
@@ -123,11 +124,6 @@ struct P2Job {
   int32_t sub, best0;                  // as BpJob::sub, BpJob::best0
   int32_t nblk;                        // 64-diagonal blocks of a row: block of diagonal k = (k + koff2) >> 6
   int64_t bm_off;                      // int32 element offset of the job's block maxima [dir][P2ROWS][comp][nblk]
-};
-struct TileTask {
-  int32_t job, dir;
-  int32_t core_lo, core_hi;            // in memory: (tile index, tile width); the kernels turn it into the inclusive
-                                       // diagonal range owned by the tile for the block at hand
 };
 
 struct BpResult {

@@ -32,7 +32,7 @@ namespace wfm { void p2_counters(unsigned long long* out); }
 namespace {
 
 using namespace wfm;
-static_assert(PLAN_SUB_NONE == SUB_NONE && OP_M == 0 && OP_X == 1 && OP_I == 2 && OP_D == 3, "wfa_plan.h spells these out (it includes no HIP header)");
+static_assert(OP_M == 0 && OP_X == 1 && OP_I == 2 && OP_D == 3, "wfa_plan.h spells these out (it includes no HIP header)");
 
 constexpr int BIALIGN_FALLBACK_MIN_SCORE = 250;   // WFA2-lib WF_BIALIGN_FALLBACK_MIN_SCORE
 constexpr int BIALIGN_FALLBACK_MIN_LENGTH = 100;  // WFA2-lib WF_BIALIGN_FALLBACK_MIN_LENGTH
@@ -230,54 +230,9 @@ inline int gapcost(const wfm_penalties_t& p, int L) {
   return std::min(p.o1 + p.e1 * L, p.o2 + p.e2 * L);
 }
 
-// Row ranges with a bound of the score (wfa_kernels.hip: Rng): the kernels' arithmetic, for tile counts and cell counts
-inline int h_rng_lo(int pl, int tl, int sub, int s) { return std::max(std::max(-pl, -s), (tl - pl) - sub + s); }
-inline int h_rng_hi(int pl, int tl, int sub, int s) { return std::min(std::min(tl, s), (tl - pl) + sub - s); }
-inline int64_t h_row_cells(int pl, int tl, int sub, int s) { return std::max(0, h_rng_hi(pl, tl, sub, s) - h_rng_lo(pl, tl, sub, s) + 1); }
-// sum of h_row_cells over the scores a .. b: the row's edges are piecewise linear in the score (each a min / max of three
-// lines), so between two consecutive kinks the count is an arithmetic series
-inline int64_t h_cells_sum(int pl, int tl, int sub, int a, int b) {
-  if (b < a) return 0;
-  const int64_t kinv = (int64_t)tl - pl, khi = kinv + sub, klo = kinv - sub;
-  // scores at which two of the lines of an edge cross (the kink lies between the floor and the next integer)
-  int64_t cand[16];
-  int nc = 0;
-  auto add = [&](int64_t x) { for (int64_t y : {x, x + 1}) if (y > a && y <= b) cand[nc++] = y; };
-  add(tl); add(khi / 2 - (khi < 0 && (khi & 1) ? 1 : 0)); add(khi - tl);     // hi: s vs tl, s vs khi - s, tl vs khi - s
-  add(pl); add((-klo) / 2 - (-klo < 0 && ((-klo) & 1) ? 1 : 0)); add(-klo - pl);  // lo: -s vs -pl, -s vs klo + s, -pl vs klo + s
-  std::sort(cand, cand + nc);
-  int64_t total = 0;
-  int64_t u = a;
-  auto cells = [&](int64_t s) { return (int64_t)h_rng_hi(pl, tl, sub, (int)s) - h_rng_lo(pl, tl, sub, (int)s) + 1; };
-  auto seg = [&](int64_t x, int64_t y) {  // linear on [x, y]
-    if (y < x) return;
-    const int64_t cx = cells(x), cy = cells(y);
-    if (cx <= 0 && cy <= 0) return;
-    if (cx > 0 && cy > 0) { total += (cx + cy) * (y - x + 1) / 2; return; }
-    if (y == x) { total += std::max<int64_t>(cx, 0); return; }
-    // one end at or below zero: the slope is (cy - cx) / (y - x), an integer (each edge moves by whole diagonals per score)
-    const int64_t slope = (cy - cx) / (y - x);
-    if (cx > 0) {  // falls: positive up to x + (cx - 1) / -slope
-      const int64_t last = x + (cx - 1) / (-slope);
-      total += (cx + cells(last)) * (last - x + 1) / 2;
-    } else {       // rises: positive from y - (cy - 1) / slope
-      const int64_t first = y - (cy - 1) / slope;
-      total += (cells(first) + cy) * (y - first + 1) / 2;
-    }
-  };
-  for (int q = 0; q < nc; ++q) {
-    if (cand[q] <= u) continue;
-    seg(u, cand[q] - 1);
-    u = cand[q];
-  }
-  seg(u, b);
-  return total;
-}
-// (the kernels' rng_block: the score bound as it stood RNG_BACK = 25 scores before the block, see wfa_kernels.hip)
-inline void h_rng_block(int pl, int tl, int sub, int s_from, int s_to, int* L, int* R) {
-  *L = std::max(std::max(-pl, -s_to), (tl - pl) - sub + s_from - 25);
-  *R = std::min(std::min(tl, s_to), (tl - pl) + sub - s_from + 25);
-}
+// a switch of the environment as a number (unset: dflt); WFM_DEBUG's level (0: unset).  Read once per call, into Knobs / TileCfg / BaseCfg
+inline int env_num(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+inline int env_debug() { return getenv("WFM_DEBUG") ? std::max(1, env_num("WFM_DEBUG", 0)) : 0; }
 
 int validate_pen(const wfm_penalties_t* pen, int* scope) {
   if (!pen) return WFM_E_ARG;
@@ -297,251 +252,282 @@ struct LevelTimer {
   double bp_ms = 0, base_ms = 0, tile_ms = 0;
 };
 
-// widest row a base job can reach (0 for the trivial all-gap jobs)
-// The diagonals a base job's rows have to hold under its score budget: within `smax` of where an alignment may begin (diagonal 0 of an
-// end-to-end job, [-pbf, tbf] of an ends-free one) -- and, when the alignment has to END in the far corner (no free ends there: leaves, and the
-// head patches, whose free ends are at the beginning), within `smax` of the corner's diagonal tl - pl as well: every change of diagonal costs at least
-// e2 = 1, so a cell further away lies on no alignment of score <= smax, no cell on such an alignment takes its value from one (the argument of the
-// score bounds, section 5 of DESIGN.md), and a job that needs more than its budget is run again anyway.  A head patch begins with ALL its diagonals
-// (its begin-free lengths are the eroded lengths: rows of 2 - 8 k diagonals for a budget of 256); with the corner's band its rows are 513 wide.
-inline void base_columns(const Node& nd, const ProbMeta& pm, int64_t* kmin_out, int64_t* kmax_out) {
-  int64_t kmin = nd.endsfree ? std::max<int64_t>(-nd.pl, -(int64_t)pm.pbf - nd.smax) : std::max<int64_t>(-nd.pl, -nd.smax);
-  int64_t kmax = nd.endsfree ? std::min<int64_t>(nd.tl, (int64_t)pm.tbf + nd.smax) : std::min<int64_t>(nd.tl, nd.smax);
+// the widest row of a base job (0 for the trivial all-gap jobs) and its columns: base_columns of wfa_plan.h on the job's problem
+inline void job_columns(const Node& nd, const ProbMeta& pm, int64_t* kmin_out, int64_t* kmax_out) {
+  // (a once-per-process switch: it stays static)
   static const bool corner_band = !(getenv("WFM_BASE_CORNER_BAND") && atoi(getenv("WFM_BASE_CORNER_BAND")) == 0);
-  const bool end_fixed = !nd.endsfree || (pm.pef == 0 && pm.tef == 0);
-  if (corner_band && end_fixed) {
-    const int64_t k_end = (int64_t)nd.tl - nd.pl;
-    const int64_t bmin = std::max(kmin, k_end - nd.smax), bmax = std::min(kmax, k_end + nd.smax);
-    // the first row must keep a cell inside (a budget that cannot reach the corner at all leaves the columns as they were: the job overflows as before)
-    const int64_t lo0 = nd.endsfree ? std::max<int64_t>(-(int64_t)pm.pbf, bmin) : 0, hi0 = nd.endsfree ? std::min<int64_t>((int64_t)pm.tbf, bmax) : 0;
-    if (bmin <= bmax && lo0 <= hi0 && lo0 >= bmin && hi0 <= bmax) { kmin = bmin; kmax = bmax; }
-  }
-  *kmin_out = kmin; *kmax_out = kmax;
+  base_columns(nd, pm.pbf, pm.pef, pm.tbf, pm.tef, corner_band, kmin_out, kmax_out);
 }
 inline int64_t base_row_width(const Node& nd, const ProbMeta& pm) {
   if (nd.tl == 0 || nd.pl == 0) return 0;
   int64_t kmin, kmax;
-  base_columns(nd, pm, &kmin, &kmax);
+  job_columns(nd, pm, &kmin, &kmax);
   return kmax - kmin + 1;
 }
 
-// Runs all base jobs of `nodes` (chunked to the memory budget, wide jobs apart from narrow ones); appends
+// ---- base jobs: run_base_jobs (at the end) is the loop over chunks of one kind, the stages before it do the work ----
+
+// The switches of the base jobs, read from the environment once per call (the tests run both forms in one process)
+struct BaseCfg {
+  bool base_v2 = true, base_tiles = true, force_tiles = false;  // BaseRules' of the same names
+  int debug = 0;                                                  // WFM_DEBUG (0: unset)
+};
+BaseCfg base_cfg(const wfm_penalties_t& pen) {
+  BaseCfg c;
+  const bool dflt_pen = pen.x == 5 && pen.o1 == 8 && pen.e1 == 2 && pen.o2 == 24 && pen.e2 == 1;
+  c.base_v2 = dflt_pen && env_num("WFM_BASE_V2", 1) != 0 && env_num("WFM_TILE_V2", 1) != 0;
+  c.base_tiles = env_num("WFM_BASE_TILES", 1) != 0;
+  c.force_tiles = env_num("WFM_BASE_TILES", 1) == 2;
+  c.debug = env_debug();
+  return c;
+}
+
+// One call of run_base_jobs and the chunk at hand: jobs of one kind (base_kind) whose arenas share the budget
+struct BaseChunk {
+  wfm_handle* h; wfm_seqset* S; const wfm_penalties_t& pen; const BaseCfg& cfg;  // run_base_jobs' arguments
+  std::vector<Node>& nodes; std::vector<Node>& retry; std::vector<int32_t>& prob_status; std::vector<uint64_t>& prob_cells;
+  LevelTimer& tm; uint32_t* pflags;
+  int RR;
+  BaseRules rules;
+  std::vector<BaseJob> jobs;  // BaseJob::pad_: the job's node
+  std::vector<BaseResult> res;
+  size_t n32 = 0, n8 = 0;     // elements of base32 / bytes of base8 the chunk's jobs take
+  size_t end = 0;             // the first node behind the chunk
+  int kind = 3;
+  float ms = 0;
+};
+
+inline bool is_acgt(const wfm_seqset* S, int32_t prob) { return (size_t)prob < S->acgt.size() && S->acgt[(size_t)prob]; }
+inline int base_kind_of(const BaseChunk& c, const Node& a) {
+  return base_kind(base_row_width(a, c.S->meta[a.prob]), a.pl, a.tl, a.tries, is_acgt(c.S, a.prob), c.rules);
+}
+
+// The chunk that begins at node i0: jobs of one kind, as many as the budget holds; their geometry and their places in the arenas
+void fill_base_chunk(BaseChunk& c, size_t i0) {
+  wfm_handle* h = c.h;
+  c.jobs.clear();
+  c.n32 = 0; c.n8 = 0; c.kind = 3;
+  size_t i = i0;
+  for (; i < c.nodes.size(); ++i) {
+    const Node& nd = c.nodes[i];
+    const ProbMeta& pm = c.S->meta[nd.prob];
+    {  // a chunk holds jobs of one kind
+      const int kind = base_kind_of(c, nd);
+      if (c.jobs.empty()) c.kind = kind;
+      else if (kind != c.kind) break;
+    }
+    BaseJob j{};
+    j.p_off = pm.p_fwd + nd.pb;
+    j.t_off = pm.t_fwd + nd.tb;
+    j.pl = nd.pl; j.tl = nd.tl;
+    j.comp_begin = nd.cb; j.comp_end = nd.ce;
+    j.endsfree = nd.endsfree;
+    j.pbf = pm.pbf; j.pef = pm.pef; j.tbf = pm.tbf; j.tef = pm.tef;
+    j.rle_end = pm.rle_off + nd.pb + nd.tb + nd.pl + nd.tl;
+    j.pad_ = (int32_t)i;
+    if (nd.tl == 0 || nd.pl == 0) {
+      j.type = nd.tl == 0 ? 1 : 2;
+      if (nd.tl == 0 && nd.pl == 0) { j.type = 1; }
+      c.jobs.push_back(j);
+      continue;
+    }
+    j.type = 0;
+    j.smax = nd.smax;
+    int64_t kmin64, kmax64;
+    job_columns(nd, pm, &kmin64, &kmax64);
+    const int kmin = (int)kmin64, kmax = (int)kmax64;
+    j.kmin = kmin;
+    j.width = kmax - kmin + 1;
+    const size_t rows = (size_t)nd.smax + 1;
+    const size_t need32 = rows * (size_t)j.width + (size_t)5 * c.RR * (size_t)j.width;
+    const size_t need8 = rows * (size_t)j.width;
+    // (a chunk of base jobs stops at 4 GB of arenas even where the budget allows more, like a chunk of rings: with the leaves of all levels going out
+    // together a batch of divergent records asked for 18 GB blocks -- 0.6 s each as a first allocation, gpurun_out/r5u_c1.err -- and thousands of
+    // leaves fill the device long before that)
+    static const size_t base_chunk_bytes = (size_t)(getenv("WFM_BASE_CHUNK_GB") ? std::max(1, atoi(getenv("WFM_BASE_CHUNK_GB"))) : 4) << 30;
+    if (!c.jobs.empty() && (c.n32 + need32) * 4 + (c.n8 + need8) > std::min(h->mem_budget, base_chunk_bytes)) break;
+    if (need32 * 4 + need8 > h->mem_budget) {  // a single job beyond the budget
+      c.prob_status[nd.prob] = WFM_ST_OOM;
+      continue;
+    }
+    j.pre_off = (int64_t)c.n32;
+    j.ring_off = (int64_t)(c.n32 + rows * (size_t)j.width);
+    j.bt_off = (int64_t)c.n8;
+    c.n32 += need32; c.n8 += need8;
+    c.jobs.push_back(j);
+  }
+  c.end = i;
+}
+
+// Kind 5, the register kernel's step on tiles: blocks of T scores, every block one launch over the tiles of all jobs and a one-thread-per-job
+// kernel behind it; the host looks at the number of jobs still running every few blocks (a launch whose jobs are all over costs microseconds)
+int launch_base_tiles(BaseChunk& c) {
+  wfm_handle* h = c.h;
+  const std::vector<BaseJob>& jobs = c.jobs;
+  // (a once-per-process switch: it stays static)
+  static const int T = getenv("WFM_BASE_TILE_T") ? std::max(5, std::min(400, atoi(getenv("WFM_BASE_TILE_T")) / 5 * 5)) : 125;
+  std::vector<int32_t> widths(jobs.size()), smaxs(jobs.size());
+  for (size_t q = 0; q < jobs.size(); ++q) { widths[q] = jobs[q].width; smaxs[q] = jobs[q].smax; }
+  const BaseTilePlan plan = plan_base_tiles(widths.data(), smaxs.data(), jobs.size(), T, B2T_THREADS);
+  std::vector<Base2TJob> tj(jobs.size());
+  std::vector<Base2TTask> tasks;
+  for (size_t q = 0; q < jobs.size(); ++q) {
+    Base2TJob& t = tj[q];
+    t.b = jobs[q];
+    t.snap_in = jobs[q].ring_off; t.snap_out = jobs[q].ring_off + (int64_t)B2T_ROWS * jobs[q].width;
+    t.core = plan.core; t.ntiles = plan.ntiles[q]; t.task0 = (int32_t)tasks.size();
+    t.s0 = 0; t.done = 0; t.end_s = 0; t.end_k = 0; t.end_off = 0;
+    for (int ti = 0; ti < t.ntiles; ++ti) tasks.push_back(Base2TTask{(int32_t)q, ti});
+  }
+  const int nblocks = plan.nblocks;
+  if (h->b2tjobs.ensure(tj.size()) || h->b2ttasks.ensure(tasks.size()) || h->b2tkeys.ensure(tasks.size()) || h->b2toffs.ensure(tasks.size()) || h->b2tactive.ensure((size_t)nblocks)) {
+    h->err = "out of device memory (base tiles)";
+    return WFM_E_NOMEM;
+  }
+  HIPCHK(h, hipMemcpyAsync(h->b2tjobs.p, tj.data(), tj.size() * sizeof(Base2TJob), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->b2ttasks.p, tasks.data(), tasks.size() * sizeof(Base2TTask), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemsetAsync(h->b2tactive.p, 0, (size_t)nblocks * sizeof(int32_t), h->stream));
+  constexpr int LOOK = 6;
+  for (int b = 0; b < nblocks; ) {
+    const int upto = std::min(nblocks, b + LOOK);
+    for (; b < upto; ++b) {
+      launch_base2t_block(c.S->d_pk, h->base32.p, h->base8.p, h->b2tjobs.p, h->b2ttasks.p, h->b2tkeys.p, h->b2toffs.p, (int)tasks.size(), T, h->stream);
+      launch_base2t_advance(h->b2tjobs.p, h->b2tkeys.p, h->b2toffs.p, (int)tj.size(), T, h->b2tactive.p + b, h->stream);
+    }
+    int32_t still = 0;
+    HIPCHK(h, hipMemcpyAsync(&still, h->b2tactive.p + (b - 1), sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (!still) break;
+  }
+  launch_base2t_finish(h->base32.p, h->base8.p, h->rle.p, h->b2tjobs.p, h->bsres.p, (int)tj.size(), h->stream);
+  return WFM_OK;
+}
+
+// The chunk on the device: its jobs up, the launch its kind asks for, the results back; the time it took
+int run_base_chunk(BaseChunk& c) {
+  wfm_handle* h = c.h;
+  const std::vector<BaseJob>& jobs = c.jobs;
+  if (h->base32.ensure(c.n32 + 16) || h->base8.ensure(c.n8 + 16) || h->bsjobs.ensure(jobs.size()) || h->bsres.ensure(jobs.size())) {
+    h->err = "out of device memory (base arena)";
+    return WFM_E_NOMEM;
+  }
+  HIPCHK(h, hipMemcpyAsync(h->bsjobs.p, jobs.data(), jobs.size() * sizeof(BaseJob), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipEventRecord(h->ev2, h->stream));
+  // (jobs arrive sorted: the wide ones -- long patches, retries with a larger budget -- in chunks of their own)
+  if (c.kind == 5) {
+    const int rc = launch_base_tiles(c);
+    if (rc != WFM_OK) return rc;
+  } else if (c.kind <= 2) {
+    int64_t wmax = 1;
+    for (const BaseJob& bj : jobs) if (bj.type == 0) wmax = std::max<int64_t>(wmax, bj.width);
+    const int threads = (int)std::min<int64_t>(1024, ((wmax + 1) / 2 + 63) / 64 * 64);
+    launch_base2(c.S->d_pk, h->base32.p, h->base8.p, h->rle.p, h->bsjobs.p, h->bsres.p, (int)jobs.size(), threads, h->stream);
+  } else {
+    const DevPen dp{c.pen.x, c.pen.o1, c.pen.e1, c.pen.o2, c.pen.e2};
+    launch_base(c.S->d_seq, h->base32.p, h->base8.p, h->rle.p, h->bsjobs.p, h->bsres.p, (int)jobs.size(), dp, c.kind == 4, c.RR, h->stream);
+  }
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipEventRecord(h->ev3, h->stream));
+  c.res.resize(jobs.size());
+  HIPCHK(h, hipMemcpyAsync(c.res.data(), h->bsres.p, jobs.size() * sizeof(BaseResult), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, hipEventElapsedTime(&c.ms, h->ev2, h->ev3));
+  c.tm.base_ms += c.ms;
+  if (h->call_base) {
+    float t0 = 0;
+    HIPCHK(h, hipEventElapsedTime(&t0, h->call_base, h->ev2));
+    h->base_iv.emplace_back(t0, t0 + c.ms);
+  }
+  h->stats.base_launches++;
+  h->stats.base_jobs += (uint32_t)jobs.size();
+  return WFM_OK;
+}
+
+// WFM_DEBUG=2: the chunk's launch in a line or two
+void print_base_chunk(const BaseChunk& c) {
+  const std::vector<BaseJob>& jobs = c.jobs;
+  const std::vector<BaseResult>& res = c.res;
+  const int chunk_kind = c.kind;
+  int64_t wsum = 0, wmax = 0, smx = 0; int over = 0, ef = 0;
+  for (size_t q = 0; q < jobs.size(); ++q) { wsum += jobs[q].width; wmax = std::max<int64_t>(wmax, jobs[q].width); smx = std::max<int64_t>(smx, jobs[q].smax); over += res[q].status == WFM_DEV_OVERFLOW; ef += jobs[q].endsfree; }
+  fprintf(stderr, "[wfm] base launch: %zu jobs (%d ends-free), %d threads, rows %lld wide on average (max %lld), score budget up to %lld, %.3f ms, %d overflowed\n", jobs.size(), ef,
+          chunk_kind == 5 ? B2T_THREADS : (chunk_kind == 4 ? 1024 : 256), (long long)(wsum / (int64_t)jobs.size()), (long long)wmax, (long long)smx, c.ms, over);
+  if (chunk_kind <= 2) {
+    double fw = 0, bk = 0; int fwm = 0, bkm = 0, scm = 0; double scs = 0;
+    for (size_t q = 0; q < jobs.size(); ++q) { const int f = (res[q].pad_ >> 16) & 0xffff, b = res[q].pad_ & 0xffff; fw += f; bk += b; fwm = std::max(fwm, f); bkm = std::max(bkm, b); scs += res[q].score; scm = std::max(scm, res[q].score); }
+    fprintf(stderr, "[wfm]   register kernel (kind %d): forward %.0f us on average (max %d), walk back %.0f us (max %d), score %.0f on average (max %d)\n", chunk_kind, fw / jobs.size(), fwm, bk / jobs.size(), bkm, scs / jobs.size(), scm);
+  }
+  else {
+    double scs = 0; int scm = 0, scn = INT_MAX;
+    for (size_t q = 0; q < jobs.size(); ++q) { scs += res[q].score; scm = std::max(scm, res[q].score); scn = std::min(scn, res[q].score); }
+    fprintf(stderr, "[wfm]   %s (kind %d): score %.0f on average (min %d, max %d)\n", chunk_kind == 5 ? "register kernel on tiles" : "ring kernel", chunk_kind, scs / jobs.size(), scn, scm);
+  }
+}
+
+// The chunk's results: cells and flags, and the jobs that overflowed their score budget once more with a larger one (into retry)
+void settle_base_chunk(BaseChunk& c) {
+  wfm_handle* h = c.h;
+  const wfm_penalties_t& pen = c.pen;
+  for (size_t q = 0; q < c.jobs.size(); ++q) {
+    const Node& nd = c.nodes[(size_t)c.jobs[q].pad_];
+    const BaseResult& r = c.res[q];
+    c.prob_cells[nd.prob] += r.cells;
+    h->stats.cells_base += r.cells;
+    if (c.pflags && (c.kind == 3 || c.kind == 4) && c.jobs[q].type == 0) c.pflags[nd.prob] |= WFM_PF_RING_KERNEL;
+    if (c.pflags && c.kind == 5) c.pflags[nd.prob] |= WFM_PF_BASE_TILES;
+    if (r.status == WFM_DEV_OVERFLOW) {
+      if (c.pflags) c.pflags[nd.prob] |= nd.tries == 0 ? WFM_PF_BASE_RETRY : WFM_PF_BASE_RETRY2;
+      Node again = nd;
+      again.tries = nd.tries + 1;
+      // No alignment costs more than the all-gap one.  A job whose begin or end component is a gap state is held to a
+      // PIECE there (a BiWFA child that ends inside a D2 gap pays o2 + e2 per base for it, however short it is --
+      // its parent counted that gap's opening on the other side of the breakpoint, so the child's own forward score
+      // exceeds the score_rem it was handed): the bound takes the dearer piece for both gaps then.
+      const bool constrained = nd.cb != C_M || nd.ce != C_M;
+      const int64_t bound = constrained
+          ? (int64_t)2 * std::max(pen.o1, pen.o2) + (int64_t)std::max(pen.e1, pen.e2) * ((int64_t)nd.pl + nd.tl) + 8
+          : (int64_t)gapcost(pen, nd.pl) + gapcost(pen, nd.tl) + 8;
+      if (nd.smax >= bound) {
+        if (c.cfg.debug) fprintf(stderr, "[wfm] problem %d: base job pl %d tl %d cb %d ce %d overflowed its score bound %d\n", nd.prob, nd.pl, nd.tl, nd.cb, nd.ce, nd.smax);
+        c.prob_status[nd.prob] = WFM_ST_UNREACHABLE; continue;
+      }
+      // (x 8; it was x 2 until round 3 and x 4 for a while: every retry is a launch that a few jobs hold up, a budget that is too large costs
+      // memory only -- 20 MB for a 2 k-wide patch at 2 k scores -- and a patch that passed 256 is as likely to need 1500 as 500)
+      again.smax = (int32_t)std::min<int64_t>((int64_t)nd.smax * 8 + 32, bound);
+      // ... but the second attempt stops at 1020: with the band around the end corner's diagonal the rows of a job with that budget are at most
+      // 2041 diagonals wide and fit the register kernel (wfa_base2_kernel: 2048), where a budget of 2080 put two dozen patches of an LPA batch
+      // on the ring kernel with rows of 2.6 - 3.4 k diagonals (9.7 ms of the batch's 83); the few that need more take a third attempt
+      // (round 6: a job the tiles of the register kernel take -- wfa_base2t_kernel, rows of any width -- has no use for the stop: its second attempt
+      // runs with the eightfold budget at once, 2.0 ms of an LPA batch's patch chain less)
+      const bool to_tiles = c.rules.base_v2 && c.rules.base_tiles && is_acgt(c.S, nd.prob);
+      if (nd.smax < 1020 && again.smax > 1020 && !to_tiles) again.smax = 1020;
+      c.retry.push_back(again);
+    } else if (r.status != 0) {
+      if (c.cfg.debug) fprintf(stderr, "[wfm] problem %d: base job pl %d tl %d status %d\n", nd.prob, nd.pl, nd.tl, r.status);
+      c.prob_status[nd.prob] = WFM_ST_UNREACHABLE;
+    }
+  }
+}
+
+// Runs all base jobs of `nodes` (chunked to the memory budget, every kind of job in chunks of its own); appends
 // overflowed nodes (with a larger budget) to `retry`.
-int run_base_jobs(wfm_handle* h, wfm_seqset* S, const wfm_penalties_t& pen, std::vector<Node>& nodes,
+int run_base_jobs(wfm_handle* h, wfm_seqset* S, const wfm_penalties_t& pen, const BaseCfg& cfg, std::vector<Node>& nodes,
                   std::vector<Node>& retry, std::vector<int32_t>& prob_status, std::vector<uint64_t>& prob_cells,
                   LevelTimer& tm, uint32_t* pflags) {
   if (nodes.empty()) return WFM_OK;
-  const int RR = ring_rows_for(std::max(pen.x, std::max(pen.o1 + pen.e1, pen.o2 + pen.e2)) + 1);
+  BaseChunk c{h, S, pen, cfg, nodes, retry, prob_status, prob_cells, tm, pflags,
+              ring_rows_for(std::max(pen.x, std::max(pen.o1 + pen.e1, pen.o2 + pen.e2)) + 1)};
   // rows beyond 2 k diagonals get 1024 threads -- and rows beyond 512 when the launch is too small to fill the device anyway
   // (the retries of the few patches that overflowed their first budget: one workgroup each, a thousand steps deep)
-  const int wide_from = nodes.size() < 128 ? 512 : 2048;
-  // Kinds of jobs, each in launches of its own: 0 / 1 / 2 = the register kernel on packed sequences (wfa_base2_kernel: default
-  // penalties, pure ACGT, rows up to 128 / 512 / 2048 diagonals, sequences that fit its windows), 3 / 4 = the ring kernel with
-  // 256 / 1024 threads (other penalties, an N, wider rows: a patch eroded to its 4096-base limit starts 8 k diagonals wide)
-  const bool dflt_pen = pen.x == 5 && pen.o1 == 8 && pen.e1 == 2 && pen.o2 == 24 && pen.e2 == 1;
-  const bool base_v2 = dflt_pen && !(getenv("WFM_BASE_V2") && atoi(getenv("WFM_BASE_V2")) == 0) && !(getenv("WFM_TILE_V2") && atoi(getenv("WFM_TILE_V2")) == 0);
-  // 5 = the register kernel's step on tiles (wfa_base2t_kernel): rows beyond 2048 diagonals of jobs the register kernel would take -- the third
-  // attempt of a patch, whose score passed 1020
-  const bool base_tiles = !(getenv("WFM_BASE_TILES") && atoi(getenv("WFM_BASE_TILES")) == 0);
-  const bool force_tiles = getenv("WFM_BASE_TILES") && atoi(getenv("WFM_BASE_TILES")) == 2;  // tests: every leaf and patch with rows beyond 128 diagonals
-  // (sequences longer than the kernel's LDS windows are fine: what lies beyond is read from the global mirror.  Jobs without
-  // any cell -- an empty pattern or text -- ride along with the first kind: they are one store each)
-  const bool few_jobs = nodes.size() < 128;
-  auto kind_of = [&](const Node& a) {
-    const int64_t w = base_row_width(a, S->meta[a.prob]);
-    if (base_v2 && (a.pl == 0 || a.tl == 0)) return 1;
-    if (base_v2 && w <= 2048 && (size_t)a.prob < S->acgt.size() && S->acgt[(size_t)a.prob])
-      // (a handful of retries: more workgroups of fewer waves per job on the tiles of the register kernel, and ONE launch with the wider ones
-      // instead of one per width class, each a few jobs and hundreds of score steps long)
-      return w <= 128 ? 0 : (base_tiles && (force_tiles || (few_jobs && (a.tries > 0 || w > 640))) ? 5 : (w <= 640 ? 1 : 2));
-    if (base_v2 && base_tiles && (size_t)a.prob < S->acgt.size() && S->acgt[(size_t)a.prob]) return 5;
-    return w > wide_from ? 4 : 3;
-  };
-  std::stable_sort(nodes.begin(), nodes.end(), [&](const Node& a, const Node& b) { return kind_of(a) < kind_of(b); });
-  const DevPen dp{pen.x, pen.o1, pen.e1, pen.o2, pen.e2};
-  size_t i0 = 0;
-  std::vector<BaseJob> jobs;
-  std::vector<BaseResult> res;
-  while (i0 < nodes.size()) {
-    jobs.clear();
-    size_t n32 = 0, n8 = 0;
-    size_t i = i0;
-    int chunk_kind = 3;
-    for (; i < nodes.size(); ++i) {
-      const Node& nd = nodes[i];
-      const ProbMeta& pm = S->meta[nd.prob];
-      {  // a chunk holds jobs of one kind
-        const int kind = kind_of(nd);
-        if (jobs.empty()) chunk_kind = kind;
-        else if (kind != chunk_kind) break;
-      }
-      BaseJob j{};
-      j.p_off = pm.p_fwd + nd.pb;
-      j.t_off = pm.t_fwd + nd.tb;
-      j.pl = nd.pl; j.tl = nd.tl;
-      j.comp_begin = nd.cb; j.comp_end = nd.ce;
-      j.endsfree = nd.endsfree;
-      j.pbf = pm.pbf; j.pef = pm.pef; j.tbf = pm.tbf; j.tef = pm.tef;
-      j.rle_end = pm.rle_off + nd.pb + nd.tb + nd.pl + nd.tl;
-      j.pad_ = (int32_t)i;
-      if (nd.tl == 0 || nd.pl == 0) {
-        j.type = nd.tl == 0 ? 1 : 2;
-        if (nd.tl == 0 && nd.pl == 0) { j.type = 1; }
-        jobs.push_back(j);
-        continue;
-      }
-      j.type = 0;
-      j.smax = nd.smax;
-      int64_t kmin64, kmax64;
-      base_columns(nd, pm, &kmin64, &kmax64);
-      const int kmin = (int)kmin64, kmax = (int)kmax64;
-      j.kmin = kmin;
-      j.width = kmax - kmin + 1;
-      const size_t rows = (size_t)nd.smax + 1;
-      const size_t need32 = rows * (size_t)j.width + (size_t)5 * RR * (size_t)j.width;
-      const size_t need8 = rows * (size_t)j.width;
-      // (a chunk of base jobs stops at 4 GB of arenas even where the budget allows more, like a chunk of rings: with the leaves of all levels going out
-      // together a batch of divergent records asked for 18 GB blocks -- 0.6 s each as a first allocation, gpurun_out/r5u_c1.err -- and thousands of
-      // leaves fill the device long before that)
-      static const size_t base_chunk_bytes = (size_t)(getenv("WFM_BASE_CHUNK_GB") ? std::max(1, atoi(getenv("WFM_BASE_CHUNK_GB"))) : 4) << 30;
-      if (!jobs.empty() && (n32 + need32) * 4 + (n8 + need8) > std::min(h->mem_budget, base_chunk_bytes)) break;
-      if (need32 * 4 + need8 > h->mem_budget) {  // a single job beyond the budget
-        prob_status[nd.prob] = WFM_ST_OOM;
-        continue;
-      }
-      j.pre_off = (int64_t)n32;
-      j.ring_off = (int64_t)(n32 + rows * (size_t)j.width);
-      j.bt_off = (int64_t)n8;
-      n32 += need32; n8 += need8;
-      jobs.push_back(j);
-    }
-    const size_t chunk_end = i;
-    if (!jobs.empty()) {
-      if (h->base32.ensure(n32 + 16) || h->base8.ensure(n8 + 16) || h->bsjobs.ensure(jobs.size()) || h->bsres.ensure(jobs.size())) {
-        h->err = "out of device memory (base arena)";
-        return WFM_E_NOMEM;
-      }
-      HIPCHK(h, hipMemcpyAsync(h->bsjobs.p, jobs.data(), jobs.size() * sizeof(BaseJob), hipMemcpyHostToDevice, h->stream));
-      HIPCHK(h, hipEventRecord(h->ev2, h->stream));
-      // (jobs arrive sorted: the wide ones -- long patches, retries with a larger budget -- in chunks of their own)
-      const bool chunk_wide = chunk_kind == 4;
-      if (chunk_kind == 5) {
-        // blocks of T scores, every block one launch over the tiles of all jobs and a one-thread-per-job kernel behind it; the host looks at the
-        // number of jobs still running every few blocks (a launch whose jobs are all over costs microseconds)
-        static const int T = getenv("WFM_BASE_TILE_T") ? std::max(5, std::min(400, atoi(getenv("WFM_BASE_TILE_T")) / 5 * 5)) : 125;
-        const int core = B2T_THREADS * 2 - 2 * T;
-        std::vector<Base2TJob> tj(jobs.size());
-        std::vector<Base2TTask> tasks;
-        int smax_all = 0;
-        for (size_t q = 0; q < jobs.size(); ++q) {
-          Base2TJob& t = tj[q];
-          t.b = jobs[q];
-          t.snap_in = jobs[q].ring_off; t.snap_out = jobs[q].ring_off + (int64_t)B2T_ROWS * jobs[q].width;
-          t.core = core; t.ntiles = (jobs[q].width + core - 1) / core; t.task0 = (int32_t)tasks.size();
-          t.s0 = 0; t.done = 0; t.end_s = 0; t.end_k = 0; t.end_off = 0;
-          for (int ti = 0; ti < t.ntiles; ++ti) tasks.push_back(Base2TTask{(int32_t)q, ti});
-          smax_all = std::max(smax_all, jobs[q].smax);
-        }
-        const int nblocks = (smax_all + T - 1) / T + 1;
-        if (h->b2tjobs.ensure(tj.size()) || h->b2ttasks.ensure(tasks.size()) || h->b2tkeys.ensure(tasks.size()) || h->b2toffs.ensure(tasks.size()) || h->b2tactive.ensure((size_t)nblocks)) {
-          h->err = "out of device memory (base tiles)";
-          return WFM_E_NOMEM;
-        }
-        HIPCHK(h, hipMemcpyAsync(h->b2tjobs.p, tj.data(), tj.size() * sizeof(Base2TJob), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->b2ttasks.p, tasks.data(), tasks.size() * sizeof(Base2TTask), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemsetAsync(h->b2tactive.p, 0, (size_t)nblocks * sizeof(int32_t), h->stream));
-        constexpr int LOOK = 6;
-        for (int b = 0; b < nblocks; ) {
-          const int upto = std::min(nblocks, b + LOOK);
-          for (; b < upto; ++b) {
-            launch_base2t_block(S->d_pk, h->base32.p, h->base8.p, h->b2tjobs.p, h->b2ttasks.p, h->b2tkeys.p, h->b2toffs.p, (int)tasks.size(), T, h->stream);
-            launch_base2t_advance(h->b2tjobs.p, h->b2tkeys.p, h->b2toffs.p, (int)tj.size(), T, h->b2tactive.p + b, h->stream);
-          }
-          int32_t still = 0;
-          HIPCHK(h, hipMemcpyAsync(&still, h->b2tactive.p + (b - 1), sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-          HIPCHK(h, hipStreamSynchronize(h->stream));
-          if (!still) break;
-        }
-        launch_base2t_finish(h->base32.p, h->base8.p, h->rle.p, h->b2tjobs.p, h->bsres.p, (int)tj.size(), h->stream);
-      } else if (chunk_kind <= 2) {
-        int64_t wmax = 1;
-        for (const BaseJob& bj : jobs) if (bj.type == 0) wmax = std::max<int64_t>(wmax, bj.width);
-        const int threads = (int)std::min<int64_t>(1024, ((wmax + 1) / 2 + 63) / 64 * 64);
-        launch_base2(S->d_pk, h->base32.p, h->base8.p, h->rle.p, h->bsjobs.p, h->bsres.p, (int)jobs.size(), threads, h->stream);
-      } else
-        launch_base(S->d_seq, h->base32.p, h->base8.p, h->rle.p, h->bsjobs.p, h->bsres.p, (int)jobs.size(), dp, chunk_wide, RR, h->stream);
-      HIPCHK(h, hipGetLastError());
-      HIPCHK(h, hipEventRecord(h->ev3, h->stream));
-      res.resize(jobs.size());
-      HIPCHK(h, hipMemcpyAsync(res.data(), h->bsres.p, jobs.size() * sizeof(BaseResult), hipMemcpyDeviceToHost, h->stream));
-      HIPCHK(h, hipStreamSynchronize(h->stream));
-      float ms = 0;
-      HIPCHK(h, hipEventElapsedTime(&ms, h->ev2, h->ev3));
-      tm.base_ms += ms;
-      if (h->call_base) {
-        float t0 = 0;
-        HIPCHK(h, hipEventElapsedTime(&t0, h->call_base, h->ev2));
-        h->base_iv.emplace_back(t0, t0 + ms);
-      }
-      h->stats.base_launches++;
-      h->stats.base_jobs += (uint32_t)jobs.size();
-      if (getenv("WFM_DEBUG") && atoi(getenv("WFM_DEBUG")) > 1) {
-        int64_t wsum = 0, wmax = 0, smx = 0; int over = 0, ef = 0;
-        for (size_t q = 0; q < jobs.size(); ++q) { wsum += jobs[q].width; wmax = std::max<int64_t>(wmax, jobs[q].width); smx = std::max<int64_t>(smx, jobs[q].smax); over += res[q].status == WFM_DEV_OVERFLOW; ef += jobs[q].endsfree; }
-        fprintf(stderr, "[wfm] base launch: %zu jobs (%d ends-free), %d threads, rows %lld wide on average (max %lld), score budget up to %lld, %.3f ms, %d overflowed\n", jobs.size(), ef,
-                chunk_kind == 5 ? B2T_THREADS : (chunk_wide ? 1024 : 256), (long long)(wsum / (int64_t)jobs.size()), (long long)wmax, (long long)smx, ms, over);
-        if (chunk_kind <= 2) {
-          double fw = 0, bk = 0; int fwm = 0, bkm = 0, scm = 0; double scs = 0;
-          for (size_t q = 0; q < jobs.size(); ++q) { const int f = (res[q].pad_ >> 16) & 0xffff, b = res[q].pad_ & 0xffff; fw += f; bk += b; fwm = std::max(fwm, f); bkm = std::max(bkm, b); scs += res[q].score; scm = std::max(scm, res[q].score); }
-          fprintf(stderr, "[wfm]   register kernel (kind %d): forward %.0f us on average (max %d), walk back %.0f us (max %d), score %.0f on average (max %d)\n", chunk_kind, fw / jobs.size(), fwm, bk / jobs.size(), bkm, scs / jobs.size(), scm);
-        }
-        else {
-          double scs = 0; int scm = 0, scn = INT_MAX;
-          for (size_t q = 0; q < jobs.size(); ++q) { scs += res[q].score; scm = std::max(scm, res[q].score); scn = std::min(scn, res[q].score); }
-          fprintf(stderr, "[wfm]   %s (kind %d): score %.0f on average (min %d, max %d)\n", chunk_kind == 5 ? "register kernel on tiles" : "ring kernel", chunk_kind, scs / jobs.size(), scn, scm);
-        }
-      }
-      for (size_t q = 0; q < jobs.size(); ++q) {
-        const Node& nd = nodes[(size_t)jobs[q].pad_];
-        const BaseResult& r = res[q];
-        prob_cells[nd.prob] += r.cells;
-        h->stats.cells_base += r.cells;
-        if (pflags && (chunk_kind == 3 || chunk_kind == 4) && jobs[q].type == 0) pflags[nd.prob] |= WFM_PF_RING_KERNEL;
-        if (pflags && chunk_kind == 5) pflags[nd.prob] |= WFM_PF_BASE_TILES;
-        if (r.status == WFM_DEV_OVERFLOW) {
-          if (pflags) pflags[nd.prob] |= nd.tries == 0 ? WFM_PF_BASE_RETRY : WFM_PF_BASE_RETRY2;
-          Node again = nd;
-          again.tries = nd.tries + 1;
-          // No alignment costs more than the all-gap one.  A job whose begin or end component is a gap state is held to a
-          // PIECE there (a BiWFA child that ends inside a D2 gap pays o2 + e2 per base for it, however short it is --
-          // its parent counted that gap's opening on the other side of the breakpoint, so the child's own forward score
-          // exceeds the score_rem it was handed): the bound takes the dearer piece for both gaps then.
-          const bool constrained = nd.cb != C_M || nd.ce != C_M;
-          const int64_t bound = constrained
-              ? (int64_t)2 * std::max(pen.o1, pen.o2) + (int64_t)std::max(pen.e1, pen.e2) * ((int64_t)nd.pl + nd.tl) + 8
-              : (int64_t)gapcost(pen, nd.pl) + gapcost(pen, nd.tl) + 8;
-          if (nd.smax >= bound) {
-            if (getenv("WFM_DEBUG")) fprintf(stderr, "[wfm] problem %d: base job pl %d tl %d cb %d ce %d overflowed its score bound %d\n", nd.prob, nd.pl, nd.tl, nd.cb, nd.ce, nd.smax);
-            prob_status[nd.prob] = WFM_ST_UNREACHABLE; continue;
-          }
-          // (x 8; it was x 2 until round 3 and x 4 for a while: every retry is a launch that a few jobs hold up, a budget that is too large costs
-          // memory only -- 20 MB for a 2 k-wide patch at 2 k scores -- and a patch that passed 256 is as likely to need 1500 as 500)
-          again.smax = (int32_t)std::min<int64_t>((int64_t)nd.smax * 8 + 32, bound);
-          // ... but the second attempt stops at 1020: with the band around the end corner's diagonal the rows of a job with that budget are at most
-          // 2041 diagonals wide and fit the register kernel (wfa_base2_kernel: 2048), where a budget of 2080 put two dozen patches of an LPA batch
-          // on the ring kernel with rows of 2.6 - 3.4 k diagonals (9.7 ms of the batch's 83); the few that need more take a third attempt
-          // (round 6: a job the tiles of the register kernel take -- wfa_base2t_kernel, rows of any width -- has no use for the stop: its second attempt
-          // runs with the eightfold budget at once, 2.0 ms of an LPA batch's patch chain less)
-          const bool to_tiles = base_v2 && base_tiles && (size_t)nd.prob < S->acgt.size() && S->acgt[(size_t)nd.prob];
-          if (nd.smax < 1020 && again.smax > 1020 && !to_tiles) again.smax = 1020;
-          retry.push_back(again);
-        } else if (r.status != 0) {
-          if (getenv("WFM_DEBUG")) fprintf(stderr, "[wfm] problem %d: base job pl %d tl %d status %d\n", nd.prob, nd.pl, nd.tl, r.status);
-          prob_status[nd.prob] = WFM_ST_UNREACHABLE;
-        }
-      }
-    }
-    i0 = chunk_end;
+  c.rules = BaseRules{cfg.base_v2, cfg.base_tiles, cfg.force_tiles, nodes.size() < 128, nodes.size() < 128 ? 512 : 2048};
+  std::stable_sort(nodes.begin(), nodes.end(), [&](const Node& a, const Node& b) { return base_kind_of(c, a) < base_kind_of(c, b); });
+  for (size_t i0 = 0; i0 < nodes.size(); i0 = c.end) {
+    fill_base_chunk(c, i0);
+    if (c.jobs.empty()) continue;
+    const int rc = run_base_chunk(c);
+    if (rc != WFM_OK) return rc;
+    if (cfg.debug > 1) print_base_chunk(c);
+    settle_base_chunk(c);
   }
   return WFM_OK;
 }
@@ -559,6 +545,10 @@ struct TileCfg {
   bool enabled = true;
   bool reg = false;  // register-resident tile kernel (default penalty lags only)
   int C = 2;
+  bool fine = true;  // WFM_TILE_FINE: the blocks of a single-tile chunk get workgroups as small as their own widest range allows
+  int debug = 0;     // WFM_DEBUG (0: unset)
+  bool p2_dump_on = false;  // WFM_P2_DUMP (diagnosis): the row maxima of job p2_dump of every chunk of phase 2
+  int p2_dump = 0;
 };
 
 TileCfg tile_cfg(const wfm_penalties_t& pen, int scope) {
@@ -571,6 +561,9 @@ TileCfg tile_cfg(const wfm_penalties_t& pen, int scope) {
   if (const char* e = getenv("WFM_TILE_THREADS")) c.threads = atoi(e);
   if (const char* e = getenv("WFM_TILE_MIN_LEN")) c.min_len = atoi(e);
   if (const char* e = getenv("WFM_TILE_MIN_SCORE")) c.min_score = atoi(e);
+  c.fine = env_num("WFM_TILE_FINE", 1) != 0;
+  c.debug = env_debug();
+  if (const char* e = getenv("WFM_P2_DUMP")) { c.p2_dump_on = true; c.p2_dump = atoi(e); }
   const int RR = ring_rows_for(scope);
   c.T = std::max(c.T, RR);  // the output snapshot needs `scope` rows of the block itself
   if (c.T_refine > 0) c.T_refine = std::max(c.T_refine, RR);
@@ -593,6 +586,234 @@ TileCfg tile_cfg(const wfm_penalties_t& pen, int scope) {
   return c;
 }
 
+// ---- the tile phase: run_tiled_phase (at the end) is the loop over chunks of blocks, the stages before it do the work ----
+
+// What the tile kernels need of a breakpoint job.  The caller sets what differs between the tile phase and the phase-2 rows:
+// ring_out, mode, tf / tr, last_fwd, fine_s, ring_prev, p2_off / w2 / koff2
+inline TileJob tile_job_from(const BpJob& j) {
+  TileJob t{};
+  t.p_fwd = j.p_fwd; t.t_fwd = j.t_fwd; t.p_rev = j.p_rev; t.t_rev = j.t_rev;
+  t.ring_in = j.ring_off;
+  t.pl = j.pl; t.tl = j.tl; t.comp_begin = j.comp_begin; t.comp_end = j.comp_end;
+  t.width = j.width; t.koff = j.koff; t.active = 1; t.packed = j.packed; t.sub = j.sub;
+  return t;
+}
+
+// One pass of the tile phase over the jobs listed in `tiled`, and the chunk of blocks at hand
+struct TilePhase {
+  wfm_handle* h; wfm_seqset* S; const DevPen& dp; int scope; const TileCfg& cfg; int T; bool refine;  // run_tiled_phase's arguments
+  std::vector<BpJob>& jobs; const std::vector<int>& tiled; std::vector<int64_t>& ring2; double& tile_ms; uint64_t& tile_cells;
+  size_t n;
+  std::vector<TileJob> tj, got;          // the jobs as the host last saw them; as the chunk left them
+  std::vector<int> fmax, rmax, s_begin;  // running maxima of the two directions; score the jobs start this pass at
+  std::vector<char> active;
+  size_t n_active = 0;
+  bool any_cut = false;  // the kernel form with the score bounds' bookkeeping is only launched when a job carries one
+  int chunk = 1;         // blocks launched back to back between two looks of the host
+  TilePlanRules rules;
+  std::vector<TilePlanJob> pjobs;
+  TileChunkPlan plan;
+  uint32_t blocks = 0;
+  double lane_cells = 0;  // threads x diagonals per thread x scores over all tiles launched (diagnostics)
+};
+
+// The jobs' TileJobs, and where they stand: at score 0 after the init kernel, or (refine) where a pass before left them
+int init_tile_jobs(TilePhase& p, const std::vector<int32_t>* fine_from, const std::vector<int64_t>* ring3) {
+  wfm_handle* h = p.h;
+  const TileCfg& cfg = p.cfg;
+  const size_t n = p.n;
+  const int T = p.T;
+  p.tj.resize(n); p.fmax.assign(n, 0); p.rmax.assign(n, 0); p.active.assign(n, 1); p.s_begin.assign(n, 0);
+  for (size_t i = 0; i < n; ++i) {
+    const BpJob& j = p.jobs[(size_t)p.tiled[i]];
+    TileJob& t = p.tj[i];
+    t = tile_job_from(j);
+    t.ring_out = p.ring2[i];
+    t.fine_s = (fine_from && i < fine_from->size()) ? (*fine_from)[i] : INT_MAX;  // (TileJob::fine_s; a job whose score nobody knows finds its meeting block by running it again)
+    // a third ring (TileJob::ring_prev): packed jobs of the exact tile phase only -- the byte kernel and the step kernel's fall-backs read gap rows
+    // 26 deep from any snapshot
+    t.ring_prev = (ring3 && i < ring3->size() && (*ring3)[i] >= 0 && (j.packed & 1) && cfg.reg && cfg.exact && !p.refine) ? (*ring3)[i] : -1;
+    h->tile_ctr[WFM_TC_RING3] += t.ring_prev >= 0;
+  }
+  if (!p.refine || T == cfg.T) h->tile_ctr[WFM_TC_JOBS] += n;  // (a WFM_TILE_T_REFINE pass goes on with jobs already counted; a resumed job enters)
+  for (size_t i = 0; i < n; ++i) p.any_cut |= p.tj[i].sub != SUB_NONE;
+  if (h->tilejobs.ensure(n) || h->tilemak.ensure(n * 2 * (size_t)std::max(T, 2))) { h->err = "out of device memory (tiles)"; return WFM_E_NOMEM; }
+  if (!p.refine) {
+    HIPCHK(h, hipMemcpyAsync(h->tilejobs.p, p.tj.data(), n * sizeof(TileJob), hipMemcpyHostToDevice, h->stream));
+    launch_tile_init(p.S->d_seq, h->ring.p, h->tilejobs.p, h->tilemak.p, (int)n, ring_rows_for(p.scope), h->stream);
+    HIPCHK(h, hipGetLastError());
+    std::vector<int32_t> mak(n * 4);
+    HIPCHK(h, hipMemcpyAsync(mak.data(), h->tilemak.p, n * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (size_t i = 0; i < n; ++i) {
+      p.fmax[i] = mak[(i * 2 + 0) * 2]; p.rmax[i] = mak[(i * 2 + 1) * 2];
+      const bool ended = mak[(i * 2 + 0) * 2 + 1] || mak[(i * 2 + 1) * 2 + 1];
+      const int A = p.tj[i].pl + p.tj[i].tl - 1;
+      if (ended || p.fmax[i] + p.rmax[i] >= A) p.active[i] = 0;  // wfa_bp_kernel handles it from score 0
+      p.n_active += p.active[i];
+      p.tj[i].active = p.active[i]; p.tj[i].fmax = p.fmax[i]; p.tj[i].rmax = p.rmax[i]; p.tj[i].nblocks = 0;
+    }
+  } else {
+    for (size_t i = 0; i < n; ++i) {
+      const BpJob& j = p.jobs[(size_t)p.tiled[i]];
+      const int A = p.tj[i].pl + p.tj[i].tl - 1;
+      p.fmax[i] = j.fmax0; p.rmax[i] = j.rmax0;
+      p.s_begin[i] = j.resume_s;
+      p.active[i] = (char)(p.fmax[i] + p.rmax[i] < A);  // jobs that were over before their first block stay where they are
+      p.n_active += p.active[i];
+      p.tj[i].s0 = j.resume_s; p.tj[i].active = p.active[i]; p.tj[i].fmax = p.fmax[i]; p.tj[i].rmax = p.rmax[i]; p.tj[i].nblocks = 0;
+    }
+  }
+  return WFM_OK;
+}
+
+// The jobs that may not start this chunk (tile_job_leaves): they leave the tile phase here and the host runs them again
+int drop_leavers(TilePhase& p) {
+  wfm_handle* h = p.h;
+  bool left = false;
+  for (size_t i = 0; i < p.n; ++i) {
+    const TileJob& t = p.tj[i];
+    if (!p.active[i] || !tile_job_leaves(t.pl, t.tl, t.sub, t.s0, p.jobs[(size_t)p.tiled[i]].band, p.chunk, p.T)) continue;
+    p.active[i] = 0; p.tj[i].active = 0; p.tj[i].mode = 3; left = true; --p.n_active;
+  }
+  if (left) HIPCHK(h, hipMemcpyAsync(h->tilejobs.p, p.tj.data(), p.n * sizeof(TileJob), hipMemcpyHostToDevice, h->stream));
+  return WFM_OK;
+}
+
+// The chunk's task list (plan_tile_chunk), built for the widest range the chunk can reach, onto the device
+int plan_tile_tasks(TilePhase& p) {
+  wfm_handle* h = p.h;
+  for (size_t i = 0; i < p.n; ++i) {
+    const TileJob& t = p.tj[i];
+    p.pjobs[i] = TilePlanJob{t.pl, t.tl, t.sub, t.s0, t.mode, t.fine_s, t.packed, p.active[i]};
+  }
+  plan_tile_chunk(p.pjobs.data(), p.n, p.rules, p.plan);
+  const std::vector<TileTask>& tasks = p.plan.tasks;
+  if (tasks.empty()) { h->err = "tile phase: active jobs without a tile"; return WFM_E_HIP; }
+  if (h->tiletasks.ensure(tasks.size())) { h->err = "out of device memory (tile tasks)"; return WFM_E_NOMEM; }
+  HIPCHK(h, hipMemcpyAsync(h->tiletasks.p, tasks.data(), tasks.size() * sizeof(TileTask), hipMemcpyHostToDevice, h->stream));
+  return WFM_OK;
+}
+
+// The chunk's blocks, each a launch of the tile kernels and the tiny kernel that replays the termination checks; the jobs' state back
+int launch_chunk(TilePhase& p) {
+  wfm_handle* h = p.h;
+  wfm_seqset* S = p.S;
+  const TileCfg& cfg = p.cfg;
+  const int T = p.T;
+  const std::vector<TileTask>& tasks = p.plan.tasks;
+  const size_t n_pk = p.plan.n_pk;
+  const std::vector<int>&threads_b = p.plan.threads_b, &variants_b = p.plan.variants_b;
+  const size_t lds = ((size_t)(p.scope + 2 * (p.dp.e1 + 1) + 2 * (p.dp.e2 + 1)) * cfg.Wt + T + 1) * 4;
+  for (int b = 0; b < p.chunk; ++b) {
+    HIPCHK(h, hipEventRecord(h->tile_ev[2 * b], h->stream));
+    if (cfg.reg) {
+      if (n_pk) {
+        launch_tile2(S->d_pk, h->ring.p, h->tilejobs.p, h->tiletasks.p, h->tilemak.p, (int)n_pk, threads_b[(size_t)b], T, variants_b[(size_t)b], h->stream);
+        h->tile_ctr[WFM_TC_BLOCKS_COARSE] += (variants_b[(size_t)b] & 1) != 0;
+        h->tile_ctr[WFM_TC_BLOCKS_FINE] += (variants_b[(size_t)b] & 2) != 0;
+      }
+      if (tasks.size() > n_pk)
+        launch_tile_reg(S->d_seq, h->ring.p, h->tilejobs.p, h->tiletasks.p + n_pk, h->tilemak.p, (int)(tasks.size() - n_pk), threads_b[(size_t)b], T, cfg.C, p.any_cut, h->stream);
+    } else launch_tile(S->d_seq, h->ring.p, h->tilejobs.p, h->tiletasks.p, h->tilemak.p, (int)tasks.size(), cfg.threads, T, cfg.Wt, lds, p.dp, p.scope, ring_rows_for(p.scope), h->stream);
+    HIPCHK(h, hipEventRecord(h->tile_ev[2 * b + 1], h->stream));
+    launch_tile_advance(h->tilejobs.p, h->tilemak.p, (int)p.n, T, p.dp, (cfg.reg && cfg.exact) ? 1 : 0, p.rules.coarse_on ? 1 : 0, variants_b[(size_t)b], h->stream);
+  }
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipMemcpyAsync(p.got.data(), h->tilejobs.p, p.n * sizeof(TileJob), hipMemcpyDeviceToHost, h->stream));
+  return WFM_OK;
+}
+
+// The device time of the chunk's blocks, and what was launched
+int time_chunk(TilePhase& p) {
+  wfm_handle* h = p.h;
+  const size_t ntasks = p.plan.tasks.size();
+  for (int b = 0; b < p.chunk; ++b) {
+    float ms = 0;
+    HIPCHK(h, hipEventElapsedTime(&ms, h->tile_ev[2 * b], h->tile_ev[2 * b + 1]));
+    p.tile_ms += ms;
+    if (h->call_base) {
+      float t0 = 0;
+      HIPCHK(h, hipEventElapsedTime(&t0, h->call_base, h->tile_ev[2 * b]));
+      h->tile_iv.emplace_back(t0, t0 + ms);
+    }
+  }
+  p.blocks += (uint32_t)p.chunk;
+  for (int b = 0; b < p.chunk; ++b) p.lane_cells += (double)ntasks * p.plan.threads_b[(size_t)b] * p.cfg.C * p.T;
+  h->stats.tile_launches += (uint32_t)p.chunk;
+  h->stats.tile_tasks += (uint32_t)(ntasks * (size_t)p.chunk);
+  return WFM_OK;
+}
+
+// The cells of the blocks every job ran since the last look, and the jobs as the chunk left them
+void account_chunk(TilePhase& p) {
+  wfm_handle* h = p.h;
+  const int T = p.T;
+  p.n_active = 0;
+  for (size_t i = 0; i < p.n; ++i) {
+    const TileJob& was = p.tj[i];
+    const TileJob& got = p.got[i];
+    // cells of the blocks this job ran since the last look (the block that found the meeting point included)
+    for (int bl = was.nblocks; bl < got.nblocks; ++bl) {
+      const bool last_exact = got.mode == 2 && bl == got.nblocks - 1;    // the block that stopped at the meeting point
+      const int base = p.s_begin[i] + (last_exact ? bl - 1 : bl) * T;    // it re-ran the block before it
+      for (int d = 0; d < 2; ++d) {
+        const int steps = last_exact ? (d == 0 ? got.tf : got.tr) : T;
+        p.tile_cells += (uint64_t)cells_sum(was.pl, was.tl, was.sub, base + 1, base + steps);
+      }
+    }
+    if (got.fine_s == -1 && was.fine_s != -1) {  // the block in which the directions met ran once more, for its per-score maxima (TileJob::fine_s)
+      for (int d = 0; d < 2; ++d) p.tile_cells += (uint64_t)cells_sum(was.pl, was.tl, was.sub, got.s0 + 1, got.s0 + T);
+      h->tile_ctr[WFM_TC_FINE_RERUNS] += 1;
+    }
+    if (got.reran > was.reran) {  // the block before the meeting block ran once more, for its gap rows (TileJob::ring_prev)
+      for (int d = 0; d < 2; ++d) p.tile_cells += (uint64_t)cells_sum(was.pl, was.tl, was.sub, got.s0 - T + 1, got.s0);
+      h->tile_ctr[WFM_TC_GAP_RERUNS] += (uint64_t)(got.reran - was.reran);
+    }
+    p.tj[i] = got;
+    p.active[i] = (char)(got.active != 0);
+    p.fmax[i] = got.fmax; p.rmax[i] = got.rmax;
+    p.n_active += p.active[i];
+  }
+}
+
+// The jobs back into their BpJobs, positioned at the last snapshot for what follows; the cells that went into the result
+void hand_back(TilePhase& p, uint32_t level, double cells_before) {
+  wfm_handle* h = p.h;
+  // cells that went into the result: both directions up to where the tile phase leaves the job (the full block in which
+  // the wavefronts met was computed as well, and then again up to the meeting point: tile_cells counts it, this does not)
+  uint64_t unique_level = 0;
+  for (size_t i = 0; i < p.n; ++i) {
+    const TileJob& t = p.tj[i];
+    const int sf_end = t.mode == 2 ? t.s0 + t.tf : t.s0, sr_end = t.mode == 2 ? t.s0 + t.tr : t.s0;
+    unique_level += (uint64_t)cells_sum(t.pl, t.tl, t.sub, p.s_begin[i] + 1, sf_end) + (uint64_t)cells_sum(t.pl, t.tl, t.sub, p.s_begin[i] + 1, sr_end);
+  }
+  h->stats.cells_tile_unique += unique_level;
+  for (size_t i = 0; i < p.n; ++i) {
+    const TileJob& t = p.tj[i];
+    BpJob& j = p.jobs[(size_t)p.tiled[i]];
+    j.ring_off = t.ring_in;
+    p.ring2[i] = t.ring_out;
+    j.resume_s = t.s0;
+    j.resume_sr = -1; j.last_fwd = 0;
+    h->tile_ctr[WFM_TC_EXACT_ENDS] += t.mode == 2;
+    h->tile_ctr[WFM_TC_LEFT_BAND] += t.mode == 3;
+    if (t.mode == 3) {  // ran out of its band: wfa_bp_kernel reports WFM_DEV_BAND
+      // (where it stands, for the host: a job that goes on from this snapshot on a wider ring resumes at resume_sr with these maxima)
+      j.resume_s = -3; j.resume_sr = t.s0; j.fmax0 = p.fmax[i]; j.rmax0 = p.rmax[i];
+      continue;
+    }
+    if (t.mode == 2) {  // stopped exactly at the meeting point: the step kernel goes straight to phase 2
+      j.resume_s = t.s0 + t.tf;
+      j.resume_sr = t.s0 + t.tr;
+      j.last_fwd = t.last_fwd;
+    }
+    j.fmax0 = p.fmax[i]; j.rmax0 = p.rmax[i];
+  }
+  if (p.cfg.debug) fprintf(stderr, "[wfm] level %u: tiled %zu jobs, %u blocks of %d scores (Wt %d), %.3f ms; %.3e cells computed on %.3e lane-steps (%.0f %% of the lanes hold a cell), %.3e of them in the result (the block in which a job's wavefronts meet runs twice)\n", level, p.n, p.blocks, p.T, p.cfg.Wt, p.tile_ms,
+                           (double)p.tile_cells - cells_before, p.lane_cells, p.lane_cells > 0 ? 100.0 * ((double)p.tile_cells - cells_before) / p.lane_cells : 0.0, (double)unique_level);
+}
+
 // Advances the jobs listed in `tiled` (indices into jobs) in blocks of T scores with the
 // time-tiled kernel until their forward/reverse antidiagonals meet inside a block; then
 // leaves them positioned at the last snapshot for wfa_bp_kernel (resume_s/fmax0/rmax0/ring_off).
@@ -604,257 +825,181 @@ int run_tiled_phase(wfm_handle* h, wfm_seqset* S, const DevPen& dp, int scope, c
                     const std::vector<int64_t>* ring3 = nullptr) {
   const size_t n = tiled.size();
   if (n == 0) return WFM_OK;
-  double lane_cells = 0;  // threads x diagonals per thread x scores over all tiles launched (diagnostics)
   const double cells_before = (double)tile_cells;
-  const int core = cfg.Wt - 2 * T;
-  std::vector<TileJob> tj(n);
-  std::vector<int> fmax(n, 0), rmax(n, 0);
-  std::vector<char> active(n, 1);
-  for (size_t i = 0; i < n; ++i) {
-    const BpJob& j = jobs[(size_t)tiled[i]];
-    TileJob& t = tj[i];
-    t.p_fwd = j.p_fwd; t.t_fwd = j.t_fwd; t.p_rev = j.p_rev; t.t_rev = j.t_rev;
-    t.ring_in = j.ring_off; t.ring_out = ring2[i];
-    t.pl = j.pl; t.tl = j.tl; t.comp_begin = j.comp_begin; t.comp_end = j.comp_end;
-    t.width = j.width; t.koff = j.koff; t.s0 = 0; t.active = 1; t.fmax = 0; t.rmax = 0; t.nblocks = 0; t.mode = 0; t.tf = 0; t.tr = 0; t.last_fwd = 0; t.packed = j.packed;
-    t.p2_off = 0; t.w2 = 0; t.koff2 = 0; t.sub = j.sub;
-    t.fine_s = (fine_from && i < fine_from->size()) ? (*fine_from)[i] : INT_MAX;  // (TileJob::fine_s; a job whose score nobody knows finds its meeting block by running it again)
-    // a third ring (TileJob::ring_prev): packed jobs of the exact tile phase only -- the byte kernel and the step kernel's fall-backs read gap rows
-    // 26 deep from any snapshot
-    t.ring_prev = (ring3 && i < ring3->size() && (*ring3)[i] >= 0 && (j.packed & 1) && cfg.reg && cfg.exact && !refine) ? (*ring3)[i] : -1;
-    t.prev_ok = 0; t.reran = 0;
-    h->tile_ctr[WFM_TC_RING3] += t.ring_prev >= 0;
-  }
-  if (!refine || T == cfg.T) h->tile_ctr[WFM_TC_JOBS] += n;  // (a WFM_TILE_T_REFINE pass goes on with jobs already counted; a resumed job enters)
-  bool any_cut = false;  // the kernel form with the score bounds' bookkeeping is only launched when a job carries one
-  for (size_t i = 0; i < n; ++i) any_cut |= tj[i].sub != SUB_NONE;
-  if (h->tilejobs.ensure(n) || h->tilemak.ensure(n * 2 * (size_t)std::max(T, 2))) { h->err = "out of device memory (tiles)"; return WFM_E_NOMEM; }
-  size_t n_active = 0;
-  std::vector<int> s_begin(n, 0);  // score the jobs start this pass at
-  if (!refine) {
-    HIPCHK(h, hipMemcpyAsync(h->tilejobs.p, tj.data(), n * sizeof(TileJob), hipMemcpyHostToDevice, h->stream));
-    launch_tile_init(S->d_seq, h->ring.p, h->tilejobs.p, h->tilemak.p, (int)n, ring_rows_for(scope), h->stream);
-    HIPCHK(h, hipGetLastError());
-    std::vector<int32_t> mak(n * 4);
-    HIPCHK(h, hipMemcpyAsync(mak.data(), h->tilemak.p, n * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (size_t i = 0; i < n; ++i) {
-      fmax[i] = mak[(i * 2 + 0) * 2]; rmax[i] = mak[(i * 2 + 1) * 2];
-      const bool ended = mak[(i * 2 + 0) * 2 + 1] || mak[(i * 2 + 1) * 2 + 1];
-      const int A = tj[i].pl + tj[i].tl - 1;
-      if (ended || fmax[i] + rmax[i] >= A) active[i] = 0;  // wfa_bp_kernel handles it from score 0
-      n_active += active[i];
-      tj[i].active = active[i]; tj[i].fmax = fmax[i]; tj[i].rmax = rmax[i]; tj[i].nblocks = 0;
-    }
-  } else {
-    for (size_t i = 0; i < n; ++i) {
-      const BpJob& j = jobs[(size_t)tiled[i]];
-      const int A = tj[i].pl + tj[i].tl - 1;
-      fmax[i] = j.fmax0; rmax[i] = j.rmax0;
-      s_begin[i] = j.resume_s;
-      active[i] = (char)(fmax[i] + rmax[i] < A);  // jobs that were over before their first block stay where they are
-      n_active += active[i];
-      tj[i].s0 = j.resume_s; tj[i].active = active[i]; tj[i].fmax = fmax[i]; tj[i].rmax = rmax[i]; tj[i].nblocks = 0;
-    }
-  }
-  const size_t lds = ((size_t)(scope + 2 * (dp.e1 + 1) + 2 * (dp.e2 + 1)) * cfg.Wt + T + 1) * 4;
-  uint32_t blocks = 0;
-  if (n_active) {
+  TilePhase p{h, S, dp, scope, cfg, T, refine, jobs, tiled, ring2, tile_ms, tile_cells, n};
+  int rc = init_tile_jobs(p, fine_from, ring3);
+  if (rc != WFM_OK) return rc;
+  if (p.n_active) {
     // The per-job state lives on the device and a tiny kernel between two blocks replays the termination
     // checks, so the host only looks every `chunk` blocks.  The task list is built per chunk for the widest
     // range the chunk can reach; a block's tiles outside its current range, and all tiles of jobs that
     // finished earlier in the chunk, exit at once.
-    std::vector<TileTask> tasks, tasks_by;
-    HIPCHK(h, hipMemcpyAsync(h->tilejobs.p, tj.data(), n * sizeof(TileJob), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->tilejobs.p, p.tj.data(), n * sizeof(TileJob), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemsetAsync(h->tilemak.p, 0, n * 2 * (size_t)T * sizeof(int32_t), h->stream));
-    const int chunk = std::max(1, std::min(cfg.chunk, (int)h->tile_ev.size() / 2));
-    std::vector<TileJob> got(n);
+    p.chunk = std::max(1, std::min(cfg.chunk, (int)h->tile_ev.size() / 2));
+    p.got.resize(n); p.pjobs.resize(n);
+    p.rules = TilePlanRules{cfg.threads, cfg.C, T, p.chunk, cfg.Wt - 2 * T, cfg.reg, cfg.fine, cfg.reg && cfg.exact && tile2_coarse_maxima()};
     auto clk = [] { return std::chrono::steady_clock::now(); };
     auto msd = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     double ms_prep = 0, ms_launch = 0, ms_wait = 0, ms_post = 0;
-    while (n_active) {
+    while (p.n_active) {
       const auto tq0 = clk();
-      // a job on a narrow ring (BpJob::band) may only start a chunk whose last score still fits; otherwise it leaves
-      // the tile phase here and is run again on a full ring (the host retries it)
-      bool out_of_band = false;
-      for (size_t i = 0; i < n; ++i) {
-        const int band = jobs[(size_t)tiled[i]].band;
-        if (active[i] && band > 0 && tj[i].s0 + chunk * T + 2 > band) {
-          active[i] = 0; tj[i].active = 0; tj[i].mode = 3; out_of_band = true; --n_active;
-        }
-        // a job whose score bound is a guess: the two directions meet near half the score, so one that is still going
-        // well past half the bound has a score above it -- it leaves here as well and is run again without the bound
-        if (active[i] && tj[i].sub != SUB_NONE) {
-          int L, R;
-          h_rng_block(tj[i].pl, tj[i].tl, tj[i].sub, tj[i].s0, tj[i].s0 + T, &L, &R);
-          if (2 * tj[i].s0 > tj[i].sub + 128 || R < L) {  // (or nothing is left within the bound)
-            active[i] = 0; tj[i].active = 0; tj[i].mode = 3; out_of_band = true; --n_active;
-          }
-        }
-      }
-      if (out_of_band) HIPCHK(h, hipMemcpyAsync(h->tilejobs.p, tj.data(), n * sizeof(TileJob), hipMemcpyHostToDevice, h->stream));
-      if (!n_active) break;
-      // as many tiles of `core` diagonals per job and direction as the last block of this chunk can need.  While the
-      // widest range of the chunk fits one tile, every job-direction is ONE tile without a halo, and the workgroups
-      // are only as large as that range needs (the first blocks of a level are a few hundred diagonals wide)
-      tasks.clear();
-      tasks_by.clear();
-      int core_c = core;
-      std::vector<int> threads_b((size_t)chunk, cfg.threads);  // workgroup size of every block of the chunk
-      if (cfg.reg && cfg.C == 2) {
-        std::vector<int> wb((size_t)chunk, 0);  // widest range per block
-        for (size_t i = 0; i < n; ++i) {
-          if (!active[i]) continue;
-          // a job may run the same block twice (the block in which its wavefronts met, up to the meeting point), and with a
-          // score bound the ranges shrink again towards the end: block b of the chunk needs the widest range up to b
-          int wmax = 0;
-          for (int b = 0; b < chunk; ++b) {
-            int L, R;
-            h_rng_block(tj[i].pl, tj[i].tl, tj[i].sub, tj[i].s0 + b * T, tj[i].s0 + (b + 1) * T, &L, &R);
-            wmax = std::max(wmax, R - L + 1);
-            wb[(size_t)b] = std::max(wb[(size_t)b], wmax);
-          }
-        }
-        if (wb[(size_t)chunk - 1] <= cfg.threads * cfg.C) {
-          // one tile per job-direction: whole waves, as many as the block's own widest range needs (two diagonals per lane)
-          const bool fine = !(getenv("WFM_TILE_FINE") && atoi(getenv("WFM_TILE_FINE")) == 0);  // (per call, like the score-bound switches: the tests run both forms in one process)
-          for (int b = 0; b < chunk; ++b) {
-            const int wdt = fine ? wb[(size_t)b] : wb[(size_t)chunk - 1];
-            threads_b[(size_t)b] = fine ? std::min(cfg.threads, std::max(64, ((wdt + cfg.C - 1) / cfg.C + 63) / 64 * 64))
-                                        : std::min(cfg.threads, wdt <= 256 ? 128 : (wdt <= 512 ? 256 : cfg.threads));
-          }
-          core_c = threads_b[(size_t)chunk - 1] * cfg.C;
-        }
-      }
-      for (size_t i = 0; i < n; ++i) {
-        if (!active[i]) continue;
-        const int core = core_c;
-        int ntiles = 0;  // of the widest block of the chunk
-        for (int b = 0; b < chunk; ++b) {
-          int L, R;
-          h_rng_block(tj[i].pl, tj[i].tl, tj[i].sub, tj[i].s0 + b * T, tj[i].s0 + (b + 1) * T, &L, &R);
-          if (R >= L) ntiles = std::max(ntiles, (R - L + core) / core);
-        }
-        // the tiles of jobs on packed sequences first (wfa_tile2_kernel), the others (an N, soft-masked bases: the byte kernel) behind them
-        for (int d = 0; d < 2; ++d)
-          for (int t = 0; t < ntiles; ++t) (tj[i].packed ? tasks : tasks_by).push_back(TileTask{(int32_t)i, d, t, core});  // (tile index, tile width): the kernel places it
-      }
-      const size_t n_pk = tasks.size();
-      tasks.insert(tasks.end(), tasks_by.begin(), tasks_by.end());
-      if (tasks.empty()) { h->err = "tile phase: active jobs without a tile"; return WFM_E_HIP; }
-      if (h->tiletasks.ensure(tasks.size())) { h->err = "out of device memory (tile tasks)"; return WFM_E_NOMEM; }
-      HIPCHK(h, hipMemcpyAsync(h->tiletasks.p, tasks.data(), tasks.size() * sizeof(TileTask), hipMemcpyHostToDevice, h->stream));
+      if ((rc = drop_leavers(p)) != WFM_OK) return rc;
+      if (!p.n_active) break;
+      if ((rc = plan_tile_tasks(p)) != WFM_OK) return rc;
       const auto tq1 = clk();
-      // which instantiations of the packed kernel a block of the chunk can have tiles for (wfa_tile2_kernel, FINE): the one without per-score
-      // maxima always (the blocks before a job's meeting block and the run up to the meeting point); the one with them where a job that simply
-      // moved on has reached its fine_s, and in the chunk's first block for the jobs the last chunk left in mode 5
-      const bool coarse_on = cfg.reg && cfg.exact && tile2_coarse_maxima();
-      std::vector<int> variants_b((size_t)chunk, coarse_on ? 0 : 2);
-      if (coarse_on) {
-        for (size_t i = 0; i < n; ++i) {
-          if (!active[i] || !(tj[i].packed & 1)) continue;
-          for (int b = 0; b < chunk; ++b) {
-            if ((tj[i].mode == 5 && b == 0) || (tj[i].mode == 0 && (int64_t)tj[i].s0 + (int64_t)(b + 1) * T >= (int64_t)tj[i].fine_s)) variants_b[(size_t)b] |= 2;
-            // without maxima: a job that simply moved on and is still below its fine_s (it may also have met meanwhile: its run up to the meeting
-            // point needs no maxima either -- and is taken by the FINE instantiation where that one is launched alone)
-            if (tj[i].mode == 0 && (int64_t)tj[i].s0 + (int64_t)(b + 1) * T < (int64_t)tj[i].fine_s) variants_b[(size_t)b] |= 1;
-          }
-        }
-        for (int b = 0; b < chunk; ++b) if (!variants_b[(size_t)b]) variants_b[(size_t)b] = 2;  // (only runs up to a meeting point: either would do)
-      }
-      for (int b = 0; b < chunk; ++b) {
-        HIPCHK(h, hipEventRecord(h->tile_ev[2 * b], h->stream));
-        if (cfg.reg) {
-          if (n_pk) {
-            launch_tile2(S->d_pk, h->ring.p, h->tilejobs.p, h->tiletasks.p, h->tilemak.p, (int)n_pk, threads_b[(size_t)b], T, variants_b[(size_t)b], h->stream);
-            h->tile_ctr[WFM_TC_BLOCKS_COARSE] += (variants_b[(size_t)b] & 1) != 0;
-            h->tile_ctr[WFM_TC_BLOCKS_FINE] += (variants_b[(size_t)b] & 2) != 0;
-          }
-          if (tasks.size() > n_pk)
-            launch_tile_reg(S->d_seq, h->ring.p, h->tilejobs.p, h->tiletasks.p + n_pk, h->tilemak.p, (int)(tasks.size() - n_pk), threads_b[(size_t)b], T, cfg.C, any_cut, h->stream);
-        } else launch_tile(S->d_seq, h->ring.p, h->tilejobs.p, h->tiletasks.p, h->tilemak.p, (int)tasks.size(), cfg.threads, T, cfg.Wt, lds, dp, scope, ring_rows_for(scope), h->stream);
-        HIPCHK(h, hipEventRecord(h->tile_ev[2 * b + 1], h->stream));
-        launch_tile_advance(h->tilejobs.p, h->tilemak.p, (int)n, T, dp, (cfg.reg && cfg.exact) ? 1 : 0, coarse_on ? 1 : 0, variants_b[(size_t)b], h->stream);
-      }
-      HIPCHK(h, hipGetLastError());
-      HIPCHK(h, hipMemcpyAsync(got.data(), h->tilejobs.p, n * sizeof(TileJob), hipMemcpyDeviceToHost, h->stream));
+      if ((rc = launch_chunk(p)) != WFM_OK) return rc;
       const auto tq2 = clk();
       HIPCHK(h, hipStreamSynchronize(h->stream));
       const auto tq3 = clk();
-      for (int b = 0; b < chunk; ++b) {
-        float ms = 0;
-        HIPCHK(h, hipEventElapsedTime(&ms, h->tile_ev[2 * b], h->tile_ev[2 * b + 1]));
-        tile_ms += ms;
-        if (h->call_base) {
-          float t0 = 0;
-          HIPCHK(h, hipEventElapsedTime(&t0, h->call_base, h->tile_ev[2 * b]));
-          h->tile_iv.emplace_back(t0, t0 + ms);
-        }
-      }
-      blocks += (uint32_t)chunk;
-      for (int b = 0; b < chunk; ++b) lane_cells += (double)tasks.size() * threads_b[(size_t)b] * cfg.C * T;
-      h->stats.tile_launches += (uint32_t)chunk;
-      h->stats.tile_tasks += (uint32_t)(tasks.size() * (size_t)chunk);
-      n_active = 0;
-      for (size_t i = 0; i < n; ++i) {
-        // cells of the blocks this job ran since the last look (the block that found the meeting point included)
-        for (int bl = tj[i].nblocks; bl < got[i].nblocks; ++bl) {
-          const bool last_exact = got[i].mode == 2 && bl == got[i].nblocks - 1;  // the block that stopped at the meeting point
-          const int base = s_begin[i] + (last_exact ? bl - 1 : bl) * T;          // it re-ran the block before it
-          for (int d = 0; d < 2; ++d) {
-            const int steps = last_exact ? (d == 0 ? got[i].tf : got[i].tr) : T;
-            tile_cells += (uint64_t)h_cells_sum(tj[i].pl, tj[i].tl, tj[i].sub, base + 1, base + steps);
-          }
-        }
-        if (got[i].fine_s == -1 && tj[i].fine_s != -1) {  // the block in which the directions met ran once more, for its per-score maxima (TileJob::fine_s)
-          for (int d = 0; d < 2; ++d) tile_cells += (uint64_t)h_cells_sum(tj[i].pl, tj[i].tl, tj[i].sub, got[i].s0 + 1, got[i].s0 + T);
-          h->tile_ctr[WFM_TC_FINE_RERUNS] += 1;
-        }
-        if (got[i].reran > tj[i].reran) {  // the block before the meeting block ran once more, for its gap rows (TileJob::ring_prev)
-          for (int d = 0; d < 2; ++d) tile_cells += (uint64_t)h_cells_sum(tj[i].pl, tj[i].tl, tj[i].sub, got[i].s0 - T + 1, got[i].s0);
-          h->tile_ctr[WFM_TC_GAP_RERUNS] += (uint64_t)(got[i].reran - tj[i].reran);
-        }
-        tj[i] = got[i];
-        active[i] = (char)(got[i].active != 0);
-        fmax[i] = got[i].fmax; rmax[i] = got[i].rmax;
-        n_active += active[i];
-      }
+      if ((rc = time_chunk(p)) != WFM_OK) return rc;
+      account_chunk(p);
       ms_prep += msd(tq0, tq1); ms_launch += msd(tq1, tq2); ms_wait += msd(tq2, tq3); ms_post += msd(tq3, clk());
     }
-    if (getenv("WFM_DEBUG") && atoi(getenv("WFM_DEBUG")) > 1)
+    if (cfg.debug > 1)
       fprintf(stderr, "[wfm] level %u tile phase, host side: task lists %.2f ms, launches %.2f ms, waiting for the device %.2f ms, bookkeeping %.2f ms\n", level, ms_prep, ms_launch, ms_wait, ms_post);
   }
-  // cells that went into the result: both directions up to where the tile phase leaves the job (the full block in which
-  // the wavefronts met was computed as well, and then again up to the meeting point: tile_cells counts it, this does not)
-  uint64_t unique_level = 0;
-  for (size_t i = 0; i < n; ++i) {
-    const int sf_end = tj[i].mode == 2 ? tj[i].s0 + tj[i].tf : tj[i].s0, sr_end = tj[i].mode == 2 ? tj[i].s0 + tj[i].tr : tj[i].s0;
-    unique_level += (uint64_t)h_cells_sum(tj[i].pl, tj[i].tl, tj[i].sub, s_begin[i] + 1, sf_end) +
-                    (uint64_t)h_cells_sum(tj[i].pl, tj[i].tl, tj[i].sub, s_begin[i] + 1, sr_end);
+  hand_back(p, level, cells_before);
+  return WFM_OK;
+}
+
+// ---- phase 2 from rows computed ahead: run_p2_phase (at the end) is the loop over chunks of candidates, the stages before it do the work ----
+
+// One call of run_p2_phase and the chunk at hand: the candidates i0 .. i0 + n, as many as the budget of the rows holds
+struct P2Chunk {
+  wfm_handle* h; wfm_seqset* S; const DevPen& dp; int scope; const TileCfg& cfg; std::vector<BpJob>& jobs;  // run_p2_phase's arguments
+  const std::vector<int>& cand; const std::vector<int64_t>& ring_other; std::vector<BpResult>& res; double& ms_out;
+  std::vector<BpResult>& carry; std::vector<char>& has_carry; bool may_continue; std::vector<int>& again;
+  std::vector<P2PlanJob> pcand;  // what plan_p2_chunk needs of every candidate
+  P2ChunkPlan plan;
+  size_t i0 = 0, n = 0;
+  std::vector<TileJob> tj;
+  std::vector<P2Job> pj;
+  std::vector<BpResult> got;
+  float ms = 0;
+};
+
+// The chunk that begins at candidate i0: its geometry and task list (plan_p2_chunk), its TileJobs (mode 4) and P2Jobs
+void fill_p2_chunk(P2Chunk& c, size_t i0) {
+  // the rows of a chunk of jobs may take a quarter of the budget (the rings hold the rest)
+  const size_t budget = std::max<size_t>(c.h->mem_budget / 4, (size_t)64 << 20);
+  plan_p2_chunk(c.pcand.data(), c.pcand.size(), i0, P2K, P2ROWS, budget, c.cfg.threads, c.cfg.Wt - 2 * P2K, c.plan);
+  c.i0 = i0; c.n = c.plan.geo.size();
+  c.tj.clear(); c.pj.clear();
+  for (size_t q = 0; q < c.n; ++q) {
+    const BpJob& j = c.jobs[(size_t)c.cand[i0 + q]];
+    const P2Geometry& g = c.plan.geo[q];
+    TileJob t = tile_job_from(j);
+    t.ring_out = c.ring_other[i0 + q];
+    t.mode = 4; t.tf = j.resume_s; t.tr = j.resume_sr; t.last_fwd = j.last_fwd;
+    t.p2_off = (int64_t)g.p2_off; t.w2 = (int32_t)g.w2; t.koff2 = g.koff2;
+    P2Job pq{};
+    pq.ring_in = j.ring_off; pq.p2_off = (int64_t)g.p2_off; pq.width = j.width; pq.koff = j.koff; pq.w2 = (int32_t)g.w2; pq.koff2 = g.koff2;
+    pq.pl = j.pl; pq.tl = j.tl; pq.sf = j.resume_s; pq.sr = j.resume_sr; pq.last_fwd = j.last_fwd; pq.sub = j.sub; pq.best0 = j.best0;
+    pq.nblk = (int32_t)g.nblk; pq.bm_off = (int64_t)g.bm_off;
+    c.tj.push_back(t); c.pj.push_back(pq);
   }
-  h->stats.cells_tile_unique += unique_level;
-  for (size_t i = 0; i < n; ++i) {
-    BpJob& j = jobs[(size_t)tiled[i]];
-    j.ring_off = tj[i].ring_in;
-    ring2[i] = tj[i].ring_out;
-    j.resume_s = tj[i].s0;
-    j.resume_sr = -1; j.last_fwd = 0;
-    h->tile_ctr[WFM_TC_EXACT_ENDS] += tj[i].mode == 2;
-    h->tile_ctr[WFM_TC_LEFT_BAND] += tj[i].mode == 3;
-    if (tj[i].mode == 3) {  // ran out of its band: wfa_bp_kernel reports WFM_DEV_BAND
-      // (where it stands, for the host: a job that goes on from this snapshot on a wider ring resumes at resume_sr with these maxima)
-      j.resume_s = -3; j.resume_sr = tj[i].s0; j.fmax0 = fmax[i]; j.rmax0 = rmax[i];
-      continue;
-    }
-    if (tj[i].mode == 2) {  // stopped exactly at the meeting point: the step kernel goes straight to phase 2
-      j.resume_s = tj[i].s0 + tj[i].tf;
-      j.resume_sr = tj[i].s0 + tj[i].tr;
-      j.last_fwd = tj[i].last_fwd;
-    }
-    j.fmax0 = fmax[i]; j.rmax0 = rmax[i];
+}
+
+// The chunk on the device: the rows computed ahead, their maxima, the walk; the results back and the time it took
+int launch_p2_chunk(P2Chunk& c) {
+  wfm_handle* h = c.h;
+  wfm_seqset* S = c.S;
+  const size_t n = c.n, elems = c.plan.elems, bm_elems = c.plan.bm_elems, n_pk = c.plan.tiles.n_pk;
+  const std::vector<TileTask>& tasks = c.plan.tiles.tasks;
+  const int threads_c = c.plan.threads_c;
+  if (h->p2rows.ensure(elems + 16) || h->p2max.ensure(n * 2 * P2ROWS * 5) || h->p2bmax.ensure(bm_elems + 16) || h->p2pbmax.ensure(bm_elems + 16) ||
+      h->p2jobs.ensure(n) || h->tilejobs.ensure(n) || h->tiletasks.ensure(tasks.size()) || h->bpres.ensure(std::max(n, c.jobs.size()))) {
+    h->err = "out of device memory (phase-2 rows)"; return WFM_E_NOMEM;
   }
-  if (getenv("WFM_DEBUG")) fprintf(stderr, "[wfm] level %u: tiled %zu jobs, %u blocks of %d scores (Wt %d), %.3f ms; %.3e cells computed on %.3e lane-steps (%.0f %% of the lanes hold a cell), %.3e of them in the result (the block in which a job's wavefronts meet runs twice)\n", level, n, blocks, T, cfg.Wt, tile_ms,
-                                   (double)tile_cells - cells_before, lane_cells, lane_cells > 0 ? 100.0 * ((double)tile_cells - cells_before) / lane_cells : 0.0, (double)unique_level);
+  HIPCHK(h, hipMemcpyAsync(h->tilejobs.p, c.tj.data(), n * sizeof(TileJob), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->p2jobs.p, c.pj.data(), n * sizeof(P2Job), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->tiletasks.p, tasks.data(), tasks.size() * sizeof(TileTask), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+  bool any_cut = false;
+  for (const TileJob& t : c.tj) any_cut |= t.sub != SUB_NONE;
+  if (n_pk) launch_tile2_p2(S->d_pk, h->ring.p, h->tilejobs.p, h->tiletasks.p, (int)n_pk, threads_c, h->p2rows.p, h->stream);
+  if (tasks.size() > n_pk) launch_tile_p2(S->d_seq, h->ring.p, h->tilejobs.p, h->tiletasks.p + n_pk, (int)(tasks.size() - n_pk), threads_c, h->p2rows.p, any_cut, h->stream);
+  launch_p2_blockmax(h->ring.p, h->p2rows.p, h->p2jobs.p, h->p2bmax.p, h->p2max.p, (int)n, h->stream);
+  static const int p2_threads = getenv("WFM_P2_THREADS") ? atoi(getenv("WFM_P2_THREADS")) : 0;  // (a once-per-process switch: it stays static)
+  launch_p2_overlap(h->ring.p, h->p2rows.p, h->p2jobs.p, h->p2max.p, h->p2bmax.p, h->p2pbmax.p, h->bpres.p, (int)n,
+                    p2_threads > 0 ? p2_threads : 1024, (int)(c.plan.maxw2 >> 6) + 1, c.dp, c.scope, h->stream);  // 16 waves over the 5 x P2G (test, component) scans of a round and their rows
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+  c.got.resize(n);
+  HIPCHK(h, hipMemcpyAsync(c.got.data(), h->bpres.p, n * sizeof(BpResult), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, hipEventElapsedTime(&c.ms, h->ev0, h->ev1));
+  c.ms_out += c.ms;
+  if (h->call_base) {
+    float t0 = 0;
+    HIPCHK(h, hipEventElapsedTime(&t0, h->call_base, h->ev0));
+    h->bp_iv.emplace_back(t0, t0 + c.ms);
+  }
+  return WFM_OK;
+}
+
+// WFM_P2_DUMP (diagnosis): the row maxima of one job of the chunk
+int dump_p2_job(P2Chunk& c) {
+  wfm_handle* h = c.h;
+  const std::vector<BpResult>& got = c.got;
+  const size_t q = std::min<size_t>((size_t)c.cfg.p2_dump, c.n - 1);
+  std::vector<int32_t> rm((size_t)2 * P2ROWS * 5);
+  HIPCHK(h, hipMemcpy(rm.data(), h->p2max.p + q * 2 * P2ROWS * 5, rm.size() * 4, hipMemcpyDeviceToHost));
+  const P2Job& pjq = c.pj[q];
+  fprintf(stderr, "[wfm] p2 dump job %zu: pl %d tl %d sf %d sr %d last_fwd %d sub %d w2 %d nblk %d -> status %d score %d (fwd %d rev %d comp %d k %d) rounds %d\n", q, pjq.pl, pjq.tl, pjq.sf,
+          pjq.sr, pjq.last_fwd, pjq.sub, pjq.w2, pjq.nblk, got[q].status, got[q].score, got[q].score_fwd, got[q].score_rev, got[q].comp, got[q].k_fwd, got[q].pad_);
+  for (int d = 0; d < 2; ++d)
+    for (int r = 0; r < P2ROWS; r += 3) {
+      const int32_t* m = rm.data() + ((size_t)d * P2ROWS + r) * 5;
+      fprintf(stderr, "[wfm]   dir %d row %d (s = %d): max M %d I1 %d I2 %d D1 %d D2 %d\n", d, r, (d == 0 ? pjq.sf : pjq.sr) - RNG_BACK + r, m[0], m[1], m[2], m[3], m[4]);
+    }
+  return WFM_OK;
+}
+
+// WFM_DEBUG: the chunk's launch and its slowest walk
+void print_p2_chunk(const P2Chunk& c) {
+  const std::vector<BpResult>& got = c.got;
+  const std::vector<P2Job>& pj = c.pj;
+  const size_t n = c.n;
+  int more = 0;
+  double tk = 0, tc = 0, rd = 0; uint32_t tkmax = 0; int rdmax = 0;
+  for (const BpResult& r : got) { more += r.status == WFM_DEV_P2_MORE; tk += r.ticks_p2; tc += r.ticks_p1; rd += r.pad_; tkmax = std::max(tkmax, r.ticks_p2); rdmax = std::max(rdmax, r.pad_); }
+  fprintf(stderr, "[wfm] phase 2 from rows computed ahead: %zu jobs, widest %zu columns, %zu tiles of %d threads, %.3f ms, %d left to the step kernel; walk per job: %.1f rounds (max %d), %.0f us (max %.0f), of which cells stage %.0f us\n",
+          n, c.plan.maxw2, c.plan.tiles.tasks.size(), c.plan.threads_c, c.ms, more, rd / n, rdmax, tk / n / 100.0, tkmax / 100.0, tc / n / 100.0);
+  size_t qs = 0;
+  for (size_t q = 0; q < n; ++q) if (got[q].ticks_p2 > got[qs].ticks_p2) qs = q;
+  fprintf(stderr, "[wfm]   slowest walk: pl %d tl %d sub %d w2 %d nblk %d: %d rounds, %.0f us = listing %.0f + cells %.0f (incl. listing) + pick %.0f, %u blocks listed, status %d\n", pj[qs].pl, pj[qs].tl,
+          pj[qs].sub == SUB_NONE ? -1 : pj[qs].sub, pj[qs].w2, pj[qs].nblk, got[qs].pad_, got[qs].ticks_p2 / 100.0, got[qs].ticks_list / 100.0, got[qs].ticks_p1 / 100.0, got[qs].ticks_pick / 100.0,
+          got[qs].work_items, got[qs].status);
+}
+
+// Another round for the jobs whose walk ran out of rows (while their rings have room for its rows); the chunk's results into res
+int continue_p2_chunk(P2Chunk& c) {
+  wfm_handle* h = c.h;
+  std::vector<BpResult>& got = c.got;
+  std::vector<P2Job> mj;
+  for (size_t q = 0; q < c.n; ++q) {
+    const size_t jq = (size_t)c.cand[c.i0 + q];
+    BpJob& j = c.jobs[jq];
+    if (got[q].status == WFM_DEV_P2_NOTHING) { got[q] = c.carry[jq]; continue; }  // nothing better than what an earlier round found
+    if (got[q].status != WFM_DEV_P2_MORE) continue;
+    if (got[q].comp >= 0) {  // a breakpoint so far (better than the one handed in, if any)
+      c.carry[jq] = got[q]; c.carry[jq].status = 0; c.has_carry[jq] = 1;
+      j.best0 = got[q].score;
+    }
+    if (!c.may_continue || (j.band > 0 && std::max(j.resume_s, j.resume_sr) + 2 * P2K + 2 > j.band)) continue;  // wfa_bp_kernel goes on from here
+    mj.push_back(c.pj[q]);
+    j.resume_s += P2K; j.resume_sr += P2K;  // 2 * P2K tests: both directions P2K rows further, the same one stepped last
+    c.again.push_back((int)(c.i0 + q));
+  }
+  if (!mj.empty()) {
+    HIPCHK(h, hipMemcpyAsync(h->p2jobs.p, mj.data(), mj.size() * sizeof(P2Job), hipMemcpyHostToDevice, h->stream));
+    launch_p2_to_ring(h->ring.p, h->p2rows.p, h->p2jobs.p, (int)mj.size(), h->stream);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));  // (mj is read by the copy above)
+  }
+  for (size_t q = 0; q < c.n; ++q) c.res[(size_t)c.cand[c.i0 + q]] = got[q];
   return WFM_OK;
 }
 
@@ -871,149 +1016,20 @@ int run_p2_phase(wfm_handle* h, wfm_seqset* S, const DevPen& dp, int scope, cons
                  const std::vector<int>& cand, const std::vector<int64_t>& ring_other, std::vector<BpResult>& res, double& ms_out,
                  std::vector<BpResult>& carry, std::vector<char>& has_carry, bool may_continue, std::vector<int>& again) {
   if (cand.empty()) return WFM_OK;
-  const int core = cfg.Wt - 2 * P2K;
-  size_t i0 = 0;
-  std::vector<TileJob> tj;
-  std::vector<P2Job> pj;
-  std::vector<TileTask> tasks, tasks_by;
-  std::vector<BpResult> got;
-  // the rows of a chunk of jobs may take a quarter of the budget (the rings hold the rest)
-  const size_t budget = std::max<size_t>(h->mem_budget / 4, (size_t)64 << 20);
-  while (i0 < cand.size()) {
-    tj.clear(); pj.clear(); tasks.clear(); tasks_by.clear();
-    size_t elems = 0, i = i0, maxw2 = 0, bm_elems = 0;
-    for (; i < cand.size(); ++i) {
-      const BpJob& j = jobs[(size_t)cand[i]];
-      const int reach = std::max(j.resume_s, j.resume_sr) + P2K;
-      int L, R;  // every diagonal a row of the window can hold: the snapshot's rows (26 back) and the rows computed ahead
-      h_rng_block(j.pl, j.tl, j.sub, std::max(0, std::min(j.resume_s, j.resume_sr) - 27), reach, &L, &R);
-      if (R < L) { L = 0; R = 0; }
-      const int koff2 = ((-L + 4) + 3) & ~3;                       // column of diagonal 0: a multiple of 4, >= 4 columns of margin
-      const size_t w2 = ((size_t)(R + koff2 + 8) + 3) & ~(size_t)3;
-      const size_t nblk = (w2 >> 6) + 1;
-      const size_t need = w2 * 2 * 5 * P2K, need_bm = nblk * 2 * P2ROWS * 5;
-      if (!tj.empty() && (elems + need + 2 * (bm_elems + need_bm)) * 4 > budget) break;
-      maxw2 = std::max(maxw2, w2);
-      TileJob t{};
-      t.p_fwd = j.p_fwd; t.t_fwd = j.t_fwd; t.p_rev = j.p_rev; t.t_rev = j.t_rev;
-      t.ring_in = j.ring_off; t.ring_out = ring_other[i];
-      t.pl = j.pl; t.tl = j.tl; t.comp_begin = j.comp_begin; t.comp_end = j.comp_end;
-      t.width = j.width; t.koff = j.koff; t.s0 = 0; t.active = 1; t.fmax = 0; t.rmax = 0; t.nblocks = 0;
-      t.mode = 4; t.tf = j.resume_s; t.tr = j.resume_sr; t.last_fwd = j.last_fwd; t.packed = j.packed;
-      t.p2_off = (int64_t)elems; t.w2 = (int32_t)w2; t.koff2 = koff2; t.sub = j.sub;
-      P2Job q{};
-      q.ring_in = j.ring_off; q.p2_off = (int64_t)elems; q.width = j.width; q.koff = j.koff; q.w2 = (int32_t)w2; q.koff2 = koff2;
-      q.pl = j.pl; q.tl = j.tl; q.sf = j.resume_s; q.sr = j.resume_sr; q.last_fwd = j.last_fwd; q.sub = j.sub; q.best0 = j.best0;
-      q.nblk = (int32_t)nblk; q.bm_off = (int64_t)bm_elems;
-      bm_elems += need_bm;
-      elems += need;
-      tj.push_back(t); pj.push_back(q);
-    }
-    const size_t n = tj.size();
-    // one tile without a halo per job-direction while the widest range of the chunk fits one (see run_tiled_phase)
-    int threads_c = cfg.threads, core_c = core;
-    {
-      int widest = 0;
-      for (const TileJob& t : tj)
-        for (int d = 0; d < 2; ++d) {
-          int L, R;
-          h_rng_block(t.pl, t.tl, t.sub, d == 0 ? t.tf : t.tr, (d == 0 ? t.tf : t.tr) + P2K, &L, &R);
-          widest = std::max(widest, R - L + 1);
-        }
-      if (widest <= cfg.threads * 2) {
-        threads_c = std::min(cfg.threads, std::max(64, ((widest + 1) / 2 + 63) / 64 * 64));
-        core_c = threads_c * 2;
-      }
-    }
-    for (size_t jn = 0; jn < n; ++jn)
-      for (int d = 0; d < 2; ++d) {
-        int Ld, Rd;
-        h_rng_block(tj[jn].pl, tj[jn].tl, tj[jn].sub, d == 0 ? tj[jn].tf : tj[jn].tr, (d == 0 ? tj[jn].tf : tj[jn].tr) + P2K, &Ld, &Rd);
-        const int ntiles = Rd >= Ld ? (Rd - Ld + core_c) / core_c : 0;
-        for (int t2 = 0; t2 < ntiles; ++t2) (tj[jn].packed ? tasks : tasks_by).push_back(TileTask{(int32_t)jn, d, t2, core_c});
-      }
-    const size_t n_pk = tasks.size();  // (packed jobs' tiles first: see run_tiled_phase)
-    tasks.insert(tasks.end(), tasks_by.begin(), tasks_by.end());
-    if (h->p2rows.ensure(elems + 16) || h->p2max.ensure(n * 2 * P2ROWS * 5) || h->p2bmax.ensure(bm_elems + 16) || h->p2pbmax.ensure(bm_elems + 16) ||
-        h->p2jobs.ensure(n) || h->tilejobs.ensure(n) || h->tiletasks.ensure(tasks.size()) || h->bpres.ensure(std::max(n, jobs.size()))) {
-      h->err = "out of device memory (phase-2 rows)"; return WFM_E_NOMEM;
-    }
-    HIPCHK(h, hipMemcpyAsync(h->tilejobs.p, tj.data(), n * sizeof(TileJob), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->p2jobs.p, pj.data(), n * sizeof(P2Job), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->tiletasks.p, tasks.data(), tasks.size() * sizeof(TileTask), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-    bool any_cut = false;
-    for (const TileJob& t : tj) any_cut |= t.sub != SUB_NONE;
-    if (n_pk) launch_tile2_p2(S->d_pk, h->ring.p, h->tilejobs.p, h->tiletasks.p, (int)n_pk, threads_c, h->p2rows.p, h->stream);
-    if (tasks.size() > n_pk) launch_tile_p2(S->d_seq, h->ring.p, h->tilejobs.p, h->tiletasks.p + n_pk, (int)(tasks.size() - n_pk), threads_c, h->p2rows.p, any_cut, h->stream);
-    launch_p2_blockmax(h->ring.p, h->p2rows.p, h->p2jobs.p, h->p2bmax.p, h->p2max.p, (int)n, h->stream);
-    static const int p2_threads = getenv("WFM_P2_THREADS") ? atoi(getenv("WFM_P2_THREADS")) : 0;
-    launch_p2_overlap(h->ring.p, h->p2rows.p, h->p2jobs.p, h->p2max.p, h->p2bmax.p, h->p2pbmax.p, h->bpres.p, (int)n,
-                      p2_threads > 0 ? p2_threads : 1024, (int)(maxw2 >> 6) + 1, dp, scope, h->stream);  // 16 waves over the 5 x P2G (test, component) scans of a round and their rows
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-    got.resize(n);
-    HIPCHK(h, hipMemcpyAsync(got.data(), h->bpres.p, n * sizeof(BpResult), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    float ms = 0;
-    HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    ms_out += ms;
-    if (h->call_base) {
-      float t0 = 0;
-      HIPCHK(h, hipEventElapsedTime(&t0, h->call_base, h->ev0));
-      h->bp_iv.emplace_back(t0, t0 + ms);
-    }
-    if (const char* de = getenv("WFM_P2_DUMP")) {  // diagnosis: the row maxima of one job of the chunk
-      const size_t q = std::min<size_t>((size_t)atoi(de), n - 1);
-      std::vector<int32_t> rm((size_t)2 * P2ROWS * 5);
-      HIPCHK(h, hipMemcpy(rm.data(), h->p2max.p + q * 2 * P2ROWS * 5, rm.size() * 4, hipMemcpyDeviceToHost));
-      const P2Job& pjq = pj[q];
-      fprintf(stderr, "[wfm] p2 dump job %zu: pl %d tl %d sf %d sr %d last_fwd %d sub %d w2 %d nblk %d -> status %d score %d (fwd %d rev %d comp %d k %d) rounds %d\n", q, pjq.pl, pjq.tl, pjq.sf,
-              pjq.sr, pjq.last_fwd, pjq.sub, pjq.w2, pjq.nblk, got[q].status, got[q].score, got[q].score_fwd, got[q].score_rev, got[q].comp, got[q].k_fwd, got[q].pad_);
-      for (int d = 0; d < 2; ++d)
-        for (int r = 0; r < P2ROWS; r += 3) {
-          const int32_t* m = rm.data() + ((size_t)d * P2ROWS + r) * 5;
-          fprintf(stderr, "[wfm]   dir %d row %d (s = %d): max M %d I1 %d I2 %d D1 %d D2 %d\n", d, r, (d == 0 ? pjq.sf : pjq.sr) - 25 + r, m[0], m[1], m[2], m[3], m[4]);
-        }
-    }
+  P2Chunk c{h, S, dp, scope, cfg, jobs, cand, ring_other, res, ms_out, carry, has_carry, may_continue, again};
+  for (int q : cand) {
+    const BpJob& j = jobs[(size_t)q];
+    c.pcand.push_back(P2PlanJob{j.pl, j.tl, j.sub, j.resume_s, j.resume_sr, j.packed});
+  }
+  for (size_t i0 = 0; i0 < cand.size(); i0 += c.n) {
+    fill_p2_chunk(c, i0);
+    int rc = launch_p2_chunk(c);
+    if (rc != WFM_OK) return rc;
+    if (cfg.p2_dump_on && (rc = dump_p2_job(c)) != WFM_OK) return rc;
     h->stats.p2_launches++;
-    h->stats.p2_jobs += (uint32_t)n;
-    if (getenv("WFM_DEBUG")) {
-      int more = 0;
-      double tk = 0, tc = 0, rd = 0; uint32_t tkmax = 0; int rdmax = 0;
-      for (const BpResult& r : got) { more += r.status == WFM_DEV_P2_MORE; tk += r.ticks_p2; tc += r.ticks_p1; rd += r.pad_; tkmax = std::max(tkmax, r.ticks_p2); rdmax = std::max(rdmax, r.pad_); }
-      fprintf(stderr, "[wfm] phase 2 from rows computed ahead: %zu jobs, widest %zu columns, %zu tiles of %d threads, %.3f ms, %d left to the step kernel; walk per job: %.1f rounds (max %d), %.0f us (max %.0f), of which cells stage %.0f us\n",
-              n, maxw2, tasks.size(), threads_c, ms, more, rd / n, rdmax, tk / n / 100.0, tkmax / 100.0, tc / n / 100.0);
-      size_t qs = 0;
-      for (size_t q = 0; q < n; ++q) if (got[q].ticks_p2 > got[qs].ticks_p2) qs = q;
-      fprintf(stderr, "[wfm]   slowest walk: pl %d tl %d sub %d w2 %d nblk %d: %d rounds, %.0f us = listing %.0f + cells %.0f (incl. listing) + pick %.0f, %u blocks listed, status %d\n", pj[qs].pl, pj[qs].tl,
-              pj[qs].sub == SUB_NONE ? -1 : pj[qs].sub, pj[qs].w2, pj[qs].nblk, got[qs].pad_, got[qs].ticks_p2 / 100.0, got[qs].ticks_list / 100.0, got[qs].ticks_p1 / 100.0, got[qs].ticks_pick / 100.0,
-              got[qs].work_items, got[qs].status);
-    }
-    // another round for the jobs whose walk ran out of rows (while their rings have room for its rows)
-    std::vector<P2Job> mj;
-    for (size_t q = 0; q < n; ++q) {
-      const size_t jq = (size_t)cand[i0 + q];
-      BpJob& j = jobs[jq];
-      if (got[q].status == WFM_DEV_P2_NOTHING) { got[q] = carry[jq]; continue; }  // nothing better than what an earlier round found
-      if (got[q].status != WFM_DEV_P2_MORE) continue;
-      if (got[q].comp >= 0) {  // a breakpoint so far (better than the one handed in, if any)
-        carry[jq] = got[q]; carry[jq].status = 0; has_carry[jq] = 1;
-        j.best0 = got[q].score;
-      }
-      if (!may_continue || (j.band > 0 && std::max(j.resume_s, j.resume_sr) + 2 * P2K + 2 > j.band)) continue;  // wfa_bp_kernel goes on from here
-      mj.push_back(pj[q]);
-      j.resume_s += P2K; j.resume_sr += P2K;  // 2 * P2K tests: both directions P2K rows further, the same one stepped last
-      again.push_back((int)(i0 + q));
-    }
-    if (!mj.empty()) {
-      HIPCHK(h, hipMemcpyAsync(h->p2jobs.p, mj.data(), mj.size() * sizeof(P2Job), hipMemcpyHostToDevice, h->stream));
-      launch_p2_to_ring(h->ring.p, h->p2rows.p, h->p2jobs.p, (int)mj.size(), h->stream);
-      HIPCHK(h, hipGetLastError());
-      HIPCHK(h, hipStreamSynchronize(h->stream));  // (mj is read by the copy above)
-    }
-    for (size_t q = 0; q < n; ++q) res[(size_t)cand[i0 + q]] = got[q];
-    i0 = i;
+    h->stats.p2_jobs += (uint32_t)c.n;
+    if (cfg.debug) print_p2_chunk(c);
+    if ((rc = continue_p2_chunk(c)) != WFM_OK) return rc;
   }
   return WFM_OK;
 }
@@ -1034,8 +1050,8 @@ struct Knobs {
   bool tile_v2 = num("WFM_TILE_V2", 1) != 0;  // 0: every tile on the byte kernel (wfa_tile_reg_kernel) -- the A/B switch of the packed kernel (wfa_tile2.hip)
   bool band_on = num("WFM_BAND", 1) != 0;
   int band_root = std::max(64, num("WFM_BAND_ROOT", 4096));
-  int resume_margin = num("WFM_RESUME_MARGIN", 26);  // (tests: a large value sends every resumed job back to score 0)
-  int debug = getenv("WFM_DEBUG") ? std::max(1, num("WFM_DEBUG", 0)) : 0;  // 0: unset
+  int resume_margin = num("WFM_RESUME_MARGIN", SNAP_ROWS);  // (tests: a large value sends every resumed job back to score 0)
+  int debug = env_debug();  // 0: unset
 };
 
 // One chunk of a level: the breakpoint jobs whose rings share the arena, and what the stages hand on about them
@@ -1073,6 +1089,7 @@ struct AlignCall {
   DevPen dp;
   const Knobs knobs;
   TileCfg tcfg;
+  BaseCfg bcfg;
   int RR;           // rows of every ring of this call
   RingRules rules;  // what plan_ring decides by: the call's, the level's (use_band, over_budget) and roots_off
   std::vector<int32_t> prob_status;  // indexed by problem id
@@ -1566,7 +1583,7 @@ int run_leaves(AlignCall& c) {
   while (!c.base_nodes.empty()) {
     retry.clear();
     const auto tb0 = std::chrono::steady_clock::now();
-    const int rc = run_base_jobs(c.h, c.S, *c.pen, c.base_nodes, retry, c.prob_status, c.prob_cells, c.tm, c.pflags);
+    const int rc = run_base_jobs(c.h, c.S, *c.pen, c.bcfg, c.base_nodes, retry, c.prob_status, c.prob_cells, c.tm, c.pflags);
     c.wall_base += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb0).count();
     if (rc != WFM_OK) return rc;
     c.base_nodes.swap(retry);
@@ -1675,6 +1692,7 @@ int align_resident_impl(wfm_handle* h, const wfm_penalties_t* pen, wfm_seqset* S
   make_roots(c);
   if ((rc = bound_roots(c)) != WFM_OK) return rc;
   c.tcfg = tile_cfg(*pen, scope);
+  c.bcfg = base_cfg(*pen);
   c.RR = ring_rows_for(scope);
   c.rules = RingRules{c.tcfg.enabled, c.tcfg.min_len, c.tcfg.min_score, c.tcfg.chunk, c.tcfg.T, c.RR, h->mem_budget, c.knobs.band_root};
 

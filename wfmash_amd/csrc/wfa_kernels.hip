@@ -196,32 +196,7 @@ __device__ __forceinline__ int imax3(int a, int b, int c) { return max(a, max(b,
 // ---------------------------------------------------------------------------
 // BiWFA breakpoint kernel
 // ---------------------------------------------------------------------------
-// Row ranges in closed form.  Score s reaches the diagonals [-s, s] (every change of diagonal costs at least e2 = 1), clipped to
-// the problem -- and, when an upper bound `sub` of the problem's score is known (a BiWFA child is handed its score by its
-// parent; a root may come with a hint), only the diagonals from which the end diagonal kinv = tl - pl is still within
-// reach: |k - kinv| <= sub - s.  A cell outside cannot lie on an alignment of score <= sub, and no cell inside depends on one
-// outside (a predecessor is one diagonal away at most and at least e2 cheaper), so the cells inside keep their exact
-// values and every breakpoint of score <= sub is found where the reference finds it: the phase-1 trigger (the running
-// maxima of the antidiagonals) can only fire LATER without the cells outside, never after a pair of cells of a real
-// overlap exists, and phase 2 tests the rows that triggered.  For a record with 1 kb end gaps this removes half the cells.
-struct Rng { int pl, tl, kb_lo, kb_hi; };  // kb_lo = kinv - sub, kb_hi = kinv + sub
-__device__ __forceinline__ Rng make_rng(int pl, int tl, int sub) { Rng r; r.pl = pl; r.tl = tl; r.kb_lo = (tl - pl) - sub; r.kb_hi = (tl - pl) + sub; return r; }
-__device__ __forceinline__ int rng_lo(const Rng& r, int s) { return max(max(-r.pl, -s), r.kb_lo + s); }
-__device__ __forceinline__ int rng_hi(const Rng& r, int s) { return min(min(r.tl, s), r.kb_hi - s); }
-// The diagonals a tile pass over the scores (s_from, s_to] has to hold: every bound at its loosest score of the block -- and
-// the score bound as it stood 25 scores BEFORE the block: the edge a score bound sets moves inwards, so the rows the block
-// starts from are wider than its own, and the snapshot it leaves behind must hold every row of the last 26 scores whole --
-// a short last block (one that stops at the meeting point after a few steps) hands rows older than its own first row to
-// phase 2, which reads each row over its full range.  (Until round 3 the bound was taken at s_from: the cells of the older
-// rows beyond it never reached the output ring, and phase 2 read whatever the ring held there.  With the slack the bounds
-// used to carry -- 56 for a child, 200 for a caller's guess -- those cells could not complete an overlap within the bound
-// and stale values of the same job never made one up; an exact bound on a small batch, where rings are reused across
-// jobs, did: a false breakpoint one point under the optimum.)
-constexpr int RNG_BACK = 25;
-__device__ __forceinline__ void rng_block(const Rng& r, int s_from, int s_to, int& L, int& R) {
-  L = max(max(-r.pl, -s_to), r.kb_lo + s_from - RNG_BACK);
-  R = min(min(r.tl, s_to), r.kb_hi - s_from + RNG_BACK);
-}
+// (row ranges in closed form, with a bound of the score: Rng / rng_lo / rng_hi / rng_block of wfa_rows.h)
 
 __device__ __forceinline__ int bp_gap_open(const DevPen& pn, int cc) {
   return (cc == C_M) ? 0 : ((cc == C_I1 || cc == C_D1) ? pn.o1 : pn.o2);
@@ -467,7 +442,7 @@ __global__ __launch_bounds__(NTMAX) void wfa_tile_reg_kernel(const uint8_t* __re
     if (CUT) rng_block(RG, sbase, s1, L, R);
     else { L = max(-J.pl, -s1); R = min(J.tl, s1); }
     const int idx = tk.core_lo, core = tk.core_hi;
-    tk.core_lo = L + idx * core;
+    tk.core_lo = L + idx * core;  // (tile_span of wfa_rows.h, spelled out: through the call the compiler forms the single-tile test below differently)
     tk.core_hi = min(R, tk.core_lo + core - 1);
     if (tk.core_lo > R) return;
     if (tk.core_lo == L && tk.core_hi == R) halo = 0;  // one tile for the whole range: nothing beside it to take from

@@ -1,7 +1,8 @@
 // wfa_plan.h -- the arithmetic of the BiWFA level driver (wfa_host.hip) that needs no device: how large a wavefront ring is, the
-// geometry of a banded ring, which ring a job gets under the memory budget (plan_ring), and how a problem's runs become its op
-// string (expand_runs).  Host only, no HIP; the CPU suite reaches it through wfmh_test_ring_plan / wfmh_test_expand_runs
-// (tests/test_ring_plan_cpu.py).
+// geometry of a banded ring, which ring a job gets under the memory budget (plan_ring), how a problem's runs become its op
+// string (expand_runs); what a chunk of the tile phase and of phase 2 launches (plan_tile_chunk, plan_p2_chunk) and which kernel a
+// base job goes to (base_kind, base_columns, plan_base_tiles).  Host only, no HIP, no getenv, no handle; the CPU suite reaches it
+// through the wfmh_test_* hooks of host/capi_host.cpp (tests/test_ring_plan_cpu.py, tests/test_tile_plan_cpu.py).
 #ifndef WFM_WFA_PLAN_H_
 #define WFM_WFA_PLAN_H_
 #include <stddef.h>
@@ -13,10 +14,9 @@
 #include <vector>
 
 #include "../../include/wfmash_hip.h"
+#include "wfa_rows.h"
 
 namespace wfm {
-
-constexpr int PLAN_SUB_NONE = 1 << 29;  // SUB_NONE of wfa_device.h (a HIP header): no upper bound of the score is known
 
 // one job of the recursion: a sub-range of a problem between two breakpoints
 struct Node {
@@ -77,12 +77,12 @@ inline RingPlan plan_ring(const Node& nd, const RingRules& r) {
   const bool tiles_take_it = p.tile_it;
   // (a root without a bound gets a guessed band only when the level would not fit otherwise: below the budget the
   // guess has nothing to win and a deep record -- 5 % divergence: 6 k scores per direction -- everything to lose)
-  const bool known = nd.score_rem != INT_MAX || nd.sub != PLAN_SUB_NONE;
+  const bool known = nd.score_rem != INT_MAX || nd.sub != SUB_NONE;
   if (r.use_band && (known || r.over_budget) && p.tile_it && !nd.noband && !(r.roots_off && nd.score_rem == INT_MAX)) {
     // scores one direction is allowed to reach
     // (a root under a bound of its score leaves the tile phase once a direction passes (bound + 128) / 2)
     int64_t dir_scores = nd.score_rem == INT_MAX ? (int64_t)r.band_root : (int64_t)nd.score_rem / 2 + 64;
-    if (nd.score_rem == INT_MAX && nd.sub != PLAN_SUB_NONE) dir_scores = std::min<int64_t>(dir_scores, ((int64_t)nd.sub + 128) / 2 + 64);
+    if (nd.score_rem == INT_MAX && nd.sub != SUB_NONE) dir_scores = std::min<int64_t>(dir_scores, ((int64_t)nd.sub + 128) / 2 + 64);
     const int64_t b = dir_scores + (int64_t)r.chunk * r.T + 16;
     const BandGeometry g = band_geometry(nd.pl, nd.tl, b);
     if (g.shift > 0 && g.width * 2 <= full_width) { p.band = (int)b; p.width = g.width; p.koff = g.koff; }  // (a band has to halve the ring)
@@ -113,6 +113,272 @@ inline RingPlan plan_ring(const Node& nd, const RingRules& r) {
     p.tile_it = tiles_take_it && ring_elems(p.width, r.RR, 2) * 4 <= r.mem_budget;
     p.need = ring_elems(p.width, r.RR, p.tile_it ? 2 : 1);
   }
+  return p;
+}
+
+// ---- cells of a job's rows ----
+// sum over the scores a .. b of the cells of a row (rng_lo .. rng_hi): the row's edges are piecewise linear in the score (each a
+// min / max of three lines), so between two consecutive kinks the count is an arithmetic series
+inline int64_t cells_sum(int pl, int tl, int sub, int a, int b) {
+  if (b < a) return 0;
+  const Rng rg = make_rng(pl, tl, sub);
+  const int64_t kinv = (int64_t)tl - pl, khi = kinv + sub, klo = kinv - sub;
+  // scores at which two of the lines of an edge cross (the kink lies between the floor and the next integer)
+  int64_t cand[16];
+  int nc = 0;
+  auto add = [&](int64_t x) { for (int64_t y : {x, x + 1}) if (y > a && y <= b) cand[nc++] = y; };
+  add(tl); add(khi / 2 - (khi < 0 && (khi & 1) ? 1 : 0)); add(khi - tl);     // hi: s vs tl, s vs khi - s, tl vs khi - s
+  add(pl); add((-klo) / 2 - (-klo < 0 && ((-klo) & 1) ? 1 : 0)); add(-klo - pl);  // lo: -s vs -pl, -s vs klo + s, -pl vs klo + s
+  std::sort(cand, cand + nc);
+  int64_t total = 0;
+  int64_t u = a;
+  auto cells = [&](int64_t s) { return (int64_t)rng_hi(rg, (int)s) - rng_lo(rg, (int)s) + 1; };
+  auto seg = [&](int64_t x, int64_t y) {  // linear on [x, y]
+    if (y < x) return;
+    const int64_t cx = cells(x), cy = cells(y);
+    if (cx <= 0 && cy <= 0) return;
+    if (cx > 0 && cy > 0) { total += (cx + cy) * (y - x + 1) / 2; return; }
+    if (y == x) { total += std::max<int64_t>(cx, 0); return; }
+    // one end at or below zero: the slope is (cy - cx) / (y - x), an integer (each edge moves by whole diagonals per score)
+    const int64_t slope = (cy - cx) / (y - x);
+    if (cx > 0) {  // falls: positive up to x + (cx - 1) / -slope
+      const int64_t last = x + (cx - 1) / (-slope);
+      total += (cx + cells(last)) * (last - x + 1) / 2;
+    } else {       // rises: positive from y - (cy - 1) / slope
+      const int64_t first = y - (cy - 1) / slope;
+      total += (cells(first) + cy) * (y - first + 1) / 2;
+    }
+  };
+  for (int q = 0; q < nc; ++q) {
+    if (cand[q] <= u) continue;
+    seg(u, cand[q] - 1);
+    u = cand[q];
+  }
+  seg(u, b);
+  return total;
+}
+
+// ---- a chunk of the tile phase (run_tiled_phase): `chunk` blocks of T scores launched back to back ----
+// what the planner needs of a job (TileJob's fields of the same names); jobs that are not active get no tile
+struct TilePlanJob { int pl, tl, sub, s0, mode, fine_s, packed, active; };
+struct TilePlanRules {
+  int threads = 512, C = 2, T = 100, chunk = 2;
+  int core = 0;            // diagonals of a tile with a halo: Wt - 2 T
+  bool reg = true;         // register tiles (TileCfg::reg)
+  bool fine = true;        // WFM_TILE_FINE: every block of a single-tile chunk gets the workgroup size its own widest range needs
+  bool coarse_on = false;  // the packed kernel keeps one maximum per block below a job's fine_s
+};
+struct TileChunkPlan {
+  std::vector<int> threads_b, variants_b;  // per block of the chunk: workgroup size; instantiations of the packed kernel (1 without per-score maxima, 2 with)
+  int core_c = 0;                          // diagonals a tile owns
+  std::vector<TileTask> tasks, tasks_by;   // tasks: the packed jobs' tiles, then (once the plan is complete) the byte kernel's, which tasks_by collects
+  size_t n_pk = 0;                         // tiles of packed jobs: tasks[0 .. n_pk)
+};
+
+// A job leaves the tile phase before a chunk (mode 3; it is run again): on a narrow ring (band > 0) when the chunk's last score
+// no longer fits it -- and under a score bound that is a guess: the two directions meet near half the score, so a job still going
+// well past half the bound has a score above it; or nothing is left within the bound.
+inline bool tile_job_leaves(int pl, int tl, int sub, int s0, int band, int chunk, int T) {
+  if (band > 0 && s0 + chunk * T + 2 > band) return true;
+  if (sub == SUB_NONE) return false;
+  int L, R;
+  rng_block(make_rng(pl, tl, sub), s0, s0 + T, L, R);
+  return 2 * s0 > sub + 128 || R < L;
+}
+
+// While the widest range of a chunk fits one tile, every job-direction is ONE tile without a halo, and the workgroups are only
+// as large as that range needs: whole waves, C diagonals per lane
+inline bool fits_one_tile(int widest, int threads, int C) { return widest <= threads * C; }
+inline int one_tile_threads(int widest, int threads, int C) { return std::min(threads, std::max(64, ((widest + C - 1) / C + 63) / 64 * 64)); }
+
+// the tiles of one direction of a job: packed jobs' (wfa_tile2_kernel) apart from the others' (an N, soft-masked bases: the byte
+// kernel), which go behind them.  A task is (tile index, tile width): the kernel places it (tile_span)
+inline void append_tile_tasks(TileChunkPlan& p, int job, int dir, int ntiles, int core, bool packed) {
+  std::vector<TileTask>& to = packed ? p.tasks : p.tasks_by;
+  for (int t = 0; t < ntiles; ++t) to.push_back(TileTask{(int32_t)job, dir, t, core});
+}
+inline void close_task_list(TileChunkPlan& p) {
+  p.n_pk = p.tasks.size();
+  p.tasks.insert(p.tasks.end(), p.tasks_by.begin(), p.tasks_by.end());
+}
+
+inline void plan_tile_chunk(const TilePlanJob* jobs, size_t n, const TilePlanRules& r, TileChunkPlan& p) {
+  const int chunk = r.chunk, T = r.T;
+  auto block_range = [&](const TilePlanJob& j, int b, int& L, int& R) { rng_block(make_rng(j.pl, j.tl, j.sub), j.s0 + b * T, j.s0 + (b + 1) * T, L, R); };
+  // as many tiles of `core` diagonals per job and direction as the last block of this chunk can need
+  p.tasks.clear(); p.tasks_by.clear();
+  p.core_c = r.core;
+  p.threads_b.assign((size_t)chunk, r.threads);
+  if (r.reg && r.C == 2) {
+    std::vector<int> wb((size_t)chunk, 0);  // widest range per block
+    for (size_t i = 0; i < n; ++i) {
+      if (!jobs[i].active) continue;
+      // a job may run the same block twice (the block in which its wavefronts met, up to the meeting point), and with a
+      // score bound the ranges shrink again towards the end: block b of the chunk needs the widest range up to b
+      int wmax = 0;
+      for (int b = 0; b < chunk; ++b) {
+        int L, R;
+        block_range(jobs[i], b, L, R);
+        wmax = std::max(wmax, R - L + 1);
+        wb[(size_t)b] = std::max(wb[(size_t)b], wmax);
+      }
+    }
+    if (fits_one_tile(wb[(size_t)chunk - 1], r.threads, r.C)) {
+      for (int b = 0; b < chunk; ++b) {
+        const int wdt = r.fine ? wb[(size_t)b] : wb[(size_t)chunk - 1];
+        p.threads_b[(size_t)b] = r.fine ? one_tile_threads(wdt, r.threads, r.C) : std::min(r.threads, wdt <= 256 ? 128 : (wdt <= 512 ? 256 : r.threads));
+      }
+      p.core_c = p.threads_b[(size_t)chunk - 1] * r.C;
+    }
+  }
+  for (size_t i = 0; i < n; ++i) {
+    if (!jobs[i].active) continue;
+    int ntiles = 0;  // of the widest block of the chunk
+    for (int b = 0; b < chunk; ++b) {
+      int L, R;
+      block_range(jobs[i], b, L, R);
+      ntiles = std::max(ntiles, tiles_for(L, R, p.core_c));
+    }
+    for (int d = 0; d < 2; ++d) append_tile_tasks(p, (int)i, d, ntiles, p.core_c, jobs[i].packed != 0);
+  }
+  close_task_list(p);
+  // which instantiations of the packed kernel a block of the chunk can have tiles for (wfa_tile2_kernel, FINE): the one without per-score
+  // maxima always (the blocks before a job's meeting block and the run up to the meeting point); the one with them where a job that simply
+  // moved on has reached its fine_s, and in the chunk's first block for the jobs the last chunk left in mode 5
+  p.variants_b.assign((size_t)chunk, r.coarse_on ? 0 : 2);
+  if (!r.coarse_on) return;
+  for (size_t i = 0; i < n; ++i) {
+    const TilePlanJob& j = jobs[i];
+    if (!j.active || !(j.packed & 1)) continue;
+    for (int b = 0; b < chunk; ++b) {
+      const bool reaches = (int64_t)j.s0 + (int64_t)(b + 1) * T >= (int64_t)j.fine_s;
+      if ((j.mode == 5 && b == 0) || (j.mode == 0 && reaches)) p.variants_b[(size_t)b] |= 2;
+      // without maxima: a job that simply moved on and is still below its fine_s (it may also have met meanwhile: its run up to the meeting
+      // point needs no maxima either -- and is taken by the FINE instantiation where that one is launched alone)
+      if (j.mode == 0 && !reaches) p.variants_b[(size_t)b] |= 1;
+    }
+  }
+  for (int b = 0; b < chunk; ++b) if (!p.variants_b[(size_t)b]) p.variants_b[(size_t)b] = 2;  // (only runs up to a meeting point: either would do)
+}
+
+// ---- a chunk of phase 2 from rows computed ahead (run_p2_phase): P2K more rows of both directions of every job ----
+struct P2PlanJob { int pl, tl, sub, sf, sr, packed; };  // sf / sr: the scores the directions stand at (BpJob::resume_s / resume_sr)
+struct P2Geometry {
+  int koff2; size_t w2, nblk;   // the job's P2 rows: column = k + koff2, w2 columns, nblk blocks of 64 diagonals
+  size_t p2_off, bm_off;        // element offsets of its rows and of its block maxima
+};
+struct P2ChunkPlan {
+  std::vector<P2Geometry> geo;  // of the jobs the chunk takes: candidates i0 .. i0 + geo.size()
+  size_t elems = 0, bm_elems = 0, maxw2 = 0;
+  int threads_c = 0;
+  TileChunkPlan tiles;          // (core_c, tasks, n_pk; jobs are numbered within the chunk)
+};
+// rows: P2K, rows_bm: P2ROWS (wfa_device.h); budget: bytes the rows of a chunk may take; core: Wt - 2 P2K
+inline void plan_p2_chunk(const P2PlanJob* cand, size_t n_cand, size_t i0, int rows, int rows_bm, size_t budget, int threads, int core, P2ChunkPlan& p) {
+  p.geo.clear(); p.elems = 0; p.bm_elems = 0; p.maxw2 = 0;
+  p.tiles.tasks.clear(); p.tiles.tasks_by.clear();
+  for (size_t i = i0; i < n_cand; ++i) {
+    const P2PlanJob& j = cand[i];
+    const int reach = std::max(j.sf, j.sr) + rows;
+    int L, R;  // every diagonal a row of the window can hold: the snapshot's rows (26 back) and the rows computed ahead
+    rng_block(make_rng(j.pl, j.tl, j.sub), std::max(0, std::min(j.sf, j.sr) - P2_BACK), reach, L, R);
+    if (R < L) { L = 0; R = 0; }
+    P2Geometry g;
+    g.koff2 = ((-L + 4) + 3) & ~3;  // column of diagonal 0: a multiple of 4, >= 4 columns of margin
+    g.w2 = ((size_t)(R + g.koff2 + 8) + 3) & ~(size_t)3;
+    g.nblk = (g.w2 >> 6) + 1;
+    const size_t need = g.w2 * 2 * 5 * rows, need_bm = g.nblk * 2 * rows_bm * 5;
+    if (!p.geo.empty() && (p.elems + need + 2 * (p.bm_elems + need_bm)) * 4 > budget) break;
+    p.maxw2 = std::max(p.maxw2, g.w2);
+    g.p2_off = p.elems; g.bm_off = p.bm_elems;
+    p.bm_elems += need_bm;
+    p.elems += need;
+    p.geo.push_back(g);
+  }
+  const size_t n = p.geo.size();
+  auto dir_range = [&](const P2PlanJob& j, int d, int& L, int& R) { rng_block(make_rng(j.pl, j.tl, j.sub), d == 0 ? j.sf : j.sr, (d == 0 ? j.sf : j.sr) + rows, L, R); };
+  // one tile without a halo per job-direction while the widest range of the chunk fits one
+  p.threads_c = threads; p.tiles.core_c = core;
+  int widest = 0;
+  for (size_t q = 0; q < n; ++q)
+    for (int d = 0; d < 2; ++d) {
+      int L, R;
+      dir_range(cand[i0 + q], d, L, R);
+      widest = std::max(widest, R - L + 1);
+    }
+  if (fits_one_tile(widest, threads, 2)) {
+    p.threads_c = one_tile_threads(widest, threads, 2);
+    p.tiles.core_c = p.threads_c * 2;
+  }
+  for (size_t q = 0; q < n; ++q)
+    for (int d = 0; d < 2; ++d) {
+      int L, R;
+      dir_range(cand[i0 + q], d, L, R);
+      append_tile_tasks(p.tiles, (int)q, d, tiles_for(L, R, p.tiles.core_c), p.tiles.core_c, cand[i0 + q].packed != 0);
+    }
+  close_task_list(p.tiles);
+}
+
+// ---- base jobs (run_base_jobs) ----
+// The diagonals a base job's rows have to hold under its score budget: within `smax` of where an alignment may begin (diagonal 0 of an
+// end-to-end job, [-pbf, tbf] of an ends-free one) -- and, when the alignment has to END in the far corner (no free ends there: leaves, and the
+// head patches, whose free ends are at the beginning), within `smax` of the corner's diagonal tl - pl as well: every change of diagonal costs at least
+// e2 = 1, so a cell further away lies on no alignment of score <= smax, no cell on such an alignment takes its value from one (the argument of the
+// score bounds, section 5 of DESIGN.md), and a job that needs more than its budget is run again anyway.  A head patch begins with ALL its diagonals
+// (its begin-free lengths are the eroded lengths: rows of 2 - 8 k diagonals for a budget of 256); with the corner's band its rows are 513 wide.
+// pbf / pef / tbf / tef: the problem's free ends (ends-free jobs); corner_band: WFM_BASE_CORNER_BAND
+inline void base_columns(const Node& nd, int pbf, int pef, int tbf, int tef, bool corner_band, int64_t* kmin_out, int64_t* kmax_out) {
+  int64_t kmin = nd.endsfree ? std::max<int64_t>(-nd.pl, -(int64_t)pbf - nd.smax) : std::max<int64_t>(-nd.pl, -nd.smax);
+  int64_t kmax = nd.endsfree ? std::min<int64_t>(nd.tl, (int64_t)tbf + nd.smax) : std::min<int64_t>(nd.tl, nd.smax);
+  const bool end_fixed = !nd.endsfree || (pef == 0 && tef == 0);
+  if (corner_band && end_fixed) {
+    const int64_t k_end = (int64_t)nd.tl - nd.pl;
+    const int64_t bmin = std::max(kmin, k_end - nd.smax), bmax = std::min(kmax, k_end + nd.smax);
+    // the first row must keep a cell inside (a budget that cannot reach the corner at all leaves the columns as they were: the job overflows as before)
+    const int64_t lo0 = nd.endsfree ? std::max<int64_t>(-(int64_t)pbf, bmin) : 0, hi0 = nd.endsfree ? std::min<int64_t>((int64_t)tbf, bmax) : 0;
+    if (bmin <= bmax && lo0 <= hi0 && lo0 >= bmin && hi0 <= bmax) { kmin = bmin; kmax = bmax; }
+  }
+  *kmin_out = kmin; *kmax_out = kmax;
+}
+
+// Kinds of base jobs, each in launches of its own: 0 / 1 / 2 = the register kernel on packed sequences (wfa_base2_kernel: default
+// penalties, pure ACGT, rows up to 128 / 512 / 2048 diagonals, sequences that fit its windows), 3 / 4 = the ring kernel with
+// 256 / 1024 threads (other penalties, an N, wider rows: a patch eroded to its 4096-base limit starts 8 k diagonals wide),
+// 5 = the register kernel's step on tiles (wfa_base2t_kernel): rows beyond 2048 diagonals of jobs the register kernel would take -- the third
+// attempt of a patch, whose score passed 1020.
+// (Sequences longer than the register kernel's LDS windows are fine: what lies beyond is read from the global mirror.  Jobs without
+// any cell -- an empty pattern or text -- ride along with kind 1: they are one store each)
+struct BaseRules {
+  bool base_v2 = true;       // default penalties, and neither WFM_BASE_V2=0 nor WFM_TILE_V2=0
+  bool base_tiles = true;    // WFM_BASE_TILES != 0
+  bool force_tiles = false;  // WFM_BASE_TILES=2 (tests): every leaf and patch with rows beyond 128 diagonals
+  bool few_jobs = false;     // fewer than 128 jobs in the call
+  int wide_from = 2048;      // rows beyond this get 1024 threads of the ring kernel (512 when the launch is too small to fill the device anyway)
+};
+// width: the job's widest row (0 for the all-gap jobs); acgt: the problem's sequences are pure upper-case ACGT
+inline int base_kind(int64_t width, int pl, int tl, int tries, bool acgt, const BaseRules& r) {
+  if (r.base_v2 && (pl == 0 || tl == 0)) return 1;
+  if (r.base_v2 && width <= 2048 && acgt)
+    // (a handful of retries: more workgroups of fewer waves per job on the tiles of the register kernel, and ONE launch with the wider ones
+    // instead of one per width class, each a few jobs and hundreds of score steps long)
+    return width <= 128 ? 0 : (r.base_tiles && (r.force_tiles || (r.few_jobs && (tries > 0 || width > 640))) ? 5 : (width <= 640 ? 1 : 2));
+  if (r.base_v2 && r.base_tiles && acgt) return 5;
+  return width > r.wide_from ? 4 : 3;
+}
+
+// base jobs on tiles: blocks of T scores; a tile is a workgroup of `threads` with two diagonals per lane that owns `core` diagonals
+// and computes T columns of halo on either side for itself
+struct BaseTilePlan { int core = 0, nblocks = 0; std::vector<int> ntiles; };
+inline BaseTilePlan plan_base_tiles(const int32_t* width, const int32_t* smax, size_t n, int T, int threads) {
+  BaseTilePlan p;
+  p.core = threads * 2 - 2 * T;
+  p.ntiles.resize(n);
+  int smax_all = 0;
+  for (size_t q = 0; q < n; ++q) {
+    p.ntiles[q] = (width[q] + p.core - 1) / p.core;
+    smax_all = std::max(smax_all, smax[q]);
+  }
+  p.nblocks = (smax_all + T - 1) / T + 1;
   return p;
 }
 

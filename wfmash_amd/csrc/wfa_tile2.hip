@@ -66,16 +66,6 @@ __device__ __forceinline__ void lds_barrier() {
 struct __attribute__((packed, aligned(4))) Pair32 { int x, y; };
 __device__ __forceinline__ void ld_pair(const int32_t* p, int& a, int& b) { const Pair32 v = *reinterpret_cast<const Pair32*>(p); a = v.x; b = v.y; }
 __device__ __forceinline__ void st_pair(int32_t* p, int a, int b) { Pair32 v; v.x = a; v.y = b; *reinterpret_cast<Pair32*>(p) = v; }
-struct Rng2 { int pl, tl, kb_lo, kb_hi; };
-__device__ __forceinline__ Rng2 make_rng2(int pl, int tl, int sub) { Rng2 r; r.pl = pl; r.tl = tl; r.kb_lo = (tl - pl) - sub; r.kb_hi = (tl - pl) + sub; return r; }
-__device__ __forceinline__ int rng2_lo(const Rng2& r, int s) { return max(max(-r.pl, -s), r.kb_lo + s); }
-__device__ __forceinline__ int rng2_hi(const Rng2& r, int s) { return min(min(r.tl, s), r.kb_hi - s); }
-constexpr int RNG2_BACK = 25;  // = RNG_BACK of wfa_kernels.hip
-__device__ __forceinline__ void rng2_block(const Rng2& r, int s_from, int s_to, int& L, int& R) {
-  L = max(max(-r.pl, -s_to), r.kb_lo + s_from - RNG2_BACK);
-  R = min(min(r.tl, s_to), r.kb_hi - s_from + RNG2_BACK);
-}
-
 __device__ __forceinline__ int rdl(int v, int src) { return __builtin_amdgcn_readlane(v, src); }
 
 // lane i <- lane i - 1 (lane 0 keeps NULL) / lane i <- lane i + 1 (lane 63 keeps NULL): one VALU instruction each
@@ -382,15 +372,15 @@ __global__ __launch_bounds__(NTMAX) void wfa_tile2_kernel(const uint32_t* __rest
   if (!J.active) return;
   // score of the snapshot this direction starts from (mode 6: the block before the job's s0 once more, from the snapshot before it -- TileJob::ring_prev)
   const int sbase = P2 ? (tk.dir == 0 ? J.tf : J.tr) : (J.mode == 6 ? J.s0 - T : J.s0);
-  const Rng2 RG = make_rng2(J.pl, J.tl, J.sub);
+  const Rng RG = make_rng(J.pl, J.tl, J.sub);
   const bool lowdiv = (J.packed & 2) != 0;  // near-identical sequences: the job's known score is under a sixteenth of its length (the host says: pk_extend2, tail_direct)
   int halo = T;  // columns computed on either side of the core (the trapezoid loses one per step)
   {
     const int s1 = sbase + T;
     int L, R;
-    rng2_block(RG, sbase, s1, L, R);
+    rng_block(RG, sbase, s1, L, R);
     const int idx = tk.core_lo, core = tk.core_hi;
-    tk.core_lo = L + idx * core;
+    tk.core_lo = L + idx * core;  // (tile_span of wfa_rows.h, spelled out: through the call the compiler forms the single-tile test below differently)
     tk.core_hi = min(R, tk.core_lo + core - 1);
     if (tk.core_lo > R) return;
     if (tk.core_lo == L && tk.core_hi == R) halo = 0;  // one tile for the whole range: nothing beside it to take from
@@ -448,7 +438,7 @@ __global__ __launch_bounds__(NTMAX) void wfa_tile2_kernel(const uint32_t* __rest
 #pragma unroll
         for (int e = 0; e < DEP; ++e) Mh[c][r][e] = WF_NULL;
     auto ld_row = [&](int comp, int sc, int& a, int& b) {
-      const int lo = rng2_lo(RG, sc), hi = rng2_hi(RG, sc);
+      const int lo = rng_lo(RG, sc), hi = rng_hi(RG, sc);
       const bool ok0 = kin0 && sc >= 0 && k0 >= lo && k0 <= hi, ok1 = kin1 && sc >= 0 && k0 + 1 >= lo && k0 + 1 <= hi;
       int x = WF_NULL, y = WF_NULL;
       if (ok0 || ok1) ld_pair(rin + ((int64_t)(comp * RING + (sc & RMASK))) * width + k0, x, y);
@@ -881,7 +871,7 @@ __global__ __launch_bounds__(NTMAX) void wfa_tile2_kernel(const uint32_t* __rest
       if (!incore[c]) continue;
       for (int d = Tn; d < H; ++d) {
         const int sc = s_end - d;
-        if (sc < 0 || k < rng2_lo(RG, sc) || k > rng2_hi(RG, sc)) continue;
+        if (sc < 0 || k < rng_lo(RG, sc) || k > rng_hi(RG, sc)) continue;
         const int64_t ro = ((int64_t)(sc & RMASK)) * width + k;
         rout[(int64_t)C_I1 * RING * width + ro] = rin[(int64_t)C_I1 * RING * width + ro];
         rout[(int64_t)C_I2 * RING * width + ro] = rin[(int64_t)C_I2 * RING * width + ro];
@@ -900,7 +890,7 @@ __global__ __launch_bounds__(NTMAX) void wfa_tile2_kernel(const uint32_t* __rest
       const int back = ((tr - r) % NCL + NCL) % NCL;     // s_end - (newest score of class r)
       const int e = (d - back) / NCL;
       const int sc = s_end - d;
-      const int lo = rng2_lo(RG, sc), hi = rng2_hi(RG, sc);
+      const int lo = rng_lo(RG, sc), hi = rng_hi(RG, sc);
       const bool w0 = incore[0] && sc >= 0 && k0 >= lo && k0 <= hi, w1 = incore[1] && sc >= 0 && k0 + 1 >= lo && k0 + 1 <= hi;
       int32_t* dst = rout + ((int64_t)(C_M * RING + (sc & RMASK))) * width + k0;
       // (a lane's two diagonals as one 8-byte store wherever both are the core's and inside the row: all lanes but a handful at the edges)

@@ -150,6 +150,78 @@ int wfmh_test_expand_runs(const uint32_t* runs, int n, const wfm_penalties_t* pe
   return rc;
 }
 
+// test hook: the row arithmetic of csrc/wfa_rows.h and csrc/wfa_plan.h, n queries of 7 numbers (op, then its arguments), two results each.
+// op 0: cells_sum(pl, tl, sub, a, b); 1: rng_block(pl, tl, sub, s_from, s_to) -> L, R; 2: tile_span(L, R, idx, core) -> lo, hi;
+// 3: tiles_for(L, R, core); 4: tile_job_leaves(pl, tl, sub, s0, band, chunk) with T = 100, 5: the same with T = 32
+int wfmh_test_rows(const int32_t* q, int64_t n, int64_t* out) {
+  for (int64_t i = 0; i < n; ++i, q += 7, out += 2) {
+    int a = 0, b = 0;
+    out[0] = out[1] = 0;
+    switch (q[0]) {
+      case 0: out[0] = wfm::cells_sum(q[1], q[2], q[3], q[4], q[5]); break;
+      case 1: wfm::rng_block(wfm::make_rng(q[1], q[2], q[3]), q[4], q[5], a, b); out[0] = a; out[1] = b; break;
+      case 2: wfm::tile_span(q[1], q[2], q[3], q[4], &a, &b); out[0] = a; out[1] = b; break;
+      case 3: out[0] = wfm::tiles_for(q[1], q[2], q[3]); break;
+      case 4: case 5: out[0] = wfm::tile_job_leaves(q[1], q[2], q[3], q[4], q[5], q[6], q[0] == 4 ? 100 : 32); break;
+      default: return -1;
+    }
+  }
+  return 0;
+}
+
+// test hook: plan_tile_chunk (csrc/wfa_plan.h).  jobs: n x (pl, tl, sub, s0, mode, fine_s, packed, active); rules: threads, C, T, chunk, core, reg,
+// fine, coarse_on.  per_block: threads_b then variants_b (chunk each); tasks: (job, dir, tile, core) each, at most tasks_cap of them are written;
+// scalars = {core_c, tasks, n_pk}
+int wfmh_test_tile_plan(const int32_t* jobs, int64_t n, const int32_t* rules, int32_t* per_block, int32_t* tasks, int64_t tasks_cap, int64_t* scalars) {
+  static_assert(sizeof(wfm::TilePlanJob) == 8 * sizeof(int32_t) && sizeof(wfm::TileTask) == 4 * sizeof(int32_t), "the hooks copy these as rows of int32");
+  wfm::TilePlanRules r{rules[0], rules[1], rules[2], rules[3], rules[4], rules[5] != 0, rules[6] != 0, rules[7] != 0};
+  if (r.chunk < 1 || r.T < 1 || r.threads < 1 || r.C < 1 || r.core < 1) return -1;
+  wfm::TileChunkPlan p;
+  wfm::plan_tile_chunk(reinterpret_cast<const wfm::TilePlanJob*>(jobs), (size_t)n, r, p);
+  std::copy(p.threads_b.begin(), p.threads_b.end(), per_block);
+  std::copy(p.variants_b.begin(), p.variants_b.end(), per_block + r.chunk);
+  memcpy(tasks, p.tasks.data(), std::min<size_t>(p.tasks.size(), (size_t)tasks_cap) * sizeof(wfm::TileTask));
+  scalars[0] = p.core_c; scalars[1] = (int64_t)p.tasks.size(); scalars[2] = (int64_t)p.n_pk;
+  return 0;
+}
+
+// test hook: plan_p2_chunk (csrc/wfa_plan.h) with P2K = rows and P2ROWS = rows_bm.  cand: n x (pl, tl, sub, sf, sr, packed); geo: per job taken
+// (koff2, w2, nblk, p2_off, bm_off); scalars = {jobs taken, elems, bm_elems, maxw2, threads_c, core_c, tasks, n_pk}
+int wfmh_test_p2_plan(const int32_t* cand, int64_t n, int64_t i0, int rows, int rows_bm, unsigned long long budget, int threads, int core, int64_t* geo,
+                      int32_t* tasks, int64_t tasks_cap, int64_t* scalars) {
+  static_assert(sizeof(wfm::P2PlanJob) == 6 * sizeof(int32_t), "the hook copies these as rows of int32");
+  if (i0 < 0 || i0 >= n || rows < 1 || threads < 1 || core < 1) return -1;
+  wfm::P2ChunkPlan p;
+  wfm::plan_p2_chunk(reinterpret_cast<const wfm::P2PlanJob*>(cand), (size_t)n, (size_t)i0, rows, rows_bm, (size_t)budget, threads, core, p);
+  for (size_t q = 0; q < p.geo.size(); ++q) {
+    const wfm::P2Geometry& g = p.geo[q];
+    const int64_t v[5] = {g.koff2, (int64_t)g.w2, (int64_t)g.nblk, (int64_t)g.p2_off, (int64_t)g.bm_off};
+    std::copy(v, v + 5, geo + 5 * q);
+  }
+  memcpy(tasks, p.tiles.tasks.data(), std::min<size_t>(p.tiles.tasks.size(), (size_t)tasks_cap) * sizeof(wfm::TileTask));
+  const int64_t v[8] = {(int64_t)p.geo.size(), (int64_t)p.elems, (int64_t)p.bm_elems, (int64_t)p.maxw2, p.threads_c, p.tiles.core_c,
+                        (int64_t)p.tiles.tasks.size(), (int64_t)p.tiles.n_pk};
+  std::copy(v, v + 8, scalars);
+  return 0;
+}
+
+// test hook: the base jobs' planners (csrc/wfa_plan.h).  op 0: base_kind -- in = n x (width, pl, tl, tries, acgt, base_v2, base_tiles, force_tiles,
+// few_jobs, wide_from), out = the kind of each; op 1: plan_base_tiles -- in = T, threads, then n x (width, smax), out = core, nblocks, then ntiles of each
+int wfmh_test_base_plan(int op, const int32_t* in, int64_t n, int32_t* out) {
+  if (op == 0) {
+    for (int64_t i = 0; i < n; ++i, in += 10)
+      out[i] = wfm::base_kind(in[0], in[1], in[2], in[3], in[4] != 0, wfm::BaseRules{in[5] != 0, in[6] != 0, in[7] != 0, in[8] != 0, in[9]});
+    return 0;
+  }
+  if (op != 1 || in[0] < 1 || in[1] * 2 <= 2 * in[0]) return -1;
+  std::vector<int32_t> width((size_t)n), smax((size_t)n);
+  for (int64_t i = 0; i < n; ++i) { width[(size_t)i] = in[2 + 2 * i]; smax[(size_t)i] = in[3 + 2 * i]; }
+  const wfm::BaseTilePlan p = wfm::plan_base_tiles(width.data(), smax.data(), (size_t)n, in[0], in[1]);
+  out[0] = p.core; out[1] = p.nblocks;
+  std::copy(p.ntiles.begin(), p.ntiles.end(), out + 2);
+  return 0;
+}
+
 char* wfmh_test_cigar(const char* fn, const char* a, const char* b, const char* query, const char* target,
                       long long i0, long long i1) {
   std::string f = fn ? fn : "", sa = a ? a : "", sb = b ? b : "", q = query ? query : "", t = target ? target : "";
