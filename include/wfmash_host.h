@@ -250,6 +250,19 @@ int wfmh_map_multi(wfm_handle_t* const* handles, int n, const char* target_fasta
  * lengths[0 .. n) goes to.  Returns 0 or WFM_E_ARG. */
 int wfmh_test_deal(const int64_t* lengths, int64_t n, int n_parts, int32_t* out_part);
 
+/* Test hook (no GPU needed): what the map driver decides without a device (wfmash_amd/host/map_plan.hpp), on in[0 .. n).
+ * The caller sizes out for the op.  Returns 0 or WFM_E_ARG.
+ *   0  layout_fragments: in = len, w, base, first_frag; out = nfrag, then the offsets
+ *   1  target_subsets:   in = batch, then the targets' lengths; out = the number of subsets, then their sizes (the targets in order)
+ *   2  plan_batch:       in = batch_bases, qi, then the queries' lengths (<= 0: missing or empty); out = next, in_place, n_bases,
+ *                        the number of members, then the members
+ *   3  in = n_handles, query_bp, nfrag, subset_size; out = batch_bases_for, mapping_cap, spare_hint, then the constants
+ *                        kBatchBases, kCopyBases, kEarlyFilterFrags, kSpareMappings
+ *   4  split_by_query:   in = nq, (first_frag, nfrag) per query, then mfrag per mapping; out = first_map[0 .. nq]
+ *   5  query_results:    in = first_frag, w, m0, nq, threads, has_perm, n_maps, then mfrag, perm and queryStartPos per mapping;
+ *                        out = orig's size, per result the mapping it was and its queryStartPos (nq each), then orig */
+int wfmh_test_map_plan(int op, const int64_t* in, int64_t n, int64_t* out);
+
 /* External seeds (-K, parse_args.hpp:78,771-773; skch::ExternalSeeder, src/map/include/externalSeeder.hpp) in place of the
  * MinHash mapper: the PAF records of another tool (seeds_paf; "-" or "/dev/stdin" = standard input) grouped by query, each query's
  * through the group plane sweep, sparsification and the scaffold filter, written as a mapping PAF (the -m / -i hand-off file) to
@@ -266,6 +279,10 @@ int wfmh_seed_paf(const char* target_fasta, const char* query_fasta, const char*
  * (malloc'd; wfmh_free).  fasta: the file whose .fai (or the FASTA itself) defines the sequences. */
 char* wfmh_test_filter(const char* stage, const wfm_mapping_t* maps, int64_t n, const char* fasta,
                        const char* query_name, const wfmh_map_params_t* prm);
+/* The same for stage "subset" with the mappings given in chaining order, as the map driver builds them from the device's
+ * permutation: orig[i] = the position maps[i] has in fragment order (filterSubsetMappings' presorted_orig). */
+char* wfmh_test_filter_ordered(const char* stage, const wfm_mapping_t* maps, int64_t n, const uint32_t* orig, const char* fasta,
+                               const char* query_name, const wfmh_map_params_t* prm);
 
 /* Test hook for the FASTA reader that stands in for faigz/htslib (src/common/faigz.h:221-505;
  * random access through .fai, and .gzi for BGZF).  name == NULL: "indexed|in-memory" + one

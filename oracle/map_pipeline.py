@@ -48,9 +48,10 @@ def fragments(seq_len, w):
 
 
 def map_queries(seqs, pct_identity, k=15, w=1000, s=None, minimum_hits=3, max_kmer_freq=0.0002, add_minmers=None,
-                skip_self=True, skip_prefix=True, lower_triangular=False, kc_threshold=0.0, queries=None):
+                skip_self=True, skip_prefix=True, lower_triangular=False, kc_threshold=0.0, queries=None, targets=None):
     """seqs: list of (name, bytes) in file order (all-vs-all).  Returns {query index: MAPPING_DTYPE array} of raw L2
-    mappings (after processFragment's query offset, before the boundary check), and the group table."""
+    mappings (after processFragment's query offset, before the boundary check), and the group table.
+    targets: the indexes of the sequences that are indexed (one target subset of -b); None: all."""
     names = [n for n, _ in seqs]
     group = ref_groups(names) if skip_prefix else ref_groups(names, "")
     S = s or sketch_size(pct_identity, w, k)
@@ -60,7 +61,7 @@ def map_queries(seqs, pct_identity, k=15, w=1000, s=None, minimum_hits=3, max_km
         add_minmers = lambda sq, sid: pymap.ref_add_minmers(sq, k, w, S, sid)
     mm = []
     for sid, (_, sq) in enumerate(seqs):
-        if len(sq) >= w:
+        if len(sq) >= w and (targets is None or sid in targets):
             mm += [(int(x["hash"]), int(x["wpos"]), int(x["wpos_end"]), int(x["seqId"]), int(x["strand"])) for x in add_minmers(sq, sid)]
     lookup, index, _ = MI.build_index(mm, max_kmer_freq)
     mh = [0] + [max(minimum_hits, MS.estimate_minimum_hits_relaxed(q, k, pi, 0.95)) for q in range(1, S + 1)]

@@ -44,6 +44,43 @@ def test_filter_subset_matches_reference_golden(fai, case):
         assert capi.host_filter("onetoone", m, fai, query, P) == GOLDEN[name]["onetoone"]
 
 
+def _chaining_order(m, query):
+    """-> (the stable permutation into (target, strand, query position, target position) order, whether two neighbours there tie);
+    keys as the boundary check leaves them, strand -1 (reverse) before +1 as chain_mappings compares them"""
+    tlen = np.array([l for _, l in FC.NAMES], dtype=np.int64)
+    ref = m["refSeqId"].astype(np.int64)
+    strand = np.where(m["flags"] & 1, -1, 1)
+    q = np.minimum(m["queryStartPos"].astype(np.int64), dict(FC.NAMES)[query])
+    r = np.minimum(m["refStartPos"].astype(np.int64), tlen[ref] - 1) if len(m) else ref
+    order = np.lexsort((r, q, strand, ref))  # (stable; the last key is the first compared)
+    keys = np.stack([ref, strand, q, r], axis=1)[order]
+    return order, bool(len(m) >= 2 and (keys[1:] == keys[:-1]).all(axis=1).any())
+
+
+def _ordered_cases():
+    """every case of filter_cases, and one more whose keys tie: the first case with one of its mappings twice"""
+    name, query, seed, over = FC.CASES[0]
+    m = FC.make_mappings(name, query, seed, over)
+    return list(FC.CASES) + [("defaults_twice", query, seed, over)], {"defaults_twice": np.concatenate([m, m[7:8]])}
+
+
+def test_filter_subset_in_device_order_matches_reference_golden(fai):
+    """filterSubsetMappings with the mappings in chaining order and their places in fragment order beside them, as the map driver
+    hands them over from the device's sort: without ties chain_mappings takes the order and skips its own sort, with a tie it
+    refuses it and puts the mappings back -- either way the text is the one of the mappings in fragment order"""
+    cases, derived = _ordered_cases()
+    taken, refused = [], []
+    for name, query, seed, over in cases:
+        m = derived[name] if name in derived else FC.make_mappings(name, query, seed, over)
+        P = capi.map_default_params(**over)
+        order, tie = _chaining_order(m, query)
+        expected = capi.host_filter("subset", m, fai, query, P) if name in derived else GOLDEN[name]["subset"]
+        assert capi.host_filter_ordered("subset", m[order], order, fai, query, P) == expected, name
+        if len(m) >= 2 and over.get("split", 1):
+            (refused if tie else taken).append(name)
+    assert len(taken) >= 18 and "defaults_twice" in refused  # the order was taken, and it was refused and undone
+
+
 def test_golden_is_not_trivial():
     n_lines = {k: len(v["subset"].splitlines()) for k, v in GOLDEN.items()}
     assert sum(1 for v in n_lines.values() if v > 10) >= 18

@@ -83,6 +83,49 @@ def test_map_paf_matches_stage_oracles(gpu, tmp_path, over):
         assert "other" not in f[0] and "other" not in f[5] and "tiny" not in line
 
 
+@pytest.fixture(scope="module")
+def subset_run(tmp_path_factory):
+    """the pangenome in target subsets of 45 kb (createTargetSubsets: a subset is closed once it holds that much), and the text the
+    stage oracles give: per subset, every query against the index of that subset alone"""
+    seqs = _pangenome(41)
+    fa = str(tmp_path_factory.mktemp("subsets") / "pan.fa")
+    _write_fasta(fa, seqs)
+    pct = 0.85
+    P = capi.map_default_params(percentage_identity=pct, auto_pct_identity=0, index_by_size=45000)
+    subsets, cur, size = [], [], 0
+    for i, (_, s) in enumerate(seqs):
+        cur.append(i)
+        size += len(s)
+        if size >= 45000 or i + 1 == len(seqs):
+            subsets.append(set(cur))
+            cur, size = [], 0
+    n_maps = 0
+    exp = ""
+    for sub in subsets:
+        text, maps, _ = _expected(seqs, fa, P, pct, targets=sub)
+        exp += text
+        n_maps += sum(len(m) for m in maps.values())
+    return seqs, fa, P, subsets, exp, n_maps
+
+
+@pytest.mark.parametrize("switch", [None, "WFM_FILTER_OVERLAP", "WFM_FILTER_WORKERS", "WFM_FILTER_DEVICE_ORDER"])
+def test_map_driver_switches_give_the_stage_oracles_text(gpu, subset_run, tmp_path, monkeypatch, switch):
+    """several target subsets and a batch of several queries per subset, with the driver as it is by default, with a batch's
+    post-processing after its mapping instead of beside it (WFM_FILTER_OVERLAP=0), with one filter thread (WFM_FILTER_WORKERS=1)
+    and with the chaining order from the host's sort instead of the device's (WFM_FILTER_DEVICE_ORDER=0): the switches are read
+    per call, and every setting gives the stage oracles' bytes"""
+    seqs, fa, P, subsets, exp, n_maps = subset_run
+    assert len(subsets) >= 2 and len(exp.splitlines()) > 10
+    if switch:
+        monkeypatch.setenv(switch, "1" if switch == "WFM_FILTER_WORKERS" else "0")
+    out = str(tmp_path / "map.paf")
+    summ = capi.map_paf(gpu, fa, out, params=P)
+    assert summ.subsets == len(subsets) and summ.queries == len(seqs)
+    assert summ.l2_mappings == n_maps > 300
+    assert open(out).read() == exp
+    assert summ.written == len(exp.splitlines())
+
+
 def test_map_paf_target_subsets_and_query_file(gpu, tmp_path):
     """-b style target batching (one index per subset) and a separate query file."""
     seqs = _pangenome(43, L=20000)

@@ -879,7 +879,7 @@ HOST_EXPORTS = ["wfmh_test_packed_lce", "wfmh_test_is_acgt", "wfmh_align_default
                 "wfmh_map_default_params", "wfmh_test_filter", "wfmh_map", "wfmh_test_winnow_chunked", "wfmh_test_fasta", "wfmh_test_winnow_thinned", "wfmh_test_sort_records", "wfmh_test_index_file",
                 "wfmh_map_multi", "wfmh_align_paf_multi", "wfmh_test_winnow_model", "wfmh_test_sortlike_model", "wfmh_test_finish_records",
                 "wfmh_release_sequences", "wfmh_test_fasta_shared", "wfmh_seed_paf", "wfmh_test_deal", "wfmh_test_subwindow",
-                "wfmh_test_rows", "wfmh_test_tile_plan", "wfmh_test_p2_plan", "wfmh_test_base_plan"]
+                "wfmh_test_rows", "wfmh_test_tile_plan", "wfmh_test_p2_plan", "wfmh_test_base_plan", "wfmh_test_map_plan", "wfmh_test_filter_ordered"]
 
 
 class MapSummary(C.Structure):
@@ -945,6 +945,19 @@ def host_deal(lengths, n_parts: int):
     if rc != 0:
         raise WfmError(f"wfmh_test_deal failed ({rc})")
     return [int(x) for x in out[:len(ln)]]
+
+
+def host_map_plan(op: int, values, out_size: int):
+    """wfmh_test_map_plan: one function of the map driver's planner (host/map_plan.hpp) on a list of integers -> out_size integers."""
+    L = load()
+    L.wfmh_test_map_plan.restype = C.c_int
+    L.wfmh_test_map_plan.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
+    v = np.ascontiguousarray(values, dtype=np.int64)
+    out = np.full(max(out_size, 1), -(1 << 62), dtype=np.int64)
+    rc = L.wfmh_test_map_plan(op, v.ctypes.data, len(v), out.ctypes.data)
+    if rc != 0:
+        raise WfmError(f"wfmh_test_map_plan failed ({rc})")
+    return out[:out_size]
 
 
 def host_fasta_shared(path: str, name: str) -> str:
@@ -1055,6 +1068,27 @@ def host_filter(stage: str, mappings, fasta: str, query_name: str, params: MapHo
     p = L.wfmh_test_filter(stage.encode(), m.ctypes.data, len(m), fasta.encode(), query_name.encode(), C.byref(params))
     if not p:
         raise WfmError("wfmh_test_filter failed")
+    s = C.string_at(p).decode()
+    L.wfmh_free(p)
+    if s.startswith("ERROR: "):
+        raise WfmError(s)
+    return s
+
+
+def host_filter_ordered(stage: str, mappings, orig, fasta: str, query_name: str, params: MapHostParams) -> str:
+    """wfmh_test_filter_ordered: host_filter on mappings given in chaining order; orig[i] = mapping i's position in fragment order."""
+    L = load()
+    m = np.ascontiguousarray(mappings, dtype=MAPPING_DTYPE)
+    o = np.ascontiguousarray(orig, dtype=np.uint32)
+    if len(o) != len(m):
+        raise ValueError("one entry of orig per mapping")
+    L.wfmh_test_filter_ordered.restype = C.c_void_p
+    L.wfmh_test_filter_ordered.argtypes = [C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(MapHostParams)]
+    L.wfmh_free.restype = None
+    L.wfmh_free.argtypes = [C.c_void_p]
+    p = L.wfmh_test_filter_ordered(stage.encode(), m.ctypes.data, len(m), o.ctypes.data, fasta.encode(), query_name.encode(), C.byref(params))
+    if not p:
+        raise WfmError("wfmh_test_filter_ordered failed")
     s = C.string_at(p).decode()
     L.wfmh_free(p)
     if s.startswith("ERROR: "):

@@ -17,6 +17,7 @@
 #include "fasta.hpp"
 #include "index_file.hpp"
 #include "map_filter.hpp"
+#include "map_plan.hpp"
 #include "mapper.hpp"
 #include "sequence_ids.hpp"
 
@@ -260,8 +261,90 @@ int wfmh_test_deal(const int64_t* lengths, int64_t n, int n_parts, int32_t* out_
   return WFM_OK;
 }
 
-char* wfmh_test_filter(const char* stage, const wfm_mapping_t* maps, int64_t n, const char* fasta, const char* query_name,
-                       const wfmh_map_params_t* prm) {
+int wfmh_test_map_plan(int op, const int64_t* in, int64_t n, int64_t* out) {
+  namespace mp = skch::map_plan;
+  if (!in || !out || n < 0) return WFM_E_ARG;
+  auto spans = [&](int64_t nq, const int64_t* v) {
+    std::vector<mp::BatchQuery> bq((size_t)nq);
+    for (int64_t i = 0; i < nq; ++i) bq[(size_t)i] = {(size_t)i, (skch::seqno_t)i, 0, 0, v[2 * i], (int)v[2 * i + 1]};
+    return bq;
+  };
+  switch (op) {
+    case 0: {  // layout_fragments
+      if (n != 4 || in[1] < 1) return WFM_E_ARG;
+      const mp::FragLayout fl = mp::layout_fragments(in[0], in[1], in[2], in[3]);
+      out[0] = fl.nfrag;
+      std::copy(fl.offsets.begin(), fl.offsets.end(), out + 1);
+      return WFM_OK;
+    }
+    case 1: {  // target_subsets; the names are their positions
+      if (n < 1) return WFM_E_ARG;
+      std::vector<std::string> names;
+      for (int64_t i = 1; i < n; ++i) names.push_back(std::to_string(i - 1));
+      const auto subsets = mp::target_subsets(names, std::vector<int64_t>(in + 1, in + n), in[0]);
+      int64_t next = 0;
+      out[0] = (int64_t)subsets.size();
+      for (size_t s = 0; s < subsets.size(); ++s) {
+        for (const auto& name : subsets[s]) if (name != std::to_string(next++)) return WFM_E_ARG;  // (in order, each once)
+        out[1 + s] = (int64_t)subsets[s].size();
+      }
+      return WFM_OK;
+    }
+    case 2: {  // plan_batch
+      if (n < 2 || in[1] < 0 || in[1] > n - 2) return WFM_E_ARG;
+      const mp::BatchPlan p = mp::plan_batch(in + 2, (size_t)(n - 2), (size_t)in[1], in[0]);
+      out[0] = (int64_t)p.next; out[1] = p.in_place; out[2] = p.n_bases; out[3] = (int64_t)p.members.size();
+      for (size_t i = 0; i < p.members.size(); ++i) out[4 + i] = (int64_t)p.members[i];
+      return WFM_OK;
+    }
+    case 3:  // batch_bases_for, mapping_cap, spare_hint and the thresholds
+      if (n != 4 || in[0] < 1) return WFM_E_ARG;
+      out[0] = mp::batch_bases_for((size_t)in[0], (uint64_t)in[1]);
+      out[1] = mp::mapping_cap(in[2], in[3]);
+      out[2] = (int64_t)mp::spare_hint((size_t)in[2], in[3]);
+      out[3] = mp::kBatchBases; out[4] = mp::kCopyBases; out[5] = (int64_t)mp::kEarlyFilterFrags; out[6] = (int64_t)mp::kSpareMappings;
+      return WFM_OK;
+    case 4: {  // split_by_query
+      if (n < 1 || in[0] < 0 || n < 1 + 2 * in[0]) return WFM_E_ARG;
+      const int64_t nq = in[0], nm = n - 1 - 2 * nq;
+      std::vector<int32_t> mfrag(in + 1 + 2 * nq, in + n);
+      const std::vector<size_t> first = mp::split_by_query(mfrag.data(), (size_t)nm, spans(nq, in + 1));
+      for (size_t i = 0; i < first.size(); ++i) out[i] = (int64_t)first[i];
+      return WFM_OK;
+    }
+    case 5: {  // query_results
+      if (n < 7) return WFM_E_ARG;
+      const int64_t first_frag = in[0], w = in[1], m0 = in[2], nq = in[3], threads = in[4], has_perm = in[5], nm = in[6];
+      if (nm < 0 || n != 7 + 3 * nm || m0 < 0 || nq < 0 || m0 + nq > nm) return WFM_E_ARG;
+      std::vector<wfm_mapping_t> maps((size_t)nm);
+      std::vector<int32_t> mfrag((size_t)nm);
+      std::vector<uint32_t> perm((size_t)nm);
+      for (int64_t i = 0; i < nm; ++i) {
+        std::memset(&maps[(size_t)i], 0, sizeof(wfm_mapping_t));
+        mfrag[(size_t)i] = (int32_t)in[7 + i];
+        perm[(size_t)i] = (uint32_t)in[7 + nm + i];
+        maps[(size_t)i].queryStartPos = (uint32_t)in[7 + 2 * nm + i];
+        maps[(size_t)i].refStartPos = (uint32_t)i;  // which mapping a result was
+      }
+      skch::MappingResultsVector_t res(3);  // (stale content, as a reused vector has)
+      std::vector<uint32_t> orig(2, 7u);
+      mp::query_results(maps.data(), mfrag.data(), has_perm ? perm.data() : nullptr, (size_t)m0, (size_t)nq, first_frag, w, res, orig, (int)threads);
+      if ((int64_t)res.size() != nq || !(orig.empty() || (int64_t)orig.size() == nq)) return WFM_E_ARG;
+      out[0] = (int64_t)orig.size();
+      for (int64_t i = 0; i < nq; ++i) { out[1 + i] = res[(size_t)i].refStartPos; out[1 + nq + i] = res[(size_t)i].queryStartPos; }
+      for (size_t i = 0; i < orig.size(); ++i) out[1 + 2 * nq + (int64_t)i] = orig[i];
+      return WFM_OK;
+    }
+    default:
+      return WFM_E_ARG;
+  }
+}
+
+namespace {
+
+// the body of wfmh_test_filter and wfmh_test_filter_ordered
+char* test_filter(const char* stage, const wfm_mapping_t* maps, int64_t n, const uint32_t* orig, const char* fasta, const char* query_name,
+                  const wfmh_map_params_t* prm) {
   if (!stage || !fasta || !query_name || !prm || n < 0 || (n && !maps)) return nullptr;
   std::string text;
   try {
@@ -277,11 +360,11 @@ char* wfmh_test_filter(const char* stage, const wfm_mapping_t* maps, int64_t n, 
     const std::string st(stage);
     if (st == "subset") {
       skch::MappingOutput::mappingBoundarySanityCheck(qlen, v, ids);
-      skch::FilteredMappingsResult r = skch::filterSubsetMappings(v, p, ids, qlen);
+      skch::FilteredMappingsResult r = skch::filterSubsetMappings(v, p, ids, qlen, orig);
       const bool merged = p.mergeMappings && p.split;
       skch::MappingOutput::reportReadMappings(merged ? r.mergedMappings : r.nonMergedMappings, merged ? r.mergedChainInfo : r.nonMergedChainInfo,
                                               query_name, os, ids, p, qlen);
-    } else if (st == "onetoone") {
+    } else if (st == "onetoone" && !orig) {
       skch::MappingResultsVector_t kept;
       skch::MappingFilterUtils::filterByGroup(v, kept, p.numMappingsForSegment - 1, true, ids, p);
       skch::MappingOutput::reportReadMappings(kept, query_name, os, ids, p, qlen);
@@ -295,6 +378,19 @@ char* wfmh_test_filter(const char* stage, const wfm_mapping_t* maps, int64_t n, 
   char* out = (char*)malloc(text.size() + 1);
   if (out) std::memcpy(out, text.c_str(), text.size() + 1);
   return out;
+}
+
+}  // namespace
+
+char* wfmh_test_filter(const char* stage, const wfm_mapping_t* maps, int64_t n, const char* fasta, const char* query_name,
+                       const wfmh_map_params_t* prm) {
+  return test_filter(stage, maps, n, nullptr, fasta, query_name, prm);
+}
+
+char* wfmh_test_filter_ordered(const char* stage, const wfm_mapping_t* maps, int64_t n, const uint32_t* orig, const char* fasta,
+                               const char* query_name, const wfmh_map_params_t* prm) {
+  if (n && !orig) return nullptr;
+  return test_filter(stage, maps, n, n ? orig : nullptr, fasta, query_name, prm);
 }
 
 // Test hook for the on-disk index (host/index_file.cpp; no GPU needed).  op "ids": the id section alone

@@ -332,17 +332,12 @@ bool strictly_ascending(const std::vector<uint32_t>& q, Less less) {
   return ok.load();
 }
 
-// f3 (SURVEY 8f-3), its first step: the caller may have the chaining order from the device (wfm_map_fragments_ordered) and have built
-// readMappings in that order already; presorted_orig[i] = the position mapping i had in the reference's input order (fragment order:
-// the ids the chain representatives are made of).  Consumed by the next chain_mappings call of this thread.
-static thread_local const uint32_t* tl_presorted = nullptr;
-static thread_local size_t tl_presorted_n = 0;
-
 // Steps 1-4 of mergeMappingsInRange[WithChains] (mappingFilter.hpp:402-498, :593-675): sorts
 // readMappings into chains and returns each mapping's chain representative.
-std::vector<offset_t> chain_mappings(MappingResultsVector_t& readMappings, int max_dist, const Parameters& param) {
-  const uint32_t* presorted = tl_presorted_n == readMappings.size() ? tl_presorted : nullptr;
-  tl_presorted = nullptr; tl_presorted_n = 0;
+// f3 (SURVEY 8f-3), its first step: the caller may have the chaining order from the device (wfm_map_fragments_ordered) and have built
+// readMappings in that order already; presorted[i] = the position mapping i had in the reference's input order (fragment order:
+// the ids the chain representatives are made of), one entry per mapping.  Null: none.
+std::vector<offset_t> chain_mappings(MappingResultsVector_t& readMappings, int max_dist, const Parameters& param, const uint32_t* presorted) {
   const size_t n = readMappings.size();
   static const bool tdbg = getenv("WFM_FILTER_TIMES") != nullptr;
   auto tnow = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -678,7 +673,8 @@ std::vector<SpanRec> collect_spans(const MappingResultsVector_t& m, const std::v
 
 }  // namespace
 
-MappingsWithChains MappingFilterUtils::mergeMappingsInRangeWithChains(MappingResultsVector_t& readMappings, int max_dist, const Parameters& param) {
+MappingsWithChains MappingFilterUtils::mergeMappingsInRangeWithChains(MappingResultsVector_t& readMappings, int max_dist, const Parameters& param,
+                                                                      const uint32_t* presorted_orig) {
   MappingsWithChains result;
   if (!param.split || readMappings.size() < 2) {
     result.mappings = readMappings;
@@ -686,7 +682,7 @@ MappingsWithChains MappingFilterUtils::mergeMappingsInRangeWithChains(MappingRes
     for (size_t i = 0; i < readMappings.size(); ++i) result.chainInfo[i] = {static_cast<uint32_t>(i), 1, 1};
     return result;
   }
-  const std::vector<offset_t> chainOf = chain_mappings(readMappings, max_dist, param);
+  const std::vector<offset_t> chainOf = chain_mappings(readMappings, max_dist, param, presorted_orig);
   // (representative -> sequential chain id in the order of first appearance: the vector is sorted by chain, so that is the chain's number;
   // chainPos counts a chain's spans from 1 in a uint16, as the reference's does)
   const std::vector<SpanRec> spans = collect_spans(readMappings, chainOf, param);
@@ -704,7 +700,7 @@ MappingsWithChains MappingFilterUtils::mergeMappingsInRangeWithChains(MappingRes
 
 MappingResultsVector_t MappingFilterUtils::mergeMappingsInRange(MappingResultsVector_t& readMappings, int max_dist, const Parameters& param) {
   if (!param.split || readMappings.size() < 2) return readMappings;
-  const std::vector<offset_t> chainOf = chain_mappings(readMappings, max_dist, param);
+  const std::vector<offset_t> chainOf = chain_mappings(readMappings, max_dist, param, nullptr);
   const std::vector<SpanRec> spans = collect_spans(readMappings, chainOf, param);
   MappingResultsVector_t out(spans.size());
   par_ranges_any(spans.size(), [&](size_t lo, size_t hi) { for (size_t k = lo; k < hi; ++k) out[k] = merge_span(readMappings, spans[k].first, spans[k].last); });
@@ -832,10 +828,9 @@ void MappingFilterUtils::filterByScaffolds(MappingResultsVector_t& readMappings,
 // Map::filterSubsetMappings (computeMap.hpp:1076-1165)
 // ---------------------------------------------------------------------------------------------
 void set_filter_threads(int threads) { tl_filter_threads = std::max(1, threads); }
-void set_presorted_order(const uint32_t* orig_index, size_t n) { tl_presorted = orig_index; tl_presorted_n = n; }
 
 FilteredMappingsResult filterSubsetMappings(MappingResultsVector_t& mappings, const Parameters& param, const SequenceIdManager& idManager,
-                                            offset_t queryLen) {
+                                            offset_t queryLen, const uint32_t* presorted_orig) {
   FilteredMappingsResult result;
   if (mappings.empty()) return result;
   static const bool tdbg = getenv("WFM_FILTER_TIMES") != nullptr;
@@ -843,7 +838,7 @@ FilteredMappingsResult filterSubsetMappings(MappingResultsVector_t& mappings, co
   const size_t n_in = mappings.size();
   MappingResultsVector_t* const scaffolds_out = param.scaffold_output_file.empty() ? nullptr : &result.scaffoldChains;
   double tt[8] = {0}; int ti = 0; tt[ti++] = tnow();
-  MappingsWithChains chained = MappingFilterUtils::mergeMappingsInRangeWithChains(mappings, (int)param.chain_gap, param);
+  MappingsWithChains chained = MappingFilterUtils::mergeMappingsInRangeWithChains(mappings, (int)param.chain_gap, param, presorted_orig);
   tt[ti++] = tnow();
   MappingResultsVector_t& merged = chained.mappings;
   if (param.mergeMappings && param.split) {

@@ -38,7 +38,8 @@ class MappingFilterUtils {
   static void sparsifyMappings(MappingResultsVector_t& readMappings, const Parameters& param);
   static void filterByGroup(MappingResultsVector_t& unfilteredMappings, MappingResultsVector_t& filteredMappings, int n_mappings,
                             bool filter_ref, const SequenceIdManager& idManager, const Parameters& param);
-  static MappingsWithChains mergeMappingsInRangeWithChains(MappingResultsVector_t& readMappings, int max_dist, const Parameters& param);
+  static MappingsWithChains mergeMappingsInRangeWithChains(MappingResultsVector_t& readMappings, int max_dist, const Parameters& param,
+                                                           const uint32_t* presorted_orig = nullptr);
   static MappingResultsVector_t mergeMappingsInRange(MappingResultsVector_t& readMappings, int max_dist, const Parameters& param);
   // chains_out (optional): receives the scaffold chains the reference writes to --scaffold-out (mappingFilter.hpp:911-945) --
   // the chains after the length cut and their own sweep, and only when anchors were found
@@ -53,14 +54,14 @@ struct FilteredMappingsResult {
 };
 // host threads the CALLING thread may use inside filterSubsetMappings (default 1): a batch with a single long query
 void set_filter_threads(int threads);
-// f3, first step: the caller built the next query's mappings in chaining order from the device's permutation
-// (wfm_map_fragments_ordered); orig_index[i] = mapping i's position in the reference's input order (fragment order).  chain_mappings checks the
-// order and skips its own sort; the pointer must stay valid until the next filterSubsetMappings / mergeMappingsInRange of this thread returns.
-void set_presorted_order(const uint32_t* orig_index, size_t n);
 
-// Map::filterSubsetMappings: everything between a query's raw L2 mappings and what is printed
+// Map::filterSubsetMappings: everything between a query's raw L2 mappings and what is printed.
+// presorted_orig (f3, first step; null: none): the caller built `mappings` in chaining order from the device's permutation
+// (wfm_map_fragments_ordered); presorted_orig[i] = mapping i's position in the reference's input order (fragment order), one entry per
+// mapping.  It goes to the first chaining call only, which checks the order, skips its own sort if it holds and undoes it if not; it is
+// read during this call alone.
 FilteredMappingsResult filterSubsetMappings(MappingResultsVector_t& mappings, const Parameters& param, const SequenceIdManager& idManager,
-                                            offset_t queryLen);
+                                            offset_t queryLen, const uint32_t* presorted_orig = nullptr);
 
 class MappingOutput {
  public:

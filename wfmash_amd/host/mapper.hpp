@@ -9,6 +9,12 @@
 //               (host, map_filter.hpp); one-to-one mode adds the reference-axis pass at the end (:790-866)
 // The reference's Taskflow/thread-pool plumbing is replaced by batches; fragment results are taken
 // in fragment order where the reference takes them in task-completion order.
+//
+// mapper.cpp: mapQuery is the loop over subsets, over stages that share one MapRun (load_sub_index / build_sub_index,
+//   write_sub_index_file, replicate_index, map_subset with one DeviceWorker per handle, one_to_one_pass).
+// map_plan.hpp: what the driver decides without a device -- names, subsets, fragments, batches, capacities, the split of a
+//   batch's mappings by query (tests/test_map_plan_cpu.py).
+// map_queue.hpp: the ordered writer of finished batches and the queue between a device thread and its filter threads.
 #pragma once
 
 #include <cstdint>
