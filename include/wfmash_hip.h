@@ -273,7 +273,10 @@ enum {
   WFM_TC_BLOCKS_COARSE = 5, /* blocks launched with the packed tile kernel's instantiation without per-score maxima              */
   WFM_TC_BLOCKS_FINE = 6,   /* blocks launched with the one that keeps them                                                      */
   WFM_TC_LEFT_BAND = 7,     /* jobs that left out of their band or out of their score bound                                      */
-  WFM_TILE_COUNTERS = 8
+  WFM_TC_REUSE_RESUMED = 8,   /* jobs whose outer direction went on from rows their parent kept (parent reuse)                    */
+  WFM_TC_REUSE_FALLBACKS = 9, /* jobs that came with such rows and gave them up: they ran (or were run again) from score 0           */
+  WFM_TC_REUSE_KEEPS = 10,    /* snapshots of one direction written to the store of kept rows                                        */
+  WFM_TILE_COUNTERS = 11
 };
 size_t wfm_get_tile_counters(const wfm_handle_t* h, uint64_t* out, size_t n);
 

@@ -98,6 +98,11 @@ int wfmh_test_tile_plan(const int32_t* jobs, int64_t n, const int32_t* rules, in
 int wfmh_test_p2_plan(const int32_t* cand, int64_t n, int64_t i0, int rows, int rows_bm, unsigned long long budget, int threads, int core, int64_t* geo,
                       int32_t* tasks, int64_t tasks_cap, int64_t* scalars);
 int wfmh_test_base_plan(int op, const int32_t* in, int64_t n, int32_t* out);
+/* ... and of parent reuse (csrc/wfa_plan.h): which keep a child resumes from, whether it may, the cadence under the store's cap; the tile plan
+ * with a direction mask per job (wrapped by tests/test_reuse_plan_cpu.py) */
+int wfmh_test_reuse_plan(int op, const int64_t* in, int64_t n, int64_t* out);
+int wfmh_test_tile_plan_dirs(const int32_t* jobs, int64_t n, const int32_t* rules, const uint8_t* dirs, int32_t* per_block, int32_t* tasks, int64_t tasks_cap,
+                             int64_t* scalars);
 /* host winnowing stage of wfm_add_minmers on caller-supplied canonical k-mer hashes (CPU tests) */
 int64_t wfmh_test_winnow(const char* seq, int64_t len, int k, int w, int s, int32_t seq_id,
                          const uint64_t* hash, const int8_t* strand, wfm_minmer_t* out, int64_t cap);

@@ -21,7 +21,8 @@ DEFAULT_PEN = (5, 8, 2, 24, 1)  # parse_args.hpp:290-294
 WFM_PF_ROOT_AGAIN, WFM_PF_JOB_AGAIN, WFM_PF_BASE_RETRY, WFM_PF_BASE_RETRY2, WFM_PF_BYTE_KERNEL, WFM_PF_P2_ROUNDS, WFM_PF_RING_KERNEL, WFM_PF_BASE_TILES = 1, 2, 4, 8, 16, 32, 64, 128
 WFM_PF_RING_GROWN = 256
 # wfm_get_tile_counters (include/wfmash_hip.h): the paths the BiWFA tile phase took in an align call, in the header's order
-TILE_COUNTERS = ("jobs", "exact_ends", "fine_reruns", "gap_reruns", "ring3", "blocks_coarse", "blocks_fine", "left_band")
+TILE_COUNTERS = ("jobs", "exact_ends", "fine_reruns", "gap_reruns", "ring3", "blocks_coarse", "blocks_fine", "left_band",
+                 "reuse_resumed", "reuse_fallbacks", "reuse_keeps")
 
 EXPORTS = [
     "wfm_create", "wfm_destroy", "wfm_last_error", "wfm_device_name",
@@ -471,7 +472,10 @@ class Handle:
         f.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         out = np.zeros(len(TILE_COUNTERS), dtype=np.uint64)
         have = f(self._p, out.ctypes.data, len(out))
-        assert have == len(TILE_COUNTERS), have
+        # (an older build of the library named by WFM_LIB_PATH or WFM_LIB -- A/B runs, scripts/driver_ab.py -- ends before the reuse counters, which
+        # then read 0; the package's own library must know every counter)
+        other_build = bool(os.environ.get("WFM_LIB_PATH") or os.environ.get("WFM_LIB"))
+        assert have == len(TILE_COUNTERS) or (other_build and 8 <= have < len(TILE_COUNTERS)), have
         return {k: int(v) for k, v in zip(TILE_COUNTERS, out)}
 
     def upload(self, items):
@@ -879,7 +883,8 @@ HOST_EXPORTS = ["wfmh_test_packed_lce", "wfmh_test_is_acgt", "wfmh_align_default
                 "wfmh_map_default_params", "wfmh_test_filter", "wfmh_map", "wfmh_test_winnow_chunked", "wfmh_test_fasta", "wfmh_test_winnow_thinned", "wfmh_test_sort_records", "wfmh_test_index_file",
                 "wfmh_map_multi", "wfmh_align_paf_multi", "wfmh_test_winnow_model", "wfmh_test_sortlike_model", "wfmh_test_finish_records",
                 "wfmh_release_sequences", "wfmh_test_fasta_shared", "wfmh_seed_paf", "wfmh_test_deal", "wfmh_test_subwindow",
-                "wfmh_test_rows", "wfmh_test_tile_plan", "wfmh_test_p2_plan", "wfmh_test_base_plan", "wfmh_test_map_plan", "wfmh_test_filter_ordered"]
+                "wfmh_test_rows", "wfmh_test_tile_plan", "wfmh_test_p2_plan", "wfmh_test_base_plan", "wfmh_test_map_plan", "wfmh_test_filter_ordered",
+                "wfmh_test_reuse_plan", "wfmh_test_tile_plan_dirs"]
 
 
 class MapSummary(C.Structure):

@@ -97,6 +97,28 @@ struct TileJob {
   int32_t reran;                       // mode-6 runs so far (the host's cell count)
 };
 
+// ---- a child's outer direction from its parent's kept rows (wfa_plan.h, "parent reuse") ----
+// A keep is one direction of a job's input snapshot at a block boundary s, compact: KEEP_ROWS rows of n columns (diagonals kmin .. kmin + n - 1),
+// row r = keep_row(r): M of score s - r for r < SNAP_ROWS, then I1 of s, s - 1, D1 of s, s - 1, I2 of s, D2 of s; WF_NULL outside a row's own range.
+struct KeepTask {
+  int32_t* dst;                        // KEEP_ROWS x n
+  int32_t job, dir;
+  int32_t expect_s;                    // the job keeps only if it stands at this score, active, in mode 0 (it moved on as the host expected)
+  int32_t kmin, n;
+  int32_t pad_;
+};
+// The keep into the planes of direction `dir` of the job's ring_in (the job stands at s_k, the keep's score), over the job's own ranges only.
+// out[2 * task] |= 1 if a cell written is within `slack` of the job's box (offset >= min(tl, pl + k) - slack: the parent may have run past a wall
+// the child stops at); out[2 * task + 1] = the largest antidiagonal 2 h - k of the M cells written.
+struct RestoreTask {
+  const int32_t* src;
+  int32_t job, dir;
+  int32_t s_k, kmin, n;
+  int32_t slack;
+};
+void launch_keep(const int32_t* ring, const TileJob* jobs, const KeepTask* tasks, int ntasks, int max_n, hipStream_t st);
+void launch_restore(int32_t* ring, const TileJob* jobs, const RestoreTask* tasks, int32_t* out, int ntasks, int max_n, hipStream_t st);
+
 // ---- phase 2 (overlap detection) without a step-by-step kernel ----
 // wavefront_bialign_find_breakpoint's second loop alternates "test the newest row of one direction against the last
 // `scope` rows of the other" and "advance the other direction by one row" until no better breakpoint is possible

@@ -101,6 +101,60 @@ struct GrownSnaps {  // (the blocks of a call that ends early go back as well)
   ~GrownSnaps() { for (size_t q = 0; q < v.size(); ++q) drop((int32_t)q + 1); }
 };
 
+// Parent reuse (wfa_plan.h): one direction of a job's snapshot at a block boundary, kept compact for the child that starts where that direction
+// started.  The rows lie in slabs of the device heap; a slab goes back when the last of its keeps has.  pl / tl / sub: the keeping job's box
+// and the bound its rows were cut to (what the child's ranges are checked against).
+struct KeptRows {
+  int32_t* d = nullptr;
+  int32_t slab = -1;
+  int32_t s0 = 0, mx = 0;      // the keep's score; the direction's running maximum there
+  int32_t kmin = 0, n = 0;     // diagonals kmin .. kmin + n - 1
+  int32_t pl = 0, tl = 0, sub = 0;
+};
+struct KeepStore {  // (the slabs of a call that ends early go back as well)
+  struct Slab { int32_t* d = nullptr; size_t cap = 0, used = 0; int64_t live = 0; };
+  std::vector<Slab> slabs;
+  std::vector<KeptRows> v;     // Node::keep = 1 + index
+  size_t cap_bytes = 0, held = 0, peak = 0;  // what the call's slabs may take; take now; took at most
+  // elems of the newest slab, or of a fresh one while the cap allows; nullptr: the store is full (or the device is)
+  int32_t* take(size_t elems, int32_t* slab_out) {
+    if (slabs.empty() || slabs.back().used + elems > slabs.back().cap) {
+      if (!slabs.empty() && slabs.back().live == 0) release((int32_t)slabs.size() - 1);
+      const size_t want = std::max<size_t>(elems, (size_t)16 << 20);  // 64 MB at least
+      if (held + want * 4 > cap_bytes) return nullptr;
+      Slab sl;
+      if (wfm_dmalloc((void**)&sl.d, want * sizeof(int32_t)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+      sl.cap = want;
+      held += want * 4; peak = std::max(peak, held);
+      slabs.push_back(sl);
+    }
+    Slab& sl = slabs.back();
+    int32_t* p = sl.d + sl.used;
+    sl.used += elems; sl.live += 1;
+    *slab_out = (int32_t)slabs.size() - 1;
+    return p;
+  }
+  // (a keep is dropped behind a wait for the call's stream, which its only writer and its only reader ran on: the slab goes back without
+  // another wait -- one for the whole device would hold up the other parts of the batch.  Not so when the call ends early.)
+  void release(int32_t i, bool wait = false) {
+    Slab& sl = slabs[(size_t)i];
+    if (!sl.d) return;
+    if (wait) wfm_dfree(sl.d); else wfm_dfree_nosync(sl.d);
+    held -= sl.cap * 4;
+    sl.d = nullptr;
+  }
+  // a keep nobody will take any more; the slab behind it once it holds none (the newest slab is still being filled: it only starts over)
+  void drop(int32_t id) {
+    if (id <= 0 || !v[(size_t)id - 1].d) return;
+    KeptRows& kr = v[(size_t)id - 1];
+    kr.d = nullptr;
+    Slab& sl = slabs[(size_t)kr.slab];
+    if (--sl.live > 0) return;
+    if ((size_t)kr.slab + 1 == slabs.size()) sl.used = 0; else release(kr.slab);
+  }
+  ~KeepStore() { for (size_t q = 0; q < slabs.size(); ++q) release((int32_t)q, true); }
+};
+
 }  // namespace
 
 struct wfm_seqset {
@@ -201,6 +255,9 @@ struct wfm_handle {
   DevBuf<int32_t> p2rows, p2max, p2bmax, p2pbmax;  // phase 2 from rows computed ahead (P2Job)
   DevBuf<P2Job> p2jobs;
   DevBuf<RingWidenJob> widenjobs;
+  DevBuf<KeepTask> keeptasks;        // parent reuse: the keeps behind a chunk of tile blocks, the restores at a look of the host and what they found
+  DevBuf<RestoreTask> restoretasks;
+  DevBuf<int32_t> restoreres;
   DevBuf<SeqRev> revjobs;
   DevBuf<BoundJob> bndjobs;   // roots whose score is bounded from above before their wavefronts run (wfa_bound_kernel)
   DevBuf<int32_t> bndres;
@@ -599,6 +656,22 @@ inline TileJob tile_job_from(const BpJob& j) {
   return t;
 }
 
+// Parent reuse, as the tile phase sees it: which of its jobs take a direction from a keep, which keep their own directions for their
+// children, and what became of both (entries follow `tiled`)
+struct ReuseUse { int32_t keep = 0, dir = 0, s_k = 0; };  // keep: Node::keep (0: both directions start at score 0), the direction it is of, its score
+struct ReuseCtl {
+  KeepStore* store = nullptr;
+  int cadence = 0;             // blocks between two keeps (whole chunks); 0: nobody keeps
+  int slack = 0;               // WFM_REUSE_TOUCH_SLACK
+  int min_blocks = 1;          // WFM_REUSE_MIN_BLOCKS: no keep below this many blocks
+  std::vector<ReuseUse> use;
+  std::vector<int32_t> upto;   // the last score the job keeps at (0: it keeps nothing)
+  std::vector<int32_t> meet;   // the score its directions meet at, where the job knows its score (half of it); 0: to be read off its progress
+  std::vector<char> bad;       // out: the job gave its keep up after it had begun: it is run again, both directions from score 0
+  std::vector<std::vector<int32_t>> kept[2];  // out: the keeps the job wrote (Node::keep values), per direction
+  uint64_t keep_bytes = 0, restore_bytes = 0;  // out: what the two kernels moved (read + written)
+};
+
 // One pass of the tile phase over the jobs listed in `tiled`, and the chunk of blocks at hand
 struct TilePhase {
   wfm_handle* h; wfm_seqset* S; const DevPen& dp; int scope; const TileCfg& cfg; int T; bool refine;  // run_tiled_phase's arguments
@@ -615,7 +688,26 @@ struct TilePhase {
   TileChunkPlan plan;
   uint32_t blocks = 0;
   double lane_cells = 0;  // threads x diagonals per thread x scores over all tiles launched (diagnostics)
+  // parent reuse (ru == nullptr: none of it)
+  ReuseCtl* ru = nullptr;
+  std::vector<uint8_t> dirs, own;   // per job: the directions that get tiles (bit 0 forward, bit 1 reverse); those it has computed from score 0 itself
+  std::vector<int32_t> resumed_at;  // the score the job took its keep at (0: it has not), -1 once it is a block past it
+  std::vector<KeepTask> ktasks;     // the keeps behind the chunk at hand, their Node::keep values
+  std::vector<int32_t> kids;
+  std::vector<RestoreTask> rtasks;
+  std::vector<int32_t> rres;
 };
+
+// A job gives up the keep it began with: it leaves the tile phase here (mode 3, as a job that ran out of its band) and the host runs it again
+// without one.  It drops no record: the node goes to the next level as it came, less the keep.
+void reuse_fall_back(TilePhase& p, size_t i) {
+  if (p.active[i]) { p.active[i] = 0; --p.n_active; }
+  p.tj[i].active = 0; p.tj[i].mode = 3;
+  p.dirs[i] = 3; p.resumed_at[i] = -1;
+  p.ru->bad[i] = 1;
+  p.ru->store->drop(p.ru->use[i].keep);
+  p.h->tile_ctr[WFM_TC_REUSE_FALLBACKS] += 1;
+}
 
 // The jobs' TileJobs, and where they stand: at score 0 after the init kernel, or (refine) where a pass before left them
 int init_tile_jobs(TilePhase& p, const std::vector<int32_t>* fine_from, const std::vector<int64_t>* ring3) {
@@ -624,6 +716,8 @@ int init_tile_jobs(TilePhase& p, const std::vector<int32_t>* fine_from, const st
   const size_t n = p.n;
   const int T = p.T;
   p.tj.resize(n); p.fmax.assign(n, 0); p.rmax.assign(n, 0); p.active.assign(n, 1); p.s_begin.assign(n, 0);
+  p.dirs.assign(n, 3); p.own.assign(n, 3); p.resumed_at.assign(n, 0);
+  if (p.ru) { p.ru->bad.assign(n, 0); p.ru->kept[0].assign(n, {}); p.ru->kept[1].assign(n, {}); }
   for (size_t i = 0; i < n; ++i) {
     const BpJob& j = p.jobs[(size_t)p.tiled[i]];
     TileJob& t = p.tj[i];
@@ -652,6 +746,22 @@ int init_tile_jobs(TilePhase& p, const std::vector<int32_t>* fine_from, const st
       if (ended || p.fmax[i] + p.rmax[i] >= A) p.active[i] = 0;  // wfa_bp_kernel handles it from score 0
       p.n_active += p.active[i];
       p.tj[i].active = p.active[i]; p.tj[i].fmax = p.fmax[i]; p.tj[i].rmax = p.rmax[i]; p.tj[i].nblocks = 0;
+    }
+    // jobs that take their outer direction from a keep run the inner one alone for now; the outer one's maximum stands at the keep's meanwhile,
+    // an upper bound of all its earlier rows (the advance kernel finds no maxima of a direction without tiles and leaves it there)
+    for (size_t i = 0; p.ru && i < n; ++i) {
+      ReuseUse& u = p.ru->use[i];
+      if (u.keep <= 0) continue;
+      const int A = p.tj[i].pl + p.tj[i].tl - 1;
+      const int kept_max = p.ru->store->v[(size_t)u.keep - 1].mx;
+      if (!p.active[i] || kept_max + (u.dir == 0 ? p.rmax[i] : p.fmax[i]) >= A) {  // nothing has run yet: the job simply starts both directions
+        p.ru->store->drop(u.keep); u.keep = 0;
+        h->tile_ctr[WFM_TC_REUSE_FALLBACKS] += 1;
+        continue;
+      }
+      (u.dir == 0 ? p.fmax[i] : p.rmax[i]) = kept_max;
+      p.tj[i].fmax = p.fmax[i]; p.tj[i].rmax = p.rmax[i];
+      p.dirs[i] = (uint8_t)(1 << (1 - u.dir)); p.own[i] = p.dirs[i];
     }
   } else {
     for (size_t i = 0; i < n; ++i) {
@@ -687,11 +797,117 @@ int plan_tile_tasks(TilePhase& p) {
     const TileJob& t = p.tj[i];
     p.pjobs[i] = TilePlanJob{t.pl, t.tl, t.sub, t.s0, t.mode, t.fine_s, t.packed, p.active[i]};
   }
-  plan_tile_chunk(p.pjobs.data(), p.n, p.rules, p.plan);
+  plan_tile_chunk(p.pjobs.data(), p.n, p.rules, p.plan, p.dirs.data());
   const std::vector<TileTask>& tasks = p.plan.tasks;
   if (tasks.empty()) { h->err = "tile phase: active jobs without a tile"; return WFM_E_HIP; }
   if (h->tiletasks.ensure(tasks.size())) { h->err = "out of device memory (tile tasks)"; return WFM_E_NOMEM; }
   HIPCHK(h, hipMemcpyAsync(h->tiletasks.p, tasks.data(), tasks.size() * sizeof(TileTask), hipMemcpyHostToDevice, h->stream));
+  return WFM_OK;
+}
+
+// Behind the chunk's last advance kernel: the snapshot every keeping job will stand at if it simply moves on, where that score is one of the
+// cadence -- the directions the job has computed from score 0 itself, each into rows of the store.  A job that did not get there keeps nothing
+// (the kernel checks; settle_keeps gives the rows back).
+int launch_keeps(TilePhase& p) {
+  wfm_handle* h = p.h;
+  p.ktasks.clear(); p.kids.clear();
+  if (!p.ru || p.ru->cadence <= 0) return WFM_OK;
+  ReuseCtl& ru = *p.ru;
+  int max_n = 0;
+  for (size_t i = 0; i < p.n && ru.cadence > 0; ++i) {
+    const TileJob& t = p.tj[i];
+    const int64_t es = (int64_t)t.s0 + (int64_t)p.chunk * p.T;
+    if (!p.active[i] || t.mode != 0 || es > ru.upto[i] || es < (int64_t)ru.min_blocks * p.T || es % ((int64_t)ru.cadence * p.T) != 0) continue;
+    if (!reuse_keep_wanted((int)es, ru.meet[i] > 0 ? ru.meet[i] : reuse_meet_estimate(t.s0, (int64_t)p.fmax[i] + p.rmax[i], t.pl + t.tl - 1), ru.cadence, p.T)) continue;
+    for (int d = 0; d < 2; ++d) {
+      if (!((p.own[i] >> d) & 1)) continue;
+      KeptRows kr;
+      kr.s0 = (int32_t)es; kr.kmin = reuse_keep_kmin(t.pl, (int)es); kr.n = reuse_keep_cols(t.pl, t.tl, (int)es);
+      kr.pl = t.pl; kr.tl = t.tl; kr.sub = t.sub;
+      kr.d = ru.store->take(reuse_keep_elems(t.pl, t.tl, (int)es), &kr.slab);
+      if (!kr.d) {  // the store is full: half as many keeps from here on (the ones held stay)
+        ru.cadence = ru.cadence * 2 <= (1 << 20) ? ru.cadence * 2 : 0;
+        break;
+      }
+      ru.store->v.push_back(kr);
+      p.kids.push_back((int32_t)ru.store->v.size());
+      p.ktasks.push_back(KeepTask{kr.d, (int32_t)i, d, kr.s0, kr.kmin, kr.n, 0});
+      max_n = std::max(max_n, kr.n);
+      ru.keep_bytes += 2ull * 4ull * (uint64_t)KEEP_ROWS * (uint64_t)kr.n;
+    }
+  }
+  if (p.ktasks.empty()) return WFM_OK;
+  if (h->keeptasks.ensure(p.ktasks.size())) { h->err = "out of device memory (keeps)"; return WFM_E_NOMEM; }
+  HIPCHK(h, hipMemcpyAsync(h->keeptasks.p, p.ktasks.data(), p.ktasks.size() * sizeof(KeepTask), hipMemcpyHostToDevice, h->stream));
+  launch_keep(h->ring.p, h->tilejobs.p, h->keeptasks.p, (int)p.ktasks.size(), max_n, h->stream);
+  HIPCHK(h, hipGetLastError());
+  return WFM_OK;
+}
+
+// The keeps the chunk really wrote (the job stands where the host expected it), with the direction's running maximum there
+void settle_keeps(TilePhase& p) {
+  for (size_t q = 0; q < p.ktasks.size(); ++q) {
+    const KeepTask& kt = p.ktasks[q];
+    const TileJob& t = p.tj[(size_t)kt.job];
+    if (t.active && t.mode == 0 && t.s0 == kt.expect_s) {
+      p.ru->store->v[(size_t)p.kids[q] - 1].mx = kt.dir == 0 ? t.fmax : t.rmax;
+      p.ru->kept[kt.dir][(size_t)kt.job].push_back(p.kids[q]);
+      p.h->tile_ctr[WFM_TC_REUSE_KEEPS] += 1;
+    } else p.ru->store->drop(p.kids[q]);
+  }
+  p.ktasks.clear(); p.kids.clear();
+}
+
+// At a look of the host: the jobs that wait for their keep and stand at its score take it (wfa_restore_kernel: the rows into the outer direction's
+// planes of ring_in, the touch flag, the direction's maximum over the job's own rows) and are tiled jobs like the others from here on -- unless a
+// kept cell touches the job's box, or the maxima fired while one direction stood still, or the job meets in the very block after the restore
+// (whose input holds no gap rows as deep as a short run up to the meeting point hands on): those give the keep up (reuse_fall_back).
+int restore_kept(TilePhase& p) {
+  wfm_handle* h = p.h;
+  if (!p.ru) return WFM_OK;
+  ReuseCtl& ru = *p.ru;
+  bool changed = false;
+  p.rtasks.clear();
+  int max_n = 0;
+  for (size_t i = 0; i < p.n; ++i) {
+    const TileJob& t = p.tj[i];
+    if (p.resumed_at[i] > 0) {  // took its keep at the last look or the one before
+      if (t.s0 > p.resumed_at[i]) p.resumed_at[i] = -1;
+      else if (!t.active || t.mode != 0) { reuse_fall_back(p, i); changed = true; }
+      continue;
+    }
+    if (p.dirs[i] == 3 || ru.bad[i]) continue;
+    const ReuseUse& u = ru.use[i];
+    if (!t.active || t.mode != 0 || t.s0 > u.s_k || (u.s_k - t.s0) % (p.chunk * p.T) != 0) { reuse_fall_back(p, i); changed = true; continue; }
+    if (t.s0 < u.s_k) continue;
+    const KeptRows& kr = ru.store->v[(size_t)u.keep - 1];
+    p.rtasks.push_back(RestoreTask{kr.d, (int32_t)i, u.dir, u.s_k, kr.kmin, kr.n, ru.slack});
+    max_n = std::max(max_n, kr.n);
+    ru.restore_bytes += 2ull * 4ull * (uint64_t)KEEP_ROWS * (uint64_t)kr.n;
+  }
+  if (!p.rtasks.empty()) {
+    p.rres.assign(p.rtasks.size() * 2, 0);
+    if (h->restoretasks.ensure(p.rtasks.size()) || h->restoreres.ensure(p.rres.size())) { h->err = "out of device memory (keeps)"; return WFM_E_NOMEM; }
+    HIPCHK(h, hipMemcpyAsync(h->restoretasks.p, p.rtasks.data(), p.rtasks.size() * sizeof(RestoreTask), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(h->restoreres.p, 0, p.rres.size() * sizeof(int32_t), h->stream));
+    launch_restore(h->ring.p, h->tilejobs.p, h->restoretasks.p, h->restoreres.p, (int)p.rtasks.size(), max_n, h->stream);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(p.rres.data(), h->restoreres.p, p.rres.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (size_t q = 0; q < p.rtasks.size(); ++q) {
+      const size_t i = (size_t)p.rtasks[q].job;
+      changed = true;
+      if (p.rres[2 * q]) { reuse_fall_back(p, i); continue; }
+      const ReuseUse& u = ru.use[i];
+      (u.dir == 0 ? p.fmax[i] : p.rmax[i]) = p.rres[2 * q + 1];
+      p.tj[i].fmax = p.fmax[i]; p.tj[i].rmax = p.rmax[i];
+      p.tj[i].prev_ok = 0;  // (ring_prev holds one direction's rows only)
+      p.dirs[i] = 3; p.resumed_at[i] = u.s_k;
+      ru.store->drop(u.keep);
+      h->tile_ctr[WFM_TC_REUSE_RESUMED] += 1;
+    }
+  }
+  if (changed) HIPCHK(h, hipMemcpyAsync(h->tilejobs.p, p.tj.data(), p.n * sizeof(TileJob), hipMemcpyHostToDevice, h->stream));
   return WFM_OK;
 }
 
@@ -720,6 +936,8 @@ int launch_chunk(TilePhase& p) {
     launch_tile_advance(h->tilejobs.p, h->tilemak.p, (int)p.n, T, p.dp, (cfg.reg && cfg.exact) ? 1 : 0, p.rules.coarse_on ? 1 : 0, variants_b[(size_t)b], h->stream);
   }
   HIPCHK(h, hipGetLastError());
+  const int rc = launch_keeps(p);
+  if (rc != WFM_OK) return rc;
   HIPCHK(h, hipMemcpyAsync(p.got.data(), h->tilejobs.p, p.n * sizeof(TileJob), hipMemcpyDeviceToHost, h->stream));
   return WFM_OK;
 }
@@ -758,16 +976,17 @@ void account_chunk(TilePhase& p) {
       const bool last_exact = got.mode == 2 && bl == got.nblocks - 1;    // the block that stopped at the meeting point
       const int base = p.s_begin[i] + (last_exact ? bl - 1 : bl) * T;    // it re-ran the block before it
       for (int d = 0; d < 2; ++d) {
+        if (!((p.dirs[i] >> d) & 1)) continue;  // (a direction that waits for its keep had no tiles)
         const int steps = last_exact ? (d == 0 ? got.tf : got.tr) : T;
         p.tile_cells += (uint64_t)cells_sum(was.pl, was.tl, was.sub, base + 1, base + steps);
       }
     }
     if (got.fine_s == -1 && was.fine_s != -1) {  // the block in which the directions met ran once more, for its per-score maxima (TileJob::fine_s)
-      for (int d = 0; d < 2; ++d) p.tile_cells += (uint64_t)cells_sum(was.pl, was.tl, was.sub, got.s0 + 1, got.s0 + T);
+      for (int d = 0; d < 2; ++d) if ((p.dirs[i] >> d) & 1) p.tile_cells += (uint64_t)cells_sum(was.pl, was.tl, was.sub, got.s0 + 1, got.s0 + T);
       h->tile_ctr[WFM_TC_FINE_RERUNS] += 1;
     }
     if (got.reran > was.reran) {  // the block before the meeting block ran once more, for its gap rows (TileJob::ring_prev)
-      for (int d = 0; d < 2; ++d) p.tile_cells += (uint64_t)cells_sum(was.pl, was.tl, was.sub, got.s0 - T + 1, got.s0);
+      for (int d = 0; d < 2; ++d) if ((p.dirs[i] >> d) & 1) p.tile_cells += (uint64_t)cells_sum(was.pl, was.tl, was.sub, got.s0 - T + 1, got.s0);
       h->tile_ctr[WFM_TC_GAP_RERUNS] += (uint64_t)(got.reran - was.reran);
     }
     p.tj[i] = got;
@@ -786,6 +1005,9 @@ void hand_back(TilePhase& p, uint32_t level, double cells_before) {
   for (size_t i = 0; i < p.n; ++i) {
     const TileJob& t = p.tj[i];
     const int sf_end = t.mode == 2 ? t.s0 + t.tf : t.s0, sr_end = t.mode == 2 ? t.s0 + t.tr : t.s0;
+    if (p.ru && p.ru->bad[i]) continue;  // (gave its keep up: what it computed goes into no result)
+    // (the rows a direction took from a keep are in the job's result as its own would be: they count here, where cells_tile -- the cells
+    // the tile kernels computed -- leaves them out)
     unique_level += (uint64_t)cells_sum(t.pl, t.tl, t.sub, p.s_begin[i] + 1, sf_end) + (uint64_t)cells_sum(t.pl, t.tl, t.sub, p.s_begin[i] + 1, sr_end);
   }
   h->stats.cells_tile_unique += unique_level;
@@ -797,7 +1019,7 @@ void hand_back(TilePhase& p, uint32_t level, double cells_before) {
     j.resume_s = t.s0;
     j.resume_sr = -1; j.last_fwd = 0;
     h->tile_ctr[WFM_TC_EXACT_ENDS] += t.mode == 2;
-    h->tile_ctr[WFM_TC_LEFT_BAND] += t.mode == 3;
+    h->tile_ctr[WFM_TC_LEFT_BAND] += t.mode == 3 && !(p.ru && p.ru->bad[i]);
     if (t.mode == 3) {  // ran out of its band: wfa_bp_kernel reports WFM_DEV_BAND
       // (where it stands, for the host: a job that goes on from this snapshot on a wider ring resumes at resume_sr with these maxima)
       j.resume_s = -3; j.resume_sr = t.s0; j.fmax0 = p.fmax[i]; j.rmax0 = p.rmax[i];
@@ -822,11 +1044,12 @@ void hand_back(TilePhase& p, uint32_t level, double cells_before) {
 int run_tiled_phase(wfm_handle* h, wfm_seqset* S, const DevPen& dp, int scope, const TileCfg& cfg, int T, bool refine,
                     std::vector<BpJob>& jobs, const std::vector<int>& tiled, std::vector<int64_t>& ring2,
                     double& tile_ms, uint64_t& tile_cells, uint32_t level, const std::vector<int32_t>* fine_from = nullptr,
-                    const std::vector<int64_t>* ring3 = nullptr) {
+                    const std::vector<int64_t>* ring3 = nullptr, ReuseCtl* reuse = nullptr) {
   const size_t n = tiled.size();
   if (n == 0) return WFM_OK;
   const double cells_before = (double)tile_cells;
   TilePhase p{h, S, dp, scope, cfg, T, refine, jobs, tiled, ring2, tile_ms, tile_cells, n};
+  p.ru = refine ? nullptr : reuse;
   int rc = init_tile_jobs(p, fine_from, ring3);
   if (rc != WFM_OK) return rc;
   if (p.n_active) {
@@ -854,6 +1077,8 @@ int run_tiled_phase(wfm_handle* h, wfm_seqset* S, const DevPen& dp, int scope, c
       const auto tq3 = clk();
       if ((rc = time_chunk(p)) != WFM_OK) return rc;
       account_chunk(p);
+      settle_keeps(p);
+      if ((rc = restore_kept(p)) != WFM_OK) return rc;
       ms_prep += msd(tq0, tq1); ms_launch += msd(tq1, tq2); ms_wait += msd(tq2, tq3); ms_post += msd(tq3, clk());
     }
     if (cfg.debug > 1)
@@ -1051,6 +1276,13 @@ struct Knobs {
   bool band_on = num("WFM_BAND", 1) != 0;
   int band_root = std::max(64, num("WFM_BAND_ROOT", 4096));
   int resume_margin = num("WFM_RESUME_MARGIN", SNAP_ROWS);  // (tests: a large value sends every resumed job back to score 0)
+  // parent reuse (wfa_plan.h): 0 = no job keeps, no child resumes; blocks between two keeps; how close to its box a kept cell may come (tests: a
+  // large value makes every resume fall back); the levels whose jobs keep (1: the roots alone, the children of deeper jobs start at score 0; 8 is
+  // what was measured: C3 56.9 - 57.4 ms a step with the roots' keeps, 56.1 - 56.2 with every level's, profiles/parent_reuse.md section 4)
+  bool reuse = num("WFM_REUSE", 1) != 0 && slack_env < (1 << 28);  // (children without their parents' scores may not resume: nobody keeps for them)
+  int reuse_min_blocks = std::max(1, num("WFM_REUSE_MIN_BLOCKS", 8));  // a keep, and a resume, fewer blocks deep is not worth its look of the host (C2, the scaled C4 rank)
+  int reuse_every = std::max(1, num("WFM_REUSE_EVERY", 2)), reuse_slack = num("WFM_REUSE_TOUCH_SLACK", 0);
+  int reuse_levels = num("WFM_REUSE_LEVELS", 8);
   int debug = env_debug();  // 0: unset
 };
 
@@ -1065,12 +1297,19 @@ struct Chunk {
   std::vector<int32_t> fine_from, fine_r, snap_r;
   std::vector<size_t> ring_third;  // elements of one ring of every tiled job of the chunk
   std::vector<char> grown_job, resume_bad, has_carry;
+  // parent reuse, per entry of `tiled` (plan_chunk): the keep the job resumes from, the last score it keeps at for its own children;
+  // per job (run_chunk_tiles): it gave its keep up, the keeps it wrote per direction
+  std::vector<ReuseUse> reuse;
+  std::vector<int32_t> keep_upto;
+  std::vector<char> reuse_bad;
+  std::vector<std::vector<int32_t>> kept[2];
   std::vector<BpResult> res, carry;  // carry: breakpoints found by rounds of phase 2 that did not end the walk
   std::vector<int> rest, more_set;   // rest: jobs for the step kernel -- not tiled, not exact, or not finished by the rows computed ahead
   void clear() {
     jobs.clear(); node_of.clear(); ring_elems = 0; maxw = 0;
     tiled.clear(); ring2.clear(); ring3.clear(); ring_third.clear(); fine_from.clear();
     tiled_r.clear(); ring2_r.clear(); fine_r.clear(); snap_r.clear(); grown_job.clear();
+    reuse.clear(); keep_upto.clear();
   }
 };
 
@@ -1105,6 +1344,10 @@ struct AlignCall {
   int64_t grown_maxband = 0;
   size_t ring_peak = 0;  // most elements a chunk's ring arena held
   GrownSnaps snaps;
+  KeepStore keeps;       // parent reuse: the rows jobs keep for their children
+  uint64_t reuse_children = 0, reuse_found = 0, reuse_taken = 0;  // children of keeping jobs; that found a keep; that were let run from it
+  uint64_t keep_bytes = 0, restore_bytes = 0;
+  uint64_t reuse_full_rings = 0;  // nodes that got a full ring in place of a narrow one to run from their keep
 };
 
 void make_roots(AlignCall& c) {
@@ -1204,8 +1447,21 @@ void plan_chunk(AlignCall& c, size_t i0) {
   for (; i < c.bp_nodes.size(); ++i) {
     const Node& nd = c.bp_nodes[i];
     const ProbMeta& pm = c.S->meta[nd.prob];
-    const RingPlan rp = plan_ring(nd, c.rules);
-    if (!rp.fits) { c.prob_status[nd.prob] = WFM_ST_OOM; c.snaps.drop(nd.snap); continue; }
+    RingPlan rp = plan_ring(nd, c.rules);
+    // the bound the job's rows are cut to (set into the job below)
+    const int32_t job_sub = (nd.sub != SUB_NONE && (int64_t)std::abs(nd.tl - nd.pl) * 8 >= (int64_t)nd.sub) ? nd.sub : SUB_NONE;
+    const bool reuse_on = c.knobs.reuse && tcfg.reg && tcfg.exact && c.RR == RING;
+    if (nd.keep > 0 && reuse_on && rp.fits && rp.band > 0 && !rp.grown) {
+      // A node that came with a keep takes it on a full ring only (a narrow one is out of parent reuse's scope).  Where the level chose a narrow
+      // one it gets the full one instead -- its parent ran on rings twice as wide in this arena -- but only if it will then really run from the keep:
+      // eligibility is decided on the full ring's plan first, and a node that fails it keeps the ring it would have had (and loses the keep below)
+      RingRules full = c.rules;
+      full.use_band = false;
+      const RingPlan fp = plan_ring(nd, full);
+      const KeptRows& kr = c.keeps.v[(size_t)nd.keep - 1];
+      if (kr.d && kr.s0 % (tcfg.chunk * tcfg.T) == 0 && reuse_eligible(nd, fp, kr.pl, kr.tl, kr.sub, job_sub, kr.s0, tcfg.T)) { rp = fp; ++c.reuse_full_rings; }
+    }
+    if (!rp.fits) { c.prob_status[nd.prob] = WFM_ST_OOM; c.snaps.drop(nd.snap); c.keeps.drop(nd.keep); continue; }
     const size_t width = rp.width, need = rp.need; const int band = rp.band; const bool tile_it = rp.tile_it, grown = rp.grown;
     // (a chunk of a level stops at 4 GB of rings even when the budget allows more: hundreds of jobs fill the device
     // long before that, and every GB of a first allocation costs 30 - 70 ms.  C1 substitute, three handles in a fresh
@@ -1229,7 +1485,7 @@ void plan_chunk(AlignCall& c, size_t i0) {
     // a bound only earns its keep when the end diagonal is far from the start diagonal relative to the score (padded
     // records and their children): for a balanced problem it starts to bind where the wavefronts meet, and costs the
     // tile kernel its bookkeeping all the way there
-    j.sub = (nd.sub != SUB_NONE && (int64_t)std::abs(nd.tl - nd.pl) * 8 >= (int64_t)nd.sub) ? nd.sub : SUB_NONE;
+    j.sub = job_sub;
     j.best0 = 0;
     j.packed = (c.knobs.tile_v2 && tcfg.reg && tcfg.C == 2 && (size_t)nd.prob < c.S->acgt.size() && c.S->acgt[(size_t)nd.prob]) ? 1 : 0;
     // bit 1: near-identical sequences -- the job's score is known (a child's, a bounded or hinted root's) to be under a sixteenth of its length; the packed
@@ -1263,7 +1519,24 @@ void plan_chunk(AlignCall& c, size_t i0) {
       const int64_t est = nd.score_rem != INT_MAX ? (int64_t)nd.score_rem : (nd.sub != SUB_NONE ? (int64_t)nd.sub : (int64_t)nd.pl + nd.tl);  // its score / the guess or bound / the worst case
       fine_min_blocks = std::min<int64_t>(fine_min_blocks, est / 2 / tcfg.T);
       k.fine_from.push_back(nd.score_rem != INT_MAX ? std::max(0, nd.score_rem / 2 - c.knobs.fine_margin) : INT_MAX);
-    }
+      // parent reuse: the keep the node came with, if it may run from it; the scores it keeps at itself
+      ReuseUse use;
+      if (nd.keep > 0 && reuse_on) {
+        const KeptRows& kr = c.keeps.v[(size_t)nd.keep - 1];
+        if (kr.d && kr.s0 % (tcfg.chunk * tcfg.T) == 0 && reuse_eligible(nd, rp, kr.pl, kr.tl, kr.sub, j.sub, kr.s0, tcfg.T)) { use.keep = nd.keep; use.dir = nd.keep_dir; use.s_k = kr.s0; ++c.reuse_taken; }
+      }
+      if (nd.keep > 0 && use.keep == 0) c.keeps.drop(nd.keep);
+      k.reuse.push_back(use);
+      // (no keep beyond the score a child could still resume at: a child's score is at most its parent's, which is at most the bound where one is known)
+      int32_t upto = 0;
+      if (reuse_on && band == 0 && !grown && (int)c.level <= c.knobs.reuse_levels) {
+        const int known = nd.score_rem != INT_MAX ? nd.score_rem : (nd.sub != SUB_NONE ? nd.sub : INT_MAX);
+        // (the two directions meet at scores a step apart: a child has half the job's score, give or take the rows the overlap phase reads)
+        upto = known != INT_MAX ? std::max(0, reuse_resume_limit(known / 2 + 2 * SNAP_ROWS, tcfg.T, c.knobs.fine_margin)) : INT_MAX;
+      }
+      k.keep_upto.push_back(upto);
+    } else c.keeps.drop(nd.keep);
+    if (resumes) c.keeps.drop(nd.keep);
     k.node_of.push_back((int32_t)i);
     k.ring_elems += need;
     // widest wavefront this job can reach: 2 diagonals per score of one direction (~half the total score)
@@ -1325,7 +1598,35 @@ int run_chunk_tiles(AlignCall& c) {
   const TileCfg& tcfg = c.tcfg;
   double tms = 0; uint64_t tcells = 0;
   const auto tw0 = std::chrono::steady_clock::now();
-  int rc = run_tiled_phase(h, c.S, c.dp, c.scope, tcfg, tcfg.T, false, k.jobs, k.tiled, k.ring2, tms, tcells, c.level, &k.fine_from, &k.ring3);
+  // parent reuse: the cadence under the store's cap -- an eighth of the part's budget -- from what the chunk's jobs would keep; a root whose score nobody
+  // knows is guessed to meet within a sixteenth of its bases (its keeps stop where it ends; should the store fill up all the same, launch_keeps thins them)
+  ReuseCtl ru;
+  ru.store = &c.keeps; ru.slack = c.knobs.reuse_slack; ru.min_blocks = c.knobs.reuse_min_blocks;
+  ru.use = k.reuse; ru.upto = k.keep_upto;
+  for (size_t q = 0; q < k.tiled.size(); ++q) {
+    const Node& nd = c.bp_nodes[(size_t)k.node_of[(size_t)k.tiled[q]]];
+    ru.meet.push_back(nd.score_rem != INT_MAX ? nd.score_rem / 2 : 0);
+  }
+  {
+    std::vector<ReuseKeeper> kp;
+    for (size_t q = 0; q < k.tiled.size(); ++q) {
+      const BpJob& j = k.jobs[(size_t)k.tiled[q]];
+      if (k.keep_upto[q] > 0) kp.push_back(ReuseKeeper{j.pl, j.tl, k.keep_upto[q] == INT_MAX ? (j.pl + j.tl) / 16 : k.keep_upto[q]});
+    }
+    c.keeps.cap_bytes = h->mem_budget / 8;
+    const int chunk_blocks = std::max(1, std::min(tcfg.chunk, (int)h->tile_ev.size() / 2));
+    ru.cadence = kp.empty() ? 0 : reuse_fit_cadence(kp.data(), kp.size(), reuse_cadence(c.knobs.reuse_every, chunk_blocks), tcfg.T, c.keeps.cap_bytes);
+  }
+  const bool any_reuse = ru.cadence > 0 || std::any_of(ru.use.begin(), ru.use.end(), [](const ReuseUse& u) { return u.keep > 0; });
+  int rc = run_tiled_phase(h, c.S, c.dp, c.scope, tcfg, tcfg.T, false, k.jobs, k.tiled, k.ring2, tms, tcells, c.level, &k.fine_from, &k.ring3, any_reuse ? &ru : nullptr);
+  k.reuse_bad.assign(k.jobs.size(), 0);
+  k.kept[0].assign(k.jobs.size(), {}); k.kept[1].assign(k.jobs.size(), {});
+  if (any_reuse && !ru.bad.empty())
+    for (size_t q = 0; q < k.tiled.size(); ++q) {
+      k.reuse_bad[(size_t)k.tiled[q]] = ru.bad[q];
+      for (int d = 0; d < 2; ++d) k.kept[d][(size_t)k.tiled[q]].swap(ru.kept[d][q]);
+    }
+  c.keep_bytes += ru.keep_bytes; c.restore_bytes += ru.restore_bytes;
   if (rc == WFM_OK && tcfg.T_refine > 0 && tcfg.T_refine < tcfg.T && !(tcfg.reg && tcfg.exact))
     rc = run_tiled_phase(h, c.S, c.dp, c.scope, tcfg, tcfg.T_refine, true, k.jobs, k.tiled, k.ring2, tms, tcells, c.level);
   if (rc == WFM_OK && !k.tiled_r.empty()) {
@@ -1480,7 +1781,7 @@ int keep_snapshot(AlignCall& c, size_t q, Node& again) {
 }
 
 // The two halves of a job on either side of its breakpoint: leaves to the base aligner, the others to the next level
-void push_children(AlignCall& c, const Node& nd, const BpResult& r, int bp_v, int bp_h) {
+void push_children(AlignCall& c, const Node& nd, const BpResult& r, int bp_v, int bp_h, size_t q) {
   const wfm_penalties_t* pen = c.pen;
   Node a{}, b{};
   a.prob = nd.prob; a.pb = nd.pb; a.pl = bp_v; a.tb = nd.tb; a.tl = bp_h;
@@ -1502,7 +1803,20 @@ void push_children(AlignCall& c, const Node& nd, const BpResult& r, int bp_v, in
       ch->smax = std::max(ch->score_rem, 0) + open_end;
       c.base_nodes.push_back(*ch);
     }
-    else c.next_bp.push_back(*ch);
+    else {
+      // parent reuse: the first child's forward direction starts where the job's did, the second child's reverse direction where its reverse
+      // one did -- the newest of the job's keeps of that direction the child may still resume at goes with it
+      const int d = ch == &a ? 0 : 1;
+      std::vector<int32_t>& kept = c.ck.kept[d][q];
+      if (!kept.empty()) {
+        ++c.reuse_children;
+        std::vector<int32_t> kept_s(kept.size());
+        for (size_t x = 0; x < kept.size(); ++x) kept_s[x] = c.keeps.v[(size_t)kept[x] - 1].s0;
+        const int pick = ch->sub != SUB_NONE ? reuse_pick_keep(kept_s.data(), kept_s.size(), ch->score_rem, c.tcfg.T, c.knobs.fine_margin, c.knobs.reuse_min_blocks) : -1;
+        if (pick >= 0) { ch->keep = kept[(size_t)pick]; ch->keep_dir = d; kept[(size_t)pick] = 0; ++c.reuse_found; }
+      }
+      c.next_bp.push_back(*ch);
+    }
   }
 }
 
@@ -1533,12 +1847,18 @@ int settle_chunk(AlignCall& c) {
     c.prob_cells[nd.prob] += r.cells;
     h->stats.cells_bp += r.cells;
     if (nd.score_rem == INT_MAX && k.jobs[q].band > 0 && !k.grown_job[q]) { ++c.roots_banded; c.roots_out += r.status == WFM_DEV_BAND; }
+    c.keeps.drop(nd.keep);  // (taken or given up long since as a rule; a job that left the tile phase otherwise still holds it)
+    if (k.reuse_bad[q]) {   // gave its keep up (restore_kept): the same node once more, both directions from score 0
+      Node again = nd; again.keep = 0; again.keep_dir = 0;
+      c.next_bp.push_back(again);
+      continue;
+    }
     const bool guessed = nd.hinted && k.jobs[q].sub != SUB_NONE;  // the job really ran under the caller's guess
     if (r.status == WFM_DEV_BAND || (guessed && (r.status < 0 || (r.status == 0 && r.score > nd.sub)))) {
       // ran out of its narrow ring, or past the caller's guess of its score: once more, at the end of this level, on
       // a full ring and without the guess
       Node again = nd; again.noband = 1; again.sub = SUB_NONE; again.hinted = 0;
-      again.band = k.jobs[q].band; again.snap = 0;
+      again.band = k.jobs[q].band; again.snap = 0; again.keep = 0; again.keep_dir = 0;
       if (c.pflags) c.pflags[nd.prob] |= nd.score_rem == INT_MAX ? WFM_PF_ROOT_AGAIN : WFM_PF_JOB_AGAIN;
       // where the full ring does not fit, the job's next ring grows from the band it had (plan_ring)
       const bool full_fits = ring_elems(ring_full_width(nd.pl, nd.tl), c.RR) * 4 <= h->mem_budget;
@@ -1559,7 +1879,7 @@ int settle_chunk(AlignCall& c) {
       continue;
     }
     if (r.status == 1) {  // end reached at score 0 -> base aligner
-      Node b = nd; b.smax = 0; c.base_nodes.push_back(b);
+      Node b = nd; b.smax = 0; b.keep = 0; c.base_nodes.push_back(b);
     } else if (r.status != 0) {
       if (c.knobs.debug) fprintf(stderr, "[wfm] problem %d: bialign job pl %d tl %d cb %d ce %d score_rem %d status %d (steps %d)\n", nd.prob, nd.pl, nd.tl, nd.cb, nd.ce, nd.score_rem, r.status, r.steps);
       c.prob_status[nd.prob] = WFM_ST_UNREACHABLE;
@@ -1571,9 +1891,12 @@ int settle_chunk(AlignCall& c) {
         c.prob_status[nd.prob] = WFM_ST_UNREACHABLE; continue;
       }
       if (c.knobs.debug > 1) fprintf(stderr, "[wfm] problem %d level %u: job pl %d tl %d cb %d ce %d rem %d -> bp v %d h %d score %d = %d + %d comp %d\n", nd.prob, c.level, nd.pl, nd.tl, nd.cb, nd.ce, nd.score_rem, bp_v, bp_h, r.score, r.score_fwd, r.score_rev, r.comp);
-      push_children(c, nd, r, bp_v, bp_h);
+      push_children(c, nd, r, bp_v, bp_h, q);
     }
   }
+  // the keeps no child took go back
+  for (int d = 0; d < 2; ++d)
+    for (std::vector<int32_t>& kept : k.kept[d]) { for (int32_t id : kept) c.keeps.drop(id); kept.clear(); }
   return WFM_OK;
 }
 
@@ -1604,6 +1927,11 @@ void print_level_totals(const AlignCall& c) {
   if (c.grown_jobs)
     fprintf(stderr, "[wfm] grown rings: %llu jobs, %llu widened and resumed, %llu started again, largest band %lld\n", (unsigned long long)c.grown_jobs,
             (unsigned long long)c.grown_widened, (unsigned long long)c.grown_restarts, (long long)c.grown_maxband);
+  if (c.reuse_children || c.h->tile_ctr[WFM_TC_REUSE_KEEPS])
+    fprintf(stderr, "[wfm] parent reuse: %llu keeps written (%.1f MB moved, store at most %.1f MB), %llu children of keeping jobs, %llu found a keep, %llu ran from it (%llu on a full ring in place of a narrow one): %llu resumed (%.1f MB moved), %llu fell back; ring arena at most %.1f MB in a chunk\n",
+            (unsigned long long)c.h->tile_ctr[WFM_TC_REUSE_KEEPS], (double)c.keep_bytes / 1048576.0, (double)c.keeps.peak / 1048576.0, (unsigned long long)c.reuse_children,
+            (unsigned long long)c.reuse_found, (unsigned long long)c.reuse_taken, (unsigned long long)c.reuse_full_rings, (unsigned long long)c.h->tile_ctr[WFM_TC_REUSE_RESUMED],
+            (double)c.restore_bytes / 1048576.0, (unsigned long long)c.h->tile_ctr[WFM_TC_REUSE_FALLBACKS], (double)c.ring_peak * 4.0 / 1048576.0);
   if (c.knobs.debug > 1) fprintf(stderr, "[wfm] ring arena: at most %.1f MB in a chunk\n", (double)c.ring_peak * 4.0 / 1048576.0);
 }
 
@@ -1815,7 +2143,7 @@ void wfm_destroy(wfm_handle_t* h) {
   h->tilejobs.release(); h->tiletasks.release(); h->tilemak.release();
   h->revjobs.release(); h->bndjobs.release(); h->bndres.release();
   if (h->stage) { (void)hipHostFree(h->stage); h->stage = nullptr; h->stage_cap = 0; }
-  h->p2rows.release(); h->p2max.release(); h->p2bmax.release(); h->p2pbmax.release(); h->p2jobs.release(); h->widenjobs.release();
+  h->p2rows.release(); h->p2max.release(); h->p2bmax.release(); h->p2pbmax.release(); h->p2jobs.release(); h->widenjobs.release(); h->keeptasks.release(); h->restoretasks.release(); h->restoreres.release();
   h->bpjobs.release(); h->bpres.release(); h->bsjobs.release(); h->bsres.release();
   h->b2tjobs.release(); h->b2ttasks.release(); h->b2tkeys.release(); h->b2toffs.release(); h->b2tactive.release();
   h->i64a.release(); h->i64b.release(); h->i64c.release(); h->i32a.release(); h->seqflags.release(); h->flagjobs.release(); h->gathertasks.release(); h->total.release();

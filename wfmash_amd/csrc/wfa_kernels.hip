@@ -838,6 +838,79 @@ __global__ __launch_bounds__(64) void wfa_tile_advance_kernel(TileJob* __restric
 }
 
 // ---------------------------------------------------------------------------
+// Parent reuse (KeepTask / RestoreTask in wfa_device.h)
+// ---------------------------------------------------------------------------
+// row r of a keep: component and how many scores behind the keep's score
+__device__ __forceinline__ void keep_row(int r, int& comp, int& back) {
+  if (r < SNAP_ROWS) { comp = C_M; back = r; return; }
+  const int q = r - SNAP_ROWS;  // I1 0, I1 1, D1 0, D1 1, I2 0, D2 0
+  comp = q < 2 ? C_I1 : (q < 4 ? C_D1 : (q == 4 ? C_I2 : C_D2));
+  back = q < 4 ? (q & 1) : 0;
+}
+// One thread per diagonal of a keep: the rows a block loads of its input snapshot, out of the ring (one strided read a row, coalesced over the
+// diagonals) into the compact copy.  Behind the chunk's last advance kernel, in its stream.
+__global__ __launch_bounds__(256) void wfa_keep_kernel(const int32_t* __restrict__ ring, const TileJob* __restrict__ jobs, const KeepTask* __restrict__ tasks) {
+  const KeepTask t = tasks[blockIdx.y];
+  const int x = blockIdx.x * 256 + threadIdx.x;
+  if (x >= t.n) return;
+  const TileJob J = jobs[t.job];
+  if (!J.active || J.mode != 0 || J.s0 != t.expect_s) return;
+  const int k = t.kmin + x;
+  const Rng RG = make_rng(J.pl, J.tl, J.sub);
+  const int64_t width = J.width;
+  const int32_t* rin = ring + J.ring_in + J.koff + (int64_t)t.dir * 5 * RING * width;
+#pragma unroll 4
+  for (int r = 0; r < KEEP_ROWS; ++r) {
+    int comp, back;
+    keep_row(r, comp, back);
+    const int sc = J.s0 - back;
+    const bool ok = sc >= 0 && k >= rng_lo(RG, sc) && k <= rng_hi(RG, sc);
+    t.dst[(int64_t)r * t.n + x] = ok ? rin[((int64_t)(comp * RING + (sc & RMASK))) * width + k] : WF_NULL;
+  }
+}
+// One thread per diagonal of a keep: its rows into the job's ring_in where the job's own rows hold the diagonal, the touch flag and the
+// direction's antidiagonal maximum over what was written
+__global__ __launch_bounds__(256) void wfa_restore_kernel(int32_t* __restrict__ ring, const TileJob* __restrict__ jobs, const RestoreTask* __restrict__ tasks,
+                                                          int32_t* __restrict__ out) {
+  const RestoreTask t = tasks[blockIdx.y];
+  const int x = blockIdx.x * 256 + threadIdx.x;
+  const TileJob J = jobs[t.job];
+  int touch = 0, mak = 0;
+  if (x < t.n && J.s0 == t.s_k) {
+    const int k = t.kmin + x;
+    if (k >= -J.pl && k <= J.tl) {
+      const Rng RG = make_rng(J.pl, J.tl, J.sub);
+      const int64_t width = J.width;
+      int32_t* rin = ring + J.ring_in + J.koff + (int64_t)t.dir * 5 * RING * width;
+      const int wall = min(J.tl, J.pl + k) - t.slack;
+      for (int r = 0; r < KEEP_ROWS; ++r) {
+        int comp, back;
+        keep_row(r, comp, back);
+        const int sc = t.s_k - back;
+        if (sc < 0 || k < rng_lo(RG, sc) || k > rng_hi(RG, sc)) continue;
+        const int v = t.src[(int64_t)r * t.n + x];
+        rin[((int64_t)(comp * RING + (sc & RMASK))) * width + k] = v;
+        touch |= v >= wall;
+        if (comp == C_M && v >= 0) mak = max(mak, 2 * v - k);
+      }
+    }
+  }
+  if (__any(touch) && (threadIdx.x & 63) == 0) atomicOr(&out[2 * blockIdx.y], 1);
+  mak = wave_max_dpp63(mak);
+  if ((threadIdx.x & 63) == 63 && mak > 0) atomicMax(&out[2 * blockIdx.y + 1], mak);
+}
+void launch_keep(const int32_t* ring, const TileJob* jobs, const KeepTask* tasks, int ntasks, int max_n, hipStream_t st) {
+  if (ntasks <= 0 || max_n <= 0) return;
+  for (int t0 = 0; t0 < ntasks; t0 += 32768)  // (a grid's second dimension ends at 65535)
+    hipLaunchKernelGGL(wfa_keep_kernel, dim3((max_n + 255) / 256, std::min(32768, ntasks - t0)), dim3(256), 0, st, ring, jobs, tasks + t0);
+}
+void launch_restore(int32_t* ring, const TileJob* jobs, const RestoreTask* tasks, int32_t* out, int ntasks, int max_n, hipStream_t st) {
+  if (ntasks <= 0 || max_n <= 0) return;
+  for (int t0 = 0; t0 < ntasks; t0 += 32768)
+    hipLaunchKernelGGL(wfa_restore_kernel, dim3((max_n + 255) / 256, std::min(32768, ntasks - t0)), dim3(256), 0, st, ring, jobs, tasks + t0, out + 2 * t0);
+}
+
+// ---------------------------------------------------------------------------
 // Phase 2 from rows computed ahead (P2Job in wfa_device.h)
 // ---------------------------------------------------------------------------
 // row s of (direction d, component cc), addressable by diagonal: a snapshot row of the ring, or one of the P2 rows

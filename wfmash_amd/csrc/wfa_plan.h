@@ -33,6 +33,8 @@ struct Node {
   int32_t band;       // bialign jobs that are run again: the band (scores a direction) of the attempt that failed, 0: it had a full ring.  Where the
                       // full ring does not fit the budget the next attempt's band grows from it (plan_ring below, called by plan_chunk)
   int32_t snap;       // bialign jobs: 1 + the index of the snapshot the job goes on from on its wider ring (GrownSnap), 0: it starts at score 0
+  int32_t keep;       // bialign jobs: 1 + the index of the kept rows of its parent that its outer direction resumes from (KeptRows), 0: both directions start at score 0
+  int32_t keep_dir;   // the direction those rows are of: 0 forward (a first child), 1 reverse (a second child)
 };
 
 // ---- the size of a ring: `w` columns of 2 directions x 5 components x RR rows of int32 ----
@@ -193,7 +195,9 @@ inline int one_tile_threads(int widest, int threads, int C) { return std::min(th
 
 // the tiles of one direction of a job: packed jobs' (wfa_tile2_kernel) apart from the others' (an N, soft-masked bases: the byte
 // kernel), which go behind them.  A task is (tile index, tile width): the kernel places it (tile_span)
-inline void append_tile_tasks(TileChunkPlan& p, int job, int dir, int ntiles, int core, bool packed) {
+// dirs: the directions of the job that run at all (bit 0 forward, bit 1 reverse; a job that waits for its parent's rows runs its inner one alone)
+inline void append_tile_tasks(TileChunkPlan& p, int job, int dir, int ntiles, int core, bool packed, int dirs = 3) {
+  if (!((dirs >> dir) & 1)) return;
   std::vector<TileTask>& to = packed ? p.tasks : p.tasks_by;
   for (int t = 0; t < ntiles; ++t) to.push_back(TileTask{(int32_t)job, dir, t, core});
 }
@@ -202,7 +206,8 @@ inline void close_task_list(TileChunkPlan& p) {
   p.tasks.insert(p.tasks.end(), p.tasks_by.begin(), p.tasks_by.end());
 }
 
-inline void plan_tile_chunk(const TilePlanJob* jobs, size_t n, const TilePlanRules& r, TileChunkPlan& p) {
+// dirs: per job the directions that get tiles (append_tile_tasks), nullptr: both of every job
+inline void plan_tile_chunk(const TilePlanJob* jobs, size_t n, const TilePlanRules& r, TileChunkPlan& p, const uint8_t* dirs = nullptr) {
   const int chunk = r.chunk, T = r.T;
   auto block_range = [&](const TilePlanJob& j, int b, int& L, int& R) { rng_block(make_rng(j.pl, j.tl, j.sub), j.s0 + b * T, j.s0 + (b + 1) * T, L, R); };
   // as many tiles of `core` diagonals per job and direction as the last block of this chunk can need
@@ -239,7 +244,7 @@ inline void plan_tile_chunk(const TilePlanJob* jobs, size_t n, const TilePlanRul
       block_range(jobs[i], b, L, R);
       ntiles = std::max(ntiles, tiles_for(L, R, p.core_c));
     }
-    for (int d = 0; d < 2; ++d) append_tile_tasks(p, (int)i, d, ntiles, p.core_c, jobs[i].packed != 0);
+    for (int d = 0; d < 2; ++d) append_tile_tasks(p, (int)i, d, ntiles, p.core_c, jobs[i].packed != 0, dirs ? dirs[i] : 3);
   }
   close_task_list(p);
   // which instantiations of the packed kernel a block of the chunk can have tiles for (wfa_tile2_kernel, FINE): the one without per-score
@@ -259,6 +264,80 @@ inline void plan_tile_chunk(const TilePlanJob* jobs, size_t n, const TilePlanRul
     }
   }
   for (int b = 0; b < chunk; ++b) if (!p.variants_b[(size_t)b]) p.variants_b[(size_t)b] = 2;  // (only runs up to a meeting point: either would do)
+}
+
+// ---- a child's outer direction from its parent's kept rows ("parent reuse") ----
+// A job's forward direction and its first child's start in the same cell, in the same component, over the same bases (and so do its reverse
+// direction and its second child's): while no cell of the parent's rows has reached the child's box, the child's own rows ARE the parent's, cut to
+// the child's ranges.  The parent keeps a compact copy of its input snapshot every `cadence` blocks (KEEP_ROWS rows a direction, each over its own
+// range); the child runs its inner direction alone up to the score of the keep it picked, takes the kept rows for the other one, and goes on as
+// any tiled job.
+// blocks between two keeps: WFM_REUSE_EVERY rounded up to whole chunks -- a keep is taken where the host looks, and a child can only take one over there
+inline int reuse_cadence(int every, int chunk) { return (std::max(1, every) + chunk - 1) / chunk * chunk; }
+// the last score a child of score `score_rem` may resume at: its meeting block must not be the first one after the restore (that block's input
+// holds the gap rows two deep and one deep, not the 26 a short run up to the meeting point hands on)
+inline int reuse_resume_limit(int score_rem, int T, int fine_margin) {
+  const int64_t x = (int64_t)score_rem / 2 - fine_margin;
+  return x < 0 ? -1 : (int)(x / T * T - T);
+}
+// the newest of the kept scores the child may take (an index into kept_s), -1: none.  min_blocks (WFM_REUSE_MIN_BLOCKS, at least 1): a keep fewer
+// blocks deep is not worth the restore -- a look of the host with a launch and a wait of its own, where the blocks it saves are a few tiles each
+inline int reuse_pick_keep(const int32_t* kept_s, size_t n, int score_rem, int T, int fine_margin, int min_blocks = 1) {
+  if (score_rem == INT_MAX) return -1;
+  const int limit = reuse_resume_limit(score_rem, T, fine_margin);
+  const int64_t least = (int64_t)std::max(1, min_blocks) * T;
+  int best = -1;
+  for (size_t i = 0; i < n; ++i)
+    if (kept_s[i] >= least && kept_s[i] <= limit && (best < 0 || kept_s[i] > kept_s[(size_t)best])) best = (int)i;
+  return best;
+}
+// every row of the keep at score s_k holds the child's whole range of that score
+inline bool reuse_ranges_contained(int ppl, int ptl, int psub, int cpl, int ctl, int csub, int s_k) {
+  const Rng P = make_rng(ppl, ptl, psub), Cc = make_rng(cpl, ctl, csub);
+  for (int s = std::max(0, s_k - RNG_BACK); s <= s_k; ++s) {
+    const int lo = rng_lo(Cc, s), hi = rng_hi(Cc, s);
+    if (hi < lo) continue;
+    if (lo < rng_lo(P, s) || hi > rng_hi(P, s)) return false;
+  }
+  return true;
+}
+// Whether a node may resume from the keep it carries: it knows its score (and the bound its parent handed it with it: a call whose children run
+// without their parents' scores -- WFM_SUB_SLACK of 2^28 and more, the tests' unbounded configuration -- computes every row itself), runs on the tile kernels on a full ring that no budget shaped,
+// and its parent's rows hold its own.  (ppl, ptl, psub: the parent's box and bound, as its rows were cut)
+inline bool reuse_eligible(const Node& nd, const RingPlan& rp, int ppl, int ptl, int psub, int child_sub, int s_k, int T) {
+  if (nd.keep <= 0 || nd.score_rem == INT_MAX || nd.sub == SUB_NONE || !rp.fits || !rp.tile_it || rp.band != 0 || rp.grown) return false;
+  if (s_k < T || s_k % T != 0) return false;
+  return reuse_ranges_contained(ppl, ptl, psub, nd.pl, nd.tl, child_sub, s_k);
+}
+// Whether a keep at score `es` can be the one a child resumes from.  The two directions of a job meet at the same score (a step apart), so
+// its children have half its score each and resume near HALF the score s_meet its directions meet at: at most s_meet / 2 - fine_margin - T, at
+// least a cadence and two blocks below that.  A child knows s_meet (half its score); a root's is read off its progress so far (reuse_meet_estimate),
+// give or take a fifth.  Keeps outside [0.4 s_meet - 64 - (2 + cadence) T, 0.6 s_meet] are not written: the copy of a keep grows with its score,
+// and all keeps up to the meeting point would be four times the bytes (a child whose keep is missing all the same starts at score 0, as ever).
+inline bool reuse_keep_wanted(int es, int64_t s_meet, int cadence, int T) {
+  if (s_meet <= 0) return false;
+  return 100 * (int64_t)es >= 40 * s_meet - 100 * (64 + (int64_t)(2 + cadence) * T) && 100 * (int64_t)es <= 60 * s_meet;
+}
+// the score a job's directions will meet at, from where it stands: at s0 with the sum `mak` of its two directions' largest antidiagonals, which
+// meet when that sum reaches A (a record with an end gap moves slowly at first: the estimate is high then); 0: nothing to go by yet
+inline int64_t reuse_meet_estimate(int s0, int64_t mak, int64_t A) { return s0 <= 0 || mak <= 0 ? 0 : (int64_t)s0 * A / mak; }
+// elements of one direction of a keep at score s: KEEP_ROWS rows over the widest of them
+inline int reuse_keep_kmin(int pl, int s) { return std::max(-pl, -s); }
+inline int reuse_keep_cols(int pl, int tl, int s) { return std::min(tl, s) - std::max(-pl, -s) + 1; }
+inline size_t reuse_keep_elems(int pl, int tl, int s) { return (size_t)KEEP_ROWS * (size_t)reuse_keep_cols(pl, tl, s); }
+// The cadence under the store's cap: what the keeping jobs would keep up to `upto` (the last score a child of theirs could resume at, where a
+// bound of the score is known; a guess otherwise) has to fit cap_bytes -- the cadence doubles until it does; 0: not even one keep a job, no reuse
+struct ReuseKeeper { int pl, tl, upto; };
+inline int reuse_fit_cadence(const ReuseKeeper* jobs, size_t n, int cadence, int T, size_t cap_bytes) {
+  int upto_max = 0;
+  for (size_t i = 0; i < n; ++i) upto_max = std::max(upto_max, jobs[i].upto);
+  for (; (int64_t)cadence * T <= upto_max; cadence *= 2) {
+    size_t bytes = 0;
+    for (size_t i = 0; i < n && bytes <= cap_bytes; ++i)
+      for (int64_t s = (int64_t)cadence * T; s <= jobs[i].upto && bytes <= cap_bytes; s += (int64_t)cadence * T) bytes += 2 * 4 * reuse_keep_elems(jobs[i].pl, jobs[i].tl, (int)s);
+    if (bytes <= cap_bytes) return cadence;
+  }
+  return 0;
 }
 
 // ---- a chunk of phase 2 from rows computed ahead (run_p2_phase): P2K more rows of both directions of every job ----

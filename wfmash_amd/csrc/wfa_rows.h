@@ -44,6 +44,7 @@ WFM_ROWS_FN int rng_hi(const Rng& r, int s) { return rows_min(rows_min(r.tl, s),
 // jobs, did: a false breakpoint one point under the optimum.)
 constexpr int RNG_BACK = 25;
 constexpr int SNAP_ROWS = RNG_BACK + 1;  // rows of a snapshot that phase 2 reads: scores sd - RNG_BACK .. sd (the default penalties' scope)
+constexpr int KEEP_ROWS = SNAP_ROWS + 6;  // rows of a kept snapshot (parent reuse): M of scores s - RNG_BACK .. s, I1 / D1 of s and s - 1, I2 / D2 of s -- what a block loads
 constexpr int P2_BACK = SNAP_ROWS + 1;   // the window of phase-2 rows begins this far before the earlier direction's score: the snapshot's rows and one of margin
 WFM_ROWS_FN void rng_block(const Rng& r, int s_from, int s_to, int& L, int& R) {
   L = rows_max(rows_max(-r.pl, -s_to), r.kb_lo + s_from - RNG_BACK);

@@ -185,6 +185,59 @@ int wfmh_test_tile_plan(const int32_t* jobs, int64_t n, const int32_t* rules, in
   return 0;
 }
 
+// test hook: the planning of parent reuse (csrc/wfa_plan.h), pure arithmetic.
+// op 0: reuse_pick_keep -- in = score_rem, T, fine_margin, min_blocks, then n kept scores; out = {index picked or -1, reuse_resume_limit}
+// op 1: reuse_eligible -- in = child pl, tl, score_rem, the sub its job runs under (the node's bound is score_rem + 56, none without a score), keep; its ring plan: fits, tile_it, band, grown; the keeping job's
+//       pl, tl, sub; s_k; T (n is not used); out = {0 / 1}
+// op 2: the cadence -- in = every, chunk, T, cap in bytes, then n x (pl, tl, upto); out = {reuse_cadence, reuse_fit_cadence from it}
+// op 3: reuse_keep_wanted on reuse_meet_estimate -- in = s0, es, mak, A, cadence, T; out = {0 / 1, the estimate}
+int wfmh_test_reuse_plan(int op, const int64_t* in, int64_t n, int64_t* out) {
+  if (op == 0) {
+    std::vector<int32_t> kept((size_t)n);
+    for (int64_t i = 0; i < n; ++i) kept[(size_t)i] = (int32_t)in[4 + i];
+    out[0] = wfm::reuse_pick_keep(kept.data(), kept.size(), (int)in[0], (int)in[1], (int)in[2], (int)in[3]);
+    out[1] = in[0] == INT_MAX ? -1 : wfm::reuse_resume_limit((int)in[0], (int)in[1], (int)in[2]);
+    return 0;
+  }
+  if (op == 1) {
+    wfm::Node nd{};
+    nd.pl = (int32_t)in[0]; nd.tl = (int32_t)in[1]; nd.score_rem = (int32_t)in[2]; nd.keep = (int32_t)in[4];
+    nd.sub = nd.score_rem == INT_MAX ? wfm::SUB_NONE : nd.score_rem + 56;
+    wfm::RingPlan rp;
+    rp.fits = in[5] != 0; rp.tile_it = in[6] != 0; rp.band = (int)in[7]; rp.grown = in[8] != 0;
+    out[0] = wfm::reuse_eligible(nd, rp, (int)in[9], (int)in[10], (int)in[11], (int)in[3], (int)in[12], (int)in[13]);
+    return 0;
+  }
+  if (op == 2) {
+    if (in[0] < 1 || in[1] < 1 || in[2] < 1) return -1;
+    std::vector<wfm::ReuseKeeper> kp((size_t)n);
+    for (int64_t i = 0; i < n; ++i) kp[(size_t)i] = wfm::ReuseKeeper{(int)in[4 + 3 * i], (int)in[5 + 3 * i], (int)in[6 + 3 * i]};
+    out[0] = wfm::reuse_cadence((int)in[0], (int)in[1]);
+    out[1] = wfm::reuse_fit_cadence(kp.data(), kp.size(), (int)out[0], (int)in[2], (size_t)in[3]);
+    return 0;
+  }
+  if (op == 3) {  // reuse_keep_wanted with reuse_meet_estimate: in = s0, es, mak, A, cadence, T
+    out[1] = wfm::reuse_meet_estimate((int)in[0], in[2], in[3]);
+    out[0] = wfm::reuse_keep_wanted((int)in[1], out[1], (int)in[4], (int)in[5]);
+    return 0;
+  }
+  return -1;
+}
+
+// test hook: plan_tile_chunk with a direction mask per job (dirs: n bytes, bit 0 forward, bit 1 reverse); everything else as wfmh_test_tile_plan
+int wfmh_test_tile_plan_dirs(const int32_t* jobs, int64_t n, const int32_t* rules, const uint8_t* dirs, int32_t* per_block, int32_t* tasks, int64_t tasks_cap,
+                             int64_t* scalars) {
+  wfm::TilePlanRules r{rules[0], rules[1], rules[2], rules[3], rules[4], rules[5] != 0, rules[6] != 0, rules[7] != 0};
+  if (r.chunk < 1 || r.T < 1 || r.threads < 1 || r.C < 1 || r.core < 1) return -1;
+  wfm::TileChunkPlan p;
+  wfm::plan_tile_chunk(reinterpret_cast<const wfm::TilePlanJob*>(jobs), (size_t)n, r, p, dirs);
+  std::copy(p.threads_b.begin(), p.threads_b.end(), per_block);
+  std::copy(p.variants_b.begin(), p.variants_b.end(), per_block + r.chunk);
+  memcpy(tasks, p.tasks.data(), std::min<size_t>(p.tasks.size(), (size_t)tasks_cap) * sizeof(wfm::TileTask));
+  scalars[0] = p.core_c; scalars[1] = (int64_t)p.tasks.size(); scalars[2] = (int64_t)p.n_pk;
+  return 0;
+}
+
 // test hook: plan_p2_chunk (csrc/wfa_plan.h) with P2K = rows and P2ROWS = rows_bm.  cand: n x (pl, tl, sub, sf, sr, packed); geo: per job taken
 // (koff2, w2, nblk, p2_off, bm_off); scalars = {jobs taken, elems, bm_elems, maxw2, threads_c, core_c, tasks, n_pk}
 int wfmh_test_p2_plan(const int32_t* cand, int64_t n, int64_t i0, int rows, int rows_bm, unsigned long long budget, int threads, int core, int64_t* geo,
