@@ -103,6 +103,11 @@ int wfmh_test_base_plan(int op, const int32_t* in, int64_t n, int32_t* out);
 int wfmh_test_reuse_plan(int op, const int64_t* in, int64_t n, int64_t* out);
 int wfmh_test_tile_plan_dirs(const int32_t* jobs, int64_t n, const int32_t* rules, const uint8_t* dirs, int32_t* per_block, int32_t* tasks, int64_t tasks_cap,
                              int64_t* scalars);
+/* ... and of the packed tile kernel's lean snapshot paths (csrc/wfa_rows.h): rng_interior against one query of (pl, tl, sub, first diagonal, last
+ * diagonal, first score, last score) each, and the waves of one block of a job that pass the kernel's two wave tests (wrapped by
+ * tests/test_tile_interior_cpu.py and tests/test_tile_lean_gpu.py) */
+int wfmh_test_tile_interior(const int32_t* q, int64_t n, int32_t* out);
+int wfmh_test_tile_lean_waves(const int32_t* in, int64_t* out);
 /* host winnowing stage of wfm_add_minmers on caller-supplied canonical k-mer hashes (CPU tests) */
 int64_t wfmh_test_winnow(const char* seq, int64_t len, int k, int w, int s, int32_t seq_id,
                          const uint64_t* hash, const int8_t* strand, wfm_minmer_t* out, int64_t cap);

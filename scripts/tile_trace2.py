@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """The split of a tile's life into snapshot load, steps and snapshot store (scripts/tile_trace.sh with TRACE_LEVEL=2 builds the library):
-one s_memtime stamp per ten-step body and four around the loop, per wave, of the first 48 workgroups of the launch that begins at score 3000, a list of more than 1024 tiles,
-of one C3 batch on one stream."""
+one s_memtime stamp per ten-step body and six around the loop, per wave, of the first 48 workgroups of the launch that begins at score 4000, a list of at least 512 tiles,
+of one C3 batch on one stream.  (Score 3000 and more than 1024 tiles until the lean snapshot paths: a C3 batch's launch at 3000 is exactly 1024 tiles now and was not sampled.)
+WFM_TILE_LEAN=0 in the environment: every wave on the general snapshot paths."""
 import ctypes as C
 import os
 import sys
@@ -24,7 +25,7 @@ buf = np.zeros(n, dtype=np.uint64)
 assert L.wfm_debug_tile_trace(buf.ctypes.data_as(C.c_void_p), n) == 0
 a = buf.reshape(48, 16, 128, 4)[:, :, :, 0].astype(np.int64)
 load, loop, store, life, body, ld_rows, ld_wlo, ld_win = [], [], [], [], [], [], [], []
-cl_lo, cl_hi = 1, np.iinfo(np.int64).max  # (the kernel stamps one launch only: the blocks that begin at score 3000)
+cl_lo, cl_hi = 1, np.iinfo(np.int64).max  # (the kernel stamps one launch only: the blocks that begin at score 4000)
 for b in range(48):
     for w in range(16):
         r = a[b, w]

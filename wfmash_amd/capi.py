@@ -884,7 +884,7 @@ HOST_EXPORTS = ["wfmh_test_packed_lce", "wfmh_test_is_acgt", "wfmh_align_default
                 "wfmh_map_multi", "wfmh_align_paf_multi", "wfmh_test_winnow_model", "wfmh_test_sortlike_model", "wfmh_test_finish_records",
                 "wfmh_release_sequences", "wfmh_test_fasta_shared", "wfmh_seed_paf", "wfmh_test_deal", "wfmh_test_subwindow",
                 "wfmh_test_rows", "wfmh_test_tile_plan", "wfmh_test_p2_plan", "wfmh_test_base_plan", "wfmh_test_map_plan", "wfmh_test_filter_ordered",
-                "wfmh_test_reuse_plan", "wfmh_test_tile_plan_dirs"]
+                "wfmh_test_reuse_plan", "wfmh_test_tile_plan_dirs", "wfmh_test_tile_interior", "wfmh_test_tile_lean_waves"]
 
 
 class MapSummary(C.Structure):

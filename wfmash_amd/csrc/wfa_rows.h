@@ -51,6 +51,32 @@ WFM_ROWS_FN void rng_block(const Rng& r, int s_from, int s_to, int& L, int& R) {
   R = rows_min(rows_min(r.tl, s_to), r.kb_hi - s_from + RNG_BACK);
 }
 
+// Does every diagonal of [k_first, k_last] lie inside its row at EVERY score of [s_first, s_last]?  The two end rows decide it.  A diagonal k is
+// inside row s where -pl <= k <= tl (no matter of s), |k| <= s and s <= min(k - kb_lo, kb_hi - k): the triangle only ever lets a diagonal
+// in as the score grows, the score bound's cone only ever lets it out, so the scores at which k is inside are one interval and k is inside
+// at every score between two at which it is.  A row's range is an interval of diagonals as well, so the span is inside a row when its two
+// end diagonals are.  Exact, not only sufficient: a span that fails at an end row is not inside at that row.  (No row of a negative score
+// holds a cell -- rng_lo > rng_hi there -- and an empty span or an empty interval of scores is never "inside".)
+WFM_ROWS_FN bool rng_interior(const Rng& r, int k_first, int k_last, int s_first, int s_last) {
+  return k_first <= k_last && s_first <= s_last && k_first >= rows_max(rng_lo(r, s_first), rng_lo(r, s_last)) &&
+         k_last <= rows_min(rng_hi(r, s_first), rng_hi(r, s_last));
+}
+// The two tests by which a wave of the packed tile kernel (wfa_tile2.hip: two diagonals a lane, WAVE_DIAGS a wave, the first of them kw) takes
+// its lean snapshot paths, from wave-uniform values alone.  Load: every lane's pair is the tile's and inside every row the block starts from
+// (M of scores s0 - RNG_BACK .. s0; the gap rows loaded are of s0 and s0 - 1).  Store: the block wrote a whole snapshot (Tn >= SNAP_ROWS steps),
+// and the part of the wave that lies in the tile's core -- all of it, or what a halo leaves of the tile's first and last wave -- is made of whole
+// lanes (a lane's pair is the core's or it is not: the part begins and ends an even number of diagonals from kw) and is inside every row of the
+// snapshot.  The lanes of that part then store their pairs without a test; the others store nothing, as in the general form.
+constexpr int WAVE_DIAGS = 128;
+WFM_ROWS_FN bool tile_wave_lean_load(const Rng& r, int kw, int kmax, int s0) {
+  return kw + WAVE_DIAGS - 1 <= kmax && s0 - RNG_BACK >= 0 && rng_interior(r, kw, kw + WAVE_DIAGS - 1, s0 - RNG_BACK, s0);
+}
+WFM_ROWS_FN bool tile_wave_lean_store(const Rng& r, int kw, int core_lo, int core_hi, int s_end, int Tn) {
+  const int a = rows_max(kw, core_lo), b = rows_min(kw + WAVE_DIAGS - 1, core_hi);
+  return Tn >= SNAP_ROWS && a <= b && ((a - kw) & 1) == 0 && ((b + 1 - kw) & 1) == 0 && s_end - RNG_BACK >= 0 &&
+         rng_interior(r, a, b, s_end - RNG_BACK, s_end);
+}
+
 // a workgroup of a tile launch
 struct TileTask {
   int32_t job, dir;

@@ -393,7 +393,7 @@ __global__ __launch_bounds__(NTMAX) void wfa_tile2_kernel(const uint32_t* __rest
   const int nw = min((int)(blockDim.x >> 6), (tk.core_hi + halo - kA) / (64 * C) + 1), NT = nw * 64;
   if (wv >= nw) return;
 #ifdef WFM_TILE_TRACE
-  const bool trace_on2 = !P2 && FAST && !WAVE1 && gridDim.x > 1024 && blockIdx.x < 48 && sbase == 3000 && J.mode == 0;  // (one launch in the middle of a deep job's run)
+  const bool trace_on2 = !P2 && FAST && !WAVE1 && gridDim.x >= 512 && blockIdx.x < 48 && sbase == 4000 && J.mode == 0;  // (one launch in the middle of a deep job's run)
 #endif
   WFM_TRACE_MARK(120);
   if (tid < 2) s_wlo[tid] = INT32_MAX;
@@ -414,7 +414,7 @@ __global__ __launch_bounds__(NTMAX) void wfa_tile2_kernel(const uint32_t* __rest
   // because the directions met in it (mode 5), and the blocks from fine_s on -- the FINE instantiation's tiles.  Elsewhere one running maximum per
   // lane and ONE wave reduction per block (mode 1, the run up to the meeting point: none at all -- nobody reads its maxima)
   if (!P2 && FAST && !(coarse & 2)) {  // (bit 1: the only instantiation launched for this block -- the FINE one -- takes every tile)
-    const bool fine = !coarse || J.mode == 5 || (J.mode == 0 && sbase + T >= J.fine_s);
+    const bool fine = !(coarse & 1) || J.mode == 5 || (J.mode == 0 && sbase + T >= J.fine_s);
     if (fine != FINE) return;
   }
   // (the running maximum of a lane lives in LDS, one ds_max_i32 per step into the lane's own word: as a register carried around the step loop it
@@ -429,7 +429,32 @@ __global__ __launch_bounds__(NTMAX) void wfa_tile2_kernel(const uint32_t* __rest
   // (round 6: a lane's two diagonals are one 8-byte load -- dword alignment is all a global load needs; with one 4-byte load per diagonal every
   // load instruction used half of each cache line it touched and the lines came up from L2 twice, the tile's 26 rows of M for one diagonal lying
   // between the two uses)
-  {
+  // Lean load (WFM_TILE_LEAN, bit 2 of `coarse`): a wave whose 128 diagonals are the tile's and inside every row it loads -- all waves of a wide
+  // job's tiles but those at the two ends of its rows -- has nothing to filter: 32 unconditional 8-byte loads from a wave-uniform row address plus
+  // the lane's own 8 bytes.  The test (tile_wave_lean_load, wfa_rows.h) is made of wave-uniform values and picks a path; it never changes a value.
+  const bool lean_on = (coarse & 4) != 0;
+  if (lean_on && tile_wave_lean_load(RG, __builtin_amdgcn_readfirstlane(k0), kmax, s0)) {
+    const int32_t* const wrow = rin + __builtin_amdgcn_readfirstlane(k0);  // the wave's first diagonal in row 0 of component 0
+    const unsigned lofs = (unsigned)lane * (unsigned)(C * sizeof(int32_t));
+    auto ld_lean = [&](int comp, int sc, int& a, int& b) {
+      ld_pair(reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(wrow + ((int64_t)(comp * RING + (sc & RMASK))) * width) + lofs), a, b);
+    };
+#pragma unroll
+    for (int d = 0; d < H; ++d) ld_lean(C_M, s0 - d, Mh[0][(NCL - d % NCL) % NCL][d / NCL], Mh[1][(NCL - d % NCL) % NCL][d / NCL]);
+#pragma unroll
+    for (int r = 1; r < NCL; ++r) { Mh[0][r][DEP - 1] = WF_NULL; Mh[1][r][DEP - 1] = WF_NULL; }  // (26 rows: class 0 has six, the others five)
+#pragma unroll
+    for (int d = 0; d < E1; ++d) {
+      ld_lean(C_I1, s0 - d, I1h[0][d], I1h[1][d]);
+      ld_lean(C_D1, s0 - d, D1h[0][d], D1h[1][d]);
+    }
+    ld_lean(C_I2, s0, I2h[0], I2h[1]);
+    ld_lean(C_D2, s0, D2h[0], D2h[1]);
+  } else {
+    // (Nothing of the kernel's entry -- the job's and the task's fields -- may still be on its way when the 32 row loads begin: a field first
+    // used behind them keeps its register pending, the row arithmetic's temporaries land on such registers, and every one of those writes waits
+    // for the counter to drain -- in order, so for the row loads issued before it as well.  One explicit wait, vmcnt(0), before the first row.)
+    __builtin_amdgcn_s_waitcnt(0x0F70);
     const bool kin0 = k0 <= kmax, kin1 = k0 + 1 <= kmax;
 #pragma unroll
     for (int c = 0; c < C; ++c)
@@ -880,8 +905,26 @@ __global__ __launch_bounds__(NTMAX) void wfa_tile2_kernel(const uint32_t* __rest
       }
     }
   }
+  // Lean store (WFM_TILE_LEAN): a wave whose diagonals of the tile's core are whole lanes and inside every row of the snapshot
+  // (tile_wave_lean_store, wfa_rows.h; wave-uniform) writes its 26 rows of M as 8-byte stores to a wave-uniform row address plus the lane's own
+  // 8 bytes, under ONE mask: the lanes of the core (all of them but in a tile's first and last wave, which begin and end in the halo).  (As
+  // compiled: 25 global_store_dwordx2 a copy; the optimizer shares the oldest row, s_end - 25, with the general code's tail as two 4-byte stores.)
+  const int k0w = __builtin_amdgcn_readfirstlane(k0);
+  const bool lean_st = (coarse & 4) != 0 && tile_wave_lean_store(RG, k0w, tk.core_lo, tk.core_hi, s_end, Tn);
+  int32_t* const wrow_out = rout + k0w;
+  const unsigned lofs_out = (unsigned)lane * (unsigned)(C * sizeof(int32_t));
   auto write_rows = [&](auto TR) {
     constexpr int tr = decltype(TR)::value;  // T mod 5
+    if (lean_st) {
+      if (incore[0])
+#pragma unroll
+      for (int d = 0; d < H; ++d) {
+        const int r = ((tr - d) % NCL + NCL) % NCL, back = ((tr - r) % NCL + NCL) % NCL, e = (d - back) / NCL;  // (as below)
+        char* const row = reinterpret_cast<char*>(wrow_out + ((int64_t)(C_M * RING + ((s_end - d) & RMASK))) * width);
+        st_pair(reinterpret_cast<int32_t*>(row + lofs_out), Mh[0][r][e], Mh[1][r][e]);
+      }
+      return;
+    }
     if (!incore[0] && !incore[1]) return;
 #pragma unroll
     for (int d = 0; d < H; ++d) {
@@ -931,6 +974,10 @@ static bool tile_fast() {  // (read per launch: the tests switch forms inside on
   const char* e = getenv("WFM_TILE_FAST");
   return !(e && atoi(e) == 0);
 }
+static int tile_lean() {  // WFM_TILE_LEAN (read per launch): bit 2 of the kernel's flag word -- interior waves load and store their snapshots without range tests
+  const char* e = getenv("WFM_TILE_LEAN");
+  return (e && atoi(e) == 0) ? 0 : 4;
+}
 bool tile2_coarse_maxima() {  // (read per launch, like tile_fast)
   const char* e = getenv("WFM_TILE_COARSE");
   return tile_fast() && !(e && atoi(e) == 0);
@@ -940,33 +987,35 @@ bool tile2_coarse_maxima() {  // (read per launch, like tile_fast)
 void launch_tile2(const uint32_t* pk, int32_t* ring, const TileJob* jobs, const TileTask* tasks, int32_t* mak, int ntasks, int threads, int T,
                   int variants, hipStream_t st) {
   const size_t lds1 = (size_t)(T + 1) * 4;
+  const int lean = tile_lean();
   if (tile_fast()) {
     const int coarse = tile2_coarse_maxima() ? 1 : 0;
     if (!coarse) variants = 2;
     // (WFM_TILE_LDS_PAD: bytes of LDS nobody uses, to take workgroups off a CU -- the occupancy experiment of DESIGN section 5, round 6)
     const size_t pad = getenv("WFM_TILE_LDS_PAD") ? (size_t)atoi(getenv("WFM_TILE_LDS_PAD")) : 0;
     if (variants & 1) {
-      if (threads <= 64) hipLaunchKernelGGL((wfa_tile2_kernel<64, false, true, false>), dim3(ntasks), dim3(64), 0, st, pk, ring, jobs, tasks, mak, T, (int32_t*)nullptr, coarse);
-      else hipLaunchKernelGGL((wfa_tile2_kernel<1024, false, true, false>), dim3(ntasks), dim3(threads), pad, st, pk, ring, jobs, tasks, mak, T, (int32_t*)nullptr, coarse);
+      if (threads <= 64) hipLaunchKernelGGL((wfa_tile2_kernel<64, false, true, false>), dim3(ntasks), dim3(64), 0, st, pk, ring, jobs, tasks, mak, T, (int32_t*)nullptr, coarse | lean);
+      else hipLaunchKernelGGL((wfa_tile2_kernel<1024, false, true, false>), dim3(ntasks), dim3(threads), pad, st, pk, ring, jobs, tasks, mak, T, (int32_t*)nullptr, coarse | lean);
     }
     if (variants & 2) {
       const int cf = coarse | (variants == 2 ? 2 : 0);
-      if (threads <= 64) hipLaunchKernelGGL((wfa_tile2_kernel<64, false, true, true>), dim3(ntasks), dim3(64), lds1, st, pk, ring, jobs, tasks, mak, T, (int32_t*)nullptr, cf);
-      else hipLaunchKernelGGL((wfa_tile2_kernel<1024, false, true, true>), dim3(ntasks), dim3(threads), lds1 * (size_t)(threads / 64), st, pk, ring, jobs, tasks, mak, T, (int32_t*)nullptr, cf);
+      if (threads <= 64) hipLaunchKernelGGL((wfa_tile2_kernel<64, false, true, true>), dim3(ntasks), dim3(64), lds1, st, pk, ring, jobs, tasks, mak, T, (int32_t*)nullptr, cf | lean);
+      else hipLaunchKernelGGL((wfa_tile2_kernel<1024, false, true, true>), dim3(ntasks), dim3(threads), lds1 * (size_t)(threads / 64), st, pk, ring, jobs, tasks, mak, T, (int32_t*)nullptr, cf | lean);
     }
   } else {
-    if (threads <= 64) hipLaunchKernelGGL((wfa_tile2_kernel<64, false, false, true>), dim3(ntasks), dim3(64), lds1, st, pk, ring, jobs, tasks, mak, T, (int32_t*)nullptr, 0);
-    else hipLaunchKernelGGL((wfa_tile2_kernel<1024, false, false, true>), dim3(ntasks), dim3(threads), lds1, st, pk, ring, jobs, tasks, mak, T, (int32_t*)nullptr, 0);
+    if (threads <= 64) hipLaunchKernelGGL((wfa_tile2_kernel<64, false, false, true>), dim3(ntasks), dim3(64), lds1, st, pk, ring, jobs, tasks, mak, T, (int32_t*)nullptr, lean);
+    else hipLaunchKernelGGL((wfa_tile2_kernel<1024, false, false, true>), dim3(ntasks), dim3(threads), lds1, st, pk, ring, jobs, tasks, mak, T, (int32_t*)nullptr, lean);
   }
 }
 void launch_tile2_p2(const uint32_t* pk, int32_t* ring, const TileJob* jobs, const TileTask* tasks, int ntasks, int threads, int32_t* p2, hipStream_t st) {
   const size_t lds1 = (size_t)(P2K + 1) * 4;
+  const int lean = tile_lean();
   if (tile_fast()) {
-    if (threads <= 64) hipLaunchKernelGGL((wfa_tile2_kernel<64, true, true, false>), dim3(ntasks), dim3(64), 0, st, pk, ring, jobs, tasks, (int32_t*)nullptr, P2K, p2, 0);
-    else hipLaunchKernelGGL((wfa_tile2_kernel<1024, true, true, false>), dim3(ntasks), dim3(threads), 0, st, pk, ring, jobs, tasks, (int32_t*)nullptr, P2K, p2, 0);
+    if (threads <= 64) hipLaunchKernelGGL((wfa_tile2_kernel<64, true, true, false>), dim3(ntasks), dim3(64), 0, st, pk, ring, jobs, tasks, (int32_t*)nullptr, P2K, p2, lean);
+    else hipLaunchKernelGGL((wfa_tile2_kernel<1024, true, true, false>), dim3(ntasks), dim3(threads), 0, st, pk, ring, jobs, tasks, (int32_t*)nullptr, P2K, p2, lean);
   } else {
-    if (threads <= 64) hipLaunchKernelGGL((wfa_tile2_kernel<64, true, false, true>), dim3(ntasks), dim3(64), lds1, st, pk, ring, jobs, tasks, (int32_t*)nullptr, P2K, p2, 0);
-    else hipLaunchKernelGGL((wfa_tile2_kernel<1024, true, false, true>), dim3(ntasks), dim3(threads), lds1, st, pk, ring, jobs, tasks, (int32_t*)nullptr, P2K, p2, 0);
+    if (threads <= 64) hipLaunchKernelGGL((wfa_tile2_kernel<64, true, false, true>), dim3(ntasks), dim3(64), lds1, st, pk, ring, jobs, tasks, (int32_t*)nullptr, P2K, p2, lean);
+    else hipLaunchKernelGGL((wfa_tile2_kernel<1024, true, false, true>), dim3(ntasks), dim3(threads), lds1, st, pk, ring, jobs, tasks, (int32_t*)nullptr, P2K, p2, lean);
   }
 }
 

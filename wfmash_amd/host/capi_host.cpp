@@ -169,6 +169,51 @@ int wfmh_test_rows(const int32_t* q, int64_t n, int64_t* out) {
   return 0;
 }
 
+// test hook: the interior test of csrc/wfa_rows.h, n queries of 7 numbers (pl, tl, sub, first diagonal, last diagonal, first score, last score),
+// three results each: rng_interior's answer, then rng_lo and rng_hi at the FIRST score (a brute force asks about one score at a time)
+int wfmh_test_tile_interior(const int32_t* q, int64_t n, int32_t* out) {
+  for (int64_t i = 0; i < n; ++i, q += 7, out += 3) {
+    const wfm::Rng r = wfm::make_rng(q[0], q[1], q[2]);
+    out[0] = wfm::rng_interior(r, q[3], q[4], q[5], q[6]) ? 1 : 0;
+    out[1] = wfm::rng_lo(r, q[5]);
+    out[2] = wfm::rng_hi(r, q[5]);
+  }
+  return 0;
+}
+
+// test hook: the waves of the packed tile kernel (csrc/wfa_tile2.hip) that take the lean snapshot paths in ONE block of one direction of a job:
+// in = pl, tl, sub, s0 (the score the block starts from), T, Tn (the steps it takes: T, or fewer in the run up to the meeting point), core, threads.
+// The block's range cut into tile_span's tiles, each tile's waves as the kernel lays them out (a halo of T diagonals on either side unless the
+// block is one tile; two diagonals a lane), and tile_wave_lean_load / tile_wave_lean_store on each -- the predicate the kernel evaluates, no
+// counter of the kernel's.  out = {tiles, waves, waves that pass the load test, waves that pass the store test, tiles that hold waves of both kinds
+// at the load}
+int wfmh_test_tile_lean_waves(const int32_t* in, int64_t* out) {
+  const wfm::Rng r = wfm::make_rng(in[0], in[1], in[2]);
+  const int s0 = in[3], T = in[4], Tn = in[5], core = in[6], threads = in[7];
+  if (T < 1 || core < 1 || threads < 64) return -1;
+  int L, R;
+  wfm::rng_block(r, s0, s0 + T, L, R);
+  const int nt = wfm::tiles_for(L, R, core);
+  out[0] = nt; out[1] = out[2] = out[3] = out[4] = 0;
+  for (int idx = 0; idx < nt; ++idx) {
+    int lo, hi;
+    wfm::tile_span(L, R, idx, core, &lo, &hi);
+    const int halo = (lo == L && hi == R) ? 0 : T;
+    const int kA = lo - halo, kmax = hi + halo;
+    const int nw = std::min(threads / 64, (kmax - kA) / wfm::WAVE_DIAGS + 1);
+    int lean_here = 0;
+    for (int w = 0; w < nw; ++w) {
+      const int kw = kA + w * wfm::WAVE_DIAGS;
+      out[1] += 1;
+      lean_here += wfm::tile_wave_lean_load(r, kw, kmax, s0) ? 1 : 0;
+      out[3] += wfm::tile_wave_lean_store(r, kw, lo, hi, s0 + Tn, Tn) ? 1 : 0;
+    }
+    out[2] += lean_here;
+    out[4] += (lean_here > 0 && lean_here < nw) ? 1 : 0;
+  }
+  return 0;
+}
+
 // test hook: plan_tile_chunk (csrc/wfa_plan.h).  jobs: n x (pl, tl, sub, s0, mode, fine_s, packed, active); rules: threads, C, T, chunk, core, reg,
 // fine, coarse_on.  per_block: threads_b then variants_b (chunk each); tasks: (job, dir, tile, core) each, at most tasks_cap of them are written;
 // scalars = {core_c, tasks, n_pk}
