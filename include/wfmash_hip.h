@@ -69,6 +69,8 @@ extern "C" {
  * record's length: where a ring over all diagonals does not fit, rings grow with the score a job reaches (about 2 x score columns of
  * 1280 bytes -- 5120 for penalties of a scope beyond 30 -- have to fit the budget). */
 #define WFM_ST_OOM         (-200)
+/* The optimal score is beyond the problem's score limit (WFM_MODE_SCORE_LIMIT below); mirrors WF_STATUS_MAX_STEPS_REACHED. */
+#define WFM_ST_MAX_SCORE   (-100)
 
 #define WFMASH_HIP_VERSION "wfmash-hip-0.3"   /* SAM @PG VN:, `wfmash-hip --version` */
 
@@ -81,18 +83,42 @@ typedef struct { int32_t x, o1, e1, o2, e2; } wfm_penalties_t;
 #define WFM_MODE_END2END_BIWFA 0   /* alignEnd2End, MemoryUltralow  (wflign.cpp:136-148) */
 #define WFM_MODE_ENDSFREE      1   /* alignEndsFree, MemoryMed      (wflign.cpp:280-305,368-397) */
 #define WFM_MODE_END2END_UNI   2   /* alignEnd2End, full backtrace (MemoryHigh)            */
+/* Flags, OR-ed into `mode` with one of the three modes above (wfm_problem_t and wfm_problem_ref_t alike).
+ *
+ * WFM_MODE_SCORE_ONLY (WFAligner's AlignmentScope Score), with any of the three modes: the result carries status, score and
+ * cells, ops_len = n_runs = 0, and nothing of the problem is written to the ops arena or to the runs.  score is the optimal
+ * gap-affine-2p score -- end-to-end for modes 0 and 2, ends-free for mode 1 -- exactly what the full alignment of the same
+ * problem reports; the device stops where it knows it: a BiWFA root at the score its directions meet at (no children, no
+ * leaves), a base job behind its forward pass (no walk back).  wfm_align_arena_bytes counts 0 for such problems,
+ * wfm_align_batch accepts ops_arena == NULL with arena_bytes == 0 when every problem is score-only, and score-only and full
+ * problems may be mixed in one call through every entry point.  wfm_get_problem_flags reports the paths taken, as ever.
+ *
+ * WFM_MODE_SCORE_LIMIT (WFAligner::setMaxAlignmentSteps), END2END_BIWFA only: score_hint (> 0) is a hard limit instead of a
+ * guess.  status is WFM_ST_OK with the exact result (the score, and the op string unless SCORE_ONLY) if and only if the optimal
+ * score is <= score_hint; otherwise status is WFM_ST_MAX_SCORE, score is -1 and there are no ops -- a failed problem in the
+ * call's return value like any other.  There is never a second run without the limit, no wavefront is computed beyond it
+ * (tile blocks stop at the first block that begins at or past it, the step kernel at the first score past it, a short
+ * problem's base job runs with the limit as its score budget), and it holds whatever the WFM_* environment switches say
+ * about hints and bounds.  With another mode, or with score_hint <= 0, the upload fails with WFM_E_ARG.
+ *
+ * Every upload (wfm_upload_sequences, wfm_upload_sequence_refs and the calls built on them) checks `mode`: a mode other than
+ * 0, 1, 2 under WFM_MODE_MASK or a bit outside the mask and the two flags is WFM_E_ARG with a message; the handle stays usable. */
+#define WFM_MODE_MASK        0xff
+#define WFM_MODE_SCORE_ONLY  0x100
+#define WFM_MODE_SCORE_LIMIT 0x200
 
 typedef struct {
   const char* pattern;  int32_t plen;     /* wfmash passes pattern = target */
   const char* text;     int32_t tlen;     /* wfmash passes text    = query  */
-  int32_t mode;                           /* WFM_MODE_*                      */
+  int32_t mode;                           /* WFM_MODE_*, optionally | WFM_MODE_SCORE_ONLY | WFM_MODE_SCORE_LIMIT */
   int32_t pattern_begin_free, pattern_end_free;   /* ENDSFREE only */
   int32_t text_begin_free, text_end_free;
   int32_t score_hint;                     /* END2END_BIWFA only; 0 = none.  A guess of an upper bound of the alignment's
                                            * score (e.g. the cost of the end gaps the caller's padding implies plus a
                                            * divergence allowance).  The wavefronts are then only computed where an
                                            * alignment of at most that score can pass; a guess that turns out too small
-                                           * costs a second run without it, never a different result. */
+                                           * costs a second run without it, never a different result.  With
+                                           * WFM_MODE_SCORE_LIMIT: the hard limit of the score (see above). */
   int32_t pad_;
 } wfm_problem_t;
 
@@ -140,7 +166,7 @@ const char* wfm_last_error(const wfm_handle_t* h);
 int  wfm_device_name(const wfm_handle_t* h, char* buf, size_t buflen);
 
 /* Upper bound of the ops_arena bytes wfm_align_batch needs for these problems
- * (sum of plen+tlen+1). */
+ * (sum of plen+tlen+1 over the problems that are not WFM_MODE_SCORE_ONLY). */
 size_t wfm_align_arena_bytes(const wfm_problem_t* problems, size_t n);
 
 /* Align n problems.  out[i].ops_off/ops_len locate the op string of problem i

@@ -15,6 +15,11 @@ LIB_PATH = os.environ.get("WFM_LIB_PATH") or os.path.join(_HERE, "libwfmash_hip.
 WFM_MODE_END2END_BIWFA = 0
 WFM_MODE_ENDSFREE = 1
 WFM_MODE_END2END_UNI = 2
+# flags OR-ed into a problem's mode (include/wfmash_hip.h): the score alone; score_hint as a hard limit of the score (END2END_BIWFA)
+WFM_MODE_MASK = 0xff
+WFM_MODE_SCORE_ONLY = 0x100
+WFM_MODE_SCORE_LIMIT = 0x200
+WFM_ST_MAX_SCORE = -100  # the optimal score is beyond the problem's limit
 
 DEFAULT_PEN = (5, 8, 2, 24, 1)  # parse_args.hpp:290-294
 # wfm_get_problem_flags (include/wfmash_hip.h): which of the rarer paths a problem took
@@ -515,7 +520,7 @@ class Handle:
             ops = None
             if r.status == 0:
                 mine = a[r.ops_off:r.ops_off + r.n_runs]
-                ops = np.repeat(opc[mine & 3], mine >> 2).tobytes()
+                ops = np.repeat(opc[mine & 3], mine >> 2).tobytes() if r.n_runs else b""
             out.append(AlignResult(r.status, r.score, ops, r.n_runs, r.cells))
         return out
 
@@ -556,6 +561,27 @@ class Handle:
             out.append(AlignResult(r.status, r.score, ops, r.n_runs, r.cells))
         return out
 
+    def scores(self, items, pen=None, limit=None):
+        """The optimal scores alone (WFM_MODE_SCORE_ONLY on every item): returns [(status, score)].  With `limit` the BiWFA items
+        run under it as a hard limit (WFM_MODE_SCORE_LIMIT): status WFM_ST_MAX_SCORE and score -1 where the score is beyond it."""
+        flagged = []
+        for it in items:
+            it = tuple(it)
+            mode = it[2] if len(it) > 2 else WFM_MODE_END2END_BIWFA
+            free = tuple(it[3:7]) if len(it) > 3 else (0, 0, 0, 0)
+            hint = it[7] if len(it) > 7 else 0
+            if limit is not None and (mode & WFM_MODE_MASK) == WFM_MODE_END2END_BIWFA:
+                mode, hint = mode | WFM_MODE_SCORE_LIMIT, limit
+            flagged.append((it[0], it[1], mode | WFM_MODE_SCORE_ONLY) + free + (hint,))
+        probs, keep, n = _make_problems(flagged)
+        pn = Penalties(*(pen or DEFAULT_PEN))
+        res = (Result * max(n, 1))()
+        f = self._L.wfm_align_batch
+        rc = f(self._p, C.byref(pn), probs, n, res, None, 0)
+        if rc < 0:
+            raise WfmError(f"wfm_align_batch failed ({rc}): {self.last_error()}")
+        return [(res[i].status, res[i].score) for i in range(n)]
+
     def score_bounds(self, items, pen=None):
         """wfm_score_bounds: per (pattern, text) an upper bound of the end-to-end score, or -1."""
         probs, keep, n = _make_problems(items)
@@ -594,7 +620,9 @@ class Handle:
         for i in range(n):
             r = res[i]
             ops = None
-            if r.status == 0:
+            if r.status == 0 and probs[i].mode & WFM_MODE_SCORE_ONLY:
+                ops = b""  # (no runs were asked for)
+            elif r.status == 0:
                 mine = arr[r.ops_off:r.ops_off + r.n_runs]
                 ops = [(int(x) >> 2, b"MXID"[int(x) & 3:(int(x) & 3) + 1]) for x in mine]
             out.append((AlignResult(r.status, r.score, ops, r.n_runs, r.cells), int(r.ops_len)))

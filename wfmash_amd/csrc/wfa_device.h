@@ -25,6 +25,7 @@ constexpr int WFM_DEV_UNREACHABLE = -300;
 constexpr int WFM_DEV_OVERFLOW = -2;  // base job exceeded its score budget (smax)
 constexpr int WFM_DEV_BAND = -4;      // bialign job ran out of its diagonal band (BpJob::band)
 constexpr int WFM_DEV_P2_NOTHING = -6; // phase 2 ended without improving on the breakpoint it was handed (BpJob / P2Job::best0): that one stands
+constexpr int WFM_DEV_LIMIT = -7;     // bialign job under a hard score limit (BpJob::limit): a direction stands at the limit and the directions have not met
 constexpr int WFM_DEV_P2_MORE = -5;   // phase 2 did not end within the P2K rows computed ahead: the step kernel takes the job
 
 struct DevPen { int x, o1, e1, o2, e2; };
@@ -51,7 +52,10 @@ struct BpJob {
                                        // computed ahead); only a better one is reported, else WFM_DEV_P2_NOTHING
   int32_t packed;                      // bit 0: both sequences are pure upper-case ACGT -- the tile kernel may read the 2-bit mirror (wfa_tile2.hip);
                                        // bit 1: near-identical sequences (score known to be under a sixteenth of the length): long runs go to the wave's tail at once
+  int32_t limit;                       // > 0: the problem's hard score limit (WFM_MODE_SCORE_LIMIT; sub <= limit then).  Phase 1 of the step kernel ends with WFM_DEV_LIMIT
+                                       // once the forward direction stands at it with the directions apart: a score within the limit would have brought it to the end
 };
+static_assert(sizeof(BpJob) == 104, "BpJob::limit fills the struct's tail padding: the job arrays keep their stride");
 
 // ---- time-tiled phase 1 (wfa_tile_kernel) ----
 // A block advances every active job by T scores.  A tile owns `core` diagonals of one
@@ -172,7 +176,9 @@ struct BaseJob {
   int32_t smax, kmin, width;
   int32_t type;          // 0 WFA; 1 all-D (tl == 0); 2 all-I (pl == 0)
   int32_t pad_;
+  int32_t score_only;    // nonzero: the job ends behind its forward pass -- BaseResult::score is all it reports, no walk back, nothing written to the RLE slots
 };
+static_assert(sizeof(BaseJob) == 112, "BaseJob::score_only fills the struct's tail padding: the job arrays keep their stride");
 
 struct BaseResult {
   int32_t status;  // 0 ok; WFM_DEV_OVERFLOW; <0 error

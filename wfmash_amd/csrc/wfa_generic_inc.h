@@ -419,6 +419,8 @@ __global__ __launch_bounds__(1024) void wfa_bp_kernel(const uint8_t* __restrict_
   //  computed here in one pass and the checks replayed in the same order)
   for (;;) {
     if (fmax + rmax >= A) break;
+    // a hard score limit: an alignment of score <= sf would have brought the forward direction to the end by now (and the directions together)
+    if (J.limit > 0 && sf >= J.limit) { status = WFM_DEV_LIMIT; break; }
     if (band > 0 && max(sf, sr) + 2 > band) { status = WFM_DEV_BAND; break; }
     buf = (buf + 1) % 3;
     if (tid == 0) { s_mak[(buf + 1) % 3][0] = 0; s_mak[(buf + 1) % 3][1] = 0; }
@@ -627,7 +629,7 @@ __global__ __launch_bounds__(NT) void wfa_base_kernel(const uint8_t* __restrict_
     if (tid == 0) {
       BaseResult r; r.status = 0; r.cells = 0; r.nruns = 0; r.score = 0;
       const int len = J.type == 1 ? J.pl : J.tl;
-      if (len > 0) { rle[J.rle_end - 1] = ((uint32_t)len << 2) | (uint32_t)(J.type == 1 ? OP_D : OP_I); r.nruns = 1; }
+      if (len > 0 && !J.score_only) { rle[J.rle_end - 1] = ((uint32_t)len << 2) | (uint32_t)(J.type == 1 ? OP_D : OP_I); r.nruns = 1; }
       results[blockIdx.x] = r;
     }
     return;
@@ -777,7 +779,7 @@ __global__ __launch_bounds__(NT) void wfa_base_kernel(const uint8_t* __restrict_
   if (tid < 64) {
     const int lane = tid;
     BaseResult r; r.status = status; r.score = s; r.nruns = 0; r.cells = cells;
-    if (status == 0) {
+    if (status == 0 && !J.score_only) {  // (a score-only job ends here: s is its score)
       RleWriter w; w.base = rle + J.rle_end; w.n = 0; w.cur_op = -1; w.cur_len = 0; w.writes = lane == 0;
       int comp = J.endsfree ? C_M : J.comp_end;
       int k = J.endsfree ? s_endk : k_end;

@@ -85,7 +85,10 @@ struct ProbMeta {
   int32_t plen, tlen;
   int32_t mode, pbf, pef, tbf, tef;
   int32_t hint;     // the caller's guess of an upper bound of the score (0: none)
-  int64_t rle_off;  // start of this problem's RLE slot range
+  int64_t rle_off;  // start of this problem's RLE slot range (a score-only problem has none: its range is empty)
+  int32_t flags;    // WFM_MODE_SCORE_ONLY / WFM_MODE_SCORE_LIMIT as the problem came with them (mode holds the bits under WFM_MODE_MASK)
+  int32_t limit;    // WFM_MODE_SCORE_LIMIT: the hard limit of the score (0: none); hint is 0 then
+  bool score_only() const { return (flags & WFM_MODE_SCORE_ONLY) != 0; }
 };
 
 // The state of a tiled job that ran out of its narrow ring, kept in a device block of its own until the job has its wider ring: the columns
@@ -344,6 +347,7 @@ struct BaseChunk {
   wfm_handle* h; wfm_seqset* S; const wfm_penalties_t& pen; const BaseCfg& cfg;  // run_base_jobs' arguments
   std::vector<Node>& nodes; std::vector<Node>& retry; std::vector<int32_t>& prob_status; std::vector<uint64_t>& prob_cells;
   LevelTimer& tm; uint32_t* pflags;
+  std::vector<int32_t>& prob_score;  // score-only problems: the score their base job found
   int RR;
   BaseRules rules;
   std::vector<BaseJob> jobs;  // BaseJob::pad_: the job's node
@@ -382,6 +386,7 @@ void fill_base_chunk(BaseChunk& c, size_t i0) {
     j.pbf = pm.pbf; j.pef = pm.pef; j.tbf = pm.tbf; j.tef = pm.tef;
     j.rle_end = pm.rle_off + nd.pb + nd.tb + nd.pl + nd.tl;
     j.pad_ = (int32_t)i;
+    j.score_only = pm.score_only() ? 1 : 0;  // (such a problem's base jobs are its roots: a score-only BiWFA root has no children)
     if (nd.tl == 0 || nd.pl == 0) {
       j.type = nd.tl == 0 ? 1 : 2;
       if (nd.tl == 0 && nd.pl == 0) { j.type = 1; }
@@ -532,6 +537,11 @@ void settle_base_chunk(BaseChunk& c) {
     h->stats.cells_base += r.cells;
     if (c.pflags && (c.kind == 3 || c.kind == 4) && c.jobs[q].type == 0) c.pflags[nd.prob] |= WFM_PF_RING_KERNEL;
     if (c.pflags && c.kind == 5) c.pflags[nd.prob] |= WFM_PF_BASE_TILES;
+    if (r.status == 0 && c.jobs[q].score_only)  // (the all-gap jobs report no score of their own: theirs is the gap's)
+      c.prob_score[nd.prob] = c.jobs[q].type == 0 ? r.score : gapcost(pen, nd.pl) + gapcost(pen, nd.tl);
+    if (r.status == WFM_DEV_OVERFLOW && nd.limit > 0 && nd.smax >= nd.limit) {  // the budget was the problem's hard limit: final
+      c.prob_status[nd.prob] = WFM_ST_MAX_SCORE; continue;
+    }
     if (r.status == WFM_DEV_OVERFLOW) {
       if (c.pflags) c.pflags[nd.prob] |= nd.tries == 0 ? WFM_PF_BASE_RETRY : WFM_PF_BASE_RETRY2;
       Node again = nd;
@@ -558,6 +568,7 @@ void settle_base_chunk(BaseChunk& c) {
       // runs with the eightfold budget at once, 2.0 ms of an LPA batch's patch chain less)
       const bool to_tiles = c.rules.base_v2 && c.rules.base_tiles && is_acgt(c.S, nd.prob);
       if (nd.smax < 1020 && again.smax > 1020 && !to_tiles) again.smax = 1020;
+      if (nd.limit > 0) again.smax = std::min(again.smax, nd.limit);
       c.retry.push_back(again);
     } else if (r.status != 0) {
       if (c.cfg.debug) fprintf(stderr, "[wfm] problem %d: base job pl %d tl %d status %d\n", nd.prob, nd.pl, nd.tl, r.status);
@@ -570,9 +581,9 @@ void settle_base_chunk(BaseChunk& c) {
 // overflowed nodes (with a larger budget) to `retry`.
 int run_base_jobs(wfm_handle* h, wfm_seqset* S, const wfm_penalties_t& pen, const BaseCfg& cfg, std::vector<Node>& nodes,
                   std::vector<Node>& retry, std::vector<int32_t>& prob_status, std::vector<uint64_t>& prob_cells,
-                  LevelTimer& tm, uint32_t* pflags) {
+                  LevelTimer& tm, uint32_t* pflags, std::vector<int32_t>& prob_score) {
   if (nodes.empty()) return WFM_OK;
-  BaseChunk c{h, S, pen, cfg, nodes, retry, prob_status, prob_cells, tm, pflags,
+  BaseChunk c{h, S, pen, cfg, nodes, retry, prob_status, prob_cells, tm, pflags, prob_score,
               ring_rows_for(std::max(pen.x, std::max(pen.o1 + pen.e1, pen.o2 + pen.e2)) + 1)};
   // rows beyond 2 k diagonals get 1024 threads -- and rows beyond 512 when the launch is too small to fill the device anyway
   // (the retries of the few patches that overflowed their first budget: one workgroup each, a thousand steps deep)
@@ -783,7 +794,9 @@ int drop_leavers(TilePhase& p) {
   bool left = false;
   for (size_t i = 0; i < p.n; ++i) {
     const TileJob& t = p.tj[i];
-    if (!p.active[i] || !tile_job_leaves(t.pl, t.tl, t.sub, t.s0, p.jobs[(size_t)p.tiled[i]].band, p.chunk, p.T)) continue;
+    const BpJob& bj = p.jobs[(size_t)p.tiled[i]];
+    // (a job under a hard limit of its score gets no block whose first score passes the limit: tile_job_beyond_limit)
+    if (!p.active[i] || !(tile_job_leaves(t.pl, t.tl, t.sub, t.s0, bj.band, p.chunk, p.T) || tile_job_beyond_limit(t.pl, t.tl, t.sub, bj.limit, t.s0, p.T))) continue;
     p.active[i] = 0; p.tj[i].active = 0; p.tj[i].mode = 3; left = true; --p.n_active;
   }
   if (left) HIPCHK(h, hipMemcpyAsync(h->tilejobs.p, p.tj.data(), p.n * sizeof(TileJob), hipMemcpyHostToDevice, h->stream));
@@ -1333,12 +1346,13 @@ struct AlignCall {
   RingRules rules;  // what plan_ring decides by: the call's, the level's (use_band, over_budget) and roots_off
   std::vector<int32_t> prob_status;  // indexed by problem id
   std::vector<uint64_t> prob_cells;
+  std::vector<int32_t> prob_score;   // score-only problems: the score, taken where the device first knows it (a root's meeting point, a base job's forward pass)
   std::vector<Node> bp_nodes, base_nodes, next_bp;
   uint32_t level = 0;
   Chunk ck;
   LevelTimer tm;
   double wall_tile = 0, wall_base = 0;
-  uint64_t band_retries = 0, band_jobs = 0, roots_banded = 0, roots_out = 0, hint_retries = 0;
+  uint64_t band_retries = 0, band_jobs = 0, roots_banded = 0, roots_out = 0, hint_retries = 0, limit_out = 0;
   // Rings that grow with the score: a job whose full ring does not fit the budget runs on bands b, 4 b, 16 b ...
   uint64_t grown_jobs = 0, grown_widened = 0, grown_restarts = 0;
   int64_t grown_maxband = 0;
@@ -1359,7 +1373,11 @@ void make_roots(AlignCall& c) {
     nd.sub = SUB_NONE; nd.hinted = 0;
     if (c.pflags && pm.mode == WFM_MODE_END2END_BIWFA && !((size_t)i < c.S->acgt.size() && c.S->acgt[i])) c.pflags[i] |= WFM_PF_BYTE_KERNEL;
     if (c.knobs.use_hints && pm.hint > 0 && pm.mode == WFM_MODE_END2END_BIWFA) { nd.sub = pm.hint; nd.hinted = 1; }
-    const int64_t bound = (int64_t)gapcost(*c.pen, pm.plen) + gapcost(*c.pen, pm.tlen) + 8;
+    // a hard limit of the score is the root's bound whatever the switches say about guesses (bound_roots may still lower it: its bound is rigorous)
+    if (pm.limit > 0) { nd.limit = pm.limit; nd.sub = pm.limit; nd.hinted = 1; }
+    int64_t bound = (int64_t)gapcost(*c.pen, pm.plen) + gapcost(*c.pen, pm.tlen) + 8;
+    if (pm.limit > 0 && (pm.plen == 0 || pm.tlen == 0) && bound - 8 > pm.limit) { c.prob_status[i] = WFM_ST_MAX_SCORE; continue; }  // (the all-gap jobs have no budget to overflow)
+    if (pm.limit > 0) bound = std::min<int64_t>(bound, pm.limit);  // a limited short problem's base job: the limit is its budget, its overflow final
     if (pm.mode == WFM_MODE_ENDSFREE) {
       nd.endsfree = 1;
       // ends-free score is bounded by the cheaper all-gap alignment; start small, double on overflow
@@ -1449,7 +1467,8 @@ void plan_chunk(AlignCall& c, size_t i0) {
     const ProbMeta& pm = c.S->meta[nd.prob];
     RingPlan rp = plan_ring(nd, c.rules);
     // the bound the job's rows are cut to (set into the job below)
-    const int32_t job_sub = (nd.sub != SUB_NONE && (int64_t)std::abs(nd.tl - nd.pl) * 8 >= (int64_t)nd.sub) ? nd.sub : SUB_NONE;
+    // (under a hard limit always: the limit has to stop the job wherever its end diagonal lies)
+    const int32_t job_sub = (nd.sub != SUB_NONE && (nd.limit > 0 || (int64_t)std::abs(nd.tl - nd.pl) * 8 >= (int64_t)nd.sub)) ? nd.sub : SUB_NONE;
     const bool reuse_on = c.knobs.reuse && tcfg.reg && tcfg.exact && c.RR == RING;
     if (nd.keep > 0 && reuse_on && rp.fits && rp.band > 0 && !rp.grown) {
       // A node that came with a keep takes it on a full ring only (a narrow one is out of parent reuse's scope).  Where the level chose a narrow
@@ -1486,6 +1505,7 @@ void plan_chunk(AlignCall& c, size_t i0) {
     // records and their children): for a balanced problem it starts to bind where the wavefronts meet, and costs the
     // tile kernel its bookkeeping all the way there
     j.sub = job_sub;
+    j.limit = nd.limit;
     j.best0 = 0;
     j.packed = (c.knobs.tile_v2 && tcfg.reg && tcfg.C == 2 && (size_t)nd.prob < c.S->acgt.size() && c.S->acgt[(size_t)nd.prob]) ? 1 : 0;
     // bit 1: near-identical sequences -- the job's score is known (a child's, a bounded or hinted root's) to be under a sixteenth of its length; the packed
@@ -1529,7 +1549,8 @@ void plan_chunk(AlignCall& c, size_t i0) {
       k.reuse.push_back(use);
       // (no keep beyond the score a child could still resume at: a child's score is at most its parent's, which is at most the bound where one is known)
       int32_t upto = 0;
-      if (reuse_on && band == 0 && !grown && (int)c.level <= c.knobs.reuse_levels) {
+      // (a score-only root has no children: nobody would resume from its keeps)
+      if (reuse_on && band == 0 && !grown && (int)c.level <= c.knobs.reuse_levels && !(nd.score_rem == INT_MAX && pm.score_only())) {
         const int known = nd.score_rem != INT_MAX ? nd.score_rem : (nd.sub != SUB_NONE ? nd.sub : INT_MAX);
         // (the two directions meet at scores a step apart: a child has half the job's score, give or take the rows the overlap phase reads)
         upto = known != INT_MAX ? std::max(0, reuse_resume_limit(known / 2 + 2 * SNAP_ROWS, tcfg.T, c.knobs.fine_margin)) : INT_MAX;
@@ -1853,6 +1874,27 @@ int settle_chunk(AlignCall& c) {
       c.next_bp.push_back(again);
       continue;
     }
+    if (nd.limit > 0 && !(r.status == 1 || (r.status == 0 && r.score <= nd.limit))) {
+      // A root under a hard limit of its score that did not end within it.  Whatever the limit itself stopped is the problem's verdict: the step
+      // kernel at the limit (WFM_DEV_LIMIT), a walk that found nothing within the bound or a job the tile phase let go on a ring without a band
+      // (no alignment of a score within the bound leaves the rows the bound cuts), and on any ring a job that left the tile phase where
+      // tile_job_beyond_limit says so.  A band that ran out says nothing about the score -- the band of a root is a guess: once more without
+      // it, still under the limit, never without a bound.
+      const BpJob& j = k.jobs[q];
+      const bool beyond = r.status == WFM_DEV_LIMIT || r.status == 0 || (r.status == WFM_DEV_BAND && j.band == 0) ||
+                          (r.status == WFM_DEV_BAND && j.resume_s == -3 && j.resume_sr >= 0 && !k.resume_bad[q] &&
+                           tile_job_beyond_limit(j.pl, j.tl, j.sub, j.limit, j.resume_sr, c.tcfg.T));
+      if (beyond) { c.prob_status[nd.prob] = WFM_ST_MAX_SCORE; ++c.limit_out; continue; }
+      if (r.status == WFM_DEV_BAND) {
+        Node again = nd; again.noband = 1; again.band = j.band; again.snap = 0; again.keep = 0; again.keep_dir = 0;
+        if (c.pflags) c.pflags[nd.prob] |= WFM_PF_ROOT_AGAIN;
+        const bool full_fits = ring_elems(ring_full_width(nd.pl, nd.tl), c.RR) * 4 <= h->mem_budget;
+        if (!full_fits && c.pflags) c.pflags[nd.prob] |= WFM_PF_RING_GROWN;  // (its next band grows from this one: plan_ring)
+        c.next_bp.push_back(again);
+        c.band_retries += full_fits;
+        continue;
+      }
+    }
     const bool guessed = nd.hinted && k.jobs[q].sub != SUB_NONE;  // the job really ran under the caller's guess
     if (r.status == WFM_DEV_BAND || (guessed && (r.status < 0 || (r.status == 0 && r.score > nd.sub)))) {
       // ran out of its narrow ring, or past the caller's guess of its score: once more, at the end of this level, on
@@ -1878,7 +1920,10 @@ int settle_chunk(AlignCall& c) {
       c.hint_retries += guessed;
       continue;
     }
-    if (r.status == 1) {  // end reached at score 0 -> base aligner
+    const bool score_root = nd.score_rem == INT_MAX && c.S->meta[nd.prob].score_only();  // the score is all the problem asks for: a root's meeting point is it
+    if (r.status == 1 && score_root) {  // end reached at score 0
+      c.prob_score[nd.prob] = 0;
+    } else if (r.status == 1) {  // end reached at score 0 -> base aligner
       Node b = nd; b.smax = 0; b.keep = 0; c.base_nodes.push_back(b);
     } else if (r.status != 0) {
       if (c.knobs.debug) fprintf(stderr, "[wfm] problem %d: bialign job pl %d tl %d cb %d ce %d score_rem %d status %d (steps %d)\n", nd.prob, nd.pl, nd.tl, nd.cb, nd.ce, nd.score_rem, r.status, r.steps);
@@ -1891,7 +1936,8 @@ int settle_chunk(AlignCall& c) {
         c.prob_status[nd.prob] = WFM_ST_UNREACHABLE; continue;
       }
       if (c.knobs.debug > 1) fprintf(stderr, "[wfm] problem %d level %u: job pl %d tl %d cb %d ce %d rem %d -> bp v %d h %d score %d = %d + %d comp %d\n", nd.prob, c.level, nd.pl, nd.tl, nd.cb, nd.ce, nd.score_rem, bp_v, bp_h, r.score, r.score_fwd, r.score_rev, r.comp);
-      push_children(c, nd, r, bp_v, bp_h, q);
+      if (score_root) c.prob_score[nd.prob] = r.score;  // (no children, no leaves; the keeps it may have written go back below)
+      else push_children(c, nd, r, bp_v, bp_h, q);
     }
   }
   // the keeps no child took go back
@@ -1906,7 +1952,7 @@ int run_leaves(AlignCall& c) {
   while (!c.base_nodes.empty()) {
     retry.clear();
     const auto tb0 = std::chrono::steady_clock::now();
-    const int rc = run_base_jobs(c.h, c.S, *c.pen, c.bcfg, c.base_nodes, retry, c.prob_status, c.prob_cells, c.tm, c.pflags);
+    const int rc = run_base_jobs(c.h, c.S, *c.pen, c.bcfg, c.base_nodes, retry, c.prob_status, c.prob_cells, c.tm, c.pflags, c.prob_score);
     c.wall_base += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb0).count();
     if (rc != WFM_OK) return rc;
     c.base_nodes.swap(retry);
@@ -1923,6 +1969,7 @@ void print_level_totals(const AlignCall& c) {
   }
   if (!c.knobs.debug) return;
   if (c.hint_retries) fprintf(stderr, "[wfm] score hints: %llu roots ran past their hint and were run again without it\n", (unsigned long long)c.hint_retries);
+  if (c.limit_out) fprintf(stderr, "[wfm] score limits: %llu roots ended beyond their hard limit\n", (unsigned long long)c.limit_out);
   if (c.band_jobs) fprintf(stderr, "[wfm] narrow rings: %llu jobs, %llu ran out of their band and were run again on full rings\n", (unsigned long long)c.band_jobs, (unsigned long long)c.band_retries);
   if (c.grown_jobs)
     fprintf(stderr, "[wfm] grown rings: %llu jobs, %llu widened and resumed, %llu started again, largest band %lld\n", (unsigned long long)c.grown_jobs,
@@ -1941,7 +1988,10 @@ int gather_runs(AlignCall& c, GatheredRuns& g) {
   wfm_handle* h = c.h;
   const size_t n = c.last - c.first;
   std::vector<int64_t> poff(n), pcap(n);
-  for (size_t i = 0; i < n; ++i) { poff[i] = c.S->meta[c.first + i].rle_off; pcap[i] = (int64_t)c.S->meta[c.first + i].plen + c.S->meta[c.first + i].tlen; }
+  for (size_t i = 0; i < n; ++i) {  // (a score-only problem has no slots)
+    const ProbMeta& pm = c.S->meta[c.first + i];
+    poff[i] = pm.rle_off; pcap[i] = pm.score_only() ? 0 : (int64_t)pm.plen + pm.tlen;
+  }
   if (h->i64a.ensure(n) || h->i64b.ensure(n) || h->i64c.ensure(n) || h->i32a.ensure(n) || h->total.ensure(1)) {
     h->err = "out of device memory"; return WFM_E_NOMEM;
   }
@@ -1967,7 +2017,7 @@ int gather_runs(AlignCall& c, GatheredRuns& g) {
 int write_results(AlignCall& c, const GatheredRuns& g, uint64_t* cells_total) {
   std::vector<uint32_t>* runs_out = c.runs_out;
   size_t arena_pos = runs_out ? runs_out->size() : c.arena_base;
-  if (runs_out) runs_out->reserve(runs_out->size() + g.runs.size() - 1);
+  if (runs_out && !g.runs.empty()) runs_out->reserve(runs_out->size() + g.runs.size() - 1);
   int failed = 0;
   for (size_t i = 0; i < c.last - c.first; ++i) {
     const size_t gi = c.first + i;  // problem id
@@ -1978,6 +2028,7 @@ int write_results(AlignCall& c, const GatheredRuns& g, uint64_t* cells_total) {
     *cells_total += c.prob_cells[gi];
     r.ops_off = arena_pos; r.ops_len = 0; r.n_runs = 0; r.score = -1;
     if (r.status != WFM_ST_OK) { ++failed; continue; }
+    if (pm.score_only()) { r.score = c.prob_score[gi]; continue; }  // (nothing of it in the arena or the runs)
     Expanded ex;
     const int err = expand_runs(g.runs.data() + g.ostart[i], g.ocount[i], *c.pen, pm.plen, pm.tlen, runs_out ? nullptr : c.ops_arena + arena_pos,
                                 c.arena_bytes > arena_pos ? c.arena_bytes - arena_pos : 0, runs_out, &ex);
@@ -2012,6 +2063,7 @@ int align_resident_impl(wfm_handle* h, const wfm_penalties_t* pen, wfm_seqset* S
   AlignCall c{h, pen, S, first, last, out, ops_arena, arena_bytes, arena_base, runs_out, pflags, scope, DevPen{pen->x, pen->o1, pen->e1, pen->o2, pen->e2}};
   c.prob_status.assign(S->meta.size(), WFM_ST_OK);
   c.prob_cells.assign(S->meta.size(), 0);
+  c.prob_score.assign(S->meta.size(), -1);
   // RLE slot buffer (zero = empty)
   if (h->rle.ensure((size_t)S->rle_total + 16) || h->rle_out.ensure((size_t)S->rle_total + 16)) {
     h->err = "out of device memory (rle)"; return WFM_E_NOMEM;
@@ -2053,7 +2105,9 @@ int align_resident_impl(wfm_handle* h, const wfm_penalties_t* pen, wfm_seqset* S
   const auto t_levels = std::chrono::steady_clock::now();
 
   GatheredRuns g;
-  if ((rc = gather_runs(c, g)) != WFM_OK) return rc;
+  bool any_full = false;  // (a call of score-only problems has no runs to gather)
+  for (size_t i = first; i < last && !any_full; ++i) any_full = !S->meta[i].score_only();
+  if (any_full && (rc = gather_runs(c, g)) != WFM_OK) return rc;
   uint64_t cells_total = 0;
   const int failed = write_results(c, g, &cells_total);
   if (failed < 0) return failed;
@@ -2193,7 +2247,8 @@ int wfm_device_name(const wfm_handle_t* h, char* buf, size_t buflen) {
 
 size_t wfm_align_arena_bytes(const wfm_problem_t* problems, size_t n) {
   size_t t = 0;
-  for (size_t i = 0; i < n; ++i) t += (size_t)problems[i].plen + (size_t)problems[i].tlen + 1;
+  for (size_t i = 0; i < n; ++i)
+    if (!(problems[i].mode & WFM_MODE_SCORE_ONLY)) t += (size_t)problems[i].plen + (size_t)problems[i].tlen + 1;
   return t;
 }
 
@@ -2202,6 +2257,22 @@ namespace {
 // The layout of a seqset, shared by wfm_upload_sequences and wfm_upload_sequence_refs (P: wfm_problem_t or wfm_problem_ref_t, lengths
 // validated by the caller): SEQ_PAD zero bytes, the forward copies -- the only part that crosses PCIe where the sides are host
 // pointers -- each followed by SEQ_PAD zero bytes, SEQ_PAD more, then the reversed copies of the BiWFA problems and a last SEQ_PAD.
+// `mode` of every problem of an upload: one of the three modes under the mask, no bit beyond the mask and the two flags, a hard limit only
+// on a BiWFA problem and only with a limit to go by.  The message names the first problem that fails.
+template <typename P>
+int check_modes(wfm_handle* h, const P* problems, size_t n) {
+  for (size_t i = 0; i < n; ++i) {
+    const int32_t mode = problems[i].mode, m = mode & WFM_MODE_MASK;
+    const char* what = nullptr;
+    if (mode & ~(WFM_MODE_MASK | WFM_MODE_SCORE_ONLY | WFM_MODE_SCORE_LIMIT)) what = "unknown bits in mode";
+    else if (m != WFM_MODE_END2END_BIWFA && m != WFM_MODE_ENDSFREE && m != WFM_MODE_END2END_UNI) what = "unknown mode";
+    else if ((mode & WFM_MODE_SCORE_LIMIT) && m != WFM_MODE_END2END_BIWFA) what = "WFM_MODE_SCORE_LIMIT takes END2END_BIWFA";
+    else if ((mode & WFM_MODE_SCORE_LIMIT) && problems[i].score_hint <= 0) what = "WFM_MODE_SCORE_LIMIT takes a score_hint > 0";
+    if (what) { h->err = "problem " + std::to_string(i) + ": " + what; return WFM_E_ARG; }
+  }
+  return WFM_OK;
+}
+
 template <typename P>
 void layout_seqset(wfm_seqset* S, const P* problems, size_t n, size_t* fwd_bytes_out) {
   S->meta.resize(n);
@@ -2210,19 +2281,21 @@ void layout_seqset(wfm_seqset* S, const P* problems, size_t n, size_t* fwd_bytes
   for (size_t i = 0; i < n; ++i) {
     const P& p = problems[i];
     ProbMeta& m = S->meta[i];
-    m.plen = p.plen; m.tlen = p.tlen; m.mode = p.mode;
-    m.hint = (p.mode == WFM_MODE_END2END_BIWFA && p.score_hint > 0) ? p.score_hint : 0;
+    m.plen = p.plen; m.tlen = p.tlen; m.mode = p.mode & WFM_MODE_MASK; m.flags = p.mode & ~WFM_MODE_MASK;  // (check_modes has seen them)
+    m.limit = (m.flags & WFM_MODE_SCORE_LIMIT) ? p.score_hint : 0;
+    m.hint = (m.mode == WFM_MODE_END2END_BIWFA && p.score_hint > 0 && !m.limit) ? p.score_hint : 0;
     m.pbf = std::min(std::max(p.pattern_begin_free, 0), p.plen); m.pef = std::min(std::max(p.pattern_end_free, 0), p.plen);
     m.tbf = std::min(std::max(p.text_begin_free, 0), p.tlen);    m.tef = std::min(std::max(p.text_end_free, 0), p.tlen);
-    if (p.mode != WFM_MODE_ENDSFREE) { m.pbf = m.pef = m.tbf = m.tef = 0; }
+    if (m.mode != WFM_MODE_ENDSFREE) { m.pbf = m.pef = m.tbf = m.tef = 0; }
     m.p_fwd = (int64_t)bytes; bytes += (size_t)p.plen + SEQ_PAD;
     m.t_fwd = (int64_t)bytes; bytes += (size_t)p.tlen + SEQ_PAD;
-    const bool need_rev = (p.mode == WFM_MODE_END2END_BIWFA);
+    const bool need_rev = (m.mode == WFM_MODE_END2END_BIWFA);
     if (need_rev) {
       m.p_rev = (int64_t)rev_bytes; rev_bytes += (size_t)p.plen + SEQ_PAD;   // relative to the end of the forward part for now
       m.t_rev = (int64_t)rev_bytes; rev_bytes += (size_t)p.tlen + SEQ_PAD;
     } else { m.p_rev = -1; m.t_rev = -1; }
-    m.rle_off = rle; rle += (int64_t)p.plen + p.tlen + 1;
+    m.rle_off = rle;
+    if (!m.score_only()) rle += (int64_t)p.plen + p.tlen + 1;
     S->seq_bases += (uint64_t)p.plen + (uint64_t)p.tlen;
   }
   bytes += SEQ_PAD;
@@ -2249,6 +2322,7 @@ int wfm_upload_sequences(wfm_handle_t* h, const wfm_problem_t* problems, size_t 
       h->err = "bad problem"; return WFM_E_ARG;
     }
   }
+  if (const int mrc = check_modes(h, problems, n)) return mrc;
   wfm_seqset* S = new wfm_seqset();
   size_t fwd_bytes = 0;
   layout_seqset(S, problems, n, &fwd_bytes);
@@ -2307,7 +2381,7 @@ int wfm_upload_sequences(wfm_handle_t* h, const wfm_problem_t* problems, size_t 
     rv.reserve(n);
     for (size_t i = 0; i < n; ++i) {
       const ProbMeta& m = S->meta[i];
-      if (problems[i].mode == WFM_MODE_END2END_BIWFA) rv.push_back(SeqRev{m.p_fwd, m.p_rev, m.t_fwd, m.t_rev, m.plen, m.tlen});
+      if (m.mode == WFM_MODE_END2END_BIWFA) rv.push_back(SeqRev{m.p_fwd, m.p_rev, m.t_fwd, m.t_rev, m.plen, m.tlen});
     }
     if (!rv.empty()) {
       if (h->revjobs.ensure(rv.size())) e = hipErrorOutOfMemory;
@@ -2455,6 +2529,7 @@ int wfm_upload_sequence_refs(wfm_handle_t* h, const wfm_seqstore_t* store, const
       }
     }
   }
+  if (const int mrc = check_modes(h, refs, n)) return mrc;
   wfm_seqset* S = new wfm_seqset();
   size_t fwd_bytes = 0;
   layout_seqset(S, refs, n, &fwd_bytes);
@@ -2505,7 +2580,7 @@ int wfm_upload_sequence_refs(wfm_handle_t* h, const wfm_seqstore_t* store, const
   for (size_t i = 0; i < n; ++i) {
     const wfm_problem_ref_t& p = refs[i];
     const ProbMeta& m = S->meta[i];
-    const bool biwfa = p.mode == WFM_MODE_END2END_BIWFA;
+    const bool biwfa = m.mode == WFM_MODE_END2END_BIWFA;
     for (int side = 0; side < 2; ++side) {
       const int32_t id = side ? p.text_seq : p.pattern_seq, len = side ? p.tlen : p.plen;
       const int64_t fwd = side ? m.t_fwd : m.p_fwd, rev = side ? m.t_rev : m.p_rev;
@@ -2713,7 +2788,7 @@ int align_resident_any(wfm_handle_t* h, const wfm_penalties_t* pen, wfm_seqset_t
   std::vector<size_t> base(np, 0);
   for (size_t k = 1; k < np; ++k) {
     base[k] = base[k - 1];
-    for (size_t i = cut[k - 1]; i < cut[k]; ++i) base[k] += (size_t)s->meta[i].plen + (size_t)s->meta[i].tlen + 1;
+    for (size_t i = cut[k - 1]; i < cut[k]; ++i) if (!s->meta[i].score_only()) base[k] += (size_t)s->meta[i].plen + (size_t)s->meta[i].tlen + 1;
   }
   const auto t0 = std::chrono::steady_clock::now();
   std::vector<int> rcs(np, 0);

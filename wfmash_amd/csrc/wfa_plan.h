@@ -35,6 +35,7 @@ struct Node {
   int32_t snap;       // bialign jobs: 1 + the index of the snapshot the job goes on from on its wider ring (GrownSnap), 0: it starts at score 0
   int32_t keep;       // bialign jobs: 1 + the index of the kept rows of its parent that its outer direction resumes from (KeptRows), 0: both directions start at score 0
   int32_t keep_dir;   // the direction those rows are of: 0 forward (a first child), 1 reverse (a second child)
+  int32_t limit;      // roots of a problem with a hard score limit (WFM_MODE_SCORE_LIMIT): the limit; 0: none.  sub <= limit then, and no attempt runs without it
 };
 
 // ---- the size of a ring: `w` columns of 2 directions x 5 components x RR rows of int32 ----
@@ -183,6 +184,18 @@ struct TileChunkPlan {
 inline bool tile_job_leaves(int pl, int tl, int sub, int s0, int band, int chunk, int T) {
   if (band > 0 && s0 + chunk * T + 2 > band) return true;
   if (sub == SUB_NONE) return false;
+  int L, R;
+  rng_block(make_rng(pl, tl, sub), s0, s0 + T, L, R);
+  return 2 * s0 > sub + 128 || R < L;
+}
+// Under a hard limit of the score (Node::limit, sub <= limit) the same tests are verdicts: a job whose directions stand apart at s0 has a score
+// above s0 (an alignment of at most s0 would have brought either direction to the far end alone) and above 2 s0 - the dearest gap opening (its
+// two halves, the opening counted twice, would have met) -- at most 124, validate_pen -- and nothing of an alignment within the bound lies outside
+// the rows the bound cuts.  So no block is planned whose first score passes the limit, and a job that leaves for one of these reasons is beyond
+// its limit whatever ring it ran on (the band's own test above is no such verdict: the band of a root is a guess).
+inline bool tile_job_beyond_limit(int pl, int tl, int sub, int limit, int s0, int T) {
+  if (limit <= 0) return false;
+  if (s0 >= limit) return true;
   int L, R;
   rng_block(make_rng(pl, tl, sub), s0, s0 + T, L, R);
   return 2 * s0 > sub + 128 || R < L;

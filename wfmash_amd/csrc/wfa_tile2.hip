@@ -1143,7 +1143,7 @@ __global__ __launch_bounds__(NTMAX) void wfa_base2_kernel(const uint32_t* __rest
     if (tid == 0) {
       BaseResult r; r.status = 0; r.cells = 0; r.nruns = 0; r.score = 0; r.pad_ = 0;
       const int len = J.type == 1 ? J.pl : J.tl;
-      if (len > 0) { rle[J.rle_end - 1] = ((uint32_t)len << 2) | (uint32_t)(J.type == 1 ? OP_D : OP_I); r.nruns = 1; }
+      if (len > 0 && !J.score_only) { rle[J.rle_end - 1] = ((uint32_t)len << 2) | (uint32_t)(J.type == 1 ? OP_D : OP_I); r.nruns = 1; }
       results[blockIdx.x] = r;
     }
     return;
@@ -1380,7 +1380,7 @@ __global__ __launch_bounds__(NTMAX) void wfa_base2_kernel(const uint32_t* __rest
   if (tid < 64) {
     const long long t_fwd = wall_clock64();
     BaseResult r; r.status = status; r.score = s; r.nruns = 0; r.cells = cells; r.pad_ = 0;
-    if (status == 0) r.nruns = base2_walk(J, pre_base, bt_base, rle, s, J.endsfree ? s_endk : k_end, J.endsfree ? s_endoff : tl, lane);
+    if (status == 0 && !J.score_only) r.nruns = base2_walk(J, pre_base, bt_base, rle, s, J.endsfree ? s_endk : k_end, J.endsfree ? s_endoff : tl, lane);  // (a score-only job ends here: s is its score)
     // diagnostics (WFM_DEBUG=2): microseconds of the forward pass and of the walk back, 16 bits each
     r.pad_ = (int32_t)((min((t_fwd - t_begin) / 100, 65535ll) << 16) | min((wall_clock64() - t_fwd) / 100, 65535ll));
     if (lane == 0) results[blockIdx.x] = r;
@@ -1699,7 +1699,7 @@ __global__ __launch_bounds__(64) void wfa_base2t_finish_kernel(const int32_t* __
   for (int d = 32; d > 0; d >>= 1) cells += __shfl_down(cells, d, 64);
   cells = __shfl(cells, 0, 64) + (unsigned long long)(hi0 - lo0 + 1);
   r.cells = cells;
-  if (JT.done == 1) r.nruns = base2_walk(J, arena32 + J.pre_off - kmin, arena8 + J.bt_off - kmin, rle, JT.end_s, JT.end_k, JT.end_off, lane);
+  if (JT.done == 1 && !J.score_only) r.nruns = base2_walk(J, arena32 + J.pre_off - kmin, arena8 + J.bt_off - kmin, rle, JT.end_s, JT.end_k, JT.end_off, lane);
   if (lane == 0) results[blockIdx.x] = r;
 }
 

@@ -10,6 +10,11 @@
 // runs their do_biwfa_alignment on the GPU through it.  The members the dormant hierarchical WFlign class uses
 // (wflign.cpp:1097-1168, wflign_patch.cpp:354-362,441-478) are here too: WFAlignerGapAffine, setHeuristicWFmash,
 // setMaxAlignmentSteps, getAlignmentStatus, and the match-callback alignEnd2End, which has no device form and throws.
+//
+// AlignmentScope and setMaxAlignmentSteps are honoured on the device: Score asks for WFM_MODE_SCORE_ONLY (the score and nothing else:
+// getAlignment yields length 0), and the MemoryUltralow end-to-end form passes its step limit as WFM_MODE_SCORE_LIMIT, so a pair beyond
+// the limit ends with WF_STATUS_MAX_STEPS_REACHED without being aligned first.  WFAlignerEdit and WFAlignerGapLinear are two-piece
+// penalties with both openings at 0.
 #pragma once
 
 // wavefront_align.h status codes as the reference tests them (wflign.cpp:150,1168; wflign_patch.cpp:362,447)
@@ -39,7 +44,8 @@ class WFAligner {
   void setHeuristicNone() {}  // the GPU path is always exact (wflign.cpp:145,289,377)
   // adaptive band of the dormant WFlambda aligner (wflign.cpp:1106-1110): the exact alignment is a valid answer
   void setHeuristicWFmash(int /*min_wavefront_length*/, int /*max_distance_threshold*/) {}
-  // an alignment whose score passes `steps` ends with WF_STATUS_MAX_STEPS_REACHED (wflign_patch.cpp:354,441,474)
+  // an alignment whose score passes `steps` ends with WF_STATUS_MAX_STEPS_REACHED (wflign_patch.cpp:354,441,474): on the device for the
+  // MemoryUltralow end-to-end form (WFM_MODE_SCORE_LIMIT), by a comparison behind the alignment for the other forms
   void setMaxAlignmentSteps(int steps) { max_steps_ = steps; }
   // match-callback form of the dormant hierarchical WFlign (wflign.cpp:1163): the callback is host code per cell
   int alignEnd2End(int (*)(int, int, void*), void*, int, int) {
@@ -65,7 +71,7 @@ class WFAligner {
   std::string getAlignment() { return std::string(arena_.data(), res_.ops_len); }  // long form (wflign.cpp:309)
 
  protected:
-  WFAligner(int mismatch, int go1, int ge1, int go2, int ge2, MemoryModel m) : pen_{mismatch, go1, ge1, go2, ge2}, mem_(m) {}
+  WFAligner(int mismatch, int go1, int ge1, int go2, int ge2, AlignmentScope s, MemoryModel m) : pen_{mismatch, go1, ge1, go2, ge2}, scope_(s), mem_(m) {}
 
  private:
   static wfm_handle_t* handle() {
@@ -78,14 +84,19 @@ class WFAligner {
   }
   int run(const char* p, int pl, const char* t, int tl, int mode, int pbf, int pef, int tbf, int tef) {
     wfm_problem_t pr{p, pl, t, tl, mode, pbf, pef, tbf, tef};
-    arena_.assign((size_t)pl + tl + 1, 0);
+    const bool limited = mode == WFM_MODE_END2END_BIWFA && max_steps_ > 0;
+    if (limited) { pr.mode |= WFM_MODE_SCORE_LIMIT; pr.score_hint = max_steps_; }
+    if (scope_ == Score) pr.mode |= WFM_MODE_SCORE_ONLY;
+    arena_.assign(scope_ == Score ? 1 : (size_t)pl + tl + 1, 0);
     res_ = wfm_result_t{};
     const int rc = wfm_align_batch(handle(), &pen_, &pr, 1, &res_, arena_.data(), arena_.size());
     if (rc < 0) res_.status = StatusOOM;
-    else if (res_.status == 0 && max_steps_ >= 0 && res_.score > max_steps_) res_.status = StatusMaxStepsReached;
+    else if (res_.status == WFM_ST_MAX_SCORE) res_.status = StatusMaxStepsReached;
+    else if (res_.status == 0 && !limited && max_steps_ >= 0 && res_.score > max_steps_) res_.status = StatusMaxStepsReached;
     return res_.status;  // 0 == WF_STATUS_ALG_COMPLETED (wflign.cpp:150,307,399)
   }
   wfm_penalties_t pen_;
+  AlignmentScope scope_;
   MemoryModel mem_;
   wfm_result_t res_{};
   std::vector<char> arena_;
@@ -95,15 +106,27 @@ class WFAligner {
 // gap-affine (one piece) = two identical pieces; only the dormant WFlign class builds it (wflign.cpp:1097-1125)
 class WFAlignerGapAffine : public WFAligner {
  public:
-  WFAlignerGapAffine(int mismatch, int gapOpening, int gapExtension, AlignmentScope, MemoryModel memoryModel)
-      : WFAligner(mismatch, gapOpening, gapExtension, gapOpening, gapExtension, memoryModel) {}
+  WFAlignerGapAffine(int mismatch, int gapOpening, int gapExtension, AlignmentScope scope, MemoryModel memoryModel)
+      : WFAligner(mismatch, gapOpening, gapExtension, gapOpening, gapExtension, scope, memoryModel) {}
 };
 
 class WFAlignerGapAffine2Pieces : public WFAligner {
  public:
   WFAlignerGapAffine2Pieces(int /*match, always 0 in wfmash*/, int mismatch, int gapOpening1, int gapExtension1,
-                            int gapOpening2, int gapExtension2, AlignmentScope, MemoryModel memoryModel)
-      : WFAligner(mismatch, gapOpening1, gapExtension1, gapOpening2, gapExtension2, memoryModel) {}
+                            int gapOpening2, int gapExtension2, AlignmentScope scope, MemoryModel memoryModel)
+      : WFAligner(mismatch, gapOpening1, gapExtension1, gapOpening2, gapExtension2, scope, memoryModel) {}
+};
+
+// edit distance and gap-linear penalties = two identical pieces that open for nothing
+class WFAlignerEdit : public WFAligner {
+ public:
+  WFAlignerEdit(AlignmentScope scope, MemoryModel memoryModel) : WFAligner(1, 0, 1, 0, 1, scope, memoryModel) {}
+};
+
+class WFAlignerGapLinear : public WFAligner {
+ public:
+  WFAlignerGapLinear(int mismatch, int indel, AlignmentScope scope, MemoryModel memoryModel)
+      : WFAligner(mismatch, 0, indel, 0, indel, scope, memoryModel) {}
 };
 
 }  // namespace wfa

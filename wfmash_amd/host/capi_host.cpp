@@ -153,6 +153,7 @@ int wfmh_test_expand_runs(const uint32_t* runs, int n, const wfm_penalties_t* pe
 // test hook: the row arithmetic of csrc/wfa_rows.h and csrc/wfa_plan.h, n queries of 7 numbers (op, then its arguments), two results each.
 // op 0: cells_sum(pl, tl, sub, a, b); 1: rng_block(pl, tl, sub, s_from, s_to) -> L, R; 2: tile_span(L, R, idx, core) -> lo, hi;
 // 3: tiles_for(L, R, core); 4: tile_job_leaves(pl, tl, sub, s0, band, chunk) with T = 100, 5: the same with T = 32
+// 6: tile_job_beyond_limit(pl, tl, sub, limit, s0) with T = 100, 7: the same with T = 32
 int wfmh_test_rows(const int32_t* q, int64_t n, int64_t* out) {
   for (int64_t i = 0; i < n; ++i, q += 7, out += 2) {
     int a = 0, b = 0;
@@ -163,6 +164,7 @@ int wfmh_test_rows(const int32_t* q, int64_t n, int64_t* out) {
       case 2: wfm::tile_span(q[1], q[2], q[3], q[4], &a, &b); out[0] = a; out[1] = b; break;
       case 3: out[0] = wfm::tiles_for(q[1], q[2], q[3]); break;
       case 4: case 5: out[0] = wfm::tile_job_leaves(q[1], q[2], q[3], q[4], q[5], q[6], q[0] == 4 ? 100 : 32); break;
+      case 6: case 7: out[0] = wfm::tile_job_beyond_limit(q[1], q[2], q[3], q[4], q[5], q[0] == 6 ? 100 : 32); break;
       default: return -1;
     }
   }
