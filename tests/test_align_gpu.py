@@ -260,6 +260,94 @@ def test_every_leaf_on_tiles_matches_oracle(gpu, oracle):
     assert not bad, f"{len(bad)}/{len(items)} differ: {bad[:8]}"
 
 
+def _three_forms_batch(oracle):
+    """(items, expected): 39 problems of 1 to 1500 bases for the three forms of the base kernels -- patches in head and tail form whose rows stay
+    under 128 diagonals (one wave) or pass them (the mailbox; tiles under WFM_BASE_TILES=2) and whose scores fall below 125, between 125 and 250 and
+    beyond (a tile block is 125 scores), BiWFA pairs with a 30 - 900 base gap (leaves that begin and end inside a gap component), plain pairs, an
+    empty side each way, and three of the problems once more as score-only.  expected: (score, ops) -- score None for the patches (the device reports the
+    penalty of the whole patch, free ends included; the tests of the patches compare ops), ops None for the score-only problems."""
+    rng = random.Random(28)
+    items, exp = [], []
+    for i, (L, div) in enumerate([(1, 0.0), (40, 0.1), (60, 0.3), (130, 0.05), (130, 0.2), (400, 0.1), (400, 0.25), (900, 0.04), (1500, 0.02)]):
+        p = synth.random_dna(6100 + i, L)
+        t = synth.mutate(p, div, 6200 + i) or b"A"
+        if i % 3 == 1:
+            t = synth.random_dna(6300 + i, 25) + t
+        for args in ((len(p), 0, len(t), 0), (0, len(p), 0, len(t))):  # head form, tail form
+            items.append((p, t, capi.WFM_MODE_ENDSFREE, args[0], args[1], args[2], args[3]))
+            rc, ops, _, _ = oracle.align_endsfree(p, args[0], args[1], t, args[2], args[3])
+            assert rc == 0
+            exp.append((None, ops))
+    pairs = []
+    for i, gap in enumerate([30, 300, 900, 30, 300, 900, 120, 600]):
+        a = synth.random_dna(6400 + i, rng.choice([400, 600]))
+        cut = rng.randrange(100, len(a) - 100)
+        b = synth.mutate(a[:cut], 0.03, 6500 + i) + synth.random_dna(6600 + i, gap) + synth.mutate(a[cut:], 0.03, 6700 + i)
+        pairs.append((a, b[:1500]) if i % 2 else (b[:1500], a))
+    for i, (L, div) in enumerate([(1, 0.0), (60, 0.1), (300, 0.02), (300, 0.3), (1000, 0.1), (1000, 0.3), (1500, 0.05), (1500, 0.2)]):
+        p = synth.random_dna(6800 + i, L)
+        pairs.append((p, synth.mutate(p, div, 6900 + i) or b"C"))
+    pairs += [(b"", synth.random_dna(6990, 70)), (synth.random_dna(6991, 90), b"")]
+    for p, t in pairs:
+        items.append((p, t))
+        rc, ops, sc, _ = oracle.align_biwfa(p, t)
+        assert rc == 0
+        exp.append((sc, ops))
+    for i in (8, 13, 23):  # a 130-base patch (head form), a 400-base patch (tail form), a pair with a 900-base gap: the score alone
+        it = items[i]
+        items.append((it[0], it[1], (it[2] if len(it) > 2 else capi.WFM_MODE_END2END_BIWFA) | capi.WFM_MODE_SCORE_ONLY) + (tuple(it[3:7]) if len(it) > 3 else (0, 0, 0, 0)))
+        exp.append((exp[i][0], None))
+    return items, exp
+
+
+def test_ring_register_and_tile_forms_agree_on_the_same_jobs(gpu, oracle):
+    """One batch through the three forms of the base kernels in one process: WFM_BASE_V2=0 (every base job on r32::wfa_base_kernel's ring), nothing
+    set (wfa_base2_kernel's registers where a job fits them), WFM_BASE_TILES=2 (wfa_base2t_kernel's tiles for every row beyond 128 diagonals).
+    The three share their walk back, their row ranges and -- registers and tiles -- their step: status, score, ops and n_runs are equal across the
+    runs, ops are the oracle's (and the score, for the BiWFA problems).  That the runs are three kernels is read from the problems' flags: WFM_PF_RING_KERNEL
+    on every problem of the first run that has a job on tiles in the third, and on none of the other two.  `cells` is asserted equal between the register and the tile runs: it is on
+    the parent of the change that shared the step, for these inputs (there the ring run's cells are the same numbers too; that is not asserted)."""
+    import os
+    items, exp = _three_forms_batch(oracle)
+    assert 36 <= len(items) <= 44
+    runs, flags = {}, {}
+    switches = ("WFM_BASE_V2", "WFM_BASE_TILES")
+    before = {k: os.environ.pop(k) for k in switches if k in os.environ}
+    try:
+        for name, env in (("ring", {"WFM_BASE_V2": "0"}), ("registers", {}), ("tiles", {"WFM_BASE_TILES": "2"})):
+            os.environ.update(env)
+            try:
+                runs[name] = gpu.align(items)
+                flags[name] = gpu.problem_flags(len(items))
+            finally:
+                for k in env:
+                    del os.environ[k]
+    finally:
+        os.environ.update(before)
+    on_tiles = [i for i, f in enumerate(flags["tiles"]) if f & capi.WFM_PF_BASE_TILES]
+    on_ring = [i for i, f in enumerate(flags["ring"]) if f & capi.WFM_PF_RING_KERNEL]
+    assert len(on_tiles) * 3 >= len(items), flags["tiles"]
+    assert not any(f & capi.WFM_PF_BASE_TILES for f in flags["ring"]), flags["ring"]
+    # the three runs are three kernels: a problem that had a job on tiles has it on the ring under WFM_BASE_V2=0, and without a switch nothing runs there
+    # (nor on tiles, but for the patches that overflow their first budget: their next attempt's rows pass 2048 diagonals)
+    assert set(on_tiles) <= set(on_ring), (on_tiles, on_ring)
+    assert not any(f & capi.WFM_PF_RING_KERNEL for f in list(flags["registers"]) + list(flags["tiles"])), (flags["registers"], flags["tiles"])
+    assert all(f & capi.WFM_PF_BASE_RETRY for f in flags["registers"] if f & capi.WFM_PF_BASE_TILES), flags["registers"]
+    assert sum(bool(f & capi.WFM_PF_BASE_TILES) for f in flags["registers"]) * 3 < len(on_tiles)
+    for i, (sc, ops) in enumerate(exp):
+        a, b, c = (runs[n][i] for n in ("ring", "registers", "tiles"))
+        where = (i, len(items[i][0]), len(items[i][1]))
+        assert a.status == b.status == c.status == 0, where
+        assert a.score == b.score == c.score and sc in (None, b.score), where
+        assert a.ops == b.ops == c.ops, where
+        assert a.n_runs == b.n_runs == c.n_runs, where
+        if ops is not None:
+            assert b.ops == ops, where
+        else:
+            assert b.ops == b"" and b.n_runs == 0, where
+    assert [r.cells for r in runs["registers"]] == [r.cells for r in runs["tiles"]]
+
+
 def test_uni_mode_matches_oracle(gpu, oracle):
     items = [(p, t, capi.WFM_MODE_END2END_UNI) for p, t in _pairs(8, 40, [50, 300, 1200], [0.02, 0.1, 0.3])]
     res = gpu.align(items)

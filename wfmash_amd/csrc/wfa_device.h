@@ -195,7 +195,7 @@ struct BaseResult {
 // the register kernel's delay lines (wfa_base2_kernel's step, its decisions, its rows of pre / bt -- written for the core only), T columns of halo on
 // either side that it computes for itself and that go wrong one column per step from the outside, a snapshot of the last 26 rows between two blocks.
 // A tiny kernel between two launches replays the end test over the tiles of a job (the first score at which a cell ends, the smallest such diagonal),
-// and one wave per job walks back through pre / bt at the end (base2_walk: the register kernel's own walk).
+// and one wave per job walks back through pre / bt at the end (base_walk in wfa_base.h: every base kernel's walk).
 struct Base2TJob {
   BaseJob b;                   // as for wfa_base2_kernel; b.ring_off: two snapshots of B2T_ROWS rows x width behind each other
   int64_t snap_in, snap_out;   // int32 element offsets of the snapshot the next block loads / writes

@@ -3,6 +3,9 @@
 // namespace wfm::r32 and namespace wfm::r128: RING / RMASK (rows a wavefront ring keeps per component, a power of two >=
 // the score scope max(x, o1 + e1, o2 + e2) + 1) resolve to 32 or 128 there.  The default penalties (scope 26) run on
 // 32 rows; any -g the reference accepts up to o2 + e2 = 125 runs on 128 (parse_args.hpp:272-288).
+// What the base kernel shares with the register and tile forms of wfa_tile2.hip -- row 0's range, the result of a trivial job,
+// the run-length writer and the walk back (base_walk) -- is not in this file and so is compiled once: wfa_base.h, included by
+// wfa_kernels.hip at wfm scope before the two inclusions of this file.
 
 struct BpCtx {
   const uint8_t* P[2];
@@ -148,7 +151,7 @@ __device__ __forceinline__ int bp_compute_row(const BpCtx& c, int dir, int s, in
   const int koff = c.koff;  // column = k + koff, multiple-of-4 columns are 16-byte aligned
   const int c_lo = (lo + koff) >> 2, c_hi = (hi + koff) >> 2;
   // the chunk loop is uniform over the workgroup (lanes past the row's end idle through it): the long extensions are
-  // finished by whole waves (wave_lce_tail_g)
+  // finished by whole waves (wave_lce_tail)
   for (int chb = c_lo; chb <= c_hi; chb += (int)blockDim.x) {
     const int ch = chb + (int)threadIdx.x;
     const bool on = ch <= c_hi;
@@ -163,7 +166,7 @@ __device__ __forceinline__ int bp_compute_row(const BpCtx& c, int dir, int s, in
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j)
-      if (__any(q.more[j])) q.ext[j] = wave_lce_tail_g(P, T, q.m[j] - (k0 + j), q.m[j], q.ext[j], q.maxn[j], q.more[j]);
+      if (__any(q.more[j])) q.ext[j] = wave_lce_tail<false>(P, T, nullptr, nullptr, q.m[j] - (k0 + j), q.m[j], q.ext[j], q.maxn[j], q.more[j], 0, 0);
     if (on) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -596,24 +599,6 @@ __device__ __forceinline__ Src bs_src(const BaseCtx& c, int comp, int s, const i
   return r;
 }
 
-struct RleWriter {
-  uint32_t* base;  // entries are written at base[-1], base[-2], ...
-  int n;
-  int cur_op;
-  uint32_t cur_len;
-  bool writes = true;  // several lanes may keep the same writer in step; one of them stores
-  __device__ void push(int op, int len) {
-    if (len <= 0) return;
-    if (op == cur_op) { cur_len += (uint32_t)len; return; }
-    flush();
-    cur_op = op; cur_len = (uint32_t)len;
-  }
-  __device__ void flush() {
-    if (cur_len) { ++n; if (writes) base[-n] = (cur_len << 2) | (uint32_t)cur_op; }
-    cur_len = 0; cur_op = -1;
-  }
-};
-
 // NT: threads of a workgroup.  256 for leaves and ordinary patches (rows of a few hundred to 1.3 k diagonals); 1024 for the
 // jobs with wide rows -- a patch eroded to its 4096-base limit starts 8 k diagonals wide, and the ones that overflow
 // their first score budget are exactly those: at 256 threads a step walked its row in 30 rounds of dependent loads and a
@@ -625,13 +610,8 @@ __global__ __launch_bounds__(NT) void wfa_base_kernel(const uint8_t* __restrict_
                                                        DevPen pen) {
   const BaseJob J = jobs[blockIdx.x];
   const int tid = threadIdx.x;
-  if (J.type != 0) {  // trivial: all-D or all-I (wavefront_bialign_alignment trivial cases)
-    if (tid == 0) {
-      BaseResult r; r.status = 0; r.cells = 0; r.nruns = 0; r.score = 0;
-      const int len = J.type == 1 ? J.pl : J.tl;
-      if (len > 0 && !J.score_only) { rle[J.rle_end - 1] = ((uint32_t)len << 2) | (uint32_t)(J.type == 1 ? OP_D : OP_I); r.nruns = 1; }
-      results[blockIdx.x] = r;
-    }
+  if (J.type != 0) {  // trivial: all-D or all-I
+    if (tid == 0) results[blockIdx.x] = base_trivial_result(J, rle);
     return;
   }
   __shared__ int s_lo[RING];
@@ -656,9 +636,8 @@ __global__ __launch_bounds__(NT) void wfa_base_kernel(const uint8_t* __restrict_
   __syncthreads();
 
   // ---- row 0 ----
-  int lo0, hi0;
-  if (J.endsfree) { lo0 = max(-J.pbf, c.kmin); hi0 = min(J.tbf, c.kmax); }
-  else { lo0 = 0; hi0 = 0; }
+  const BaseRows R0 = base_rows(J);
+  const int lo0 = R0.lo0, hi0 = R0.hi0;
   for (int kb = lo0; kb <= hi0; kb += blockDim.x) {  // uniform over the workgroup: wave_lce is a wave-wide call
     const int k = kb + tid;
     const bool on = k <= hi0;
@@ -771,91 +750,13 @@ __global__ __launch_bounds__(NT) void wfa_base_kernel(const uint8_t* __restrict_
     done = J.endsfree ? (s_endk != INT32_MAX) : (s_done != 0);
   }
 
-  // ---- backtrace (wavefront_backtrace_affine): the first wave, every lane with the same state.  Inside a gap the walk
-  // visits one cell per base and each visit is a dependent load of a decision byte; a patch begins with the ~1 kb end gap
-  // of its record, so those walks were most of this kernel's time.  The cells of a gap lie on a known line -- (score - j e,
-  // diagonal +- j) -- so the 64 lanes read the next 64 decision bytes at once and the walk jumps to the first one that
-  // does not say "extension".  Lane 0 writes.
+  // ---- backtrace (base_walk, wfa_base.h): the first wave, every lane with the same state; lane 0 writes.  The ends-free walk
+  // starts from the offset its end cell holds.  (A score-only job ends here: s is its score.)
   if (tid < 64) {
     const int lane = tid;
     BaseResult r; r.status = status; r.score = s; r.nruns = 0; r.cells = cells;
-    if (status == 0 && !J.score_only) {  // (a score-only job ends here: s is its score)
-      RleWriter w; w.base = rle + J.rle_end; w.n = 0; w.cur_op = -1; w.cur_len = 0; w.writes = lane == 0;
-      int comp = J.endsfree ? C_M : J.comp_end;
-      int k = J.endsfree ? s_endk : k_end;
-      int off = J.endsfree ? bs_row(c, C_M, s)[k] : c.tl;
-      int sc = s;
-      int h = off, v = off - k;
-      if (comp == C_M) {
-        if (v < c.pl) w.push(OP_D, c.pl - v);
-        if (h < c.tl) w.push(OP_I, c.tl - h);
-      }
-      const DevPen& pn = c.pen;
-      while (v > 0 && h > 0 && sc > 0) {
-        if (comp != C_M) {
-          // a run of gap cells: j-th cell of the line, with the loop's own conditions
-          const bool ins = comp == C_I1 || comp == C_I2;
-          const int e = (comp == C_I1 || comp == C_D1) ? pn.e1 : pn.e2, o = (comp == C_I1 || comp == C_D1) ? pn.o1 : pn.o2;
-          const unsigned mask = comp == C_I1 ? BT_I1_EXT : (comp == C_I2 ? BT_I2_EXT : (comp == C_D1 ? BT_D1_EXT : BT_D2_EXT));
-          const int scj = sc - lane * e, kj = ins ? k - lane : k + lane;
-          const bool alive = scj > 0 && (ins ? h - lane > 0 : v - lane > 0);
-          const unsigned bj = alive ? c.bt[(int64_t)scj * c.width + kj] : 0u;
-          const unsigned long long stop = __ballot(!(alive && (bj & mask)));
-          const int j0 = stop ? (int)__builtin_ctzll(stop) : 64;  // cells 0 .. j0-1 continue the gap
-          if (j0 > 0) {
-            w.push(ins ? OP_I : OP_D, j0);
-            sc -= j0 * e;
-            if (ins) { k -= j0; off -= j0; } else k += j0;
-            v = off - k; h = off;
-          }
-          if (j0 < 64) {
-            if (!(v > 0 && h > 0 && sc > 0)) break;   // the walk ends inside the gap
-            // the cell that opened the gap
-            sc -= o + e; comp = C_M;
-            w.push(ins ? OP_I : OP_D, 1);
-            if (ins) { --k; --off; } else ++k;
-            v = off - k; h = off;
-          }
-          continue;
-        }
-        // (round 6) A run of mismatches stays on its diagonal, x scores apart -- and between unrelated sequences (the patches that pass every
-        // score budget) that is what a path is made of: thousands of cells, each a dependent load.  The 64 lanes read the decision byte and the
-        // offset of the next 64 cells of that line at once; the walk goes through them from registers for as long as each one's source is the
-        // mismatch.  (Measured: it is NOT what C2's 9.3 ms launches of this kernel are made of -- nor are the ring loads or the extension's
-        // round trips to L2, both tried in LDS / batched four diagonals at a time and taken out again: ~4000 score steps at 2.3 us, ~250
-        // instructions per wave and step over rows of 3.4 k diagonals.  DESIGN.md section 8.)
-        const int scj = sc - lane * pn.x;
-        const unsigned bj = scj > 0 ? (unsigned)c.bt[(int64_t)scj * c.width + k] : 0u;
-        const int pj = scj > 0 ? c.pre[(int64_t)scj * c.width + k] : 0;
-        bool stop = false;
-        for (int j = 0; j < 64; ++j) {
-          const unsigned b = (unsigned)rdlane((int)bj, j);
-          const int pre = rdlane(pj, j);
-          w.push(OP_M, off - pre);
-          off = pre; v = off - k; h = off;
-          if (v <= 0 || h <= 0) { stop = true; break; }
-          const unsigned src = b & 7u;
-          if (src == C_M) {
-            sc -= pn.x; comp = C_M; w.push(OP_X, 1); --off;
-            v = off - k; h = off;
-            if (!(v > 0 && h > 0 && sc > 0)) break;  // (the walk's own condition: it ends here)
-            continue;                                // the next cell of the line: lane j + 1 holds it
-          }
-          if (src == C_I1) { if (b & BT_I1_EXT) { sc -= pn.e1; comp = C_I1; } else { sc -= pn.o1 + pn.e1; comp = C_M; } w.push(OP_I, 1); --k; --off; }
-          else if (src == C_I2) { if (b & BT_I2_EXT) { sc -= pn.e2; comp = C_I2; } else { sc -= pn.o2 + pn.e2; comp = C_M; } w.push(OP_I, 1); --k; --off; }
-          else if (src == C_D1) { if (b & BT_D1_EXT) { sc -= pn.e1; comp = C_D1; } else { sc -= pn.o1 + pn.e1; comp = C_M; } w.push(OP_D, 1); ++k; }
-          else { if (b & BT_D2_EXT) { sc -= pn.e2; comp = C_D2; } else { sc -= pn.o2 + pn.e2; comp = C_M; } w.push(OP_D, 1); ++k; }
-          v = off - k; h = off;
-          break;  // the path leaves the line
-        }
-        if (stop) break;
-      }
-      if (comp == C_M && v > 0 && h > 0) { const int nm = min(v, h); w.push(OP_M, nm); v -= nm; h -= nm; }
-      if (v > 0) w.push(OP_D, v);
-      if (h > 0) w.push(OP_I, h);
-      w.flush();
-      r.nruns = w.n;
-    }
+    if (status == 0 && !J.score_only)
+      r.nruns = base_walk(J, c.pen, c.pre, c.bt, rle, s, J.endsfree ? s_endk : k_end, J.endsfree ? bs_row(c, C_M, s)[s_endk] : c.tl, lane);
     if (lane == 0) results[blockIdx.x] = r;
   }
 }

@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "wfa_device.h"
+#include "wfa_base.h"
 
 namespace wfm {
 
@@ -72,15 +73,32 @@ __device__ __forceinline__ int lce_bounded(const uint8_t* P, const uint8_t* T, i
   return min(lce_from(P + v, T + h, 0, maxn), maxn);
 }
 
-// ---- wave-cooperative long extensions (global-memory form; the tile kernel's LDS-window form follows further down) ----
+// ---- wave-cooperative long extensions ----
 // A run of matches is usually over within a few bases (a cell off the optimal path) -- or it is hundreds to thousands of
 // bases long (the optimal path of a low-divergence record), and then one lane walks it 32 bases per round while the
 // other 63 lanes of its wave, and behind the step's barrier the whole workgroup, wait.  So a lane only looks at the
 // first 40 bases itself; runs that go on are finished by the whole wave, one pending lane after the other, 64 lanes x
 // 8 bases = 512 bases per round trip.  Every lane of the wave must make the call (pend = false when it has nothing).
-__device__ __forceinline__ int rdlane(int v, int src) { return __builtin_amdgcn_readlane(v, src); }
-
-__device__ __forceinline__ int wave_lce_tail_g(const uint8_t* P, const uint8_t* T, int v, int h, int n, int maxn, bool pend) {
+// wave_lce_tail<USE_WIN>: through the LDS sequence windows of the register tile kernel (further down), or -- false, the window arguments
+// unused -- from global memory, which is the form of every kernel of wfa_generic_inc.h and of wfa_bound_kernel.
+constexpr int SEQ_WIN = 8192;  // bytes per window
+__device__ __forceinline__ uint64_t lds_load8(const uint32_t* win, unsigned off) {
+  const uint32_t* w = win + (off >> 2);
+  const unsigned sh = (off & 3u) * 8u;
+  const uint32_t w0 = w[0], w1 = w[1], w2 = w[2];
+  const uint32_t lo = __builtin_amdgcn_alignbit(w1, w0, sh), hi = __builtin_amdgcn_alignbit(w2, w1, sh);
+  return ((uint64_t)hi << 32) | lo;
+}
+// 8 bases of P[v..) xor T[h..)
+__device__ __forceinline__ uint64_t win_xor8(const uint8_t* P, const uint8_t* T, const uint32_t* winP, const uint32_t* winT, int v, int h,
+                                             int wP0, int wT0) {
+  const unsigned ov = (unsigned)(v - wP0), oh = (unsigned)(h - wT0);
+  if (ov <= (unsigned)(SEQ_WIN - 8) && oh <= (unsigned)(SEQ_WIN - 8)) return lds_load8(winP, ov) ^ lds_load8(winT, oh);
+  return load8(P + v) ^ load8(T + h);
+}
+template <bool USE_WIN>
+__device__ __forceinline__ int wave_lce_tail(const uint8_t* P, const uint8_t* T, const uint32_t* winP, const uint32_t* winT, int v, int h,
+                                             int n, int maxn, bool pend, int wP0, int wT0) {
   unsigned long long todo = __ballot(pend);
   const int lane = (int)(threadIdx.x & 63u);
   while (todo) {
@@ -93,7 +111,10 @@ __device__ __forceinline__ int wave_lce_tail_g(const uint8_t* P, const uint8_t* 
       const int off = nn + lane * 8;
       const bool past = off >= mx;
       uint64_t x = 0;
-      if (!past) x = load8(P + v0 + off) ^ load8(T + h0 + off);
+      if (!past) {
+        if (USE_WIN) x = win_xor8(P, T, winP, winT, v0 + off, h0 + off, wP0, wT0);
+        else x = load8(P + v0 + off) ^ load8(T + h0 + off);
+      }
       const unsigned long long hit = __ballot(past || x != 0);
       if (hit) {
         const int f = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(hit));
@@ -110,7 +131,9 @@ __device__ __forceinline__ int wave_lce_tail_g(const uint8_t* P, const uint8_t* 
   return n;
 }
 
-// what a lane does on its own: 8 bases (x8 = their xor, already loaded), then one round of 32; more = the run goes on
+// what a lane does on its own: 8 bases (x8 = their xor, already loaded), then one round of 32; more = the run goes on.  (lce_head40<false>,
+// further down, is the same decision with its short-run loop written out instead of through lce_from, and compiles to 3 % more instructions in
+// wfa_bp_kernel: this form stays -- profiles/base_step_shared.md)
 __device__ __forceinline__ int lce_head40_g(const uint8_t* P, const uint8_t* T, int v, int h, uint64_t x8, int maxn, bool& more) {
   more = false;
   if (x8) return min((int)(__builtin_ctzll(x8) >> 3), maxn);
@@ -133,7 +156,7 @@ __device__ __forceinline__ int wave_lce(const uint8_t* P, const uint8_t* T, int 
   bool more = false;
   int n = 0;
   if (live && maxn > 0) n = lce_head40_g(P, T, v, h, load8(P + v) ^ load8(T + h), maxn, more);
-  if (__any(more)) n = wave_lce_tail_g(P, T, v, h, n, maxn, more);
+  if (__any(more)) n = wave_lce_tail<false>(P, T, nullptr, nullptr, v, h, n, maxn, more, 0, 0);
   return n;
 }
 
@@ -269,21 +292,6 @@ __global__ __launch_bounds__(256) void rle_compact_kernel(const uint32_t* __rest
 // longest stall of a score step.  A tile only touches a few kilobases of either sequence during its T
 // steps (offsets never decrease and fall off by ~5 bases per diagonal away from the furthest one), so a
 // window of each sequence is staged in LDS once per tile; anything outside it still comes from global.
-constexpr int SEQ_WIN = 8192;  // bytes per window
-__device__ __forceinline__ uint64_t lds_load8(const uint32_t* win, unsigned off) {
-  const uint32_t* w = win + (off >> 2);
-  const unsigned sh = (off & 3u) * 8u;
-  const uint32_t w0 = w[0], w1 = w[1], w2 = w[2];
-  const uint32_t lo = __builtin_amdgcn_alignbit(w1, w0, sh), hi = __builtin_amdgcn_alignbit(w2, w1, sh);
-  return ((uint64_t)hi << 32) | lo;
-}
-// 8 bases of P[v..) xor T[h..)
-__device__ __forceinline__ uint64_t win_xor8(const uint8_t* P, const uint8_t* T, const uint32_t* winP, const uint32_t* winT, int v, int h,
-                                             int wP0, int wT0) {
-  const unsigned ov = (unsigned)(v - wP0), oh = (unsigned)(h - wT0);
-  if (ov <= (unsigned)(SEQ_WIN - 8) && oh <= (unsigned)(SEQ_WIN - 8)) return lds_load8(winP, ov) ^ lds_load8(winT, oh);
-  return load8(P + v) ^ load8(T + h);
-}
 // longest common extension from (v, h) on, at most maxn
 __device__ __forceinline__ int win_lce(const uint8_t* P, const uint8_t* T, const uint32_t* winP, const uint32_t* winT, int v, int h, int maxn,
                                        int wP0, int wT0) {
@@ -325,42 +333,6 @@ __device__ __forceinline__ int win_lce(const uint8_t* P, const uint8_t* T, const
     n += 8;
   }
   return min(n, maxn);
-}
-
-// ---- wave-cooperative long extensions, reading through the LDS sequence windows (see wave_lce_tail_g) ----
-template <bool USE_WIN>
-__device__ __forceinline__ int wave_lce_tail(const uint8_t* P, const uint8_t* T, const uint32_t* winP, const uint32_t* winT, int v, int h,
-                                             int n, int maxn, bool pend, int wP0, int wT0) {
-  unsigned long long todo = __ballot(pend);
-  const int lane = (int)(threadIdx.x & 63u);
-  while (todo) {
-    const int src = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(todo));
-    todo &= todo - 1;
-    const int v0 = rdlane(v, src), h0 = rdlane(h, src), mx = rdlane(maxn, src);
-    int nn = rdlane(n, src);  // bases known to match so far (uniform)
-    int res;
-    for (;;) {
-      const int off = nn + lane * 8;
-      const bool past = off >= mx;
-      uint64_t x = 0;
-      if (!past) {
-        if (USE_WIN) x = win_xor8(P, T, winP, winT, v0 + off, h0 + off, wP0, wT0);
-        else x = load8(P + v0 + off) ^ load8(T + h0 + off);
-      }
-      const unsigned long long hit = __ballot(past || x != 0);
-      if (hit) {
-        const int f = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(hit));
-        const unsigned xlo = (unsigned)rdlane((int)(uint32_t)x, f), xhi = (unsigned)rdlane((int)(uint32_t)(x >> 32), f);
-        const uint64_t xf = ((uint64_t)xhi << 32) | xlo;
-        const int at = nn + f * 8;
-        res = at >= mx ? mx : min(mx, at + (xf ? (int)(__builtin_ctzll(xf) >> 3) : 0));
-        break;
-      }
-      nn += 512;
-    }
-    if (lane == src) n = res;
-  }
-  return n;
 }
 
 // what a lane does on its own: 8 bases (x8 = their xor, already loaded), then one round of 32; more = the run goes on
@@ -1415,7 +1387,7 @@ __global__ __launch_bounds__(64) void wfa_bound_kernel(const uint8_t* __restrict
   int events = 0, forced = 0;
   for (;;) {
     const int maxn = min(pl - v, tl - h);
-    int n = wave_lce_tail_g(P, T, v, h, 0, maxn, lane == 0 && maxn > 0);
+    int n = wave_lce_tail<false>(P, T, nullptr, nullptr, v, h, 0, maxn, lane == 0 && maxn > 0, 0, 0);
     n = rdlane(n, 0);
     v += n; h += n;
     if (v >= pl || h >= tl) break;

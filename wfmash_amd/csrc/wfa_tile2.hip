@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "wfa_device.h"
+#include "wfa_base.h"
 #include "wfa_pack.h"
 
 // WFM_TILE_TRACE (a build switch of its own, never the shipped library: scripts/tile_trace.sh): s_memtime stamps of one step's phases, per wave, of the
@@ -66,7 +67,6 @@ __device__ __forceinline__ void lds_barrier() {
 struct __attribute__((packed, aligned(4))) Pair32 { int x, y; };
 __device__ __forceinline__ void ld_pair(const int32_t* p, int& a, int& b) { const Pair32 v = *reinterpret_cast<const Pair32*>(p); a = v.x; b = v.y; }
 __device__ __forceinline__ void st_pair(int32_t* p, int a, int b) { Pair32 v; v.x = a; v.y = b; *reinterpret_cast<Pair32*>(p) = v; }
-__device__ __forceinline__ int rdl(int v, int src) { return __builtin_amdgcn_readlane(v, src); }
 
 // lane i <- lane i - 1 (lane 0 keeps NULL) / lane i <- lane i + 1 (lane 63 keeps NULL): one VALU instruction each
 __device__ __forceinline__ int from_prev_lane(int x) { return __builtin_amdgcn_update_dpp(WF_NULL, x, 0x138, 0xf, 0xf, false); }  // wave_shr:1
@@ -129,9 +129,9 @@ __device__ __forceinline__ int pk_wave_tail(const PkSrc& S, unsigned oP, unsigne
   while (todo) {
     const int src = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(todo));
     todo &= todo - 1;
-    const unsigned p0 = (unsigned)rdl((int)oP, src), t0 = (unsigned)rdl((int)oT, src);
-    const int mx = rdl(maxn, src);
-    int nn = rdl(n, src);
+    const unsigned p0 = (unsigned)rdlane((int)oP, src), t0 = (unsigned)rdlane((int)oT, src);
+    const int mx = rdlane(maxn, src);
+    int nn = rdlane(n, src);
     int res;
     for (;;) {
       const int off = nn + lane * 32;
@@ -145,7 +145,7 @@ __device__ __forceinline__ int pk_wave_tail(const PkSrc& S, unsigned oP, unsigne
       const unsigned long long hit = __ballot(past || x != 0);
       if (hit) {
         const int f = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(hit));
-        const unsigned xlo = (unsigned)rdl((int)(uint32_t)x, f), xhi = (unsigned)rdl((int)(uint32_t)(x >> 32), f);
+        const unsigned xlo = (unsigned)rdlane((int)(uint32_t)x, f), xhi = (unsigned)rdlane((int)(uint32_t)(x >> 32), f);
         const uint64_t xf = ((uint64_t)xhi << 32) | xlo;
         const int at = nn + f * 32;
         res = at >= mx ? mx : min(mx, at + (xf ? (int)(__builtin_ctzll(xf) >> 1) : 0));
@@ -1031,107 +1031,187 @@ void launch_tile2_p2(const uint32_t* pk, int32_t* ring, const TileJob* jobs, con
 // (extension wins ties over opening: BT_*_EXT; source of M on equal offsets: mismatch > D2 > D1 > I2 > I1).  The row ranges
 // the result counts as cells are the ones the ring kernel keeps (per row the union of its sources' ranges), and the
 // backtrace is its backtrace.  Jobs with other penalties, an N, wider rows or longer sequences stay with the ring kernel.
-struct RleWriter2 {
-  uint32_t* base;  // entries are written at base[-1], base[-2], ...
-  int n;
-  int cur_op;
-  uint32_t cur_len;
-  bool writes;
-  __device__ void push(int op, int len) {
-    if (len <= 0) return;
-    if (op == cur_op) { cur_len += (uint32_t)len; return; }
-    flush();
-    cur_op = op; cur_len = (uint32_t)len;
-  }
-  __device__ void flush() {
-    if (cur_len) { ++n; if (writes) base[-n] = (cur_len << 2) | (uint32_t)cur_op; }
-    cur_len = 0; cur_op = -1;
-  }
-};
+// The walk back and the run-length writer are the ring kernel's own (base_walk in wfa_base.h, with these penalties as constants).
+//
+// wfa_base2_kernel (one workgroup holds the row) and wfa_base2t_kernel (a row wider than that, cut into tiles) run ONE step: the
+// b2_ functions below are what a cell computes, for both.  They take the delay lines and the per-lane constants as separate array
+// references, which stay the registers they were (profiles/base_step_shared.md: gathered into structs the same code came out with
+// 12 % more instructions in the tile kernel and 32 spilled registers at 1024 threads).
+constexpr int B2_C = 2, B2_NCL = 5, B2_DEP = 6, B2_E1 = 2;  // diagonals per thread; Mh[c][s % 5][e]: M of diagonal c at the e-th newest score of that class; rows of I1 / D1 kept
+constexpr DevPen B2_PEN{5, 8, 2, 24, 1};                    // the penalties this form is built for (the host checks)
 
-// wavefront_backtrace_affine over the rows a forward pass has left (pre: the offset of every M cell before its extension, bt: its decision byte; both
-// addressed [score][diagonal] with the job's width): every lane of the wave with the same state, lane 0 writes; a run of gap cells is read 64 decision
-// bytes at a time (r32::wfa_base_kernel).  Returns the number of runs written below rle[J.rle_end].
-__device__ __forceinline__ int base2_walk(const BaseJob& J, const int32_t* __restrict__ pre_base, const uint8_t* __restrict__ bt_base, uint32_t* __restrict__ rle,
-                                          int s, int k_from, int off_from, int lane) {
-  constexpr int PX = 5, PO1 = 8, PE1 = 2, PO2 = 24, PE2 = 1;
+// ---- the sequences whole in the windows (the host sends only jobs whose sequences fit); `stride` threads make the call.  dP / dT: where the
+// sequences begin behind the windows' origin
+__device__ __forceinline__ PkSrc b2_load_windows(const BaseJob& J, const uint32_t* __restrict__ pk, uint32_t* s_winP, uint32_t* s_winT, int tid, int stride,
+                                                 int& dP, int& dT) {
+  const int64_t oriP = J.p_off & ~(int64_t)15, oriT = J.t_off & ~(int64_t)15;
+  dP = (int)(J.p_off - oriP); dT = (int)(J.t_off - oriT);
+  PkSrc SRC;
+  SRC.lP = (lds_words)s_winP; SRC.lT = (lds_words)s_winT;
+  SRC.gP = (glb_words)pk + (oriP >> 4); SRC.gT = (glb_words)pk + (oriT >> 4);
+  const int nP = min(PK_WIN_DW + PK_SLACK_DW, (J.pl + dP + 15) / 16 + 8), nT = min(PK_WIN_DW + PK_SLACK_DW, (J.tl + dT + 15) / 16 + 8);
+  for (int i = tid; i < nP; i += stride) s_winP[i] = SRC.gP[i];
+  for (int i = tid; i < nT; i += stride) s_winT[i] = SRC.gT[i];
+  return SRC;
+}
+
+// ---- does the cell of diagonal k end the alignment?  s_done / s_endk: the workgroup's (LDS) -- end2end: 1 when reached; ends-free: the smallest
+// diagonal that satisfies the end condition
+__device__ __forceinline__ void b2_end_checks(const BaseJob& J, int* s_done, int* s_endk, int k, int m_ext, int ins1, int ins2, int del1, int del2) {
   const int pl = J.pl, tl = J.tl;
-  const int64_t width = J.width;
-  RleWriter2 w; w.base = rle + J.rle_end; w.n = 0; w.cur_op = -1; w.cur_len = 0; w.writes = lane == 0;
-  int comp = J.endsfree ? C_M : J.comp_end;
-  int k = k_from;
-  int off = off_from;
-  int sc = s;
-  int h = off, v = off - k;
-  if (comp == C_M) {
-    if (v < pl) w.push(OP_D, pl - v);
-    if (h < tl) w.push(OP_I, tl - h);
-  }
-  while (v > 0 && h > 0 && sc > 0) {
-    if (comp != C_M) {
-      const bool ins = comp == C_I1 || comp == C_I2;
-      const int e = (comp == C_I1 || comp == C_D1) ? PE1 : PE2, o = (comp == C_I1 || comp == C_D1) ? PO1 : PO2;
-      const unsigned mask = comp == C_I1 ? BT_I1_EXT : (comp == C_I2 ? BT_I2_EXT : (comp == C_D1 ? BT_D1_EXT : BT_D2_EXT));
-      const int scj = sc - lane * e, kj = ins ? k - lane : k + lane;
-      const bool alive = scj > 0 && (ins ? h - lane > 0 : v - lane > 0);
-      const unsigned bj = alive ? bt_base[(int64_t)scj * width + kj] : 0u;
-      const unsigned long long stop = __ballot(!(alive && (bj & mask)));
-      const int j0 = stop ? (int)__builtin_ctzll(stop) : 64;  // cells 0 .. j0-1 continue the gap
-      if (j0 > 0) {
-        w.push(ins ? OP_I : OP_D, j0);
-        sc -= j0 * e;
-        if (ins) { k -= j0; off -= j0; } else k += j0;
-        v = off - k; h = off;
-      }
-      if (j0 < 64) {
-        if (!(v > 0 && h > 0 && sc > 0)) break;   // the walk ends inside the gap
-        sc -= o + e; comp = C_M;                  // the cell that opened the gap
-        w.push(ins ? OP_I : OP_D, 1);
-        if (ins) { --k; --off; } else ++k;
-        v = off - k; h = off;
-      }
-      continue;
+  if (J.endsfree) {
+    if (m_ext >= 0) {
+      const int h = m_ext, v = m_ext - k;
+      if ((h >= tl && pl - v <= J.pef) || (v >= pl && tl - h <= J.tef)) atomicMin(s_endk, k);
     }
-    // (round 6, as in the ring kernel's walk -- wfa_generic_inc.h: a run of mismatches stays on its diagonal, PX scores apart: the lanes read
-    // the next 64 cells of that line at once, the walk goes through them from registers while each one's source is the mismatch)
-    const int scj = sc - lane * PX;
-    const unsigned bj = scj > 0 ? (unsigned)bt_base[(int64_t)scj * width + k] : 0u;
-    const int pj = scj > 0 ? pre_base[(int64_t)scj * width + k] : 0;
-    bool stop = false;
-    for (int j = 0; j < 64; ++j) {
-      const unsigned b = (unsigned)rdl((int)bj, j);
-      const int pre = rdl(pj, j);
-      w.push(OP_M, off - pre);
-      off = pre; v = off - k; h = off;
-      if (v <= 0 || h <= 0) { stop = true; break; }
-      const unsigned src = b & 7u;
-      if (src == C_M) {
-        sc -= PX; comp = C_M; w.push(OP_X, 1); --off;
-        v = off - k; h = off;
-        if (!(v > 0 && h > 0 && sc > 0)) break;
-        continue;
-      }
-      if (src == C_I1) { if (b & BT_I1_EXT) { sc -= PE1; comp = C_I1; } else { sc -= PO1 + PE1; comp = C_M; } w.push(OP_I, 1); --k; --off; }
-      else if (src == C_I2) { if (b & BT_I2_EXT) { sc -= PE2; comp = C_I2; } else { sc -= PO2 + PE2; comp = C_M; } w.push(OP_I, 1); --k; --off; }
-      else if (src == C_D1) { if (b & BT_D1_EXT) { sc -= PE1; comp = C_D1; } else { sc -= PO1 + PE1; comp = C_M; } w.push(OP_D, 1); ++k; }
-      else { if (b & BT_D2_EXT) { sc -= PE2; comp = C_D2; } else { sc -= PO2 + PE2; comp = C_M; } w.push(OP_D, 1); ++k; }
-      v = off - k; h = off;
-      break;
-    }
-    if (stop) break;
+  } else if (k == tl - pl) {
+    const int ev = J.comp_end == C_M ? m_ext : (J.comp_end == C_I1 ? ins1 : (J.comp_end == C_I2 ? ins2 : (J.comp_end == C_D1 ? del1 : del2)));
+    if (ev >= tl) *s_done = 1;
   }
-  if (comp == C_M && v > 0 && h > 0) { const int nm = min(v, h); w.push(OP_M, nm); v -= nm; h -= nm; }
-  if (v > 0) w.push(OP_D, v);
-  if (h > 0) w.push(OP_I, h);
-  w.flush();
-  return w.n;
+}
+
+// ---- row 0 over [lo0, hi0]: the ends-free form or the job's begin component, extended; no cell of it has a neighbour to wait for (a tile's halo
+// cells are right).  keep[c]: the cell's pre / bt are written and its end test is made -- every cell's (registers), or the tile's core's
+__device__ __forceinline__ void b2_row0(const BaseJob& J, const PkSrc& SRC, int dT, int lo0, int hi0, int k0, const int (&cP)[B2_C], const bool (&keep)[B2_C],
+                                        int32_t* pre_base, uint8_t* bt_base, int* s_done, int* s_endk, int (&Mh)[B2_C][B2_NCL][B2_DEP], int (&I1h)[B2_C][B2_E1],
+                                        int (&D1h)[B2_C][B2_E1], int (&I2h)[B2_C], int (&D2h)[B2_C], int (&mcur)[B2_C]) {
+  constexpr int C = B2_C;
+  const int pl = J.pl, tl = J.tl, k_end = tl - pl;
+  int m0[C], ext[C], maxn[C];
+  unsigned oP[C], oT[C];
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    const int k = k0 + c;
+    const bool on = k >= lo0 && k <= hi0;
+    int m = WF_NULL;
+    if (on) {
+      if (J.endsfree) m = k > 0 ? k : 0;
+      else {
+        if (J.comp_begin == C_M) m = 0;
+        I1h[c][0] = J.comp_begin == C_I1 ? 0 : WF_NULL;
+        I2h[c] = J.comp_begin == C_I2 ? 0 : WF_NULL;
+        D1h[c][0] = J.comp_begin == C_D1 ? 0 : WF_NULL;
+        D2h[c] = J.comp_begin == C_D2 ? 0 : WF_NULL;
+      }
+    }
+    m0[c] = m;
+    oP[c] = (unsigned)(m + cP[c]); oT[c] = (unsigned)(m + dT);
+    maxn[c] = m >= 0 ? min(pl - (m - k), tl - m) : 0;
+  }
+  pk_extend2(SRC, m0, oP, oT, maxn, ext);
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    const int k = k0 + c;
+    if (k < lo0 || k > hi0) continue;
+    if (keep[c]) { pre_base[k] = m0[c]; bt_base[k] = 0; }
+    int m = m0[c];
+    if (m >= 0) m += ext[c];
+    if (keep[c]) {
+      if (J.endsfree) b2_end_checks(J, s_done, s_endk, k, m, WF_NULL, WF_NULL, WF_NULL, WF_NULL);
+      else if (k == k_end && J.comp_end == C_M && m >= tl) *s_done = 1;
+    }
+    Mh[c][0][0] = m;
+    mcur[c] = m;
+  }
+}
+
+// ---- the mailbox: what the step of class cl reads from a wave's edge lanes, published for the wave's neighbours before the step's barrier, and
+// behind it the values of the diagonals k0 - 1 (l*) and k0 + C (r*) -- the next lane's, or across a wave's edge the mailbox's.  WAVE1: the workgroup
+// is one wave and there is no mailbox; nw: the waves of the workgroup that run
+template <bool WAVE1, int NWV>
+__device__ __forceinline__ void b2_publish_edges(int (&s_edge)[2][NWV][2][4], int par, int wv, int lane, int cl, const int (&Mh)[B2_C][B2_NCL][B2_DEP],
+                                                 const int (&I1h)[B2_C][B2_E1], const int (&D1h)[B2_C][B2_E1], const int (&I2h)[B2_C], const int (&D2h)[B2_C]) {
+  constexpr int C = B2_C, E1 = B2_E1;
+  if (WAVE1) return;
+  if (lane == 63) { int* e = s_edge[par][wv][0]; e[0] = Mh[C - 1][cl][1]; e[1] = Mh[C - 1][cl][4]; e[2] = I1h[C - 1][E1 - 1]; e[3] = I2h[C - 1]; }
+  if (lane == 0)  { int* e = s_edge[par][wv][1]; e[0] = Mh[0][cl][1];     e[1] = Mh[0][cl][4];     e[2] = D1h[0][E1 - 1];     e[3] = D2h[0]; }
+}
+template <bool WAVE1, int NWV>
+__device__ __forceinline__ void b2_neighbours(const int (&s_edge)[2][NWV][2][4], int par, int wv, int nw, int lane, int cl,
+                                              const int (&Mh)[B2_C][B2_NCL][B2_DEP], const int (&I1h)[B2_C][B2_E1], const int (&D1h)[B2_C][B2_E1],
+                                              const int (&I2h)[B2_C], const int (&D2h)[B2_C], int& lM10, int& lM25, int& lI1, int& lI2, int& rM10, int& rM25,
+                                              int& rD1, int& rD2) {
+  constexpr int C = B2_C, E1 = B2_E1;
+  lM10 = from_prev_lane(Mh[C - 1][cl][1]); lM25 = from_prev_lane(Mh[C - 1][cl][4]);
+  lI1 = from_prev_lane(I1h[C - 1][E1 - 1]); lI2 = from_prev_lane(I2h[C - 1]);
+  rM10 = from_next_lane(Mh[0][cl][1]); rM25 = from_next_lane(Mh[0][cl][4]);
+  rD1 = from_next_lane(D1h[0][E1 - 1]); rD2 = from_next_lane(D2h[0]);
+  if (WAVE1) return;
+  if (lane == 0 && wv > 0) { const int* e = s_edge[par][wv - 1][0]; lM10 = e[0]; lM25 = e[1]; lI1 = e[2]; lI2 = e[3]; }
+  if (lane == 63 && wv + 1 < nw) { const int* e = s_edge[par][wv + 1][1]; rM10 = e[0]; rM25 = e[1]; rD1 = e[2]; rD2 = e[3]; }
+}
+
+// ---- the recurrences of row s over [lo, hi] for the thread's diagonals k0 .. k0 + C - 1, from the delay lines and the neighbours' values (l*: of
+// diagonal k0 - 1, r*: of k0 + C): the five components before the extension and the decision byte of each M cell
+__device__ __forceinline__ void b2_cells(const int (&Mh)[B2_C][B2_NCL][B2_DEP], const int (&I1h)[B2_C][B2_E1], const int (&D1h)[B2_C][B2_E1], const int (&I2h)[B2_C],
+                                         const int (&D2h)[B2_C], int cl, int lM10, int lM25, int lI1, int lI2, int rM10, int rM25, int rD1, int rD2,
+                                         const unsigned (&hmaxu)[B2_C], const bool (&colok)[B2_C], int k0, int lo, int hi, int (&nM)[B2_C], int (&nI1)[B2_C],
+                                         int (&nI2)[B2_C], int (&nD1)[B2_C], int (&nD2)[B2_C], unsigned (&btb)[B2_C]) {
+  constexpr int C = B2_C, E1 = B2_E1;
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    const int k = k0 + c;
+    const int a10 = c == 0 ? lM10 : Mh[c - 1][cl][1], b10 = c == C - 1 ? rM10 : Mh[c + 1][cl][1];
+    const int a25 = c == 0 ? lM25 : Mh[c - 1][cl][4], b25 = c == C - 1 ? rM25 : Mh[c + 1][cl][4];
+    const int i1 = c == 0 ? lI1 : I1h[c - 1][E1 - 1], d1 = c == C - 1 ? rD1 : D1h[c + 1][E1 - 1];
+    const int i2 = c == 0 ? lI2 : I2h[c - 1], d2 = c == C - 1 ? rD2 : D2h[c + 1];
+    const int mx = Mh[c][cl][0];
+    unsigned bits = 0;
+    // ext wins ties (WFA2-lib: ext type > open type; piggyback: ext >= open)
+    if (i1 >= a10) bits |= BT_I1_EXT;
+    if (i2 >= a25) bits |= BT_I2_EXT;
+    if (d1 >= b10) bits |= BT_D1_EXT;
+    if (d2 >= b25) bits |= BT_D2_EXT;
+    const unsigned hm = hmaxu[c];
+    int ins1 = max(a10, i1) + 1, ins2 = max(a25, i2) + 1, del1 = max(b10, d1), del2 = max(b25, d2), mis = mx + 1;
+    ins1 = (unsigned)ins1 <= hm ? ins1 : WF_NULL;
+    ins2 = (unsigned)ins2 <= hm ? ins2 : WF_NULL;
+    del1 = (unsigned)del1 <= hm ? del1 : WF_NULL;
+    del2 = (unsigned)del2 <= hm ? del2 : WF_NULL;
+    mis = (unsigned)mis <= hm ? mis : WF_NULL;
+    // M source priority on equal offsets: mismatch > D2 > D1 > I2 > I1
+    int m = ins1; unsigned src = C_I1;
+    if (ins2 >= m) { m = ins2; src = C_I2; }
+    if (del1 >= m) { m = del1; src = C_D1; }
+    if (del2 >= m) { m = del2; src = C_D2; }
+    if (mis >= m)  { m = mis;  src = C_M; }
+    const bool on = k >= lo && k <= hi;  // (outside the row's range the ring kernel computes nothing: nothing is kept there)
+    nI1[c] = on ? ins1 : WF_NULL; nI2[c] = on ? ins2 : WF_NULL; nD1[c] = on ? del1 : WF_NULL; nD2[c] = on ? del2 : WF_NULL;
+    nM[c] = (on && colok[c]) ? m : WF_NULL;
+    btb[c] = bits | src;
+  }
+}
+// ---- the new row into the delay lines
+__device__ __forceinline__ void b2_shift(int (&Mh)[B2_C][B2_NCL][B2_DEP], int (&I1h)[B2_C][B2_E1], int (&D1h)[B2_C][B2_E1], int (&I2h)[B2_C], int (&D2h)[B2_C],
+                                         int (&mcur)[B2_C], int cl, const int (&nM)[B2_C], const int (&nI1)[B2_C], const int (&nI2)[B2_C],
+                                         const int (&nD1)[B2_C], const int (&nD2)[B2_C]) {
+#pragma unroll
+  for (int c = 0; c < B2_C; ++c) {
+    mcur[c] = nM[c];
+#pragma unroll
+    for (int e = B2_DEP - 1; e > 0; --e) Mh[c][cl][e] = Mh[c][cl][e - 1];
+    Mh[c][cl][0] = nM[c];
+#pragma unroll
+    for (int d = B2_E1 - 1; d > 0; --d) { I1h[c][d] = I1h[c][d - 1]; D1h[c][d] = D1h[c][d - 1]; }
+    I1h[c][0] = nI1[c]; D1h[c][0] = nD1[c];
+    I2h[c] = nI2[c]; D2h[c] = nD2[c];
+  }
+}
+
+// ---- the snapshot between two blocks of a tile job, B2T_ROWS rows of the job's width: rows 0 .. 25 = M of scores s0, s0 - 1, ..; 26 / 27 = I1 of
+// s0 / s0 - 1; 28 / 29 = D1; 30 = I2; 31 = D2.  The delay-line register that holds a row's value of one diagonal (row: a constant where it is used)
+__device__ __forceinline__ int& b2_snap_reg(int (&M)[B2_NCL][B2_DEP], int (&I1)[B2_E1], int (&D1)[B2_E1], int& I2, int& D2, int row) {
+  static_assert(B2T_ROWS == SNAP_ROWS + 2 * B2_E1 + 2, "the snapshot's rows");
+  if (row < SNAP_ROWS) return M[(B2_NCL - row % B2_NCL) % B2_NCL][row / B2_NCL];
+  if (row < SNAP_ROWS + B2_E1) return I1[row - SNAP_ROWS];
+  if (row < SNAP_ROWS + 2 * B2_E1) return D1[row - SNAP_ROWS - B2_E1];
+  return row == SNAP_ROWS + 2 * B2_E1 ? I2 : D2;
 }
 
 template <int NTMAX>
 __global__ __launch_bounds__(NTMAX) void wfa_base2_kernel(const uint32_t* __restrict__ pk, int32_t* __restrict__ arena32, uint8_t* __restrict__ arena8,
                                                         uint32_t* __restrict__ rle, const BaseJob* __restrict__ jobs, BaseResult* __restrict__ results) {
-  constexpr int C = 2, NCL = 5, DEP = 6, E1 = 2;
-  constexpr int PX = 5, PO1 = 8, PE1 = 2, PO2 = 24, PE2 = 1;  // the penalties this form is built for (the host checks)
+  constexpr int C = B2_C, NCL = B2_NCL, DEP = B2_DEP, E1 = B2_E1;
   constexpr bool WAVE1 = NTMAX == 64;
   const BaseJob J = jobs[blockIdx.x];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -1139,13 +1219,8 @@ __global__ __launch_bounds__(NTMAX) void wfa_base2_kernel(const uint32_t* __rest
   const int nw = J.type != 0 ? 1 : min((int)(blockDim.x >> 6), (int)((J.width - 1) / (64 * 2)) + 1), NT = nw * 64;
   if (wv >= nw) return;
   const long long t_begin = wall_clock64();
-  if (J.type != 0) {  // trivial: all-D or all-I (wavefront_bialign_alignment trivial cases)
-    if (tid == 0) {
-      BaseResult r; r.status = 0; r.cells = 0; r.nruns = 0; r.score = 0; r.pad_ = 0;
-      const int len = J.type == 1 ? J.pl : J.tl;
-      if (len > 0 && !J.score_only) { rle[J.rle_end - 1] = ((uint32_t)len << 2) | (uint32_t)(J.type == 1 ? OP_D : OP_I); r.nruns = 1; }
-      results[blockIdx.x] = r;
-    }
+  if (J.type != 0) {
+    if (tid == 0) results[blockIdx.x] = base_trivial_result(J, rle);
     return;
   }
   __shared__ int s_edge[2][WAVE1 ? 1 : 16][2][4];
@@ -1156,17 +1231,8 @@ __global__ __launch_bounds__(NTMAX) void wfa_base2_kernel(const uint32_t* __rest
   int32_t* pre_base = arena32 + J.pre_off - kmin;
   uint8_t* bt_base = arena8 + J.bt_off - kmin;
   const int k_end = tl - pl;
-  // ---- the sequences whole in the windows (the host sends only jobs whose sequences fit)
-  const int64_t oriP = J.p_off & ~(int64_t)15, oriT = J.t_off & ~(int64_t)15;
-  const int dP = (int)(J.p_off - oriP), dT = (int)(J.t_off - oriT);
-  PkSrc SRC;
-  SRC.lP = (lds_words)s_winP; SRC.lT = (lds_words)s_winT;
-  SRC.gP = (glb_words)pk + (oriP >> 4); SRC.gT = (glb_words)pk + (oriT >> 4);
-  {
-    const int nP = min(PK_WIN_DW + PK_SLACK_DW, (pl + dP + 15) / 16 + 8), nT = min(PK_WIN_DW + PK_SLACK_DW, (tl + dT + 15) / 16 + 8);
-    for (int i = tid; i < nP; i += NT) s_winP[i] = SRC.gP[i];
-    for (int i = tid; i < nT; i += NT) s_winT[i] = SRC.gT[i];
-  }
+  int dP, dT;
+  const PkSrc SRC = b2_load_windows(J, pk, s_winP, s_winT, tid, NT, dP, dT);
   if (tid == 0) { s_done = 0; s_endk = INT32_MAX; s_endoff = 0; }
   for (int i = tid; i < (int)(sizeof(s_edge) / sizeof(int)); i += NT) ((int*)s_edge)[i] = WF_NULL;  // (a wave that has no cell yet publishes nothing)
   __syncthreads();
@@ -1194,58 +1260,10 @@ __global__ __launch_bounds__(NTMAX) void wfa_base2_kernel(const uint32_t* __rest
     wlim[c] = PK_WIN_BASES - 1 - max(cP[c], dT);
     mcur[c] = WF_NULL;
   }
-  auto end_checks = [&](int c, int k, int m_ext, int ins1, int ins2, int del1, int del2) {
-    if (J.endsfree) {
-      if (m_ext >= 0) {
-        const int h = m_ext, v = m_ext - k;
-        if ((h >= tl && pl - v <= J.pef) || (v >= pl && tl - h <= J.tef)) atomicMin(&s_endk, k);
-      }
-    } else if (k == k_end) {
-      const int ev = J.comp_end == C_M ? m_ext : (J.comp_end == C_I1 ? ins1 : (J.comp_end == C_I2 ? ins2 : (J.comp_end == C_D1 ? del1 : del2)));
-      if (ev >= tl) s_done = 1;
-    }
-    (void)c;
-  };
-  // ---- row 0
-  int lo0, hi0;
-  if (J.endsfree) { lo0 = max(-J.pbf, kmin); hi0 = min(J.tbf, kmax); }
-  else { lo0 = 0; hi0 = 0; }
-  {
-    int m0[C], ext[C], maxn[C];
-    unsigned oP[C], oT[C];
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-      const int k = k0 + c;
-      const bool on = k >= lo0 && k <= hi0;
-      int m = WF_NULL;
-      if (on) {
-        if (J.endsfree) m = k > 0 ? k : 0;
-        else {
-          if (J.comp_begin == C_M) m = 0;
-          I1h[c][0] = J.comp_begin == C_I1 ? 0 : WF_NULL;
-          I2h[c] = J.comp_begin == C_I2 ? 0 : WF_NULL;
-          D1h[c][0] = J.comp_begin == C_D1 ? 0 : WF_NULL;
-          D2h[c] = J.comp_begin == C_D2 ? 0 : WF_NULL;
-        }
-      }
-      m0[c] = m;
-      oP[c] = (unsigned)(m + cP[c]); oT[c] = (unsigned)(m + dT);
-      maxn[c] = m >= 0 ? min(pl - (m - k), tl - m) : 0;
-    }
-    pk_extend2(SRC, m0, oP, oT, maxn, ext);
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-      const int k = k0 + c;
-      if (k < lo0 || k > hi0) continue;
-      pre_base[k] = m0[c]; bt_base[k] = 0;
-      int m = m0[c];
-      if (m >= 0) m += ext[c];
-      if (J.endsfree) end_checks(c, k, m, WF_NULL, WF_NULL, WF_NULL, WF_NULL);
-      else if (k == k_end && J.comp_end == C_M && m >= tl) s_done = 1;
-      Mh[c][0][0] = m;
-      mcur[c] = m;
-    }
-  }
+  const BaseRows R = base_rows(J);
+  const int lo0 = R.lo0, hi0 = R.hi0;
+  const bool keep[C] = {true, true};  // (every cell is this workgroup's)
+  b2_row0(J, SRC, dT, lo0, hi0, k0, cP, keep, pre_base, bt_base, &s_done, &s_endk, Mh, I1h, D1h, I2h, D2h, mcur);
   uint64_t cells = (uint64_t)(hi0 - lo0 + 1);
   int s = 0, status = 0;
   bool done = false;
@@ -1255,21 +1273,15 @@ __global__ __launch_bounds__(NTMAX) void wfa_base2_kernel(const uint32_t* __rest
   for (int jj = 1; jj <= NCL; ++jj) {
     const int cl = jj % NCL;
     const int sn = tb + jj;  // the score this step computes
-    int lM10, lM25, lI1, lI2, rM10, rM25, rD1, rD2;
     const int par = sn & 1;
-    if (!WAVE1) {
-      if (lane == 63) { int* e = s_edge[par][wv][0]; e[0] = Mh[C - 1][cl][1]; e[1] = Mh[C - 1][cl][4]; e[2] = I1h[C - 1][E1 - 1]; e[3] = I2h[C - 1]; }
-      if (lane == 0)  { int* e = s_edge[par][wv][1]; e[0] = Mh[0][cl][1];     e[1] = Mh[0][cl][4];     e[2] = D1h[0][E1 - 1];     e[3] = D2h[0]; }
-    }
+    b2_publish_edges<WAVE1>(s_edge, par, wv, lane, cl, Mh, I1h, D1h, I2h, D2h);
     lds_barrier();  // the previous step's end checks and row range are visible; the edges of this one are published (the rows of pre / bt are read after the loop's end)
     done = J.endsfree ? (s_endk != INT32_MAX) : (s_done != 0);
     if (done) break;
     if (sn > J.smax) { status = WFM_DEV_OVERFLOW; break; }
     s = sn;
-    // The row's range as the ring kernel keeps it -- the union of its sources' ranges, the I / D sources reaching one diagonal
-    // further -- in closed form: row s - 1 is among the sources (e2 = 1) and holds every older row, so a row is its predecessor
-    // and one diagonal more on either side, clipped to the problem and to the job's columns
-    const int lo = max(lo0 - s, max(-pl, kmin)), hi = min(hi0 + s, min(tl, kmax));
+    int lo, hi;
+    base_row(R, s, lo, hi);
     const bool valid = lo <= hi;
     if (valid) cells += (uint64_t)(hi - lo + 1);
     // A wave whose diagonals lie outside the row (and one column around it) has nothing to do: rows only grow (a row holds its
@@ -1277,50 +1289,11 @@ __global__ __launch_bounds__(NTMAX) void wfa_base2_kernel(const uint32_t* __rest
     // it would publish for its neighbours is what it published before.  The budget of a leaf is its exact score and the rows
     // are laid out for the budget: on average a third of the waves of a launch have cells at a given step.
     if (!valid || kw_hi < lo - 1 || kw_lo > hi + 1) continue;
-    lM10 = from_prev_lane(Mh[C - 1][cl][1]); lM25 = from_prev_lane(Mh[C - 1][cl][4]);
-    lI1 = from_prev_lane(I1h[C - 1][E1 - 1]); lI2 = from_prev_lane(I2h[C - 1]);
-    rM10 = from_next_lane(Mh[0][cl][1]); rM25 = from_next_lane(Mh[0][cl][4]);
-    rD1 = from_next_lane(D1h[0][E1 - 1]); rD2 = from_next_lane(D2h[0]);
-    if (!WAVE1) {
-      if (lane == 0 && wv > 0) { const int* e = s_edge[par][wv - 1][0]; lM10 = e[0]; lM25 = e[1]; lI1 = e[2]; lI2 = e[3]; }
-      if (lane == 63 && wv + 1 < nw) { const int* e = s_edge[par][wv + 1][1]; rM10 = e[0]; rM25 = e[1]; rD1 = e[2]; rD2 = e[3]; }
-    }
-    int nM[C], nI1[C], nI2[C], nD1[C], nD2[C], preM[C];
+    int lM10, lM25, lI1, lI2, rM10, rM25, rD1, rD2;
+    b2_neighbours<WAVE1>(s_edge, par, wv, nw, lane, cl, Mh, I1h, D1h, I2h, D2h, lM10, lM25, lI1, lI2, rM10, rM25, rD1, rD2);
+    int nM[C], nI1[C], nI2[C], nD1[C], nD2[C];
     unsigned btb[C];
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-      const int k = k0 + c;
-      const int a10 = c == 0 ? lM10 : Mh[c - 1][cl][1], b10 = c == C - 1 ? rM10 : Mh[c + 1][cl][1];
-      const int a25 = c == 0 ? lM25 : Mh[c - 1][cl][4], b25 = c == C - 1 ? rM25 : Mh[c + 1][cl][4];
-      const int i1 = c == 0 ? lI1 : I1h[c - 1][E1 - 1], d1 = c == C - 1 ? rD1 : D1h[c + 1][E1 - 1];
-      const int i2 = c == 0 ? lI2 : I2h[c - 1], d2 = c == C - 1 ? rD2 : D2h[c + 1];
-      const int mx = Mh[c][cl][0];
-      unsigned bits = 0;
-      // ext wins ties (WFA2-lib: ext type > open type; piggyback: ext >= open)
-      if (i1 >= a10) bits |= BT_I1_EXT;
-      if (i2 >= a25) bits |= BT_I2_EXT;
-      if (d1 >= b10) bits |= BT_D1_EXT;
-      if (d2 >= b25) bits |= BT_D2_EXT;
-      const unsigned hm = hmaxu[c];
-      int ins1 = max(a10, i1) + 1, ins2 = max(a25, i2) + 1, del1 = max(b10, d1), del2 = max(b25, d2), mis = mx + 1;
-      ins1 = (unsigned)ins1 <= hm ? ins1 : WF_NULL;
-      ins2 = (unsigned)ins2 <= hm ? ins2 : WF_NULL;
-      del1 = (unsigned)del1 <= hm ? del1 : WF_NULL;
-      del2 = (unsigned)del2 <= hm ? del2 : WF_NULL;
-      mis = (unsigned)mis <= hm ? mis : WF_NULL;
-      // M source priority on equal offsets: mismatch > D2 > D1 > I2 > I1
-      int m = ins1; unsigned src = C_I1;
-      if (ins2 >= m) { m = ins2; src = C_I2; }
-      if (del1 >= m) { m = del1; src = C_D1; }
-      if (del2 >= m) { m = del2; src = C_D2; }
-      if (mis >= m)  { m = mis;  src = C_M; }
-      const bool on = valid && k >= lo && k <= hi;  // (outside the row's range the ring kernel computes nothing: nothing is kept there)
-      nI1[c] = on ? ins1 : WF_NULL; nI2[c] = on ? ins2 : WF_NULL; nD1[c] = on ? del1 : WF_NULL; nD2[c] = on ? del2 : WF_NULL;
-      nM[c] = (on && colok[c]) ? m : WF_NULL;
-      preM[c] = nM[c];
-      btb[c] = bits | src;
-      (void)k;
-    }
+    b2_cells(Mh, I1h, D1h, I2h, D2h, cl, lM10, lM25, lI1, lI2, rM10, rM25, rD1, rD2, hmaxu, colok, k0, lo, hi, nM, nI1, nI2, nD1, nD2, btb);
     int ext[C], maxn[C];
     unsigned oP[C], oT[C];
 #pragma unroll
@@ -1339,11 +1312,10 @@ __global__ __launch_bounds__(NTMAX) void wfa_base2_kernel(const uint32_t* __rest
 #pragma unroll
     for (int c = 0; c < C; ++c) {
       const int k = k0 + c;
-      const bool on = valid && k >= lo && k <= hi;
-      if (on) {
-        pre[k] = preM[c];
-        bt[k] = (uint8_t)btb[c];
+      if (k >= lo && k <= hi) {
         int m = nM[c];
+        pre[k] = m;  // (the offset before its extension)
+        bt[k] = (uint8_t)btb[c];
         if (m >= 0) m += ext[c];
         nM[c] = m;
         reached |= !J.endsfree || m >= (int)hmaxu[c];
@@ -1353,20 +1325,10 @@ __global__ __launch_bounds__(NTMAX) void wfa_base2_kernel(const uint32_t* __rest
 #pragma unroll
       for (int c = 0; c < C; ++c) {
         const int k = k0 + c;
-        if (valid && k >= lo && k <= hi) end_checks(c, k, nM[c], nI1[c], nI2[c], nD1[c], nD2[c]);
+        if (k >= lo && k <= hi) b2_end_checks(J, &s_done, &s_endk, k, nM[c], nI1[c], nI2[c], nD1[c], nD2[c]);
       }
     }
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-      mcur[c] = nM[c];
-#pragma unroll
-      for (int e = DEP - 1; e > 0; --e) Mh[c][cl][e] = Mh[c][cl][e - 1];
-      Mh[c][cl][0] = nM[c];
-#pragma unroll
-      for (int d = E1 - 1; d > 0; --d) { I1h[c][d] = I1h[c][d - 1]; D1h[c][d] = D1h[c][d - 1]; }
-      I1h[c][0] = nI1[c]; D1h[c][0] = nD1[c];
-      I2h[c] = nI2[c]; D2h[c] = nD2[c];
-    }
+    b2_shift(Mh, I1h, D1h, I2h, D2h, mcur, cl, nM, nI1, nI2, nD1, nD2);
   }
   }
   // ---- the ends-free walk starts from the offset its end cell holds
@@ -1380,7 +1342,7 @@ __global__ __launch_bounds__(NTMAX) void wfa_base2_kernel(const uint32_t* __rest
   if (tid < 64) {
     const long long t_fwd = wall_clock64();
     BaseResult r; r.status = status; r.score = s; r.nruns = 0; r.cells = cells; r.pad_ = 0;
-    if (status == 0 && !J.score_only) r.nruns = base2_walk(J, pre_base, bt_base, rle, s, J.endsfree ? s_endk : k_end, J.endsfree ? s_endoff : tl, lane);  // (a score-only job ends here: s is its score)
+    if (status == 0 && !J.score_only) r.nruns = base_walk(J, B2_PEN, pre_base, bt_base, rle, s, J.endsfree ? s_endk : k_end, J.endsfree ? s_endoff : tl, lane);  // (a score-only job ends here: s is its score)
     // diagnostics (WFM_DEBUG=2): microseconds of the forward pass and of the walk back, 16 bits each
     r.pad_ = (int32_t)((min((t_fwd - t_begin) / 100, 65535ll) << 16) | min((wall_clock64() - t_fwd) / 100, 65535ll));
     if (lane == 0) results[blockIdx.x] = r;
@@ -1390,14 +1352,17 @@ __global__ __launch_bounds__(NTMAX) void wfa_base2_kernel(const uint32_t* __rest
 // ---------------------------------------------------------------------------
 // Base jobs wider than a workgroup's registers: wfa_base2_kernel's step on tiles (Base2TJob in wfa_device.h)
 // ---------------------------------------------------------------------------
-// One workgroup = one tile of one job for one block of T scores (T a multiple of 5: a block begins with class 1).  Everything a cell computes and
-// everything that is written about it is wfa_base2_kernel's -- same recurrences, same decision bits, same range of a row, same end tests -- but rows of
-// pre / bt and the end tests are the core's alone: the halo's cells are right only as far from the tile's edge as the block is old.
+// One workgroup = one tile of one job for one block of T scores (T a multiple of 5: a block begins with class 1).  What a cell computes is shared code
+// with wfa_base2_kernel, not a copy of it: row 0, the mailbox, the recurrences with their decision bits, the end tests and the delay-line shift are the
+// b2_ functions above, the range of a row is base_row (wfa_base.h).  What this kernel adds is one predicate: rows of pre / bt and the end tests are the
+// core's alone (`incore`, the `keep` of b2_row0), since the halo's cells are right only as far from the tile's edge as the block is old.  The
+// extension's offsets, the stores of pre / bt and the pass over the cells that reached their diagonal's end are still written in both kernels: as one
+// function they cost wfa_base2_kernel<1024> its registers (profiles/base_step_shared.md).
 template <int NTMAX>
 __global__ __launch_bounds__(NTMAX) void wfa_base2t_kernel(const uint32_t* __restrict__ pk, int32_t* __restrict__ arena32, uint8_t* __restrict__ arena8,
                                                          const Base2TJob* __restrict__ jobs, const Base2TTask* __restrict__ tasks,
                                                          unsigned long long* __restrict__ tile_key, int32_t* __restrict__ tile_off, int T) {
-  constexpr int C = 2, NCL = 5, DEP = 6, E1 = 2, H = 26;
+  constexpr int C = B2_C, NCL = B2_NCL, DEP = B2_DEP, E1 = B2_E1;
   constexpr int NW = NTMAX / 64;
   const Base2TTask tk = tasks[blockIdx.x];
   const Base2TJob JT = jobs[tk.job];
@@ -1416,16 +1381,8 @@ __global__ __launch_bounds__(NTMAX) void wfa_base2t_kernel(const uint32_t* __res
   const int k_end = tl - pl;
   const int s0 = JT.s0;
   const int core_lo = kmin + tk.tile * JT.core, core_hi = min(kmax, core_lo + JT.core - 1);
-  const int64_t oriP = J.p_off & ~(int64_t)15, oriT = J.t_off & ~(int64_t)15;
-  const int dP = (int)(J.p_off - oriP), dT = (int)(J.t_off - oriT);
-  PkSrc SRC;
-  SRC.lP = (lds_words)s_winP; SRC.lT = (lds_words)s_winT;
-  SRC.gP = (glb_words)pk + (oriP >> 4); SRC.gT = (glb_words)pk + (oriT >> 4);
-  {
-    const int nP = min(PK_WIN_DW + PK_SLACK_DW, (pl + dP + 15) / 16 + 8), nT = min(PK_WIN_DW + PK_SLACK_DW, (tl + dT + 15) / 16 + 8);
-    for (int i = tid; i < nP; i += NTMAX) s_winP[i] = SRC.gP[i];
-    for (int i = tid; i < nT; i += NTMAX) s_winT[i] = SRC.gT[i];
-  }
+  int dP, dT;
+  const PkSrc SRC = b2_load_windows(J, pk, s_winP, s_winT, tid, NTMAX, dP, dT);
   if (tid == 0) { s_done = 0; s_endk = INT32_MAX; s_endoff = 0; }
   for (int i = tid; i < (int)(sizeof(s_edge) / sizeof(int)); i += NTMAX) ((int*)s_edge)[i] = WF_NULL;
   __syncthreads();
@@ -1454,70 +1411,17 @@ __global__ __launch_bounds__(NTMAX) void wfa_base2t_kernel(const uint32_t* __res
     wlim[c] = PK_WIN_BASES - 1 - max(cP[c], dT);
     mcur[c] = WF_NULL;
   }
-  auto end_checks = [&](int k, int m_ext, int ins1, int ins2, int del1, int del2) {
-    if (J.endsfree) {
-      if (m_ext >= 0) {
-        const int h = m_ext, v = m_ext - k;
-        if ((h >= tl && pl - v <= J.pef) || (v >= pl && tl - h <= J.tef)) atomicMin(&s_endk, k);
-      }
-    } else if (k == k_end) {
-      const int ev = J.comp_end == C_M ? m_ext : (J.comp_end == C_I1 ? ins1 : (J.comp_end == C_I2 ? ins2 : (J.comp_end == C_D1 ? del1 : del2)));
-      if (ev >= tl) s_done = 1;
-    }
-  };
-  int lo0, hi0;
-  if (J.endsfree) { lo0 = max(-J.pbf, kmin); hi0 = min(J.tbf, kmax); }
-  else { lo0 = 0; hi0 = 0; }
-  if (s0 == 0) {
-    // ---- row 0 (no cell of it has a neighbour to wait for: the halo's are right)
-    int m0[C], ext[C], maxn[C];
-    unsigned oP[C], oT[C];
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-      const int k = k0 + c;
-      const bool on = k >= lo0 && k <= hi0;
-      int m = WF_NULL;
-      if (on) {
-        if (J.endsfree) m = k > 0 ? k : 0;
-        else {
-          if (J.comp_begin == C_M) m = 0;
-          I1h[c][0] = J.comp_begin == C_I1 ? 0 : WF_NULL;
-          I2h[c] = J.comp_begin == C_I2 ? 0 : WF_NULL;
-          D1h[c][0] = J.comp_begin == C_D1 ? 0 : WF_NULL;
-          D2h[c] = J.comp_begin == C_D2 ? 0 : WF_NULL;
-        }
-      }
-      m0[c] = m;
-      oP[c] = (unsigned)(m + cP[c]); oT[c] = (unsigned)(m + dT);
-      maxn[c] = m >= 0 ? min(pl - (m - k), tl - m) : 0;
-    }
-    pk_extend2(SRC, m0, oP, oT, maxn, ext);
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-      const int k = k0 + c;
-      if (k < lo0 || k > hi0) continue;
-      if (incore[c]) { pre_base[k] = m0[c]; bt_base[k] = 0; }
-      int m = m0[c];
-      if (m >= 0) m += ext[c];
-      if (incore[c]) {
-        if (J.endsfree) end_checks(k, m, WF_NULL, WF_NULL, WF_NULL, WF_NULL);
-        else if (k == k_end && J.comp_end == C_M && m >= tl) s_done = 1;
-      }
-      Mh[c][0][0] = m;
-      mcur[c] = m;
-    }
-  } else {
-    // ---- the snapshot of the block before: rows 0 .. 25 = M of scores s0, s0 - 1, ..; 26 / 27 = I1 of s0 / s0 - 1; 28 / 29 = D1; 30 = I2; 31 = D2.
-    // Every column of the job lies in one tile's core and was written there, NULL where the row had no cell
+  const BaseRows R = base_rows(J);
+  const int lo0 = R.lo0, hi0 = R.hi0;
+  if (s0 == 0) b2_row0(J, SRC, dT, lo0, hi0, k0, cP, incore, pre_base, bt_base, &s_done, &s_endk, Mh, I1h, D1h, I2h, D2h, mcur);
+  else {
+    // ---- the snapshot of the block before (b2_snap_reg).  Every column of the job lies in one tile's core and was written there, NULL where the row had no cell
 #pragma unroll
     for (int c = 0; c < C; ++c) {
       const int k = k0 + c;
       if (k < kmin || k > kmax) continue;
 #pragma unroll
-      for (int d = 0; d < H; ++d) Mh[c][(NCL - d % NCL) % NCL][d / NCL] = snap_in[(int64_t)d * width + k];
-#pragma unroll
-      for (int d = 0; d < E1; ++d) { I1h[c][d] = snap_in[(int64_t)(26 + d) * width + k]; D1h[c][d] = snap_in[(int64_t)(28 + d) * width + k]; }
-      I2h[c] = snap_in[(int64_t)30 * width + k]; D2h[c] = snap_in[(int64_t)31 * width + k];
+      for (int row = 0; row < B2T_ROWS; ++row) b2_snap_reg(Mh[c], I1h[c], D1h[c], I2h[c], D2h[c], row) = snap_in[(int64_t)row * width + k];
       mcur[c] = Mh[c][0][0];
     }
   }
@@ -1529,56 +1433,21 @@ __global__ __launch_bounds__(NTMAX) void wfa_base2t_kernel(const uint32_t* __res
   for (int jj = 1; jj <= NCL; ++jj) {
     const int cl = jj % NCL;
     const int sn = tb + jj;
-    int lM10, lM25, lI1, lI2, rM10, rM25, rD1, rD2;
     const int par = sn & 1;
-    if (lane == 63) { int* e = s_edge[par][wv][0]; e[0] = Mh[C - 1][cl][1]; e[1] = Mh[C - 1][cl][4]; e[2] = I1h[C - 1][E1 - 1]; e[3] = I2h[C - 1]; }
-    if (lane == 0)  { int* e = s_edge[par][wv][1]; e[0] = Mh[0][cl][1];     e[1] = Mh[0][cl][4];     e[2] = D1h[0][E1 - 1];     e[3] = D2h[0]; }
+    b2_publish_edges<false>(s_edge, par, wv, lane, cl, Mh, I1h, D1h, I2h, D2h);
     lds_barrier();
     done = J.endsfree ? (s_endk != INT32_MAX) : (s_done != 0);
     if (done || sn > s_stop) break;
     s = sn;
-    const int lo = max(lo0 - s, max(-pl, kmin)), hi = min(hi0 + s, min(tl, kmax));
+    int lo, hi;
+    base_row(R, s, lo, hi);
     const bool valid = lo <= hi;
     if (!valid || kw_hi < lo - 1 || kw_lo > hi + 1) continue;
-    lM10 = from_prev_lane(Mh[C - 1][cl][1]); lM25 = from_prev_lane(Mh[C - 1][cl][4]);
-    lI1 = from_prev_lane(I1h[C - 1][E1 - 1]); lI2 = from_prev_lane(I2h[C - 1]);
-    rM10 = from_next_lane(Mh[0][cl][1]); rM25 = from_next_lane(Mh[0][cl][4]);
-    rD1 = from_next_lane(D1h[0][E1 - 1]); rD2 = from_next_lane(D2h[0]);
-    if (lane == 0 && wv > 0) { const int* e = s_edge[par][wv - 1][0]; lM10 = e[0]; lM25 = e[1]; lI1 = e[2]; lI2 = e[3]; }
-    if (lane == 63 && wv + 1 < NW) { const int* e = s_edge[par][wv + 1][1]; rM10 = e[0]; rM25 = e[1]; rD1 = e[2]; rD2 = e[3]; }
-    int nM[C], nI1[C], nI2[C], nD1[C], nD2[C], preM[C];
+    int lM10, lM25, lI1, lI2, rM10, rM25, rD1, rD2;
+    b2_neighbours<false>(s_edge, par, wv, NW, lane, cl, Mh, I1h, D1h, I2h, D2h, lM10, lM25, lI1, lI2, rM10, rM25, rD1, rD2);
+    int nM[C], nI1[C], nI2[C], nD1[C], nD2[C];
     unsigned btb[C];
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-      const int k = k0 + c;
-      const int a10 = c == 0 ? lM10 : Mh[c - 1][cl][1], b10 = c == C - 1 ? rM10 : Mh[c + 1][cl][1];
-      const int a25 = c == 0 ? lM25 : Mh[c - 1][cl][4], b25 = c == C - 1 ? rM25 : Mh[c + 1][cl][4];
-      const int i1 = c == 0 ? lI1 : I1h[c - 1][E1 - 1], d1 = c == C - 1 ? rD1 : D1h[c + 1][E1 - 1];
-      const int i2 = c == 0 ? lI2 : I2h[c - 1], d2 = c == C - 1 ? rD2 : D2h[c + 1];
-      const int mx = Mh[c][cl][0];
-      unsigned bits = 0;
-      if (i1 >= a10) bits |= BT_I1_EXT;
-      if (i2 >= a25) bits |= BT_I2_EXT;
-      if (d1 >= b10) bits |= BT_D1_EXT;
-      if (d2 >= b25) bits |= BT_D2_EXT;
-      const unsigned hm = hmaxu[c];
-      int ins1 = max(a10, i1) + 1, ins2 = max(a25, i2) + 1, del1 = max(b10, d1), del2 = max(b25, d2), mis = mx + 1;
-      ins1 = (unsigned)ins1 <= hm ? ins1 : WF_NULL;
-      ins2 = (unsigned)ins2 <= hm ? ins2 : WF_NULL;
-      del1 = (unsigned)del1 <= hm ? del1 : WF_NULL;
-      del2 = (unsigned)del2 <= hm ? del2 : WF_NULL;
-      mis = (unsigned)mis <= hm ? mis : WF_NULL;
-      int m = ins1; unsigned src = C_I1;
-      if (ins2 >= m) { m = ins2; src = C_I2; }
-      if (del1 >= m) { m = del1; src = C_D1; }
-      if (del2 >= m) { m = del2; src = C_D2; }
-      if (mis >= m)  { m = mis;  src = C_M; }
-      const bool on = k >= lo && k <= hi;
-      nI1[c] = on ? ins1 : WF_NULL; nI2[c] = on ? ins2 : WF_NULL; nD1[c] = on ? del1 : WF_NULL; nD2[c] = on ? del2 : WF_NULL;
-      nM[c] = (on && colok[c]) ? m : WF_NULL;
-      preM[c] = nM[c];
-      btb[c] = bits | src;
-    }
+    b2_cells(Mh, I1h, D1h, I2h, D2h, cl, lM10, lM25, lI1, lI2, rM10, rM25, rD1, rD2, hmaxu, colok, k0, lo, hi, nM, nI1, nI2, nD1, nD2, btb);
     int ext[C], maxn[C];
     unsigned oP[C], oT[C];
 #pragma unroll
@@ -1595,13 +1464,13 @@ __global__ __launch_bounds__(NTMAX) void wfa_base2t_kernel(const uint32_t* __res
 #pragma unroll
     for (int c = 0; c < C; ++c) {
       const int k = k0 + c;
-      const bool on = k >= lo && k <= hi;
-      if (on) {
-        int m = nM[c];
+      if (k >= lo && k <= hi) {
+        const int m0 = nM[c];  // (the offset before its extension)
+        int m = m0;
         if (m >= 0) m += ext[c];
         nM[c] = m;
         if (incore[c]) {
-          pre[k] = preM[c];
+          pre[k] = m0;
           bt[k] = (uint8_t)btb[c];
           reached |= !J.endsfree || m >= (int)hmaxu[c];
         }
@@ -1611,20 +1480,10 @@ __global__ __launch_bounds__(NTMAX) void wfa_base2t_kernel(const uint32_t* __res
 #pragma unroll
       for (int c = 0; c < C; ++c) {
         const int k = k0 + c;
-        if (k >= lo && k <= hi && incore[c]) end_checks(k, nM[c], nI1[c], nI2[c], nD1[c], nD2[c]);
+        if (k >= lo && k <= hi && incore[c]) b2_end_checks(J, &s_done, &s_endk, k, nM[c], nI1[c], nI2[c], nD1[c], nD2[c]);
       }
     }
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-      mcur[c] = nM[c];
-#pragma unroll
-      for (int e = DEP - 1; e > 0; --e) Mh[c][cl][e] = Mh[c][cl][e - 1];
-      Mh[c][cl][0] = nM[c];
-#pragma unroll
-      for (int d = E1 - 1; d > 0; --d) { I1h[c][d] = I1h[c][d - 1]; D1h[c][d] = D1h[c][d - 1]; }
-      I1h[c][0] = nI1[c]; D1h[c][0] = nD1[c];
-      I2h[c] = nI2[c]; D2h[c] = nD2[c];
-    }
+    b2_shift(Mh, I1h, D1h, I2h, D2h, mcur, cl, nM, nI1, nI2, nD1, nD2);
   }
   }
   __syncthreads();  // (the end tests of the block's last step)
@@ -1650,10 +1509,7 @@ __global__ __launch_bounds__(NTMAX) void wfa_base2t_kernel(const uint32_t* __res
     const int k = k0 + c;
     if (!incore[c]) continue;
 #pragma unroll
-    for (int d = 0; d < H; ++d) snap_out[(int64_t)d * width + k] = Mh[c][(NCL - d % NCL) % NCL][d / NCL];
-#pragma unroll
-    for (int d = 0; d < E1; ++d) { snap_out[(int64_t)(26 + d) * width + k] = I1h[c][d]; snap_out[(int64_t)(28 + d) * width + k] = D1h[c][d]; }
-    snap_out[(int64_t)30 * width + k] = I2h[c]; snap_out[(int64_t)31 * width + k] = D2h[c];
+    for (int row = 0; row < B2T_ROWS; ++row) snap_out[(int64_t)row * width + k] = b2_snap_reg(Mh[c], I1h[c], D1h[c], I2h[c], D2h[c], row);
   }
 }
 
@@ -1685,21 +1541,21 @@ __global__ __launch_bounds__(64) void wfa_base2t_finish_kernel(const int32_t* __
   const Base2TJob JT = jobs[blockIdx.x];
   const BaseJob& J = JT.b;
   const int lane = threadIdx.x;
-  const int kmin = J.kmin, kmax = J.kmin + J.width - 1;
+  const int kmin = J.kmin;
   BaseResult r; r.status = JT.done == 1 ? 0 : WFM_DEV_OVERFLOW; r.score = JT.end_s; r.nruns = 0; r.pad_ = 0;
   // the cells of the rows 0 .. end_s as wfa_base2_kernel counts them
-  int lo0, hi0;
-  if (J.endsfree) { lo0 = max(-J.pbf, kmin); hi0 = min(J.tbf, kmax); }
-  else { lo0 = 0; hi0 = 0; }
+  const BaseRows R = base_rows(J);
+  const int lo0 = R.lo0, hi0 = R.hi0;
   unsigned long long cells = 0;
   for (int s = 1 + lane; s <= JT.end_s; s += 64) {
-    const int lo = max(lo0 - s, max(-J.pl, kmin)), hi = min(hi0 + s, min(J.tl, kmax));
+    int lo, hi;
+    base_row(R, s, lo, hi);
     if (lo <= hi) cells += (unsigned long long)(hi - lo + 1);
   }
   for (int d = 32; d > 0; d >>= 1) cells += __shfl_down(cells, d, 64);
   cells = __shfl(cells, 0, 64) + (unsigned long long)(hi0 - lo0 + 1);
   r.cells = cells;
-  if (JT.done == 1 && !J.score_only) r.nruns = base2_walk(J, arena32 + J.pre_off - kmin, arena8 + J.bt_off - kmin, rle, JT.end_s, JT.end_k, JT.end_off, lane);
+  if (JT.done == 1 && !J.score_only) r.nruns = base_walk(J, B2_PEN, arena32 + J.pre_off - kmin, arena8 + J.bt_off - kmin, rle, JT.end_s, JT.end_k, JT.end_off, lane);
   if (lane == 0) results[blockIdx.x] = r;
 }
 
