@@ -469,3 +469,98 @@ def test_device_winnower_model_on_arbitrary_sequences():
         assert got.tobytes() == one.tobytes()
 
     check()
+
+
+# ---- the sketch pipeline (minmers.cpp, SketchRun): its scheduling alone, and every route of one call ----
+
+def test_sketch_queue_check_program(tmp_path):
+    """scripts/micro/sketch_queue_check.cpp: the pipeline's hand-offs, slot ring, window, in-order delivery, first-error
+    record and joiner with fake stages (no device): delivery in order, slots and window back, threads joined, also with a
+    failing stage and with an exception in the feeder.  A hang is the failure it exists to show: one minute."""
+    import shutil
+    import subprocess
+    gxx = shutil.which("g++")
+    if not gxx:
+        pytest.skip("no g++")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "sketch_queue_check")
+    subprocess.run([gxx, "-std=c++17", "-O2", "-pthread", os.path.join(root, "scripts", "micro", "sketch_queue_check.cpp"), "-o", exe], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and "sketch_queue_check: ok" in r.stdout, (r.stdout[-1000:], r.stderr[-1000:])
+
+
+def _mixed_routes():
+    """one call, every route (k, w, s = 15, 256, 12; WFM_WINNOW_CHUNK=16384, WFM_WINNOW_DEV_MIN=50000): the device; no record;
+    the host's streamed chunks; kept from the device by an unnoticed N; dense through the ring; thinned, one chunk; the device"""
+    g = synth.random_dna(0x5e7, 70000)
+    return [synth.random_dna(0x5e1, 60000), synth.random_dna(0x5e2, 10), synth.random_dna(0x5e3, 40000),
+            b"ACGNTACGTTGCA" + synth.random_dna(0x5e4, 60000), synth.random_dna(0x5e5, 200), synth.random_dna(0x5e6, 300),
+            g[:33500] + b"N" * 3000 + g[36500:]]
+
+
+def _mixed_call(threads, **switches):
+    """the mixed list through wfm_add_minmers_multi in a fresh process (stderr is read), held against one wfm_add_minmers call
+    per sequence -- the dense single stream -- and, where it was built, the reference's own addMinmers; -> what the multi call
+    wrote to stderr"""
+    import subprocess
+    import sys
+    code = (
+        "import sys; sys.path.insert(0, '.'); sys.path.insert(0, 'tests')\n"
+        "from wfmash_amd import capi\n"
+        "from oracle import pymap\n"
+        "from test_minmers import _mixed_routes\n"
+        "h = capi.Handle(0)\n"
+        "seqs = _mixed_routes()\n"
+        "single = [h.add_minmers(sq, 15, 256, 12, i) for i, sq in enumerate(seqs)]\n"
+        "print('-- the multi call --', file=sys.stderr, flush=True)\n"
+        f"multi = h.add_minmers_multi(seqs, 15, 256, 12, threads={threads})\n"
+        "assert [len(a) for a in multi] == [len(b) for b in single], ([len(a) for a in multi], [len(b) for b in single])\n"
+        "assert len(multi[1]) == 0 and all(len(multi[i]) > 0 for i in (0, 2, 3, 5, 6))  # (4 is shorter than a window)\n"
+        "bad = [i for i, (a, b) in enumerate(zip(multi, single)) if a.tobytes() != b.tobytes()]\n"
+        "assert not bad, bad\n"
+        "if pymap.have_ref():\n"
+        "    ref = [pymap.ref_add_minmers(sq, 15, 256, 12, i) for i, sq in enumerate(seqs)]\n"
+        "    bad = [i for i, (a, b) in enumerate(zip(multi, ref)) if a.tobytes() != b.tobytes()]\n"
+        "    assert not bad, ('reference', bad)\n"
+        "print('same', sum(len(a) for a in multi))\n")
+    env = {k: v for k, v in os.environ.items() if not k.startswith(("WFM_WINNOW", "WFM_PREFILTER")) and k != "WFM_FINISH_DEVICE"}
+    env.update(WFM_WINNOW_CHUNK="16384", WFM_WINNOW_DEV_MIN="50000", WFM_DEBUG="1")
+    env.update(switches)
+    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    assert r.returncode == 0 and "same" in r.stdout, (r.stdout[-1000:], r.stderr[-3000:])
+    return r.stderr.split("-- the multi call --")[1]  # (the single calls write their own [wfm] lines before it)
+
+
+def _device_line(stderr):
+    lines = [l for l in stderr.splitlines() if "winnowing on the device" in l]
+    assert len(lines) == 1, stderr[-3000:]
+    nseq = int(lines[0].split("winnowing on the device:")[1].split("sequences")[0])
+    back = int(lines[0].split(";")[1].split("handed back")[0])
+    return lines[0], nseq, back
+
+
+@pytest.mark.gpu
+def test_add_minmers_multi_mixed_routes_in_one_call():
+    """device, no record, streamed host chunks, unnoticed N, dense through the ring, thinned single chunk, device again: the
+    records and counts of every sequence are the single call's; two sequences went to the device, none came back"""
+    err = _mixed_call(8)
+    line, nseq, back = _device_line(err)
+    assert nseq == 2 and back == 0 and "closing sort on the device" in line, line
+    assert sum("streamed through the pinned ring" in l for l in err.splitlines()) == 1, err[-3000:]
+
+
+@pytest.mark.gpu
+def test_add_minmers_multi_host_closing_sort_of_device_records():
+    """WFM_FINISH_DEVICE=0: the device winnows, a host worker runs the closing cut / sort / de-duplication"""
+    line, nseq, back = _device_line(_mixed_call(8, WFM_FINISH_DEVICE="0"))
+    assert nseq == 2 and back == 0 and "closing sort on the host" in line, line
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("threads,chunk", [(1, "16384"), (8, "1000")])
+def test_add_minmers_multi_unstreamed_form(threads, chunk):
+    """one worker, or a chunk length under 64 w: whole sequences through ordinary memory, nothing thinned, nothing for the device"""
+    err = _mixed_call(threads, WFM_WINNOW_CHUNK=chunk)
+    lines = [l for l in err.splitlines() if "add_minmers_multi:" in l]
+    assert len(lines) == 1 and "whole sequences" in lines[0], err[-3000:]
+    assert "winnowing on the device" not in err, err[-3000:]

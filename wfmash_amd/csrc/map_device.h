@@ -85,7 +85,8 @@ void map_hashed_free(MapHashedSeq* s);
 int map_hashed_fetch(const MapHashedSeq* s, int64_t from, int64_t to, int64_t base_from, int64_t base_to, uint64_t* hash, int8_t* strand,
                      char* norm);
 
-// Pinned staging ring for streaming hashed slices to host workers (minmers.cpp): a slot receives
+// Pinned staging ring for streaming hashed slices to host workers (minmers.cpp: SketchRun::streamer_loop fills a slot,
+// SketchRun::take_slot empties it): a slot receives
 //   uint64 hash[to-from] | int8 strand[to-from] | char norm[base_to-base_from]
 // by asynchronous copies on the ring's own stream; map_stage_wait blocks the calling thread until the
 // slot's copies have landed.  The ring is kept with the handle and reused by later calls.
@@ -131,7 +132,7 @@ void map_thin_work_free(MapThinWork* wk);
 // Device blocks that come and go once per sequence (the kept k-mers, a sequence's records) are taken from and returned to
 // a small pool: hipMalloc / hipFree wait for the whole device, and with the winnowing on a thread and stream of its own
 // every such call would make the two threads wait for each other's kernels.  map_dev_pool_trim frees what is pooled
-// (add_minmers_core calls it before it returns: the memory belongs to whoever runs next).
+// (add_minmers_core's SketchWork calls it when the call's work buffers go: the memory belongs to whoever runs next).
 void* map_dev_pool_get(int device, size_t bytes);
 void map_dev_pool_put(int device, void* p);
 void map_dev_pool_trim();
@@ -152,7 +153,8 @@ struct MapWinnowWork {  // grow-only device buffers, reused from sequence to seq
 void map_winnow_work_free(MapWinnowWork* wk);
 struct MapWinnowInfo { int chunks = 0, bad_chunks = 0, rerun_chunks = 0, replays = 0, resolve_rounds = 0; uint32_t why = 0; int64_t records = 0; };
 // WFM_OK: *d_out (inside wk, valid until the next call) holds *n_out raw records in emission order, interval starts
-// resolved; 1: this sequence is not for the device (info->why), the caller winnows it on the host; < 0: error
+// resolved; 1: this sequence is not for the device (info->why), the caller winnows it on the host (minmers.cpp:
+// SketchRun::route_device_outcome passes it to the streamer); < 0: error
 int map_winnow_sparse_device(wfm_handle_t* h, const MapSparseSeq* sp, int64_t len, int k, int w, int s, int32_t seq_id, int64_t chunk_len,
                              MapWinnowWork* wk, wfm_minmer_t** d_out, int64_t* n_out, MapWinnowInfo* info, hipStream_t stream = nullptr);
 // The closing steps of addMinmers on the device (map_finish.hip): pieces of at most w windows, strand signs, std::sort's

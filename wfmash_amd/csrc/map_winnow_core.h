@@ -5,7 +5,8 @@
 // wave: every lane takes the same branches, only the primitives spread work over the lanes.
 //
 // What is replayed is host/minmers.cpp's Winnower::advance_sparse with its leave / arrive / maintain steps -- see there
-// for why the thinned stream gives the full stream's records.  Two things are put differently, neither observable:
+// for why the thinned stream gives the full stream's records (SketchRun::winnow_on_device, also there, is the caller of the
+// kernel).  Two things are put differently, neither observable:
 //   * the pool is the SET of window k-mers outside the sketch, kept in (hash, index) order; an entry whose k-mer has left
 //     the window is never looked at again (the reference pops such entries lazily when they surface; they are never
 //     chosen -- Winnower::maintain);

@@ -27,6 +27,12 @@
 // holds whole-sequence arrays.  A replay fetches its chunk again.  One stream per sequence
 // (wfm_add_minmers, threads == 1) stays dense: the tests hold the two forms against each other.
 //
+// The driver.  One call is a SketchRun: its switches are read once (SketchKnobs::read), its stages are member
+// functions (feed_one / route, streamer_loop, worker_loop, device_loop, deliver), and what passes between its threads --
+// three closable hand-offs, the ring's slot pool, the window of bases in flight, in-order delivery, the first error,
+// the order in which the threads end -- is sketch_queue.hpp, which names no device type and has a check program of its
+// own (scripts/micro/sketch_queue_check.cpp).
+//
 // State (names follow the roles, not the reference's identifiers):
 //   arrivals  every valid k-mer still inside (or lingering behind) the window, arrival order
 //   sketch    ordered map hash -> open interval + occurrences: the <= s smallest hashes
@@ -35,9 +41,9 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cassert>
 #include <chrono>
 #include <cmath>
-#include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -56,8 +62,11 @@
 #include "../csrc/dev_cache.h"
 #include "../csrc/map_device.h"
 #include "../csrc/wfa_handle.h"
+#include "sketch_queue.hpp"
 
 namespace {
+
+inline double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 inline uint64_t rotl64(uint64_t x, int r) { return (x << r) | (x >> (64 - r)); }
 inline uint64_t fmix64(uint64_t k) {
@@ -464,8 +473,7 @@ void finish_records(std::vector<wfm_minmer_t>& out, int w, int threads = 1) {
 // -- is laid out at its final size and filled by `threads` threads, each list into its own place.
 void finish_lists(const std::vector<const std::vector<wfm_minmer_t>*>& lists, int w, int threads, RecBuf& out, double* ms = nullptr) {
   const size_t nl = lists.size();
-  auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  const double t0 = now();
+  const double t0 = now_ms();
   std::vector<size_t> n_short(nl + 1, 0), n_piece(nl + 1, 0);
   auto spread = [&](auto&& fn) {
     std::atomic<size_t> next{0};
@@ -486,7 +494,7 @@ void finish_lists(const std::vector<const std::vector<wfm_minmer_t>*>& lists, in
   for (size_t j = 0; j < nl; ++j) { n_short[j + 1] += n_short[j]; n_piece[j + 1] += n_piece[j]; }
   const size_t total_short = n_short[nl], total = total_short + n_piece[nl];
   out.allocate(total);
-  const double t1 = now();
+  const double t1 = now_ms();
   spread([&](size_t j) {
     wfm_minmer_t* a = out.p + n_short[j];
     wfm_minmer_t* b = out.p + total_short + n_piece[j];
@@ -502,11 +510,11 @@ void finish_lists(const std::vector<const std::vector<wfm_minmer_t>*>& lists, in
       }
     }
   });
-  const double t2 = now();
+  const double t2 = now_ms();
   sort_as_std(out.p, out.p + total, by_window, threads);
-  const double t3 = now();
+  const double t3 = now_ms();
   out.n = (size_t)(std::unique(out.p, out.p + total, [](const wfm_minmer_t& l, const wfm_minmer_t& r) { return l.wpos == r.wpos && l.hash == r.hash; }) - out.p);
-  if (ms) { ms[0] = t1 - t0; ms[1] = t2 - t1; ms[2] = t3 - t2; ms[3] = now() - t3; }
+  if (ms) { ms[0] = t1 - t0; ms[1] = t2 - t1; ms[2] = t3 - t2; ms[3] = now_ms() - t3; }
 }
 
 void normalise(char* p, int64_t n) {  // makeUpperCaseAndValidDNA (commonFunc.hpp:132-142)
@@ -527,6 +535,8 @@ void winnow(const char* seq, int64_t len, int k, int w, int s, int32_t seq_id, c
   finish_records(out, w);
 }
 
+const uint32_t kNoKmer = 0;  // where the positions of an empty thinned stream point: it is still a thinned one
+
 // ---- one sequence cut into speculative chunks ----
 struct SeqJob {
   int64_t idx = 0;           // position in the caller's list
@@ -544,8 +554,7 @@ struct SeqJob {
   std::atomic<int> pending{0};
   int replays = 0;
   int fetch_rc = WFM_OK;
-  std::atomic<bool> stitched{false};   // result is final
-  int sort_threads = 1;                // for the closing sort of stitch()
+  int sort_threads = 1;               // for the closing sort of stitch()
   double ms_stitch = 0;
   double ms_parts[6] = {0, 0, 0, 0, 0, 0};  // compare, count, fill, sort, unique, release
   RecBuf result;
@@ -582,6 +591,27 @@ struct SeqJob {
     sp.strand = reinterpret_cast<const int8_t*>(buf + mc * 12);
     sp.n = mc;
     return sp;
+  }
+
+  void shape(int64_t at, int32_t id, int64_t n, int k_, int w_, int s_, int sorters) {
+    idx = at; seq_id = id; len = n; nk = n - k_ + 1; k = k_; w = w_; s = s_; sort_threads = sorters;
+  }
+  // test hooks: the sequence from host arrays, cut every chunk_len k-mers (0: one chunk)
+  void load_host(const char* seq, int64_t n, int k_, int w_, int s_, int32_t id, const uint64_t* h, const int8_t* st, int64_t chunk_len) {
+    shape(0, id, n, k_, w_, s_, 4);
+    norm.reset(new char[(size_t)len]);
+    memcpy(norm.get(), seq, (size_t)len);
+    normalise(norm.get(), len);
+    hash.reset(new uint64_t[(size_t)nk]);
+    strand.reset(new int8_t[(size_t)nk]);
+    memcpy(hash.get(), h, (size_t)nk * 8);
+    memcpy(strand.get(), st, (size_t)nk);
+    bounds.assign(1, 0);
+    if (chunk_len > 0)
+      for (int64_t b = chunk_len; b < nk; b += chunk_len) bounds.push_back(b);
+    bounds.push_back(nk);
+    chunk.resize(bounds.size() - 1);
+    started_from.resize(bounds.size() - 1);
   }
 
   Slice whole() const { return Slice{hash.get(), strand.get(), norm.get(), 0, 0}; }
@@ -639,8 +669,7 @@ struct SeqJob {
     if (!thinned) { v.d = refetch(bounds[j], bounds[j + 1], buf); return v; }
     const int64_t c0 = cidx[j], c1 = cidx[j + 1];
     if (!h_pos.empty() || c1 == c0) {
-      static const uint32_t none = 0;
-      v.sp.pos = h_pos.empty() ? &none : h_pos.data() + c0; v.sp.hash = h_hash.data() + c0; v.sp.strand = h_strand.data() + c0; v.sp.n = (size_t)(c1 - c0);
+      v.sp.pos = h_pos.empty() ? &kNoKmer : h_pos.data() + c0; v.sp.hash = h_hash.data() + c0; v.sp.strand = h_strand.data() + c0; v.sp.n = (size_t)(c1 - c0);
       return v;
     }
     buf.resize((size_t)(c1 - c0) * 13);
@@ -677,7 +706,7 @@ struct SeqJob {
       norm.reset(); hash.reset(); strand.reset();
       return;
     }
-    const auto tb = std::chrono::steady_clock::now();
+    const double tb = now_ms();
     for (size_t j = 1; j < chunk.size(); ++j) {
       const Winnower& prev = *chunk[j - 1];
       if (force == 1 || !(started_from[j] == prev.live_state(bounds[j]))) {
@@ -691,15 +720,15 @@ struct SeqJob {
       }
     }
     chunk.back()->flush_end();
-    const auto tc = std::chrono::steady_clock::now();
+    const double tc = now_ms();
     std::vector<const std::vector<wfm_minmer_t>*> lists;
     for (const auto& c : chunk) lists.push_back(&c->out);
     finish_lists(lists, w, sort_threads, result, ms_parts + 1);
-    const auto td = std::chrono::steady_clock::now();
+    const double td = now_ms();
     chunk.clear();
     started_from.clear();
-    ms_parts[0] = std::chrono::duration<double, std::milli>(tc - tb).count();
-    ms_parts[5] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - td).count();
+    ms_parts[0] = tc - tb;
+    ms_parts[5] = now_ms() - td;
     norm.reset(); hash.reset(); strand.reset();
   }
 };
@@ -715,20 +744,59 @@ double prefilter_c(int s) {
   const double root = (5.0 + std::sqrt(25.0 + 4.0 * (double)std::max(1, s))) / 2.0;
   return std::min(3.0, root * root / (double)std::max(1, s));
 }
-uint64_t prefilter_tau(int s, int64_t W) {
-  const char* on = getenv("WFM_PREFILTER");
-  if (on && atoi(on) == 0) return 0;
-  const char* ce = getenv("WFM_PREFILTER_C");
-  const double c = ce ? atof(ce) : prefilter_c(s);
-  const double share = c * (double)s / (double)std::max<int64_t>(1, W);
-  if (!(share > 0) || share > 0.5) return 0;
-  return map_prefilter_tau(c, s, W);
-}
 
-int64_t chunk_length() {
-  const char* e = getenv("WFM_WINNOW_CHUNK");  // k-mers per speculative chunk; 0 = one stream per sequence
-  return e ? atoll(e) : (int64_t)1 << 18;
-}
+// Every switch of one add_minmers_core call, read once when it begins, and what follows from them.
+struct SketchKnobs {
+  int threads = 1;          // host workers
+  int64_t chunk_len = 0;    // WFM_WINNOW_CHUNK: k-mers per speculative chunk; 0 = one stream per sequence
+  bool streamed = false;    // chunks through the pinned ring; otherwise whole sequences through ordinary memory
+  int64_t W = 1;            // k-mers per window
+  uint64_t tau = 0;         // the thinned stream's hash threshold; 0 = no thinning
+  int64_t slot_kmers = 0;
+  size_t slot_bytes = 0;
+  int nslots = 16;
+  int dev_threads = 2;      // WFM_WINNOW_DEV_THREADS
+  bool dev_finish = true;   // WFM_FINISH_DEVICE: the closing sort on the device as well
+  bool dev_winnow = true;   // WFM_WINNOW_DEVICE
+  int64_t dev_min = (int64_t)1 << 22;  // WFM_WINNOW_DEV_MIN: k-mers from which on a sequence goes to the device
+  int64_t dev_chunk = 0;    // WFM_WINNOW_DEV_CHUNK; 0: by sequence length
+  bool debug = false;       // WFM_DEBUG: the two [wfm] lines
+
+  static SketchKnobs read(int threads, int k, int w, int s) {
+    SketchKnobs K;
+    K.threads = std::max(1, threads);
+    const char* e = getenv("WFM_WINNOW_CHUNK");
+    K.chunk_len = K.threads > 1 ? (e ? atoll(e) : (int64_t)1 << 18) : 0;
+    K.streamed = K.chunk_len >= 64 * (int64_t)w;
+    K.W = (int64_t)w - k + 1;
+    const char* on = getenv("WFM_PREFILTER");
+    if (K.streamed && !(on && atoi(on) == 0)) {
+      const char* ce = getenv("WFM_PREFILTER_C");
+      const double c = ce ? atof(ce) : prefilter_c(s);
+      const double share = c * (double)s / (double)std::max<int64_t>(1, K.W);
+      if (share > 0 && share <= 0.5) K.tau = map_prefilter_tau(c, s, K.W);
+    }
+    K.slot_kmers = K.chunk_len + K.chunk_len / 2 + 2 * (int64_t)w + 1;
+    K.slot_bytes = std::max(map_stage_bytes(K.slot_kmers, K.slot_kmers + k), (size_t)K.slot_kmers * 13);
+    // several device threads, each with a stream and work buffers of its own: a sequence costs the device path 2 - 3 ms of
+    // launches and round trips whatever its length, which the threads overlap (chromosome-sized sequences are one launch
+    // set each and fill the device alone; a yeast genome is 128 short ones)
+    if ((e = getenv("WFM_WINNOW_DEV_THREADS"))) K.dev_threads = atoi(e);
+    K.dev_threads = std::max(1, std::min(16, K.dev_threads));
+    if ((e = getenv("WFM_FINISH_DEVICE"))) K.dev_finish = atoi(e) != 0;
+    if ((e = getenv("WFM_WINNOW_DEVICE"))) K.dev_winnow = atoi(e) != 0;
+    // Sequences under 4 M k-mers stay with the host's workers.  Round 3 tried to move the switch down with several device
+    // threads (each its own stream and buffers): on the C1 substitute (128 sequences of 0.2 - 1.5 Mbp) the index took 0.25 s with
+    // 4 device threads from 256 k k-mers on, 0.19 - 0.21 s with the closing sort left to the host, against 0.13 - 0.15 s on the
+    // host path (also with 32 host threads) -- a sequence costs the device path 2 - 4 ms of launches and stream
+    // synchronisations whatever its length, the threads contend for the queue, and the feeding thread (hash + thin: 0.9 ms per
+    // sequence) slows down beside them.  Only launch sets that span many sequences would change that.
+    if ((e = getenv("WFM_WINNOW_DEV_MIN"))) K.dev_min = atoll(e);
+    if ((e = getenv("WFM_WINNOW_DEV_CHUNK"))) K.dev_chunk = atoll(e);
+    K.debug = getenv("WFM_DEBUG") != nullptr;
+    return K;
+  }
+};
 
 }  // namespace
 
@@ -777,13 +845,13 @@ extern "C" int64_t wfm_add_minmers(wfm_handle_t* h, const char* seq, int64_t len
   return wfm_add_minmers_multi(h, seqs, &len, &seq_id, 1, k, w, s, 1, out, cap, nullptr);
 }
 
-// Many sequences at once.  The calling thread hashes one sequence after the other on the GPU; the
-// hashes stay there.  A second thread streams them out chunk by chunk through a small ring of pinned
-// slots (asynchronous copies at link speed, no page faults); `threads` host workers take a slot's
-// bytes into their own reused buffer, hand the slot back and winnow the chunk -- sequences side by
-// side (the reference's ThreadPool over buildHelper, winSketch.hpp:200-239) and, within a long
-// sequence, its speculative chunks.  The host never holds more than one chunk per worker.
-// Output is the concatenation in input order.
+// Many sequences at once (add_minmers_core, one SketchRun per call).  The calling thread hashes one sequence after the
+// other on the GPU (feed_one); the hashes stay there.  A second thread streams them out chunk by chunk through a small
+// ring of pinned slots (streamer_loop: asynchronous copies at link speed, no page faults); `threads` host workers take
+// a slot's bytes into their own reused buffer, hand the slot back and winnow the chunk (worker_loop, take_slot) --
+// sequences side by side (the reference's ThreadPool over buildHelper, winSketch.hpp:200-239) and, within a long
+// sequence, its speculative chunks.  The host never holds more than one chunk per worker.  Long thinned sequences are
+// winnowed by the device threads instead (device_loop).  Output is the concatenation in input order (deliver).
 namespace {
 // where the records of the sequences go: put() is called once per sequence, in input order, from the calling thread
 struct MinmerSink {
@@ -792,436 +860,385 @@ struct MinmerSink {
   virtual int put_device(const wfm_minmer_t* d_recs, int64_t n) = 0;  // the same, records on the device
 };
 
-// later: (optional) receives the release of the device work buffers and of the block pool instead of it being done before
-// the return -- the caller that goes on to allocate gigabytes (the index) runs it afterwards: memory the driver has just
-// been handed back is scrubbed in the background, and an allocation that follows on its heels waits for that
-int64_t add_minmers_core(wfm_handle_t* h, const char* const* seqs, const int64_t* lens, const int32_t* seq_ids, int64_t nseq,
-                         int k, int w, int s, int threads, MinmerSink& sink, int64_t* counts, std::function<void()>* later = nullptr) {
-  if (!h || nseq < 0 || (nseq && (!seqs || !lens || !seq_ids))) return WFM_E_ARG;
-  if (k < 1 || k > 32 || w < k || s < 1) { wfm_set_error(h, "need 1 <= k <= 32, w >= k, s >= 1"); return WFM_E_UNSUPPORTED; }
-  const int nthreads = std::max(1, threads);
-  const int64_t chunk_len = nthreads > 1 ? chunk_length() : 0;
-  const bool streamed = chunk_len >= 64 * (int64_t)w;  // otherwise: whole sequences through ordinary memory
-  MapStage* stage = nullptr;
-  const int64_t W = (int64_t)w - k + 1;  // k-mers per window
-  const uint64_t tau = streamed ? prefilter_tau(s, W) : 0;
-  const int64_t slot_kmers = chunk_len + chunk_len / 2 + 2 * (int64_t)w + 1;
-  const size_t slot_bytes = std::max(map_stage_bytes(slot_kmers, slot_kmers + k), (size_t)slot_kmers * 13);
-  const int nslots = 16;
-  if (streamed) {
-    const int src = map_stage_acquire(h, slot_bytes, nslots, &stage);
-    if (src != WFM_OK) return src;
+// the device work buffers of one call; calling it releases them and trims the block pool (add_minmers_core's `later`)
+struct SketchWork {
+  MapHashWork hash;
+  MapThinWork thin;
+  std::vector<MapWinnowWork> winnow;  // one per device thread
+  std::vector<MapFinishWork> finish;
+  void operator()() {
+    map_hash_work_free(&hash);
+    map_thin_work_free(&thin);
+    for (auto& wk : winnow) map_winnow_work_free(&wk);
+    for (auto& wk : finish) map_finish_work_free(&wk);
+    map_dev_pool_trim();
+  }
+};
+
+const char* const kStreamingFailed = "device-to-host streaming of k-mer hashes failed";
+
+// One add_minmers_core call.  The calling thread feeds (feed_one: hash, plan, thin, route), delivers in input order and
+// releases; K.threads workers winnow chunks and stitch; K.dev_threads device threads winnow thinned sequences on the device;
+// one streamer (streamed calls only) copies chunks into the ring.  The scheduling is sketch_queue.hpp's.
+struct SketchRun {
+  struct Task { SeqJob* job; size_t chunk; int slot; };  // slot < 0: the job's own host arrays, or its closing sort
+
+  wfm_handle_t* const h;
+  const SketchKnobs K;
+  const int k, w, s;
+  MapStage* const stage;  // the pinned ring (streamed calls)
+  MinmerSink& sink;
+  int64_t* const counts;
+  const int64_t nseq;
+  std::vector<std::unique_ptr<SeqJob>> jobs;  // written by the calling thread only
+  SketchWork work_bufs;
+  std::mutex gpu_mu;  // the handle's stream and error string: the calling thread, and a worker that hashes a sequence again
+
+  skch::Handoff<Task> work;          // for the workers
+  skch::Handoff<SeqJob*> to_stream;  // for the streamer
+  skch::Handoff<SeqJob*> to_device;  // for the device threads
+  skch::SlotPool slots;
+  skch::InflightWindow window{(int64_t)1 << 31};  // ~2 Gbp hashed but not yet winnowed: 10 B/base on the device
+  skch::DeliveryCursor cursor;
+  skch::FirstError err;
+  std::mutex release_mu;
+  std::vector<SeqJob*> to_release;  // final, device arrays still held: released by the calling thread
+
+  int64_t total = 0;
+  int sink_rc = WFM_OK;
+  // for the two [wfm] lines
+  double t_start = 0, t_fed = 0, ms_hash = 0, ms_thin = 0;
+  int64_t kept_kmers = 0, thinned_kmers = 0;
+  std::mutex dev_stat_mu;  // the counters below
+  int64_t dev_seqs = 0, dev_handed_back = 0, dev_chunks = 0, dev_replays = 0, dev_heaps = 0;
+  int dev_levels = 0;
+  uint32_t dev_why = 0;
+  double ms_winnow = 0;
+
+  skch::StageThreads<Task, SeqJob*> threads{work, to_stream, to_device};  // last: joined before anything above goes
+
+  SketchRun(wfm_handle_t* h_, const SketchKnobs& K_, int k_, int w_, int s_, MapStage* stage_, MinmerSink& sink_, int64_t* counts_, int64_t nseq_)
+      : h(h_), K(K_), k(k_), w(w_), s(s_), stage(stage_), sink(sink_), counts(counts_), nseq(nseq_), jobs((size_t)nseq_),
+        slots(K_.streamed ? stage_->nslots : 0), cursor(nseq_) {
+    work_bufs.winnow.resize((size_t)K.dev_threads);
+    work_bufs.finish.resize((size_t)K.dev_threads);
   }
 
-  std::vector<std::unique_ptr<SeqJob>> jobs((size_t)nseq);
-  struct Task { SeqJob* job; size_t chunk; int slot; };
-  std::deque<Task> queue;       // for the workers
-  std::deque<SeqJob*> hashed;   // for the streaming thread
-  std::vector<int> free_slots;
-  for (int i = 0; i < (streamed ? stage->nslots : 0); ++i) free_slots.push_back(i);
-  std::vector<SeqJob*> stitched;  // device arrays to release (done by the calling thread)
-  std::mutex mu;
-  std::condition_variable cv_work, cv_room, cv_slot, cv_hashed;
-  bool done = false, hashed_done = false;
-  std::atomic<int> async_rc{WFM_OK};
-  std::atomic<bool> async_msg_set{false};  // the failing path left its own text in the handle: do not overwrite it
-  int64_t inflight_bases = 0;
-  const int64_t max_inflight = 1ll << 31;  // ~2 Gbp hashed but not yet winnowed: 10 B/base on the device
+  void start() {
+    threads.start_workers(K.threads, [this] { worker_loop(); });
+    threads.start_device(K.dev_threads, [this](int t) { device_loop(t); });
+    if (K.streamed) threads.start_streamer([this] { streamer_loop(); });
+    t_start = now_ms();
+  }
 
-  auto worker = [&]() {
+  // ---- a sequence is final: the one place ----
+  void retire(SeqJob* J, bool holds_arrays) {
+    cursor.mark_final(J->idx);
+    if (holds_arrays) { std::lock_guard<std::mutex> lk(release_mu); to_release.push_back(J); }
+    window.retire(J->len);
+  }
+
+  // ---- host workers ----
+  void worker_loop() {
     std::vector<char> local;
-    for (;;) {
-      Task task;
-      {
-        std::unique_lock<std::mutex> lk(mu);
-        cv_work.wait(lk, [&] { return done || !queue.empty(); });
-        if (queue.empty()) return;
-        task = queue.front();
-        queue.pop_front();
-      }
+    for (Task task; work.pop(&task);) {
       SeqJob* J = task.job;
-      if (J->dev_winnowed) {  // winnowed on the device: only the closing sort is left
-        const auto ts = std::chrono::steady_clock::now();
-        J->finish_device_records();
-        J->ms_stitch = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ts).count();
-        J->stitched.store(true, std::memory_order_release);
-        {
-          std::lock_guard<std::mutex> lk(mu);
-          inflight_bases -= J->len;
-          stitched.push_back(J);
-        }
-        cv_room.notify_one();
-        continue;
-      }
+      if (J->dev_winnowed) { close_device_winnowed(J); continue; }
       SeqJob::View v;
       v.d = J->whole();
-      if (task.slot >= 0) {
-        int64_t kf, kt, bt;
-        J->chunk_range(task.chunk, &kf, &kt, &bt);
-        const size_t mc = J->thinned ? (size_t)(J->cidx[task.chunk + 1] - J->cidx_warm[task.chunk]) : 0;
-        const size_t nbytes = J->thinned ? mc * 13 : map_stage_bytes(kt - kf, bt - kf);
-        if (local.size() < std::max<size_t>(nbytes, 16)) local.resize(std::max(nbytes, stage->slot_bytes));
-        const int wrc = map_stage_wait(stage, task.slot);
-        if (wrc == WFM_OK) memcpy(local.data(), stage->slot(task.slot), nbytes);
-        else { memset(local.data(), 0, nbytes); async_rc.store(wrc); }
-        {
-          std::lock_guard<std::mutex> lk(mu);
-          free_slots.push_back(task.slot);
-        }
-        cv_slot.notify_one();
-        if (J->thinned) {
-          static const uint32_t none = 0;
-          v.sp = SeqJob::packed_sparse(local.data(), mc);
-          if (mc == 0) v.sp.pos = &none;  // an empty stream is still a thinned one
-        } else {
-          v.d = SeqJob::packed(local.data(), kf, kt);
-        }
-      }
+      if (task.slot >= 0) v = take_slot(task, local);
       J->run_chunk(task.chunk, v);
       if (J->pending.fetch_sub(1) == 1) {  // last chunk of this sequence: stitch here
-        const auto ts = std::chrono::steady_clock::now();
+        const double ts = now_ms();
         J->stitch();
-        J->ms_stitch = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ts).count();
-        if (J->fetch_rc != WFM_OK) async_rc.store(J->fetch_rc);
-        J->stitched.store(true, std::memory_order_release);
-        {
-          std::lock_guard<std::mutex> lk(mu);
-          inflight_bases -= J->len;
-          stitched.push_back(J);
-        }
-        cv_room.notify_one();
+        J->ms_stitch = now_ms() - ts;
+        if (J->fetch_rc != WFM_OK) err.set(J->fetch_rc, kStreamingFailed);
+        retire(J, true);
       }
     }
-  };
-  // streams the chunks of every hashed sequence into the ring, in order
-  auto streamer = [&]() {
-    for (;;) {
-      SeqJob* J;
-      {
-        std::unique_lock<std::mutex> lk(mu);
-        cv_hashed.wait(lk, [&] { return hashed_done || !hashed.empty(); });
-        if (hashed.empty()) break;
-        J = hashed.front();
-        hashed.pop_front();
-      }
+  }
+  // a slot's bytes into the worker's own buffer, the slot back to the ring, a view of the copy
+  SeqJob::View take_slot(const Task& task, std::vector<char>& local) {
+    SeqJob* J = task.job;
+    int64_t kf, kt, bt;
+    J->chunk_range(task.chunk, &kf, &kt, &bt);
+    const size_t mc = J->thinned ? (size_t)(J->cidx[task.chunk + 1] - J->cidx_warm[task.chunk]) : 0;
+    const size_t nbytes = J->thinned ? mc * 13 : map_stage_bytes(kt - kf, bt - kf);
+    if (local.size() < std::max<size_t>(nbytes, 16)) local.resize(std::max(nbytes, stage->slot_bytes));
+    const int wrc = map_stage_wait(stage, task.slot);
+    if (wrc == WFM_OK) memcpy(local.data(), stage->slot(task.slot), nbytes);
+    else { memset(local.data(), 0, nbytes); err.set(wrc, kStreamingFailed); }
+    slots.give(task.slot);
+    SeqJob::View v;
+    if (J->thinned) {
+      v.sp = SeqJob::packed_sparse(local.data(), mc);
+      if (mc == 0) v.sp.pos = &kNoKmer;
+    } else {
+      v.d = SeqJob::packed(local.data(), kf, kt);
+    }
+    return v;
+  }
+  // winnowed on the device (WFM_FINISH_DEVICE=0): only the closing sort is left
+  void close_device_winnowed(SeqJob* J) {
+    const double ts = now_ms();
+    J->finish_device_records();
+    J->ms_stitch = now_ms() - ts;
+    retire(J, true);
+  }
+
+  // ---- the streamer: the chunks of every sequence it is given into the ring, in order ----
+  void streamer_loop() {
+    for (SeqJob* J; to_stream.pop(&J);) {
       for (size_t c = 0; c + 1 < J->bounds.size(); ++c) {
-        int slot;
-        {
-          std::unique_lock<std::mutex> lk(mu);
-          cv_slot.wait(lk, [&] { return !free_slots.empty(); });
-          slot = free_slots.back();
-          free_slots.pop_back();
-        }
+        const int slot = slots.take();
         int64_t kf, kt, bt;
         J->chunk_range(c, &kf, &kt, &bt);
         const int crc = J->thinned ? map_stage_copy_sparse(stage, slot, &J->sparse, J->cidx_warm[c], J->cidx[c + 1])
                                    : map_stage_copy(stage, slot, &J->dev, kf, kt, kf, bt);
-        if (crc != WFM_OK) async_rc.store(crc);  // the worker still runs (on whatever the slot holds): keeps the bookkeeping simple
-        {
-          std::lock_guard<std::mutex> lk(mu);
-          queue.push_back(Task{J, c, slot});
-        }
-        cv_work.notify_one();
+        if (crc != WFM_OK) err.set(crc, kStreamingFailed);  // the worker still runs (on whatever the slot holds): keeps the bookkeeping simple
+        work.push(Task{J, c, slot});
       }
     }
-    {
-      std::lock_guard<std::mutex> lk(mu);
-      done = true;
-    }
-    cv_work.notify_all();
-  };
-  auto release_stitched = [&]() {
-    std::vector<SeqJob*> list;
-    {
-      std::lock_guard<std::mutex> lk(mu);
-      list.swap(stitched);
-    }
-    for (SeqJob* J : list) {
-      if (J->on_device) { map_hashed_free(&J->dev); J->on_device = false; }
-      map_sparse_free(&J->sparse);
-    }
-  };
+  }
 
-  // finished sequences leave in input order while the later ones are still being worked on
-  int64_t next_out = 0, total = 0;
-  int sink_rc = WFM_OK;
-  auto flush_ready = [&](int64_t limit) {
-    for (; next_out < limit; ++next_out) {
-      SeqJob* J = jobs[(size_t)next_out].get();
-      if (J && !J->stitched.load(std::memory_order_acquire)) break;
-      const int64_t n = J ? (J->d_result ? J->n_result : (int64_t)J->result.size()) : 0;
-      if (counts) counts[next_out] = n;
-      if (n && sink_rc == WFM_OK) sink_rc = J->d_result ? sink.put_device(J->d_result, n) : sink.put(J->result.data(), n);
-      total += n;
-      if (J) J->result.release();
-      if (J && J->d_result) {
-        // the sink's device-to-device copy runs on the null stream and need not be over when the call returns; the
-        // device thread's stream does not wait for the null stream, so the block must not go back to the pool before it is
-        if (hipStreamSynchronize(nullptr) != hipSuccess && sink_rc == WFM_OK) sink_rc = WFM_E_HIP;
-        map_dev_pool_put(wfm_device(h), J->d_result);
-        J->d_result = nullptr;
-      }
-    }
-  };
-  std::mutex gpu_mu;  // the handle's stream and error string: this thread, and a worker that hashes a sequence again
-  MapHashWork hash_work;
-  MapThinWork thin_work;
-
-  // several device threads, each with a stream and work buffers of its own: a sequence costs the device path 2 - 3 ms of
-  // launches and round trips whatever its length, which the threads overlap (chromosome-sized sequences are one launch
-  // set each and fill the device alone; a yeast genome is 128 short ones)
-  const int n_dev_threads = std::max(1, std::min(16, getenv("WFM_WINNOW_DEV_THREADS") ? atoi(getenv("WFM_WINNOW_DEV_THREADS")) : 2));
-  std::vector<MapWinnowWork> winnow_works((size_t)n_dev_threads);
-  std::vector<MapFinishWork> finish_works((size_t)n_dev_threads);
-  const bool dev_finish = !(getenv("WFM_FINISH_DEVICE") && atoi(getenv("WFM_FINISH_DEVICE")) == 0);
-  int dev_levels = 0;
-  int64_t dev_heaps = 0;
-  const bool dev_winnow = !(getenv("WFM_WINNOW_DEVICE") && atoi(getenv("WFM_WINNOW_DEVICE")) == 0);
-  // Sequences under 4 M k-mers stay with the host's workers.  Round 3 tried to move the switch down with several device
-  // threads (each its own stream and buffers): on the C1 substitute (128 sequences of 0.2 - 1.5 Mbp) the index took 0.25 s with
-  // 4 device threads from 256 k k-mers on, 0.19 - 0.21 s with the closing sort left to the host, against 0.13 - 0.15 s on the
-  // host path (also with 32 host threads) -- a sequence costs the device path 2 - 4 ms of launches and stream
-  // synchronisations whatever its length, the threads contend for the queue, and the feeding thread (hash + thin: 0.9 ms per
-  // sequence) slows down beside them.  Only launch sets that span many sequences would change that.
-  const int64_t dev_min = getenv("WFM_WINNOW_DEV_MIN") ? atoll(getenv("WFM_WINNOW_DEV_MIN")) : (int64_t)1 << 22;
-  const int64_t dev_chunk = getenv("WFM_WINNOW_DEV_CHUNK") ? atoll(getenv("WFM_WINNOW_DEV_CHUNK")) : 0;  // 0: by sequence length
-  int64_t dev_seqs = 0, dev_handed_back = 0, dev_chunks = 0, dev_replays = 0;
-  uint32_t dev_why = 0;
-  double ms_winnow = 0;
-  // Winnowing and the closing sort of thinned sequences on the device (map_winnow.hip, map_finish.hip), on a stream and a
-  // thread of their own: the calling thread is hashing and thinning the next sequence meanwhile.  A sequence the device
-  // hands back joins the host path (the streamer's list).
-  std::deque<SeqJob*> dev_queue;
-  std::condition_variable cv_dev;
-  bool dev_done = false;
-  auto seq_finished = [&](SeqJob* J) {
-    J->stitched.store(true, std::memory_order_release);
-    {
-      std::lock_guard<std::mutex> lk(mu);
-      inflight_bases -= J->len;
-    }
-    cv_room.notify_one();
-  };
-  std::mutex dev_stat_mu;  // the counters below
-  auto device_thread = [&](int dti) {
+  // ---- device threads ----
+  // Winnowing and the closing sort of thinned sequences on the device (map_winnow.hip, map_finish.hip), each thread on a
+  // stream of its own: the calling thread is hashing and thinning the next sequence meanwhile.
+  void device_loop(int dti) {
     (void)hipSetDevice(wfm_device(h));
-    MapWinnowWork& winnow_work = winnow_works[(size_t)dti];
-    MapFinishWork& finish_work = finish_works[(size_t)dti];
-    hipStream_t st2 = nullptr;
-    if (hipStreamCreateWithFlags(&st2, hipStreamNonBlocking) != hipSuccess) st2 = nullptr;
-    for (;;) {
-      SeqJob* J;
-      {
-        std::unique_lock<std::mutex> lk(mu);
-        cv_dev.wait(lk, [&] { return dev_done || !dev_queue.empty(); });
-        if (dev_queue.empty()) break;
-        J = dev_queue.front();
-        dev_queue.pop_front();
-      }
-      const auto tw = std::chrono::steady_clock::now();
-      wfm_minmer_t* d_recs = nullptr;
-      int64_t n_recs = 0;
+    hipStream_t st = nullptr;
+    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) st = nullptr;
+    for (SeqJob* J; to_device.pop(&J);) {
       MapWinnowInfo wi;
-      // chunk length: one wave per chunk, and about as many chunks as the device keeps resident at once (a chunk's two
-      // windows of warm-up are its overhead: no chunk under four windows)
-      const int64_t auto_chunk = std::min<int64_t>((J->nk + 6143) / 6144, (int64_t)1 << 16);
-      // (no stream of its own: the sequence goes to the host's winnower like any other the device hands back)
-      int wrc = st2 ? map_winnow_sparse_device(h, &J->sparse, J->len, k, w, s, J->seq_id, std::max<int64_t>(dev_chunk > 0 ? dev_chunk : auto_chunk, 4 * (int64_t)w),
-                                               &winnow_work, &d_recs, &n_recs, &wi, st2)
-                    : 1;
-      { std::lock_guard<std::mutex> lk(dev_stat_mu); dev_chunks += wi.chunks; dev_replays += wi.replays; }
-      if (wrc == WFM_OK && dev_finish) {  // the closing cut / sort / de-duplication on the device as well
-        wfm_minmer_t* d_fin = nullptr;
-        int64_t n_fin = 0;
-        MapFinishInfo fi;
-        wrc = map_finish_records_device(h, d_recs, n_recs, w, &finish_work, &d_fin, &n_fin, &fi, st2);
-        if (wrc == WFM_OK && n_fin) {
-          J->d_result = (wfm_minmer_t*)map_dev_pool_get(wfm_device(h), (size_t)n_fin * sizeof(wfm_minmer_t));
-          if (!J->d_result || hipMemcpyAsync(J->d_result, d_fin, (size_t)n_fin * sizeof(wfm_minmer_t), hipMemcpyDeviceToDevice, st2) != hipSuccess ||
-              hipStreamSynchronize(st2) != hipSuccess) {
-            wfm_set_error(h, "out of device memory (minmer records)");
-            wrc = WFM_E_NOMEM;
-          }
-        }
-        if (wrc == WFM_OK) {
-          J->n_result = n_fin;
-          J->dev_winnowed = true;
-          std::lock_guard<std::mutex> lk(dev_stat_mu);
-          ++dev_seqs;
-          dev_levels = std::max(dev_levels, fi.levels);
-          dev_heaps += fi.heap_ranges;
-        }
-      } else if (wrc == WFM_OK) {  // WFM_FINISH_DEVICE=0: the closing sort by a host worker
-        J->dev_raw.resize((size_t)n_recs);
-        if (n_recs && (hipMemcpyAsync(J->dev_raw.data(), d_recs, (size_t)n_recs * sizeof(wfm_minmer_t), hipMemcpyDeviceToHost, st2) != hipSuccess ||
-                       hipStreamSynchronize(st2) != hipSuccess)) {
-          wfm_set_error(h, "device-to-host copy of minmer records failed");
-          wrc = WFM_E_HIP;
-        } else {
-          J->dev_winnowed = true;
-          std::lock_guard<std::mutex> lk(dev_stat_mu);
-          ++dev_seqs;
-        }
-      }
-      { std::lock_guard<std::mutex> lk(dev_stat_mu); ms_winnow += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw).count(); }
-      if (wrc < 0) {  // an error: the sequence ends here with no records, the call fails (the failing path has set the message)
-        async_msg_set.store(true);
-        async_rc.store(wrc);
-        map_sparse_free(&J->sparse);
-        seq_finished(J);
-      } else if (wrc == 1) {  // not for the device after all: the host's chunks
-        { std::lock_guard<std::mutex> lk(dev_stat_mu); ++dev_handed_back; dev_why |= wi.why; }
-        {
-          std::lock_guard<std::mutex> lk(mu);
-          hashed.push_back(J);
-        }
-        cv_hashed.notify_one();
-      } else if (J->d_result || J->dev_raw.empty()) {  // winnowed and finished: nothing left to do
-        map_sparse_free(&J->sparse);
-        seq_finished(J);
-      } else {
-        map_sparse_free(&J->sparse);
-        {
-          std::lock_guard<std::mutex> lk(mu);
-          queue.push_back(Task{J, 0, -1});
-        }
-        cv_work.notify_one();
+      const int wrc = winnow_on_device(J, dti, st, &wi);
+      route_device_outcome(J, wrc, wi);
+    }
+    if (st) (void)hipStreamDestroy(st);
+  }
+  // -> WFM_OK (J->dev_winnowed; records in J->d_result, or raw in J->dev_raw), 1 = not for the device after all, < 0 an error
+  int winnow_on_device(SeqJob* J, int dti, hipStream_t st, MapWinnowInfo* wi) {
+    const double tw = now_ms();
+    wfm_minmer_t* d_recs = nullptr;
+    int64_t n_recs = 0;
+    // chunk length: one wave per chunk, and about as many chunks as the device keeps resident at once (a chunk's two
+    // windows of warm-up are its overhead: no chunk under four windows)
+    const int64_t auto_chunk = std::min<int64_t>((J->nk + 6143) / 6144, (int64_t)1 << 16);
+    // (no stream of its own: the sequence goes to the host's winnower like any other the device hands back)
+    int wrc = st ? map_winnow_sparse_device(h, &J->sparse, J->len, k, w, s, J->seq_id, std::max<int64_t>(K.dev_chunk > 0 ? K.dev_chunk : auto_chunk, 4 * (int64_t)w),
+                                            &work_bufs.winnow[(size_t)dti], &d_recs, &n_recs, wi, st)
+                 : 1;
+    { std::lock_guard<std::mutex> lk(dev_stat_mu); dev_chunks += wi->chunks; dev_replays += wi->replays; }
+    if (wrc == WFM_OK) wrc = K.dev_finish ? finish_on_device(J, dti, st, d_recs, n_recs) : fetch_raw_records(J, st, d_recs, n_recs);
+    { std::lock_guard<std::mutex> lk(dev_stat_mu); ms_winnow += now_ms() - tw; }
+    return wrc;
+  }
+  // the closing cut / sort / de-duplication on the device as well; the records end in a pooled block
+  int finish_on_device(SeqJob* J, int dti, hipStream_t st, const wfm_minmer_t* d_recs, int64_t n_recs) {
+    wfm_minmer_t* d_fin = nullptr;
+    int64_t n_fin = 0;
+    MapFinishInfo fi;
+    const int rc = map_finish_records_device(h, d_recs, n_recs, w, &work_bufs.finish[(size_t)dti], &d_fin, &n_fin, &fi, st);
+    if (rc != WFM_OK) return rc;
+    if (n_fin) {
+      J->d_result = (wfm_minmer_t*)map_dev_pool_get(wfm_device(h), (size_t)n_fin * sizeof(wfm_minmer_t));
+      if (!J->d_result || hipMemcpyAsync(J->d_result, d_fin, (size_t)n_fin * sizeof(wfm_minmer_t), hipMemcpyDeviceToDevice, st) != hipSuccess ||
+          hipStreamSynchronize(st) != hipSuccess) {
+        err.set(WFM_E_NOMEM, "out of device memory (minmer records)");
+        return WFM_E_NOMEM;
       }
     }
-    if (st2) (void)hipStreamDestroy(st2);
-  };
-  std::vector<std::thread> pool;
-  for (int t = 0; t < nthreads; ++t) pool.emplace_back(worker);
-  std::vector<std::thread> dev_threads;
-  for (int t = 0; t < n_dev_threads; ++t) dev_threads.emplace_back(device_thread, t);
-  std::thread stream_thread;
-  if (streamed) stream_thread = std::thread(streamer);
-  int rc = WFM_OK;
-  const auto t_start = std::chrono::steady_clock::now();
-  double ms_hash = 0, ms_thin = 0;
-  int64_t kept_kmers = 0, thinned_kmers = 0;
-  for (int64_t i = 0; i < nseq && rc == WFM_OK; ++i) {
-    const int64_t len = lens[i];
-    if (!seqs[i] || len < 0) { rc = WFM_E_ARG; break; }
-    if (len < k) continue;
-    {
-      std::unique_lock<std::mutex> lk(mu);
-      cv_room.wait(lk, [&] { return inflight_bases == 0 || inflight_bases + len <= max_inflight; });
-      inflight_bases += len;
+    J->n_result = n_fin;
+    J->dev_winnowed = true;
+    std::lock_guard<std::mutex> lk(dev_stat_mu);
+    ++dev_seqs;
+    dev_levels = std::max(dev_levels, fi.levels);
+    dev_heaps += fi.heap_ranges;
+    return WFM_OK;
+  }
+  // WFM_FINISH_DEVICE=0: the raw records to the host, the closing sort by a host worker
+  int fetch_raw_records(SeqJob* J, hipStream_t st, const wfm_minmer_t* d_recs, int64_t n_recs) {
+    J->dev_raw.resize((size_t)n_recs);
+    if (n_recs && (hipMemcpyAsync(J->dev_raw.data(), d_recs, (size_t)n_recs * sizeof(wfm_minmer_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
+                   hipStreamSynchronize(st) != hipSuccess)) {
+      err.set(WFM_E_HIP, "device-to-host copy of minmer records failed");
+      return WFM_E_HIP;
     }
+    J->dev_winnowed = true;
+    std::lock_guard<std::mutex> lk(dev_stat_mu);
+    ++dev_seqs;
+    return WFM_OK;
+  }
+  void route_device_outcome(SeqJob* J, int wrc, const MapWinnowInfo& wi) {
+    if (wrc == 1) {  // not for the device after all: the host's chunks, through the streamer (there is one: see route())
+      { std::lock_guard<std::mutex> lk(dev_stat_mu); ++dev_handed_back; dev_why |= wi.why; }
+      to_stream.push(J);
+      return;
+    }
+    map_sparse_free(&J->sparse);
+    if (wrc < 0) {  // the sequence ends here with no records, the call fails (text: set above, or left in the handle by the device call)
+      err.set(wrc, nullptr);
+      retire(J, false);
+    } else if (J->d_result || J->dev_raw.empty()) {  // winnowed and finished: nothing left to do
+      retire(J, false);
+    } else {
+      work.push(Task{J, 0, -1});
+    }
+  }
+
+  // ---- the calling thread: feeding ----
+  int feed_one(int64_t i, const char* seq, int64_t len, int32_t seq_id) {
+    if (!seq || len < 0) return WFM_E_ARG;
+    if (len < k) { cursor.mark_final(i); return WFM_OK; }  // no record
+    window.admit(len);
     release_stitched();
-    flush_ready(i);
+    deliver_ready(i);
     auto J = std::make_unique<SeqJob>();
-    J->idx = i; J->seq_id = seq_ids[i]; J->len = len; J->nk = len - k + 1; J->k = k; J->w = w; J->s = s;
-    J->sort_threads = std::min(16, nthreads);
-    const auto t0 = std::chrono::steady_clock::now();
-    const bool thin = tau != 0 && J->nk >= W && J->nk < ((int64_t)1 << 32) - 1;
+    J->shape(i, seq_id, len, k, w, s, std::min(16, K.threads));
+    int rc;
+    try {
+      rc = hash_and_route(J.get(), seq);
+    } catch (...) {  // never queued: the job goes with J, jobs[i] stays empty and counts as final
+      release_arrays(J.get());
+      window.retire(len);
+      throw;
+    }
+    // A job is in jobs[] only once a thread has it: what is there and not final WILL be made final, or drain() would wait
+    // for nobody.  (The stages hold the plain pointer; delivery and this line are the same thread.)
+    if (rc == WFM_OK) jobs[(size_t)i] = std::move(J);
+    else window.retire(len);
+    return rc;
+  }
+  int hash_and_route(SeqJob* J, const char* seq) {
+    const double t0 = now_ms();
+    const bool thin = K.tau != 0 && J->nk >= K.W && J->nk < ((int64_t)1 << 32) - 1;
     std::unique_lock<std::mutex> gpu(gpu_mu);
     // GPU: normalise + 2 x MurmurHash3 per base; the thinned form reuses one set of device buffers
-    rc = thin ? map_hash_sequence_into(h, &hash_work, seqs[i], len, k, &J->dev) : map_hash_sequence_device(h, seqs[i], len, k, &J->dev);
-    if (rc != WFM_OK) break;
+    int rc = thin ? map_hash_sequence_into(h, &work_bufs.hash, seq, J->len, k, &J->dev) : map_hash_sequence_device(h, seq, J->len, k, &J->dev);
+    if (rc != WFM_OK) return rc;
     J->on_device = true;
-    ms_hash += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    J->plan(streamed ? chunk_len : 0);
-    const auto t1 = std::chrono::steady_clock::now();
-    if (thin) {
-      // thin the stream on the device; only the kept k-mers outlive this iteration
-      J->raw = seqs[i]; J->handle = h; J->gpu_mu = &gpu_mu;
-      rc = map_prefilter_device(h, &J->dev, W, s, tau, &J->sparse, &thin_work);
-      if (rc != WFM_OK) { map_hashed_free(&J->dev); break; }
-      J->thinned = true;
-      kept_kmers += J->sparse.m;
-      thinned_kmers += J->nk;
-      J->head.assign((size_t)std::min<int64_t>(len, 2 * (int64_t)k), 'N');
-      rc = map_hashed_fetch(&J->dev, 0, 0, 0, (int64_t)J->head.size(), nullptr, nullptr, &J->head[0]);
-      const size_t nc = J->bounds.size() - 1;
-      std::vector<int64_t> q(2 * nc + 1), r(2 * nc + 1);
-      for (size_t c = 0; c <= nc; ++c) q[c] = J->bounds[c];
-      for (size_t c = 0; c < nc; ++c) q[nc + 1 + c] = J->warm_from(c);
-      if (rc == WFM_OK) rc = map_sparse_lower_bound(h, &J->sparse, q.data(), (int)q.size(), r.data());
-      if (rc != WFM_OK) { map_hashed_free(&J->dev); map_sparse_free(&J->sparse); break; }
-      J->cidx.assign(r.begin(), r.begin() + (long)nc + 1);
-      J->cidx_warm.assign(r.begin() + (long)nc + 1, r.end());
-      map_hashed_free(&J->dev);  // borrowed: just forgets the pointers
-      J->on_device = false;
-      // the winnowing itself goes to the device (map_winnow.hip, its own thread and stream below) unless the sequence starts
-      // with a k-mer whose N the reference does not notice
-      // -- or is short: the device path costs a few milliseconds per sequence in launches and round trips whatever its
-      // length, the host's workers take short sequences side by side (WFM_WINNOW_DEV_MIN: k-mers from which on the device is used)
-      J->for_device = dev_winnow && J->nk >= dev_min && !has_unnoticed_n(J->head.data(), (int64_t)J->head.size(), k);
-    }
+    ms_hash += now_ms() - t0;
+    J->plan(K.streamed ? K.chunk_len : 0);
+    const double t1 = now_ms();
+    if (thin && (rc = thin_on_device(J, seq)) != WFM_OK) return rc;
     gpu.unlock();
-    ms_thin += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
-    SeqJob* Jp = J.get();
-    jobs[(size_t)i] = std::move(J);
-    if (Jp->for_device) {
-      {
-        std::lock_guard<std::mutex> lk(mu);
-        dev_queue.push_back(Jp);
-      }
-      cv_dev.notify_one();
-    } else if (streamed) {
-      {
-        std::lock_guard<std::mutex> lk(mu);
-        hashed.push_back(Jp);
-      }
-      cv_hashed.notify_one();
-    } else {
-      Jp->norm.reset(new char[(size_t)len]);
-      Jp->hash.reset(new uint64_t[(size_t)Jp->nk]);
-      Jp->strand.reset(new int8_t[(size_t)Jp->nk]);
-      rc = map_hashed_fetch(&Jp->dev, 0, Jp->nk, 0, len, Jp->hash.get(), Jp->strand.get(), Jp->norm.get());
-      map_hashed_free(&Jp->dev);
-      Jp->on_device = false;
-      if (rc != WFM_OK) { wfm_set_error(h, "device-to-host copy of k-mer hashes failed"); jobs[(size_t)i].reset(); break; }  // never queued: nobody will stitch it
-      {
-        std::lock_guard<std::mutex> lk(mu);
-        queue.push_back(Task{Jp, 0, -1});
-      }
-      cv_work.notify_one();
+    ms_thin += now_ms() - t1;
+    return route(J);
+  }
+  // thin the stream on the device (gpu_mu held); only the kept k-mers, the head and the chunks' indices outlive the call
+  int thin_on_device(SeqJob* J, const char* seq) {
+    J->raw = seq; J->handle = h; J->gpu_mu = &gpu_mu;
+    int rc = map_prefilter_device(h, &J->dev, K.W, s, K.tau, &J->sparse, &work_bufs.thin);
+    if (rc != WFM_OK) { map_hashed_free(&J->dev); return rc; }
+    J->thinned = true;
+    kept_kmers += J->sparse.m;
+    thinned_kmers += J->nk;
+    J->head.assign((size_t)std::min<int64_t>(J->len, 2 * (int64_t)k), 'N');
+    rc = map_hashed_fetch(&J->dev, 0, 0, 0, (int64_t)J->head.size(), nullptr, nullptr, &J->head[0]);
+    const size_t nc = J->bounds.size() - 1;
+    std::vector<int64_t> q(2 * nc + 1), r(2 * nc + 1);
+    for (size_t c = 0; c <= nc; ++c) q[c] = J->bounds[c];
+    for (size_t c = 0; c < nc; ++c) q[nc + 1 + c] = J->warm_from(c);
+    if (rc == WFM_OK) rc = map_sparse_lower_bound(h, &J->sparse, q.data(), (int)q.size(), r.data());
+    if (rc != WFM_OK) { map_hashed_free(&J->dev); map_sparse_free(&J->sparse); return rc; }
+    J->cidx.assign(r.begin(), r.begin() + (long)nc + 1);
+    J->cidx_warm.assign(r.begin() + (long)nc + 1, r.end());
+    map_hashed_free(&J->dev);  // borrowed: just forgets the pointers
+    J->on_device = false;
+    // The winnowing itself goes to the device unless the sequence starts with a k-mer whose N the reference does not notice
+    // -- or is short: the device path costs a few milliseconds per sequence in launches and round trips whatever its
+    // length, the host's workers take short sequences side by side.  And only in a streamed call (thinning implies one;
+    // said here because everything hangs on it): a sequence the device hands back goes to the streamer, and the workers'
+    // list is closed by the streamer.
+    J->for_device = K.streamed && K.dev_winnow && J->nk >= K.dev_min && !has_unnoticed_n(J->head.data(), (int64_t)J->head.size(), k);
+    return WFM_OK;
+  }
+  int route(SeqJob* J) {
+    assert(K.streamed || !J->for_device);  // (a check of builds without NDEBUG; what holds in every build is the term in thin_on_device)
+    if (J->for_device) { to_device.push(J); return WFM_OK; }
+    if (K.streamed) { to_stream.push(J); return WFM_OK; }
+    const int rc = fetch_whole(J);
+    if (rc != WFM_OK) return rc;  // never queued: nobody will stitch it
+    work.push(Task{J, 0, -1});
+    return WFM_OK;
+  }
+  // the unstreamed form: the whole sequence's hashes into ordinary memory
+  int fetch_whole(SeqJob* J) {
+    J->norm.reset(new char[(size_t)J->len]);
+    J->hash.reset(new uint64_t[(size_t)J->nk]);
+    J->strand.reset(new int8_t[(size_t)J->nk]);
+    const int rc = map_hashed_fetch(&J->dev, 0, J->nk, 0, J->len, J->hash.get(), J->strand.get(), J->norm.get());
+    map_hashed_free(&J->dev);
+    J->on_device = false;
+    if (rc != WFM_OK) wfm_set_error(h, "device-to-host copy of k-mer hashes failed");
+    return rc;
+  }
+  // nothing more will be fed: device threads joined, lists closed (StageThreads has the order)
+  void close() {
+    threads.close_feed();
+    for (int64_t i = 0; i < nseq; ++i)
+      if (!jobs[(size_t)i]) cursor.mark_final(i);  // skipped, failed or never reached
+    t_fed = now_ms();
+  }
+
+  // ---- the calling thread: delivery and release ----
+  // finished sequences leave in input order while the later ones are still being worked on
+  void deliver_ready(int64_t limit) {
+    for (int64_t i; (i = cursor.take(limit)) >= 0;) deliver(i);
+  }
+  void drain() {
+    while (!cursor.done()) {
+      cursor.wait_next(window);
+      deliver_ready(nseq);
     }
   }
-  {
-    std::lock_guard<std::mutex> lk(mu);
-    dev_done = true;
-  }
-  cv_dev.notify_all();
-  for (auto& t : dev_threads) t.join();  // before the streamer is told that nothing more will come: the device may still hand sequences back
-  {
-    std::lock_guard<std::mutex> lk(mu);
-    hashed_done = true;
-    if (!streamed) done = true;
-  }
-  cv_hashed.notify_all();
-  cv_work.notify_all();
-  const auto t_fed = std::chrono::steady_clock::now();
-  {  // hand the sequences on in order as their stitches finish, while the later ones are still being stitched
-    std::unique_lock<std::mutex> lk(mu);
-    while (next_out < nseq) {
-      SeqJob* J = jobs[(size_t)next_out].get();
-      if (J && !J->stitched.load(std::memory_order_acquire)) { cv_room.wait(lk); continue; }  // a worker signals after every stitch
-      lk.unlock();
-      flush_ready(next_out + 1);
-      lk.lock();
+  void deliver(int64_t i) {
+    SeqJob* J = jobs[(size_t)i].get();
+    const int64_t n = J ? (J->d_result ? J->n_result : (int64_t)J->result.size()) : 0;
+    if (counts) counts[i] = n;
+    if (n && sink_rc == WFM_OK) sink_rc = J->d_result ? sink.put_device(J->d_result, n) : sink.put(J->result.data(), n);
+    total += n;
+    if (J) J->result.release();
+    if (J && J->d_result) {
+      // the sink's device-to-device copy runs on the null stream and need not be over when the call returns; the
+      // device thread's stream does not wait for the null stream, so the block must not go back to the pool before it is
+      if (hipStreamSynchronize(nullptr) != hipSuccess && sink_rc == WFM_OK) sink_rc = WFM_E_HIP;
+      map_dev_pool_put(wfm_device(h), J->d_result);
+      J->d_result = nullptr;
     }
   }
-  if (stream_thread.joinable()) stream_thread.join();
-  for (auto& t : pool) t.join();
-  release_stitched();
-  for (auto& J : jobs)
-    if (J) { if (J->on_device) { map_hashed_free(&J->dev); J->on_device = false; } map_sparse_free(&J->sparse); if (J->d_result) { map_dev_pool_put(wfm_device(h), J->d_result); J->d_result = nullptr; } }  // after an error
-  auto release_work = [hash_work, thin_work, winnow_works, finish_works]() mutable {
-    map_hash_work_free(&hash_work);
-    map_thin_work_free(&thin_work);
-    for (auto& wk : winnow_works) map_winnow_work_free(&wk);
-    for (auto& wk : finish_works) map_finish_work_free(&wk);
-    map_dev_pool_trim();
-  };
-  if (getenv("WFM_DEBUG") && (dev_seqs || dev_handed_back))
-    fprintf(stderr, "[wfm] winnowing on the device: %lld sequences in %lld chunks (WFM_WINNOW_DEV_CHUNK %lld), %lld chunks replayed after a failed speculation, %.1f ms (closing sort %s: %d levels at most, %lld ranges heap-sorted); %lld handed back to the host (why 0x%x)\n",
-            (long long)dev_seqs, (long long)dev_chunks, (long long)dev_chunk, (long long)dev_replays, ms_winnow, dev_finish ? "on the device" : "on the host", dev_levels, (long long)dev_heaps,
-            (long long)dev_handed_back, dev_why);
-  if (getenv("WFM_DEBUG")) {
+  static void release_arrays(SeqJob* J) {
+    if (J->on_device) { map_hashed_free(&J->dev); J->on_device = false; }
+    map_sparse_free(&J->sparse);
+  }
+  void release_stitched() {
+    std::vector<SeqJob*> list;
+    { std::lock_guard<std::mutex> lk(release_mu); list.swap(to_release); }
+    for (SeqJob* J : list) release_arrays(J);
+  }
+  // after the drain: the last threads, and whatever a sequence still holds (after an error)
+  void join_and_release() {
+    threads.join();
+    release_stitched();
+    for (auto& J : jobs) {
+      if (!J) continue;
+      release_arrays(J.get());
+      if (J->d_result) { map_dev_pool_put(wfm_device(h), J->d_result); J->d_result = nullptr; }
+    }
+  }
+  // the feeder's error first, then the first of the other threads'; the pipeline's own text goes to the handle here, from
+  // the calling thread after the joins
+  int result_code(int rc) {
+    if (rc != WFM_OK || err.code() == WFM_OK) return rc;
+    if (err.text()) wfm_set_error(h, err.text());
+    return err.code();
+  }
+
+  void report() const {
+    if (!K.debug) return;
+    if (dev_seqs || dev_handed_back)
+      fprintf(stderr, "[wfm] winnowing on the device: %lld sequences in %lld chunks (WFM_WINNOW_DEV_CHUNK %lld), %lld chunks replayed after a failed speculation, %.1f ms (closing sort %s: %d levels at most, %lld ranges heap-sorted); %lld handed back to the host (why 0x%x)\n",
+              (long long)dev_seqs, (long long)dev_chunks, (long long)K.dev_chunk, (long long)dev_replays, ms_winnow, K.dev_finish ? "on the device" : "on the host", dev_levels, (long long)dev_heaps,
+              (long long)dev_handed_back, dev_why);
     int64_t nchunks = 0, replays = 0;
     double stitch_max = 0;
     const SeqJob* slowest = nullptr;
@@ -1231,20 +1248,44 @@ int64_t add_minmers_core(wfm_handle_t* h, const char* const* seqs, const int64_t
       fprintf(stderr, "[wfm] longest stitch: compare %.1f, count %.1f, fill %.1f, sort %.1f, unique %.1f, release %.1f ms\n", slowest->ms_parts[0],
               slowest->ms_parts[1], slowest->ms_parts[2], slowest->ms_parts[3], slowest->ms_parts[4], slowest->ms_parts[5]);
     fprintf(stderr, "[wfm] add_minmers_multi: %lld sequences in %lld chunks (%lld replayed), %d workers, %s, %.1f %% of the k-mers kept: hashing thread %.1f ms (GPU hashing %.1f, thinning %.1f), drain %.1f ms (longest stitch %.1f)\n",
-            (long long)nseq, (long long)nchunks, (long long)replays, nthreads, streamed ? "streamed through the pinned ring" : "whole sequences",
-            thinned_kmers ? 100.0 * (double)kept_kmers / (double)thinned_kmers : 100.0,
-            std::chrono::duration<double, std::milli>(t_fed - t_start).count(), ms_hash, ms_thin,
-            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_fed).count(), stitch_max);
+            (long long)nseq, (long long)nchunks, (long long)replays, K.threads, K.streamed ? "streamed through the pinned ring" : "whole sequences",
+            thinned_kmers ? 100.0 * (double)kept_kmers / (double)thinned_kmers : 100.0, t_fed - t_start, ms_hash, ms_thin, now_ms() - t_fed, stitch_max);
   }
-  if (rc == WFM_OK && async_rc.load() != WFM_OK) {
-    rc = async_rc.load();
-    if (!async_msg_set.load()) wfm_set_error(h, "device-to-host streaming of k-mer hashes failed");
+};
+
+// later: (optional) receives the release of the device work buffers and of the block pool instead of it being done before
+// the return -- the caller that goes on to allocate gigabytes (the index) runs it afterwards: memory the driver has just
+// been handed back is scrubbed in the background, and an allocation that follows on its heels waits for that
+int64_t add_minmers_core(wfm_handle_t* h, const char* const* seqs, const int64_t* lens, const int32_t* seq_ids, int64_t nseq,
+                         int k, int w, int s, int threads, MinmerSink& sink, int64_t* counts, std::function<void()>* later = nullptr) {
+  if (!h || nseq < 0 || (nseq && (!seqs || !lens || !seq_ids))) return WFM_E_ARG;
+  if (k < 1 || k > 32 || w < k || s < 1) { wfm_set_error(h, "need 1 <= k <= 32, w >= k, s >= 1"); return WFM_E_UNSUPPORTED; }
+  const SketchKnobs K = SketchKnobs::read(threads, k, w, s);
+  MapStage* stage = nullptr;
+  if (K.streamed) {
+    const int src = map_stage_acquire(h, K.slot_bytes, K.nslots, &stage);
+    if (src != WFM_OK) return src;
   }
-  if (rc != WFM_OK) { release_work(); return rc; }
-  flush_ready(nseq);  // (the records of the last sequences leave their pooled blocks here)
-  if (later) *later = release_work; else release_work();
-  if (sink_rc != WFM_OK) return sink_rc;
-  return total;
+  SketchRun run(h, K, k, w, s, stage, sink, counts, nseq);  // (its threads are joined on every way out of here)
+  int rc = WFM_OK;
+  try {  // whatever the feeder throws, the call closes, drains, joins and releases as after any other error
+    run.start();
+    for (int64_t i = 0; i < nseq && rc == WFM_OK; ++i) rc = run.feed_one(i, seqs[i], lens[i], seq_ids[i]);
+  } catch (const std::exception& e) {
+    const bool nomem = dynamic_cast<const std::bad_alloc*>(&e) != nullptr;
+    std::lock_guard<std::mutex> g(run.gpu_mu);
+    wfm_set_error(h, nomem ? "out of host memory (sketch pipeline)" : e.what());
+    rc = nomem ? WFM_E_NOMEM : WFM_E_HIP;
+  }
+  run.close();
+  run.drain();  // in order as the stitches finish, while the later ones are still being stitched
+  run.join_and_release();
+  run.report();
+  rc = run.result_code(rc);
+  if (rc != WFM_OK) { run.work_bufs(); return rc; }
+  if (later) *later = run.work_bufs; else run.work_bufs();
+  if (run.sink_rc != WFM_OK) return run.sink_rc;
+  return run.total;
 }
 
 // records into the caller's array, as far as it goes
@@ -1393,21 +1434,7 @@ extern "C" int64_t wfmh_test_winnow_chunked(const char* seq, int64_t len, int k,
                                             const int8_t* strand, int64_t chunk_len, wfm_minmer_t* out, int64_t cap, int* replays) {
   if (len < k) return 0;
   SeqJob J;
-  J.seq_id = seq_id; J.len = len; J.nk = len - k + 1; J.k = k; J.w = w; J.s = s;
-  J.sort_threads = 4;
-  J.norm.reset(new char[(size_t)len]);
-  memcpy(J.norm.get(), seq, (size_t)len);
-  normalise(J.norm.get(), len);
-  J.hash.reset(new uint64_t[(size_t)J.nk]);
-  J.strand.reset(new int8_t[(size_t)J.nk]);
-  memcpy(J.hash.get(), hash, (size_t)J.nk * 8);
-  memcpy(J.strand.get(), strand, (size_t)J.nk);
-  J.bounds.assign(1, 0);
-  if (chunk_len > 0)
-    for (int64_t b = chunk_len; b < J.nk; b += chunk_len) J.bounds.push_back(b);
-  J.bounds.push_back(J.nk);
-  J.chunk.resize(J.bounds.size() - 1);
-  J.started_from.resize(J.bounds.size() - 1);
+  J.load_host(seq, len, k, w, s, seq_id, hash, strand, chunk_len);
   for (size_t c = 0; c + 1 < J.bounds.size(); ++c) { SeqJob::View v; v.d = J.whole(); J.run_chunk(c, v); }
   J.stitch();
   if (replays) *replays = J.replays;
@@ -1437,36 +1464,21 @@ extern "C" int64_t wfmh_test_winnow_thinned(const char* seq, int64_t len, int k,
                                             uint32_t* kept_pos, int64_t cap_kept, int64_t* n_kept, int* replays) {
   if (len < k) return 0;
   SeqJob J;
-  J.seq_id = seq_id; J.len = len; J.nk = len - k + 1; J.k = k; J.w = w; J.s = s;
-  J.sort_threads = 4;
+  J.load_host(seq, len, k, w, s, seq_id, hash, strand, chunk_len);
   const int64_t n = J.nk, W = (int64_t)w - k + 1;
-  J.norm.reset(new char[(size_t)len]);
-  memcpy(J.norm.get(), seq, (size_t)len);
-  normalise(J.norm.get(), len);
-  J.hash.reset(new uint64_t[(size_t)n]);
-  J.strand.reset(new int8_t[(size_t)n]);
-  memcpy(J.hash.get(), hash, (size_t)n * 8);
-  memcpy(J.strand.get(), strand, (size_t)n);
   thin_on_host(hash, strand, n, W, s, map_prefilter_tau(c_factor, s, W), J.h_pos, J.h_hash, J.h_strand);
   if (n_kept) *n_kept = (int64_t)J.h_pos.size();
   for (size_t i = 0; kept_pos && i < J.h_pos.size() && (int64_t)i < cap_kept; ++i) kept_pos[i] = J.h_pos[i];
   J.thinned = true;
   J.head.assign(J.norm.get(), (size_t)std::min<int64_t>(len, 2 * (int64_t)k));
-  J.bounds.assign(1, 0);
-  if (chunk_len > 0)
-    for (int64_t b = chunk_len; b < n; b += chunk_len) J.bounds.push_back(b);
-  J.bounds.push_back(n);
   const size_t nc = J.bounds.size() - 1;
-  J.chunk.resize(nc);
-  J.started_from.resize(nc);
   auto before = [&](int64_t x) { return (int64_t)(std::lower_bound(J.h_pos.begin(), J.h_pos.end(), x, [](uint32_t p, int64_t v) { return (int64_t)p < v; }) - J.h_pos.begin()); };
   for (size_t c = 0; c <= nc; ++c) J.cidx.push_back(before(J.bounds[c]));
   for (size_t c = 0; c < nc; ++c) J.cidx_warm.push_back(before(J.warm_from(c)));
-  static const uint32_t none = 0;
   for (size_t c = 0; c < nc; ++c) {
     SeqJob::View v;
     const int64_t c0 = J.cidx_warm[c], c1 = J.cidx[c + 1];
-    v.sp.pos = J.h_pos.empty() ? &none : J.h_pos.data() + c0; v.sp.hash = J.h_hash.data() + c0; v.sp.strand = J.h_strand.data() + c0; v.sp.n = (size_t)(c1 - c0);
+    v.sp.pos = J.h_pos.empty() ? &kNoKmer : J.h_pos.data() + c0; v.sp.hash = J.h_hash.data() + c0; v.sp.strand = J.h_strand.data() + c0; v.sp.n = (size_t)(c1 - c0);
     J.run_chunk(c, v);
   }
   J.stitch();
@@ -1501,8 +1513,8 @@ extern "C" int64_t wfmh_test_winnow_model(const char* seq, int64_t len, int k, i
   std::vector<uint32_t> pos; std::vector<uint64_t> hs; std::vector<int8_t> st;
   thin_on_host(hash, strand, n, W, s, map_prefilter_tau(c_factor, s, W), pos, hs, st);
   std::vector<wfm_minmer_t> recs;
-  static const uint32_t none_p = 0; static const uint64_t none_h = 0; static const int8_t none_s = 0;
-  const int64_t got = map_winnow_model(pos.empty() ? &none_p : pos.data(), hs.empty() ? &none_h : hs.data(), st.empty() ? &none_s : st.data(),
+  static const uint64_t none_h = 0; static const int8_t none_s = 0;
+  const int64_t got = map_winnow_model(pos.empty() ? &kNoKmer : pos.data(), hs.empty() ? &none_h : hs.data(), st.empty() ? &none_s : st.data(),
                                        (int64_t)pos.size(), len, k, w, s, seq_id, chunk_len, &recs, why, force_replay, nullptr);
   if (got < 0) return -1;
   finish_records(recs, w, 1);
