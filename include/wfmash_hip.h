@@ -124,7 +124,8 @@ typedef struct {
 
 typedef struct {
   int32_t  status;     /* WFM_ST_*                                             */
-  int32_t  score;      /* gap-affine-2p penalty of the returned alignment      */
+  int32_t  score;      /* gap-affine-2p penalty of the returned alignment; ENDSFREE: the ends-free score (the free
+                        * parts of the op string's first and last gap cost nothing), what alignEndsFree reports      */
   uint64_t ops_off;    /* offset of this problem's op string in ops_arena (wfm_align_batch_rle: index of its first run) */
   uint32_t ops_len;    /* number of ops over {M,X,I,D}; I = text-only, D = pattern-only */
   uint32_t n_runs;     /* number of run-length encoded CIGAR runs             */

@@ -4,7 +4,7 @@ sequences, very unequal lengths; BiWFA end-to-end and the two ends-free patch fo
 CPU oracle (oracle/wfa2p.c; its calls run on a thread pool, ctypes releases the GIL).  A tool for a GPU box beside the suite (it lives under tests/ because it calls the oracle; pytest does not collect it):
 the suite's own cases came out of runs like this one.
 
-Usage: python tests/fuzz_align.py [--rounds 20] [--items 240] [--seed 1] [--max-len 9000] [--threads N]
+Usage: python tests/fuzz_align.py [--rounds 20] [--items 240] [--seed 1] [--max-len 9000] [--threads N] [--pens] [--general-free]
 Prints one line per round and a JSON summary; exit code 1 if anything differs (the failing problems are written to --dump as FASTA-like text)."""
 import argparse
 import json
@@ -80,13 +80,22 @@ def gen_pair(rng, k, max_len):
     return p, t
 
 
-def run(rounds=20, items=240, seed=1, max_len=9000, threads=None, pens=False, dump="", quiet=False):
-    """the campaign; returns {"problems", "differ", "failed", ...}"""
+def draw_free(rng, plen, tlen):
+    """a general tuple (pbf, pef, tbf, tef): each length nothing, everything, a few bases or anything up to its sequence's length"""
+    def one(n):
+        return rng.choice([0, n, rng.randrange(0, min(n, 8) + 1), rng.randrange(0, n + 1)])
+    return (one(plen), one(plen), one(tlen), one(tlen))
+
+
+def run(rounds=20, items=240, seed=1, max_len=9000, threads=None, pens=False, dump="", quiet=False, general_free=False):
+    """the campaign; returns {"problems", "differ", "failed", ...}.  general_free: the ends-free problems take four independent free
+    lengths (draw_free) instead of the two patch forms, empty and one-base sides stay with them, and their scores are compared as well
+    (off by default: the random streams of the seeds in use stay as they are)"""
     threads = threads or min(64, os.cpu_count() or 1)
     pyoracle.lib()
     h = capi.Handle(0)
     pool = ThreadPoolExecutor(threads)
-    total = bad = failed = 0
+    total = bad = failed = n_ef = 0
     t_gpu = t_cpu = 0.0
     dumped = []
     for rnd in range(rounds):
@@ -99,11 +108,14 @@ def run(rounds=20, items=240, seed=1, max_len=9000, threads=None, pens=False, du
         for k in range(items):
             p, t = gen_pair(rng, rng.randrange(0, 12), max_len)
             mode = rng.random()
-            if mode < 0.7 or not p or not t or max(len(p), len(t)) > 4000:
+            if mode < 0.7 or (not general_free and (not p or not t)) or max(len(p), len(t)) > 4000:
                 batch.append((p, t))
                 calls.append(("bi", p, t))
-            else:  # the patch forms of do_biwfa_alignment: free beginnings (head) or free ends (tail)
+            else:  # the patch forms of do_biwfa_alignment: free beginnings (head) or free ends (tail); or any four lengths
                 args = (len(p), 0, len(t), 0) if mode < 0.85 else (0, len(p), 0, len(t))
+                if general_free:
+                    args = draw_free(rng, len(p), len(t))
+                n_ef += 1
                 batch.append((p, t, capi.WFM_MODE_ENDSFREE) + args)
                 calls.append(("ef", p, t) + args)
         t0 = time.time()
@@ -124,7 +136,7 @@ def run(rounds=20, items=240, seed=1, max_len=9000, threads=None, pens=False, du
                 continue  # (the oracle itself gave up: not a parity statement)
             if r.status != 0:
                 rf += 1
-            elif r.ops != ops or (c[0] == "bi" and r.score != sc):
+            elif r.ops != ops or ((c[0] == "bi" or general_free) and r.score != sc):
                 rb += 1
             else:
                 continue
@@ -139,7 +151,7 @@ def run(rounds=20, items=240, seed=1, max_len=9000, threads=None, pens=False, du
     if dumped and dump:
         with open(dump, "w") as f:
             json.dump(dumped, f)
-    return {"problems": total, "differ": bad, "failed": failed, "seed": seed, "rounds": rounds, "items": items, "max_len": max_len}
+    return {"problems": total, "endsfree": n_ef, "differ": bad, "failed": failed, "seed": seed, "rounds": rounds, "items": items, "max_len": max_len}
 
 
 def main():
@@ -151,8 +163,9 @@ def main():
     ap.add_argument("--threads", type=int, default=min(64, os.cpu_count() or 1))
     ap.add_argument("--dump", default="")
     ap.add_argument("--pens", action="store_true", help="a penalty set per round (mismatch, o1, e1, o2, e2) drawn from sets within the supported scope instead of the defaults")
+    ap.add_argument("--general-free", action="store_true", help="four independent free lengths for the ends-free problems (empty and one-base sides included), their scores compared as well")
     a = ap.parse_args()
-    out = run(a.rounds, a.items, a.seed, a.max_len, a.threads, a.pens, a.dump)
+    out = run(a.rounds, a.items, a.seed, a.max_len, a.threads, a.pens, a.dump, general_free=a.general_free)
     print(json.dumps(out))
     sys.exit(1 if out["differ"] or out["failed"] else 0)
 

@@ -264,8 +264,8 @@ def _three_forms_batch(oracle):
     """(items, expected): 39 problems of 1 to 1500 bases for the three forms of the base kernels -- patches in head and tail form whose rows stay
     under 128 diagonals (one wave) or pass them (the mailbox; tiles under WFM_BASE_TILES=2) and whose scores fall below 125, between 125 and 250 and
     beyond (a tile block is 125 scores), BiWFA pairs with a 30 - 900 base gap (leaves that begin and end inside a gap component), plain pairs, an
-    empty side each way, and three of the problems once more as score-only.  expected: (score, ops) -- score None for the patches (the device reports the
-    penalty of the whole patch, free ends included; the tests of the patches compare ops), ops None for the score-only problems."""
+    empty side each way, and three of the problems once more as score-only.  expected: (score, ops) -- the ends-free score for the patches (free end gaps cost
+    nothing), ops None for the score-only problems."""
     rng = random.Random(28)
     items, exp = [], []
     for i, (L, div) in enumerate([(1, 0.0), (40, 0.1), (60, 0.3), (130, 0.05), (130, 0.2), (400, 0.1), (400, 0.25), (900, 0.04), (1500, 0.02)]):
@@ -275,9 +275,9 @@ def _three_forms_batch(oracle):
             t = synth.random_dna(6300 + i, 25) + t
         for args in ((len(p), 0, len(t), 0), (0, len(p), 0, len(t))):  # head form, tail form
             items.append((p, t, capi.WFM_MODE_ENDSFREE, args[0], args[1], args[2], args[3]))
-            rc, ops, _, _ = oracle.align_endsfree(p, args[0], args[1], t, args[2], args[3])
+            rc, ops, sc, _ = oracle.align_endsfree(p, args[0], args[1], t, args[2], args[3])
             assert rc == 0
-            exp.append((None, ops))
+            exp.append((sc, ops))
     pairs = []
     for i, gap in enumerate([30, 300, 900, 30, 300, 900, 120, 600]):
         a = synth.random_dna(6400 + i, rng.choice([400, 600]))

@@ -18,6 +18,10 @@ def test_align_campaign_two_rounds():
     assert out["problems"] == 320 and out["differ"] == 0 and out["failed"] == 0, out
     out = fuzz_align.run(rounds=2, items=120, seed=8, max_len=2500, pens=True, quiet=True)
     assert out["differ"] == 0 and out["failed"] == 0, out
+    # general free lengths for the ends-free problems (empty and one-base sides among them), their scores compared too
+    out = fuzz_align.run(rounds=1, items=160, seed=9, max_len=2500, general_free=True, quiet=True)
+    assert out["differ"] == 0 and out["failed"] == 0, out
+    assert out["endsfree"] >= 30, out
 
 
 def test_map_campaign_two_rounds():

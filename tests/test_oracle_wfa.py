@@ -8,6 +8,7 @@ import random
 
 import pytest
 
+import endsfree_cases
 from wfmash_amd import synth
 
 
@@ -62,6 +63,37 @@ def test_endsfree_scores_match_dp(oracle):
             rc, ops, sc, _ = oracle.align_endsfree(p, args[0], args[1], t, args[2], args[3])
             assert rc == 0 and sc == dp
             assert oracle.ops_check(ops, p, t) == 0
+
+
+@pytest.mark.parametrize("pen", endsfree_cases.PENS, ids=lambda p: "default" if p is None else "-".join(map(str, p)))
+def test_endsfree_general_free_lengths_match_dp(oracle, pen):
+    """The four free lengths as independent values (tests/endsfree_cases.py: partial lengths, one free end alone, begin and end free at
+    once, empty sides): the oracle's score is the O(nm) DP's, its op string spans both sequences, and the string priced on its own
+    (endsfree_price: no code of the oracle's) costs exactly that score.  Every case is asserted."""
+    cases = endsfree_cases.build_cases()
+    assert len(cases) >= 350
+    some_gap_free = 0
+    for c in cases:
+        dp = oracle.dp_score_endsfree(c.p, c.t, *c.free, pen=pen)
+        rc, ops, sc, _ = oracle.align_endsfree(c.p, c.free[0], c.free[1], c.t, c.free[2], c.free[3], pen=pen)
+        assert rc == 0, (c.name, c.free)
+        assert sc == dp, (c.name, c.free, sc, dp)
+        assert oracle.ops_check(ops, c.p, c.t) == 0, (c.name, c.free)
+        assert endsfree_cases.endsfree_price(ops, c.free, pen) == sc, (c.name, c.free, sc)
+        some_gap_free += oracle.ops_score(ops, pen) != sc
+    assert some_gap_free * 3 >= len(cases)  # (the family is about free gaps: a third of it at least uses one)
+
+
+def test_endsfree_price_on_hand_made_strings():
+    price = endsfree_cases.endsfree_price
+    assert price(b"IIIIIIIIII", (0, 0, 4, 3)) == 8 + 2 * 3  # one run: both allowances of its side
+    assert price(b"IIIIIIIIII", (0, 0, 10, 0)) == 0 and price(b"IIIIIIIIII", (0, 0, 6, 6)) == 0
+    assert price(b"IIIIIIIIII", (4, 3, 0, 0)) == 8 + 2 * 10  # (the pattern's allowances do not free text bases)
+    assert price(b"DDDMMXMMII", (2, 0, 9, 1)) == (8 + 2 * 1) + 5 + (8 + 2 * 1)
+    assert price(b"DDDIII", (3, 0, 0, 3)) == 0 and price(b"DDDIII", (0, 3, 3, 0)) == 2 * (8 + 2 * 3)  # begin-free I behind a D: not leading
+    assert price(b"MMIDMM", (9, 9, 9, 9)) == 2 * (8 + 2)  # gaps inside are paid
+    assert price(b"D" * 40 + b"M", (10, 0, 0, 0)) == 24 + 30 and price(b"", (1, 1, 1, 1)) == 0
+    assert price(b"XDD", (0, 1, 0, 0), (4, 6, 2, 12, 1)) == 4 + 6 + 2
 
 
 def test_component_halves_concatenate(oracle):

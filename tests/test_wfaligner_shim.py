@@ -31,10 +31,37 @@ int main(int argc, char** argv) {
 '''
 
 
-def _build(tmp_path):
-    src = tmp_path / "shim_user.cpp"
-    src.write_text(SRC)
-    exe = tmp_path / "shim_user"
+# alignEndsFree with any four free lengths, in both scopes: per scope one line "status score ops_len", then the status under each limit
+SRC_ENDSFREE = r'''
+#include <cstdio>
+#include <cstdlib>
+#include <string>
+#include "wfmash_amd/host/WFAligner.hpp"
+int main(int argc, char** argv) {
+  if (argc < 7) return 1;
+  std::string pattern = argv[1], text = argv[2];
+  const int pbf = atoi(argv[3]), pef = atoi(argv[4]), tbf = atoi(argv[5]), tef = atoi(argv[6]);
+  const wfa::WFAligner::AlignmentScope scopes[2] = {wfa::WFAligner::Alignment, wfa::WFAligner::Score};
+  for (int s = 0; s < 2; ++s) {
+    wfa::WFAlignerGapAffine2Pieces a(0, 5, 8, 2, 24, 1, scopes[s], wfa::WFAligner::MemoryMed);
+    a.setHeuristicNone();
+    const int st = a.alignEndsFree(pattern, pbf, pef, text, tbf, tef);
+    printf("%d %d %d\n", st, a.getAlignmentScore(), (int)a.getAlignment().size());
+    for (int i = 7; i < argc; ++i) {
+      a.setMaxAlignmentSteps(atoi(argv[i]));
+      const int lst = a.alignEndsFree(pattern, pbf, pef, text, tbf, tef);
+      printf("%d %d\n", lst, a.getAlignmentStatus());
+    }
+  }
+  return 0;
+}
+'''
+
+
+def _build(tmp_path, text=SRC, name="shim_user"):
+    src = tmp_path / (name + ".cpp")
+    src.write_text(text)
+    exe = tmp_path / name
     subprocess.check_call(["g++", "-O1", "-std=c++17", "-I" + ROOT, str(src), "-o", str(exe),
                            "-L" + os.path.join(ROOT, "wfmash_amd"), "-lwfmash_hip",
                            "-Wl,-rpath," + os.path.join(ROOT, "wfmash_amd")])
@@ -43,6 +70,31 @@ def _build(tmp_path):
 
 def test_shim_compiles_and_links(tmp_path):
     _build(tmp_path)
+    _build(tmp_path, SRC_ENDSFREE, "shim_endsfree")
+
+
+@pytest.mark.gpu
+def test_shim_endsfree_score_and_step_limit_are_the_same_in_both_scopes(tmp_path, oracle):
+    """alignEndsFree with partial free lengths: getAlignmentScore() is minus the oracle's ends-free score in Alignment and in Score scope,
+    and setMaxAlignmentSteps means the same in both -- a limit between the ends-free score and the price of the op string's runs (which
+    counts the free end gaps) lets the call complete, a limit below the ends-free score ends it WF_STATUS_MAX_STEPS_REACHED."""
+    from wfmash_amd import synth
+    import endsfree_cases
+    core = synth.random_dna(0x5A1, 300)
+    p = core
+    t = synth.random_dna(0x5A2, 80) + synth.mutate(core, 0.05, 0x5A3) + synth.random_dna(0x5A4, 60)
+    free = (0, 0, 90, 50)  # the junk in front is covered, ten bases of the junk behind are paid
+    rc, ops, sc, _ = oracle.align_endsfree(p, free[0], free[1], t, free[2], free[3])
+    assert rc == 0 and sc == oracle.dp_score_endsfree(p, t, *free) == endsfree_cases.endsfree_price(ops, free)
+    by_runs = oracle.ops_score(ops)
+    assert 0 < sc < by_runs - 1
+    between, below = (sc + by_runs) // 2, sc - 1
+    exe = _build(tmp_path, SRC_ENDSFREE, "shim_endsfree")
+    out = subprocess.check_output([exe, p.decode(), t.decode()] + [str(x) for x in free + (between, sc, below)]).decode().split("\n")
+    for scope, lines in (("Alignment", out[0:4]), ("Score", out[4:8])):
+        assert lines[0] == "0 %d %d" % (-sc, len(ops) if scope == "Alignment" else 0), (scope, lines[0], sc, by_runs)
+        assert lines[1] == "0 0" and lines[2] == "0 0", (scope, lines)  # within the limit, and exactly at it
+        assert lines[3] == "-100 -100", (scope, lines)
 
 
 @pytest.mark.gpu

@@ -537,8 +537,15 @@ void settle_base_chunk(BaseChunk& c) {
     h->stats.cells_base += r.cells;
     if (c.pflags && (c.kind == 3 || c.kind == 4) && c.jobs[q].type == 0) c.pflags[nd.prob] |= WFM_PF_RING_KERNEL;
     if (c.pflags && c.kind == 5) c.pflags[nd.prob] |= WFM_PF_BASE_TILES;
-    if (r.status == 0 && c.jobs[q].score_only)  // (the all-gap jobs report no score of their own: theirs is the gap's)
-      c.prob_score[nd.prob] = c.jobs[q].type == 0 ? r.score : gapcost(pen, nd.pl) + gapcost(pen, nd.tl);
+    // The score of a problem whose root is this job: a score-only problem's, and an ends-free problem's either way (what its op string
+    // costs run by run counts the free end gaps as well; the job's own score does not).  The all-gap jobs report no score of their own:
+    // theirs is the gap's -- of an ends-free problem, what its side's two free lengths leave of it
+    if (r.status == 0 && (c.jobs[q].score_only || nd.endsfree)) {
+      const ProbMeta& pm = c.S->meta[nd.prob];
+      const int all_gap = nd.endsfree ? gapcost(pen, nd.pl - pm.pbf - pm.pef) + gapcost(pen, nd.tl - pm.tbf - pm.tef)
+                                      : gapcost(pen, nd.pl) + gapcost(pen, nd.tl);
+      c.prob_score[nd.prob] = c.jobs[q].type == 0 ? r.score : all_gap;
+    }
     if (r.status == WFM_DEV_OVERFLOW && nd.limit > 0 && nd.smax >= nd.limit) {  // the budget was the problem's hard limit: final
       c.prob_status[nd.prob] = WFM_ST_MAX_SCORE; continue;
     }
@@ -1371,7 +1378,7 @@ void make_roots(AlignCall& c) {
     nd.prob = (int32_t)i; nd.pb = 0; nd.pl = pm.plen; nd.tb = 0; nd.tl = pm.tlen;
     nd.cb = C_M; nd.ce = C_M; nd.score_rem = INT_MAX; nd.endsfree = 0;
     nd.sub = SUB_NONE; nd.hinted = 0;
-    if (c.pflags && pm.mode == WFM_MODE_END2END_BIWFA && !((size_t)i < c.S->acgt.size() && c.S->acgt[i])) c.pflags[i] |= WFM_PF_BYTE_KERNEL;
+    if (c.pflags && (pm.mode == WFM_MODE_END2END_BIWFA || pm.mode == WFM_MODE_ENDSFREE) && !((size_t)i < c.S->acgt.size() && c.S->acgt[i])) c.pflags[i] |= WFM_PF_BYTE_KERNEL;
     if (c.knobs.use_hints && pm.hint > 0 && pm.mode == WFM_MODE_END2END_BIWFA) { nd.sub = pm.hint; nd.hinted = 1; }
     // a hard limit of the score is the root's bound whatever the switches say about guesses (bound_roots may still lower it: its bound is rigorous)
     if (pm.limit > 0) { nd.limit = pm.limit; nd.sub = pm.limit; nd.hinted = 1; }
@@ -2040,7 +2047,8 @@ int write_results(AlignCall& c, const GatheredRuns& g, uint64_t* cells_total) {
       ++failed;
       continue;
     }
-    r.ops_len = ex.ops_len; r.n_runs = ex.n_runs; r.score = ex.score;
+    // (the runs' own price is the score of an end-to-end alignment; an ends-free problem reports its base job's score, full or score-only)
+    r.ops_len = ex.ops_len; r.n_runs = ex.n_runs; r.score = pm.mode == WFM_MODE_ENDSFREE ? c.prob_score[gi] : ex.score;
     arena_pos = runs_out ? runs_out->size() : arena_pos + ex.ops_len;
   }
   return failed;
