@@ -303,7 +303,10 @@ enum {
   WFM_TC_REUSE_RESUMED = 8,   /* jobs whose outer direction went on from rows their parent kept (parent reuse)                    */
   WFM_TC_REUSE_FALLBACKS = 9, /* jobs that came with such rows and gave them up: they ran (or were run again) from score 0           */
   WFM_TC_REUSE_KEEPS = 10,    /* snapshots of one direction written to the store of kept rows                                        */
-  WFM_TILE_COUNTERS = 11
+  /* the fallbacks by cause (the two add up to WFM_TC_REUSE_FALLBACKS): */
+  WFM_TC_REUSE_TOUCHED = 11,  /* the restore found a kept cell on the job's box or beyond it (v >= hmax_c(k) - WFM_REUSE_TOUCH_SLACK)    */
+  WFM_TC_REUSE_FELL_OTHER = 12, /* any other cause: the maxima fired while one direction waited, the job met right behind the restore ... */
+  WFM_TILE_COUNTERS = 13
 };
 size_t wfm_get_tile_counters(const wfm_handle_t* h, uint64_t* out, size_t n);
 

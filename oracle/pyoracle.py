@@ -68,6 +68,8 @@ def lib():
         L.wfo_find_breakpoint_bounded.argtypes = [cp, ci, cp, ci, PP, ci, ci, ci, C.POINTER(Breakpoint), SP]
         L.wfo_meet_point.restype = ci
         L.wfo_meet_point.argtypes = [cp, ci, cp, ci, PP, ci, ci, C.POINTER(C.c_int32)]
+        L.wfo_forward_rows.restype = ci
+        L.wfo_forward_rows.argtypes = [cp, ci, cp, ci, PP, ci, ci, C.c_void_p, ci, ci, ci, C.c_void_p, C.c_void_p]
         L.wfo_ops_score.restype = C.c_int64
         L.wfo_ops_score.argtypes = [cp, ci, PP]
         L.wfo_ops_check.restype = ci
@@ -159,6 +161,30 @@ def meet_point(pattern: bytes, text: bytes, pen=None, comp_begin=0, comp_end=0):
     if rc < 0:
         raise RuntimeError("wfo_meet_point: status %d" % rc)
     return int(m[0]), int(m[1]), int(m[2])
+
+
+ROWS = 26                    # WFO_ROWS: the scores score - 25 .. score
+ROW_NULL = -(1 << 30)        # WFO_NULL
+
+
+def forward_rows(pattern: bytes, text: bytes, score, comp_begin=0, sub=-1, pen=None):
+    """the unidirectional forward wavefronts at the scores score - 25 .. score (wfo_forward_rows) -> (kmin, offsets, ranges):
+    offsets[c, back, k - kmin] is component c at score `score - back` on diagonal k (ROW_NULL: nothing there), over the
+    diagonals -min(plen, score) .. min(tlen, score); ranges[c, back] = (lo, hi) of the row, lo > hi: no row.  sub >= 0: rows
+    cut as find_breakpoint_bounded cuts them.  A reverse direction: both sequences reversed.  `score` may be an ascending
+    list: one pass, the arrays get a leading axis over the scores and the window is the last score's."""
+    p = _pen(pen)
+    many = not isinstance(score, (int, np.integer))
+    sc = np.array(score if many else [score], dtype=np.int32)
+    kmin, kmax = -min(len(pattern), int(sc[-1])), min(len(text), int(sc[-1]))
+    n = kmax - kmin + 1
+    off = np.empty((len(sc), 5, ROWS, n), dtype=np.int32)
+    rng = np.empty((len(sc), 5, ROWS, 2), dtype=np.int32)
+    rc = lib().wfo_forward_rows(pattern, len(pattern), text, len(text), C.byref(p), comp_begin, sub, sc.ctypes.data, len(sc),
+                                kmin, n, off.ctypes.data, rng.ctypes.data)
+    if rc < 0:
+        raise RuntimeError("wfo_forward_rows: status %d" % rc)
+    return (kmin, off, rng) if many else (kmin, off[0], rng[0])
 
 
 def ops_score(ops: bytes, pen=None) -> int:

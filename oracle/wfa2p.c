@@ -771,6 +771,43 @@ int wfo_meet_point(const char* pattern, int plen, const char* text, int tlen,
   return find_breakpoint_sub(pattern, plen, text, tlen, pen, comp_begin, comp_end, &bp, NULL, 0, 0, 0, NULL, meet);
 }
 
+int wfo_forward_rows(const char* pattern, int plen, const char* text, int tlen,
+                     const wfo_penalties_t* pen, int comp_begin, int sub, const int32_t* scores, int nscores,
+                     int kmin, int ncols, int32_t* offsets, int32_t* ranges) {
+  al_t a;
+  if (nscores <= 0 || ncols <= 0 || scores[0] < 0) return ST_UNREACHABLE;
+  for (int i = 1; i < nscores; ++i) if (scores[i] <= scores[i - 1]) return ST_UNREACHABLE;
+  int rc = al_init(&a, pattern, plen, text, tlen, pen, 1, 0, NULL);
+  if (rc != ST_OK) { al_free(&a); return rc; }
+  if (a.scope < WFO_ROWS) { al_free(&a); return ST_UNREACHABLE; }  /* the modular store holds `scope` scores */
+  a.comp_begin = comp_begin; a.comp_end = WFO_M;
+  a.bounded = sub >= 0; a.sub = sub >= 0 ? sub : 0;
+  rc = init_wavefronts(&a);
+  /* the search's own steps: extend s, compute s + 1 from the extended rows (no termination test: the rows go on past the end cell) */
+  if (rc == ST_OK) extend_step(&a, 0, NULL, 0);
+  for (int s = 0, i = 0; rc == ST_OK && i < nscores; ++s) {
+    if (s > 0) {
+      rc = compute_step(&a, s);
+      if (rc == ST_OK) extend_step(&a, s, NULL, 0);
+    }
+    if (rc != ST_OK || s != scores[i]) continue;
+    for (int c = 0; c < 5; ++c)
+      for (int back = 0; back < WFO_ROWS; ++back) {
+        const size_t r = ((size_t)i * 5 + (size_t)c) * WFO_ROWS + (size_t)back;
+        int32_t* row = offsets + r * (size_t)ncols;
+        for (int x = 0; x < ncols; ++x) row[x] = WF_NULL;
+        ranges[2 * r] = 1; ranges[2 * r + 1] = 0;  /* no row */
+        const wf_t* w = get_wf(&a, c, s - back);
+        if (!w || w->lo > w->hi) continue;
+        ranges[2 * r] = w->lo; ranges[2 * r + 1] = w->hi;
+        for (int k = MAXI(w->lo, kmin); k <= MINI(w->hi, kmin + ncols - 1); ++k) row[k - kmin] = w->off[k] < 0 ? WF_NULL : w->off[k];
+      }
+    ++i;
+  }
+  al_free(&a);
+  return rc;
+}
+
 int wfo_align_end2end_biwfa(const char* pattern, int plen, const char* text, int tlen,
                             const wfo_penalties_t* pen, char* ops_out, int* nops, int* score, wfo_stats_t* stats) {
   int rc;

@@ -123,6 +123,21 @@ int wfo_find_breakpoint_rounds(const char* pattern, int plen, const char* text, 
 int wfo_meet_point(const char* pattern, int plen, const char* text, int tlen,
                    const wfo_penalties_t* pen, int comp_begin, int comp_end, int32_t* meet);
 
+/* The rows of ONE direction on its own: the unidirectional forward wavefronts that begin in component comp_begin, by the
+ * recurrences and the extension the breakpoint search uses (M rows as they stand after their extension).  For each of the
+ * nscores scores of `scores` (ascending; one pass serves them all) the WFO_ROWS rows of the scores score - (WFO_ROWS - 1)
+ * .. score.  sub >= 0: rows cut as wfo_find_breakpoint_bounded cuts them, |k - (tlen - plen)| <= sub - s; sub < 0: no
+ * bound.  A reverse direction is the same call on both sequences reversed.  With r = (i * 5 + c) * WFO_ROWS + back:
+ *   offsets[r * ncols + (k - kmin)]: component c at score scores[i] - back on diagonal k, for the window kmin ..
+ *     kmin + ncols - 1; WFO_NULL where the row does not hold k, holds no offset there, or the score is negative
+ *   ranges[2 * r + {0, 1}]: the row's [lo, hi] after trimming; lo > hi: no row
+ * Returns 0, < 0 on error. */
+#define WFO_ROWS 26
+#define WFO_NULL (INT32_MIN / 2)
+int wfo_forward_rows(const char* pattern, int plen, const char* text, int tlen,
+                     const wfo_penalties_t* pen, int comp_begin, int sub, const int32_t* scores, int nscores,
+                     int kmin, int ncols, int32_t* offsets, int32_t* ranges);
+
 /* Score implied by an op string under the reference's cost model
  * (wflign_alignment.cpp:680-722: a gap run of length L costs
  * o1+e1+min(e1*(L-1), o2+e2*(L-1)) ... note this equals min(o1+L*e1,o2+o1... )

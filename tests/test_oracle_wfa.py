@@ -310,3 +310,52 @@ def test_meet_point_against_the_breakpoint(oracle):
         assert (bp.score_forward >= sf and bp.score_reverse > sr - scope) or (bp.score_reverse >= sr and bp.score_forward > sf - scope), \
             (sf, sr, bp.score_forward, bp.score_reverse)
     assert n >= 180
+
+
+def _all_rows(oracle, p, t, upto, **kw):
+    """{(component, score): {k: offset}} of forward_rows for every score 0 .. upto, from calls 26 scores apart (one pass)"""
+    scores = sorted(set(range(upto, -1, -oracle.ROWS)))
+    kmin, off, rng = oracle.forward_rows(p, t, scores, **kw)
+    out = {}
+    for i, s in enumerate(scores):
+        for c in range(5):
+            for back in range(oracle.ROWS):
+                if s - back < 0:
+                    assert rng[i, c, back, 0] > rng[i, c, back, 1] and (off[i, c, back] == oracle.ROW_NULL).all()
+                    continue
+                lo, hi = int(rng[i, c, back, 0]), int(rng[i, c, back, 1])
+                row = off[i, c, back]
+                held = {k: int(row[k - kmin]) for k in range(max(lo, kmin), min(hi, kmin + len(row) - 1) + 1) if row[k - kmin] != oracle.ROW_NULL}
+                assert all(row[x] == oracle.ROW_NULL for x in range(len(row)) if not lo <= x + kmin <= hi)   # nothing outside the row's range
+                assert (c, s - back) not in out or out[(c, s - back)] == held                             # (scores two calls share)
+                out[(c, s - back)] = held
+    return out
+
+
+def test_forward_rows_reach_the_end_at_the_dp_score_and_never_step_back(oracle):
+    pairs = [(p, t) for p, t in _rand_pairs(23, 260, [1, 2, 7, 40, 64, 100, 101], [0.0, 0.02, 0.1, 0.3]) if p and t]
+    assert len(pairs) >= 200
+    for p, t in pairs:
+        dp = oracle.dp_score(p, t)
+        rows = _all_rows(oracle, p, t, dp)
+        kinv = len(t) - len(p)
+        first = min((s for (c, s), r in rows.items() if c == 0 and r.get(kinv, -1) >= len(t)), default=None)
+        assert first == dp, (len(p), len(t), dp, first)
+        # Offsets on a diagonal never decrease with the score -- from a score to the one a mismatch later, which is how a row is made of an
+        # earlier one: M[s][k] >= M[s - x][k] + 1.  (Not from s - 1 to s: the rows of two consecutive scores
+        # have different sources, and M[25][k] out of a gap opened at score 0 can lie beyond M[26][k].)  So the largest of x consecutive rows never
+        # decreases, and no row holds less than the gap rows of its score.
+        x = oracle.DEFAULT_PEN[0]
+        for s in range(x, dp + 1):
+            before, now = rows[(0, s - x)], rows[(0, s)]
+            for k, v in before.items():
+                # (where the later row holds the diagonal at all: a cell whose largest source lies beyond the rectangle is nulled as a whole)
+                assert k not in now or now[k] >= v + 1, (s, k)
+        for s in range(dp + 1):
+            for c in range(1, 5):
+                assert all(rows[(0, s)].get(k, v) >= v for k, v in rows[(c, s)].items()), (c, s)
+        for (c, s), r in rows.items():   # every offset inside the rectangle for M; a row never holds a diagonal its score cannot reach
+            assert all(abs(k) <= s for k in r)
+            if c == 0:
+                assert all(0 <= v <= len(t) and 0 <= v - k <= len(p) for k, v in r.items())
+

@@ -718,13 +718,14 @@ struct TilePhase {
 
 // A job gives up the keep it began with: it leaves the tile phase here (mode 3, as a job that ran out of its band) and the host runs it again
 // without one.  It drops no record: the node goes to the next level as it came, less the keep.
-void reuse_fall_back(TilePhase& p, size_t i) {
+void reuse_fall_back(TilePhase& p, size_t i, bool touched = false) {
   if (p.active[i]) { p.active[i] = 0; --p.n_active; }
   p.tj[i].active = 0; p.tj[i].mode = 3;
   p.dirs[i] = 3; p.resumed_at[i] = -1;
   p.ru->bad[i] = 1;
   p.ru->store->drop(p.ru->use[i].keep);
   p.h->tile_ctr[WFM_TC_REUSE_FALLBACKS] += 1;
+  p.h->tile_ctr[touched ? WFM_TC_REUSE_TOUCHED : WFM_TC_REUSE_FELL_OTHER] += 1;
 }
 
 // The jobs' TileJobs, and where they stand: at score 0 after the init kernel, or (refine) where a pass before left them
@@ -775,6 +776,7 @@ int init_tile_jobs(TilePhase& p, const std::vector<int32_t>* fine_from, const st
       if (!p.active[i] || kept_max + (u.dir == 0 ? p.rmax[i] : p.fmax[i]) >= A) {  // nothing has run yet: the job simply starts both directions
         p.ru->store->drop(u.keep); u.keep = 0;
         h->tile_ctr[WFM_TC_REUSE_FALLBACKS] += 1;
+        h->tile_ctr[WFM_TC_REUSE_FELL_OTHER] += 1;
         continue;
       }
       (u.dir == 0 ? p.fmax[i] : p.rmax[i]) = kept_max;
@@ -917,7 +919,7 @@ int restore_kept(TilePhase& p) {
     for (size_t q = 0; q < p.rtasks.size(); ++q) {
       const size_t i = (size_t)p.rtasks[q].job;
       changed = true;
-      if (p.rres[2 * q]) { reuse_fall_back(p, i); continue; }
+      if (p.rres[2 * q]) { reuse_fall_back(p, i, true); continue; }  // a kept cell touches the job's box
       const ReuseUse& u = ru.use[i];
       (u.dir == 0 ? p.fmax[i] : p.rmax[i]) = p.rres[2 * q + 1];
       p.tj[i].fmax = p.fmax[i]; p.tj[i].rmax = p.rmax[i];
@@ -1301,7 +1303,7 @@ struct Knobs {
   // what was measured: C3 56.9 - 57.4 ms a step with the roots' keeps, 56.1 - 56.2 with every level's, profiles/parent_reuse.md section 4)
   bool reuse = num("WFM_REUSE", 1) != 0 && slack_env < (1 << 28);  // (children without their parents' scores may not resume: nobody keeps for them)
   int reuse_min_blocks = std::max(1, num("WFM_REUSE_MIN_BLOCKS", 8));  // a keep, and a resume, fewer blocks deep is not worth its look of the host (C2, the scaled C4 rank)
-  int reuse_every = std::max(1, num("WFM_REUSE_EVERY", 2)), reuse_slack = num("WFM_REUSE_TOUCH_SLACK", 0);
+  int reuse_every = std::max(1, num("WFM_REUSE_EVERY", 2)), reuse_slack = std::max(0, num("WFM_REUSE_TOUCH_SLACK", 0));  // (never below 0: that would switch the check off and let a restored row hold offsets outside the job's box)
   int reuse_levels = num("WFM_REUSE_LEVELS", 8);
   int debug = env_debug();  // 0: unset
 };
