@@ -196,3 +196,48 @@ def test_align_paf_bytes_do_not_depend_on_batching_or_on_a_seekable_input(gpu, t
     capi.align_paf(gpu, fa, fifo, out)
     t.join()
     assert open(out, "rb").read() == want
+
+
+def test_align_paf_reaches_the_late_tail_call(gpu, tmp_path, monkeypatch, capfd):
+    """The third device call of a batch (wflign_hip.cpp: patch_late_tails) takes the records whose tail scan looked at a run the head
+    patch can touch (cigar_ops.hpp: plan_patches).  Each scan erodes at least 128 bases of both axes, so the two meet only in a record
+    of fewer than some 300 bases: _make_case has none (its windows carry 1000 bases of padding; seeds 7, 21 and 33 give 39, 43 and 48
+    independent rows and no other), and neither do rows of 300 - 800 bases.  This case has 12 rows of 100 - 280 bases, 12 of 300 - 800
+    and 12 of 4000, without padding; the rows' classes come from the oracle's main CIGAR, the driver says how many tails it scanned
+    late (WFM_DEBUG), and the output is the reference restatement's."""
+    import re
+    from oracle import pyoracle as O
+    rng = random.Random(5)
+    base = synth.random_dna(5, 12000)
+    seqs = {"a#1#chr1": synth.mutate(base, 0.03, 51), "b#1#chr1": synth.mutate(base, 0.06, 52)}
+    fa = str(tmp_path / "two.fa")
+    _write_fasta(fa, seqs)
+    lines = []
+    for k in range(36):
+        seg = (rng.randrange(100, 280), rng.randrange(300, 800), 4000)[k % 3]
+        qs = rng.randrange(200, 12000 - seg - 400)
+        lines.append("\t".join(map(str, ["a#1#chr1", len(seqs["a#1#chr1"]), qs, qs + seg, "+", "b#1#chr1", len(seqs["b#1#chr1"]),
+                                         qs + rng.randrange(-20, 20), qs + seg + rng.randrange(-20, 20), 100, seg, 30, "id:f:0.95",
+                                         "kc:f:0.9", f"ch:Z:{k + 1}.1.1"])))
+    paf = str(tmp_path / "map.paf")
+    with open(paf, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    n_independent = n_later = 0
+    for line in lines:
+        row = W.parse_mashmap_row(line, 0, 0)
+        tgt = W.upper_valid_dna(seqs[row["refId"]][row["rStartPos"]:row["rEndPos"]])
+        q = W.upper_valid_dna(seqs[row["qId"]][row["qStartPos"]:row["qEndPos"]])
+        rc, ops, _, _ = O.align_biwfa(tgt, q)
+        assert rc == 0
+        plan = capi.host_patch_plan(W.compress(ops))
+        n_later += not plan["tail_independent"]
+        n_independent += plan["head_wanted"] and plan["tail_independent"]
+    assert n_independent >= 4 and n_later >= 4, (n_independent, n_later)
+    out = str(tmp_path / "out.paf")
+    monkeypatch.setenv("WFM_DEBUG", "1")
+    capfd.readouterr()
+    summ = capi.align_paf(gpu, fa, paf, out, params={"target_padding": 0, "query_padding": 0})
+    late = [int(x) for x in re.findall(r"\((\d+) tails scanned after their heads\)", capfd.readouterr().err)]
+    assert summ.batches == 1 and late == [n_later]
+    got = [l.rstrip("\n") for l in open(out)]
+    assert got == W.align_mapping_lines(lines, seqs, seqs, target_padding=0, query_padding=0) and len(got) >= 30

@@ -1186,11 +1186,34 @@ def host_subwindow(win_start, win_end, rev, a, b):
 
 
 def host_plan_batch_bytes(file_bytes, rows, row_bytes, row_bases_sum, batch_records, batch_bases, nworkers, ngpu=1, min_batches=1, level=True) -> int:
-    """Aligner::plan_batch_bytes: bytes of the mapping file one batch may hold (2**64 - 1: no limit)."""
+    """plan_batch_bytes (host/align_plan.hpp): bytes of the mapping file one batch may hold (2**64 - 1: no limit)."""
     L = _host()
     L.wfmh_test_plan_batch_bytes.restype = C.c_ulonglong
     L.wfmh_test_plan_batch_bytes.argtypes = [C.c_ulonglong] * 9 + [C.c_int]
     return int(L.wfmh_test_plan_batch_bytes(file_bytes, rows, row_bytes, row_bases_sum, batch_records, batch_bases, nworkers, ngpu, min_batches, 1 if level else 0))
+
+
+def host_align_plan(op: int, values, out_size: int):
+    """wfmh_test_align_plan: one function of the align driver's planner (host/align_plan.hpp) on a list of numbers -> out_size doubles.
+    op 0 workers_per_gpu(threads, ngpu, override); 1 estimate_batches(file_bytes, rows, row_bytes, row_bases_sum, batch_records, batch_bases,
+    batch_bytes) with -1 for "no limit", -1 back for "unknown"; 2 interval_union of (from, to) pairs -> count, total, the intervals;
+    3 its twenty-bin histogram -> total, span, the bins."""
+    L = _host()
+    L.wfmh_test_align_plan.restype = C.c_int
+    L.wfmh_test_align_plan.argtypes = [C.c_int, C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_double)]
+    v = (C.c_double * max(1, len(values)))(*values)
+    out = (C.c_double * out_size)()
+    rc = L.wfmh_test_align_plan(op, v, len(values) // 2 if op >= 2 else len(values), out)
+    if rc != 0:
+        raise WfmError(f"wfmh_test_align_plan failed ({rc})")
+    return list(out)
+
+
+def host_patch_plan(cigar: str):
+    """plan_patches (host/cigar_ops.hpp) of a main CIGAR: dict(head=(query_eroded, target_eroded, runs eroded),
+    tail=(query_eroded, target_eroded, index of the first eroded run), head_wanted, tail_wanted, tail_independent)."""
+    v = [int(x) for x in host_cigar_fn("patch_plan", cigar).split(",")]
+    return dict(head=tuple(v[0:3]), tail=tuple(v[3:6]), head_wanted=bool(v[6]), tail_wanted=bool(v[7]), tail_independent=bool(v[8]))
 
 
 SCORE_NONE, SUB_NONE = 2**31 - 1, 1 << 29  # Node::score_rem of a root; "no bound of the score" (csrc/wfa_device.h)

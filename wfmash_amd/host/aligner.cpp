@@ -1,4 +1,5 @@
 #include "aligner.hpp"
+#include "map_queue.hpp"
 #include "parallel.hpp"
 #include "../csrc/wfa_handle.h"
 
@@ -66,7 +67,9 @@ std::string revcomp(const std::string& s) {
   return r;
 }
 
-struct Fetched {
+}  // namespace
+
+struct Aligner::Fetched {
   MappingBoundaryRow row;
   std::string ref;    // padded reference window
   std::string qry;    // strand-adjusted query window
@@ -75,8 +78,6 @@ struct Fetched {
   int32_t ref_seq = -1, qry_seq = -1;  // resident_sequences: the sides' ids in the device's store (-1: by host pointer)
   bool lazy = false;                   // ... both are there and the output is PAF: the bases are fetched only on demand
 };
-
-}  // namespace
 
 Aligner::Aligner(const Parameters& p, wfm_handle_t* g) : Aligner(p, std::vector<wfm_handle_t*>{g}) {}
 
@@ -190,13 +191,11 @@ void write_record_tags(const std::vector<uint64_t>& row_no, const std::vector<wf
     fclose(f);
   }
 }
-}  // namespace
 
-std::string Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<std::string>& lines, int threads, Summary& sum, uint64_t first_row) {
-  std::string out;
-  const bool dbg = getenv("WFM_DEBUG") != nullptr;
-  const auto tb0 = std::chrono::steady_clock::now();
-  auto since = [](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count(); };
+using Clock = std::chrono::steady_clock;
+double ms_since(Clock::time_point a) { return std::chrono::duration<double, std::milli>(Clock::now() - a).count(); }
+
+wflign::wflign_penalties_t penalties_of(const Parameters& param) {
   wflign::wflign_penalties_t pen;
   pen.match = 0;
   pen.mismatch = param.wfa_patching_mismatch_score;
@@ -204,12 +203,39 @@ std::string Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<std::stri
   pen.gap_extension1 = param.wfa_patching_gap_extension_score1;
   pen.gap_opening2 = param.wfa_patching_gap_opening_score2;
   pen.gap_extension2 = param.wfa_patching_gap_extension_score2;
+  return pen;
+}
+wflign::PafParams filters_of(const Parameters& param) {
   wflign::PafParams pp;
   pp.min_identity = param.min_identity;
   pp.min_alignment_length = param.min_alignment_length;
   pp.min_block_identity = param.min_block_identity;
+  return pp;
+}
+wflign::OutputFormat format_of(const Parameters& param, int threads) {
+  wflign::OutputFormat fmt;
+  fmt.paf_format_else_sam = !param.sam_format;
+  fmt.no_seq_in_sam = param.no_seq_in_sam;
+  fmt.emit_md_tag = param.emit_md_tag;
+  fmt.threads = threads;
+  return fmt;
+}
+}  // namespace
 
-  // rows first (cheap, in order), then the sequence fetches of the whole batch on `threads` threads
+// the stages' times of one batch: lap() is the time since the lap before
+struct Aligner::BatchTimes {
+  Clock::time_point at = Clock::now();
+  double rows = 0, fetch = 0, wflign = 0, text = 0;
+  double lap() {
+    const auto now = Clock::now();
+    const double ms = std::chrono::duration<double, std::milli>(now - at).count();
+    at = now;
+    return ms;
+  }
+};
+
+// rows first (cheap, in order); a row that does not parse or names an unknown sequence is reported and skipped
+std::vector<Aligner::Fetched> Aligner::parse_rows(std::vector<std::string>& lines, uint64_t first_row, Summary& sum) const {
   std::vector<Fetched> rows;
   uint64_t row_no = first_row;
   for (const std::string& line : lines) {
@@ -230,53 +256,52 @@ std::string Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<std::stri
     }
   }
   std::vector<std::string>().swap(lines);
-  const double ms_parse = since(tb0);
-  const auto tb1 = std::chrono::steady_clock::now();
-  // resident_sequences: the sides' ids in the device's store, each sequence added on first use.  A record with both sides there
-  // is not fetched up front when the output is PAF (SAM needs the bases for SEQ and MD).
-  DeviceStore* ds = param.resident_sequences ? device_store(gpu_handle) : nullptr;
-  if (ds) {
-    for (Fetched& f : rows) {
-      if (f.row.rStartPos >= 0 && f.row.rEndPos > f.row.rStartPos && (uint64_t)f.row.rEndPos <= f.ref_total)
-        f.ref_seq = resident_id(gpu_handle, *ds, ref.get(), ref->find(f.row.refId));
-      if (f.row.qStartPos >= 0 && f.row.qEndPos > f.row.qStartPos && (uint64_t)f.row.qEndPos <= f.q_total)
-        f.qry_seq = resident_id(gpu_handle, *ds, query, query->find(f.row.qId));
-      f.lazy = f.ref_seq >= 0 && f.qry_seq >= 0 && !param.sam_format;
-    }
+  return rows;
+}
+
+// resident_sequences: the sides' ids in the device's store, each sequence added on first use.  A record with both sides there
+// is not fetched up front when the output is PAF (SAM needs the bases for SEQ and MD).
+void Aligner::assign_resident_ids(wfm_handle_t* gpu_handle, DeviceStore& ds, std::vector<Fetched>& rows) {
+  for (Fetched& f : rows) {
+    if (f.row.rStartPos >= 0 && f.row.rEndPos > f.row.rStartPos && (uint64_t)f.row.rEndPos <= f.ref_total)
+      f.ref_seq = resident_id(gpu_handle, ds, ref.get(), ref->find(f.row.refId));
+    if (f.row.qStartPos >= 0 && f.row.qEndPos > f.row.qStartPos && (uint64_t)f.row.qEndPos <= f.q_total)
+      f.qry_seq = resident_id(gpu_handle, ds, query, query->find(f.row.qId));
+    f.lazy = f.ref_seq >= 0 && f.qry_seq >= 0 && !param.sam_format;
   }
-  // the padded reference window and the strand-adjusted query window of a row, normalised
-  auto fetch_windows = [&](Fetched& f) {
-    const int64_t ref_size = (int64_t)f.ref_total;
-    const uint64_t head_pad = (uint64_t)f.row.rStartPos >= param.wflign_max_len_minor ? param.wflign_max_len_minor : (uint64_t)f.row.rStartPos;
-    const uint64_t tail_pad = (uint64_t)(ref_size - f.row.rEndPos) >= param.wflign_max_len_minor ? param.wflign_max_len_minor : (uint64_t)(ref_size - f.row.rEndPos);
-    f.ref = ref->fetch(f.row.refId, f.row.rStartPos - (int64_t)head_pad, f.row.rEndPos + (int64_t)tail_pad - 1);
-    if (f.ref.empty()) throw std::runtime_error("Failed to fetch reference sequence");
-    std::string q = query->fetch(f.row.qId, f.row.qStartPos, f.row.qEndPos - 1);
-    if (q.empty()) throw std::runtime_error("Failed to fetch query sequence");
-    f.ref_start = (uint64_t)f.row.rStartPos - head_pad;
-    upper_valid_dna(f.ref);
-    upper_valid_dna(q);
-    f.qry = f.row.strand == FWD ? std::move(q) : revcomp(q);
-  };
+}
+
+// the padded reference window and the strand-adjusted query window of a row, normalised
+void Aligner::fetch_windows(Fetched& f) const {
+  const int64_t ref_size = (int64_t)f.ref_total;
+  const uint64_t head_pad = (uint64_t)f.row.rStartPos >= param.wflign_max_len_minor ? param.wflign_max_len_minor : (uint64_t)f.row.rStartPos;
+  const uint64_t tail_pad = (uint64_t)(ref_size - f.row.rEndPos) >= param.wflign_max_len_minor ? param.wflign_max_len_minor : (uint64_t)(ref_size - f.row.rEndPos);
+  f.ref = ref->fetch(f.row.refId, f.row.rStartPos - (int64_t)head_pad, f.row.rEndPos + (int64_t)tail_pad - 1);
+  if (f.ref.empty()) throw std::runtime_error("Failed to fetch reference sequence");
+  std::string q = query->fetch(f.row.qId, f.row.qStartPos, f.row.qEndPos - 1);
+  if (q.empty()) throw std::runtime_error("Failed to fetch query sequence");
+  f.ref_start = (uint64_t)f.row.rStartPos - head_pad;
+  upper_valid_dna(f.ref);
+  upper_valid_dna(q);
+  f.qry = f.row.strand == FWD ? std::move(q) : revcomp(q);
+}
+
+// the sequence fetches of the whole batch on `threads` threads (lazy rows aside); a row whose fetch fails is reported and skipped
+std::vector<Aligner::Fetched> Aligner::fetch_eager(std::vector<Fetched>& rows, int threads, Summary& sum) const {
   std::vector<std::string> fetch_error(rows.size());
-  {
-    std::atomic<size_t> next{0};
-    auto work = [&] {
-      for (size_t k; (k = next.fetch_add(1)) < rows.size();) {
-        Fetched& f = rows[k];
-        if (f.lazy) continue;
-        try {
-          fetch_windows(f);
-        } catch (const std::exception& e) {
-          fetch_error[k] = e.what();
-          if (fetch_error[k].empty()) fetch_error[k] = "error";
-        }
+  std::atomic<size_t> next{0};
+  const int nt = (int)std::min<size_t>((size_t)std::max(1, threads), rows.size());
+  // (helpers from the process's pool, parallel.hpp: every one of them shares the rows out by the one counter)
+  wfmash_host::parallel_for((size_t)nt, nt, [&](size_t) {
+    for (size_t k; (k = next.fetch_add(1)) < rows.size();) {
+      if (rows[k].lazy) continue;
+      try {
+        fetch_windows(rows[k]);
+      } catch (const std::exception& e) {
+        fetch_error[k] = *e.what() ? e.what() : "error";
       }
-    };
-    const int nt = (int)std::min<size_t>((size_t)std::max(1, threads), rows.size());
-    // (helpers from the process's pool, parallel.hpp: every one of them runs `work`, which shares the rows out by its own counter)
-    wfmash_host::parallel_for((size_t)nt, nt, [&](size_t) { work(); });
-  }
+    }
+  });
   std::vector<Fetched> fetched;
   fetched.reserve(rows.size());
   for (size_t k = 0; k < rows.size(); ++k) {
@@ -287,15 +312,19 @@ std::string Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<std::stri
     }
     fetched.push_back(std::move(rows[k]));
   }
-  if (fetched.empty()) return out;
+  return fetched;
+}
+
+// the host pointers of a record whose windows have been fetched
+void Aligner::point_at(wflign::BiwfaRecord& r, const Fetched& f) {
+  const uint64_t skip = (uint64_t)f.row.rStartPos - f.ref_start;
+  r.query = f.qry.data();
+  r.target = f.ref.data() + skip;
+  r.target_avail = f.ref.size() - skip;
+}
+
+std::vector<wflign::BiwfaRecord> Aligner::make_records(const std::vector<Fetched>& fetched) {
   std::vector<wflign::BiwfaRecord> recs(fetched.size());
-  // the host pointers of a record whose windows have been fetched
-  auto point_at = [](wflign::BiwfaRecord& r, const Fetched& f) {
-    const uint64_t skip = (uint64_t)f.row.rStartPos - f.ref_start;
-    r.query = f.qry.data();
-    r.target = f.ref.data() + skip;
-    r.target_avail = f.ref.size() - skip;
-  };
   for (size_t k = 0; k < fetched.size(); ++k) {
     const Fetched& f = fetched[k];
     wflign::BiwfaRecord& r = recs[k];
@@ -314,6 +343,50 @@ std::string Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<std::stri
     r.mashmap_estimated_identity = f.row.mashmap_estimated_identity;
     r.chain_id = f.row.chain_id; r.chain_length = f.row.chain_length; r.chain_pos = f.row.chain_pos;
   }
+  return recs;
+}
+
+// what the device call did, into the summary; the records' tags where they are asked for
+void Aligner::account(Summary& sum, const wflign::BiwfaStats& st, const wflign::ResidentSeqs& resident, const std::vector<Fetched>& fetched,
+                      const std::vector<wflign::BiwfaRecord>& recs) {
+  sum.lazy_fetches += resident.lazy_fetches.load();
+  sum.cells += st.cells; sum.ms_gpu += st.ms_gpu;
+  sum.cells_tile += st.cells_tile; sum.tile_launches += st.tile_launches; sum.ms_tile += st.ms_tile;
+  sum.busy.insert(sum.busy.end(), st.busy.begin(), st.busy.end());
+  if (getenv("WFM_RECORD_TAGS")) {
+    const auto tt = Clock::now();
+    std::vector<uint64_t> rn(fetched.size());
+    for (size_t k = 0; k < fetched.size(); ++k) rn[k] = fetched[k].row_no;
+    write_record_tags(rn, recs);
+    sum.ms_tags += ms_since(tt);
+  }
+}
+
+std::string Aligner::gather_text(Summary& sum, const std::vector<Fetched>& fetched, const std::vector<wflign::BiwfaRecord>& recs) {
+  std::string out;
+  for (size_t k = 0; k < recs.size(); ++k) {
+    sum.records++;
+    sum.records_resident += recs[k].target_seq >= 0 && recs[k].query_seq >= 0;
+    sum.aligned_bp += (uint64_t)(fetched[k].row.qEndPos - fetched[k].row.qStartPos);
+    if (recs[k].paf.empty()) continue;
+    // PAF: the record is already in the form processMappingRecord gives it (fields re-joined with single tabs,
+    // computeAlignments.hpp:484-525); SAM: no cg:Z: field -> the writer's line passes through unchanged
+    out += recs[k].paf;
+    sum.written++;
+  }
+  return out;
+}
+
+std::string Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<std::string>& lines, int threads, Summary& sum, uint64_t first_row) {
+  const bool dbg = getenv("WFM_DEBUG") != nullptr;
+  BatchTimes t;
+  std::vector<Fetched> rows = parse_rows(lines, first_row, sum);
+  t.rows = t.lap();
+  DeviceStore* ds = param.resident_sequences ? device_store(gpu_handle) : nullptr;
+  if (ds) assign_resident_ids(gpu_handle, *ds, rows);
+  std::vector<Fetched> fetched = fetch_eager(rows, threads, sum);
+  if (fetched.empty()) return std::string();
+  std::vector<wflign::BiwfaRecord> recs = make_records(fetched);
   wflign::ResidentSeqs resident;
   if (ds) {
     resident.store = ds->store;
@@ -327,44 +400,19 @@ std::string Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<std::stri
       }
     };
   }
-  const double ms_fetch = since(tb1);
-  const auto tb2 = std::chrono::steady_clock::now();
+  t.fetch = t.lap();
   wflign::BiwfaStats st;
-  wflign::OutputFormat fmt;
-  fmt.paf_format_else_sam = !param.sam_format;
-  fmt.no_seq_in_sam = param.no_seq_in_sam;
-  fmt.emit_md_tag = param.emit_md_tag;
-  fmt.threads = threads;
-  const int rc = wflign::do_biwfa_alignment_batch(gpu_handle, recs, pen, param.disable_chain_patching, pp, &st, fmt, ds ? &resident : nullptr);
+  const int rc = wflign::do_biwfa_alignment_batch(gpu_handle, recs, penalties_of(param), param.disable_chain_patching, filters_of(param), &st,
+                                                  format_of(param, threads), ds ? &resident : nullptr);
   if (rc < 0) throw std::runtime_error(std::string("[wfmash::align] GPU alignment failed: ") + st.error);
-  sum.lazy_fetches += resident.lazy_fetches.load();
-  sum.cells += st.cells; sum.ms_gpu += st.ms_gpu;
-  sum.cells_tile += st.cells_tile; sum.tile_launches += st.tile_launches; sum.ms_tile += st.ms_tile;
-  sum.busy.insert(sum.busy.end(), st.busy.begin(), st.busy.end());
-  if (getenv("WFM_RECORD_TAGS")) {
-    const auto tt = std::chrono::steady_clock::now();
-    std::vector<uint64_t> rn(fetched.size());
-    for (size_t k = 0; k < fetched.size(); ++k) rn[k] = fetched[k].row_no;
-    write_record_tags(rn, recs);
-    sum.ms_tags += since(tt);
-  }
-  const double ms_biwfa = since(tb2);
-  const auto tb3 = std::chrono::steady_clock::now();
-  for (size_t k = 0; k < recs.size(); ++k) {
-    sum.records++;
-    sum.records_resident += recs[k].target_seq >= 0 && recs[k].query_seq >= 0;
-    sum.aligned_bp += (uint64_t)(fetched[k].row.qEndPos - fetched[k].row.qStartPos);
-    if (recs[k].paf.empty()) continue;
-    // PAF: the record is already in the form processMappingRecord gives it (fields re-joined with single tabs,
-    // computeAlignments.hpp:484-525); SAM: no cg:Z: field -> the writer's line passes through unchanged
-    out += recs[k].paf;
-    sum.written++;
-  }
-  const double ms_text = since(tb3);
-  sum.ms_rows += ms_parse; sum.ms_fetch += ms_fetch; sum.ms_wflign += ms_biwfa; sum.ms_text += ms_text; sum.batches++;
+  account(sum, st, resident, fetched, recs);
+  t.wflign = t.lap();
+  std::string out = gather_text(sum, fetched, recs);
+  t.text = t.lap();
+  sum.ms_rows += t.rows; sum.ms_fetch += t.fetch; sum.ms_wflign += t.wflign; sum.ms_text += t.text; sum.batches++;
   if (dbg)
     fprintf(stderr, "[wfmash::align] batch of %zu records on %d threads: rows %.1f ms, fetch %.1f ms, wflign %.1f ms (device busy %.1f), text %.1f ms\n",
-            recs.size(), threads, ms_parse, ms_fetch, ms_biwfa, st.ms_gpu, ms_text);
+            recs.size(), threads, t.rows, t.fetch, t.wflign, st.ms_gpu, t.text);
   return out;
 }
 
@@ -384,42 +432,216 @@ std::string Aligner::align_lines(const std::vector<std::string>& lines, Summary&
   return out;
 }
 
-// bases a mapping row will align, padding aside (the reader sizes batches by it)
-uint64_t Aligner::plan_batch_bytes(uint64_t file_bytes, uint64_t rows, uint64_t row_bytes, uint64_t row_bases_sum, uint64_t batch_records,
-                                   uint64_t batch_bases, uint64_t nworkers, uint64_t ngpu, uint64_t min_batches, bool level) {
-  if (file_bytes == 0) return ~0ull;
-  uint64_t want = ngpu > 1 ? 8 * ngpu : std::max<uint64_t>(1, min_batches);
-  if (level && nworkers > 1 && rows > 0 && row_bytes > 0) {
-    const double est_rows = (double)file_bytes / ((double)row_bytes / (double)rows);
-    const double est_bases = est_rows * ((double)row_bases_sum / (double)rows);
-    const uint64_t need = (uint64_t)std::ceil(std::max(est_rows / (double)std::max<uint64_t>(1, batch_records), est_bases / (double)std::max<uint64_t>(1, batch_bases)));
-    if (need >= 2 && need < 8 * nworkers) want = std::max<uint64_t>(want, (need + nworkers - 1) / nworkers * nworkers);
-  }
-  return want > 1 ? std::max<uint64_t>(1, file_bytes / want + 1) : ~0ull;
-}
-
-uint64_t Aligner::row_bases(const std::string& line) {
-  uint64_t v[9] = {0};
-  size_t pos = 0;
-  for (int col = 0; col < 9; ++col) {
-    while (pos < line.size() && std::isspace((unsigned char)line[pos])) ++pos;
-    const size_t st = pos;
-    while (pos < line.size() && !std::isspace((unsigned char)line[pos])) ++pos;
-    if (st == pos) return 0;
-    if (col == 2 || col == 3 || col == 7 || col == 8) v[col] = strtoull(line.c_str() + st, nullptr, 10);
-  }
-  return (v[3] > v[2] ? v[3] - v[2] : 0) + (v[8] > v[7] ? v[8] - v[7] : 0);
-}
-
+// ---------------------------------------------------------------------------
 // The reference streams records from a reader through a pool of workers to a writer
 // (computeAlignments.hpp:318-455).  Here the reader hands out batches of mapping rows, one worker per GPU
 // takes the next batch whenever its device is free (the greedy least-loaded assignment of
 // scripts/split_approx_mappings_in_chunks.py:19-27,47, taken at run time instead of from predicted weights),
 // and finished batches are written in the order they were read: the output does not depend on the number of
 // GPUs, and host memory holds the batches in flight, not the run.
+// ---------------------------------------------------------------------------
+namespace {
+// Every worker beyond the first of a device works on a handle of its own (own stream, own arenas): its batch's device
+// calls then really run beside the other workers' -- the few-workgroup tails of one batch (the patches that overflow
+// their score budget, the last leaves) under the wide levels of another -- instead of taking turns on one handle.
+// The extra handles stay with the process (two per device at most, or a worker's number less one) and serve the next run as
+// well: their arenas are what a first use pays for, and a handle given back to the driver costs the next hipMalloc its scrubbing.
+class HandlePool {
+ public:
+  // what one run has borrowed: given back when it goes out of scope
+  class Loan {
+   public:
+    explicit Loan(HandlePool& p) : pool_(p) {}
+    Loan(const Loan&) = delete;
+    Loan& operator=(const Loan&) = delete;
+    ~Loan() {
+      std::lock_guard<std::mutex> lk(pool_.mu_);
+      for (auto& x : borrowed_) pool_.by_device_[x.first][(size_t)x.second].second = false;
+    }
+    // a free handle of the device, or a new one while the device would then have fewer than `limit`; null: none is to be had
+    wfm_handle_t* borrow(int dev, size_t limit) {
+      std::lock_guard<std::mutex> lk(pool_.mu_);
+      auto& v = pool_.by_device_[dev];
+      int slot = -1;
+      for (size_t q = 0; q < v.size(); ++q) if (!v[q].second) { slot = (int)q; break; }
+      if (slot < 0 && v.size() + 1 < limit) {
+        wfm_handle_t* nh = nullptr;
+        if (wfm_create(dev, &nh) == WFM_OK) { v.emplace_back(nh, false); slot = (int)v.size() - 1; }
+      }
+      if (slot < 0) return nullptr;
+      v[(size_t)slot].second = true;
+      borrowed_.emplace_back(dev, slot);
+      return v[(size_t)slot].first;
+    }
+
+   private:
+    HandlePool& pool_;
+    std::vector<std::pair<int, int>> borrowed_;  // (device, slot)
+  };
+
+ private:
+  std::mutex mu_;
+  std::map<int, std::vector<std::pair<wfm_handle_t*, bool>>> by_device_;  // handle, in use
+};
+
+// the ordered writer's sink: the output file, flushed once per put
+struct TextSink {
+  std::ofstream* out;
+  void write(std::string& text) { *out << text; }
+  void flush() { out->flush(); }
+};
+}  // namespace
+
+struct Aligner::Run {
+  Run(const Parameters& p, const RunPlan& pl, size_t n_gpu, Clock::time_point start, std::ifstream& i, std::ofstream& o)
+      : param(p), plan(pl), ngpu(n_gpu), t0(start), in(i), writer(TextSink{&o}), in_flight(n_gpu), first_taken(n_gpu), use(pl.nworkers, nullptr),
+        part(pl.nworkers), threads_each(std::max(1, p.threads / (int)pl.nworkers)) {
+    for (auto& a : in_flight) a.store(0);
+    for (auto& a : first_taken) a.store(0);
+  }
+  const Parameters& param;
+  const RunPlan plan;
+  const size_t ngpu;
+  const Clock::time_point t0;
+  std::ifstream& in;
+  skch::OrderedWriter<std::string, TextSink> writer;
+  std::mutex read_mu;
+  uint64_t next_seq = 0;   // (under read_mu) the next batch's number
+  uint64_t rows_read = 0;  // (under read_mu) non-empty rows handed out so far
+  bool more_rows = true;   // (under read_mu) rows are left behind the batch handed out last
+  std::vector<std::atomic<int>> in_flight;    // batches on the device right now, per device
+  std::vector<std::atomic<int>> first_taken;  // the device's first batch has been handed out (or there is none)
+  std::mutex error_mu;
+  std::string first_error;
+  std::atomic<bool> failed{false};
+  std::vector<wfm_handle_t*> use;  // the handle of each worker
+  std::vector<Summary> part;
+  const int threads_each;
+
+  double ms() const { return ms_since(t0); }
+  // the next batch's number, or -1 at the end
+  int64_t read_batch(std::vector<std::string>& batch, uint64_t& first_row) {
+    std::lock_guard<std::mutex> lk(read_mu);
+    batch.clear();
+    first_row = rows_read;
+    uint64_t bases = 0, bytes = 0;
+    std::string line;
+    while (batch.size() < param.batch_records && bases < param.batch_bases && bytes < plan.batch_bytes && std::getline(in, line)) {
+      if (line.empty()) continue;
+      bases += row_bases(line);
+      bytes += line.size() + 1;
+      batch.push_back(std::move(line));
+    }
+    rows_read += batch.size();
+    more_rows = !batch.empty() && in.peek() != std::char_traits<char>::eof();
+    return batch.empty() ? -1 : (int64_t)next_seq++;
+  }
+};
+
+// Workers and batch size from the host's threads, the file's size and its first rows (unknown for a stream).
+Aligner::RunPlan Aligner::plan_run(std::ifstream& in) const {
+  const size_t ngpu = gpus.size();
+  static const size_t workers_env = getenv("WFM_ALIGN_WORKERS") ? (size_t)std::max(1, atoi(getenv("WFM_ALIGN_WORKERS"))) : 0;  // A/B runs
+  static const uint64_t min_batches = getenv("WFM_ALIGN_MIN_BATCHES") ? (uint64_t)std::max(1, atoi(getenv("WFM_ALIGN_MIN_BATCHES"))) : 1;
+  static const bool level_batches = !(getenv("WFM_ALIGN_LEVEL") && atoi(getenv("WFM_ALIGN_LEVEL")) == 0);
+  RunPlan plan;
+  plan.per_gpu = workers_per_gpu((size_t)param.threads, ngpu, workers_env);
+  const size_t nworkers_max = ngpu * plan.per_gpu;
+  // (a mapping file that cannot be rewound -- a FIFO, /dev/stdin -- is read as it comes: no size, no look ahead)
+  in.seekg(0, std::ios::end);
+  const std::streamoff end_at = in.fail() ? (std::streamoff)-1 : (std::streamoff)in.tellg();
+  in.clear();
+  if (end_at >= 0) in.seekg(0, std::ios::beg);
+  const bool seekable = end_at >= 0 && !in.fail();
+  in.clear();
+  const uint64_t file_bytes = seekable ? (uint64_t)end_at : 0;
+  uint64_t rows = 0, bytes = 0, bases = 0;
+  if (level_batches && nworkers_max > 1 && file_bytes > 0) {
+    std::string line;
+    while (rows < 256 && std::getline(in, line)) {
+      if (line.empty()) continue;
+      ++rows; bytes += line.size() + 1; bases += row_bases(line);
+    }
+    in.clear();
+    in.seekg(0, std::ios::beg);
+  }
+  plan.batch_bytes = plan_batch_bytes(file_bytes, rows, bytes, bases, param.batch_records, param.batch_bases, nworkers_max, ngpu, min_batches, level_batches);
+  // (no more workers than the file has batches: a worker beyond the first of a device brings a handle with arenas of its own, and the host threads are shared
+  // out over the workers -- a mapping file of one batch keeps them all)
+  const uint64_t est_batches = estimate_batches(file_bytes, rows, bytes, bases, param.batch_records, param.batch_bases, plan.batch_bytes);
+  plan.nworkers = (size_t)std::max<uint64_t>(ngpu, std::min<uint64_t>(nworkers_max, est_batches));
+  return plan;
+}
+
+void Aligner::run_worker(Run& run, size_t wk) {
+  const size_t dev = wk % run.ngpu;
+  try {
+    std::vector<std::string> batch;
+    // (the first batch of a device goes to its first worker, the one on the caller's handle: a file of one batch then runs
+    // on arenas that are most likely there already)
+    if (wk >= run.ngpu) while (!run.first_taken[dev].load() && !run.failed.load()) std::this_thread::yield();
+    uint64_t first_row = 0;
+    for (int64_t seq; !run.failed.load() && (seq = run.read_batch(batch, first_row)) >= 0;) {
+      run.first_taken[dev].store(1);
+      const double at0 = run.ms();
+      // a batch that has its device to itself -- none beside it, none to come -- is cut into parts by the device layer
+      // (wfm_set_concurrent_calls: its levels are chains of short launches, and one chain does not fill a device)
+      // (both under the readers' lock: two workers that start together must not each see the device as theirs alone)
+      bool more;
+      int beside;
+      { std::lock_guard<std::mutex> lk(run.read_mu); more = run.more_rows; beside = run.in_flight[dev].fetch_add(1); }
+      wfm_set_concurrent_calls(run.use[wk], beside + (more && run.plan.per_gpu > 1 ? 1 : 0));
+      struct Leave { std::atomic<int>& a; ~Leave() { a.fetch_sub(1); } } leave{run.in_flight[dev]};
+      std::string text = align_batch(run.use[wk], batch, run.threads_each, run.part[wk], first_row);
+      const double at1 = run.ms();
+      run.writer.put((uint64_t)seq, std::move(text));
+      if (getenv("WFM_DEBUG"))
+        fprintf(stderr, "[wfmash::align] worker %zu: batch %lld from +%.0f ms to +%.0f ms, written at +%.0f ms\n", wk, (long long)seq, at0, at1, run.ms());
+    }
+  } catch (const std::exception& e) {
+    std::lock_guard<std::mutex> lk(run.error_mu);
+    if (run.first_error.empty()) run.first_error = e.what();
+    run.failed.store(true);
+  }
+  run.first_taken[dev].store(1);  // (nothing left for this device's first worker either: the others must not wait)
+}
+
+// the workers' parts into the run's summary; per device, the time during which a kernel of any of its workers' calls was
+// running (their calls overlap)
+void Aligner::sum_up(Summary& sum, const std::vector<Summary>& part, std::chrono::steady_clock::time_point t0) const {
+  const size_t ngpu = gpus.size();
+  std::vector<std::vector<Interval>> iv(ngpu);
+  for (size_t wk = 0; wk < part.size(); ++wk) {
+    const Summary& p = part[wk];
+    sum.records += p.records; sum.aligned_bp += p.aligned_bp; sum.written += p.written; sum.skipped += p.skipped;
+    sum.cells += p.cells;
+    sum.records_resident += p.records_resident; sum.lazy_fetches += p.lazy_fetches;
+    sum.cells_tile += p.cells_tile; sum.tile_launches += p.tile_launches; sum.ms_tile += p.ms_tile; sum.ms_tags += p.ms_tags;
+    sum.ms_rows += p.ms_rows; sum.ms_fetch += p.ms_fetch; sum.ms_wflign += p.ms_wflign; sum.ms_text += p.ms_text; sum.batches += p.batches;
+    iv[wk % ngpu].insert(iv[wk % ngpu].end(), p.busy.begin(), p.busy.end());
+  }
+  for (auto& v : iv) {
+    const std::vector<Interval> busy = interval_union(v);
+    const double total = total_length(busy);
+    sum.ms_gpu = std::max(sum.ms_gpu, total);
+    if (getenv("WFM_DEBUG") && !v.empty()) {
+      // where the device had no kernel running: its busy share per twentieth of the span from its first kernel to its last (the intervals
+      // are on the device's own clock; the run's wall time less that span is the head before the first kernel plus the tail after the last)
+      const double wall = ms_since(t0);
+      const double d_lo = span_of(v).first, span = span_of(v).second;
+      const std::vector<double> busy20 = covered_per_bin(busy, d_lo, span, 20);
+      fprintf(stderr, "[wfmash::align] device: first kernel to last %.1f ms of the run's %.1f (head + tail %.1f), busy %.1f; busy share per twentieth of that span:", span, wall, wall - span, total);
+      for (int q = 0; q < 20; ++q) fprintf(stderr, " %.2f", busy20[(size_t)q] / (span / 20));
+      fprintf(stderr, "\n");
+    }
+  }
+  // (a worker's own calls follow one another: the sum of their busy times is a lower bound of its device's)
+  for (const Summary& p : part) sum.ms_gpu = std::max(sum.ms_gpu, p.ms_gpu);
+}
+
 Summary Aligner::compute() {
   Summary sum;
-  const auto t0 = std::chrono::steady_clock::now();
+  const auto t0 = Clock::now();
   std::ifstream in(param.mashmapPafFile);
   if (!in.is_open()) throw std::runtime_error("[wfmash::align] Error! Failed to open input mapping file: " + param.mashmapPafFile);
   std::ofstream outstream(param.pafOutputFile);
@@ -429,213 +651,26 @@ Summary Aligner::compute() {
     outstream << "@PG\tID:wfmash\tPN:wfmash\tVN:" WFMASH_HIP_VERSION "\tCL:wfmash\n";
   }
   const size_t ngpu = gpus.size();
-  // up to three batches per GPU in flight when there are host threads for it: the host stages of a batch (sequence
-  // fetches, CIGAR surgery, PAF text) run while the device works on another
-  static const size_t workers_env = getenv("WFM_ALIGN_WORKERS") ? (size_t)std::max(1, atoi(getenv("WFM_ALIGN_WORKERS"))) : 0;  // A/B runs
-  // (four since round 5 where the host has 16 threads per GPU: with the round's kernels a batch of a pangenome rank is 100 ms of device time in 170 ms
-  // of its worker's, and a full-size rank went from 1.37 - 1.42 s on three workers to 1.18 - 1.29 s on four -- gpurun_out/r5i.log; six gain nothing more)
-  // (six since round 6 where the host has 48 threads per GPU: on the all-vs-all job at north_star's size -- 187 batches -- the device's busy time went from 7.58 to 7.30 s
-  // and the align phase from 8.3 - 8.45 to 7.8 - 8.1 s, eight workers 8.2 - 8.3 s: gpurun_out/r6cb; a rank's 28 batches are the same 1.08 - 1.12 s on four, five or six)
-  const size_t per_gpu = workers_env ? workers_env
-                                     : ((size_t)param.threads >= 48 * ngpu ? 6 : ((size_t)param.threads >= 16 * ngpu ? 4 : ((size_t)param.threads >= 12 * ngpu ? 3 : ((size_t)param.threads >= 2 * ngpu ? 2 : 1))));
-  const size_t nworkers_max = ngpu * per_gpu;
-  uint64_t est_batches = ~0ull;  // (from the file's size and its first rows; unknown for a stream)
-  // several GPUs: no batch may hold more than an eighth of one GPU's share of the file.  One GPU: a file of one batch
-  // stays one batch (WFM_ALIGN_MIN_BATCHES cuts it for A/B runs); a file of a few batches is cut into a multiple of the
-  // workers' number, level ones -- four batches on three workers are two rounds of which the second leaves the device to
-  // one batch's tails.  (The number of records is estimated from the file's size and its first rows.)
-  uint64_t batch_bytes = ~0ull;
-  static const uint64_t min_batches = getenv("WFM_ALIGN_MIN_BATCHES") ? (uint64_t)std::max(1, atoi(getenv("WFM_ALIGN_MIN_BATCHES"))) : 1;
-  static const bool level_batches = !(getenv("WFM_ALIGN_LEVEL") && atoi(getenv("WFM_ALIGN_LEVEL")) == 0);
-  {
-    // (a mapping file that cannot be rewound -- a FIFO, /dev/stdin -- is read as it comes: no size, no look ahead)
-    in.seekg(0, std::ios::end);
-    const std::streamoff end_at = in.fail() ? (std::streamoff)-1 : (std::streamoff)in.tellg();
-    in.clear();
-    if (end_at >= 0) in.seekg(0, std::ios::beg);
-    const bool seekable = end_at >= 0 && !in.fail();
-    in.clear();
-    const uint64_t file_bytes = seekable ? (uint64_t)end_at : 0;
-    uint64_t rows = 0, bytes = 0, bases = 0;
-    if (level_batches && nworkers_max > 1 && file_bytes > 0) {
-      std::string line;
-      while (rows < 256 && std::getline(in, line)) {
-        if (line.empty()) continue;
-        ++rows; bytes += line.size() + 1; bases += row_bases(line);
-      }
-      in.clear();
-      in.seekg(0, std::ios::beg);
-    }
-    batch_bytes = plan_batch_bytes(file_bytes, rows, bytes, bases, param.batch_records, param.batch_bases, nworkers_max, ngpu, min_batches, level_batches);
-    // (no more workers than the file has batches: a worker beyond the first of a device brings a handle with arenas of its own, and the host threads are shared
-    // out over the workers -- a mapping file of one batch keeps them all)
-    if (rows > 0 && bytes > 0) {
-      const double est_rows = (double)file_bytes / ((double)bytes / (double)rows);
-      const double est_bases = est_rows * ((double)bases / (double)rows);
-      uint64_t need = (uint64_t)std::ceil(std::max(est_rows / (double)std::max<uint64_t>(1, param.batch_records), est_bases / (double)std::max<uint64_t>(1, param.batch_bases)));
-      if (batch_bytes != ~0ull) need = std::max<uint64_t>(need, (file_bytes + batch_bytes - 1) / batch_bytes);
-      est_batches = std::max<uint64_t>(1, need);
-    }
-  }
-  const size_t nworkers = (size_t)std::max<uint64_t>(ngpu, std::min<uint64_t>(nworkers_max, est_batches));
-  std::mutex read_mu, write_mu;
-  uint64_t next_seq = 0, next_write = 0;
-  std::map<uint64_t, std::string> pending;
-  std::string first_error;
-  std::atomic<bool> failed{false};
-  bool more_rows = true;  // (under read_mu) rows are left behind the batch handed out last
-  std::vector<std::atomic<int>> in_flight(ngpu);  // batches on the device right now, per device
-  for (auto& a : in_flight) a.store(0);
-  uint64_t rows_read = 0;  // (under read_mu) non-empty rows handed out so far
-  auto read_batch = [&](std::vector<std::string>& batch, uint64_t& first_row) -> int64_t {  // the batch's number, or -1 at the end
-    std::lock_guard<std::mutex> lk(read_mu);
-    batch.clear();
-    first_row = rows_read;
-    uint64_t bases = 0, bytes = 0;
-    std::string line;
-    while (batch.size() < param.batch_records && bases < param.batch_bases && bytes < batch_bytes && std::getline(in, line)) {
-      if (line.empty()) continue;
-      bases += row_bases(line);
-      bytes += line.size() + 1;
-      batch.push_back(std::move(line));
-    }
-    rows_read += batch.size();
-    more_rows = !batch.empty() && in.peek() != std::char_traits<char>::eof();
-    return batch.empty() ? -1 : (int64_t)next_seq++;
-  };
-  auto write_batch = [&](uint64_t seq, std::string&& text) {
-    std::lock_guard<std::mutex> lk(write_mu);
-    pending.emplace(seq, std::move(text));
-    for (auto it = pending.begin(); it != pending.end() && it->first == next_write; it = pending.erase(it), ++next_write)
-      outstream << it->second;
-    outstream.flush();
-  };
-  std::vector<Summary> part(nworkers);
-  const int threads_each = std::max(1, param.threads / (int)nworkers);
-  // Every worker beyond the first of a device works on a handle of its own (own stream, own arenas): its batch's device
-  // calls then really run beside the other workers' -- the few-workgroup tails of one batch (the patches that overflow
-  // their score budget, the last leaves) under the wide levels of another -- instead of taking turns on one handle.
-  // The extra handles stay with the process (two per device at most) and serve the next run as well: their arenas are
-  // what a first use pays for, and a handle given back to the driver costs the next hipMalloc its scrubbing.
-  std::vector<wfm_handle_t*> use(nworkers, nullptr);
-  std::vector<std::pair<int, int>> borrowed;  // (device, slot) taken from the pool
+  Run run(param, plan_run(in), ngpu, t0, in, outstream);
+  const size_t nworkers = run.plan.nworkers;
   static const bool own_handles = !(getenv("WFM_ALIGN_OWN_HANDLES") && atoi(getenv("WFM_ALIGN_OWN_HANDLES")) == 0);
-  struct Pool {
-    std::mutex mu;
-    std::map<int, std::vector<std::pair<wfm_handle_t*, bool>>> by_device;  // handle, in use
-  };
-  static Pool pool;
+  static HandlePool pool;
+  HandlePool::Loan loan(pool);
   for (size_t wk = 0; wk < nworkers; ++wk) {
-    use[wk] = gpus[wk % ngpu];
+    run.use[wk] = gpus[wk % ngpu];
     if (wk < ngpu || !own_handles) continue;
-    const int dev = wfm_device(gpus[wk % ngpu]);
-    std::lock_guard<std::mutex> lk(pool.mu);
-    auto& v = pool.by_device[dev];
-    int slot = -1;
-    for (size_t q = 0; q < v.size(); ++q) if (!v[q].second) { slot = (int)q; break; }
-    if (slot < 0 && v.size() + 1 < std::max<size_t>(3, per_gpu)) {
-      wfm_handle_t* nh = nullptr;
-      if (wfm_create(dev, &nh) == WFM_OK) { v.emplace_back(nh, false); slot = (int)v.size() - 1; }
-    }
-    if (slot >= 0) { v[(size_t)slot].second = true; use[wk] = v[(size_t)slot].first; borrowed.emplace_back(dev, slot); }
+    if (wfm_handle_t* own = loan.borrow(wfm_device(gpus[wk % ngpu]), std::max<size_t>(3, run.plan.per_gpu))) run.use[wk] = own;
   }
-  struct Return {
-    Pool& p; std::vector<std::pair<int, int>>& b;
-    ~Return() { std::lock_guard<std::mutex> lk(p.mu); for (auto& x : b) p.by_device[x.first][(size_t)x.second].second = false; }
-  } give_back{pool, borrowed};
-  // (the first batch of a device goes to its first worker, the one on the caller's handle: a file of one batch then runs
-  // on arenas that are most likely there already)
-  std::vector<std::atomic<int>> first_taken(ngpu);
-  for (auto& a : first_taken) a.store(0);
-  auto worker = [&](size_t wk) {
-    try {
-      std::vector<std::string> batch;
-      if (wk >= ngpu) while (!first_taken[wk % ngpu].load() && !failed.load()) std::this_thread::yield();
-      uint64_t first_row = 0;
-      for (int64_t seq; !failed.load() && (seq = read_batch(batch, first_row)) >= 0;) {
-        first_taken[wk % ngpu].store(1);
-        const double at0 = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        // a batch that has its device to itself -- none beside it, none to come -- is cut into parts by the device layer
-        // (wfm_set_concurrent_calls: its levels are chains of short launches, and one chain does not fill a device)
-        // (both under the readers' lock: two workers that start together must not each see the device as theirs alone)
-        bool more;
-        int beside;
-        { std::lock_guard<std::mutex> lk(read_mu); more = more_rows; beside = in_flight[wk % ngpu].fetch_add(1); }
-        wfm_set_concurrent_calls(use[wk], beside + (more && per_gpu > 1 ? 1 : 0));
-        struct Leave { std::atomic<int>& a; ~Leave() { a.fetch_sub(1); } } leave{in_flight[wk % ngpu]};
-        std::string text = align_batch(use[wk], batch, threads_each, part[wk], first_row);
-        const double at1 = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        write_batch((uint64_t)seq, std::move(text));
-        if (getenv("WFM_DEBUG"))
-          fprintf(stderr, "[wfmash::align] worker %zu: batch %lld from +%.0f ms to +%.0f ms, written at +%.0f ms\n", wk, (long long)seq, at0, at1,
-                  std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-      }
-    } catch (const std::exception& e) {
-      std::lock_guard<std::mutex> lk(write_mu);
-      if (first_error.empty()) first_error = e.what();
-      failed.store(true);
-    }
-    first_taken[wk % ngpu].store(1);  // (nothing left for this device's first worker either: the others must not wait)
-  };
   {
-    std::vector<std::thread> pool;
-    for (size_t wk = 1; wk < nworkers; ++wk) pool.emplace_back(worker, wk);
-    worker(0);
-    for (auto& t : pool) t.join();
+    std::vector<std::thread> threads;
+    for (size_t wk = 1; wk < nworkers; ++wk) threads.emplace_back([this, &run, wk] { run_worker(run, wk); });
+    run_worker(run, 0);
+    for (auto& t : threads) t.join();
   }
-  if (failed.load()) throw std::runtime_error(first_error);
-  {
-    // per device: the time during which a kernel of any of its workers' calls was running (their calls overlap)
-    std::vector<std::vector<std::pair<double, double>>> iv(ngpu);
-    for (size_t wk = 0; wk < nworkers; ++wk) {
-      const Summary& p = part[wk];
-      sum.records += p.records; sum.aligned_bp += p.aligned_bp; sum.written += p.written; sum.skipped += p.skipped;
-      sum.cells += p.cells;
-      sum.records_resident += p.records_resident; sum.lazy_fetches += p.lazy_fetches;
-      sum.cells_tile += p.cells_tile; sum.tile_launches += p.tile_launches; sum.ms_tile += p.ms_tile; sum.ms_tags += p.ms_tags;
-      sum.ms_rows += p.ms_rows; sum.ms_fetch += p.ms_fetch; sum.ms_wflign += p.ms_wflign; sum.ms_text += p.ms_text; sum.batches += p.batches;
-      iv[wk % ngpu].insert(iv[wk % ngpu].end(), p.busy.begin(), p.busy.end());
-    }
-    for (auto& v : iv) {
-      std::sort(v.begin(), v.end());
-      double total = 0, lo = 0, hi = -1;
-      for (const auto& x : v) {
-        if (x.first > hi) { if (hi > lo) total += hi - lo; lo = x.first; hi = x.second; }
-        else hi = std::max(hi, x.second);
-      }
-      if (hi > lo) total += hi - lo;
-      sum.ms_gpu = std::max(sum.ms_gpu, total);
-      if (getenv("WFM_DEBUG") && !v.empty()) {
-        // where the device had no kernel running: its busy share per twentieth of the span from its first kernel to its last (the intervals
-        // are on the device's own clock; the run's wall time less that span is the head before the first kernel plus the tail after the last)
-        const double wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        double d_lo = v.front().first, d_hi = d_lo;
-        for (const auto& x : v) d_hi = std::max(d_hi, x.second);
-        const double span = std::max(d_hi - d_lo, 1e-6);
-        std::vector<double> busy20(20, 0.0);
-        auto add = [&](double a, double b) {
-          for (int q = 0; q < 20; ++q) {
-            const double qa = d_lo + span * q / 20, qb = d_lo + span * (q + 1) / 20;
-            const double o = std::min(b, qb) - std::max(a, qa);
-            if (o > 0) busy20[(size_t)q] += o;
-          }
-        };
-        double mlo = 0, mhi = -1;
-        for (const auto& x : v) {
-          if (x.first > mhi) { if (mhi > mlo) add(mlo, mhi); mlo = x.first; mhi = x.second; }
-          else mhi = std::max(mhi, x.second);
-        }
-        if (mhi > mlo) add(mlo, mhi);
-        fprintf(stderr, "[wfmash::align] device: first kernel to last %.1f ms of the run's %.1f (head + tail %.1f), busy %.1f; busy share per twentieth of that span:", span, wall, wall - span, total);
-        for (int q = 0; q < 20; ++q) fprintf(stderr, " %.2f", busy20[(size_t)q] / (span / 20));
-        fprintf(stderr, "\n");
-      }
-    }
-    // (a worker's own calls follow one another: the sum of their busy times is a lower bound of its device's)
-    for (size_t wk = 0; wk < nworkers; ++wk) sum.ms_gpu = std::max(sum.ms_gpu, part[wk].ms_gpu);
-  }
+  if (run.failed.load()) throw std::runtime_error(run.first_error);
+  sum_up(sum, run.part, t0);
   outstream.close();
-  sum.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  sum.ms_total = ms_since(t0);
   std::cerr << "[wfmash::align] total aligned records = " << sum.records << ", total aligned bp = " << sum.aligned_bp
             << ", completed in " << (uint64_t)(sum.ms_total / 1000.0) << " seconds" << std::endl;
   return sum;

@@ -5,7 +5,9 @@
 // of one Taskflow task per record (computeAlignments.hpp:398-435).
 #pragma once
 
+#include <chrono>
 #include <cstdint>
+#include <iosfwd>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -13,6 +15,7 @@
 #include <vector>
 
 #include "../../include/wfmash_hip.h"
+#include "align_plan.hpp"
 #include "fasta.hpp"
 #include "wflign_hip.hpp"
 
@@ -91,14 +94,26 @@ class Aligner {
   Summary compute();  // streams param.mashmapPafFile through the GPUs into param.pafOutputFile
   // Aligns mapping lines already in memory on the first GPU; returns the PAF text.
   std::string align_lines(const std::vector<std::string>& lines, Summary& sum);
-  // Bytes of the mapping file one batch may hold (~0: no limit beyond batch_records / batch_bases).  file_bytes = 0: the
-  // file cannot be rewound or is empty.  rows / row_bytes / row_bases_sum: the first rows looked at (rows = 0: none).
-  static uint64_t plan_batch_bytes(uint64_t file_bytes, uint64_t rows, uint64_t row_bytes, uint64_t row_bases_sum, uint64_t batch_records,
-                                   uint64_t batch_bases, uint64_t nworkers, uint64_t ngpu, uint64_t min_batches, bool level);
 
  private:
+  // ---- one batch of mapping rows on one handle (aligner.cpp: align_batch and its stages) ----
+  struct Fetched;     // a row, its windows and where its sides are
+  struct BatchTimes;  // the stages' times, into the Summary at the end
   std::string align_batch(wfm_handle_t* gpu, std::vector<std::string>& lines, int threads, Summary& sum, uint64_t first_row = 0);
-  static uint64_t row_bases(const std::string& line);
+  std::vector<Fetched> parse_rows(std::vector<std::string>& lines, uint64_t first_row, Summary& sum) const;
+  void fetch_windows(Fetched& f) const;
+  std::vector<Fetched> fetch_eager(std::vector<Fetched>& rows, int threads, Summary& sum) const;
+  static void point_at(wflign::BiwfaRecord& r, const Fetched& f);
+  static std::vector<wflign::BiwfaRecord> make_records(const std::vector<Fetched>& fetched);
+  static void account(Summary& sum, const wflign::BiwfaStats& st, const wflign::ResidentSeqs& resident, const std::vector<Fetched>& fetched,
+                      const std::vector<wflign::BiwfaRecord>& recs);
+  static std::string gather_text(Summary& sum, const std::vector<Fetched>& fetched, const std::vector<wflign::BiwfaRecord>& recs);
+  // ---- the run over the mapping file (aligner.cpp: compute and its stages) ----
+  struct Run;  // what the workers of one compute() share
+  struct RunPlan { size_t per_gpu = 1, nworkers = 1; uint64_t batch_bytes = ~0ull; };
+  RunPlan plan_run(std::ifstream& in) const;
+  void run_worker(Run& run, size_t wk);
+  void sum_up(Summary& sum, const std::vector<Summary>& part, std::chrono::steady_clock::time_point t0) const;
   const Parameters& param;
   std::vector<wfm_handle_t*> gpus;
   std::shared_ptr<wfmash_host::FastaStore> ref, query_own;
@@ -115,6 +130,7 @@ class Aligner {
   std::mutex stores_mu;
   std::map<int, std::unique_ptr<DeviceStore>> stores;  // by device
   DeviceStore* device_store(wfm_handle_t* h);
+  void assign_resident_ids(wfm_handle_t* gpu, DeviceStore& ds, std::vector<Fetched>& rows);
   int32_t resident_id(wfm_handle_t* h, DeviceStore& ds, const wfmash_host::FastaStore* fa, int idx);
 };
 

@@ -115,11 +115,41 @@ void wfmh_test_subwindow(int64_t win_start, int64_t win_end, int rev, int64_t a,
   if (out_end) *out_end = off + (b - a);
 }
 
-// test hook: the align driver's batch plan (Aligner::plan_batch_bytes), pure arithmetic
+// test hook: the align driver's batch plan (plan_batch_bytes, host/align_plan.hpp), pure arithmetic
 unsigned long long wfmh_test_plan_batch_bytes(unsigned long long file_bytes, unsigned long long rows, unsigned long long row_bytes,
                                               unsigned long long row_bases_sum, unsigned long long batch_records, unsigned long long batch_bases,
                                               unsigned long long nworkers, unsigned long long ngpu, unsigned long long min_batches, int level) {
-  return align::Aligner::plan_batch_bytes(file_bytes, rows, row_bytes, row_bases_sum, batch_records, batch_bases, nworkers, ngpu, min_batches, level != 0);
+  return align::plan_batch_bytes(file_bytes, rows, row_bytes, row_bases_sum, batch_records, batch_bases, nworkers, ngpu, min_batches, level != 0);
+}
+
+// test hook: the align driver's other plans (host/align_plan.hpp), pure arithmetic on doubles (-1 stands for "none" / "no limit").
+// op 0: workers_per_gpu -- in = threads, ngpu, override; out = {workers}
+// op 1: estimate_batches -- in = file_bytes, rows, row_bytes, row_bases_sum, batch_records, batch_bases, batch_bytes; out = {batches or -1}
+// op 2: interval_union -- in = n x (from, to); out = {intervals of the union, their total length, then the intervals}
+// op 3: the twenty-bin histogram of the union over span_of the sorted input (n >= 1) -- out = {total, span, then 20 bins}
+int wfmh_test_align_plan(int op, const double* in, int64_t n, double* out) {
+  auto u64 = [](double v) { return v < 0 ? ~0ull : (uint64_t)v; };
+  if (op == 0) { out[0] = (double)align::workers_per_gpu((size_t)in[0], (size_t)in[1], (size_t)in[2]); return 0; }
+  if (op == 1) {
+    const uint64_t b = align::estimate_batches(u64(in[0]), u64(in[1]), u64(in[2]), u64(in[3]), u64(in[4]), u64(in[5]), u64(in[6]));
+    out[0] = b == ~0ull ? -1.0 : (double)b;
+    return 0;
+  }
+  if (op != 2 && op != 3) return -1;
+  std::vector<align::Interval> v;
+  for (int64_t i = 0; i < n; ++i) v.emplace_back(in[2 * i], in[2 * i + 1]);
+  const std::vector<align::Interval> u = align::interval_union(v);
+  if (op == 2) {
+    out[0] = (double)u.size(); out[1] = align::total_length(u);
+    for (size_t i = 0; i < u.size(); ++i) { out[2 + 2 * i] = u[i].first; out[3 + 2 * i] = u[i].second; }
+    return 0;
+  }
+  if (v.empty()) return -1;
+  const align::Interval sp = align::span_of(v);
+  const std::vector<double> bins = align::covered_per_bin(u, sp.first, sp.second, 20);
+  out[0] = align::total_length(u); out[1] = sp.second;
+  std::copy(bins.begin(), bins.end(), out + 2);
+  return 0;
 }
 
 // test hook: which ring a BiWFA job gets (csrc/wfa_plan.h, plan_ring), pure arithmetic.  node: pl, tl, score_rem, sub, noband, band;
@@ -326,60 +356,31 @@ char* wfmh_test_cigar(const char* fn, const char* a, const char* b, const char* 
                       long long i0, long long i1) {
   std::string f = fn ? fn : "", sa = a ? a : "", sb = b ? b : "", q = query ? query : "", t = target ? target : "";
   std::string r;
-  if (f == "erode") r = wflign::erode_short_matches_in_cigar(sa, (int)i0, i1 != 0);
-  else if (f == "merge") r = wflign::merge_adjacent_ops(sa, sb);
+  const wflign::CigarOps o2 = wflign::parse_cigar(sb);
+  wflign::CigarOps o = wflign::parse_cigar(sa);  // every CIGAR helper: parse, the run form, text
+  auto erosion = [](const wflign::Erosion& e, size_t third) { return std::to_string(e.query_eroded) + "," + std::to_string(e.target_eroded) + "," + std::to_string(third); };
+  if (f == "erode") { wflign::erode_short_matches_in_cigar(o, (int)i0, i1 != 0); r = wflign::cigar_to_string(o); }
+  else if (f == "merge") { wflign::merge_adjacent_ops(o, o2, 0, o2.size()); r = wflign::cigar_to_string(o); }
   else if (f == "compress") r = wflign::compress_ops(sa.data(), sa.size());
-  else if (f == "swap_start") r = wflign::try_swap_start_pattern(sa, q, t, 0, 0);
-  else if (f == "swap_end") r = wflign::try_swap_end_pattern(sa, q, t, 0, 0);
-  // ---- the batch pipeline's forms on runs (count, op): held against the text forms above by the CPU suite ----
-  else if (f == "erode_ops") {
-    wflign::CigarOps o = wflign::parse_cigar(sa);
-    wflign::erode_short_matches_ops(o, (int)i0, i1 != 0);
-    r = wflign::cigar_to_string(o);
-  } else if (f == "merge_ops") {
-    wflign::CigarOps o = wflign::parse_cigar(sa);
-    const wflign::CigarOps o2 = wflign::parse_cigar(sb);
-    wflign::append_merged(o, o2, 0, o2.size());
-    r = wflign::cigar_to_string(o);
-  } else if (f == "swap_start_ops") {
-    wflign::CigarOps o = wflign::parse_cigar(sa);
-    wflign::try_swap_start_ops(o, q.data(), (int64_t)q.size(), t.data(), (int64_t)t.size());
-    r = wflign::cigar_to_string(o);
-  } else if (f == "swap_end_ops") {
-    wflign::CigarOps o = wflign::parse_cigar(sa);
-    wflign::try_swap_end_ops(o, q.data(), (int64_t)q.size(), t.data(), (int64_t)t.size());
-    r = wflign::cigar_to_string(o);
-  } else if (f == "head_erosion_ops") {  // third value: the text position behind the eroded runs, for comparison
-    const wflign::CigarOps o = wflign::parse_cigar(sa);
-    const wflign::Erosion e = wflign::scan_head_erosion_ops(o);
-    const size_t pos = wflign::cigar_to_string(wflign::CigarOps(o.begin(), o.begin() + (long)e.erode_end_pos)).size();
-    r = std::to_string(e.query_eroded) + "," + std::to_string(e.target_eroded) + "," + std::to_string(pos);
+  else if (f == "swap_start") { wflign::try_swap_start_pattern(o, q.data(), (int64_t)q.size(), t.data(), (int64_t)t.size()); r = wflign::cigar_to_string(o); }
+  else if (f == "swap_end") { wflign::try_swap_end_pattern(o, q.data(), (int64_t)q.size(), t.data(), (int64_t)t.size()); r = wflign::cigar_to_string(o); }
+  else if (f == "head_erosion") {  // third value: the text position behind the eroded runs
+    const wflign::Erosion e = wflign::scan_head_erosion(o);
+    r = erosion(e, wflign::cigar_to_string(o, 0, e.erode_end_pos).size());
+  } else if (f == "tail_erosion") {
+    const wflign::Erosion e = wflign::scan_tail_erosion(o);
+    r = erosion(e, e.erode_start_idx);
+  } else if (f == "patch_plan") {  // head erosion (third value: runs eroded), tail erosion, head wanted, tail wanted, tail independent
+    const wflign::PatchPlan pl = wflign::plan_patches(o);
+    r = erosion(pl.head, pl.head.erode_end_pos) + "," + erosion(pl.tail, pl.tail.erode_start_idx) + "," + std::to_string((int)pl.head_wanted) + "," +
+        std::to_string((int)pl.tail_wanted) + "," + std::to_string((int)pl.tail_independent);
   } else if (f == "runs") {  // a = runs as decimal numbers separated by commas -> CIGAR text
     std::vector<uint32_t> runs;
     std::stringstream ss(sa);
     std::string item;
     while (std::getline(ss, item, ',')) if (!item.empty()) runs.push_back((uint32_t)std::stoul(item));
-    wflign::CigarOps o;
     wflign::ops_from_runs(runs.data(), runs.size(), o);
     r = wflign::cigar_to_string(o);
-  } else if (f == "paf_ops") {
-    std::vector<std::string> p;
-    std::stringstream ss(sb);
-    std::string item;
-    while (std::getline(ss, item, '|')) p.push_back(item);
-    if (p.size() == 12) {
-      wflign::PafParams pp;
-      wflign::write_alignment_paf_ops(r, wflign::parse_cigar(sa), p[0], std::stoull(p[1]), std::stoull(p[2]), std::stoull(p[3]), p[4] == "1", p[5],
-                                      std::stoull(p[6]), std::stoull(p[7]), pp, std::stof(p[8]), std::stoi(p[9]), std::stoi(p[10]),
-                                      std::stoi(p[11]));
-    }
-  }
-  else if (f == "head_erosion") {
-    const wflign::Erosion e = wflign::scan_head_erosion(sa);
-    r = std::to_string(e.query_eroded) + "," + std::to_string(e.target_eroded) + "," + std::to_string(e.erode_end_pos);
-  } else if (f == "tail_erosion") {
-    const wflign::Erosion e = wflign::scan_tail_erosion(wflign::parse_cigar(sa));
-    r = std::to_string(e.query_eroded) + "," + std::to_string(e.target_eroded) + "," + std::to_string(e.erode_start_idx);
   } else if (f == "paf") {
     // b = qname|qtotal|qoff|qlen|qrev|tname|ttotal|toff|mmid|chain_id|chain_len|chain_pos
     std::vector<std::string> p;
@@ -388,7 +389,7 @@ char* wfmh_test_cigar(const char* fn, const char* a, const char* b, const char* 
     while (std::getline(ss, item, '|')) p.push_back(item);
     if (p.size() == 12) {
       wflign::PafParams pp;
-      wflign::write_alignment_paf(r, sa, p[0], std::stoull(p[1]), std::stoull(p[2]), std::stoull(p[3]), p[4] == "1", p[5],
+      wflign::write_alignment_paf(r, o, p[0], std::stoull(p[1]), std::stoull(p[2]), std::stoull(p[3]), p[4] == "1", p[5],
                                   std::stoull(p[6]), std::stoull(p[7]), pp, std::stof(p[8]), std::stoi(p[9]), std::stoi(p[10]),
                                   std::stoi(p[11]));
     }
@@ -409,7 +410,7 @@ char* wfmh_test_cigar(const char* fn, const char* a, const char* b, const char* 
       for (size_t i = 0; i < keep.size(); ++i) { if (i) r += ","; r += std::to_string((int)keep[i]) + ":" + std::to_string((int)ident[i]); }
     }
   } else if (f == "md") {
-    r = wflign::md_string(sa, (int)i0, t.c_str());
+    r = wflign::md_string(o, 0, o.size(), (int)i0, t.c_str());
   } else if (f == "parse_row") {
     try {
       align::MappingBoundaryRow row;

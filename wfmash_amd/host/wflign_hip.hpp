@@ -6,10 +6,11 @@
 // aligns one mapping record per Taskflow task; here every stage of
 // do_biwfa_alignment runs over a whole batch so each stage is one
 // wfm_align_batch call on the GPU:
-//   stage 1    main BiWFA alignment                        (wflign.cpp:136-165)
-//   stage 2+3  erosion scans + ends-free head and tail patches, one call for both
-//                                                          (wflign.cpp:241-320, 323-418)
-//   stage 4    swizzle + PAF record                         (wflign.cpp:423-454)
+//   align_main         main BiWFA alignment, runs, plan_patches      (wflign.cpp:136-165)
+//   patch_ends         ends-free head and tail patches, one call for both
+//                                                            (wflign.cpp:241-320, 323-418)
+//   patch_late_tails   the tails whose scan has to see the patched head  (wflign.cpp:323-418)
+//   swizzle_and_write  swizzle + PAF / SAM record             (wflign.cpp:423-454)
 // and CIGARs are runs (count, op) from the device to the record's text: nothing is expanded to one byte per base.
 #pragma once
 
@@ -22,6 +23,7 @@
 #include <vector>
 
 #include "../../include/wfmash_hip.h"
+#include "cigar_ops.hpp"  // CigarOps, the CIGAR helpers, plan_patches, PafParams and the two record writers
 
 namespace wflign {
 
@@ -34,71 +36,6 @@ struct wflign_penalties_t {
   int gap_opening2 = 24;
   int gap_extension2 = 1;
 };
-
-using CigarOps = std::vector<std::pair<int, char>>;
-
-// ---- CIGAR helpers (behaviour of the lambdas at wflign.cpp:174-238) ----
-CigarOps parse_cigar(const std::string& cigar);
-std::string cigar_to_string(const CigarOps& ops);
-// long-form op string {M,X,I,D} -> run-length CIGAR with M written as '='
-// (wfa_edit_cigar_to_string, wflign_swizzle.cpp:359-382; compress_cigar, wflign.cpp:183-208)
-std::string compress_ops(const char* ops, size_t n);
-std::string merge_adjacent_ops(const std::string& cigar1, const std::string& cigar2);  // wflign.cpp:211-238
-std::string erode_short_matches_in_cigar(const std::string& cigar, int max_match_length = 3,
-                                         bool is_head_cigar = true);                  // wflign.cpp:19-106
-
-struct Erosion {
-  uint64_t query_eroded = 0, target_eroded = 0;
-  size_t erode_end_pos = 0;    // head: byte position in the CIGAR string after the eroded ops
-  size_t erode_start_idx = 0;  // tail: index of the first eroded op
-};
-Erosion scan_head_erosion(const std::string& main_cigar);                       // wflign.cpp:241-276
-Erosion scan_tail_erosion(const CigarOps& ops);                                 // wflign.cpp:331-364
-
-// ---- the same on runs (the batch pipeline's form; "position in the text" = index of the run) ----
-void ops_from_runs(const uint32_t* runs, size_t n, CigarOps& out);            // wfm_align_batch_rle runs -> (count, op), M as '='
-bool erode_short_matches_ops(CigarOps& ops, int max_match_length, bool is_head_cigar);
-void append_merged(CigarOps& dst, const CigarOps& src, size_t from, size_t to);
-Erosion scan_head_erosion_ops(const CigarOps& ops);                           // erode_end_pos = runs eroded
-bool try_swap_start_ops(CigarOps& ops, const char* q, int64_t qn, const char* t, int64_t tn);
-bool try_swap_end_ops(CigarOps& ops, const char* q, int64_t qn, const char* t, int64_t tn);
-
-// ---- swizzle (wflign_swizzle.cpp:217-299) ----
-std::string try_swap_start_pattern(const std::string& cigar, const std::string& query_seq,
-                                   const std::string& target_seq, int64_t query_start, int64_t target_start);
-std::string try_swap_end_pattern(const std::string& cigar, const std::string& query_seq,
-                                 const std::string& target_seq, int64_t query_start, int64_t target_start);
-
-// ---- PAF record (wflign_patch.cpp:2611-2734) ----
-double float2phred(double prob);
-struct PafParams {
-  float min_identity = 0.0f;
-  uint64_t min_alignment_length = 32;
-  float min_block_identity = 0.1f;
-};
-// Returns true and appends one PAF line (with the trailing tab of the
-// reference writer, no newline) if the record passes the filters.
-bool write_alignment_paf(std::string& out, const std::string& cigar_str, const std::string& query_name,
-                         uint64_t query_total_length, uint64_t query_offset, uint64_t query_length, bool query_is_rev,
-                         const std::string& target_name, uint64_t target_total_length, uint64_t target_offset,
-                         const PafParams& pp, float mashmap_estimated_identity, int32_t chain_id, int32_t chain_length,
-                         int32_t chain_pos);
-
-// The same from runs, in the form the align driver writes in the end: fields joined by single tabs, closing newline
-// (processMappingRecord re-tokenises the writer's text, computeAlignments.hpp:484-525).
-bool write_alignment_paf_ops(std::string& out, const CigarOps& ops, const std::string& query_name, uint64_t query_total_length,
-                             uint64_t query_offset, uint64_t query_length, bool query_is_rev, const std::string& target_name,
-                             uint64_t target_total_length, uint64_t target_offset, const PafParams& pp,
-                             float mashmap_estimated_identity, int32_t chain_id, int32_t chain_length, int32_t chain_pos);
-
-// SAM record (wflign_patch.cpp:2480-2609) incl. the MD:Z tag (write_tag_and_md_string :2397-2478).
-// `query` / `target` are the strand-adjusted query window and the target window (target offset 0).
-bool write_alignment_sam(std::string& out, const std::string& cigar_str, const std::string& query_name,
-                         uint64_t query_offset, bool query_is_rev, const std::string& target_name,
-                         uint64_t target_offset, const PafParams& pp, float mashmap_estimated_identity,
-                         bool no_seq_in_sam, bool emit_md_tag, const char* query, const char* target,
-                         int32_t chain_id, int32_t chain_length, int32_t chain_pos);
-std::string md_string(const std::string& cigar, int target_start, const char* target);  // "MD:Z:..."
 
 // ---- batch form of do_biwfa_alignment (wflign.cpp:108-483) ----
 struct BiwfaRecord {
