@@ -265,6 +265,36 @@ int wfm_align_refs_rle(wfm_handle_t* h, const wfm_penalties_t* pen, const wfm_se
  * out (may be NULL); returns the buffer's size or a WFM_E_* code. */
 int64_t wfm_download_sequences(wfm_handle_t* h, const wfm_seqset_t* s, uint8_t* out, int64_t cap);
 
+/* ---- every run of a CIGAR held against the bases it covers ----
+ * A self-check that is independent of the aligners: it reads the forward BYTE copies of the seqset (never the 2-bit mirror the
+ * kernels extend on) and shares no code with the cell step or the walk back (wfmash_amd/csrc/wfa_check.hip).  s is any seqset,
+ * res[i].ops_off / res[i].n_runs locate problem i's runs in `runs` in the format of wfm_align_batch_rle, out receives one
+ * wfm_check_t per problem of s.  Bases are compared as bytes, as oracle/wfa2p.c compares them: N equals N, 'a' differs from 'A',
+ * nothing is normalised.  The price: X costs x per base, a gap run of L bases min(o1 + e1 L, o2 + e2 L); in a WFM_MODE_ENDSFREE
+ * problem the first run loses up to pattern_begin_free (D) or text_begin_free (I) bases before it is priced and the last run up
+ * to pattern_end_free / text_end_free (a single run may use both allowances of its side) -- the score alignEndsFree reports.
+ * bad_p / bad_t / bad_run name the offending base with the smallest pattern index, whatever order the device finds them in;
+ * without one, bad_p = bad_t = -1 and bad_run is the first bad run (0: none).  No byte outside the problem's two sequences is
+ * read: bases are compared only where the runs' totals do not exceed plen and tlen (WFM_CK_SPANS alone otherwise).
+ * Returns the number of problems whose flags hold anything but WFM_CK_NOT_CHECKED, or a WFM_E_* code; a run range that leaves
+ * runs[0 .. n_runs_total) is WFM_E_ARG.  Optimality is not checked: that stays with the CPU oracle. */
+#define WFM_CK_NOT_CHECKED  1u  /* no runs to check: a score-only problem, or status != 0 */
+#define WFM_CK_BAD_RUN      2u  /* a run of length 0, or two adjacent runs with one op */
+#define WFM_CK_SPANS        4u  /* the runs do not span exactly plen pattern and tlen text bases */
+#define WFM_CK_M_DIFFERS    8u  /* an M run covers two different bytes */
+#define WFM_CK_X_EQUAL     16u  /* an X run covers two equal bytes */
+#define WFM_CK_SCORE       32u  /* the price of the runs is not res[i].score (compared only when res[i].score >= 0) */
+#define WFM_CK_COUNTS      64u  /* ops_len of the result differs from what its n_runs runs spell (a wrong n_runs shows here too) */
+typedef struct {
+  uint32_t flags; int32_t score;        /* price of the runs under pen (ENDSFREE: ends-free price, above) */
+  int32_t  bad_p, bad_t;                /* pattern / text index of the FIRST offending base (-1: none) */
+  uint32_t bad_run, n_runs;             /* index of the run that holds it (or of the first bad run); runs read */
+  uint32_t matches, mismatches, ins_runs, ins_bases, del_runs, del_bases;
+} wfm_check_t;                          /* 48 bytes */
+#define WFM_CHECK_SLICE 16384           /* ops one compare task covers, as WFM_SEQ_GATHER_CHUNK */
+int wfm_check_runs(wfm_handle_t* h, const wfm_penalties_t* pen, const wfm_seqset_t* s,
+                   const wfm_result_t* res, const uint32_t* runs, size_t n_runs_total, wfm_check_t* out);
+
 /* How many other align calls the caller keeps in flight on this handle's DEVICE while a call on this handle runs (the align
  * driver's workers, each on a handle of its own: wfmash_amd/host/aligner.cpp).  0, the default: none -- a batch is then cut
  * into up to three parts that run side by side on streams of their own, because the levels of a batch of near-identical

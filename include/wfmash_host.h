@@ -81,6 +81,27 @@ int wfmh_align_paf_multi(wfm_handle_t* const* handles, int n, const char* target
                          const char* mapping_paf, const char* out_paf,
                          const wfmh_align_params_t* params, wfmh_align_summary_t* summary);
 
+/* ---- every aligned PAF line held against the bases it names (wfmash_amd/host/verify_paf.hpp) ----
+ * A finished line is parsed on its own -- names, qs, qe, strand, ts, te as written, cg:Z: -- and becomes a problem by reference:
+ * pattern = target [ts, te), text = query [qs, qe) (reverse-complemented for '-'), both normalised as every window the driver
+ * fetches; the CIGAR becomes runs (= M, X X, I I, D D) and batches of lines go through wfm_upload_sequence_refs and
+ * wfm_check_runs (wfmash_hip.h), by store id where the run keeps its sequences on the device (resident_sequences), by host
+ * pointer otherwise.  A line without cg:Z: or with an op outside =XID (a plain M) is counted as unverifiable, not as failed.
+ * What is checked: spans, run structure, every M and X base.  What is not: optimality, which stays with the CPU oracle.
+ *
+ * wfmh_set_verify(1): from now on every wfmh_align_paf[_multi] call of the process verifies each batch's finished lines -- what
+ * the user gets after patching, erosion and swizzle -- before they are written; the output bytes do not change, a failure is
+ * one line on stderr (query, target, coordinates, flag names, first offending position), SAM output is not verified.  Every
+ * call of wfmh_set_verify zeroes the counts.  wfmh_verify_counts: out = {lines checked, failed, unverifiable, bases compared}
+ * since then.  wfmh_verify_paf: the same check on an existing aligned PAF (this build's or the reference's), no mapping and no
+ * alignment; query_fasta may be NULL (= target_fasta); out as above, for this call alone.  Returns 0 or WFM_E_*. */
+void wfmh_set_verify(int on);
+int  wfmh_verify_counts(uint64_t out[4]);
+int  wfmh_verify_paf(wfm_handle_t* h, const char* target_fasta, const char* query_fasta, const char* aligned_paf, uint64_t out[4]);
+/* Test hook (no GPU): a line as the verifier reads it -- "ok", qname, qs, qe, strand, tname, ts, te and the runs spelled back as
+ * a CIGAR over =XID, separated by tabs; or "unverifiable" / "malformed" and the reason.  Release with wfmh_free. */
+char* wfmh_test_verify_parse(const char* line);
+
 /* Test hooks: the pure host-side CIGAR functions (erode / merge / swizzle / PAF writer /
  * parseMashmapRow) behind one string interface so the CPU test-suite can check them
  * without a GPU.  fn in {erode, merge, compress, swap_start, swap_end, head_erosion,

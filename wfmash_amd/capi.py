@@ -44,7 +44,12 @@ EXPORTS = [
     "wfm_sketch_part", "wfm_minmer_part_info", "wfm_minmer_part_download", "wfm_minmer_part_free", "wfm_index_build_parts",
     "wfm_seqstore_create", "wfm_seqstore_free", "wfm_seqstore_add", "wfm_seqstore_info",
     "wfm_upload_sequence_refs", "wfm_align_refs_rle", "wfm_download_sequences",
+    "wfm_check_runs",
 ]
+# wfm_check_runs (include/wfmash_hip.h): what a problem's runs were flagged for
+WFM_CK_NOT_CHECKED, WFM_CK_BAD_RUN, WFM_CK_SPANS, WFM_CK_M_DIFFERS, WFM_CK_X_EQUAL, WFM_CK_SCORE, WFM_CK_COUNTS = 1, 2, 4, 8, 16, 32, 64
+CK_NAMES = ("NOT_CHECKED", "BAD_RUN", "SPANS", "M_DIFFERS", "X_EQUAL", "SCORE", "COUNTS")
+CHECK_SLICE = 16384  # WFM_CHECK_SLICE: ops one compare task covers
 SEQ_GATHER_CHUNK = 16384  # WFM_SEQ_GATHER_CHUNK (include/wfmash_hip.h): destination bytes per task of the gather kernel
 
 
@@ -79,6 +84,14 @@ class Result(C.Structure):
     _fields_ = [("status", C.c_int32), ("score", C.c_int32),
                 ("ops_off", C.c_uint64), ("ops_len", C.c_uint32),
                 ("n_runs", C.c_uint32), ("cells", C.c_uint64)]
+
+
+class Check(C.Structure):
+    """wfm_check_t: what wfm_check_runs found in one problem's runs."""
+    _fields_ = [("flags", C.c_uint32), ("score", C.c_int32), ("bad_p", C.c_int32), ("bad_t", C.c_int32),
+                ("bad_run", C.c_uint32), ("n_runs", C.c_uint32),
+                ("matches", C.c_uint32), ("mismatches", C.c_uint32), ("ins_runs", C.c_uint32), ("ins_bases", C.c_uint32),
+                ("del_runs", C.c_uint32), ("del_bases", C.c_uint32)]
 
 
 class Stats(C.Structure):
@@ -595,6 +608,47 @@ class Handle:
             raise WfmError(f"wfm_score_bounds failed ({rc}): {self.last_error()}")
         return out[:n]
 
+    def align_resident_rle(self, seqset, pen=None):
+        """wfm_align_resident_rle: fills seqset.results (ops_off / n_runs index the runs) and returns (failed, runs as a uint32 array)."""
+        pn = Penalties(*(pen or DEFAULT_PEN))
+        runs = C.POINTER(C.c_uint32)()
+        total = C.c_size_t(0)
+        f = self._L.wfm_align_resident_rle
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_size_t)]
+        self._L.wfm_free_runs.restype = None
+        self._L.wfm_free_runs.argtypes = [C.POINTER(C.c_uint32)]
+        rc = f(self._p, C.byref(pn), seqset._p, seqset.results, C.byref(runs), C.byref(total))
+        if rc < 0:
+            raise WfmError(f"wfm_align_resident_rle failed ({rc}): {self.last_error()}")
+        try:
+            arr = np.ctypeslib.as_array(runs, shape=(total.value,)).copy() if total.value else np.zeros(0, dtype=np.uint32)
+        finally:
+            self._L.wfm_free_runs(runs)
+        return rc, arr
+
+    def check_runs(self, seqset, results, runs, pen=None):
+        """wfm_check_runs: every run held against the bases it covers.  results: a ctypes array of Result (seqset.results after an
+        align call) or a list of (status, score, ops_off, ops_len, n_runs), one per problem of the seqset; runs: uint32 runs,
+        (length << 2) | op.  Returns (flagged, [Check])."""
+        n = seqset.n
+        if not isinstance(results, C.Array):
+            arr = (Result * max(n, 1))()
+            assert len(results) == n, (len(results), n)
+            for i, (status, score, ops_off, ops_len, n_runs) in enumerate(results):
+                arr[i].status, arr[i].score, arr[i].ops_off, arr[i].ops_len, arr[i].n_runs = status, score, ops_off, ops_len, n_runs
+            results = arr
+        runs = np.ascontiguousarray(runs, dtype=np.uint32)
+        pn = Penalties(*(pen or DEFAULT_PEN))
+        out = (Check * max(n, 1))()
+        f = self._L.wfm_check_runs
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        rc = f(self._p, C.byref(pn), seqset._p, results, runs.ctypes.data if len(runs) else None, len(runs), out)
+        if rc < 0:
+            raise WfmError(f"wfm_check_runs failed ({rc}): {self.last_error()}")
+        return rc, [out[i] for i in range(n)]
+
     def align_rle(self, items, pen=None):
         """wfm_align_batch_rle: the same problems, run-length output.  AlignResult.ops is the list of (length, op) runs
         with op in b'MXID' (adjacent runs never share an op), .n_runs their number; `ops_len` travels as an extra
@@ -912,7 +966,7 @@ HOST_EXPORTS = ["wfmh_test_packed_lce", "wfmh_test_is_acgt", "wfmh_align_default
                 "wfmh_map_multi", "wfmh_align_paf_multi", "wfmh_test_winnow_model", "wfmh_test_sortlike_model", "wfmh_test_finish_records",
                 "wfmh_release_sequences", "wfmh_test_fasta_shared", "wfmh_seed_paf", "wfmh_test_deal", "wfmh_test_subwindow",
                 "wfmh_test_rows", "wfmh_test_tile_plan", "wfmh_test_p2_plan", "wfmh_test_base_plan", "wfmh_test_map_plan", "wfmh_test_filter_ordered",
-                "wfmh_test_reuse_plan", "wfmh_test_tile_plan_dirs", "wfmh_test_tile_interior", "wfmh_test_tile_lean_waves"]
+                "wfmh_test_reuse_plan", "wfmh_test_tile_plan_dirs", "wfmh_test_tile_interior", "wfmh_test_tile_lean_waves", "wfmh_set_verify", "wfmh_verify_counts", "wfmh_verify_paf", "wfmh_test_verify_parse"]
 
 
 class MapSummary(C.Structure):
@@ -1168,6 +1222,50 @@ def host_cigar_fn(fn, a=b"", b=b"", query=b"", target=b"", i0=0, i1=0) -> str:
     L = _host()
     enc = lambda x: x if isinstance(x, bytes) else x.encode()
     p = L.wfmh_test_cigar(enc(fn), enc(a), enc(b), enc(query), enc(target), i0, i1)
+    s = C.string_at(p).decode()
+    L.wfmh_free(p)
+    return s
+
+
+def set_verify(on: bool) -> None:
+    """wfmh_set_verify: every later align_paf call of the process verifies its finished PAF lines on the device; zeroes the counts."""
+    f = _host().wfmh_set_verify
+    f.restype = None
+    f.argtypes = [C.c_int]
+    f(1 if on else 0)
+
+
+def verify_counts():
+    """wfmh_verify_counts: (lines checked, failed, unverifiable, bases compared) since wfmh_set_verify was last called."""
+    f = _host().wfmh_verify_counts
+    f.restype = C.c_int
+    f.argtypes = [C.POINTER(C.c_uint64)]
+    out = (C.c_uint64 * 4)()
+    rc = f(out)
+    if rc != 0:
+        raise WfmError(f"wfmh_verify_counts failed ({rc})")
+    return tuple(int(v) for v in out)
+
+
+def verify_paf(handle, target_fasta, aligned_paf, query_fasta=None):
+    """wfmh_verify_paf: an existing aligned PAF held against its bases; returns (checked, failed, unverifiable, bases compared)."""
+    f = _host().wfmh_verify_paf
+    f.restype = C.c_int
+    f.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_uint64)]
+    out = (C.c_uint64 * 4)()
+    rc = f(handle._p, os.fsencode(target_fasta), os.fsencode(query_fasta) if query_fasta else None, os.fsencode(aligned_paf), out)
+    if rc != 0:
+        raise WfmError(f"wfmh_verify_paf failed ({rc}): {handle.last_error()}")
+    return tuple(int(v) for v in out)
+
+
+def host_verify_parse(line) -> str:
+    """wfmh_test_verify_parse (no GPU): a PAF line as the verifier reads it, fields separated by tabs."""
+    L = _host()
+    f = L.wfmh_test_verify_parse
+    f.restype = C.c_void_p
+    f.argtypes = [C.c_char_p]
+    p = f(line if isinstance(line, bytes) else line.encode())
     s = C.string_at(p).decode()
     L.wfmh_free(p)
     return s

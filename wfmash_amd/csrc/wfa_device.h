@@ -225,6 +225,22 @@ void launch_reverse(uint8_t* seq, const SeqRev* jobs, int njobs, int pad, hipStr
 // most WFM_SEQ_GATHER_CHUNK bytes; the aligned 16-byte words of the source it reads reach at most 15 bytes beyond [src, src + len).
 struct SeqGatherTask { const uint8_t* src; uint8_t* dst; int32_t len, pad; int32_t reverse, complement; };
 void launch_seq_gather(const SeqGatherTask* tasks, int64_t ntasks, hipStream_t st);
+// wfm_check_runs (wfa_check.hip): a problem's forward byte copies in the seqset, its runs, and what its result claims
+struct CheckProb {
+  int64_t p_off, t_off;                // byte offsets of the forward copies in the sequence buffer
+  uint64_t run_off;                    // index of the problem's first run
+  uint32_t n_runs;
+  int32_t plen, tlen;
+  int32_t pbf, pef, tbf, tef;          // ENDSFREE allowances (0 for the other modes)
+  int32_t res_score;                   // < 0: the price is not compared
+  uint32_t res_ops_len;
+  int32_t skip;                        // nonzero: WFM_CK_NOT_CHECKED (score-only, or status != 0)
+};
+struct CheckTask { int32_t prob, slice; };  // ops [slice, slice + 1) * WFM_CHECK_SLICE of a problem
+// scan, compare and finish on st.  ops_pre / p_pre / t_pre: one element per run of the call; cmp_ops / keys: one per problem; out: nprob wfm_check_t
+void launch_check(const uint8_t* seq, const uint32_t* runs, const CheckProb* probs, int nprob, const CheckTask* tasks, int64_t ntasks,
+                  uint32_t* ops_pre, uint32_t* p_pre, uint32_t* t_pre, uint32_t* cmp_ops, unsigned long long* keys, void* out, DevPen pen,
+                  hipStream_t st);
 // makeUpperCaseAndValidDNA in place on nbytes (rounded up to 16) from a 16-byte aligned device address (wfm_seqstore_add)
 void launch_seq_normalize(uint8_t* seq, int64_t nbytes, hipStream_t st);
 // the 2-bit mirror of the sequence buffer (word i = bytes 16 i .. 16 i + 15) and, per BiWFA problem, "pure ACGT" (flag stays nonzero)

@@ -278,6 +278,7 @@ struct wfm_handle {
   DevBuf<int32_t> seqflags;  // wfm_upload_sequences: per problem, nonzero = pure ACGT
   DevBuf<SeqRev> flagjobs;
   DevBuf<SeqGatherTask> gathertasks;  // wfm_upload_sequence_refs
+  DevBuf<uint64_t> checkbuf;         // wfm_check_runs: everything the call has on the device, carved out of one block
   DevBuf<unsigned long long> total;
   void* attachment = nullptr;  // owned by another translation unit (map_kernels.hip: the pinned staging ring)
   void (*attachment_free)(void*) = nullptr;
@@ -2210,7 +2211,7 @@ void wfm_destroy(wfm_handle_t* h) {
   h->p2rows.release(); h->p2max.release(); h->p2bmax.release(); h->p2pbmax.release(); h->p2jobs.release(); h->widenjobs.release(); h->keeptasks.release(); h->restoretasks.release(); h->restoreres.release();
   h->bpjobs.release(); h->bpres.release(); h->bsjobs.release(); h->bsres.release();
   h->b2tjobs.release(); h->b2ttasks.release(); h->b2tkeys.release(); h->b2toffs.release(); h->b2tactive.release();
-  h->i64a.release(); h->i64b.release(); h->i64c.release(); h->i32a.release(); h->seqflags.release(); h->flagjobs.release(); h->gathertasks.release(); h->total.release();
+  h->i64a.release(); h->i64b.release(); h->i64c.release(); h->i32a.release(); h->seqflags.release(); h->flagjobs.release(); h->gathertasks.release(); h->checkbuf.release(); h->total.release();
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->ev2) (void)hipEventDestroy(h->ev2);
@@ -2658,6 +2659,77 @@ int64_t wfm_download_sequences(wfm_handle_t* h, const wfm_seqset_t* s, uint8_t* 
     HIPCHK(h, hipStreamSynchronize(h->stream));
   }
   return (int64_t)s->bytes;
+}
+
+// ---- every run held against its bases (wfmash_hip.h; the kernels: wfa_check.hip) ----
+int wfm_check_runs(wfm_handle_t* h, const wfm_penalties_t* pen, const wfm_seqset_t* s, const wfm_result_t* res, const uint32_t* runs,
+                   size_t n_runs_total, wfm_check_t* out) {
+  if (!h || !s || !out || !res || (n_runs_total && !runs)) return WFM_E_ARG;
+  int scope = 0;
+  if (const int prc = validate_pen(pen, &scope)) { h->err = "unsupported penalties"; return prc; }
+  const size_t n = s->meta.size();
+  if (n == 0) return 0;
+  if (n > (size_t)INT32_MAX || n_runs_total > ((size_t)1 << 32)) { h->err = "wfm_check_runs: too many problems or runs for one call"; return WFM_E_ARG; }
+  HIPCHK(h, hipSetDevice(h->device));
+  // the problems as the kernels see them; the run ranges are validated here, before anything is launched
+  std::vector<CheckProb> probs(n);
+  std::vector<CheckTask> tasks;
+  for (size_t i = 0; i < n; ++i) {
+    const ProbMeta& m = s->meta[i];
+    CheckProb& c = probs[i];
+    c.p_off = m.p_fwd; c.t_off = m.t_fwd;
+    c.plen = m.plen; c.tlen = m.tlen;
+    c.pbf = m.pbf; c.pef = m.pef; c.tbf = m.tbf; c.tef = m.tef;  // (0 unless the mode is ENDSFREE: layout_seqset)
+    c.res_score = res[i].score; c.res_ops_len = res[i].ops_len;
+    c.skip = (m.score_only() || res[i].status != 0) ? 1 : 0;
+    c.run_off = 0; c.n_runs = 0;
+    if (c.skip) continue;
+    if (res[i].ops_off > n_runs_total || (uint64_t)res[i].n_runs > n_runs_total - res[i].ops_off) {
+      h->err = "problem " + std::to_string(i) + ": its runs leave the run buffer";
+      return WFM_E_ARG;
+    }
+    c.run_off = res[i].ops_off; c.n_runs = res[i].n_runs;
+    // (compared runs spell at most plen + tlen ops: a slice beyond what the scan finds ends at once)
+    const int64_t slices = ((int64_t)m.plen + m.tlen + WFM_CHECK_SLICE - 1) / WFM_CHECK_SLICE;
+    for (int64_t q = 0; q < slices; ++q) tasks.push_back(CheckTask{(int32_t)i, (int32_t)q});
+  }
+  // one block: [runs | ops_pre | p_pre | t_pre | cmp_ops] as 32-bit words, then keys, results, problems and tasks (8-byte aligned each)
+  const size_t nr = n_runs_total;
+  auto words64 = [](size_t bytes) { return (bytes + 7) / 8; };
+  const size_t w_runs = words64(nr * 4), w_cmp = words64(n * 4), w_keys = n, w_out = words64(n * sizeof(wfm_check_t)),
+               w_probs = words64(n * sizeof(CheckProb)), w_tasks = words64(tasks.size() * sizeof(CheckTask));
+  if (h->checkbuf.ensure(4 * w_runs + w_cmp + w_keys + w_out + w_probs + w_tasks + 8)) { h->err = "out of device memory (run check)"; return WFM_E_NOMEM; }
+  uint64_t* at = h->checkbuf.p;
+  uint32_t* d_runs = (uint32_t*)at; at += w_runs;
+  uint32_t* d_opre = (uint32_t*)at; at += w_runs;
+  uint32_t* d_ppre = (uint32_t*)at; at += w_runs;
+  uint32_t* d_tpre = (uint32_t*)at; at += w_runs;
+  uint32_t* d_cmp = (uint32_t*)at; at += w_cmp;
+  unsigned long long* d_keys = (unsigned long long*)at; at += w_keys;
+  wfm_check_t* d_out = (wfm_check_t*)at; at += w_out;
+  CheckProb* d_probs = (CheckProb*)at; at += w_probs;
+  CheckTask* d_tasks = (CheckTask*)at;
+  if (nr) HIPCHK(h, hipMemcpyAsync(d_runs, runs, nr * 4, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(d_probs, probs.data(), n * sizeof(CheckProb), hipMemcpyHostToDevice, h->stream));
+  if (!tasks.empty()) HIPCHK(h, hipMemcpyAsync(d_tasks, tasks.data(), tasks.size() * sizeof(CheckTask), hipMemcpyHostToDevice, h->stream));
+  const bool timed = getenv("WFM_DEBUG") != nullptr;
+  if (timed) HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+  launch_check(s->d_seq, d_runs, d_probs, (int)n, d_tasks, (int64_t)tasks.size(), d_opre, d_ppre, d_tpre, d_cmp, d_keys, d_out,
+               DevPen{pen->x, pen->o1, pen->e1, pen->o2, pen->e2}, h->stream);
+  HIPCHK(h, hipGetLastError());
+  if (timed) HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+  HIPCHK(h, hipMemcpyAsync(out, d_out, n * sizeof(wfm_check_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (timed) {
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess)
+      fprintf(stderr, "[wfm] run check: %zu problems, %zu runs, %zu compare tasks, %llu bases of sequence in %.3f ms\n", n, nr, tasks.size(),
+              (unsigned long long)s->seq_bases, ms);
+    else (void)hipGetLastError();
+  }
+  int flagged = 0;
+  for (size_t i = 0; i < n; ++i) flagged += (out[i].flags & ~WFM_CK_NOT_CHECKED) != 0;
+  return flagged;
 }
 
 namespace {

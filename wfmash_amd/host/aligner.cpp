@@ -1,4 +1,5 @@
 #include "aligner.hpp"
+#include "verify_paf.hpp"
 #include "map_queue.hpp"
 #include "parallel.hpp"
 #include "../csrc/wfa_handle.h"
@@ -48,6 +49,8 @@ bool is_a_number(const std::string& s) {  // utils.cpp:9-11
   return !s.empty() && s.find_first_not_of("0123456789.") == std::string::npos && std::count(s.begin(), s.end(), '.') < 2;
 }
 
+}  // namespace
+
 // makeUpperCaseAndValidDNA (commonFunc.hpp:132-142)
 void upper_valid_dna(std::string& s) {
   for (auto& c : s) {
@@ -66,8 +69,6 @@ std::string revcomp(const std::string& s) {
   }
   return r;
 }
-
-}  // namespace
 
 struct Aligner::Fetched {
   MappingBoundaryRow row;
@@ -409,6 +410,18 @@ std::string Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<std::stri
   t.wflign = t.lap();
   std::string out = gather_text(sum, fetched, recs);
   t.text = t.lap();
+  if (verify::enabled() && !param.sam_format) {  // --verify: the finished lines, before they are written (SAM records carry no =/X CIGAR)
+    verify::Source src;
+    src.target = ref.get(); src.query = query; src.threads = threads;
+    if (ds) {
+      src.store = ds->store;
+      src.resident_id = [&](const wfmash_host::FastaStore* fa, int idx) { return resident_id(gpu_handle, *ds, fa, idx); };
+    }
+    verify::Counts vc;
+    verify::verify_text(gpu_handle, src, out, vc);
+    verify::add_counts(vc);
+    if (dbg) fprintf(stderr, "[wfmash::align] verify: %llu lines, %llu failed, %.1f ms\n", (unsigned long long)vc.checked, (unsigned long long)vc.failed, t.lap());
+  }
   sum.ms_rows += t.rows; sum.ms_fetch += t.fetch; sum.ms_wflign += t.wflign; sum.ms_text += t.text; sum.batches++;
   if (dbg)
     fprintf(stderr, "[wfmash::align] batch of %zu records on %d threads: rows %.1f ms, fetch %.1f ms, wflign %.1f ms (device busy %.1f), text %.1f ms\n",

@@ -82,6 +82,11 @@ struct Summary {
   std::vector<std::pair<double, double>> busy;  // a worker's device-busy intervals (merged per device at the end of compute())
 };
 
+// makeUpperCaseAndValidDNA (commonFunc.hpp:132-142) in place, and reverseComplement (commonFunc.hpp:74-83) on validated DNA: the
+// form every window the driver fetches is brought into (the PAF verifier fetches through them as well)
+void upper_valid_dna(std::string& s);
+std::string revcomp(const std::string& s);
+
 class Aligner {
  public:
   Aligner(const Parameters& p, wfm_handle_t* gpu);

@@ -16,6 +16,11 @@
 //                                              minmers (:137, :177; winSketch.hpp:467-497); no effect with -K or -i
 //   --resident-seqs                            whole sequences stay on the device (up to WFM_SEQSTORE_GB, 32) and the align phase names
 //                                              its windows by reference instead of fetching and uploading each; off by default
+//   --verify                                   every finished PAF line of the run is held against its bases on the device before it is
+//                                              written (spans, run structure, every = and X base; not optimality); a failure is one line
+//                                              on stderr and exit status 3 after everything has been written; refused together with -a
+//   --verify-paf FILE target.fa [query.fa]     the same check on an existing aligned PAF (this build's or the reference's): no mapping,
+//                                              no alignment; exit status 3 if a line fails
 //   --hg-filter n,D,conf                       numerator, ANI difference and confidence of the L1 / L2 cutoffs (:94, :700-725)
 //   -B DIR / -Z                                directory of the map-to-align hand-off file [cwd] / keep that file (:134-135)
 //   --quiet, --ani-sketch-size INT             accepted and without effect: there is no progress meter, and the identity
@@ -92,6 +97,8 @@ static void usage() {
           "            -Y C group delimiter [#]   -X self maps   -L lower triangular   -t INT threads [1]\n"
           "  alignment -g x,o1,e1,o2,e2 [5,8,2,24,1]   -E INT target padding   -U INT query padding   -a SAM   -d MD tag\n"
           "            --resident-seqs keep whole sequences on the GPU and align windows of them by reference [off]\n"
+          "            --verify check every PAF line written against its bases on the GPU (exit status 3 if one fails; not with -a)\n"
+          "            --verify-paf FILE check an existing aligned PAF against target.fa [query.fa] and stop (exit status 3 if a line fails)\n"
           "  other     --out FILE [stdout]   --device INT [0]   --gpus N|all [1] GPUs of this node, starting at --device\n"
           "            -B DIR directory of the hand-off file [cwd]   -Z keep the hand-off file   --quiet (no effect)\n");
 }
@@ -102,7 +109,8 @@ int main(int argc, char** argv) {
   ap.threads = 1;  // -t, default 1 as in the reference (parse_args.hpp: thread_count); the C ABI default (0) means all cores
   wfmh_map_params_t mp;
   wfmh_map_default_params(&mp);
-  std::string mapping_in, out = "/dev/stdout", target, query, seeds_in, scaffold_out, tmp_base;
+  std::string mapping_in, out = "/dev/stdout", target, query, seeds_in, scaffold_out, tmp_base, verify_in;
+  bool verify = false;
   bool approx_only = false, target_padding_given = false, query_padding_given = false, keep_temp = false;
   int device = 0, gpus = 1;
   for (int i = 1; i < argc; ++i) {
@@ -231,12 +239,27 @@ int main(int argc, char** argv) {
     else if (a == "-a" || a == "--sam") ap.sam_format = 1;
     else if (a == "-d" || a == "--md-tag") ap.emit_md_tag = 1;
     else if (a == "--resident-seqs") ap.resident_sequences = 1;
+    else if (a == "--verify") verify = true;
+    else if (a == "--verify-paf") verify_in = next("--verify-paf");
     else if (a == "-h" || a == "--help") { usage(); return 0; }
     else if (a == "-v" || a == "--version") { std::printf("%s\n", WFMASH_HIP_VERSION); return 0; }
     else if (a[0] != '-') { if (target.empty()) target = a; else query = a; }
     else { fprintf(stderr, "[wfmash] unknown option %s\n", a.c_str()); usage(); return 1; }
   }
   if (target.empty()) { fprintf(stderr, "[wfmash] ERROR: need a target FASTA\n"); usage(); return 1; }
+  if (verify && ap.sam_format) { fprintf(stderr, "[wfmash] ERROR: --verify reads the =/X CIGAR of PAF lines: it cannot be combined with -a (SAM)\n"); return 1; }
+  if (verify && approx_only) { fprintf(stderr, "[wfmash] ERROR: --verify checks alignments: it cannot be combined with -m\n"); return 1; }
+  if (!verify_in.empty()) {  // an existing PAF against its sequences; nothing else runs
+    wfm_handle_t* hv = nullptr;
+    if (wfm_create(device, &hv) != WFM_OK) { fprintf(stderr, "[wfmash] ERROR: no usable MI355X device %d (there is no CPU fallback)\n", device); return 2; }
+    uint64_t vc[4] = {0, 0, 0, 0};
+    const int vrc = wfmh_verify_paf(hv, target.c_str(), query.empty() ? nullptr : query.c_str(), verify_in.c_str(), vc);
+    if (vrc != WFM_OK) fprintf(stderr, "[wfmash::verify] ERROR: %s\n", wfm_last_error(hv));
+    else fprintf(stderr, "[wfmash::verify] %llu lines checked, %llu failed, %llu unverifiable, %llu bases compared\n", (unsigned long long)vc[0],
+                 (unsigned long long)vc[1], (unsigned long long)vc[2], (unsigned long long)vc[3]);
+    wfm_destroy(hv);
+    return vrc == WFM_OK && vc[1] == 0 ? 0 : 3;
+  }
   if (approx_only && !mapping_in.empty()) { fprintf(stderr, "[wfmash] ERROR: -m and -i exclude each other\n"); return 1; }
   if (!seeds_in.empty() && !mapping_in.empty()) { fprintf(stderr, "[wfmash] ERROR: -K (external seeds) and -i (align mappings from a file) exclude each other\n"); return 1; }
   if (!seeds_in.empty() && mp.index_file) { fprintf(stderr, "[wfmash] ERROR: -K (external seeds) does not read or write an index (-W / -I)\n"); return 1; }
@@ -330,15 +353,24 @@ int main(int argc, char** argv) {
     destroy_all();
     return rc == WFM_OK ? 0 : 3;
   }
+  bool verify_failed = false;
   if (rc == WFM_OK && !approx_only) {
     wfmh_align_summary_t s;
+    if (verify) wfmh_set_verify(1);
     rc = wfmh_align_paf_multi(hs.data(), (int)hs.size(), target.c_str(), q, mapping.c_str(), out.c_str(), &ap, &s);
     if (rc == WFM_OK)
       fprintf(stderr, "[wfmash::align] %llu records, %llu aligned bp, %.1f ms GPU kernels, %.1f ms total => %.3g aligned bp/s\n",
               (unsigned long long)s.records, (unsigned long long)s.aligned_bp, s.ms_gpu, s.ms_total, s.aligned_bp / (s.ms_total * 1e-3));
     else fprintf(stderr, "[wfmash::align] ERROR: %s\n", wfm_last_error(h));
+    if (verify && rc == WFM_OK) {  // everything has been written by now
+      uint64_t vc[4] = {0, 0, 0, 0};
+      wfmh_verify_counts(vc);
+      fprintf(stderr, "[wfmash::verify] %llu lines checked, %llu failed, %llu unverifiable, %llu bases compared\n", (unsigned long long)vc[0],
+              (unsigned long long)vc[1], (unsigned long long)vc[2], (unsigned long long)vc[3]);
+      verify_failed = vc[1] != 0;
+    }
   }
   release_temp();
   destroy_all();
-  return rc == WFM_OK ? 0 : 3;
+  return rc == WFM_OK && !verify_failed ? 0 : 3;
 }

@@ -1,0 +1,240 @@
+// verify_paf.cpp -- the PAF line verifier behind --verify and --verify-paf (verify_paf.hpp; C entry points at the end).
+#include "verify_paf.hpp"
+
+#include <algorithm>
+#include <atomic>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <iostream>
+#include <mutex>
+#include <stdexcept>
+#include <thread>
+
+#include "../../include/wfmash_host.h"
+#include "../csrc/wfa_handle.h"
+#include "aligner.hpp"
+#include "parallel.hpp"
+#include "wflign_hip.hpp"
+
+namespace verify {
+
+namespace {
+
+std::atomic<bool> g_enabled{false};
+std::atomic<uint64_t> g_counts[4];
+
+const char* const FLAG_NAMES[7] = {"NOT_CHECKED", "BAD_RUN", "SPANS", "M_DIFFERS", "X_EQUAL", "SCORE", "COUNTS"};
+std::string flag_names(uint32_t f) {
+  std::string s;
+  for (int b = 0; b < 7; ++b)
+    if (f & (1u << b)) { if (!s.empty()) s += '|'; s += FLAG_NAMES[b]; }
+  return s;
+}
+
+// one line of stderr per failed record (several workers verify at once)
+std::mutex g_report_mu;
+void report(const Line& l, const std::string& what, const std::string& where) {
+  std::lock_guard<std::mutex> lk(g_report_mu);
+  std::cerr << "[wfmash::verify] FAILED " << l.qname << ' ' << l.qs << '-' << l.qe << ' ' << (l.rev ? '-' : '+') << ' ' << l.tname << ' ' << l.ts << '-' << l.te
+            << ": " << what << where << std::endl;
+}
+
+constexpr int64_t MAX_PROBLEM_BASES = (int64_t)1 << 29;   // wfm_upload_sequence_refs' limit of plen + tlen
+constexpr int64_t BATCH_BASES = (int64_t)256 << 20;       // bases one device call holds
+constexpr size_t BATCH_LINES = 8192;
+
+// the lines in hand on the device: upload by reference, check, report
+void verify_batch(wfm_handle_t* h, const Source& src, std::vector<Line>& lines, Counts& c) {
+  if (lines.empty()) return;
+  const size_t n = lines.size();
+  std::vector<wfm_problem_ref_t> refs(n);
+  std::vector<wfm_result_t> res(n);
+  std::vector<std::string> pat(n), txt(n);  // the host-pointer sides, normalised
+  std::vector<uint32_t> runs;
+  for (size_t i = 0; i < n; ++i) {
+    const Line& l = lines[i];
+    wfm_problem_ref_t& r = refs[i];
+    memset(&r, 0, sizeof(r));
+    r.plen = (int32_t)(l.te - l.ts); r.tlen = (int32_t)(l.qe - l.qs);
+    r.mode = WFM_MODE_END2END_UNI;  // (no reversed copies are made for it)
+    r.pattern_seq = r.text_seq = -1;
+    const int ti = src.target->find(l.tname), qi = src.query->find(l.qname);
+    if (src.store && src.resident_id) {
+      if (r.plen) r.pattern_seq = src.resident_id(src.target, ti);
+      if (r.tlen) r.text_seq = src.resident_id(src.query, qi);
+    }
+    if (r.pattern_seq >= 0) r.pattern_off = l.ts;
+    if (r.text_seq >= 0) { r.text_off = l.qs; r.text_revcomp = l.rev ? 1 : 0; }
+    wfm_result_t& q = res[i];
+    memset(&q, 0, sizeof(q));
+    q.status = 0; q.score = -1;  // the price is not compared: a PAF line carries none
+    q.ops_off = runs.size(); q.n_runs = (uint32_t)l.runs.size();
+    uint64_t ops = 0;
+    for (uint32_t w : l.runs) ops += WFM_RUN_LEN(w);
+    q.ops_len = (uint32_t)std::min<uint64_t>(ops, 0xffffffffu);
+    runs.insert(runs.end(), l.runs.begin(), l.runs.end());
+  }
+  // the host-pointer sides, fetched and normalised as the align driver's windows are, on the caller's threads
+  std::atomic<bool> fetch_failed{false};
+  wfmash_host::parallel_for(n, std::max(1, src.threads), [&](size_t i) {
+    const Line& l = lines[i];
+    wfm_problem_ref_t& r = refs[i];
+    try {
+      if (r.pattern_seq < 0 && r.plen) {
+        pat[i] = src.target->fetch(l.tname, l.ts, l.te - 1);
+        align::upper_valid_dna(pat[i]);
+        r.pattern = pat[i].data();
+      }
+      if (r.text_seq < 0 && r.tlen) {
+        txt[i] = src.query->fetch(l.qname, l.qs, l.qe - 1);
+        align::upper_valid_dna(txt[i]);
+        if (l.rev) txt[i] = align::revcomp(txt[i]);
+        r.text = txt[i].data();
+      }
+      if ((r.pattern_seq < 0 && (int64_t)pat[i].size() != r.plen) || (r.text_seq < 0 && (int64_t)txt[i].size() != r.tlen)) fetch_failed.store(true);
+    } catch (const std::exception&) {
+      fetch_failed.store(true);
+    }
+  });
+  if (fetch_failed.load()) throw std::runtime_error("[wfmash::verify] cannot fetch the bases of a line's windows");
+  const wfm_penalties_t pen{5, 8, 2, 24, 1};  // (prices nothing that is compared)
+  std::vector<wfm_check_t> out(n);
+  {
+    std::lock_guard<std::mutex> lk(wflign::handle_lock(h));
+    wfm_seqset_t* S = nullptr;
+    int rc = wfm_upload_sequence_refs(h, src.store, refs.data(), n, &S);
+    if (rc == WFM_OK) {
+      rc = wfm_check_runs(h, &pen, S, res.data(), runs.data(), runs.size(), out.data());
+      wfm_free_sequences(h, S);
+    }
+    if (rc < 0) throw std::runtime_error(std::string("[wfmash::verify] device check failed: ") + wfm_last_error(h));
+  }
+  for (size_t i = 0; i < n; ++i) {
+    const Line& l = lines[i];
+    const wfm_check_t& k = out[i];
+    c.checked++;
+    c.bases += (uint64_t)k.matches + k.mismatches;
+    if (!(k.flags & ~WFM_CK_NOT_CHECKED)) continue;
+    c.failed++;
+    std::string where;
+    if (k.bad_p >= 0) {
+      const int64_t qpos = l.rev ? l.qe - 1 - k.bad_t : l.qs + k.bad_t;
+      where = "; first offending base: query " + std::to_string(qpos) + ", target " + std::to_string(l.ts + k.bad_p) + ", CIGAR run " + std::to_string(k.bad_run);
+    } else if (k.flags & WFM_CK_BAD_RUN) where = "; first bad CIGAR run " + std::to_string(k.bad_run);
+    report(l, flag_names(k.flags), where);
+  }
+  lines.clear();
+}
+
+}  // namespace
+
+void verify_text(wfm_handle_t* h, const Source& src, const std::string& text, Counts& c) {
+  std::vector<Line> batch;
+  int64_t bases = 0;
+  size_t at = 0;
+  while (at < text.size()) {
+    size_t nl = text.find('\n', at);
+    if (nl == std::string::npos) nl = text.size();
+    const std::string line = text.substr(at, nl - at);
+    at = nl + 1;
+    if (line.empty() || line[0] == '@') continue;
+    Line l;
+    std::string why;
+    const int st = parse_line(line, l, &why);
+    if (st == LINE_UNVERIFIABLE) { c.unverifiable++; continue; }
+    if (st == LINE_MALFORMED) {
+      c.checked++; c.failed++;
+      std::lock_guard<std::mutex> lk(g_report_mu);
+      std::cerr << "[wfmash::verify] FAILED line: " << why << ": " << line.substr(0, 120) << std::endl;
+      continue;
+    }
+    // the sequences the line names, as the files have them
+    const int64_t tl = src.target->seq_len(l.tname), ql = src.query->seq_len(l.qname);
+    if (tl < 0 || ql < 0) { c.checked++; c.failed++; report(l, "UNKNOWN_SEQUENCE", ""); continue; }
+    if (l.te > tl || l.qe > ql) { c.checked++; c.failed++; report(l, "COORDINATES", "; the window leaves its sequence"); continue; }
+    if ((l.te - l.ts) + (l.qe - l.qs) > MAX_PROBLEM_BASES) { c.unverifiable++; continue; }
+    bases += (l.te - l.ts) + (l.qe - l.qs);
+    batch.push_back(std::move(l));
+    if (batch.size() >= BATCH_LINES || bases >= BATCH_BASES) { verify_batch(h, src, batch, c); bases = 0; }
+  }
+  verify_batch(h, src, batch, c);
+}
+
+void set_enabled(bool on) {
+  g_enabled.store(on);
+  for (auto& a : g_counts) a.store(0);
+}
+bool enabled() { return g_enabled.load(); }
+void add_counts(const Counts& c) {
+  g_counts[0] += c.checked; g_counts[1] += c.failed; g_counts[2] += c.unverifiable; g_counts[3] += c.bases;
+}
+Counts total_counts() {
+  Counts c;
+  c.checked = g_counts[0].load(); c.failed = g_counts[1].load(); c.unverifiable = g_counts[2].load(); c.bases = g_counts[3].load();
+  return c;
+}
+
+}  // namespace verify
+
+extern "C" {
+
+void wfmh_set_verify(int on) { verify::set_enabled(on != 0); }
+
+int wfmh_verify_counts(uint64_t out[4]) {
+  if (!out) return WFM_E_ARG;
+  const verify::Counts c = verify::total_counts();
+  out[0] = c.checked; out[1] = c.failed; out[2] = c.unverifiable; out[3] = c.bases;
+  return WFM_OK;
+}
+
+int wfmh_verify_paf(wfm_handle_t* h, const char* target_fasta, const char* query_fasta, const char* aligned_paf, uint64_t out[4]) {
+  if (!h || !target_fasta || !aligned_paf) return WFM_E_ARG;
+  try {
+    std::shared_ptr<wfmash_host::FastaStore> target = wfmash_host::open_shared(target_fasta), query_own;
+    const std::string qpath = query_fasta ? query_fasta : target_fasta;
+    if (qpath != target_fasta) query_own = wfmash_host::open_shared(qpath);
+    verify::Source src;
+    src.target = target.get();
+    src.query = query_own ? query_own.get() : target.get();
+    src.threads = (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+    std::ifstream in(aligned_paf);
+    if (!in.is_open()) throw std::runtime_error(std::string("[wfmash::verify] cannot open ") + aligned_paf);
+    verify::Counts c;
+    std::string text, line;
+    while (std::getline(in, line)) {
+      text += line; text += '\n';
+      if (text.size() >= ((size_t)64 << 20)) { verify::verify_text(h, src, text, c); text.clear(); }
+    }
+    verify::verify_text(h, src, text, c);
+    if (out) { out[0] = c.checked; out[1] = c.failed; out[2] = c.unverifiable; out[3] = c.bases; }
+    return WFM_OK;
+  } catch (const std::exception& e) {
+    std::cerr << e.what() << std::endl;
+    wfm_set_error(h, e.what());
+    return WFM_E_ARG;
+  }
+}
+
+// test hook (no GPU): a line as the verifier reads it.  "ok <TAB> qname qs qe strand tname ts te runs" with the runs spelled
+// back as a CIGAR over =XID, or "unverifiable <TAB> reason" / "malformed <TAB> reason".  Release with wfmh_free.
+char* wfmh_test_verify_parse(const char* line) {
+  if (!line) return nullptr;
+  verify::Line l;
+  std::string why;
+  const int st = verify::parse_line(line, l, &why);
+  std::string s;
+  if (st == verify::LINE_UNVERIFIABLE) s = "unverifiable\t" + why;
+  else if (st == verify::LINE_MALFORMED) s = "malformed\t" + why;
+  else {
+    s = "ok\t" + l.qname + "\t" + std::to_string(l.qs) + "\t" + std::to_string(l.qe) + "\t" + (l.rev ? "-" : "+") + "\t" + l.tname + "\t" +
+        std::to_string(l.ts) + "\t" + std::to_string(l.te) + "\t";
+    for (uint32_t w : l.runs) { s += std::to_string(WFM_RUN_LEN(w)); s += "=XID"[WFM_RUN_OP(w)]; }
+  }
+  char* p = (char*)malloc(s.size() + 1);
+  if (p) memcpy(p, s.c_str(), s.size() + 1);
+  return p;
+}
+
+}  // extern "C"
