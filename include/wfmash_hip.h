@@ -277,7 +277,7 @@ int64_t wfm_download_sequences(wfm_handle_t* h, const wfm_seqset_t* s, uint8_t* 
  * without one, bad_p = bad_t = -1 and bad_run is the first bad run (0: none).  No byte outside the problem's two sequences is
  * read: bases are compared only where the runs' totals do not exceed plen and tlen (WFM_CK_SPANS alone otherwise).
  * Returns the number of problems whose flags hold anything but WFM_CK_NOT_CHECKED, or a WFM_E_* code; a run range that leaves
- * runs[0 .. n_runs_total) is WFM_E_ARG.  Optimality is not checked: that stays with the CPU oracle. */
+ * runs[0 .. n_runs_total) is WFM_E_ARG.  Optimality is not checked here: wfm_check_optimal, below, proves it. */
 #define WFM_CK_NOT_CHECKED  1u  /* no runs to check: a score-only problem, or status != 0 */
 #define WFM_CK_BAD_RUN      2u  /* a run of length 0, or two adjacent runs with one op */
 #define WFM_CK_SPANS        4u  /* the runs do not span exactly plen pattern and tlen text bases */
@@ -294,6 +294,54 @@ typedef struct {
 #define WFM_CHECK_SLICE 16384           /* ops one compare task covers, as WFM_SEQ_GATHER_CHUNK */
 int wfm_check_runs(wfm_handle_t* h, const wfm_penalties_t* pen, const wfm_seqset_t* s,
                    const wfm_result_t* res, const uint32_t* runs, size_t n_runs_total, wfm_check_t* out);
+
+/* ---- every score proved optimal by a banded DP ----
+ * What wfm_check_runs leaves out.  For every problem of the seqset s whose result claims a score S = res[i].score, a classical
+ * minimising gap-affine-2-piece DP over cells (i = pattern index, j = text index) is run on the device, restricted to a band of
+ * diagonals k = j - i; the kernel (wfmash_amd/csrc/wfa_optcheck.hip) shares no code with the aligners, reads the forward BYTE copies
+ * only and compares bytes as bytes (N equals N, 'a' differs from 'A').  END2END_BIWFA and END2END_UNI run from (0, 0) to
+ * (plen, tlen); ENDSFREE starts at price 0 on (0, j <= text_begin_free) or (i <= pattern_begin_free, 0) and ends at the minimum over
+ * (plen, j >= tlen - text_end_free) and (i >= plen - pattern_end_free, tlen).  Score-only results are checked like any other.
+ *
+ * The band lemma.  g(L) = min(o1 + e1 L, o2 + e2 L) for L > 0, 0 otherwise; kf = tlen - plen; start diagonals [-pbf, tbf], end
+ * diagonals [kf - tef, kf + pef] (free lengths clamped to their sequence; end-to-end: 0 and kf).  With hi0 = max(tbf, kf + pef) and
+ * lo0 = min(-pbf, kf - tef): every diagonal in [lo0, hi0] is in the band; k > hi0 iff g(k - tbf) + g(k - kf - pef) <= S; k < lo0 iff
+ * g(-pbf - k) + g(kf - tef - k) <= S.  (A path that reaches a diagonal above both its start and its end inserts at least k - ks bases
+ * on the way out and deletes at least k - ke on the way back, in runs of their own; g is non-decreasing and subadditive, so the runs
+ * of one kind cost at least g of their total.  Between start and end diagonals nothing can be excluded.)  Every alignment of price
+ * <= S therefore lies inside the band, and the banded optimum dp tells the whole story: dp == S: S is optimal; dp < S: a cheaper
+ * alignment exists (and dp is the true optimum); dp > S or no path inside the band: no alignment of price S exists.
+ * band_lo / band_hi report the band, cut to the matrix [-plen, tlen].
+ *
+ * What is proved: that res[i].score is the optimal price of problem i's two byte strings under pen and its mode.  What is not: that
+ * the CIGAR has that price or fits its bases (wfm_check_runs), that it is the reference's choice among co-optimal alignments, or
+ * anything the host does to it afterwards.
+ *
+ * One workgroup per problem, so throughput rests on many problems per call (64 problems fill 64 of 256 CUs, and one huge problem
+ * runs on one CU however empty the device is).  Rows of a band of up to WFM_OPT_BAND_C1 diagonals stay in registers with 1 diagonal
+ * per thread (256 threads), up to WFM_OPT_BAND_C4 with 4 (256 threads), up to WFM_OPT_REG_MAX with 8 (512 threads); a wider band keeps
+ * its rows in a block of the device heap, 12 bytes per diagonal, swept in tiles of WFM_OPT_REG_MAX diagonals by 1024 threads, and no
+ * band is refused for its width.  The problems of a call are launched largest first; the memory-held rows of one launch take at most
+ * WFM_OPT_ROWS_MB MiB (one problem alone may take more), and the problems run in chunks if they do not all fit.
+ * Penalties: x, e1, e2 > 0 and o1, o2 >= 0, each at most 32767 (WFM_E_UNSUPPORTED otherwise); the aligners' scope limit does not apply.
+ * A problem is WFM_OPT_NOT_CHECKED if its status != 0, its score < 0 or its score >= 2^29 (the DP's "no path").  max_cells caps the
+ * cells of one problem's band (0: no cap): a problem beyond it is WFM_OPT_SKIPPED and nothing of it is computed.
+ * Returns the number of problems flagged CHEAPER or UNREACHED, or a WFM_E_* code. */
+#define WFM_OPT_NOT_CHECKED 1u  /* status != 0 or score < 0 */
+#define WFM_OPT_SKIPPED     2u  /* the band holds more cells than max_cells: nothing was computed */
+#define WFM_OPT_CHEAPER     4u  /* an alignment cheaper than res[i].score exists: the score is not optimal */
+#define WFM_OPT_UNREACHED   8u  /* no alignment of price res[i].score exists */
+typedef struct {
+  uint32_t flags; int32_t dp_score;     /* the best price inside the band (-1: no path inside); the true optimum whenever <= the claim */
+  int32_t  band_lo, band_hi;            /* the band of diagonals that was swept (0, -1 when nothing was) */
+  uint64_t cells;                       /* DP cells computed (0 when skipped or not checked) */
+} wfm_optcheck_t;                       /* 24 bytes */
+#define WFM_OPT_BAND_C1   256           /* widest band with 1 diagonal per thread */
+#define WFM_OPT_BAND_C4   1024          /* ... with 4 */
+#define WFM_OPT_REG_MAX   4096          /* ... with 8 (512 threads): the widest band whose rows stay in registers; the memory form's tile */
+#define WFM_OPT_ROWS_MB   256           /* device heap the memory-held rows of one launch may take */
+int wfm_check_optimal(wfm_handle_t* h, const wfm_penalties_t* pen, const wfm_seqset_t* s,
+                      const wfm_result_t* res, uint64_t max_cells /* per problem, 0 = no cap */, wfm_optcheck_t* out);
 
 /* How many other align calls the caller keeps in flight on this handle's DEVICE while a call on this handle runs (the align
  * driver's workers, each on a handle of its own: wfmash_amd/host/aligner.cpp).  0, the default: none -- a batch is then cut

@@ -87,7 +87,7 @@ int wfmh_align_paf_multi(wfm_handle_t* const* handles, int n, const char* target
  * fetches; the CIGAR becomes runs (= M, X X, I I, D D) and batches of lines go through wfm_upload_sequence_refs and
  * wfm_check_runs (wfmash_hip.h), by store id where the run keeps its sequences on the device (resident_sequences), by host
  * pointer otherwise.  A line without cg:Z: or with an op outside =XID (a plain M) is counted as unverifiable, not as failed.
- * What is checked: spans, run structure, every M and X base.  What is not: optimality, which stays with the CPU oracle.
+ * What is checked: spans, run structure, every M and X base.  What is not: optimality (wfmh_set_verify_optimal, below).
  *
  * wfmh_set_verify(1): from now on every wfmh_align_paf[_multi] call of the process verifies each batch's finished lines -- what
  * the user gets after patching, erosion and swizzle -- before they are written; the output bytes do not change, a failure is
@@ -101,6 +101,19 @@ int  wfmh_verify_paf(wfm_handle_t* h, const char* target_fasta, const char* quer
 /* Test hook (no GPU): a line as the verifier reads it -- "ok", qname, qs, qe, strand, tname, ts, te and the runs spelled back as
  * a CIGAR over =XID, separated by tabs; or "unverifiable" / "malformed" and the reason.  Release with wfmh_free. */
 char* wfmh_test_verify_parse(const char* line);
+
+/* ---- every score of the align driver proved optimal (wfm_check_optimal, wfmash_hip.h) ----
+ * wfmh_set_verify_optimal(1, max_cells): from now on every device call of the align driver -- main BiWFA problems, head and tail
+ * patches, late tails -- runs as upload, wfm_align_resident_rle, wfm_check_optimal, free instead of the one-call forms, and every
+ * score it returns is held against a banded DP of the same two byte strings on the device.  The output bytes do not change.  A
+ * failed problem is one line on stderr: "[wfmash::verify] NOT OPTIMAL" (a cheaper alignment exists) or "UNREACHED" (no alignment of
+ * that price exists), the record's names and coordinates, which of its problems it is, the mode, the claimed and the DP score.
+ * max_cells caps the DP cells of one problem (0: no cap); a problem beyond it is counted as skipped.  Every call zeroes the counts.
+ * wfmh_verify_optimal_counts: out = {problems checked (the skipped among them), failed, skipped, DP cells computed} since then.
+ * What is not proved: that the CIGAR is the reference's choice among co-optimal ones, or that the host's surgery on it (patching,
+ * erosion, swizzle) is right -- wfmh_set_verify covers the latter.  Off by default; with the switch off nothing new runs. */
+void wfmh_set_verify_optimal(int on, uint64_t max_cells);
+int  wfmh_verify_optimal_counts(uint64_t out[4]);
 
 /* Test hooks: the pure host-side CIGAR functions (erode / merge / swizzle / PAF writer /
  * parseMashmapRow) behind one string interface so the CPU test-suite can check them
@@ -129,6 +142,9 @@ int wfmh_test_tile_plan_dirs(const int32_t* jobs, int64_t n, const int32_t* rule
  * tests/test_tile_interior_cpu.py and tests/test_tile_lean_gpu.py) */
 int wfmh_test_tile_interior(const int32_t* q, int64_t n, int32_t* out);
 int wfmh_test_tile_lean_waves(const int32_t* in, int64_t* out);
+/* ... and the band of wfm_check_optimal (csrc/wfa_optband.h; wrapped by tests/test_optcheck_cpu.py): in = {x, o1, e1, o2, e2, plen, tlen,
+ * pbf, pef, tbf, tef, S}, out = {band_lo, band_hi, cells} */
+int wfmh_test_opt_band(const int64_t* in, int64_t* out);
 /* host winnowing stage of wfm_add_minmers on caller-supplied canonical k-mer hashes (CPU tests) */
 int64_t wfmh_test_winnow(const char* seq, int64_t len, int k, int w, int s, int32_t seq_id,
                          const uint64_t* hash, const int8_t* strand, wfm_minmer_t* out, int64_t cap);

@@ -44,12 +44,17 @@ EXPORTS = [
     "wfm_sketch_part", "wfm_minmer_part_info", "wfm_minmer_part_download", "wfm_minmer_part_free", "wfm_index_build_parts",
     "wfm_seqstore_create", "wfm_seqstore_free", "wfm_seqstore_add", "wfm_seqstore_info",
     "wfm_upload_sequence_refs", "wfm_align_refs_rle", "wfm_download_sequences",
-    "wfm_check_runs",
+    "wfm_check_runs", "wfm_check_optimal",
 ]
 # wfm_check_runs (include/wfmash_hip.h): what a problem's runs were flagged for
 WFM_CK_NOT_CHECKED, WFM_CK_BAD_RUN, WFM_CK_SPANS, WFM_CK_M_DIFFERS, WFM_CK_X_EQUAL, WFM_CK_SCORE, WFM_CK_COUNTS = 1, 2, 4, 8, 16, 32, 64
 CK_NAMES = ("NOT_CHECKED", "BAD_RUN", "SPANS", "M_DIFFERS", "X_EQUAL", "SCORE", "COUNTS")
 CHECK_SLICE = 16384  # WFM_CHECK_SLICE: ops one compare task covers
+# wfm_check_optimal (include/wfmash_hip.h): what a problem's score was flagged for, and the band widths at which the kernel changes form
+WFM_OPT_NOT_CHECKED, WFM_OPT_SKIPPED, WFM_OPT_CHEAPER, WFM_OPT_UNREACHED = 1, 2, 4, 8
+OPT_NAMES = ("NOT_CHECKED", "SKIPPED", "CHEAPER", "UNREACHED")
+OPT_BAND_C1, OPT_BAND_C4, OPT_REG_MAX = 256, 1024, 4096  # WFM_OPT_BAND_C1 / WFM_OPT_BAND_C4 / WFM_OPT_REG_MAX
+OPT_ROWS_MB = 256  # WFM_OPT_ROWS_MB
 SEQ_GATHER_CHUNK = 16384  # WFM_SEQ_GATHER_CHUNK (include/wfmash_hip.h): destination bytes per task of the gather kernel
 
 
@@ -92,6 +97,11 @@ class Check(C.Structure):
                 ("bad_run", C.c_uint32), ("n_runs", C.c_uint32),
                 ("matches", C.c_uint32), ("mismatches", C.c_uint32), ("ins_runs", C.c_uint32), ("ins_bases", C.c_uint32),
                 ("del_runs", C.c_uint32), ("del_bases", C.c_uint32)]
+
+
+class OptCheck(C.Structure):
+    """wfm_optcheck_t: what wfm_check_optimal found for one problem's score."""
+    _fields_ = [("flags", C.c_uint32), ("dp_score", C.c_int32), ("band_lo", C.c_int32), ("band_hi", C.c_int32), ("cells", C.c_uint64)]
 
 
 class Stats(C.Structure):
@@ -649,6 +659,27 @@ class Handle:
             raise WfmError(f"wfm_check_runs failed ({rc}): {self.last_error()}")
         return rc, [out[i] for i in range(n)]
 
+    def check_optimal(self, seqset, results, pen=None, max_cells=0):
+        """wfm_check_optimal: every score held against a banded DP on the device.  results: a ctypes array of Result (seqset.results after
+        an align call), or a list of (status, score) or plain scores, one per problem of the seqset.  Returns the list of OptCheck records
+        (flags, dp_score, band_lo, band_hi, cells)."""
+        n = seqset.n
+        if not isinstance(results, C.Array):
+            arr = (Result * max(n, 1))()
+            assert len(results) == n, (len(results), n)
+            for i, r in enumerate(results):
+                arr[i].status, arr[i].score = r if isinstance(r, tuple) else (0, r)
+            results = arr
+        pn = Penalties(*(pen or DEFAULT_PEN))
+        out = (OptCheck * max(n, 1))()
+        f = self._L.wfm_check_optimal
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+        rc = f(self._p, C.byref(pn), seqset._p, results, int(max_cells), out)
+        if rc < 0:
+            raise WfmError(f"wfm_check_optimal failed ({rc}): {self.last_error()}")
+        return [out[i] for i in range(n)]
+
     def align_rle(self, items, pen=None):
         """wfm_align_batch_rle: the same problems, run-length output.  AlignResult.ops is the list of (length, op) runs
         with op in b'MXID' (adjacent runs never share an op), .n_runs their number; `ops_len` travels as an extra
@@ -966,7 +997,8 @@ HOST_EXPORTS = ["wfmh_test_packed_lce", "wfmh_test_is_acgt", "wfmh_align_default
                 "wfmh_map_multi", "wfmh_align_paf_multi", "wfmh_test_winnow_model", "wfmh_test_sortlike_model", "wfmh_test_finish_records",
                 "wfmh_release_sequences", "wfmh_test_fasta_shared", "wfmh_seed_paf", "wfmh_test_deal", "wfmh_test_subwindow",
                 "wfmh_test_rows", "wfmh_test_tile_plan", "wfmh_test_p2_plan", "wfmh_test_base_plan", "wfmh_test_map_plan", "wfmh_test_filter_ordered",
-                "wfmh_test_reuse_plan", "wfmh_test_tile_plan_dirs", "wfmh_test_tile_interior", "wfmh_test_tile_lean_waves", "wfmh_set_verify", "wfmh_verify_counts", "wfmh_verify_paf", "wfmh_test_verify_parse"]
+                "wfmh_test_reuse_plan", "wfmh_test_tile_plan_dirs", "wfmh_test_tile_interior", "wfmh_test_tile_lean_waves", "wfmh_set_verify", "wfmh_verify_counts", "wfmh_verify_paf", "wfmh_test_verify_parse",
+                "wfmh_set_verify_optimal", "wfmh_verify_optimal_counts", "wfmh_test_opt_band"]
 
 
 class MapSummary(C.Structure):
@@ -1245,6 +1277,39 @@ def verify_counts():
     if rc != 0:
         raise WfmError(f"wfmh_verify_counts failed ({rc})")
     return tuple(int(v) for v in out)
+
+
+def set_verify_optimal(on: bool, max_cells: int = 0) -> None:
+    """wfmh_set_verify_optimal: every later device call of the align driver proves its scores optimal (wfm_check_optimal); max_cells caps
+    one problem's DP cells (0: no cap); zeroes the counts."""
+    f = _host().wfmh_set_verify_optimal
+    f.restype = None
+    f.argtypes = [C.c_int, C.c_uint64]
+    f(1 if on else 0, int(max_cells))
+
+
+def verify_optimal_counts():
+    """wfmh_verify_optimal_counts: (problems checked, failed, skipped over the cell cap, DP cells) since wfmh_set_verify_optimal was last called."""
+    f = _host().wfmh_verify_optimal_counts
+    f.restype = C.c_int
+    f.argtypes = [C.POINTER(C.c_uint64)]
+    out = (C.c_uint64 * 4)()
+    rc = f(out)
+    if rc != 0:
+        raise WfmError(f"wfmh_verify_optimal_counts failed ({rc})")
+    return tuple(int(v) for v in out)
+
+
+def host_opt_band(pen, plen, tlen, free, score):
+    """wfmh_test_opt_band (no GPU): the band of wfm_check_optimal for a claimed score -> (band_lo, band_hi, cells)."""
+    f = _host().wfmh_test_opt_band
+    f.restype = C.c_int
+    f.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    a = (C.c_int64 * 12)(*(list(pen or DEFAULT_PEN) + [plen, tlen] + list(free) + [score]))
+    out = (C.c_int64 * 3)()
+    if f(a, out) != 0:
+        raise WfmError("wfmh_test_opt_band: bad arguments")
+    return int(out[0]), int(out[1]), int(out[2])
 
 
 def verify_paf(handle, target_fasta, aligned_paf, query_fasta=None):

@@ -241,6 +241,17 @@ struct CheckTask { int32_t prob, slice; };  // ops [slice, slice + 1) * WFM_CHEC
 void launch_check(const uint8_t* seq, const uint32_t* runs, const CheckProb* probs, int nprob, const CheckTask* tasks, int64_t ntasks,
                   uint32_t* ops_pre, uint32_t* p_pre, uint32_t* t_pre, uint32_t* cmp_ops, unsigned long long* keys, void* out, DevPen pen,
                   hipStream_t st);
+// wfm_check_optimal (wfa_optcheck.hip): a problem's forward byte copies, its ends-free allowances (clamped; 0 for the other modes),
+// its band of diagonals (wfa_optband.h) and, for the memory form, where its three row arrays begin in `rows` (32-bit elements)
+struct OptProb {
+  int64_t p_off, t_off, row_off;
+  int32_t plen, tlen;
+  int32_t pbf, pef, tbf, tef;
+  int32_t band_lo, band_hi;
+};
+// one workgroup per problem; form 0 / 1 / 2: rows in registers, 1 / 4 / 8 diagonals per thread (bands up to WFM_OPT_BAND_C1 / _C4 /
+// WFM_OPT_REG_MAX); form 3: rows in `rows`, 3 x (tiles x WFM_OPT_REG_MAX + 1) elements per problem.  out[i]: the banded optimum or -1
+void launch_optcheck(const uint8_t* seq, const OptProb* probs, int nprob, int form, int32_t* rows, int32_t* out, DevPen pen, hipStream_t st);
 // makeUpperCaseAndValidDNA in place on nbytes (rounded up to 16) from a 16-byte aligned device address (wfm_seqstore_add)
 void launch_seq_normalize(uint8_t* seq, int64_t nbytes, hipStream_t st);
 // the 2-bit mirror of the sequence buffer (word i = bytes 16 i .. 16 i + 15) and, per BiWFA problem, "pure ACGT" (flag stays nonzero)

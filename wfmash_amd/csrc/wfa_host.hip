@@ -24,6 +24,7 @@
 #include "wfa_device.h"
 #include "dev_cache.h"
 #include "wfa_plan.h"
+#include "wfa_optband.h"
 
 #ifdef WFM_PROFILE_SECTIONS
 namespace wfm { void read_sections(long long* out); }
@@ -279,6 +280,8 @@ struct wfm_handle {
   DevBuf<SeqRev> flagjobs;
   DevBuf<SeqGatherTask> gathertasks;  // wfm_upload_sequence_refs
   DevBuf<uint64_t> checkbuf;         // wfm_check_runs: everything the call has on the device, carved out of one block
+  DevBuf<uint64_t> optbuf;           // wfm_check_optimal: the problems and their results
+  DevBuf<int32_t> optrows;           // ... and the rows of the bands too wide for registers
   DevBuf<unsigned long long> total;
   void* attachment = nullptr;  // owned by another translation unit (map_kernels.hip: the pinned staging ring)
   void (*attachment_free)(void*) = nullptr;
@@ -2211,7 +2214,7 @@ void wfm_destroy(wfm_handle_t* h) {
   h->p2rows.release(); h->p2max.release(); h->p2bmax.release(); h->p2pbmax.release(); h->p2jobs.release(); h->widenjobs.release(); h->keeptasks.release(); h->restoretasks.release(); h->restoreres.release();
   h->bpjobs.release(); h->bpres.release(); h->bsjobs.release(); h->bsres.release();
   h->b2tjobs.release(); h->b2ttasks.release(); h->b2tkeys.release(); h->b2toffs.release(); h->b2tactive.release();
-  h->i64a.release(); h->i64b.release(); h->i64c.release(); h->i32a.release(); h->seqflags.release(); h->flagjobs.release(); h->gathertasks.release(); h->checkbuf.release(); h->total.release();
+  h->i64a.release(); h->i64b.release(); h->i64c.release(); h->i32a.release(); h->seqflags.release(); h->flagjobs.release(); h->gathertasks.release(); h->checkbuf.release(); h->optbuf.release(); h->optrows.release(); h->total.release();
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->ev2) (void)hipEventDestroy(h->ev2);
@@ -2729,6 +2732,98 @@ int wfm_check_runs(wfm_handle_t* h, const wfm_penalties_t* pen, const wfm_seqset
   }
   int flagged = 0;
   for (size_t i = 0; i < n; ++i) flagged += (out[i].flags & ~WFM_CK_NOT_CHECKED) != 0;
+  return flagged;
+}
+
+// ---- every score proved optimal by a banded DP (wfmash_hip.h; the band: wfa_optband.h; the kernel: wfa_optcheck.hip) ----
+int wfm_check_optimal(wfm_handle_t* h, const wfm_penalties_t* pen, const wfm_seqset_t* s, const wfm_result_t* res, uint64_t max_cells,
+                      wfm_optcheck_t* out) {
+  if (!h || !s || !out || !res || !pen) return WFM_E_ARG;
+  const int pmax = 32767;
+  if (pen->x <= 0 || pen->e1 <= 0 || pen->e2 <= 0 || pen->o1 < 0 || pen->o2 < 0 || pen->x > pmax || pen->o1 > pmax || pen->e1 > pmax ||
+      pen->o2 > pmax || pen->e2 > pmax) { h->err = "wfm_check_optimal: unsupported penalties"; return WFM_E_UNSUPPORTED; }
+  const size_t n = s->meta.size();
+  if (n == 0) return 0;
+  if (n > (size_t)INT32_MAX) { h->err = "wfm_check_optimal: too many problems for one call"; return WFM_E_ARG; }
+  HIPCHK(h, hipSetDevice(h->device));
+  const OptPen op{pen->x, pen->o1, pen->e1, pen->o2, pen->e2};
+  // the plan: every checked problem's band, the form it runs in, and per form the problems largest first
+  struct Item { uint64_t cells; uint32_t prob; };
+  std::vector<Item> forms[4];
+  std::vector<OptProb> probs(n);
+  for (size_t i = 0; i < n; ++i) {
+    const ProbMeta& m = s->meta[i];
+    wfm_optcheck_t& o = out[i];
+    o.flags = 0; o.dp_score = -1; o.band_lo = 0; o.band_hi = -1; o.cells = 0;
+    if (res[i].status != 0 || res[i].score < 0 || res[i].score >= (1 << 29)) { o.flags = WFM_OPT_NOT_CHECKED; continue; }
+    const OptBand b = opt_band(op, m.plen, m.tlen, m.pbf, m.pef, m.tbf, m.tef, res[i].score);  // (0 unless the mode is ENDSFREE: layout_seqset)
+    o.band_lo = (int32_t)b.lo; o.band_hi = (int32_t)b.hi;
+    if (max_cells && b.cells > max_cells) { o.flags = WFM_OPT_SKIPPED; continue; }
+    o.cells = b.cells;
+    OptProb& c = probs[i];
+    c.p_off = m.p_fwd; c.t_off = m.t_fwd; c.row_off = 0;
+    c.plen = m.plen; c.tlen = m.tlen;
+    c.pbf = std::min(std::max(m.pbf, 0), m.plen); c.pef = std::min(std::max(m.pef, 0), m.plen);
+    c.tbf = std::min(std::max(m.tbf, 0), m.tlen); c.tef = std::min(std::max(m.tef, 0), m.tlen);
+    c.band_lo = o.band_lo; c.band_hi = o.band_hi;
+    const int64_t W = b.hi - b.lo + 1;
+    forms[W <= WFM_OPT_BAND_C1 ? 0 : W <= WFM_OPT_BAND_C4 ? 1 : W <= WFM_OPT_REG_MAX ? 2 : 3].push_back(Item{b.cells, (uint32_t)i});
+  }
+  const bool timed = getenv("WFM_DEBUG") != nullptr;
+  const auto t0 = std::chrono::steady_clock::now();
+  uint64_t cells_total = 0;
+  size_t launches = 0;
+  std::vector<OptProb> chunk;
+  std::vector<int32_t> dp;
+  const size_t rows_cap = ((size_t)WFM_OPT_ROWS_MB << 20) / sizeof(int32_t);
+  for (int form = 0; form < 4; ++form) {
+    std::vector<Item>& v = forms[form];
+    std::stable_sort(v.begin(), v.end(), [](const Item& a, const Item& b) { return a.cells > b.cells; });
+    for (size_t i0 = 0; i0 < v.size();) {
+      // a chunk: all of a register form at once; of the memory form as many as the row budget holds (one at least)
+      chunk.clear();
+      size_t row_elems = 0, i1 = i0;
+      for (; i1 < v.size(); ++i1) {
+        OptProb c = probs[v[i1].prob];
+        if (form == 3) {
+          const size_t W = (size_t)((int64_t)c.band_hi - c.band_lo + 1);
+          const size_t need = 3 * ((W + WFM_OPT_REG_MAX - 1) / WFM_OPT_REG_MAX * WFM_OPT_REG_MAX + 1);
+          if (!chunk.empty() && row_elems + need > rows_cap) break;
+          c.row_off = (int64_t)row_elems;
+          row_elems += need;
+        }
+        chunk.push_back(c);
+      }
+      const size_t m = chunk.size();
+      const size_t w_probs = (m * sizeof(OptProb) + 7) / 8, w_out = (m * 4 + 7) / 8;
+      if (h->optbuf.ensure(w_probs + w_out + 8)) { h->err = "out of device memory (optimality check)"; return WFM_E_NOMEM; }
+      if (row_elems && h->optrows.ensure(row_elems)) { h->err = "out of device memory (optimality check: rows of a wide band)"; return WFM_E_NOMEM; }
+      OptProb* d_probs = (OptProb*)h->optbuf.p;
+      int32_t* d_out = (int32_t*)(h->optbuf.p + w_probs);
+      HIPCHK(h, hipMemcpyAsync(d_probs, chunk.data(), m * sizeof(OptProb), hipMemcpyHostToDevice, h->stream));
+      launch_optcheck(s->d_seq, d_probs, (int)m, form, h->optrows.p, d_out, DevPen{pen->x, pen->o1, pen->e1, pen->o2, pen->e2}, h->stream);
+      HIPCHK(h, hipGetLastError());
+      dp.resize(m);
+      HIPCHK(h, hipMemcpyAsync(dp.data(), d_out, m * 4, hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(h, hipStreamSynchronize(h->stream));  // (the chunk's host vectors and the row block are free for the next one)
+      for (size_t q = 0; q < m; ++q) out[v[i0 + q].prob].dp_score = dp[q];
+      ++launches;
+      i0 = i1;
+    }
+  }
+  int flagged = 0;
+  for (size_t i = 0; i < n; ++i) {
+    wfm_optcheck_t& o = out[i];
+    if (o.flags) continue;
+    cells_total += o.cells;
+    if (o.dp_score < 0 || o.dp_score > res[i].score) o.flags = WFM_OPT_UNREACHED;
+    else if (o.dp_score < res[i].score) o.flags = WFM_OPT_CHEAPER;
+    flagged += o.flags != 0;
+  }
+  if (timed)
+    fprintf(stderr, "[wfm] optimality check: %zu problems (%zu / %zu / %zu in registers, %zu from memory), %zu launches, %llu cells in %.3f ms\n", n,
+            forms[0].size(), forms[1].size(), forms[2].size(), forms[3].size(), launches, (unsigned long long)cells_total,
+            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
   return flagged;
 }
 

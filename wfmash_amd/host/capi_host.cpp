@@ -10,6 +10,7 @@
 #include "../csrc/wfa_handle.h"
 #include "../csrc/wfa_pack.h"
 #include "../csrc/wfa_plan.h"
+#include "../csrc/wfa_optband.h"
 #include "aligner.hpp"
 #include "fasta.hpp"
 #include "map_stats.hpp"
@@ -243,6 +244,14 @@ int wfmh_test_tile_lean_waves(const int32_t* in, int64_t* out) {
     out[2] += lean_here;
     out[4] += (lean_here > 0 && lean_here < nw) ? 1 : 0;
   }
+  return 0;
+}
+
+// the band of wfm_check_optimal (csrc/wfa_optband.h): in = {x, o1, e1, o2, e2, plen, tlen, pbf, pef, tbf, tef, S}, out = {band_lo, band_hi, cells}
+int wfmh_test_opt_band(const int64_t* in, int64_t* out) {
+  if (!in || !out || in[5] < 0 || in[6] < 0 || in[11] < 0) return -1;
+  const wfm::OptBand b = wfm::opt_band(wfm::OptPen{in[0], in[1], in[2], in[3], in[4]}, in[5], in[6], in[7], in[8], in[9], in[10], in[11]);
+  out[0] = b.lo; out[1] = b.hi; out[2] = (int64_t)b.cells;
   return 0;
 }
 

@@ -19,6 +19,11 @@
 //   --verify                                   every finished PAF line of the run is held against its bases on the device before it is
 //                                              written (spans, run structure, every = and X base; not optimality); a failure is one line
 //                                              on stderr and exit status 3 after everything has been written; refused together with -a
+//   --verify-optimal [--verify-optimal-cells N] every score a device call of the align phase returns (main alignments, head and tail patches)
+//                                              is proved optimal by a banded DP on the device (wfm_check_optimal); the output bytes do
+//                                              not change; a failure is one line on stderr and exit status 3; N caps the DP cells of one
+//                                              problem (problems beyond it are counted as skipped); allowed with --verify, -a and
+//                                              --resident-seqs, refused with -m.  Costs far more than the alignment on near-identical records
 //   --verify-paf FILE target.fa [query.fa]     the same check on an existing aligned PAF (this build's or the reference's): no mapping,
 //                                              no alignment; exit status 3 if a line fails
 //   --hg-filter n,D,conf                       numerator, ANI difference and confidence of the L1 / L2 cutoffs (:94, :700-725)
@@ -98,6 +103,8 @@ static void usage() {
           "  alignment -g x,o1,e1,o2,e2 [5,8,2,24,1]   -E INT target padding   -U INT query padding   -a SAM   -d MD tag\n"
           "            --resident-seqs keep whole sequences on the GPU and align windows of them by reference [off]\n"
           "            --verify check every PAF line written against its bases on the GPU (exit status 3 if one fails; not with -a)\n"
+          "            --verify-optimal prove every alignment score optimal by a banded DP on the GPU (slow; exit status 3 if one is not; not with -m)\n"
+          "            --verify-optimal-cells N skip problems whose band holds more than N DP cells [no cap]\n"
           "            --verify-paf FILE check an existing aligned PAF against target.fa [query.fa] and stop (exit status 3 if a line fails)\n"
           "  other     --out FILE [stdout]   --device INT [0]   --gpus N|all [1] GPUs of this node, starting at --device\n"
           "            -B DIR directory of the hand-off file [cwd]   -Z keep the hand-off file   --quiet (no effect)\n");
@@ -110,7 +117,8 @@ int main(int argc, char** argv) {
   wfmh_map_params_t mp;
   wfmh_map_default_params(&mp);
   std::string mapping_in, out = "/dev/stdout", target, query, seeds_in, scaffold_out, tmp_base, verify_in;
-  bool verify = false;
+  bool verify = false, verify_optimal = false;
+  uint64_t verify_optimal_cells = 0;
   bool approx_only = false, target_padding_given = false, query_padding_given = false, keep_temp = false;
   int device = 0, gpus = 1;
   for (int i = 1; i < argc; ++i) {
@@ -240,6 +248,8 @@ int main(int argc, char** argv) {
     else if (a == "-d" || a == "--md-tag") ap.emit_md_tag = 1;
     else if (a == "--resident-seqs") ap.resident_sequences = 1;
     else if (a == "--verify") verify = true;
+    else if (a == "--verify-optimal") verify_optimal = true;
+    else if (a == "--verify-optimal-cells") verify_optimal_cells = std::strtoull(next("--verify-optimal-cells").c_str(), nullptr, 10);
     else if (a == "--verify-paf") verify_in = next("--verify-paf");
     else if (a == "-h" || a == "--help") { usage(); return 0; }
     else if (a == "-v" || a == "--version") { std::printf("%s\n", WFMASH_HIP_VERSION); return 0; }
@@ -249,6 +259,8 @@ int main(int argc, char** argv) {
   if (target.empty()) { fprintf(stderr, "[wfmash] ERROR: need a target FASTA\n"); usage(); return 1; }
   if (verify && ap.sam_format) { fprintf(stderr, "[wfmash] ERROR: --verify reads the =/X CIGAR of PAF lines: it cannot be combined with -a (SAM)\n"); return 1; }
   if (verify && approx_only) { fprintf(stderr, "[wfmash] ERROR: --verify checks alignments: it cannot be combined with -m\n"); return 1; }
+  if (verify_optimal && approx_only) { fprintf(stderr, "[wfmash] ERROR: --verify-optimal checks alignment scores: it cannot be combined with -m\n"); return 1; }
+  if (verify_optimal_cells && !verify_optimal) { fprintf(stderr, "[wfmash] ERROR: --verify-optimal-cells needs --verify-optimal\n"); return 1; }
   if (!verify_in.empty()) {  // an existing PAF against its sequences; nothing else runs
     wfm_handle_t* hv = nullptr;
     if (wfm_create(device, &hv) != WFM_OK) { fprintf(stderr, "[wfmash] ERROR: no usable MI355X device %d (there is no CPU fallback)\n", device); return 2; }
@@ -357,6 +369,7 @@ int main(int argc, char** argv) {
   if (rc == WFM_OK && !approx_only) {
     wfmh_align_summary_t s;
     if (verify) wfmh_set_verify(1);
+    if (verify_optimal) wfmh_set_verify_optimal(1, verify_optimal_cells);
     rc = wfmh_align_paf_multi(hs.data(), (int)hs.size(), target.c_str(), q, mapping.c_str(), out.c_str(), &ap, &s);
     if (rc == WFM_OK)
       fprintf(stderr, "[wfmash::align] %llu records, %llu aligned bp, %.1f ms GPU kernels, %.1f ms total => %.3g aligned bp/s\n",
@@ -368,6 +381,13 @@ int main(int argc, char** argv) {
       fprintf(stderr, "[wfmash::verify] %llu lines checked, %llu failed, %llu unverifiable, %llu bases compared\n", (unsigned long long)vc[0],
               (unsigned long long)vc[1], (unsigned long long)vc[2], (unsigned long long)vc[3]);
       verify_failed = vc[1] != 0;
+    }
+    if (verify_optimal && rc == WFM_OK) {
+      uint64_t oc[4] = {0, 0, 0, 0};
+      wfmh_verify_optimal_counts(oc);
+      fprintf(stderr, "[wfmash::verify] optimal: %llu problems checked, %llu failed, %llu skipped (over the cell cap), %llu cells\n", (unsigned long long)oc[0],
+              (unsigned long long)oc[1], (unsigned long long)oc[2], (unsigned long long)oc[3]);
+      verify_failed = verify_failed || oc[1] != 0;
     }
   }
   release_temp();

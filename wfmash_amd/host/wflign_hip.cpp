@@ -43,6 +43,12 @@ std::mutex& handle_lock(wfm_handle_t* h) {
 }
 namespace {
 
+// --verify-optimal: the process-wide switch, the cap of one problem's DP cells (0: none) and {problems checked (the skipped among them), failed,
+// skipped, cells} since it was set
+std::atomic<bool> g_optimal{false};
+std::atomic<uint64_t> g_optimal_cells{0};
+std::atomic<uint64_t> g_optimal_counts[4];
+
 // The problems of one device call, always written by reference (a side without a store id carries its host pointer); without a
 // store they go to the device as plain wfm_problem_t, as they always have.
 struct GpuBatch {
@@ -52,7 +58,51 @@ struct GpuBatch {
   std::vector<uint32_t> flags;  // WFM_PF_* per problem (wfm_get_problem_flags), fetched while the handle is still ours
   uint32_t* runs = nullptr;
   std::string err;  // the handle's message, copied while the handle is still ours
+  // --verify-optimal: what a failed problem is reported as -- its record and what of it the problem is
+  const std::vector<BiwfaRecord>* recs = nullptr;
+  std::vector<std::pair<size_t, const char*>> who;  // per problem (or empty: problem i is the main alignment of record i)
   ~GpuBatch() { wfm_free_runs(runs); }
+  // upload -> wfm_align_resident_rle -> wfm_check_optimal -> free: what wfm_align_refs_rle / wfm_align_batch_rle do, with the check
+  // between the last two.  The results and runs are the unchecked call's; the check only reads the seqset and the scores.
+  int run_checked(wfm_handle_t* h, const wfm_penalties_t& pen, const std::vector<wfm_problem_t>& plain) {
+    wfm_seqset_t* S = nullptr;
+    int rc = store ? wfm_upload_sequence_refs(h, store, probs.data(), probs.size(), &S) : wfm_upload_sequences(h, plain.data(), plain.size(), &S);
+    if (rc != WFM_OK) return rc;
+    rc = wfm_align_resident_rle(h, &pen, S, res.data(), &runs, nullptr);
+    if (rc >= 0) {
+      std::vector<wfm_optcheck_t> oc(probs.size());
+      const int crc = wfm_check_optimal(h, &pen, S, res.data(), g_optimal_cells.load(), oc.data());
+      if (crc < 0) rc = crc;
+      else report_optimal(oc);
+    }
+    wfm_free_sequences(h, S);
+    return rc;
+  }
+  void report_optimal(const std::vector<wfm_optcheck_t>& oc) const {
+    uint64_t checked = 0, failed = 0, skipped = 0, cells = 0;
+    for (size_t i = 0; i < oc.size(); ++i) {
+      const wfm_optcheck_t& o = oc[i];
+      if (o.flags & WFM_OPT_NOT_CHECKED) continue;  // (a problem without a score: the driver drops or keeps the record as ever)
+      ++checked;
+      cells += o.cells;
+      if (o.flags & WFM_OPT_SKIPPED) { ++skipped; continue; }
+      if (!(o.flags & (WFM_OPT_CHEAPER | WFM_OPT_UNREACHED))) continue;
+      ++failed;
+      const size_t ri = who.empty() ? i : who[i].first;
+      const char* part = who.empty() ? "main alignment" : who[i].second;
+      const int mode = probs[i].mode & WFM_MODE_MASK;
+      const char* mname = mode == WFM_MODE_ENDSFREE ? "ends-free" : mode == WFM_MODE_END2END_UNI ? "end-to-end (uni)" : "end-to-end (BiWFA)";
+      std::string where = "problem " + std::to_string(i);
+      if (recs && ri < recs->size()) {
+        const BiwfaRecord& r = (*recs)[ri];
+        where = r.query_name + ":" + std::to_string(r.query_offset) + "-" + std::to_string(r.query_offset + r.query_length) + (r.query_is_rev ? " - " : " + ") +
+                r.target_name + ":" + std::to_string(r.target_offset) + "-" + std::to_string(r.target_offset + r.target_length);
+      }
+      fprintf(stderr, "[wfmash::verify] %s %s (%s, %s, %d x %d bases): claimed score %d, DP score %d\n", (o.flags & WFM_OPT_CHEAPER) ? "NOT OPTIMAL" : "UNREACHED",
+              where.c_str(), part, mname, probs[i].plen, probs[i].tlen, res[i].score, o.dp_score);
+    }
+    g_optimal_counts[0] += checked; g_optimal_counts[1] += failed; g_optimal_counts[2] += skipped; g_optimal_counts[3] += cells;
+  }
   int run(wfm_handle_t* h, const wfm_penalties_t& pen, BiwfaStats* st) {
     res.assign(probs.size(), wfm_result_t{});
     wfm_free_runs(runs);
@@ -60,16 +110,18 @@ struct GpuBatch {
     if (probs.empty()) return 0;
     std::lock_guard<std::mutex> lk(handle_lock(h));
     int rc;
-    if (store) rc = wfm_align_refs_rle(h, &pen, store, probs.data(), probs.size(), res.data(), &runs, nullptr);
-    else {
-      std::vector<wfm_problem_t> plain(probs.size());
+    std::vector<wfm_problem_t> plain;
+    if (!store) {
+      plain.resize(probs.size());
       for (size_t i = 0; i < probs.size(); ++i) {
         const wfm_problem_ref_t& r = probs[i];
         plain[i] = wfm_problem_t{r.pattern, r.plen, r.text, r.tlen, r.mode, r.pattern_begin_free, r.pattern_end_free,
                                  r.text_begin_free, r.text_end_free, r.score_hint, 0};
       }
-      rc = wfm_align_batch_rle(h, &pen, plain.data(), plain.size(), res.data(), &runs, nullptr);
     }
+    if (g_optimal.load()) rc = run_checked(h, pen, plain);  // --verify-optimal: the same call in its parts, the seqset kept for the check
+    else if (store) rc = wfm_align_refs_rle(h, &pen, store, probs.data(), probs.size(), res.data(), &runs, nullptr);
+    else rc = wfm_align_batch_rle(h, &pen, plain.data(), plain.size(), res.data(), &runs, nullptr);
     if (rc < 0) err = wfm_last_error(h);
     flags.assign(probs.size(), 0u);
     if (rc >= 0) wfm_get_problem_flags(h, flags.data(), flags.size());
@@ -171,6 +223,7 @@ int align_main(BiwfaBatch& b, bool plan) {
   const size_t n = b.recs.size();
   GpuBatch g;
   g.store = b.store;
+  g.recs = &b.recs;
   g.probs.reserve(n);
   for (const auto& r : b.recs) {
     wfm_problem_ref_t p = window_problem(r, 0, r.target_length, 0, r.query_length);
@@ -221,12 +274,13 @@ void splice_tail(CigarOps& out, const GpuBatch& g, size_t slot) {
 int patch_ends(BiwfaBatch& b, GpuBatch& g) {
   const size_t n = b.recs.size();
   g.store = b.store;
+  g.recs = &b.recs;
   for (size_t i = 0; i < n; ++i) {
     if (!b.recs[i].ok) continue;
     BiwfaBatch::Work& w = b.wk[i];
-    if (w.plan.head_wanted) { w.head_slot = (int)g.probs.size(); g.probs.push_back(head_problem(b.recs[i], w.plan.head)); }
+    if (w.plan.head_wanted) { w.head_slot = (int)g.probs.size(); g.probs.push_back(head_problem(b.recs[i], w.plan.head)); g.who.emplace_back(i, "head patch"); }
     if (!w.plan.tail_independent) { ++b.later; continue; }
-    if (w.plan.tail_wanted) { w.tail_slot = (int)g.probs.size(); g.probs.push_back(tail_problem(b.recs[i], w.plan.tail)); }
+    if (w.plan.tail_wanted) { w.tail_slot = (int)g.probs.size(); g.probs.push_back(tail_problem(b.recs[i], w.plan.tail)); g.who.emplace_back(i, "tail patch"); }
   }
   const int rc = g.run(b.h, b.pen, b.stats);
   if (rc < 0) return b.fail(g, rc);
@@ -261,12 +315,13 @@ int patch_ends(BiwfaBatch& b, GpuBatch& g) {
 int patch_late_tails(BiwfaBatch& b) {
   GpuBatch g;
   g.store = b.store;
+  g.recs = &b.recs;
   std::vector<size_t> owner;
   std::vector<size_t> cut;  // erode_start_idx of the owner's new tail scan
   for (size_t i = 0; i < b.recs.size(); ++i) {
     if (!b.recs[i].ok || b.wk[i].plan.tail_independent) continue;
     const Erosion te = scan_tail_erosion(b.recs[i].ops);
-    if (patch_wanted(te)) { owner.push_back(i); cut.push_back(te.erode_start_idx); g.probs.push_back(tail_problem(b.recs[i], te)); }
+    if (patch_wanted(te)) { owner.push_back(i); cut.push_back(te.erode_start_idx); g.probs.push_back(tail_problem(b.recs[i], te)); g.who.emplace_back(i, "late tail patch"); }
   }
   const int rc = g.run(b.h, b.pen, b.stats);
   if (rc < 0) return b.fail(g, rc);
@@ -336,3 +391,19 @@ int do_biwfa_alignment_batch(wfm_handle_t* h, std::vector<BiwfaRecord>& recs, co
 }
 
 }  // namespace wflign
+
+extern "C" {
+
+void wfmh_set_verify_optimal(int on, uint64_t max_cells) {
+  wflign::g_optimal_cells.store(on ? max_cells : 0);
+  for (auto& a : wflign::g_optimal_counts) a.store(0);
+  wflign::g_optimal.store(on != 0);
+}
+
+int wfmh_verify_optimal_counts(uint64_t out[4]) {
+  if (!out) return WFM_E_ARG;
+  for (int q = 0; q < 4; ++q) out[q] = wflign::g_optimal_counts[q].load();
+  return WFM_OK;
+}
+
+}  // extern "C"
