@@ -35,6 +35,7 @@
  *                              mappingCore.hpp:307-442, slidingMap.hpp:28-212, computeMap.hpp:989-1061
  *     wfm_map_fragments     <- Map::mapSingleQueryFrag for a whole batch, computeMap.hpp:875-938
  *     wfm_minhash_sketch    <- StreamingMinHash over one sequence (ANI estimate), map_stats.hpp:569-616
+ *     wfm_sketch_intersections <- the estimate's pairwise merge of pooled sketches, map_stats.hpp:719-731, all pairs at once
  *   (file-level drivers of both phases: include/wfmash_host.h)
  *
  * All pointers are HOST memory unless stated; the library owns every device
@@ -563,6 +564,26 @@ int64_t wfm_minhash_sketch(wfm_handle_t* h, const char* seq, int64_t len, int k,
  * computeMap.hpp:405-484: two passes over the files there too).  The caller keeps the host memory alive and unchanged while the scope is open;
  * scopes nest, the last close releases the copies.  wfmh_map_paf opens one around its whole call. */
 int wfm_map_sequence_cache(wfm_handle_t* h, int open);
+
+/* The shared-hash counts of many sketches at once: the pairwise merge of the ANI estimate (map_stats.hpp:719-731) for every
+ * (row, column) pair of a matrix, on the device (wfmash_amd/csrc/map_isect.hip).
+ * shared[r * n_cols + c] = the multiset intersection size of sketches rows[r] and cols[c]:
+ * the sum over values v of min(count of v in A, count of v in B).  This is exactly what the
+ * two-pointer merge of map_stats.hpp:719-731 counts on two ascending sketches with duplicates.
+ * Sketches are given CSR-style: sketch i is hashes[offsets[i] .. offsets[i+1]), ascending,
+ * duplicates allowed, and may be empty (offsets has n_sketches + 1 entries).  rows and cols name sketches by index, in any order,
+ * repeats allowed.  A column sketch of up to WFM_ISECT_LDS_MAX hashes is searched in LDS, a longer one in global memory; the counts
+ * do not depend on which.  The matrix is computed in launches of at most 64 M cells (WFM_ISECT_CELLS, read per call: another bound,
+ * a test switch), so device memory is the sketches plus one such block whatever n_rows x n_cols is; the call returns with the
+ * counts on the host.
+ * WFM_E_ARG, with a message, nothing written to shared and the handle usable afterwards: offsets[0] != 0 or offsets that decrease,
+ * a sketch of more than 2^32 - 1 hashes, an index outside [0, n_sketches), a sketch that does not ascend (found by a device pass
+ * over hashes before any intersection runs; the message names the first such sketch).  n_rows == 0 or n_cols == 0: WFM_OK,
+ * nothing is written. */
+#define WFM_ISECT_LDS_MAX 4096   /* longest column sketch held in LDS; longer ones take the global-memory form */
+int wfm_sketch_intersections(wfm_handle_t* h, const uint64_t* hashes, const int64_t* offsets, int64_t n_sketches,
+                             const int32_t* rows, int64_t n_rows, const int32_t* cols, int64_t n_cols,
+                             uint32_t* shared /* n_rows * n_cols, row-major */);
 
 /* L1 stage: getSeedIntervalPoints + computeL1CandidateRegions + doL1Mapping's group loop
  * (mappingCore.hpp:82-301, computeMap.hpp:945-984) for a batch of query fragments against a

@@ -293,6 +293,40 @@ int wfmh_map(wfm_handle_t* h, const char* target_fasta, const char* query_fasta,
 int wfmh_map_multi(wfm_handle_t* const* handles, int n, const char* target_fasta, const char* query_fasta, const char* out_paf,
                    const wfmh_map_params_t* params, wfmh_map_summary_t* summary);
 
+/* ---- the group-by-group ANI table the identity estimate is made from (wfmash_amd/host/ani_estimate.hpp) ----
+ * estimate_identity_for_groups sketches every sequence on the device, pools the sketches per group and turns every (query group,
+ * target group) pair's shared-hash count into an ANI (map_stats.hpp:325-822); the reference prints that table to stderr
+ * (:746-752).  Here it is a file.  One row per ordered pair (query group q, target group t) with q != t, in ascending (q, t) group
+ * ids: the two group prefixes, the sizes of the two pooled sketches, `shared` from one wfm_sketch_intersections call on
+ * handles[0], jaccard = shared / the smaller size, ani = 1 - j2md((float)jaccard, 21) -- the estimate's arithmetic.  Pairs without
+ * a shared hash or with an empty sketch are rows of zeros (the estimate drops them, the table shows them).  The text form: the line
+ *   #query_group<TAB>target_group<TAB>query_hashes<TAB>target_hashes<TAB>shared<TAB>jaccard<TAB>ani
+ * then one line per row, jaccard and ani as %.6f.
+ *
+ * wfmh_ani_matrix: the table of the sequences a map call with these files and params would take (-T, -Q, -R, -A, -Y apply), written
+ * to out_tsv; sketching is spread over the handles as the estimate spreads it, the intersections run on handles[0]; no index, no
+ * mapping.  query_fasta may be NULL (= target_fasta).  wfmh_ani_matrix_rows: the same rows as values instead of text (*rows is
+ * released with wfmh_free_ani_rows).  wfmh_set_ani_matrix(path): the NEXT wfmh_map / wfmh_map_multi call of the process writes the
+ * table to path before it maps -- from the very sketches its estimate uses, made also when auto_pct_identity is 0 -- and then goes
+ * on as it would have: its PAF is byte for byte the one without the table.  The call takes the setting with it; NULL clears it.
+ * Returns 0 or WFM_E_* (message in wfm_last_error(handles[0])). */
+typedef struct {
+  char*    query_group;
+  char*    target_group;
+  uint64_t query_hashes, target_hashes, shared;
+  double   jaccard, ani;
+} wfmh_ani_row_t;
+int  wfmh_ani_matrix(wfm_handle_t* const* handles, int n, const char* target_fasta, const char* query_fasta,
+                     const wfmh_map_params_t* params, const char* out_tsv);
+int  wfmh_ani_matrix_rows(wfm_handle_t* const* handles, int n, const char* target_fasta, const char* query_fasta,
+                          const wfmh_map_params_t* params, wfmh_ani_row_t** rows, int64_t* n_rows);
+void wfmh_free_ani_rows(wfmh_ani_row_t* rows, int64_t n_rows);
+void wfmh_set_ani_matrix(const char* out_tsv);
+/* Test hook (no GPU needed): the table's text from n rows given as names, sketch sizes and counts; jaccard and ani are computed
+ * as above.  malloc'd, wfmh_free. */
+char* wfmh_test_ani_tsv(const char* const* query_groups, const char* const* target_groups, const uint64_t* query_hashes,
+                        const uint64_t* target_hashes, const uint64_t* shared, int64_t n);
+
 /* Test hook (no GPU needed): the deal of wfmh_map_multi's index build.  out_part[i] = the part (0 .. n_parts - 1) that item i of
  * lengths[0 .. n) goes to.  Returns 0 or WFM_E_ARG. */
 int wfmh_test_deal(const int64_t* lengths, int64_t n, int n_parts, int32_t* out_part);

@@ -45,7 +45,9 @@ EXPORTS = [
     "wfm_seqstore_create", "wfm_seqstore_free", "wfm_seqstore_add", "wfm_seqstore_info",
     "wfm_upload_sequence_refs", "wfm_align_refs_rle", "wfm_download_sequences",
     "wfm_check_runs", "wfm_check_optimal",
+    "wfm_sketch_intersections",
 ]
+ISECT_LDS_MAX = 4096  # WFM_ISECT_LDS_MAX: the longest column sketch wfm_sketch_intersections searches in LDS
 # wfm_check_runs (include/wfmash_hip.h): what a problem's runs were flagged for
 WFM_CK_NOT_CHECKED, WFM_CK_BAD_RUN, WFM_CK_SPANS, WFM_CK_M_DIFFERS, WFM_CK_X_EQUAL, WFM_CK_SCORE, WFM_CK_COUNTS = 1, 2, 4, 8, 16, 32, 64
 CK_NAMES = ("NOT_CHECKED", "BAD_RUN", "SPANS", "M_DIFFERS", "X_EQUAL", "SCORE", "COUNTS")
@@ -890,6 +892,29 @@ class Handle:
             raise WfmError(f"wfm_minhash_sketch failed ({n}): {self.last_error()}")
         return out[:n]
 
+    def sketch_intersections(self, sketches, rows=None, cols=None, offsets=None):
+        """wfm_sketch_intersections: the multiset intersection sizes of sketches[rows[r]] and sketches[cols[c]] as a uint32 array
+        [n_rows, n_cols].  sketches: a list of ascending uint64 arrays (duplicates allowed, empty allowed); rows / cols default to all
+        of them.  offsets (a test's way to hand in a broken CSR) replaces the offsets the sketches' lengths give."""
+        n = len(sketches)
+        parts = [np.ascontiguousarray(s, dtype=np.uint64) for s in sketches]
+        hashes = np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint64)
+        if offsets is None:
+            offsets = np.concatenate([[0], np.cumsum([len(p) for p in parts], dtype=np.int64)])
+        offs = np.ascontiguousarray(offsets, dtype=np.int64)
+        if len(offs) != n + 1:
+            raise ValueError("one offset per sketch and one more")
+        r = np.ascontiguousarray(np.arange(n) if rows is None else rows, dtype=np.int32)
+        c = np.ascontiguousarray(np.arange(n) if cols is None else cols, dtype=np.int32)
+        out = np.zeros((len(r), len(c)), dtype=np.uint32)
+        f = self._L.wfm_sketch_intersections
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
+        rc = f(self._p, hashes.ctypes.data, offs.ctypes.data, n, r.ctypes.data, len(r), c.ctypes.data, len(c), out.ctypes.data)
+        if rc != 0:
+            raise WfmError(f"wfm_sketch_intersections failed ({rc}): {self.last_error()}")
+        return out
+
     def map_l2(self, index, qsketch, qcount, q_len, q_kc, s, cands, params):
         """wfm_map_l2: mappings (MAPPING_DTYPE) + fragment ids for a batch of L1 candidates.
         params: dict(window_length, sketch_size, stage1_topani, keep_table, ident_table, cutoff_j)."""
@@ -998,7 +1023,8 @@ HOST_EXPORTS = ["wfmh_test_packed_lce", "wfmh_test_is_acgt", "wfmh_align_default
                 "wfmh_release_sequences", "wfmh_test_fasta_shared", "wfmh_seed_paf", "wfmh_test_deal", "wfmh_test_subwindow",
                 "wfmh_test_rows", "wfmh_test_tile_plan", "wfmh_test_p2_plan", "wfmh_test_base_plan", "wfmh_test_map_plan", "wfmh_test_filter_ordered",
                 "wfmh_test_reuse_plan", "wfmh_test_tile_plan_dirs", "wfmh_test_tile_interior", "wfmh_test_tile_lean_waves", "wfmh_set_verify", "wfmh_verify_counts", "wfmh_verify_paf", "wfmh_test_verify_parse",
-                "wfmh_set_verify_optimal", "wfmh_verify_optimal_counts", "wfmh_test_opt_band"]
+                "wfmh_set_verify_optimal", "wfmh_verify_optimal_counts", "wfmh_test_opt_band",
+                "wfmh_ani_matrix", "wfmh_ani_matrix_rows", "wfmh_free_ani_rows", "wfmh_set_ani_matrix", "wfmh_test_ani_tsv"]
 
 
 class MapSummary(C.Structure):
@@ -1050,6 +1076,76 @@ def map_paf(handle, target_fasta: str, out_paf: str, query_fasta: str = None, pa
                     C.byref(params) if params is not None else None, C.byref(s))
     if rc != 0:
         raise WfmError(f"wfmh_map failed ({rc}): {handle.last_error()}")
+    return s
+
+
+class AniRowC(C.Structure):
+    """wfmh_ani_row_t (include/wfmash_host.h)"""
+    _fields_ = [("query_group", C.c_void_p), ("target_group", C.c_void_p), ("query_hashes", C.c_uint64), ("target_hashes", C.c_uint64),
+                ("shared", C.c_uint64), ("jaccard", C.c_double), ("ani", C.c_double)]
+
+
+def ani_matrix(handles_or_handle, target_fasta: str, query_fasta: str = None, params=None):
+    """wfmh_ani_matrix_rows: the group-by-group ANI table the identity estimate is made from, one tuple (query_group, target_group,
+    query_hashes, target_hashes, shared, jaccard, ani) per ordered pair of different groups, in ascending group ids."""
+    L = load()
+    handles = list(handles_or_handle) if isinstance(handles_or_handle, (list, tuple)) else [handles_or_handle]
+    f = L.wfmh_ani_matrix_rows
+    f.restype = C.c_int
+    f.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.c_void_p, C.POINTER(C.POINTER(AniRowC)), C.POINTER(C.c_int64)]
+    L.wfmh_free_ani_rows.restype = None
+    L.wfmh_free_ani_rows.argtypes = [C.POINTER(AniRowC), C.c_int64]
+    rows, n = C.POINTER(AniRowC)(), C.c_int64(0)
+    rc = f(_handle_array(handles), len(handles), os.fsencode(target_fasta), os.fsencode(query_fasta) if query_fasta else None,
+           C.byref(params) if params is not None else None, C.byref(rows), C.byref(n))
+    if rc != 0:
+        raise WfmError(f"wfmh_ani_matrix_rows failed ({rc}): {handles[0].last_error()}")
+    try:
+        return [(C.string_at(r.query_group).decode(), C.string_at(r.target_group).decode(), int(r.query_hashes), int(r.target_hashes),
+                 int(r.shared), float(r.jaccard), float(r.ani)) for r in (rows[i] for i in range(n.value))]
+    finally:
+        L.wfmh_free_ani_rows(rows, n)
+
+
+def ani_matrix_tsv(handles_or_handle, target_fasta: str, out_tsv: str, query_fasta: str = None, params=None) -> None:
+    """wfmh_ani_matrix: the same table written as TSV (what `wfmash-hip --ani-only --ani-matrix FILE` writes)."""
+    L = load()
+    handles = list(handles_or_handle) if isinstance(handles_or_handle, (list, tuple)) else [handles_or_handle]
+    f = L.wfmh_ani_matrix
+    f.restype = C.c_int
+    f.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.c_void_p, C.c_char_p]
+    rc = f(_handle_array(handles), len(handles), os.fsencode(target_fasta), os.fsencode(query_fasta) if query_fasta else None,
+           C.byref(params) if params is not None else None, os.fsencode(out_tsv))
+    if rc != 0:
+        raise WfmError(f"wfmh_ani_matrix failed ({rc}): {handles[0].last_error()}")
+
+
+def set_ani_matrix(out_tsv) -> None:
+    """wfmh_set_ani_matrix: the next map_paf / map_paf_multi call writes the ANI table to out_tsv before it maps (None clears)."""
+    f = load().wfmh_set_ani_matrix
+    f.restype = None
+    f.argtypes = [C.c_char_p]
+    f(os.fsencode(out_tsv) if out_tsv is not None else None)
+
+
+def host_ani_tsv(rows) -> str:
+    """wfmh_test_ani_tsv (no GPU): the table's text from (query_group, target_group, query_hashes, target_hashes, shared) tuples."""
+    L = load()
+    n = len(rows)
+    enc = lambda x: x if isinstance(x, bytes) else x.encode()
+    qn = (C.c_char_p * max(n, 1))(*[enc(r[0]) for r in rows])
+    tn = (C.c_char_p * max(n, 1))(*[enc(r[1]) for r in rows])
+    qh, th, sh = (np.array([r[j] for r in rows], dtype=np.uint64) for j in (2, 3, 4))
+    f = L.wfmh_test_ani_tsv
+    f.restype = C.c_void_p
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+    L.wfmh_free.restype = None
+    L.wfmh_free.argtypes = [C.c_void_p]
+    p = f(qn, tn, qh.ctypes.data, th.ctypes.data, sh.ctypes.data, n)
+    if not p:
+        raise WfmError("wfmh_test_ani_tsv failed")
+    s = C.string_at(p).decode()
+    L.wfmh_free(p)
     return s
 
 

@@ -35,7 +35,7 @@ double estimate_identity_for_groups(const Parameters& params, const SequenceIdMa
   return estimate_identity_for_groups(params, idManager, std::vector<wfm_handle_t*>{h});
 }
 
-double estimate_identity_for_groups(const Parameters& params, const SequenceIdManager& idManager, const std::vector<wfm_handle_t*>& hs) {
+GroupSketches sketch_groups(const Parameters& params, const SequenceIdManager& idManager, const std::vector<wfm_handle_t*>& hs) {
   if (hs.empty()) throw std::runtime_error("no GPU handle");
   struct Role { std::string file; bool is_query = false, is_target = false; };
   std::map<std::string, Role> roles;  // the reference walks a hash map here; the result does not depend on the order
@@ -58,13 +58,14 @@ double estimate_identity_for_groups(const Parameters& params, const SequenceIdMa
     for (int i = 0; i < fa.nseq(); ++i)
       if (known(fa.name(i))) { Role& r = roles[fa.name(i)]; if (r.file.empty()) r.file = file; r.is_target = true; }
   }
-  std::map<int, std::vector<hash_t>> query_groups, target_groups;
+  GroupSketches out;
+  std::map<int, std::vector<hash_t>>& query_groups = out.query_groups;
+  std::map<int, std::vector<hash_t>>& target_groups = out.target_groups;
   for (const auto& [name, role] : roles) {
     const int g = idManager.getRefGroup(idManager.getSequenceId(name));
     if (role.is_query) query_groups[g];
     if (role.is_target) target_groups[g];
   }
-  int query_seq_count = 0, target_seq_count = 0;
   {  // indexed files: read the sequences side by side instead of one after the other
     std::unordered_map<std::string, std::vector<int>> want;
     for (const auto& [name, role] : roles) {
@@ -103,10 +104,20 @@ double estimate_identity_for_groups(const Parameters& params, const SequenceIdMa
   }
   for (const Item& it : items) {
     const int g = idManager.getRefGroup(idManager.getSequenceId(*it.name));
-    if (it.role->is_query) { pool(query_groups[g], it.sketch); ++query_seq_count; }
-    if (it.role->is_target) { pool(target_groups[g], it.sketch); ++target_seq_count; }
+    if (it.role->is_query) { pool(query_groups[g], it.sketch); ++out.query_seq_count; }
+    if (it.role->is_target) { pool(target_groups[g], it.sketch); ++out.target_seq_count; }
   }
-  if (query_seq_count == 0 || target_seq_count == 0) return kFallbackIdentity;
+  return out;
+}
+
+double estimate_identity_for_groups(const Parameters& params, const SequenceIdManager& idManager, const std::vector<wfm_handle_t*>& hs) {
+  return estimate_identity_from(sketch_groups(params, idManager, hs), params);
+}
+
+double estimate_identity_from(const GroupSketches& gs, const Parameters& params) {
+  if (gs.query_seq_count == 0 || gs.target_seq_count == 0) return kFallbackIdentity;
+  const std::map<int, std::vector<hash_t>>& query_groups = gs.query_groups;
+  const std::map<int, std::vector<hash_t>>& target_groups = gs.target_groups;
 
   std::vector<double> anis;
   for (const auto& [qg, qs] : query_groups) {
@@ -134,6 +145,41 @@ double estimate_identity_for_groups(const Parameters& params, const SequenceIdMa
   if (adjusted < 0.0) adjusted = 0.0;
   if (adjusted > 1.0) adjusted = 1.0;
   return adjusted;
+}
+
+std::vector<AniRow> ani_matrix_from(const GroupSketches& gs, const SequenceIdManager& idManager, wfm_handle_t* h) {
+  if (!h) throw std::runtime_error("no GPU handle");
+  // CSR: the query groups' sketches, then the target groups'; rows name the former, columns the latter
+  std::vector<hash_t> hashes;
+  std::vector<int64_t> offsets{0};
+  std::vector<int32_t> rows, cols;
+  for (const auto* side : {&gs.query_groups, &gs.target_groups}) {
+    for (const auto& [g, sketch] : *side) {
+      (side == &gs.query_groups ? rows : cols).push_back((int32_t)(offsets.size() - 1));
+      hashes.insert(hashes.end(), sketch.begin(), sketch.end());
+      offsets.push_back((int64_t)hashes.size());
+    }
+  }
+  std::vector<uint32_t> shared(rows.size() * cols.size());
+  const int rc = wfm_sketch_intersections(h, hashes.data(), offsets.data(), (int64_t)offsets.size() - 1, rows.data(), (int64_t)rows.size(), cols.data(),
+                                          (int64_t)cols.size(), shared.data());
+  if (rc != WFM_OK) throw std::runtime_error(std::string("wfm_sketch_intersections failed: ") + wfm_last_error(h));
+  std::vector<AniRow> out;
+  size_t r = 0;
+  for (const auto& [qg, qs] : gs.query_groups) {
+    size_t c = 0;
+    for (const auto& [tg, ts] : gs.target_groups) {
+      if (qg != tg) out.push_back(ani_row(idManager.getGroupPrefix(qg), idManager.getGroupPrefix(tg), qs.size(), ts.size(), shared[r * cols.size() + c]));
+      ++c;
+    }
+    ++r;
+  }
+  return out;
+}
+
+std::vector<AniRow> ani_matrix(const Parameters& params, const SequenceIdManager& idManager, const std::vector<wfm_handle_t*>& hs) {
+  const GroupSketches gs = sketch_groups(params, idManager, hs);
+  return ani_matrix_from(gs, idManager, hs[0]);
 }
 
 }  // namespace Stat

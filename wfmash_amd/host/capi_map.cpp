@@ -6,8 +6,11 @@
 #include <cstdio>
 #include <cstring>
 #include <limits>
+#include <memory>
+#include <mutex>
 #include <sstream>
 #include <string>
+#include <vector>
 
 #include "../../include/wfmash_host.h"
 #include "../csrc/wfa_handle.h"
@@ -75,6 +78,48 @@ skch::Parameters to_parameters(const wfmh_map_params_t& c) {
   }
   return p;
 }
+
+namespace {
+skch::SequenceIdManager make_id_manager(const skch::Parameters& p) {
+  std::vector<std::string> target_prefix_vec;
+  if (!p.target_prefix.empty()) target_prefix_vec.push_back(p.target_prefix);
+  return skch::SequenceIdManager(p.querySequences, p.refSequences, p.query_prefix, target_prefix_vec, std::string(1, p.prefix_delim), p.query_list,
+                                 p.target_list);
+}
+
+void write_text_file(const std::string& path, const std::string& text) {
+  std::ofstream f(path, std::ios::binary);
+  if (!f.is_open()) throw std::runtime_error("cannot open " + path + " for writing");
+  f << text;
+  f.close();
+  if (!f) throw std::runtime_error("writing " + path + " failed");
+}
+
+// wfmh_set_ani_matrix: where the next map call writes the ANI table (empty: nowhere)
+std::mutex g_ani_out_mu;
+std::string g_ani_out;
+std::string take_ani_matrix_out() {
+  std::lock_guard<std::mutex> lk(g_ani_out_mu);
+  std::string s;
+  s.swap(g_ani_out);
+  return s;
+}
+
+// what wfmh_map_multi does up to its sketches, then the table instead of the mapping
+std::vector<skch::Stat::AniRow> ani_matrix_of_files(wfm_handle_t* const* handles, int n, const char* target_fasta, const char* query_fasta,
+                                                    const wfmh_map_params_t* params) {
+  wfmh_map_params_t def;
+  wfmh_map_default_params(&def);
+  skch::Parameters p = to_parameters(params ? *params : def);
+  p.refSequences = {std::string(target_fasta)};
+  p.querySequences = {std::string(query_fasta ? query_fasta : target_fasta)};
+  std::vector<std::shared_ptr<FastaStore>> files;
+  for (const auto& f : p.refSequences) files.push_back(open_shared(f));
+  for (const auto& f : p.querySequences) files.push_back(open_shared(f));
+  const skch::SequenceIdManager ids = make_id_manager(p);
+  return skch::Stat::ani_matrix(p, ids, std::vector<wfm_handle_t*>(handles, handles + n));
+}
+}  // namespace
 
 }  // namespace wfmash_host
 
@@ -162,13 +207,14 @@ int wfmh_map_multi(wfm_handle_t* const* handles, int n, const char* target_fasta
         SeqCacheScope(wfm_handle_t* const* hh, int nn) : hs(hh), n(nn) { for (int i = 0; i < n; ++i) (void)wfm_map_sequence_cache(hs[i], 1); }
         ~SeqCacheScope() { for (int i = n - 1; i >= 0; --i) (void)wfm_map_sequence_cache(hs[i], 0); }
       } seq_cache_scope(handles, n);
-      if (p.auto_pct_identity) {
+      const std::string ani_tsv_out = wfmash_host::take_ani_matrix_out();  // wfmh_set_ani_matrix: empty unless asked for
+      if (p.auto_pct_identity || !ani_tsv_out.empty()) {
         // main.cpp:72-128: estimate, then derive the sketch size from the estimate unless -s was given
-        std::vector<std::string> target_prefix_vec;
-        if (!p.target_prefix.empty()) target_prefix_vec.push_back(p.target_prefix);
-        const skch::SequenceIdManager ids(p.querySequences, p.refSequences, p.query_prefix, target_prefix_vec,
-                                          std::string(1, p.prefix_delim), p.query_list, p.target_list);
-        p.percentageIdentity = skch::Stat::estimate_identity_for_groups(p, ids, std::vector<wfm_handle_t*>(handles, handles + n));
+        const skch::SequenceIdManager ids = wfmash_host::make_id_manager(p);
+        const skch::Stat::GroupSketches gs = skch::Stat::sketch_groups(p, ids, std::vector<wfm_handle_t*>(handles, handles + n));
+        // the table and the estimate are made from the same sketches; the table changes nothing the mapping reads
+        if (!ani_tsv_out.empty()) wfmash_host::write_text_file(ani_tsv_out, skch::Stat::ani_tsv(skch::Stat::ani_matrix_from(gs, ids, h)));
+        if (p.auto_pct_identity) p.percentageIdentity = skch::Stat::estimate_identity_from(gs, p);
         ms_identity = ms_since(t_call);
       }
       skch::Map mapper(p, std::vector<wfm_handle_t*>(handles, handles + n));
@@ -199,6 +245,62 @@ int wfmh_map_multi(wfm_handle_t* const* handles, int n, const char* target_fasta
     wfm_set_error(h, e.what());
     return WFM_E_ARG;
   }
+}
+
+void wfmh_set_ani_matrix(const char* out_tsv) {
+  std::lock_guard<std::mutex> lk(wfmash_host::g_ani_out_mu);
+  wfmash_host::g_ani_out = out_tsv ? out_tsv : "";
+}
+
+int wfmh_ani_matrix(wfm_handle_t* const* handles, int n, const char* target_fasta, const char* query_fasta, const wfmh_map_params_t* params,
+                    const char* out_tsv) {
+  if (!handles || n < 1 || !target_fasta || !out_tsv) return WFM_E_ARG;
+  for (int i = 0; i < n; ++i) if (!handles[i]) return WFM_E_ARG;
+  try {
+    wfmash_host::write_text_file(out_tsv, skch::Stat::ani_tsv(wfmash_host::ani_matrix_of_files(handles, n, target_fasta, query_fasta, params)));
+    return WFM_OK;
+  } catch (const std::exception& e) {
+    wfm_set_error(handles[0], e.what());
+    return WFM_E_ARG;
+  }
+}
+
+int wfmh_ani_matrix_rows(wfm_handle_t* const* handles, int n, const char* target_fasta, const char* query_fasta, const wfmh_map_params_t* params,
+                         wfmh_ani_row_t** rows, int64_t* n_rows) {
+  if (!handles || n < 1 || !target_fasta || !rows || !n_rows) return WFM_E_ARG;
+  for (int i = 0; i < n; ++i) if (!handles[i]) return WFM_E_ARG;
+  *rows = nullptr;
+  *n_rows = 0;
+  try {
+    const std::vector<skch::Stat::AniRow> r = wfmash_host::ani_matrix_of_files(handles, n, target_fasta, query_fasta, params);
+    wfmh_ani_row_t* out = (wfmh_ani_row_t*)std::calloc(std::max<size_t>(r.size(), 1), sizeof(wfmh_ani_row_t));
+    if (!out) return WFM_E_NOMEM;
+    for (size_t i = 0; i < r.size(); ++i) {
+      out[i].query_group = strdup(r[i].query_group.c_str());
+      out[i].target_group = strdup(r[i].target_group.c_str());
+      out[i].query_hashes = r[i].query_hashes; out[i].target_hashes = r[i].target_hashes; out[i].shared = r[i].shared;
+      out[i].jaccard = r[i].jaccard; out[i].ani = r[i].ani;
+    }
+    *rows = out;
+    *n_rows = (int64_t)r.size();
+    return WFM_OK;
+  } catch (const std::exception& e) {
+    wfm_set_error(handles[0], e.what());
+    return WFM_E_ARG;
+  }
+}
+
+void wfmh_free_ani_rows(wfmh_ani_row_t* rows, int64_t n_rows) {
+  if (!rows) return;
+  for (int64_t i = 0; i < n_rows; ++i) { std::free(rows[i].query_group); std::free(rows[i].target_group); }
+  std::free(rows);
+}
+
+char* wfmh_test_ani_tsv(const char* const* query_groups, const char* const* target_groups, const uint64_t* query_hashes, const uint64_t* target_hashes,
+                        const uint64_t* shared, int64_t n) {
+  std::vector<skch::Stat::AniRow> rows;
+  for (int64_t i = 0; i < n; ++i) rows.push_back(skch::Stat::ani_row(query_groups[i], target_groups[i], query_hashes[i], target_hashes[i], shared[i]));
+  return strdup(skch::Stat::ani_tsv(rows).c_str());
 }
 
 int wfmh_seed_paf(const char* target_fasta, const char* query_fasta, const char* seeds_paf, const char* out_paf, const wfmh_map_params_t* params,

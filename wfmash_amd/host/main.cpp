@@ -26,6 +26,12 @@
 //                                              --resident-seqs, refused with -m.  Costs far more than the alignment on near-identical records
 //   --verify-paf FILE target.fa [query.fa]     the same check on an existing aligned PAF (this build's or the reference's): no mapping,
 //                                              no alignment; exit status 3 if a line fails
+//   --ani-matrix FILE [--ani-only]             the group-by-group ANI table the identity estimate (-p aniN) is made from, as TSV: per
+//                                              (query group, target group) pair the sizes of the two pooled MinHash sketches, their shared
+//                                              hashes (counted on the device, wfm_sketch_intersections), Jaccard and ANI; written before
+//                                              mapping starts, also when -p gives a number, and the run then goes on unchanged (the reference
+//                                              prints the table to stderr, map_stats.hpp:746-752).  --ani-only stops after the table: no
+//                                              index, no PAF.  Refused with -i and with -K (no map phase)
 //   --hg-filter n,D,conf                       numerator, ANI difference and confidence of the L1 / L2 cutoffs (:94, :700-725)
 //   -B DIR / -Z                                directory of the map-to-align hand-off file [cwd] / keep that file (:134-135)
 //   --quiet, --ani-sketch-size INT             accepted and without effect: there is no progress meter, and the identity
@@ -94,6 +100,8 @@ static void usage() {
           "            -N no split   -M no merge   -f no filter   -o one-to-one   -O FLOAT max overlap [0.95]   -x FLOAT sparsify [1.0]\n"
           "            -H INT L1 hits [3]   -F FLOAT high-frequency filter [0.0002]   -b SIZE target batch [all]\n"
           "            --hg-filter n,D,conf hypergeometric filter [1.0,0.0,99.9]   --ani-sketch-size INT (no effect)\n"
+          "            --ani-matrix FILE write the group-by-group ANI table the identity estimate is made from (TSV), then go on\n"
+          "            --ani-only stop after the table (needs --ani-matrix)\n"
           "            -W FILE build the index, write it and stop   -I FILE read the index from FILE\n"
           "            --streaming-minhash target sketches from a per-sequence bottom-s MinHash (experimental)\n"
           "            -K FILE external PAF seeds in place of the mapper ('-' = stdin)\n"
@@ -116,8 +124,8 @@ int main(int argc, char** argv) {
   ap.threads = 1;  // -t, default 1 as in the reference (parse_args.hpp: thread_count); the C ABI default (0) means all cores
   wfmh_map_params_t mp;
   wfmh_map_default_params(&mp);
-  std::string mapping_in, out = "/dev/stdout", target, query, seeds_in, scaffold_out, tmp_base, verify_in;
-  bool verify = false, verify_optimal = false;
+  std::string mapping_in, out = "/dev/stdout", target, query, seeds_in, scaffold_out, tmp_base, verify_in, ani_matrix_out;
+  bool verify = false, verify_optimal = false, ani_only = false;
   uint64_t verify_optimal_cells = 0;
   bool approx_only = false, target_padding_given = false, query_padding_given = false, keep_temp = false;
   int device = 0, gpus = 1;
@@ -145,6 +153,8 @@ int main(int argc, char** argv) {
     else if (a == "-Z" || a == "--keep-temp") keep_temp = true;
     else if (a == "--quiet") {}  // no progress meter to turn off
     else if (a == "--streaming-minhash") mp.streaming_minhash = 1;
+    else if (a == "--ani-matrix") ani_matrix_out = next("--ani-matrix");
+    else if (a == "--ani-only") ani_only = true;
     // ---- mapping (parse_args.hpp:71-115)
     else if (a == "-k" || a == "--kmer-size") mp.kmer_size = atoi(next("-k").c_str());
     else if (a == "-s" || a == "--sketch-size") mp.sketch_size = atoi(next("-s").c_str());
@@ -261,6 +271,16 @@ int main(int argc, char** argv) {
   if (verify && approx_only) { fprintf(stderr, "[wfmash] ERROR: --verify checks alignments: it cannot be combined with -m\n"); return 1; }
   if (verify_optimal && approx_only) { fprintf(stderr, "[wfmash] ERROR: --verify-optimal checks alignment scores: it cannot be combined with -m\n"); return 1; }
   if (verify_optimal_cells && !verify_optimal) { fprintf(stderr, "[wfmash] ERROR: --verify-optimal-cells needs --verify-optimal\n"); return 1; }
+  if (ani_only && ani_matrix_out.empty()) { fprintf(stderr, "[wfmash] ERROR: --ani-only needs --ani-matrix FILE\n"); return 1; }
+  if (!ani_matrix_out.empty() && !mapping_in.empty()) {
+    fprintf(stderr, "[wfmash] ERROR: --ani-matrix belongs to the map phase: it cannot be combined with -i (align mappings from a file)\n");
+    return 1;
+  }
+  if (!ani_matrix_out.empty() && !seeds_in.empty()) {
+    fprintf(stderr, "[wfmash] ERROR: --ani-matrix belongs to the map phase: it cannot be combined with -K (external seeds)\n");
+    return 1;
+  }
+  if (!ani_matrix_out.empty() && !verify_in.empty()) { fprintf(stderr, "[wfmash] ERROR: --ani-matrix cannot be combined with --verify-paf\n"); return 1; }
   if (!verify_in.empty()) {  // an existing PAF against its sequences; nothing else runs
     wfm_handle_t* hv = nullptr;
     if (wfm_create(device, &hv) != WFM_OK) { fprintf(stderr, "[wfmash] ERROR: no usable MI355X device %d (there is no CPU fallback)\n", device); return 2; }
@@ -328,6 +348,14 @@ int main(int argc, char** argv) {
   }
   wfm_handle_t* h = hs.front();
   auto destroy_all = [&] { for (wfm_handle_t* o : hs) wfm_destroy(o); };
+  if (ani_only) {  // the table and nothing else: no index, no mapping, no PAF
+    const int arc = wfmh_ani_matrix(hs.data(), (int)hs.size(), target.c_str(), q, &mp, ani_matrix_out.c_str());
+    if (arc == WFM_OK) fprintf(stderr, "[wfmash::ani] table written to %s\n", ani_matrix_out.c_str());
+    else fprintf(stderr, "[wfmash::ani] ERROR: %s\n", wfm_last_error(h));
+    destroy_all();
+    return arc == WFM_OK ? 0 : 3;
+  }
+  if (!ani_matrix_out.empty()) wfmh_set_ani_matrix(ani_matrix_out.c_str());  // the map call below writes it before it maps
   int rc = WFM_OK;
   std::string mapping = mapping_in;
   std::string temp;
