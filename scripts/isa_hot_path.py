@@ -4,15 +4,23 @@ assembly (hipcc -S --cuda-device-only): the text between two consecutive s_barri
 and TAKING every forward `s_cbranch_vccz / s_cbranch_execz` (the branches that skip work no lane has: the special selects, the global-mirror
 probe, stage 2, the wave tail).  Each vector instruction is priced with the issue cycles profiles/r6_valu_issue.md measured for its kind
 (W = 4 column); the sum is the issue time of a wave's step and the weighted mean is what bench.py's `valu` peak uses.
-usage: isa_hot_path.py tile2.s [step_index]"""
+usage: isa_hot_path.py tile2.s [step_index] [--fine[=SLOTS]]
+--fine prices the instantiation with per-score maxima, <1024, false, true, true, SLOTS> (SLOTS: its LDS slots per score, default 16; --fine=0:
+an assembly from before the slots, <1024, false, true, true>) instead of the coarse one."""
 import re
 import sys
 from collections import Counter
 
-asm = open(sys.argv[1]).read().split("\n")
-which = int(sys.argv[2]) if len(sys.argv) > 2 else 5
-# the phase-1 multi-wave FAST kernel
-start = next(i for i, l in enumerate(asm) if l.startswith("_ZN3wfm16wfa_tile2_kernelILi1024ELb0ELb1ELb0EEE") and l.rstrip().endswith(":") or (l.startswith("_ZN3wfm16wfa_tile2_kernelILi1024ELb0ELb1ELb0EEE") and ":" in l))
+fine = [a for a in sys.argv[1:] if a.startswith("--fine")]
+args = [a for a in sys.argv[1:] if not a.startswith("--fine")]
+asm = open(args[0]).read().split("\n")
+which = int(args[1]) if len(args) > 1 else 5
+# the phase-1 multi-wave FAST kernel (the name's prefix: the coarse form's slot parameter is 0, older assemblies have none)
+name = "_ZN3wfm16wfa_tile2_kernelILi1024ELb0ELb1ELb0E"
+if fine:
+    slots = int(fine[0].split("=")[1]) if "=" in fine[0] else 16
+    name = "_ZN3wfm16wfa_tile2_kernelILi1024ELb0ELb1ELb1E" + (f"Li{slots}EEE" if slots else "EE")
+start = next(i for i, l in enumerate(asm) if l.startswith(name) and ":" in l)
 end = next(i for i in range(start, len(asm)) if "s_endpgm" in asm[i])
 body = asm[start:end]
 bars = [i for i, l in enumerate(body) if l.strip() == "s_barrier"]

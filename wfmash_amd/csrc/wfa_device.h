@@ -259,6 +259,13 @@ void launch_seq_pack(const uint8_t* seq, uint32_t* pk, int64_t nwords, int64_t n
 constexpr int64_t PK_PAD_WORDS = 2048 + 64;  // words of padding behind the mirror: a tile stages a whole window from any origin inside
 // the tile kernel on packed sequences (wfa_tile2.hip): same contract as launch_tile_reg / launch_tile_p2
 void launch_tile2(const uint32_t* pk, int32_t* ring, const TileJob* jobs, const TileTask* tasks, int32_t* mak, int ntasks, int threads, int T, int variants, hipStream_t st);
+// LDS slots per score of the packed kernel's per-score maxima (its FAST + FINE phase-1 form), by workgroup size: (T + 1) * slots * 4 bytes of
+// dynamic LDS beside ~17.5 KB of static, sized so that the workgroups a CU holds by registers still fit its 160 KB (8 of 128 threads, 4 of 256)
+#ifndef WFM_TILE_SLOTS_WIDE
+#define WFM_TILE_SLOTS_WIDE 16
+#endif
+constexpr int TILE_SLOTS_WAVE1 = 2, TILE_SLOTS_SMALL = 4, TILE_SLOTS_WIDE = WFM_TILE_SLOTS_WIDE;
+constexpr int tile_fine_slots(int threads) { return threads <= 64 ? TILE_SLOTS_WAVE1 : (threads <= 128 ? TILE_SLOTS_SMALL : TILE_SLOTS_WIDE); }
 bool tile2_coarse_maxima();  // wfa_tile2_kernel keeps one maximum per block below TileJob::fine_s (the FAST form; WFM_TILE_COARSE=0: per score always)
 void launch_tile2_p2(const uint32_t* pk, int32_t* ring, const TileJob* jobs, const TileTask* tasks, int ntasks, int threads, int32_t* p2, hipStream_t st);
 int selftest_dpp(int* host_out128, hipStream_t st);

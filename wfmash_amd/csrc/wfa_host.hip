@@ -650,9 +650,12 @@ TileCfg tile_cfg(const wfm_penalties_t& pen, int scope) {
   c.reg = dflt && !(getenv("WFM_TILE_REG") && atoi(getenv("WFM_TILE_REG")) == 0);
   if (c.reg) {
     if (!getenv("WFM_TILE_THREADS")) c.threads = 512;
-    // (the FINE instantiation of the packed kernel keeps a row of T + 1 maxima per wave in dynamic LDS beside ~24 KB of static: a WFM_TILE_T that
-    // would not fit 64 KB is cut here instead of failing the launch)
-    c.T = std::min(c.T, (int)((40 * 1024) / (4 * std::max(1, c.threads / 64))) - 1);
+    // (the FINE instantiation of the packed kernel keeps T + 1 scores' maxima, tile_fine_slots words each, in dynamic LDS beside ~24 KB of static:
+    // a WFM_TILE_T that would not fit 64 KB is cut here instead of failing the launch -- at the slots of the widest workgroups, whatever c.threads)
+    c.T = std::min(c.T, (int)((40 * 1024) / (4 * TILE_SLOTS_WIDE)) - 1);
+    // (a tile beside others keeps Wt - 2 T diagonals of its own between its halos: a WFM_TILE_THREADS too small to keep any is raised, wave by
+    // wave, to the first that does -- 64 threads at T = 100 run as 128)
+    while (c.threads * c.C <= 2 * c.T && c.threads < 1024) c.threads += 64;
     // (two diagonals per lane, always: the phase-2 rows, the single-tile sizing and the packed kernel are built for it.  The WFM_TILE_C=4
     // switch of round 1 sized the tasks for four while those stages went on with two -- wrong results; it is gone)
     if (const char* e = getenv("WFM_TILE_CHUNK")) c.chunk = std::max(1, atoi(e));

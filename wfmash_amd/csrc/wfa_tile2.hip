@@ -338,16 +338,21 @@ void launch_seq_pack(const uint8_t* seq, uint32_t* pk, int64_t nwords, int64_t n
 //    problem (h > tl or v > pl: the far edges of the matrix, which the two directions of a BiWFA job never reach together); otherwise every
 //    source is either inside or NULL already.  A NULL then drifts -- NULL + 1 + ... -- instead of being set back to WF_NULL at every step:
 //    every reader of a wavefront takes "negative" for NULL (max(), >= 0, o0 + o1 >= tl), and -2^30 + 17 per step stays negative for 6 * 10^7 steps;
-//  * the per-step maximum of the antidiagonals goes to a slot of the wave's own (plain store) instead of through an LDS atomic (a scalar loop);
+//  * the per-step maximum of the antidiagonals went to a slot of the wave's own (plain store) instead of through atomicMax (as compiled: a scalar
+//    loop over the lanes); the phase-1 forms have a ds_max_i32 without a return value now (__hip_atomic_fetch_max, relaxed, workgroup scope: FINE, below);
 //  * the mailbox's buffer index is the step's parity within the ten-step body, at compile time (adjacent steps never share a buffer);
 //  * the probe's window words are addressed by masking (pk_extend2<true>), dead cells keep what the arithmetic leaves them with.
-// FINE (round 6, FAST phase-1 form only): the per-score maxima of the antidiagonals -- a six-step DPP reduction per wave and score, a seventh of
-// the step's vector issue -- are kept only by the FINE instantiation, which takes the tiles of the jobs whose block needs them (TileJob::fine_s:
-// the block in which the directions meet); the other instantiation takes all other tiles and keeps one running maximum per lane, reduced once
-// per block.  Both are launched over the same task list (the host leaves out the one no job of the block can need); a tile that is not this
+// FINE (round 6, FAST phase-1 form only): the per-score maxima of the antidiagonals are kept only by the FINE instantiation, which takes the
+// tiles of the jobs whose block needs them (TileJob::fine_s: the block in which the directions meet); the other instantiation takes all other
+// tiles and keeps one running maximum per lane, reduced once per block.  The FINE one paid a six-step DPP reduction per wave and score for them
+// (12 vector instructions, 7 s_nop and a masked store: a seventh of the step's vector issue); now a score has MS slots in LDS, s_makr[T + 1][MS],
+// shared by the workgroup's waves, a lane puts its maximum into slot lane & (MS - 1) with one ds_max_i32 -- the other instantiation's price --
+// and the slots are reduced once per block, behind the loop: a FINE step is the other's, instruction for instruction (profiles/fine_maxima_lds.md).
+// MS is the launch's (tile_fine_slots, wfa_device.h): what the workgroups a CU holds by registers can pay in LDS.
+// Both are launched over the same task list (the host leaves out the one no job of the block can need); a tile that is not this
 // instantiation's ends before its first load.  (One kernel with a runtime test was built first: the optimizer then neither unrolls the ten-step
 // body nor keeps the delay lines in registers; two copies of the loop in one kernel spill.)
-template <int NTMAX, bool P2, bool FAST, bool FINE = true>
+template <int NTMAX, bool P2, bool FAST, bool FINE = true, int MS = 0>
 __global__ __launch_bounds__(NTMAX) void wfa_tile2_kernel(const uint32_t* __restrict__ pk, int32_t* __restrict__ ring_arena,
                                                         const TileJob* __restrict__ jobs, const TileTask* __restrict__ tasks,
                                                         int32_t* __restrict__ mak_out, int T, int32_t* __restrict__ p2_arena, int coarse) {
@@ -360,13 +365,17 @@ __global__ __launch_bounds__(NTMAX) void wfa_tile2_kernel(const uint32_t* __rest
   // chains in one basic block instead of one chain of twice the length.  The row waits in pM[] (before its extension); its delay line takes it
   // one step late, which no reader can see (a class's line is only read at its own steps).
   constexpr bool PIPE = FAST && !P2;
+  // SLOTS: the FAST + FINE phase-1 form keeps a score's maximum in MS words of LDS, a lane's slot being lane & (MS - 1) -- one ds_max_i32 per step,
+  // the price of the coarse form's running maximum; the slots are reduced once, behind the loop (launch_tile2 picks MS by the workgroup's size)
+  constexpr bool SLOTS = FAST && FINE && !P2;
+  static_assert(!SLOTS || (MS >= 2 && MS <= 64 && (MS & (MS - 1)) == 0), "slots per score: a power of two within a wave");
   // mailbox of the wave edges: [parity][slot][side][value].  Side 0 of slot w holds what lane 63 of wave w - 1 hands to lane 0 of wave w, side 1 of
   // slot w what lane 0 of wave w hands to lane 63 of wave w - 1; slot 0's side 0 and the slot behind the last wave are never written and stay
   // NULL, so the edge lanes of a tile read their mailbox like all others and the wave shifts need no NULL to fall back on
   __shared__ __attribute__((aligned(16))) int s_edge[2][WAVE1 ? 1 : 17][2][4];
   __shared__ __attribute__((aligned(16))) uint32_t s_winP[PK_WIN_DW + PK_SLACK_DW], s_winT[PK_WIN_DW + PK_SLACK_DW];
   __shared__ int s_wlo[2];
-  extern __shared__ __attribute__((aligned(16))) int s_makr[];  // [T + 1]; FAST: [waves][T + 1], a row per wave
+  extern __shared__ __attribute__((aligned(16))) int s_makr[];  // [T + 1]; SLOTS: [T + 1][MS], a score's MS slots shared by all waves
   TileTask tk = tasks[blockIdx.x];
   const TileJob J = jobs[tk.job];
   if (!J.active) return;
@@ -480,8 +489,14 @@ __global__ __launch_bounds__(NTMAX) void wfa_tile2_kernel(const uint32_t* __rest
     ld_row(C_I2, s0, I2h[0], I2h[1]);
     ld_row(C_D2, s0, D2h[0], D2h[1]);
   }
-  const int MKS = T + 1;  // stride of a wave's row of s_makr (FAST)
-  if (FINE && !P2) for (int t = tid; t < (FAST && !WAVE1 ? nw * MKS : MKS); t += NT) s_makr[t] = 0;
+  if (FINE && !P2) for (int t = tid; t < (SLOTS ? (T + 1) * MS : T + 1); t += NT) s_makr[t] = 0;
+  // SLOTS: a score's maximum into the lane's slot of it.  mk_off: the byte offset of the lane's slot of the body's first score, carried from body to
+  // body, so that a step's place within the body is the instruction's offset field and costs no address arithmetic (addressed from the step's
+  // number, a scalar, every step made its address with two vector instructions)
+  unsigned mk_off = (unsigned)(lane & (MS - 1)) * 4u;
+  auto slot_max = [&](int j, int mak) {  // ds_max_i32, nothing returned
+    (void)__hip_atomic_fetch_max(static_cast<int*>(__builtin_assume_aligned(reinterpret_cast<char*>(s_makr) + mk_off, 4)) + j * MS, mak, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  };
   // ---- per-cell constants
   unsigned hmaxu[C];  // largest offset inside the problem on this diagonal: min(tl, pl + k)
   int s_last[C];      // the last score at which the cell is inside its row (columns outside [-pl, tl]: never)
@@ -739,12 +754,7 @@ __global__ __launch_bounds__(NTMAX) void wfa_tile2_kernel(const uint32_t* __rest
         default: line_take(std::integral_constant<int, 9>{}, fin); break;
       }
       if (!FINE) (void)__hip_atomic_fetch_max(&s_run[tid], mak, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);  // ds_max_i32, nothing returned
-      else {
-        // (Tried in round 6 and taken out: four row steps and an LDS maximum from the four row ends instead of six DPP steps and a masked store --
-        // ten instructions less in the instantiation C1 / C2 / C4 run every block of, and nothing in their device time: gpurun_out/r6y/ab4.log.)
-        mak = wave_max63(mak);
-        if (lane == 63) s_makr[(WAVE1 ? 0 : wv * MKS) + t - 1] = mak;
-      }
+      else slot_max(jj - 1, mak);  // (round 6 had six DPP steps and a masked store per wave here, then tried four row steps and an LDS maximum: DESIGN section 8 (i))
       // ---- this step's row waits for its extension; its gap components are final
       if (__builtin_expect(t > t_stream, 0)) {  // stream the last rows of I/D of the core to the output snapshot
         stream_gap_rows(s, nI1, nI2, nD1, nD2);
@@ -827,8 +837,7 @@ __global__ __launch_bounds__(NTMAX) void wfa_tile2_kernel(const uint32_t* __rest
       if (FAST && !FINE) (void)__hip_atomic_fetch_max(&s_run[tid], mak, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);  // ds_max_i32, nothing returned
       else {
         mak = wave_max63(mak);
-        if (FAST) { if (lane == 63) s_makr[(WAVE1 ? 0 : wv * MKS) + t] = mak; }
-        else if (lane == 63 && mak > 0) {
+        if (lane == 63 && mak > 0) {
           if (WAVE1) s_makr[t] = mak;
           else atomicMax(&s_makr[t], mak);
         }
@@ -839,6 +848,7 @@ __global__ __launch_bounds__(NTMAX) void wfa_tile2_kernel(const uint32_t* __rest
 #undef M_S10
 #undef M_S25
   }
+    if (SLOTS) { mk_off += (unsigned)(UB * MS * 4); asm volatile("" : "+v"(mk_off)); }  // (opaque: else the optimizer goes back to the step's number)
   }
   if (PIPE) {
     // the last step's row is still pending: its extension, then into its line
@@ -865,7 +875,7 @@ __global__ __launch_bounds__(NTMAX) void wfa_tile2_kernel(const uint32_t* __rest
       default: line_take(std::integral_constant<int, UB>{}, fin); break;
     }
     if (!FINE) (void)__hip_atomic_fetch_max(&s_run[tid], mak, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    else { mak = wave_max63(mak); if (lane == 63) s_makr[(WAVE1 ? 0 : wv * MKS) + Tn] = mak; }
+    else slot_max(Tn - (Tn + UB - 1) / UB * UB, mak);  // (mk_off stands one body behind the last)
   }
   WFM_TRACE_MARK(122);
   // ---- output snapshot: the newest H rows of M for the core ----
@@ -963,11 +973,19 @@ __global__ __launch_bounds__(NTMAX) void wfa_tile2_kernel(const uint32_t* __rest
     return;
   }
   __syncthreads();
-  for (int t = 1 + tid; t <= T; t += NT) {
-    int v = s_makr[t];
-    if (FAST && !WAVE1) for (int w = 1; w < nw; ++w) v = max(v, s_makr[w * MKS + t]);
-    if (v > 0) atomicMax(&mk[t - 1], v);
+  if (SLOTS) {
+    // a wave takes 64 / MS scores at a time: a lane reads one slot, the MS lanes of a score reduce among themselves (every lane of the wave makes
+    // the shuffles: the loop's bounds are wave-uniform), the score's first lane hands the maximum on
+    for (int i0 = wv * 64; i0 < T * MS; i0 += NT) {
+      const int i = i0 + lane;  // slot i % MS of score 1 + i / MS
+      int v = i < T * MS ? s_makr[MS + i] : 0;
+#pragma unroll
+      for (int o = MS / 2; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
+      if ((i & (MS - 1)) == 0 && i < T * MS && v > 0) atomicMax(&mk[i / MS], v);
+    }
+    return;
   }
+  for (int t = 1 + tid; t <= T; t += NT) if (s_makr[t] > 0) atomicMax(&mk[t - 1], s_makr[t]);
 }
 
 static bool tile_fast() {  // (read per launch: the tests switch forms inside one process)
@@ -999,8 +1017,11 @@ void launch_tile2(const uint32_t* pk, int32_t* ring, const TileJob* jobs, const 
     }
     if (variants & 2) {
       const int cf = coarse | (variants == 2 ? 2 : 0);
-      if (threads <= 64) hipLaunchKernelGGL((wfa_tile2_kernel<64, false, true, true>), dim3(ntasks), dim3(64), lds1, st, pk, ring, jobs, tasks, mak, T, (int32_t*)nullptr, cf | lean);
-      else hipLaunchKernelGGL((wfa_tile2_kernel<1024, false, true, true>), dim3(ntasks), dim3(threads), lds1 * (size_t)(threads / 64), st, pk, ring, jobs, tasks, mak, T, (int32_t*)nullptr, cf | lean);
+      // (slots per score by the workgroup's size, tile_fine_slots: what the workgroups a CU holds by registers can pay in LDS -- profiles/fine_maxima_lds.md)
+      const size_t ldsm = lds1 * (size_t)tile_fine_slots(threads);
+      if (threads <= 64) hipLaunchKernelGGL((wfa_tile2_kernel<64, false, true, true, TILE_SLOTS_WAVE1>), dim3(ntasks), dim3(64), ldsm, st, pk, ring, jobs, tasks, mak, T, (int32_t*)nullptr, cf | lean);
+      else if (threads <= 128) hipLaunchKernelGGL((wfa_tile2_kernel<1024, false, true, true, TILE_SLOTS_SMALL>), dim3(ntasks), dim3(threads), ldsm, st, pk, ring, jobs, tasks, mak, T, (int32_t*)nullptr, cf | lean);
+      else hipLaunchKernelGGL((wfa_tile2_kernel<1024, false, true, true, TILE_SLOTS_WIDE>), dim3(ntasks), dim3(threads), ldsm, st, pk, ring, jobs, tasks, mak, T, (int32_t*)nullptr, cf | lean);
     }
   } else {
     if (threads <= 64) hipLaunchKernelGGL((wfa_tile2_kernel<64, false, false, true>), dim3(ntasks), dim3(64), lds1, st, pk, ring, jobs, tasks, mak, T, (int32_t*)nullptr, lean);
