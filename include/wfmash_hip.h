@@ -296,6 +296,39 @@ typedef struct {
 int wfm_check_runs(wfm_handle_t* h, const wfm_penalties_t* pen, const wfm_seqset_t* s,
                    const wfm_result_t* res, const uint32_t* runs, size_t n_runs_total, wfm_check_t* out);
 
+/* ---- every interior gap moved to its leftmost placement ----
+ * An indel inside a homopolymer or a tandem repeat has many placements of one score; the aligners leave it at the rightmost (they extend
+ * matches before they open a gap).  This call moves every interior gap as far to the left as a rotation of its own bases allows -- the
+ * convention of minimap2 and of VCF normalisation -- on the device (wfmash_amd/csrc/wfa_leftalign.hip; forward BYTE copies only, bytes compared
+ * as bytes like wfm_check_runs: N equals N).  s, res and runs as for wfm_check_runs; the runs must be valid (M over equal bytes, X over
+ * different ones, spanning plen x tlen).
+ *
+ * The rule.  The runs are taken from left to right and the output is built on the way.  An interior gap is an I or D run of L bases that is
+ * neither the problem's first nor its last run (those are never touched); g = its first index in S, S = pattern for D, text for I.
+ *   rot  = the number of k >= 1, counted consecutively from 1, with S[g - k] == S[g + L - k];
+ *   room = 0 if the run now before the gap in the output is no M run, else that run's current length e (with what the gap before may have
+ *          added to it) -- but e - 1 if that M run is the output's first run or the run before it is a gap of the same op: a gap never
+ *          becomes the first run, and two gaps of one op never merge;
+ *   d    = min(rot, room): the M run before the gap loses d bases (and goes at 0), the gap keeps its length, the d bases join the M run
+ *          behind it or become a new M run where what follows is no M run.
+ * So a problem's run count may shrink, or grow by at most one per gap.  The result is a valid CIGAR of the same bases with the same price
+ * under any penalties and the same wfm_check_t counts; the first and last runs keep their ops; applying the call twice changes nothing.
+ * Not normalised: end gaps, a gap behind an X run, gaps that would merge, co-optimal placements that differ by more than a rotation.
+ *
+ * *runs_out receives the new runs of all problems end to end (release with wfm_free_runs), adjacent runs never sharing an op,
+ * *n_runs_out_total their number; res[i].ops_off and res[i].n_runs are rewritten to locate problem i in *runs_out, and score, ops_len and
+ * cells are never touched.  out receives one wfm_leftalign_t per problem: gaps = its interior gaps, moved = those with d > 0, bases_moved
+ * = the sum of d, longest = the largest d, runs_out = its runs now.  A problem flagged WFM_LA_NOT_DONE or WFM_LA_SPANS keeps its runs
+ * verbatim.  Returns the number of problems flagged WFM_LA_SPANS, or a WFM_E_* code; a run range that leaves runs[0 .. n_runs_total) is
+ * WFM_E_ARG (the handle stays usable).  (WFM_LA_LANE_MAX, read per call: the bases after which a gap's comparison leaves its single lane for
+ * a whole wave, 256; a measuring switch.) */
+typedef struct { uint32_t flags, gaps, moved, runs_out; uint64_t bases_moved; uint32_t longest, pad_; } wfm_leftalign_t;  /* 32 bytes */
+#define WFM_LA_NOT_DONE 1u   /* status != 0, score-only, no runs */
+#define WFM_LA_SPANS    2u   /* the runs do not span plen x tlen, or hold a bad run: left exactly as they came */
+int wfm_left_align_runs(wfm_handle_t* h, const wfm_seqset_t* s, wfm_result_t* res /* n_runs, ops_off rewritten */,
+                        const uint32_t* runs, size_t n_runs_total, uint32_t** runs_out, size_t* n_runs_out_total,
+                        wfm_leftalign_t* out);   /* runs_out: wfm_free_runs */
+
 /* ---- every score proved optimal by a banded DP ----
  * What wfm_check_runs leaves out.  For every problem of the seqset s whose result claims a score S = res[i].score, a classical
  * minimising gap-affine-2-piece DP over cells (i = pattern index, j = text index) is run on the device, restricted to a band of

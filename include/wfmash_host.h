@@ -115,6 +115,17 @@ char* wfmh_test_verify_parse(const char* line);
 void wfmh_set_verify_optimal(int on, uint64_t max_cells);
 int  wfmh_verify_optimal_counts(uint64_t out[4]);
 
+/* ---- every interior gap of the records' final CIGARs at its leftmost placement (wfm_left_align_runs, wfmash_hip.h) ----
+ * wfmh_set_left_align(1): from now on every batch of wfmh_align_paf[_multi] runs ONE more device call between the swizzle and the record
+ * writers: the runs each record's line will spell (its final ops without the leading and trailing gaps the writers strip) against the
+ * sub-windows they cover, by reference where the run keeps its sequences on the device.  Only cg:Z: changes in a PAF line, only CIGAR
+ * and MD in a SAM record; wfmh_set_verify then checks the normalised lines.  A record whose runs do not span its windows is written as
+ * it is and counted as left alone (the pipeline produces none).  Every call zeroes the counts.  wfmh_left_align_counts: out = {records
+ * handed to the device, their interior gaps, gaps moved, records left alone} since then.  Off by default; with the switch off the
+ * swizzle and the writers run back to back as ever, nothing new is called and the counts stay 0. */
+void wfmh_set_left_align(int on);
+int  wfmh_left_align_counts(uint64_t out[4]);
+
 /* Test hooks: the pure host-side CIGAR functions (erode / merge / swizzle / PAF writer /
  * parseMashmapRow) behind one string interface so the CPU test-suite can check them
  * without a GPU.  fn in {erode, merge, compress, swap_start, swap_end, head_erosion,

@@ -44,7 +44,7 @@ EXPORTS = [
     "wfm_sketch_part", "wfm_minmer_part_info", "wfm_minmer_part_download", "wfm_minmer_part_free", "wfm_index_build_parts",
     "wfm_seqstore_create", "wfm_seqstore_free", "wfm_seqstore_add", "wfm_seqstore_info",
     "wfm_upload_sequence_refs", "wfm_align_refs_rle", "wfm_download_sequences",
-    "wfm_check_runs", "wfm_check_optimal",
+    "wfm_check_runs", "wfm_check_optimal", "wfm_left_align_runs",
     "wfm_sketch_intersections",
 ]
 ISECT_LDS_MAX = 4096  # WFM_ISECT_LDS_MAX: the longest column sketch wfm_sketch_intersections searches in LDS
@@ -52,6 +52,8 @@ ISECT_LDS_MAX = 4096  # WFM_ISECT_LDS_MAX: the longest column sketch wfm_sketch_
 WFM_CK_NOT_CHECKED, WFM_CK_BAD_RUN, WFM_CK_SPANS, WFM_CK_M_DIFFERS, WFM_CK_X_EQUAL, WFM_CK_SCORE, WFM_CK_COUNTS = 1, 2, 4, 8, 16, 32, 64
 CK_NAMES = ("NOT_CHECKED", "BAD_RUN", "SPANS", "M_DIFFERS", "X_EQUAL", "SCORE", "COUNTS")
 CHECK_SLICE = 16384  # WFM_CHECK_SLICE: ops one compare task covers
+# wfm_left_align_runs (include/wfmash_hip.h): why a problem's runs were left as they came
+WFM_LA_NOT_DONE, WFM_LA_SPANS = 1, 2
 # wfm_check_optimal (include/wfmash_hip.h): what a problem's score was flagged for, and the band widths at which the kernel changes form
 WFM_OPT_NOT_CHECKED, WFM_OPT_SKIPPED, WFM_OPT_CHEAPER, WFM_OPT_UNREACHED = 1, 2, 4, 8
 OPT_NAMES = ("NOT_CHECKED", "SKIPPED", "CHEAPER", "UNREACHED")
@@ -99,6 +101,12 @@ class Check(C.Structure):
                 ("bad_run", C.c_uint32), ("n_runs", C.c_uint32),
                 ("matches", C.c_uint32), ("mismatches", C.c_uint32), ("ins_runs", C.c_uint32), ("ins_bases", C.c_uint32),
                 ("del_runs", C.c_uint32), ("del_bases", C.c_uint32)]
+
+
+class LeftAlign(C.Structure):
+    """wfm_leftalign_t: what wfm_left_align_runs did to one problem's runs."""
+    _fields_ = [("flags", C.c_uint32), ("gaps", C.c_uint32), ("moved", C.c_uint32), ("runs_out", C.c_uint32),
+                ("bases_moved", C.c_uint64), ("longest", C.c_uint32), ("pad_", C.c_uint32)]
 
 
 class OptCheck(C.Structure):
@@ -661,6 +669,37 @@ class Handle:
             raise WfmError(f"wfm_check_runs failed ({rc}): {self.last_error()}")
         return rc, [out[i] for i in range(n)]
 
+    def left_align(self, seqset, results, runs):
+        """wfm_left_align_runs: every interior gap moved to its leftmost placement.  results and runs as for check_runs (a list of
+        (status, score, ops_off, ops_len, n_runs) is copied; a ctypes array of Result is copied as well: the caller's stays as it is).
+        Returns (results: a new ctypes array of Result whose ops_off / n_runs locate the problems in the new runs, runs: uint32 array,
+        stats: [LeftAlign], one per problem)."""
+        n = seqset.n
+        arr = (Result * max(n, 1))()
+        if isinstance(results, C.Array):
+            C.memmove(arr, results, C.sizeof(Result) * n)
+        else:
+            assert len(results) == n, (len(results), n)
+            for i, (status, score, ops_off, ops_len, n_runs) in enumerate(results):
+                arr[i].status, arr[i].score, arr[i].ops_off, arr[i].ops_len, arr[i].n_runs = status, score, ops_off, ops_len, n_runs
+        runs = np.ascontiguousarray(runs, dtype=np.uint32)
+        out = (LeftAlign * max(n, 1))()
+        new = C.POINTER(C.c_uint32)()
+        total = C.c_size_t(0)
+        f = self._L.wfm_left_align_runs
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_size_t), C.c_void_p]
+        self._L.wfm_free_runs.restype = None
+        self._L.wfm_free_runs.argtypes = [C.POINTER(C.c_uint32)]
+        rc = f(self._p, seqset._p, arr, runs.ctypes.data if len(runs) else None, len(runs), C.byref(new), C.byref(total), out)
+        if rc < 0:
+            raise WfmError(f"wfm_left_align_runs failed ({rc}): {self.last_error()}")
+        try:
+            a = np.ctypeslib.as_array(new, shape=(total.value,)).copy() if total.value else np.zeros(0, dtype=np.uint32)
+        finally:
+            self._L.wfm_free_runs(new)
+        return arr, a, [out[i] for i in range(n)]
+
     def check_optimal(self, seqset, results, pen=None, max_cells=0):
         """wfm_check_optimal: every score held against a banded DP on the device.  results: a ctypes array of Result (seqset.results after
         an align call), or a list of (status, score) or plain scores, one per problem of the seqset.  Returns the list of OptCheck records
@@ -1023,7 +1062,7 @@ HOST_EXPORTS = ["wfmh_test_packed_lce", "wfmh_test_is_acgt", "wfmh_align_default
                 "wfmh_release_sequences", "wfmh_test_fasta_shared", "wfmh_seed_paf", "wfmh_test_deal", "wfmh_test_subwindow",
                 "wfmh_test_rows", "wfmh_test_tile_plan", "wfmh_test_p2_plan", "wfmh_test_base_plan", "wfmh_test_map_plan", "wfmh_test_filter_ordered",
                 "wfmh_test_reuse_plan", "wfmh_test_tile_plan_dirs", "wfmh_test_tile_interior", "wfmh_test_tile_lean_waves", "wfmh_set_verify", "wfmh_verify_counts", "wfmh_verify_paf", "wfmh_test_verify_parse",
-                "wfmh_set_verify_optimal", "wfmh_verify_optimal_counts", "wfmh_test_opt_band",
+                "wfmh_set_verify_optimal", "wfmh_verify_optimal_counts", "wfmh_test_opt_band", "wfmh_set_left_align", "wfmh_left_align_counts",
                 "wfmh_ani_matrix", "wfmh_ani_matrix_rows", "wfmh_free_ani_rows", "wfmh_set_ani_matrix", "wfmh_test_ani_tsv"]
 
 
@@ -1372,6 +1411,27 @@ def verify_counts():
     rc = f(out)
     if rc != 0:
         raise WfmError(f"wfmh_verify_counts failed ({rc})")
+    return tuple(int(v) for v in out)
+
+
+def set_left_align(on: bool) -> None:
+    """wfmh_set_left_align: every later align_paf call of the process left-aligns its records' interior gaps on the device before they are
+    written; zeroes the counts."""
+    f = _host().wfmh_set_left_align
+    f.restype = None
+    f.argtypes = [C.c_int]
+    f(1 if on else 0)
+
+
+def left_align_counts():
+    """wfmh_left_align_counts: (records, gaps, gaps moved, records left alone) since wfmh_set_left_align was last called."""
+    f = _host().wfmh_left_align_counts
+    f.restype = C.c_int
+    f.argtypes = [C.POINTER(C.c_uint64)]
+    out = (C.c_uint64 * 4)()
+    rc = f(out)
+    if rc != 0:
+        raise WfmError(f"wfmh_left_align_counts failed ({rc})")
     return tuple(int(v) for v in out)
 
 

@@ -241,6 +241,22 @@ struct CheckTask { int32_t prob, slice; };  // ops [slice, slice + 1) * WFM_CHEC
 void launch_check(const uint8_t* seq, const uint32_t* runs, const CheckProb* probs, int nprob, const CheckTask* tasks, int64_t ntasks,
                   uint32_t* ops_pre, uint32_t* p_pre, uint32_t* t_pre, uint32_t* cmp_ops, unsigned long long* keys, void* out, DevPen pen,
                   hipStream_t st);
+// wfm_left_align_runs (wfa_leftalign.hip): a problem's forward byte copies, its runs, its slots in the output (n_runs + n_gaps of them)
+// and in the list of interior gaps
+struct LaProb {
+  int64_t p_off, t_off;
+  uint64_t run_off, out_off, gap_off;
+  uint32_t n_runs, n_gaps;             // n_gaps: interior I / D runs (neither the first nor the last run)
+  int32_t plen, tlen;
+  int32_t skip, pad_;                  // nonzero: WFM_LA_NOT_DONE (score-only, or status != 0)
+};
+struct LaGap { int64_t s_off; uint32_t g, len, prob, run; };  // S = the sequence buffer at s_off; the gap covers S[g, g + len); run: its index in the problem
+// index, rot (one lane per gap, then one wave per gap of the second list), shift + rewrite, on st.  rot / dval: one element per run of the call;
+// flags: one per problem; gaps / long_list: ngaps; long_count: 1, zeroed by the caller; stats: nprob wfm_leftalign_t.  lane_max: the bases after
+// which a gap leaves the lane kernel for the wave kernel
+void launch_left_align(const uint8_t* seq, const uint32_t* runs, const LaProb* probs, int nprob, uint32_t* rot, uint32_t* dval, LaGap* gaps,
+                       uint64_t ngaps, uint32_t* flags, uint32_t* long_list, uint32_t* long_count, uint32_t* out, void* stats, uint32_t lane_max,
+                       hipStream_t st);
 // wfm_check_optimal (wfa_optcheck.hip): a problem's forward byte copies, its ends-free allowances (clamped; 0 for the other modes),
 // its band of diagonals (wfa_optband.h) and, for the memory form, where its three row arrays begin in `rows` (32-bit elements)
 struct OptProb {

@@ -281,6 +281,7 @@ struct wfm_handle {
   DevBuf<SeqGatherTask> gathertasks;  // wfm_upload_sequence_refs
   DevBuf<uint64_t> checkbuf;         // wfm_check_runs: everything the call has on the device, carved out of one block
   DevBuf<uint64_t> optbuf;           // wfm_check_optimal: the problems and their results
+  DevBuf<uint64_t> labuf;            // wfm_left_align_runs: everything the call has on the device, carved out of one block
   DevBuf<int32_t> optrows;           // ... and the rows of the bands too wide for registers
   DevBuf<unsigned long long> total;
   void* attachment = nullptr;  // owned by another translation unit (map_kernels.hip: the pinned staging ring)
@@ -2217,7 +2218,7 @@ void wfm_destroy(wfm_handle_t* h) {
   h->p2rows.release(); h->p2max.release(); h->p2bmax.release(); h->p2pbmax.release(); h->p2jobs.release(); h->widenjobs.release(); h->keeptasks.release(); h->restoretasks.release(); h->restoreres.release();
   h->bpjobs.release(); h->bpres.release(); h->bsjobs.release(); h->bsres.release();
   h->b2tjobs.release(); h->b2ttasks.release(); h->b2tkeys.release(); h->b2toffs.release(); h->b2tactive.release();
-  h->i64a.release(); h->i64b.release(); h->i64c.release(); h->i32a.release(); h->seqflags.release(); h->flagjobs.release(); h->gathertasks.release(); h->checkbuf.release(); h->optbuf.release(); h->optrows.release(); h->total.release();
+  h->i64a.release(); h->i64b.release(); h->i64c.release(); h->i32a.release(); h->seqflags.release(); h->flagjobs.release(); h->gathertasks.release(); h->checkbuf.release(); h->optbuf.release(); h->labuf.release(); h->optrows.release(); h->total.release();
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->ev2) (void)hipEventDestroy(h->ev2);
@@ -2736,6 +2737,102 @@ int wfm_check_runs(wfm_handle_t* h, const wfm_penalties_t* pen, const wfm_seqset
   int flagged = 0;
   for (size_t i = 0; i < n; ++i) flagged += (out[i].flags & ~WFM_CK_NOT_CHECKED) != 0;
   return flagged;
+}
+
+// ---- every interior gap moved to its leftmost placement (wfmash_hip.h; the kernels: wfa_leftalign.hip) ----
+int wfm_left_align_runs(wfm_handle_t* h, const wfm_seqset_t* s, wfm_result_t* res, const uint32_t* runs, size_t n_runs_total, uint32_t** runs_out,
+                        size_t* n_runs_out_total, wfm_leftalign_t* out) {
+  if (!h || !s || !out || !res || !runs_out || (n_runs_total && !runs)) return WFM_E_ARG;
+  *runs_out = nullptr;
+  if (n_runs_out_total) *n_runs_out_total = 0;
+  const size_t n = s->meta.size();
+  if (n == 0) return 0;
+  if (n > (size_t)INT32_MAX || n_runs_total > ((size_t)1 << 31)) { h->err = "wfm_left_align_runs: too many problems or runs for one call"; return WFM_E_ARG; }
+  HIPCHK(h, hipSetDevice(h->device));
+  // the problems as the kernels see them; the run ranges are validated here, before anything is launched.  The interior gaps are counted on the
+  // way (the runs are in host memory and are read once for the upload anyway): a problem's slots in the output and in the gap list follow from it
+  std::vector<LaProb> probs(n);
+  uint64_t out_total = 0, gap_total = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const ProbMeta& m = s->meta[i];
+    LaProb& c = probs[i];
+    memset(&c, 0, sizeof(c));
+    c.p_off = m.p_fwd; c.t_off = m.t_fwd;
+    c.plen = m.plen; c.tlen = m.tlen;
+    c.skip = (m.score_only() || res[i].status != 0 || res[i].n_runs == 0) ? 1 : 0;
+    const bool inside = res[i].ops_off <= n_runs_total && (uint64_t)res[i].n_runs <= n_runs_total - res[i].ops_off;
+    if (!c.skip && !inside) {
+      h->err = "problem " + std::to_string(i) + ": its runs leave the run buffer";
+      return WFM_E_ARG;
+    }
+    if (inside) { c.run_off = res[i].ops_off; c.n_runs = res[i].n_runs; }  // (a problem that is not done keeps the runs it names, if it names any)
+    if (!c.skip)
+      for (uint32_t r = 1; r + 1 < c.n_runs; ++r) c.n_gaps += WFM_RUN_OP(runs[c.run_off + r]) >= 2u;
+    c.out_off = out_total; c.gap_off = gap_total;
+    out_total += (uint64_t)c.n_runs + c.n_gaps;
+    gap_total += c.n_gaps;
+  }
+  // one block: [runs | rot | dval] one word per run, [out] one per output slot, [flags] one per problem, [long list] one per gap, the counter;
+  // then the gap records, the problems and the results (8-byte aligned each)
+  const size_t nr = n_runs_total;
+  auto words64 = [](size_t bytes) { return (bytes + 7) / 8; };
+  const size_t w_runs = words64(nr * 4), w_out = words64(out_total * 4), w_flags = words64(n * 4), w_long = words64(gap_total * 4) + 1,
+               w_gaps = words64(gap_total * sizeof(LaGap)), w_probs = words64(n * sizeof(LaProb)), w_stats = words64(n * sizeof(wfm_leftalign_t));
+  if (h->labuf.ensure(3 * w_runs + w_out + w_flags + w_long + w_gaps + w_probs + w_stats + 8)) { h->err = "out of device memory (left-align)"; return WFM_E_NOMEM; }
+  uint64_t* at = h->labuf.p;
+  uint32_t* d_runs = (uint32_t*)at; at += w_runs;
+  uint32_t* d_rot = (uint32_t*)at; at += w_runs;
+  uint32_t* d_dval = (uint32_t*)at; at += w_runs;
+  uint32_t* d_out = (uint32_t*)at; at += w_out;
+  uint32_t* d_flags = (uint32_t*)at; at += w_flags;
+  uint32_t* d_count = (uint32_t*)at; uint32_t* d_long = d_count + 2; at += w_long;
+  LaGap* d_gaps = (LaGap*)at; at += w_gaps;
+  LaProb* d_probs = (LaProb*)at; at += w_probs;
+  wfm_leftalign_t* d_stats = (wfm_leftalign_t*)at;
+  if (nr) HIPCHK(h, hipMemcpyAsync(d_runs, runs, nr * 4, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(d_probs, probs.data(), n * sizeof(LaProb), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemsetAsync(d_count, 0, 8, h->stream));
+  if (gap_total) HIPCHK(h, hipMemsetAsync(d_gaps, 0xff, gap_total * sizeof(LaGap), h->stream));  // (a record nobody writes names no problem)
+  const int dbg = env_debug();
+  const uint32_t lane_max = (uint32_t)std::max(8, env_num("WFM_LA_LANE_MAX", 256));
+  if (dbg) HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+  launch_left_align(s->d_seq, d_runs, d_probs, (int)n, d_rot, d_dval, d_gaps, gap_total, d_flags, d_long, d_count, d_out, d_stats, lane_max, h->stream);
+  HIPCHK(h, hipGetLastError());
+  if (dbg) HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+  std::vector<uint32_t> slots(out_total);
+  uint32_t n_long = 0;
+  if (out_total) HIPCHK(h, hipMemcpyAsync(slots.data(), d_out, out_total * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(out, d_stats, n * sizeof(wfm_leftalign_t), hipMemcpyDeviceToHost, h->stream));
+  if (dbg) HIPCHK(h, hipMemcpyAsync(&n_long, d_count, 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  // the problems' runs end to end (a problem used at most n_runs + n_gaps of its slots)
+  uint64_t total = 0;
+  for (size_t i = 0; i < n; ++i) {
+    if (out[i].runs_out > probs[i].n_runs + probs[i].n_gaps) { h->err = "wfm_left_align_runs: a problem's runs outgrew their slots"; return WFM_E_HIP; }
+    total += out[i].runs_out;
+  }
+  uint32_t* packed = (uint32_t*)malloc(std::max<size_t>(total, 1) * 4);
+  if (!packed) { h->err = "out of host memory (left-align)"; return WFM_E_NOMEM; }
+  uint64_t pos = 0;
+  int spans = 0;
+  uint64_t moved = 0, bases = 0;
+  for (size_t i = 0; i < n; ++i) {
+    if (out[i].runs_out) memcpy(packed + pos, slots.data() + probs[i].out_off, (size_t)out[i].runs_out * 4);
+    res[i].ops_off = pos; res[i].n_runs = out[i].runs_out;
+    pos += out[i].runs_out;
+    spans += (out[i].flags & WFM_LA_SPANS) != 0;
+    moved += out[i].moved; bases += out[i].bases_moved;
+  }
+  *runs_out = packed;
+  if (n_runs_out_total) *n_runs_out_total = (size_t)total;
+  if (dbg) {
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess)
+      fprintf(stderr, "[wfm] left-align: %zu problems, %zu runs, %llu gaps (%u to the wave kernel), %llu moved by %llu bases in %.3f ms\n", n, nr,
+              (unsigned long long)gap_total, n_long, (unsigned long long)moved, (unsigned long long)bases, ms);
+    else (void)hipGetLastError();
+  }
+  return spans;
 }
 
 // ---- every score proved optimal by a banded DP (wfmash_hip.h; the band: wfa_optband.h; the kernel: wfa_optcheck.hip) ----

@@ -24,6 +24,12 @@
 //                                              not change; a failure is one line on stderr and exit status 3; N caps the DP cells of one
 //                                              problem (problems beyond it are counted as skipped); allowed with --verify, -a and
 //                                              --resident-seqs, refused with -m.  Costs far more than the alignment on near-identical records
+//   --left-align                               every interior gap of the records' final CIGARs is moved to its leftmost placement on the
+//                                              device before the record is written (wfm_left_align_runs: an indel in a homopolymer or a
+//                                              tandem repeat lands where minimap2 and VCF normalisation put it); only cg:Z: changes in a
+//                                              PAF line, only CIGAR and MD in a SAM record; allowed with -a, -d, --verify (which then checks
+//                                              the normalised lines), --verify-optimal, --resident-seqs, --gpus, -i and -K, refused with -m;
+//                                              off by default
 //   --verify-paf FILE target.fa [query.fa]     the same check on an existing aligned PAF (this build's or the reference's): no mapping,
 //                                              no alignment; exit status 3 if a line fails
 //   --ani-matrix FILE [--ani-only]             the group-by-group ANI table the identity estimate (-p aniN) is made from, as TSV: per
@@ -113,6 +119,7 @@ static void usage() {
           "            --verify check every PAF line written against its bases on the GPU (exit status 3 if one fails; not with -a)\n"
           "            --verify-optimal prove every alignment score optimal by a banded DP on the GPU (slow; exit status 3 if one is not; not with -m)\n"
           "            --verify-optimal-cells N skip problems whose band holds more than N DP cells [no cap]\n"
+          "            --left-align move every interior gap of the final CIGARs to its leftmost placement on the GPU (only cg:Z: / CIGAR and MD change; not with -m)\n"
           "            --verify-paf FILE check an existing aligned PAF against target.fa [query.fa] and stop (exit status 3 if a line fails)\n"
           "  other     --out FILE [stdout]   --device INT [0]   --gpus N|all [1] GPUs of this node, starting at --device\n"
           "            -B DIR directory of the hand-off file [cwd]   -Z keep the hand-off file   --quiet (no effect)\n");
@@ -125,7 +132,7 @@ int main(int argc, char** argv) {
   wfmh_map_params_t mp;
   wfmh_map_default_params(&mp);
   std::string mapping_in, out = "/dev/stdout", target, query, seeds_in, scaffold_out, tmp_base, verify_in, ani_matrix_out;
-  bool verify = false, verify_optimal = false, ani_only = false;
+  bool verify = false, verify_optimal = false, ani_only = false, left_align = false;
   uint64_t verify_optimal_cells = 0;
   bool approx_only = false, target_padding_given = false, query_padding_given = false, keep_temp = false;
   int device = 0, gpus = 1;
@@ -259,6 +266,7 @@ int main(int argc, char** argv) {
     else if (a == "--resident-seqs") ap.resident_sequences = 1;
     else if (a == "--verify") verify = true;
     else if (a == "--verify-optimal") verify_optimal = true;
+    else if (a == "--left-align") left_align = true;
     else if (a == "--verify-optimal-cells") verify_optimal_cells = std::strtoull(next("--verify-optimal-cells").c_str(), nullptr, 10);
     else if (a == "--verify-paf") verify_in = next("--verify-paf");
     else if (a == "-h" || a == "--help") { usage(); return 0; }
@@ -269,6 +277,7 @@ int main(int argc, char** argv) {
   if (target.empty()) { fprintf(stderr, "[wfmash] ERROR: need a target FASTA\n"); usage(); return 1; }
   if (verify && ap.sam_format) { fprintf(stderr, "[wfmash] ERROR: --verify reads the =/X CIGAR of PAF lines: it cannot be combined with -a (SAM)\n"); return 1; }
   if (verify && approx_only) { fprintf(stderr, "[wfmash] ERROR: --verify checks alignments: it cannot be combined with -m\n"); return 1; }
+  if (left_align && approx_only) { fprintf(stderr, "[wfmash] ERROR: --left-align normalises alignments: it cannot be combined with -m\n"); return 1; }
   if (verify_optimal && approx_only) { fprintf(stderr, "[wfmash] ERROR: --verify-optimal checks alignment scores: it cannot be combined with -m\n"); return 1; }
   if (verify_optimal_cells && !verify_optimal) { fprintf(stderr, "[wfmash] ERROR: --verify-optimal-cells needs --verify-optimal\n"); return 1; }
   if (ani_only && ani_matrix_out.empty()) { fprintf(stderr, "[wfmash] ERROR: --ani-only needs --ani-matrix FILE\n"); return 1; }
@@ -398,11 +407,18 @@ int main(int argc, char** argv) {
     wfmh_align_summary_t s;
     if (verify) wfmh_set_verify(1);
     if (verify_optimal) wfmh_set_verify_optimal(1, verify_optimal_cells);
+    if (left_align) wfmh_set_left_align(1);
     rc = wfmh_align_paf_multi(hs.data(), (int)hs.size(), target.c_str(), q, mapping.c_str(), out.c_str(), &ap, &s);
     if (rc == WFM_OK)
       fprintf(stderr, "[wfmash::align] %llu records, %llu aligned bp, %.1f ms GPU kernels, %.1f ms total => %.3g aligned bp/s\n",
               (unsigned long long)s.records, (unsigned long long)s.aligned_bp, s.ms_gpu, s.ms_total, s.aligned_bp / (s.ms_total * 1e-3));
     else fprintf(stderr, "[wfmash::align] ERROR: %s\n", wfm_last_error(h));
+    if (left_align && rc == WFM_OK) {
+      uint64_t lc[4] = {0, 0, 0, 0};
+      wfmh_left_align_counts(lc);
+      fprintf(stderr, "[wfmash::left-align] %llu records, %llu interior gaps, %llu moved, %llu records left alone\n", (unsigned long long)lc[0],
+              (unsigned long long)lc[1], (unsigned long long)lc[2], (unsigned long long)lc[3]);
+    }
     if (verify && rc == WFM_OK) {  // everything has been written by now
       uint64_t vc[4] = {0, 0, 0, 0};
       wfmh_verify_counts(vc);

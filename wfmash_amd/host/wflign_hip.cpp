@@ -49,6 +49,10 @@ std::atomic<bool> g_optimal{false};
 std::atomic<uint64_t> g_optimal_cells{0};
 std::atomic<uint64_t> g_optimal_counts[4];
 
+// --left-align: the process-wide switch and {records handed to the device, their interior gaps, gaps moved, records left alone} since it was set
+std::atomic<bool> g_left_align{false};
+std::atomic<uint64_t> g_left_align_counts[4];
+
 // The problems of one device call, always written by reference (a side without a store id carries its host pointer); without a
 // store they go to the device as plain wfm_problem_t, as they always have.
 struct GpuBatch {
@@ -336,8 +340,8 @@ int patch_late_tails(BiwfaBatch& b) {
   return 0;
 }
 
-// ---- swizzle + record (wflign.cpp:423-454) ----
-void swizzle_and_write(BiwfaBatch& b, size_t ri) {
+// ---- swizzle (wflign.cpp:423-433) ----
+void swizzle(BiwfaBatch& b, size_t ri) {
   BiwfaRecord& r = b.recs[ri];
   if (!r.ok) return;
   if (!r.query || !r.target) {
@@ -351,6 +355,99 @@ void swizzle_and_write(BiwfaBatch& b, size_t ri) {
     try_swap_start_pattern(r.ops, r.query, qn, r.target, tn);
     try_swap_end_pattern(r.ops, r.query, qn, r.target, tn);
   }
+}
+
+// ---- --left-align: the interior gaps of every record's final ops moved to their leftmost placement, ONE device call per batch
+// (wfm_left_align_runs).  What goes to the device is what the writers spell: both of them begin by stripping the leading and trailing I
+// and D runs and shifting the start coordinates (trim_and_filter), so a record's problem is the runs ops[b, e) that remain against the
+// sub-windows they cover.  The line's first and last runs are then the problem's first and last, which the rule never touches -- no
+// coordinate moves, and the CIGAR of the line is the rule applied to the line.  Records go by reference where the batch has a store.
+// The ops of an ok record always span its windows (an end-to-end alignment does, a patch replaces eroded runs by an alignment of exactly
+// their bases, erosion and the swaps keep both totals), so a record left alone is a defect; it is written as it is and counted. ----
+int left_align_records(BiwfaBatch& b) {
+  const auto t0 = Clock::now();
+  struct Part { size_t rec, b, e; };
+  std::vector<Part> parts;
+  std::vector<wfm_problem_ref_t> probs;
+  std::vector<wfm_result_t> res;
+  std::vector<uint32_t> runs;
+  for (size_t i = 0; i < b.recs.size(); ++i) {
+    const BiwfaRecord& r = b.recs[i];
+    if (!r.ok) continue;
+    const CigarOps& ops = r.ops;
+    size_t ob = 0, oe = ops.size();
+    uint64_t ta = 0, qa = 0;
+    while (ob < oe && (ops[ob].second == 'I' || ops[ob].second == 'D')) { (ops[ob].second == 'I' ? qa : ta) += (uint64_t)ops[ob].first; ++ob; }
+    while (oe > ob && (ops[oe - 1].second == 'I' || ops[oe - 1].second == 'D')) --oe;
+    if (oe - ob < 3) continue;  // no interior run
+    const CigarStats cs = cigar_stats(ops, ob, oe);
+    wfm_problem_ref_t p = window_problem(r, ta, cs.ref_len, qa, cs.q_len);
+    p.mode = WFM_MODE_END2END_UNI;  // (no reversed copies are made for it)
+    wfm_result_t q{};
+    q.status = 0; q.score = -1;
+    q.ops_off = runs.size(); q.n_runs = (uint32_t)(oe - ob);
+    bool known = true;
+    for (size_t k = ob; k < oe; ++k) {
+      const char c = ops[k].second;
+      const uint32_t op = c == '=' ? 0u : c == 'X' ? 1u : c == 'I' ? 2u : c == 'D' ? 3u : 4u;
+      if (op > 3u || ops[k].first <= 0 || (uint32_t)ops[k].first >= (1u << 30)) { known = false; break; }
+      runs.push_back(((uint32_t)ops[k].first << 2) | op);
+    }
+    if (!known) { runs.resize((size_t)q.ops_off); g_left_align_counts[0] += 1; g_left_align_counts[3] += 1; continue; }
+    q.ops_len = (uint32_t)std::min<uint64_t>(cs.ref_len + cs.q_len, 0xffffffffu);
+    parts.push_back(Part{i, ob, oe});
+    probs.push_back(p);
+    res.push_back(q);
+  }
+  if (parts.empty()) return 0;
+  const size_t n = parts.size();
+  std::vector<wfm_leftalign_t> la(n);
+  uint32_t* out = nullptr;
+  int rc;
+  {
+    std::lock_guard<std::mutex> lk(handle_lock(b.h));
+    wfm_seqset_t* S = nullptr;
+    if (b.store) rc = wfm_upload_sequence_refs(b.h, b.store, probs.data(), n, &S);
+    else {
+      std::vector<wfm_problem_t> plain(n);
+      for (size_t i = 0; i < n; ++i) plain[i] = wfm_problem_t{probs[i].pattern, probs[i].plen, probs[i].text, probs[i].tlen, probs[i].mode, 0, 0, 0, 0, 0, 0};
+      rc = wfm_upload_sequences(b.h, plain.data(), n, &S);
+    }
+    if (rc == WFM_OK) {
+      rc = wfm_left_align_runs(b.h, S, res.data(), runs.data(), runs.size(), &out, nullptr, la.data());
+      wfm_free_sequences(b.h, S);
+    }
+    if (rc < 0 && b.stats) b.stats->error = wfm_last_error(b.h);
+  }
+  if (rc < 0) { wfm_free_runs(out); return rc; }
+  std::atomic<uint64_t> gaps{0}, moved{0}, alone{0};
+  for_each_record(n, b.fmt.threads, [&](size_t j) {
+    const Part& pt = parts[j];
+    const wfm_leftalign_t& l = la[j];
+    if (l.flags) { alone.fetch_add(1); return; }
+    gaps.fetch_add(l.gaps);
+    if (!l.moved) return;
+    moved.fetch_add(l.moved);
+    CigarOps& ops = b.recs[pt.rec].ops;
+    CigarOps mid;
+    ops_from_runs(out + res[j].ops_off, res[j].n_runs, mid);
+    CigarOps all(ops.begin(), ops.begin() + (long)pt.b);
+    all.insert(all.end(), mid.begin(), mid.end());
+    all.insert(all.end(), ops.begin() + (long)pt.e, ops.end());
+    ops.swap(all);
+  });
+  wfm_free_runs(out);
+  g_left_align_counts[0] += n; g_left_align_counts[1] += gaps.load(); g_left_align_counts[2] += moved.load(); g_left_align_counts[3] += alone.load();
+  if (getenv("WFM_DEBUG"))
+    fprintf(stderr, "[wflign] left-align: %zu records, %zu runs, %llu gaps, %llu moved, %llu left alone, %.1f ms (upload, device call, splice)\n", n, runs.size(),
+            (unsigned long long)gaps.load(), (unsigned long long)moved.load(), (unsigned long long)alone.load(), ms_between(t0, Clock::now()));
+  return 0;
+}
+
+// ---- record (wflign.cpp:434-454) ----
+void write_record(BiwfaBatch& b, size_t ri) {
+  BiwfaRecord& r = b.recs[ri];
+  if (!r.ok) return;
   if (b.fmt.paf_format_else_sam)
     write_alignment_paf(r.paf, r.ops, r.query_name, r.query_total_length, r.query_offset, r.query_length, r.query_is_rev,
                         r.target_name, r.target_total_length, r.target_offset, b.pp, r.mashmap_estimated_identity, r.chain_id,
@@ -383,7 +480,13 @@ int do_biwfa_alignment_batch(wfm_handle_t* h, std::vector<BiwfaRecord>& recs, co
     if (stats) { stats->head_patches += b.n_head.load(); stats->tail_patches += b.n_tail.load(); }
   }
   const auto ts2 = Clock::now();
-  for_each_record(n, fmt.threads, [&](size_t ri) { swizzle_and_write(b, ri); });
+  if (g_left_align.load()) {  // the two halves with the device call between them
+    for_each_record(n, fmt.threads, [&](size_t ri) { swizzle(b, ri); });
+    if ((rc = left_align_records(b)) < 0) return rc;
+    for_each_record(n, fmt.threads, [&](size_t ri) { write_record(b, ri); });
+  } else {
+    for_each_record(n, fmt.threads, [&](size_t ri) { swizzle(b, ri); write_record(b, ri); });
+  }
   if (dbg)
     fprintf(stderr, "[wflign] %zu records: main alignment + runs + scans %.1f ms (incl. waiting for the device), patches %.1f ms (%zu tails scanned after their heads), swizzle + records %.1f ms\n",
             n, ms_between(ts0, ts1), ms_between(ts1, ts2), b.later, ms_between(ts2, Clock::now()));
@@ -398,6 +501,17 @@ void wfmh_set_verify_optimal(int on, uint64_t max_cells) {
   wflign::g_optimal_cells.store(on ? max_cells : 0);
   for (auto& a : wflign::g_optimal_counts) a.store(0);
   wflign::g_optimal.store(on != 0);
+}
+
+void wfmh_set_left_align(int on) {
+  for (auto& a : wflign::g_left_align_counts) a.store(0);
+  wflign::g_left_align.store(on != 0);
+}
+
+int wfmh_left_align_counts(uint64_t out[4]) {
+  if (!out) return WFM_E_ARG;
+  for (int q = 0; q < 4; ++q) out[q] = wflign::g_left_align_counts[q].load();
+  return WFM_OK;
 }
 
 int wfmh_verify_optimal_counts(uint64_t out[4]) {

@@ -10,7 +10,9 @@
 //   patch_ends         ends-free head and tail patches, one call for both
 //                                                            (wflign.cpp:241-320, 323-418)
 //   patch_late_tails   the tails whose scan has to see the patched head  (wflign.cpp:323-418)
-//   swizzle_and_write  swizzle + PAF / SAM record             (wflign.cpp:423-454)
+//   swizzle            the two end swaps                       (wflign.cpp:423-433)
+//   left_align_records --left-align only: every interior gap to its leftmost placement, one wfm_left_align_runs call
+//   write_record       PAF / SAM record                        (wflign.cpp:434-454)
 // and CIGARs are runs (count, op) from the device to the record's text: nothing is expanded to one byte per base.
 #pragma once
 
