@@ -329,6 +329,41 @@ int wfm_left_align_runs(wfm_handle_t* h, const wfm_seqset_t* s, wfm_result_t* re
                         const uint32_t* runs, size_t n_runs_total, uint32_t** runs_out, size_t* n_runs_out_total,
                         wfm_leftalign_t* out);   /* runs_out: wfm_free_runs */
 
+/* ---- minimap2's cs difference string of every problem's runs ----
+ * A CIGAR with = and X says where the bases differ; the cs string says which they are, so that substitutions, inserted and deleted bases
+ * can be read off a line without either FASTA.  This call spells it on the device (wfmash_amd/csrc/wfa_cs.hip; forward BYTE copies only,
+ * never the 2-bit mirror; nothing is shared with the aligners).  s, res and runs as for wfm_check_runs: res[i].ops_off may come in any order,
+ * with unused words between the problems.
+ *
+ * The grammar.  Pattern = target = reference side P; text = query side T as aligned (already reverse-complemented for a '-' record).  The
+ * problem's runs are spelled from left to right, p and t being the indices the run begins at:
+ *   run                        WFM_CS_SHORT                              WFM_CS_LONG
+ *   M of L bases               ':' + L in decimal                        '=' + the L pattern bytes as they are
+ *   X of L bases               L times '*' + lc(P[p+j]) + lc(T[t+j])     the same
+ *   I of L bases (text only)   '+' + lc of the L text bytes              the same
+ *   D of L bases (pattern)     '-' + lc of the L pattern bytes           the same
+ * lc maps 'A'..'Z' to 'a'..'z' and leaves every other byte alone (N becomes n).  The string is spelled from the runs and never from a
+ * comparison: an X over two equal bytes is spelled "*aa", and an M over different bytes takes its bytes from the pattern in the long form.
+ * Whether the runs fit the bases is wfm_check_runs' business.
+ *
+ * *out receives the strings of all problems end to end in problem order, not NUL-terminated, *out_bytes their total; the buffer is host
+ * memory owned by the caller (release with wfm_free_cs).  per receives one wfm_cs_t per problem: off / len locate its string in *out, n_runs
+ * is the number of runs it was spelled from.  A problem flagged WFM_CS_NOT_DONE or WFM_CS_SPANS has len 0 and nothing of it is spelled.
+ * Returns the number of problems flagged WFM_CS_SPANS, or a WFM_E_* code; a run range that leaves runs[0 .. n_runs_total) and a form other
+ * than the two are WFM_E_ARG with a message (*out is NULL, the handle stays usable).  No problems: WFM_OK, *out = NULL, *out_bytes = 0.
+ * One workgroup writes WFM_CS_SLICE bytes of the output whatever runs or problems they belong to, and the problems are worked in chunks
+ * whose device output block holds at most WFM_CS_OUT_MB MiB (environment, read per call, 256; a single problem may exceed it alone), each
+ * copied to its place in *out: device memory stays bounded whatever a long-form batch spells. */
+#define WFM_CS_SHORT 0
+#define WFM_CS_LONG  1
+#define WFM_CS_NOT_DONE 1u   /* status != 0, score-only, no runs: len = 0 */
+#define WFM_CS_SPANS    2u   /* a run of length 0, two neighbours with one op, totals other than plen x tlen: len = 0, nothing spelled */
+typedef struct { uint32_t flags, n_runs; uint64_t off, len; } wfm_cs_t;   /* 24 bytes; off/len locate the string in *out */
+#define WFM_CS_SLICE 16384   /* output bytes one workgroup writes */
+int  wfm_cs_strings(wfm_handle_t* h, const wfm_seqset_t* s, const wfm_result_t* res, const uint32_t* runs, size_t n_runs_total,
+                    int form, char** out, size_t* out_bytes, wfm_cs_t* per);
+void wfm_free_cs(char* p);
+
 /* ---- every score proved optimal by a banded DP ----
  * What wfm_check_runs leaves out.  For every problem of the seqset s whose result claims a score S = res[i].score, a classical
  * minimising gap-affine-2-piece DP over cells (i = pattern index, j = text index) is run on the device, restricted to a band of

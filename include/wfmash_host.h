@@ -126,6 +126,18 @@ int  wfmh_verify_optimal_counts(uint64_t out[4]);
 void wfmh_set_left_align(int on);
 int  wfmh_left_align_counts(uint64_t out[4]);
 
+/* ---- minimap2's cs:Z: tag on every record written (wfm_cs_strings, wfmash_hip.h) ----
+ * wfmh_set_cs(form), form 0 off, 1 short, 2 long: from now on every batch of wfmh_align_paf[_multi] runs ONE more device call between the
+ * swizzle (and the left-align call, where that switch is on) and the record writers: the cs string of the runs each record's line will
+ * spell against the sub-windows they cover, by reference where the run keeps its sequences on the device -- the host never needs a
+ * record's bases for it.  With wfmh_set_left_align as well the windows are uploaded once for both calls and the string is that of the
+ * normalised runs.  "\tcs:Z:" + the string becomes the last field of the PAF line or the SAM record; nothing else of the line changes.
+ * A record whose runs do not span its windows is written without the field and counted (the pipeline produces none).  Every call
+ * zeroes the counts.  wfmh_cs_counts: out = {records written with a string, bytes of those strings, records written without one, 0}
+ * since then.  Off by default; with the switch off nothing new is called and the output bytes are what they always were. */
+void wfmh_set_cs(int form);
+int  wfmh_cs_counts(uint64_t out[4]);
+
 /* Test hooks: the pure host-side CIGAR functions (erode / merge / swizzle / PAF writer /
  * parseMashmapRow) behind one string interface so the CPU test-suite can check them
  * without a GPU.  fn in {erode, merge, compress, swap_start, swap_end, head_erosion,

@@ -44,7 +44,7 @@ EXPORTS = [
     "wfm_sketch_part", "wfm_minmer_part_info", "wfm_minmer_part_download", "wfm_minmer_part_free", "wfm_index_build_parts",
     "wfm_seqstore_create", "wfm_seqstore_free", "wfm_seqstore_add", "wfm_seqstore_info",
     "wfm_upload_sequence_refs", "wfm_align_refs_rle", "wfm_download_sequences",
-    "wfm_check_runs", "wfm_check_optimal", "wfm_left_align_runs",
+    "wfm_check_runs", "wfm_check_optimal", "wfm_left_align_runs", "wfm_cs_strings", "wfm_free_cs",
     "wfm_sketch_intersections",
 ]
 ISECT_LDS_MAX = 4096  # WFM_ISECT_LDS_MAX: the longest column sketch wfm_sketch_intersections searches in LDS
@@ -54,6 +54,10 @@ CK_NAMES = ("NOT_CHECKED", "BAD_RUN", "SPANS", "M_DIFFERS", "X_EQUAL", "SCORE", 
 CHECK_SLICE = 16384  # WFM_CHECK_SLICE: ops one compare task covers
 # wfm_left_align_runs (include/wfmash_hip.h): why a problem's runs were left as they came
 WFM_LA_NOT_DONE, WFM_LA_SPANS = 1, 2
+# wfm_cs_strings (include/wfmash_hip.h): the two forms, why a problem has no string, and the output bytes one workgroup writes
+WFM_CS_SHORT, WFM_CS_LONG = 0, 1
+WFM_CS_NOT_DONE, WFM_CS_SPANS = 1, 2
+WFM_CS_SLICE = 16384
 # wfm_check_optimal (include/wfmash_hip.h): what a problem's score was flagged for, and the band widths at which the kernel changes form
 WFM_OPT_NOT_CHECKED, WFM_OPT_SKIPPED, WFM_OPT_CHEAPER, WFM_OPT_UNREACHED = 1, 2, 4, 8
 OPT_NAMES = ("NOT_CHECKED", "SKIPPED", "CHEAPER", "UNREACHED")
@@ -107,6 +111,11 @@ class LeftAlign(C.Structure):
     """wfm_leftalign_t: what wfm_left_align_runs did to one problem's runs."""
     _fields_ = [("flags", C.c_uint32), ("gaps", C.c_uint32), ("moved", C.c_uint32), ("runs_out", C.c_uint32),
                 ("bases_moved", C.c_uint64), ("longest", C.c_uint32), ("pad_", C.c_uint32)]
+
+
+class Cs(C.Structure):
+    """wfm_cs_t: where wfm_cs_strings put one problem's cs string, and the runs it was spelled from."""
+    _fields_ = [("flags", C.c_uint32), ("n_runs", C.c_uint32), ("off", C.c_uint64), ("len", C.c_uint64)]
 
 
 class OptCheck(C.Structure):
@@ -700,6 +709,36 @@ class Handle:
             self._L.wfm_free_runs(new)
         return arr, a, [out[i] for i in range(n)]
 
+    def cs_strings(self, seqset, results, runs, form):
+        """wfm_cs_strings: minimap2's cs difference string of every problem's runs, spelled on the device.  results and runs as for
+        check_runs; form: WFM_CS_SHORT or WFM_CS_LONG.  Returns (the strings as bytes, one per problem -- b"" for a flagged one --,
+        [Cs], one per problem)."""
+        n = seqset.n
+        arr = (Result * max(n, 1))()
+        if isinstance(results, C.Array):
+            C.memmove(arr, results, C.sizeof(Result) * n)
+        else:
+            assert len(results) == n, (len(results), n)
+            for i, (status, score, ops_off, ops_len, n_runs) in enumerate(results):
+                arr[i].status, arr[i].score, arr[i].ops_off, arr[i].ops_len, arr[i].n_runs = status, score, ops_off, ops_len, n_runs
+        runs = np.ascontiguousarray(runs, dtype=np.uint32)
+        per = (Cs * max(n, 1))()
+        text = C.c_void_p()
+        total = C.c_size_t(0)
+        f = self._L.wfm_cs_strings
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p]
+        self._L.wfm_free_cs.restype = None
+        self._L.wfm_free_cs.argtypes = [C.c_void_p]
+        rc = f(self._p, seqset._p, arr, runs.ctypes.data if len(runs) else None, len(runs), int(form), C.byref(text), C.byref(total), per)
+        if rc < 0:
+            raise WfmError(f"wfm_cs_strings failed ({rc}): {self.last_error()}")
+        try:
+            blob = C.string_at(text, total.value) if total.value else b""
+        finally:
+            self._L.wfm_free_cs(text)
+        return [blob[per[i].off:per[i].off + per[i].len] for i in range(n)], [per[i] for i in range(n)]
+
     def check_optimal(self, seqset, results, pen=None, max_cells=0):
         """wfm_check_optimal: every score held against a banded DP on the device.  results: a ctypes array of Result (seqset.results after
         an align call), or a list of (status, score) or plain scores, one per problem of the seqset.  Returns the list of OptCheck records
@@ -1062,7 +1101,7 @@ HOST_EXPORTS = ["wfmh_test_packed_lce", "wfmh_test_is_acgt", "wfmh_align_default
                 "wfmh_release_sequences", "wfmh_test_fasta_shared", "wfmh_seed_paf", "wfmh_test_deal", "wfmh_test_subwindow",
                 "wfmh_test_rows", "wfmh_test_tile_plan", "wfmh_test_p2_plan", "wfmh_test_base_plan", "wfmh_test_map_plan", "wfmh_test_filter_ordered",
                 "wfmh_test_reuse_plan", "wfmh_test_tile_plan_dirs", "wfmh_test_tile_interior", "wfmh_test_tile_lean_waves", "wfmh_set_verify", "wfmh_verify_counts", "wfmh_verify_paf", "wfmh_test_verify_parse",
-                "wfmh_set_verify_optimal", "wfmh_verify_optimal_counts", "wfmh_test_opt_band", "wfmh_set_left_align", "wfmh_left_align_counts",
+                "wfmh_set_verify_optimal", "wfmh_verify_optimal_counts", "wfmh_test_opt_band", "wfmh_set_left_align", "wfmh_left_align_counts", "wfmh_set_cs", "wfmh_cs_counts",
                 "wfmh_ani_matrix", "wfmh_ani_matrix_rows", "wfmh_free_ani_rows", "wfmh_set_ani_matrix", "wfmh_test_ani_tsv"]
 
 
@@ -1432,6 +1471,28 @@ def left_align_counts():
     rc = f(out)
     if rc != 0:
         raise WfmError(f"wfmh_left_align_counts failed ({rc})")
+    return tuple(int(v) for v in out)
+
+
+def set_cs(form: int) -> None:
+    """wfmh_set_cs: every later align_paf call of the process appends minimap2's cs:Z: string, spelled on the device, to every record it
+    writes (0: off, 1: short, 2: long); zeroes the counts."""
+    f = _host().wfmh_set_cs
+    f.restype = None
+    f.argtypes = [C.c_int]
+    f(int(form))
+
+
+def cs_counts():
+    """wfmh_cs_counts: (records written with a string, bytes of those strings, records written without one, 0) since wfmh_set_cs was
+    last called."""
+    f = _host().wfmh_cs_counts
+    f.restype = C.c_int
+    f.argtypes = [C.POINTER(C.c_uint64)]
+    out = (C.c_uint64 * 4)()
+    rc = f(out)
+    if rc != 0:
+        raise WfmError(f"wfmh_cs_counts failed ({rc})")
     return tuple(int(v) for v in out)
 
 

@@ -257,6 +257,22 @@ struct LaGap { int64_t s_off; uint32_t g, len, prob, run; };  // S = the sequenc
 void launch_left_align(const uint8_t* seq, const uint32_t* runs, const LaProb* probs, int nprob, uint32_t* rot, uint32_t* dval, LaGap* gaps,
                        uint64_t ngaps, uint32_t* flags, uint32_t* long_list, uint32_t* long_count, uint32_t* out, void* stats, uint32_t lane_max,
                        hipStream_t st);
+// wfm_cs_strings (wfa_cs.hip): a problem's forward byte copies, its runs and its slots in the table of run records (one uint4 per run:
+// pattern index, text index, offset of the run's bytes in the problem's string, the run)
+struct CsProb {
+  int64_t p_off, t_off;
+  uint64_t run_off, rec_off;
+  uint32_t n_runs;
+  int32_t plen, tlen;
+  int32_t skip;                        // nonzero: WFM_CS_NOT_DONE (score-only, status != 0, no runs)
+};
+// recs: one uint4 per run of the problems that are not skipped; totals / flags: one per problem (a flagged problem's total is 0)
+void launch_cs_index(const uint32_t* runs, const CsProb* probs, int nprob, int form, void* recs, unsigned long long* totals, uint32_t* flags,
+                     hipStream_t st);
+// the problems [ka, kb), whose strings are the chunk_bytes bytes behind goff[ka] (goff: the n + 1 offsets of the call's strings), into out,
+// which holds chunk_bytes rounded up to a multiple of WFM_CS_SLICE
+void launch_cs_write(const uint8_t* seq, const CsProb* probs, const void* recs, const unsigned long long* goff, uint32_t ka, uint32_t kb,
+                     unsigned long long chunk_bytes, int form, uint8_t* out, hipStream_t st);
 // wfm_check_optimal (wfa_optcheck.hip): a problem's forward byte copies, its ends-free allowances (clamped; 0 for the other modes),
 // its band of diagonals (wfa_optband.h) and, for the memory form, where its three row arrays begin in `rows` (32-bit elements)
 struct OptProb {

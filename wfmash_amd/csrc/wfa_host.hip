@@ -282,6 +282,9 @@ struct wfm_handle {
   DevBuf<uint64_t> checkbuf;         // wfm_check_runs: everything the call has on the device, carved out of one block
   DevBuf<uint64_t> optbuf;           // wfm_check_optimal: the problems and their results
   DevBuf<uint64_t> labuf;            // wfm_left_align_runs: everything the call has on the device, carved out of one block
+  DevBuf<uint64_t> csbuf;            // wfm_cs_strings: the runs, their records, the problems and their offsets, carved out of one block
+  DevBuf<uint64_t> csout;            // ... and the output block of one chunk of problems
+  uint8_t* cspin[2] = {nullptr, nullptr};  // ... whose bytes reach the caller's buffer through these two pinned pieces (CS_PIN_PIECE each)
   DevBuf<int32_t> optrows;           // ... and the rows of the bands too wide for registers
   DevBuf<unsigned long long> total;
   void* attachment = nullptr;  // owned by another translation unit (map_kernels.hip: the pinned staging ring)
@@ -2215,10 +2218,12 @@ void wfm_destroy(wfm_handle_t* h) {
   h->tilejobs.release(); h->tiletasks.release(); h->tilemak.release();
   h->revjobs.release(); h->bndjobs.release(); h->bndres.release();
   if (h->stage) { (void)hipHostFree(h->stage); h->stage = nullptr; h->stage_cap = 0; }
+  for (int k = 0; k < 2; ++k)
+    if (h->cspin[k]) { (void)hipHostFree(h->cspin[k]); h->cspin[k] = nullptr; }
   h->p2rows.release(); h->p2max.release(); h->p2bmax.release(); h->p2pbmax.release(); h->p2jobs.release(); h->widenjobs.release(); h->keeptasks.release(); h->restoretasks.release(); h->restoreres.release();
   h->bpjobs.release(); h->bpres.release(); h->bsjobs.release(); h->bsres.release();
   h->b2tjobs.release(); h->b2ttasks.release(); h->b2tkeys.release(); h->b2toffs.release(); h->b2tactive.release();
-  h->i64a.release(); h->i64b.release(); h->i64c.release(); h->i32a.release(); h->seqflags.release(); h->flagjobs.release(); h->gathertasks.release(); h->checkbuf.release(); h->optbuf.release(); h->labuf.release(); h->optrows.release(); h->total.release();
+  h->i64a.release(); h->i64b.release(); h->i64c.release(); h->i32a.release(); h->seqflags.release(); h->flagjobs.release(); h->gathertasks.release(); h->checkbuf.release(); h->optbuf.release(); h->labuf.release(); h->csbuf.release(); h->csout.release(); h->optrows.release(); h->total.release();
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->ev2) (void)hipEventDestroy(h->ev2);
@@ -2834,6 +2839,136 @@ int wfm_left_align_runs(wfm_handle_t* h, const wfm_seqset_t* s, wfm_result_t* re
   }
   return spans;
 }
+
+// ---- the cs difference string of every problem's runs (wfmash_hip.h; the kernels: wfa_cs.hip) ----
+int wfm_cs_strings(wfm_handle_t* h, const wfm_seqset_t* s, const wfm_result_t* res, const uint32_t* runs, size_t n_runs_total, int form, char** out,
+                   size_t* out_bytes, wfm_cs_t* per) {
+  if (!h || !s || !out || !out_bytes || (n_runs_total && !runs)) return WFM_E_ARG;
+  *out = nullptr;
+  *out_bytes = 0;
+  const auto t_call = std::chrono::steady_clock::now();
+  if (form != WFM_CS_SHORT && form != WFM_CS_LONG) { h->err = "wfm_cs_strings: form " + std::to_string(form) + " is neither WFM_CS_SHORT nor WFM_CS_LONG"; return WFM_E_ARG; }
+  const size_t n = s->meta.size();
+  if (n == 0) return WFM_OK;
+  if (!res || !per) return WFM_E_ARG;
+  if (n > (size_t)INT32_MAX || n_runs_total > ((size_t)1 << 31)) { h->err = "wfm_cs_strings: too many problems or runs for one call"; return WFM_E_ARG; }
+  HIPCHK(h, hipSetDevice(h->device));
+  // the problems as the kernels see them; the run ranges are validated here, before anything is launched.  The run records lie in problem
+  // order whatever order the runs come in
+  std::vector<CsProb> probs(n);
+  uint64_t rec_total = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const ProbMeta& m = s->meta[i];
+    CsProb& c = probs[i];
+    memset(&c, 0, sizeof(c));
+    c.p_off = m.p_fwd; c.t_off = m.t_fwd;
+    c.plen = m.plen; c.tlen = m.tlen;
+    c.skip = (m.score_only() || res[i].status != 0 || res[i].n_runs == 0) ? 1 : 0;
+    if (c.skip) continue;
+    if (!(res[i].ops_off <= n_runs_total && (uint64_t)res[i].n_runs <= n_runs_total - res[i].ops_off)) {
+      h->err = "problem " + std::to_string(i) + ": its runs leave the run buffer";
+      return WFM_E_ARG;
+    }
+    c.run_off = res[i].ops_off; c.n_runs = res[i].n_runs;
+    c.rec_off = rec_total;
+    rec_total += c.n_runs;
+  }
+  // one block: [records] 16 bytes per run, [offsets] n + 1 and [totals] n of 8 bytes, [problems], [runs], [flags]
+  auto words64 = [](size_t bytes) { return (bytes + 7) / 8; };
+  const size_t nr = n_runs_total;
+  const size_t w_recs = 2 * (size_t)rec_total, w_goff = n + 1, w_tot = n, w_probs = words64(n * sizeof(CsProb)), w_runs = words64(nr * 4), w_flags = words64(n * 4);
+  if (h->csbuf.ensure(w_recs + w_goff + w_tot + w_probs + w_runs + w_flags + 8)) { h->err = "out of device memory (cs)"; return WFM_E_NOMEM; }
+  uint64_t* at = h->csbuf.p;
+  void* d_recs = at; at += w_recs;
+  unsigned long long* d_goff = (unsigned long long*)at; at += w_goff;
+  unsigned long long* d_tot = (unsigned long long*)at; at += w_tot;
+  CsProb* d_probs = (CsProb*)at; at += w_probs;
+  uint32_t* d_runs = (uint32_t*)at; at += w_runs;
+  uint32_t* d_flags = (uint32_t*)at;
+  if (nr) HIPCHK(h, hipMemcpyAsync(d_runs, runs, nr * 4, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(d_probs, probs.data(), n * sizeof(CsProb), hipMemcpyHostToDevice, h->stream));
+  const int dbg = env_debug();
+  if (dbg) HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+  launch_cs_index(d_runs, d_probs, (int)n, form, d_recs, d_tot, d_flags, h->stream);
+  HIPCHK(h, hipGetLastError());
+  if (dbg) HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+  // the problems' totals, once: the host sizes the output and takes their prefix sum
+  std::vector<unsigned long long> goff(n + 1);
+  std::vector<uint32_t> flags(n);
+  HIPCHK(h, hipMemcpyAsync(goff.data() + 1, d_tot, n * 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(flags.data(), d_flags, n * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  float ms_index = 0, ms_write = 0;
+  if (dbg && hipEventElapsedTime(&ms_index, h->ev0, h->ev1) != hipSuccess) (void)hipGetLastError();
+  goff[0] = 0;
+  int spans = 0;
+  for (size_t i = 0; i < n; ++i) {
+    per[i].flags = flags[i]; per[i].n_runs = probs[i].n_runs;
+    per[i].off = goff[i]; per[i].len = goff[i + 1];
+    goff[i + 1] += goff[i];
+    spans += (flags[i] & WFM_CS_SPANS) != 0;
+  }
+  const unsigned long long total = goff[n];
+  if (total == 0) return spans;
+  HIPCHK(h, hipMemcpyAsync(d_goff, goff.data(), (n + 1) * 8, hipMemcpyHostToDevice, h->stream));
+  char* host = (char*)malloc((size_t)total);
+  if (!host) { (void)hipStreamSynchronize(h->stream); h->err = "out of host memory (cs)"; return WFM_E_NOMEM; }
+  // chunks of problems whose strings fit the output block (a problem larger than that is a chunk of its own)
+  const unsigned long long cap = (unsigned long long)std::max(1, env_num("WFM_CS_OUT_MB", 256)) << 20;
+  constexpr size_t CS_PIN_PIECE = (size_t)4 << 20;
+  bool pinned = true;  // (without the pinned pieces the block goes down in one pageable copy)
+  for (int k = 0; k < 2 && pinned; ++k)
+    if (!h->cspin[k] && hipHostMalloc((void**)&h->cspin[k], CS_PIN_PIECE, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); h->cspin[k] = nullptr; pinned = false; }
+  size_t chunks = 0;
+  for (size_t ka = 0; ka < n;) {
+    size_t kb = ka + 1;
+    while (kb < n && goff[kb + 1] - goff[ka] <= cap) ++kb;
+    const unsigned long long bytes = goff[kb] - goff[ka];
+    if (bytes) {
+      const size_t block = (size_t)((bytes + WFM_CS_SLICE - 1) / WFM_CS_SLICE) * WFM_CS_SLICE;
+      int rc = WFM_OK;
+      if (h->csout.ensure(block / 8)) { h->err = "out of device memory (cs output)"; rc = WFM_E_NOMEM; }
+      hipError_t e = hipSuccess;
+      if (rc == WFM_OK) {
+        if (dbg) (void)hipEventRecord(h->ev0, h->stream);
+        launch_cs_write(s->d_seq, d_probs, d_recs, d_goff, (uint32_t)ka, (uint32_t)kb, bytes, form, (uint8_t*)h->csout.p, h->stream);
+        e = hipGetLastError();
+        if (dbg) (void)hipEventRecord(h->ev1, h->stream);
+        // down in pieces through the two pinned buffers: piece j + 1 crosses PCIe while piece j is copied to its place (one pageable
+        // hipMemcpy of a fresh block took 2 ms for 3.7 MB, and 18 - 28 ms every other call: profiles/cs_tag.md)
+        const uint8_t* d_block = (const uint8_t*)h->csout.p;
+        const size_t pieces = pinned ? ((size_t)bytes + CS_PIN_PIECE - 1) / CS_PIN_PIECE : 0;
+        auto piece_len = [&](size_t j) { return std::min<size_t>(CS_PIN_PIECE, (size_t)bytes - j * CS_PIN_PIECE); };
+        if (!pinned && e == hipSuccess) e = hipMemcpyAsync(host + goff[ka], d_block, (size_t)bytes, hipMemcpyDeviceToHost, h->stream);
+        if (pinned && e == hipSuccess) e = hipMemcpyAsync(h->cspin[0], d_block, piece_len(0), hipMemcpyDeviceToHost, h->stream);
+        for (size_t j = 0; j < pieces && e == hipSuccess; ++j) {
+          e = hipStreamSynchronize(h->stream);
+          if (e == hipSuccess && j + 1 < pieces)
+            e = hipMemcpyAsync(h->cspin[(j + 1) & 1], d_block + (j + 1) * CS_PIN_PIECE, piece_len(j + 1), hipMemcpyDeviceToHost, h->stream);
+          if (e == hipSuccess) memcpy(host + goff[ka] + j * CS_PIN_PIECE, h->cspin[j & 1], piece_len(j));
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);  // (the block is the next chunk's)
+        if (e != hipSuccess) { h->err = std::string("wfm_cs_strings: ") + hipGetErrorString(e); rc = WFM_E_HIP; }
+      }
+      if (rc != WFM_OK) { free(host); return rc; }
+      if (dbg) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess) ms_write += ms; else (void)hipGetLastError();
+      }
+      ++chunks;
+    }
+    ka = kb;
+  }
+  *out = host;
+  *out_bytes = (size_t)total;
+  if (dbg)
+    fprintf(stderr, "[wfm] cs (%s): %zu problems, %zu runs, %llu bytes in %zu chunks, index %.3f ms, write %.3f ms (device events), the call %.3f ms (host clock)\n",
+            form == WFM_CS_LONG ? "long" : "short", n, (size_t)rec_total, total, chunks, ms_index, ms_write,
+            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count());
+  return spans;
+}
+
+void wfm_free_cs(char* p) { free(p); }
 
 // ---- every score proved optimal by a banded DP (wfmash_hip.h; the band: wfa_optband.h; the kernel: wfa_optcheck.hip) ----
 int wfm_check_optimal(wfm_handle_t* h, const wfm_penalties_t* pen, const wfm_seqset_t* s, const wfm_result_t* res, uint64_t max_cells,

@@ -30,6 +30,13 @@
 //                                              PAF line, only CIGAR and MD in a SAM record; allowed with -a, -d, --verify (which then checks
 //                                              the normalised lines), --verify-optimal, --resident-seqs, --gpus, -i and -K, refused with -m;
 //                                              off by default
+//   --cs | --cs=short | --cs=long              minimap2's cs:Z: difference string as the last field of every PAF line and SAM record,
+//                                              spelled on the device from the runs the record spells (wfm_cs_strings): which bases are
+//                                              substituted, inserted and deleted (short), with the matching bases as well (long); the
+//                                              value is attached with '=', so a following file name is never taken for it; nothing else
+//                                              of a line changes; allowed with -a, -d, -i, -K, --gpus, --resident-seqs, --verify,
+//                                              --verify-optimal and --left-align (the string is then that of the normalised runs),
+//                                              refused with -m and --verify-paf; off by default
 //   --verify-paf FILE target.fa [query.fa]     the same check on an existing aligned PAF (this build's or the reference's): no mapping,
 //                                              no alignment; exit status 3 if a line fails
 //   --ani-matrix FILE [--ani-only]             the group-by-group ANI table the identity estimate (-p aniN) is made from, as TSV: per
@@ -120,6 +127,7 @@ static void usage() {
           "            --verify-optimal prove every alignment score optimal by a banded DP on the GPU (slow; exit status 3 if one is not; not with -m)\n"
           "            --verify-optimal-cells N skip problems whose band holds more than N DP cells [no cap]\n"
           "            --left-align move every interior gap of the final CIGARs to its leftmost placement on the GPU (only cg:Z: / CIGAR and MD change; not with -m)\n"
+          "            --cs[=short|=long] append minimap2's cs:Z: difference string, spelled on the GPU, to every PAF line / SAM record (not with -m, --verify-paf)\n"
           "            --verify-paf FILE check an existing aligned PAF against target.fa [query.fa] and stop (exit status 3 if a line fails)\n"
           "  other     --out FILE [stdout]   --device INT [0]   --gpus N|all [1] GPUs of this node, starting at --device\n"
           "            -B DIR directory of the hand-off file [cwd]   -Z keep the hand-off file   --quiet (no effect)\n");
@@ -134,6 +142,7 @@ int main(int argc, char** argv) {
   std::string mapping_in, out = "/dev/stdout", target, query, seeds_in, scaffold_out, tmp_base, verify_in, ani_matrix_out;
   bool verify = false, verify_optimal = false, ani_only = false, left_align = false;
   uint64_t verify_optimal_cells = 0;
+  int cs_form = 0;  // --cs: 0 off, 1 short, 2 long
   bool approx_only = false, target_padding_given = false, query_padding_given = false, keep_temp = false;
   int device = 0, gpus = 1;
   for (int i = 1; i < argc; ++i) {
@@ -267,6 +276,9 @@ int main(int argc, char** argv) {
     else if (a == "--verify") verify = true;
     else if (a == "--verify-optimal") verify_optimal = true;
     else if (a == "--left-align") left_align = true;
+    else if (a == "--cs" || a == "--cs=short") cs_form = 1;
+    else if (a == "--cs=long") cs_form = 2;
+    else if (a.compare(0, 5, "--cs=") == 0) { fprintf(stderr, "[wfmash] ERROR: --cs takes =short or =long, not '%s'\n", a.c_str() + 5); return 1; }
     else if (a == "--verify-optimal-cells") verify_optimal_cells = std::strtoull(next("--verify-optimal-cells").c_str(), nullptr, 10);
     else if (a == "--verify-paf") verify_in = next("--verify-paf");
     else if (a == "-h" || a == "--help") { usage(); return 0; }
@@ -278,6 +290,8 @@ int main(int argc, char** argv) {
   if (verify && ap.sam_format) { fprintf(stderr, "[wfmash] ERROR: --verify reads the =/X CIGAR of PAF lines: it cannot be combined with -a (SAM)\n"); return 1; }
   if (verify && approx_only) { fprintf(stderr, "[wfmash] ERROR: --verify checks alignments: it cannot be combined with -m\n"); return 1; }
   if (left_align && approx_only) { fprintf(stderr, "[wfmash] ERROR: --left-align normalises alignments: it cannot be combined with -m\n"); return 1; }
+  if (cs_form && approx_only) { fprintf(stderr, "[wfmash] ERROR: --cs spells alignments: it cannot be combined with -m\n"); return 1; }
+  if (cs_form && !verify_in.empty()) { fprintf(stderr, "[wfmash] ERROR: --cs belongs to the align phase: it cannot be combined with --verify-paf\n"); return 1; }
   if (verify_optimal && approx_only) { fprintf(stderr, "[wfmash] ERROR: --verify-optimal checks alignment scores: it cannot be combined with -m\n"); return 1; }
   if (verify_optimal_cells && !verify_optimal) { fprintf(stderr, "[wfmash] ERROR: --verify-optimal-cells needs --verify-optimal\n"); return 1; }
   if (ani_only && ani_matrix_out.empty()) { fprintf(stderr, "[wfmash] ERROR: --ani-only needs --ani-matrix FILE\n"); return 1; }
@@ -408,6 +422,7 @@ int main(int argc, char** argv) {
     if (verify) wfmh_set_verify(1);
     if (verify_optimal) wfmh_set_verify_optimal(1, verify_optimal_cells);
     if (left_align) wfmh_set_left_align(1);
+    if (cs_form) wfmh_set_cs(cs_form);
     rc = wfmh_align_paf_multi(hs.data(), (int)hs.size(), target.c_str(), q, mapping.c_str(), out.c_str(), &ap, &s);
     if (rc == WFM_OK)
       fprintf(stderr, "[wfmash::align] %llu records, %llu aligned bp, %.1f ms GPU kernels, %.1f ms total => %.3g aligned bp/s\n",
@@ -418,6 +433,12 @@ int main(int argc, char** argv) {
       wfmh_left_align_counts(lc);
       fprintf(stderr, "[wfmash::left-align] %llu records, %llu interior gaps, %llu moved, %llu records left alone\n", (unsigned long long)lc[0],
               (unsigned long long)lc[1], (unsigned long long)lc[2], (unsigned long long)lc[3]);
+    }
+    if (cs_form && rc == WFM_OK) {
+      uint64_t cc[4] = {0, 0, 0, 0};
+      wfmh_cs_counts(cc);
+      fprintf(stderr, "[wfmash::cs] %llu records, %llu bytes (%s), %llu records left without a string\n", (unsigned long long)cc[0], (unsigned long long)cc[1],
+              cs_form == 2 ? "long" : "short", (unsigned long long)cc[2]);
     }
     if (verify && rc == WFM_OK) {  // everything has been written by now
       uint64_t vc[4] = {0, 0, 0, 0};

@@ -53,6 +53,10 @@ std::atomic<uint64_t> g_optimal_counts[4];
 std::atomic<bool> g_left_align{false};
 std::atomic<uint64_t> g_left_align_counts[4];
 
+// --cs: the process-wide switch (0 off, 1 short, 2 long) and {records spelled, bytes spelled, records left without a string, 0} since it was set
+std::atomic<int> g_cs{0};
+std::atomic<uint64_t> g_cs_counts[4];
+
 // The problems of one device call, always written by reference (a side without a store id carries its host pointer); without a
 // store they go to the device as plain wfm_problem_t, as they always have.
 struct GpuBatch {
@@ -199,6 +203,8 @@ wfm_problem_ref_t tail_problem(const BiwfaRecord& r, const Erosion& e) {  // wfl
 using Clock = std::chrono::steady_clock;
 double ms_between(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
 
+struct WindowSet;  // the records' final runs as device problems (left_align_records, cs_records)
+
 // One call of do_biwfa_alignment_batch: what its stages share.
 struct BiwfaBatch {
   wfm_handle_t* h;
@@ -218,6 +224,8 @@ struct BiwfaBatch {
   std::vector<char> over_budget;  // WFM_ST_OOM: dropped like every record whose main alignment fails, but not silently
   size_t later = 0;               // records whose tail is scanned on the head-patched CIGAR
   std::atomic<uint64_t> n_head{0}, n_tail{0};
+  int cs_form = 0;                // --cs as the batch found it: 0 off, 1 short, 2 long
+  std::unique_ptr<WindowSet> windows;  // what left_align_records leaves for cs_records
   // the handle's message was copied while the handle was still this thread's (another batch may be using it by now)
   int fail(const GpuBatch& g, int rc) const { if (stats) stats->error = g.err; return rc; }
 };
@@ -244,6 +252,7 @@ int align_main(BiwfaBatch& b, bool plan) {
     r.score = g.res[i].score;
     r.tags = g.flags[i] & 0xffu;
     r.paf.clear();
+    r.cs.clear();
     r.ops.clear();
     if (!r.ok) return;
     g.ops(i, r.ops);
@@ -357,20 +366,28 @@ void swizzle(BiwfaBatch& b, size_t ri) {
   }
 }
 
-// ---- --left-align: the interior gaps of every record's final ops moved to their leftmost placement, ONE device call per batch
-// (wfm_left_align_runs).  What goes to the device is what the writers spell: both of them begin by stripping the leading and trailing I
-// and D runs and shifting the start coordinates (trim_and_filter), so a record's problem is the runs ops[b, e) that remain against the
-// sub-windows they cover.  The line's first and last runs are then the problem's first and last, which the rule never touches -- no
-// coordinate moves, and the CIGAR of the line is the rule applied to the line.  Records go by reference where the batch has a store.
-// The ops of an ok record always span its windows (an end-to-end alignment does, a patch replaces eroded runs by an alignment of exactly
-// their bases, erosion and the swaps keep both totals), so a record left alone is a defect; it is written as it is and counted. ----
-int left_align_records(BiwfaBatch& b) {
-  const auto t0 = Clock::now();
+// ---- the records' final runs as device problems of their own: what --left-align and --cs work on.  What goes to the device is what the
+// writers spell: both of them begin by stripping the leading and trailing I and D runs and shifting the start coordinates
+// (trim_and_filter), so a record's problem is the runs ops[b, e) that remain against the sub-windows they cover.  Records go by reference
+// where the batch has a store.  The ops of an ok record always span its windows (an end-to-end alignment does, a patch replaces eroded
+// runs by an alignment of exactly their bases, erosion and the swaps keep both totals). ----
+struct WindowSet {
   struct Part { size_t rec, b, e; };
   std::vector<Part> parts;
   std::vector<wfm_problem_ref_t> probs;
-  std::vector<wfm_result_t> res;
-  std::vector<uint32_t> runs;
+  std::vector<wfm_result_t> res;   // locates every part's runs in cur()
+  std::vector<uint32_t> runs;      // as built from the records' ops
+  uint32_t* la_runs = nullptr;     // wfm_left_align_runs' output once it has run: res locates the parts there from then on
+  size_t n_la_runs = 0;
+  size_t unknown = 0;              // records with an op or a length the device's runs cannot hold: left out
+  wfm_seqset_t* S = nullptr;       // the sub-windows on the device, uploaded once for both calls
+  const uint32_t* cur() const { return la_runs ? la_runs : runs.data(); }
+  size_t n_cur() const { return la_runs ? n_la_runs : runs.size(); }
+};
+
+// every ok record whose trimmed part has at least min_runs runs
+std::unique_ptr<WindowSet> window_parts(const BiwfaBatch& b, size_t min_runs) {
+  std::unique_ptr<WindowSet> w(new WindowSet());
   for (size_t i = 0; i < b.recs.size(); ++i) {
     const BiwfaRecord& r = b.recs[i];
     if (!r.ok) continue;
@@ -379,50 +396,72 @@ int left_align_records(BiwfaBatch& b) {
     uint64_t ta = 0, qa = 0;
     while (ob < oe && (ops[ob].second == 'I' || ops[ob].second == 'D')) { (ops[ob].second == 'I' ? qa : ta) += (uint64_t)ops[ob].first; ++ob; }
     while (oe > ob && (ops[oe - 1].second == 'I' || ops[oe - 1].second == 'D')) --oe;
-    if (oe - ob < 3) continue;  // no interior run
+    if (oe - ob < min_runs) continue;
     const CigarStats cs = cigar_stats(ops, ob, oe);
     wfm_problem_ref_t p = window_problem(r, ta, cs.ref_len, qa, cs.q_len);
     p.mode = WFM_MODE_END2END_UNI;  // (no reversed copies are made for it)
     wfm_result_t q{};
     q.status = 0; q.score = -1;
-    q.ops_off = runs.size(); q.n_runs = (uint32_t)(oe - ob);
+    q.ops_off = w->runs.size(); q.n_runs = (uint32_t)(oe - ob);
     bool known = true;
     for (size_t k = ob; k < oe; ++k) {
       const char c = ops[k].second;
       const uint32_t op = c == '=' ? 0u : c == 'X' ? 1u : c == 'I' ? 2u : c == 'D' ? 3u : 4u;
       if (op > 3u || ops[k].first <= 0 || (uint32_t)ops[k].first >= (1u << 30)) { known = false; break; }
-      runs.push_back(((uint32_t)ops[k].first << 2) | op);
+      w->runs.push_back(((uint32_t)ops[k].first << 2) | op);
     }
-    if (!known) { runs.resize((size_t)q.ops_off); g_left_align_counts[0] += 1; g_left_align_counts[3] += 1; continue; }
+    if (!known) { w->runs.resize((size_t)q.ops_off); ++w->unknown; continue; }
     q.ops_len = (uint32_t)std::min<uint64_t>(cs.ref_len + cs.q_len, 0xffffffffu);
-    parts.push_back(Part{i, ob, oe});
-    probs.push_back(p);
-    res.push_back(q);
+    w->parts.push_back(WindowSet::Part{i, ob, oe});
+    w->probs.push_back(p);
+    w->res.push_back(q);
   }
-  if (parts.empty()) return 0;
-  const size_t n = parts.size();
+  return w;
+}
+
+// the parts' sub-windows to the device (the caller holds the handle's lock)
+int upload_windows(BiwfaBatch& b, WindowSet& w) {
+  const size_t n = w.parts.size();
+  if (b.store) return wfm_upload_sequence_refs(b.h, b.store, w.probs.data(), n, &w.S);
+  std::vector<wfm_problem_t> plain(n);
+  for (size_t i = 0; i < n; ++i) plain[i] = wfm_problem_t{w.probs[i].pattern, w.probs[i].plen, w.probs[i].text, w.probs[i].tlen, w.probs[i].mode, 0, 0, 0, 0, 0, 0};
+  return wfm_upload_sequences(b.h, plain.data(), n, &w.S);
+}
+
+void release_windows(BiwfaBatch& b) {
+  if (!b.windows) return;
+  if (b.windows->S) {
+    std::lock_guard<std::mutex> lk(handle_lock(b.h));
+    wfm_free_sequences(b.h, b.windows->S);
+  }
+  wfm_free_runs(b.windows->la_runs);
+  b.windows.reset();
+}
+
+// ---- --left-align: the interior gaps of every record's final ops moved to their leftmost placement, ONE device call per batch
+// (wfm_left_align_runs).  The line's first and last runs are the problem's first and last, which the rule never touches -- no
+// coordinate moves, and the CIGAR of the line is the rule applied to the line.  A record left alone is a defect; it is written as it is
+// and counted.  Alone, the stage takes the records with an interior run; with --cs as well (keep) it takes every record cs_records
+// will spell, and leaves the uploaded windows and the new runs in b.windows for it. ----
+int left_align_records(BiwfaBatch& b, bool keep) {
+  const auto t0 = Clock::now();
+  b.windows = window_parts(b, keep ? 1 : 3);
+  WindowSet& w = *b.windows;
+  g_left_align_counts[0] += w.unknown; g_left_align_counts[3] += w.unknown;
+  if (w.parts.empty()) return 0;
+  const size_t n = w.parts.size();
   std::vector<wfm_leftalign_t> la(n);
-  uint32_t* out = nullptr;
   int rc;
   {
     std::lock_guard<std::mutex> lk(handle_lock(b.h));
-    wfm_seqset_t* S = nullptr;
-    if (b.store) rc = wfm_upload_sequence_refs(b.h, b.store, probs.data(), n, &S);
-    else {
-      std::vector<wfm_problem_t> plain(n);
-      for (size_t i = 0; i < n; ++i) plain[i] = wfm_problem_t{probs[i].pattern, probs[i].plen, probs[i].text, probs[i].tlen, probs[i].mode, 0, 0, 0, 0, 0, 0};
-      rc = wfm_upload_sequences(b.h, plain.data(), n, &S);
-    }
-    if (rc == WFM_OK) {
-      rc = wfm_left_align_runs(b.h, S, res.data(), runs.data(), runs.size(), &out, nullptr, la.data());
-      wfm_free_sequences(b.h, S);
-    }
+    rc = upload_windows(b, w);
+    if (rc == WFM_OK) rc = wfm_left_align_runs(b.h, w.S, w.res.data(), w.runs.data(), w.runs.size(), &w.la_runs, &w.n_la_runs, la.data());
     if (rc < 0 && b.stats) b.stats->error = wfm_last_error(b.h);
   }
-  if (rc < 0) { wfm_free_runs(out); return rc; }
+  if (rc < 0) return rc;
   std::atomic<uint64_t> gaps{0}, moved{0}, alone{0};
   for_each_record(n, b.fmt.threads, [&](size_t j) {
-    const Part& pt = parts[j];
+    const WindowSet::Part& pt = w.parts[j];
     const wfm_leftalign_t& l = la[j];
     if (l.flags) { alone.fetch_add(1); return; }
     gaps.fetch_add(l.gaps);
@@ -430,17 +469,49 @@ int left_align_records(BiwfaBatch& b) {
     moved.fetch_add(l.moved);
     CigarOps& ops = b.recs[pt.rec].ops;
     CigarOps mid;
-    ops_from_runs(out + res[j].ops_off, res[j].n_runs, mid);
+    ops_from_runs(w.la_runs + w.res[j].ops_off, w.res[j].n_runs, mid);
     CigarOps all(ops.begin(), ops.begin() + (long)pt.b);
     all.insert(all.end(), mid.begin(), mid.end());
     all.insert(all.end(), ops.begin() + (long)pt.e, ops.end());
     ops.swap(all);
   });
-  wfm_free_runs(out);
   g_left_align_counts[0] += n; g_left_align_counts[1] += gaps.load(); g_left_align_counts[2] += moved.load(); g_left_align_counts[3] += alone.load();
   if (getenv("WFM_DEBUG"))
-    fprintf(stderr, "[wflign] left-align: %zu records, %zu runs, %llu gaps, %llu moved, %llu left alone, %.1f ms (upload, device call, splice)\n", n, runs.size(),
+    fprintf(stderr, "[wflign] left-align: %zu records, %zu runs, %llu gaps, %llu moved, %llu left alone, %.1f ms (upload, device call, splice)\n", n, w.runs.size(),
             (unsigned long long)gaps.load(), (unsigned long long)moved.load(), (unsigned long long)alone.load(), ms_between(t0, Clock::now()));
+  return 0;
+}
+
+// ---- --cs: the cs difference string of every record's line, ONE device call per batch (wfm_cs_strings) on the runs the line spells
+// -- behind left_align_records, the normalised ones on the windows it uploaded.  Every ok record whose trimmed part is not empty takes
+// part.  A record the device flags (its runs do not span its windows) is a defect: it is written without the field and counted. ----
+int cs_records(BiwfaBatch& b) {
+  const auto t0 = Clock::now();
+  if (!b.windows) b.windows = window_parts(b, 1);
+  WindowSet& w = *b.windows;
+  if (w.parts.empty()) return 0;
+  const size_t n = w.parts.size();
+  std::vector<wfm_cs_t> per(n);
+  char* text = nullptr;
+  size_t bytes = 0;
+  int rc = WFM_OK;
+  auto t1 = t0;
+  {
+    std::lock_guard<std::mutex> lk(handle_lock(b.h));
+    if (!w.S) rc = upload_windows(b, w);
+    t1 = Clock::now();
+    if (rc == WFM_OK) rc = wfm_cs_strings(b.h, w.S, w.res.data(), w.cur(), w.n_cur(), b.cs_form == 2 ? WFM_CS_LONG : WFM_CS_SHORT, &text, &bytes, per.data());
+    if (rc < 0 && b.stats) b.stats->error = wfm_last_error(b.h);
+  }
+  if (rc < 0) return rc;
+  const auto t2 = Clock::now();
+  for_each_record(n, b.fmt.threads, [&](size_t j) {
+    if (per[j].flags == 0 && per[j].len) b.recs[w.parts[j].rec].cs.assign(text + per[j].off, (size_t)per[j].len);
+  });
+  wfm_free_cs(text);
+  if (getenv("WFM_DEBUG"))
+    fprintf(stderr, "[wflign] cs (%s): %zu records, %zu runs, %zu bytes, %d flagged, %.1f ms (upload %.1f, device call %.1f, splice %.1f)\n", b.cs_form == 2 ? "long" : "short",
+            n, w.n_cur(), bytes, rc, ms_between(t0, Clock::now()), ms_between(t0, t1), ms_between(t1, t2), ms_between(t2, Clock::now()));
   return 0;
 }
 
@@ -448,14 +519,24 @@ int left_align_records(BiwfaBatch& b) {
 void write_record(BiwfaBatch& b, size_t ri) {
   BiwfaRecord& r = b.recs[ri];
   if (!r.ok) return;
+  bool written;
   if (b.fmt.paf_format_else_sam)
-    write_alignment_paf(r.paf, r.ops, r.query_name, r.query_total_length, r.query_offset, r.query_length, r.query_is_rev,
+    written = write_alignment_paf(r.paf, r.ops, r.query_name, r.query_total_length, r.query_offset, r.query_length, r.query_is_rev,
                         r.target_name, r.target_total_length, r.target_offset, b.pp, r.mashmap_estimated_identity, r.chain_id,
                         r.chain_length, r.chain_pos);
   else
-    write_alignment_sam(r.paf, r.ops, r.query_name, r.query_offset, r.query_is_rev, r.target_name, r.target_offset, b.pp,
+    written = write_alignment_sam(r.paf, r.ops, r.query_name, r.query_offset, r.query_is_rev, r.target_name, r.target_offset, b.pp,
                         r.mashmap_estimated_identity, b.fmt.no_seq_in_sam, b.fmt.emit_md_tag, r.query, r.target, r.chain_id,
                         r.chain_length, r.chain_pos);
+  if (!b.cs_form || !written) return;
+  if (r.cs.empty()) { g_cs_counts[2] += 1; return; }  // (flagged by the device, or runs it cannot hold)
+  // the last field of the line, before its closing newline
+  r.paf.pop_back();
+  r.paf.reserve(r.paf.size() + r.cs.size() + 7);
+  r.paf += "\tcs:Z:";
+  r.paf += r.cs;
+  r.paf += '\n';
+  g_cs_counts[0] += 1; g_cs_counts[1] += r.cs.size();
 }
 }  // namespace
 
@@ -480,9 +561,14 @@ int do_biwfa_alignment_batch(wfm_handle_t* h, std::vector<BiwfaRecord>& recs, co
     if (stats) { stats->head_patches += b.n_head.load(); stats->tail_patches += b.n_tail.load(); }
   }
   const auto ts2 = Clock::now();
-  if (g_left_align.load()) {  // the two halves with the device call between them
+  const bool left = g_left_align.load();
+  b.cs_form = g_cs.load(std::memory_order_relaxed);
+  if (left || b.cs_form) {  // the two halves with the device calls between them
     for_each_record(n, fmt.threads, [&](size_t ri) { swizzle(b, ri); });
-    if ((rc = left_align_records(b)) < 0) return rc;
+    if (left) rc = left_align_records(b, b.cs_form != 0);
+    if (rc >= 0 && b.cs_form) rc = cs_records(b);
+    release_windows(b);
+    if (rc < 0) return rc;
     for_each_record(n, fmt.threads, [&](size_t ri) { write_record(b, ri); });
   } else {
     for_each_record(n, fmt.threads, [&](size_t ri) { swizzle(b, ri); write_record(b, ri); });
@@ -506,6 +592,17 @@ void wfmh_set_verify_optimal(int on, uint64_t max_cells) {
 void wfmh_set_left_align(int on) {
   for (auto& a : wflign::g_left_align_counts) a.store(0);
   wflign::g_left_align.store(on != 0);
+}
+
+void wfmh_set_cs(int form) {
+  for (auto& a : wflign::g_cs_counts) a.store(0);
+  wflign::g_cs.store(form == 1 || form == 2 ? form : 0);
+}
+
+int wfmh_cs_counts(uint64_t out[4]) {
+  if (!out) return WFM_E_ARG;
+  for (int q = 0; q < 4; ++q) out[q] = wflign::g_cs_counts[q].load();
+  return WFM_OK;
 }
 
 int wfmh_left_align_counts(uint64_t out[4]) {

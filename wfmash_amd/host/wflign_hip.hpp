@@ -12,7 +12,9 @@
 //   patch_late_tails   the tails whose scan has to see the patched head  (wflign.cpp:323-418)
 //   swizzle            the two end swaps                       (wflign.cpp:423-433)
 //   left_align_records --left-align only: every interior gap to its leftmost placement, one wfm_left_align_runs call
-//   write_record       PAF / SAM record                        (wflign.cpp:434-454)
+//   cs_records         --cs only: the cs difference string of every record's line, one wfm_cs_strings call (on the windows
+//                      left_align_records uploaded, where both are on)
+//   write_record       PAF / SAM record (+ cs:Z: as its last field)   (wflign.cpp:434-454)
 // and CIGARs are runs (count, op) from the device to the record's text: nothing is expanded to one byte per base.
 #pragma once
 
@@ -61,6 +63,7 @@ struct BiwfaRecord {
   int32_t score = -1;
   CigarOps ops;                      // final CIGAR as runs (after patching + swizzle)
   std::string paf;                   // the record's line incl. newline, as the align driver writes it ("" if filtered)
+  std::string cs;                    // --cs: the cs string of the line's runs, without its tag ("" if off, or if the record has none)
   uint32_t tags = 0;                 // WFM_PF_* of the main alignment | of the head patch << 8 | of the tail patch << 16 (diagnostics: WFM_RECORD_TAGS)
 };
 
