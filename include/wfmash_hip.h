@@ -364,6 +364,49 @@ int  wfm_cs_strings(wfm_handle_t* h, const wfm_seqset_t* s, const wfm_result_t* 
                     int form, char** out, size_t* out_bytes, wfm_cs_t* per);
 void wfm_free_cs(char* p);
 
+/* ---- the variants of every problem's runs ----
+ * The list of differences itself: every substitution, insertion and deletion of a problem's runs as a record in VCF form, REF and ALT
+ * alleles included, called on the device (wfmash_amd/csrc/wfa_variants.hip; forward BYTE copies only; nothing is shared with the aligners).
+ * s, res and runs as for wfm_cs_strings: res[i].ops_off may come in any order, with unused words between the problems.
+ *
+ * The grammar.  Pattern = target = REF side P; text = query side T as aligned.  p and t are the indices a run begins at:
+ *   run                        records                fields                                                         allele bytes
+ *   M of L                     none                                                                                  0
+ *   X of L                     L SNVs, j = 0..L-1     p = p+j, t = t+j, REF = P[p+j], ALT = T[t+j]; kind carries      2 each
+ *                                                     WFM_VAR_MASKED when either byte is outside ACGTacgt
+ *   I of L, called             1 INS                  p = p-1 (the anchor), t = t, REF = P[p-1], ALT = P[p-1] + T[t..t+L)   L + 2
+ *   D of L, called             1 DEL                  p = p-1, t = t, REF = P[p-1..p+L), ALT = P[p-1]                  L + 2
+ *   I or D, not called         none: counted in end_gaps                                                             0
+ * A gap is called unless it is the problem's first or last run -- an alignment end, not a variant -- or no pattern base lies before it
+ * (p = 0: it has no anchor, which happens only behind a first run that is an I).  Bytes are emitted as they are, with no case change.  Two
+ * adjacent gaps (2I3D) and a gap behind an X run each keep the rule; they share an anchor, which is valid VCF.  The records are called
+ * from the runs and never from a comparison, so their number and the allele bytes follow from the runs alone: a masked SNV is a flagged
+ * record, not a missing one.  The defining property: applying a problem's records to P from the last to the first (SNV: P[p] = ALT; INS:
+ * insert ALT[1:] behind P[p]; DEL: remove P[p+1 .. p+ref_len)) gives T for every valid CIGAR without end gaps.
+ *
+ * *vars receives the records of all problems -- problems in problem order, runs in run order, an X run's bases in base order -- and
+ * *n_vars their number; *alleles the allele bytes in the same order, *allele_bytes their total: a record's REF is alleles[off .. off +
+ * ref_len), its ALT the alt_len bytes behind.  Both are host memory owned by the caller (release with wfm_free_variants).  per receives
+ * one wfm_varcall_t per problem: first / count locate its records in *vars, n_runs is the number of runs they were called from.  A
+ * problem flagged WFM_VAR_NOT_DONE or WFM_VAR_SPANS has count 0 and nothing of it is called.  Returns the number of problems flagged
+ * WFM_VAR_SPANS, or a WFM_E_* code; a run range that leaves runs[0 .. n_runs_total) is WFM_E_ARG with a message (the outputs are NULL,
+ * the handle stays usable).  No problems: WFM_OK, NULL outputs and zero counts.
+ * One workgroup writes WFM_VAR_SLICE allele bytes whatever runs or problems they belong to, and the problems are worked in chunks whose
+ * device blocks, alleles and records together, hold at most WFM_VAR_OUT_MB MiB (environment, read per call, 256; a single problem may
+ * exceed it alone).  No atomics: two calls give the same bytes. */
+typedef struct { uint32_t problem, kind; uint32_t p, t; uint32_t ref_len, alt_len; uint64_t off; } wfm_variant_t;   /* 32 bytes */
+typedef struct { uint32_t flags, n_runs; uint64_t first, count; uint32_t end_gaps, pad_; } wfm_varcall_t;        /* 32 bytes */
+#define WFM_VAR_SNV 0u
+#define WFM_VAR_INS 1u
+#define WFM_VAR_DEL 2u
+#define WFM_VAR_MASKED 256u      /* bit of kind: an SNV whose REF or ALT byte is not one of ACGTacgt */
+#define WFM_VAR_NOT_DONE 1u      /* as WFM_CS_NOT_DONE */
+#define WFM_VAR_SPANS    2u      /* as WFM_CS_SPANS: nothing of the problem is called */
+#define WFM_VAR_SLICE 16384      /* allele bytes one workgroup writes */
+int  wfm_call_variants(wfm_handle_t* h, const wfm_seqset_t* s, const wfm_result_t* res, const uint32_t* runs, size_t n_runs_total,
+                       wfm_variant_t** vars, size_t* n_vars, char** alleles, size_t* allele_bytes, wfm_varcall_t* per);
+void wfm_free_variants(wfm_variant_t* vars, char* alleles);
+
 /* ---- every score proved optimal by a banded DP ----
  * What wfm_check_runs leaves out.  For every problem of the seqset s whose result claims a score S = res[i].score, a classical
  * minimising gap-affine-2-piece DP over cells (i = pattern index, j = text index) is run on the device, restricted to a band of

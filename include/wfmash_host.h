@@ -138,6 +138,24 @@ int  wfmh_left_align_counts(uint64_t out[4]);
 void wfmh_set_cs(int form);
 int  wfmh_cs_counts(uint64_t out[4]);
 
+/* ---- the variants of every record written, as a VCF (wfm_call_variants, wfmash_hip.h) ----
+ * wfmh_set_variants(path): from now on every batch of wfmh_align_paf[_multi] runs ONE more device call between the swizzle (and the
+ * left-align and cs calls, where those switches are on) and the record writers: the SNVs, insertions and deletions of the runs each
+ * record's line will spell, alleles included, against the sub-windows they cover -- by reference where the run keeps its sequences on the
+ * device, so the host never needs a record's bases.  The windows are uploaded once whichever of the three switches are on, and with
+ * wfmh_set_left_align the variants are those of the normalised runs.  No output byte of the PAF or SAM changes.  The align phase writes
+ * `path`: the header (##fileformat=VCFv4.2, ##source, one ##contig per sequence of the target index in index order, the ##INFO lines of
+ * QNAME, QSTART, QEND and QSTRAND, #CHROM .. INFO: no sample columns), then the lines of every record written, in the order of the
+ * records whatever the number of devices, within a record in ascending POS: POS = the record's target start + p + 1; ID, QUAL and
+ * FILTER are '.'; alleles on the target's strand; [QSTART, QEND) = the 0-based forward-strand span of the query bases in ALT (one base
+ * for an SNV, the inserted bases for an insertion, empty at the junction for a deletion).  The file is not sorted across records.  SNVs
+ * with a base outside ACGT are left out and counted; a record whose runs do not span its windows has no lines and is counted as left
+ * alone (the pipeline produces none).  NULL or "" switches it off.  Every call zeroes the counts.  wfmh_variants_counts: out = {records
+ * called, variants written, SNVs masked, records left alone} since then.  Off by default; with the switch off nothing new is called
+ * and no file is written. */
+void wfmh_set_variants(const char* path_or_null);
+int  wfmh_variants_counts(uint64_t out[4]);
+
 /* Test hooks: the pure host-side CIGAR functions (erode / merge / swizzle / PAF writer /
  * parseMashmapRow) behind one string interface so the CPU test-suite can check them
  * without a GPU.  fn in {erode, merge, compress, swap_start, swap_end, head_erosion,

@@ -45,6 +45,7 @@ EXPORTS = [
     "wfm_seqstore_create", "wfm_seqstore_free", "wfm_seqstore_add", "wfm_seqstore_info",
     "wfm_upload_sequence_refs", "wfm_align_refs_rle", "wfm_download_sequences",
     "wfm_check_runs", "wfm_check_optimal", "wfm_left_align_runs", "wfm_cs_strings", "wfm_free_cs",
+    "wfm_call_variants", "wfm_free_variants",
     "wfm_sketch_intersections",
 ]
 ISECT_LDS_MAX = 4096  # WFM_ISECT_LDS_MAX: the longest column sketch wfm_sketch_intersections searches in LDS
@@ -58,6 +59,11 @@ WFM_LA_NOT_DONE, WFM_LA_SPANS = 1, 2
 WFM_CS_SHORT, WFM_CS_LONG = 0, 1
 WFM_CS_NOT_DONE, WFM_CS_SPANS = 1, 2
 WFM_CS_SLICE = 16384
+# wfm_call_variants (include/wfmash_hip.h): a record's kind and its MASKED bit, why a problem has no records, the allele bytes one workgroup writes
+WFM_VAR_SNV, WFM_VAR_INS, WFM_VAR_DEL = 0, 1, 2
+WFM_VAR_MASKED = 256
+WFM_VAR_NOT_DONE, WFM_VAR_SPANS = 1, 2
+WFM_VAR_SLICE = 16384
 # wfm_check_optimal (include/wfmash_hip.h): what a problem's score was flagged for, and the band widths at which the kernel changes form
 WFM_OPT_NOT_CHECKED, WFM_OPT_SKIPPED, WFM_OPT_CHEAPER, WFM_OPT_UNREACHED = 1, 2, 4, 8
 OPT_NAMES = ("NOT_CHECKED", "SKIPPED", "CHEAPER", "UNREACHED")
@@ -116,6 +122,21 @@ class LeftAlign(C.Structure):
 class Cs(C.Structure):
     """wfm_cs_t: where wfm_cs_strings put one problem's cs string, and the runs it was spelled from."""
     _fields_ = [("flags", C.c_uint32), ("n_runs", C.c_uint32), ("off", C.c_uint64), ("len", C.c_uint64)]
+
+
+class Variant(C.Structure):
+    """wfm_variant_t: one record of wfm_call_variants; its REF is alleles[off : off + ref_len], its ALT the alt_len bytes behind."""
+    _fields_ = [("problem", C.c_uint32), ("kind", C.c_uint32), ("p", C.c_uint32), ("t", C.c_uint32),
+                ("ref_len", C.c_uint32), ("alt_len", C.c_uint32), ("off", C.c_uint64)]
+
+
+VARIANT_DTYPE = np.dtype([("problem", "<u4"), ("kind", "<u4"), ("p", "<u4"), ("t", "<u4"), ("ref_len", "<u4"), ("alt_len", "<u4"), ("off", "<u8")])
+
+
+class VarCall(C.Structure):
+    """wfm_varcall_t: where wfm_call_variants put one problem's records, the runs they were called from and the gaps it did not call."""
+    _fields_ = [("flags", C.c_uint32), ("n_runs", C.c_uint32), ("first", C.c_uint64), ("count", C.c_uint64),
+                ("end_gaps", C.c_uint32), ("pad_", C.c_uint32)]
 
 
 class OptCheck(C.Structure):
@@ -739,6 +760,39 @@ class Handle:
             self._L.wfm_free_cs(text)
         return [blob[per[i].off:per[i].off + per[i].len] for i in range(n)], [per[i] for i in range(n)]
 
+    def call_variants(self, seqset, results, runs):
+        """wfm_call_variants: the SNVs, insertions and deletions of every problem's runs, called on the device.  results and runs as for
+        check_runs.  Returns (records: a numpy structured array with the fields of Variant, alleles: all allele bytes as bytes,
+        [VarCall], one per problem)."""
+        n = seqset.n
+        arr = (Result * max(n, 1))()
+        if isinstance(results, C.Array):
+            C.memmove(arr, results, C.sizeof(Result) * n)
+        else:
+            assert len(results) == n, (len(results), n)
+            for i, (status, score, ops_off, ops_len, n_runs) in enumerate(results):
+                arr[i].status, arr[i].score, arr[i].ops_off, arr[i].ops_len, arr[i].n_runs = status, score, ops_off, ops_len, n_runs
+        runs = np.ascontiguousarray(runs, dtype=np.uint32)
+        per = (VarCall * max(n, 1))()
+        recs, alleles = C.c_void_p(), C.c_void_p()
+        n_recs, n_bytes = C.c_size_t(0), C.c_size_t(0)
+        f = self._L.wfm_call_variants
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                      C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p]
+        self._L.wfm_free_variants.restype = None
+        self._L.wfm_free_variants.argtypes = [C.c_void_p, C.c_void_p]
+        rc = f(self._p, seqset._p, arr, runs.ctypes.data if len(runs) else None, len(runs), C.byref(recs), C.byref(n_recs),
+               C.byref(alleles), C.byref(n_bytes), per)
+        if rc < 0:
+            raise WfmError(f"wfm_call_variants failed ({rc}): {self.last_error()}")
+        try:
+            raw = C.string_at(recs, n_recs.value * C.sizeof(Variant)) if n_recs.value else b""
+            blob = C.string_at(alleles, n_bytes.value) if n_bytes.value else b""
+        finally:
+            self._L.wfm_free_variants(recs, alleles)
+        return np.frombuffer(raw, dtype=VARIANT_DTYPE), blob, [per[i] for i in range(n)]
+
     def check_optimal(self, seqset, results, pen=None, max_cells=0):
         """wfm_check_optimal: every score held against a banded DP on the device.  results: a ctypes array of Result (seqset.results after
         an align call), or a list of (status, score) or plain scores, one per problem of the seqset.  Returns the list of OptCheck records
@@ -1101,7 +1155,7 @@ HOST_EXPORTS = ["wfmh_test_packed_lce", "wfmh_test_is_acgt", "wfmh_align_default
                 "wfmh_release_sequences", "wfmh_test_fasta_shared", "wfmh_seed_paf", "wfmh_test_deal", "wfmh_test_subwindow",
                 "wfmh_test_rows", "wfmh_test_tile_plan", "wfmh_test_p2_plan", "wfmh_test_base_plan", "wfmh_test_map_plan", "wfmh_test_filter_ordered",
                 "wfmh_test_reuse_plan", "wfmh_test_tile_plan_dirs", "wfmh_test_tile_interior", "wfmh_test_tile_lean_waves", "wfmh_set_verify", "wfmh_verify_counts", "wfmh_verify_paf", "wfmh_test_verify_parse",
-                "wfmh_set_verify_optimal", "wfmh_verify_optimal_counts", "wfmh_test_opt_band", "wfmh_set_left_align", "wfmh_left_align_counts", "wfmh_set_cs", "wfmh_cs_counts",
+                "wfmh_set_verify_optimal", "wfmh_verify_optimal_counts", "wfmh_test_opt_band", "wfmh_set_left_align", "wfmh_left_align_counts", "wfmh_set_cs", "wfmh_cs_counts", "wfmh_set_variants", "wfmh_variants_counts",
                 "wfmh_ani_matrix", "wfmh_ani_matrix_rows", "wfmh_free_ani_rows", "wfmh_set_ani_matrix", "wfmh_test_ani_tsv"]
 
 
@@ -1493,6 +1547,27 @@ def cs_counts():
     rc = f(out)
     if rc != 0:
         raise WfmError(f"wfmh_cs_counts failed ({rc})")
+    return tuple(int(v) for v in out)
+
+
+def set_variants(path) -> None:
+    """wfmh_set_variants: every later align_paf call of the process writes the variants of the records it writes, called on the device, as a
+    VCF to `path` (None: off); zeroes the counts."""
+    f = _host().wfmh_set_variants
+    f.restype = None
+    f.argtypes = [C.c_char_p]
+    f(os.fsencode(path) if path else None)
+
+
+def variants_counts():
+    """wfmh_variants_counts: (records called, variants written, SNVs masked, records left alone) since wfmh_set_variants was last called."""
+    f = _host().wfmh_variants_counts
+    f.restype = C.c_int
+    f.argtypes = [C.POINTER(C.c_uint64)]
+    out = (C.c_uint64 * 4)()
+    rc = f(out)
+    if rc != 0:
+        raise WfmError(f"wfmh_variants_counts failed ({rc})")
     return tuple(int(v) for v in out)
 
 

@@ -19,6 +19,7 @@
 
 #include "../../include/wfmash_hip.h"
 #include "wfa_device.h"
+#include "wfa_scan.h"
 
 namespace wfm {
 namespace {
@@ -27,30 +28,6 @@ constexpr int CS_THREADS = 256;
 constexpr int CS_WAVES = CS_THREADS / 64;
 constexpr int CS_WRITE_THREADS = 1024;  // cs_write_kernel: a slice is 16 rounds of one byte per lane (with 256 lanes a short-form call of few slices waited on 64)
 constexpr int CS_STAGE = 1024;  // run records staged at a time: 16 KB of LDS beside the slice's 16 KB
-
-__device__ __forceinline__ unsigned long long cs_shfl_up64(unsigned long long v, int d) {
-  const unsigned lo = __shfl_up((unsigned)v, d, 64), hi = __shfl_up((unsigned)(v >> 32), d, 64);
-  return ((unsigned long long)hi << 32) | lo;
-}
-
-// exclusive prefix of v over the workgroup's threads (in thread order) and the total; wtot: CS_WAVES words of LDS.  Two barriers.
-__device__ __forceinline__ unsigned long long cs_block_excl(unsigned long long v, unsigned long long* wtot, unsigned long long* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  unsigned long long incl = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const unsigned long long u = cs_shfl_up64(incl, d);
-    if (lane >= d) incl += u;
-  }
-  __syncthreads();  // (the words may still be read from the scan before)
-  if (lane == 63) wtot[wave] = incl;
-  __syncthreads();
-  unsigned long long before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < CS_WAVES; ++w) { if (w < wave) before += wtot[w]; all += wtot[w]; }
-  *total = all;
-  return before + incl - v;
-}
 
 __device__ __forceinline__ uint32_t cs_digits(uint32_t v) {  // v < 2^30: at most 10
   return 1u + (v >= 10u) + (v >= 100u) + (v >= 1000u) + (v >= 10000u) + (v >= 100000u) + (v >= 1000000u) + (v >= 10000000u) + (v >= 100000000u) +
@@ -96,9 +73,9 @@ __global__ __launch_bounds__(CS_THREADS) void cs_index_kernel(const uint32_t* __
     const unsigned long long ao = valid ? cs_run_bytes(op, len, form) : 0ull;
     if (valid && (len == 0 || (r > 0 && WFM_RUN_OP(my[r - 1]) == op))) bad = true;
     unsigned long long tp, tt, to;
-    const unsigned long long pp = carry_p + cs_block_excl(ap, wtot, &tp);
-    const unsigned long long tx = carry_t + cs_block_excl(at, wtot, &tt);
-    const unsigned long long oo = carry_o + cs_block_excl(ao, wtot, &to);
+    const unsigned long long pp = carry_p + block_excl<CS_WAVES>(ap, wtot, &tp);
+    const unsigned long long tx = carry_t + block_excl<CS_WAVES>(at, wtot, &tt);
+    const unsigned long long oo = carry_o + block_excl<CS_WAVES>(ao, wtot, &to);
     // (a problem whose totals pass its sequences' lengths, or 32 bits, is flagged below and its records are never read)
     if (valid) rec[r] = make_uint4((uint32_t)pp, (uint32_t)tx, (uint32_t)oo, run);
     carry_p += tp; carry_t += tt; carry_o += to;
@@ -144,15 +121,7 @@ __global__ __launch_bounds__(CS_WRITE_THREADS) void cs_write_kernel(const uint8_
   unsigned long long g = chunk_base + s0;
   const unsigned long long gend = chunk_base + s1;
   // the problem the slice begins in: the last k in [ka, kb) with goff[k] <= g (goff[kb] >= gend > g, so its own end lies behind g)
-  uint32_t k = ka;
-  {
-    uint32_t lo = ka, hi = kb;  // goff[lo] <= g < goff[hi]
-    while (hi - lo > 1) {
-      const uint32_t mid = lo + (hi - lo) / 2;
-      if (goff[mid] <= g) lo = mid; else hi = mid;
-    }
-    k = lo;
-  }
+  uint32_t k = last_le(ka, kb, [&](uint32_t i) { return goff[i] <= g; });  // goff[ka] <= g < goff[kb]
   while (g < gend) {  // (uniform over the workgroup)
     const unsigned long long pb = goff[k], pe = goff[k + 1];
     if (pe <= g) { ++k; continue; }  // a problem without a string
@@ -161,15 +130,7 @@ __global__ __launch_bounds__(CS_WRITE_THREADS) void cs_write_kernel(const uint8_
     const uint32_t n = pr.n_runs, rel = (uint32_t)(g - pb);
     // the run the byte g lies in: the last r with R[r].z <= rel.  Only where the slice begins inside a problem: behind that the walk
     // arrives at every run's first byte
-    uint32_t r0 = 0;
-    if (rel) {
-      uint32_t lo = 0, hi = n;
-      while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (R[mid].z <= rel) lo = mid; else hi = mid;
-      }
-      r0 = lo;
-    }
+    const uint32_t r0 = rel ? last_le(0u, n, [&](uint32_t i) { return R[i].z <= rel; }) : 0u;
     const uint32_t cnt = n - r0 < (uint32_t)CS_STAGE ? n - r0 : (uint32_t)CS_STAGE;
     __syncthreads();  // (the records of the round before are no longer read)
     for (uint32_t i = (uint32_t)tid; i < cnt; i += CS_WRITE_THREADS) s_rec[i] = R[r0 + i];
@@ -180,12 +141,7 @@ __global__ __launch_bounds__(CS_WRITE_THREADS) void cs_write_kernel(const uint8_
     const uint8_t* T = seq + pr.t_off;
     for (unsigned long long q = g + (unsigned long long)tid; q < seg_end; q += CS_WRITE_THREADS) {
       const uint32_t rq = (uint32_t)(q - pb);
-      uint32_t lo = 0, hi = cnt;  // s_rec[lo].z <= rq (< the offset behind the staged runs)
-      while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (s_rec[mid].z <= rq) lo = mid; else hi = mid;
-      }
-      const uint4 rc = s_rec[lo];
+      const uint4 rc = s_rec[last_le(0u, cnt, [&](uint32_t i) { return s_rec[i].z <= rq; })];  // s_rec[0].z <= rq (< the offset behind the staged runs)
       s_out[(uint32_t)(q - chunk_base - s0)] = cs_byte(rc.w, rq - rc.z, P + rc.x, T + rc.y, form);
     }
     g = seg_end;

@@ -273,6 +273,16 @@ void launch_cs_index(const uint32_t* runs, const CsProb* probs, int nprob, int f
 // which holds chunk_bytes rounded up to a multiple of WFM_CS_SLICE
 void launch_cs_write(const uint8_t* seq, const CsProb* probs, const void* recs, const unsigned long long* goff, uint32_t ka, uint32_t kb,
                      unsigned long long chunk_bytes, int form, uint8_t* out, hipStream_t st);
+// wfm_call_variants (wfa_variants.hip): the problems are CsProb as well.  recs: one uint4 per run of the problems that are not skipped
+// (pattern index, text index, offset of the run's allele bytes in the problem's, the run), rpre: the index of the run's first record in
+// the problem's; tot_bytes / tot_recs / end_gaps / flags: one per problem (a flagged problem's are 0)
+void launch_var_index(const uint32_t* runs, const CsProb* probs, int nprob, void* recs, uint32_t* rpre, unsigned long long* tot_bytes,
+                      unsigned long long* tot_recs, uint32_t* end_gaps, uint32_t* flags, hipStream_t st);
+// the problems [ka, kb): their chunk_bytes allele bytes behind goff[ka] into out, which holds chunk_bytes rounded up to a multiple of
+// WFM_VAR_SLICE, and their voff[kb] - voff[ka] records into vars, 32 bytes each (goff / voff: the n + 1 offsets of the call's problems)
+void launch_var_write(const uint8_t* seq, const CsProb* probs, const void* recs, const uint32_t* rpre, const unsigned long long* goff,
+                      const unsigned long long* voff, uint32_t ka, uint32_t kb, unsigned long long chunk_bytes, uint8_t* out, void* vars,
+                      hipStream_t st);
 // wfm_check_optimal (wfa_optcheck.hip): a problem's forward byte copies, its ends-free allowances (clamped; 0 for the other modes),
 // its band of diagonals (wfa_optband.h) and, for the memory form, where its three row arrays begin in `rows` (32-bit elements)
 struct OptProb {

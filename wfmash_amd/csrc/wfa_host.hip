@@ -285,6 +285,7 @@ struct wfm_handle {
   DevBuf<uint64_t> csbuf;            // wfm_cs_strings: the runs, their records, the problems and their offsets, carved out of one block
   DevBuf<uint64_t> csout;            // ... and the output block of one chunk of problems
   uint8_t* cspin[2] = {nullptr, nullptr};  // ... whose bytes reach the caller's buffer through these two pinned pieces (CS_PIN_PIECE each)
+  DevBuf<uint64_t> varbuf, varout;   // wfm_call_variants: the same two blocks (the output block: a chunk's records, then its alleles)
   DevBuf<int32_t> optrows;           // ... and the rows of the bands too wide for registers
   DevBuf<unsigned long long> total;
   void* attachment = nullptr;  // owned by another translation unit (map_kernels.hip: the pinned staging ring)
@@ -2223,7 +2224,7 @@ void wfm_destroy(wfm_handle_t* h) {
   h->p2rows.release(); h->p2max.release(); h->p2bmax.release(); h->p2pbmax.release(); h->p2jobs.release(); h->widenjobs.release(); h->keeptasks.release(); h->restoretasks.release(); h->restoreres.release();
   h->bpjobs.release(); h->bpres.release(); h->bsjobs.release(); h->bsres.release();
   h->b2tjobs.release(); h->b2ttasks.release(); h->b2tkeys.release(); h->b2toffs.release(); h->b2tactive.release();
-  h->i64a.release(); h->i64b.release(); h->i64c.release(); h->i32a.release(); h->seqflags.release(); h->flagjobs.release(); h->gathertasks.release(); h->checkbuf.release(); h->optbuf.release(); h->labuf.release(); h->csbuf.release(); h->csout.release(); h->optrows.release(); h->total.release();
+  h->i64a.release(); h->i64b.release(); h->i64c.release(); h->i32a.release(); h->seqflags.release(); h->flagjobs.release(); h->gathertasks.release(); h->checkbuf.release(); h->optbuf.release(); h->labuf.release(); h->csbuf.release(); h->csout.release(); h->varbuf.release(); h->varout.release(); h->optrows.release(); h->total.release();
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->ev2) (void)hipEventDestroy(h->ev2);
@@ -2840,6 +2841,38 @@ int wfm_left_align_runs(wfm_handle_t* h, const wfm_seqset_t* s, wfm_result_t* re
   return spans;
 }
 
+// ---- how the output blocks of wfm_cs_strings and wfm_call_variants reach the caller's buffer ----
+namespace {
+constexpr size_t CS_PIN_PIECE = (size_t)4 << 20;
+
+// the handle's two pinned pieces, allocated at first use; false: there are none, and a block goes down in one pageable copy
+bool cs_pin_pieces(wfm_handle_t* h) {
+  for (int k = 0; k < 2; ++k)
+    if (!h->cspin[k] && hipHostMalloc((void**)&h->cspin[k], CS_PIN_PIECE, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); h->cspin[k] = nullptr; return false; }
+  return true;
+}
+
+// bytes of the device block src to dst, finished on return.  Down in pieces through the two pinned buffers: piece j + 1 crosses PCIe while
+// piece j is copied to its place (one pageable hipMemcpy of a fresh block took 2 ms for 3.7 MB, and 18 - 28 ms every other call:
+// profiles/cs_tag.md)
+hipError_t cs_copy_down(wfm_handle_t* h, bool pinned, char* dst, const uint8_t* src, size_t bytes) {
+  if (bytes == 0) return hipSuccess;
+  hipError_t e = hipSuccess;
+  const size_t pieces = pinned ? (bytes + CS_PIN_PIECE - 1) / CS_PIN_PIECE : 0;
+  auto piece_len = [&](size_t j) { return std::min<size_t>(CS_PIN_PIECE, bytes - j * CS_PIN_PIECE); };
+  if (!pinned) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream);
+  if (pinned) e = hipMemcpyAsync(h->cspin[0], src, piece_len(0), hipMemcpyDeviceToHost, h->stream);
+  for (size_t j = 0; j < pieces && e == hipSuccess; ++j) {
+    e = hipStreamSynchronize(h->stream);
+    if (e == hipSuccess && j + 1 < pieces)
+      e = hipMemcpyAsync(h->cspin[(j + 1) & 1], src + (j + 1) * CS_PIN_PIECE, piece_len(j + 1), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) memcpy(dst + j * CS_PIN_PIECE, h->cspin[j & 1], piece_len(j));
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  return e;
+}
+}  // namespace
+
 // ---- the cs difference string of every problem's runs (wfmash_hip.h; the kernels: wfa_cs.hip) ----
 int wfm_cs_strings(wfm_handle_t* h, const wfm_seqset_t* s, const wfm_result_t* res, const uint32_t* runs, size_t n_runs_total, int form, char** out,
                    size_t* out_bytes, wfm_cs_t* per) {
@@ -2915,10 +2948,7 @@ int wfm_cs_strings(wfm_handle_t* h, const wfm_seqset_t* s, const wfm_result_t* r
   if (!host) { (void)hipStreamSynchronize(h->stream); h->err = "out of host memory (cs)"; return WFM_E_NOMEM; }
   // chunks of problems whose strings fit the output block (a problem larger than that is a chunk of its own)
   const unsigned long long cap = (unsigned long long)std::max(1, env_num("WFM_CS_OUT_MB", 256)) << 20;
-  constexpr size_t CS_PIN_PIECE = (size_t)4 << 20;
-  bool pinned = true;  // (without the pinned pieces the block goes down in one pageable copy)
-  for (int k = 0; k < 2 && pinned; ++k)
-    if (!h->cspin[k] && hipHostMalloc((void**)&h->cspin[k], CS_PIN_PIECE, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); h->cspin[k] = nullptr; pinned = false; }
+  const bool pinned = cs_pin_pieces(h);
   size_t chunks = 0;
   for (size_t ka = 0; ka < n;) {
     size_t kb = ka + 1;
@@ -2934,20 +2964,7 @@ int wfm_cs_strings(wfm_handle_t* h, const wfm_seqset_t* s, const wfm_result_t* r
         launch_cs_write(s->d_seq, d_probs, d_recs, d_goff, (uint32_t)ka, (uint32_t)kb, bytes, form, (uint8_t*)h->csout.p, h->stream);
         e = hipGetLastError();
         if (dbg) (void)hipEventRecord(h->ev1, h->stream);
-        // down in pieces through the two pinned buffers: piece j + 1 crosses PCIe while piece j is copied to its place (one pageable
-        // hipMemcpy of a fresh block took 2 ms for 3.7 MB, and 18 - 28 ms every other call: profiles/cs_tag.md)
-        const uint8_t* d_block = (const uint8_t*)h->csout.p;
-        const size_t pieces = pinned ? ((size_t)bytes + CS_PIN_PIECE - 1) / CS_PIN_PIECE : 0;
-        auto piece_len = [&](size_t j) { return std::min<size_t>(CS_PIN_PIECE, (size_t)bytes - j * CS_PIN_PIECE); };
-        if (!pinned && e == hipSuccess) e = hipMemcpyAsync(host + goff[ka], d_block, (size_t)bytes, hipMemcpyDeviceToHost, h->stream);
-        if (pinned && e == hipSuccess) e = hipMemcpyAsync(h->cspin[0], d_block, piece_len(0), hipMemcpyDeviceToHost, h->stream);
-        for (size_t j = 0; j < pieces && e == hipSuccess; ++j) {
-          e = hipStreamSynchronize(h->stream);
-          if (e == hipSuccess && j + 1 < pieces)
-            e = hipMemcpyAsync(h->cspin[(j + 1) & 1], d_block + (j + 1) * CS_PIN_PIECE, piece_len(j + 1), hipMemcpyDeviceToHost, h->stream);
-          if (e == hipSuccess) memcpy(host + goff[ka] + j * CS_PIN_PIECE, h->cspin[j & 1], piece_len(j));
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);  // (the block is the next chunk's)
+        if (e == hipSuccess) e = cs_copy_down(h, pinned, host + goff[ka], (const uint8_t*)h->csout.p, (size_t)bytes);  // (the block is the next chunk's)
         if (e != hipSuccess) { h->err = std::string("wfm_cs_strings: ") + hipGetErrorString(e); rc = WFM_E_HIP; }
       }
       if (rc != WFM_OK) { free(host); return rc; }
@@ -2969,6 +2986,134 @@ int wfm_cs_strings(wfm_handle_t* h, const wfm_seqset_t* s, const wfm_result_t* r
 }
 
 void wfm_free_cs(char* p) { free(p); }
+
+// ---- the variants of every problem's runs (wfmash_hip.h; the kernels: wfa_variants.hip) ----
+int wfm_call_variants(wfm_handle_t* h, const wfm_seqset_t* s, const wfm_result_t* res, const uint32_t* runs, size_t n_runs_total, wfm_variant_t** vars,
+                      size_t* n_vars, char** alleles, size_t* allele_bytes, wfm_varcall_t* per) {
+  if (!h || !s || !vars || !n_vars || !alleles || !allele_bytes || (n_runs_total && !runs)) return WFM_E_ARG;
+  *vars = nullptr; *alleles = nullptr;
+  *n_vars = 0; *allele_bytes = 0;
+  const auto t_call = std::chrono::steady_clock::now();
+  const size_t n = s->meta.size();
+  if (n == 0) return WFM_OK;
+  if (!res || !per) return WFM_E_ARG;
+  if (n > (size_t)INT32_MAX || n_runs_total > ((size_t)1 << 31)) { h->err = "wfm_call_variants: too many problems or runs for one call"; return WFM_E_ARG; }
+  HIPCHK(h, hipSetDevice(h->device));
+  // the problems as the kernels see them (wfm_cs_strings'); the run ranges are validated here, before anything is launched
+  std::vector<CsProb> probs(n);
+  uint64_t rec_total = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const ProbMeta& m = s->meta[i];
+    CsProb& c = probs[i];
+    memset(&c, 0, sizeof(c));
+    c.p_off = m.p_fwd; c.t_off = m.t_fwd;
+    c.plen = m.plen; c.tlen = m.tlen;
+    c.skip = (m.score_only() || res[i].status != 0 || res[i].n_runs == 0) ? 1 : 0;
+    if (c.skip) continue;
+    if (!(res[i].ops_off <= n_runs_total && (uint64_t)res[i].n_runs <= n_runs_total - res[i].ops_off)) {
+      h->err = "problem " + std::to_string(i) + ": its runs leave the run buffer";
+      return WFM_E_ARG;
+    }
+    c.run_off = res[i].ops_off; c.n_runs = res[i].n_runs;
+    c.rec_off = rec_total;
+    rec_total += c.n_runs;
+  }
+  // one block: [run records] 16 bytes per run, [offsets of the alleles] and [of the records] n + 1 each, [totals of both] n each of 8 bytes,
+  // [problems], [runs], [record prefixes] one word per run, [flags], [end gaps]
+  auto words64 = [](size_t bytes) { return (bytes + 7) / 8; };
+  const size_t nr = n_runs_total;
+  const size_t w_recs = 2 * (size_t)rec_total, w_off = n + 1, w_tot = n, w_probs = words64(n * sizeof(CsProb)), w_runs = words64(nr * 4),
+               w_rpre = words64((size_t)rec_total * 4), w_flags = words64(n * 4);
+  if (h->varbuf.ensure(w_recs + 2 * w_off + 2 * w_tot + w_probs + w_runs + w_rpre + 2 * w_flags + 8)) { h->err = "out of device memory (variants)"; return WFM_E_NOMEM; }
+  uint64_t* at = h->varbuf.p;
+  void* d_recs = at; at += w_recs;
+  unsigned long long* d_goff = (unsigned long long*)at; at += w_off;
+  unsigned long long* d_voff = (unsigned long long*)at; at += w_off;
+  unsigned long long* d_totb = (unsigned long long*)at; at += w_tot;
+  unsigned long long* d_totr = (unsigned long long*)at; at += w_tot;
+  CsProb* d_probs = (CsProb*)at; at += w_probs;
+  uint32_t* d_runs = (uint32_t*)at; at += w_runs;
+  uint32_t* d_rpre = (uint32_t*)at; at += w_rpre;
+  uint32_t* d_flags = (uint32_t*)at; at += w_flags;
+  uint32_t* d_ends = (uint32_t*)at;
+  if (nr) HIPCHK(h, hipMemcpyAsync(d_runs, runs, nr * 4, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(d_probs, probs.data(), n * sizeof(CsProb), hipMemcpyHostToDevice, h->stream));
+  const int dbg = env_debug();
+  if (dbg) HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+  launch_var_index(d_runs, d_probs, (int)n, d_recs, d_rpre, d_totb, d_totr, d_ends, d_flags, h->stream);
+  HIPCHK(h, hipGetLastError());
+  if (dbg) HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+  // the problems' totals, once: the host sizes the outputs and takes the two prefix sums
+  std::vector<unsigned long long> goff(n + 1), voff(n + 1);
+  std::vector<uint32_t> flags(n), ends(n);
+  HIPCHK(h, hipMemcpyAsync(goff.data() + 1, d_totb, n * 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(voff.data() + 1, d_totr, n * 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(flags.data(), d_flags, n * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(ends.data(), d_ends, n * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  float ms_index = 0, ms_write = 0;
+  if (dbg && hipEventElapsedTime(&ms_index, h->ev0, h->ev1) != hipSuccess) (void)hipGetLastError();
+  goff[0] = 0; voff[0] = 0;
+  int spans = 0;
+  for (size_t i = 0; i < n; ++i) {
+    per[i].flags = flags[i]; per[i].n_runs = probs[i].n_runs;
+    per[i].first = voff[i]; per[i].count = voff[i + 1];
+    per[i].end_gaps = ends[i]; per[i].pad_ = 0;
+    goff[i + 1] += goff[i]; voff[i + 1] += voff[i];
+    spans += (flags[i] & WFM_VAR_SPANS) != 0;
+  }
+  const unsigned long long total = goff[n], total_vars = voff[n];
+  if (total == 0) return spans;  // (a record has allele bytes: no bytes, no records)
+  HIPCHK(h, hipMemcpyAsync(d_goff, goff.data(), (n + 1) * 8, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(d_voff, voff.data(), (n + 1) * 8, hipMemcpyHostToDevice, h->stream));
+  char* host = (char*)malloc((size_t)total);
+  wfm_variant_t* host_vars = (wfm_variant_t*)malloc((size_t)total_vars * sizeof(wfm_variant_t));
+  if (!host || !host_vars) { (void)hipStreamSynchronize(h->stream); free(host); free(host_vars); h->err = "out of host memory (variants)"; return WFM_E_NOMEM; }
+  // chunks of problems whose records and alleles fit the output block (a problem larger than that is a chunk of its own)
+  const unsigned long long cap = (unsigned long long)std::max(1, env_num("WFM_VAR_OUT_MB", 256)) << 20;
+  auto cost = [&](size_t ka, size_t kb) { return (goff[kb] - goff[ka]) + (voff[kb] - voff[ka]) * sizeof(wfm_variant_t); };
+  const bool pinned = cs_pin_pieces(h);
+  size_t chunks = 0;
+  for (size_t ka = 0; ka < n;) {
+    size_t kb = ka + 1;
+    while (kb < n && cost(ka, kb + 1) <= cap) ++kb;
+    const unsigned long long bytes = goff[kb] - goff[ka];
+    if (bytes) {
+      // the block: the chunk's records, then its alleles in whole slices
+      const size_t rec_bytes = (size_t)(voff[kb] - voff[ka]) * sizeof(wfm_variant_t);
+      const size_t block = rec_bytes + (size_t)((bytes + WFM_VAR_SLICE - 1) / WFM_VAR_SLICE) * WFM_VAR_SLICE;
+      int rc = WFM_OK;
+      if (h->varout.ensure(block / 8)) { h->err = "out of device memory (variants output)"; rc = WFM_E_NOMEM; }
+      if (rc == WFM_OK) {
+        uint8_t* d_vars = (uint8_t*)h->varout.p;
+        uint8_t* d_all = d_vars + rec_bytes;
+        if (dbg) (void)hipEventRecord(h->ev0, h->stream);
+        launch_var_write(s->d_seq, d_probs, d_recs, d_rpre, d_goff, d_voff, (uint32_t)ka, (uint32_t)kb, bytes, d_all, d_vars, h->stream);
+        hipError_t e = hipGetLastError();
+        if (dbg) (void)hipEventRecord(h->ev1, h->stream);
+        if (e == hipSuccess) e = cs_copy_down(h, pinned, (char*)(host_vars + voff[ka]), d_vars, rec_bytes);
+        if (e == hipSuccess) e = cs_copy_down(h, pinned, host + goff[ka], d_all, (size_t)bytes);  // (the block is the next chunk's)
+        if (e != hipSuccess) { h->err = std::string("wfm_call_variants: ") + hipGetErrorString(e); rc = WFM_E_HIP; }
+      }
+      if (rc != WFM_OK) { free(host); free(host_vars); return rc; }
+      if (dbg) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess) ms_write += ms; else (void)hipGetLastError();
+      }
+      ++chunks;
+    }
+    ka = kb;
+  }
+  *vars = host_vars; *n_vars = (size_t)total_vars;
+  *alleles = host; *allele_bytes = (size_t)total;
+  if (dbg)
+    fprintf(stderr, "[wfm] variants: %zu problems, %zu runs, %llu records, %llu allele bytes in %zu chunks, index %.3f ms, write %.3f ms (device events), the call %.3f ms (host clock)\n",
+            n, (size_t)rec_total, total_vars, total, chunks, ms_index, ms_write,
+            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count());
+  return spans;
+}
+
+void wfm_free_variants(wfm_variant_t* vars, char* alleles) { free(vars); free(alleles); }
 
 // ---- every score proved optimal by a banded DP (wfmash_hip.h; the band: wfa_optband.h; the kernel: wfa_optcheck.hip) ----
 int wfm_check_optimal(wfm_handle_t* h, const wfm_penalties_t* pen, const wfm_seqset_t* s, const wfm_result_t* res, uint64_t max_cells,

@@ -378,7 +378,8 @@ std::string Aligner::gather_text(Summary& sum, const std::vector<Fetched>& fetch
   return out;
 }
 
-std::string Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<std::string>& lines, int threads, Summary& sum, uint64_t first_row) {
+std::string Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<std::string>& lines, int threads, Summary& sum, uint64_t first_row,
+                                 std::string* vcf) {
   const bool dbg = getenv("WFM_DEBUG") != nullptr;
   BatchTimes t;
   std::vector<Fetched> rows = parse_rows(lines, first_row, sum);
@@ -409,6 +410,8 @@ std::string Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<std::stri
   account(sum, st, resident, fetched, recs);
   t.wflign = t.lap();
   std::string out = gather_text(sum, fetched, recs);
+  if (vcf)
+    for (const auto& r : recs) *vcf += r.vcf;  // (a record without a line has no VCF lines: write_record)
   t.text = t.lap();
   if (verify::enabled() && !param.sam_format) {  // --verify: the finished lines, before they are written (SAM records carry no =/X CIGAR)
     verify::Source src;
@@ -518,6 +521,7 @@ struct Aligner::Run {
   const Clock::time_point t0;
   std::ifstream& in;
   skch::OrderedWriter<std::string, TextSink> writer;
+  std::unique_ptr<skch::OrderedWriter<std::string, TextSink>> vcf_writer;  // --variants: the second file, keyed by the same batch numbers
   std::mutex read_mu;
   uint64_t next_seq = 0;   // (under read_mu) the next batch's number
   uint64_t rows_read = 0;  // (under read_mu) non-empty rows handed out so far
@@ -605,9 +609,11 @@ void Aligner::run_worker(Run& run, size_t wk) {
       { std::lock_guard<std::mutex> lk(run.read_mu); more = run.more_rows; beside = run.in_flight[dev].fetch_add(1); }
       wfm_set_concurrent_calls(run.use[wk], beside + (more && run.plan.per_gpu > 1 ? 1 : 0));
       struct Leave { std::atomic<int>& a; ~Leave() { a.fetch_sub(1); } } leave{run.in_flight[dev]};
-      std::string text = align_batch(run.use[wk], batch, run.threads_each, run.part[wk], first_row);
+      std::string vcf;
+      std::string text = align_batch(run.use[wk], batch, run.threads_each, run.part[wk], first_row, run.vcf_writer ? &vcf : nullptr);
       const double at1 = run.ms();
       run.writer.put((uint64_t)seq, std::move(text));
+      if (run.vcf_writer) run.vcf_writer->put((uint64_t)seq, std::move(vcf));
       if (getenv("WFM_DEBUG"))
         fprintf(stderr, "[wfmash::align] worker %zu: batch %lld from +%.0f ms to +%.0f ms, written at +%.0f ms\n", wk, (long long)seq, at0, at1, run.ms());
     }
@@ -665,6 +671,20 @@ Summary Aligner::compute() {
   }
   const size_t ngpu = gpus.size();
   Run run(param, plan_run(in), ngpu, t0, in, outstream);
+  std::ofstream vcfstream;
+  const std::string vcf_path = wflign::variants_path();
+  if (!vcf_path.empty()) {  // --variants: the header here, the batches' lines through a second ordered writer
+    vcfstream.open(vcf_path);
+    if (!vcfstream.is_open()) throw std::runtime_error("[wfmash::align] Error! Failed to open the variants file: " + vcf_path);
+    vcfstream << "##fileformat=VCFv4.2\n##source=wfmash-hip " WFMASH_HIP_VERSION "\n";
+    for (int i = 0; i < ref->nseq(); ++i) vcfstream << "##contig=<ID=" << ref->name(i) << ",length=" << ref->length(i) << ">\n";
+    vcfstream << "##INFO=<ID=QNAME,Number=1,Type=String,Description=\"Query sequence name\">\n"
+                 "##INFO=<ID=QSTART,Number=1,Type=Integer,Description=\"Start of the query bases in ALT, 0-based, forward strand\">\n"
+                 "##INFO=<ID=QEND,Number=1,Type=Integer,Description=\"End of the query bases in ALT, exclusive, forward strand\">\n"
+                 "##INFO=<ID=QSTRAND,Number=1,Type=String,Description=\"Strand of the query in the alignment\">\n"
+                 "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n";
+    run.vcf_writer.reset(new skch::OrderedWriter<std::string, TextSink>(TextSink{&vcfstream}));
+  }
   const size_t nworkers = run.plan.nworkers;
   static const bool own_handles = !(getenv("WFM_ALIGN_OWN_HANDLES") && atoi(getenv("WFM_ALIGN_OWN_HANDLES")) == 0);
   static HandlePool pool;
@@ -683,6 +703,7 @@ Summary Aligner::compute() {
   if (run.failed.load()) throw std::runtime_error(run.first_error);
   sum_up(sum, run.part, t0);
   outstream.close();
+  if (vcfstream.is_open()) vcfstream.close();
   sum.ms_total = ms_since(t0);
   std::cerr << "[wfmash::align] total aligned records = " << sum.records << ", total aligned bp = " << sum.aligned_bp
             << ", completed in " << (uint64_t)(sum.ms_total / 1000.0) << " seconds" << std::endl;

@@ -104,7 +104,9 @@ class Aligner {
   // ---- one batch of mapping rows on one handle (aligner.cpp: align_batch and its stages) ----
   struct Fetched;     // a row, its windows and where its sides are
   struct BatchTimes;  // the stages' times, into the Summary at the end
-  std::string align_batch(wfm_handle_t* gpu, std::vector<std::string>& lines, int threads, Summary& sum, uint64_t first_row = 0);
+  // (vcf: where the VCF lines of the records written go, --variants; null: nowhere)
+  std::string align_batch(wfm_handle_t* gpu, std::vector<std::string>& lines, int threads, Summary& sum, uint64_t first_row = 0,
+                          std::string* vcf = nullptr);
   std::vector<Fetched> parse_rows(std::vector<std::string>& lines, uint64_t first_row, Summary& sum) const;
   void fetch_windows(Fetched& f) const;
   std::vector<Fetched> fetch_eager(std::vector<Fetched>& rows, int threads, Summary& sum) const;

@@ -37,6 +37,13 @@
 //                                              of a line changes; allowed with -a, -d, -i, -K, --gpus, --resident-seqs, --verify,
 //                                              --verify-optimal and --left-align (the string is then that of the normalised runs),
 //                                              refused with -m and --verify-paf; off by default
+//   --variants FILE                            the substitutions, insertions and deletions of every record written, as a VCF: called on
+//                                              the device from the runs the record spells, alleles included (wfm_call_variants); one line
+//                                              per variant in PAF record order, ascending POS within a record, alleles on the target's
+//                                              strand, INFO = QNAME, QSTART, QEND, QSTRAND; not sorted across records, no sample columns
+//                                              (bcftools sort); no output byte of the PAF or SAM changes; allowed with -a, -d, -i, -K,
+//                                              --gpus, --resident-seqs, --verify, --verify-optimal, --left-align (the variants are then
+//                                              those of the normalised runs) and --cs, refused with -m and --verify-paf; off by default
 //   --verify-paf FILE target.fa [query.fa]     the same check on an existing aligned PAF (this build's or the reference's): no mapping,
 //                                              no alignment; exit status 3 if a line fails
 //   --ani-matrix FILE [--ani-only]             the group-by-group ANI table the identity estimate (-p aniN) is made from, as TSV: per
@@ -128,6 +135,7 @@ static void usage() {
           "            --verify-optimal-cells N skip problems whose band holds more than N DP cells [no cap]\n"
           "            --left-align move every interior gap of the final CIGARs to its leftmost placement on the GPU (only cg:Z: / CIGAR and MD change; not with -m)\n"
           "            --cs[=short|=long] append minimap2's cs:Z: difference string, spelled on the GPU, to every PAF line / SAM record (not with -m, --verify-paf)\n"
+          "            --variants FILE write the SNVs, insertions and deletions of every record, called on the GPU, as a VCF (unsorted; not with -m, --verify-paf)\n"
           "            --verify-paf FILE check an existing aligned PAF against target.fa [query.fa] and stop (exit status 3 if a line fails)\n"
           "  other     --out FILE [stdout]   --device INT [0]   --gpus N|all [1] GPUs of this node, starting at --device\n"
           "            -B DIR directory of the hand-off file [cwd]   -Z keep the hand-off file   --quiet (no effect)\n");
@@ -139,7 +147,7 @@ int main(int argc, char** argv) {
   ap.threads = 1;  // -t, default 1 as in the reference (parse_args.hpp: thread_count); the C ABI default (0) means all cores
   wfmh_map_params_t mp;
   wfmh_map_default_params(&mp);
-  std::string mapping_in, out = "/dev/stdout", target, query, seeds_in, scaffold_out, tmp_base, verify_in, ani_matrix_out;
+  std::string mapping_in, out = "/dev/stdout", target, query, seeds_in, scaffold_out, tmp_base, verify_in, ani_matrix_out, variants_out;
   bool verify = false, verify_optimal = false, ani_only = false, left_align = false;
   uint64_t verify_optimal_cells = 0;
   int cs_form = 0;  // --cs: 0 off, 1 short, 2 long
@@ -279,6 +287,7 @@ int main(int argc, char** argv) {
     else if (a == "--cs" || a == "--cs=short") cs_form = 1;
     else if (a == "--cs=long") cs_form = 2;
     else if (a.compare(0, 5, "--cs=") == 0) { fprintf(stderr, "[wfmash] ERROR: --cs takes =short or =long, not '%s'\n", a.c_str() + 5); return 1; }
+    else if (a == "--variants") variants_out = next("--variants");
     else if (a == "--verify-optimal-cells") verify_optimal_cells = std::strtoull(next("--verify-optimal-cells").c_str(), nullptr, 10);
     else if (a == "--verify-paf") verify_in = next("--verify-paf");
     else if (a == "-h" || a == "--help") { usage(); return 0; }
@@ -292,6 +301,8 @@ int main(int argc, char** argv) {
   if (left_align && approx_only) { fprintf(stderr, "[wfmash] ERROR: --left-align normalises alignments: it cannot be combined with -m\n"); return 1; }
   if (cs_form && approx_only) { fprintf(stderr, "[wfmash] ERROR: --cs spells alignments: it cannot be combined with -m\n"); return 1; }
   if (cs_form && !verify_in.empty()) { fprintf(stderr, "[wfmash] ERROR: --cs belongs to the align phase: it cannot be combined with --verify-paf\n"); return 1; }
+  if (!variants_out.empty() && approx_only) { fprintf(stderr, "[wfmash] ERROR: --variants calls alignments: it cannot be combined with -m\n"); return 1; }
+  if (!variants_out.empty() && !verify_in.empty()) { fprintf(stderr, "[wfmash] ERROR: --variants belongs to the align phase: it cannot be combined with --verify-paf\n"); return 1; }
   if (verify_optimal && approx_only) { fprintf(stderr, "[wfmash] ERROR: --verify-optimal checks alignment scores: it cannot be combined with -m\n"); return 1; }
   if (verify_optimal_cells && !verify_optimal) { fprintf(stderr, "[wfmash] ERROR: --verify-optimal-cells needs --verify-optimal\n"); return 1; }
   if (ani_only && ani_matrix_out.empty()) { fprintf(stderr, "[wfmash] ERROR: --ani-only needs --ani-matrix FILE\n"); return 1; }
@@ -423,6 +434,7 @@ int main(int argc, char** argv) {
     if (verify_optimal) wfmh_set_verify_optimal(1, verify_optimal_cells);
     if (left_align) wfmh_set_left_align(1);
     if (cs_form) wfmh_set_cs(cs_form);
+    if (!variants_out.empty()) wfmh_set_variants(variants_out.c_str());
     rc = wfmh_align_paf_multi(hs.data(), (int)hs.size(), target.c_str(), q, mapping.c_str(), out.c_str(), &ap, &s);
     if (rc == WFM_OK)
       fprintf(stderr, "[wfmash::align] %llu records, %llu aligned bp, %.1f ms GPU kernels, %.1f ms total => %.3g aligned bp/s\n",
@@ -439,6 +451,12 @@ int main(int argc, char** argv) {
       wfmh_cs_counts(cc);
       fprintf(stderr, "[wfmash::cs] %llu records, %llu bytes (%s), %llu records left without a string\n", (unsigned long long)cc[0], (unsigned long long)cc[1],
               cs_form == 2 ? "long" : "short", (unsigned long long)cc[2]);
+    }
+    if (!variants_out.empty() && rc == WFM_OK) {
+      uint64_t vc[4] = {0, 0, 0, 0};
+      wfmh_variants_counts(vc);
+      fprintf(stderr, "[wfmash::variants] %llu records, %llu variants written, %llu SNVs masked, %llu records left alone\n", (unsigned long long)vc[0],
+              (unsigned long long)vc[1], (unsigned long long)vc[2], (unsigned long long)vc[3]);
     }
     if (verify && rc == WFM_OK) {  // everything has been written by now
       uint64_t vc[4] = {0, 0, 0, 0};

@@ -57,6 +57,13 @@ std::atomic<uint64_t> g_left_align_counts[4];
 std::atomic<int> g_cs{0};
 std::atomic<uint64_t> g_cs_counts[4];
 
+// --variants: the process-wide switch, the file the align phase writes and {records called, variants written, SNVs masked, records left
+// alone} since it was set
+std::atomic<bool> g_variants{false};
+std::mutex g_variants_mu;
+std::string g_variants_path;
+std::atomic<uint64_t> g_variants_counts[4];
+
 // The problems of one device call, always written by reference (a side without a store id carries its host pointer); without a
 // store they go to the device as plain wfm_problem_t, as they always have.
 struct GpuBatch {
@@ -203,7 +210,7 @@ wfm_problem_ref_t tail_problem(const BiwfaRecord& r, const Erosion& e) {  // wfl
 using Clock = std::chrono::steady_clock;
 double ms_between(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
 
-struct WindowSet;  // the records' final runs as device problems (left_align_records, cs_records)
+struct WindowSet;  // the records' final runs as device problems (left_align_records, cs_records, variant_records)
 
 // One call of do_biwfa_alignment_batch: what its stages share.
 struct BiwfaBatch {
@@ -225,7 +232,8 @@ struct BiwfaBatch {
   size_t later = 0;               // records whose tail is scanned on the head-patched CIGAR
   std::atomic<uint64_t> n_head{0}, n_tail{0};
   int cs_form = 0;                // --cs as the batch found it: 0 off, 1 short, 2 long
-  std::unique_ptr<WindowSet> windows;  // what left_align_records leaves for cs_records
+  bool variants = false;          // --variants as the batch found it
+  std::unique_ptr<WindowSet> windows;  // what left_align_records leaves for cs_records and variant_records, and cs_records for variant_records
   // the handle's message was copied while the handle was still this thread's (another batch may be using it by now)
   int fail(const GpuBatch& g, int rc) const { if (stats) stats->error = g.err; return rc; }
 };
@@ -253,6 +261,8 @@ int align_main(BiwfaBatch& b, bool plan) {
     r.tags = g.flags[i] & 0xffu;
     r.paf.clear();
     r.cs.clear();
+    r.vcf.clear();
+    r.vcf_called = false; r.vcf_masked = 0;
     r.ops.clear();
     if (!r.ok) return;
     g.ops(i, r.ops);
@@ -366,7 +376,7 @@ void swizzle(BiwfaBatch& b, size_t ri) {
   }
 }
 
-// ---- the records' final runs as device problems of their own: what --left-align and --cs work on.  What goes to the device is what the
+// ---- the records' final runs as device problems of their own: what --left-align, --cs and --variants work on.  What goes to the device is what the
 // writers spell: both of them begin by stripping the leading and trailing I and D runs and shifting the start coordinates
 // (trim_and_filter), so a record's problem is the runs ops[b, e) that remain against the sub-windows they cover.  Records go by reference
 // where the batch has a store.  The ops of an ok record always span its windows (an end-to-end alignment does, a patch replaces eroded
@@ -380,7 +390,7 @@ struct WindowSet {
   uint32_t* la_runs = nullptr;     // wfm_left_align_runs' output once it has run: res locates the parts there from then on
   size_t n_la_runs = 0;
   size_t unknown = 0;              // records with an op or a length the device's runs cannot hold: left out
-  wfm_seqset_t* S = nullptr;       // the sub-windows on the device, uploaded once for both calls
+  wfm_seqset_t* S = nullptr;       // the sub-windows on the device, uploaded once for all the calls
   const uint32_t* cur() const { return la_runs ? la_runs : runs.data(); }
   size_t n_cur() const { return la_runs ? n_la_runs : runs.size(); }
 };
@@ -441,8 +451,8 @@ void release_windows(BiwfaBatch& b) {
 // ---- --left-align: the interior gaps of every record's final ops moved to their leftmost placement, ONE device call per batch
 // (wfm_left_align_runs).  The line's first and last runs are the problem's first and last, which the rule never touches -- no
 // coordinate moves, and the CIGAR of the line is the rule applied to the line.  A record left alone is a defect; it is written as it is
-// and counted.  Alone, the stage takes the records with an interior run; with --cs as well (keep) it takes every record cs_records
-// will spell, and leaves the uploaded windows and the new runs in b.windows for it. ----
+// and counted.  Alone, the stage takes the records with an interior run; with --cs or --variants as well (keep) it takes every record
+// those stages will work on, and leaves the uploaded windows and the new runs in b.windows for them. ----
 int left_align_records(BiwfaBatch& b, bool keep) {
   const auto t0 = Clock::now();
   b.windows = window_parts(b, keep ? 1 : 3);
@@ -515,6 +525,76 @@ int cs_records(BiwfaBatch& b) {
   return 0;
 }
 
+// ---- --variants: the VCF lines of every record's line, ONE device call per batch (wfm_call_variants) on the runs the line spells --
+// behind left_align_records the normalised ones -- on the windows the stages before uploaded, if any did.  Every ok record whose trimmed
+// part is not empty takes part; a part begins and ends with an = or X run, so it has no end gaps and every gap of it is called.  The
+// line's coordinates are the writer's (write_alignment_paf): POS = the target start it writes + p + 1; [QSTART, QEND) = the span
+// [t, t + n) of the line's text -- n = 1 for an SNV, the inserted bases for an INS, 0 for a DEL -- on the query's forward strand.  Masked
+// SNVs are left out and counted.  A record the device flags is a defect: it has no lines and is counted. ----
+int variant_records(BiwfaBatch& b) {
+  const auto t0 = Clock::now();
+  if (!b.windows) b.windows = window_parts(b, 1);
+  WindowSet& w = *b.windows;
+  if (w.parts.empty()) return 0;
+  const size_t n = w.parts.size();
+  std::vector<wfm_varcall_t> per(n);
+  wfm_variant_t* vars = nullptr;
+  char* alleles = nullptr;
+  size_t n_vars = 0, bytes = 0;
+  int rc = WFM_OK;
+  auto t1 = t0;
+  {
+    std::lock_guard<std::mutex> lk(handle_lock(b.h));
+    if (!w.S) rc = upload_windows(b, w);
+    t1 = Clock::now();
+    if (rc == WFM_OK) rc = wfm_call_variants(b.h, w.S, w.res.data(), w.cur(), w.n_cur(), &vars, &n_vars, &alleles, &bytes, per.data());
+    if (rc < 0 && b.stats) b.stats->error = wfm_last_error(b.h);
+  }
+  if (rc < 0) return rc;
+  const auto t2 = Clock::now();
+  for_each_record(n, b.fmt.threads, [&](size_t j) {
+    if (per[j].flags) return;
+    const WindowSet::Part& pt = w.parts[j];
+    BiwfaRecord& r = b.recs[pt.rec];
+    r.vcf_called = true;
+    // where the part begins in the record's windows, as trim_and_filter will find it
+    uint64_t ta = 0, qa = 0;
+    for (size_t k = 0; k < pt.b; ++k) (r.ops[k].second == 'I' ? qa : ta) += (uint64_t)r.ops[k].first;
+    const uint64_t ts = r.target_offset + ta, q_len = (uint64_t)w.probs[j].tlen;
+    const uint64_t qs = r.query_is_rev ? r.query_offset + (r.query_length - qa - q_len) : r.query_offset + qa, qe = qs + q_len;
+    std::string tail = "\t.\t.\tQNAME=" + r.query_name + ";QSTART=";
+    char num[64];
+    for (uint64_t k = per[j].first; k < per[j].first + per[j].count; ++k) {
+      const wfm_variant_t& v = vars[k];
+      if (v.kind & WFM_VAR_MASKED) { ++r.vcf_masked; continue; }
+      const uint32_t kind = v.kind & 255u;
+      const uint64_t span = kind == WFM_VAR_SNV ? 1u : kind == WFM_VAR_INS ? v.alt_len - 1u : 0u;
+      const uint64_t a = r.query_is_rev ? qe - v.t - span : qs + v.t;
+      r.vcf += r.target_name;
+      r.vcf.append(num, (size_t)snprintf(num, sizeof num, "\t%llu\t.\t", (unsigned long long)(ts + v.p + 1)));
+      r.vcf.append(alleles + v.off, v.ref_len);
+      r.vcf += '\t';
+      r.vcf.append(alleles + v.off + v.ref_len, v.alt_len);
+      r.vcf += tail;
+      r.vcf.append(num, (size_t)snprintf(num, sizeof num, "%llu;QEND=%llu;QSTRAND=%c\n", (unsigned long long)a, (unsigned long long)(a + span),
+                                         r.query_is_rev ? '-' : '+'));
+    }
+  });
+  wfm_free_variants(vars, alleles);
+  if (getenv("WFM_DEBUG"))
+    fprintf(stderr, "[wflign] variants: %zu records, %zu runs, %zu variants, %zu allele bytes, %d flagged, %.1f ms (upload %.1f, device call %.1f, text %.1f)\n",
+            n, w.n_cur(), n_vars, bytes, rc, ms_between(t0, Clock::now()), ms_between(t0, t1), ms_between(t1, t2), ms_between(t2, Clock::now()));
+  return 0;
+}
+
+// --variants: a record's lines go out with its line or not at all
+void account_variants(BiwfaRecord& r, bool written) {
+  if (!written) { r.vcf.clear(); return; }
+  if (!r.vcf_called) { g_variants_counts[3] += 1; return; }  // (flagged by the device, or runs it cannot hold)
+  g_variants_counts[0] += 1; g_variants_counts[2] += r.vcf_masked;
+  g_variants_counts[1] += (uint64_t)std::count(r.vcf.begin(), r.vcf.end(), '\n');
+}
+
 // ---- record (wflign.cpp:434-454) ----
 void write_record(BiwfaBatch& b, size_t ri) {
   BiwfaRecord& r = b.recs[ri];
@@ -528,6 +608,7 @@ void write_record(BiwfaBatch& b, size_t ri) {
     written = write_alignment_sam(r.paf, r.ops, r.query_name, r.query_offset, r.query_is_rev, r.target_name, r.target_offset, b.pp,
                         r.mashmap_estimated_identity, b.fmt.no_seq_in_sam, b.fmt.emit_md_tag, r.query, r.target, r.chain_id,
                         r.chain_length, r.chain_pos);
+  if (b.variants) account_variants(r, written);
   if (!b.cs_form || !written) return;
   if (r.cs.empty()) { g_cs_counts[2] += 1; return; }  // (flagged by the device, or runs it cannot hold)
   // the last field of the line, before its closing newline
@@ -539,6 +620,11 @@ void write_record(BiwfaBatch& b, size_t ri) {
   g_cs_counts[0] += 1; g_cs_counts[1] += r.cs.size();
 }
 }  // namespace
+
+std::string variants_path() {
+  std::lock_guard<std::mutex> lk(g_variants_mu);
+  return g_variants.load() ? g_variants_path : std::string();
+}
 
 int do_biwfa_alignment_batch(wfm_handle_t* h, std::vector<BiwfaRecord>& recs, const wflign_penalties_t& penalties,
                              bool disable_chain_patching, const PafParams& pp, BiwfaStats* stats, const OutputFormat& fmt,
@@ -563,10 +649,12 @@ int do_biwfa_alignment_batch(wfm_handle_t* h, std::vector<BiwfaRecord>& recs, co
   const auto ts2 = Clock::now();
   const bool left = g_left_align.load();
   b.cs_form = g_cs.load(std::memory_order_relaxed);
-  if (left || b.cs_form) {  // the two halves with the device calls between them
+  b.variants = g_variants.load(std::memory_order_relaxed);
+  if (left || b.cs_form || b.variants) {  // the two halves with the device calls between them
     for_each_record(n, fmt.threads, [&](size_t ri) { swizzle(b, ri); });
-    if (left) rc = left_align_records(b, b.cs_form != 0);
+    if (left) rc = left_align_records(b, b.cs_form != 0 || b.variants);
     if (rc >= 0 && b.cs_form) rc = cs_records(b);
+    if (rc >= 0 && b.variants) rc = variant_records(b);
     release_windows(b);
     if (rc < 0) return rc;
     for_each_record(n, fmt.threads, [&](size_t ri) { write_record(b, ri); });
@@ -597,6 +685,21 @@ void wfmh_set_left_align(int on) {
 void wfmh_set_cs(int form) {
   for (auto& a : wflign::g_cs_counts) a.store(0);
   wflign::g_cs.store(form == 1 || form == 2 ? form : 0);
+}
+
+void wfmh_set_variants(const char* path_or_null) {
+  for (auto& a : wflign::g_variants_counts) a.store(0);
+  {
+    std::lock_guard<std::mutex> lk(wflign::g_variants_mu);
+    wflign::g_variants_path = path_or_null ? path_or_null : "";
+  }
+  wflign::g_variants.store(path_or_null && *path_or_null);
+}
+
+int wfmh_variants_counts(uint64_t out[4]) {
+  if (!out) return WFM_E_ARG;
+  for (int q = 0; q < 4; ++q) out[q] = wflign::g_variants_counts[q].load();
+  return WFM_OK;
 }
 
 int wfmh_cs_counts(uint64_t out[4]) {

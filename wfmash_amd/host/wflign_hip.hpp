@@ -14,6 +14,8 @@
 //   left_align_records --left-align only: every interior gap to its leftmost placement, one wfm_left_align_runs call
 //   cs_records         --cs only: the cs difference string of every record's line, one wfm_cs_strings call (on the windows
 //                      left_align_records uploaded, where both are on)
+//   variant_records    --variants only: the VCF lines of every record's line, one wfm_call_variants call (on the same windows,
+//                      uploaded once whichever of the three switches are on)
 //   write_record       PAF / SAM record (+ cs:Z: as its last field)   (wflign.cpp:434-454)
 // and CIGARs are runs (count, op) from the device to the record's text: nothing is expanded to one byte per base.
 #pragma once
@@ -64,6 +66,9 @@ struct BiwfaRecord {
   CigarOps ops;                      // final CIGAR as runs (after patching + swizzle)
   std::string paf;                   // the record's line incl. newline, as the align driver writes it ("" if filtered)
   std::string cs;                    // --cs: the cs string of the line's runs, without its tag ("" if off, or if the record has none)
+  std::string vcf;                   // --variants: the VCF lines of the line's variants, each with its newline ("" if off, filtered, or none)
+  bool vcf_called = false;           // ... the device called the record's variants (false: off, or the record was left alone)
+  uint32_t vcf_masked = 0;           // ... SNVs left out of `vcf` because a base of theirs is not one of ACGT
   uint32_t tags = 0;                 // WFM_PF_* of the main alignment | of the head patch << 8 | of the tail patch << 16 (diagnostics: WFM_RECORD_TAGS)
 };
 
@@ -103,6 +108,9 @@ struct OutputFormat {
   bool emit_md_tag = false;
   int threads = 1;                   // host threads for the per-record CIGAR / PAF work of a batch
 };
+
+// --variants: the file wfmh_set_variants named ("" while the switch is off); the align phase writes the batches' BiwfaRecord::vcf to it
+std::string variants_path();
 
 int do_biwfa_alignment_batch(wfm_handle_t* h, std::vector<BiwfaRecord>& recs, const wflign_penalties_t& penalties,
                              bool disable_chain_patching, const PafParams& pp, BiwfaStats* stats,
