@@ -407,6 +407,48 @@ int  wfm_call_variants(wfm_handle_t* h, const wfm_seqset_t* s, const wfm_result_
                        wfm_variant_t** vars, size_t* n_vars, char** alleles, size_t* allele_bytes, wfm_varcall_t* per);
 void wfm_free_variants(wfm_variant_t* vars, char* alleles);
 
+/* ---- per-base depth of the target from the runs of many records ----
+ * What the calls above leave out: they take every problem alone.  A coverage object sums over all the problems added to it, call after
+ * call: a zeroed DIFFERENCE array of int32 words, n_bases + 1 of them, over the concatenation of the target sequences, on the handle's
+ * device (wfmash_amd/csrc/wfa_coverage.hip).  No sequence bytes are read: nothing goes up but runs.  depth(x) = the number of added
+ * problems with an = or X base at x: D bases do not count, I runs advance nothing.
+ *
+ * wfm_coverage_create: 4 bytes per target base; refused with WFM_E_ARG and a message naming the GiB needed where that is more than
+ * WFM_COV_GB GiB (environment, a decimal, read per call, 32).  The object is used with the handle it was made on and freed before it.
+ * wfm_coverage_add: probs[i] = {base: the global index of the first pattern base, runs_off / n_runs: its runs in runs[0 .. n_runs_total)}.
+ * An aligned segment -- =/X runs with no I or D between -- adds +1 at its first word and -1 behind its last: two integer atomics per
+ * segment; abutting segments of two records cancel at the word they share.  A problem whose pattern span leaves [0, n_bases], or with
+ * an empty run, adds NOTHING and is flagged WFM_COV_SPANS in flags_out[i] (the span is taken before any word is written).  Returns the
+ * number of problems flagged, or WFM_E_*: a run range that leaves the run buffer is WFM_E_ARG with a message, nothing is added and the
+ * handle stays usable.  No problems: WFM_OK.
+ * wfm_coverage_export: the non-zero words as {pos, delta} in ascending pos, by a device compaction (count per tile of WFM_COV_TILE words,
+ * prefix of the counts, write) brought down in chunks of at most WFM_COV_OUT_MB MiB (environment, a decimal, 256; one tile at least).
+ * Host memory owned by the caller (wfm_coverage_free_list); NULL and 0 where every word is zero.
+ * wfm_coverage_import: such a list added into this object (the merge of the objects of several devices); a pos beyond n_bases is
+ * WFM_E_ARG and nothing is added.
+ * wfm_coverage_intervals: the maximal intervals of constant depth: depth changes exactly at the non-zero words, so interval k starts at
+ * the k-th of them with depth = the inclusive prefix sum of delta, taken on the device over the compact list (scans in the reduce /
+ * scan-of-sums / apply form over blocks of WFM_COV_SCAN_BLOCK entries; dense depths are never made).  An interval ends where the next
+ * starts, the last at n_bases; the first starts at 0 (depth 0 where word 0 is zero); an object with every word zero gives {0, 0} alone.
+ * totals = {bases with depth >= 1, sum of depth over all bases, largest depth}, reduced on the device.  Release with
+ * wfm_coverage_free_list.
+ * Integer atomics only: any order of adds gives the same array, and two calls give the same bytes. */
+typedef struct wfm_coverage wfm_coverage_t;
+typedef struct { uint64_t base, runs_off; uint32_t n_runs, pad_; } wfm_cov_prob_t;      /* 24 bytes */
+typedef struct { uint64_t pos; int32_t delta; uint32_t pad_; } wfm_cov_entry_t;         /* 16 bytes */
+typedef struct { uint64_t start; uint32_t depth, pad_; } wfm_cov_interval_t;            /* 16 bytes */
+#define WFM_COV_SPANS 2u          /* as WFM_VAR_SPANS: nothing of the problem is added */
+#define WFM_COV_TILE 4096         /* words of the difference array one workgroup counts and writes */
+#define WFM_COV_SCAN_BLOCK 1024   /* elements one workgroup takes in the two scans */
+int  wfm_coverage_create(wfm_handle_t* h, uint64_t n_bases, wfm_coverage_t** cov);
+void wfm_coverage_free(wfm_coverage_t* cov);
+int  wfm_coverage_add(wfm_handle_t* h, wfm_coverage_t* cov, const wfm_cov_prob_t* probs, size_t n, const uint32_t* runs, size_t n_runs_total,
+                      uint32_t* flags_out);
+int  wfm_coverage_export(wfm_handle_t* h, wfm_coverage_t* cov, wfm_cov_entry_t** entries, size_t* n);
+int  wfm_coverage_import(wfm_handle_t* h, wfm_coverage_t* cov, const wfm_cov_entry_t* entries, size_t n);
+int  wfm_coverage_intervals(wfm_handle_t* h, wfm_coverage_t* cov, wfm_cov_interval_t** iv, size_t* n, uint64_t totals[3]);
+void wfm_coverage_free_list(void* p);
+
 /* ---- every score proved optimal by a banded DP ----
  * What wfm_check_runs leaves out.  For every problem of the seqset s whose result claims a score S = res[i].score, a classical
  * minimising gap-affine-2-piece DP over cells (i = pattern index, j = text index) is run on the device, restricted to a band of

@@ -156,6 +156,30 @@ int  wfmh_cs_counts(uint64_t out[4]);
 void wfmh_set_variants(const char* path_or_null);
 int  wfmh_variants_counts(uint64_t out[4]);
 
+/* ---- per-base depth of the target from the records written, as a bedGraph (wfm_coverage_*, wfmash_hip.h) ----
+ * wfmh_set_coverage(path): from now on every batch of wfmh_align_paf[_multi] runs ONE more device call behind the record writers: the
+ * runs of every record WRITTEN -- a record the filters drop adds nothing; with wfmh_set_left_align the normalised runs -- are added to a
+ * depth object of the batch's handle (4 bytes per target base on each handle the run uses, made at the handle's first batch; refused
+ * beyond WFM_COV_GB GiB, 32).  depth(c, x) = the number of written records whose line has an = or X base at x of target sequence c: D
+ * bases do not count.  No output byte of the PAF or SAM changes.  After the last batch the objects are merged into one and the align
+ * phase writes `path`: plain bedGraph without a track line, name<TAB>start<TAB>end<TAB>depth, the target's sequences in index order, per
+ * sequence the maximal intervals of constant depth tiling [0, length) exactly, depth 0 included; a sequence without an alignment is one
+ * line of depth 0.  The file does not depend on the number of devices, handles, threads or the order of the batches.  NULL or ""
+ * switches it off.  Every call zeroes the counts.  wfmh_coverage_counts: out = {records added, target bases with depth >= 1, sum of
+ * depth, intervals written} since then; the sum of depth is the total of the = and X run lengths of the lines written.  Off by
+ * default; with the switch off nothing new is called and no file is written.
+ * wfmh_coverage_paf: the same file for an existing aligned PAF (this build's, the reference's, minimap2 -c --eqx's); nothing else
+ * runs.  A line without cg:Z: or with an op outside =XID, a malformed line, a line whose target the file does not have or whose tlen is
+ * not the file's is skipped and counted; one line on stderr has the totals.  out = {lines added, lines skipped, covered bases, sum of
+ * depth}.  Returns 0 or WFM_E_*. */
+void wfmh_set_coverage(const char* path_or_null);
+int  wfmh_coverage_counts(uint64_t out[4]);
+int  wfmh_coverage_paf(wfm_handle_t* h, const char* target_fasta, const char* aligned_paf, const char* out_path, uint64_t out[4]);
+/* Test hook (no GPU): the bedGraph of n_iv intervals of constant depth over the concatenation of n_seq sequences (starts ascending;
+ * the first at 0, or depth 0 before it), exactly as the align phase writes it.  malloc'd, wfmh_free. */
+char* wfmh_test_coverage_bedgraph(const char* const* names, const uint64_t* lengths, int n_seq, const uint64_t* starts, const uint32_t* depths,
+                                  int64_t n_iv);
+
 /* Test hooks: the pure host-side CIGAR functions (erode / merge / swizzle / PAF writer /
  * parseMashmapRow) behind one string interface so the CPU test-suite can check them
  * without a GPU.  fn in {erode, merge, compress, swap_start, swap_end, head_erosion,

@@ -46,6 +46,8 @@ EXPORTS = [
     "wfm_upload_sequence_refs", "wfm_align_refs_rle", "wfm_download_sequences",
     "wfm_check_runs", "wfm_check_optimal", "wfm_left_align_runs", "wfm_cs_strings", "wfm_free_cs",
     "wfm_call_variants", "wfm_free_variants",
+    "wfm_coverage_create", "wfm_coverage_free", "wfm_coverage_add", "wfm_coverage_export", "wfm_coverage_import", "wfm_coverage_intervals",
+    "wfm_coverage_free_list",
     "wfm_sketch_intersections",
 ]
 ISECT_LDS_MAX = 4096  # WFM_ISECT_LDS_MAX: the longest column sketch wfm_sketch_intersections searches in LDS
@@ -64,6 +66,10 @@ WFM_VAR_SNV, WFM_VAR_INS, WFM_VAR_DEL = 0, 1, 2
 WFM_VAR_MASKED = 256
 WFM_VAR_NOT_DONE, WFM_VAR_SPANS = 1, 2
 WFM_VAR_SLICE = 16384
+# wfm_coverage_* (include/wfmash_hip.h): why a problem adds nothing, the words one workgroup counts and writes, the elements one workgroup scans
+WFM_COV_SPANS = 2
+WFM_COV_TILE = 4096
+WFM_COV_SCAN_BLOCK = 1024
 # wfm_check_optimal (include/wfmash_hip.h): what a problem's score was flagged for, and the band widths at which the kernel changes form
 WFM_OPT_NOT_CHECKED, WFM_OPT_SKIPPED, WFM_OPT_CHEAPER, WFM_OPT_UNREACHED = 1, 2, 4, 8
 OPT_NAMES = ("NOT_CHECKED", "SKIPPED", "CHEAPER", "UNREACHED")
@@ -137,6 +143,26 @@ class VarCall(C.Structure):
     """wfm_varcall_t: where wfm_call_variants put one problem's records, the runs they were called from and the gaps it did not call."""
     _fields_ = [("flags", C.c_uint32), ("n_runs", C.c_uint32), ("first", C.c_uint64), ("count", C.c_uint64),
                 ("end_gaps", C.c_uint32), ("pad_", C.c_uint32)]
+
+
+class CovProb(C.Structure):
+    """wfm_cov_prob_t: a problem of wfm_coverage_add: the global index of its first pattern base and its runs in the call's run buffer."""
+    _fields_ = [("base", C.c_uint64), ("runs_off", C.c_uint64), ("n_runs", C.c_uint32), ("pad_", C.c_uint32)]
+
+
+class CovEntry(C.Structure):
+    """wfm_cov_entry_t: a non-zero word of a coverage object's difference array."""
+    _fields_ = [("pos", C.c_uint64), ("delta", C.c_int32), ("pad_", C.c_uint32)]
+
+
+class CovInterval(C.Structure):
+    """wfm_cov_interval_t: an interval of constant depth; it ends where the next begins."""
+    _fields_ = [("start", C.c_uint64), ("depth", C.c_uint32), ("pad_", C.c_uint32)]
+
+
+COV_PROB_DTYPE = np.dtype([("base", "<u8"), ("runs_off", "<u8"), ("n_runs", "<u4"), ("pad_", "<u4")])
+COV_ENTRY_DTYPE = np.dtype([("pos", "<u8"), ("delta", "<i4"), ("pad_", "<u4")])
+COV_INTERVAL_DTYPE = np.dtype([("start", "<u8"), ("depth", "<u4"), ("pad_", "<u4")])
 
 
 class OptCheck(C.Structure):
@@ -488,6 +514,94 @@ class SeqStore:
             pass
 
 
+class Coverage:
+    """wfm_coverage_t: per-base depth of n_bases target bases, summed on the device over every problem added (include/wfmash_hip.h).
+    Close it before its handle."""
+
+    def __init__(self, handle, n_bases):
+        self._h, self._L = handle, handle._L
+        self.n_bases = int(n_bases)
+        L = self._L
+        L.wfm_coverage_create.restype = C.c_int
+        L.wfm_coverage_create.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]
+        L.wfm_coverage_free.restype = None
+        L.wfm_coverage_free.argtypes = [C.c_void_p]
+        L.wfm_coverage_add.restype = C.c_int
+        L.wfm_coverage_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.wfm_coverage_export.restype = C.c_int
+        L.wfm_coverage_export.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+        L.wfm_coverage_import.restype = C.c_int
+        L.wfm_coverage_import.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        L.wfm_coverage_intervals.restype = C.c_int
+        L.wfm_coverage_intervals.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]
+        L.wfm_coverage_free_list.restype = None
+        L.wfm_coverage_free_list.argtypes = [C.c_void_p]
+        p = C.c_void_p()
+        rc = L.wfm_coverage_create(handle._p, self.n_bases, C.byref(p))
+        if rc != 0:
+            raise WfmError(f"wfm_coverage_create failed ({rc}): {handle.last_error()}")
+        self._p = p
+
+    def close(self):
+        if self._p:
+            self._L.wfm_coverage_free(self._p)
+            self._p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, problems, runs):
+        """wfm_coverage_add.  problems: a list of (base, runs_off, n_runs); runs: the run words ((length << 2) | op).  Returns the
+        problems' flags as a numpy array (WFM_COV_SPANS: nothing of the problem was added)."""
+        probs = np.zeros(len(problems), dtype=COV_PROB_DTYPE)
+        for i, (base, off, n) in enumerate(problems):
+            probs[i] = (base, off, n, 0)
+        runs = np.ascontiguousarray(runs, dtype=np.uint32)
+        flags = np.zeros(max(len(problems), 1), dtype=np.uint32)
+        rc = self._L.wfm_coverage_add(self._h._p, self._p, probs.ctypes.data if len(probs) else None, len(probs),
+                                      runs.ctypes.data if len(runs) else None, len(runs), flags.ctypes.data)
+        if rc < 0:
+            raise WfmError(f"wfm_coverage_add failed ({rc}): {self._h.last_error()}")
+        assert rc == int(np.count_nonzero(flags[:len(problems)] & WFM_COV_SPANS))
+        return flags[:len(problems)]
+
+    def export(self):
+        """wfm_coverage_export: the non-zero words of the difference array, ascending, as a numpy array with the fields of CovEntry."""
+        ptr, n = C.c_void_p(), C.c_size_t(0)
+        rc = self._L.wfm_coverage_export(self._h._p, self._p, C.byref(ptr), C.byref(n))
+        if rc != 0:
+            raise WfmError(f"wfm_coverage_export failed ({rc}): {self._h.last_error()}")
+        try:
+            raw = C.string_at(ptr, n.value * C.sizeof(CovEntry)) if n.value else b""
+        finally:
+            self._L.wfm_coverage_free_list(ptr)
+        return np.frombuffer(raw, dtype=COV_ENTRY_DTYPE)
+
+    def import_entries(self, entries):
+        """wfm_coverage_import: such a list (of another object, of another device) added into this one."""
+        e = np.ascontiguousarray(entries, dtype=COV_ENTRY_DTYPE)
+        rc = self._L.wfm_coverage_import(self._h._p, self._p, e.ctypes.data if len(e) else None, len(e))
+        if rc != 0:
+            raise WfmError(f"wfm_coverage_import failed ({rc}): {self._h.last_error()}")
+
+    def intervals(self):
+        """wfm_coverage_intervals: (the maximal intervals of constant depth as a numpy array with the fields of CovInterval,
+        (covered bases, sum of depth, max depth))."""
+        ptr, n = C.c_void_p(), C.c_size_t(0)
+        tot = (C.c_uint64 * 3)()
+        rc = self._L.wfm_coverage_intervals(self._h._p, self._p, C.byref(ptr), C.byref(n), tot)
+        if rc != 0:
+            raise WfmError(f"wfm_coverage_intervals failed ({rc}): {self._h.last_error()}")
+        try:
+            raw = C.string_at(ptr, n.value * C.sizeof(CovInterval)) if n.value else b""
+        finally:
+            self._L.wfm_coverage_free_list(ptr)
+        return np.frombuffer(raw, dtype=COV_INTERVAL_DTYPE), tuple(int(v) for v in tot)
+
+
 class Handle:
     """One handle per GPU (wfm_create)."""
 
@@ -792,6 +906,10 @@ class Handle:
         finally:
             self._L.wfm_free_variants(recs, alleles)
         return np.frombuffer(raw, dtype=VARIANT_DTYPE), blob, [per[i] for i in range(n)]
+
+    def coverage(self, n_bases):
+        """wfm_coverage_create: a depth object over n_bases target bases on this handle's device."""
+        return Coverage(self, n_bases)
 
     def check_optimal(self, seqset, results, pen=None, max_cells=0):
         """wfm_check_optimal: every score held against a banded DP on the device.  results: a ctypes array of Result (seqset.results after
@@ -1156,6 +1274,7 @@ HOST_EXPORTS = ["wfmh_test_packed_lce", "wfmh_test_is_acgt", "wfmh_align_default
                 "wfmh_test_rows", "wfmh_test_tile_plan", "wfmh_test_p2_plan", "wfmh_test_base_plan", "wfmh_test_map_plan", "wfmh_test_filter_ordered",
                 "wfmh_test_reuse_plan", "wfmh_test_tile_plan_dirs", "wfmh_test_tile_interior", "wfmh_test_tile_lean_waves", "wfmh_set_verify", "wfmh_verify_counts", "wfmh_verify_paf", "wfmh_test_verify_parse",
                 "wfmh_set_verify_optimal", "wfmh_verify_optimal_counts", "wfmh_test_opt_band", "wfmh_set_left_align", "wfmh_left_align_counts", "wfmh_set_cs", "wfmh_cs_counts", "wfmh_set_variants", "wfmh_variants_counts",
+                "wfmh_set_coverage", "wfmh_coverage_counts", "wfmh_coverage_paf", "wfmh_test_coverage_bedgraph",
                 "wfmh_ani_matrix", "wfmh_ani_matrix_rows", "wfmh_free_ani_rows", "wfmh_set_ani_matrix", "wfmh_test_ani_tsv"]
 
 
@@ -1569,6 +1688,56 @@ def variants_counts():
     if rc != 0:
         raise WfmError(f"wfmh_variants_counts failed ({rc})")
     return tuple(int(v) for v in out)
+
+
+def set_coverage(path) -> None:
+    """wfmh_set_coverage: every later align_paf call of the process writes the per-base depth of the target, summed on the device over the
+    records it writes, as a bedGraph to `path` (None: off); zeroes the counts."""
+    f = _host().wfmh_set_coverage
+    f.restype = None
+    f.argtypes = [C.c_char_p]
+    f(os.fsencode(path) if path else None)
+
+
+def coverage_counts():
+    """wfmh_coverage_counts: (records added, target bases with depth >= 1, sum of depth, intervals written) since wfmh_set_coverage."""
+    f = _host().wfmh_coverage_counts
+    f.restype = C.c_int
+    f.argtypes = [C.POINTER(C.c_uint64)]
+    out = (C.c_uint64 * 4)()
+    rc = f(out)
+    if rc != 0:
+        raise WfmError(f"wfmh_coverage_counts failed ({rc})")
+    return tuple(int(v) for v in out)
+
+
+def coverage_paf(handle, target_fasta, aligned_paf, out_path):
+    """wfmh_coverage_paf: the depth bedGraph of an existing aligned PAF; returns (lines added, lines skipped, covered bases, sum of depth)."""
+    f = _host().wfmh_coverage_paf
+    f.restype = C.c_int
+    f.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_uint64)]
+    out = (C.c_uint64 * 4)()
+    rc = f(handle._p, os.fsencode(target_fasta), os.fsencode(aligned_paf), os.fsencode(out_path), out)
+    if rc != 0:
+        raise WfmError(f"wfmh_coverage_paf failed ({rc}): {handle.last_error()}")
+    return tuple(int(v) for v in out)
+
+
+def host_coverage_bedgraph(names, lengths, intervals) -> str:
+    """wfmh_test_coverage_bedgraph (no GPU): the bedGraph of `intervals` = [(start, depth)] over the concatenation of the sequences."""
+    L = _host()
+    f = L.wfmh_test_coverage_bedgraph
+    f.restype = C.c_void_p
+    f.argtypes = [C.POINTER(C.c_char_p), C.POINTER(C.c_uint64), C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.c_int64]
+    n, m = len(names), len(intervals)
+    nm = (C.c_char_p * max(n, 1))(*[x.encode() if isinstance(x, str) else x for x in names])
+    ln = (C.c_uint64 * max(n, 1))(*[int(x) for x in lengths])
+    st = (C.c_uint64 * max(m, 1))(*[int(a) for a, _ in intervals])
+    dp = (C.c_uint32 * max(m, 1))(*[int(d) for _, d in intervals])
+    p = f(nm, ln, n, st, dp, m)
+    s = C.string_at(p).decode()
+    L.wfmh_free(p)
+    return s
 
 
 def set_verify_optimal(on: bool, max_cells: int = 0) -> None:

@@ -283,6 +283,25 @@ void launch_var_index(const uint32_t* runs, const CsProb* probs, int nprob, void
 void launch_var_write(const uint8_t* seq, const CsProb* probs, const void* recs, const uint32_t* rpre, const unsigned long long* goff,
                       const unsigned long long* voff, uint32_t ka, uint32_t kb, unsigned long long chunk_bytes, uint8_t* out, void* vars,
                       hipStream_t st);
+// wfm_coverage_* (wfa_coverage.hip).  A problem is wfm_cov_prob_t as the caller wrote it; d: the difference array, a whole number of
+// tiles of WFM_COV_TILE words of which the first n_bases + 1 are used
+struct CovProb {
+  uint64_t base, runs_off;
+  uint32_t n_runs, pad_;
+};
+void launch_cov_add(const uint32_t* runs, const CovProb* probs, int nprob, int32_t* d, unsigned long long n_bases, uint32_t* flags, hipStream_t st);
+// count, sum, scan of sums, apply: tile_cnt: ntiles; sums: ntiles / WFM_COV_SCAN_BLOCK rounded up, + 1; tile_off: ntiles + 1
+void launch_cov_tile_offsets(const int32_t* d, unsigned long long ntiles, uint32_t* tile_cnt, unsigned long long* sums, unsigned long long* tile_off,
+                             hipStream_t st);
+// the non-zero words of the tiles [tile_a, tile_b) as 16-byte entries; out[0] is entry number out_base of the whole list
+void launch_cov_write(const int32_t* d, const unsigned long long* tile_off, unsigned long long tile_a, unsigned long long tile_b,
+                      unsigned long long out_base, void* out, hipStream_t st);
+void launch_cov_import(const void* ent, unsigned long long n, int32_t* d, hipStream_t st);
+// m entries of the list to m intervals (sum, scan of sums, apply).  sums: m / WFM_COV_SCAN_BLOCK rounded up, + 1; *carry: the depth behind
+// the entries of the chunks before (0 at the first), brought up to date; prev_pos: the pos of the entry before ent[0]; last: this is the
+// list's last chunk; totals: three words, zeroed before the first chunk
+void launch_cov_intervals(const void* ent, unsigned long long m, unsigned long long* sums, unsigned long long* carry, unsigned long long prev_pos,
+                          unsigned long long n_bases, int last, void* iv, unsigned long long* totals, hipStream_t st);
 // wfm_check_optimal (wfa_optcheck.hip): a problem's forward byte copies, its ends-free allowances (clamped; 0 for the other modes),
 // its band of diagonals (wfa_optband.h) and, for the memory form, where its three row arrays begin in `rows` (32-bit elements)
 struct OptProb {

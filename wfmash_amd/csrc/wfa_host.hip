@@ -3115,6 +3115,244 @@ int wfm_call_variants(wfm_handle_t* h, const wfm_seqset_t* s, const wfm_result_t
 
 void wfm_free_variants(wfm_variant_t* vars, char* alleles) { free(vars); free(alleles); }
 
+// ---- per-base depth of the target from the runs of many records (wfmash_hip.h; the kernels: wfa_coverage.hip) ----
+struct wfm_coverage {
+  int device = 0;
+  uint64_t n_bases = 0, ntiles = 0;
+  int32_t* d = nullptr;                      // the difference array: ntiles whole tiles, zero behind word n_bases
+  uint64_t* aux = nullptr;                   // one block for the four below
+  uint32_t* tile_cnt = nullptr;              // ntiles
+  unsigned long long* tile_off = nullptr;    // ntiles + 1
+  unsigned long long* tile_sums = nullptr;   // one per WFM_COV_SCAN_BLOCK tiles, + 1
+  unsigned long long* cells = nullptr;       // the depth carried from chunk to chunk, then the three totals
+  DevBuf<uint64_t> work;                     // a call's problems and runs, or a chunk's entries, intervals and block sums
+};
+
+extern "C++" {  // (a template among them)
+namespace {
+static_assert(sizeof(wfm_cov_prob_t) == 24 && sizeof(CovProb) == 24 && sizeof(wfm_cov_entry_t) == 16 && sizeof(wfm_cov_interval_t) == 16, "wfmash_hip.h states these sizes");
+
+double env_decimal(const char* name, double dflt) { const char* e = getenv(name); return e && *e ? atof(e) : dflt; }
+
+int cov_usable(wfm_handle_t* h, const wfm_coverage_t* cov) {
+  if (cov->device == h->device) return WFM_OK;
+  h->err = "the coverage object lives on device " + std::to_string(cov->device) + ", the handle on " + std::to_string(h->device);
+  return WFM_E_ARG;
+}
+
+// every tile's offset in the compact list, on the device (cov->tile_off) and here
+int cov_tile_offsets(wfm_handle_t* h, wfm_coverage_t* cov, std::vector<unsigned long long>& off) {
+  launch_cov_tile_offsets(cov->d, cov->ntiles, cov->tile_cnt, cov->tile_sums, cov->tile_off, h->stream);
+  HIPCHK(h, hipGetLastError());
+  off.resize((size_t)cov->ntiles + 1);
+  HIPCHK(h, hipMemcpyAsync(off.data(), cov->tile_off, off.size() * 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return WFM_OK;
+}
+
+// The compact list in chunks of whole tiles that hold at most WFM_COV_OUT_MB MiB of entries: each chunk's entries are written to the head
+// of cov->work, which holds words_per_entry 8-byte words for every entry of the chunk and room for its block sums, and handed to
+// f(d_entries, first entry, entries, last chunk) -> WFM_*.
+template <class F>
+int cov_chunks(wfm_handle_t* h, wfm_coverage_t* cov, const std::vector<unsigned long long>& off, size_t words_per_entry, F f) {
+  const unsigned long long total = off.back();
+  const unsigned long long cap = std::max<unsigned long long>(WFM_COV_TILE, (unsigned long long)(std::max(0.0, env_decimal("WFM_COV_OUT_MB", 256.0)) * 1048576.0) / 16u);
+  for (size_t ta = 0; ta < (size_t)cov->ntiles;) {
+    size_t tb = (size_t)(std::upper_bound(off.begin() + (ptrdiff_t)ta + 1, off.end(), off[ta] + cap) - off.begin()) - 1;
+    if (tb <= ta) tb = ta + 1;
+    const unsigned long long m = off[tb] - off[ta];
+    if (m) {
+      if (cov->work.ensure((size_t)m * words_per_entry + (size_t)m / WFM_COV_SCAN_BLOCK + 8)) { h->err = "out of device memory (coverage list)"; return WFM_E_NOMEM; }
+      launch_cov_write(cov->d, cov->tile_off, ta, tb, off[ta], cov->work.p, h->stream);
+      HIPCHK(h, hipGetLastError());
+      const int rc = f((const uint8_t*)cov->work.p, off[ta], m, off[tb] == total);
+      if (rc != WFM_OK) return rc;
+    }
+    ta = tb;
+  }
+  return WFM_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int wfm_coverage_create(wfm_handle_t* h, uint64_t n_bases, wfm_coverage_t** cov) {
+  if (!h || !cov) return WFM_E_ARG;
+  *cov = nullptr;
+  const double gib = env_decimal("WFM_COV_GB", 32.0), need = ((double)n_bases + 1.0) * 4.0 / 1073741824.0;
+  if (n_bases >= ((uint64_t)1 << 40) || need > gib) {
+    char msg[200];
+    snprintf(msg, sizeof msg, "wfm_coverage_create: the difference array of %llu target bases needs %.3f GiB, more than WFM_COV_GB = %.3f",
+             (unsigned long long)n_bases, need, gib);
+    h->err = msg;
+    return WFM_E_ARG;
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  std::unique_ptr<wfm_coverage> c(new wfm_coverage());
+  c->device = h->device;
+  c->n_bases = n_bases;
+  c->ntiles = (n_bases + 1 + WFM_COV_TILE - 1) / WFM_COV_TILE;
+  const size_t nsums = (size_t)(c->ntiles + WFM_COV_SCAN_BLOCK - 1) / WFM_COV_SCAN_BLOCK + 1;
+  const size_t w_cnt = ((size_t)c->ntiles * 4 + 7) / 8, w_off = (size_t)c->ntiles + 1;
+  if (wfm_dmalloc((void**)&c->d, (size_t)c->ntiles * WFM_COV_TILE * 4) != hipSuccess ||
+      wfm_dmalloc((void**)&c->aux, (w_cnt + w_off + nsums + 4) * 8) != hipSuccess) {
+    (void)hipGetLastError();
+    if (c->d) wfm_dfree(c->d);
+    h->err = "out of device memory (coverage)";
+    return WFM_E_NOMEM;
+  }
+  c->tile_cnt = (uint32_t*)c->aux;
+  c->tile_off = (unsigned long long*)(c->aux + w_cnt);
+  c->tile_sums = c->tile_off + w_off;
+  c->cells = c->tile_sums + nsums;
+  hipError_t e = hipMemsetAsync(c->d, 0, (size_t)c->ntiles * WFM_COV_TILE * 4, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e != hipSuccess) { wfm_dfree(c->d); wfm_dfree(c->aux); h->err = std::string("wfm_coverage_create: ") + hipGetErrorString(e); return WFM_E_HIP; }
+  *cov = c.release();
+  return WFM_OK;
+}
+
+void wfm_coverage_free(wfm_coverage_t* cov) {
+  if (!cov) return;
+  int cur = 0;
+  const bool swap = hipGetDevice(&cur) == hipSuccess && cur != cov->device;
+  if (swap) (void)hipSetDevice(cov->device);
+  cov->work.release();
+  if (cov->d) wfm_dfree(cov->d);
+  if (cov->aux) wfm_dfree(cov->aux);
+  if (swap) (void)hipSetDevice(cur);
+  delete cov;
+}
+
+int wfm_coverage_add(wfm_handle_t* h, wfm_coverage_t* cov, const wfm_cov_prob_t* probs, size_t n, const uint32_t* runs, size_t n_runs_total,
+                     uint32_t* flags_out) {
+  if (!h || !cov || (n && (!probs || !flags_out)) || (n_runs_total && !runs)) return WFM_E_ARG;
+  if (n == 0) return WFM_OK;
+  if (n > (size_t)INT32_MAX || n_runs_total > ((size_t)1 << 31)) { h->err = "wfm_coverage_add: too many problems or runs for one call"; return WFM_E_ARG; }
+  if (int rc = cov_usable(h, cov)) return rc;
+  // the run ranges are validated here, before anything is launched
+  for (size_t i = 0; i < n; ++i)
+    if (!(probs[i].runs_off <= n_runs_total && (uint64_t)probs[i].n_runs <= n_runs_total - probs[i].runs_off)) {
+      h->err = "problem " + std::to_string(i) + ": its runs leave the run buffer";
+      return WFM_E_ARG;
+    }
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t w_probs = n * 3, w_runs = (n_runs_total * 4 + 7) / 8, w_flags = (n * 4 + 7) / 8;
+  if (cov->work.ensure(w_probs + w_runs + w_flags + 8)) { h->err = "out of device memory (coverage add)"; return WFM_E_NOMEM; }
+  CovProb* d_probs = (CovProb*)cov->work.p;
+  uint32_t* d_runs = (uint32_t*)(cov->work.p + w_probs);
+  uint32_t* d_flags = (uint32_t*)(cov->work.p + w_probs + w_runs);
+  HIPCHK(h, hipMemcpyAsync(d_probs, probs, n * sizeof(CovProb), hipMemcpyHostToDevice, h->stream));
+  if (n_runs_total) HIPCHK(h, hipMemcpyAsync(d_runs, runs, n_runs_total * 4, hipMemcpyHostToDevice, h->stream));
+  launch_cov_add(d_runs, d_probs, (int)n, cov->d, cov->n_bases, d_flags, h->stream);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipMemcpyAsync(flags_out, d_flags, n * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  int spans = 0;
+  for (size_t i = 0; i < n; ++i) spans += (flags_out[i] & WFM_COV_SPANS) != 0;
+  return spans;
+}
+
+int wfm_coverage_export(wfm_handle_t* h, wfm_coverage_t* cov, wfm_cov_entry_t** entries, size_t* n) {
+  if (!h || !cov || !entries || !n) return WFM_E_ARG;
+  *entries = nullptr; *n = 0;
+  if (int rc = cov_usable(h, cov)) return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  const auto t_call = std::chrono::steady_clock::now();
+  std::vector<unsigned long long> off;
+  if (int rc = cov_tile_offsets(h, cov, off)) return rc;
+  const auto t_off = std::chrono::steady_clock::now();
+  const unsigned long long total = off.back();
+  if (total == 0) return WFM_OK;
+  char* host = (char*)malloc((size_t)total * sizeof(wfm_cov_entry_t));
+  if (!host) { h->err = "out of host memory (coverage list)"; return WFM_E_NOMEM; }
+  const bool pinned = cs_pin_pieces(h);
+  const int rc = cov_chunks(h, cov, off, 2, [&](const uint8_t* d_ent, unsigned long long first, unsigned long long m, bool) {
+    const hipError_t e = cs_copy_down(h, pinned, host + first * sizeof(wfm_cov_entry_t), d_ent, (size_t)m * sizeof(wfm_cov_entry_t));  // (the block is the next chunk's)
+    if (e != hipSuccess) { h->err = std::string("wfm_coverage_export: ") + hipGetErrorString(e); return (int)WFM_E_HIP; }
+    return (int)WFM_OK;
+  });
+  if (rc != WFM_OK) { free(host); return rc; }
+  *entries = (wfm_cov_entry_t*)host; *n = (size_t)total;
+  if (env_debug())
+    fprintf(stderr, "[wfm] coverage export: %llu bases, %llu non-zero words, count + offsets %.3f ms, write + copy down %.3f ms (host clock, each ends in a synchronise)\n",
+            (unsigned long long)cov->n_bases, total, std::chrono::duration<double, std::milli>(t_off - t_call).count(),
+            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_off).count());
+  return WFM_OK;
+}
+
+int wfm_coverage_import(wfm_handle_t* h, wfm_coverage_t* cov, const wfm_cov_entry_t* entries, size_t n) {
+  if (!h || !cov || (n && !entries)) return WFM_E_ARG;
+  if (n == 0) return WFM_OK;
+  if (int rc = cov_usable(h, cov)) return rc;
+  for (size_t i = 0; i < n; ++i)
+    if (entries[i].pos > cov->n_bases) { h->err = "entry " + std::to_string(i) + ": its position lies beyond the object's bases"; return WFM_E_ARG; }
+  HIPCHK(h, hipSetDevice(h->device));
+  constexpr size_t PIECE = (size_t)4 << 20;  // entries: 64 MiB a piece
+  if (cov->work.ensure(std::min(n, PIECE) * 2)) { h->err = "out of device memory (coverage import)"; return WFM_E_NOMEM; }
+  for (size_t at = 0; at < n; at += PIECE) {
+    const size_t m = std::min(PIECE, n - at);
+    HIPCHK(h, hipMemcpyAsync(cov->work.p, entries + at, m * sizeof(wfm_cov_entry_t), hipMemcpyHostToDevice, h->stream));
+    launch_cov_import(cov->work.p, m, cov->d, h->stream);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));  // (the block is the next piece's)
+  }
+  return WFM_OK;
+}
+
+int wfm_coverage_intervals(wfm_handle_t* h, wfm_coverage_t* cov, wfm_cov_interval_t** iv, size_t* n, uint64_t totals[3]) {
+  if (!h || !cov || !iv || !n) return WFM_E_ARG;
+  *iv = nullptr; *n = 0;
+  if (totals) totals[0] = totals[1] = totals[2] = 0;
+  if (int rc = cov_usable(h, cov)) return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  const auto t_call = std::chrono::steady_clock::now();
+  std::vector<unsigned long long> off;
+  if (int rc = cov_tile_offsets(h, cov, off)) return rc;
+  const auto t_off = std::chrono::steady_clock::now();
+  const unsigned long long total = off.back();
+  // (slot 0 is kept for the interval that begins at 0 where the first non-zero word lies further on)
+  wfm_cov_interval_t* host = (wfm_cov_interval_t*)malloc(((size_t)total + 1) * sizeof(wfm_cov_interval_t));
+  if (!host) { h->err = "out of host memory (coverage intervals)"; return WFM_E_NOMEM; }
+  host[0].start = 0; host[0].depth = 0; host[0].pad_ = 0;
+  hipError_t e0 = hipMemsetAsync(cov->cells, 0, 4 * 8, h->stream);
+  if (e0 != hipSuccess) { free(host); h->err = std::string("wfm_coverage_intervals: ") + hipGetErrorString(e0); return WFM_E_HIP; }
+  const bool pinned = cs_pin_pieces(h);
+  unsigned long long prev_pos = 0;
+  size_t chunks = 0;
+  int rc = cov_chunks(h, cov, off, 4, [&](const uint8_t* d_ent, unsigned long long first, unsigned long long m, bool last) {
+    uint8_t* d_iv = (uint8_t*)(cov->work.p + 2 * (size_t)m);
+    unsigned long long* d_sums = (unsigned long long*)(cov->work.p + 4 * (size_t)m);
+    launch_cov_intervals(d_ent, m, d_sums, cov->cells, prev_pos, cov->n_bases, last ? 1 : 0, d_iv, cov->cells + 1, h->stream);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = cs_copy_down(h, pinned, (char*)(host + 1 + first), d_iv, (size_t)m * sizeof(wfm_cov_interval_t));
+    if (e != hipSuccess) { h->err = std::string("wfm_coverage_intervals: ") + hipGetErrorString(e); return (int)WFM_E_HIP; }
+    prev_pos = host[first + m].start;
+    ++chunks;
+    return (int)WFM_OK;
+  });
+  unsigned long long tot[3] = {0, 0, 0};
+  if (rc == WFM_OK) {
+    hipError_t e = hipMemcpyAsync(tot, cov->cells + 1, sizeof tot, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) { h->err = std::string("wfm_coverage_intervals: ") + hipGetErrorString(e); rc = WFM_E_HIP; }
+  }
+  if (rc != WFM_OK) { free(host); return rc; }
+  // the word at n_bases starts no interval; the interval from 0 is there already where word 0 is non-zero
+  size_t count = (size_t)total;
+  if (count && host[count].start >= cov->n_bases) --count;
+  const bool lead = count == 0 || host[1].start != 0;
+  if (!lead) memmove(host, host + 1, count * sizeof(wfm_cov_interval_t));
+  *iv = host; *n = count + (lead ? 1 : 0);
+  if (totals) { totals[0] = tot[0]; totals[1] = tot[1]; totals[2] = tot[2]; }
+  if (env_debug())
+    fprintf(stderr, "[wfm] coverage intervals: %llu bases, %llu non-zero words in %zu chunks, %zu intervals, count + offsets %.3f ms, write + scan + copy down %.3f ms (host clock, each ends in a synchronise)\n",
+            (unsigned long long)cov->n_bases, total, chunks, *n, std::chrono::duration<double, std::milli>(t_off - t_call).count(),
+            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_off).count());
+  return WFM_OK;
+}
+
+void wfm_coverage_free_list(void* p) { free(p); }
+
 // ---- every score proved optimal by a banded DP (wfmash_hip.h; the band: wfa_optband.h; the kernel: wfa_optcheck.hip) ----
 int wfm_check_optimal(wfm_handle_t* h, const wfm_penalties_t* pen, const wfm_seqset_t* s, const wfm_result_t* res, uint64_t max_cells,
                       wfm_optcheck_t* out) {

@@ -1,5 +1,6 @@
 #include "aligner.hpp"
 #include "verify_paf.hpp"
+#include "coverage_text.hpp"
 #include "map_queue.hpp"
 #include "parallel.hpp"
 #include "../csrc/wfa_handle.h"
@@ -379,7 +380,7 @@ std::string Aligner::gather_text(Summary& sum, const std::vector<Fetched>& fetch
 }
 
 std::string Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<std::string>& lines, int threads, Summary& sum, uint64_t first_row,
-                                 std::string* vcf) {
+                                 std::string* vcf, wfm_coverage_t* coverage, const std::vector<uint64_t>* seq_offsets) {
   const bool dbg = getenv("WFM_DEBUG") != nullptr;
   BatchTimes t;
   std::vector<Fetched> rows = parse_rows(lines, first_row, sum);
@@ -389,6 +390,8 @@ std::string Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<std::stri
   std::vector<Fetched> fetched = fetch_eager(rows, threads, sum);
   if (fetched.empty()) return std::string();
   std::vector<wflign::BiwfaRecord> recs = make_records(fetched);
+  if (coverage)
+    for (wflign::BiwfaRecord& r : recs) r.target_global = (*seq_offsets)[(size_t)ref->find(r.target_name)];  // (parse_rows has found every name)
   wflign::ResidentSeqs resident;
   if (ds) {
     resident.store = ds->store;
@@ -404,8 +407,10 @@ std::string Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<std::stri
   }
   t.fetch = t.lap();
   wflign::BiwfaStats st;
+  wflign::OutputFormat fmt = format_of(param, threads);
+  fmt.coverage = coverage;
   const int rc = wflign::do_biwfa_alignment_batch(gpu_handle, recs, penalties_of(param), param.disable_chain_patching, filters_of(param), &st,
-                                                  format_of(param, threads), ds ? &resident : nullptr);
+                                                  fmt, ds ? &resident : nullptr);
   if (rc < 0) throw std::runtime_error(std::string("[wfmash::align] GPU alignment failed: ") + st.error);
   account(sum, st, resident, fetched, recs);
   t.wflign = t.lap();
@@ -522,6 +527,27 @@ struct Aligner::Run {
   std::ifstream& in;
   skch::OrderedWriter<std::string, TextSink> writer;
   std::unique_ptr<skch::OrderedWriter<std::string, TextSink>> vcf_writer;  // --variants: the second file, keyed by the same batch numbers
+  // --coverage: where each target sequence begins in the concatenation (nseq + 1 values; empty: the switch is off), and the depth object
+  // of every handle the run has used so far, made at the handle's first batch
+  std::vector<uint64_t> seq_offsets;
+  std::mutex coverage_mu;
+  std::vector<std::pair<wfm_handle_t*, wfm_coverage_t*>> coverage;
+  ~Run() {
+    for (auto& hc : coverage) {
+      std::lock_guard<std::mutex> lk(wflign::handle_lock(hc.first));
+      wfm_coverage_free(hc.second);
+    }
+  }
+  wfm_coverage_t* coverage_of(wfm_handle_t* h) {
+    if (seq_offsets.empty()) return nullptr;
+    std::lock_guard<std::mutex> lk(coverage_mu);
+    for (auto& hc : coverage) if (hc.first == h) return hc.second;
+    wfm_coverage_t* c = nullptr;
+    std::lock_guard<std::mutex> hl(wflign::handle_lock(h));
+    if (wfm_coverage_create(h, seq_offsets.back(), &c) != WFM_OK) throw std::runtime_error(std::string("[wfmash::align] --coverage: ") + wfm_last_error(h));
+    coverage.emplace_back(h, c);
+    return c;
+  }
   std::mutex read_mu;
   uint64_t next_seq = 0;   // (under read_mu) the next batch's number
   uint64_t rows_read = 0;  // (under read_mu) non-empty rows handed out so far
@@ -610,7 +636,8 @@ void Aligner::run_worker(Run& run, size_t wk) {
       wfm_set_concurrent_calls(run.use[wk], beside + (more && run.plan.per_gpu > 1 ? 1 : 0));
       struct Leave { std::atomic<int>& a; ~Leave() { a.fetch_sub(1); } } leave{run.in_flight[dev]};
       std::string vcf;
-      std::string text = align_batch(run.use[wk], batch, run.threads_each, run.part[wk], first_row, run.vcf_writer ? &vcf : nullptr);
+      std::string text = align_batch(run.use[wk], batch, run.threads_each, run.part[wk], first_row, run.vcf_writer ? &vcf : nullptr,
+                                     run.coverage_of(run.use[wk]), &run.seq_offsets);
       const double at1 = run.ms();
       run.writer.put((uint64_t)seq, std::move(text));
       if (run.vcf_writer) run.vcf_writer->put((uint64_t)seq, std::move(vcf));
@@ -658,6 +685,46 @@ void Aligner::sum_up(Summary& sum, const std::vector<Summary>& part, std::chrono
   for (const Summary& p : part) sum.ms_gpu = std::max(sum.ms_gpu, p.ms_gpu);
 }
 
+// --coverage: every other handle's object exported and imported into the first (integer adds: the order does not matter), the intervals of
+// the sum taken once on the device, the file through coverage_bedgraph
+void Aligner::finish_coverage(Run& run, std::ofstream& out) {
+  const auto t0 = Clock::now();
+  auto fail = [](wfm_handle_t* h, const char* what) { throw std::runtime_error(std::string("[wfmash::align] --coverage: ") + what + ": " + wfm_last_error(h)); };
+  std::vector<coverage::Interval> iv;
+  uint64_t totals[3] = {0, 0, 0};
+  if (!run.coverage.empty()) {
+    wfm_handle_t* h0 = run.coverage.front().first;
+    wfm_coverage_t* c0 = run.coverage.front().second;
+    for (size_t k = 1; k < run.coverage.size(); ++k) {
+      wfm_cov_entry_t* list = nullptr;
+      size_t n = 0;
+      {
+        std::lock_guard<std::mutex> lk(wflign::handle_lock(run.coverage[k].first));
+        if (wfm_coverage_export(run.coverage[k].first, run.coverage[k].second, &list, &n) != WFM_OK) fail(run.coverage[k].first, "export");
+      }
+      std::lock_guard<std::mutex> lk(wflign::handle_lock(h0));
+      const int rc = wfm_coverage_import(h0, c0, list, n);
+      wfm_coverage_free_list(list);
+      if (rc != WFM_OK) fail(h0, "import");
+    }
+    wfm_cov_interval_t* d_iv = nullptr;
+    size_t n = 0;
+    std::lock_guard<std::mutex> lk(wflign::handle_lock(h0));
+    if (wfm_coverage_intervals(h0, c0, &d_iv, &n, totals) != WFM_OK) fail(h0, "intervals");
+    iv.resize(n);
+    for (size_t i = 0; i < n; ++i) iv[i] = coverage::Interval{d_iv[i].start, d_iv[i].depth};
+    wfm_coverage_free_list(d_iv);
+  }
+  std::vector<std::string> names;
+  std::vector<uint64_t> lengths;
+  for (int i = 0; i < ref->nseq(); ++i) { names.push_back(ref->name(i)); lengths.push_back((uint64_t)ref->length(i)); }
+  uint64_t lines = 0;
+  out << coverage::coverage_bedgraph(names, lengths, iv, &lines);
+  wflign::coverage_finished(totals[0], totals[1], lines);
+  if (getenv("WFM_DEBUG"))
+    fprintf(stderr, "[wfmash::align] coverage: %zu objects merged, %zu intervals, %llu lines, %.1f ms\n", run.coverage.size(), iv.size(), (unsigned long long)lines, ms_since(t0));
+}
+
 Summary Aligner::compute() {
   Summary sum;
   const auto t0 = Clock::now();
@@ -685,6 +752,14 @@ Summary Aligner::compute() {
                  "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n";
     run.vcf_writer.reset(new skch::OrderedWriter<std::string, TextSink>(TextSink{&vcfstream}));
   }
+  std::ofstream covstream;
+  const std::string cov_path = wflign::coverage_path();
+  if (!cov_path.empty()) {  // --coverage: the file is opened before anything is aligned, and written once the workers are done
+    covstream.open(cov_path);
+    if (!covstream.is_open()) throw std::runtime_error("[wfmash::align] Error! Failed to open the coverage file: " + cov_path);
+    run.seq_offsets.assign(1, 0);
+    for (int i = 0; i < ref->nseq(); ++i) run.seq_offsets.push_back(run.seq_offsets.back() + (uint64_t)ref->length(i));
+  }
   const size_t nworkers = run.plan.nworkers;
   static const bool own_handles = !(getenv("WFM_ALIGN_OWN_HANDLES") && atoi(getenv("WFM_ALIGN_OWN_HANDLES")) == 0);
   static HandlePool pool;
@@ -701,6 +776,7 @@ Summary Aligner::compute() {
     for (auto& t : threads) t.join();
   }
   if (run.failed.load()) throw std::runtime_error(run.first_error);
+  if (covstream.is_open()) { finish_coverage(run, covstream); covstream.close(); }
   sum_up(sum, run.part, t0);
   outstream.close();
   if (vcfstream.is_open()) vcfstream.close();

@@ -104,9 +104,10 @@ class Aligner {
   // ---- one batch of mapping rows on one handle (aligner.cpp: align_batch and its stages) ----
   struct Fetched;     // a row, its windows and where its sides are
   struct BatchTimes;  // the stages' times, into the Summary at the end
-  // (vcf: where the VCF lines of the records written go, --variants; null: nowhere)
+  // (vcf: where the VCF lines of the records written go, --variants; null: nowhere.  coverage: the depth object of this handle the records
+  // written are added to, --coverage, with seq_offsets: where each target sequence begins in the concatenation; null: none)
   std::string align_batch(wfm_handle_t* gpu, std::vector<std::string>& lines, int threads, Summary& sum, uint64_t first_row = 0,
-                          std::string* vcf = nullptr);
+                          std::string* vcf = nullptr, wfm_coverage_t* coverage = nullptr, const std::vector<uint64_t>* seq_offsets = nullptr);
   std::vector<Fetched> parse_rows(std::vector<std::string>& lines, uint64_t first_row, Summary& sum) const;
   void fetch_windows(Fetched& f) const;
   std::vector<Fetched> fetch_eager(std::vector<Fetched>& rows, int threads, Summary& sum) const;
@@ -120,6 +121,7 @@ class Aligner {
   struct RunPlan { size_t per_gpu = 1, nworkers = 1; uint64_t batch_bytes = ~0ull; };
   RunPlan plan_run(std::ifstream& in) const;
   void run_worker(Run& run, size_t wk);
+  void finish_coverage(Run& run, std::ofstream& out);  // --coverage: the handles' depth objects merged into one, its intervals as a bedGraph
   void sum_up(Summary& sum, const std::vector<Summary>& part, std::chrono::steady_clock::time_point t0) const;
   const Parameters& param;
   std::vector<wfm_handle_t*> gpus;

@@ -44,6 +44,17 @@
 //                                              (bcftools sort); no output byte of the PAF or SAM changes; allowed with -a, -d, -i, -K,
 //                                              --gpus, --resident-seqs, --verify, --verify-optimal, --left-align (the variants are then
 //                                              those of the normalised runs) and --cs, refused with -m and --verify-paf; off by default
+//   --coverage FILE                            per-base depth of every target sequence as a bedGraph (name, start, end, depth; no track
+//                                              line): depth = the number of records WRITTEN with an = or X base there (D bases do not
+//                                              count), summed on the device over all batches and GPUs (wfm_coverage_*); sequences in index
+//                                              order, maximal intervals of constant depth tiling [0, length), depth 0 included; 4 bytes of
+//                                              device memory per target base on every handle (WFM_COV_GB, 32); no output byte of the PAF
+//                                              or SAM changes; allowed with -a, -d, -i, -K, --gpus, --resident-seqs, --verify,
+//                                              --verify-optimal, --left-align (the depth is then that of the normalised runs), --cs and
+//                                              --variants, refused with -m and --verify-paf; off by default
+//   --coverage-paf IN.paf --coverage FILE target.fa   the same file for an existing aligned PAF (this build's, the reference's,
+//                                              minimap2 -c --eqx's): no mapping, no alignment; lines without an =XID cg:Z:, malformed
+//                                              lines, unknown targets and other tlens are skipped and counted; only --device beside it
 //   --verify-paf FILE target.fa [query.fa]     the same check on an existing aligned PAF (this build's or the reference's): no mapping,
 //                                              no alignment; exit status 3 if a line fails
 //   --ani-matrix FILE [--ani-only]             the group-by-group ANI table the identity estimate (-p aniN) is made from, as TSV: per
@@ -136,6 +147,8 @@ static void usage() {
           "            --left-align move every interior gap of the final CIGARs to its leftmost placement on the GPU (only cg:Z: / CIGAR and MD change; not with -m)\n"
           "            --cs[=short|=long] append minimap2's cs:Z: difference string, spelled on the GPU, to every PAF line / SAM record (not with -m, --verify-paf)\n"
           "            --variants FILE write the SNVs, insertions and deletions of every record, called on the GPU, as a VCF (unsorted; not with -m, --verify-paf)\n"
+          "            --coverage FILE write the per-base depth of every target sequence, summed on the GPU over the records written, as a bedGraph (not with -m, --verify-paf)\n"
+          "            --coverage-paf FILE with --coverage: the depth of an existing aligned PAF over target.fa, and stop (only --device beside it)\n"
           "            --verify-paf FILE check an existing aligned PAF against target.fa [query.fa] and stop (exit status 3 if a line fails)\n"
           "  other     --out FILE [stdout]   --device INT [0]   --gpus N|all [1] GPUs of this node, starting at --device\n"
           "            -B DIR directory of the hand-off file [cwd]   -Z keep the hand-off file   --quiet (no effect)\n");
@@ -147,7 +160,8 @@ int main(int argc, char** argv) {
   ap.threads = 1;  // -t, default 1 as in the reference (parse_args.hpp: thread_count); the C ABI default (0) means all cores
   wfmh_map_params_t mp;
   wfmh_map_default_params(&mp);
-  std::string mapping_in, out = "/dev/stdout", target, query, seeds_in, scaffold_out, tmp_base, verify_in, ani_matrix_out, variants_out;
+  std::string mapping_in, out = "/dev/stdout", target, query, seeds_in, scaffold_out, tmp_base, verify_in, ani_matrix_out, variants_out, coverage_out, coverage_in;
+  bool other_options = false;  // --coverage-paf: anything beside it, --coverage, --device and the target
   bool verify = false, verify_optimal = false, ani_only = false, left_align = false;
   uint64_t verify_optimal_cells = 0;
   int cs_form = 0;  // --cs: 0 off, 1 short, 2 long
@@ -155,6 +169,7 @@ int main(int argc, char** argv) {
   int device = 0, gpus = 1;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
+    if (a[0] == '-' ? (a != "--coverage" && a != "--coverage-paf" && a != "--device" && a != "-h" && a != "--help") : !target.empty()) other_options = true;
     auto next = [&](const char* name) -> std::string {
       if (i + 1 >= argc) { fprintf(stderr, "[wfmash] ERROR: missing value for %s\n", name); exit(1); }
       return argv[++i];
@@ -288,6 +303,8 @@ int main(int argc, char** argv) {
     else if (a == "--cs=long") cs_form = 2;
     else if (a.compare(0, 5, "--cs=") == 0) { fprintf(stderr, "[wfmash] ERROR: --cs takes =short or =long, not '%s'\n", a.c_str() + 5); return 1; }
     else if (a == "--variants") variants_out = next("--variants");
+    else if (a == "--coverage") coverage_out = next("--coverage");
+    else if (a == "--coverage-paf") coverage_in = next("--coverage-paf");
     else if (a == "--verify-optimal-cells") verify_optimal_cells = std::strtoull(next("--verify-optimal-cells").c_str(), nullptr, 10);
     else if (a == "--verify-paf") verify_in = next("--verify-paf");
     else if (a == "-h" || a == "--help") { usage(); return 0; }
@@ -303,6 +320,10 @@ int main(int argc, char** argv) {
   if (cs_form && !verify_in.empty()) { fprintf(stderr, "[wfmash] ERROR: --cs belongs to the align phase: it cannot be combined with --verify-paf\n"); return 1; }
   if (!variants_out.empty() && approx_only) { fprintf(stderr, "[wfmash] ERROR: --variants calls alignments: it cannot be combined with -m\n"); return 1; }
   if (!variants_out.empty() && !verify_in.empty()) { fprintf(stderr, "[wfmash] ERROR: --variants belongs to the align phase: it cannot be combined with --verify-paf\n"); return 1; }
+  if (!coverage_out.empty() && approx_only) { fprintf(stderr, "[wfmash] ERROR: --coverage counts alignments: it cannot be combined with -m\n"); return 1; }
+  if (!coverage_out.empty() && !verify_in.empty()) { fprintf(stderr, "[wfmash] ERROR: --coverage belongs to the align phase: it cannot be combined with --verify-paf\n"); return 1; }
+  if (!coverage_in.empty() && coverage_out.empty()) { fprintf(stderr, "[wfmash] ERROR: --coverage-paf needs --coverage FILE\n"); return 1; }
+  if (!coverage_in.empty() && other_options) { fprintf(stderr, "[wfmash] ERROR: --coverage-paf runs nothing else: besides --coverage FILE and the target FASTA it takes the number of the GPU only\n"); return 1; }
   if (verify_optimal && approx_only) { fprintf(stderr, "[wfmash] ERROR: --verify-optimal checks alignment scores: it cannot be combined with -m\n"); return 1; }
   if (verify_optimal_cells && !verify_optimal) { fprintf(stderr, "[wfmash] ERROR: --verify-optimal-cells needs --verify-optimal\n"); return 1; }
   if (ani_only && ani_matrix_out.empty()) { fprintf(stderr, "[wfmash] ERROR: --ani-only needs --ani-matrix FILE\n"); return 1; }
@@ -315,6 +336,15 @@ int main(int argc, char** argv) {
     return 1;
   }
   if (!ani_matrix_out.empty() && !verify_in.empty()) { fprintf(stderr, "[wfmash] ERROR: --ani-matrix cannot be combined with --verify-paf\n"); return 1; }
+  if (!coverage_in.empty()) {  // the depth of an existing PAF; nothing else runs
+    wfm_handle_t* hc = nullptr;
+    if (wfm_create(device, &hc) != WFM_OK) { fprintf(stderr, "[wfmash] ERROR: no usable MI355X device %d (there is no CPU fallback)\n", device); return 2; }
+    uint64_t cc[4] = {0, 0, 0, 0};
+    const int crc = wfmh_coverage_paf(hc, target.c_str(), coverage_in.c_str(), coverage_out.c_str(), cc);
+    if (crc != WFM_OK) fprintf(stderr, "[wfmash::coverage] ERROR: %s\n", wfm_last_error(hc));
+    wfm_destroy(hc);
+    return crc == WFM_OK ? 0 : 2;
+  }
   if (!verify_in.empty()) {  // an existing PAF against its sequences; nothing else runs
     wfm_handle_t* hv = nullptr;
     if (wfm_create(device, &hv) != WFM_OK) { fprintf(stderr, "[wfmash] ERROR: no usable MI355X device %d (there is no CPU fallback)\n", device); return 2; }
@@ -435,6 +465,7 @@ int main(int argc, char** argv) {
     if (left_align) wfmh_set_left_align(1);
     if (cs_form) wfmh_set_cs(cs_form);
     if (!variants_out.empty()) wfmh_set_variants(variants_out.c_str());
+    if (!coverage_out.empty()) wfmh_set_coverage(coverage_out.c_str());
     rc = wfmh_align_paf_multi(hs.data(), (int)hs.size(), target.c_str(), q, mapping.c_str(), out.c_str(), &ap, &s);
     if (rc == WFM_OK)
       fprintf(stderr, "[wfmash::align] %llu records, %llu aligned bp, %.1f ms GPU kernels, %.1f ms total => %.3g aligned bp/s\n",
@@ -457,6 +488,12 @@ int main(int argc, char** argv) {
       wfmh_variants_counts(vc);
       fprintf(stderr, "[wfmash::variants] %llu records, %llu variants written, %llu SNVs masked, %llu records left alone\n", (unsigned long long)vc[0],
               (unsigned long long)vc[1], (unsigned long long)vc[2], (unsigned long long)vc[3]);
+    }
+    if (!coverage_out.empty() && rc == WFM_OK) {
+      uint64_t cc[4] = {0, 0, 0, 0};
+      wfmh_coverage_counts(cc);
+      fprintf(stderr, "[wfmash::coverage] %llu records added, %llu bases covered, sum of depth %llu, %llu intervals written\n", (unsigned long long)cc[0],
+              (unsigned long long)cc[1], (unsigned long long)cc[2], (unsigned long long)cc[3]);
     }
     if (verify && rc == WFM_OK) {  // everything has been written by now
       uint64_t vc[4] = {0, 0, 0, 0};

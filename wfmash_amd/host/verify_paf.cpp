@@ -15,6 +15,7 @@
 #include "../../include/wfmash_host.h"
 #include "../csrc/wfa_handle.h"
 #include "aligner.hpp"
+#include "coverage_text.hpp"
 #include "parallel.hpp"
 #include "wflign_hip.hpp"
 
@@ -215,6 +216,90 @@ int wfmh_verify_paf(wfm_handle_t* h, const char* target_fasta, const char* query
     wfm_set_error(h, e.what());
     return WFM_E_ARG;
   }
+}
+
+// --coverage-paf: the depth of an existing aligned PAF.  Lines go to the device in batches of runs; nothing else runs.
+int wfmh_coverage_paf(wfm_handle_t* h, const char* target_fasta, const char* aligned_paf, const char* out_path, uint64_t out[4]) {
+  if (!h || !target_fasta || !aligned_paf || !out_path) return WFM_E_ARG;
+  wfm_coverage_t* cov = nullptr;
+  try {
+    std::shared_ptr<wfmash_host::FastaStore> target = wfmash_host::open_shared(target_fasta);
+    std::ifstream in(aligned_paf);
+    if (!in.is_open()) throw std::runtime_error(std::string("[wfmash::coverage] cannot open ") + aligned_paf);
+    std::ofstream outstream(out_path);
+    if (!outstream.is_open()) throw std::runtime_error(std::string("[wfmash::coverage] cannot open ") + out_path);
+    std::vector<std::string> names;
+    std::vector<uint64_t> lengths, offsets(1, 0);
+    for (int i = 0; i < target->nseq(); ++i) {
+      names.push_back(target->name(i));
+      lengths.push_back((uint64_t)target->length(i));
+      offsets.push_back(offsets.back() + lengths.back());
+    }
+    auto device = [&](int rc, const char* what) {
+      if (rc < 0) throw std::runtime_error(std::string("[wfmash::coverage] ") + what + " failed: " + wfm_last_error(h));
+      return rc;
+    };
+    std::lock_guard<std::mutex> lk(wflign::handle_lock(h));
+    device(wfm_coverage_create(h, offsets.back(), &cov), "create");
+    uint64_t added = 0, skipped[5] = {0, 0, 0, 0, 0};
+    std::vector<wfm_cov_prob_t> probs;
+    std::vector<uint32_t> runs, flags;
+    auto flush = [&]() {
+      if (probs.empty()) return;
+      flags.resize(probs.size());
+      const int refused = device(wfm_coverage_add(h, cov, probs.data(), probs.size(), runs.data(), runs.size(), flags.data()), "add");
+      added += probs.size() - (uint64_t)refused;
+      skipped[coverage::LINE_MALFORMED] += (uint64_t)refused;  // (a span that leaves the target: classify_line lets none through)
+      probs.clear(); runs.clear();
+    };
+    std::string line;
+    verify::Line l;
+    while (std::getline(in, line)) {
+      if (line.empty() || line[0] == '@') continue;
+      int ti = -1;
+      const int code = coverage::classify_line(line, [&](const std::string& name) { return target->find(name); }, lengths, l, &ti);
+      if (code != coverage::LINE_ADD) { skipped[code]++; continue; }
+      probs.push_back(wfm_cov_prob_t{offsets[(size_t)ti] + (uint64_t)l.ts, (uint64_t)runs.size(), (uint32_t)l.runs.size(), 0u});
+      runs.insert(runs.end(), l.runs.begin(), l.runs.end());
+      if (probs.size() >= 65536 || runs.size() >= ((size_t)16 << 20)) flush();
+    }
+    flush();
+    wfm_cov_interval_t* d_iv = nullptr;
+    size_t n = 0;
+    uint64_t totals[3] = {0, 0, 0};
+    device(wfm_coverage_intervals(h, cov, &d_iv, &n, totals), "intervals");
+    std::vector<coverage::Interval> iv(n);
+    for (size_t i = 0; i < n; ++i) iv[i] = coverage::Interval{d_iv[i].start, d_iv[i].depth};
+    wfm_coverage_free_list(d_iv);
+    wfm_coverage_free(cov);
+    cov = nullptr;
+    uint64_t lines = 0;
+    outstream << coverage::coverage_bedgraph(names, lengths, iv, &lines);
+    const uint64_t all_skipped = skipped[1] + skipped[2] + skipped[3] + skipped[4];
+    std::cerr << "[wfmash::coverage] " << added << " lines added, " << all_skipped << " skipped (" << skipped[1] << " without an =XID cg:Z:, " << skipped[2]
+              << " malformed, " << skipped[3] << " with an unknown target, " << skipped[4] << " with another tlen), " << totals[0] << " bases covered, sum of depth "
+              << totals[1] << ", max depth " << totals[2] << ", " << lines << " intervals" << std::endl;
+    if (out) { out[0] = added; out[1] = all_skipped; out[2] = totals[0]; out[3] = totals[1]; }
+    return WFM_OK;
+  } catch (const std::exception& e) {
+    if (cov) wfm_coverage_free(cov);
+    std::cerr << e.what() << std::endl;
+    wfm_set_error(h, e.what());
+    return WFM_E_ARG;
+  }
+}
+
+// test hook (no GPU): the bedGraph of n_iv intervals over n_seq sequences, as the align phase writes it.  malloc'd, wfmh_free.
+char* wfmh_test_coverage_bedgraph(const char* const* names, const uint64_t* lengths, int n_seq, const uint64_t* starts, const uint32_t* depths, int64_t n_iv) {
+  std::vector<std::string> nm;
+  std::vector<uint64_t> len;
+  std::vector<coverage::Interval> iv;
+  for (int i = 0; i < n_seq; ++i) { nm.push_back(names[i]); len.push_back(lengths[i]); }
+  for (int64_t i = 0; i < n_iv; ++i) iv.push_back(coverage::Interval{starts[i], depths[i]});
+  const std::string s = coverage::coverage_bedgraph(nm, len, iv, nullptr);
+  char* p = (char*)malloc(s.size() + 1);
+  if (p) memcpy(p, s.c_str(), s.size() + 1);
+  return p;
 }
 
 // test hook (no GPU): a line as the verifier reads it.  "ok <TAB> qname qs qe strand tname ts te runs" with the runs spelled

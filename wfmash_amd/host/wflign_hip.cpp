@@ -64,6 +64,13 @@ std::mutex g_variants_mu;
 std::string g_variants_path;
 std::atomic<uint64_t> g_variants_counts[4];
 
+// --coverage: the process-wide switch, the file the align phase writes and {records added, target bases with depth >= 1, sum of depth,
+// intervals written} since it was set
+std::atomic<bool> g_coverage{false};
+std::mutex g_coverage_mu;
+std::string g_coverage_path;
+std::atomic<uint64_t> g_coverage_counts[4];
+
 // The problems of one device call, always written by reference (a side without a store id carries its host pointer); without a
 // store they go to the device as plain wfm_problem_t, as they always have.
 struct GpuBatch {
@@ -598,6 +605,7 @@ void account_variants(BiwfaRecord& r, bool written) {
 // ---- record (wflign.cpp:434-454) ----
 void write_record(BiwfaBatch& b, size_t ri) {
   BiwfaRecord& r = b.recs[ri];
+  r.written = false;
   if (!r.ok) return;
   bool written;
   if (b.fmt.paf_format_else_sam)
@@ -608,6 +616,7 @@ void write_record(BiwfaBatch& b, size_t ri) {
     written = write_alignment_sam(r.paf, r.ops, r.query_name, r.query_offset, r.query_is_rev, r.target_name, r.target_offset, b.pp,
                         r.mashmap_estimated_identity, b.fmt.no_seq_in_sam, b.fmt.emit_md_tag, r.query, r.target, r.chain_id,
                         r.chain_length, r.chain_pos);
+  r.written = written;
   if (b.variants) account_variants(r, written);
   if (!b.cs_form || !written) return;
   if (r.cs.empty()) { g_cs_counts[2] += 1; return; }  // (flagged by the device, or runs it cannot hold)
@@ -619,7 +628,61 @@ void write_record(BiwfaBatch& b, size_t ri) {
   r.paf += '\n';
   g_cs_counts[0] += 1; g_cs_counts[1] += r.cs.size();
 }
+// ---- --coverage: the runs of every record WRITTEN into the depth object of the batch's handle, ONE device call per batch
+// (wfm_coverage_add).  It runs behind write_record, where the filters have spoken.  A record's problem is what its line spells: the ops
+// trimmed of their leading and trailing I and D runs (window_parts' rule, trim_and_filter's), at base = the target sequence's offset in
+// the concatenation + the target start the writer wrote -- variant_records' ts.  Nothing goes up but runs.  A record the device
+// refuses, or whose ops its runs cannot hold, is a defect: it adds nothing, is counted and reported. ----
+int coverage_records(BiwfaBatch& b) {
+  const auto t0 = Clock::now();
+  std::vector<wfm_cov_prob_t> probs;
+  std::vector<uint32_t> runs;
+  uint64_t unknown = 0;
+  for (const BiwfaRecord& r : b.recs) {
+    if (!r.ok || !r.written) continue;
+    const CigarOps& ops = r.ops;
+    size_t ob = 0, oe = ops.size();
+    uint64_t ta = 0;
+    while (ob < oe && (ops[ob].second == 'I' || ops[ob].second == 'D')) { if (ops[ob].second == 'D') ta += (uint64_t)ops[ob].first; ++ob; }
+    while (oe > ob && (ops[oe - 1].second == 'I' || ops[oe - 1].second == 'D')) --oe;
+    if (oe == ob) continue;
+    wfm_cov_prob_t p{r.target_global + r.target_offset + ta, (uint64_t)runs.size(), (uint32_t)(oe - ob), 0u};
+    bool known = true;
+    for (size_t k = ob; k < oe; ++k) {
+      const char c = ops[k].second;
+      const uint32_t op = c == '=' ? 0u : c == 'X' ? 1u : c == 'I' ? 2u : c == 'D' ? 3u : 4u;
+      if (op > 3u || ops[k].first <= 0 || (uint32_t)ops[k].first >= (1u << 30)) { known = false; break; }
+      runs.push_back(((uint32_t)ops[k].first << 2) | op);
+    }
+    if (!known) { runs.resize((size_t)p.runs_off); ++unknown; continue; }
+    probs.push_back(p);
+  }
+  int rc = WFM_OK;
+  if (!probs.empty()) {
+    std::vector<uint32_t> flags(probs.size());
+    std::lock_guard<std::mutex> lk(handle_lock(b.h));
+    rc = wfm_coverage_add(b.h, b.fmt.coverage, probs.data(), probs.size(), runs.data(), runs.size(), flags.data());
+    if (rc < 0 && b.stats) b.stats->error = wfm_last_error(b.h);
+  }
+  if (rc < 0) return rc;
+  g_coverage_counts[0] += probs.size() - (uint64_t)rc;
+  if (rc > 0 || unknown)
+    fprintf(stderr, "[wflign] coverage: %llu records of a batch were NOT added to the depth (their runs leave the target or cannot be held)\n",
+            (unsigned long long)((uint64_t)rc + unknown));
+  if (getenv("WFM_DEBUG"))
+    fprintf(stderr, "[wflign] coverage: %zu records, %zu runs, %d flagged, %.1f ms\n", probs.size(), runs.size(), rc, ms_between(t0, Clock::now()));
+  return 0;
+}
 }  // namespace
+
+std::string coverage_path() {
+  std::lock_guard<std::mutex> lk(g_coverage_mu);
+  return g_coverage.load() ? g_coverage_path : std::string();
+}
+
+void coverage_finished(uint64_t covered, uint64_t depth_sum, uint64_t intervals) {
+  g_coverage_counts[1] += covered; g_coverage_counts[2] += depth_sum; g_coverage_counts[3] += intervals;
+}
 
 std::string variants_path() {
   std::lock_guard<std::mutex> lk(g_variants_mu);
@@ -661,6 +724,7 @@ int do_biwfa_alignment_batch(wfm_handle_t* h, std::vector<BiwfaRecord>& recs, co
   } else {
     for_each_record(n, fmt.threads, [&](size_t ri) { swizzle(b, ri); write_record(b, ri); });
   }
+  if (fmt.coverage && (rc = coverage_records(b)) < 0) return rc;
   if (dbg)
     fprintf(stderr, "[wflign] %zu records: main alignment + runs + scans %.1f ms (incl. waiting for the device), patches %.1f ms (%zu tails scanned after their heads), swizzle + records %.1f ms\n",
             n, ms_between(ts0, ts1), ms_between(ts1, ts2), b.later, ms_between(ts2, Clock::now()));
@@ -694,6 +758,21 @@ void wfmh_set_variants(const char* path_or_null) {
     wflign::g_variants_path = path_or_null ? path_or_null : "";
   }
   wflign::g_variants.store(path_or_null && *path_or_null);
+}
+
+void wfmh_set_coverage(const char* path_or_null) {
+  for (auto& a : wflign::g_coverage_counts) a.store(0);
+  {
+    std::lock_guard<std::mutex> lk(wflign::g_coverage_mu);
+    wflign::g_coverage_path = path_or_null ? path_or_null : "";
+  }
+  wflign::g_coverage.store(path_or_null && *path_or_null);
+}
+
+int wfmh_coverage_counts(uint64_t out[4]) {
+  if (!out) return WFM_E_ARG;
+  for (int q = 0; q < 4; ++q) out[q] = wflign::g_coverage_counts[q].load();
+  return WFM_OK;
 }
 
 int wfmh_variants_counts(uint64_t out[4]) {

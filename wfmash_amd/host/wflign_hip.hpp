@@ -17,6 +17,8 @@
 //   variant_records    --variants only: the VCF lines of every record's line, one wfm_call_variants call (on the same windows,
 //                      uploaded once whichever of the three switches are on)
 //   write_record       PAF / SAM record (+ cs:Z: as its last field)   (wflign.cpp:434-454)
+//   coverage_records   --coverage only: the runs of every record WRITTEN into the handle's depth object, one wfm_coverage_add call
+//                      (nothing is uploaded but runs; whether a record is written is only known behind write_record)
 // and CIGARs are runs (count, op) from the device to the record's text: nothing is expanded to one byte per base.
 #pragma once
 
@@ -69,6 +71,8 @@ struct BiwfaRecord {
   std::string vcf;                   // --variants: the VCF lines of the line's variants, each with its newline ("" if off, filtered, or none)
   bool vcf_called = false;           // ... the device called the record's variants (false: off, or the record was left alone)
   uint32_t vcf_masked = 0;           // ... SNVs left out of `vcf` because a base of theirs is not one of ACGT
+  uint64_t target_global = 0;        // --coverage: where the target sequence begins in the concatenation of the target's sequences
+  bool written = false;              // the filters let the record's line through (write_record)
   uint32_t tags = 0;                 // WFM_PF_* of the main alignment | of the head patch << 8 | of the tail patch << 16 (diagnostics: WFM_RECORD_TAGS)
 };
 
@@ -107,10 +111,16 @@ struct OutputFormat {
   bool no_seq_in_sam = false;
   bool emit_md_tag = false;
   int threads = 1;                   // host threads for the per-record CIGAR / PAF work of a batch
+  wfm_coverage_t* coverage = nullptr;  // --coverage: the depth object of the batch's handle (null: the stage is not run)
 };
 
 // --variants: the file wfmh_set_variants named ("" while the switch is off); the align phase writes the batches' BiwfaRecord::vcf to it
 std::string variants_path();
+
+// --coverage: the file wfmh_set_coverage named ("" while the switch is off), and what the align phase adds to the counts once it has
+// the intervals: {target bases with depth >= 1, sum of depth, intervals written}
+std::string coverage_path();
+void coverage_finished(uint64_t covered, uint64_t depth_sum, uint64_t intervals);
 
 int do_biwfa_alignment_batch(wfm_handle_t* h, std::vector<BiwfaRecord>& recs, const wflign_penalties_t& penalties,
                              bool disable_chain_patching, const PafParams& pp, BiwfaStats* stats,
