@@ -538,7 +538,8 @@ enum {
   /* the fallbacks by cause (the two add up to WFM_TC_REUSE_FALLBACKS): */
   WFM_TC_REUSE_TOUCHED = 11,  /* the restore found a kept cell on the job's box or beyond it (v >= hmax_c(k) - WFM_REUSE_TOUCH_SLACK)    */
   WFM_TC_REUSE_FELL_OTHER = 12, /* any other cause: the maxima fired while one direction waited, the job met right behind the restore ... */
-  WFM_TILE_COUNTERS = 13
+  WFM_TC_PLANNED_ENDS = 13,  /* jobs that ended phase 1 at the state planned from their known score, without a search (WFM_TILE_PLANNED_END)   */
+  WFM_TILE_COUNTERS = 14
 };
 size_t wfm_get_tile_counters(const wfm_handle_t* h, uint64_t* out, size_t n);
 

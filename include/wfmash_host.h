@@ -200,6 +200,7 @@ int wfmh_test_base_plan(int op, const int32_t* in, int64_t n, int32_t* out);
 /* ... and of parent reuse (csrc/wfa_plan.h): which keep a child resumes from, whether it may, the cadence under the store's cap; the tile plan
  * with a direction mask per job (wrapped by tests/test_reuse_plan_cpu.py) */
 int wfmh_test_reuse_plan(int op, const int64_t* in, int64_t n, int64_t* out);
+int wfmh_test_planned_meet(const int64_t* in, int64_t n, int64_t* out);
 int wfmh_test_tile_plan_dirs(const int32_t* jobs, int64_t n, const int32_t* rules, const uint8_t* dirs, int32_t* per_block, int32_t* tasks, int64_t tasks_cap,
                              int64_t* scalars);
 /* ... and of the packed tile kernel's lean snapshot paths (csrc/wfa_rows.h): rng_interior against one query of (pl, tl, sub, first diagonal, last

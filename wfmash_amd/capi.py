@@ -27,7 +27,7 @@ WFM_PF_ROOT_AGAIN, WFM_PF_JOB_AGAIN, WFM_PF_BASE_RETRY, WFM_PF_BASE_RETRY2, WFM_
 WFM_PF_RING_GROWN = 256
 # wfm_get_tile_counters (include/wfmash_hip.h): the paths the BiWFA tile phase took in an align call, in the header's order
 TILE_COUNTERS = ("jobs", "exact_ends", "fine_reruns", "gap_reruns", "ring3", "blocks_coarse", "blocks_fine", "left_band",
-                 "reuse_resumed", "reuse_fallbacks", "reuse_keeps", "reuse_touched", "reuse_fell_other")
+                 "reuse_resumed", "reuse_fallbacks", "reuse_keeps", "reuse_touched", "reuse_fell_other", "planned_ends")
 
 EXPORTS = [
     "wfm_create", "wfm_destroy", "wfm_last_error", "wfm_device_name",
@@ -1272,7 +1272,7 @@ HOST_EXPORTS = ["wfmh_test_packed_lce", "wfmh_test_is_acgt", "wfmh_align_default
                 "wfmh_map_multi", "wfmh_align_paf_multi", "wfmh_test_winnow_model", "wfmh_test_sortlike_model", "wfmh_test_finish_records",
                 "wfmh_release_sequences", "wfmh_test_fasta_shared", "wfmh_seed_paf", "wfmh_test_deal", "wfmh_test_subwindow",
                 "wfmh_test_rows", "wfmh_test_tile_plan", "wfmh_test_p2_plan", "wfmh_test_base_plan", "wfmh_test_map_plan", "wfmh_test_filter_ordered",
-                "wfmh_test_reuse_plan", "wfmh_test_tile_plan_dirs", "wfmh_test_tile_interior", "wfmh_test_tile_lean_waves", "wfmh_set_verify", "wfmh_verify_counts", "wfmh_verify_paf", "wfmh_test_verify_parse",
+                "wfmh_test_reuse_plan", "wfmh_test_planned_meet", "wfmh_test_tile_plan_dirs", "wfmh_test_tile_interior", "wfmh_test_tile_lean_waves", "wfmh_set_verify", "wfmh_verify_counts", "wfmh_verify_paf", "wfmh_test_verify_parse",
                 "wfmh_set_verify_optimal", "wfmh_verify_optimal_counts", "wfmh_test_opt_band", "wfmh_set_left_align", "wfmh_left_align_counts", "wfmh_set_cs", "wfmh_cs_counts", "wfmh_set_variants", "wfmh_variants_counts",
                 "wfmh_set_coverage", "wfmh_coverage_counts", "wfmh_coverage_paf", "wfmh_test_coverage_bedgraph",
                 "wfmh_ani_matrix", "wfmh_ani_matrix_rows", "wfmh_free_ani_rows", "wfmh_set_ani_matrix", "wfmh_test_ani_tsv"]

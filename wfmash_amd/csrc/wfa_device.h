@@ -77,6 +77,7 @@ struct TileJob {
   int32_t mode;                        // 0: full blocks; 1: next block stops exactly at the meeting point; 2: stopped there; 6: the block BEFORE s0 runs again (ring_prev, below);
                                        // 5: the block after s0 runs again with per-score maxima (it ran with one maximum for the whole block
                                        // and the wavefronts met inside it: fine_s below)
+                                       // (a job with a planned end -- plan_sum below -- knows where mode 1 begins and never takes mode 5)
   int32_t tf, tr;                      // mode >= 1: steps of the forward / reverse direction inside the block after s0
   int32_t last_fwd;                    // mode >= 1: 1 if the forward check ended phase 1 (reverse is one step behind)
   int32_t packed;                      // as BpJob::packed (the job's tiles run wfa_tile2_kernel)
@@ -99,7 +100,42 @@ struct TileJob {
   int64_t ring_prev;
   int32_t prev_ok;                     // ring_prev holds the snapshot of score s0 - T (false before the phase's second block)
   int32_t reran;                       // mode-6 runs so far (the host's cell count)
+  // The planned end (wfa_plan.h, planned_meet): a job whose score is known need not search for its meeting point.  plan_sum > 0 is sf + sr of the
+  // state of the reference's alternating track at which this job's phase 1 ends -- forward (plan_sum + 1) / 2, reverse plan_sum / 2, the forward
+  // direction stepped last iff plan_sum is odd; no test of phase 2 before that state can hit, so phase 2 from there finds the reference's
+  // breakpoint.  Such a job never reads its maxima score by score: it is never in mode 5, no block of it runs in full only to be run again.  In
+  // a chunk that launches both instantiations its fine_s is INT_MAX: every block of it belongs to the one without per-score maxima, and it never
+  // counts for the other.  In a chunk that keeps per-score maxima from the first block on (fine_s = 0 for all of its jobs: too many jobs, or
+  // too few blocks, for the coarse path -- the flagship workload's deeper levels) its fine_s is 0 like its neighbours' and it rides in that
+  // chunk's one launch per block, the instantiation WITH per-score maxima, whose maxima nobody reads for it.  Either way the advance kernel moves it
+  // on block by block whatever the maxima say, and when the block behind s0 holds the planned end the job goes to mode 1 (mode 6 first where min(tf, tr) < 26 and
+  // ring_prev holds the block before) with the planned tf / tr / last_fwd -- the host does the same at set-up for a planned end in the first
+  // block.  The run up to a meeting point takes no maxima: fmax / rmax of such a job are those of s0, and nobody reads them behind an exact end.
+  // 0: the job searches (roots, jobs without their bound, the byte kernel's, grown rings, WFM_TILE_PLANNED_END=0).
+  int32_t plan_sum;
+  // 1: where the run up to the planned end is shorter than the 26 rows phase 2 reads behind it, the block BEFORE it writes the gap rows of its last
+  // 26 scores the first time it runs (the stores are mode 6's; the block is known one block ahead, tile_plan_short_next) and no block runs again;
+  // 0: that block runs again for them, mode 6, as for a job that searches
+  int32_t plan_deep;
 };
+static_assert(sizeof(TileJob) == 160, "TileJob::plan_sum and its padding behind reran: no field the tile kernels read has moved");
+// A job with a planned end that stands at s0 in mode 0: if the block behind s0 holds the planned end, the job's next block is the run up to it
+// (the advance kernel between two blocks, the host at set-up).  -> whether it does
+__host__ __device__ inline bool tile_plan_enter(TileJob& J, int T) {
+  if (J.plan_sum <= 0) return false;
+  const int sf = (J.plan_sum + 1) / 2, sr = J.plan_sum / 2;
+  if ((sf - 1) / T * T != J.s0) return false;
+  J.tf = sf - J.s0; J.tr = sr - J.s0; J.last_fwd = J.plan_sum & 1;
+  // (prev_ok: the block before s0 ran as a block of this job -- with plan_deep it wrote the rows a short run needs, tile_plan_short_next)
+  J.mode = (J.ring_prev >= 0 && J.prev_ok && !J.plan_deep && (J.tf < J.tr ? J.tf : J.tr) < 26) ? 6 : 1;
+  return true;
+}
+// the block behind s0 of a job in mode 0 is the one BEFORE a run up to the planned end of fewer than 26 steps: it writes its gap rows 26 deep
+__host__ __device__ inline bool tile_plan_short_next(const TileJob& J, int T) {
+  if (J.plan_sum <= 0 || !J.plan_deep || J.mode != 0) return false;
+  const int sf = (J.plan_sum + 1) / 2, sr = J.plan_sum / 2, b0 = (sf - 1) / T * T;
+  return b0 == J.s0 + T && sr - b0 < 26;
+}
 
 // ---- a child's outer direction from its parent's kept rows (wfa_plan.h, "parent reuse") ----
 // A keep is one direction of a job's input snapshot at a block boundary s, compact: KEEP_ROWS rows of n columns (diagonals kmin .. kmin + n - 1),

@@ -420,7 +420,9 @@ __global__ __launch_bounds__(1024) void wfa_bp_kernel(const uint8_t* __restrict_
   // ---- phase 1: advance both directions until the antidiagonals meet ----
   // (the reference alternates forward, reverse; both rows of a round are
   //  computed here in one pass and the checks replayed in the same order)
-  for (;;) {
+  // (not for a job that comes with its exact end: phase 1 is over there whatever the maxima sum to -- a planned end, TileJob::plan_sum, may lie a
+  // few states before the trigger, and its running maxima are those of the last block boundary)
+  for (; !exact;) {
     if (fmax + rmax >= A) break;
     // a hard score limit: an alignment of score <= sf would have brought the forward direction to the end by now (and the directions together)
     if (J.limit > 0 && sf >= J.limit) { status = WFM_DEV_LIMIT; break; }

@@ -712,11 +712,14 @@ struct TilePhase {
   std::vector<char> active;
   size_t n_active = 0;
   bool any_cut = false;  // the kernel form with the score bounds' bookkeeping is only launched when a job carries one
+  bool any_planned = false;  // jobs with a planned end run on the instantiation without per-score maxima (TilePlanRules::planned)
+  bool plan_deep = env_num("WFM_TILE_PLANNED_DEEP", 1) != 0;  // TileJob::plan_deep (read per call)
   int chunk = 1;         // blocks launched back to back between two looks of the host
   TilePlanRules rules;
   std::vector<TilePlanJob> pjobs;
   TileChunkPlan plan;
   uint32_t blocks = 0;
+  uint32_t launches_coarse = 0, launches_fine = 0, reruns5 = 0, reruns6 = 0;  // this phase's share of the call's tile counters (the WFM_DEBUG line)
   double lane_cells = 0;  // threads x diagonals per thread x scores over all tiles launched (diagnostics)
   // parent reuse (ru == nullptr: none of it)
   ReuseCtl* ru = nullptr;
@@ -741,7 +744,7 @@ void reuse_fall_back(TilePhase& p, size_t i, bool touched = false) {
 }
 
 // The jobs' TileJobs, and where they stand: at score 0 after the init kernel, or (refine) where a pass before left them
-int init_tile_jobs(TilePhase& p, const std::vector<int32_t>* fine_from, const std::vector<int64_t>* ring3) {
+int init_tile_jobs(TilePhase& p, const std::vector<int32_t>* fine_from, const std::vector<int64_t>* ring3, const std::vector<int32_t>* plan_from) {
   wfm_handle* h = p.h;
   const TileCfg& cfg = p.cfg;
   const size_t n = p.n;
@@ -759,6 +762,10 @@ int init_tile_jobs(TilePhase& p, const std::vector<int32_t>* fine_from, const st
     // 26 deep from any snapshot
     t.ring_prev = (ring3 && i < ring3->size() && (*ring3)[i] >= 0 && (j.packed & 1) && cfg.reg && cfg.exact && !p.refine) ? (*ring3)[i] : -1;
     h->tile_ctr[WFM_TC_RING3] += t.ring_prev >= 0;
+    // the planned end (TileJob::plan_sum): the exact tile phase's first pass only
+    t.plan_sum = (plan_from && i < plan_from->size() && !p.refine && cfg.reg && cfg.exact && (j.packed & 1)) ? (*plan_from)[i] : 0;
+    t.plan_deep = (t.plan_sum > 0 && p.plan_deep) ? 1 : 0;
+    p.any_planned |= t.plan_sum > 0 && t.fine_s == INT_MAX;
   }
   if (!p.refine || T == cfg.T) h->tile_ctr[WFM_TC_JOBS] += n;  // (a WFM_TILE_T_REFINE pass goes on with jobs already counted; a resumed job enters)
   for (size_t i = 0; i < n; ++i) p.any_cut |= p.tj[i].sub != SUB_NONE;
@@ -795,6 +802,8 @@ int init_tile_jobs(TilePhase& p, const std::vector<int32_t>* fine_from, const st
       p.tj[i].fmax = p.fmax[i]; p.tj[i].rmax = p.rmax[i];
       p.dirs[i] = (uint8_t)(1 << (1 - u.dir)); p.own[i] = p.dirs[i];
     }
+    // a planned end in the first block: that block is the run up to it (the advance kernel does the same between two blocks)
+    for (size_t i = 0; i < n; ++i) if (p.active[i]) tile_plan_enter(p.tj[i], T);
   } else {
     for (size_t i = 0; i < n; ++i) {
       const BpJob& j = p.jobs[(size_t)p.tiled[i]];
@@ -962,6 +971,7 @@ int launch_chunk(TilePhase& p) {
         launch_tile2(S->d_pk, h->ring.p, h->tilejobs.p, h->tiletasks.p, h->tilemak.p, (int)n_pk, threads_b[(size_t)b], T, variants_b[(size_t)b], h->stream);
         h->tile_ctr[WFM_TC_BLOCKS_COARSE] += (variants_b[(size_t)b] & 1) != 0;
         h->tile_ctr[WFM_TC_BLOCKS_FINE] += (variants_b[(size_t)b] & 2) != 0;
+        p.launches_coarse += (variants_b[(size_t)b] & 1) != 0; p.launches_fine += (variants_b[(size_t)b] & 2) != 0;
       }
       if (tasks.size() > n_pk)
         launch_tile_reg(S->d_seq, h->ring.p, h->tilejobs.p, h->tiletasks.p + n_pk, h->tilemak.p, (int)(tasks.size() - n_pk), threads_b[(size_t)b], T, cfg.C, p.any_cut, h->stream);
@@ -1008,7 +1018,8 @@ void account_chunk(TilePhase& p) {
     // cells of the blocks this job ran since the last look (the block that found the meeting point included)
     for (int bl = was.nblocks; bl < got.nblocks; ++bl) {
       const bool last_exact = got.mode == 2 && bl == got.nblocks - 1;    // the block that stopped at the meeting point
-      const int base = p.s_begin[i] + (last_exact ? bl - 1 : bl) * T;    // it re-ran the block before it
+      // it re-ran the block before it -- unless the job came with its planned end: no block of it ran twice
+      const int base = p.s_begin[i] + ((last_exact && got.plan_sum <= 0) ? bl - 1 : bl) * T;
       for (int d = 0; d < 2; ++d) {
         if (!((p.dirs[i] >> d) & 1)) continue;  // (a direction that waits for its keep had no tiles)
         const int steps = last_exact ? (d == 0 ? got.tf : got.tr) : T;
@@ -1018,10 +1029,12 @@ void account_chunk(TilePhase& p) {
     if (got.fine_s == -1 && was.fine_s != -1) {  // the block in which the directions met ran once more, for its per-score maxima (TileJob::fine_s)
       for (int d = 0; d < 2; ++d) if ((p.dirs[i] >> d) & 1) p.tile_cells += (uint64_t)cells_sum(was.pl, was.tl, was.sub, got.s0 + 1, got.s0 + T);
       h->tile_ctr[WFM_TC_FINE_RERUNS] += 1;
+      p.reruns5 += 1;
     }
     if (got.reran > was.reran) {  // the block before the meeting block ran once more, for its gap rows (TileJob::ring_prev)
       for (int d = 0; d < 2; ++d) if ((p.dirs[i] >> d) & 1) p.tile_cells += (uint64_t)cells_sum(was.pl, was.tl, was.sub, got.s0 - T + 1, got.s0);
       h->tile_ctr[WFM_TC_GAP_RERUNS] += (uint64_t)(got.reran - was.reran);
+      p.reruns6 += (uint32_t)(got.reran - was.reran);
     }
     p.tj[i] = got;
     p.active[i] = (char)(got.active != 0);
@@ -1053,6 +1066,7 @@ void hand_back(TilePhase& p, uint32_t level, double cells_before) {
     j.resume_s = t.s0;
     j.resume_sr = -1; j.last_fwd = 0;
     h->tile_ctr[WFM_TC_EXACT_ENDS] += t.mode == 2;
+    h->tile_ctr[WFM_TC_PLANNED_ENDS] += t.mode == 2 && t.plan_sum > 0;
     h->tile_ctr[WFM_TC_LEFT_BAND] += t.mode == 3 && !(p.ru && p.ru->bad[i]);
     if (t.mode == 3) {  // ran out of its band: wfa_bp_kernel reports WFM_DEV_BAND
       // (where it stands, for the host: a job that goes on from this snapshot on a wider ring resumes at resume_sr with these maxima)
@@ -1066,8 +1080,9 @@ void hand_back(TilePhase& p, uint32_t level, double cells_before) {
     }
     j.fmax0 = p.fmax[i]; j.rmax0 = p.rmax[i];
   }
-  if (p.cfg.debug) fprintf(stderr, "[wfm] level %u: tiled %zu jobs, %u blocks of %d scores (Wt %d), %.3f ms; %.3e cells computed on %.3e lane-steps (%.0f %% of the lanes hold a cell), %.3e of them in the result (the block in which a job's wavefronts meet runs twice)\n", level, p.n, p.blocks, p.T, p.cfg.Wt, p.tile_ms,
-                           (double)p.tile_cells - cells_before, p.lane_cells, p.lane_cells > 0 ? 100.0 * ((double)p.tile_cells - cells_before) / p.lane_cells : 0.0, (double)unique_level);
+  if (p.cfg.debug) fprintf(stderr, "[wfm] level %u: tiled %zu jobs, %u blocks of %d scores (Wt %d), %.3f ms; %.3e cells computed on %.3e lane-steps (%.0f %% of the lanes hold a cell), %.3e of them in the result (the block in which a job's wavefronts meet runs twice); launches of the packed kernel without / with per-score maxima %u / %u, mode-5 reruns %u, mode-6 reruns %u\n", level, p.n, p.blocks, p.T, p.cfg.Wt, p.tile_ms,
+                           (double)p.tile_cells - cells_before, p.lane_cells, p.lane_cells > 0 ? 100.0 * ((double)p.tile_cells - cells_before) / p.lane_cells : 0.0, (double)unique_level,
+                           p.launches_coarse, p.launches_fine, p.reruns5, p.reruns6);
 }
 
 // Advances the jobs listed in `tiled` (indices into jobs) in blocks of T scores with the
@@ -1078,13 +1093,13 @@ void hand_back(TilePhase& p, uint32_t level, double cells_before) {
 int run_tiled_phase(wfm_handle* h, wfm_seqset* S, const DevPen& dp, int scope, const TileCfg& cfg, int T, bool refine,
                     std::vector<BpJob>& jobs, const std::vector<int>& tiled, std::vector<int64_t>& ring2,
                     double& tile_ms, uint64_t& tile_cells, uint32_t level, const std::vector<int32_t>* fine_from = nullptr,
-                    const std::vector<int64_t>* ring3 = nullptr, ReuseCtl* reuse = nullptr) {
+                    const std::vector<int64_t>* ring3 = nullptr, ReuseCtl* reuse = nullptr, const std::vector<int32_t>* plan_from = nullptr) {
   const size_t n = tiled.size();
   if (n == 0) return WFM_OK;
   const double cells_before = (double)tile_cells;
   TilePhase p{h, S, dp, scope, cfg, T, refine, jobs, tiled, ring2, tile_ms, tile_cells, n};
   p.ru = refine ? nullptr : reuse;
-  int rc = init_tile_jobs(p, fine_from, ring3);
+  int rc = init_tile_jobs(p, fine_from, ring3, plan_from);
   if (rc != WFM_OK) return rc;
   if (p.n_active) {
     // The per-job state lives on the device and a tiny kernel between two blocks replays the termination
@@ -1095,7 +1110,7 @@ int run_tiled_phase(wfm_handle* h, wfm_seqset* S, const DevPen& dp, int scope, c
     HIPCHK(h, hipMemsetAsync(h->tilemak.p, 0, n * 2 * (size_t)T * sizeof(int32_t), h->stream));
     p.chunk = std::max(1, std::min(cfg.chunk, (int)h->tile_ev.size() / 2));
     p.got.resize(n); p.pjobs.resize(n);
-    p.rules = TilePlanRules{cfg.threads, cfg.C, T, p.chunk, cfg.Wt - 2 * T, cfg.reg, cfg.fine, cfg.reg && cfg.exact && tile2_coarse_maxima()};
+    p.rules = TilePlanRules{cfg.threads, cfg.C, T, p.chunk, cfg.Wt - 2 * T, cfg.reg, cfg.fine, cfg.reg && cfg.exact && tile2_coarse_maxima(), p.any_planned};
     auto clk = [] { return std::chrono::steady_clock::now(); };
     auto msd = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     double ms_prep = 0, ms_launch = 0, ms_wait = 0, ms_post = 0;
@@ -1306,6 +1321,9 @@ struct Knobs {
   int p2_rounds = std::max(1, num("WFM_P2_ROUNDS", 64));
   int fine_margin = num("WFM_TILE_FINE_MARGIN", 48);
   int coarse_min_blocks = num("WFM_TILE_COARSE_MIN_BLOCKS", 32), coarse_max_jobs = num("WFM_TILE_COARSE_MAX_JOBS", 128);
+  // a job whose score is known ends phase 1 at the state planned from it (wfa_plan.h, planned_meet) instead of searching for its meeting point;
+  // not in the unbounded configuration of the tests (children without their parents' scores)
+  bool planned_end = num("WFM_TILE_PLANNED_END", 1) != 0 && slack_env < (1 << 28);
   bool tile_v2 = num("WFM_TILE_V2", 1) != 0;  // 0: every tile on the byte kernel (wfa_tile_reg_kernel) -- the A/B switch of the packed kernel (wfa_tile2.hip)
   bool band_on = num("WFM_BAND", 1) != 0;
   int band_root = std::max(64, num("WFM_BAND_ROOT", 4096));
@@ -1329,6 +1347,7 @@ struct Chunk {
   std::vector<int> tiled, tiled_r;  // jobs of the tile phase (indices into jobs); _r: those that go on from a snapshot.  Their second and third rings, their fine_s:
   std::vector<int64_t> ring2, ring3, ring2_r;
   std::vector<int32_t> fine_from, fine_r, snap_r;
+  std::vector<int32_t> plan_from;  // per entry of `tiled`: sf + sr of the planned end the job takes (TileJob::plan_sum), 0: it searches
   std::vector<size_t> ring_third;  // elements of one ring of every tiled job of the chunk
   std::vector<char> grown_job, resume_bad, has_carry;
   // parent reuse, per entry of `tiled` (plan_chunk): the keep the job resumes from, the last score it keeps at for its own children;
@@ -1343,7 +1362,7 @@ struct Chunk {
     jobs.clear(); node_of.clear(); ring_elems = 0; maxw = 0;
     tiled.clear(); ring2.clear(); ring3.clear(); ring_third.clear(); fine_from.clear();
     tiled_r.clear(); ring2_r.clear(); fine_r.clear(); snap_r.clear(); grown_job.clear();
-    reuse.clear(); keep_upto.clear();
+    reuse.clear(); keep_upto.clear(); plan_from.clear();
   }
 };
 
@@ -1568,6 +1587,10 @@ void plan_chunk(AlignCall& c, size_t i0) {
       }
       if (nd.keep > 0 && use.keep == 0) c.keeps.drop(nd.keep);
       k.reuse.push_back(use);
+      // the planned end (wfa_plan.h): a job that knows its score, on the packed kernel, on a ring no budget shaped, ends phase 1 where its score says
+      const bool planned = c.knobs.planned_end && tcfg.reg && tcfg.exact && c.RR == RING &&
+                           planned_meet_eligible(nd, rp, (j.packed & 1) != 0, use.keep > 0 ? use.s_k : 0, tcfg.T);
+      k.plan_from.push_back(planned ? nd.meet : 0);
       // (no keep beyond the score a child could still resume at: a child's score is at most its parent's, which is at most the bound where one is known)
       int32_t upto = 0;
       // (a score-only root has no children: nobody would resume from its keeps)
@@ -1594,6 +1617,9 @@ void plan_chunk(AlignCall& c, size_t i0) {
   // at least coarse_min_blocks blocks deep; everybody else keeps the per-score maxima from the first block on (one launch per block, as before).
   if (k.tiled.size() > (size_t)c.knobs.coarse_max_jobs || fine_min_blocks < (int64_t)c.knobs.coarse_min_blocks) std::fill(k.fine_from.begin(), k.fine_from.end(), 0);
   if (k.tiled_r.size() > (size_t)c.knobs.coarse_max_jobs || fine_min_blocks_r < (int64_t)c.knobs.coarse_min_blocks) std::fill(k.fine_r.begin(), k.fine_r.end(), 0);
+  // (a job with a planned end reads no maxima score by score: where the chunk launches the instantiation without them it never counts for the
+  // other one; in a chunk that keeps per-score maxima from the first block on it rides along in that one launch per block, at the same price)
+  for (size_t q = 0; q < k.tiled.size(); ++q) if (k.plan_from[q] > 0 && k.fine_from[q] > 0) k.fine_from[q] = INT_MAX;
   // third rings behind the chunk's rings (TileJob::ring_prev), for all of its tiled jobs or for none: where half as much again still fits the
   // budget (and 12 GB: fresh memory is 30 ms per GB).  The chunk's composition does not depend on it.
   size_t third = 0;
@@ -1660,7 +1686,7 @@ int run_chunk_tiles(AlignCall& c) {
     ru.cadence = kp.empty() ? 0 : reuse_fit_cadence(kp.data(), kp.size(), reuse_cadence(c.knobs.reuse_every, chunk_blocks), tcfg.T, c.keeps.cap_bytes);
   }
   const bool any_reuse = ru.cadence > 0 || std::any_of(ru.use.begin(), ru.use.end(), [](const ReuseUse& u) { return u.keep > 0; });
-  int rc = run_tiled_phase(h, c.S, c.dp, c.scope, tcfg, tcfg.T, false, k.jobs, k.tiled, k.ring2, tms, tcells, c.level, &k.fine_from, &k.ring3, any_reuse ? &ru : nullptr);
+  int rc = run_tiled_phase(h, c.S, c.dp, c.scope, tcfg, tcfg.T, false, k.jobs, k.tiled, k.ring2, tms, tcells, c.level, &k.fine_from, &k.ring3, any_reuse ? &ru : nullptr, &k.plan_from);
   k.reuse_bad.assign(k.jobs.size(), 0);
   k.kept[0].assign(k.jobs.size(), {}); k.kept[1].assign(k.jobs.size(), {});
   if (any_reuse && !ru.bad.empty())
@@ -1836,6 +1862,9 @@ void push_children(AlignCall& c, const Node& nd, const BpResult& r, int bp_v, in
   a.cb = nd.cb; a.ce = r.comp; a.score_rem = r.score_fwd;
   b.prob = nd.prob; b.pb = nd.pb + bp_v; b.pl = nd.pl - bp_v; b.tb = nd.tb + bp_h; b.tl = nd.tl - bp_h;
   b.cb = r.comp; b.ce = nd.ce; b.score_rem = r.score_rev;
+  // where phase 1 of either may end without a search (Node::meet; whether the job takes it is plan_chunk's decision)
+  a.meet = planned_meet_sum(a.score_rem, *pen, a.cb, a.ce, false);
+  b.meet = planned_meet_sum(b.score_rem, *pen, b.cb, b.ce, true);
   for (Node* ch : {&a, &b}) {
     if (ch->pl == 0 || ch->tl == 0) { ch->smax = 0; c.base_nodes.push_back(*ch); }
     else if (ch->score_rem <= BIALIGN_FALLBACK_MIN_SCORE) {

@@ -713,6 +713,8 @@ __global__ __launch_bounds__(NTMAX) void wfa_tile_reg_kernel(const uint8_t* __re
 // (round 6) `coarse`: wfa_tile2_kernel kept ONE maximum per direction for a block that ends below TileJob::fine_s (in the block's last slot: the
 // prefix maxima below make of it what the per-score maxima would have left at the block's end, and the running maxima are monotone, so "the
 // directions met in this block" is decided exactly).  Such a block runs again with per-score maxima (mode 5) before the run up to the meeting point.
+// A job with a planned end (TileJob::plan_sum: its score is known, so is the state at which its phase 1 may end) takes none of this: it moves on
+// block by block and enters mode 1 / 6 where the next block holds that state (tile_plan_enter, wfa_device.h).
 __global__ __launch_bounds__(64) void wfa_tile_advance_kernel(TileJob* __restrict__ jobs, int32_t* __restrict__ mak, int njobs, int T, DevPen pen,
                                                               int exact, int coarse, int launched) {
   const int i = blockIdx.x, lane = threadIdx.x;
@@ -751,6 +753,8 @@ __global__ __launch_bounds__(64) void wfa_tile_advance_kernel(TileJob* __restric
     return;
   }
   const int A = J.pl + J.tl - 1;
+  // a job with a planned end (TileJob::plan_sum) does not search: its running maxima move on to the block's end whatever they sum to
+  const bool planned = J.plan_sum > 0;
   int fm = J.fmax, rm = J.rmax;  // running maxima before the chunk of 64 scores at hand (uniform)
   int tf = 0, tr = 0, last_fwd = 0;
   bool term = false;
@@ -769,7 +773,7 @@ __global__ __launch_bounds__(64) void wfa_tile_advance_kernel(TileJob* __restric
     // the reference alternates: forward step t, check, reverse step t, check
     const bool hit_f = t < T && fm_t + rm_before >= A, hit_r = t < T && fm_t + rm_t >= A;
     const unsigned long long bf = __ballot(hit_f), br = __ballot(hit_r);
-    if (bf | br) {
+    if ((bf | br) && !planned) {
       const int lf = bf ? __builtin_ctzll(bf) : 64, lr = br ? __builtin_ctzll(br) : 64;
       term = true;
       if (lf <= lr) { last_fwd = 1; tf = base + lf + 1; tr = base + lf; fm = __shfl(fm_t, lf, 64); rm = __shfl(rm_before, lf, 64); }
@@ -805,6 +809,9 @@ __global__ __launch_bounds__(64) void wfa_tile_advance_kernel(TileJob* __restric
     } else {
       const int64_t t = J.ring_in; J.ring_in = J.ring_out; J.ring_out = t;
     }
+    // the planned end lies in the block behind the new s0: that block is the run up to it (mode 1, or mode 6 first) -- no block runs in full for
+    // its maxima, none a second time
+    tile_plan_enter(J, T);
   }
   jobs[i] = J;
 }

@@ -36,6 +36,7 @@ struct Node {
   int32_t keep;       // bialign jobs: 1 + the index of the kept rows of its parent that its outer direction resumes from (KeptRows), 0: both directions start at score 0
   int32_t keep_dir;   // the direction those rows are of: 0 forward (a first child), 1 reverse (a second child)
   int32_t limit;      // roots of a problem with a hard score limit (WFM_MODE_SCORE_LIMIT): the limit; 0: none.  sub <= limit then, and no attempt runs without it
+  int32_t meet;       // bialign children: sf + sr of the planned end of phase 1 (planned_meet below), 0: none -- the job searches for its meeting point
 };
 
 // ---- the size of a ring: `w` columns of 2 directions x 5 components x RR rows of int32 ----
@@ -170,6 +171,8 @@ struct TilePlanRules {
   bool reg = true;         // register tiles (TileCfg::reg)
   bool fine = true;        // WFM_TILE_FINE: every block of a single-tile chunk gets the workgroup size its own widest range needs
   bool coarse_on = false;  // the packed kernel keeps one maximum per block below a job's fine_s
+  bool planned = false;    // jobs with a planned end (TileJob::plan_sum) that carry fine_s = INT_MAX are among the phase's: a block of nothing but runs
+                           // up to a meeting point goes to the instantiation without per-score maxima, so that such jobs alone never launch the other
 };
 struct TileChunkPlan {
   std::vector<int> threads_b, variants_b;  // per block of the chunk: workgroup size; instantiations of the packed kernel (1 without per-score maxima, 2 with)
@@ -276,7 +279,8 @@ inline void plan_tile_chunk(const TilePlanJob* jobs, size_t n, const TilePlanRul
       if (j.mode == 0 && !reaches) p.variants_b[(size_t)b] |= 1;
     }
   }
-  for (int b = 0; b < chunk; ++b) if (!p.variants_b[(size_t)b]) p.variants_b[(size_t)b] = 2;  // (only runs up to a meeting point: either would do)
+  // (a job with a planned end in a chunk that launches both carries fine_s = INT_MAX: it never reaches it, and counts for the instantiation without maxima in every block)
+  for (int b = 0; b < chunk; ++b) if (!p.variants_b[(size_t)b]) p.variants_b[(size_t)b] = r.planned ? 1 : 2;  // (only runs up to a meeting point: either would do)
 }
 
 // ---- a child's outer direction from its parent's kept rows ("parent reuse") ----
@@ -351,6 +355,53 @@ inline int reuse_fit_cadence(const ReuseKeeper* jobs, size_t n, int cadence, int
     if (bytes <= cap_bytes) return cadence;
   }
   return 0;
+}
+
+// ---- the planned end of phase 1 of a job whose score is known ("the planned end") ----
+// The reference's first loop (wavefront_bialign_find_breakpoint, oracle/wfa2p.c) walks a fixed track of states (sf, sr): (1, 0), (1, 1), (2, 1),
+// (2, 2) ... -- the state with sf + sr = P is (ceil(P / 2), floor(P / 2)), the forward direction stepped last iff P is odd -- and leaves it at the
+// trigger Y, where the two largest antidiagonals sum to pl + tl - 1.  The second loop goes on along the SAME track (test the direction stepped
+// last against the other's newest `scope` rows, step the other), so "phase 2 from the state X" differs from "phase 2 from Y" only in the tests
+// at the states between the two, and both give the same breakpoint, field for field, if all of those fail:
+//  * X behind Y.  A test at (sf, sr) pairs row sf (or sr) with rows si <= sr (sf) of the other direction; a pair that hits in component c --
+//    o0 + o1 >= tl on a diagonal -- is an alignment of score sf + si - gopen(c) of the job in the job's own terms (below).  None is cheaper than
+//    the optimum S_own, so no test at a state with sf + sr < S_own hits; nor does the loop end there (it ends when sf + sr - (scope - 1) -
+//    max(o1, o2) reaches the best score in hand, which starts above the job's bound).
+//  * X before Y.  M[s][k] >= every gap component's [s][k] (a row's M is the maximum of its sources), so a hit in any component puts two M cells
+//    with o0 + o1 >= tl on a diagonal, whose antidiagonals 2 o - k sum to at least pl + tl: the trigger has fired by then.  No test before Y hits.
+// So every X with sf + sr <= S_own will do, and the largest leaves the fewest tests: the walk of phase 2 runs on to sf + sr = best + scope - 1 +
+// max(o1, o2) (49 past S_own at the default penalties), inside the 2 * P2K = 64 tests of one round only if X is less than 15 short of S_own.
+// S_own in terms of Node::score_rem, the score the PARENT's search credited the child with: a direction that starts in a gap component extends
+// that gap without opening it (the row of score 0 is the component's), and a gap the breakpoint cut was opened on BOTH sides of the cut (hence
+// the reference's "- gopen" in a gap breakpoint's score).  A first child (comp_end is the cut) was credited score_forward, its parent's forward
+// direction's cost INCLUDING that opening; its own search starts the reverse direction inside the gap and never pays it: S_own = score_rem -
+// gopen(comp_end).  A second child (comp_begin is the cut): S_own = score_rem - gopen(comp_begin).  The other end's component came down from an
+// ancestor whose direction started in it at score 0: nothing to subtract.  (A child that is one gap from end to end has no pattern or no text
+// and is a base job.)  D = that opening, 0 for a cut in M: exact, so the walk stays within one round.
+// second: the job is the second child of its parent (its comp_begin is the cut, not its comp_end).  -> sf + sr of X; 0: no plan (no known score)
+inline int planned_meet_sum(int score_rem, const wfm_penalties_t& pen, int comp_begin, int comp_end, bool second) {
+  if (score_rem == INT_MAX || score_rem <= 0) return 0;
+  const int cut = second ? comp_begin : comp_end;
+  const int D = cut == 0 ? 0 : ((cut == 1 || cut == 3) ? pen.o1 : pen.o2);  // (wfa_device.h: C_M 0, C_I1 1, C_I2 2, C_D1 3, C_D2 4)
+  return std::max(0, score_rem - D);
+}
+struct PlannedMeet { int sf, sr, last_fwd; };
+inline PlannedMeet planned_meet_state(int sum) { return PlannedMeet{(sum + 1) / 2, sum / 2, sum & 1}; }
+inline PlannedMeet planned_meet(int score_rem, const wfm_penalties_t& pen, int comp_begin, int comp_end, bool second) {
+  return planned_meet_state(planned_meet_sum(score_rem, pen, comp_begin, comp_end, second));
+}
+// the block of T scores the planned end lies in begins at this score: the state (s0 + tf, s0 + tr) with tf in 1 .. T, tr in 0 .. T
+inline int planned_meet_block(int sum, int T) { return ((sum + 1) / 2 - 1) / T * T; }
+// Whether a node takes its planned end (the same shape of test as reuse_eligible): it knows its score and carries the bound that came with it
+// (not so the children of a call in the unbounded WFM_SUB_SLACK configuration), and runs on the packed tile kernel on a ring no budget shaped --
+// the full one, or the narrow one the level chose for its known score (band = score_rem / 2 + 64 + chunk * T + 16: every row up to the planned
+// end, at most score_rem / 2, and the P2K rows behind it lie inside; a ring that GREW under the budget is a guess and stays on the search).
+// s_keep: the score of the keep the job resumes from (0: none) -- the block of the planned end must not be the first one after the restore
+// (reuse_resume_limit's rule: that block's input holds no gap rows 26 deep)
+inline bool planned_meet_eligible(const Node& nd, const RingPlan& rp, bool packed, int s_keep, int T) {
+  if (nd.meet <= 0 || nd.score_rem == INT_MAX || nd.sub == SUB_NONE || !rp.fits || !rp.tile_it || rp.grown || !packed) return false;
+  if (planned_meet_state(nd.meet).sf < 1) return false;
+  return s_keep <= 0 || planned_meet_block(nd.meet, T) >= s_keep + T;
 }
 
 // ---- a chunk of phase 2 from rows computed ahead (run_p2_phase): P2K more rows of both directions of every job ----

@@ -418,7 +418,8 @@ __global__ __launch_bounds__(NTMAX) void wfa_tile2_kernel(const uint32_t* __rest
   // how many of the block's last rows of the gap components go into the output snapshot: all H where somebody may read that deep (the run up to
   // the meeting point, whose output phase 2 reads; the block that runs again for such a run's sake; jobs without a third ring), else the E1 rows
   // the next block loads
-  const int t_stream = Tn - ((J.mode == 1 || J.mode == 6 || J.ring_prev < 0) ? H : E1);
+  // (or the block before a short run up to a PLANNED end, known a block ahead: TileJob::plan_deep)
+  const int t_stream = Tn - ((J.mode == 1 || J.mode == 6 || J.ring_prev < 0 || (!P2 && tile_plan_short_next(J, T))) ? H : E1);
   // per-score maxima of the antidiagonals only where the advance kernel reads them score by score (TileJob::fine_s): the block that runs again
   // because the directions met in it (mode 5), and the blocks from fine_s on -- the FINE instantiation's tiles.  Elsewhere one running maximum per
   // lane and ONE wave reduction per block (mode 1, the run up to the meeting point: none at all -- nobody reads its maxima)

@@ -310,6 +310,29 @@ int wfmh_test_reuse_plan(int op, const int64_t* in, int64_t n, int64_t* out) {
   return -1;
 }
 
+// test hook: the planned end of phase 1 (csrc/wfa_plan.h), pure arithmetic, n queries of 16 numbers, 8 results each.
+// in = x, o1, e1, o2, e2; score_rem, comp_begin, comp_end, second child (0 / 1); then for the eligibility test: the node's bound (sub, 1 << 29: none),
+// its ring plan: fits, tile_it, grown; packed; the score of the keep it resumes from (0: none); T
+// out = {sf + sr, sf, sr, last_fwd, the score the block of the planned end begins at, tf, tr, planned_meet_eligible}
+int wfmh_test_planned_meet(const int64_t* in, int64_t n, int64_t* out) {
+  for (int64_t i = 0; i < n; ++i, in += 16, out += 8) {
+    wfm_penalties_t pen{};
+    pen.x = (int)in[0]; pen.o1 = (int)in[1]; pen.e1 = (int)in[2]; pen.o2 = (int)in[3]; pen.e2 = (int)in[4];
+    const int T = (int)in[15];
+    if (T < 1) return -1;
+    const int sum = wfm::planned_meet_sum((int)in[5], pen, (int)in[6], (int)in[7], in[8] != 0);
+    const wfm::PlannedMeet m = wfm::planned_meet((int)in[5], pen, (int)in[6], (int)in[7], in[8] != 0);
+    const int b0 = wfm::planned_meet_block(sum, T);
+    wfm::Node nd{};
+    nd.score_rem = (int32_t)in[5]; nd.cb = (int32_t)in[6]; nd.ce = (int32_t)in[7]; nd.sub = (int32_t)in[9]; nd.meet = sum;
+    wfm::RingPlan rp;
+    rp.fits = in[10] != 0; rp.tile_it = in[11] != 0; rp.grown = in[12] != 0;
+    out[0] = sum; out[1] = m.sf; out[2] = m.sr; out[3] = m.last_fwd; out[4] = b0; out[5] = m.sf - b0; out[6] = m.sr - b0;
+    out[7] = wfm::planned_meet_eligible(nd, rp, in[13] != 0, (int)in[14], T) ? 1 : 0;
+  }
+  return 0;
+}
+
 // test hook: plan_tile_chunk with a direction mask per job (dirs: n bytes, bit 0 forward, bit 1 reverse); everything else as wfmh_test_tile_plan
 int wfmh_test_tile_plan_dirs(const int32_t* jobs, int64_t n, const int32_t* rules, const uint8_t* dirs, int32_t* per_block, int32_t* tasks, int64_t tasks_cap,
                              int64_t* scalars) {
