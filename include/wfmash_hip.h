@@ -449,6 +449,45 @@ int  wfm_coverage_import(wfm_handle_t* h, wfm_coverage_t* cov, const wfm_cov_ent
 int  wfm_coverage_intervals(wfm_handle_t* h, wfm_coverage_t* cov, wfm_cov_interval_t** iv, size_t* n, uint64_t totals[3]);
 void wfm_coverage_free_list(void* p);
 
+/* ---- target intervals lifted through the runs of many records ----
+ * "Where does this piece of the target lie in the query?"  A liftset is a sorted list of intervals over the concatenation of the target
+ * sequences (the coordinate space of wfm_coverage_*), uploaded once per handle; wfm_lift_runs lifts them through every problem's runs on
+ * the device (wfmash_amd/csrc/wfa_lift.hip).  The pattern is the target, the text the query as aligned; nothing goes up but runs.
+ *
+ * wfm_liftset_create: iv[0 .. n) half-open, sorted by (start, end), start < end <= n_bases; anything else is WFM_E_ARG with a message and
+ * nothing is kept.  The device also makes pm[i] = max(end[0 .. i]) (a reduce / scan-of-sums / apply prefix over blocks of
+ * WFM_LIFT_SCAN_BLOCK intervals with max in place of sum): the intervals that can overlap a span [a, b) are the indices in [lo, hi), lo = the
+ * first i with pm[i] > a, hi = the first i with start[i] >= b -- two binary searches, however the intervals nest -- and inside that window
+ * an interval overlaps iff end[i] > a.  n == 0 is legal: every later call returns no lifts.  The set is used with the handle it was made
+ * on and freed before it.
+ * wfm_lift_runs: probs as wfm_coverage_add takes them.  One wfm_lift_t for every (problem, interval) pair whose interval overlaps the
+ * problem's pattern span [base, base + plen), problems in problem order, a problem's intervals in ascending index; per[i] = {flags, n_runs,
+ * first, count} locates problem i's lifts.  A problem with an empty run, without runs, whose pattern span leaves [0, n_bases] or whose
+ * pattern or text span does not fit 32 bits is flagged WFM_LIFT_SPANS and has count 0 (the spans are taken before anything is written).
+ * Every field of a lift is an offset inside the problem, p* into the pattern, t* into the text.  With the interval clipped to the span,
+ * c0 = max(start, base) - base, c1 = min(end, base + plen) - base, and a pattern base called ALIGNED where an = or X run covers it: p0 =
+ * the first aligned pattern base >= c0, p1 = one past the last aligned pattern base < c1, t0 = the text base opposite p0, t1 = one past
+ * the text base opposite p1 - 1.  So an endpoint in a D run snaps inward, an I run strictly between two lifted bases lies inside
+ * [t0, t1), an I run directly before p0 or behind p1 - 1 outside it.  eq / x = the = / X columns in [p0, p1); inserted bases are
+ * (t1 - t0) - (eq + x), deleted bases (p1 - p0) - (eq + x).  Where [c0, c1) holds no aligned base the pair is still there, with p0 = p1 =
+ * c0, t0 = t1 = the text index reached at c0 and eq = x = 0: present in the target, absent from the query.
+ * Per problem the runs are indexed once (four exclusive prefixes per run as one 16-byte word); every endpoint is resolved by binary
+ * searches over them, O(log n_runs), never by a walk.  Lifts are placed by block scans, not atomics: two calls give the same bytes.  The
+ * output comes down in chunks of whole problems holding at most WFM_LIFT_OUT_MB MiB of lifts (environment, a decimal, read per call,
+ * 256; one problem at least).  Host memory owned by the caller (wfm_free_lifts); NULL and 0 without problems or pairs.  A run range that
+ * leaves the run buffer is WFM_E_ARG with a message, the outputs are NULL and the handle stays usable.  Returns WFM_OK or WFM_E_*. */
+typedef struct wfm_liftset wfm_liftset_t;
+typedef struct { uint64_t start, end; } wfm_lift_iv_t;                              /* 16 bytes; global target coordinates, half-open */
+typedef struct { uint32_t problem, interval, p0, p1, t0, t1, eq, x; } wfm_lift_t;   /* 32 bytes */
+typedef struct { uint32_t flags, n_runs; uint64_t first, count; } wfm_liftcall_t;   /* 24 bytes */
+#define WFM_LIFT_SPANS 2u          /* as WFM_COV_SPANS: nothing of the problem is lifted */
+#define WFM_LIFT_SCAN_BLOCK 1024   /* intervals one workgroup takes in the running maximum */
+int  wfm_liftset_create(wfm_handle_t* h, const wfm_lift_iv_t* iv, size_t n, uint64_t n_bases, wfm_liftset_t** out);
+void wfm_liftset_free(wfm_liftset_t* s);
+int  wfm_lift_runs(wfm_handle_t* h, const wfm_liftset_t* s, const wfm_cov_prob_t* probs, size_t n, const uint32_t* runs, size_t n_runs_total,
+                   wfm_lift_t** lifts, size_t* n_lifts, wfm_liftcall_t* per);
+void wfm_free_lifts(wfm_lift_t* p);
+
 /* ---- every score proved optimal by a banded DP ----
  * What wfm_check_runs leaves out.  For every problem of the seqset s whose result claims a score S = res[i].score, a classical
  * minimising gap-affine-2-piece DP over cells (i = pattern index, j = text index) is run on the device, restricted to a band of

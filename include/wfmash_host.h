@@ -180,6 +180,37 @@ int  wfmh_coverage_paf(wfm_handle_t* h, const char* target_fasta, const char* al
 char* wfmh_test_coverage_bedgraph(const char* const* names, const uint64_t* lengths, int n_seq, const uint64_t* starts, const uint32_t* depths,
                                   int64_t n_iv);
 
+/* ---- target intervals lifted through the records written (wfm_liftset_*, wfm_lift_runs, wfmash_hip.h) ----
+ * wfmh_set_lift(bed, out): from now on every batch of wfmh_align_paf[_multi] runs ONE more device call behind the record writers: the
+ * intervals of the BED file `bed` -- positions on the target's sequences -- are lifted through the runs of every record WRITTEN (a
+ * record the filters drop has no lines; with wfmh_set_left_align the normalised runs).  The BED is read once per run and uploaded once
+ * per handle, at the handle's first batch; nothing else goes up but runs.  No output byte of the PAF or SAM changes.  The align phase
+ * writes `out` through an ordered writer, in the order of the PAF's records and per record in ascending (start, end, input order) of the
+ * intervals: the file does not depend on the number of devices, handles, threads or the order of the batches.
+ * BED: tab-separated, three columns at least, column 4 the name ("." without one).  Skipped and counted: blank lines, lines that begin
+ * with '#', `track` and `browser` lines, fewer than three columns, a start or end that is not a plain decimal, a sequence the target
+ * does not have, start >= end, end beyond the sequence.
+ * One line per (record, overlapping interval), 14 tab-separated columns, no header:
+ *   qname qstart qend name strand tname tstart tend istart iend eq x ins del
+ * [tstart, tend): the part actually lifted, on the target sequence; [istart, iend): the input interval; [qstart, qend): where it lies on
+ * the query's forward strand; eq / x / ins / del: the = columns, X columns, inserted and deleted bases between the lifted ends.  An
+ * interval that lies in a deletion has qstart == qend, tstart == tend and eq = x = 0: present in the target, absent from the query.
+ * Either path NULL or "" switches it off.  Every call zeroes the counts.  wfmh_lift_counts: out = {records lifted, lines written, empty
+ * lifts, BED lines skipped} since then.  Off by default; with the switch off nothing new is called and no file is written.
+ * wfmh_lift_paf: the same file for an existing aligned PAF (this build's, the reference's, minimap2 -c --eqx's); nothing else runs.
+ * Lines are read and skipped exactly as wfmh_coverage_paf does; one line on stderr has the totals.  out = the same four counts.
+ * Returns 0 or WFM_E_*. */
+void wfmh_set_lift(const char* bed_path_or_null, const char* out_path_or_null);
+int  wfmh_lift_counts(uint64_t out[4]);
+int  wfmh_lift_paf(wfm_handle_t* h, const char* target_fasta, const char* aligned_paf, const char* bed_path, const char* out_path, uint64_t out[4]);
+/* Test hook (no GPU): the text side alone.  bed: the text of a BED file over n_seq target sequences; spec: lines "R<TAB>qname<TAB>qs
+ * <TAB>qe<TAB>strand<TAB>tname<TAB>ts" (a record as its PAF line has it) and "L<TAB>record<TAB>interval<TAB>p0<TAB>p1<TAB>t0<TAB>t1<TAB>eq
+ * <TAB>x" (a lift of record number `record` and interval number `interval` of the sorted list, as wfm_lift_runs gives it).  Returns
+ * "#skipped<TAB>n", one "#iv<TAB>seq<TAB>start<TAB>end<TAB>name<TAB>input order<TAB>global start<TAB>global end" per interval kept, in
+ * sorted order, then the L lines' lines of the lift file exactly as the align phase writes them; NULL for a spec it cannot read.
+ * malloc'd, wfmh_free. */
+char* wfmh_test_lift_lines(const char* const* names, const uint64_t* lengths, int n_seq, const char* bed, const char* spec);
+
 /* Test hooks: the pure host-side CIGAR functions (erode / merge / swizzle / PAF writer /
  * parseMashmapRow) behind one string interface so the CPU test-suite can check them
  * without a GPU.  fn in {erode, merge, compress, swap_start, swap_end, head_erosion,

@@ -48,6 +48,7 @@ EXPORTS = [
     "wfm_call_variants", "wfm_free_variants",
     "wfm_coverage_create", "wfm_coverage_free", "wfm_coverage_add", "wfm_coverage_export", "wfm_coverage_import", "wfm_coverage_intervals",
     "wfm_coverage_free_list",
+    "wfm_liftset_create", "wfm_liftset_free", "wfm_lift_runs", "wfm_free_lifts",
     "wfm_sketch_intersections",
 ]
 ISECT_LDS_MAX = 4096  # WFM_ISECT_LDS_MAX: the longest column sketch wfm_sketch_intersections searches in LDS
@@ -70,6 +71,9 @@ WFM_VAR_SLICE = 16384
 WFM_COV_SPANS = 2
 WFM_COV_TILE = 4096
 WFM_COV_SCAN_BLOCK = 1024
+# wfm_liftset_* / wfm_lift_runs (include/wfmash_hip.h): why a problem has no lifts, the intervals one workgroup takes in the running maximum
+WFM_LIFT_SPANS = 2
+WFM_LIFT_SCAN_BLOCK = 1024
 # wfm_check_optimal (include/wfmash_hip.h): what a problem's score was flagged for, and the band widths at which the kernel changes form
 WFM_OPT_NOT_CHECKED, WFM_OPT_SKIPPED, WFM_OPT_CHEAPER, WFM_OPT_UNREACHED = 1, 2, 4, 8
 OPT_NAMES = ("NOT_CHECKED", "SKIPPED", "CHEAPER", "UNREACHED")
@@ -163,6 +167,22 @@ class CovInterval(C.Structure):
 COV_PROB_DTYPE = np.dtype([("base", "<u8"), ("runs_off", "<u8"), ("n_runs", "<u4"), ("pad_", "<u4")])
 COV_ENTRY_DTYPE = np.dtype([("pos", "<u8"), ("delta", "<i4"), ("pad_", "<u4")])
 COV_INTERVAL_DTYPE = np.dtype([("start", "<u8"), ("depth", "<u4"), ("pad_", "<u4")])
+
+
+class Lift(C.Structure):
+    """wfm_lift_t: one (problem, interval) pair of wfm_lift_runs; every field an offset inside the problem."""
+    _fields_ = [("problem", C.c_uint32), ("interval", C.c_uint32), ("p0", C.c_uint32), ("p1", C.c_uint32), ("t0", C.c_uint32), ("t1", C.c_uint32),
+                ("eq", C.c_uint32), ("x", C.c_uint32)]
+
+
+class LiftCall(C.Structure):
+    """wfm_liftcall_t: where a problem's lifts lie in the output of wfm_lift_runs."""
+    _fields_ = [("flags", C.c_uint32), ("n_runs", C.c_uint32), ("first", C.c_uint64), ("count", C.c_uint64)]
+
+
+LIFT_IV_DTYPE = np.dtype([("start", "<u8"), ("end", "<u8")])
+LIFT_DTYPE = np.dtype([("problem", "<u4"), ("interval", "<u4"), ("p0", "<u4"), ("p1", "<u4"), ("t0", "<u4"), ("t1", "<u4"), ("eq", "<u4"), ("x", "<u4")])
+LIFTCALL_DTYPE = np.dtype([("flags", "<u4"), ("n_runs", "<u4"), ("first", "<u8"), ("count", "<u8")])
 
 
 class OptCheck(C.Structure):
@@ -602,6 +622,65 @@ class Coverage:
         return np.frombuffer(raw, dtype=COV_INTERVAL_DTYPE), tuple(int(v) for v in tot)
 
 
+class LiftSet:
+    """wfm_liftset_t: sorted intervals [(start, end)] over n_bases target bases, on the handle's device (include/wfmash_hip.h).  Close it
+    before its handle."""
+
+    def __init__(self, handle, intervals, n_bases):
+        self._h, self._L = handle, handle._L
+        self.n_bases = int(n_bases)
+        L = self._L
+        L.wfm_liftset_create.restype = C.c_int
+        L.wfm_liftset_create.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.POINTER(C.c_void_p)]
+        L.wfm_liftset_free.restype = None
+        L.wfm_liftset_free.argtypes = [C.c_void_p]
+        L.wfm_lift_runs.restype = C.c_int
+        L.wfm_lift_runs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                    C.c_void_p]
+        L.wfm_free_lifts.restype = None
+        L.wfm_free_lifts.argtypes = [C.c_void_p]
+        iv = np.zeros(len(intervals), dtype=LIFT_IV_DTYPE)
+        for i, (a, b) in enumerate(intervals):
+            iv[i] = (a, b)
+        self.n = len(iv)
+        p = C.c_void_p()
+        rc = L.wfm_liftset_create(handle._p, iv.ctypes.data if len(iv) else None, len(iv), self.n_bases, C.byref(p))
+        if rc != 0:
+            raise WfmError(f"wfm_liftset_create failed ({rc}): {handle.last_error()}")
+        self._p = p
+
+    def close(self):
+        if self._p:
+            self._L.wfm_liftset_free(self._p)
+            self._p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def lift(self, problems, runs):
+        """wfm_lift_runs.  problems: a list of (base, runs_off, n_runs); runs: the run words ((length << 2) | op).  Returns (the lifts as
+        a numpy array with the fields of Lift, the problems' records as one with the fields of LiftCall)."""
+        probs = np.zeros(len(problems), dtype=COV_PROB_DTYPE)
+        for i, (base, off, n) in enumerate(problems):
+            probs[i] = (base, off, n, 0)
+        runs = np.ascontiguousarray(runs, dtype=np.uint32)
+        per = np.zeros(max(len(problems), 1), dtype=LIFTCALL_DTYPE)
+        ptr, n = C.c_void_p(), C.c_size_t(0)
+        rc = self._L.wfm_lift_runs(self._h._p, self._p, probs.ctypes.data if len(probs) else None, len(probs),
+                                   runs.ctypes.data if len(runs) else None, len(runs), C.byref(ptr), C.byref(n), per.ctypes.data)
+        if rc != 0:
+            assert not ptr.value and n.value == 0
+            raise WfmError(f"wfm_lift_runs failed ({rc}): {self._h.last_error()}")
+        try:
+            raw = C.string_at(ptr, n.value * C.sizeof(Lift)) if n.value else b""
+        finally:
+            self._L.wfm_free_lifts(ptr)
+        return np.frombuffer(raw, dtype=LIFT_DTYPE), per[:len(problems)]
+
+
 class Handle:
     """One handle per GPU (wfm_create)."""
 
@@ -906,6 +985,11 @@ class Handle:
         finally:
             self._L.wfm_free_variants(recs, alleles)
         return np.frombuffer(raw, dtype=VARIANT_DTYPE), blob, [per[i] for i in range(n)]
+
+    def liftset(self, intervals, n_bases):
+        """wfm_liftset_create: the sorted intervals [(start, end)] over n_bases target bases on this handle's device; .lift(problems, runs)
+        lifts them through runs, .close() frees the set."""
+        return LiftSet(self, intervals, n_bases)
 
     def coverage(self, n_bases):
         """wfm_coverage_create: a depth object over n_bases target bases on this handle's device."""
@@ -1275,6 +1359,7 @@ HOST_EXPORTS = ["wfmh_test_packed_lce", "wfmh_test_is_acgt", "wfmh_align_default
                 "wfmh_test_reuse_plan", "wfmh_test_planned_meet", "wfmh_test_tile_plan_dirs", "wfmh_test_tile_interior", "wfmh_test_tile_lean_waves", "wfmh_set_verify", "wfmh_verify_counts", "wfmh_verify_paf", "wfmh_test_verify_parse",
                 "wfmh_set_verify_optimal", "wfmh_verify_optimal_counts", "wfmh_test_opt_band", "wfmh_set_left_align", "wfmh_left_align_counts", "wfmh_set_cs", "wfmh_cs_counts", "wfmh_set_variants", "wfmh_variants_counts",
                 "wfmh_set_coverage", "wfmh_coverage_counts", "wfmh_coverage_paf", "wfmh_test_coverage_bedgraph",
+                "wfmh_set_lift", "wfmh_lift_counts", "wfmh_lift_paf", "wfmh_test_lift_lines",
                 "wfmh_ani_matrix", "wfmh_ani_matrix_rows", "wfmh_free_ani_rows", "wfmh_set_ani_matrix", "wfmh_test_ani_tsv"]
 
 
@@ -1735,6 +1820,56 @@ def host_coverage_bedgraph(names, lengths, intervals) -> str:
     st = (C.c_uint64 * max(m, 1))(*[int(a) for a, _ in intervals])
     dp = (C.c_uint32 * max(m, 1))(*[int(d) for _, d in intervals])
     p = f(nm, ln, n, st, dp, m)
+    s = C.string_at(p).decode()
+    L.wfmh_free(p)
+    return s
+
+
+def set_lift(bed_path, out_path) -> None:
+    """wfmh_set_lift: every later align_paf call of the process lifts the intervals of the BED file through the records it writes, on the
+    device, and writes the lines to `out_path` (None: off); zeroes the counts."""
+    f = _host().wfmh_set_lift
+    f.restype = None
+    f.argtypes = [C.c_char_p, C.c_char_p]
+    f(os.fsencode(bed_path) if bed_path else None, os.fsencode(out_path) if out_path else None)
+
+
+def lift_counts():
+    """wfmh_lift_counts: (records lifted, lines written, empty lifts, BED lines skipped) since wfmh_set_lift."""
+    f = _host().wfmh_lift_counts
+    f.restype = C.c_int
+    f.argtypes = [C.POINTER(C.c_uint64)]
+    out = (C.c_uint64 * 4)()
+    rc = f(out)
+    if rc != 0:
+        raise WfmError(f"wfmh_lift_counts failed ({rc})")
+    return tuple(int(v) for v in out)
+
+
+def lift_paf(handle, target_fasta, aligned_paf, bed_path, out_path):
+    """wfmh_lift_paf: the lift file of an existing aligned PAF; returns (records lifted, lines written, empty lifts, BED lines skipped)."""
+    f = _host().wfmh_lift_paf
+    f.restype = C.c_int
+    f.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_uint64)]
+    out = (C.c_uint64 * 4)()
+    rc = f(handle._p, os.fsencode(target_fasta), os.fsencode(aligned_paf), os.fsencode(bed_path), os.fsencode(out_path), out)
+    if rc != 0:
+        raise WfmError(f"wfmh_lift_paf failed ({rc}): {handle.last_error()}")
+    return tuple(int(v) for v in out)
+
+
+def host_lift_lines(names, lengths, bed_text, spec) -> str:
+    """wfmh_test_lift_lines (no GPU): what the BED parser keeps, and the lift file's lines of the lifts in `spec` (include/wfmash_host.h)."""
+    L = _host()
+    f = L.wfmh_test_lift_lines
+    f.restype = C.c_void_p
+    f.argtypes = [C.POINTER(C.c_char_p), C.POINTER(C.c_uint64), C.c_int, C.c_char_p, C.c_char_p]
+    n = len(names)
+    nm = (C.c_char_p * max(n, 1))(*[x.encode() if isinstance(x, str) else x for x in names])
+    ln = (C.c_uint64 * max(n, 1))(*[int(x) for x in lengths])
+    p = f(nm, ln, n, bed_text.encode(), spec.encode())
+    if not p:
+        raise WfmError("wfmh_test_lift_lines cannot read the spec")
     s = C.string_at(p).decode()
     L.wfmh_free(p)
     return s

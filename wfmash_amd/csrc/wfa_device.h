@@ -338,6 +338,24 @@ void launch_cov_import(const void* ent, unsigned long long n, int32_t* d, hipStr
 // list's last chunk; totals: three words, zeroed before the first chunk
 void launch_cov_intervals(const void* ent, unsigned long long m, unsigned long long* sums, unsigned long long* carry, unsigned long long prev_pos,
                           unsigned long long n_bases, int last, void* iv, unsigned long long* totals, hipStream_t st);
+// wfm_liftset_* / wfm_lift_runs (wfa_lift.hip).  A problem is wfm_cov_prob_t with the place of its n_runs + 1 prefix words in `pre`; what
+// lift_index_kernel leaves per problem: its window [lo, hi) of candidate intervals, how many of them overlap it, its flags, its pattern span
+struct LiftProb {
+  uint64_t base, runs_off, pre_off;
+  uint32_t n_runs, pad_;
+};
+struct LiftWin {
+  uint64_t lo, hi, count;
+  uint32_t flags, plen;
+};
+// iv: n intervals {start, end}, 16 bytes each, sorted; maxs: n / WFM_LIFT_SCAN_BLOCK rounded up; pm: n
+void launch_lift_pm(const void* iv, unsigned long long n, unsigned long long* maxs, unsigned long long* pm, hipStream_t st);
+// pre: 16-byte words, the problems' n_runs + 1 each; win: nprob; off: nprob + 1
+void launch_lift_index(const uint32_t* runs, const LiftProb* probs, int nprob, const void* iv, const unsigned long long* pm, unsigned long long n_iv,
+                       unsigned long long n_bases, void* pre, LiftWin* win, unsigned long long* off, hipStream_t st);
+// the lifts of the problems [ka, kb), 32 bytes each; out[0] is lift number off[ka] of the call
+void launch_lift_write(const uint32_t* runs, const LiftProb* probs, const void* iv, const void* pre, const LiftWin* win, const unsigned long long* off,
+                       uint32_t ka, uint32_t kb, void* out, hipStream_t st);
 // wfm_check_optimal (wfa_optcheck.hip): a problem's forward byte copies, its ends-free allowances (clamped; 0 for the other modes),
 // its band of diagonals (wfa_optband.h) and, for the memory form, where its three row arrays begin in `rows` (32-bit elements)
 struct OptProb {

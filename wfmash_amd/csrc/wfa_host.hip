@@ -3382,6 +3382,138 @@ int wfm_coverage_intervals(wfm_handle_t* h, wfm_coverage_t* cov, wfm_cov_interva
 
 void wfm_coverage_free_list(void* p) { free(p); }
 
+// ---- target intervals lifted through the runs of many records (wfmash_hip.h; the kernels: wfa_lift.hip) ----
+struct wfm_liftset {
+  int device = 0;
+  uint64_t n = 0, n_bases = 0;
+  uint64_t* iv = nullptr;               // one block: n intervals {start, end}, then pm (n), then the blocks' maxima
+  unsigned long long* pm = nullptr;
+  mutable DevBuf<uint64_t> work;        // a call's prefix words, problems, windows, offsets and runs
+  mutable DevBuf<uint64_t> out;         // a chunk's lifts
+};
+
+static_assert(sizeof(wfm_lift_iv_t) == 16 && sizeof(wfm_lift_t) == 32 && sizeof(wfm_liftcall_t) == 24 && sizeof(LiftProb) == 32 && sizeof(LiftWin) == 32,
+              "wfmash_hip.h and wfa_device.h state these sizes");
+
+int wfm_liftset_create(wfm_handle_t* h, const wfm_lift_iv_t* iv, size_t n, uint64_t n_bases, wfm_liftset_t** out) {
+  if (!h || !out || (n && !iv)) return WFM_E_ARG;
+  *out = nullptr;
+  if (n >= ((size_t)1 << 32)) { h->err = "wfm_liftset_create: too many intervals for one set"; return WFM_E_ARG; }
+  for (size_t i = 0; i < n; ++i) {
+    if (!(iv[i].start < iv[i].end && iv[i].end <= n_bases)) {
+      h->err = "wfm_liftset_create: interval " + std::to_string(i) + " is empty or ends beyond the " + std::to_string(n_bases) + " target bases";
+      return WFM_E_ARG;
+    }
+    if (i && (iv[i].start < iv[i - 1].start || (iv[i].start == iv[i - 1].start && iv[i].end < iv[i - 1].end))) {
+      h->err = "wfm_liftset_create: interval " + std::to_string(i) + " lies before its predecessor: the intervals must be sorted by (start, end)";
+      return WFM_E_ARG;
+    }
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  std::unique_ptr<wfm_liftset> s(new wfm_liftset());
+  s->device = h->device;
+  s->n = n;
+  s->n_bases = n_bases;
+  if (n) {
+    const size_t nb = (n + WFM_LIFT_SCAN_BLOCK - 1) / WFM_LIFT_SCAN_BLOCK;
+    if (wfm_dmalloc((void**)&s->iv, (n * 3 + nb + 2) * 8) != hipSuccess) { (void)hipGetLastError(); h->err = "out of device memory (liftset)"; return WFM_E_NOMEM; }
+    s->pm = (unsigned long long*)(s->iv + n * 2);
+    hipError_t e = hipMemcpyAsync(s->iv, iv, n * sizeof(wfm_lift_iv_t), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) { launch_lift_pm(s->iv, n, s->pm + n, s->pm, h->stream); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) { wfm_dfree(s->iv); h->err = std::string("wfm_liftset_create: ") + hipGetErrorString(e); return WFM_E_HIP; }
+  }
+  *out = s.release();
+  return WFM_OK;
+}
+
+void wfm_liftset_free(wfm_liftset_t* s) {
+  if (!s) return;
+  int cur = 0;
+  const bool swap = hipGetDevice(&cur) == hipSuccess && cur != s->device;
+  if (swap) (void)hipSetDevice(s->device);
+  s->work.release();
+  s->out.release();
+  if (s->iv) wfm_dfree(s->iv);
+  if (swap) (void)hipSetDevice(cur);
+  delete s;
+}
+
+int wfm_lift_runs(wfm_handle_t* h, const wfm_liftset_t* s, const wfm_cov_prob_t* probs, size_t n, const uint32_t* runs, size_t n_runs_total,
+                  wfm_lift_t** lifts, size_t* n_lifts, wfm_liftcall_t* per) {
+  if (!h || !s || !lifts || !n_lifts || (n && (!probs || !per)) || (n_runs_total && !runs)) return WFM_E_ARG;
+  *lifts = nullptr; *n_lifts = 0;
+  if (n == 0) return WFM_OK;
+  if (n > (size_t)INT32_MAX || n_runs_total > ((size_t)1 << 31)) { h->err = "wfm_lift_runs: too many problems or runs for one call"; return WFM_E_ARG; }
+  if (s->device != h->device) {
+    h->err = "the liftset lives on device " + std::to_string(s->device) + ", the handle on " + std::to_string(h->device);
+    return WFM_E_ARG;
+  }
+  // the run ranges are validated here, before anything is launched
+  std::vector<LiftProb> lp(n);
+  uint64_t n_pre = 0;
+  for (size_t i = 0; i < n; ++i) {
+    if (!(probs[i].runs_off <= n_runs_total && (uint64_t)probs[i].n_runs <= n_runs_total - probs[i].runs_off)) {
+      h->err = "problem " + std::to_string(i) + ": its runs leave the run buffer";
+      return WFM_E_ARG;
+    }
+    lp[i] = LiftProb{probs[i].base, probs[i].runs_off, n_pre, probs[i].n_runs, 0u};
+    n_pre += (uint64_t)probs[i].n_runs + 1;
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  const auto t_call = std::chrono::steady_clock::now();
+  // (in 8-byte words; the prefix words come first: they are read 16 bytes at a time)
+  const size_t w_pre = (size_t)n_pre * 2, w_probs = n * 4, w_win = n * 4, w_off = n + 1, w_runs = (n_runs_total * 4 + 7) / 8;
+  if (s->work.ensure(w_pre + w_probs + w_win + w_off + w_runs + 2)) { h->err = "out of device memory (lift)"; return WFM_E_NOMEM; }
+  void* d_pre = s->work.p;
+  LiftProb* d_probs = (LiftProb*)(s->work.p + w_pre);
+  LiftWin* d_win = (LiftWin*)(s->work.p + w_pre + w_probs);
+  unsigned long long* d_off = (unsigned long long*)(s->work.p + w_pre + w_probs + w_win);
+  uint32_t* d_runs = (uint32_t*)(s->work.p + w_pre + w_probs + w_win + w_off);
+  HIPCHK(h, hipMemcpyAsync(d_probs, lp.data(), n * sizeof(LiftProb), hipMemcpyHostToDevice, h->stream));
+  if (n_runs_total) HIPCHK(h, hipMemcpyAsync(d_runs, runs, n_runs_total * 4, hipMemcpyHostToDevice, h->stream));
+  launch_lift_index(d_runs, d_probs, (int)n, s->iv, s->pm, s->n, s->n_bases, d_pre, d_win, d_off, h->stream);
+  HIPCHK(h, hipGetLastError());
+  std::vector<LiftWin> win(n);
+  std::vector<unsigned long long> off(n + 1);
+  HIPCHK(h, hipMemcpyAsync(win.data(), d_win, n * sizeof(LiftWin), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(off.data(), d_off, (n + 1) * 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  const auto t_index = std::chrono::steady_clock::now();
+  for (size_t i = 0; i < n; ++i) per[i] = wfm_liftcall_t{win[i].flags, probs[i].n_runs, off[i], win[i].count};
+  const unsigned long long total = off[n];
+  if (total == 0) return WFM_OK;
+  // chunks of whole problems that hold at most WFM_LIFT_OUT_MB MiB of lifts; a single problem may exceed that alone
+  const unsigned long long cap = std::max<unsigned long long>(1, (unsigned long long)(std::max(0.0, env_decimal("WFM_LIFT_OUT_MB", 256.0)) * 1048576.0) / sizeof(wfm_lift_t));
+  std::vector<std::pair<size_t, size_t>> chunks;
+  unsigned long long widest = 0;
+  for (size_t ka = 0; ka < n;) {
+    size_t kb = (size_t)(std::upper_bound(off.begin() + (ptrdiff_t)ka + 1, off.end(), off[ka] + cap) - off.begin()) - 1;
+    if (kb <= ka) kb = ka + 1;
+    if (off[kb] > off[ka]) { chunks.emplace_back(ka, kb); widest = std::max(widest, off[kb] - off[ka]); }
+    ka = kb;
+  }
+  char* host = (char*)malloc((size_t)total * sizeof(wfm_lift_t));
+  if (!host) { h->err = "out of host memory (lifts)"; return WFM_E_NOMEM; }
+  if (s->out.ensure((size_t)widest * 4)) { free(host); h->err = "out of device memory (lifts)"; return WFM_E_NOMEM; }
+  uint8_t* d_out = (uint8_t*)s->out.p;
+  const bool pinned = cs_pin_pieces(h);
+  for (const auto& c : chunks) {
+    launch_lift_write(d_runs, d_probs, s->iv, d_pre, d_win, d_off, (uint32_t)c.first, (uint32_t)c.second, d_out, h->stream);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = cs_copy_down(h, pinned, host + off[c.first] * sizeof(wfm_lift_t), d_out, (size_t)(off[c.second] - off[c.first]) * sizeof(wfm_lift_t));  // (the block is the next chunk's)
+    if (e != hipSuccess) { free(host); h->err = std::string("wfm_lift_runs: ") + hipGetErrorString(e); return WFM_E_HIP; }
+  }
+  *lifts = (wfm_lift_t*)host; *n_lifts = (size_t)total;
+  if (env_debug())
+    fprintf(stderr, "[wfm] lift: %zu problems, %zu runs, %llu intervals, %llu lifts in %zu chunks, upload + index + count %.3f ms, write + copy down %.3f ms (host clock, each ends in a synchronise)\n",
+            n, n_runs_total, (unsigned long long)s->n, total, chunks.size(), std::chrono::duration<double, std::milli>(t_index - t_call).count(),
+            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_index).count());
+  return WFM_OK;
+}
+
+void wfm_free_lifts(wfm_lift_t* p) { free(p); }
+
 // ---- every score proved optimal by a banded DP (wfmash_hip.h; the band: wfa_optband.h; the kernel: wfa_optcheck.hip) ----
 int wfm_check_optimal(wfm_handle_t* h, const wfm_penalties_t* pen, const wfm_seqset_t* s, const wfm_result_t* res, uint64_t max_cells,
                       wfm_optcheck_t* out) {

@@ -1,6 +1,7 @@
 #include "aligner.hpp"
 #include "verify_paf.hpp"
 #include "coverage_text.hpp"
+#include "lift_text.hpp"
 #include "map_queue.hpp"
 #include "parallel.hpp"
 #include "../csrc/wfa_handle.h"
@@ -16,6 +17,7 @@
 #include <cstring>
 #include <fstream>
 #include <iostream>
+#include <iterator>
 #include <map>
 #include <mutex>
 #include <sstream>
@@ -380,7 +382,8 @@ std::string Aligner::gather_text(Summary& sum, const std::vector<Fetched>& fetch
 }
 
 std::string Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<std::string>& lines, int threads, Summary& sum, uint64_t first_row,
-                                 std::string* vcf, wfm_coverage_t* coverage, const std::vector<uint64_t>* seq_offsets) {
+                                 std::string* vcf, wfm_coverage_t* coverage, const std::vector<uint64_t>* seq_offsets, std::string* lift,
+                                 const wfm_liftset_t* liftset, const std::vector<lift::Interval>* lift_intervals) {
   const bool dbg = getenv("WFM_DEBUG") != nullptr;
   BatchTimes t;
   std::vector<Fetched> rows = parse_rows(lines, first_row, sum);
@@ -390,7 +393,7 @@ std::string Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<std::stri
   std::vector<Fetched> fetched = fetch_eager(rows, threads, sum);
   if (fetched.empty()) return std::string();
   std::vector<wflign::BiwfaRecord> recs = make_records(fetched);
-  if (coverage)
+  if (coverage || liftset)
     for (wflign::BiwfaRecord& r : recs) r.target_global = (*seq_offsets)[(size_t)ref->find(r.target_name)];  // (parse_rows has found every name)
   wflign::ResidentSeqs resident;
   if (ds) {
@@ -409,6 +412,8 @@ std::string Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<std::stri
   wflign::BiwfaStats st;
   wflign::OutputFormat fmt = format_of(param, threads);
   fmt.coverage = coverage;
+  fmt.liftset = liftset;
+  fmt.lift_intervals = lift_intervals;
   const int rc = wflign::do_biwfa_alignment_batch(gpu_handle, recs, penalties_of(param), param.disable_chain_patching, filters_of(param), &st,
                                                   fmt, ds ? &resident : nullptr);
   if (rc < 0) throw std::runtime_error(std::string("[wfmash::align] GPU alignment failed: ") + st.error);
@@ -417,6 +422,8 @@ std::string Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<std::stri
   std::string out = gather_text(sum, fetched, recs);
   if (vcf)
     for (const auto& r : recs) *vcf += r.vcf;  // (a record without a line has no VCF lines: write_record)
+  if (lift)
+    for (const auto& r : recs) *lift += r.lift;  // (in the order of the records' lines: gather_text's)
   t.text = t.lap();
   if (verify::enabled() && !param.sam_format) {  // --verify: the finished lines, before they are written (SAM records carry no =/X CIGAR)
     verify::Source src;
@@ -527,9 +534,28 @@ struct Aligner::Run {
   std::ifstream& in;
   skch::OrderedWriter<std::string, TextSink> writer;
   std::unique_ptr<skch::OrderedWriter<std::string, TextSink>> vcf_writer;  // --variants: the second file, keyed by the same batch numbers
-  // --coverage: where each target sequence begins in the concatenation (nseq + 1 values; empty: the switch is off), and the depth object
+  // --lift: the third file, keyed by the same batch numbers; the BED's intervals sorted as the device takes them, and the liftset of every
+  // handle the run has used so far, made at the handle's first batch
+  std::unique_ptr<skch::OrderedWriter<std::string, TextSink>> lift_writer;
+  std::vector<lift::Interval> lift_iv;
+  std::mutex lift_mu;
+  std::vector<std::pair<wfm_handle_t*, wfm_liftset_t*>> liftsets;
+  const wfm_liftset_t* liftset_of(wfm_handle_t* h) {
+    if (!lift_writer) return nullptr;
+    std::lock_guard<std::mutex> lk(lift_mu);
+    for (auto& hs : liftsets) if (hs.first == h) return hs.second;
+    std::vector<wfm_lift_iv_t> raw(lift_iv.size());
+    for (size_t i = 0; i < raw.size(); ++i) raw[i] = wfm_lift_iv_t{lift_iv[i].gstart, lift_iv[i].gend};
+    wfm_liftset_t* s = nullptr;
+    std::lock_guard<std::mutex> hl(wflign::handle_lock(h));
+    if (wfm_liftset_create(h, raw.data(), raw.size(), seq_offsets.back(), &s) != WFM_OK) throw std::runtime_error(std::string("[wfmash::align] --lift: ") + wfm_last_error(h));
+    liftsets.emplace_back(h, s);
+    return s;
+  }
+  // --coverage, --lift: where each target sequence begins in the concatenation (nseq + 1 values; empty: both are off).  --coverage: the depth object
   // of every handle the run has used so far, made at the handle's first batch
   std::vector<uint64_t> seq_offsets;
+  bool coverage_on = false;
   std::mutex coverage_mu;
   std::vector<std::pair<wfm_handle_t*, wfm_coverage_t*>> coverage;
   ~Run() {
@@ -537,9 +563,13 @@ struct Aligner::Run {
       std::lock_guard<std::mutex> lk(wflign::handle_lock(hc.first));
       wfm_coverage_free(hc.second);
     }
+    for (auto& hs : liftsets) {
+      std::lock_guard<std::mutex> lk(wflign::handle_lock(hs.first));
+      wfm_liftset_free(hs.second);
+    }
   }
   wfm_coverage_t* coverage_of(wfm_handle_t* h) {
-    if (seq_offsets.empty()) return nullptr;
+    if (!coverage_on) return nullptr;
     std::lock_guard<std::mutex> lk(coverage_mu);
     for (auto& hc : coverage) if (hc.first == h) return hc.second;
     wfm_coverage_t* c = nullptr;
@@ -635,12 +665,14 @@ void Aligner::run_worker(Run& run, size_t wk) {
       { std::lock_guard<std::mutex> lk(run.read_mu); more = run.more_rows; beside = run.in_flight[dev].fetch_add(1); }
       wfm_set_concurrent_calls(run.use[wk], beside + (more && run.plan.per_gpu > 1 ? 1 : 0));
       struct Leave { std::atomic<int>& a; ~Leave() { a.fetch_sub(1); } } leave{run.in_flight[dev]};
-      std::string vcf;
+      std::string vcf, lifted;
       std::string text = align_batch(run.use[wk], batch, run.threads_each, run.part[wk], first_row, run.vcf_writer ? &vcf : nullptr,
-                                     run.coverage_of(run.use[wk]), &run.seq_offsets);
+                                     run.coverage_of(run.use[wk]), &run.seq_offsets, run.lift_writer ? &lifted : nullptr, run.liftset_of(run.use[wk]),
+                                     &run.lift_iv);
       const double at1 = run.ms();
       run.writer.put((uint64_t)seq, std::move(text));
       if (run.vcf_writer) run.vcf_writer->put((uint64_t)seq, std::move(vcf));
+      if (run.lift_writer) run.lift_writer->put((uint64_t)seq, std::move(lifted));
       if (getenv("WFM_DEBUG"))
         fprintf(stderr, "[wfmash::align] worker %zu: batch %lld from +%.0f ms to +%.0f ms, written at +%.0f ms\n", wk, (long long)seq, at0, at1, run.ms());
     }
@@ -757,8 +789,27 @@ Summary Aligner::compute() {
   if (!cov_path.empty()) {  // --coverage: the file is opened before anything is aligned, and written once the workers are done
     covstream.open(cov_path);
     if (!covstream.is_open()) throw std::runtime_error("[wfmash::align] Error! Failed to open the coverage file: " + cov_path);
+    run.coverage_on = true;
+  }
+  std::ofstream liftstream;
+  std::string lift_bed, lift_out;
+  wflign::lift_paths(lift_bed, lift_out);
+  if (!cov_path.empty() || !lift_out.empty()) {
     run.seq_offsets.assign(1, 0);
     for (int i = 0; i < ref->nseq(); ++i) run.seq_offsets.push_back(run.seq_offsets.back() + (uint64_t)ref->length(i));
+  }
+  if (!lift_out.empty()) {  // --lift: the BED is read once, here; the batches' lines go through a third ordered writer
+    std::ifstream bed(lift_bed, std::ios::binary);
+    if (!bed.is_open()) throw std::runtime_error("[wfmash::align] Error! Failed to open the BED file of --lift: " + lift_bed);
+    const std::string text((std::istreambuf_iterator<char>(bed)), std::istreambuf_iterator<char>());
+    std::vector<uint64_t> lengths;
+    for (int i = 0; i < ref->nseq(); ++i) lengths.push_back((uint64_t)ref->length(i));
+    lift::Bed parsed = lift::parse_bed(text, [&](const std::string& name) { return ref->find(name); }, lengths, run.seq_offsets);
+    run.lift_iv = std::move(parsed.iv);
+    wflign::lift_bed_read(parsed.skipped);
+    liftstream.open(lift_out);
+    if (!liftstream.is_open()) throw std::runtime_error("[wfmash::align] Error! Failed to open the lift file: " + lift_out);
+    run.lift_writer.reset(new skch::OrderedWriter<std::string, TextSink>(TextSink{&liftstream}));
   }
   const size_t nworkers = run.plan.nworkers;
   static const bool own_handles = !(getenv("WFM_ALIGN_OWN_HANDLES") && atoi(getenv("WFM_ALIGN_OWN_HANDLES")) == 0);
@@ -780,6 +831,7 @@ Summary Aligner::compute() {
   sum_up(sum, run.part, t0);
   outstream.close();
   if (vcfstream.is_open()) vcfstream.close();
+  if (liftstream.is_open()) liftstream.close();
   sum.ms_total = ms_since(t0);
   std::cerr << "[wfmash::align] total aligned records = " << sum.records << ", total aligned bp = " << sum.aligned_bp
             << ", completed in " << (uint64_t)(sum.ms_total / 1000.0) << " seconds" << std::endl;

@@ -13,6 +13,7 @@
 #include "../csrc/wfa_optband.h"
 #include "aligner.hpp"
 #include "fasta.hpp"
+#include "lift_text.hpp"
 #include "map_stats.hpp"
 
 extern "C" {
@@ -108,6 +109,49 @@ int wfmh_align_paf_multi(wfm_handle_t* const* handles, int n, const char* target
 extern "C" {
 
 void wfmh_free(char* p) { free(p); }
+
+// test hook (no GPU): the text side of --lift (lift_text.hpp): what the parser makes of a BED, and the lines of given lifts
+char* wfmh_test_lift_lines(const char* const* names, const uint64_t* lengths, int n_seq, const char* bed, const char* spec) {
+  if (n_seq < 0 || (n_seq && (!names || !lengths)) || !bed || !spec) return nullptr;
+  std::vector<std::string> nm;
+  std::vector<uint64_t> len, off(1, 0);
+  for (int i = 0; i < n_seq; ++i) { nm.push_back(names[i]); len.push_back(lengths[i]); off.push_back(off.back() + lengths[i]); }
+  const lift::Bed parsed = lift::parse_bed(std::string(bed), [&](const std::string& name) {
+    for (size_t i = 0; i < nm.size(); ++i) if (nm[i] == name) return (int)i;
+    return -1;
+  }, len, off);
+  std::string out = lift::bed_dump(parsed);
+  std::vector<lift::Record> recs;
+  std::istringstream in(spec);
+  std::string line;
+  while (std::getline(in, line)) {
+    if (line.empty()) continue;
+    std::vector<std::string> f;
+    for (size_t at = 0;;) {
+      const size_t tab = line.find('\t', at);
+      f.push_back(line.substr(at, tab == std::string::npos ? std::string::npos : tab - at));
+      if (tab == std::string::npos) break;
+      at = tab + 1;
+    }
+    uint64_t v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (f[0] == "R" && f.size() == 7) {
+      lift::Record r;
+      r.qname = f[1]; r.tname = f[5]; r.rev = f[4] == "-";
+      if (!lift::decimal(f[2], 0, f[2].size(), &r.qs) || !lift::decimal(f[3], 0, f[3].size(), &r.qe) || !lift::decimal(f[6], 0, f[6].size(), &r.ts)) return nullptr;
+      recs.push_back(r);
+    } else if (f[0] == "L" && f.size() == 9) {
+      for (int k = 0; k < 8; ++k)
+        if (!lift::decimal(f[(size_t)k + 1], 0, f[(size_t)k + 1].size(), &v[k]) || v[k] > 0xffffffffull) return nullptr;
+      if (v[0] >= recs.size() || v[1] >= parsed.iv.size()) return nullptr;
+      lift::lift_line(out, recs[(size_t)v[0]], parsed.iv[(size_t)v[1]], (uint32_t)v[2], (uint32_t)v[3], (uint32_t)v[4], (uint32_t)v[5], (uint32_t)v[6], (uint32_t)v[7]);
+    } else {
+      return nullptr;
+    }
+  }
+  char* p = (char*)malloc(out.size() + 1);
+  if (p) memcpy(p, out.c_str(), out.size() + 1);
+  return p;
+}
 
 // test hook: the sub-window translation of the problems by reference (wflign::sub_window_off)
 void wfmh_test_subwindow(int64_t win_start, int64_t win_end, int rev, int64_t a, int64_t b, int64_t* out_start, int64_t* out_end) {

@@ -55,6 +55,16 @@
 //   --coverage-paf IN.paf --coverage FILE target.fa   the same file for an existing aligned PAF (this build's, the reference's,
 //                                              minimap2 -c --eqx's): no mapping, no alignment; lines without an =XID cg:Z:, malformed
 //                                              lines, unknown targets and other tlens are skipped and counted; only --device beside it
+//   --lift IN.bed --lift-out FILE              where the BED's target intervals lie in every query: the intervals are lifted on the device
+//                                              through the runs of every record WRITTEN (wfm_lift_runs; nothing goes up but runs), one
+//                                              line per (record, overlapping interval) in the order of the PAF's records: qname qstart qend
+//                                              name strand tname tstart tend istart iend eq x ins del; an interval in a deletion has
+//                                              qstart == qend; no output byte of the PAF or SAM changes; allowed with -a, -d, -i, -K,
+//                                              --gpus, --resident-seqs, --verify, --verify-optimal, --left-align (the lifts are then those
+//                                              of the normalised runs), --cs, --variants and --coverage, refused with -m and --verify-paf;
+//                                              each of the two is an error without the other; off by default
+//   --lift-paf IN.paf --lift IN.bed --lift-out FILE target.fa   the same file for an existing aligned PAF: no mapping, no alignment;
+//                                              lines are skipped and counted as --coverage-paf does; only --device beside it
 //   --verify-paf FILE target.fa [query.fa]     the same check on an existing aligned PAF (this build's or the reference's): no mapping,
 //                                              no alignment; exit status 3 if a line fails
 //   --ani-matrix FILE [--ani-only]             the group-by-group ANI table the identity estimate (-p aniN) is made from, as TSV: per
@@ -149,6 +159,8 @@ static void usage() {
           "            --variants FILE write the SNVs, insertions and deletions of every record, called on the GPU, as a VCF (unsorted; not with -m, --verify-paf)\n"
           "            --coverage FILE write the per-base depth of every target sequence, summed on the GPU over the records written, as a bedGraph (not with -m, --verify-paf)\n"
           "            --coverage-paf FILE with --coverage: the depth of an existing aligned PAF over target.fa, and stop (only --device beside it)\n"
+          "            --lift BED --lift-out FILE lift the BED's target intervals through every record written, on the GPU: one line per record and interval (not with -m, --verify-paf)\n"
+          "            --lift-paf FILE with --lift, --lift-out: lift through an existing aligned PAF over target.fa, and stop (only --device beside it)\n"
           "            --verify-paf FILE check an existing aligned PAF against target.fa [query.fa] and stop (exit status 3 if a line fails)\n"
           "  other     --out FILE [stdout]   --device INT [0]   --gpus N|all [1] GPUs of this node, starting at --device\n"
           "            -B DIR directory of the hand-off file [cwd]   -Z keep the hand-off file   --quiet (no effect)\n");
@@ -160,8 +172,9 @@ int main(int argc, char** argv) {
   ap.threads = 1;  // -t, default 1 as in the reference (parse_args.hpp: thread_count); the C ABI default (0) means all cores
   wfmh_map_params_t mp;
   wfmh_map_default_params(&mp);
-  std::string mapping_in, out = "/dev/stdout", target, query, seeds_in, scaffold_out, tmp_base, verify_in, ani_matrix_out, variants_out, coverage_out, coverage_in;
+  std::string mapping_in, out = "/dev/stdout", target, query, seeds_in, scaffold_out, tmp_base, verify_in, ani_matrix_out, variants_out, coverage_out, coverage_in, lift_bed, lift_out, lift_in;
   bool other_options = false;  // --coverage-paf: anything beside it, --coverage, --device and the target
+  bool lift_other = false;     // --lift-paf: anything beside it, --lift, --lift-out, --device and the target
   bool verify = false, verify_optimal = false, ani_only = false, left_align = false;
   uint64_t verify_optimal_cells = 0;
   int cs_form = 0;  // --cs: 0 off, 1 short, 2 long
@@ -169,6 +182,7 @@ int main(int argc, char** argv) {
   int device = 0, gpus = 1;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
+    if (a[0] == '-' ? (a != "--lift" && a != "--lift-out" && a != "--lift-paf" && a != "--device" && a != "-h" && a != "--help") : !target.empty()) lift_other = true;
     if (a[0] == '-' ? (a != "--coverage" && a != "--coverage-paf" && a != "--device" && a != "-h" && a != "--help") : !target.empty()) other_options = true;
     auto next = [&](const char* name) -> std::string {
       if (i + 1 >= argc) { fprintf(stderr, "[wfmash] ERROR: missing value for %s\n", name); exit(1); }
@@ -305,6 +319,9 @@ int main(int argc, char** argv) {
     else if (a == "--variants") variants_out = next("--variants");
     else if (a == "--coverage") coverage_out = next("--coverage");
     else if (a == "--coverage-paf") coverage_in = next("--coverage-paf");
+    else if (a == "--lift") lift_bed = next("--lift");
+    else if (a == "--lift-out") lift_out = next("--lift-out");
+    else if (a == "--lift-paf") lift_in = next("--lift-paf");
     else if (a == "--verify-optimal-cells") verify_optimal_cells = std::strtoull(next("--verify-optimal-cells").c_str(), nullptr, 10);
     else if (a == "--verify-paf") verify_in = next("--verify-paf");
     else if (a == "-h" || a == "--help") { usage(); return 0; }
@@ -323,6 +340,12 @@ int main(int argc, char** argv) {
   if (!coverage_out.empty() && approx_only) { fprintf(stderr, "[wfmash] ERROR: --coverage counts alignments: it cannot be combined with -m\n"); return 1; }
   if (!coverage_out.empty() && !verify_in.empty()) { fprintf(stderr, "[wfmash] ERROR: --coverage belongs to the align phase: it cannot be combined with --verify-paf\n"); return 1; }
   if (!coverage_in.empty() && coverage_out.empty()) { fprintf(stderr, "[wfmash] ERROR: --coverage-paf needs --coverage FILE\n"); return 1; }
+  if (!lift_bed.empty() && lift_out.empty()) { fprintf(stderr, "[wfmash] ERROR: --lift needs --lift-out FILE\n"); return 1; }
+  if (lift_bed.empty() && !lift_out.empty()) { fprintf(stderr, "[wfmash] ERROR: --lift-out needs --lift IN.bed\n"); return 1; }
+  if (!lift_in.empty() && lift_bed.empty()) { fprintf(stderr, "[wfmash] ERROR: --lift-paf needs --lift IN.bed and --lift-out FILE\n"); return 1; }
+  if (!lift_bed.empty() && approx_only) { fprintf(stderr, "[wfmash] ERROR: --lift lifts through alignments: it cannot be combined with -m\n"); return 1; }
+  if (!lift_bed.empty() && !verify_in.empty()) { fprintf(stderr, "[wfmash] ERROR: --lift belongs to the align phase: it cannot be combined with --verify-paf\n"); return 1; }
+  if (!lift_in.empty() && lift_other) { fprintf(stderr, "[wfmash] ERROR: --lift-paf runs nothing else: besides --lift IN.bed, --lift-out FILE and the target FASTA it takes the number of the GPU only\n"); return 1; }
   if (!coverage_in.empty() && other_options) { fprintf(stderr, "[wfmash] ERROR: --coverage-paf runs nothing else: besides --coverage FILE and the target FASTA it takes the number of the GPU only\n"); return 1; }
   if (verify_optimal && approx_only) { fprintf(stderr, "[wfmash] ERROR: --verify-optimal checks alignment scores: it cannot be combined with -m\n"); return 1; }
   if (verify_optimal_cells && !verify_optimal) { fprintf(stderr, "[wfmash] ERROR: --verify-optimal-cells needs --verify-optimal\n"); return 1; }
@@ -336,6 +359,15 @@ int main(int argc, char** argv) {
     return 1;
   }
   if (!ani_matrix_out.empty() && !verify_in.empty()) { fprintf(stderr, "[wfmash] ERROR: --ani-matrix cannot be combined with --verify-paf\n"); return 1; }
+  if (!lift_in.empty()) {  // the BED through an existing PAF; nothing else runs
+    wfm_handle_t* hl = nullptr;
+    if (wfm_create(device, &hl) != WFM_OK) { fprintf(stderr, "[wfmash] ERROR: no usable MI355X device %d (there is no CPU fallback)\n", device); return 2; }
+    uint64_t lc[4] = {0, 0, 0, 0};
+    const int lrc = wfmh_lift_paf(hl, target.c_str(), lift_in.c_str(), lift_bed.c_str(), lift_out.c_str(), lc);
+    if (lrc != WFM_OK) fprintf(stderr, "[wfmash::lift] ERROR: %s\n", wfm_last_error(hl));
+    wfm_destroy(hl);
+    return lrc == WFM_OK ? 0 : 2;
+  }
   if (!coverage_in.empty()) {  // the depth of an existing PAF; nothing else runs
     wfm_handle_t* hc = nullptr;
     if (wfm_create(device, &hc) != WFM_OK) { fprintf(stderr, "[wfmash] ERROR: no usable MI355X device %d (there is no CPU fallback)\n", device); return 2; }
@@ -466,6 +498,7 @@ int main(int argc, char** argv) {
     if (cs_form) wfmh_set_cs(cs_form);
     if (!variants_out.empty()) wfmh_set_variants(variants_out.c_str());
     if (!coverage_out.empty()) wfmh_set_coverage(coverage_out.c_str());
+    if (!lift_bed.empty()) wfmh_set_lift(lift_bed.c_str(), lift_out.c_str());
     rc = wfmh_align_paf_multi(hs.data(), (int)hs.size(), target.c_str(), q, mapping.c_str(), out.c_str(), &ap, &s);
     if (rc == WFM_OK)
       fprintf(stderr, "[wfmash::align] %llu records, %llu aligned bp, %.1f ms GPU kernels, %.1f ms total => %.3g aligned bp/s\n",
@@ -488,6 +521,12 @@ int main(int argc, char** argv) {
       wfmh_variants_counts(vc);
       fprintf(stderr, "[wfmash::variants] %llu records, %llu variants written, %llu SNVs masked, %llu records left alone\n", (unsigned long long)vc[0],
               (unsigned long long)vc[1], (unsigned long long)vc[2], (unsigned long long)vc[3]);
+    }
+    if (!lift_bed.empty() && rc == WFM_OK) {
+      uint64_t lc[4] = {0, 0, 0, 0};
+      wfmh_lift_counts(lc);
+      fprintf(stderr, "[wfmash::lift] %llu records lifted, %llu lines written, %llu of them empty, %llu BED lines skipped\n", (unsigned long long)lc[0],
+              (unsigned long long)lc[1], (unsigned long long)lc[2], (unsigned long long)lc[3]);
     }
     if (!coverage_out.empty() && rc == WFM_OK) {
       uint64_t cc[4] = {0, 0, 0, 0};

@@ -16,6 +16,7 @@
 #include "../csrc/wfa_handle.h"
 #include "aligner.hpp"
 #include "coverage_text.hpp"
+#include "lift_text.hpp"
 #include "parallel.hpp"
 #include "wflign_hip.hpp"
 
@@ -283,6 +284,94 @@ int wfmh_coverage_paf(wfm_handle_t* h, const char* target_fasta, const char* ali
     return WFM_OK;
   } catch (const std::exception& e) {
     if (cov) wfm_coverage_free(cov);
+    std::cerr << e.what() << std::endl;
+    wfm_set_error(h, e.what());
+    return WFM_E_ARG;
+  }
+}
+
+// --lift-paf: the BED intervals lifted through an existing aligned PAF.  Lines go to the device in batches of runs, read and skipped by
+// wfmh_coverage_paf's rules (coverage::classify_line); nothing else runs.
+int wfmh_lift_paf(wfm_handle_t* h, const char* target_fasta, const char* aligned_paf, const char* bed_path, const char* out_path, uint64_t out[4]) {
+  if (!h || !target_fasta || !aligned_paf || !bed_path || !out_path) return WFM_E_ARG;
+  wfm_liftset_t* set = nullptr;
+  try {
+    std::shared_ptr<wfmash_host::FastaStore> target = wfmash_host::open_shared(target_fasta);
+    std::ifstream in(aligned_paf);
+    if (!in.is_open()) throw std::runtime_error(std::string("[wfmash::lift] cannot open ") + aligned_paf);
+    std::ifstream bedstream(bed_path, std::ios::binary);
+    if (!bedstream.is_open()) throw std::runtime_error(std::string("[wfmash::lift] cannot open ") + bed_path);
+    const std::string bed_text((std::istreambuf_iterator<char>(bedstream)), std::istreambuf_iterator<char>());
+    std::ofstream outstream(out_path);
+    if (!outstream.is_open()) throw std::runtime_error(std::string("[wfmash::lift] cannot open ") + out_path);
+    std::vector<uint64_t> lengths, offsets(1, 0);
+    for (int i = 0; i < target->nseq(); ++i) {
+      lengths.push_back((uint64_t)target->length(i));
+      offsets.push_back(offsets.back() + lengths.back());
+    }
+    const lift::Bed bed = lift::parse_bed(bed_text, [&](const std::string& name) { return target->find(name); }, lengths, offsets);
+    auto device = [&](int rc, const char* what) {
+      if (rc < 0) throw std::runtime_error(std::string("[wfmash::lift] ") + what + " failed: " + wfm_last_error(h));
+      return rc;
+    };
+    std::lock_guard<std::mutex> lk(wflign::handle_lock(h));
+    {
+      std::vector<wfm_lift_iv_t> raw(bed.iv.size());
+      for (size_t i = 0; i < raw.size(); ++i) raw[i] = wfm_lift_iv_t{bed.iv[i].gstart, bed.iv[i].gend};
+      device(wfm_liftset_create(h, raw.data(), raw.size(), offsets.back(), &set), "create");
+    }
+    uint64_t lifted = 0, n_lines = 0, empty = 0, skipped[5] = {0, 0, 0, 0, 0};
+    std::vector<wfm_cov_prob_t> probs;
+    std::vector<uint32_t> runs;
+    std::vector<lift::Record> where;
+    std::vector<wfm_liftcall_t> per;
+    std::string text;
+    auto flush = [&]() {
+      if (probs.empty()) return;
+      per.resize(probs.size());
+      wfm_lift_t* lifts = nullptr;
+      size_t n = 0;
+      device(wfm_lift_runs(h, set, probs.data(), probs.size(), runs.data(), runs.size(), &lifts, &n, per.data()), "lift");
+      text.clear();
+      for (size_t j = 0; j < probs.size(); ++j) {
+        if (per[j].flags) { skipped[coverage::LINE_MALFORMED]++; continue; }  // (a span that leaves the target: classify_line lets none through)
+        ++lifted;
+        for (uint64_t k = per[j].first; k < per[j].first + per[j].count; ++k) {
+          const wfm_lift_t& l = lifts[k];
+          lift::lift_line(text, where[j], bed.iv[l.interval], l.p0, l.p1, l.t0, l.t1, l.eq, l.x);
+          empty += l.eq + l.x == 0;
+        }
+        n_lines += per[j].count;
+      }
+      wfm_free_lifts(lifts);
+      outstream << text;
+      probs.clear(); runs.clear(); where.clear();
+    };
+    std::string line;
+    verify::Line l;
+    while (std::getline(in, line)) {
+      if (line.empty() || line[0] == '@') continue;
+      int ti = -1;
+      const int code = coverage::classify_line(line, [&](const std::string& name) { return target->find(name); }, lengths, l, &ti);
+      if (code != coverage::LINE_ADD) { skipped[code]++; continue; }
+      probs.push_back(wfm_cov_prob_t{offsets[(size_t)ti] + (uint64_t)l.ts, (uint64_t)runs.size(), (uint32_t)l.runs.size(), 0u});
+      runs.insert(runs.end(), l.runs.begin(), l.runs.end());
+      lift::Record r;
+      r.qname = l.qname; r.tname = l.tname; r.qs = (uint64_t)l.qs; r.qe = (uint64_t)l.qe; r.ts = (uint64_t)l.ts; r.rev = l.rev;
+      where.push_back(std::move(r));
+      if (probs.size() >= 65536 || runs.size() >= ((size_t)16 << 20)) flush();
+    }
+    flush();
+    wfm_liftset_free(set);
+    set = nullptr;
+    const uint64_t all_skipped = skipped[1] + skipped[2] + skipped[3] + skipped[4];
+    std::cerr << "[wfmash::lift] " << bed.iv.size() << " intervals (" << bed.skipped << " BED lines skipped), " << lifted << " lines lifted, " << all_skipped
+              << " skipped (" << skipped[1] << " without an =XID cg:Z:, " << skipped[2] << " malformed, " << skipped[3] << " with an unknown target, " << skipped[4]
+              << " with another tlen), " << n_lines << " lifts written, " << empty << " of them empty" << std::endl;
+    if (out) { out[0] = lifted; out[1] = n_lines; out[2] = empty; out[3] = bed.skipped; }
+    return WFM_OK;
+  } catch (const std::exception& e) {
+    if (set) wfm_liftset_free(set);
     std::cerr << e.what() << std::endl;
     wfm_set_error(h, e.what());
     return WFM_E_ARG;

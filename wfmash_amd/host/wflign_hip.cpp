@@ -3,6 +3,7 @@
 // through wfm_align_batch (no CPU fallback).
 #include "wflign_hip.hpp"
 #include "parallel.hpp"
+#include "lift_text.hpp"
 #include "../csrc/wfa_handle.h"
 
 #include <algorithm>
@@ -70,6 +71,13 @@ std::atomic<bool> g_coverage{false};
 std::mutex g_coverage_mu;
 std::string g_coverage_path;
 std::atomic<uint64_t> g_coverage_counts[4];
+
+// --lift: the process-wide switch, the BED of target intervals and the file the align phase writes, and {records lifted, lines written,
+// empty lifts, BED lines skipped} since it was set
+std::atomic<bool> g_lift{false};
+std::mutex g_lift_mu;
+std::string g_lift_bed, g_lift_out;
+std::atomic<uint64_t> g_lift_counts[4];
 
 // The problems of one device call, always written by reference (a side without a store id carries its host pointer); without a
 // store they go to the device as plain wfm_problem_t, as they always have.
@@ -673,7 +681,92 @@ int coverage_records(BiwfaBatch& b) {
     fprintf(stderr, "[wflign] coverage: %zu records, %zu runs, %d flagged, %.1f ms\n", probs.size(), runs.size(), rc, ms_between(t0, Clock::now()));
   return 0;
 }
+// ---- --lift: the BED intervals through the runs of every record WRITTEN, ONE device call per batch (wfm_lift_runs).  It runs where
+// coverage_records runs and takes the same problems: the part of the ops the line spells, at base = the target sequence's offset in the
+// concatenation + the target start the writer wrote; the query window is the writer's too (variant_records' qs, qe).  Nothing goes up
+// but runs.  The lines of a record go into BiwfaRecord::lift in the order the device gives them: ascending interval.  A record the device
+// refuses, or whose ops its runs cannot hold, is a defect: it has no lines and is reported. ----
+int lift_records(BiwfaBatch& b) {
+  const auto t0 = Clock::now();
+  std::vector<wfm_cov_prob_t> probs;
+  std::vector<uint32_t> runs;
+  std::vector<size_t> rec_of;
+  std::vector<lift::Record> where;
+  uint64_t unknown = 0;
+  for (size_t ri = 0; ri < b.recs.size(); ++ri) {
+    BiwfaRecord& r = b.recs[ri];
+    r.lift.clear();
+    if (!r.ok || !r.written) continue;
+    const CigarOps& ops = r.ops;
+    size_t ob = 0, oe = ops.size();
+    uint64_t ta = 0, qa = 0, q_len = 0;
+    while (ob < oe && (ops[ob].second == 'I' || ops[ob].second == 'D')) { (ops[ob].second == 'D' ? ta : qa) += (uint64_t)ops[ob].first; ++ob; }
+    while (oe > ob && (ops[oe - 1].second == 'I' || ops[oe - 1].second == 'D')) --oe;
+    if (oe == ob) continue;
+    wfm_cov_prob_t p{r.target_global + r.target_offset + ta, (uint64_t)runs.size(), (uint32_t)(oe - ob), 0u};
+    bool known = true;
+    for (size_t k = ob; k < oe; ++k) {
+      const char c = ops[k].second;
+      const uint32_t op = c == '=' ? 0u : c == 'X' ? 1u : c == 'I' ? 2u : c == 'D' ? 3u : 4u;
+      if (op > 3u || ops[k].first <= 0 || (uint32_t)ops[k].first >= (1u << 30)) { known = false; break; }
+      runs.push_back(((uint32_t)ops[k].first << 2) | op);
+      if (op != 3u) q_len += (uint64_t)ops[k].first;
+    }
+    if (!known) { runs.resize((size_t)p.runs_off); ++unknown; continue; }
+    lift::Record lr;
+    lr.qname = r.query_name; lr.tname = r.target_name; lr.rev = r.query_is_rev;
+    lr.qs = r.query_is_rev ? r.query_offset + (r.query_length - qa - q_len) : r.query_offset + qa;
+    lr.qe = lr.qs + q_len;
+    lr.ts = r.target_offset + ta;
+    probs.push_back(p);
+    rec_of.push_back(ri);
+    where.push_back(std::move(lr));
+  }
+  int rc = WFM_OK;
+  wfm_lift_t* lifts = nullptr;
+  size_t n_lifts = 0;
+  std::vector<wfm_liftcall_t> per(probs.size());
+  auto t1 = t0;
+  if (!probs.empty()) {
+    std::lock_guard<std::mutex> lk(handle_lock(b.h));
+    t1 = Clock::now();
+    rc = wfm_lift_runs(b.h, b.fmt.liftset, probs.data(), probs.size(), runs.data(), runs.size(), &lifts, &n_lifts, per.data());
+    if (rc < 0 && b.stats) b.stats->error = wfm_last_error(b.h);
+  }
+  if (rc < 0) return rc;
+  const auto t2 = Clock::now();
+  const std::vector<lift::Interval>& iv = *b.fmt.lift_intervals;
+  std::atomic<uint64_t> lines{0}, empty{0}, refused{0};
+  for_each_record(probs.size(), b.fmt.threads, [&](size_t j) {
+    if (per[j].flags) { refused += 1; return; }
+    std::string& out = b.recs[rec_of[j]].lift;
+    uint64_t e = 0;
+    for (uint64_t k = per[j].first; k < per[j].first + per[j].count; ++k) {
+      const wfm_lift_t& l = lifts[k];
+      lift::lift_line(out, where[j], iv[l.interval], l.p0, l.p1, l.t0, l.t1, l.eq, l.x);
+      e += l.eq + l.x == 0;
+    }
+    lines += per[j].count; empty += e;
+  });
+  wfm_free_lifts(lifts);
+  g_lift_counts[0] += probs.size() - refused.load(); g_lift_counts[1] += lines.load(); g_lift_counts[2] += empty.load();
+  if (refused.load() || unknown)
+    fprintf(stderr, "[wflign] lift: %llu records of a batch were NOT lifted (their runs leave the target or cannot be held)\n",
+            (unsigned long long)(refused.load() + unknown));
+  if (getenv("WFM_DEBUG"))
+    fprintf(stderr, "[wflign] lift: %zu records, %zu runs, %zu lifts, %.1f ms (runs %.1f, device call %.1f, text %.1f)\n", probs.size(), runs.size(), n_lifts,
+            ms_between(t0, Clock::now()), ms_between(t0, t1), ms_between(t1, t2), ms_between(t2, Clock::now()));
+  return 0;
+}
 }  // namespace
+
+void lift_paths(std::string& bed, std::string& out) {
+  std::lock_guard<std::mutex> lk(g_lift_mu);
+  bed = g_lift.load() ? g_lift_bed : std::string();
+  out = g_lift.load() ? g_lift_out : std::string();
+}
+
+void lift_bed_read(uint64_t skipped) { g_lift_counts[3] += skipped; }
 
 std::string coverage_path() {
   std::lock_guard<std::mutex> lk(g_coverage_mu);
@@ -725,6 +818,7 @@ int do_biwfa_alignment_batch(wfm_handle_t* h, std::vector<BiwfaRecord>& recs, co
     for_each_record(n, fmt.threads, [&](size_t ri) { swizzle(b, ri); write_record(b, ri); });
   }
   if (fmt.coverage && (rc = coverage_records(b)) < 0) return rc;
+  if (fmt.liftset && (rc = lift_records(b)) < 0) return rc;
   if (dbg)
     fprintf(stderr, "[wflign] %zu records: main alignment + runs + scans %.1f ms (incl. waiting for the device), patches %.1f ms (%zu tails scanned after their heads), swizzle + records %.1f ms\n",
             n, ms_between(ts0, ts1), ms_between(ts1, ts2), b.later, ms_between(ts2, Clock::now()));
@@ -767,6 +861,23 @@ void wfmh_set_coverage(const char* path_or_null) {
     wflign::g_coverage_path = path_or_null ? path_or_null : "";
   }
   wflign::g_coverage.store(path_or_null && *path_or_null);
+}
+
+void wfmh_set_lift(const char* bed_path_or_null, const char* out_path_or_null) {
+  for (auto& a : wflign::g_lift_counts) a.store(0);
+  const bool on = bed_path_or_null && *bed_path_or_null && out_path_or_null && *out_path_or_null;
+  {
+    std::lock_guard<std::mutex> lk(wflign::g_lift_mu);
+    wflign::g_lift_bed = on ? bed_path_or_null : "";
+    wflign::g_lift_out = on ? out_path_or_null : "";
+  }
+  wflign::g_lift.store(on);
+}
+
+int wfmh_lift_counts(uint64_t out[4]) {
+  if (!out) return WFM_E_ARG;
+  for (int q = 0; q < 4; ++q) out[q] = wflign::g_lift_counts[q].load();
+  return WFM_OK;
 }
 
 int wfmh_coverage_counts(uint64_t out[4]) {

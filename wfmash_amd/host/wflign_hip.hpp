@@ -19,6 +19,8 @@
 //   write_record       PAF / SAM record (+ cs:Z: as its last field)   (wflign.cpp:434-454)
 //   coverage_records   --coverage only: the runs of every record WRITTEN into the handle's depth object, one wfm_coverage_add call
 //                      (nothing is uploaded but runs; whether a record is written is only known behind write_record)
+//   lift_records       --lift only: the BED intervals lifted through the runs of every record WRITTEN, one wfm_lift_runs call
+//                      (runs alone again), the record's lines into BiwfaRecord::lift
 // and CIGARs are runs (count, op) from the device to the record's text: nothing is expanded to one byte per base.
 #pragma once
 
@@ -32,6 +34,8 @@
 
 #include "../../include/wfmash_hip.h"
 #include "cigar_ops.hpp"  // CigarOps, the CIGAR helpers, plan_patches, PafParams and the two record writers
+
+namespace lift { struct Interval; }  // lift_text.hpp
 
 namespace wflign {
 
@@ -71,8 +75,9 @@ struct BiwfaRecord {
   std::string vcf;                   // --variants: the VCF lines of the line's variants, each with its newline ("" if off, filtered, or none)
   bool vcf_called = false;           // ... the device called the record's variants (false: off, or the record was left alone)
   uint32_t vcf_masked = 0;           // ... SNVs left out of `vcf` because a base of theirs is not one of ACGT
-  uint64_t target_global = 0;        // --coverage: where the target sequence begins in the concatenation of the target's sequences
+  uint64_t target_global = 0;        // --coverage, --lift: where the target sequence begins in the concatenation of the target's sequences
   bool written = false;              // the filters let the record's line through (write_record)
+  std::string lift;                  // --lift: the lines of the BED intervals the record's target span overlaps, each with its newline ("" if off or not written)
   uint32_t tags = 0;                 // WFM_PF_* of the main alignment | of the head patch << 8 | of the tail patch << 16 (diagnostics: WFM_RECORD_TAGS)
 };
 
@@ -112,6 +117,8 @@ struct OutputFormat {
   bool emit_md_tag = false;
   int threads = 1;                   // host threads for the per-record CIGAR / PAF work of a batch
   wfm_coverage_t* coverage = nullptr;  // --coverage: the depth object of the batch's handle (null: the stage is not run)
+  const wfm_liftset_t* liftset = nullptr;                    // --lift: the intervals on the batch's handle (null: the stage is not run) ...
+  const std::vector<lift::Interval>* lift_intervals = nullptr;  // ... and as the BED had them, in the set's order
 };
 
 // --variants: the file wfmh_set_variants named ("" while the switch is off); the align phase writes the batches' BiwfaRecord::vcf to it
@@ -121,6 +128,11 @@ std::string variants_path();
 // the intervals: {target bases with depth >= 1, sum of depth, intervals written}
 std::string coverage_path();
 void coverage_finished(uint64_t covered, uint64_t depth_sum, uint64_t intervals);
+
+// --lift: the BED and the file wfmh_set_lift named (both "" while the switch is off), and what the align phase adds to the counts once it
+// has read the BED: the lines it skipped
+void lift_paths(std::string& bed, std::string& out);
+void lift_bed_read(uint64_t skipped);
 
 int do_biwfa_alignment_batch(wfm_handle_t* h, std::vector<BiwfaRecord>& recs, const wflign_penalties_t& penalties,
                              bool disable_chain_patching, const PafParams& pp, BiwfaStats* stats,
