@@ -488,6 +488,51 @@ int  wfm_lift_runs(wfm_handle_t* h, const wfm_liftset_t* s, const wfm_cov_prob_t
                    wfm_lift_t** lifts, size_t* n_lifts, wfm_liftcall_t* per);
 void wfm_free_lifts(wfm_lift_t* p);
 
+/* ---- presence of target intervals per group of records ----
+ * What wfm_coverage_* cannot say: WHICH records cover a base.  Every problem carries a group (a sample, a haplotype); a pav object keeps,
+ * per group, the UNION of the = and X bases of the problems added to it, as a list of segments on the handle's device
+ * (wfmash_amd/csrc/wfa_pav.hip) -- 16 bytes a segment whatever the target's length, never a dense array -- and answers for every
+ * (interval, group) cell how many bases of the interval lie in that group's union.  D bases do not count, I runs advance nothing.
+ *
+ * wfm_pav_create: n_bases >= 2^40 or n_groups >= 2^24 is WFM_E_ARG with a message: a segment's sort key is group << 40 | start.  On the
+ * device a segment is its two keys {group << 40 | start, group << 40 | end}, two 64-bit words; wfm_pav_seg_t is what export and import
+ * speak.  The list grows through the device block cache.  The object is used with the handle it was made on and freed before it.
+ * wfm_pav_add: probs[i] = {base, runs_off, n_runs, group}, runs as wfm_coverage_add takes them.  One segment per maximal stretch of =/X
+ * runs (not per run) is appended.  A problem with an empty run, whose pattern span leaves [0, n_bases] or does not fit 32 bits, or whose
+ * group is not below n_groups adds NOTHING and is flagged WFM_PAV_SPANS in flags_out[i] (taken before anything is written).  The slots are
+ * placed by scans, not atomics: two calls give the same list.  Returns the number of problems flagged, or WFM_E_*.  Where the raw part
+ * of the list then exceeds WFM_PAV_MB MiB (environment, a decimal, read per call, 256) the union is taken at once.
+ * wfm_pav_union: the list sorted by key (rocprim::radix_sort_pairs), the inclusive running maximum of the end keys (later groups dominate
+ * earlier ones, so a plain prefix maximum is a per-group one; reduce / scan-of-maxima / apply over blocks of WFM_PAV_SCAN_BLOCK segments,
+ * three launches), segment i heading a union interval iff i == 0 or its start key > the running maximum before it (abutting segments
+ * merge), the heads compacted by a prefix of the flags, a union interval's end the running maximum at its last member.  The disjoint
+ * union REPLACES the list, and an exclusive prefix C of its lengths (64 bits) is kept beside it.  Running it twice changes nothing.
+ * wfm_pav_export: the union, sorted by (group, start); a union interval of 2^32 bases or more comes as abutting pieces.  Host memory
+ * owned by the caller (wfm_pav_free_list); NULL and 0 for an empty object.
+ * wfm_pav_import: such a list (any list of segments with length >= 1 inside [0, n_bases] and group < n_groups; anything else is
+ * WFM_E_ARG and nothing is added) appended as raw segments: the merge of the objects of several devices is a union of unions.
+ * wfm_pav_matrix: iv[0 .. n_iv) half-open global intervals, start <= end <= n_bases and end - start < 2^32, else WFM_E_ARG; out:
+ * n_iv * n_groups words, row-major.  One thread per cell, with a = group << 40 | start, b = group << 40 | end over the union's keys:
+ * lo = the first u with end key > a, hi = the first u with start key >= b, 0 where hi <= lo, else C[hi] - C[lo] - max(0, a - start[lo])
+ * - max(0, end[hi - 1] - b): two binary searches, never a walk.  Rows come down in chunks of at most WFM_PAV_OUT_MB MiB (environment, a
+ * decimal, 256; one row at least).
+ * wfm_pav_counts: out = {segments added (import included), union intervals after the last union, unions run}. */
+typedef struct wfm_pav wfm_pav_t;
+typedef struct { uint64_t base, runs_off; uint32_t n_runs, group; } wfm_pav_prob_t;   /* 24 bytes */
+typedef struct { uint64_t start; uint32_t length, group; } wfm_pav_seg_t;             /* 16 bytes */
+#define WFM_PAV_SPANS 2u          /* as WFM_COV_SPANS: nothing of the problem is added */
+#define WFM_PAV_SCAN_BLOCK 1024   /* segments one workgroup takes in the scans of the union */
+int  wfm_pav_create(wfm_handle_t* h, uint64_t n_bases, uint32_t n_groups, wfm_pav_t** pav);
+void wfm_pav_free(wfm_pav_t* pav);
+int  wfm_pav_add(wfm_handle_t* h, wfm_pav_t* pav, const wfm_pav_prob_t* probs, size_t n, const uint32_t* runs, size_t n_runs_total,
+                 uint32_t* flags_out);
+int  wfm_pav_union(wfm_handle_t* h, wfm_pav_t* pav);
+int  wfm_pav_export(wfm_handle_t* h, wfm_pav_t* pav, wfm_pav_seg_t** segs, size_t* n);
+int  wfm_pav_import(wfm_handle_t* h, wfm_pav_t* pav, const wfm_pav_seg_t* segs, size_t n);
+int  wfm_pav_matrix(wfm_handle_t* h, wfm_pav_t* pav, const wfm_lift_iv_t* iv, size_t n_iv, uint32_t* out);
+int  wfm_pav_counts(const wfm_pav_t* pav, uint64_t out[3]);
+void wfm_pav_free_list(void* p);
+
 /* ---- every score proved optimal by a banded DP ----
  * What wfm_check_runs leaves out.  For every problem of the seqset s whose result claims a score S = res[i].score, a classical
  * minimising gap-affine-2-piece DP over cells (i = pattern index, j = text index) is run on the device, restricted to a band of

@@ -203,6 +203,33 @@ char* wfmh_test_coverage_bedgraph(const char* const* names, const uint64_t* leng
 void wfmh_set_lift(const char* bed_path_or_null, const char* out_path_or_null);
 int  wfmh_lift_counts(uint64_t out[4]);
 int  wfmh_lift_paf(wfm_handle_t* h, const char* target_fasta, const char* aligned_paf, const char* bed_path, const char* out_path, uint64_t out[4]);
+/* ---- presence of target intervals per group of query sequences (wfm_pav_*, wfmash_hip.h) ----
+ * wfmh_set_pav(bed, window, out): from now on every batch of wfmh_align_paf[_multi] runs ONE more device call behind the record writers:
+ * the runs of every record WRITTEN (with wfmh_set_left_align the normalised runs) go into the handle's presence object under the column
+ * of the query sequence's group.  Once the workers are done the objects of the handles are merged (export, import: a union of unions),
+ * the table is taken once on the device and `out` is written: pav(j, g) = the bases of interval j under an = or X base of at least one
+ * record written whose query belongs to group g.  D bases do not count.  No output byte of the PAF or SAM changes, and the file does not
+ * depend on the number of devices, handles, threads or the order of the batches.
+ * Groups: a query name's key is the part before its LAST '#', else the whole name; the columns are the distinct keys of ALL sequences of
+ * the query FASTA, sorted bytewise; a group without a written record is a column of zeros.  The target's own group is a column like the
+ * others: where the mapper skips self or same-group mappings it is 0.
+ * Intervals: `bed` (read and skipped as wfmh_set_lift reads it, sorted by (global start, end, input order)), or window > 0: windows of
+ * that many bases tiling every target sequence in index order, the last one shorter, named ".".  Exactly one of the two; anything else,
+ * or no `out`, switches it off.
+ * File: "#tname tstart tend name len" and the group keys, tab-separated, then one row per interval; cells are covered bases.
+ * Every call zeroes the counts.  wfmh_pav_counts: out = {records added, rows written, union intervals, BED lines skipped} since then.
+ * wfmh_pav_paf: the same file for an existing aligned PAF; query_fasta NULL or "": the target's sequences are the queries too.  Lines
+ * are read and skipped exactly as wfmh_coverage_paf does; a line whose query is not in the query FASTA is skipped and counted; one line
+ * on stderr has the totals.  out = the same four counts.  Returns 0 or WFM_E_*. */
+void wfmh_set_pav(const char* bed_path_or_null, uint64_t window, const char* out_path_or_null);
+int  wfmh_pav_counts(uint64_t out[4]);
+int  wfmh_pav_paf(wfm_handle_t* h, const char* target_fasta, const char* query_fasta_or_null, const char* aligned_paf, const char* bed_path_or_null,
+                  uint64_t window, const char* out_path, uint64_t out[4]);
+/* Test hook (no GPU): the text side alone (pav_text.hpp).  names: n_q query names; lengths: n_t target lengths; window: --pav-window's.
+ * Returns "#key<TAB>name<TAB>key<TAB>column" per name, the header line, then one row per window with cell g = (row number + g): malloc'd,
+ * wfmh_free. */
+char* wfmh_test_pav_text(const char* const* names, int n_q, const char* const* tnames, const uint64_t* lengths, int n_t, uint64_t window);
+
 /* Test hook (no GPU): the text side alone.  bed: the text of a BED file over n_seq target sequences; spec: lines "R<TAB>qname<TAB>qs
  * <TAB>qe<TAB>strand<TAB>tname<TAB>ts" (a record as its PAF line has it) and "L<TAB>record<TAB>interval<TAB>p0<TAB>p1<TAB>t0<TAB>t1<TAB>eq
  * <TAB>x" (a lift of record number `record` and interval number `interval` of the sorted list, as wfm_lift_runs gives it).  Returns

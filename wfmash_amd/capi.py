@@ -49,6 +49,8 @@ EXPORTS = [
     "wfm_coverage_create", "wfm_coverage_free", "wfm_coverage_add", "wfm_coverage_export", "wfm_coverage_import", "wfm_coverage_intervals",
     "wfm_coverage_free_list",
     "wfm_liftset_create", "wfm_liftset_free", "wfm_lift_runs", "wfm_free_lifts",
+    "wfm_pav_create", "wfm_pav_free", "wfm_pav_add", "wfm_pav_union", "wfm_pav_export", "wfm_pav_import", "wfm_pav_matrix", "wfm_pav_counts",
+    "wfm_pav_free_list",
     "wfm_sketch_intersections",
 ]
 ISECT_LDS_MAX = 4096  # WFM_ISECT_LDS_MAX: the longest column sketch wfm_sketch_intersections searches in LDS
@@ -74,6 +76,9 @@ WFM_COV_SCAN_BLOCK = 1024
 # wfm_liftset_* / wfm_lift_runs (include/wfmash_hip.h): why a problem has no lifts, the intervals one workgroup takes in the running maximum
 WFM_LIFT_SPANS = 2
 WFM_LIFT_SCAN_BLOCK = 1024
+# wfm_pav_* (include/wfmash_hip.h): why a problem added nothing, the segments one workgroup takes in the scans of the union
+WFM_PAV_SPANS = 2
+WFM_PAV_SCAN_BLOCK = 1024
 # wfm_check_optimal (include/wfmash_hip.h): what a problem's score was flagged for, and the band widths at which the kernel changes form
 WFM_OPT_NOT_CHECKED, WFM_OPT_SKIPPED, WFM_OPT_CHEAPER, WFM_OPT_UNREACHED = 1, 2, 4, 8
 OPT_NAMES = ("NOT_CHECKED", "SKIPPED", "CHEAPER", "UNREACHED")
@@ -183,6 +188,10 @@ class LiftCall(C.Structure):
 LIFT_IV_DTYPE = np.dtype([("start", "<u8"), ("end", "<u8")])
 LIFT_DTYPE = np.dtype([("problem", "<u4"), ("interval", "<u4"), ("p0", "<u4"), ("p1", "<u4"), ("t0", "<u4"), ("t1", "<u4"), ("eq", "<u4"), ("x", "<u4")])
 LIFTCALL_DTYPE = np.dtype([("flags", "<u4"), ("n_runs", "<u4"), ("first", "<u8"), ("count", "<u8")])
+
+
+PAV_PROB_DTYPE = np.dtype([("base", "<u8"), ("runs_off", "<u8"), ("n_runs", "<u4"), ("group", "<u4")])
+PAV_SEG_DTYPE = np.dtype([("start", "<u8"), ("length", "<u4"), ("group", "<u4")])
 
 
 class OptCheck(C.Structure):
@@ -681,6 +690,113 @@ class LiftSet:
         return np.frombuffer(raw, dtype=LIFT_DTYPE), per[:len(problems)]
 
 
+class Pav:
+    """wfm_pav_t: per group the union of the aligned bases of every problem added, as segments on the handle's device, over n_bases target
+    bases and n_groups groups (include/wfmash_hip.h).  Close it before its handle."""
+
+    def __init__(self, handle, n_bases, n_groups):
+        self._h, self._L = handle, handle._L
+        self.n_bases, self.n_groups = int(n_bases), int(n_groups)
+        self._p = None
+        L = self._L
+        L.wfm_pav_create.restype = C.c_int
+        L.wfm_pav_create.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]
+        L.wfm_pav_free.restype = None
+        L.wfm_pav_free.argtypes = [C.c_void_p]
+        L.wfm_pav_add.restype = C.c_int
+        L.wfm_pav_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.wfm_pav_union.restype = C.c_int
+        L.wfm_pav_union.argtypes = [C.c_void_p, C.c_void_p]
+        L.wfm_pav_export.restype = C.c_int
+        L.wfm_pav_export.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+        L.wfm_pav_import.restype = C.c_int
+        L.wfm_pav_import.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        L.wfm_pav_matrix.restype = C.c_int
+        L.wfm_pav_matrix.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.wfm_pav_counts.restype = C.c_int
+        L.wfm_pav_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        L.wfm_pav_free_list.restype = None
+        L.wfm_pav_free_list.argtypes = [C.c_void_p]
+        if not 0 <= self.n_groups < (1 << 32):
+            raise WfmError(f"wfm_pav_create: {self.n_groups} groups do not fit 32 bits")
+        p = C.c_void_p()
+        rc = L.wfm_pav_create(handle._p, self.n_bases, self.n_groups, C.byref(p))
+        if rc != 0:
+            raise WfmError(f"wfm_pav_create failed ({rc}): {handle.last_error()}")
+        self._p = p
+
+    def close(self):
+        if self._p:
+            self._L.wfm_pav_free(self._p)
+            self._p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, problems, runs):
+        """wfm_pav_add.  problems: a list of (base, runs_off, n_runs, group); runs: the run words ((length << 2) | op).  Returns the
+        problems' flags as a numpy array (WFM_PAV_SPANS: nothing of the problem was added)."""
+        probs = np.zeros(len(problems), dtype=PAV_PROB_DTYPE)
+        for i, (base, off, n, g) in enumerate(problems):
+            probs[i] = (base, off, n, g)
+        runs = np.ascontiguousarray(runs, dtype=np.uint32)
+        flags = np.zeros(max(len(problems), 1), dtype=np.uint32)
+        rc = self._L.wfm_pav_add(self._h._p, self._p, probs.ctypes.data if len(probs) else None, len(probs),
+                                 runs.ctypes.data if len(runs) else None, len(runs), flags.ctypes.data)
+        if rc < 0:
+            raise WfmError(f"wfm_pav_add failed ({rc}): {self._h.last_error()}")
+        assert rc == int(np.count_nonzero(flags[:len(problems)] & WFM_PAV_SPANS))
+        return flags[:len(problems)]
+
+    def union(self):
+        """wfm_pav_union: the list becomes the disjoint union per group."""
+        rc = self._L.wfm_pav_union(self._h._p, self._p)
+        if rc != 0:
+            raise WfmError(f"wfm_pav_union failed ({rc}): {self._h.last_error()}")
+
+    def export(self):
+        """wfm_pav_export: the union sorted by (group, start) as a numpy array with the fields {start, length, group}."""
+        ptr, n = C.c_void_p(), C.c_size_t(0)
+        rc = self._L.wfm_pav_export(self._h._p, self._p, C.byref(ptr), C.byref(n))
+        if rc != 0:
+            raise WfmError(f"wfm_pav_export failed ({rc}): {self._h.last_error()}")
+        try:
+            raw = C.string_at(ptr, n.value * PAV_SEG_DTYPE.itemsize) if n.value else b""
+        finally:
+            self._L.wfm_pav_free_list(ptr)
+        return np.frombuffer(raw, dtype=PAV_SEG_DTYPE)
+
+    def import_(self, segs):
+        """wfm_pav_import: such a list (of another object, of another device) appended as raw segments."""
+        e = np.ascontiguousarray(segs, dtype=PAV_SEG_DTYPE)
+        rc = self._L.wfm_pav_import(self._h._p, self._p, e.ctypes.data if len(e) else None, len(e))
+        if rc != 0:
+            raise WfmError(f"wfm_pav_import failed ({rc}): {self._h.last_error()}")
+
+    def matrix(self, intervals):
+        """wfm_pav_matrix.  intervals: a list of (start, end), global and half-open.  Returns a numpy array [interval, group] of the
+        covered bases."""
+        iv = np.zeros(len(intervals), dtype=LIFT_IV_DTYPE)
+        for i, (a, b) in enumerate(intervals):
+            iv[i] = (a, b)
+        out = np.zeros((len(iv), self.n_groups), dtype=np.uint32)
+        rc = self._L.wfm_pav_matrix(self._h._p, self._p, iv.ctypes.data if len(iv) else None, len(iv), out.ctypes.data if out.size else None)
+        if rc != 0:
+            raise WfmError(f"wfm_pav_matrix failed ({rc}): {self._h.last_error()}")
+        return out
+
+    def counts(self):
+        """wfm_pav_counts: (segments added, union intervals after the last union, unions run)."""
+        out = (C.c_uint64 * 3)()
+        rc = self._L.wfm_pav_counts(self._p, out)
+        if rc != 0:
+            raise WfmError(f"wfm_pav_counts failed ({rc})")
+        return tuple(int(v) for v in out)
+
+
 class Handle:
     """One handle per GPU (wfm_create)."""
 
@@ -990,6 +1106,11 @@ class Handle:
         """wfm_liftset_create: the sorted intervals [(start, end)] over n_bases target bases on this handle's device; .lift(problems, runs)
         lifts them through runs, .close() frees the set."""
         return LiftSet(self, intervals, n_bases)
+
+    def pav(self, n_bases, n_groups):
+        """wfm_pav_create: a presence object over n_bases target bases and n_groups groups on this handle's device; .add, .union, .export,
+        .import_, .matrix, .counts, .close."""
+        return Pav(self, n_bases, n_groups)
 
     def coverage(self, n_bases):
         """wfm_coverage_create: a depth object over n_bases target bases on this handle's device."""
@@ -1360,6 +1481,7 @@ HOST_EXPORTS = ["wfmh_test_packed_lce", "wfmh_test_is_acgt", "wfmh_align_default
                 "wfmh_set_verify_optimal", "wfmh_verify_optimal_counts", "wfmh_test_opt_band", "wfmh_set_left_align", "wfmh_left_align_counts", "wfmh_set_cs", "wfmh_cs_counts", "wfmh_set_variants", "wfmh_variants_counts",
                 "wfmh_set_coverage", "wfmh_coverage_counts", "wfmh_coverage_paf", "wfmh_test_coverage_bedgraph",
                 "wfmh_set_lift", "wfmh_lift_counts", "wfmh_lift_paf", "wfmh_test_lift_lines",
+                "wfmh_set_pav", "wfmh_pav_counts", "wfmh_pav_paf", "wfmh_test_pav_text",
                 "wfmh_ani_matrix", "wfmh_ani_matrix_rows", "wfmh_free_ani_rows", "wfmh_set_ani_matrix", "wfmh_test_ani_tsv"]
 
 
@@ -1870,6 +1992,59 @@ def host_lift_lines(names, lengths, bed_text, spec) -> str:
     p = f(nm, ln, n, bed_text.encode(), spec.encode())
     if not p:
         raise WfmError("wfmh_test_lift_lines cannot read the spec")
+    s = C.string_at(p).decode()
+    L.wfmh_free(p)
+    return s
+
+
+def set_pav(bed_path, window, out_path) -> None:
+    """wfmh_set_pav: every later align_paf call of the process keeps per group of query sequences the union of the aligned target bases
+    of the records it writes, on the device, and writes the table of the BED's intervals (or of windows of `window` bases) to `out_path`
+    (None: off); zeroes the counts."""
+    f = _host().wfmh_set_pav
+    f.restype = None
+    f.argtypes = [C.c_char_p, C.c_uint64, C.c_char_p]
+    f(os.fsencode(bed_path) if bed_path else None, int(window or 0), os.fsencode(out_path) if out_path else None)
+
+
+def pav_counts():
+    """wfmh_pav_counts: (records added, rows written, union intervals, BED lines skipped) since wfmh_set_pav."""
+    f = _host().wfmh_pav_counts
+    f.restype = C.c_int
+    f.argtypes = [C.POINTER(C.c_uint64)]
+    out = (C.c_uint64 * 4)()
+    rc = f(out)
+    if rc != 0:
+        raise WfmError(f"wfmh_pav_counts failed ({rc})")
+    return tuple(int(v) for v in out)
+
+
+def pav_paf(handle, target_fasta, query_fasta, aligned_paf, bed_path, window, out_path):
+    """wfmh_pav_paf: the table of an existing aligned PAF; returns (lines added, rows written, union intervals, BED lines skipped)."""
+    f = _host().wfmh_pav_paf
+    f.restype = C.c_int
+    f.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint64, C.c_char_p, C.POINTER(C.c_uint64)]
+    out = (C.c_uint64 * 4)()
+    rc = f(handle._p, os.fsencode(target_fasta), os.fsencode(query_fasta) if query_fasta else None, os.fsencode(aligned_paf),
+           os.fsencode(bed_path) if bed_path else None, int(window or 0), os.fsencode(out_path), out)
+    if rc != 0:
+        raise WfmError(f"wfmh_pav_paf failed ({rc}): {handle.last_error()}")
+    return tuple(int(v) for v in out)
+
+
+def host_pav_text(qnames, tnames, tlengths, window) -> str:
+    """wfmh_test_pav_text (no GPU): the names' keys and columns, the header, the windows' rows (include/wfmash_host.h)."""
+    L = _host()
+    f = L.wfmh_test_pav_text
+    f.restype = C.c_void_p
+    f.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_uint64), C.c_int, C.c_uint64]
+    nq, nt = len(qnames), len(tnames)
+    qn = (C.c_char_p * max(nq, 1))(*[x.encode() if isinstance(x, str) else x for x in qnames])
+    tn = (C.c_char_p * max(nt, 1))(*[x.encode() if isinstance(x, str) else x for x in tnames])
+    ln = (C.c_uint64 * max(nt, 1))(*[int(x) for x in tlengths])
+    p = f(qn, nq, tn, ln, nt, int(window))
+    if not p:
+        raise WfmError("wfmh_test_pav_text failed")
     s = C.string_at(p).decode()
     L.wfmh_free(p)
     return s

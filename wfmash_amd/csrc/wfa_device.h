@@ -356,6 +356,32 @@ void launch_lift_index(const uint32_t* runs, const LiftProb* probs, int nprob, c
 // the lifts of the problems [ka, kb), 32 bytes each; out[0] is lift number off[ka] of the call
 void launch_lift_write(const uint32_t* runs, const LiftProb* probs, const void* iv, const void* pre, const LiftWin* win, const unsigned long long* off,
                        uint32_t ka, uint32_t kb, void* out, hipStream_t st);
+// wfm_pav_* (wfa_pav.hip).  A problem is wfm_pav_prob_t as the caller wrote it.  A segment list is two arrays of keys, ks[i] = group << 40 |
+// start and ke[i] = group << 40 | end
+struct PavProb {
+  uint64_t base, runs_off;
+  uint32_t n_runs, group;
+};
+// flags: nprob; cnt: nprob, the segments each problem will write (0 where flagged); off: nprob + 1, their exclusive prefixes
+void launch_pav_count(const uint32_t* runs, const PavProb* probs, int nprob, unsigned long long n_bases, uint32_t n_groups, uint32_t* flags,
+                      unsigned long long* cnt, unsigned long long* off, hipStream_t st);
+// the segments of the problems, problem i's from slot off[i] of ks / ke on (the caller has made room for off[nprob] of them)
+void launch_pav_write(const uint32_t* runs, const PavProb* probs, int nprob, const uint32_t* flags, const unsigned long long* off,
+                      unsigned long long* ks, unsigned long long* ke, hipStream_t st);
+// rocprim::radix_sort_pairs of (ks, ke) by ks into (ks2, ke2), bits [0, end_bit); tmp == nullptr: *tmp_bytes = what it needs
+hipError_t pav_sort(void* tmp, size_t* tmp_bytes, const unsigned long long* ks, unsigned long long* ks2, const unsigned long long* ke,
+                    unsigned long long* ke2, unsigned long long n, unsigned end_bit, hipStream_t st);
+// ke (sorted by ks) to its inclusive running maximum, in place; aux: n / WFM_PAV_SCAN_BLOCK rounded up, + 1
+void launch_pav_runmax(unsigned long long* ke, unsigned long long n, unsigned long long* aux, hipStream_t st);
+// the union of (ks, rm), rm the running maximum: its intervals to (uks, uke), their number to aux[number of blocks]
+void launch_pav_compact(const unsigned long long* ks, const unsigned long long* rm, unsigned long long n, unsigned long long* aux,
+                        unsigned long long* uks, unsigned long long* uke, hipStream_t st);
+// C[i] = the bases of the union intervals before i, C[m] = all of them
+void launch_pav_prefix(const unsigned long long* uks, const unsigned long long* uke, unsigned long long m, unsigned long long* aux,
+                       unsigned long long* C, hipStream_t st);
+// the cells of rows [ra, rb), out[(j - ra) * n_groups + g]; iv: {start, end}, 16 bytes an interval
+void launch_pav_matrix(const unsigned long long* uks, const unsigned long long* uke, const unsigned long long* C, unsigned long long m, const void* iv,
+                       unsigned long long ra, unsigned long long rb, uint32_t n_groups, uint32_t* out, hipStream_t st);
 // wfm_check_optimal (wfa_optcheck.hip): a problem's forward byte copies, its ends-free allowances (clamped; 0 for the other modes),
 // its band of diagonals (wfa_optband.h) and, for the memory form, where its three row arrays begin in `rows` (32-bit elements)
 struct OptProb {

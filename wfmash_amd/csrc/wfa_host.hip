@@ -3514,6 +3514,276 @@ int wfm_lift_runs(wfm_handle_t* h, const wfm_liftset_t* s, const wfm_cov_prob_t*
 
 void wfm_free_lifts(wfm_lift_t* p) { free(p); }
 
+// ---- presence of target intervals per group of records (wfmash_hip.h; the kernels and the sort: wfa_pav.hip) ----
+struct wfm_pav {
+  int device = 0;
+  uint64_t n_bases = 0;
+  uint32_t n_groups = 0;
+  unsigned long long* list = nullptr;    // one block: the start keys [0, cap), then the end keys [cap, 2 cap)
+  size_t cap = 0, n = 0, n_union = 0;    // segments the block holds; segments in it; the first n_union of them are the last union's
+  bool clean = false;                    // the list is a union and C its prefix
+  DevBuf<uint64_t> c;                    // C: n_union + 1
+  DevBuf<uint64_t> work;                 // a call's problems, runs, flags, counts and offsets; the sorted copy and the block words; a chunk of rows
+  DevBuf<uint64_t> tmp;                  // the sort's own
+  uint64_t added = 0, unions = 0;
+  unsigned long long* ks() const { return list; }
+  unsigned long long* ke() const { return list + cap; }
+};
+
+extern "C++" {
+namespace {
+static_assert(sizeof(wfm_pav_prob_t) == 24 && sizeof(PavProb) == 24 && sizeof(wfm_pav_seg_t) == 16, "wfmash_hip.h states these sizes");
+constexpr unsigned PAV_SHIFT = 40;
+constexpr size_t PAV_MAX_SEGS = (size_t)1 << 31;
+
+int pav_usable(wfm_handle_t* h, const wfm_pav_t* pav) {
+  if (pav->device == h->device) return WFM_OK;
+  h->err = "the pav object lives on device " + std::to_string(pav->device) + ", the handle on " + std::to_string(h->device);
+  return WFM_E_ARG;
+}
+
+// room for `need` segments; what the list holds moves with it.  The block that is outgrown goes to the block cache, not to the driver.
+int pav_reserve(wfm_handle_t* h, wfm_pav_t* pav, size_t need) {
+  if (need <= pav->cap) return WFM_OK;
+  if (need > PAV_MAX_SEGS) { h->err = "wfm_pav: more than 2^31 segments in one object; lower WFM_PAV_MB so that the union is taken sooner"; return WFM_E_NOMEM; }
+  const size_t cap = std::max<size_t>(need + need / 2, 4096);
+  unsigned long long* blk = nullptr;
+  if (wfm_dmalloc((void**)&blk, cap * 16) != hipSuccess) { (void)hipGetLastError(); h->err = "out of device memory (pav segments)"; return WFM_E_NOMEM; }
+  if (pav->n) {
+    hipError_t e = hipMemcpyAsync(blk, pav->ks(), pav->n * 8, hipMemcpyDeviceToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(blk + cap, pav->ke(), pav->n * 8, hipMemcpyDeviceToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) { wfm_dfree(blk); h->err = std::string("wfm_pav: ") + hipGetErrorString(e); return WFM_E_HIP; }
+  }
+  if (pav->list) wfm_dfree(pav->list);
+  pav->list = blk;
+  pav->cap = cap;
+  return WFM_OK;
+}
+
+// the union where the raw part of the list has outgrown WFM_PAV_MB MiB
+int pav_maybe_union(wfm_handle_t* h, wfm_pav_t* pav) {
+  const double limit = std::max(0.0, env_decimal("WFM_PAV_MB", 256.0)) * 1048576.0;
+  if (pav->n > pav->n_union && (double)(pav->n - pav->n_union) * 16.0 > limit) return wfm_pav_union(h, pav);
+  return WFM_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int wfm_pav_create(wfm_handle_t* h, uint64_t n_bases, uint32_t n_groups, wfm_pav_t** pav) {
+  if (!h || !pav) return WFM_E_ARG;
+  *pav = nullptr;
+  if (n_bases >= ((uint64_t)1 << PAV_SHIFT) || n_groups >= (1u << 24)) {
+    h->err = "wfm_pav_create: " + std::to_string(n_bases) + " target bases and " + std::to_string(n_groups) +
+             " groups do not fit a segment's key, group << 40 | start: fewer than 2^40 bases and 2^24 groups";
+    return WFM_E_ARG;
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  std::unique_ptr<wfm_pav> p(new wfm_pav());
+  p->device = h->device;
+  p->n_bases = n_bases;
+  p->n_groups = n_groups;
+  p->clean = true;  // (the empty union)
+  *pav = p.release();
+  return WFM_OK;
+}
+
+void wfm_pav_free(wfm_pav_t* pav) {
+  if (!pav) return;
+  int cur = 0;
+  const bool swap = hipGetDevice(&cur) == hipSuccess && cur != pav->device;
+  if (swap) (void)hipSetDevice(pav->device);
+  pav->c.release();
+  pav->work.release();
+  pav->tmp.release();
+  if (pav->list) wfm_dfree(pav->list);
+  if (swap) (void)hipSetDevice(cur);
+  delete pav;
+}
+
+int wfm_pav_add(wfm_handle_t* h, wfm_pav_t* pav, const wfm_pav_prob_t* probs, size_t n, const uint32_t* runs, size_t n_runs_total, uint32_t* flags_out) {
+  if (!h || !pav || (n && (!probs || !flags_out)) || (n_runs_total && !runs)) return WFM_E_ARG;
+  if (n == 0) return WFM_OK;
+  if (n > (size_t)INT32_MAX || n_runs_total > ((size_t)1 << 31)) { h->err = "wfm_pav_add: too many problems or runs for one call"; return WFM_E_ARG; }
+  if (int rc = pav_usable(h, pav)) return rc;
+  // the run ranges are validated here, before anything is launched
+  for (size_t i = 0; i < n; ++i)
+    if (!(probs[i].runs_off <= n_runs_total && (uint64_t)probs[i].n_runs <= n_runs_total - probs[i].runs_off)) {
+      h->err = "problem " + std::to_string(i) + ": its runs leave the run buffer";
+      return WFM_E_ARG;
+    }
+  HIPCHK(h, hipSetDevice(h->device));
+  const auto t_call = std::chrono::steady_clock::now();
+  const size_t w_probs = n * 3, w_runs = (n_runs_total * 4 + 7) / 8, w_flags = (n * 4 + 7) / 8, w_cnt = n, w_off = n + 1;
+  if (pav->work.ensure(w_probs + w_runs + w_flags + w_cnt + w_off + 8)) { h->err = "out of device memory (pav add)"; return WFM_E_NOMEM; }
+  PavProb* d_probs = (PavProb*)pav->work.p;
+  uint32_t* d_runs = (uint32_t*)(pav->work.p + w_probs);
+  uint32_t* d_flags = (uint32_t*)(pav->work.p + w_probs + w_runs);
+  unsigned long long* d_cnt = (unsigned long long*)(pav->work.p + w_probs + w_runs + w_flags);
+  unsigned long long* d_off = d_cnt + w_cnt;
+  HIPCHK(h, hipMemcpyAsync(d_probs, probs, n * sizeof(PavProb), hipMemcpyHostToDevice, h->stream));
+  if (n_runs_total) HIPCHK(h, hipMemcpyAsync(d_runs, runs, n_runs_total * 4, hipMemcpyHostToDevice, h->stream));
+  launch_pav_count(d_runs, d_probs, (int)n, pav->n_bases, pav->n_groups, d_flags, d_cnt, d_off, h->stream);
+  HIPCHK(h, hipGetLastError());
+  unsigned long long total = 0;
+  HIPCHK(h, hipMemcpyAsync(flags_out, d_flags, n * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(&total, d_off + n, 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  int spans = 0;
+  for (size_t i = 0; i < n; ++i) spans += (flags_out[i] & WFM_PAV_SPANS) != 0;
+  if (total) {
+    if (int rc = pav_reserve(h, pav, pav->n + (size_t)total)) return rc;
+    launch_pav_write(d_runs, d_probs, (int)n, d_flags, d_off, pav->ks() + pav->n, pav->ke() + pav->n, h->stream);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    pav->n += (size_t)total;
+    pav->added += total;
+    pav->clean = false;
+  }
+  if (env_debug())
+    fprintf(stderr, "[wfm] pav add: %zu problems, %zu runs, %llu segments, %d flagged, %.3f ms (host clock, ends in a synchronise); the list holds %zu\n",
+            n, n_runs_total, total, spans, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count(), pav->n);
+  if (int rc = pav_maybe_union(h, pav)) return rc;
+  return spans;
+}
+
+int wfm_pav_union(wfm_handle_t* h, wfm_pav_t* pav) {
+  if (!h || !pav) return WFM_E_ARG;
+  if (int rc = pav_usable(h, pav)) return rc;
+  if (pav->clean) return WFM_OK;  // (nothing was added since the last one)
+  HIPCHK(h, hipSetDevice(h->device));
+  const auto t_call = std::chrono::steady_clock::now();
+  const size_t n = pav->n, nb = (n + WFM_PAV_SCAN_BLOCK - 1) / WFM_PAV_SCAN_BLOCK;
+  // the sorted copy: start keys, end keys, then the blocks' words
+  if (pav->work.ensure(2 * n + nb + 8)) { h->err = "out of device memory (pav union)"; return WFM_E_NOMEM; }
+  unsigned long long* ks2 = (unsigned long long*)pav->work.p;
+  unsigned long long* ke2 = ks2 + n;
+  unsigned long long* aux = ke2 + n;
+  unsigned end_bit = PAV_SHIFT;
+  while (end_bit < 64 && ((uint64_t)pav->n_groups >> (end_bit - PAV_SHIFT)) != 0) ++end_bit;  // (keys are below n_groups << 40)
+  size_t tmp_bytes = 0;
+  HIPCHK(h, pav_sort(nullptr, &tmp_bytes, pav->ks(), ks2, pav->ke(), ke2, n, end_bit, h->stream));
+  if (pav->tmp.ensure(tmp_bytes / 8 + 2)) { h->err = "out of device memory (pav sort)"; return WFM_E_NOMEM; }
+  HIPCHK(h, pav_sort(pav->tmp.p, &tmp_bytes, pav->ks(), ks2, pav->ke(), ke2, n, end_bit, h->stream));
+  launch_pav_runmax(ke2, n, aux, h->stream);
+  HIPCHK(h, hipGetLastError());
+  // (a union has no more intervals than the list has segments: the block holds it)
+  launch_pav_compact(ks2, ke2, n, aux, pav->ks(), pav->ke(), h->stream);
+  HIPCHK(h, hipGetLastError());
+  unsigned long long m = 0;
+  HIPCHK(h, hipMemcpyAsync(&m, aux + nb, 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (m > n) { h->err = "wfm_pav_union: the union has more intervals than the list had segments"; return WFM_E_HIP; }
+  if (pav->c.ensure((size_t)m + 2)) { h->err = "out of device memory (pav prefix)"; return WFM_E_NOMEM; }
+  launch_pav_prefix(pav->ks(), pav->ke(), m, aux, (unsigned long long*)pav->c.p, h->stream);
+  HIPCHK(h, hipGetLastError());
+  if (m == 0) HIPCHK(h, hipMemsetAsync(pav->c.p, 0, 8, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  pav->n = pav->n_union = (size_t)m;
+  pav->clean = true;
+  pav->unions += 1;
+  if (env_debug())
+    fprintf(stderr, "[wfm] pav union: %zu segments to %llu intervals in %.3f ms (host clock, ends in a synchronise); device bytes: the list's block %zu, the sorted copy and block words %zu, the sort's own %zu, the prefix %zu\n",
+            n, m, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count(), pav->cap * 16, pav->work.cap * 8, pav->tmp.cap * 8,
+            pav->c.cap * 8);
+  return WFM_OK;
+}
+
+int wfm_pav_export(wfm_handle_t* h, wfm_pav_t* pav, wfm_pav_seg_t** segs, size_t* n) {
+  if (!h || !pav || !segs || !n) return WFM_E_ARG;
+  *segs = nullptr; *n = 0;
+  if (int rc = wfm_pav_union(h, pav)) return rc;
+  const size_t m = pav->n;
+  if (m == 0) return WFM_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  std::vector<unsigned long long> keys(2 * m);
+  const bool pinned = cs_pin_pieces(h);
+  hipError_t e = cs_copy_down(h, pinned, (char*)keys.data(), (const uint8_t*)pav->ks(), m * 8);
+  if (e == hipSuccess) e = cs_copy_down(h, pinned, (char*)(keys.data() + m), (const uint8_t*)pav->ke(), m * 8);
+  if (e != hipSuccess) { h->err = std::string("wfm_pav_export: ") + hipGetErrorString(e); return WFM_E_HIP; }
+  // a union interval of 2^32 bases or more comes as abutting pieces
+  const uint64_t mask = ((uint64_t)1 << PAV_SHIFT) - 1, piece = 0x80000000ull;
+  size_t total = 0;
+  for (size_t i = 0; i < m; ++i) { const uint64_t len = keys[m + i] - keys[i]; total += len > 0xffffffffull ? (size_t)((len + piece - 1) / piece) : 1; }
+  wfm_pav_seg_t* out = (wfm_pav_seg_t*)malloc(total * sizeof(wfm_pav_seg_t));
+  if (!out) { h->err = "out of host memory (pav list)"; return WFM_E_NOMEM; }
+  size_t at = 0;
+  for (size_t i = 0; i < m; ++i) {
+    uint64_t s = keys[i] & mask, len = keys[m + i] - keys[i];
+    const uint32_t g = (uint32_t)(keys[i] >> PAV_SHIFT);
+    while (len > 0xffffffffull) { out[at++] = wfm_pav_seg_t{s, (uint32_t)piece, g}; s += piece; len -= piece; }
+    out[at++] = wfm_pav_seg_t{s, (uint32_t)len, g};
+  }
+  *segs = out; *n = at;
+  return WFM_OK;
+}
+
+int wfm_pav_import(wfm_handle_t* h, wfm_pav_t* pav, const wfm_pav_seg_t* segs, size_t n) {
+  if (!h || !pav || (n && !segs)) return WFM_E_ARG;
+  if (n == 0) return WFM_OK;
+  if (int rc = pav_usable(h, pav)) return rc;
+  std::vector<unsigned long long> keys(2 * n);
+  for (size_t i = 0; i < n; ++i) {
+    if (segs[i].length == 0 || segs[i].start > pav->n_bases || segs[i].length > pav->n_bases - segs[i].start || segs[i].group >= pav->n_groups) {
+      h->err = "wfm_pav_import: segment " + std::to_string(i) + " is empty, leaves the " + std::to_string(pav->n_bases) + " target bases or names a group that is not below " +
+               std::to_string(pav->n_groups);
+      return WFM_E_ARG;
+    }
+    keys[i] = ((uint64_t)segs[i].group << PAV_SHIFT) | segs[i].start;
+    keys[n + i] = keys[i] + segs[i].length;
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  if (int rc = pav_reserve(h, pav, pav->n + n)) return rc;
+  HIPCHK(h, hipMemcpyAsync(pav->ks() + pav->n, keys.data(), n * 8, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(pav->ke() + pav->n, keys.data() + n, n * 8, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  pav->n += n;
+  pav->added += n;
+  pav->clean = false;
+  return pav_maybe_union(h, pav);
+}
+
+int wfm_pav_matrix(wfm_handle_t* h, wfm_pav_t* pav, const wfm_lift_iv_t* iv, size_t n_iv, uint32_t* out) {
+  if (!h || !pav || (n_iv && (!iv || (pav->n_groups && !out)))) return WFM_E_ARG;
+  for (size_t j = 0; j < n_iv; ++j)
+    if (!(iv[j].start <= iv[j].end && iv[j].end <= pav->n_bases && iv[j].end - iv[j].start <= 0xffffffffull)) {
+      h->err = "wfm_pav_matrix: interval " + std::to_string(j) + " is reversed, ends beyond the " + std::to_string(pav->n_bases) + " target bases or is 2^32 bases long or longer";
+      return WFM_E_ARG;
+    }
+  if (int rc = wfm_pav_union(h, pav)) return rc;
+  if (n_iv == 0 || pav->n_groups == 0) return WFM_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  const auto t_call = std::chrono::steady_clock::now();
+  const size_t G = pav->n_groups;
+  const size_t rows = std::min<size_t>(n_iv, std::max<size_t>(1, (size_t)(std::max(0.0, env_decimal("WFM_PAV_OUT_MB", 256.0)) * 1048576.0) / (G * 4)));
+  const size_t w_iv = n_iv * 2, w_out = (rows * G * 4 + 7) / 8;
+  if (pav->work.ensure(w_iv + w_out + 8)) { h->err = "out of device memory (pav matrix)"; return WFM_E_NOMEM; }
+  void* d_iv = pav->work.p;
+  uint32_t* d_out = (uint32_t*)(pav->work.p + w_iv);
+  HIPCHK(h, hipMemcpyAsync(d_iv, iv, n_iv * sizeof(wfm_lift_iv_t), hipMemcpyHostToDevice, h->stream));
+  const bool pinned = cs_pin_pieces(h);
+  size_t chunks = 0;
+  for (size_t ra = 0; ra < n_iv; ra += rows, ++chunks) {
+    const size_t rb = std::min(n_iv, ra + rows);
+    launch_pav_matrix(pav->ks(), pav->ke(), (const unsigned long long*)pav->c.p, pav->n, d_iv, ra, rb, pav->n_groups, d_out, h->stream);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = cs_copy_down(h, pinned, (char*)(out + ra * G), (const uint8_t*)d_out, (rb - ra) * G * 4);  // (the block is the next chunk's)
+    if (e != hipSuccess) { h->err = std::string("wfm_pav_matrix: ") + hipGetErrorString(e); return WFM_E_HIP; }
+  }
+  if (env_debug())
+    fprintf(stderr, "[wfm] pav matrix: %zu intervals x %zu groups over %zu union intervals in %zu chunks, %.3f ms (host clock, ends in a synchronise)\n", n_iv, G,
+            pav->n, chunks, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count());
+  return WFM_OK;
+}
+
+int wfm_pav_counts(const wfm_pav_t* pav, uint64_t out[3]) {
+  if (!pav || !out) return WFM_E_ARG;
+  out[0] = pav->added; out[1] = pav->n_union; out[2] = pav->unions;
+  return WFM_OK;
+}
+
+void wfm_pav_free_list(void* p) { free(p); }
+
 // ---- every score proved optimal by a banded DP (wfmash_hip.h; the band: wfa_optband.h; the kernel: wfa_optcheck.hip) ----
 int wfm_check_optimal(wfm_handle_t* h, const wfm_penalties_t* pen, const wfm_seqset_t* s, const wfm_result_t* res, uint64_t max_cells,
                       wfm_optcheck_t* out) {

@@ -2,6 +2,7 @@
 #include "verify_paf.hpp"
 #include "coverage_text.hpp"
 #include "lift_text.hpp"
+#include "pav_text.hpp"
 #include "map_queue.hpp"
 #include "parallel.hpp"
 #include "../csrc/wfa_handle.h"
@@ -383,7 +384,8 @@ std::string Aligner::gather_text(Summary& sum, const std::vector<Fetched>& fetch
 
 std::string Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<std::string>& lines, int threads, Summary& sum, uint64_t first_row,
                                  std::string* vcf, wfm_coverage_t* coverage, const std::vector<uint64_t>* seq_offsets, std::string* lift,
-                                 const wfm_liftset_t* liftset, const std::vector<lift::Interval>* lift_intervals) {
+                                 const wfm_liftset_t* liftset, const std::vector<lift::Interval>* lift_intervals, wfm_pav_t* pav,
+                                 const std::vector<uint32_t>* pav_columns) {
   const bool dbg = getenv("WFM_DEBUG") != nullptr;
   BatchTimes t;
   std::vector<Fetched> rows = parse_rows(lines, first_row, sum);
@@ -393,8 +395,13 @@ std::string Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<std::stri
   std::vector<Fetched> fetched = fetch_eager(rows, threads, sum);
   if (fetched.empty()) return std::string();
   std::vector<wflign::BiwfaRecord> recs = make_records(fetched);
-  if (coverage || liftset)
+  if (coverage || liftset || pav)
     for (wflign::BiwfaRecord& r : recs) r.target_global = (*seq_offsets)[(size_t)ref->find(r.target_name)];  // (parse_rows has found every name)
+  if (pav)
+    for (wflign::BiwfaRecord& r : recs) {
+      const int qi = query->find(r.query_name);
+      r.pav_group = qi >= 0 ? (*pav_columns)[(size_t)qi] : 0xffffffffu;  // (no column: the device flags the record and adds nothing)
+    }
   wflign::ResidentSeqs resident;
   if (ds) {
     resident.store = ds->store;
@@ -412,6 +419,7 @@ std::string Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<std::stri
   wflign::BiwfaStats st;
   wflign::OutputFormat fmt = format_of(param, threads);
   fmt.coverage = coverage;
+  fmt.pav = pav;
   fmt.liftset = liftset;
   fmt.lift_intervals = lift_intervals;
   const int rc = wflign::do_biwfa_alignment_batch(gpu_handle, recs, penalties_of(param), param.disable_chain_patching, filters_of(param), &st,
@@ -552,7 +560,24 @@ struct Aligner::Run {
     liftsets.emplace_back(h, s);
     return s;
   }
-  // --coverage, --lift: where each target sequence begins in the concatenation (nseq + 1 values; empty: both are off).  --coverage: the depth object
+  // --pav: the intervals of the table in the file's order, the columns (and every query sequence's), and the presence object of every
+  // handle the run has used so far, made at the handle's first batch
+  bool pav_on = false;
+  std::vector<lift::Interval> pav_iv;
+  pav::Columns pav_cols;
+  std::mutex pav_mu;
+  std::vector<std::pair<wfm_handle_t*, wfm_pav_t*>> pavs;
+  wfm_pav_t* pav_of(wfm_handle_t* h) {
+    if (!pav_on) return nullptr;
+    std::lock_guard<std::mutex> lk(pav_mu);
+    for (auto& hp : pavs) if (hp.first == h) return hp.second;
+    wfm_pav_t* p = nullptr;
+    std::lock_guard<std::mutex> hl(wflign::handle_lock(h));
+    if (wfm_pav_create(h, seq_offsets.back(), (uint32_t)pav_cols.keys.size(), &p) != WFM_OK) throw std::runtime_error(std::string("[wfmash::align] --pav: ") + wfm_last_error(h));
+    pavs.emplace_back(h, p);
+    return p;
+  }
+  // --coverage, --lift, --pav: where each target sequence begins in the concatenation (nseq + 1 values; empty: all are off).  --coverage: the depth object
   // of every handle the run has used so far, made at the handle's first batch
   std::vector<uint64_t> seq_offsets;
   bool coverage_on = false;
@@ -566,6 +591,10 @@ struct Aligner::Run {
     for (auto& hs : liftsets) {
       std::lock_guard<std::mutex> lk(wflign::handle_lock(hs.first));
       wfm_liftset_free(hs.second);
+    }
+    for (auto& hp : pavs) {
+      std::lock_guard<std::mutex> lk(wflign::handle_lock(hp.first));
+      wfm_pav_free(hp.second);
     }
   }
   wfm_coverage_t* coverage_of(wfm_handle_t* h) {
@@ -668,7 +697,7 @@ void Aligner::run_worker(Run& run, size_t wk) {
       std::string vcf, lifted;
       std::string text = align_batch(run.use[wk], batch, run.threads_each, run.part[wk], first_row, run.vcf_writer ? &vcf : nullptr,
                                      run.coverage_of(run.use[wk]), &run.seq_offsets, run.lift_writer ? &lifted : nullptr, run.liftset_of(run.use[wk]),
-                                     &run.lift_iv);
+                                     &run.lift_iv, run.pav_of(run.use[wk]), &run.pav_cols.of_seq);
       const double at1 = run.ms();
       run.writer.put((uint64_t)seq, std::move(text));
       if (run.vcf_writer) run.vcf_writer->put((uint64_t)seq, std::move(vcf));
@@ -757,6 +786,48 @@ void Aligner::finish_coverage(Run& run, std::ofstream& out) {
     fprintf(stderr, "[wfmash::align] coverage: %zu objects merged, %zu intervals, %llu lines, %.1f ms\n", run.coverage.size(), iv.size(), (unsigned long long)lines, ms_since(t0));
 }
 
+// --pav: every other handle's object exported and imported into the first (a union of unions: the order does not matter), the table of
+// the merged object taken once on the device, the file through pav_text.hpp
+void Aligner::finish_pav(Run& run, std::ofstream& out, uint64_t bed_skipped) {
+  const auto t0 = Clock::now();
+  auto fail = [](wfm_handle_t* h, const char* what) { throw std::runtime_error(std::string("[wfmash::align] --pav: ") + what + ": " + wfm_last_error(h)); };
+  const size_t G = run.pav_cols.keys.size(), n_iv = run.pav_iv.size();
+  std::vector<uint32_t> cells(G * n_iv, 0u);
+  uint64_t counts[3] = {0, 0, 0};
+  if (!run.pavs.empty()) {
+    wfm_handle_t* h0 = run.pavs.front().first;
+    wfm_pav_t* p0 = run.pavs.front().second;
+    for (size_t k = 1; k < run.pavs.size(); ++k) {
+      wfm_pav_seg_t* list = nullptr;
+      size_t n = 0;
+      {
+        std::lock_guard<std::mutex> lk(wflign::handle_lock(run.pavs[k].first));
+        if (wfm_pav_export(run.pavs[k].first, run.pavs[k].second, &list, &n) != WFM_OK) fail(run.pavs[k].first, "export");
+      }
+      std::lock_guard<std::mutex> lk(wflign::handle_lock(h0));
+      const int rc = wfm_pav_import(h0, p0, list, n);
+      wfm_pav_free_list(list);
+      if (rc != WFM_OK) fail(h0, "import");
+    }
+    std::vector<wfm_lift_iv_t> raw(n_iv);
+    for (size_t j = 0; j < n_iv; ++j) raw[j] = wfm_lift_iv_t{run.pav_iv[j].gstart, run.pav_iv[j].gend};
+    std::lock_guard<std::mutex> lk(wflign::handle_lock(h0));
+    if (wfm_pav_matrix(h0, p0, raw.data(), n_iv, cells.data()) != WFM_OK) fail(h0, "matrix");
+    wfm_pav_counts(p0, counts);
+  }
+  const auto t1 = Clock::now();
+  std::string text = pav::header(run.pav_cols.keys);
+  for (size_t j = 0; j < n_iv; ++j) {
+    pav::row(text, ref->name(run.pav_iv[j].seq), run.pav_iv[j], cells.data() + j * G, G);
+    if (text.size() >= ((size_t)1 << 20)) { out << text; text.clear(); }
+  }
+  out << text;
+  wflign::pav_finished(n_iv, counts[1], bed_skipped);
+  if (getenv("WFM_DEBUG"))
+    fprintf(stderr, "[wfmash::align] pav: %zu objects merged, %llu segments added, %llu union intervals, %zu rows x %zu groups, merge + union + matrix %.1f ms, text %.1f ms\n",
+            run.pavs.size(), (unsigned long long)counts[0], (unsigned long long)counts[1], n_iv, G, std::chrono::duration<double, std::milli>(t1 - t0).count(), ms_since(t1));
+}
+
 Summary Aligner::compute() {
   Summary sum;
   const auto t0 = Clock::now();
@@ -794,7 +865,11 @@ Summary Aligner::compute() {
   std::ofstream liftstream;
   std::string lift_bed, lift_out;
   wflign::lift_paths(lift_bed, lift_out);
-  if (!cov_path.empty() || !lift_out.empty()) {
+  std::ofstream pavstream;
+  std::string pav_bed, pav_out;
+  uint64_t pav_window = 0, pav_skipped = 0;
+  wflign::pav_paths(pav_bed, pav_window, pav_out);
+  if (!cov_path.empty() || !lift_out.empty() || !pav_out.empty()) {
     run.seq_offsets.assign(1, 0);
     for (int i = 0; i < ref->nseq(); ++i) run.seq_offsets.push_back(run.seq_offsets.back() + (uint64_t)ref->length(i));
   }
@@ -810,6 +885,26 @@ Summary Aligner::compute() {
     liftstream.open(lift_out);
     if (!liftstream.is_open()) throw std::runtime_error("[wfmash::align] Error! Failed to open the lift file: " + lift_out);
     run.lift_writer.reset(new skch::OrderedWriter<std::string, TextSink>(TextSink{&liftstream}));
+  }
+  if (!pav_out.empty()) {  // --pav: the intervals and the columns are known before anything is aligned; the file is written once the workers are done
+    std::vector<uint64_t> lengths;
+    for (int i = 0; i < ref->nseq(); ++i) lengths.push_back((uint64_t)ref->length(i));
+    if (!pav_bed.empty()) {
+      std::ifstream bed(pav_bed, std::ios::binary);
+      if (!bed.is_open()) throw std::runtime_error("[wfmash::align] Error! Failed to open the BED file of --pav: " + pav_bed);
+      const std::string text((std::istreambuf_iterator<char>(bed)), std::istreambuf_iterator<char>());
+      lift::Bed parsed = lift::parse_bed(text, [&](const std::string& name) { return ref->find(name); }, lengths, run.seq_offsets);
+      run.pav_iv = std::move(parsed.iv);
+      pav_skipped = parsed.skipped;
+    } else {
+      run.pav_iv = pav::windows(lengths, run.seq_offsets, pav_window);
+    }
+    std::vector<std::string> qnames;
+    for (int i = 0; i < query->nseq(); ++i) qnames.push_back(query->name(i));
+    run.pav_cols = pav::columns(qnames);
+    pavstream.open(pav_out);
+    if (!pavstream.is_open()) throw std::runtime_error("[wfmash::align] Error! Failed to open the pav file: " + pav_out);
+    run.pav_on = true;
   }
   const size_t nworkers = run.plan.nworkers;
   static const bool own_handles = !(getenv("WFM_ALIGN_OWN_HANDLES") && atoi(getenv("WFM_ALIGN_OWN_HANDLES")) == 0);
@@ -828,6 +923,7 @@ Summary Aligner::compute() {
   }
   if (run.failed.load()) throw std::runtime_error(run.first_error);
   if (covstream.is_open()) { finish_coverage(run, covstream); covstream.close(); }
+  if (pavstream.is_open()) { finish_pav(run, pavstream, pav_skipped); pavstream.close(); }
   sum_up(sum, run.part, t0);
   outstream.close();
   if (vcfstream.is_open()) vcfstream.close();

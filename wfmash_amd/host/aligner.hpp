@@ -106,10 +106,12 @@ class Aligner {
   struct BatchTimes;  // the stages' times, into the Summary at the end
   // (vcf: where the VCF lines of the records written go, --variants; null: nowhere.  coverage: the depth object of this handle the records
   // written are added to, --coverage, with seq_offsets: where each target sequence begins in the concatenation; null: none.  lift: where
-  // the lift lines of the records written go, --lift, with the handle's liftset and the intervals in its order; null: nowhere)
+  // the lift lines of the records written go, --lift, with the handle's liftset and the intervals in its order; null: nowhere.  pav: the
+  // presence object of this handle the records written are added to, --pav, with the column of every query sequence; null: none)
   std::string align_batch(wfm_handle_t* gpu, std::vector<std::string>& lines, int threads, Summary& sum, uint64_t first_row = 0,
                           std::string* vcf = nullptr, wfm_coverage_t* coverage = nullptr, const std::vector<uint64_t>* seq_offsets = nullptr,
-                          std::string* lift = nullptr, const wfm_liftset_t* liftset = nullptr, const std::vector<lift::Interval>* lift_intervals = nullptr);
+                          std::string* lift = nullptr, const wfm_liftset_t* liftset = nullptr, const std::vector<lift::Interval>* lift_intervals = nullptr,
+                          wfm_pav_t* pav = nullptr, const std::vector<uint32_t>* pav_columns = nullptr);
   std::vector<Fetched> parse_rows(std::vector<std::string>& lines, uint64_t first_row, Summary& sum) const;
   void fetch_windows(Fetched& f) const;
   std::vector<Fetched> fetch_eager(std::vector<Fetched>& rows, int threads, Summary& sum) const;
@@ -124,6 +126,7 @@ class Aligner {
   RunPlan plan_run(std::ifstream& in) const;
   void run_worker(Run& run, size_t wk);
   void finish_coverage(Run& run, std::ofstream& out);  // --coverage: the handles' depth objects merged into one, its intervals as a bedGraph
+  void finish_pav(Run& run, std::ofstream& out, uint64_t bed_skipped);  // --pav: the handles' presence objects merged into one, its table as TSV
   void sum_up(Summary& sum, const std::vector<Summary>& part, std::chrono::steady_clock::time_point t0) const;
   const Parameters& param;
   std::vector<wfm_handle_t*> gpus;

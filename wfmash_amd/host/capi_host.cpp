@@ -14,6 +14,7 @@
 #include "aligner.hpp"
 #include "fasta.hpp"
 #include "lift_text.hpp"
+#include "pav_text.hpp"
 #include "map_stats.hpp"
 
 extern "C" {
@@ -147,6 +148,28 @@ char* wfmh_test_lift_lines(const char* const* names, const uint64_t* lengths, in
     } else {
       return nullptr;
     }
+  }
+  char* p = (char*)malloc(out.size() + 1);
+  if (p) memcpy(p, out.c_str(), out.size() + 1);
+  return p;
+}
+
+// test hook (no GPU): the text side of --pav (pav_text.hpp): the names' keys and columns, the header, the windows' rows
+char* wfmh_test_pav_text(const char* const* names, int n_q, const char* const* tnames, const uint64_t* lengths, int n_t, uint64_t window) {
+  if (n_q < 0 || n_t < 0 || (n_q && !names) || (n_t && (!tnames || !lengths))) return nullptr;
+  std::vector<std::string> nm;
+  for (int i = 0; i < n_q; ++i) nm.push_back(names[i]);
+  std::vector<uint64_t> len, off(1, 0);
+  for (int i = 0; i < n_t; ++i) { len.push_back(lengths[i]); off.push_back(off.back() + lengths[i]); }
+  const pav::Columns cols = pav::columns(nm);
+  std::string out;
+  for (size_t i = 0; i < nm.size(); ++i) out += "#key\t" + nm[i] + "\t" + pav::group_key(nm[i]) + "\t" + std::to_string(cols.of_seq[i]) + "\n";
+  out += pav::header(cols.keys);
+  const std::vector<lift::Interval> win = pav::windows(len, off, window);
+  std::vector<uint32_t> cells(cols.keys.size());
+  for (size_t j = 0; j < win.size(); ++j) {
+    for (size_t g = 0; g < cells.size(); ++g) cells[g] = (uint32_t)(j + g);
+    pav::row(out, tnames[win[j].seq], win[j], cells.data(), cells.size());
   }
   char* p = (char*)malloc(out.size() + 1);
   if (p) memcpy(p, out.c_str(), out.size() + 1);

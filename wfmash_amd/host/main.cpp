@@ -65,6 +65,18 @@
 //                                              each of the two is an error without the other; off by default
 //   --lift-paf IN.paf --lift IN.bed --lift-out FILE target.fa   the same file for an existing aligned PAF: no mapping, no alignment;
 //                                              lines are skipped and counted as --coverage-paf does; only --device beside it
+//   --pav IN.bed | --pav-window N, --pav-out FILE   which groups of query sequences (haplotypes, samples: the part of the name before its
+//                                              last '#') have each target interval, and how much of it: the runs of every record WRITTEN go
+//                                              into a per-group union of aligned segments on the device (wfm_pav_*; 16 bytes a segment, never
+//                                              a dense array); one row per interval -- the BED's, or windows of N bases tiling every target
+//                                              sequence -- and one column per group of the query FASTA, cells = bases of the interval under
+//                                              an = or X base of at least one record of the group; the target's own group is a column like
+//                                              the others (0 where the mapper skips self or same-group mappings); no output byte of the PAF
+//                                              or SAM changes; refused with -m and --verify-paf; --pav and --pav-window exclude each other
+//                                              and each needs --pav-out; off by default
+//   --pav-paf IN.paf (--pav IN.bed | --pav-window N) --pav-out FILE target.fa [query.fa]   the same file for an existing aligned PAF: no
+//                                              mapping, no alignment; lines are skipped and counted as --coverage-paf does, and a line whose
+//                                              query is not in the query FASTA; only --device beside it
 //   --verify-paf FILE target.fa [query.fa]     the same check on an existing aligned PAF (this build's or the reference's): no mapping,
 //                                              no alignment; exit status 3 if a line fails
 //   --ani-matrix FILE [--ani-only]             the group-by-group ANI table the identity estimate (-p aniN) is made from, as TSV: per
@@ -161,6 +173,8 @@ static void usage() {
           "            --coverage-paf FILE with --coverage: the depth of an existing aligned PAF over target.fa, and stop (only --device beside it)\n"
           "            --lift BED --lift-out FILE lift the BED's target intervals through every record written, on the GPU: one line per record and interval (not with -m, --verify-paf)\n"
           "            --lift-paf FILE with --lift, --lift-out: lift through an existing aligned PAF over target.fa, and stop (only --device beside it)\n"
+          "            --pav BED | --pav-window N, --pav-out FILE per target interval and group of query sequences the bases present, from per-group unions on the GPU (not with -m, --verify-paf)\n"
+          "            --pav-paf FILE with --pav or --pav-window, --pav-out: the table of an existing aligned PAF over target.fa [query.fa], and stop (only --device beside it)\n"
           "            --verify-paf FILE check an existing aligned PAF against target.fa [query.fa] and stop (exit status 3 if a line fails)\n"
           "  other     --out FILE [stdout]   --device INT [0]   --gpus N|all [1] GPUs of this node, starting at --device\n"
           "            -B DIR directory of the hand-off file [cwd]   -Z keep the hand-off file   --quiet (no effect)\n");
@@ -172,7 +186,10 @@ int main(int argc, char** argv) {
   ap.threads = 1;  // -t, default 1 as in the reference (parse_args.hpp: thread_count); the C ABI default (0) means all cores
   wfmh_map_params_t mp;
   wfmh_map_default_params(&mp);
-  std::string mapping_in, out = "/dev/stdout", target, query, seeds_in, scaffold_out, tmp_base, verify_in, ani_matrix_out, variants_out, coverage_out, coverage_in, lift_bed, lift_out, lift_in;
+  std::string mapping_in, out = "/dev/stdout", target, query, seeds_in, scaffold_out, tmp_base, verify_in, ani_matrix_out, variants_out, coverage_out, coverage_in, lift_bed, lift_out, lift_in, pav_bed, pav_out, pav_in;
+  uint64_t pav_window = 0;
+  bool pav_window_set = false;
+  bool pav_other = false;      // --pav-paf: anything beside it, --pav, --pav-window, --pav-out, --device and the two FASTAs
   bool other_options = false;  // --coverage-paf: anything beside it, --coverage, --device and the target
   bool lift_other = false;     // --lift-paf: anything beside it, --lift, --lift-out, --device and the target
   bool verify = false, verify_optimal = false, ani_only = false, left_align = false;
@@ -182,6 +199,7 @@ int main(int argc, char** argv) {
   int device = 0, gpus = 1;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
+    if (a[0] == '-' ? (a != "--pav" && a != "--pav-window" && a != "--pav-out" && a != "--pav-paf" && a != "--device" && a != "-h" && a != "--help") : !query.empty()) pav_other = true;
     if (a[0] == '-' ? (a != "--lift" && a != "--lift-out" && a != "--lift-paf" && a != "--device" && a != "-h" && a != "--help") : !target.empty()) lift_other = true;
     if (a[0] == '-' ? (a != "--coverage" && a != "--coverage-paf" && a != "--device" && a != "-h" && a != "--help") : !target.empty()) other_options = true;
     auto next = [&](const char* name) -> std::string {
@@ -322,6 +340,16 @@ int main(int argc, char** argv) {
     else if (a == "--lift") lift_bed = next("--lift");
     else if (a == "--lift-out") lift_out = next("--lift-out");
     else if (a == "--lift-paf") lift_in = next("--lift-paf");
+    else if (a == "--pav") pav_bed = next("--pav");
+    else if (a == "--pav-out") pav_out = next("--pav-out");
+    else if (a == "--pav-paf") pav_in = next("--pav-paf");
+    else if (a == "--pav-window") {
+      const std::string v = next("--pav-window");
+      char* end = nullptr;
+      pav_window = std::strtoull(v.c_str(), &end, 10);
+      if (v.empty() || *end || v[0] == '-' || pav_window == 0) { fprintf(stderr, "[wfmash] ERROR: --pav-window takes a positive number of bases\n"); return 1; }
+      pav_window_set = true;
+    }
     else if (a == "--verify-optimal-cells") verify_optimal_cells = std::strtoull(next("--verify-optimal-cells").c_str(), nullptr, 10);
     else if (a == "--verify-paf") verify_in = next("--verify-paf");
     else if (a == "-h" || a == "--help") { usage(); return 0; }
@@ -346,6 +374,14 @@ int main(int argc, char** argv) {
   if (!lift_bed.empty() && approx_only) { fprintf(stderr, "[wfmash] ERROR: --lift lifts through alignments: it cannot be combined with -m\n"); return 1; }
   if (!lift_bed.empty() && !verify_in.empty()) { fprintf(stderr, "[wfmash] ERROR: --lift belongs to the align phase: it cannot be combined with --verify-paf\n"); return 1; }
   if (!lift_in.empty() && lift_other) { fprintf(stderr, "[wfmash] ERROR: --lift-paf runs nothing else: besides --lift IN.bed, --lift-out FILE and the target FASTA it takes the number of the GPU only\n"); return 1; }
+  const bool pav_on = !pav_bed.empty() || pav_window_set;
+  if (!pav_bed.empty() && pav_window_set) { fprintf(stderr, "[wfmash] ERROR: --pav IN.bed and --pav-window N exclude each other\n"); return 1; }
+  if (pav_on && pav_out.empty()) { fprintf(stderr, "[wfmash] ERROR: %s needs --pav-out FILE\n", pav_window_set ? "--pav-window" : "--pav"); return 1; }
+  if (!pav_on && !pav_out.empty()) { fprintf(stderr, "[wfmash] ERROR: --pav-out needs --pav IN.bed or --pav-window N\n"); return 1; }
+  if (!pav_in.empty() && !pav_on) { fprintf(stderr, "[wfmash] ERROR: --pav-paf needs --pav IN.bed or --pav-window N, and --pav-out FILE\n"); return 1; }
+  if (pav_on && approx_only) { fprintf(stderr, "[wfmash] ERROR: --pav reads alignments: it cannot be combined with -m\n"); return 1; }
+  if (pav_on && !verify_in.empty()) { fprintf(stderr, "[wfmash] ERROR: --pav belongs to the align phase: it cannot be combined with --verify-paf\n"); return 1; }
+  if (!pav_in.empty() && pav_other) { fprintf(stderr, "[wfmash] ERROR: --pav-paf runs nothing else: besides --pav IN.bed or --pav-window N, --pav-out FILE and the FASTAs it takes the number of the GPU only\n"); return 1; }
   if (!coverage_in.empty() && other_options) { fprintf(stderr, "[wfmash] ERROR: --coverage-paf runs nothing else: besides --coverage FILE and the target FASTA it takes the number of the GPU only\n"); return 1; }
   if (verify_optimal && approx_only) { fprintf(stderr, "[wfmash] ERROR: --verify-optimal checks alignment scores: it cannot be combined with -m\n"); return 1; }
   if (verify_optimal_cells && !verify_optimal) { fprintf(stderr, "[wfmash] ERROR: --verify-optimal-cells needs --verify-optimal\n"); return 1; }
@@ -359,6 +395,16 @@ int main(int argc, char** argv) {
     return 1;
   }
   if (!ani_matrix_out.empty() && !verify_in.empty()) { fprintf(stderr, "[wfmash] ERROR: --ani-matrix cannot be combined with --verify-paf\n"); return 1; }
+  if (!pav_in.empty()) {  // the presence table of an existing PAF; nothing else runs
+    wfm_handle_t* hp = nullptr;
+    if (wfm_create(device, &hp) != WFM_OK) { fprintf(stderr, "[wfmash] ERROR: no usable MI355X device %d (there is no CPU fallback)\n", device); return 2; }
+    uint64_t pc[4] = {0, 0, 0, 0};
+    const int prc = wfmh_pav_paf(hp, target.c_str(), query.empty() ? nullptr : query.c_str(), pav_in.c_str(), pav_bed.empty() ? nullptr : pav_bed.c_str(), pav_window,
+                                 pav_out.c_str(), pc);
+    if (prc != WFM_OK) fprintf(stderr, "[wfmash::pav] ERROR: %s\n", wfm_last_error(hp));
+    wfm_destroy(hp);
+    return prc == WFM_OK ? 0 : 2;
+  }
   if (!lift_in.empty()) {  // the BED through an existing PAF; nothing else runs
     wfm_handle_t* hl = nullptr;
     if (wfm_create(device, &hl) != WFM_OK) { fprintf(stderr, "[wfmash] ERROR: no usable MI355X device %d (there is no CPU fallback)\n", device); return 2; }
@@ -499,6 +545,7 @@ int main(int argc, char** argv) {
     if (!variants_out.empty()) wfmh_set_variants(variants_out.c_str());
     if (!coverage_out.empty()) wfmh_set_coverage(coverage_out.c_str());
     if (!lift_bed.empty()) wfmh_set_lift(lift_bed.c_str(), lift_out.c_str());
+    if (pav_on) wfmh_set_pav(pav_bed.empty() ? nullptr : pav_bed.c_str(), pav_window, pav_out.c_str());
     rc = wfmh_align_paf_multi(hs.data(), (int)hs.size(), target.c_str(), q, mapping.c_str(), out.c_str(), &ap, &s);
     if (rc == WFM_OK)
       fprintf(stderr, "[wfmash::align] %llu records, %llu aligned bp, %.1f ms GPU kernels, %.1f ms total => %.3g aligned bp/s\n",
@@ -521,6 +568,12 @@ int main(int argc, char** argv) {
       wfmh_variants_counts(vc);
       fprintf(stderr, "[wfmash::variants] %llu records, %llu variants written, %llu SNVs masked, %llu records left alone\n", (unsigned long long)vc[0],
               (unsigned long long)vc[1], (unsigned long long)vc[2], (unsigned long long)vc[3]);
+    }
+    if (pav_on && rc == WFM_OK) {
+      uint64_t pc[4] = {0, 0, 0, 0};
+      wfmh_pav_counts(pc);
+      fprintf(stderr, "[wfmash::pav] %llu records added, %llu rows written, %llu union intervals, %llu BED lines skipped\n", (unsigned long long)pc[0],
+              (unsigned long long)pc[1], (unsigned long long)pc[2], (unsigned long long)pc[3]);
     }
     if (!lift_bed.empty() && rc == WFM_OK) {
       uint64_t lc[4] = {0, 0, 0, 0};

@@ -17,6 +17,7 @@
 #include "aligner.hpp"
 #include "coverage_text.hpp"
 #include "lift_text.hpp"
+#include "pav_text.hpp"
 #include "parallel.hpp"
 #include "wflign_hip.hpp"
 
@@ -372,6 +373,100 @@ int wfmh_lift_paf(wfm_handle_t* h, const char* target_fasta, const char* aligned
     return WFM_OK;
   } catch (const std::exception& e) {
     if (set) wfm_liftset_free(set);
+    std::cerr << e.what() << std::endl;
+    wfm_set_error(h, e.what());
+    return WFM_E_ARG;
+  }
+}
+
+// --pav-paf: the presence table of an existing aligned PAF.  Lines go to the device in batches of runs, read and skipped by
+// wfmh_coverage_paf's rules (coverage::classify_line); a line whose query the query FASTA does not have is skipped and counted too.
+int wfmh_pav_paf(wfm_handle_t* h, const char* target_fasta, const char* query_fasta_or_null, const char* aligned_paf, const char* bed_path_or_null,
+                 uint64_t window, const char* out_path, uint64_t out[4]) {
+  const bool with_bed = bed_path_or_null && *bed_path_or_null;
+  if (!h || !target_fasta || !aligned_paf || !out_path || with_bed == (window != 0)) return WFM_E_ARG;
+  wfm_pav_t* obj = nullptr;
+  try {
+    std::shared_ptr<wfmash_host::FastaStore> target = wfmash_host::open_shared(target_fasta);
+    std::shared_ptr<wfmash_host::FastaStore> query = query_fasta_or_null && *query_fasta_or_null ? wfmash_host::open_shared(query_fasta_or_null) : target;
+    std::ifstream in(aligned_paf);
+    if (!in.is_open()) throw std::runtime_error(std::string("[wfmash::pav] cannot open ") + aligned_paf);
+    std::vector<uint64_t> lengths, offsets(1, 0);
+    for (int i = 0; i < target->nseq(); ++i) {
+      lengths.push_back((uint64_t)target->length(i));
+      offsets.push_back(offsets.back() + lengths.back());
+    }
+    std::vector<lift::Interval> iv;
+    uint64_t bed_skipped = 0;
+    if (with_bed) {
+      std::ifstream bedstream(bed_path_or_null, std::ios::binary);
+      if (!bedstream.is_open()) throw std::runtime_error(std::string("[wfmash::pav] cannot open ") + bed_path_or_null);
+      const std::string bed_text((std::istreambuf_iterator<char>(bedstream)), std::istreambuf_iterator<char>());
+      lift::Bed bed = lift::parse_bed(bed_text, [&](const std::string& name) { return target->find(name); }, lengths, offsets);
+      iv = std::move(bed.iv);
+      bed_skipped = bed.skipped;
+    } else {
+      iv = pav::windows(lengths, offsets, window);
+    }
+    std::vector<std::string> qnames;
+    for (int i = 0; i < query->nseq(); ++i) qnames.push_back(query->name(i));
+    const pav::Columns cols = pav::columns(qnames);
+    std::ofstream outstream(out_path);
+    if (!outstream.is_open()) throw std::runtime_error(std::string("[wfmash::pav] cannot open ") + out_path);
+    auto device = [&](int rc, const char* what) {
+      if (rc < 0) throw std::runtime_error(std::string("[wfmash::pav] ") + what + " failed: " + wfm_last_error(h));
+      return rc;
+    };
+    std::lock_guard<std::mutex> lk(wflign::handle_lock(h));
+    device(wfm_pav_create(h, offsets.back(), (uint32_t)cols.keys.size(), &obj), "create");
+    uint64_t added = 0, no_query = 0, skipped[5] = {0, 0, 0, 0, 0};
+    std::vector<wfm_pav_prob_t> probs;
+    std::vector<uint32_t> runs, flags;
+    auto flush = [&]() {
+      if (probs.empty()) return;
+      flags.resize(probs.size());
+      const int refused = device(wfm_pav_add(h, obj, probs.data(), probs.size(), runs.data(), runs.size(), flags.data()), "add");
+      added += probs.size() - (uint64_t)refused;
+      skipped[coverage::LINE_MALFORMED] += (uint64_t)refused;  // (a span that leaves the target: classify_line lets none through)
+      probs.clear(); runs.clear();
+    };
+    std::string line;
+    verify::Line l;
+    while (std::getline(in, line)) {
+      if (line.empty() || line[0] == '@') continue;
+      int ti = -1;
+      const int code = coverage::classify_line(line, [&](const std::string& name) { return target->find(name); }, lengths, l, &ti);
+      if (code != coverage::LINE_ADD) { skipped[code]++; continue; }
+      const int qi = query->find(l.qname);
+      if (qi < 0) { ++no_query; continue; }
+      probs.push_back(wfm_pav_prob_t{offsets[(size_t)ti] + (uint64_t)l.ts, (uint64_t)runs.size(), (uint32_t)l.runs.size(), cols.of_seq[(size_t)qi]});
+      runs.insert(runs.end(), l.runs.begin(), l.runs.end());
+      if (probs.size() >= 65536 || runs.size() >= ((size_t)16 << 20)) flush();
+    }
+    flush();
+    const size_t G = cols.keys.size();
+    std::vector<uint32_t> cells(G * iv.size(), 0u);
+    std::vector<wfm_lift_iv_t> raw(iv.size());
+    for (size_t j = 0; j < iv.size(); ++j) raw[j] = wfm_lift_iv_t{iv[j].gstart, iv[j].gend};
+    device(wfm_pav_matrix(h, obj, raw.data(), raw.size(), cells.data()), "matrix");
+    uint64_t counts[3] = {0, 0, 0};
+    wfm_pav_counts(obj, counts);
+    wfm_pav_free(obj);
+    obj = nullptr;
+    std::string text = pav::header(cols.keys);
+    for (size_t j = 0; j < iv.size(); ++j) {
+      pav::row(text, target->name(iv[j].seq), iv[j], cells.data() + j * G, G);
+      if (text.size() >= ((size_t)1 << 20)) { outstream << text; text.clear(); }
+    }
+    outstream << text;
+    const uint64_t all_skipped = skipped[1] + skipped[2] + skipped[3] + skipped[4] + no_query;
+    std::cerr << "[wfmash::pav] " << iv.size() << " intervals (" << bed_skipped << " BED lines skipped) x " << G << " groups, " << added << " lines added, " << all_skipped
+              << " skipped (" << skipped[1] << " without an =XID cg:Z:, " << skipped[2] << " malformed, " << skipped[3] << " with an unknown target, " << skipped[4]
+              << " with another tlen, " << no_query << " with an unknown query), " << counts[1] << " union intervals" << std::endl;
+    if (out) { out[0] = added; out[1] = iv.size(); out[2] = counts[1]; out[3] = bed_skipped; }
+    return WFM_OK;
+  } catch (const std::exception& e) {
+    if (obj) wfm_pav_free(obj);
     std::cerr << e.what() << std::endl;
     wfm_set_error(h, e.what());
     return WFM_E_ARG;

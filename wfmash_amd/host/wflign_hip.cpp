@@ -79,6 +79,14 @@ std::mutex g_lift_mu;
 std::string g_lift_bed, g_lift_out;
 std::atomic<uint64_t> g_lift_counts[4];
 
+// --pav: the process-wide switch, the BED of target intervals or the window size, the file the align phase writes, and {records added,
+// rows written, union intervals, BED lines skipped} since it was set
+std::atomic<bool> g_pav{false};
+std::mutex g_pav_mu;
+std::string g_pav_bed, g_pav_out;
+uint64_t g_pav_window = 0;
+std::atomic<uint64_t> g_pav_counts[4];
+
 // The problems of one device call, always written by reference (a side without a store id carries its host pointer); without a
 // store they go to the device as plain wfm_problem_t, as they always have.
 struct GpuBatch {
@@ -681,6 +689,53 @@ int coverage_records(BiwfaBatch& b) {
     fprintf(stderr, "[wflign] coverage: %zu records, %zu runs, %d flagged, %.1f ms\n", probs.size(), runs.size(), rc, ms_between(t0, Clock::now()));
   return 0;
 }
+// ---- --pav: the runs of every record WRITTEN into the presence object of the batch's handle, with the column of the query's group, ONE
+// device call per batch (wfm_pav_add).  It runs beside coverage_records and takes the same problems: the same trimmed ops at the same
+// base.  Nothing goes up but runs.  A record the device refuses, or whose ops its runs cannot hold, is a defect: it adds nothing, is
+// counted and reported. ----
+int pav_records(BiwfaBatch& b) {
+  const auto t0 = Clock::now();
+  std::vector<wfm_pav_prob_t> probs;
+  std::vector<uint32_t> runs;
+  uint64_t unknown = 0;
+  for (const BiwfaRecord& r : b.recs) {
+    if (!r.ok || !r.written) continue;
+    const CigarOps& ops = r.ops;
+    size_t ob = 0, oe = ops.size();
+    uint64_t ta = 0;
+    while (ob < oe && (ops[ob].second == 'I' || ops[ob].second == 'D')) { if (ops[ob].second == 'D') ta += (uint64_t)ops[ob].first; ++ob; }
+    while (oe > ob && (ops[oe - 1].second == 'I' || ops[oe - 1].second == 'D')) --oe;
+    if (oe == ob) continue;
+    wfm_pav_prob_t p{r.target_global + r.target_offset + ta, (uint64_t)runs.size(), (uint32_t)(oe - ob), r.pav_group};
+    bool known = true;
+    for (size_t k = ob; k < oe; ++k) {
+      const char c = ops[k].second;
+      const uint32_t op = c == '=' ? 0u : c == 'X' ? 1u : c == 'I' ? 2u : c == 'D' ? 3u : 4u;
+      if (op > 3u || ops[k].first <= 0 || (uint32_t)ops[k].first >= (1u << 30)) { known = false; break; }
+      runs.push_back(((uint32_t)ops[k].first << 2) | op);
+    }
+    if (!known) { runs.resize((size_t)p.runs_off); ++unknown; continue; }
+    probs.push_back(p);
+  }
+  int rc = WFM_OK;
+  auto t1 = t0;
+  if (!probs.empty()) {
+    std::vector<uint32_t> flags(probs.size());
+    std::lock_guard<std::mutex> lk(handle_lock(b.h));
+    t1 = Clock::now();
+    rc = wfm_pav_add(b.h, b.fmt.pav, probs.data(), probs.size(), runs.data(), runs.size(), flags.data());
+    if (rc < 0 && b.stats) b.stats->error = wfm_last_error(b.h);
+  }
+  if (rc < 0) return rc;
+  g_pav_counts[0] += probs.size() - (uint64_t)rc;
+  if (rc > 0 || unknown)
+    fprintf(stderr, "[wflign] pav: %llu records of a batch were NOT added (their runs leave the target or cannot be held, or their query has no column)\n",
+            (unsigned long long)((uint64_t)rc + unknown));
+  if (getenv("WFM_DEBUG"))
+    fprintf(stderr, "[wflign] pav: %zu records, %zu runs, %d flagged, %.1f ms (runs %.1f, device call %.1f)\n", probs.size(), runs.size(), rc,
+            ms_between(t0, Clock::now()), ms_between(t0, t1), ms_between(t1, Clock::now()));
+  return 0;
+}
 // ---- --lift: the BED intervals through the runs of every record WRITTEN, ONE device call per batch (wfm_lift_runs).  It runs where
 // coverage_records runs and takes the same problems: the part of the ops the line spells, at base = the target sequence's offset in the
 // concatenation + the target start the writer wrote; the query window is the writer's too (variant_records' qs, qe).  Nothing goes up
@@ -768,6 +823,18 @@ void lift_paths(std::string& bed, std::string& out) {
 
 void lift_bed_read(uint64_t skipped) { g_lift_counts[3] += skipped; }
 
+void pav_paths(std::string& bed, uint64_t& window, std::string& out) {
+  std::lock_guard<std::mutex> lk(g_pav_mu);
+  const bool on = g_pav.load();
+  bed = on ? g_pav_bed : std::string();
+  window = on ? g_pav_window : 0;
+  out = on ? g_pav_out : std::string();
+}
+
+void pav_finished(uint64_t rows, uint64_t union_intervals, uint64_t bed_skipped) {
+  g_pav_counts[1] += rows; g_pav_counts[2] += union_intervals; g_pav_counts[3] += bed_skipped;
+}
+
 std::string coverage_path() {
   std::lock_guard<std::mutex> lk(g_coverage_mu);
   return g_coverage.load() ? g_coverage_path : std::string();
@@ -818,6 +885,7 @@ int do_biwfa_alignment_batch(wfm_handle_t* h, std::vector<BiwfaRecord>& recs, co
     for_each_record(n, fmt.threads, [&](size_t ri) { swizzle(b, ri); write_record(b, ri); });
   }
   if (fmt.coverage && (rc = coverage_records(b)) < 0) return rc;
+  if (fmt.pav && (rc = pav_records(b)) < 0) return rc;
   if (fmt.liftset && (rc = lift_records(b)) < 0) return rc;
   if (dbg)
     fprintf(stderr, "[wflign] %zu records: main alignment + runs + scans %.1f ms (incl. waiting for the device), patches %.1f ms (%zu tails scanned after their heads), swizzle + records %.1f ms\n",
@@ -872,6 +940,25 @@ void wfmh_set_lift(const char* bed_path_or_null, const char* out_path_or_null) {
     wflign::g_lift_out = on ? out_path_or_null : "";
   }
   wflign::g_lift.store(on);
+}
+
+void wfmh_set_pav(const char* bed_path_or_null, uint64_t window, const char* out_path_or_null) {
+  for (auto& a : wflign::g_pav_counts) a.store(0);
+  const bool bed = bed_path_or_null && *bed_path_or_null;
+  const bool on = out_path_or_null && *out_path_or_null && (bed != (window != 0));  // (one of the two, never both)
+  {
+    std::lock_guard<std::mutex> lk(wflign::g_pav_mu);
+    wflign::g_pav_bed = on && bed ? bed_path_or_null : "";
+    wflign::g_pav_window = on && !bed ? window : 0;
+    wflign::g_pav_out = on ? out_path_or_null : "";
+  }
+  wflign::g_pav.store(on);
+}
+
+int wfmh_pav_counts(uint64_t out[4]) {
+  if (!out) return WFM_E_ARG;
+  for (int q = 0; q < 4; ++q) out[q] = wflign::g_pav_counts[q].load();
+  return WFM_OK;
 }
 
 int wfmh_lift_counts(uint64_t out[4]) {

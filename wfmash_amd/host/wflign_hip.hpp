@@ -19,6 +19,8 @@
 //   write_record       PAF / SAM record (+ cs:Z: as its last field)   (wflign.cpp:434-454)
 //   coverage_records   --coverage only: the runs of every record WRITTEN into the handle's depth object, one wfm_coverage_add call
 //                      (nothing is uploaded but runs; whether a record is written is only known behind write_record)
+//   pav_records        --pav only: the runs of every record WRITTEN, with the column of its query's group, into the handle's presence
+//                      object, one wfm_pav_add call (runs alone again)
 //   lift_records       --lift only: the BED intervals lifted through the runs of every record WRITTEN, one wfm_lift_runs call
 //                      (runs alone again), the record's lines into BiwfaRecord::lift
 // and CIGARs are runs (count, op) from the device to the record's text: nothing is expanded to one byte per base.
@@ -77,6 +79,7 @@ struct BiwfaRecord {
   uint32_t vcf_masked = 0;           // ... SNVs left out of `vcf` because a base of theirs is not one of ACGT
   uint64_t target_global = 0;        // --coverage, --lift: where the target sequence begins in the concatenation of the target's sequences
   bool written = false;              // the filters let the record's line through (write_record)
+  uint32_t pav_group = 0;            // --pav: the column of the query sequence's group
   std::string lift;                  // --lift: the lines of the BED intervals the record's target span overlaps, each with its newline ("" if off or not written)
   uint32_t tags = 0;                 // WFM_PF_* of the main alignment | of the head patch << 8 | of the tail patch << 16 (diagnostics: WFM_RECORD_TAGS)
 };
@@ -117,7 +120,8 @@ struct OutputFormat {
   bool emit_md_tag = false;
   int threads = 1;                   // host threads for the per-record CIGAR / PAF work of a batch
   wfm_coverage_t* coverage = nullptr;  // --coverage: the depth object of the batch's handle (null: the stage is not run)
-  const wfm_liftset_t* liftset = nullptr;                    // --lift: the intervals on the batch's handle (null: the stage is not run) ...
+  wfm_pav_t* pav = nullptr;            // --pav: the presence object of the batch's handle (null: the stage is not run)
+  const wfm_liftset_t* liftset = nullptr;                   // --lift: the intervals on the batch's handle (null: the stage is not run) ...
   const std::vector<lift::Interval>* lift_intervals = nullptr;  // ... and as the BED had them, in the set's order
 };
 
@@ -133,6 +137,11 @@ void coverage_finished(uint64_t covered, uint64_t depth_sum, uint64_t intervals)
 // has read the BED: the lines it skipped
 void lift_paths(std::string& bed, std::string& out);
 void lift_bed_read(uint64_t skipped);
+
+// --pav: the BED, the window size and the file wfmh_set_pav named (out "" while the switch is off; one of bed and window is set), and what
+// the align phase adds to the counts once it has written the file: its rows, the union's intervals, the BED lines it skipped
+void pav_paths(std::string& bed, uint64_t& window, std::string& out);
+void pav_finished(uint64_t rows, uint64_t union_intervals, uint64_t bed_skipped);
 
 int do_biwfa_alignment_batch(wfm_handle_t* h, std::vector<BiwfaRecord>& recs, const wflign_penalties_t& penalties,
                              bool disable_chain_patching, const PafParams& pp, BiwfaStats* stats,
