@@ -490,6 +490,27 @@ def test_driver_windows(gpu, case):
     assert at == dict(zip(case.names, case.lengths))
 
 
+def test_driver_all_three_switches_on_one_run(gpu, case):
+    """--coverage, --pav and --lift together pack a batch's records once: the three files and the PAF are, byte for byte, those of three
+    runs with one switch each (the run with --pav alone is the fixture's)"""
+    d = case.dir
+
+    def run(tag, cov, pav, lift):
+        capi.set_lift(case.bed if lift else None, lift)
+        try:
+            text, table, _ = _align([gpu], case, os.path.join(d, tag + ".paf"), case.bed if pav else None, 0, pav, coverage=cov)
+        finally:
+            capi.set_lift(None, None)
+        return text, table, (open(cov, "rb").read() if cov else None), (open(lift, "rb").read() if lift else None)
+
+    text_c, _, bedgraph, _ = run("only_cov", os.path.join(d, "only.bg"), None, None)
+    text_l, _, _, lifts = run("only_lift", None, None, os.path.join(d, "only.lift"))
+    text, table, bedgraph3, lifts3 = run("all3", os.path.join(d, "all3.bg"), os.path.join(d, "all3.pav"), os.path.join(d, "all3.lift"))
+    assert text == text_c == text_l == case.with_text == case.text
+    assert len(bedgraph) > 0 and len(lifts) > 0
+    assert bedgraph3 == bedgraph and lifts3 == lifts and table == case.table
+
+
 def test_pav_paf_entry_point(gpu, case):
     out = os.path.join(case.dir, "offline.pav")
     counts = capi.pav_paf(gpu, case.fa, None, os.path.join(case.dir, "plain.paf"), case.bed, 0, out)

@@ -338,6 +338,30 @@ def _make_problems(items):
     return arr, keep, len(items)
 
 
+def _result_array(results, n, copy=False):
+    """The results of n problems as a ctypes array of Result.  results: such an array (returned as it is, or copied with copy=True: the
+    call writes into it), or a list of (status, score, ops_off, ops_len, n_runs)."""
+    if isinstance(results, C.Array) and not copy:
+        return results
+    arr = (Result * max(n, 1))()
+    if isinstance(results, C.Array):
+        C.memmove(arr, results, C.sizeof(Result) * n)
+    else:
+        assert len(results) == n, (len(results), n)
+        for i, (status, score, ops_off, ops_len, n_runs) in enumerate(results):
+            arr[i].status, arr[i].score, arr[i].ops_off, arr[i].ops_len, arr[i].n_runs = status, score, ops_off, ops_len, n_runs
+    return arr
+
+
+def _run_problems(problems, dtype):
+    """A list of (base, runs_off, n_runs) or (base, runs_off, n_runs, group) as a numpy array of wfm_cov_prob_t / wfm_pav_prob_t, and its
+    address (None for an empty list)."""
+    probs = np.zeros(len(problems), dtype=dtype)
+    for i, p in enumerate(problems):
+        probs[i] = tuple(p) + (0,) * (4 - len(p))
+    return probs, (probs.ctypes.data if len(probs) else None)
+
+
 def _make_refs(refs):
     """refs: iterable of ProblemRef, or of dicts keyed by its field names.  A side is either a window of the store
     (pattern_seq / pattern_off / plen[/ pattern_revcomp], likewise text_*) or host bytes (pattern=b"...", text=b"..."; the
@@ -585,12 +609,10 @@ class Coverage:
     def add(self, problems, runs):
         """wfm_coverage_add.  problems: a list of (base, runs_off, n_runs); runs: the run words ((length << 2) | op).  Returns the
         problems' flags as a numpy array (WFM_COV_SPANS: nothing of the problem was added)."""
-        probs = np.zeros(len(problems), dtype=COV_PROB_DTYPE)
-        for i, (base, off, n) in enumerate(problems):
-            probs[i] = (base, off, n, 0)
+        probs, probs_p = _run_problems(problems, COV_PROB_DTYPE)
         runs = np.ascontiguousarray(runs, dtype=np.uint32)
         flags = np.zeros(max(len(problems), 1), dtype=np.uint32)
-        rc = self._L.wfm_coverage_add(self._h._p, self._p, probs.ctypes.data if len(probs) else None, len(probs),
+        rc = self._L.wfm_coverage_add(self._h._p, self._p, probs_p, len(probs),
                                       runs.ctypes.data if len(runs) else None, len(runs), flags.ctypes.data)
         if rc < 0:
             raise WfmError(f"wfm_coverage_add failed ({rc}): {self._h.last_error()}")
@@ -672,13 +694,11 @@ class LiftSet:
     def lift(self, problems, runs):
         """wfm_lift_runs.  problems: a list of (base, runs_off, n_runs); runs: the run words ((length << 2) | op).  Returns (the lifts as
         a numpy array with the fields of Lift, the problems' records as one with the fields of LiftCall)."""
-        probs = np.zeros(len(problems), dtype=COV_PROB_DTYPE)
-        for i, (base, off, n) in enumerate(problems):
-            probs[i] = (base, off, n, 0)
+        probs, probs_p = _run_problems(problems, COV_PROB_DTYPE)
         runs = np.ascontiguousarray(runs, dtype=np.uint32)
         per = np.zeros(max(len(problems), 1), dtype=LIFTCALL_DTYPE)
         ptr, n = C.c_void_p(), C.c_size_t(0)
-        rc = self._L.wfm_lift_runs(self._h._p, self._p, probs.ctypes.data if len(probs) else None, len(probs),
+        rc = self._L.wfm_lift_runs(self._h._p, self._p, probs_p, len(probs),
                                    runs.ctypes.data if len(runs) else None, len(runs), C.byref(ptr), C.byref(n), per.ctypes.data)
         if rc != 0:
             assert not ptr.value and n.value == 0
@@ -739,12 +759,10 @@ class Pav:
     def add(self, problems, runs):
         """wfm_pav_add.  problems: a list of (base, runs_off, n_runs, group); runs: the run words ((length << 2) | op).  Returns the
         problems' flags as a numpy array (WFM_PAV_SPANS: nothing of the problem was added)."""
-        probs = np.zeros(len(problems), dtype=PAV_PROB_DTYPE)
-        for i, (base, off, n, g) in enumerate(problems):
-            probs[i] = (base, off, n, g)
+        probs, probs_p = _run_problems(problems, PAV_PROB_DTYPE)
         runs = np.ascontiguousarray(runs, dtype=np.uint32)
         flags = np.zeros(max(len(problems), 1), dtype=np.uint32)
-        rc = self._L.wfm_pav_add(self._h._p, self._p, probs.ctypes.data if len(probs) else None, len(probs),
+        rc = self._L.wfm_pav_add(self._h._p, self._p, probs_p, len(probs),
                                  runs.ctypes.data if len(runs) else None, len(runs), flags.ctypes.data)
         if rc < 0:
             raise WfmError(f"wfm_pav_add failed ({rc}): {self._h.last_error()}")
@@ -991,12 +1009,7 @@ class Handle:
         align call) or a list of (status, score, ops_off, ops_len, n_runs), one per problem of the seqset; runs: uint32 runs,
         (length << 2) | op.  Returns (flagged, [Check])."""
         n = seqset.n
-        if not isinstance(results, C.Array):
-            arr = (Result * max(n, 1))()
-            assert len(results) == n, (len(results), n)
-            for i, (status, score, ops_off, ops_len, n_runs) in enumerate(results):
-                arr[i].status, arr[i].score, arr[i].ops_off, arr[i].ops_len, arr[i].n_runs = status, score, ops_off, ops_len, n_runs
-            results = arr
+        results = _result_array(results, n)
         runs = np.ascontiguousarray(runs, dtype=np.uint32)
         pn = Penalties(*(pen or DEFAULT_PEN))
         out = (Check * max(n, 1))()
@@ -1014,13 +1027,7 @@ class Handle:
         Returns (results: a new ctypes array of Result whose ops_off / n_runs locate the problems in the new runs, runs: uint32 array,
         stats: [LeftAlign], one per problem)."""
         n = seqset.n
-        arr = (Result * max(n, 1))()
-        if isinstance(results, C.Array):
-            C.memmove(arr, results, C.sizeof(Result) * n)
-        else:
-            assert len(results) == n, (len(results), n)
-            for i, (status, score, ops_off, ops_len, n_runs) in enumerate(results):
-                arr[i].status, arr[i].score, arr[i].ops_off, arr[i].ops_len, arr[i].n_runs = status, score, ops_off, ops_len, n_runs
+        arr = _result_array(results, n, copy=True)
         runs = np.ascontiguousarray(runs, dtype=np.uint32)
         out = (LeftAlign * max(n, 1))()
         new = C.POINTER(C.c_uint32)()
@@ -1044,13 +1051,7 @@ class Handle:
         check_runs; form: WFM_CS_SHORT or WFM_CS_LONG.  Returns (the strings as bytes, one per problem -- b"" for a flagged one --,
         [Cs], one per problem)."""
         n = seqset.n
-        arr = (Result * max(n, 1))()
-        if isinstance(results, C.Array):
-            C.memmove(arr, results, C.sizeof(Result) * n)
-        else:
-            assert len(results) == n, (len(results), n)
-            for i, (status, score, ops_off, ops_len, n_runs) in enumerate(results):
-                arr[i].status, arr[i].score, arr[i].ops_off, arr[i].ops_len, arr[i].n_runs = status, score, ops_off, ops_len, n_runs
+        arr = _result_array(results, n, copy=True)
         runs = np.ascontiguousarray(runs, dtype=np.uint32)
         per = (Cs * max(n, 1))()
         text = C.c_void_p()
@@ -1074,13 +1075,7 @@ class Handle:
         check_runs.  Returns (records: a numpy structured array with the fields of Variant, alleles: all allele bytes as bytes,
         [VarCall], one per problem)."""
         n = seqset.n
-        arr = (Result * max(n, 1))()
-        if isinstance(results, C.Array):
-            C.memmove(arr, results, C.sizeof(Result) * n)
-        else:
-            assert len(results) == n, (len(results), n)
-            for i, (status, score, ops_off, ops_len, n_runs) in enumerate(results):
-                arr[i].status, arr[i].score, arr[i].ops_off, arr[i].ops_len, arr[i].n_runs = status, score, ops_off, ops_len, n_runs
+        arr = _result_array(results, n, copy=True)
         runs = np.ascontiguousarray(runs, dtype=np.uint32)
         per = (VarCall * max(n, 1))()
         recs, alleles = C.c_void_p(), C.c_void_p()
@@ -1122,11 +1117,7 @@ class Handle:
         (flags, dp_score, band_lo, band_hi, cells)."""
         n = seqset.n
         if not isinstance(results, C.Array):
-            arr = (Result * max(n, 1))()
-            assert len(results) == n, (len(results), n)
-            for i, r in enumerate(results):
-                arr[i].status, arr[i].score = r if isinstance(r, tuple) else (0, r)
-            results = arr
+            results = _result_array([(r if isinstance(r, tuple) else (0, r)) + (0, 0, 0) for r in results], n)
         pn = Penalties(*(pen or DEFAULT_PEN))
         out = (OptCheck * max(n, 1))()
         f = self._L.wfm_check_optimal

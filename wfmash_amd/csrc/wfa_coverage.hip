@@ -1,14 +1,14 @@
 // wfa_coverage.hip -- the kernels behind wfm_coverage_* (include/wfmash_hip.h): per-base depth of the target from the runs of many records,
 // kept as a DIFFERENCE array of int32 words over the concatenation of the target sequences.  Nothing but runs is read: no sequence bytes.
 //
-//   cov_add_kernel        one workgroup per problem.  A first pass over the runs takes the pattern span (and refuses the problem when it leaves
+//   cov_add_kernel        one workgroup per problem.  wfa_scan.h's run_span takes the pattern span (the problem is refused when it leaves
 //                         [0, n_bases] or holds an empty run) BEFORE any word is touched; the second pass goes in rounds of 256 runs with a
 //                         carry (var_index_kernel's shape, wfa_scan.h's block_excl for the pattern advance) and emits +1 where an aligned
 //                         segment (=/X runs with no I or D between them) begins and -1 where it ends: two integer atomics per segment.
 //   cov_count_kernel      one workgroup per tile of WFM_COV_TILE words: how many are non-zero, read in 16-byte loads.
-//   cov_sum_kernel /      the two scans (tile counts; the deltas of a compact list) in the reduce / scan-of-sums / apply form, as separate
-//   cov_scan_sums_kernel  launches: per block of WFM_COV_SCAN_BLOCK elements its sum; ONE workgroup turns the sums into exclusive prefixes
-//                         (rounds of 256 with a carry); the apply step is the consumer's.  No workgroup ever waits for another.
+//   cov_sum_kernel        the two scans (tile counts; the deltas of a compact list) in the reduce / scan-of-sums / apply form, as separate
+//                         launches: per block of WFM_COV_SCAN_BLOCK elements its sum; ONE workgroup turns the sums into exclusive prefixes
+//                         (wfa_scan.h's scan_sums_kernel); the apply step is the consumer's.  No workgroup ever waits for another.
 //   cov_offsets_kernel    apply for the tile counts: every tile's offset in the compact list.
 //   cov_write_kernel      one workgroup per tile: the non-zero words as {pos, delta} in ascending pos, 16 bytes a store.
 //   cov_import_kernel     one lane per entry of such a list: atomicAdd into another array (the merge of two devices' objects).
@@ -37,22 +37,12 @@ __global__ __launch_bounds__(COV_THREADS) void cov_add_kernel(const uint32_t* __
   const int tid = threadIdx.x;
   __shared__ unsigned long long wtot[COV_WAVES];
   __shared__ uint32_t s_bad;
-  if (tid == 0) s_bad = 0;
   const uint32_t* my = runs + pr.runs_off;
   const uint32_t n = pr.n_runs;
   // the span first: nothing is written for a problem that would leave the array
-  unsigned long long mine = 0;
-  bool bad = false;
-  for (uint32_t r = (uint32_t)tid; r < n; r += COV_THREADS) {
-    const uint32_t run = my[r];
-    if (WFM_RUN_LEN(run) == 0) bad = true;
-    if (WFM_RUN_OP(run) != OP_I) mine += WFM_RUN_LEN(run);
-  }
   unsigned long long span;
-  (void)block_excl<COV_WAVES>(mine, wtot, &span);
-  if (bad) s_bad = 1;  // (every writer stores the same value)
-  __syncthreads();
-  const bool spans = s_bad || pr.base > n_bases || span > n_bases - pr.base;
+  const bool empty_run = run_span<COV_WAVES, false>(my, n, wtot, &s_bad, &span, nullptr);
+  const bool spans = empty_run || pr.base > n_bases || span > n_bases - pr.base;
   if (tid == 0) flags[blockIdx.x] = spans ? WFM_COV_SPANS : 0u;
   if (spans) return;
   unsigned long long carry = 0;
@@ -97,22 +87,6 @@ __global__ __launch_bounds__(COV_THREADS) void cov_sum_kernel(const void* __rest
   unsigned long long all;
   (void)block_excl<COV_WAVES>(v, wtot, &all);
   if (threadIdx.x == 0) sums[blockIdx.x] = all;
-}
-
-// ONE workgroup: sums[0 .. nb) to their exclusive prefixes, begun at *carry where there is one, sums[nb] = the total, *carry = the total too
-__global__ __launch_bounds__(COV_THREADS) void cov_scan_sums_kernel(unsigned long long* __restrict__ sums, unsigned long long nb, unsigned long long* carry) {
-  __shared__ unsigned long long wtot[COV_WAVES];
-  unsigned long long run = carry ? *carry : 0ull;
-  __syncthreads();  // (thread 0 writes *carry at the end)
-  for (unsigned long long base = 0; base < nb; base += COV_THREADS) {
-    const unsigned long long i = base + threadIdx.x;
-    const unsigned long long v = i < nb ? sums[i] : 0ull;
-    unsigned long long all;
-    const unsigned long long ex = block_excl<COV_WAVES>(v, wtot, &all);
-    if (i < nb) sums[i] = run + ex;
-    run += all;
-  }
-  if (threadIdx.x == 0) { sums[nb] = run; if (carry) *carry = run; }
 }
 
 // tile_off[t] = the number of non-zero words in the tiles before t; tile_off[ntiles] = all of them (by the block that holds the last tile)
@@ -234,7 +208,8 @@ void launch_cov_tile_offsets(const int32_t* d, unsigned long long ntiles, uint32
   const unsigned nb = blocks_of(ntiles, WFM_COV_SCAN_BLOCK);
   hipLaunchKernelGGL(cov_count_kernel, dim3((unsigned)ntiles), dim3(COV_THREADS), 0, st, (const uint4*)d, tile_cnt);
   hipLaunchKernelGGL(cov_sum_kernel<false>, dim3(nb), dim3(COV_THREADS), 0, st, (const void*)tile_cnt, ntiles, sums);
-  hipLaunchKernelGGL(cov_scan_sums_kernel, dim3(1), dim3(COV_THREADS), 0, st, sums, (unsigned long long)nb, (unsigned long long*)nullptr);
+  hipLaunchKernelGGL((scan_sums_kernel<COV_WAVES, false, LoadWord>), dim3(1), dim3(COV_THREADS), 0, st, LoadWord{sums}, (unsigned long long)nb, sums,
+                     (unsigned long long*)nullptr);
   hipLaunchKernelGGL(cov_offsets_kernel, dim3(nb), dim3(COV_THREADS), 0, st, (const uint32_t*)tile_cnt, ntiles, (const unsigned long long*)sums, tile_off);
 }
 
@@ -254,7 +229,8 @@ void launch_cov_intervals(const void* ent, unsigned long long m, unsigned long l
   if (m == 0) return;
   const unsigned nb = blocks_of(m, WFM_COV_SCAN_BLOCK);
   hipLaunchKernelGGL(cov_sum_kernel<true>, dim3(nb), dim3(COV_THREADS), 0, st, ent, m, sums);
-  hipLaunchKernelGGL(cov_scan_sums_kernel, dim3(1), dim3(COV_THREADS), 0, st, sums, (unsigned long long)nb, carry);
+  // (the prefixes begin at *carry, the depth behind the chunks before, and *carry is brought up to date)
+  hipLaunchKernelGGL((scan_sums_kernel<COV_WAVES, true, LoadWord>), dim3(1), dim3(COV_THREADS), 0, st, LoadWord{sums}, (unsigned long long)nb, sums, carry);
   hipLaunchKernelGGL(cov_intervals_kernel, dim3(nb), dim3(COV_THREADS), 0, st, (const uint4*)ent, m, (const unsigned long long*)sums, prev_pos, n_bases, last,
                      (uint4*)iv, totals);
 }

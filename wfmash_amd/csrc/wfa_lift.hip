@@ -1,17 +1,15 @@
 // wfa_lift.hip -- the kernels behind wfm_liftset_* and wfm_lift_runs (include/wfmash_hip.h): where intervals of the target lie in the query,
 // through the runs of many records.  The pattern is the target, the text the query as aligned.  Nothing but runs is read: no sequence bytes.
 //
-//   lift_block_max_kernel /  the running maximum of `end` over the sorted intervals, pm[i] = max(end[0 .. i]), in the reduce / scan-of-sums /
-//   lift_scan_max_kernel /   apply form of wfa_coverage.hip with max in place of sum, as separate launches: per block of WFM_LIFT_SCAN_BLOCK
-//   lift_pm_kernel           intervals its maximum; ONE workgroup turns the maxima into the maximum before each block (rounds of 256 with a
-//                            carry); the apply step scans its block again.  No workgroup ever waits for another.
-//   lift_index_kernel        one workgroup per problem.  A first pass over the runs takes the pattern and text spans (and refuses the problem
+//   launch_runmax            (wfa_scan.h) the running maximum of `end` over the sorted intervals, pm[i] = max(end[0 .. i]), per block of
+//                            WFM_LIFT_SCAN_BLOCK intervals.
+//   lift_index_kernel        one workgroup per problem.  wfa_scan.h's run_span takes the pattern and text spans (the problem is refused
 //                            when the pattern span leaves [0, n_bases], a span does not fit 32 bits or a run is empty) BEFORE anything is
 //                            written; the second pass goes in rounds of 256 runs with a carry and stores per run the four exclusive prefixes
 //                            {pattern, text, = columns, X columns} as ONE 16-byte word, and the four totals behind the last run.  Then the
 //                            candidate window [lo, hi) of the problem's span [a, b): lo = the first i with pm[i] > a, hi = the first i with
 //                            start[i] >= b, two binary searches, and the count of the intervals in it with end > a.
-//   lift_offsets_kernel      ONE workgroup: the counts to their exclusive prefixes over the problems (rounds of 256 with a carry).
+//   scan_sums_kernel         (wfa_scan.h) ONE workgroup: the counts to their exclusive prefixes over the problems.
 //   lift_write_kernel        one workgroup per problem of a chunk: the same enumeration in rounds of 256 intervals, every overlapping interval
 //                            placed by a block scan (no atomics: two calls give the same bytes), ONE lane per pair resolving its endpoints in
 //                            four binary searches over the prefix words (lift_resolve), 32 bytes a lift in two 16-byte stores.
@@ -30,93 +28,6 @@ constexpr int LIFT_THREADS = 256;
 constexpr int LIFT_WAVES = LIFT_THREADS / 64;
 static_assert(WFM_LIFT_SCAN_BLOCK == LIFT_THREADS * 4, "a scan block is four intervals per lane");
 
-// inclusive running maximum of v over the workgroup's threads (in thread order) and the maximum of all; wmax: LIFT_WAVES words of LDS
-__device__ __forceinline__ unsigned long long block_incl_max(unsigned long long v, unsigned long long* wmax, unsigned long long* all) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  unsigned long long incl = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const unsigned long long u = scan_shfl_up64(incl, d);
-    if (lane >= d && u > incl) incl = u;
-  }
-  __syncthreads();  // (the words may still be read from the scan before)
-  if (lane == 63) wmax[wave] = incl;
-  __syncthreads();
-  unsigned long long top = 0;
-#pragma unroll
-  for (int w = 0; w < LIFT_WAVES; ++w) {
-    if (w < wave && wmax[w] > incl) incl = wmax[w];
-    if (wmax[w] > top) top = wmax[w];
-  }
-  *all = top;
-  return incl;
-}
-
-// maxs[b] = the largest end of block b (iv: {start, end} as two 64-bit words, 16 bytes an interval)
-__global__ __launch_bounds__(LIFT_THREADS) void lift_block_max_kernel(const ulonglong2* __restrict__ iv, unsigned long long n, unsigned long long* __restrict__ maxs) {
-  __shared__ unsigned long long wmax[LIFT_WAVES];
-  const unsigned long long at = (unsigned long long)blockIdx.x * WFM_LIFT_SCAN_BLOCK + (unsigned long long)threadIdx.x * 4u;
-  unsigned long long v = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-    if (at + k < n && iv[at + k].y > v) v = iv[at + k].y;
-  unsigned long long all;
-  (void)block_incl_max(v, wmax, &all);
-  if (threadIdx.x == 0) maxs[blockIdx.x] = all;
-}
-
-// ONE workgroup: maxs[0 .. nb) to the maximum of the blocks BEFORE each (0 before the first: every end is 1 at least)
-__global__ __launch_bounds__(LIFT_THREADS) void lift_scan_max_kernel(unsigned long long* __restrict__ maxs, unsigned long long nb) {
-  __shared__ unsigned long long wmax[LIFT_WAVES];
-  __shared__ unsigned long long prev[LIFT_THREADS];
-  unsigned long long run = 0;
-  for (unsigned long long base = 0; base < nb; base += LIFT_THREADS) {
-    const unsigned long long i = base + threadIdx.x;
-    const unsigned long long v = i < nb ? maxs[i] : 0ull;
-    unsigned long long all;
-    const unsigned long long incl = block_incl_max(v, wmax, &all);
-    __syncthreads();  // (prev may still be read from the round before)
-    prev[threadIdx.x] = incl;
-    __syncthreads();
-    const unsigned long long before = threadIdx.x ? prev[threadIdx.x - 1] : 0ull;
-    if (i < nb) maxs[i] = run > before ? run : before;
-    if (all > run) run = all;
-  }
-}
-
-// apply: pm[i] = max(the maximum before the block, the ends of the block up to i)
-__global__ __launch_bounds__(LIFT_THREADS) void lift_pm_kernel(const ulonglong2* __restrict__ iv, unsigned long long n, const unsigned long long* __restrict__ maxs,
-                                                               unsigned long long* __restrict__ pm) {
-  __shared__ unsigned long long wmax[LIFT_WAVES];
-  __shared__ unsigned long long prev[LIFT_THREADS];
-  const unsigned long long at = (unsigned long long)blockIdx.x * WFM_LIFT_SCAN_BLOCK + (unsigned long long)threadIdx.x * 4u;
-  unsigned long long e[4], v = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) { e[k] = at + k < n ? iv[at + k].y : 0ull; if (e[k] > v) v = e[k]; }
-  unsigned long long all;
-  const unsigned long long incl = block_incl_max(v, wmax, &all);
-  prev[threadIdx.x] = incl;
-  __syncthreads();
-  unsigned long long run = maxs[blockIdx.x];
-  if (threadIdx.x && prev[threadIdx.x - 1] > run) run = prev[threadIdx.x - 1];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    if (e[k] > run) run = e[k];
-    if (at + k < n) pm[at + k] = run;
-  }
-}
-
-// the first i in [0, n) with gt(i), or n; gt is false on a prefix of the range and true behind it
-template <class Gt>
-__device__ __forceinline__ unsigned long long first_true(unsigned long long n, Gt gt) {
-  unsigned long long lo = 0, hi = n;
-  while (lo < hi) {
-    const unsigned long long mid = lo + (hi - lo) / 2;
-    if (gt(mid)) hi = mid; else lo = mid + 1;
-  }
-  return lo;
-}
-
 __global__ __launch_bounds__(LIFT_THREADS) void lift_index_kernel(const uint32_t* __restrict__ runs, const LiftProb* __restrict__ probs,
                                                                   const ulonglong2* __restrict__ iv, const unsigned long long* __restrict__ pm,
                                                                   unsigned long long n_iv, unsigned long long n_bases, uint4* __restrict__ pre,
@@ -126,24 +37,12 @@ __global__ __launch_bounds__(LIFT_THREADS) void lift_index_kernel(const uint32_t
   __shared__ unsigned long long wtot[LIFT_WAVES];
   __shared__ uint32_t s_bad;
   __shared__ unsigned long long s_lo, s_hi;
-  if (tid == 0) s_bad = 0;
   const uint32_t* my = runs + pr.runs_off;
   const uint32_t n = pr.n_runs;
   // the spans first: nothing is written for a problem that is refused
-  unsigned long long mine_p = 0, mine_t = 0;
-  bool bad = false;
-  for (uint32_t r = (uint32_t)tid; r < n; r += LIFT_THREADS) {
-    const uint32_t run = my[r];
-    if (WFM_RUN_LEN(run) == 0) bad = true;
-    if (WFM_RUN_OP(run) != OP_I) mine_p += WFM_RUN_LEN(run);
-    if (WFM_RUN_OP(run) != OP_D) mine_t += WFM_RUN_LEN(run);
-  }
   unsigned long long span, tspan;
-  (void)block_excl<LIFT_WAVES>(mine_p, wtot, &span);
-  (void)block_excl<LIFT_WAVES>(mine_t, wtot, &tspan);
-  if (bad) s_bad = 1;  // (every writer stores the same value)
-  __syncthreads();
-  const bool spans = s_bad || n == 0 || pr.base > n_bases || span > n_bases - pr.base || span > 0xffffffffull || tspan > 0xffffffffull;
+  const bool empty_run = run_span<LIFT_WAVES, true>(my, n, wtot, &s_bad, &span, &tspan);
+  const bool spans = empty_run || n == 0 || pr.base > n_bases || span > n_bases - pr.base || span > 0xffffffffull || tspan > 0xffffffffull;
   if (spans) {
     if (tid == 0) { LiftWin w; w.lo = 0; w.hi = 0; w.count = 0; w.flags = WFM_LIFT_SPANS; w.plen = 0; win[blockIdx.x] = w; }
     return;
@@ -177,21 +76,6 @@ __global__ __launch_bounds__(LIFT_THREADS) void lift_index_kernel(const uint32_t
   unsigned long long all;
   (void)block_excl<LIFT_WAVES>(c, wtot, &all);
   if (tid == 0) { LiftWin w; w.lo = lo; w.hi = hi; w.count = all; w.flags = 0; w.plen = (uint32_t)span; win[blockIdx.x] = w; }
-}
-
-// ONE workgroup: off[i] = the lifts of the problems before i, off[n] = all of them
-__global__ __launch_bounds__(LIFT_THREADS) void lift_offsets_kernel(const LiftWin* __restrict__ win, unsigned long long n, unsigned long long* __restrict__ off) {
-  __shared__ unsigned long long wtot[LIFT_WAVES];
-  unsigned long long run = 0;
-  for (unsigned long long base = 0; base < n; base += LIFT_THREADS) {
-    const unsigned long long i = base + threadIdx.x;
-    const unsigned long long v = i < n ? win[i].count : 0ull;
-    unsigned long long all;
-    const unsigned long long ex = block_excl<LIFT_WAVES>(v, wtot, &all);
-    if (i < n) off[i] = run + ex;
-    run += all;
-  }
-  if (threadIdx.x == 0) off[n] = run;
 }
 
 // One pair.  P: the problem's n + 1 prefix words {pattern, text, = columns, X columns} (the totals last); [c0, c1), c0 < c1 <= the pattern
@@ -251,23 +135,20 @@ __global__ __launch_bounds__(LIFT_THREADS) void lift_write_kernel(const uint32_t
   }
 }
 
-unsigned blocks_of(unsigned long long n, unsigned long long per) { return (unsigned)((n + per - 1) / per); }
-
 }  // namespace
 
 void launch_lift_pm(const void* iv, unsigned long long n, unsigned long long* maxs, unsigned long long* pm, hipStream_t st) {
   if (n == 0) return;
-  const unsigned nb = blocks_of(n, WFM_LIFT_SCAN_BLOCK);
-  hipLaunchKernelGGL(lift_block_max_kernel, dim3(nb), dim3(LIFT_THREADS), 0, st, (const ulonglong2*)iv, n, maxs);
-  hipLaunchKernelGGL(lift_scan_max_kernel, dim3(1), dim3(LIFT_THREADS), 0, st, maxs, (unsigned long long)nb);
-  hipLaunchKernelGGL(lift_pm_kernel, dim3(nb), dim3(LIFT_THREADS), 0, st, (const ulonglong2*)iv, n, (const unsigned long long*)maxs, pm);
+  launch_runmax<LIFT_WAVES>(LoadEnd{(const ulonglong2*)iv}, n, maxs, pm, st);  // pm[i] = max(end[0 .. i])
 }
 
 void launch_lift_index(const uint32_t* runs, const LiftProb* probs, int nprob, const void* iv, const unsigned long long* pm, unsigned long long n_iv,
                        unsigned long long n_bases, void* pre, LiftWin* win, unsigned long long* off, hipStream_t st) {
   if (nprob <= 0) return;
   hipLaunchKernelGGL(lift_index_kernel, dim3((unsigned)nprob), dim3(LIFT_THREADS), 0, st, runs, probs, (const ulonglong2*)iv, pm, n_iv, n_bases, (uint4*)pre, win);
-  hipLaunchKernelGGL(lift_offsets_kernel, dim3(1), dim3(LIFT_THREADS), 0, st, (const LiftWin*)win, (unsigned long long)nprob, off);
+  // off[i] = the lifts of the problems before i, off[nprob] = all of them
+  hipLaunchKernelGGL((scan_sums_kernel<LIFT_WAVES, false, LoadWinCount>), dim3(1), dim3(LIFT_THREADS), 0, st, LoadWinCount{win}, (unsigned long long)nprob, off,
+                     (unsigned long long*)nullptr);
 }
 
 void launch_lift_write(const uint32_t* runs, const LiftProb* probs, const void* iv, const void* pre, const LiftWin* win, const unsigned long long* off,

@@ -1,0 +1,1203 @@
+// wfa_passes.hip -- the record passes of the C ABI (see include/wfmash_hip.h): host code that takes the final runs of a batch and
+// produces something from them -- the check against the bases, left-aligned gaps, cs strings, variants, target depth, lifted
+// intervals, presence per group, the proof of optimality.  The kernels are in wfa_check.hip, wfa_leftalign.hip, wfa_cs.hip,
+// wfa_variants.hip, wfa_coverage.hip, wfa_lift.hip, wfa_pav.hip and wfa_optcheck.hip.
+//
+// Every pass has the same frame, written once below: it validates the run ranges before anything is launched, carves what the
+// call has on the device out of one block, launches, writes its output in chunks that fit a cap, and waits for the stream before
+// it returns (so one scratch block and one output block of the handle serve all of them).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <climits>
+#include <cstdio>
+#include <cstring>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "wfa_host_shared.h"
+#include "wfa_optband.h"
+
+namespace {
+
+using namespace wfm;
+
+double env_decimal(const char* name, double dflt) { const char* e = getenv(name); return e && *e ? atof(e) : dflt; }
+// a cap given in MiB by the environment (a fraction is fine), in units of `unit` bytes, `least` at least
+unsigned long long cap_units(const char* name, size_t unit, unsigned long long least) {
+  return std::max<unsigned long long>(least, (unsigned long long)(std::max(0.0, env_decimal(name, 256.0)) * 1048576.0) / unit);
+}
+
+// ---- the frame ----
+
+// Typed, 8-byte aligned pieces of one device block: piece() notes where each will lie, commit() sizes the block for their sum and
+// sets the pointers.  `pass` is what the out-of-memory text names.
+struct Carver {
+  DevBuf<uint64_t>& buf;
+  const char* pass;
+  struct Slot { void* pp; size_t at; void (*set)(void* pp, uint64_t* at); };
+  Slot slots[12];
+  int n = 0;
+  size_t words = 0;
+  static size_t words64(size_t bytes) { return (bytes + 7) / 8; }
+  template <class T>
+  void piece(T** p, size_t count) {
+    slots[n++] = Slot{p, words, [](void* pp, uint64_t* at) { *(T**)pp = (T*)at; }};
+    words += words64(count * sizeof(T));
+  }
+  int commit(wfm_handle_t* h) {
+    if (buf.ensure(words + 8)) { h->err = std::string("out of device memory (") + pass + ")"; return WFM_E_NOMEM; }
+    for (int k = 0; k < n; ++k) slots[k].set(slots[k].pp, buf.p + slots[k].at);
+    return WFM_OK;
+  }
+};
+
+inline bool runs_inside(uint64_t off, uint64_t n_runs, size_t n_runs_total) { return off <= n_runs_total && n_runs <= n_runs_total - off; }
+int runs_leave(wfm_handle_t* h, size_t i) {
+  h->err = "problem " + std::to_string(i) + ": its runs leave the run buffer";
+  return WFM_E_ARG;
+}
+// every problem's range of a list of wfm_cov_prob_t / wfm_pav_prob_t, before anything is launched
+template <class P>
+int all_runs_inside(wfm_handle_t* h, const P* probs, size_t n, size_t n_runs_total) {
+  for (size_t i = 0; i < n; ++i)
+    if (!runs_inside(probs[i].runs_off, probs[i].n_runs, n_runs_total)) return runs_leave(h, i);
+  return WFM_OK;
+}
+
+// What CheckProb, LaProb, CsProb and OptProb share: the forward copies and their lengths; whether the problem has nothing for the pass
+// (score-only, status != 0, and for all but the check a result without runs)
+template <class P>
+void fill_seq(P& c, const ProbMeta& m) { c.p_off = m.p_fwd; c.t_off = m.t_fwd; c.plen = m.plen; c.tlen = m.tlen; }
+template <class P>
+void fill_ends(P& c, const ProbMeta& m) { c.pbf = m.pbf; c.pef = m.pef; c.tbf = m.tbf; c.tef = m.tef; }  // (0 unless the mode is ENDSFREE: layout_seqset)
+template <class P>
+void fill_prob(P& c, const ProbMeta& m, const wfm_result_t& r, bool skip_without_runs) {
+  fill_seq(c, m);
+  c.skip = (m.score_only() || r.status != 0 || (skip_without_runs && r.n_runs == 0)) ? 1 : 0;
+}
+
+// The largest kb in (ka, n] whose cost(ka, kb) fits the cap, ka + 1 at least (one problem, tile or row larger than the cap is a chunk of its
+// own).  cost grows with kb.
+template <class Cost>
+size_t chunk_end(size_t ka, size_t n, unsigned long long cap, Cost cost) {
+  size_t lo = ka + 1, hi = n;
+  while (lo < hi) {
+    const size_t mid = lo + (hi - lo + 1) / 2;
+    if (cost(ka, mid) <= cap) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+inline size_t chunk_end(size_t ka, const std::vector<unsigned long long>& off, unsigned long long cap) {
+  return chunk_end(ka, off.size() - 1, cap, [&](size_t a, size_t b) { return off[b] - off[a]; });
+}
+
+// An object of a device: usable() refuses a handle of another device; a guard makes the object's device current while it is freed
+struct DeviceGuard {
+  int cur = 0;
+  bool swap = false;
+  explicit DeviceGuard(int device) { swap = hipGetDevice(&cur) == hipSuccess && cur != device; if (swap) (void)hipSetDevice(device); }
+  ~DeviceGuard() { if (swap) (void)hipSetDevice(cur); }
+  static int usable(wfm_handle_t* h, int device, const char* what) {
+    if (device == h->device) return WFM_OK;
+    h->err = std::string(what) + " lives on device " + std::to_string(device) + ", the handle on " + std::to_string(h->device);
+    return WFM_E_ARG;
+  }
+};
+
+// The times of the [wfm] lines: the host clock from the construction or the last lap(), and the handle's two events around a launch.
+// on: WFM_DEBUG is set; without it nothing is recorded.
+struct PassTimer {
+  wfm_handle_t* h;
+  bool on = env_debug() != 0;
+  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now(), t_lap = t0;
+  explicit PassTimer(wfm_handle_t* h_) : h(h_) {}
+  hipError_t begin() { return on ? hipEventRecord(h->ev0, h->stream) : hipSuccess; }
+  hipError_t end() { return on ? hipEventRecord(h->ev1, h->stream) : hipSuccess; }
+  bool event_ms(float* ms) {  // (behind a wait for the stream)
+    if (!on) return false;
+    if (hipEventElapsedTime(ms, h->ev0, h->ev1) == hipSuccess) return true;
+    (void)hipGetLastError();
+    return false;
+  }
+  double host_ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+  double lap() {
+    const auto t = std::chrono::steady_clock::now();
+    const double ms = std::chrono::duration<double, std::milli>(t - t_lap).count();
+    t_lap = t;
+    return ms;
+  }
+};
+
+}  // namespace
+
+extern "C" {
+
+// ---- every run held against its bases (wfmash_hip.h; the kernels: wfa_check.hip) ----
+int wfm_check_runs(wfm_handle_t* h, const wfm_penalties_t* pen, const wfm_seqset_t* s, const wfm_result_t* res, const uint32_t* runs,
+                   size_t n_runs_total, wfm_check_t* out) {
+  if (!h || !s || !out || !res || (n_runs_total && !runs)) return WFM_E_ARG;
+  int scope = 0;
+  if (const int prc = validate_pen(pen, &scope)) { h->err = "unsupported penalties"; return prc; }
+  const size_t n = s->meta.size();
+  if (n == 0) return 0;
+  if (n > (size_t)INT32_MAX || n_runs_total > ((size_t)1 << 32)) { h->err = "wfm_check_runs: too many problems or runs for one call"; return WFM_E_ARG; }
+  HIPCHK(h, hipSetDevice(h->device));
+  // the problems as the kernels see them; the run ranges are validated here, before anything is launched
+  std::vector<CheckProb> probs(n);
+  std::vector<CheckTask> tasks;
+  for (size_t i = 0; i < n; ++i) {
+    const ProbMeta& m = s->meta[i];
+    CheckProb& c = probs[i];
+    fill_prob(c, m, res[i], false);  // (a result without runs is checked like any other)
+    fill_ends(c, m);
+    c.res_score = res[i].score; c.res_ops_len = res[i].ops_len;
+    c.run_off = 0; c.n_runs = 0;
+    if (c.skip) continue;
+    if (!runs_inside(res[i].ops_off, res[i].n_runs, n_runs_total)) return runs_leave(h, i);
+    c.run_off = res[i].ops_off; c.n_runs = res[i].n_runs;
+    // (compared runs spell at most plen + tlen ops: a slice beyond what the scan finds ends at once)
+    const int64_t slices = ((int64_t)m.plen + m.tlen + WFM_CHECK_SLICE - 1) / WFM_CHECK_SLICE;
+    for (int64_t q = 0; q < slices; ++q) tasks.push_back(CheckTask{(int32_t)i, (int32_t)q});
+  }
+  // one block: [runs | ops_pre | p_pre | t_pre | cmp_ops] as 32-bit words, then keys, results, problems and tasks (8-byte aligned each)
+  const size_t nr = n_runs_total;
+  uint32_t *d_runs, *d_opre, *d_ppre, *d_tpre, *d_cmp;
+  unsigned long long* d_keys;
+  wfm_check_t* d_out;
+  CheckProb* d_probs;
+  CheckTask* d_tasks;
+  Carver cv{h->scratch, "run check"};
+  cv.piece(&d_runs, nr); cv.piece(&d_opre, nr); cv.piece(&d_ppre, nr); cv.piece(&d_tpre, nr); cv.piece(&d_cmp, n);
+  cv.piece(&d_keys, n); cv.piece(&d_out, n); cv.piece(&d_probs, n); cv.piece(&d_tasks, tasks.size());
+  if (int rc = cv.commit(h)) return rc;
+  if (nr) HIPCHK(h, hipMemcpyAsync(d_runs, runs, nr * 4, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(d_probs, probs.data(), n * sizeof(CheckProb), hipMemcpyHostToDevice, h->stream));
+  if (!tasks.empty()) HIPCHK(h, hipMemcpyAsync(d_tasks, tasks.data(), tasks.size() * sizeof(CheckTask), hipMemcpyHostToDevice, h->stream));
+  PassTimer tm(h);
+  HIPCHK(h, tm.begin());
+  launch_check(s->d_seq, d_runs, d_probs, (int)n, d_tasks, (int64_t)tasks.size(), d_opre, d_ppre, d_tpre, d_cmp, d_keys, d_out,
+               DevPen{pen->x, pen->o1, pen->e1, pen->o2, pen->e2}, h->stream);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, tm.end());
+  HIPCHK(h, hipMemcpyAsync(out, d_out, n * sizeof(wfm_check_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  float ms = 0;
+  if (tm.event_ms(&ms))
+    fprintf(stderr, "[wfm] run check: %zu problems, %zu runs, %zu compare tasks, %llu bases of sequence in %.3f ms\n", n, nr, tasks.size(),
+            (unsigned long long)s->seq_bases, ms);
+  int flagged = 0;
+  for (size_t i = 0; i < n; ++i) flagged += (out[i].flags & ~WFM_CK_NOT_CHECKED) != 0;
+  return flagged;
+}
+
+// ---- every interior gap moved to its leftmost placement (wfmash_hip.h; the kernels: wfa_leftalign.hip) ----
+int wfm_left_align_runs(wfm_handle_t* h, const wfm_seqset_t* s, wfm_result_t* res, const uint32_t* runs, size_t n_runs_total, uint32_t** runs_out,
+                        size_t* n_runs_out_total, wfm_leftalign_t* out) {
+  if (!h || !s || !out || !res || !runs_out || (n_runs_total && !runs)) return WFM_E_ARG;
+  *runs_out = nullptr;
+  if (n_runs_out_total) *n_runs_out_total = 0;
+  const size_t n = s->meta.size();
+  if (n == 0) return 0;
+  if (n > (size_t)INT32_MAX || n_runs_total > ((size_t)1 << 31)) { h->err = "wfm_left_align_runs: too many problems or runs for one call"; return WFM_E_ARG; }
+  HIPCHK(h, hipSetDevice(h->device));
+  // the problems as the kernels see them; the run ranges are validated here, before anything is launched.  The interior gaps are counted on the
+  // way (the runs are in host memory and are read once for the upload anyway): a problem's slots in the output and in the gap list follow from it
+  std::vector<LaProb> probs(n);
+  uint64_t out_total = 0, gap_total = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const ProbMeta& m = s->meta[i];
+    LaProb& c = probs[i];
+    memset(&c, 0, sizeof(c));
+    fill_prob(c, m, res[i], true);
+    const bool inside = runs_inside(res[i].ops_off, res[i].n_runs, n_runs_total);
+    if (!c.skip && !inside) return runs_leave(h, i);
+    if (inside) { c.run_off = res[i].ops_off; c.n_runs = res[i].n_runs; }  // (a problem that is not done keeps the runs it names, if it names any)
+    if (!c.skip)
+      for (uint32_t r = 1; r + 1 < c.n_runs; ++r) c.n_gaps += WFM_RUN_OP(runs[c.run_off + r]) >= 2u;
+    c.out_off = out_total; c.gap_off = gap_total;
+    out_total += (uint64_t)c.n_runs + c.n_gaps;
+    gap_total += c.n_gaps;
+  }
+  // one block: [runs | rot | dval] one word per run, [out] one per output slot, [flags] one per problem, [long list] one per gap, the counter;
+  // then the gap records, the problems and the results (8-byte aligned each)
+  const size_t nr = n_runs_total;
+  uint32_t *d_runs, *d_rot, *d_dval, *d_out, *d_flags, *d_count;
+  LaGap* d_gaps;
+  LaProb* d_probs;
+  wfm_leftalign_t* d_stats;
+  Carver cv{h->scratch, "left-align"};
+  cv.piece(&d_runs, nr); cv.piece(&d_rot, nr); cv.piece(&d_dval, nr); cv.piece(&d_out, out_total); cv.piece(&d_flags, n);
+  cv.piece(&d_count, gap_total + 2);  // (the counter's 8 bytes, then the long list)
+  cv.piece(&d_gaps, gap_total); cv.piece(&d_probs, n); cv.piece(&d_stats, n);
+  if (int rc = cv.commit(h)) return rc;
+  uint32_t* d_long = d_count + 2;
+  if (nr) HIPCHK(h, hipMemcpyAsync(d_runs, runs, nr * 4, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(d_probs, probs.data(), n * sizeof(LaProb), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemsetAsync(d_count, 0, 8, h->stream));
+  if (gap_total) HIPCHK(h, hipMemsetAsync(d_gaps, 0xff, gap_total * sizeof(LaGap), h->stream));  // (a record nobody writes names no problem)
+  PassTimer tm(h);
+  const uint32_t lane_max = (uint32_t)std::max(8, env_num("WFM_LA_LANE_MAX", 256));
+  HIPCHK(h, tm.begin());
+  launch_left_align(s->d_seq, d_runs, d_probs, (int)n, d_rot, d_dval, d_gaps, gap_total, d_flags, d_long, d_count, d_out, d_stats, lane_max, h->stream);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, tm.end());
+  std::vector<uint32_t> slots(out_total);
+  uint32_t n_long = 0;
+  if (out_total) HIPCHK(h, hipMemcpyAsync(slots.data(), d_out, out_total * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(out, d_stats, n * sizeof(wfm_leftalign_t), hipMemcpyDeviceToHost, h->stream));
+  if (tm.on) HIPCHK(h, hipMemcpyAsync(&n_long, d_count, 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  // the problems' runs end to end (a problem used at most n_runs + n_gaps of its slots)
+  uint64_t total = 0;
+  for (size_t i = 0; i < n; ++i) {
+    if (out[i].runs_out > probs[i].n_runs + probs[i].n_gaps) { h->err = "wfm_left_align_runs: a problem's runs outgrew their slots"; return WFM_E_HIP; }
+    total += out[i].runs_out;
+  }
+  uint32_t* packed = (uint32_t*)malloc(std::max<size_t>(total, 1) * 4);
+  if (!packed) { h->err = "out of host memory (left-align)"; return WFM_E_NOMEM; }
+  uint64_t pos = 0;
+  int spans = 0;
+  uint64_t moved = 0, bases = 0;
+  for (size_t i = 0; i < n; ++i) {
+    if (out[i].runs_out) memcpy(packed + pos, slots.data() + probs[i].out_off, (size_t)out[i].runs_out * 4);
+    res[i].ops_off = pos; res[i].n_runs = out[i].runs_out;
+    pos += out[i].runs_out;
+    spans += (out[i].flags & WFM_LA_SPANS) != 0;
+    moved += out[i].moved; bases += out[i].bases_moved;
+  }
+  *runs_out = packed;
+  if (n_runs_out_total) *n_runs_out_total = (size_t)total;
+  float ms = 0;
+  if (tm.event_ms(&ms))
+    fprintf(stderr, "[wfm] left-align: %zu problems, %zu runs, %llu gaps (%u to the wave kernel), %llu moved by %llu bases in %.3f ms\n", n, nr,
+            (unsigned long long)gap_total, n_long, (unsigned long long)moved, (unsigned long long)bases, ms);
+  return spans;
+}
+
+// ---- how the output blocks of wfm_cs_strings and wfm_call_variants reach the caller's buffer ----
+namespace {
+constexpr size_t CS_PIN_PIECE = (size_t)4 << 20;
+
+// the handle's two pinned pieces, allocated at first use; false: there are none, and a block goes down in one pageable copy
+bool cs_pin_pieces(wfm_handle_t* h) {
+  for (int k = 0; k < 2; ++k)
+    if (!h->cspin[k] && hipHostMalloc((void**)&h->cspin[k], CS_PIN_PIECE, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); h->cspin[k] = nullptr; return false; }
+  return true;
+}
+
+// bytes of the device block src to dst, finished on return.  Down in pieces through the two pinned buffers: piece j + 1 crosses PCIe while
+// piece j is copied to its place (one pageable hipMemcpy of a fresh block took 2 ms for 3.7 MB, and 18 - 28 ms every other call:
+// profiles/cs_tag.md)
+hipError_t cs_copy_down(wfm_handle_t* h, bool pinned, char* dst, const uint8_t* src, size_t bytes) {
+  if (bytes == 0) return hipSuccess;
+  hipError_t e = hipSuccess;
+  const size_t pieces = pinned ? (bytes + CS_PIN_PIECE - 1) / CS_PIN_PIECE : 0;
+  auto piece_len = [&](size_t j) { return std::min<size_t>(CS_PIN_PIECE, bytes - j * CS_PIN_PIECE); };
+  if (!pinned) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream);
+  if (pinned) e = hipMemcpyAsync(h->cspin[0], src, piece_len(0), hipMemcpyDeviceToHost, h->stream);
+  for (size_t j = 0; j < pieces && e == hipSuccess; ++j) {
+    e = hipStreamSynchronize(h->stream);
+    if (e == hipSuccess && j + 1 < pieces)
+      e = hipMemcpyAsync(h->cspin[(j + 1) & 1], src + (j + 1) * CS_PIN_PIECE, piece_len(j + 1), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) memcpy(dst + j * CS_PIN_PIECE, h->cspin[j & 1], piece_len(j));
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  return e;
+}
+}  // namespace
+
+namespace {
+// the problems as wfa_cs.hip and wfa_variants.hip see them; the run ranges are validated here, before anything is launched.  The run records
+// lie in problem order whatever order the runs come in
+int cs_problems(wfm_handle_t* h, const wfm_seqset_t* s, const wfm_result_t* res, size_t n_runs_total, std::vector<CsProb>& probs, uint64_t* rec_total) {
+  const size_t n = s->meta.size();
+  probs.resize(n);
+  for (size_t i = 0; i < n; ++i) {
+    CsProb& c = probs[i];
+    memset(&c, 0, sizeof(c));
+    fill_prob(c, s->meta[i], res[i], true);
+    if (c.skip) continue;
+    if (!runs_inside(res[i].ops_off, res[i].n_runs, n_runs_total)) return runs_leave(h, i);
+    c.run_off = res[i].ops_off; c.n_runs = res[i].n_runs;
+    c.rec_off = *rec_total;
+    *rec_total += c.n_runs;
+  }
+  return WFM_OK;
+}
+}  // namespace
+
+// ---- the cs difference string of every problem's runs (wfmash_hip.h; the kernels: wfa_cs.hip) ----
+int wfm_cs_strings(wfm_handle_t* h, const wfm_seqset_t* s, const wfm_result_t* res, const uint32_t* runs, size_t n_runs_total, int form, char** out,
+                   size_t* out_bytes, wfm_cs_t* per) {
+  if (!h || !s || !out || !out_bytes || (n_runs_total && !runs)) return WFM_E_ARG;
+  *out = nullptr;
+  *out_bytes = 0;
+  PassTimer tm(h);
+  if (form != WFM_CS_SHORT && form != WFM_CS_LONG) { h->err = "wfm_cs_strings: form " + std::to_string(form) + " is neither WFM_CS_SHORT nor WFM_CS_LONG"; return WFM_E_ARG; }
+  const size_t n = s->meta.size();
+  if (n == 0) return WFM_OK;
+  if (!res || !per) return WFM_E_ARG;
+  if (n > (size_t)INT32_MAX || n_runs_total > ((size_t)1 << 31)) { h->err = "wfm_cs_strings: too many problems or runs for one call"; return WFM_E_ARG; }
+  HIPCHK(h, hipSetDevice(h->device));
+  std::vector<CsProb> probs;
+  uint64_t rec_total = 0;
+  if (int rc = cs_problems(h, s, res, n_runs_total, probs, &rec_total)) return rc;
+  // one block: [records] 16 bytes per run, [offsets] n + 1 and [totals] n of 8 bytes, [problems], [runs], [flags]
+  const size_t nr = n_runs_total;
+  uint4* d_recs;
+  unsigned long long *d_goff, *d_tot;
+  CsProb* d_probs;
+  uint32_t *d_runs, *d_flags;
+  Carver cv{h->scratch, "cs"};
+  cv.piece(&d_recs, (size_t)rec_total); cv.piece(&d_goff, n + 1); cv.piece(&d_tot, n); cv.piece(&d_probs, n); cv.piece(&d_runs, nr); cv.piece(&d_flags, n);
+  if (int rc = cv.commit(h)) return rc;
+  if (nr) HIPCHK(h, hipMemcpyAsync(d_runs, runs, nr * 4, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(d_probs, probs.data(), n * sizeof(CsProb), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, tm.begin());
+  launch_cs_index(d_runs, d_probs, (int)n, form, d_recs, d_tot, d_flags, h->stream);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, tm.end());
+  // the problems' totals, once: the host sizes the output and takes their prefix sum
+  std::vector<unsigned long long> goff(n + 1);
+  std::vector<uint32_t> flags(n);
+  HIPCHK(h, hipMemcpyAsync(goff.data() + 1, d_tot, n * 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(flags.data(), d_flags, n * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  float ms_index = 0, ms_write = 0, ms = 0;
+  (void)tm.event_ms(&ms_index);
+  goff[0] = 0;
+  int spans = 0;
+  for (size_t i = 0; i < n; ++i) {
+    per[i].flags = flags[i]; per[i].n_runs = probs[i].n_runs;
+    per[i].off = goff[i]; per[i].len = goff[i + 1];
+    goff[i + 1] += goff[i];
+    spans += (flags[i] & WFM_CS_SPANS) != 0;
+  }
+  const unsigned long long total = goff[n];
+  if (total == 0) return spans;
+  HIPCHK(h, hipMemcpyAsync(d_goff, goff.data(), (n + 1) * 8, hipMemcpyHostToDevice, h->stream));
+  char* host = (char*)malloc((size_t)total);
+  if (!host) { (void)hipStreamSynchronize(h->stream); h->err = "out of host memory (cs)"; return WFM_E_NOMEM; }
+  // chunks of problems whose strings fit the output block (a problem larger than that is a chunk of its own)
+  const unsigned long long cap = (unsigned long long)std::max(1, env_num("WFM_CS_OUT_MB", 256)) << 20;
+  const bool pinned = cs_pin_pieces(h);
+  size_t chunks = 0;
+  for (size_t ka = 0, kb; ka < n; ka = kb) {
+    kb = chunk_end(ka, goff, cap);
+    const unsigned long long bytes = goff[kb] - goff[ka];
+    if (bytes == 0) continue;
+    const size_t block = (size_t)((bytes + WFM_CS_SLICE - 1) / WFM_CS_SLICE) * WFM_CS_SLICE;
+    int rc = WFM_OK;
+    if (h->outblk.ensure(block / 8)) { h->err = "out of device memory (cs output)"; rc = WFM_E_NOMEM; }
+    if (rc == WFM_OK) {
+      (void)tm.begin();
+      launch_cs_write(s->d_seq, d_probs, d_recs, d_goff, (uint32_t)ka, (uint32_t)kb, bytes, form, (uint8_t*)h->outblk.p, h->stream);
+      hipError_t e = hipGetLastError();
+      (void)tm.end();
+      if (e == hipSuccess) e = cs_copy_down(h, pinned, host + goff[ka], (const uint8_t*)h->outblk.p, (size_t)bytes);  // (the block is the next chunk's)
+      if (e != hipSuccess) { h->err = std::string("wfm_cs_strings: ") + hipGetErrorString(e); rc = WFM_E_HIP; }
+    }
+    if (rc != WFM_OK) { free(host); return rc; }
+    if (tm.event_ms(&ms)) ms_write += ms;
+    ++chunks;
+  }
+  *out = host;
+  *out_bytes = (size_t)total;
+  if (tm.on)
+    fprintf(stderr, "[wfm] cs (%s): %zu problems, %zu runs, %llu bytes in %zu chunks, index %.3f ms, write %.3f ms (device events), the call %.3f ms (host clock)\n",
+            form == WFM_CS_LONG ? "long" : "short", n, (size_t)rec_total, total, chunks, ms_index, ms_write, tm.host_ms());
+  return spans;
+}
+
+void wfm_free_cs(char* p) { free(p); }
+
+// ---- the variants of every problem's runs (wfmash_hip.h; the kernels: wfa_variants.hip) ----
+int wfm_call_variants(wfm_handle_t* h, const wfm_seqset_t* s, const wfm_result_t* res, const uint32_t* runs, size_t n_runs_total, wfm_variant_t** vars,
+                      size_t* n_vars, char** alleles, size_t* allele_bytes, wfm_varcall_t* per) {
+  if (!h || !s || !vars || !n_vars || !alleles || !allele_bytes || (n_runs_total && !runs)) return WFM_E_ARG;
+  *vars = nullptr; *alleles = nullptr;
+  *n_vars = 0; *allele_bytes = 0;
+  PassTimer tm(h);
+  const size_t n = s->meta.size();
+  if (n == 0) return WFM_OK;
+  if (!res || !per) return WFM_E_ARG;
+  if (n > (size_t)INT32_MAX || n_runs_total > ((size_t)1 << 31)) { h->err = "wfm_call_variants: too many problems or runs for one call"; return WFM_E_ARG; }
+  HIPCHK(h, hipSetDevice(h->device));
+  std::vector<CsProb> probs;
+  uint64_t rec_total = 0;
+  if (int rc = cs_problems(h, s, res, n_runs_total, probs, &rec_total)) return rc;
+  // one block: [run records] 16 bytes per run, [offsets of the alleles] and [of the records] n + 1 each, [totals of both] n each of 8 bytes,
+  // [problems], [runs], [record prefixes] one word per run, [flags], [end gaps]
+  const size_t nr = n_runs_total;
+  uint4* d_recs;
+  unsigned long long *d_goff, *d_voff, *d_totb, *d_totr;
+  CsProb* d_probs;
+  uint32_t *d_runs, *d_rpre, *d_flags, *d_ends;
+  Carver cv{h->scratch, "variants"};
+  cv.piece(&d_recs, (size_t)rec_total); cv.piece(&d_goff, n + 1); cv.piece(&d_voff, n + 1); cv.piece(&d_totb, n); cv.piece(&d_totr, n);
+  cv.piece(&d_probs, n); cv.piece(&d_runs, nr); cv.piece(&d_rpre, (size_t)rec_total); cv.piece(&d_flags, n); cv.piece(&d_ends, n);
+  if (int rc = cv.commit(h)) return rc;
+  if (nr) HIPCHK(h, hipMemcpyAsync(d_runs, runs, nr * 4, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(d_probs, probs.data(), n * sizeof(CsProb), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, tm.begin());
+  launch_var_index(d_runs, d_probs, (int)n, d_recs, d_rpre, d_totb, d_totr, d_ends, d_flags, h->stream);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, tm.end());
+  // the problems' totals, once: the host sizes the outputs and takes the two prefix sums
+  std::vector<unsigned long long> goff(n + 1), voff(n + 1);
+  std::vector<uint32_t> flags(n), ends(n);
+  HIPCHK(h, hipMemcpyAsync(goff.data() + 1, d_totb, n * 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(voff.data() + 1, d_totr, n * 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(flags.data(), d_flags, n * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(ends.data(), d_ends, n * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  float ms_index = 0, ms_write = 0, ms = 0;
+  (void)tm.event_ms(&ms_index);
+  goff[0] = 0; voff[0] = 0;
+  int spans = 0;
+  for (size_t i = 0; i < n; ++i) {
+    per[i].flags = flags[i]; per[i].n_runs = probs[i].n_runs;
+    per[i].first = voff[i]; per[i].count = voff[i + 1];
+    per[i].end_gaps = ends[i]; per[i].pad_ = 0;
+    goff[i + 1] += goff[i]; voff[i + 1] += voff[i];
+    spans += (flags[i] & WFM_VAR_SPANS) != 0;
+  }
+  const unsigned long long total = goff[n], total_vars = voff[n];
+  if (total == 0) return spans;  // (a record has allele bytes: no bytes, no records)
+  HIPCHK(h, hipMemcpyAsync(d_goff, goff.data(), (n + 1) * 8, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(d_voff, voff.data(), (n + 1) * 8, hipMemcpyHostToDevice, h->stream));
+  char* host = (char*)malloc((size_t)total);
+  wfm_variant_t* host_vars = (wfm_variant_t*)malloc((size_t)total_vars * sizeof(wfm_variant_t));
+  if (!host || !host_vars) { (void)hipStreamSynchronize(h->stream); free(host); free(host_vars); h->err = "out of host memory (variants)"; return WFM_E_NOMEM; }
+  // chunks of problems whose records and alleles fit the output block (a problem larger than that is a chunk of its own)
+  const unsigned long long cap = (unsigned long long)std::max(1, env_num("WFM_VAR_OUT_MB", 256)) << 20;
+  auto cost = [&](size_t ka, size_t kb) { return (goff[kb] - goff[ka]) + (voff[kb] - voff[ka]) * sizeof(wfm_variant_t); };
+  const bool pinned = cs_pin_pieces(h);
+  size_t chunks = 0;
+  for (size_t ka = 0, kb; ka < n; ka = kb) {
+    kb = chunk_end(ka, n, cap, cost);
+    const unsigned long long bytes = goff[kb] - goff[ka];
+    if (bytes == 0) continue;
+    // the block: the chunk's records, then its alleles in whole slices
+    const size_t rec_bytes = (size_t)(voff[kb] - voff[ka]) * sizeof(wfm_variant_t);
+    const size_t block = rec_bytes + (size_t)((bytes + WFM_VAR_SLICE - 1) / WFM_VAR_SLICE) * WFM_VAR_SLICE;
+    int rc = WFM_OK;
+    if (h->outblk.ensure(block / 8)) { h->err = "out of device memory (variants output)"; rc = WFM_E_NOMEM; }
+    if (rc == WFM_OK) {
+      uint8_t* d_vars = (uint8_t*)h->outblk.p;
+      uint8_t* d_all = d_vars + rec_bytes;
+      (void)tm.begin();
+      launch_var_write(s->d_seq, d_probs, d_recs, d_rpre, d_goff, d_voff, (uint32_t)ka, (uint32_t)kb, bytes, d_all, d_vars, h->stream);
+      hipError_t e = hipGetLastError();
+      (void)tm.end();
+      if (e == hipSuccess) e = cs_copy_down(h, pinned, (char*)(host_vars + voff[ka]), d_vars, rec_bytes);
+      if (e == hipSuccess) e = cs_copy_down(h, pinned, host + goff[ka], d_all, (size_t)bytes);  // (the block is the next chunk's)
+      if (e != hipSuccess) { h->err = std::string("wfm_call_variants: ") + hipGetErrorString(e); rc = WFM_E_HIP; }
+    }
+    if (rc != WFM_OK) { free(host); free(host_vars); return rc; }
+    if (tm.event_ms(&ms)) ms_write += ms;
+    ++chunks;
+  }
+  *vars = host_vars; *n_vars = (size_t)total_vars;
+  *alleles = host; *allele_bytes = (size_t)total;
+  if (tm.on)
+    fprintf(stderr, "[wfm] variants: %zu problems, %zu runs, %llu records, %llu allele bytes in %zu chunks, index %.3f ms, write %.3f ms (device events), the call %.3f ms (host clock)\n",
+            n, (size_t)rec_total, total_vars, total, chunks, ms_index, ms_write, tm.host_ms());
+  return spans;
+}
+
+void wfm_free_variants(wfm_variant_t* vars, char* alleles) { free(vars); free(alleles); }
+
+// ---- per-base depth of the target from the runs of many records (wfmash_hip.h; the kernels: wfa_coverage.hip) ----
+struct wfm_coverage {
+  int device = 0;
+  uint64_t n_bases = 0, ntiles = 0;
+  int32_t* d = nullptr;                      // the difference array: ntiles whole tiles, zero behind word n_bases
+  uint64_t* aux = nullptr;                   // one block for the four below
+  uint32_t* tile_cnt = nullptr;              // ntiles
+  unsigned long long* tile_off = nullptr;    // ntiles + 1
+  unsigned long long* tile_sums = nullptr;   // one per WFM_COV_SCAN_BLOCK tiles, + 1
+  unsigned long long* cells = nullptr;       // the depth carried from chunk to chunk, then the three totals
+  DevBuf<uint64_t> work;                     // a call's problems and runs, or a chunk's entries, intervals and block sums
+};
+
+extern "C++" {  // (a template among them)
+namespace {
+static_assert(sizeof(wfm_cov_prob_t) == 24 && sizeof(CovProb) == 24 && sizeof(wfm_cov_entry_t) == 16 && sizeof(wfm_cov_interval_t) == 16, "wfmash_hip.h states these sizes");
+
+int cov_usable(wfm_handle_t* h, const wfm_coverage_t* cov) { return DeviceGuard::usable(h, cov->device, "the coverage object"); }
+
+// every tile's offset in the compact list, on the device (cov->tile_off) and here
+int cov_tile_offsets(wfm_handle_t* h, wfm_coverage_t* cov, std::vector<unsigned long long>& off) {
+  launch_cov_tile_offsets(cov->d, cov->ntiles, cov->tile_cnt, cov->tile_sums, cov->tile_off, h->stream);
+  HIPCHK(h, hipGetLastError());
+  off.resize((size_t)cov->ntiles + 1);
+  HIPCHK(h, hipMemcpyAsync(off.data(), cov->tile_off, off.size() * 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return WFM_OK;
+}
+
+// The compact list in chunks of whole tiles that hold at most WFM_COV_OUT_MB MiB of entries: each chunk's entries are written to the head
+// of cov->work, which holds words_per_entry 8-byte words for every entry of the chunk and room for its block sums, and handed to
+// f(d_entries, first entry, entries, last chunk) -> WFM_*.
+template <class F>
+int cov_chunks(wfm_handle_t* h, wfm_coverage_t* cov, const std::vector<unsigned long long>& off, size_t words_per_entry, F f) {
+  const unsigned long long total = off.back();
+  const unsigned long long cap = cap_units("WFM_COV_OUT_MB", 16, WFM_COV_TILE);
+  for (size_t ta = 0, tb; ta < (size_t)cov->ntiles; ta = tb) {
+    tb = chunk_end(ta, off, cap);
+    const unsigned long long m = off[tb] - off[ta];
+    if (m == 0) continue;
+    if (cov->work.ensure((size_t)m * words_per_entry + (size_t)m / WFM_COV_SCAN_BLOCK + 8)) { h->err = "out of device memory (coverage list)"; return WFM_E_NOMEM; }
+    launch_cov_write(cov->d, cov->tile_off, ta, tb, off[ta], cov->work.p, h->stream);
+    HIPCHK(h, hipGetLastError());
+    const int rc = f((const uint8_t*)cov->work.p, off[ta], m, off[tb] == total);
+    if (rc != WFM_OK) return rc;
+  }
+  return WFM_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int wfm_coverage_create(wfm_handle_t* h, uint64_t n_bases, wfm_coverage_t** cov) {
+  if (!h || !cov) return WFM_E_ARG;
+  *cov = nullptr;
+  const double gib = env_decimal("WFM_COV_GB", 32.0), need = ((double)n_bases + 1.0) * 4.0 / 1073741824.0;
+  if (n_bases >= ((uint64_t)1 << 40) || need > gib) {
+    char msg[200];
+    snprintf(msg, sizeof msg, "wfm_coverage_create: the difference array of %llu target bases needs %.3f GiB, more than WFM_COV_GB = %.3f",
+             (unsigned long long)n_bases, need, gib);
+    h->err = msg;
+    return WFM_E_ARG;
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  std::unique_ptr<wfm_coverage> c(new wfm_coverage());
+  c->device = h->device;
+  c->n_bases = n_bases;
+  c->ntiles = (n_bases + 1 + WFM_COV_TILE - 1) / WFM_COV_TILE;
+  const size_t nsums = (size_t)(c->ntiles + WFM_COV_SCAN_BLOCK - 1) / WFM_COV_SCAN_BLOCK + 1;
+  const size_t w_cnt = ((size_t)c->ntiles * 4 + 7) / 8, w_off = (size_t)c->ntiles + 1;
+  if (wfm_dmalloc((void**)&c->d, (size_t)c->ntiles * WFM_COV_TILE * 4) != hipSuccess ||
+      wfm_dmalloc((void**)&c->aux, (w_cnt + w_off + nsums + 4) * 8) != hipSuccess) {
+    (void)hipGetLastError();
+    if (c->d) wfm_dfree(c->d);
+    h->err = "out of device memory (coverage)";
+    return WFM_E_NOMEM;
+  }
+  c->tile_cnt = (uint32_t*)c->aux;
+  c->tile_off = (unsigned long long*)(c->aux + w_cnt);
+  c->tile_sums = c->tile_off + w_off;
+  c->cells = c->tile_sums + nsums;
+  hipError_t e = hipMemsetAsync(c->d, 0, (size_t)c->ntiles * WFM_COV_TILE * 4, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e != hipSuccess) { wfm_dfree(c->d); wfm_dfree(c->aux); h->err = std::string("wfm_coverage_create: ") + hipGetErrorString(e); return WFM_E_HIP; }
+  *cov = c.release();
+  return WFM_OK;
+}
+
+void wfm_coverage_free(wfm_coverage_t* cov) {
+  if (!cov) return;
+  DeviceGuard on(cov->device);
+  cov->work.release();
+  if (cov->d) wfm_dfree(cov->d);
+  if (cov->aux) wfm_dfree(cov->aux);
+  delete cov;
+}
+
+int wfm_coverage_add(wfm_handle_t* h, wfm_coverage_t* cov, const wfm_cov_prob_t* probs, size_t n, const uint32_t* runs, size_t n_runs_total,
+                     uint32_t* flags_out) {
+  if (!h || !cov || (n && (!probs || !flags_out)) || (n_runs_total && !runs)) return WFM_E_ARG;
+  if (n == 0) return WFM_OK;
+  if (n > (size_t)INT32_MAX || n_runs_total > ((size_t)1 << 31)) { h->err = "wfm_coverage_add: too many problems or runs for one call"; return WFM_E_ARG; }
+  if (int rc = cov_usable(h, cov)) return rc;
+  if (int rc = all_runs_inside(h, probs, n, n_runs_total)) return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  CovProb* d_probs;
+  uint32_t *d_runs, *d_flags;
+  Carver cv{cov->work, "coverage add"};
+  cv.piece(&d_probs, n); cv.piece(&d_runs, n_runs_total); cv.piece(&d_flags, n);
+  if (int rc = cv.commit(h)) return rc;
+  HIPCHK(h, hipMemcpyAsync(d_probs, probs, n * sizeof(CovProb), hipMemcpyHostToDevice, h->stream));
+  if (n_runs_total) HIPCHK(h, hipMemcpyAsync(d_runs, runs, n_runs_total * 4, hipMemcpyHostToDevice, h->stream));
+  launch_cov_add(d_runs, d_probs, (int)n, cov->d, cov->n_bases, d_flags, h->stream);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipMemcpyAsync(flags_out, d_flags, n * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  int spans = 0;
+  for (size_t i = 0; i < n; ++i) spans += (flags_out[i] & WFM_COV_SPANS) != 0;
+  return spans;
+}
+
+int wfm_coverage_export(wfm_handle_t* h, wfm_coverage_t* cov, wfm_cov_entry_t** entries, size_t* n) {
+  if (!h || !cov || !entries || !n) return WFM_E_ARG;
+  *entries = nullptr; *n = 0;
+  if (int rc = cov_usable(h, cov)) return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  PassTimer tm(h);
+  std::vector<unsigned long long> off;
+  if (int rc = cov_tile_offsets(h, cov, off)) return rc;
+  const double ms_off = tm.lap();
+  const unsigned long long total = off.back();
+  if (total == 0) return WFM_OK;
+  char* host = (char*)malloc((size_t)total * sizeof(wfm_cov_entry_t));
+  if (!host) { h->err = "out of host memory (coverage list)"; return WFM_E_NOMEM; }
+  const bool pinned = cs_pin_pieces(h);
+  const int rc = cov_chunks(h, cov, off, 2, [&](const uint8_t* d_ent, unsigned long long first, unsigned long long m, bool) {
+    const hipError_t e = cs_copy_down(h, pinned, host + first * sizeof(wfm_cov_entry_t), d_ent, (size_t)m * sizeof(wfm_cov_entry_t));  // (the block is the next chunk's)
+    if (e != hipSuccess) { h->err = std::string("wfm_coverage_export: ") + hipGetErrorString(e); return (int)WFM_E_HIP; }
+    return (int)WFM_OK;
+  });
+  if (rc != WFM_OK) { free(host); return rc; }
+  *entries = (wfm_cov_entry_t*)host; *n = (size_t)total;
+  if (tm.on)
+    fprintf(stderr, "[wfm] coverage export: %llu bases, %llu non-zero words, count + offsets %.3f ms, write + copy down %.3f ms (host clock, each ends in a synchronise)\n",
+            (unsigned long long)cov->n_bases, total, ms_off, tm.lap());
+  return WFM_OK;
+}
+
+int wfm_coverage_import(wfm_handle_t* h, wfm_coverage_t* cov, const wfm_cov_entry_t* entries, size_t n) {
+  if (!h || !cov || (n && !entries)) return WFM_E_ARG;
+  if (n == 0) return WFM_OK;
+  if (int rc = cov_usable(h, cov)) return rc;
+  for (size_t i = 0; i < n; ++i)
+    if (entries[i].pos > cov->n_bases) { h->err = "entry " + std::to_string(i) + ": its position lies beyond the object's bases"; return WFM_E_ARG; }
+  HIPCHK(h, hipSetDevice(h->device));
+  constexpr size_t PIECE = (size_t)4 << 20;  // entries: 64 MiB a piece
+  if (cov->work.ensure(std::min(n, PIECE) * 2)) { h->err = "out of device memory (coverage import)"; return WFM_E_NOMEM; }
+  for (size_t at = 0; at < n; at += PIECE) {
+    const size_t m = std::min(PIECE, n - at);
+    HIPCHK(h, hipMemcpyAsync(cov->work.p, entries + at, m * sizeof(wfm_cov_entry_t), hipMemcpyHostToDevice, h->stream));
+    launch_cov_import(cov->work.p, m, cov->d, h->stream);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));  // (the block is the next piece's)
+  }
+  return WFM_OK;
+}
+
+int wfm_coverage_intervals(wfm_handle_t* h, wfm_coverage_t* cov, wfm_cov_interval_t** iv, size_t* n, uint64_t totals[3]) {
+  if (!h || !cov || !iv || !n) return WFM_E_ARG;
+  *iv = nullptr; *n = 0;
+  if (totals) totals[0] = totals[1] = totals[2] = 0;
+  if (int rc = cov_usable(h, cov)) return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  PassTimer tm(h);
+  std::vector<unsigned long long> off;
+  if (int rc = cov_tile_offsets(h, cov, off)) return rc;
+  const double ms_off = tm.lap();
+  const unsigned long long total = off.back();
+  // (slot 0 is kept for the interval that begins at 0 where the first non-zero word lies further on)
+  wfm_cov_interval_t* host = (wfm_cov_interval_t*)malloc(((size_t)total + 1) * sizeof(wfm_cov_interval_t));
+  if (!host) { h->err = "out of host memory (coverage intervals)"; return WFM_E_NOMEM; }
+  host[0].start = 0; host[0].depth = 0; host[0].pad_ = 0;
+  hipError_t e0 = hipMemsetAsync(cov->cells, 0, 4 * 8, h->stream);
+  if (e0 != hipSuccess) { free(host); h->err = std::string("wfm_coverage_intervals: ") + hipGetErrorString(e0); return WFM_E_HIP; }
+  const bool pinned = cs_pin_pieces(h);
+  unsigned long long prev_pos = 0;
+  size_t chunks = 0;
+  int rc = cov_chunks(h, cov, off, 4, [&](const uint8_t* d_ent, unsigned long long first, unsigned long long m, bool last) {
+    uint8_t* d_iv = (uint8_t*)(cov->work.p + 2 * (size_t)m);
+    unsigned long long* d_sums = (unsigned long long*)(cov->work.p + 4 * (size_t)m);
+    launch_cov_intervals(d_ent, m, d_sums, cov->cells, prev_pos, cov->n_bases, last ? 1 : 0, d_iv, cov->cells + 1, h->stream);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = cs_copy_down(h, pinned, (char*)(host + 1 + first), d_iv, (size_t)m * sizeof(wfm_cov_interval_t));
+    if (e != hipSuccess) { h->err = std::string("wfm_coverage_intervals: ") + hipGetErrorString(e); return (int)WFM_E_HIP; }
+    prev_pos = host[first + m].start;
+    ++chunks;
+    return (int)WFM_OK;
+  });
+  unsigned long long tot[3] = {0, 0, 0};
+  if (rc == WFM_OK) {
+    hipError_t e = hipMemcpyAsync(tot, cov->cells + 1, sizeof tot, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) { h->err = std::string("wfm_coverage_intervals: ") + hipGetErrorString(e); rc = WFM_E_HIP; }
+  }
+  if (rc != WFM_OK) { free(host); return rc; }
+  // the word at n_bases starts no interval; the interval from 0 is there already where word 0 is non-zero
+  size_t count = (size_t)total;
+  if (count && host[count].start >= cov->n_bases) --count;
+  const bool lead = count == 0 || host[1].start != 0;
+  if (!lead) memmove(host, host + 1, count * sizeof(wfm_cov_interval_t));
+  *iv = host; *n = count + (lead ? 1 : 0);
+  if (totals) { totals[0] = tot[0]; totals[1] = tot[1]; totals[2] = tot[2]; }
+  if (tm.on)
+    fprintf(stderr, "[wfm] coverage intervals: %llu bases, %llu non-zero words in %zu chunks, %zu intervals, count + offsets %.3f ms, write + scan + copy down %.3f ms (host clock, each ends in a synchronise)\n",
+            (unsigned long long)cov->n_bases, total, chunks, *n, ms_off, tm.lap());
+  return WFM_OK;
+}
+
+void wfm_coverage_free_list(void* p) { free(p); }
+
+// ---- target intervals lifted through the runs of many records (wfmash_hip.h; the kernels: wfa_lift.hip) ----
+struct wfm_liftset {
+  int device = 0;
+  uint64_t n = 0, n_bases = 0;
+  uint64_t* iv = nullptr;               // one block: n intervals {start, end}, then pm (n), then the blocks' maxima
+  unsigned long long* pm = nullptr;
+  mutable DevBuf<uint64_t> work;        // a call's prefix words, problems, windows, offsets and runs
+  mutable DevBuf<uint64_t> out;         // a chunk's lifts
+};
+
+static_assert(sizeof(wfm_lift_iv_t) == 16 && sizeof(wfm_lift_t) == 32 && sizeof(wfm_liftcall_t) == 24 && sizeof(LiftProb) == 32 && sizeof(LiftWin) == 32,
+              "wfmash_hip.h and wfa_device.h state these sizes");
+
+int wfm_liftset_create(wfm_handle_t* h, const wfm_lift_iv_t* iv, size_t n, uint64_t n_bases, wfm_liftset_t** out) {
+  if (!h || !out || (n && !iv)) return WFM_E_ARG;
+  *out = nullptr;
+  if (n >= ((size_t)1 << 32)) { h->err = "wfm_liftset_create: too many intervals for one set"; return WFM_E_ARG; }
+  for (size_t i = 0; i < n; ++i) {
+    if (!(iv[i].start < iv[i].end && iv[i].end <= n_bases)) {
+      h->err = "wfm_liftset_create: interval " + std::to_string(i) + " is empty or ends beyond the " + std::to_string(n_bases) + " target bases";
+      return WFM_E_ARG;
+    }
+    if (i && (iv[i].start < iv[i - 1].start || (iv[i].start == iv[i - 1].start && iv[i].end < iv[i - 1].end))) {
+      h->err = "wfm_liftset_create: interval " + std::to_string(i) + " lies before its predecessor: the intervals must be sorted by (start, end)";
+      return WFM_E_ARG;
+    }
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  std::unique_ptr<wfm_liftset> s(new wfm_liftset());
+  s->device = h->device;
+  s->n = n;
+  s->n_bases = n_bases;
+  if (n) {
+    const size_t nb = (n + WFM_LIFT_SCAN_BLOCK - 1) / WFM_LIFT_SCAN_BLOCK;
+    if (wfm_dmalloc((void**)&s->iv, (n * 3 + nb + 2) * 8) != hipSuccess) { (void)hipGetLastError(); h->err = "out of device memory (liftset)"; return WFM_E_NOMEM; }
+    s->pm = (unsigned long long*)(s->iv + n * 2);
+    hipError_t e = hipMemcpyAsync(s->iv, iv, n * sizeof(wfm_lift_iv_t), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) { launch_lift_pm(s->iv, n, s->pm + n, s->pm, h->stream); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) { wfm_dfree(s->iv); h->err = std::string("wfm_liftset_create: ") + hipGetErrorString(e); return WFM_E_HIP; }
+  }
+  *out = s.release();
+  return WFM_OK;
+}
+
+void wfm_liftset_free(wfm_liftset_t* s) {
+  if (!s) return;
+  DeviceGuard on(s->device);
+  s->work.release();
+  s->out.release();
+  if (s->iv) wfm_dfree(s->iv);
+  delete s;
+}
+
+int wfm_lift_runs(wfm_handle_t* h, const wfm_liftset_t* s, const wfm_cov_prob_t* probs, size_t n, const uint32_t* runs, size_t n_runs_total,
+                  wfm_lift_t** lifts, size_t* n_lifts, wfm_liftcall_t* per) {
+  if (!h || !s || !lifts || !n_lifts || (n && (!probs || !per)) || (n_runs_total && !runs)) return WFM_E_ARG;
+  *lifts = nullptr; *n_lifts = 0;
+  if (n == 0) return WFM_OK;
+  if (n > (size_t)INT32_MAX || n_runs_total > ((size_t)1 << 31)) { h->err = "wfm_lift_runs: too many problems or runs for one call"; return WFM_E_ARG; }
+  if (int rc = DeviceGuard::usable(h, s->device, "the liftset")) return rc;
+  if (int rc = all_runs_inside(h, probs, n, n_runs_total)) return rc;
+  std::vector<LiftProb> lp(n);
+  uint64_t n_pre = 0;
+  for (size_t i = 0; i < n; ++i) {
+    lp[i] = LiftProb{probs[i].base, probs[i].runs_off, n_pre, probs[i].n_runs, 0u};
+    n_pre += (uint64_t)probs[i].n_runs + 1;
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  PassTimer tm(h);
+  // (the prefix words come first: they are read 16 bytes at a time)
+  uint4* d_pre;
+  LiftProb* d_probs;
+  LiftWin* d_win;
+  unsigned long long* d_off;
+  uint32_t* d_runs;
+  Carver cv{s->work, "lift"};
+  cv.piece(&d_pre, (size_t)n_pre); cv.piece(&d_probs, n); cv.piece(&d_win, n); cv.piece(&d_off, n + 1); cv.piece(&d_runs, n_runs_total);
+  if (int rc = cv.commit(h)) return rc;
+  HIPCHK(h, hipMemcpyAsync(d_probs, lp.data(), n * sizeof(LiftProb), hipMemcpyHostToDevice, h->stream));
+  if (n_runs_total) HIPCHK(h, hipMemcpyAsync(d_runs, runs, n_runs_total * 4, hipMemcpyHostToDevice, h->stream));
+  launch_lift_index(d_runs, d_probs, (int)n, s->iv, s->pm, s->n, s->n_bases, d_pre, d_win, d_off, h->stream);
+  HIPCHK(h, hipGetLastError());
+  std::vector<LiftWin> win(n);
+  std::vector<unsigned long long> off(n + 1);
+  HIPCHK(h, hipMemcpyAsync(win.data(), d_win, n * sizeof(LiftWin), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(off.data(), d_off, (n + 1) * 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  const double ms_index = tm.lap();
+  for (size_t i = 0; i < n; ++i) per[i] = wfm_liftcall_t{win[i].flags, probs[i].n_runs, off[i], win[i].count};
+  const unsigned long long total = off[n];
+  if (total == 0) return WFM_OK;
+  // chunks of whole problems that hold at most WFM_LIFT_OUT_MB MiB of lifts; a single problem may exceed that alone
+  const unsigned long long cap = cap_units("WFM_LIFT_OUT_MB", sizeof(wfm_lift_t), 1);
+  std::vector<std::pair<size_t, size_t>> chunks;
+  unsigned long long widest = 0;
+  for (size_t ka = 0, kb; ka < n; ka = kb) {
+    kb = chunk_end(ka, off, cap);
+    if (off[kb] > off[ka]) { chunks.emplace_back(ka, kb); widest = std::max(widest, off[kb] - off[ka]); }
+  }
+  char* host = (char*)malloc((size_t)total * sizeof(wfm_lift_t));
+  if (!host) { h->err = "out of host memory (lifts)"; return WFM_E_NOMEM; }
+  if (s->out.ensure((size_t)widest * 4)) { free(host); h->err = "out of device memory (lifts)"; return WFM_E_NOMEM; }
+  uint8_t* d_out = (uint8_t*)s->out.p;
+  const bool pinned = cs_pin_pieces(h);
+  for (const auto& c : chunks) {
+    launch_lift_write(d_runs, d_probs, s->iv, d_pre, d_win, d_off, (uint32_t)c.first, (uint32_t)c.second, d_out, h->stream);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = cs_copy_down(h, pinned, host + off[c.first] * sizeof(wfm_lift_t), d_out, (size_t)(off[c.second] - off[c.first]) * sizeof(wfm_lift_t));  // (the block is the next chunk's)
+    if (e != hipSuccess) { free(host); h->err = std::string("wfm_lift_runs: ") + hipGetErrorString(e); return WFM_E_HIP; }
+  }
+  *lifts = (wfm_lift_t*)host; *n_lifts = (size_t)total;
+  if (tm.on)
+    fprintf(stderr, "[wfm] lift: %zu problems, %zu runs, %llu intervals, %llu lifts in %zu chunks, upload + index + count %.3f ms, write + copy down %.3f ms (host clock, each ends in a synchronise)\n",
+            n, n_runs_total, (unsigned long long)s->n, total, chunks.size(), ms_index, tm.lap());
+  return WFM_OK;
+}
+
+void wfm_free_lifts(wfm_lift_t* p) { free(p); }
+
+// ---- presence of target intervals per group of records (wfmash_hip.h; the kernels and the sort: wfa_pav.hip) ----
+struct wfm_pav {
+  int device = 0;
+  uint64_t n_bases = 0;
+  uint32_t n_groups = 0;
+  unsigned long long* list = nullptr;    // one block: the start keys [0, cap), then the end keys [cap, 2 cap)
+  size_t cap = 0, n = 0, n_union = 0;    // segments the block holds; segments in it; the first n_union of them are the last union's
+  bool clean = false;                    // the list is a union and C its prefix
+  DevBuf<uint64_t> c;                    // C: n_union + 1
+  DevBuf<uint64_t> work;                 // a call's problems, runs, flags, counts and offsets; the sorted copy and the block words; a chunk of rows
+  DevBuf<uint64_t> tmp;                  // the sort's own
+  uint64_t added = 0, unions = 0;
+  unsigned long long* ks() const { return list; }
+  unsigned long long* ke() const { return list + cap; }
+};
+
+extern "C++" {
+namespace {
+static_assert(sizeof(wfm_pav_prob_t) == 24 && sizeof(PavProb) == 24 && sizeof(wfm_pav_seg_t) == 16, "wfmash_hip.h states these sizes");
+constexpr unsigned PAV_SHIFT = 40;
+constexpr size_t PAV_MAX_SEGS = (size_t)1 << 31;
+
+int pav_usable(wfm_handle_t* h, const wfm_pav_t* pav) { return DeviceGuard::usable(h, pav->device, "the pav object"); }
+
+// room for `need` segments; what the list holds moves with it.  The block that is outgrown goes to the block cache, not to the driver.
+int pav_reserve(wfm_handle_t* h, wfm_pav_t* pav, size_t need) {
+  if (need <= pav->cap) return WFM_OK;
+  if (need > PAV_MAX_SEGS) { h->err = "wfm_pav: more than 2^31 segments in one object; lower WFM_PAV_MB so that the union is taken sooner"; return WFM_E_NOMEM; }
+  const size_t cap = std::max<size_t>(need + need / 2, 4096);
+  unsigned long long* blk = nullptr;
+  if (wfm_dmalloc((void**)&blk, cap * 16) != hipSuccess) { (void)hipGetLastError(); h->err = "out of device memory (pav segments)"; return WFM_E_NOMEM; }
+  if (pav->n) {
+    hipError_t e = hipMemcpyAsync(blk, pav->ks(), pav->n * 8, hipMemcpyDeviceToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(blk + cap, pav->ke(), pav->n * 8, hipMemcpyDeviceToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) { wfm_dfree(blk); h->err = std::string("wfm_pav: ") + hipGetErrorString(e); return WFM_E_HIP; }
+  }
+  if (pav->list) wfm_dfree(pav->list);
+  pav->list = blk;
+  pav->cap = cap;
+  return WFM_OK;
+}
+
+// the union where the raw part of the list has outgrown WFM_PAV_MB MiB
+int pav_maybe_union(wfm_handle_t* h, wfm_pav_t* pav) {
+  const double limit = std::max(0.0, env_decimal("WFM_PAV_MB", 256.0)) * 1048576.0;
+  if (pav->n > pav->n_union && (double)(pav->n - pav->n_union) * 16.0 > limit) return wfm_pav_union(h, pav);
+  return WFM_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int wfm_pav_create(wfm_handle_t* h, uint64_t n_bases, uint32_t n_groups, wfm_pav_t** pav) {
+  if (!h || !pav) return WFM_E_ARG;
+  *pav = nullptr;
+  if (n_bases >= ((uint64_t)1 << PAV_SHIFT) || n_groups >= (1u << 24)) {
+    h->err = "wfm_pav_create: " + std::to_string(n_bases) + " target bases and " + std::to_string(n_groups) +
+             " groups do not fit a segment's key, group << 40 | start: fewer than 2^40 bases and 2^24 groups";
+    return WFM_E_ARG;
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  std::unique_ptr<wfm_pav> p(new wfm_pav());
+  p->device = h->device;
+  p->n_bases = n_bases;
+  p->n_groups = n_groups;
+  p->clean = true;  // (the empty union)
+  *pav = p.release();
+  return WFM_OK;
+}
+
+void wfm_pav_free(wfm_pav_t* pav) {
+  if (!pav) return;
+  DeviceGuard on(pav->device);
+  pav->c.release();
+  pav->work.release();
+  pav->tmp.release();
+  if (pav->list) wfm_dfree(pav->list);
+  delete pav;
+}
+
+int wfm_pav_add(wfm_handle_t* h, wfm_pav_t* pav, const wfm_pav_prob_t* probs, size_t n, const uint32_t* runs, size_t n_runs_total, uint32_t* flags_out) {
+  if (!h || !pav || (n && (!probs || !flags_out)) || (n_runs_total && !runs)) return WFM_E_ARG;
+  if (n == 0) return WFM_OK;
+  if (n > (size_t)INT32_MAX || n_runs_total > ((size_t)1 << 31)) { h->err = "wfm_pav_add: too many problems or runs for one call"; return WFM_E_ARG; }
+  if (int rc = pav_usable(h, pav)) return rc;
+  if (int rc = all_runs_inside(h, probs, n, n_runs_total)) return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  PassTimer tm(h);
+  PavProb* d_probs;
+  uint32_t *d_runs, *d_flags;
+  unsigned long long *d_cnt, *d_off;
+  Carver cv{pav->work, "pav add"};
+  cv.piece(&d_probs, n); cv.piece(&d_runs, n_runs_total); cv.piece(&d_flags, n); cv.piece(&d_cnt, n); cv.piece(&d_off, n + 1);
+  if (int rc = cv.commit(h)) return rc;
+  HIPCHK(h, hipMemcpyAsync(d_probs, probs, n * sizeof(PavProb), hipMemcpyHostToDevice, h->stream));
+  if (n_runs_total) HIPCHK(h, hipMemcpyAsync(d_runs, runs, n_runs_total * 4, hipMemcpyHostToDevice, h->stream));
+  launch_pav_count(d_runs, d_probs, (int)n, pav->n_bases, pav->n_groups, d_flags, d_cnt, d_off, h->stream);
+  HIPCHK(h, hipGetLastError());
+  unsigned long long total = 0;
+  HIPCHK(h, hipMemcpyAsync(flags_out, d_flags, n * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(&total, d_off + n, 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  int spans = 0;
+  for (size_t i = 0; i < n; ++i) spans += (flags_out[i] & WFM_PAV_SPANS) != 0;
+  if (total) {
+    if (int rc = pav_reserve(h, pav, pav->n + (size_t)total)) return rc;
+    launch_pav_write(d_runs, d_probs, (int)n, d_flags, d_off, pav->ks() + pav->n, pav->ke() + pav->n, h->stream);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    pav->n += (size_t)total;
+    pav->added += total;
+    pav->clean = false;
+  }
+  if (tm.on)
+    fprintf(stderr, "[wfm] pav add: %zu problems, %zu runs, %llu segments, %d flagged, %.3f ms (host clock, ends in a synchronise); the list holds %zu\n",
+            n, n_runs_total, total, spans, tm.host_ms(), pav->n);
+  if (int rc = pav_maybe_union(h, pav)) return rc;
+  return spans;
+}
+
+int wfm_pav_union(wfm_handle_t* h, wfm_pav_t* pav) {
+  if (!h || !pav) return WFM_E_ARG;
+  if (int rc = pav_usable(h, pav)) return rc;
+  if (pav->clean) return WFM_OK;  // (nothing was added since the last one)
+  HIPCHK(h, hipSetDevice(h->device));
+  PassTimer tm(h);
+  const size_t n = pav->n, nb = (n + WFM_PAV_SCAN_BLOCK - 1) / WFM_PAV_SCAN_BLOCK;
+  // the sorted copy: start keys, end keys, then the blocks' words
+  unsigned long long *ks2, *ke2, *aux;
+  Carver cv{pav->work, "pav union"};
+  cv.piece(&ks2, n); cv.piece(&ke2, n); cv.piece(&aux, nb + 1);
+  if (int rc = cv.commit(h)) return rc;
+  unsigned end_bit = PAV_SHIFT;
+  while (end_bit < 64 && ((uint64_t)pav->n_groups >> (end_bit - PAV_SHIFT)) != 0) ++end_bit;  // (keys are below n_groups << 40)
+  size_t tmp_bytes = 0;
+  HIPCHK(h, pav_sort(nullptr, &tmp_bytes, pav->ks(), ks2, pav->ke(), ke2, n, end_bit, h->stream));
+  if (pav->tmp.ensure(tmp_bytes / 8 + 2)) { h->err = "out of device memory (pav sort)"; return WFM_E_NOMEM; }
+  HIPCHK(h, pav_sort(pav->tmp.p, &tmp_bytes, pav->ks(), ks2, pav->ke(), ke2, n, end_bit, h->stream));
+  launch_pav_runmax(ke2, n, aux, h->stream);
+  HIPCHK(h, hipGetLastError());
+  // (a union has no more intervals than the list has segments: the block holds it)
+  launch_pav_compact(ks2, ke2, n, aux, pav->ks(), pav->ke(), h->stream);
+  HIPCHK(h, hipGetLastError());
+  unsigned long long m = 0;
+  HIPCHK(h, hipMemcpyAsync(&m, aux + nb, 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (m > n) { h->err = "wfm_pav_union: the union has more intervals than the list had segments"; return WFM_E_HIP; }
+  if (pav->c.ensure((size_t)m + 2)) { h->err = "out of device memory (pav prefix)"; return WFM_E_NOMEM; }
+  launch_pav_prefix(pav->ks(), pav->ke(), m, aux, (unsigned long long*)pav->c.p, h->stream);
+  HIPCHK(h, hipGetLastError());
+  if (m == 0) HIPCHK(h, hipMemsetAsync(pav->c.p, 0, 8, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  pav->n = pav->n_union = (size_t)m;
+  pav->clean = true;
+  pav->unions += 1;
+  if (tm.on)
+    fprintf(stderr, "[wfm] pav union: %zu segments to %llu intervals in %.3f ms (host clock, ends in a synchronise); device bytes: the list's block %zu, the sorted copy and block words %zu, the sort's own %zu, the prefix %zu\n",
+            n, m, tm.host_ms(), pav->cap * 16, pav->work.cap * 8, pav->tmp.cap * 8,
+            pav->c.cap * 8);
+  return WFM_OK;
+}
+
+int wfm_pav_export(wfm_handle_t* h, wfm_pav_t* pav, wfm_pav_seg_t** segs, size_t* n) {
+  if (!h || !pav || !segs || !n) return WFM_E_ARG;
+  *segs = nullptr; *n = 0;
+  if (int rc = wfm_pav_union(h, pav)) return rc;
+  const size_t m = pav->n;
+  if (m == 0) return WFM_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  std::vector<unsigned long long> keys(2 * m);
+  const bool pinned = cs_pin_pieces(h);
+  hipError_t e = cs_copy_down(h, pinned, (char*)keys.data(), (const uint8_t*)pav->ks(), m * 8);
+  if (e == hipSuccess) e = cs_copy_down(h, pinned, (char*)(keys.data() + m), (const uint8_t*)pav->ke(), m * 8);
+  if (e != hipSuccess) { h->err = std::string("wfm_pav_export: ") + hipGetErrorString(e); return WFM_E_HIP; }
+  // a union interval of 2^32 bases or more comes as abutting pieces
+  const uint64_t mask = ((uint64_t)1 << PAV_SHIFT) - 1, piece = 0x80000000ull;
+  size_t total = 0;
+  for (size_t i = 0; i < m; ++i) { const uint64_t len = keys[m + i] - keys[i]; total += len > 0xffffffffull ? (size_t)((len + piece - 1) / piece) : 1; }
+  wfm_pav_seg_t* out = (wfm_pav_seg_t*)malloc(total * sizeof(wfm_pav_seg_t));
+  if (!out) { h->err = "out of host memory (pav list)"; return WFM_E_NOMEM; }
+  size_t at = 0;
+  for (size_t i = 0; i < m; ++i) {
+    uint64_t s = keys[i] & mask, len = keys[m + i] - keys[i];
+    const uint32_t g = (uint32_t)(keys[i] >> PAV_SHIFT);
+    while (len > 0xffffffffull) { out[at++] = wfm_pav_seg_t{s, (uint32_t)piece, g}; s += piece; len -= piece; }
+    out[at++] = wfm_pav_seg_t{s, (uint32_t)len, g};
+  }
+  *segs = out; *n = at;
+  return WFM_OK;
+}
+
+int wfm_pav_import(wfm_handle_t* h, wfm_pav_t* pav, const wfm_pav_seg_t* segs, size_t n) {
+  if (!h || !pav || (n && !segs)) return WFM_E_ARG;
+  if (n == 0) return WFM_OK;
+  if (int rc = pav_usable(h, pav)) return rc;
+  std::vector<unsigned long long> keys(2 * n);
+  for (size_t i = 0; i < n; ++i) {
+    if (segs[i].length == 0 || segs[i].start > pav->n_bases || segs[i].length > pav->n_bases - segs[i].start || segs[i].group >= pav->n_groups) {
+      h->err = "wfm_pav_import: segment " + std::to_string(i) + " is empty, leaves the " + std::to_string(pav->n_bases) + " target bases or names a group that is not below " +
+               std::to_string(pav->n_groups);
+      return WFM_E_ARG;
+    }
+    keys[i] = ((uint64_t)segs[i].group << PAV_SHIFT) | segs[i].start;
+    keys[n + i] = keys[i] + segs[i].length;
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  if (int rc = pav_reserve(h, pav, pav->n + n)) return rc;
+  HIPCHK(h, hipMemcpyAsync(pav->ks() + pav->n, keys.data(), n * 8, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(pav->ke() + pav->n, keys.data() + n, n * 8, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  pav->n += n;
+  pav->added += n;
+  pav->clean = false;
+  return pav_maybe_union(h, pav);
+}
+
+int wfm_pav_matrix(wfm_handle_t* h, wfm_pav_t* pav, const wfm_lift_iv_t* iv, size_t n_iv, uint32_t* out) {
+  if (!h || !pav || (n_iv && (!iv || (pav->n_groups && !out)))) return WFM_E_ARG;
+  for (size_t j = 0; j < n_iv; ++j)
+    if (!(iv[j].start <= iv[j].end && iv[j].end <= pav->n_bases && iv[j].end - iv[j].start <= 0xffffffffull)) {
+      h->err = "wfm_pav_matrix: interval " + std::to_string(j) + " is reversed, ends beyond the " + std::to_string(pav->n_bases) + " target bases or is 2^32 bases long or longer";
+      return WFM_E_ARG;
+    }
+  if (int rc = wfm_pav_union(h, pav)) return rc;
+  if (n_iv == 0 || pav->n_groups == 0) return WFM_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  PassTimer tm(h);
+  const size_t G = pav->n_groups;
+  // chunks of whole rows that hold at most WFM_PAV_OUT_MB MiB of the matrix
+  const size_t cap = (size_t)cap_units("WFM_PAV_OUT_MB", G * 4, 1);
+  wfm_lift_iv_t* d_iv;
+  uint32_t* d_out;
+  Carver cv{pav->work, "pav matrix"};
+  cv.piece(&d_iv, n_iv); cv.piece(&d_out, std::min(n_iv, cap) * G);
+  if (int rc = cv.commit(h)) return rc;
+  HIPCHK(h, hipMemcpyAsync(d_iv, iv, n_iv * sizeof(wfm_lift_iv_t), hipMemcpyHostToDevice, h->stream));
+  const bool pinned = cs_pin_pieces(h);
+  size_t chunks = 0;
+  for (size_t ra = 0, rb; ra < n_iv; ra = rb, ++chunks) {
+    rb = chunk_end(ra, n_iv, cap, [](size_t a, size_t b) { return (unsigned long long)(b - a); });
+    launch_pav_matrix(pav->ks(), pav->ke(), (const unsigned long long*)pav->c.p, pav->n, d_iv, ra, rb, pav->n_groups, d_out, h->stream);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = cs_copy_down(h, pinned, (char*)(out + ra * G), (const uint8_t*)d_out, (rb - ra) * G * 4);  // (the block is the next chunk's)
+    if (e != hipSuccess) { h->err = std::string("wfm_pav_matrix: ") + hipGetErrorString(e); return WFM_E_HIP; }
+  }
+  if (tm.on)
+    fprintf(stderr, "[wfm] pav matrix: %zu intervals x %zu groups over %zu union intervals in %zu chunks, %.3f ms (host clock, ends in a synchronise)\n", n_iv, G,
+            pav->n, chunks, tm.host_ms());
+  return WFM_OK;
+}
+
+int wfm_pav_counts(const wfm_pav_t* pav, uint64_t out[3]) {
+  if (!pav || !out) return WFM_E_ARG;
+  out[0] = pav->added; out[1] = pav->n_union; out[2] = pav->unions;
+  return WFM_OK;
+}
+
+void wfm_pav_free_list(void* p) { free(p); }
+
+// ---- every score proved optimal by a banded DP (wfmash_hip.h; the band: wfa_optband.h; the kernel: wfa_optcheck.hip) ----
+int wfm_check_optimal(wfm_handle_t* h, const wfm_penalties_t* pen, const wfm_seqset_t* s, const wfm_result_t* res, uint64_t max_cells,
+                      wfm_optcheck_t* out) {
+  if (!h || !s || !out || !res || !pen) return WFM_E_ARG;
+  const int pmax = 32767;
+  if (pen->x <= 0 || pen->e1 <= 0 || pen->e2 <= 0 || pen->o1 < 0 || pen->o2 < 0 || pen->x > pmax || pen->o1 > pmax || pen->e1 > pmax ||
+      pen->o2 > pmax || pen->e2 > pmax) { h->err = "wfm_check_optimal: unsupported penalties"; return WFM_E_UNSUPPORTED; }
+  const size_t n = s->meta.size();
+  if (n == 0) return 0;
+  if (n > (size_t)INT32_MAX) { h->err = "wfm_check_optimal: too many problems for one call"; return WFM_E_ARG; }
+  HIPCHK(h, hipSetDevice(h->device));
+  const OptPen op{pen->x, pen->o1, pen->e1, pen->o2, pen->e2};
+  // the plan: every checked problem's band, the form it runs in, and per form the problems largest first
+  struct Item { uint64_t cells; uint32_t prob; };
+  std::vector<Item> forms[4];
+  std::vector<OptProb> probs(n);
+  for (size_t i = 0; i < n; ++i) {
+    const ProbMeta& m = s->meta[i];
+    wfm_optcheck_t& o = out[i];
+    o.flags = 0; o.dp_score = -1; o.band_lo = 0; o.band_hi = -1; o.cells = 0;
+    if (res[i].status != 0 || res[i].score < 0 || res[i].score >= (1 << 29)) { o.flags = WFM_OPT_NOT_CHECKED; continue; }
+    const OptBand b = opt_band(op, m.plen, m.tlen, m.pbf, m.pef, m.tbf, m.tef, res[i].score);  // (0 unless the mode is ENDSFREE: layout_seqset)
+    o.band_lo = (int32_t)b.lo; o.band_hi = (int32_t)b.hi;
+    if (max_cells && b.cells > max_cells) { o.flags = WFM_OPT_SKIPPED; continue; }
+    o.cells = b.cells;
+    OptProb& c = probs[i];
+    fill_seq(c, m);
+    c.row_off = 0;
+    c.pbf = std::min(std::max(m.pbf, 0), m.plen); c.pef = std::min(std::max(m.pef, 0), m.plen);
+    c.tbf = std::min(std::max(m.tbf, 0), m.tlen); c.tef = std::min(std::max(m.tef, 0), m.tlen);
+    c.band_lo = o.band_lo; c.band_hi = o.band_hi;
+    const int64_t W = b.hi - b.lo + 1;
+    forms[W <= WFM_OPT_BAND_C1 ? 0 : W <= WFM_OPT_BAND_C4 ? 1 : W <= WFM_OPT_REG_MAX ? 2 : 3].push_back(Item{b.cells, (uint32_t)i});
+  }
+  PassTimer tm(h);
+  uint64_t cells_total = 0;
+  size_t launches = 0;
+  std::vector<OptProb> chunk;
+  std::vector<int32_t> dp;
+  const size_t rows_cap = ((size_t)WFM_OPT_ROWS_MB << 20) / sizeof(int32_t);
+  for (int form = 0; form < 4; ++form) {
+    std::vector<Item>& v = forms[form];
+    std::stable_sort(v.begin(), v.end(), [](const Item& a, const Item& b) { return a.cells > b.cells; });
+    for (size_t i0 = 0; i0 < v.size();) {
+      // a chunk: all of a register form at once; of the memory form as many as the row budget holds (one at least)
+      chunk.clear();
+      size_t row_elems = 0, i1 = i0;
+      for (; i1 < v.size(); ++i1) {
+        OptProb c = probs[v[i1].prob];
+        if (form == 3) {
+          const size_t W = (size_t)((int64_t)c.band_hi - c.band_lo + 1);
+          const size_t need = 3 * ((W + WFM_OPT_REG_MAX - 1) / WFM_OPT_REG_MAX * WFM_OPT_REG_MAX + 1);
+          if (!chunk.empty() && row_elems + need > rows_cap) break;
+          c.row_off = (int64_t)row_elems;
+          row_elems += need;
+        }
+        chunk.push_back(c);
+      }
+      const size_t m = chunk.size();
+      OptProb* d_probs;
+      int32_t* d_out;
+      Carver cv{h->scratch, "optimality check"};
+      cv.piece(&d_probs, m); cv.piece(&d_out, m);
+      if (int rc = cv.commit(h)) return rc;
+      if (row_elems && h->optrows.ensure(row_elems)) { h->err = "out of device memory (optimality check: rows of a wide band)"; return WFM_E_NOMEM; }
+      HIPCHK(h, hipMemcpyAsync(d_probs, chunk.data(), m * sizeof(OptProb), hipMemcpyHostToDevice, h->stream));
+      launch_optcheck(s->d_seq, d_probs, (int)m, form, h->optrows.p, d_out, DevPen{pen->x, pen->o1, pen->e1, pen->o2, pen->e2}, h->stream);
+      HIPCHK(h, hipGetLastError());
+      dp.resize(m);
+      HIPCHK(h, hipMemcpyAsync(dp.data(), d_out, m * 4, hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(h, hipStreamSynchronize(h->stream));  // (the chunk's host vectors and the row block are free for the next one)
+      for (size_t q = 0; q < m; ++q) out[v[i0 + q].prob].dp_score = dp[q];
+      ++launches;
+      i0 = i1;
+    }
+  }
+  int flagged = 0;
+  for (size_t i = 0; i < n; ++i) {
+    wfm_optcheck_t& o = out[i];
+    if (o.flags) continue;
+    cells_total += o.cells;
+    if (o.dp_score < 0 || o.dp_score > res[i].score) o.flags = WFM_OPT_UNREACHED;
+    else if (o.dp_score < res[i].score) o.flags = WFM_OPT_CHEAPER;
+    flagged += o.flags != 0;
+  }
+  if (tm.on)
+    fprintf(stderr, "[wfm] optimality check: %zu problems (%zu / %zu / %zu in registers, %zu from memory), %zu launches, %llu cells in %.3f ms\n", n,
+            forms[0].size(), forms[1].size(), forms[2].size(), forms[3].size(), launches, (unsigned long long)cells_total, tm.host_ms());
+  return flagged;
+}
+
+}  // extern "C"

@@ -181,6 +181,56 @@ Counts total_counts() {
 
 }  // namespace verify
 
+namespace {
+// What --coverage-paf, --lift-paf and --pav-paf share: the target's offsets in the concatenation, the lines of an aligned PAF read and
+// skipped by one rule (coverage::classify_line), their runs gathered into batches of 65536 problems or 16 Mi runs, and device calls
+// that throw.  An entry point supplies what it keeps per line and what a batch is flushed into.
+struct PafRuns {
+  wfm_handle_t* h;
+  const char* tag;                      // "coverage", "lift", "pav": the [wfmash::...] of the texts
+  const wfmash_host::FastaStore& target;
+  std::vector<uint64_t> lengths, offsets;
+  uint64_t skipped[5] = {0, 0, 0, 0, 0};  // by coverage::LINE_*
+  std::vector<wfm_cov_prob_t> probs;    // the batch at hand: base, runs_off, n_runs of every line
+  std::vector<uint32_t> runs;
+
+  PafRuns(wfm_handle_t* h_, const char* tag_, const wfmash_host::FastaStore& target_) : h(h_), tag(tag_), target(target_), offsets(1, 0) {
+    for (int i = 0; i < target.nseq(); ++i) {
+      lengths.push_back((uint64_t)target.length(i));
+      offsets.push_back(offsets.back() + lengths.back());
+    }
+  }
+  int device(int rc, const char* what) const {
+    if (rc < 0) throw std::runtime_error(std::string("[wfmash::") + tag + "] " + what + " failed: " + wfm_last_error(h));
+    return rc;
+  }
+  void refused(uint64_t n) { skipped[coverage::LINE_MALFORMED] += n; }  // (a span that leaves the target: classify_line lets none through)
+  uint64_t all_skipped() const { return skipped[1] + skipped[2] + skipped[3] + skipped[4]; }
+  // extra(line) -> false: the line is not taken (the caller counts it); flush(): the batch to the device, whatever extra kept given back
+  template <class Extra, class Flush>
+  void read(std::istream& in, Extra extra, Flush flush) {
+    auto flush_batch = [&]() {
+      if (probs.empty()) return;
+      flush();
+      probs.clear(); runs.clear();
+    };
+    std::string line;
+    verify::Line l;
+    while (std::getline(in, line)) {
+      if (line.empty() || line[0] == '@') continue;
+      int ti = -1;
+      const int code = coverage::classify_line(line, [&](const std::string& name) { return target.find(name); }, lengths, l, &ti);
+      if (code != coverage::LINE_ADD) { skipped[code]++; continue; }
+      if (!extra(l)) continue;
+      probs.push_back(wfm_cov_prob_t{offsets[(size_t)ti] + (uint64_t)l.ts, (uint64_t)runs.size(), (uint32_t)l.runs.size(), 0u});
+      runs.insert(runs.end(), l.runs.begin(), l.runs.end());
+      if (probs.size() >= 65536 || runs.size() >= ((size_t)16 << 20)) flush_batch();
+    }
+    flush_batch();
+  }
+};
+}  // namespace
+
 extern "C" {
 
 void wfmh_set_verify(int on) { verify::set_enabled(on != 0); }
@@ -231,45 +281,24 @@ int wfmh_coverage_paf(wfm_handle_t* h, const char* target_fasta, const char* ali
     std::ofstream outstream(out_path);
     if (!outstream.is_open()) throw std::runtime_error(std::string("[wfmash::coverage] cannot open ") + out_path);
     std::vector<std::string> names;
-    std::vector<uint64_t> lengths, offsets(1, 0);
-    for (int i = 0; i < target->nseq(); ++i) {
-      names.push_back(target->name(i));
-      lengths.push_back((uint64_t)target->length(i));
-      offsets.push_back(offsets.back() + lengths.back());
-    }
-    auto device = [&](int rc, const char* what) {
-      if (rc < 0) throw std::runtime_error(std::string("[wfmash::coverage] ") + what + " failed: " + wfm_last_error(h));
-      return rc;
-    };
+    for (int i = 0; i < target->nseq(); ++i) names.push_back(target->name(i));
+    PafRuns pr(h, "coverage", *target);
+    const std::vector<uint64_t>& lengths = pr.lengths;
+    const uint64_t* skipped = pr.skipped;
     std::lock_guard<std::mutex> lk(wflign::handle_lock(h));
-    device(wfm_coverage_create(h, offsets.back(), &cov), "create");
-    uint64_t added = 0, skipped[5] = {0, 0, 0, 0, 0};
-    std::vector<wfm_cov_prob_t> probs;
-    std::vector<uint32_t> runs, flags;
-    auto flush = [&]() {
-      if (probs.empty()) return;
-      flags.resize(probs.size());
-      const int refused = device(wfm_coverage_add(h, cov, probs.data(), probs.size(), runs.data(), runs.size(), flags.data()), "add");
-      added += probs.size() - (uint64_t)refused;
-      skipped[coverage::LINE_MALFORMED] += (uint64_t)refused;  // (a span that leaves the target: classify_line lets none through)
-      probs.clear(); runs.clear();
-    };
-    std::string line;
-    verify::Line l;
-    while (std::getline(in, line)) {
-      if (line.empty() || line[0] == '@') continue;
-      int ti = -1;
-      const int code = coverage::classify_line(line, [&](const std::string& name) { return target->find(name); }, lengths, l, &ti);
-      if (code != coverage::LINE_ADD) { skipped[code]++; continue; }
-      probs.push_back(wfm_cov_prob_t{offsets[(size_t)ti] + (uint64_t)l.ts, (uint64_t)runs.size(), (uint32_t)l.runs.size(), 0u});
-      runs.insert(runs.end(), l.runs.begin(), l.runs.end());
-      if (probs.size() >= 65536 || runs.size() >= ((size_t)16 << 20)) flush();
-    }
-    flush();
+    pr.device(wfm_coverage_create(h, pr.offsets.back(), &cov), "create");
+    uint64_t added = 0;
+    std::vector<uint32_t> flags;
+    pr.read(in, [](const verify::Line&) { return true; }, [&]() {
+      flags.resize(pr.probs.size());
+      const int refused = pr.device(wfm_coverage_add(h, cov, pr.probs.data(), pr.probs.size(), pr.runs.data(), pr.runs.size(), flags.data()), "add");
+      added += pr.probs.size() - (uint64_t)refused;
+      pr.refused((uint64_t)refused);
+    });
     wfm_cov_interval_t* d_iv = nullptr;
     size_t n = 0;
     uint64_t totals[3] = {0, 0, 0};
-    device(wfm_coverage_intervals(h, cov, &d_iv, &n, totals), "intervals");
+    pr.device(wfm_coverage_intervals(h, cov, &d_iv, &n, totals), "intervals");
     std::vector<coverage::Interval> iv(n);
     for (size_t i = 0; i < n; ++i) iv[i] = coverage::Interval{d_iv[i].start, d_iv[i].depth};
     wfm_coverage_free_list(d_iv);
@@ -277,7 +306,7 @@ int wfmh_coverage_paf(wfm_handle_t* h, const char* target_fasta, const char* ali
     cov = nullptr;
     uint64_t lines = 0;
     outstream << coverage::coverage_bedgraph(names, lengths, iv, &lines);
-    const uint64_t all_skipped = skipped[1] + skipped[2] + skipped[3] + skipped[4];
+    const uint64_t all_skipped = pr.all_skipped();
     std::cerr << "[wfmash::coverage] " << added << " lines added, " << all_skipped << " skipped (" << skipped[1] << " without an =XID cg:Z:, " << skipped[2]
               << " malformed, " << skipped[3] << " with an unknown target, " << skipped[4] << " with another tlen), " << totals[0] << " bases covered, sum of depth "
               << totals[1] << ", max depth " << totals[2] << ", " << lines << " intervals" << std::endl;
@@ -305,37 +334,27 @@ int wfmh_lift_paf(wfm_handle_t* h, const char* target_fasta, const char* aligned
     const std::string bed_text((std::istreambuf_iterator<char>(bedstream)), std::istreambuf_iterator<char>());
     std::ofstream outstream(out_path);
     if (!outstream.is_open()) throw std::runtime_error(std::string("[wfmash::lift] cannot open ") + out_path);
-    std::vector<uint64_t> lengths, offsets(1, 0);
-    for (int i = 0; i < target->nseq(); ++i) {
-      lengths.push_back((uint64_t)target->length(i));
-      offsets.push_back(offsets.back() + lengths.back());
-    }
-    const lift::Bed bed = lift::parse_bed(bed_text, [&](const std::string& name) { return target->find(name); }, lengths, offsets);
-    auto device = [&](int rc, const char* what) {
-      if (rc < 0) throw std::runtime_error(std::string("[wfmash::lift] ") + what + " failed: " + wfm_last_error(h));
-      return rc;
-    };
+    PafRuns pr(h, "lift", *target);
+    const uint64_t* skipped = pr.skipped;
+    const lift::Bed bed = lift::parse_bed(bed_text, [&](const std::string& name) { return target->find(name); }, pr.lengths, pr.offsets);
     std::lock_guard<std::mutex> lk(wflign::handle_lock(h));
     {
       std::vector<wfm_lift_iv_t> raw(bed.iv.size());
       for (size_t i = 0; i < raw.size(); ++i) raw[i] = wfm_lift_iv_t{bed.iv[i].gstart, bed.iv[i].gend};
-      device(wfm_liftset_create(h, raw.data(), raw.size(), offsets.back(), &set), "create");
+      pr.device(wfm_liftset_create(h, raw.data(), raw.size(), pr.offsets.back(), &set), "create");
     }
-    uint64_t lifted = 0, n_lines = 0, empty = 0, skipped[5] = {0, 0, 0, 0, 0};
-    std::vector<wfm_cov_prob_t> probs;
-    std::vector<uint32_t> runs;
+    uint64_t lifted = 0, n_lines = 0, empty = 0;
     std::vector<lift::Record> where;
     std::vector<wfm_liftcall_t> per;
     std::string text;
     auto flush = [&]() {
-      if (probs.empty()) return;
-      per.resize(probs.size());
+      per.resize(pr.probs.size());
       wfm_lift_t* lifts = nullptr;
       size_t n = 0;
-      device(wfm_lift_runs(h, set, probs.data(), probs.size(), runs.data(), runs.size(), &lifts, &n, per.data()), "lift");
+      pr.device(wfm_lift_runs(h, set, pr.probs.data(), pr.probs.size(), pr.runs.data(), pr.runs.size(), &lifts, &n, per.data()), "lift");
       text.clear();
-      for (size_t j = 0; j < probs.size(); ++j) {
-        if (per[j].flags) { skipped[coverage::LINE_MALFORMED]++; continue; }  // (a span that leaves the target: classify_line lets none through)
+      for (size_t j = 0; j < pr.probs.size(); ++j) {
+        if (per[j].flags) { pr.refused(1); continue; }
         ++lifted;
         for (uint64_t k = per[j].first; k < per[j].first + per[j].count; ++k) {
           const wfm_lift_t& l = lifts[k];
@@ -346,26 +365,17 @@ int wfmh_lift_paf(wfm_handle_t* h, const char* target_fasta, const char* aligned
       }
       wfm_free_lifts(lifts);
       outstream << text;
-      probs.clear(); runs.clear(); where.clear();
+      where.clear();
     };
-    std::string line;
-    verify::Line l;
-    while (std::getline(in, line)) {
-      if (line.empty() || line[0] == '@') continue;
-      int ti = -1;
-      const int code = coverage::classify_line(line, [&](const std::string& name) { return target->find(name); }, lengths, l, &ti);
-      if (code != coverage::LINE_ADD) { skipped[code]++; continue; }
-      probs.push_back(wfm_cov_prob_t{offsets[(size_t)ti] + (uint64_t)l.ts, (uint64_t)runs.size(), (uint32_t)l.runs.size(), 0u});
-      runs.insert(runs.end(), l.runs.begin(), l.runs.end());
+    pr.read(in, [&](const verify::Line& l) {
       lift::Record r;
       r.qname = l.qname; r.tname = l.tname; r.qs = (uint64_t)l.qs; r.qe = (uint64_t)l.qe; r.ts = (uint64_t)l.ts; r.rev = l.rev;
       where.push_back(std::move(r));
-      if (probs.size() >= 65536 || runs.size() >= ((size_t)16 << 20)) flush();
-    }
-    flush();
+      return true;
+    }, flush);
     wfm_liftset_free(set);
     set = nullptr;
-    const uint64_t all_skipped = skipped[1] + skipped[2] + skipped[3] + skipped[4];
+    const uint64_t all_skipped = pr.all_skipped();
     std::cerr << "[wfmash::lift] " << bed.iv.size() << " intervals (" << bed.skipped << " BED lines skipped), " << lifted << " lines lifted, " << all_skipped
               << " skipped (" << skipped[1] << " without an =XID cg:Z:, " << skipped[2] << " malformed, " << skipped[3] << " with an unknown target, " << skipped[4]
               << " with another tlen), " << n_lines << " lifts written, " << empty << " of them empty" << std::endl;
@@ -391,11 +401,9 @@ int wfmh_pav_paf(wfm_handle_t* h, const char* target_fasta, const char* query_fa
     std::shared_ptr<wfmash_host::FastaStore> query = query_fasta_or_null && *query_fasta_or_null ? wfmash_host::open_shared(query_fasta_or_null) : target;
     std::ifstream in(aligned_paf);
     if (!in.is_open()) throw std::runtime_error(std::string("[wfmash::pav] cannot open ") + aligned_paf);
-    std::vector<uint64_t> lengths, offsets(1, 0);
-    for (int i = 0; i < target->nseq(); ++i) {
-      lengths.push_back((uint64_t)target->length(i));
-      offsets.push_back(offsets.back() + lengths.back());
-    }
+    PafRuns pr(h, "pav", *target);
+    const std::vector<uint64_t>&lengths = pr.lengths, &offsets = pr.offsets;
+    const uint64_t* skipped = pr.skipped;
     std::vector<lift::Interval> iv;
     uint64_t bed_skipped = 0;
     if (with_bed) {
@@ -413,42 +421,30 @@ int wfmh_pav_paf(wfm_handle_t* h, const char* target_fasta, const char* query_fa
     const pav::Columns cols = pav::columns(qnames);
     std::ofstream outstream(out_path);
     if (!outstream.is_open()) throw std::runtime_error(std::string("[wfmash::pav] cannot open ") + out_path);
-    auto device = [&](int rc, const char* what) {
-      if (rc < 0) throw std::runtime_error(std::string("[wfmash::pav] ") + what + " failed: " + wfm_last_error(h));
-      return rc;
-    };
     std::lock_guard<std::mutex> lk(wflign::handle_lock(h));
-    device(wfm_pav_create(h, offsets.back(), (uint32_t)cols.keys.size(), &obj), "create");
-    uint64_t added = 0, no_query = 0, skipped[5] = {0, 0, 0, 0, 0};
+    pr.device(wfm_pav_create(h, offsets.back(), (uint32_t)cols.keys.size(), &obj), "create");
+    uint64_t added = 0, no_query = 0;
+    std::vector<uint32_t> group, flags;  // the column of every line of the batch at hand
     std::vector<wfm_pav_prob_t> probs;
-    std::vector<uint32_t> runs, flags;
-    auto flush = [&]() {
-      if (probs.empty()) return;
-      flags.resize(probs.size());
-      const int refused = device(wfm_pav_add(h, obj, probs.data(), probs.size(), runs.data(), runs.size(), flags.data()), "add");
-      added += probs.size() - (uint64_t)refused;
-      skipped[coverage::LINE_MALFORMED] += (uint64_t)refused;  // (a span that leaves the target: classify_line lets none through)
-      probs.clear(); runs.clear();
-    };
-    std::string line;
-    verify::Line l;
-    while (std::getline(in, line)) {
-      if (line.empty() || line[0] == '@') continue;
-      int ti = -1;
-      const int code = coverage::classify_line(line, [&](const std::string& name) { return target->find(name); }, lengths, l, &ti);
-      if (code != coverage::LINE_ADD) { skipped[code]++; continue; }
+    pr.read(in, [&](const verify::Line& l) {
       const int qi = query->find(l.qname);
-      if (qi < 0) { ++no_query; continue; }
-      probs.push_back(wfm_pav_prob_t{offsets[(size_t)ti] + (uint64_t)l.ts, (uint64_t)runs.size(), (uint32_t)l.runs.size(), cols.of_seq[(size_t)qi]});
-      runs.insert(runs.end(), l.runs.begin(), l.runs.end());
-      if (probs.size() >= 65536 || runs.size() >= ((size_t)16 << 20)) flush();
-    }
-    flush();
+      if (qi < 0) { ++no_query; return false; }
+      group.push_back(cols.of_seq[(size_t)qi]);
+      return true;
+    }, [&]() {
+      probs.resize(pr.probs.size());
+      for (size_t j = 0; j < probs.size(); ++j) probs[j] = wfm_pav_prob_t{pr.probs[j].base, pr.probs[j].runs_off, pr.probs[j].n_runs, group[j]};
+      flags.resize(probs.size());
+      const int refused = pr.device(wfm_pav_add(h, obj, probs.data(), probs.size(), pr.runs.data(), pr.runs.size(), flags.data()), "add");
+      added += probs.size() - (uint64_t)refused;
+      pr.refused((uint64_t)refused);
+      group.clear();
+    });
     const size_t G = cols.keys.size();
     std::vector<uint32_t> cells(G * iv.size(), 0u);
     std::vector<wfm_lift_iv_t> raw(iv.size());
     for (size_t j = 0; j < iv.size(); ++j) raw[j] = wfm_lift_iv_t{iv[j].gstart, iv[j].gend};
-    device(wfm_pav_matrix(h, obj, raw.data(), raw.size(), cells.data()), "matrix");
+    pr.device(wfm_pav_matrix(h, obj, raw.data(), raw.size(), cells.data()), "matrix");
     uint64_t counts[3] = {0, 0, 0};
     wfm_pav_counts(obj, counts);
     wfm_pav_free(obj);
@@ -459,7 +455,7 @@ int wfmh_pav_paf(wfm_handle_t* h, const char* target_fasta, const char* query_fa
       if (text.size() >= ((size_t)1 << 20)) { outstream << text; text.clear(); }
     }
     outstream << text;
-    const uint64_t all_skipped = skipped[1] + skipped[2] + skipped[3] + skipped[4] + no_query;
+    const uint64_t all_skipped = pr.all_skipped() + no_query;
     std::cerr << "[wfmash::pav] " << iv.size() << " intervals (" << bed_skipped << " BED lines skipped) x " << G << " groups, " << added << " lines added, " << all_skipped
               << " skipped (" << skipped[1] << " without an =XID cg:Z:, " << skipped[2] << " malformed, " << skipped[3] << " with an unknown target, " << skipped[4]
               << " with another tlen, " << no_query << " with an unknown query), " << counts[1] << " union intervals" << std::endl;

@@ -644,113 +644,24 @@ void write_record(BiwfaBatch& b, size_t ri) {
   r.paf += '\n';
   g_cs_counts[0] += 1; g_cs_counts[1] += r.cs.size();
 }
-// ---- --coverage: the runs of every record WRITTEN into the depth object of the batch's handle, ONE device call per batch
-// (wfm_coverage_add).  It runs behind write_record, where the filters have spoken.  A record's problem is what its line spells: the ops
-// trimmed of their leading and trailing I and D runs (window_parts' rule, trim_and_filter's), at base = the target sequence's offset in
-// the concatenation + the target start the writer wrote -- variant_records' ts.  Nothing goes up but runs.  A record the device
-// refuses, or whose ops its runs cannot hold, is a defect: it adds nothing, is counted and reported. ----
-int coverage_records(BiwfaBatch& b) {
+// ---- the written records of a batch as --coverage, --pav and --lift take them, packed ONCE per batch.  It runs behind write_record, where
+// the filters have spoken.  A record's problem is what its line spells: the ops trimmed of their leading and trailing I and D runs
+// (window_parts' rule, trim_and_filter's), at base = the target sequence's offset in the concatenation + the target start the writer
+// wrote -- variant_records' ts.  Nothing goes up but runs.  A record whose ops the runs cannot hold is a defect: it is in no list, and
+// every stage counts and reports it. ----
+struct PackedRuns {
+  std::vector<wfm_cov_prob_t> probs;   // base, runs_off, n_runs of every record packed
+  std::vector<uint32_t> runs;          // their trimmed ops as run words
+  std::vector<size_t> rec;             // the record's index in the batch
+  std::vector<uint64_t> ta, qa, q_len; // the target and query bases trimmed in front; the query bases the runs spell
+  uint64_t unknown = 0;                // records whose ops the runs cannot hold
+  double ms = 0;                       // what the packing took
+};
+PackedRuns pack_written(const BiwfaBatch& b) {
   const auto t0 = Clock::now();
-  std::vector<wfm_cov_prob_t> probs;
-  std::vector<uint32_t> runs;
-  uint64_t unknown = 0;
-  for (const BiwfaRecord& r : b.recs) {
-    if (!r.ok || !r.written) continue;
-    const CigarOps& ops = r.ops;
-    size_t ob = 0, oe = ops.size();
-    uint64_t ta = 0;
-    while (ob < oe && (ops[ob].second == 'I' || ops[ob].second == 'D')) { if (ops[ob].second == 'D') ta += (uint64_t)ops[ob].first; ++ob; }
-    while (oe > ob && (ops[oe - 1].second == 'I' || ops[oe - 1].second == 'D')) --oe;
-    if (oe == ob) continue;
-    wfm_cov_prob_t p{r.target_global + r.target_offset + ta, (uint64_t)runs.size(), (uint32_t)(oe - ob), 0u};
-    bool known = true;
-    for (size_t k = ob; k < oe; ++k) {
-      const char c = ops[k].second;
-      const uint32_t op = c == '=' ? 0u : c == 'X' ? 1u : c == 'I' ? 2u : c == 'D' ? 3u : 4u;
-      if (op > 3u || ops[k].first <= 0 || (uint32_t)ops[k].first >= (1u << 30)) { known = false; break; }
-      runs.push_back(((uint32_t)ops[k].first << 2) | op);
-    }
-    if (!known) { runs.resize((size_t)p.runs_off); ++unknown; continue; }
-    probs.push_back(p);
-  }
-  int rc = WFM_OK;
-  if (!probs.empty()) {
-    std::vector<uint32_t> flags(probs.size());
-    std::lock_guard<std::mutex> lk(handle_lock(b.h));
-    rc = wfm_coverage_add(b.h, b.fmt.coverage, probs.data(), probs.size(), runs.data(), runs.size(), flags.data());
-    if (rc < 0 && b.stats) b.stats->error = wfm_last_error(b.h);
-  }
-  if (rc < 0) return rc;
-  g_coverage_counts[0] += probs.size() - (uint64_t)rc;
-  if (rc > 0 || unknown)
-    fprintf(stderr, "[wflign] coverage: %llu records of a batch were NOT added to the depth (their runs leave the target or cannot be held)\n",
-            (unsigned long long)((uint64_t)rc + unknown));
-  if (getenv("WFM_DEBUG"))
-    fprintf(stderr, "[wflign] coverage: %zu records, %zu runs, %d flagged, %.1f ms\n", probs.size(), runs.size(), rc, ms_between(t0, Clock::now()));
-  return 0;
-}
-// ---- --pav: the runs of every record WRITTEN into the presence object of the batch's handle, with the column of the query's group, ONE
-// device call per batch (wfm_pav_add).  It runs beside coverage_records and takes the same problems: the same trimmed ops at the same
-// base.  Nothing goes up but runs.  A record the device refuses, or whose ops its runs cannot hold, is a defect: it adds nothing, is
-// counted and reported. ----
-int pav_records(BiwfaBatch& b) {
-  const auto t0 = Clock::now();
-  std::vector<wfm_pav_prob_t> probs;
-  std::vector<uint32_t> runs;
-  uint64_t unknown = 0;
-  for (const BiwfaRecord& r : b.recs) {
-    if (!r.ok || !r.written) continue;
-    const CigarOps& ops = r.ops;
-    size_t ob = 0, oe = ops.size();
-    uint64_t ta = 0;
-    while (ob < oe && (ops[ob].second == 'I' || ops[ob].second == 'D')) { if (ops[ob].second == 'D') ta += (uint64_t)ops[ob].first; ++ob; }
-    while (oe > ob && (ops[oe - 1].second == 'I' || ops[oe - 1].second == 'D')) --oe;
-    if (oe == ob) continue;
-    wfm_pav_prob_t p{r.target_global + r.target_offset + ta, (uint64_t)runs.size(), (uint32_t)(oe - ob), r.pav_group};
-    bool known = true;
-    for (size_t k = ob; k < oe; ++k) {
-      const char c = ops[k].second;
-      const uint32_t op = c == '=' ? 0u : c == 'X' ? 1u : c == 'I' ? 2u : c == 'D' ? 3u : 4u;
-      if (op > 3u || ops[k].first <= 0 || (uint32_t)ops[k].first >= (1u << 30)) { known = false; break; }
-      runs.push_back(((uint32_t)ops[k].first << 2) | op);
-    }
-    if (!known) { runs.resize((size_t)p.runs_off); ++unknown; continue; }
-    probs.push_back(p);
-  }
-  int rc = WFM_OK;
-  auto t1 = t0;
-  if (!probs.empty()) {
-    std::vector<uint32_t> flags(probs.size());
-    std::lock_guard<std::mutex> lk(handle_lock(b.h));
-    t1 = Clock::now();
-    rc = wfm_pav_add(b.h, b.fmt.pav, probs.data(), probs.size(), runs.data(), runs.size(), flags.data());
-    if (rc < 0 && b.stats) b.stats->error = wfm_last_error(b.h);
-  }
-  if (rc < 0) return rc;
-  g_pav_counts[0] += probs.size() - (uint64_t)rc;
-  if (rc > 0 || unknown)
-    fprintf(stderr, "[wflign] pav: %llu records of a batch were NOT added (their runs leave the target or cannot be held, or their query has no column)\n",
-            (unsigned long long)((uint64_t)rc + unknown));
-  if (getenv("WFM_DEBUG"))
-    fprintf(stderr, "[wflign] pav: %zu records, %zu runs, %d flagged, %.1f ms (runs %.1f, device call %.1f)\n", probs.size(), runs.size(), rc,
-            ms_between(t0, Clock::now()), ms_between(t0, t1), ms_between(t1, Clock::now()));
-  return 0;
-}
-// ---- --lift: the BED intervals through the runs of every record WRITTEN, ONE device call per batch (wfm_lift_runs).  It runs where
-// coverage_records runs and takes the same problems: the part of the ops the line spells, at base = the target sequence's offset in the
-// concatenation + the target start the writer wrote; the query window is the writer's too (variant_records' qs, qe).  Nothing goes up
-// but runs.  The lines of a record go into BiwfaRecord::lift in the order the device gives them: ascending interval.  A record the device
-// refuses, or whose ops its runs cannot hold, is a defect: it has no lines and is reported. ----
-int lift_records(BiwfaBatch& b) {
-  const auto t0 = Clock::now();
-  std::vector<wfm_cov_prob_t> probs;
-  std::vector<uint32_t> runs;
-  std::vector<size_t> rec_of;
-  std::vector<lift::Record> where;
-  uint64_t unknown = 0;
+  PackedRuns pk;
   for (size_t ri = 0; ri < b.recs.size(); ++ri) {
-    BiwfaRecord& r = b.recs[ri];
-    r.lift.clear();
+    const BiwfaRecord& r = b.recs[ri];
     if (!r.ok || !r.written) continue;
     const CigarOps& ops = r.ops;
     size_t ob = 0, oe = ops.size();
@@ -758,24 +669,84 @@ int lift_records(BiwfaBatch& b) {
     while (ob < oe && (ops[ob].second == 'I' || ops[ob].second == 'D')) { (ops[ob].second == 'D' ? ta : qa) += (uint64_t)ops[ob].first; ++ob; }
     while (oe > ob && (ops[oe - 1].second == 'I' || ops[oe - 1].second == 'D')) --oe;
     if (oe == ob) continue;
-    wfm_cov_prob_t p{r.target_global + r.target_offset + ta, (uint64_t)runs.size(), (uint32_t)(oe - ob), 0u};
+    const wfm_cov_prob_t p{r.target_global + r.target_offset + ta, (uint64_t)pk.runs.size(), (uint32_t)(oe - ob), 0u};
     bool known = true;
     for (size_t k = ob; k < oe; ++k) {
       const char c = ops[k].second;
       const uint32_t op = c == '=' ? 0u : c == 'X' ? 1u : c == 'I' ? 2u : c == 'D' ? 3u : 4u;
       if (op > 3u || ops[k].first <= 0 || (uint32_t)ops[k].first >= (1u << 30)) { known = false; break; }
-      runs.push_back(((uint32_t)ops[k].first << 2) | op);
+      pk.runs.push_back(((uint32_t)ops[k].first << 2) | op);
       if (op != 3u) q_len += (uint64_t)ops[k].first;
     }
-    if (!known) { runs.resize((size_t)p.runs_off); ++unknown; continue; }
-    lift::Record lr;
+    if (!known) { pk.runs.resize((size_t)p.runs_off); ++pk.unknown; continue; }
+    pk.probs.push_back(p);
+    pk.rec.push_back(ri);
+    pk.ta.push_back(ta); pk.qa.push_back(qa); pk.q_len.push_back(q_len);
+  }
+  pk.ms = ms_between(t0, Clock::now());
+  return pk;
+}
+// ---- --coverage: the packed runs into the depth object of the batch's handle, ONE device call per batch (wfm_coverage_add).  A record
+// the device refuses adds nothing, is counted and reported. ----
+int coverage_records(BiwfaBatch& b, const PackedRuns& pk) {
+  const auto t0 = Clock::now();
+  const std::vector<wfm_cov_prob_t>& probs = pk.probs;
+  int rc = WFM_OK;
+  if (!probs.empty()) {
+    std::vector<uint32_t> flags(probs.size());
+    std::lock_guard<std::mutex> lk(handle_lock(b.h));
+    rc = wfm_coverage_add(b.h, b.fmt.coverage, probs.data(), probs.size(), pk.runs.data(), pk.runs.size(), flags.data());
+    if (rc < 0 && b.stats) b.stats->error = wfm_last_error(b.h);
+  }
+  if (rc < 0) return rc;
+  g_coverage_counts[0] += probs.size() - (uint64_t)rc;
+  if (rc > 0 || pk.unknown)
+    fprintf(stderr, "[wflign] coverage: %llu records of a batch were NOT added to the depth (their runs leave the target or cannot be held)\n",
+            (unsigned long long)((uint64_t)rc + pk.unknown));
+  if (getenv("WFM_DEBUG"))
+    fprintf(stderr, "[wflign] coverage: %zu records, %zu runs, %d flagged, %.1f ms\n", probs.size(), pk.runs.size(), rc, pk.ms + ms_between(t0, Clock::now()));
+  return 0;
+}
+// ---- --pav: the same problems into the presence object of the batch's handle, each with the column of its query's group, ONE device call
+// per batch (wfm_pav_add).  A record the device refuses adds nothing, is counted and reported. ----
+int pav_records(BiwfaBatch& b, const PackedRuns& pk) {
+  const auto t0 = Clock::now();
+  std::vector<wfm_pav_prob_t> probs(pk.probs.size());
+  for (size_t j = 0; j < probs.size(); ++j) probs[j] = wfm_pav_prob_t{pk.probs[j].base, pk.probs[j].runs_off, pk.probs[j].n_runs, b.recs[pk.rec[j]].pav_group};
+  int rc = WFM_OK;
+  auto t1 = t0;
+  if (!probs.empty()) {
+    std::vector<uint32_t> flags(probs.size());
+    std::lock_guard<std::mutex> lk(handle_lock(b.h));
+    t1 = Clock::now();
+    rc = wfm_pav_add(b.h, b.fmt.pav, probs.data(), probs.size(), pk.runs.data(), pk.runs.size(), flags.data());
+    if (rc < 0 && b.stats) b.stats->error = wfm_last_error(b.h);
+  }
+  if (rc < 0) return rc;
+  g_pav_counts[0] += probs.size() - (uint64_t)rc;
+  if (rc > 0 || pk.unknown)
+    fprintf(stderr, "[wflign] pav: %llu records of a batch were NOT added (their runs leave the target or cannot be held, or their query has no column)\n",
+            (unsigned long long)((uint64_t)rc + pk.unknown));
+  if (getenv("WFM_DEBUG"))
+    fprintf(stderr, "[wflign] pav: %zu records, %zu runs, %d flagged, %.1f ms (runs %.1f, device call %.1f)\n", probs.size(), pk.runs.size(), rc,
+            pk.ms + ms_between(t0, Clock::now()), pk.ms + ms_between(t0, t1), ms_between(t1, Clock::now()));
+  return 0;
+}
+// ---- --lift: the BED intervals through the same problems, ONE device call per batch (wfm_lift_runs); the query window is the writer's
+// (variant_records' qs, qe).  The lines of a record go into BiwfaRecord::lift in the order the device gives them: ascending interval.  A
+// record the device refuses has no lines and is reported. ----
+int lift_records(BiwfaBatch& b, const PackedRuns& pk) {
+  const auto t0 = Clock::now();
+  const std::vector<wfm_cov_prob_t>& probs = pk.probs;
+  for (BiwfaRecord& r : b.recs) r.lift.clear();
+  std::vector<lift::Record> where(probs.size());
+  for (size_t j = 0; j < probs.size(); ++j) {
+    const BiwfaRecord& r = b.recs[pk.rec[j]];
+    lift::Record& lr = where[j];
     lr.qname = r.query_name; lr.tname = r.target_name; lr.rev = r.query_is_rev;
-    lr.qs = r.query_is_rev ? r.query_offset + (r.query_length - qa - q_len) : r.query_offset + qa;
-    lr.qe = lr.qs + q_len;
-    lr.ts = r.target_offset + ta;
-    probs.push_back(p);
-    rec_of.push_back(ri);
-    where.push_back(std::move(lr));
+    lr.qs = r.query_is_rev ? r.query_offset + (r.query_length - pk.qa[j] - pk.q_len[j]) : r.query_offset + pk.qa[j];
+    lr.qe = lr.qs + pk.q_len[j];
+    lr.ts = r.target_offset + pk.ta[j];
   }
   int rc = WFM_OK;
   wfm_lift_t* lifts = nullptr;
@@ -785,7 +756,7 @@ int lift_records(BiwfaBatch& b) {
   if (!probs.empty()) {
     std::lock_guard<std::mutex> lk(handle_lock(b.h));
     t1 = Clock::now();
-    rc = wfm_lift_runs(b.h, b.fmt.liftset, probs.data(), probs.size(), runs.data(), runs.size(), &lifts, &n_lifts, per.data());
+    rc = wfm_lift_runs(b.h, b.fmt.liftset, probs.data(), probs.size(), pk.runs.data(), pk.runs.size(), &lifts, &n_lifts, per.data());
     if (rc < 0 && b.stats) b.stats->error = wfm_last_error(b.h);
   }
   if (rc < 0) return rc;
@@ -794,7 +765,7 @@ int lift_records(BiwfaBatch& b) {
   std::atomic<uint64_t> lines{0}, empty{0}, refused{0};
   for_each_record(probs.size(), b.fmt.threads, [&](size_t j) {
     if (per[j].flags) { refused += 1; return; }
-    std::string& out = b.recs[rec_of[j]].lift;
+    std::string& out = b.recs[pk.rec[j]].lift;
     uint64_t e = 0;
     for (uint64_t k = per[j].first; k < per[j].first + per[j].count; ++k) {
       const wfm_lift_t& l = lifts[k];
@@ -805,12 +776,12 @@ int lift_records(BiwfaBatch& b) {
   });
   wfm_free_lifts(lifts);
   g_lift_counts[0] += probs.size() - refused.load(); g_lift_counts[1] += lines.load(); g_lift_counts[2] += empty.load();
-  if (refused.load() || unknown)
+  if (refused.load() || pk.unknown)
     fprintf(stderr, "[wflign] lift: %llu records of a batch were NOT lifted (their runs leave the target or cannot be held)\n",
-            (unsigned long long)(refused.load() + unknown));
+            (unsigned long long)(refused.load() + pk.unknown));
   if (getenv("WFM_DEBUG"))
-    fprintf(stderr, "[wflign] lift: %zu records, %zu runs, %zu lifts, %.1f ms (runs %.1f, device call %.1f, text %.1f)\n", probs.size(), runs.size(), n_lifts,
-            ms_between(t0, Clock::now()), ms_between(t0, t1), ms_between(t1, t2), ms_between(t2, Clock::now()));
+    fprintf(stderr, "[wflign] lift: %zu records, %zu runs, %zu lifts, %.1f ms (runs %.1f, device call %.1f, text %.1f)\n", probs.size(), pk.runs.size(), n_lifts,
+            pk.ms + ms_between(t0, Clock::now()), pk.ms + ms_between(t0, t1), ms_between(t1, t2), ms_between(t2, Clock::now()));
   return 0;
 }
 }  // namespace
@@ -884,9 +855,12 @@ int do_biwfa_alignment_batch(wfm_handle_t* h, std::vector<BiwfaRecord>& recs, co
   } else {
     for_each_record(n, fmt.threads, [&](size_t ri) { swizzle(b, ri); write_record(b, ri); });
   }
-  if (fmt.coverage && (rc = coverage_records(b)) < 0) return rc;
-  if (fmt.pav && (rc = pav_records(b)) < 0) return rc;
-  if (fmt.liftset && (rc = lift_records(b)) < 0) return rc;
+  if (fmt.coverage || fmt.pav || fmt.liftset) {  // one packing for the stages that are on; each makes its own device call
+    const PackedRuns pk = pack_written(b);
+    if (fmt.coverage && (rc = coverage_records(b, pk)) < 0) return rc;
+    if (fmt.pav && (rc = pav_records(b, pk)) < 0) return rc;
+    if (fmt.liftset && (rc = lift_records(b, pk)) < 0) return rc;
+  }
   if (dbg)
     fprintf(stderr, "[wflign] %zu records: main alignment + runs + scans %.1f ms (incl. waiting for the device), patches %.1f ms (%zu tails scanned after their heads), swizzle + records %.1f ms\n",
             n, ms_between(ts0, ts1), ms_between(ts1, ts2), b.later, ms_between(ts2, Clock::now()));
