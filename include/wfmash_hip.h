@@ -623,7 +623,9 @@ enum {
   WFM_TC_REUSE_TOUCHED = 11,  /* the restore found a kept cell on the job's box or beyond it (v >= hmax_c(k) - WFM_REUSE_TOUCH_SLACK)    */
   WFM_TC_REUSE_FELL_OTHER = 12, /* any other cause: the maxima fired while one direction waited, the job met right behind the restore ... */
   WFM_TC_PLANNED_ENDS = 13,  /* jobs that ended phase 1 at the state planned from their known score, without a search (WFM_TILE_PLANNED_END)   */
-  WFM_TILE_COUNTERS = 14
+  WFM_TC_P2_EXACT = 14,        /* jobs whose phase 2 took the exact walk: they stood at their own score, so only pairs of exactly that score were looked at (WFM_P2_EXACT) */
+  WFM_TC_P2_EXACT_MISSES = 15, /* of those, the jobs that found no such pair within its reach and went through the ordinary walk from the same state                    */
+  WFM_TILE_COUNTERS = 16
 };
 size_t wfm_get_tile_counters(const wfm_handle_t* h, uint64_t* out, size_t n);
 

@@ -27,7 +27,8 @@ WFM_PF_ROOT_AGAIN, WFM_PF_JOB_AGAIN, WFM_PF_BASE_RETRY, WFM_PF_BASE_RETRY2, WFM_
 WFM_PF_RING_GROWN = 256
 # wfm_get_tile_counters (include/wfmash_hip.h): the paths the BiWFA tile phase took in an align call, in the header's order
 TILE_COUNTERS = ("jobs", "exact_ends", "fine_reruns", "gap_reruns", "ring3", "blocks_coarse", "blocks_fine", "left_band",
-                 "reuse_resumed", "reuse_fallbacks", "reuse_keeps", "reuse_touched", "reuse_fell_other", "planned_ends")
+                 "reuse_resumed", "reuse_fallbacks", "reuse_keeps", "reuse_touched", "reuse_fell_other", "planned_ends",
+                 "p2_exact", "p2_exact_misses")
 
 EXPORTS = [
     "wfm_create", "wfm_destroy", "wfm_last_error", "wfm_device_name",

@@ -27,6 +27,7 @@ constexpr int WFM_DEV_BAND = -4;      // bialign job ran out of its diagonal ban
 constexpr int WFM_DEV_P2_NOTHING = -6; // phase 2 ended without improving on the breakpoint it was handed (BpJob / P2Job::best0): that one stands
 constexpr int WFM_DEV_LIMIT = -7;     // bialign job under a hard score limit (BpJob::limit): a direction stands at the limit and the directions have not met
 constexpr int WFM_DEV_P2_MORE = -5;   // phase 2 did not end within the P2K rows computed ahead: the step kernel takes the job
+constexpr int WFM_DEV_P2_EXACT_MISS = -8;  // the exact walk (P2Job::exact) found no pair of the job's own score within its reach: the ordinary walk takes the job from the same state
 
 struct DevPen { int x, o1, e1, o2, e2; };
 
@@ -171,6 +172,9 @@ void launch_restore(int32_t* ring, const TileJob* jobs, const RestoreTask* tasks
 // the tests left in it (doing all tests of a job side by side was tried: without the best breakpoint so far to prune
 // with, the tests after the first hit cost more than the whole sequential walk).  A job whose loop has not ended after
 // 2 * P2K tests (WFM_DEV_P2_MORE) is finished by wfa_bp_kernel from the same snapshot.
+// A job that stands at the end planned from its known score needs neither the maxima nor the pruning: only pairs of rows of exactly its own
+// score can be the breakpoint, one row per component and test (P2Job::exact, wfa_p2_exact_kernel).  A chunk's jobs that search come first on
+// the device, the maxima and the two kernels above are theirs alone; below the roots' level a chunk usually has none.
 constexpr int P2K = 32;            // (48 until jobs could take further rounds: most walks end within 2 x 26 tests, and the rows of the
                                     // others are computed when they are asked for -- C3 109 -> 106 ms per step, C1 substitute 5.5 -> 5.4 s)
 constexpr int P2ROWS = SNAP_ROWS + P2K;  // row maxima per direction: the snapshot's rows sd-25 .. sd, then sd+1 .. sd+P2K
@@ -185,8 +189,13 @@ struct P2Job {
   int32_t sf, sr, last_fwd;            // state at the meeting point
   int32_t sub, best0;                  // as BpJob::sub, BpJob::best0
   int32_t nblk;                        // 64-diagonal blocks of a row: block of diagonal k = (k + koff2) >> 6
+  // > 0: the job stands at the end planned from its known score, sf + sr = exact = that score (wfa_plan.h, planned_meet): no pair of rows is
+  // cheaper, so the walk only looks at the pairs of exactly this score, at most one row per component and test, and ends at the first that
+  // meets (wfa_p2_exact_kernel: no maxima, no bm_off).  0: the job searches (wfa_p2_blockmax_kernel, wfa_p2_overlap_kernel)
+  int32_t exact;
   int64_t bm_off;                      // int32 element offset of the job's block maxima [dir][P2ROWS][comp][nblk]
 };
+static_assert(sizeof(P2Job) == 80, "P2Job is built by the host per launch: nothing else holds its layout");
 
 struct BpResult {
   int32_t status;  // 0 breakpoint found; 1 end reached at score 0; <0 error
@@ -438,8 +447,10 @@ struct RingWidenJob {
 };
 void launch_ring_widen(const RingWidenJob* jobs, int njobs, int max_dst_w, int ring_rows, hipStream_t st);
 void launch_p2_blockmax(const int32_t* ring, const int32_t* p2, const P2Job* jobs, int32_t* bmax, int32_t* p2max, int njobs, hipStream_t st);
-void launch_p2_overlap(const int32_t* ring, const int32_t* p2, const P2Job* jobs, const int32_t* p2max, const int32_t* bmax, int32_t* pbmax,
+void launch_p2_overlap(const int32_t* ring, const int32_t* p2, const P2Job* jobs, const int32_t* p2max, const int32_t* bmax,
                        BpResult* res, int njobs, int threads, int max_nblk, DevPen pen, int scope, hipStream_t st);
+// the walk of the jobs with P2Job::exact > 0, one workgroup of `threads` per job (no maxima)
+void launch_p2_exact(const int32_t* ring, const int32_t* p2, const P2Job* jobs, BpResult* res, int njobs, int threads, DevPen pen, int scope, hipStream_t st);
 void launch_base(const uint8_t* seq, int32_t* a32, uint8_t* a8, uint32_t* rle, const BaseJob* jobs, BaseResult* res,
                  int njobs, DevPen pen, bool wide, int ring_rows, hipStream_t st);  // wide: 1024 threads per job instead of 256
 void launch_compact(const uint32_t* rle, const int64_t* off, const int64_t* cap, uint32_t* out, unsigned long long* total,

@@ -1001,11 +1001,18 @@ struct P2Chunk {
   wfm_handle* h; wfm_seqset* S; const DevPen& dp; int scope; const TileCfg& cfg; std::vector<BpJob>& jobs;  // run_p2_phase's arguments
   const std::vector<int>& cand; const std::vector<int64_t>& ring_other; std::vector<BpResult>& res; double& ms_out;
   std::vector<BpResult>& carry; std::vector<char>& has_carry; bool may_continue; std::vector<int>& again;
+  const std::vector<int32_t>& exact_of;  // per candidate: P2Job::exact (0: the job searches)
   std::vector<P2PlanJob> pcand;  // what plan_p2_chunk needs of every candidate
+  std::vector<char> pexact;      // exact_of[i] > 0
   P2ChunkPlan plan;
   size_t i0 = 0, n = 0;
   std::vector<TileJob> tj;
   std::vector<P2Job> pj;
+  // the order of the P2Jobs on the device: the jobs that search first (positions 0 .. ns), then the exact ones; at[q] is job q's position,
+  // pj_dev[at[q]] = pj[q].  The maxima, wfa_p2_blockmax_kernel and wfa_p2_overlap_kernel are the search jobs' alone.
+  std::vector<int> at;
+  std::vector<P2Job> pj_dev;
+  size_t ns = 0, ns_dump = 0;  // ns_dump: search jobs whose row maxima are still in p2max behind the launch (WFM_P2_DUMP)
   std::vector<BpResult> got;
   float ms = 0;
 };
@@ -1014,9 +1021,12 @@ struct P2Chunk {
 void fill_p2_chunk(P2Chunk& c, size_t i0) {
   // the rows of a chunk of jobs may take a quarter of the budget (the rings hold the rest)
   const size_t budget = std::max<size_t>(c.h->mem_budget / 4, (size_t)64 << 20);
-  plan_p2_chunk(c.pcand.data(), c.pcand.size(), i0, P2K, P2ROWS, budget, c.cfg.threads, c.cfg.Wt - 2 * P2K, c.plan);
+  plan_p2_chunk(c.pcand.data(), c.pcand.size(), i0, P2K, P2ROWS, budget, c.cfg.threads, c.cfg.Wt - 2 * P2K, c.plan, c.pexact.data());
   c.i0 = i0; c.n = c.plan.geo.size();
   c.tj.clear(); c.pj.clear();
+  c.at.assign(c.n, 0); c.ns = 0;
+  for (size_t q = 0; q < c.n; ++q) c.ns += !c.pexact[i0 + q];
+  for (size_t q = 0, s = 0, e = c.ns; q < c.n; ++q) c.at[q] = (int)(c.pexact[i0 + q] ? e++ : s++);
   for (size_t q = 0; q < c.n; ++q) {
     const BpJob& j = c.jobs[(size_t)c.cand[i0 + q]];
     const P2Geometry& g = c.plan.geo[q];
@@ -1027,46 +1037,91 @@ void fill_p2_chunk(P2Chunk& c, size_t i0) {
     P2Job pq{};
     pq.ring_in = j.ring_off; pq.p2_off = (int64_t)g.p2_off; pq.width = j.width; pq.koff = j.koff; pq.w2 = (int32_t)g.w2; pq.koff2 = g.koff2;
     pq.pl = j.pl; pq.tl = j.tl; pq.sf = j.resume_s; pq.sr = j.resume_sr; pq.last_fwd = j.last_fwd; pq.sub = j.sub; pq.best0 = j.best0;
-    pq.nblk = (int32_t)g.nblk; pq.bm_off = (int64_t)g.bm_off;
+    pq.nblk = (int32_t)g.nblk; pq.bm_off = (int64_t)g.bm_off; pq.exact = c.exact_of[i0 + q];
     c.tj.push_back(t); c.pj.push_back(pq);
   }
+  c.pj_dev.resize(c.n);
+  for (size_t q = 0; q < c.n; ++q) c.pj_dev[(size_t)c.at[q]] = c.pj[q];
 }
 
 // The chunk on the device: the rows computed ahead, their maxima, the walk; the results back and the time it took
 int launch_p2_chunk(P2Chunk& c) {
   wfm_handle* h = c.h;
   wfm_seqset* S = c.S;
-  const size_t n = c.n, elems = c.plan.elems, bm_elems = c.plan.bm_elems, n_pk = c.plan.tiles.n_pk;
+  const size_t n = c.n, ns = c.ns, elems = c.plan.elems, bm_elems = c.plan.bm_elems, n_pk = c.plan.tiles.n_pk;
   const std::vector<TileTask>& tasks = c.plan.tiles.tasks;
   const int threads_c = c.plan.threads_c;
-  if (h->p2rows.ensure(elems + 16) || h->p2max.ensure(n * 2 * P2ROWS * 5) || h->p2bmax.ensure(bm_elems + 16) || h->p2pbmax.ensure(bm_elems + 16) ||
+  if (h->p2rows.ensure(elems + 16) || h->p2max.ensure(ns * 2 * P2ROWS * 5) || h->p2bmax.ensure(bm_elems + 16) ||
       h->p2jobs.ensure(n) || h->tilejobs.ensure(n) || h->tiletasks.ensure(tasks.size()) || h->bpres.ensure(std::max(n, c.jobs.size()))) {
     h->err = "out of device memory (phase-2 rows)"; return WFM_E_NOMEM;
   }
   HIPCHK(h, hipMemcpyAsync(h->tilejobs.p, c.tj.data(), n * sizeof(TileJob), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(h->p2jobs.p, c.pj.data(), n * sizeof(P2Job), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->p2jobs.p, c.pj_dev.data(), n * sizeof(P2Job), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(h->tiletasks.p, tasks.data(), tasks.size() * sizeof(TileTask), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipEventRecord(h->ev0, h->stream));
   bool any_cut = false;
   for (const TileJob& t : c.tj) any_cut |= t.sub != SUB_NONE;
   if (n_pk) launch_tile2_p2(S->d_pk, h->ring.p, h->tilejobs.p, h->tiletasks.p, (int)n_pk, threads_c, h->p2rows.p, h->stream);
   if (tasks.size() > n_pk) launch_tile_p2(S->d_seq, h->ring.p, h->tilejobs.p, h->tiletasks.p + n_pk, (int)(tasks.size() - n_pk), threads_c, h->p2rows.p, any_cut, h->stream);
-  launch_p2_blockmax(h->ring.p, h->p2rows.p, h->p2jobs.p, h->p2bmax.p, h->p2max.p, (int)n, h->stream);
   static const int p2_threads = getenv("WFM_P2_THREADS") ? atoi(getenv("WFM_P2_THREADS")) : 0;  // (a once-per-process switch: it stays static)
-  launch_p2_overlap(h->ring.p, h->p2rows.p, h->p2jobs.p, h->p2max.p, h->p2bmax.p, h->p2pbmax.p, h->bpres.p, (int)n,
-                    p2_threads > 0 ? p2_threads : 1024, (int)(c.plan.maxw2 >> 6) + 1, c.dp, c.scope, h->stream);  // 16 waves over the 5 x P2G (test, component) scans of a round and their rows
+  static const int p2x_threads = getenv("WFM_P2_EXACT_THREADS") ? atoi(getenv("WFM_P2_EXACT_THREADS")) : 0;  // (likewise)
+  // the jobs that search (positions 0 .. ns of p2jobs): their maxima, then the walk that prunes by them.  16 waves over the 5 x P2G (test, component) scans of a round and their rows
+  auto launch_search = [&](size_t cnt) {
+    launch_p2_blockmax(h->ring.p, h->p2rows.p, h->p2jobs.p, h->p2bmax.p, h->p2max.p, (int)cnt, h->stream);
+    launch_p2_overlap(h->ring.p, h->p2rows.p, h->p2jobs.p, h->p2max.p, h->p2bmax.p, h->bpres.p, (int)cnt,
+                      p2_threads > 0 ? p2_threads : 1024, (int)(c.plan.maxw2 >> 6) + 1, c.dp, c.scope, h->stream);
+  };
+  if (ns) launch_search(ns);
+  // the exact jobs behind them: no maxima
+  launch_p2_exact(h->ring.p, h->p2rows.p, h->p2jobs.p + ns, h->bpres.p + ns, (int)(n - ns), p2x_threads > 0 ? p2x_threads : p2_exact_threads(c.plan.maxw2), c.dp, c.scope, h->stream);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-  c.got.resize(n);
-  HIPCHK(h, hipMemcpyAsync(c.got.data(), h->bpres.p, n * sizeof(BpResult), hipMemcpyDeviceToHost, h->stream));
+  std::vector<BpResult> dev(n);
+  HIPCHK(h, hipMemcpyAsync(dev.data(), h->bpres.p, n * sizeof(BpResult), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   HIPCHK(h, hipEventElapsedTime(&c.ms, h->ev0, h->ev1));
-  c.ms_out += c.ms;
-  if (h->call_base) {
+  auto note_busy = [&](float ms) {  // (between ev0 and ev1, as just recorded)
+    if (!h->call_base) return hipSuccess;
     float t0 = 0;
-    HIPCHK(h, hipEventElapsedTime(&t0, h->call_base, h->ev0));
-    h->bp_iv.emplace_back(t0, t0 + c.ms);
+    const hipError_t e = hipEventElapsedTime(&t0, h->call_base, h->ev0);
+    if (e == hipSuccess) h->bp_iv.emplace_back(t0, t0 + ms);
+    return e;
+  };
+  HIPCHK(h, note_busy(c.ms));
+  c.got.resize(n);
+  for (size_t q = 0; q < n; ++q) c.got[q] = dev[(size_t)c.at[q]];
+  c.ns_dump = ns;
+  h->tile_ctr[WFM_TC_P2_EXACT] += n - ns;
+  // An exact job without a hit within its reach: once more from the same state as a job that searches (exact = 0, so this cannot come round
+  // again), over the rows that are still there.  The maxima of the chunk's search jobs have been read; theirs take the buffers' front.
+  std::vector<size_t> miss;
+  for (size_t q = 0; q < n; ++q) if (c.got[q].status == WFM_DEV_P2_EXACT_MISS) miss.push_back(q);
+  if (!miss.empty()) {
+    h->tile_ctr[WFM_TC_P2_EXACT_MISSES] += miss.size();
+    std::vector<P2Job> mj;
+    size_t bm = 0;
+    for (size_t q : miss) {
+      P2Job& pq = c.pj[q];
+      pq.exact = 0; pq.bm_off = (int64_t)bm;
+      bm += (size_t)pq.nblk * 2 * P2ROWS * 5;
+      mj.push_back(pq);
+    }
+    if (h->p2max.ensure(mj.size() * 2 * P2ROWS * 5) || h->p2bmax.ensure(bm + 16)) { h->err = "out of device memory (phase-2 maxima)"; return WFM_E_NOMEM; }
+    HIPCHK(h, hipMemcpyAsync(h->p2jobs.p, mj.data(), mj.size() * sizeof(P2Job), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+    launch_search(mj.size());
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+    HIPCHK(h, hipMemcpyAsync(dev.data(), h->bpres.p, mj.size() * sizeof(BpResult), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    float ms2 = 0;
+    HIPCHK(h, hipEventElapsedTime(&ms2, h->ev0, h->ev1));
+    HIPCHK(h, note_busy(ms2));
+    c.ms += ms2;
+    for (size_t m = 0; m < miss.size(); ++m) c.got[miss[m]] = dev[m];
+    c.ns_dump = 0;  // (the maxima at the buffers' front are no longer the chunk's search jobs')
   }
+  c.ms_out += c.ms;
   return WFM_OK;
 }
 
@@ -1074,9 +1129,13 @@ int launch_p2_chunk(P2Chunk& c) {
 int dump_p2_job(P2Chunk& c) {
   wfm_handle* h = c.h;
   const std::vector<BpResult>& got = c.got;
-  const size_t q = std::min<size_t>((size_t)c.cfg.p2_dump, c.n - 1);
+  // (only a job that searches has maxima: the one at position p2_dump among them, in the order of the device)
+  if (c.ns_dump == 0) { fprintf(stderr, "[wfm] p2 dump: no job of this chunk of %zu searches with its row maxima at hand (%zu take the exact walk)\n", c.n, c.n - c.ns); return WFM_OK; }
+  const size_t pos = std::min<size_t>((size_t)c.cfg.p2_dump, c.ns_dump - 1);
+  size_t q = 0;
+  while ((size_t)c.at[q] != pos) ++q;
   std::vector<int32_t> rm((size_t)2 * P2ROWS * 5);
-  HIPCHK(h, hipMemcpy(rm.data(), h->p2max.p + q * 2 * P2ROWS * 5, rm.size() * 4, hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(rm.data(), h->p2max.p + pos * 2 * P2ROWS * 5, rm.size() * 4, hipMemcpyDeviceToHost));
   const P2Job& pjq = c.pj[q];
   fprintf(stderr, "[wfm] p2 dump job %zu: pl %d tl %d sf %d sr %d last_fwd %d sub %d w2 %d nblk %d -> status %d score %d (fwd %d rev %d comp %d k %d) rounds %d\n", q, pjq.pl, pjq.tl, pjq.sf,
           pjq.sr, pjq.last_fwd, pjq.sub, pjq.w2, pjq.nblk, got[q].status, got[q].score, got[q].score_fwd, got[q].score_rev, got[q].comp, got[q].k_fwd, got[q].pad_);
@@ -1096,8 +1155,14 @@ void print_p2_chunk(const P2Chunk& c) {
   int more = 0;
   double tk = 0, tc = 0, rd = 0; uint32_t tkmax = 0; int rdmax = 0;
   for (const BpResult& r : got) { more += r.status == WFM_DEV_P2_MORE; tk += r.ticks_p2; tc += r.ticks_p1; rd += r.pad_; tkmax = std::max(tkmax, r.ticks_p2); rdmax = std::max(rdmax, r.pad_); }
-  fprintf(stderr, "[wfm] phase 2 from rows computed ahead: %zu jobs, widest %zu columns, %zu tiles of %d threads, %.3f ms, %d left to the step kernel; walk per job: %.1f rounds (max %d), %.0f us (max %.0f), of which cells stage %.0f us\n",
-          n, c.plan.maxw2, c.plan.tiles.tasks.size(), c.plan.threads_c, c.ms, more, rd / n, rdmax, tk / n / 100.0, tkmax / 100.0, tc / n / 100.0);
+  double tests = 0; int tests_max = 0;  // the rows the walk went through behind the state it began at
+  for (const BpResult& r : got) { tests += r.steps - r.steps_p1; tests_max = std::max(tests_max, r.steps - r.steps_p1); }
+  size_t missed = 0;  // (a job that missed has searched since: pj[q].exact is 0 again, and it was not among the chunk's search jobs)
+  for (size_t q = 0; q < n; ++q) missed += pj[q].exact == 0 && (size_t)c.at[q] >= c.ns;
+  fprintf(stderr, "[wfm] phase 2 from rows computed ahead: %zu jobs, widest %zu columns, %zu tiles of %d threads, %.3f ms, %d left to the step kernel; walk per job: %.1f rounds (max %d), %.0f us (max %.0f), of which cells stage %.0f us; "
+          "%.1f tests (max %d); exact walk %.1f %% of the jobs, missed %.1f %%\n",
+          n, c.plan.maxw2, c.plan.tiles.tasks.size(), c.plan.threads_c, c.ms, more, rd / n, rdmax, tk / n / 100.0, tkmax / 100.0, tc / n / 100.0, tests / n, tests_max,
+          100.0 * (n - c.ns) / n, 100.0 * missed / n);
   size_t qs = 0;
   for (size_t q = 0; q < n; ++q) if (got[q].ticks_p2 > got[qs].ticks_p2) qs = q;
   fprintf(stderr, "[wfm]   slowest walk: pl %d tl %d sub %d w2 %d nblk %d: %d rounds, %.0f us = listing %.0f + cells %.0f (incl. listing) + pick %.0f, %u blocks listed, status %d\n", pj[qs].pl, pj[qs].tl,
@@ -1145,12 +1210,13 @@ int continue_p2_chunk(P2Chunk& c) {
 // diagonal; finishing them step by step in wfa_bp_kernel was half of C2's device time.)
 int run_p2_phase(wfm_handle* h, wfm_seqset* S, const DevPen& dp, int scope, const TileCfg& cfg, std::vector<BpJob>& jobs,
                  const std::vector<int>& cand, const std::vector<int64_t>& ring_other, std::vector<BpResult>& res, double& ms_out,
-                 std::vector<BpResult>& carry, std::vector<char>& has_carry, bool may_continue, std::vector<int>& again) {
+                 std::vector<BpResult>& carry, std::vector<char>& has_carry, bool may_continue, std::vector<int>& again, const std::vector<int32_t>& exact_of) {
   if (cand.empty()) return WFM_OK;
-  P2Chunk c{h, S, dp, scope, cfg, jobs, cand, ring_other, res, ms_out, carry, has_carry, may_continue, again};
-  for (int q : cand) {
-    const BpJob& j = jobs[(size_t)q];
+  P2Chunk c{h, S, dp, scope, cfg, jobs, cand, ring_other, res, ms_out, carry, has_carry, may_continue, again, exact_of};
+  for (size_t i = 0; i < cand.size(); ++i) {
+    const BpJob& j = jobs[(size_t)cand[i]];
     c.pcand.push_back(P2PlanJob{j.pl, j.tl, j.sub, j.resume_s, j.resume_sr, j.packed});
+    c.pexact.push_back((char)(exact_of[i] > 0));
   }
   for (size_t i0 = 0; i0 < cand.size(); i0 += c.n) {
     fill_p2_chunk(c, i0);
@@ -1175,6 +1241,7 @@ struct Knobs {
   bool use_bound = use_hints && num("WFM_BOUND", 1) != 0;
   int slack_env = num("WFM_SUB_SLACK", -1);  // tests: < 0 default, >= 2^28 none
   bool ring3_on = num("WFM_TILE_RING3", 1) != 0, p2_on = num("WFM_P2", 1) != 0;
+  bool p2_exact = num("WFM_P2_EXACT", 1) != 0;  // 0: every job of phase 2 searches (wfa_p2_overlap_kernel), also the ones that stand at their own score (P2Job::exact)
   int p2_rounds = std::max(1, num("WFM_P2_ROUNDS", 64));
   int fine_margin = num("WFM_TILE_FINE_MARGIN", 48);
   int coarse_min_blocks = num("WFM_TILE_COARSE_MIN_BLOCKS", 32), coarse_max_jobs = num("WFM_TILE_COARSE_MAX_JOBS", 128);
@@ -1588,11 +1655,20 @@ int run_chunk_p2(AlignCall& c) {
   k.rest.clear(); k.more_set.clear();
   std::vector<int> cand;
   std::vector<int64_t> other;
+  std::vector<int32_t> exact_of;  // per candidate: P2Job::exact in the first round of rows (a later round starts behind the planned end: it searches)
   std::vector<char> is_cand(k.jobs.size(), 0);
   if (c.knobs.p2_on && c.tcfg.reg && c.tcfg.exact)
     for (size_t q = 0; q < k.tiled.size(); ++q) {
       const BpJob& j = k.jobs[(size_t)k.tiled[q]];
-      if (j.resume_s >= 0 && j.resume_sr >= 0) { cand.push_back(k.tiled[q]); other.push_back(k.ring2[q]); is_cand[(size_t)k.tiled[q]] = 1; }
+      if (j.resume_s >= 0 && j.resume_sr >= 0) {
+        cand.push_back(k.tiled[q]); other.push_back(k.ring2[q]); is_cand[(size_t)k.tiled[q]] = 1;
+        // the exact walk (P2Job::exact): the job left the tile phase at its planned end, the state whose scores sum to its own score (only jobs
+        // on the packed kernel, on a ring no budget shaped, with their bound are planned: plan_chunk).  The pick's order is the reference's under
+        // o2 >= o1 >= 0 (wfa_p2_overlap_kernel); other penalties search.  (A job that resumed on a wider ring sits behind plan_from's end.)
+        const bool exact = c.knobs.p2_exact && q < k.plan_from.size() && k.plan_from[q] > 0 && j.resume_s + j.resume_sr == k.plan_from[q] && j.best0 == 0 &&
+                           c.dp.o2 >= c.dp.o1 && c.dp.o1 >= 0;
+        exact_of.push_back(exact ? k.plan_from[q] : 0);
+      }
     }
   double pms = 0;
   k.carry.assign(k.jobs.size(), BpResult{});
@@ -1601,7 +1677,8 @@ int run_chunk_p2(AlignCall& c) {
   std::vector<int64_t> other_r = other;
   for (int round = 1; !cand_r.empty(); ++round) {
     again.clear();
-    const int rc = run_p2_phase(h, c.S, c.dp, c.scope, c.tcfg, k.jobs, cand_r, other_r, k.res, pms, k.carry, k.has_carry, round < c.knobs.p2_rounds, again);
+    if (round > 1) exact_of.assign(cand_r.size(), 0);
+    const int rc = run_p2_phase(h, c.S, c.dp, c.scope, c.tcfg, k.jobs, cand_r, other_r, k.res, pms, k.carry, k.has_carry, round < c.knobs.p2_rounds, again, exact_of);
     if (rc != WFM_OK) return rc;
     std::vector<int> c2; std::vector<int64_t> o2;
     for (int a : again) {
@@ -2107,7 +2184,7 @@ void wfm_destroy(wfm_handle_t* h) {
   if (h->stage) { (void)hipHostFree(h->stage); h->stage = nullptr; h->stage_cap = 0; }
   for (int k = 0; k < 2; ++k)
     if (h->cspin[k]) { (void)hipHostFree(h->cspin[k]); h->cspin[k] = nullptr; }
-  h->p2rows.release(); h->p2max.release(); h->p2bmax.release(); h->p2pbmax.release(); h->p2jobs.release(); h->widenjobs.release(); h->keeptasks.release(); h->restoretasks.release(); h->restoreres.release();
+  h->p2rows.release(); h->p2max.release(); h->p2bmax.release(); h->p2jobs.release(); h->widenjobs.release(); h->keeptasks.release(); h->restoretasks.release(); h->restoreres.release();
   h->bpjobs.release(); h->bpres.release(); h->bsjobs.release(); h->bsres.release();
   h->b2tjobs.release(); h->b2ttasks.release(); h->b2tkeys.release(); h->b2toffs.release(); h->b2tactive.release();
   h->i64a.release(); h->i64b.release(); h->i64c.release(); h->i32a.release(); h->seqflags.release(); h->flagjobs.release(); h->gathertasks.release(); h->scratch.release(); h->outblk.release(); h->optrows.release(); h->total.release();

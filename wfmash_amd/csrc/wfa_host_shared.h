@@ -125,7 +125,7 @@ struct wfm_handle {
   wfm::DevBuf<wfm::TileJob> tilejobs;
   wfm::DevBuf<wfm::TileTask> tiletasks;
   wfm::DevBuf<int32_t> tilemak;
-  wfm::DevBuf<int32_t> p2rows, p2max, p2bmax, p2pbmax;  // phase 2 from rows computed ahead (P2Job)
+  wfm::DevBuf<int32_t> p2rows, p2max, p2bmax;  // phase 2 from rows computed ahead (P2Job)
   wfm::DevBuf<wfm::P2Job> p2jobs;
   wfm::DevBuf<wfm::RingWidenJob> widenjobs;
   wfm::DevBuf<wfm::KeepTask> keeptasks;        // parent reuse: the keeps behind a chunk of tile blocks, the restores at a look of the host and what they found

@@ -952,26 +952,6 @@ __global__ __launch_bounds__(256) void wfa_p2_blockmax_kernel(const int32_t* __r
 // tests in the reference's order -- the data-parallel half of a test (smallest diagonal per (row of the other direction,
 // component) on which the offsets meet, pruned by the best breakpoint so far and by the row maxima) and one lane's replay of
 // the nested conditions, exactly as wfa_bp_kernel does them -- but no row is computed between two tests.
-// Running maxima of the block maxima over the rows of a direction: pb[row r] = max over rows 0 .. r.  What a test
-// prunes with (whole blocks of the tested row, then single diagonals) must only be an upper bound of what the rows in its
-// scope hold in a block; the rows before them hold less almost everywhere, so the bound loses little and costs one read.
-__global__ __launch_bounds__(256) void wfa_p2_prefixmax_kernel(const P2Job* __restrict__ jobs, const int32_t* __restrict__ bmax,
-                                                              int32_t* __restrict__ pbmax, int njobs) {
-  const int job = blockIdx.y;
-  const P2Job J = jobs[job];
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;  // (direction, component, block)
-  const int per_dir = 5 * J.nblk;
-  if (e >= 2 * per_dir) return;
-  const int d = e / per_dir, rest = e % per_dir;  // rest = cc * nblk + b
-  const int32_t* src = bmax + J.bm_off + (int64_t)d * P2ROWS * per_dir + rest;
-  int32_t* dst = pbmax + J.bm_off + (int64_t)d * P2ROWS * per_dir + rest;
-  int run = 0;
-  for (int r = 0; r < P2ROWS; ++r) {
-    run = max(run, src[(int64_t)r * per_dir]);
-    dst[(int64_t)r * per_dir] = run;
-  }
-}
-
 __device__ unsigned long long g_p2cnt[8];  // WFM_P2_COUNT diagnostics: tests, tests with candidates, pairs listed, blocks tested cell by cell, pairs that met, most pairs in a round, most blocks one wave tested in a round
 
 // The loop for one workgroup, P2G tests per round.  Every stage of a round is spread over the threads; the stages are
@@ -992,13 +972,12 @@ constexpr int P2CM = 128;     // widest rows (in blocks of 64 diagonals) whose c
                               // (with antidiagonal maxima those prune well on their own; C3's rows of 200 blocks: 13.9 -> 12.7 ms per step without)
 __global__ __launch_bounds__(1024) void wfa_p2_overlap_kernel(const int32_t* __restrict__ ring, const int32_t* __restrict__ p2,
                                                              const P2Job* __restrict__ jobs, const int32_t* __restrict__ p2max,
-                                                             const int32_t* __restrict__ bmax, const int32_t* __restrict__ pbmax,
+                                                             const int32_t* __restrict__ bmax,
                                                              BpResult* __restrict__ results, DevPen pen, int scope, int count, int work_cap, int cm_max) {
   const int job = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nw = blockDim.x >> 6;
   const P2Job J = jobs[job];
   const int nblk = J.nblk;
   const int32_t* bmj = bmax + J.bm_off;
-  (void)pbmax;
   __shared__ int s_mink[P2G][P2ENT];
   __shared__ int s_k[P2G][4];   // per test: [2] = some pair can still matter
   __shared__ unsigned s_pmask[P2G][5];  // per (test, component): the rows of the other direction (bit i = row s1 - i) that can still matter
@@ -1334,6 +1313,131 @@ __global__ __launch_bounds__(1024) void wfa_p2_overlap_kernel(const int32_t* __r
   }
 }
 
+// The walk of a job that stands at its own score (P2Job::exact = sf + sr = S_own; DESIGN.md section 5, "the exact walk").  The reference takes a
+// hit only when its score is strictly below the best in hand and no pair of rows is cheaper than S_own: its final breakpoint is the FIRST hit of
+// score exactly S_own in its walk order -- dearer hits before it are replaced, nothing after it can replace it (and its loop cannot end before
+// it: it ends when no later pair can be cheaper than the best in hand, which is above S_own until then).  At the test u states behind the job's
+// (s0 + s1 = S_own + u) the pair (row s1 - i of the other direction, component cc) has score S_own iff i = u - gopen(cc): at most one row per
+// component, no list of pairs to prune, so no maxima.  The rounds are wfa_p2_overlap_kernel's: P2G tests side by side, a barrier, the pick in
+// track order.  With 0 <= i < scope the hit lies at u <= scope - 1 + max(o1, o2); a job without one by then (or by the last row computed ahead)
+// leaves with WFM_DEV_P2_EXACT_MISS and the host sends it through the ordinary walk.  The host only marks jobs exact under o2 >= o1 >= 0.
+__global__ __launch_bounds__(1024) void wfa_p2_exact_kernel(const int32_t* __restrict__ ring, const int32_t* __restrict__ p2, const P2Job* __restrict__ jobs,
+                                                           BpResult* __restrict__ results, DevPen pen, int scope, int reach) {
+  const int job = blockIdx.x, tid = threadIdx.x;
+  const P2Job J = jobs[job];
+  __shared__ int s_mink[P2G * 5];  // per (test, component) of the round: the smallest diagonal of the tested row on which the offsets meet
+  __shared__ int s_end[2];         // [0]: 0 running, 1 hit, 2 no hit within reach; [1]: tests done
+  __shared__ int s_bp[8];
+  __shared__ unsigned long long s_cells;
+  if (tid == 0) { s_end[0] = 0; s_end[1] = 0; s_cells = 0; }
+  if (tid < 8) s_bp[tid] = 0;
+  __syncthreads();
+  const int pl = J.pl, tl = J.tl, kinv = tl - pl;
+  const Rng RG = make_rng(pl, tl, J.sub);
+  const int n_tests = min(min(scope + max(pen.o1, pen.o2), P2TESTS), reach);  // tests u = 0 .. scope - 1 + max(o1, o2), as far as their rows are there
+  // test u of the track: the direction that stepped last is tested first, then the two alternate
+  auto test_of = [&](int u, int& d0, int& s0, int& s1) {
+    const int first = J.last_fwd ? 0 : 1;
+    const int a = first == 0 ? J.sf : J.sr, b = first == 0 ? J.sr : J.sf;
+    if ((u & 1) == 0) { d0 = first; s0 = a + u / 2; s1 = b + u / 2; }
+    else { d0 = first ^ 1; s0 = b + (u + 1) / 2; s1 = a + (u - 1) / 2; }
+  };
+  // the one row of the other direction whose pair with the tested row in component cc has score `exact`: i rows behind s1 (-1: none)
+  auto row_of = [&](int s0, int s1, int cc) {
+    const int i = s0 + s1 - bp_gap_open(pen, cc) - J.exact;
+    return (i >= 0 && i < scope && s1 - i >= 0) ? i : -1;
+  };
+  const long long t_begin = wall_clock64();
+  long long t_cells = 0, t_pick = 0;
+  int rounds = 0;
+  for (;;) {
+    const int u0 = s_end[1];
+    if (s_end[0] != 0) break;
+    ++rounds;
+    const int ng = min(P2G, n_tests - u0);
+    if (tid < P2G * 5) s_mink[tid] = INT32_MAX;
+    __syncthreads();
+    const long long t_c0 = wall_clock64();
+    // ---- scan: every (test, component) of the round, the whole workgroup over the mirrored part of its two rows (no exit at a hit: the loads
+    // of a thread do not wait for one another)
+    for (int it = 0; it < ng * 5; ++it) {
+      const int g = it / 5, cc = it % 5;
+      int d0, s0, s1;
+      test_of(u0 + g, d0, s0, s1);
+      const int i = row_of(s0, s1, cc);
+      if (i < 0) continue;
+      const int si = s1 - i;
+      const int ka = max(rng_lo(RG, s0), kinv - rng_hi(RG, si)), kb = min(rng_hi(RG, s0), kinv - rng_lo(RG, si));
+      if (ka > kb) continue;
+      const int32_t* R0 = p2_row(ring, p2, J, d0, cc, s0);
+      const int32_t* R1 = p2_row(ring, p2, J, d0 ^ 1, cc, si) + kinv;  // R1[-k0]: the mirrored diagonal
+      int mk = INT32_MAX;
+      // four diagonals a thread at a time, their eight loads in flight together (a scan is a handful of round trips to the rows, not one a diagonal)
+      for (int kk = ka + tid; kk <= kb; kk += 4 * (int)blockDim.x) {
+        int o0[4], o1[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int k0 = kk + j * (int)blockDim.x;
+          o0[j] = k0 <= kb ? R0[k0] : WF_NULL;
+          o1[j] = k0 <= kb ? R1[-k0] : WF_NULL;
+        }
+#pragma unroll
+        for (int j = 3; j >= 0; --j)
+          if (o0[j] + o1[j] >= tl) mk = min(mk, kk + j * (int)blockDim.x);  // (a NULL offset is -2^30: the sum stays far below)
+      }
+      if (mk != INT32_MAX) atomicMin(&s_mink[it], mk);
+    }
+    __syncthreads();
+    t_cells += wall_clock64() - t_c0;
+    const long long t_p0 = wall_clock64();
+    // ---- pick: the first test in track order with a hit; among its hits the reference's order, i ascending, then D2, I2, D1, I1, M
+    if (tid == 0) {
+      unsigned long long cells = 0;
+      int status = 0, u = u0;
+      for (int g = 0; g < ng; ++g, ++u) {
+        int d0, s0, s1;
+        test_of(u, d0, s0, s1);
+        int key = INT32_MAX;
+        for (int cc = 0; cc < 5; ++cc) {
+          if (s_mink[g * 5 + cc] == INT32_MAX) continue;
+          const int oi = cc == C_D2 ? 0 : (cc == C_I2 ? 1 : (cc == C_D1 ? 2 : (cc == C_I1 ? 3 : 4)));
+          key = min(key, row_of(s0, s1, cc) * 5 + oi);
+        }
+        if (key != INT32_MAX) {
+          const int i = key / 5, oi = key % 5, si = s1 - i;
+          const int cc = oi == 0 ? C_D2 : (oi == 1 ? C_I2 : (oi == 2 ? C_D1 : (oi == 3 ? C_I1 : C_M)));
+          const int k0 = s_mink[g * 5 + cc], k1 = kinv - k0;
+          if (d0 == 0) { s_bp[1] = s0; s_bp[2] = si; s_bp[3] = k0; s_bp[4] = p2_row(ring, p2, J, 0, cc, s0)[k0]; }
+          else         { s_bp[1] = si; s_bp[2] = s0; s_bp[3] = k1; s_bp[4] = p2_row(ring, p2, J, 0, cc, si)[k1]; }
+          s_bp[5] = cc;
+          status = 1;
+          break;
+        }
+        // the other direction advances by one row (computed ahead: only the bookkeeping is left)
+        const int sn = s1 + 1;
+        cells += (unsigned long long)(rng_hi(RG, sn) - rng_lo(RG, sn) + 1);
+      }
+      if (status == 0 && u >= n_tests) status = 2;
+      s_end[0] = status; s_end[1] = u;
+      s_cells += cells;
+    }
+    __syncthreads();
+    t_pick += wall_clock64() - t_p0;
+  }
+  if (tid == 0) {
+    BpResult r;
+    const bool hit = s_end[0] == 1;
+    r.status = hit ? 0 : WFM_DEV_P2_EXACT_MISS;
+    r.score = J.exact; r.score_fwd = s_bp[1]; r.score_rev = s_bp[2]; r.k_fwd = s_bp[3]; r.off_fwd = s_bp[4]; r.comp = hit ? s_bp[5] : -1;
+    r.steps = J.sf + J.sr + s_end[1];  // the rows up to the test that hit
+    r.cells = s_cells;
+    r.steps_p1 = J.sf + J.sr;
+    r.ticks_p1 = (uint32_t)t_cells; r.ticks_p2 = (uint32_t)(wall_clock64() - t_begin); r.pad_ = rounds;  // diagnostics (WFM_DEBUG)
+    r.ticks_list = 0; r.ticks_pick = (uint32_t)t_pick; r.work_items = 0; r.pad2_ = 0;
+    results[job] = r;
+  }
+}
+
 // ---------------------------------------------------------------------------
 // An upper bound of a root's score: the cost of ONE valid global alignment, found greedily
 // ---------------------------------------------------------------------------
@@ -1658,13 +1762,19 @@ void launch_ring_widen(const RingWidenJob* jobs, int njobs, int max_dst_w, int r
 void launch_p2_blockmax(const int32_t* ring, const int32_t* p2, const P2Job* jobs, int32_t* bmax, int32_t* p2max, int njobs, hipStream_t st) {
   hipLaunchKernelGGL(wfa_p2_blockmax_kernel, dim3(njobs * 2 * P2ROWS), dim3(256), 0, st, ring, p2, jobs, bmax, p2max);
 }
-void launch_p2_overlap(const int32_t* ring, const int32_t* p2, const P2Job* jobs, const int32_t* p2max, const int32_t* bmax, int32_t* pbmax,
+void launch_p2_overlap(const int32_t* ring, const int32_t* p2, const P2Job* jobs, const int32_t* p2max, const int32_t* bmax,
                        BpResult* res, int njobs, int threads, int max_nblk, DevPen pen, int scope, hipStream_t st) {
   static const int count = getenv("WFM_P2_COUNT") ? atoi(getenv("WFM_P2_COUNT")) : 0;
   (void)max_nblk;  // (the walk prunes with each row's own block maxima; the running maxima over the rows are not needed any more)
   static const int work_cap = getenv("WFM_P2_WORKCAP") ? std::max(1, std::min(P2WORK, atoi(getenv("WFM_P2_WORKCAP")))) : P2WORK;  // (tests: a small list forces the overflow path)
   static const int cm_max = getenv("WFM_P2_COLMAX") ? std::max(0, std::min(P2CM, atoi(getenv("WFM_P2_COLMAX")))) : P2CM;  // rows up to this many blocks get column maxima (0: none)
-  hipLaunchKernelGGL(wfa_p2_overlap_kernel, dim3(njobs), dim3(threads), 0, st, ring, p2, jobs, p2max, bmax, pbmax, res, pen, scope, count, work_cap, cm_max);
+  hipLaunchKernelGGL(wfa_p2_overlap_kernel, dim3(njobs), dim3(threads), 0, st, ring, p2, jobs, p2max, bmax, res, pen, scope, count, work_cap, cm_max);
+}
+void launch_p2_exact(const int32_t* ring, const int32_t* p2, const P2Job* jobs, BpResult* res, int njobs, int threads, DevPen pen, int scope, hipStream_t st) {
+  if (njobs <= 0) return;
+  const char* e = getenv("WFM_P2_EXACT_REACH");  // (tests: a walk of this many tests at the most, so that jobs miss and go through the search; read per launch)
+  const int reach = e ? std::max(1, atoi(e)) : P2TESTS;
+  hipLaunchKernelGGL(wfa_p2_exact_kernel, dim3(njobs), dim3(std::max(64, std::min(1024, threads & ~63))), 0, st, ring, p2, jobs, res, pen, scope, reach);
 }
 void p2_counters(unsigned long long* out) { (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_p2cnt), sizeof(unsigned long long) * 8); }
 void launch_base(const uint8_t* seq, int32_t* a32, uint8_t* a8, uint32_t* rle, const BaseJob* jobs, BaseResult* res,

@@ -417,7 +417,10 @@ struct P2ChunkPlan {
   TileChunkPlan tiles;          // (core_c, tasks, n_pk; jobs are numbered within the chunk)
 };
 // rows: P2K, rows_bm: P2ROWS (wfa_device.h); budget: bytes the rows of a chunk may take; core: Wt - 2 P2K
-inline void plan_p2_chunk(const P2PlanJob* cand, size_t n_cand, size_t i0, int rows, int rows_bm, size_t budget, int threads, int core, P2ChunkPlan& p) {
+// exact: per candidate, nonzero where the job takes the exact walk (P2Job::exact) -- it reads no maxima, so none are laid out for it (bm_off 0);
+// nullptr: every job searches
+inline void plan_p2_chunk(const P2PlanJob* cand, size_t n_cand, size_t i0, int rows, int rows_bm, size_t budget, int threads, int core, P2ChunkPlan& p,
+                          const char* exact = nullptr) {
   p.geo.clear(); p.elems = 0; p.bm_elems = 0; p.maxw2 = 0;
   p.tiles.tasks.clear(); p.tiles.tasks_by.clear();
   for (size_t i = i0; i < n_cand; ++i) {
@@ -430,7 +433,7 @@ inline void plan_p2_chunk(const P2PlanJob* cand, size_t n_cand, size_t i0, int r
     g.koff2 = ((-L + 4) + 3) & ~3;  // column of diagonal 0: a multiple of 4, >= 4 columns of margin
     g.w2 = ((size_t)(R + g.koff2 + 8) + 3) & ~(size_t)3;
     g.nblk = (g.w2 >> 6) + 1;
-    const size_t need = g.w2 * 2 * 5 * rows, need_bm = g.nblk * 2 * rows_bm * 5;
+    const size_t need = g.w2 * 2 * 5 * rows, need_bm = (exact && exact[i]) ? 0 : g.nblk * 2 * rows_bm * 5;
     if (!p.geo.empty() && (p.elems + need + 2 * (p.bm_elems + need_bm)) * 4 > budget) break;
     p.maxw2 = std::max(p.maxw2, g.w2);
     g.p2_off = p.elems; g.bm_off = p.bm_elems;
@@ -460,6 +463,14 @@ inline void plan_p2_chunk(const P2PlanJob* cand, size_t n_cand, size_t i0, int r
       append_tile_tasks(p.tiles, (int)q, d, tiles_for(L, R, p.tiles.core_c), p.tiles.core_c, cand[i0 + q].packed != 0);
     }
   close_task_list(p.tiles);
+}
+
+// The workgroup of wfa_p2_exact_kernel for a chunk whose widest rows hold maxw2 columns: a thread takes four diagonals of a scan at a time, so
+// this many threads pass the widest row in one stride; narrower chunks (the deep levels: thousands of jobs of a few hundred columns) get
+// small workgroups, several of which share a compute unit
+inline int p2_exact_threads(size_t maxw2) {
+  const size_t t = ((maxw2 + 3) / 4 + 63) / 64 * 64;
+  return (int)std::min<size_t>(1024, std::max<size_t>(128, t));
 }
 
 // ---- base jobs (run_base_jobs) ----
