@@ -488,6 +488,40 @@ int  wfm_lift_runs(wfm_handle_t* h, const wfm_liftset_t* s, const wfm_cov_prob_t
                    wfm_lift_t** lifts, size_t* n_lifts, wfm_liftcall_t* per);
 void wfm_free_lifts(wfm_lift_t* p);
 
+/* ---- the blocks and gaps of a UCSC chain from the runs of many records ----
+ * A chain is a compaction of the runs: ungapped blocks and the pair of gap lengths between two of them.  wfm_chain_runs makes them on the
+ * device (wfmash_amd/csrc/wfa_chain.hip).  The pattern is the target, the text the query as aligned; nothing goes up but runs.
+ *
+ * probs[i] = {runs_off, n_runs, flags}, runs as wfm_coverage_add takes them.  Block k of a problem is its k-th maximal stretch of =/X runs:
+ * size = the stretch's columns, eq = the = columns among them, dt = the D bases and dq = the I bases between block k and block k + 1.  Any
+ * number of I and D runs may lie between two blocks, in any order: 2I3D gives (3, 2), 10 000 alternating 1I1D give (10000, 10000).  The last
+ * block of a problem has dt = dq = 0.  per[i] = {flags, n_runs, first, count, lead_dt, lead_dq, trail_dt, trail_dq, eq, x} locates problem
+ * i's blocks, problems in problem order; lead_* and trail_* are the D and I bases before the first block and behind the last one (a chain
+ * cannot spell them: the caller moves its start and end by them), eq and x the problem's totals.  A problem of gap runs only is legal:
+ * count = 0, no flag, and in the plain output everything in lead_* and trail_* = 0.
+ * With the plain output B[0 .. n), the gaps G[0 .. n - 1), lead L and trail R: WFM_CHAIN_REVERSE gives the blocks B[n - 1 - k], the gap
+ * behind output block k is G[n - 2 - k], lead becomes R and trail becomes L (what a chain of the other strand lists); WFM_CHAIN_SWAP
+ * exchanges the two members of every pair, lead and trail included (what chainSwap does to the two sides); both bits do both.  eq and x
+ * do not change under either.  Any other flag bit is WFM_E_ARG with a message.
+ * A problem with an empty run, without runs, or whose pattern or text span does not fit 32 bits is flagged WFM_CHAIN_SPANS and has count 0
+ * and zeros elsewhere (the spans are taken before anything is written).
+ * Per problem the runs are indexed once (four exclusive prefixes per run as one 16-byte word, as wfm_lift_runs); a block's head is an aligned
+ * run whose predecessor is not aligned (or the first run); the end of its stretch and the next head are found by binary searches over the
+ * prefix words, O(log n_runs), never by a walk.  Blocks are placed by block scans, not atomics: two calls give the same bytes.  The output
+ * comes down in chunks of whole problems holding at most WFM_CHAIN_OUT_MB MiB of blocks (environment, a decimal, read per call, 256; one
+ * problem at least).  Host memory owned by the caller (wfm_free_chain); NULL and 0 without problems or blocks.  A run range that leaves
+ * the run buffer is WFM_E_ARG with a message, the outputs are NULL and the handle stays usable.  Returns WFM_OK or WFM_E_*. */
+typedef struct { uint64_t runs_off; uint32_t n_runs, flags; } wfm_chain_prob_t;   /* 16 bytes */
+#define WFM_CHAIN_SWAP    1u   /* dt and dq change places (lead and trail pairs too) */
+#define WFM_CHAIN_REVERSE 2u   /* blocks from the last to the first; lead and trail change places */
+typedef struct { uint32_t size, dt, dq, eq; } wfm_chain_block_t;                  /* 16 bytes */
+typedef struct { uint32_t flags, n_runs; uint64_t first, count;
+                 uint32_t lead_dt, lead_dq, trail_dt, trail_dq, eq, x; } wfm_chaincall_t;   /* 48 bytes */
+#define WFM_CHAIN_SPANS 2u     /* as WFM_LIFT_SPANS: nothing of the problem is written */
+int  wfm_chain_runs(wfm_handle_t* h, const wfm_chain_prob_t* probs, size_t n, const uint32_t* runs, size_t n_runs_total,
+                    wfm_chain_block_t** blocks, size_t* n_blocks, wfm_chaincall_t* per);
+void wfm_free_chain(wfm_chain_block_t* p);
+
 /* ---- presence of target intervals per group of records ----
  * What wfm_coverage_* cannot say: WHICH records cover a base.  Every problem carries a group (a sample, a haplotype); a pav object keeps,
  * per group, the UNION of the = and X bases of the problems added to it, as a list of segments on the handle's device

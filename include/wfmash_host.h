@@ -203,6 +203,38 @@ char* wfmh_test_coverage_bedgraph(const char* const* names, const uint64_t* leng
 void wfmh_set_lift(const char* bed_path_or_null, const char* out_path_or_null);
 int  wfmh_lift_counts(uint64_t out[4]);
 int  wfmh_lift_paf(wfm_handle_t* h, const char* target_fasta, const char* aligned_paf, const char* bed_path, const char* out_path, uint64_t out[4]);
+/* ---- UCSC chain files from the records written (wfm_chain_runs, wfmash_hip.h) ----
+ * wfmh_set_chain(path, swap): from now on every batch of wfmh_align_paf[_multi] runs ONE more device call behind the record writers: the
+ * runs of every record WRITTEN, on the part of the ops its line spells (with wfmh_set_left_align the normalised runs), are compacted to
+ * the blocks and gaps of a chain on the device; nothing goes up but runs.  No output byte of the PAF or SAM changes.  The align phase
+ * writes `path` through an ordered writer, one chain per record in the order of the PAF's records, and the writer numbers the chains
+ * 1, 2, 3 ... as it writes them: the file does not depend on the number of devices, handles, threads or the order of the batches.  A
+ * record the filters drop has no chain; a record the device refuses has none, is counted and reported on stderr.
+ * A chain: the header "chain score tName tSize + tStart tEnd qName qSize qStrand qStart qEnd id", space-separated; one line
+ * "size<TAB>dt<TAB>dq" per block, the last block's `size` alone; one empty line.  The chain runs from the target to the query (what
+ * liftOver, CrossMap and bcftools +liftover take to carry target positions to the query): [tStart, tEnd) is the target span the line's
+ * runs spell, [qStart, qEnd) the query span on +, and on - [qSize - qEnd, qSize - qStart) of the PAF's forward coordinates: the chain
+ * format counts a - side on the reverse strand.  score = the record's = columns: an integer that ranks longer and more identical chains
+ * first, which is all liftOver uses it for; it is not blastz's score.
+ * swap != 0 writes what chainSwap makes of that file, to lift the other way: the PAF query is the first side, always + with its forward
+ * coordinates, the PAF target the second side with the record's strand, on - at [tSize - tEnd, tSize - tStart); every (dt, dq) changes
+ * places and the blocks of a - record run from the last to the first (WFM_CHAIN_SWAP on every record, WFM_CHAIN_REVERSE on the - ones).
+ * path NULL or "" switches it off.  Every call zeroes the counts.  wfmh_chain_counts: out = {chains written, blocks, records refused, 0}
+ * since then.  Off by default; with the switch off nothing new is called and no file is written.
+ * wfmh_chain_paf: the same file for an existing aligned PAF (this build's, the reference's, minimap2 -c --eqx's); nothing else runs.
+ * Lines are read and skipped exactly as wfmh_coverage_paf does, the query's name and length are the line's; a cg:Z: that begins or ends
+ * with I or D runs moves the chain's ends inward by them.  One line on stderr has the totals.  out = the same four counts.  Returns 0 or
+ * WFM_E_*. */
+void wfmh_set_chain(const char* path_or_null, int swap);
+int  wfmh_chain_counts(uint64_t out[4]);
+int  wfmh_chain_paf(wfm_handle_t* h, const char* target_fasta, const char* aligned_paf, const char* out_path, int swap, uint64_t out[4]);
+/* Test hook (no GPU): the text side alone (chain_text.hpp).  spec: lines "R<TAB>qname<TAB>qsize<TAB>qs<TAB>qe<TAB>strand<TAB>tname<TAB>tsize
+ * <TAB>ts<TAB>te<TAB>eq<TAB>lead_dt<TAB>lead_dq<TAB>trail_dt<TAB>trail_dq" (a record as its PAF line has it, and what wfm_chain_runs says of
+ * its problem beside the blocks) each followed by its blocks "B<TAB>size<TAB>dt<TAB>dq" as the device gives them.  flags_out (or NULL):
+ * per R line the flags its problem carries under `swap`.  Returns the chain file exactly as the align phase writes it, ids from 1; NULL
+ * for a spec it cannot read.  malloc'd, wfmh_free. */
+char* wfmh_test_chain_lines(const char* spec, int swap, uint32_t* flags_out);
+
 /* ---- presence of target intervals per group of query sequences (wfm_pav_*, wfmash_hip.h) ----
  * wfmh_set_pav(bed, window, out): from now on every batch of wfmh_align_paf[_multi] runs ONE more device call behind the record writers:
  * the runs of every record WRITTEN (with wfmh_set_left_align the normalised runs) go into the handle's presence object under the column

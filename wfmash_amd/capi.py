@@ -50,6 +50,7 @@ EXPORTS = [
     "wfm_coverage_create", "wfm_coverage_free", "wfm_coverage_add", "wfm_coverage_export", "wfm_coverage_import", "wfm_coverage_intervals",
     "wfm_coverage_free_list",
     "wfm_liftset_create", "wfm_liftset_free", "wfm_lift_runs", "wfm_free_lifts",
+    "wfm_chain_runs", "wfm_free_chain",
     "wfm_pav_create", "wfm_pav_free", "wfm_pav_add", "wfm_pav_union", "wfm_pav_export", "wfm_pav_import", "wfm_pav_matrix", "wfm_pav_counts",
     "wfm_pav_free_list",
     "wfm_sketch_intersections",
@@ -77,6 +78,9 @@ WFM_COV_SCAN_BLOCK = 1024
 # wfm_liftset_* / wfm_lift_runs (include/wfmash_hip.h): why a problem has no lifts, the intervals one workgroup takes in the running maximum
 WFM_LIFT_SPANS = 2
 WFM_LIFT_SCAN_BLOCK = 1024
+# wfm_chain_runs (include/wfmash_hip.h): a problem's two flags, and why a problem has no blocks
+WFM_CHAIN_SWAP, WFM_CHAIN_REVERSE = 1, 2
+WFM_CHAIN_SPANS = 2
 # wfm_pav_* (include/wfmash_hip.h): why a problem added nothing, the segments one workgroup takes in the scans of the union
 WFM_PAV_SPANS = 2
 WFM_PAV_SCAN_BLOCK = 1024
@@ -189,6 +193,13 @@ class LiftCall(C.Structure):
 LIFT_IV_DTYPE = np.dtype([("start", "<u8"), ("end", "<u8")])
 LIFT_DTYPE = np.dtype([("problem", "<u4"), ("interval", "<u4"), ("p0", "<u4"), ("p1", "<u4"), ("t0", "<u4"), ("t1", "<u4"), ("eq", "<u4"), ("x", "<u4")])
 LIFTCALL_DTYPE = np.dtype([("flags", "<u4"), ("n_runs", "<u4"), ("first", "<u8"), ("count", "<u8")])
+
+
+# wfm_chain_prob_t, wfm_chain_block_t and wfm_chaincall_t of wfm_chain_runs
+CHAIN_PROB_DTYPE = np.dtype([("runs_off", "<u8"), ("n_runs", "<u4"), ("flags", "<u4")])
+CHAIN_BLOCK_DTYPE = np.dtype([("size", "<u4"), ("dt", "<u4"), ("dq", "<u4"), ("eq", "<u4")])
+CHAINCALL_DTYPE = np.dtype([("flags", "<u4"), ("n_runs", "<u4"), ("first", "<u8"), ("count", "<u8"), ("lead_dt", "<u4"), ("lead_dq", "<u4"),
+                            ("trail_dt", "<u4"), ("trail_dq", "<u4"), ("eq", "<u4"), ("x", "<u4")])
 
 
 PAV_PROB_DTYPE = np.dtype([("base", "<u8"), ("runs_off", "<u8"), ("n_runs", "<u4"), ("group", "<u4")])
@@ -355,11 +366,11 @@ def _result_array(results, n, copy=False):
 
 
 def _run_problems(problems, dtype):
-    """A list of (base, runs_off, n_runs) or (base, runs_off, n_runs, group) as a numpy array of wfm_cov_prob_t / wfm_pav_prob_t, and its
-    address (None for an empty list)."""
+    """A list of (base, runs_off, n_runs), (base, runs_off, n_runs, group) or (runs_off, n_runs, flags) as a numpy array of wfm_cov_prob_t /
+    wfm_pav_prob_t / wfm_chain_prob_t, and its address (None for an empty list)."""
     probs = np.zeros(len(problems), dtype=dtype)
     for i, p in enumerate(problems):
-        probs[i] = tuple(p) + (0,) * (4 - len(p))
+        probs[i] = tuple(p) + (0,) * (len(dtype.names) - len(p))
     return probs, (probs.ctypes.data if len(probs) else None)
 
 
@@ -1098,6 +1109,29 @@ class Handle:
             self._L.wfm_free_variants(recs, alleles)
         return np.frombuffer(raw, dtype=VARIANT_DTYPE), blob, [per[i] for i in range(n)]
 
+    def chain_runs(self, problems, runs):
+        """wfm_chain_runs: the blocks and gaps of a UCSC chain from every problem's runs.  problems: a list of (runs_off, n_runs, flags),
+        flags of WFM_CHAIN_SWAP and WFM_CHAIN_REVERSE; runs: the run words ((length << 2) | op).  Returns (the blocks as a numpy array with
+        CHAIN_BLOCK_DTYPE, the problems' records as one with CHAINCALL_DTYPE)."""
+        probs, probs_p = _run_problems(problems, CHAIN_PROB_DTYPE)
+        runs = np.ascontiguousarray(runs, dtype=np.uint32)
+        per = np.zeros(max(len(problems), 1), dtype=CHAINCALL_DTYPE)
+        ptr, n = C.c_void_p(), C.c_size_t(0)
+        f = self._L.wfm_chain_runs
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p]
+        self._L.wfm_free_chain.restype = None
+        self._L.wfm_free_chain.argtypes = [C.c_void_p]
+        rc = f(self._p, probs_p, len(probs), runs.ctypes.data if len(runs) else None, len(runs), C.byref(ptr), C.byref(n), per.ctypes.data)
+        if rc != 0:
+            assert not ptr.value and n.value == 0
+            raise WfmError(f"wfm_chain_runs failed ({rc}): {self.last_error()}")
+        try:
+            raw = C.string_at(ptr, n.value * CHAIN_BLOCK_DTYPE.itemsize) if n.value else b""
+        finally:
+            self._L.wfm_free_chain(ptr)
+        return np.frombuffer(raw, dtype=CHAIN_BLOCK_DTYPE), per[:len(problems)]
+
     def liftset(self, intervals, n_bases):
         """wfm_liftset_create: the sorted intervals [(start, end)] over n_bases target bases on this handle's device; .lift(problems, runs)
         lifts them through runs, .close() frees the set."""
@@ -1473,6 +1507,7 @@ HOST_EXPORTS = ["wfmh_test_packed_lce", "wfmh_test_is_acgt", "wfmh_align_default
                 "wfmh_set_verify_optimal", "wfmh_verify_optimal_counts", "wfmh_test_opt_band", "wfmh_set_left_align", "wfmh_left_align_counts", "wfmh_set_cs", "wfmh_cs_counts", "wfmh_set_variants", "wfmh_variants_counts",
                 "wfmh_set_coverage", "wfmh_coverage_counts", "wfmh_coverage_paf", "wfmh_test_coverage_bedgraph",
                 "wfmh_set_lift", "wfmh_lift_counts", "wfmh_lift_paf", "wfmh_test_lift_lines",
+                "wfmh_set_chain", "wfmh_chain_counts", "wfmh_chain_paf", "wfmh_test_chain_lines",
                 "wfmh_set_pav", "wfmh_pav_counts", "wfmh_pav_paf", "wfmh_test_pav_text",
                 "wfmh_ani_matrix", "wfmh_ani_matrix_rows", "wfmh_free_ani_rows", "wfmh_set_ani_matrix", "wfmh_test_ani_tsv"]
 
@@ -1987,6 +2022,56 @@ def host_lift_lines(names, lengths, bed_text, spec) -> str:
     s = C.string_at(p).decode()
     L.wfmh_free(p)
     return s
+
+
+def set_chain(path, swap=False) -> None:
+    """wfmh_set_chain: every later align_paf call of the process writes the UCSC chain of every record it writes to `path` (None: off), its
+    blocks and gaps made on the device; swap: the file from the query to the target, as chainSwap would make it; zeroes the counts."""
+    f = _host().wfmh_set_chain
+    f.restype = None
+    f.argtypes = [C.c_char_p, C.c_int]
+    f(os.fsencode(path) if path else None, 1 if swap else 0)
+
+
+def chain_counts():
+    """wfmh_chain_counts: (chains written, blocks, records refused, 0) since wfmh_set_chain."""
+    f = _host().wfmh_chain_counts
+    f.restype = C.c_int
+    f.argtypes = [C.POINTER(C.c_uint64)]
+    out = (C.c_uint64 * 4)()
+    rc = f(out)
+    if rc != 0:
+        raise WfmError(f"wfmh_chain_counts failed ({rc})")
+    return tuple(int(v) for v in out)
+
+
+def chain_paf(handle, target_fasta, aligned_paf, out_path, swap=False):
+    """wfmh_chain_paf: the chain file of an existing aligned PAF; returns (chains written, blocks, records refused, 0)."""
+    f = _host().wfmh_chain_paf
+    f.restype = C.c_int
+    f.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_uint64)]
+    out = (C.c_uint64 * 4)()
+    rc = f(handle._p, os.fsencode(target_fasta), os.fsencode(aligned_paf), os.fsencode(out_path), 1 if swap else 0, out)
+    if rc != 0:
+        raise WfmError(f"wfmh_chain_paf failed ({rc}): {handle.last_error()}")
+    return tuple(int(v) for v in out)
+
+
+def host_chain_lines(spec, swap=False):
+    """wfmh_test_chain_lines (no GPU): the chain file of the records and blocks in `spec` (include/wfmash_host.h) as bytes, and the flags
+    the records' problems carry under `swap`."""
+    n_records = sum(1 for ln in spec.split("\n") if ln.startswith("R\t"))
+    L = _host()
+    f = L.wfmh_test_chain_lines
+    f.restype = C.c_void_p
+    f.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_uint32)]
+    flags = (C.c_uint32 * max(n_records, 1))()
+    p = f(spec.encode(), 1 if swap else 0, flags if n_records else None)
+    if not p:
+        raise WfmError("wfmh_test_chain_lines cannot read the spec")
+    s = C.string_at(p)
+    L.wfmh_free(p)
+    return s, [int(v) for v in flags[:n_records]]
 
 
 def set_pav(bed_path, window, out_path) -> None:

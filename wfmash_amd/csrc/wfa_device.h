@@ -365,6 +365,22 @@ void launch_lift_index(const uint32_t* runs, const LiftProb* probs, int nprob, c
 // the lifts of the problems [ka, kb), 32 bytes each; out[0] is lift number off[ka] of the call
 void launch_lift_write(const uint32_t* runs, const LiftProb* probs, const void* iv, const void* pre, const LiftWin* win, const unsigned long long* off,
                        uint32_t ka, uint32_t kb, void* out, hipStream_t st);
+// wfm_chain_runs (wfa_chain.hip).  A problem is wfm_chain_prob_t with the place of its n_runs + 1 prefix words in `pre`; what
+// chain_index_kernel leaves per problem: its blocks, its flags, the bases before the first and behind the last block (as the problem's flags
+// order them) and its = and X columns
+struct ChainProb {
+  uint64_t runs_off, pre_off;
+  uint32_t n_runs, flags;
+};
+struct ChainWin {
+  uint64_t count;
+  uint32_t flags, lead_dt, lead_dq, trail_dt, trail_dq, eq, x, pad_;
+};
+// pre: 16-byte words, the problems' n_runs + 1 each; win: nprob; off: nprob + 1
+void launch_chain_index(const uint32_t* runs, const ChainProb* probs, int nprob, void* pre, ChainWin* win, unsigned long long* off, hipStream_t st);
+// the blocks of the problems [ka, kb), 16 bytes each; out[0] is block number off[ka] of the call
+void launch_chain_write(const uint32_t* runs, const ChainProb* probs, const void* pre, const ChainWin* win, const unsigned long long* off, uint32_t ka,
+                        uint32_t kb, void* out, hipStream_t st);
 // wfm_pav_* (wfa_pav.hip).  A problem is wfm_pav_prob_t as the caller wrote it.  A segment list is two arrays of keys, ks[i] = group << 40 |
 // start and ke[i] = group << 40 | end
 struct PavProb {

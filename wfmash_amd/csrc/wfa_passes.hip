@@ -1,7 +1,7 @@
 // wfa_passes.hip -- the record passes of the C ABI (see include/wfmash_hip.h): host code that takes the final runs of a batch and
 // produces something from them -- the check against the bases, left-aligned gaps, cs strings, variants, target depth, lifted
-// intervals, presence per group, the proof of optimality.  The kernels are in wfa_check.hip, wfa_leftalign.hip, wfa_cs.hip,
-// wfa_variants.hip, wfa_coverage.hip, wfa_lift.hip, wfa_pav.hip and wfa_optcheck.hip.
+// intervals, the blocks of a chain, presence per group, the proof of optimality.  The kernels are in wfa_check.hip, wfa_leftalign.hip,
+// wfa_cs.hip, wfa_variants.hip, wfa_coverage.hip, wfa_lift.hip, wfa_chain.hip, wfa_pav.hip and wfa_optcheck.hip.
 //
 // Every pass has the same frame, written once below: it validates the run ranges before anything is launched, carves what the
 // call has on the device out of one block, launches, writes its output in chunks that fit a cap, and waits for the stream before
@@ -849,6 +849,88 @@ int wfm_lift_runs(wfm_handle_t* h, const wfm_liftset_t* s, const wfm_cov_prob_t*
 }
 
 void wfm_free_lifts(wfm_lift_t* p) { free(p); }
+
+// ---- the blocks and gaps of a chain from every problem's runs (wfmash_hip.h; the kernels: wfa_chain.hip) ----
+static_assert(sizeof(wfm_chain_prob_t) == 16 && sizeof(wfm_chain_block_t) == 16 && sizeof(wfm_chaincall_t) == 48 && sizeof(ChainProb) == 24 && sizeof(ChainWin) == 40,
+              "wfmash_hip.h and wfa_device.h state these sizes");
+
+int wfm_chain_runs(wfm_handle_t* h, const wfm_chain_prob_t* probs, size_t n, const uint32_t* runs, size_t n_runs_total, wfm_chain_block_t** blocks,
+                   size_t* n_blocks, wfm_chaincall_t* per) {
+  if (!h || !blocks || !n_blocks || (n && (!probs || !per)) || (n_runs_total && !runs)) return WFM_E_ARG;
+  *blocks = nullptr; *n_blocks = 0;
+  if (n == 0) return WFM_OK;
+  if (n > (size_t)INT32_MAX || n_runs_total > ((size_t)1 << 31)) { h->err = "wfm_chain_runs: too many problems or runs for one call"; return WFM_E_ARG; }
+  if (int rc = all_runs_inside(h, probs, n, n_runs_total)) return rc;
+  std::vector<ChainProb> cp(n);
+  uint64_t n_pre = 0;
+  for (size_t i = 0; i < n; ++i) {
+    if (probs[i].flags & ~(WFM_CHAIN_SWAP | WFM_CHAIN_REVERSE)) {
+      h->err = "problem " + std::to_string(i) + ": flags " + std::to_string(probs[i].flags) + " hold a bit that is neither WFM_CHAIN_SWAP nor WFM_CHAIN_REVERSE";
+      return WFM_E_ARG;
+    }
+    cp[i] = ChainProb{probs[i].runs_off, n_pre, probs[i].n_runs, probs[i].flags};
+    n_pre += (uint64_t)probs[i].n_runs + 1;
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  PassTimer tm(h);
+  // (the prefix words come first: they are read 16 bytes at a time)
+  uint4* d_pre;
+  ChainProb* d_probs;
+  ChainWin* d_win;
+  unsigned long long* d_off;
+  uint32_t* d_runs;
+  Carver cv{h->scratch, "chain"};
+  cv.piece(&d_pre, (size_t)n_pre); cv.piece(&d_probs, n); cv.piece(&d_win, n); cv.piece(&d_off, n + 1); cv.piece(&d_runs, n_runs_total);
+  if (int rc = cv.commit(h)) return rc;
+  HIPCHK(h, hipMemcpyAsync(d_probs, cp.data(), n * sizeof(ChainProb), hipMemcpyHostToDevice, h->stream));
+  if (n_runs_total) HIPCHK(h, hipMemcpyAsync(d_runs, runs, n_runs_total * 4, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, tm.begin());
+  launch_chain_index(d_runs, d_probs, (int)n, d_pre, d_win, d_off, h->stream);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, tm.end());
+  std::vector<ChainWin> win(n);
+  std::vector<unsigned long long> off(n + 1);
+  HIPCHK(h, hipMemcpyAsync(win.data(), d_win, n * sizeof(ChainWin), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(off.data(), d_off, (n + 1) * 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  float ms_index = 0, ms_write = 0, ms = 0;
+  (void)tm.event_ms(&ms_index);
+  for (size_t i = 0; i < n; ++i) {
+    const ChainWin& w = win[i];
+    per[i] = wfm_chaincall_t{w.flags, probs[i].n_runs, off[i], w.count, w.lead_dt, w.lead_dq, w.trail_dt, w.trail_dq, w.eq, w.x};
+  }
+  const unsigned long long total = off[n];
+  if (total == 0) return WFM_OK;
+  // chunks of whole problems that hold at most WFM_CHAIN_OUT_MB MiB of blocks; a single problem may exceed that alone
+  const unsigned long long cap = cap_units("WFM_CHAIN_OUT_MB", sizeof(wfm_chain_block_t), 1);
+  std::vector<std::pair<size_t, size_t>> chunks;
+  unsigned long long widest = 0;
+  for (size_t ka = 0, kb; ka < n; ka = kb) {
+    kb = chunk_end(ka, off, cap);
+    if (off[kb] > off[ka]) { chunks.emplace_back(ka, kb); widest = std::max(widest, off[kb] - off[ka]); }
+  }
+  char* host = (char*)malloc((size_t)total * sizeof(wfm_chain_block_t));
+  if (!host) { h->err = "out of host memory (chain)"; return WFM_E_NOMEM; }
+  if (h->outblk.ensure((size_t)widest * 2)) { free(host); h->err = "out of device memory (chain output)"; return WFM_E_NOMEM; }
+  uint8_t* d_out = (uint8_t*)h->outblk.p;
+  const bool pinned = cs_pin_pieces(h);
+  for (const auto& c : chunks) {
+    (void)tm.begin();
+    launch_chain_write(d_runs, d_probs, d_pre, d_win, d_off, (uint32_t)c.first, (uint32_t)c.second, d_out, h->stream);
+    hipError_t e = hipGetLastError();
+    (void)tm.end();
+    if (e == hipSuccess) e = cs_copy_down(h, pinned, host + off[c.first] * sizeof(wfm_chain_block_t), d_out, (size_t)(off[c.second] - off[c.first]) * sizeof(wfm_chain_block_t));  // (the block is the next chunk's)
+    if (e != hipSuccess) { free(host); h->err = std::string("wfm_chain_runs: ") + hipGetErrorString(e); return WFM_E_HIP; }
+    if (tm.event_ms(&ms)) ms_write += ms;
+  }
+  *blocks = (wfm_chain_block_t*)host; *n_blocks = (size_t)total;
+  if (tm.on)
+    fprintf(stderr, "[wfm] chain: %zu problems, %zu runs, %llu blocks in %zu chunks, index %.3f ms, write %.3f ms (device events), the call %.3f ms (host clock)\n",
+            n, n_runs_total, total, chunks.size(), ms_index, ms_write, tm.host_ms());
+  return WFM_OK;
+}
+
+void wfm_free_chain(wfm_chain_block_t* p) { free(p); }
 
 // ---- presence of target intervals per group of records (wfmash_hip.h; the kernels and the sort: wfa_pav.hip) ----
 struct wfm_pav {

@@ -2,6 +2,7 @@
 #include "verify_paf.hpp"
 #include "coverage_text.hpp"
 #include "lift_text.hpp"
+#include "chain_text.hpp"
 #include "pav_text.hpp"
 #include "map_queue.hpp"
 #include "parallel.hpp"
@@ -385,7 +386,7 @@ std::string Aligner::gather_text(Summary& sum, const std::vector<Fetched>& fetch
 std::string Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<std::string>& lines, int threads, Summary& sum, uint64_t first_row,
                                  std::string* vcf, wfm_coverage_t* coverage, const std::vector<uint64_t>* seq_offsets, std::string* lift,
                                  const wfm_liftset_t* liftset, const std::vector<lift::Interval>* lift_intervals, wfm_pav_t* pav,
-                                 const std::vector<uint32_t>* pav_columns) {
+                                 const std::vector<uint32_t>* pav_columns, std::string* chain, bool chain_swap) {
   const bool dbg = getenv("WFM_DEBUG") != nullptr;
   BatchTimes t;
   std::vector<Fetched> rows = parse_rows(lines, first_row, sum);
@@ -422,6 +423,7 @@ std::string Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<std::stri
   fmt.pav = pav;
   fmt.liftset = liftset;
   fmt.lift_intervals = lift_intervals;
+  fmt.chain = chain ? (chain_swap ? 2 : 1) : 0;
   const int rc = wflign::do_biwfa_alignment_batch(gpu_handle, recs, penalties_of(param), param.disable_chain_patching, filters_of(param), &st,
                                                   fmt, ds ? &resident : nullptr);
   if (rc < 0) throw std::runtime_error(std::string("[wfmash::align] GPU alignment failed: ") + st.error);
@@ -432,6 +434,8 @@ std::string Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<std::stri
     for (const auto& r : recs) *vcf += r.vcf;  // (a record without a line has no VCF lines: write_record)
   if (lift)
     for (const auto& r : recs) *lift += r.lift;  // (in the order of the records' lines: gather_text's)
+  if (chain)
+    for (const auto& r : recs) *chain += r.chain;  // (likewise; the ids are the writer's)
   t.text = t.lap();
   if (verify::enabled() && !param.sam_format) {  // --verify: the finished lines, before they are written (SAM records carry no =/X CIGAR)
     verify::Source src;
@@ -526,6 +530,18 @@ struct TextSink {
   void write(std::string& text) { *out << text; }
   void flush() { out->flush(); }
 };
+// --chain: the chains of a batch come without their ids; the writer numbers them 1, 2, 3 ... as it writes them, in file order
+struct ChainSink {
+  std::ofstream* out;
+  uint64_t next = 1;
+  std::string numbered;
+  void write(std::string& text) {
+    numbered.clear();
+    chain::number(text, &next, numbered);
+    *out << numbered;
+  }
+  void flush() { out->flush(); }
+};
 }  // namespace
 
 struct Aligner::Run {
@@ -560,6 +576,9 @@ struct Aligner::Run {
     liftsets.emplace_back(h, s);
     return s;
   }
+  // --chain: the fourth file, keyed by the same batch numbers
+  std::unique_ptr<skch::OrderedWriter<std::string, ChainSink>> chain_writer;
+  bool chain_swap = false;
   // --pav: the intervals of the table in the file's order, the columns (and every query sequence's), and the presence object of every
   // handle the run has used so far, made at the handle's first batch
   bool pav_on = false;
@@ -694,14 +713,15 @@ void Aligner::run_worker(Run& run, size_t wk) {
       { std::lock_guard<std::mutex> lk(run.read_mu); more = run.more_rows; beside = run.in_flight[dev].fetch_add(1); }
       wfm_set_concurrent_calls(run.use[wk], beside + (more && run.plan.per_gpu > 1 ? 1 : 0));
       struct Leave { std::atomic<int>& a; ~Leave() { a.fetch_sub(1); } } leave{run.in_flight[dev]};
-      std::string vcf, lifted;
+      std::string vcf, lifted, chains;
       std::string text = align_batch(run.use[wk], batch, run.threads_each, run.part[wk], first_row, run.vcf_writer ? &vcf : nullptr,
                                      run.coverage_of(run.use[wk]), &run.seq_offsets, run.lift_writer ? &lifted : nullptr, run.liftset_of(run.use[wk]),
-                                     &run.lift_iv, run.pav_of(run.use[wk]), &run.pav_cols.of_seq);
+                                     &run.lift_iv, run.pav_of(run.use[wk]), &run.pav_cols.of_seq, run.chain_writer ? &chains : nullptr, run.chain_swap);
       const double at1 = run.ms();
       run.writer.put((uint64_t)seq, std::move(text));
       if (run.vcf_writer) run.vcf_writer->put((uint64_t)seq, std::move(vcf));
       if (run.lift_writer) run.lift_writer->put((uint64_t)seq, std::move(lifted));
+      if (run.chain_writer) run.chain_writer->put((uint64_t)seq, std::move(chains));
       if (getenv("WFM_DEBUG"))
         fprintf(stderr, "[wfmash::align] worker %zu: batch %lld from +%.0f ms to +%.0f ms, written at +%.0f ms\n", wk, (long long)seq, at0, at1, run.ms());
     }
@@ -865,6 +885,14 @@ Summary Aligner::compute() {
   std::ofstream liftstream;
   std::string lift_bed, lift_out;
   wflign::lift_paths(lift_bed, lift_out);
+  std::ofstream chainstream;
+  std::string chain_out;
+  wflign::chain_path(chain_out, run.chain_swap);
+  if (!chain_out.empty()) {  // --chain: the batches' chains go through a fourth ordered writer, which numbers them
+    chainstream.open(chain_out);
+    if (!chainstream.is_open()) throw std::runtime_error("[wfmash::align] Error! Failed to open the chain file: " + chain_out);
+    run.chain_writer.reset(new skch::OrderedWriter<std::string, ChainSink>(ChainSink{&chainstream}));
+  }
   std::ofstream pavstream;
   std::string pav_bed, pav_out;
   uint64_t pav_window = 0, pav_skipped = 0;
@@ -928,6 +956,7 @@ Summary Aligner::compute() {
   outstream.close();
   if (vcfstream.is_open()) vcfstream.close();
   if (liftstream.is_open()) liftstream.close();
+  if (chainstream.is_open()) chainstream.close();
   sum.ms_total = ms_since(t0);
   std::cerr << "[wfmash::align] total aligned records = " << sum.records << ", total aligned bp = " << sum.aligned_bp
             << ", completed in " << (uint64_t)(sum.ms_total / 1000.0) << " seconds" << std::endl;

@@ -107,11 +107,13 @@ class Aligner {
   // (vcf: where the VCF lines of the records written go, --variants; null: nowhere.  coverage: the depth object of this handle the records
   // written are added to, --coverage, with seq_offsets: where each target sequence begins in the concatenation; null: none.  lift: where
   // the lift lines of the records written go, --lift, with the handle's liftset and the intervals in its order; null: nowhere.  pav: the
-  // presence object of this handle the records written are added to, --pav, with the column of every query sequence; null: none)
+  // presence object of this handle the records written are added to, --pav, with the column of every query sequence; null: none.  chain:
+  // where the chains of the records written go, without their ids, --chain, swapped or not; null: nowhere)
   std::string align_batch(wfm_handle_t* gpu, std::vector<std::string>& lines, int threads, Summary& sum, uint64_t first_row = 0,
                           std::string* vcf = nullptr, wfm_coverage_t* coverage = nullptr, const std::vector<uint64_t>* seq_offsets = nullptr,
                           std::string* lift = nullptr, const wfm_liftset_t* liftset = nullptr, const std::vector<lift::Interval>* lift_intervals = nullptr,
-                          wfm_pav_t* pav = nullptr, const std::vector<uint32_t>* pav_columns = nullptr);
+                          wfm_pav_t* pav = nullptr, const std::vector<uint32_t>* pav_columns = nullptr,
+                          std::string* chain = nullptr, bool chain_swap = false);
   std::vector<Fetched> parse_rows(std::vector<std::string>& lines, uint64_t first_row, Summary& sum) const;
   void fetch_windows(Fetched& f) const;
   std::vector<Fetched> fetch_eager(std::vector<Fetched>& rows, int threads, Summary& sum) const;

@@ -13,6 +13,7 @@
 #include "../csrc/wfa_optband.h"
 #include "aligner.hpp"
 #include "fasta.hpp"
+#include "chain_text.hpp"
 #include "lift_text.hpp"
 #include "pav_text.hpp"
 #include "map_stats.hpp"
@@ -149,6 +150,61 @@ char* wfmh_test_lift_lines(const char* const* names, const uint64_t* lengths, in
       return nullptr;
     }
   }
+  char* p = (char*)malloc(out.size() + 1);
+  if (p) memcpy(p, out.c_str(), out.size() + 1);
+  return p;
+}
+
+// test hook (no GPU): the text side of --chain (chain_text.hpp): the flags of the records' problems and the file of given blocks
+char* wfmh_test_chain_lines(const char* spec, int swap, uint32_t* flags_out) {
+  if (!spec) return nullptr;
+  std::string body;
+  chain::Record r;
+  chain::Ends e;
+  std::vector<chain::Block> blocks;
+  bool open = false;
+  size_t n_rec = 0;
+  auto close = [&]() {
+    if (open) chain::chain_body(body, r, swap != 0, e, blocks.data(), blocks.size());
+    blocks.clear();
+  };
+  std::istringstream in(spec);
+  std::string line;
+  while (std::getline(in, line)) {
+    if (line.empty()) continue;
+    std::vector<std::string> f;
+    for (size_t at = 0;;) {
+      const size_t tab = line.find('\t', at);
+      f.push_back(line.substr(at, tab == std::string::npos ? std::string::npos : tab - at));
+      if (tab == std::string::npos) break;
+      at = tab + 1;
+    }
+    uint64_t v[5] = {0, 0, 0, 0, 0};
+    if (f[0] == "R" && f.size() == 15) {
+      close();
+      open = true;
+      r = chain::Record();
+      r.qname = f[1]; r.tname = f[6]; r.rev = f[5] == "-";
+      if (!lift::decimal(f[2], 0, f[2].size(), &r.qsize) || !lift::decimal(f[3], 0, f[3].size(), &r.qs) || !lift::decimal(f[4], 0, f[4].size(), &r.qe) ||
+          !lift::decimal(f[7], 0, f[7].size(), &r.tsize) || !lift::decimal(f[8], 0, f[8].size(), &r.ts) || !lift::decimal(f[9], 0, f[9].size(), &r.te))
+        return nullptr;
+      for (int k = 0; k < 5; ++k)
+        if (!lift::decimal(f[(size_t)k + 10], 0, f[(size_t)k + 10].size(), &v[k]) || v[k] > 0xffffffffull) return nullptr;
+      e.eq = (uint32_t)v[0]; e.lead_dt = (uint32_t)v[1]; e.lead_dq = (uint32_t)v[2]; e.trail_dt = (uint32_t)v[3]; e.trail_dq = (uint32_t)v[4];
+      if (flags_out) flags_out[n_rec] = chain::flags_of(swap != 0, r.rev);
+      ++n_rec;
+    } else if (f[0] == "B" && f.size() == 4 && open) {
+      for (int k = 0; k < 3; ++k)
+        if (!lift::decimal(f[(size_t)k + 1], 0, f[(size_t)k + 1].size(), &v[k]) || v[k] > 0xffffffffull) return nullptr;
+      blocks.push_back(chain::Block{(uint32_t)v[0], (uint32_t)v[1], (uint32_t)v[2], 0u});
+    } else {
+      return nullptr;
+    }
+  }
+  close();
+  std::string out;
+  uint64_t next = 1;
+  chain::number(body, &next, out);
   char* p = (char*)malloc(out.size() + 1);
   if (p) memcpy(p, out.c_str(), out.size() + 1);
   return p;

@@ -1,0 +1,72 @@
+// chain_text.hpp -- the text side of --chain: which flags a record's device problem carries, the coordinates of the two sides of a UCSC
+// chain and the lines of the chain file.  Pure host code on the standard library alone, so that it can be built on its own
+// (scripts/micro/chain_check.cpp runs it under the address and undefined-behaviour sanitizers).
+#pragma once
+
+#include <cstdint>
+#include <cstdio>
+#include <string>
+
+namespace chain {
+
+// a record as its PAF line has it: the query window [qs, qe) and the target window [ts, te) on the forward strands, the two sequences'
+// lengths, the strand
+struct Record {
+  std::string qname, tname;
+  uint64_t qsize = 0, qs = 0, qe = 0, tsize = 0, ts = 0, te = 0;
+  bool rev = false;
+};
+
+// a block as wfm_chain_runs gives it (wfm_chain_block_t), and what it says of the problem beside its blocks (of wfm_chaincall_t)
+struct Block { uint32_t size, dt, dq, eq; };
+struct Ends { uint32_t lead_dt = 0, lead_dq = 0, trail_dt = 0, trail_dq = 0, eq = 0; };
+
+// The flags of a record's problem (WFM_CHAIN_SWAP = 1, WFM_CHAIN_REVERSE = 2).  The plain file runs from the target to the query: the
+// runs as they are.  The swapped file's first side is the query, which a chain lists on its forward strand: every pair changes places,
+// and the blocks of a - record, whose runs walk the query backwards, are taken from the last to the first.
+inline uint32_t flags_of(bool swap, bool rev) { return swap ? (rev ? 3u : 1u) : 0u; }
+
+// One chain WITHOUT its id: "chain score tName tSize + tStart tEnd qName qSize qStrand qStart qEnd " (the id and the newline are the
+// writer's: number()), one line "size<TAB>dt<TAB>dq" per block, the last block's `size` alone, one empty line.  blocks, ends: what the
+// device gave for the problem with flags_of(swap, r.rev).  The first side is always +; the second carries the record's strand and, on -,
+// is counted on the reverse strand: [size - end, size - start).  A chain cannot spell the bases before its first and behind its last
+// block: both sides begin lead_* later and end trail_* earlier.  score = the record's = columns: an integer that ranks longer and more
+// identical chains first, not blastz's score.  Nothing is written for a record without blocks.
+inline void chain_body(std::string& out, const Record& r, bool swap, const Ends& e, const Block* blocks, uint64_t n) {
+  if (n == 0) return;
+  const std::string &aname = swap ? r.qname : r.tname, &bname = swap ? r.tname : r.qname;
+  const uint64_t asize = swap ? r.qsize : r.tsize, bsize = swap ? r.tsize : r.qsize;
+  uint64_t as = swap ? r.qs : r.ts, ae = swap ? r.qe : r.te, bs = swap ? r.ts : r.qs, be = swap ? r.te : r.qe;
+  if (r.rev) { const uint64_t s = bsize - be; be = bsize - bs; bs = s; }
+  char num[200];
+  out.append(num, (size_t)snprintf(num, sizeof num, "chain %u ", e.eq));
+  out += aname;
+  out.append(num, (size_t)snprintf(num, sizeof num, " %llu + %llu %llu ", (unsigned long long)asize, (unsigned long long)(as + e.lead_dt),
+                                   (unsigned long long)(ae - e.trail_dt)));
+  out += bname;
+  out.append(num, (size_t)snprintf(num, sizeof num, " %llu %c %llu %llu \n", (unsigned long long)bsize, r.rev ? '-' : '+', (unsigned long long)(bs + e.lead_dq),
+                                   (unsigned long long)(be - e.trail_dq)));
+  for (uint64_t k = 0; k < n; ++k) {
+    const Block& b = blocks[k];
+    if (k + 1 < n) out.append(num, (size_t)snprintf(num, sizeof num, "%u\t%u\t%u\n", b.size, b.dt, b.dq));
+    else out.append(num, (size_t)snprintf(num, sizeof num, "%u\n\n", b.size));
+  }
+}
+
+// The chains of `text` (chain_body's) with their ids, *next, *next + 1, ... in the order they stand in, appended to `out`: a header is the
+// line that begins with 'c' (a block line begins with a digit), and its id goes before its newline.  Returns the chains numbered.
+inline uint64_t number(const std::string& text, uint64_t* next, std::string& out) {
+  uint64_t n = 0;
+  char num[32];
+  for (size_t at = 0; at < text.size();) {
+    size_t nl = text.find('\n', at);
+    if (nl == std::string::npos) nl = text.size();
+    out.append(text, at, nl - at);
+    if (text[at] == 'c') { out.append(num, (size_t)snprintf(num, sizeof num, "%llu", (unsigned long long)(*next)++)); ++n; }
+    if (nl < text.size()) out += '\n';
+    at = nl + 1;
+  }
+  return n;
+}
+
+}  // namespace chain

@@ -65,6 +65,16 @@
 //                                              each of the two is an error without the other; off by default
 //   --lift-paf IN.paf --lift IN.bed --lift-out FILE target.fa   the same file for an existing aligned PAF: no mapping, no alignment;
 //                                              lines are skipped and counted as --coverage-paf does; only --device beside it
+//   --chain FILE [--chain-swap]                a UCSC chain file of every record WRITTEN, from the target to the query (what liftOver,
+//                                              CrossMap and bcftools +liftover take): the runs are compacted to blocks and gaps on the device
+//                                              (wfm_chain_runs; nothing goes up but runs), one chain per record in the order of the PAF's
+//                                              records, ids 1, 2, 3 ... in file order; score = the record's = columns (it ranks chains, it is
+//                                              not blastz's score); --chain-swap: the file chainSwap would make of it, from the query to the
+//                                              target; no output byte of the PAF or SAM changes; allowed and refused beside what --lift is;
+//                                              --chain-swap without --chain is an error; off by default
+//   --chain-paf IN.paf --chain FILE [--chain-swap] target.fa [query.fa]   the same file for an existing aligned PAF: no mapping, no
+//                                              alignment; lines are skipped and counted as --coverage-paf does (the query's name and
+//                                              length are the line's: query.fa is not read); only --device beside it
 //   --pav IN.bed | --pav-window N, --pav-out FILE   which groups of query sequences (haplotypes, samples: the part of the name before its
 //                                              last '#') have each target interval, and how much of it: the runs of every record WRITTEN go
 //                                              into a per-group union of aligned segments on the device (wfm_pav_*; 16 bytes a segment, never
@@ -173,6 +183,9 @@ static void usage() {
           "            --coverage-paf FILE with --coverage: the depth of an existing aligned PAF over target.fa, and stop (only --device beside it)\n"
           "            --lift BED --lift-out FILE lift the BED's target intervals through every record written, on the GPU: one line per record and interval (not with -m, --verify-paf)\n"
           "            --lift-paf FILE with --lift, --lift-out: lift through an existing aligned PAF over target.fa, and stop (only --device beside it)\n"
+          "            --chain FILE  write a UCSC chain file (target to query) of every record written, blocks and gaps made on the GPU; score = the = columns (not with -m, --verify-paf)\n"
+          "            --chain-swap  with --chain: the swapped file (query to target), what chainSwap would make of it\n"
+          "            --chain-paf FILE with --chain: the chain file of an existing aligned PAF over target.fa, and stop (only --chain-swap and --device beside it)\n"
           "            --pav BED | --pav-window N, --pav-out FILE per target interval and group of query sequences the bases present, from per-group unions on the GPU (not with -m, --verify-paf)\n"
           "            --pav-paf FILE with --pav or --pav-window, --pav-out: the table of an existing aligned PAF over target.fa [query.fa], and stop (only --device beside it)\n"
           "            --verify-paf FILE check an existing aligned PAF against target.fa [query.fa] and stop (exit status 3 if a line fails)\n"
@@ -186,12 +199,14 @@ int main(int argc, char** argv) {
   ap.threads = 1;  // -t, default 1 as in the reference (parse_args.hpp: thread_count); the C ABI default (0) means all cores
   wfmh_map_params_t mp;
   wfmh_map_default_params(&mp);
-  std::string mapping_in, out = "/dev/stdout", target, query, seeds_in, scaffold_out, tmp_base, verify_in, ani_matrix_out, variants_out, coverage_out, coverage_in, lift_bed, lift_out, lift_in, pav_bed, pav_out, pav_in;
+  std::string mapping_in, out = "/dev/stdout", target, query, seeds_in, scaffold_out, tmp_base, verify_in, ani_matrix_out, variants_out, coverage_out, coverage_in, lift_bed, lift_out, lift_in, pav_bed, pav_out, pav_in, chain_out, chain_in;
   uint64_t pav_window = 0;
   bool pav_window_set = false;
   bool pav_other = false;      // --pav-paf: anything beside it, --pav, --pav-window, --pav-out, --device and the two FASTAs
   bool other_options = false;  // --coverage-paf: anything beside it, --coverage, --device and the target
   bool lift_other = false;     // --lift-paf: anything beside it, --lift, --lift-out, --device and the target
+  bool chain_other = false;    // --chain-paf: anything beside it, --chain, --chain-swap, --device and the two FASTAs
+  bool chain_swap = false;
   bool verify = false, verify_optimal = false, ani_only = false, left_align = false;
   uint64_t verify_optimal_cells = 0;
   int cs_form = 0;  // --cs: 0 off, 1 short, 2 long
@@ -200,6 +215,7 @@ int main(int argc, char** argv) {
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
     if (a[0] == '-' ? (a != "--pav" && a != "--pav-window" && a != "--pav-out" && a != "--pav-paf" && a != "--device" && a != "-h" && a != "--help") : !query.empty()) pav_other = true;
+    if (a[0] == '-' ? (a != "--chain" && a != "--chain-swap" && a != "--chain-paf" && a != "--device" && a != "-h" && a != "--help") : !query.empty()) chain_other = true;
     if (a[0] == '-' ? (a != "--lift" && a != "--lift-out" && a != "--lift-paf" && a != "--device" && a != "-h" && a != "--help") : !target.empty()) lift_other = true;
     if (a[0] == '-' ? (a != "--coverage" && a != "--coverage-paf" && a != "--device" && a != "-h" && a != "--help") : !target.empty()) other_options = true;
     auto next = [&](const char* name) -> std::string {
@@ -340,6 +356,9 @@ int main(int argc, char** argv) {
     else if (a == "--lift") lift_bed = next("--lift");
     else if (a == "--lift-out") lift_out = next("--lift-out");
     else if (a == "--lift-paf") lift_in = next("--lift-paf");
+    else if (a == "--chain") chain_out = next("--chain");
+    else if (a == "--chain-swap") chain_swap = true;
+    else if (a == "--chain-paf") chain_in = next("--chain-paf");
     else if (a == "--pav") pav_bed = next("--pav");
     else if (a == "--pav-out") pav_out = next("--pav-out");
     else if (a == "--pav-paf") pav_in = next("--pav-paf");
@@ -373,6 +392,11 @@ int main(int argc, char** argv) {
   if (!lift_in.empty() && lift_bed.empty()) { fprintf(stderr, "[wfmash] ERROR: --lift-paf needs --lift IN.bed and --lift-out FILE\n"); return 1; }
   if (!lift_bed.empty() && approx_only) { fprintf(stderr, "[wfmash] ERROR: --lift lifts through alignments: it cannot be combined with -m\n"); return 1; }
   if (!lift_bed.empty() && !verify_in.empty()) { fprintf(stderr, "[wfmash] ERROR: --lift belongs to the align phase: it cannot be combined with --verify-paf\n"); return 1; }
+  if (chain_swap && chain_out.empty()) { fprintf(stderr, "[wfmash] ERROR: --chain-swap needs --chain FILE\n"); return 1; }
+  if (!chain_in.empty() && chain_out.empty()) { fprintf(stderr, "[wfmash] ERROR: --chain-paf needs --chain FILE\n"); return 1; }
+  if (!chain_out.empty() && approx_only) { fprintf(stderr, "[wfmash] ERROR: --chain writes chains of alignments: it cannot be combined with -m\n"); return 1; }
+  if (!chain_out.empty() && !verify_in.empty()) { fprintf(stderr, "[wfmash] ERROR: --chain belongs to the align phase: it cannot be combined with --verify-paf\n"); return 1; }
+  if (!chain_in.empty() && chain_other) { fprintf(stderr, "[wfmash] ERROR: --chain-paf runs nothing else: besides --chain FILE, --chain-swap and the FASTAs it takes the number of the GPU only\n"); return 1; }
   if (!lift_in.empty() && lift_other) { fprintf(stderr, "[wfmash] ERROR: --lift-paf runs nothing else: besides --lift IN.bed, --lift-out FILE and the target FASTA it takes the number of the GPU only\n"); return 1; }
   const bool pav_on = !pav_bed.empty() || pav_window_set;
   if (!pav_bed.empty() && pav_window_set) { fprintf(stderr, "[wfmash] ERROR: --pav IN.bed and --pav-window N exclude each other\n"); return 1; }
@@ -404,6 +428,15 @@ int main(int argc, char** argv) {
     if (prc != WFM_OK) fprintf(stderr, "[wfmash::pav] ERROR: %s\n", wfm_last_error(hp));
     wfm_destroy(hp);
     return prc == WFM_OK ? 0 : 2;
+  }
+  if (!chain_in.empty()) {  // the chain file of an existing PAF; nothing else runs
+    wfm_handle_t* hc = nullptr;
+    if (wfm_create(device, &hc) != WFM_OK) { fprintf(stderr, "[wfmash] ERROR: no usable MI355X device %d (there is no CPU fallback)\n", device); return 2; }
+    uint64_t cc[4] = {0, 0, 0, 0};
+    const int crc = wfmh_chain_paf(hc, target.c_str(), chain_in.c_str(), chain_out.c_str(), chain_swap ? 1 : 0, cc);
+    if (crc != WFM_OK) fprintf(stderr, "[wfmash::chain] ERROR: %s\n", wfm_last_error(hc));
+    wfm_destroy(hc);
+    return crc == WFM_OK ? 0 : 2;
   }
   if (!lift_in.empty()) {  // the BED through an existing PAF; nothing else runs
     wfm_handle_t* hl = nullptr;
@@ -545,6 +578,7 @@ int main(int argc, char** argv) {
     if (!variants_out.empty()) wfmh_set_variants(variants_out.c_str());
     if (!coverage_out.empty()) wfmh_set_coverage(coverage_out.c_str());
     if (!lift_bed.empty()) wfmh_set_lift(lift_bed.c_str(), lift_out.c_str());
+    if (!chain_out.empty()) wfmh_set_chain(chain_out.c_str(), chain_swap ? 1 : 0);
     if (pav_on) wfmh_set_pav(pav_bed.empty() ? nullptr : pav_bed.c_str(), pav_window, pav_out.c_str());
     rc = wfmh_align_paf_multi(hs.data(), (int)hs.size(), target.c_str(), q, mapping.c_str(), out.c_str(), &ap, &s);
     if (rc == WFM_OK)
@@ -580,6 +614,12 @@ int main(int argc, char** argv) {
       wfmh_lift_counts(lc);
       fprintf(stderr, "[wfmash::lift] %llu records lifted, %llu lines written, %llu of them empty, %llu BED lines skipped\n", (unsigned long long)lc[0],
               (unsigned long long)lc[1], (unsigned long long)lc[2], (unsigned long long)lc[3]);
+    }
+    if (!chain_out.empty() && rc == WFM_OK) {
+      uint64_t hc[4] = {0, 0, 0, 0};
+      wfmh_chain_counts(hc);
+      fprintf(stderr, "[wfmash::chain] %llu chains written, %llu blocks, %llu records refused\n", (unsigned long long)hc[0], (unsigned long long)hc[1],
+              (unsigned long long)hc[2]);
     }
     if (!coverage_out.empty() && rc == WFM_OK) {
       uint64_t cc[4] = {0, 0, 0, 0};

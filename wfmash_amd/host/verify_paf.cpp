@@ -17,6 +17,7 @@
 #include "aligner.hpp"
 #include "coverage_text.hpp"
 #include "lift_text.hpp"
+#include "chain_text.hpp"
 #include "pav_text.hpp"
 #include "parallel.hpp"
 #include "wflign_hip.hpp"
@@ -383,6 +384,63 @@ int wfmh_lift_paf(wfm_handle_t* h, const char* target_fasta, const char* aligned
     return WFM_OK;
   } catch (const std::exception& e) {
     if (set) wfm_liftset_free(set);
+    std::cerr << e.what() << std::endl;
+    wfm_set_error(h, e.what());
+    return WFM_E_ARG;
+  }
+}
+
+// --chain-paf: the chain file of an existing aligned PAF.  Lines go to the device in batches of runs, read and skipped by
+// wfmh_coverage_paf's rules (coverage::classify_line); nothing else runs.
+int wfmh_chain_paf(wfm_handle_t* h, const char* target_fasta, const char* aligned_paf, const char* out_path, int swap, uint64_t out[4]) {
+  if (!h || !target_fasta || !aligned_paf || !out_path) return WFM_E_ARG;
+  try {
+    std::shared_ptr<wfmash_host::FastaStore> target = wfmash_host::open_shared(target_fasta);
+    std::ifstream in(aligned_paf);
+    if (!in.is_open()) throw std::runtime_error(std::string("[wfmash::chain] cannot open ") + aligned_paf);
+    std::ofstream outstream(out_path);
+    if (!outstream.is_open()) throw std::runtime_error(std::string("[wfmash::chain] cannot open ") + out_path);
+    PafRuns pr(h, "chain", *target);
+    const uint64_t* skipped = pr.skipped;
+    std::lock_guard<std::mutex> lk(wflign::handle_lock(h));
+    uint64_t chains = 0, n_blocks = 0, refused = 0, next = 1;
+    std::vector<chain::Record> where;
+    std::vector<wfm_chain_prob_t> probs;
+    std::vector<wfm_chaincall_t> per;
+    std::string body, text;
+    auto flush = [&]() {
+      probs.resize(pr.probs.size());
+      per.resize(pr.probs.size());
+      for (size_t j = 0; j < probs.size(); ++j) probs[j] = wfm_chain_prob_t{pr.probs[j].runs_off, pr.probs[j].n_runs, chain::flags_of(swap != 0, where[j].rev)};
+      wfm_chain_block_t* blocks = nullptr;
+      size_t n = 0;
+      pr.device(wfm_chain_runs(h, probs.data(), probs.size(), pr.runs.data(), pr.runs.size(), &blocks, &n, per.data()), "chain");
+      body.clear(); text.clear();
+      for (size_t j = 0; j < probs.size(); ++j) {
+        if (per[j].flags) { pr.refused(1); ++refused; continue; }
+        chain::Ends e;
+        e.lead_dt = per[j].lead_dt; e.lead_dq = per[j].lead_dq; e.trail_dt = per[j].trail_dt; e.trail_dq = per[j].trail_dq; e.eq = per[j].eq;
+        chain::chain_body(body, where[j], swap != 0, e, (const chain::Block*)blocks + per[j].first, per[j].count);
+      }
+      wfm_free_chain(blocks);
+      chains += chain::number(body, &next, text);
+      n_blocks += n;
+      outstream << text;
+      where.clear();
+    };
+    pr.read(in, [&](const verify::Line& l) {
+      chain::Record r;
+      r.qname = l.qname; r.tname = l.tname; r.rev = l.rev;
+      r.qsize = (uint64_t)l.qlen; r.qs = (uint64_t)l.qs; r.qe = (uint64_t)l.qe; r.tsize = (uint64_t)l.tlen; r.ts = (uint64_t)l.ts; r.te = (uint64_t)l.te;
+      where.push_back(std::move(r));
+      return true;
+    }, flush);
+    const uint64_t all_skipped = pr.all_skipped();
+    std::cerr << "[wfmash::chain] " << chains << " chains written, " << n_blocks << " blocks, " << all_skipped << " lines skipped (" << skipped[1]
+              << " without an =XID cg:Z:, " << skipped[2] << " malformed, " << skipped[3] << " with an unknown target, " << skipped[4] << " with another tlen)" << std::endl;
+    if (out) { out[0] = chains; out[1] = n_blocks; out[2] = refused; out[3] = 0; }
+    return WFM_OK;
+  } catch (const std::exception& e) {
     std::cerr << e.what() << std::endl;
     wfm_set_error(h, e.what());
     return WFM_E_ARG;

@@ -4,6 +4,7 @@
 #include "wflign_hip.hpp"
 #include "parallel.hpp"
 #include "lift_text.hpp"
+#include "chain_text.hpp"
 #include "../csrc/wfa_handle.h"
 
 #include <algorithm>
@@ -78,6 +79,10 @@ std::atomic<bool> g_lift{false};
 std::mutex g_lift_mu;
 std::string g_lift_bed, g_lift_out;
 std::atomic<uint64_t> g_lift_counts[4];
+std::atomic<bool> g_chain{false}, g_chain_swap{false};
+std::mutex g_chain_mu;
+std::string g_chain_out;
+std::atomic<uint64_t> g_chain_counts[4];
 
 // --pav: the process-wide switch, the BED of target intervals or the window size, the file the align phase writes, and {records added,
 // rows written, union intervals, BED lines skipped} since it was set
@@ -654,6 +659,7 @@ struct PackedRuns {
   std::vector<uint32_t> runs;          // their trimmed ops as run words
   std::vector<size_t> rec;             // the record's index in the batch
   std::vector<uint64_t> ta, qa, q_len; // the target and query bases trimmed in front; the query bases the runs spell
+  std::vector<uint64_t> t_len;         // the target bases the runs spell
   uint64_t unknown = 0;                // records whose ops the runs cannot hold
   double ms = 0;                       // what the packing took
 };
@@ -665,7 +671,7 @@ PackedRuns pack_written(const BiwfaBatch& b) {
     if (!r.ok || !r.written) continue;
     const CigarOps& ops = r.ops;
     size_t ob = 0, oe = ops.size();
-    uint64_t ta = 0, qa = 0, q_len = 0;
+    uint64_t ta = 0, qa = 0, q_len = 0, t_len = 0;
     while (ob < oe && (ops[ob].second == 'I' || ops[ob].second == 'D')) { (ops[ob].second == 'D' ? ta : qa) += (uint64_t)ops[ob].first; ++ob; }
     while (oe > ob && (ops[oe - 1].second == 'I' || ops[oe - 1].second == 'D')) --oe;
     if (oe == ob) continue;
@@ -677,11 +683,12 @@ PackedRuns pack_written(const BiwfaBatch& b) {
       if (op > 3u || ops[k].first <= 0 || (uint32_t)ops[k].first >= (1u << 30)) { known = false; break; }
       pk.runs.push_back(((uint32_t)ops[k].first << 2) | op);
       if (op != 3u) q_len += (uint64_t)ops[k].first;
+      if (op != 2u) t_len += (uint64_t)ops[k].first;
     }
     if (!known) { pk.runs.resize((size_t)p.runs_off); ++pk.unknown; continue; }
     pk.probs.push_back(p);
     pk.rec.push_back(ri);
-    pk.ta.push_back(ta); pk.qa.push_back(qa); pk.q_len.push_back(q_len);
+    pk.ta.push_back(ta); pk.qa.push_back(qa); pk.q_len.push_back(q_len); pk.t_len.push_back(t_len);
   }
   pk.ms = ms_between(t0, Clock::now());
   return pk;
@@ -784,7 +791,65 @@ int lift_records(BiwfaBatch& b, const PackedRuns& pk) {
             pk.ms + ms_between(t0, Clock::now()), pk.ms + ms_between(t0, t1), ms_between(t1, t2), ms_between(t2, Clock::now()));
   return 0;
 }
+// ---- --chain: the same problems compacted to the blocks and gaps of a UCSC chain, ONE device call per batch (wfm_chain_runs); the two
+// windows are the writer's (lift_records' qs, qe and ts).  swap: the query is the chain's first side (chain_text.hpp).  A record's chain goes
+// into BiwfaRecord::chain without its id, which the ordered writer gives it.  A record the device refuses has no chain and is reported. ----
+static_assert(sizeof(chain::Block) == sizeof(wfm_chain_block_t), "chain_text.hpp restates wfm_chain_block_t");
+int chain_records(BiwfaBatch& b, const PackedRuns& pk) {
+  const auto t0 = Clock::now();
+  const bool swap = b.fmt.chain == 2;
+  for (BiwfaRecord& r : b.recs) r.chain.clear();
+  const size_t n = pk.probs.size();
+  std::vector<wfm_chain_prob_t> probs(n);
+  std::vector<chain::Record> where(n);
+  for (size_t j = 0; j < n; ++j) {
+    const BiwfaRecord& r = b.recs[pk.rec[j]];
+    chain::Record& cr = where[j];
+    cr.qname = r.query_name; cr.tname = r.target_name; cr.rev = r.query_is_rev;
+    cr.qsize = r.query_total_length; cr.tsize = r.target_total_length;
+    cr.qs = r.query_is_rev ? r.query_offset + (r.query_length - pk.qa[j] - pk.q_len[j]) : r.query_offset + pk.qa[j];
+    cr.qe = cr.qs + pk.q_len[j];
+    cr.ts = r.target_offset + pk.ta[j];
+    cr.te = cr.ts + pk.t_len[j];
+    probs[j] = wfm_chain_prob_t{pk.probs[j].runs_off, pk.probs[j].n_runs, chain::flags_of(swap, cr.rev)};
+  }
+  int rc = WFM_OK;
+  wfm_chain_block_t* blocks = nullptr;
+  size_t n_blocks = 0;
+  std::vector<wfm_chaincall_t> per(n);
+  auto t1 = t0;
+  if (n) {
+    std::lock_guard<std::mutex> lk(handle_lock(b.h));
+    t1 = Clock::now();
+    rc = wfm_chain_runs(b.h, probs.data(), n, pk.runs.data(), pk.runs.size(), &blocks, &n_blocks, per.data());
+    if (rc < 0 && b.stats) b.stats->error = wfm_last_error(b.h);
+  }
+  if (rc < 0) return rc;
+  const auto t2 = Clock::now();
+  std::atomic<uint64_t> chains{0}, refused{0};
+  for_each_record(n, b.fmt.threads, [&](size_t j) {
+    if (per[j].flags) { refused += 1; return; }
+    chain::Ends e;
+    e.lead_dt = per[j].lead_dt; e.lead_dq = per[j].lead_dq; e.trail_dt = per[j].trail_dt; e.trail_dq = per[j].trail_dq; e.eq = per[j].eq;
+    chain::chain_body(b.recs[pk.rec[j]].chain, where[j], swap, e, (const chain::Block*)blocks + per[j].first, per[j].count);
+    chains += per[j].count != 0;
+  });
+  wfm_free_chain(blocks);
+  g_chain_counts[0] += chains.load(); g_chain_counts[1] += n_blocks; g_chain_counts[2] += refused.load();
+  if (refused.load() || pk.unknown)
+    fprintf(stderr, "[wflign] chain: %llu records of a batch have NO chain (their runs cannot be held)\n", (unsigned long long)(refused.load() + pk.unknown));
+  if (getenv("WFM_DEBUG"))
+    fprintf(stderr, "[wflign] chain: %zu records, %zu runs, %zu blocks, %.1f ms (runs %.1f, device call %.1f, text %.1f)\n", n, pk.runs.size(), n_blocks,
+            pk.ms + ms_between(t0, Clock::now()), pk.ms + ms_between(t0, t1), ms_between(t1, t2), ms_between(t2, Clock::now()));
+  return 0;
+}
 }  // namespace
+
+void chain_path(std::string& out, bool& swap) {
+  std::lock_guard<std::mutex> lk(g_chain_mu);
+  out = g_chain.load() ? g_chain_out : std::string();
+  swap = g_chain_swap.load();
+}
 
 void lift_paths(std::string& bed, std::string& out) {
   std::lock_guard<std::mutex> lk(g_lift_mu);
@@ -855,11 +920,12 @@ int do_biwfa_alignment_batch(wfm_handle_t* h, std::vector<BiwfaRecord>& recs, co
   } else {
     for_each_record(n, fmt.threads, [&](size_t ri) { swizzle(b, ri); write_record(b, ri); });
   }
-  if (fmt.coverage || fmt.pav || fmt.liftset) {  // one packing for the stages that are on; each makes its own device call
+  if (fmt.coverage || fmt.pav || fmt.liftset || fmt.chain) {  // one packing for the stages that are on; each makes its own device call
     const PackedRuns pk = pack_written(b);
     if (fmt.coverage && (rc = coverage_records(b, pk)) < 0) return rc;
     if (fmt.pav && (rc = pav_records(b, pk)) < 0) return rc;
     if (fmt.liftset && (rc = lift_records(b, pk)) < 0) return rc;
+    if (fmt.chain && (rc = chain_records(b, pk)) < 0) return rc;
   }
   if (dbg)
     fprintf(stderr, "[wflign] %zu records: main alignment + runs + scans %.1f ms (incl. waiting for the device), patches %.1f ms (%zu tails scanned after their heads), swizzle + records %.1f ms\n",
@@ -914,6 +980,23 @@ void wfmh_set_lift(const char* bed_path_or_null, const char* out_path_or_null) {
     wflign::g_lift_out = on ? out_path_or_null : "";
   }
   wflign::g_lift.store(on);
+}
+
+void wfmh_set_chain(const char* path_or_null, int swap) {
+  for (auto& a : wflign::g_chain_counts) a.store(0);
+  const bool on = path_or_null && *path_or_null;
+  {
+    std::lock_guard<std::mutex> lk(wflign::g_chain_mu);
+    wflign::g_chain_out = on ? path_or_null : "";
+  }
+  wflign::g_chain_swap.store(on && swap != 0);
+  wflign::g_chain.store(on);
+}
+
+int wfmh_chain_counts(uint64_t out[4]) {
+  if (!out) return WFM_E_ARG;
+  for (int q = 0; q < 4; ++q) out[q] = wflign::g_chain_counts[q].load();
+  return WFM_OK;
 }
 
 void wfmh_set_pav(const char* bed_path_or_null, uint64_t window, const char* out_path_or_null) {

@@ -23,6 +23,8 @@
 //                      object, one wfm_pav_add call (runs alone again)
 //   lift_records       --lift only: the BED intervals lifted through the runs of every record WRITTEN, one wfm_lift_runs call
 //                      (runs alone again), the record's lines into BiwfaRecord::lift
+//   chain_records      --chain only: the runs of every record WRITTEN compacted to the blocks and gaps of a UCSC chain, one
+//                      wfm_chain_runs call (runs alone again), the record's chain without its id into BiwfaRecord::chain
 // and CIGARs are runs (count, op) from the device to the record's text: nothing is expanded to one byte per base.
 #pragma once
 
@@ -81,6 +83,7 @@ struct BiwfaRecord {
   bool written = false;              // the filters let the record's line through (write_record)
   uint32_t pav_group = 0;            // --pav: the column of the query sequence's group
   std::string lift;                  // --lift: the lines of the BED intervals the record's target span overlaps, each with its newline ("" if off or not written)
+  std::string chain;                 // --chain: the record's chain without its id (chain_text.hpp; "" if off, not written, refused or without a block)
   uint32_t tags = 0;                 // WFM_PF_* of the main alignment | of the head patch << 8 | of the tail patch << 16 (diagnostics: WFM_RECORD_TAGS)
 };
 
@@ -123,6 +126,7 @@ struct OutputFormat {
   wfm_pav_t* pav = nullptr;            // --pav: the presence object of the batch's handle (null: the stage is not run)
   const wfm_liftset_t* liftset = nullptr;                   // --lift: the intervals on the batch's handle (null: the stage is not run) ...
   const std::vector<lift::Interval>* lift_intervals = nullptr;  // ... and as the BED had them, in the set's order
+  int chain = 0;                       // --chain: 1 = the chain of every record written, 2 = the swapped one (0: the stage is not run)
 };
 
 // --variants: the file wfmh_set_variants named ("" while the switch is off); the align phase writes the batches' BiwfaRecord::vcf to it
@@ -137,6 +141,9 @@ void coverage_finished(uint64_t covered, uint64_t depth_sum, uint64_t intervals)
 // has read the BED: the lines it skipped
 void lift_paths(std::string& bed, std::string& out);
 void lift_bed_read(uint64_t skipped);
+
+// --chain: the file wfmh_set_chain named ("" while the switch is off) and whether the two sides change places
+void chain_path(std::string& out, bool& swap);
 
 // --pav: the BED, the window size and the file wfmh_set_pav named (out "" while the switch is off; one of bed and window is set), and what
 // the align phase adds to the counts once it has written the file: its rows, the union's intervals, the BED lines it skipped
