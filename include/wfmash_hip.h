@@ -61,6 +61,7 @@ extern "C" {
 #define WFM_E_NOMEM        (-4)
 #define WFM_E_UNSUPPORTED  (-5)   /* e.g. penalties whose score scope exceeds the ring */
 #define WFM_E_ARENA        (-6)   /* caller's ops arena too small */
+#define WFM_E_INTERNAL     (-7)   /* the library's own invariant did not hold (wfm_sites_table: a hash collision); see wfm_last_error */
 
 /* per-problem status (wfm_result_t.status); 0 mirrors WF_STATUS_ALG_COMPLETED
  * tested at wflign.cpp:150,307,399 */
@@ -566,6 +567,63 @@ int  wfm_pav_import(wfm_handle_t* h, wfm_pav_t* pav, const wfm_pav_seg_t* segs, 
 int  wfm_pav_matrix(wfm_handle_t* h, wfm_pav_t* pav, const wfm_lift_iv_t* iv, size_t n_iv, uint32_t* out);
 int  wfm_pav_counts(const wfm_pav_t* pav, uint64_t out[3]);
 void wfm_pav_free_list(void* p);
+
+/* ---- the variants of many records joined into sites, and a haploid genotype per (site, group) ----
+ * wfm_call_variants names the differences of ONE record.  A sites object takes the variants of many records, each with a GLOBAL position
+ * and the group of its record, and the = runs of the same records, and answers with the distinct sites and a table sites x groups.
+ *
+ * A VARIANT is {pos, kind, group, ref_len, alt_len, off}: what wfm_call_variants calls (WFM_VAR_SNV / _INS / _DEL, without the MASKED
+ * bit: the caller leaves masked SNVs out), pos = the global position of its first REF base, REF = alleles[off .. off + ref_len), ALT the
+ * alt_len bytes behind.  The allele bytes are folded to upper case on the device: a soft-masked record does not make a second site.
+ * A SITE is a distinct (pos, kind, REF bytes, ALT bytes).  Sites are biallelic; nothing is joined into multi-allelic lines.
+ * CELL (site, g), haploid:
+ *   '1'  at least one variant of group g is exactly this site;
+ *   '0'  otherwise, if the whole REF span [pos, pos + ref_len) lies inside the union of the = runs of group g's records -- = runs only,
+ *        not =/X; abutting segments of several records merge, as in the pav union; another group's bases never count;
+ *   '.'  otherwise: not aligned, under a D, under an X that spells another ALT, or only partly covered.
+ * So a group with ANOTHER insertion at the same anchor, = on the anchor, is '0' on this line and '1' on its own (the convention of
+ * bcftools norm -m-), and '1' wins over '0' where overlapping records of one group disagree.  The table is a set function of (variants,
+ * = runs): the order of records, calls, objects and devices does not change a byte of it.
+ *
+ * wfm_sites_create: wfm_pav_create's limits and refusals (n_bases < 2^40, n_groups < 2^24).  The object is used with the handle it was
+ *   made on and freed before it; it keeps its own device blocks.
+ * wfm_sites_add_variants: appends.  WFM_E_ARG with a message, NOTHING added and the handle usable, for: a kind beyond SNV/INS/DEL;
+ *   lengths that do not fit the kind (SNV 1/1, INS 1/L+1, DEL L+1/1, L >= 1); pos + ref_len > n_bases; group >= n_groups; an allele
+ *   range that leaves alleles[0 .. bytes); more than 2^31 - 1 variants in the object.
+ * wfm_sites_add_ref: wfm_pav_add's arguments, flags and return value; one segment per maximal stretch of = RUNS (an X ends a stretch)
+ *   goes to a per-group union of its own.  Where the raw part of that list exceeds WFM_SITES_MB MiB (environment, 256) the union is
+ *   taken at once.
+ * wfm_sites_table: keys k1 = pos << 2 | kind, k2 = a 64-bit hash of the lengths and the folded bytes, k3 = group.  The hash is a
+ *   polynomial modulo 2^64 whose per-slice partials add up exactly: alleles of up to WFM_SITES_SLICE bytes (REF + ALT) go one per lane,
+ *   longer ones one slice per lane, WFM_SITES_TASK bytes per workgroup.  Three stable radix sorts (k3, k2, k1), each over the bits its
+ *   keys can have.  Sorted record i heads a site iff i == 0, or (k1, k2) differ from i - 1's, or the lengths or BYTES differ (long
+ *   alleles are compared by workgroups).  Equal keys with different bytes is a COLLISION: counted, and if there is one the call fails
+ *   with WFM_E_INTERNAL and a message and returns nothing -- a site is never split or merged silently.  WFM_SITES_HASH_BITS (environment,
+ *   per call, 64) cuts k2 to its low bits, for tests.  Returns the sites in ascending pos (the order among the sites of one pos is a
+ *   function of the set), one representative's bytes per site (*alleles, off into it), and gt: n_sites * n_groups bytes, row-major.  Rows
+ *   come down in chunks of at most WFM_SITES_OUT_MB MiB (environment, per call, 256; one row at least).  Host memory owned by the
+ *   caller (wfm_sites_free_list each).  An empty object: WFM_OK, NULLs and 0.
+ * wfm_sites_export / _import: the raw variants and their (folded) bytes as add_variants takes them, the = union as wfm_pav_seg_t; the
+ *   merge of the objects of several devices is an import.
+ * wfm_sites_counts: out = {variants added (import included), distinct sites of the last table, = union intervals after the last union,
+ *   collisions of the last table}. */
+typedef struct wfm_sites wfm_sites_t;
+typedef struct { uint64_t pos; uint32_t kind, group; uint32_t ref_len, alt_len; uint64_t off; } wfm_site_var_t;             /* 32 bytes */
+typedef struct { uint64_t pos; uint32_t kind, n_carrier_groups; uint32_t ref_len, alt_len; uint64_t off; } wfm_site_t;     /* 32 bytes */
+#define WFM_SITES_SLICE 64       /* allele bytes one lane hashes or compares */
+#define WFM_SITES_TASK 16384     /* allele bytes of a long allele pair one workgroup hashes or compares */
+int  wfm_sites_create(wfm_handle_t* h, uint64_t n_bases, uint32_t n_groups, wfm_sites_t** s);
+void wfm_sites_free(wfm_sites_t* s);
+int  wfm_sites_add_variants(wfm_handle_t* h, wfm_sites_t* s, const wfm_site_var_t* vars, size_t n, const char* alleles, size_t bytes);
+int  wfm_sites_add_ref(wfm_handle_t* h, wfm_sites_t* s, const wfm_pav_prob_t* probs, size_t n, const uint32_t* runs, size_t n_runs_total,
+                       uint32_t* flags_out);
+int  wfm_sites_table(wfm_handle_t* h, wfm_sites_t* s, wfm_site_t** sites, size_t* n_sites, char** alleles, size_t* bytes, char** gt);
+int  wfm_sites_export(wfm_handle_t* h, wfm_sites_t* s, wfm_site_var_t** vars, size_t* n, char** alleles, size_t* bytes, wfm_pav_seg_t** segs,
+                      size_t* n_segs);
+int  wfm_sites_import(wfm_handle_t* h, wfm_sites_t* s, const wfm_site_var_t* vars, size_t n, const char* alleles, size_t bytes,
+                      const wfm_pav_seg_t* segs, size_t n_segs);
+int  wfm_sites_counts(const wfm_sites_t* s, uint64_t out[4]);
+void wfm_sites_free_list(void* p);
 
 /* ---- every score proved optimal by a banded DP ----
  * What wfm_check_runs leaves out.  For every problem of the seqset s whose result claims a score S = res[i].score, a classical

@@ -257,6 +257,26 @@ void wfmh_set_pav(const char* bed_path_or_null, uint64_t window, const char* out
 int  wfmh_pav_counts(uint64_t out[4]);
 int  wfmh_pav_paf(wfm_handle_t* h, const char* target_fasta, const char* query_fasta_or_null, const char* aligned_paf, const char* bed_path_or_null,
                   uint64_t window, const char* out_path, uint64_t out[4]);
+/* ---- one sorted VCF of all records' variants with a haploid genotype per group of query sequences (wfm_sites_*, wfmash_hip.h) ----
+ * wfmh_set_genotypes(path): from now on every batch of wfmh_align_paf[_multi] calls the variants of its records (as wfmh_set_variants does,
+ * whether that switch is on or not: its file and counts do not change) and, behind the record writers, adds those of every record WRITTEN
+ * -- masked SNVs left out, positions global, the group of the query sequence as wfmh_set_pav has it -- and the same records' runs to the
+ * handle's sites object: two device calls per batch.  With wfmh_set_left_align they are the normalised runs' (give both: otherwise one
+ * indel in a repeat can be two sites).  Once the workers are done the objects of the handles are merged (export, import), the table is
+ * taken once on the device and `path` is written: --variants' header, AC and AN, FORMAT GT, the columns #CHROM .. INFO FORMAT and the
+ * group keys, then one line per distinct site, "CHROM POS . REF ALT . . AC=a;AN=n GT" and one cell per group ('1' carried, '0' the REF
+ * span under = bases of the group, '.' neither), sorted by (target sequence in index order, POS, REF bytes, ALT bytes).  The file is a set
+ * function of the records written: it does not depend on the number of devices, handles, threads or the order of the batches.  NULL or ""
+ * switches it off.  Every call zeroes the counts.
+ * wfmh_genotypes_counts: out = {records added, sites written, variants merged away (variants added - sites), records left alone}. */
+void wfmh_set_genotypes(const char* path_or_null);
+int  wfmh_genotypes_counts(uint64_t out[4]);
+/* Test hook (no GPU): the text side alone (genotype_text.hpp).  tnames / lengths: the n_t target sequences; keys: the n_groups columns;
+ * sites: n_sites x {pos, ref_len, alt_len, off} as four uint64 each, pos global, in ascending pos; alleles: their bytes; gt: n_sites x
+ * n_groups cells.  Returns the header and the lines in file order: malloc'd, wfmh_free. */
+char* wfmh_test_genotype_text(const char* version, const char* const* tnames, const uint64_t* lengths, int n_t, const char* const* keys, int n_groups,
+                              const uint64_t* sites, size_t n_sites, const char* alleles, const char* gt);
+
 /* Test hook (no GPU): the text side alone (pav_text.hpp).  names: n_q query names; lengths: n_t target lengths; window: --pav-window's.
  * Returns "#key<TAB>name<TAB>key<TAB>column" per name, the header line, then one row per window with cell g = (row number + g): malloc'd,
  * wfmh_free. */

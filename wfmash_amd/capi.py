@@ -53,6 +53,8 @@ EXPORTS = [
     "wfm_chain_runs", "wfm_free_chain",
     "wfm_pav_create", "wfm_pav_free", "wfm_pav_add", "wfm_pav_union", "wfm_pav_export", "wfm_pav_import", "wfm_pav_matrix", "wfm_pav_counts",
     "wfm_pav_free_list",
+    "wfm_sites_create", "wfm_sites_free", "wfm_sites_add_variants", "wfm_sites_add_ref", "wfm_sites_table", "wfm_sites_export", "wfm_sites_import",
+    "wfm_sites_counts", "wfm_sites_free_list",
     "wfm_sketch_intersections",
 ]
 ISECT_LDS_MAX = 4096  # WFM_ISECT_LDS_MAX: the longest column sketch wfm_sketch_intersections searches in LDS
@@ -84,6 +86,10 @@ WFM_CHAIN_SPANS = 2
 # wfm_pav_* (include/wfmash_hip.h): why a problem added nothing, the segments one workgroup takes in the scans of the union
 WFM_PAV_SPANS = 2
 WFM_PAV_SCAN_BLOCK = 1024
+# wfm_sites_* (include/wfmash_hip.h): the allele bytes one lane / one workgroup hashes or compares, the code of a hash collision
+WFM_SITES_SLICE = 64
+WFM_SITES_TASK = 16384
+WFM_E_ARG, WFM_E_INTERNAL = -3, -7
 # wfm_check_optimal (include/wfmash_hip.h): what a problem's score was flagged for, and the band widths at which the kernel changes form
 WFM_OPT_NOT_CHECKED, WFM_OPT_SKIPPED, WFM_OPT_CHEAPER, WFM_OPT_UNREACHED = 1, 2, 4, 8
 OPT_NAMES = ("NOT_CHECKED", "SKIPPED", "CHEAPER", "UNREACHED")
@@ -204,6 +210,8 @@ CHAINCALL_DTYPE = np.dtype([("flags", "<u4"), ("n_runs", "<u4"), ("first", "<u8"
 
 PAV_PROB_DTYPE = np.dtype([("base", "<u8"), ("runs_off", "<u8"), ("n_runs", "<u4"), ("group", "<u4")])
 PAV_SEG_DTYPE = np.dtype([("start", "<u8"), ("length", "<u4"), ("group", "<u4")])
+SITE_VAR_DTYPE = np.dtype([("pos", "<u8"), ("kind", "<u4"), ("group", "<u4"), ("ref_len", "<u4"), ("alt_len", "<u4"), ("off", "<u8")])
+SITE_DTYPE = np.dtype([("pos", "<u8"), ("kind", "<u4"), ("n_carrier_groups", "<u4"), ("ref_len", "<u4"), ("alt_len", "<u4"), ("off", "<u8")])
 
 
 class OptCheck(C.Structure):
@@ -827,6 +835,131 @@ class Pav:
         return tuple(int(v) for v in out)
 
 
+class Sites:
+    """wfm_sites_t: the variants of many records (global position, group, alleles) and the = runs of the same records, on the handle's device;
+    .table() joins them into distinct sites and a sites x groups table of '0' / '1' / '.' (include/wfmash_hip.h).  Close it before its handle."""
+
+    def __init__(self, handle, n_bases, n_groups):
+        self._h, self._L = handle, handle._L
+        self.n_bases, self.n_groups = int(n_bases), int(n_groups)
+        self._p = None
+        L = self._L
+        P = C.POINTER
+        L.wfm_sites_create.restype = C.c_int
+        L.wfm_sites_create.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, P(C.c_void_p)]
+        L.wfm_sites_free.restype = None
+        L.wfm_sites_free.argtypes = [C.c_void_p]
+        L.wfm_sites_add_variants.restype = C.c_int
+        L.wfm_sites_add_variants.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_char_p, C.c_size_t]
+        L.wfm_sites_add_ref.restype = C.c_int
+        L.wfm_sites_add_ref.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.wfm_sites_table.restype = C.c_int
+        L.wfm_sites_table.argtypes = [C.c_void_p, C.c_void_p, P(C.c_void_p), P(C.c_size_t), P(C.c_void_p), P(C.c_size_t), P(C.c_void_p)]
+        L.wfm_sites_export.restype = C.c_int
+        L.wfm_sites_export.argtypes = [C.c_void_p, C.c_void_p, P(C.c_void_p), P(C.c_size_t), P(C.c_void_p), P(C.c_size_t), P(C.c_void_p), P(C.c_size_t)]
+        L.wfm_sites_import.restype = C.c_int
+        L.wfm_sites_import.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t]
+        L.wfm_sites_counts.restype = C.c_int
+        L.wfm_sites_counts.argtypes = [C.c_void_p, P(C.c_uint64)]
+        L.wfm_sites_free_list.restype = None
+        L.wfm_sites_free_list.argtypes = [C.c_void_p]
+        if not 0 <= self.n_groups < (1 << 32):
+            raise WfmError(f"wfm_sites_create: {self.n_groups} groups do not fit 32 bits")
+        p = C.c_void_p()
+        rc = L.wfm_sites_create(handle._p, self.n_bases, self.n_groups, C.byref(p))
+        if rc != 0:
+            raise WfmError(f"wfm_sites_create failed ({rc}): {handle.last_error()}")
+        self._p = p
+
+    def close(self):
+        if self._p:
+            self._L.wfm_sites_free(self._p)
+            self._p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def pack(variants):
+        """[(pos, kind, group, ref bytes, alt bytes)] as (an array of wfm_site_var_t, the allele bytes)"""
+        v = np.zeros(len(variants), dtype=SITE_VAR_DTYPE)
+        parts, at = [], 0
+        for i, (pos, kind, group, ref, alt) in enumerate(variants):
+            v[i] = (pos, kind, group, len(ref), len(alt), at)
+            parts += [ref, alt]
+            at += len(ref) + len(alt)
+        return v, b"".join(parts)
+
+    def add_variants(self, variants, alleles=None):
+        """wfm_sites_add_variants.  variants: a list of (pos, kind, group, ref bytes, alt bytes), or, with `alleles`, an array of
+        wfm_site_var_t whose off point into those bytes."""
+        v, a = self.pack(variants) if alleles is None else (np.ascontiguousarray(variants, dtype=SITE_VAR_DTYPE), bytes(alleles))
+        rc = self._L.wfm_sites_add_variants(self._h._p, self._p, v.ctypes.data if len(v) else None, len(v), a if a else None, len(a))
+        if rc != 0:
+            raise WfmError(f"wfm_sites_add_variants failed ({rc}): {self._h.last_error()}")
+
+    def add_ref(self, problems, runs):
+        """wfm_sites_add_ref: Pav.add's arguments and flags; the = runs alone make segments."""
+        probs, probs_p = _run_problems(problems, PAV_PROB_DTYPE)
+        runs = np.ascontiguousarray(runs, dtype=np.uint32)
+        flags = np.zeros(max(len(problems), 1), dtype=np.uint32)
+        rc = self._L.wfm_sites_add_ref(self._h._p, self._p, probs_p, len(probs), runs.ctypes.data if len(runs) else None, len(runs), flags.ctypes.data)
+        if rc < 0:
+            raise WfmError(f"wfm_sites_add_ref failed ({rc}): {self._h.last_error()}")
+        assert rc == int(np.count_nonzero(flags[:len(problems)] & WFM_PAV_SPANS))
+        return flags[:len(problems)]
+
+    def _take(self, ptr, nbytes):
+        try:
+            return C.string_at(ptr, nbytes) if nbytes else b""
+        finally:
+            self._L.wfm_sites_free_list(ptr)
+
+    def table(self):
+        """wfm_sites_table: (sites as an array of wfm_site_t in ascending pos, their allele bytes, gt as a uint8 array [site, group] of
+        b'0' / b'1' / b'.')."""
+        sp, ap, gp, n, nb = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_size_t(0), C.c_size_t(0)
+        rc = self._L.wfm_sites_table(self._h._p, self._p, C.byref(sp), C.byref(n), C.byref(ap), C.byref(nb), C.byref(gp))
+        if rc != 0:
+            raise WfmError(f"wfm_sites_table failed ({rc}): {self._h.last_error()}")
+        if n.value == 0:
+            assert not sp.value and not ap.value and not gp.value and nb.value == 0
+        sites = np.frombuffer(self._take(sp, n.value * SITE_DTYPE.itemsize), dtype=SITE_DTYPE)
+        alleles = self._take(ap, nb.value)
+        gt = np.frombuffer(self._take(gp, n.value * self.n_groups), dtype=np.uint8).reshape(n.value, self.n_groups)
+        return sites, alleles, gt
+
+    def export(self):
+        """wfm_sites_export: (the raw variants as an array of wfm_site_var_t, their folded allele bytes, the = union as Pav.export gives it)."""
+        vp, ap, gp, n, nb, ns = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        rc = self._L.wfm_sites_export(self._h._p, self._p, C.byref(vp), C.byref(n), C.byref(ap), C.byref(nb), C.byref(gp), C.byref(ns))
+        if rc != 0:
+            raise WfmError(f"wfm_sites_export failed ({rc}): {self._h.last_error()}")
+        return (np.frombuffer(self._take(vp, n.value * SITE_VAR_DTYPE.itemsize), dtype=SITE_VAR_DTYPE), self._take(ap, nb.value),
+                np.frombuffer(self._take(gp, ns.value * PAV_SEG_DTYPE.itemsize), dtype=PAV_SEG_DTYPE))
+
+    def import_(self, variants, alleles, segs):
+        """wfm_sites_import: what export returned (of another object, of another device), appended."""
+        v = np.ascontiguousarray(variants, dtype=SITE_VAR_DTYPE)
+        e = np.ascontiguousarray(segs, dtype=PAV_SEG_DTYPE)
+        a = bytes(alleles)
+        rc = self._L.wfm_sites_import(self._h._p, self._p, v.ctypes.data if len(v) else None, len(v), a if a else None, len(a),
+                                      e.ctypes.data if len(e) else None, len(e))
+        if rc != 0:
+            raise WfmError(f"wfm_sites_import failed ({rc}): {self._h.last_error()}")
+
+    def counts(self):
+        """wfm_sites_counts: (variants added, distinct sites of the last table, = union intervals after the last union, collisions of the last table)."""
+        out = (C.c_uint64 * 4)()
+        rc = self._L.wfm_sites_counts(self._p, out)
+        if rc != 0:
+            raise WfmError(f"wfm_sites_counts failed ({rc})")
+        return tuple(int(v) for v in out)
+
+
 class Handle:
     """One handle per GPU (wfm_create)."""
 
@@ -1141,6 +1274,11 @@ class Handle:
         """wfm_pav_create: a presence object over n_bases target bases and n_groups groups on this handle's device; .add, .union, .export,
         .import_, .matrix, .counts, .close."""
         return Pav(self, n_bases, n_groups)
+
+    def sites(self, n_bases, n_groups):
+        """wfm_sites_create: a sites object over n_bases target bases and n_groups groups on this handle's device; .add_variants, .add_ref,
+        .table, .export, .import_, .counts, .close."""
+        return Sites(self, n_bases, n_groups)
 
     def coverage(self, n_bases):
         """wfm_coverage_create: a depth object over n_bases target bases on this handle's device."""
@@ -1509,6 +1647,7 @@ HOST_EXPORTS = ["wfmh_test_packed_lce", "wfmh_test_is_acgt", "wfmh_align_default
                 "wfmh_set_lift", "wfmh_lift_counts", "wfmh_lift_paf", "wfmh_test_lift_lines",
                 "wfmh_set_chain", "wfmh_chain_counts", "wfmh_chain_paf", "wfmh_test_chain_lines",
                 "wfmh_set_pav", "wfmh_pav_counts", "wfmh_pav_paf", "wfmh_test_pav_text",
+                "wfmh_set_genotypes", "wfmh_genotypes_counts", "wfmh_test_genotype_text",
                 "wfmh_ani_matrix", "wfmh_ani_matrix_rows", "wfmh_free_ani_rows", "wfmh_set_ani_matrix", "wfmh_test_ani_tsv"]
 
 
@@ -2122,6 +2261,54 @@ def host_pav_text(qnames, tnames, tlengths, window) -> str:
     p = f(qn, nq, tn, ln, nt, int(window))
     if not p:
         raise WfmError("wfmh_test_pav_text failed")
+    s = C.string_at(p).decode()
+    L.wfmh_free(p)
+    return s
+
+
+def set_genotypes(path) -> None:
+    """wfmh_set_genotypes: every later align_paf call of the process joins the variants of the records it writes into one sorted VCF with a
+    haploid GT column per group of query sequences, on the device, and writes it to `path` (None: off); zeroes the counts."""
+    f = _host().wfmh_set_genotypes
+    f.restype = None
+    f.argtypes = [C.c_char_p]
+    f(os.fsencode(path) if path else None)
+
+
+def genotypes_counts():
+    """wfmh_genotypes_counts: (records added, sites written, variants merged away, records left alone) since wfmh_set_genotypes."""
+    f = _host().wfmh_genotypes_counts
+    f.restype = C.c_int
+    f.argtypes = [C.POINTER(C.c_uint64)]
+    out = (C.c_uint64 * 4)()
+    rc = f(out)
+    if rc != 0:
+        raise WfmError(f"wfmh_genotypes_counts failed ({rc})")
+    return tuple(int(v) for v in out)
+
+
+def host_genotype_text(version, tnames, tlengths, keys, sites, rows) -> str:
+    """wfmh_test_genotype_text (no GPU): the header and the lines of --genotypes in file order.  sites: [(global pos, ref bytes, alt
+    bytes)] in ascending pos; rows: per site a string of len(keys) cells (include/wfmash_host.h)."""
+    L = _host()
+    f = L.wfmh_test_genotype_text
+    f.restype = C.c_void_p
+    f.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.POINTER(C.c_uint64), C.c_int, C.POINTER(C.c_char_p), C.c_int, C.POINTER(C.c_uint64), C.c_size_t,
+                  C.c_char_p, C.c_char_p]
+    nt, ng, ns = len(tnames), len(keys), len(sites)
+    tn = (C.c_char_p * max(nt, 1))(*[x.encode() if isinstance(x, str) else x for x in tnames])
+    ln = (C.c_uint64 * max(nt, 1))(*[int(x) for x in tlengths])
+    kn = (C.c_char_p * max(ng, 1))(*[x.encode() if isinstance(x, str) else x for x in keys])
+    flat, alleles = [], b""
+    for pos, ref, alt in sites:
+        flat += [int(pos), len(ref), len(alt), len(alleles)]
+        alleles += ref + alt
+    arr = (C.c_uint64 * max(len(flat), 1))(*flat)
+    gt = "".join(rows).encode()
+    assert len(gt) == ns * ng
+    p = f(version.encode(), tn, ln, nt, kn, ng, arr, ns, alleles, gt)
+    if not p:
+        raise WfmError("wfmh_test_genotype_text failed")
     s = C.string_at(p).decode()
     L.wfmh_free(p)
     return s

@@ -387,12 +387,13 @@ struct PavProb {
   uint64_t base, runs_off;
   uint32_t n_runs, group;
 };
-// flags: nprob; cnt: nprob, the segments each problem will write (0 where flagged); off: nprob + 1, their exclusive prefixes
+// flags: nprob; cnt: nprob, the segments each problem will write (0 where flagged); off: nprob + 1, their exclusive prefixes.  eq_only: a
+// segment is a maximal stretch of = runs (wfm_sites_add_ref), not of =/X runs (wfm_pav_add); the same for launch_pav_write
 void launch_pav_count(const uint32_t* runs, const PavProb* probs, int nprob, unsigned long long n_bases, uint32_t n_groups, uint32_t* flags,
-                      unsigned long long* cnt, unsigned long long* off, hipStream_t st);
+                      unsigned long long* cnt, unsigned long long* off, bool eq_only, hipStream_t st);
 // the segments of the problems, problem i's from slot off[i] of ks / ke on (the caller has made room for off[nprob] of them)
 void launch_pav_write(const uint32_t* runs, const PavProb* probs, int nprob, const uint32_t* flags, const unsigned long long* off,
-                      unsigned long long* ks, unsigned long long* ke, hipStream_t st);
+                      unsigned long long* ks, unsigned long long* ke, bool eq_only, hipStream_t st);
 // rocprim::radix_sort_pairs of (ks, ke) by ks into (ks2, ke2), bits [0, end_bit); tmp == nullptr: *tmp_bytes = what it needs
 hipError_t pav_sort(void* tmp, size_t* tmp_bytes, const unsigned long long* ks, unsigned long long* ks2, const unsigned long long* ke,
                     unsigned long long* ke2, unsigned long long n, unsigned end_bit, hipStream_t st);
@@ -407,6 +408,49 @@ void launch_pav_prefix(const unsigned long long* uks, const unsigned long long* 
 // the cells of rows [ra, rb), out[(j - ra) * n_groups + g]; iv: {start, end}, 16 bytes an interval
 void launch_pav_matrix(const unsigned long long* uks, const unsigned long long* uke, const unsigned long long* C, unsigned long long m, const void* iv,
                        unsigned long long ra, unsigned long long rb, uint32_t n_groups, uint32_t* out, hipStream_t st);
+// wfm_sites_* (wfa_sites.hip).  A variant is wfm_site_var_t as the caller wrote it, its REF at alle[off .. off + ref_len), its ALT behind.
+struct SiteVar {
+  uint64_t pos;
+  uint32_t kind, group;
+  uint32_t ref_len, alt_len;
+  uint64_t off;
+};
+struct SiteRow {  // wfm_site_t; off: still the representative's place in the object's allele block
+  uint64_t pos;
+  uint32_t kind, n_carrier_groups;
+  uint32_t ref_len, alt_len;
+  uint64_t off;
+};
+// what the table call has on the device; every array but tasks has n elements (first and gfirst n + 1)
+struct SitesWork {
+  unsigned long long *k1, *k2, *kg, *ks;  // pos << 2 | kind; the hash; a gathered key; a sorted key (in the end: the sorted k1, and kg the sorted k2)
+  uint32_t *k3, *sk3, *pa, *pb;           // the group; the sorted group; two permutations
+  uint32_t *first, *gfirst;               // per site its first sorted record and the distinct (site, group) pairs before it
+  uint8_t* flag;                          // per sorted record: 0 not a head, 1 a head by its keys, 2 long alleles still equal, 3 a head by a collision
+  const unsigned long long* tasks;        // record << 32 | piece, a piece = WFM_SITES_TASK bytes of a long allele pair
+  unsigned long long* aux;                // the blocks' sums: n / WFM_PAV_SCAN_BLOCK rounded up, + 1; then one word: the collisions
+};
+// upper case in place
+void launch_sites_fold(uint8_t* alle, unsigned long long bytes, hipStream_t st);
+// k1, k2 (masked to hash_bits), k3 of every variant, and pa = 0, 1, 2, ...
+void launch_sites_keys(const SiteVar* vars, const uint8_t* alle, uint32_t n, const SitesWork& w, unsigned long long n_tasks, unsigned hash_bits, hipStream_t st);
+// out[i] = in[perm[i]]
+void launch_sites_gather64(const unsigned long long* in, const uint32_t* perm, uint32_t n, unsigned long long* out, hipStream_t st);
+void launch_sites_gather32(const uint32_t* in, const uint32_t* perm, uint32_t n, uint32_t* out, hipStream_t st);
+// stable rocprim::radix_sort_pairs over bits [0, end_bit); tmp == nullptr: *tmp_bytes = what it needs
+hipError_t sites_sort64(void* tmp, size_t* tmp_bytes, const unsigned long long* k, unsigned long long* k2, const uint32_t* v, uint32_t* v2, uint32_t n,
+                        unsigned end_bit, hipStream_t st);
+hipError_t sites_sort32(void* tmp, size_t* tmp_bytes, const uint32_t* k, uint32_t* k2, const uint32_t* v, uint32_t* v2, uint32_t n, unsigned end_bit,
+                        hipStream_t st);
+// the heads of the sorted list (keys w.ks, w.kg, w.sk3; permutation perm; inv: n words of room), compacted: w.first, w.gfirst; the sites'
+// number in the low and the (site, group) pairs in the high half of w.aux[blocks], the collisions in w.aux[blocks + 1]
+void launch_sites_heads(const SiteVar* vars, const uint8_t* alle, uint32_t n, const SitesWork& w, const uint32_t* perm, uint32_t* inv,
+                        unsigned long long n_tasks, hipStream_t st);
+void launch_sites_rows(const SiteVar* vars, const uint32_t* perm, const uint32_t* first, const uint32_t* gfirst, uint32_t n_sites, SiteRow* rows, hipStream_t st);
+// the cells of rows [ra, rb), out[(s - ra) * n_groups + g] = '0' / '1' / '.'; (uks, uke, C, m): the = union as wfm_pav_union leaves it
+void launch_sites_gt(const SiteRow* rows, const uint32_t* first, const uint32_t* sk3, const unsigned long long* uks, const unsigned long long* uke,
+                     const unsigned long long* C, unsigned long long m, unsigned long long ra, unsigned long long rb, uint32_t n_groups, uint8_t* out,
+                     hipStream_t st);
 // wfm_check_optimal (wfa_optcheck.hip): a problem's forward byte copies, its ends-free allowances (clamped; 0 for the other modes),
 // its band of diagonals (wfa_optband.h) and, for the memory form, where its three row arrays begin in `rows` (32-bit elements)
 struct OptProb {

@@ -1,7 +1,8 @@
 // wfa_passes.hip -- the record passes of the C ABI (see include/wfmash_hip.h): host code that takes the final runs of a batch and
 // produces something from them -- the check against the bases, left-aligned gaps, cs strings, variants, target depth, lifted
-// intervals, the blocks of a chain, presence per group, the proof of optimality.  The kernels are in wfa_check.hip, wfa_leftalign.hip,
-// wfa_cs.hip, wfa_variants.hip, wfa_coverage.hip, wfa_lift.hip, wfa_chain.hip, wfa_pav.hip and wfa_optcheck.hip.
+// intervals, the blocks of a chain, presence per group, the sites and genotypes of many records, the proof of optimality.  The kernels are
+// in wfa_check.hip, wfa_leftalign.hip, wfa_cs.hip, wfa_variants.hip, wfa_coverage.hip, wfa_lift.hip, wfa_chain.hip, wfa_pav.hip,
+// wfa_sites.hip and wfa_optcheck.hip.
 //
 // Every pass has the same frame, written once below: it validates the run ranges before anything is launched, carves what the
 // call has on the device out of one block, launches, writes its output in chunks that fit a cap, and waits for the stream before
@@ -38,7 +39,7 @@ struct Carver {
   DevBuf<uint64_t>& buf;
   const char* pass;
   struct Slot { void* pp; size_t at; void (*set)(void* pp, uint64_t* at); };
-  Slot slots[12];
+  Slot slots[16];
   int n = 0;
   size_t words = 0;
   static size_t words64(size_t bytes) { return (bytes + 7) / 8; }
@@ -944,6 +945,7 @@ struct wfm_pav {
   DevBuf<uint64_t> work;                 // a call's problems, runs, flags, counts and offsets; the sorted copy and the block words; a chunk of rows
   DevBuf<uint64_t> tmp;                  // the sort's own
   uint64_t added = 0, unions = 0;
+  bool eq_only = false;                  // the = union of a sites object: a segment is a stretch of = runs, the limit WFM_SITES_MB
   unsigned long long* ks() const { return list; }
   unsigned long long* ke() const { return list + cap; }
 };
@@ -975,9 +977,9 @@ int pav_reserve(wfm_handle_t* h, wfm_pav_t* pav, size_t need) {
   return WFM_OK;
 }
 
-// the union where the raw part of the list has outgrown WFM_PAV_MB MiB
+// the union where the raw part of the list has outgrown WFM_PAV_MB MiB (the = union of a sites object: WFM_SITES_MB)
 int pav_maybe_union(wfm_handle_t* h, wfm_pav_t* pav) {
-  const double limit = std::max(0.0, env_decimal("WFM_PAV_MB", 256.0)) * 1048576.0;
+  const double limit = std::max(0.0, env_decimal(pav->eq_only ? "WFM_SITES_MB" : "WFM_PAV_MB", 256.0)) * 1048576.0;
   if (pav->n > pav->n_union && (double)(pav->n - pav->n_union) * 16.0 > limit) return wfm_pav_union(h, pav);
   return WFM_OK;
 }
@@ -1028,7 +1030,7 @@ int wfm_pav_add(wfm_handle_t* h, wfm_pav_t* pav, const wfm_pav_prob_t* probs, si
   if (int rc = cv.commit(h)) return rc;
   HIPCHK(h, hipMemcpyAsync(d_probs, probs, n * sizeof(PavProb), hipMemcpyHostToDevice, h->stream));
   if (n_runs_total) HIPCHK(h, hipMemcpyAsync(d_runs, runs, n_runs_total * 4, hipMemcpyHostToDevice, h->stream));
-  launch_pav_count(d_runs, d_probs, (int)n, pav->n_bases, pav->n_groups, d_flags, d_cnt, d_off, h->stream);
+  launch_pav_count(d_runs, d_probs, (int)n, pav->n_bases, pav->n_groups, d_flags, d_cnt, d_off, pav->eq_only, h->stream);
   HIPCHK(h, hipGetLastError());
   unsigned long long total = 0;
   HIPCHK(h, hipMemcpyAsync(flags_out, d_flags, n * 4, hipMemcpyDeviceToHost, h->stream));
@@ -1038,7 +1040,7 @@ int wfm_pav_add(wfm_handle_t* h, wfm_pav_t* pav, const wfm_pav_prob_t* probs, si
   for (size_t i = 0; i < n; ++i) spans += (flags_out[i] & WFM_PAV_SPANS) != 0;
   if (total) {
     if (int rc = pav_reserve(h, pav, pav->n + (size_t)total)) return rc;
-    launch_pav_write(d_runs, d_probs, (int)n, d_flags, d_off, pav->ks() + pav->n, pav->ke() + pav->n, h->stream);
+    launch_pav_write(d_runs, d_probs, (int)n, d_flags, d_off, pav->ks() + pav->n, pav->ke() + pav->n, pav->eq_only, h->stream);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));
     pav->n += (size_t)total;
@@ -1190,6 +1192,285 @@ int wfm_pav_counts(const wfm_pav_t* pav, uint64_t out[3]) {
 }
 
 void wfm_pav_free_list(void* p) { free(p); }
+
+// ---- the variants of many records joined into sites and genotypes (wfmash_hip.h; the kernels and the sorts: wfa_sites.hip) ----
+struct wfm_sites {
+  int device = 0;
+  uint64_t n_bases = 0;
+  uint32_t n_groups = 0;
+  wfm_pav_t* eq = nullptr;        // the = union, a pav object in its eq_only mode
+  SiteVar* vars = nullptr;        // the raw variants; off: into alle
+  size_t vcap = 0, n = 0;
+  uint8_t* alle = nullptr;        // their folded allele bytes
+  size_t acap = 0, bytes = 0;
+  std::vector<uint64_t> tasks;    // record << 32 | piece for every WFM_SITES_TASK bytes of a pair longer than WFM_SITES_SLICE
+  DevBuf<uint64_t> work;          // the table call's keys, permutations, flags and rows; a chunk of cells
+  DevBuf<uint64_t> tmp;           // the sorts' own
+  uint64_t added = 0, last_sites = 0, last_collisions = 0;
+};
+
+extern "C++" {
+namespace {
+static_assert(sizeof(wfm_site_var_t) == 32 && sizeof(SiteVar) == 32 && sizeof(wfm_site_t) == 32 && sizeof(SiteRow) == 32, "wfmash_hip.h states these sizes");
+constexpr size_t SITES_MAX_VARS = ((size_t)1 << 31) - 1;
+
+int sites_usable(wfm_handle_t* h, const wfm_sites_t* s) { return DeviceGuard::usable(h, s->device, "the sites object"); }
+
+// room for `need` elements of a block that holds `have`; what it holds moves with it
+template <class T>
+int sites_reserve(wfm_handle_t* h, T** blk, size_t* cap, size_t have, size_t need, const char* what) {
+  if (need <= *cap) return WFM_OK;
+  const size_t ncap = std::max<size_t>(need + need / 2, 4096);
+  T* nb = nullptr;
+  if (wfm_dmalloc((void**)&nb, ncap * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); h->err = std::string("out of device memory (") + what + ")"; return WFM_E_NOMEM; }
+  if (have) {
+    hipError_t e = hipMemcpyAsync(nb, *blk, have * sizeof(T), hipMemcpyDeviceToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) { wfm_dfree(nb); h->err = std::string("wfm_sites: ") + hipGetErrorString(e); return WFM_E_HIP; }
+  }
+  if (*blk) wfm_dfree(*blk);
+  *blk = nb;
+  *cap = ncap;
+  return WFM_OK;
+}
+
+int sites_refuse(wfm_handle_t* h, size_t i, const std::string& why) {
+  h->err = "wfm_sites_add_variants: variant " + std::to_string(i) + " " + why + "; nothing was added";
+  return WFM_E_ARG;
+}
+}  // namespace
+}  // extern "C++"
+
+int wfm_sites_create(wfm_handle_t* h, uint64_t n_bases, uint32_t n_groups, wfm_sites_t** s) {
+  if (!h || !s) return WFM_E_ARG;
+  *s = nullptr;
+  wfm_pav_t* eq = nullptr;
+  if (int rc = wfm_pav_create(h, n_bases, n_groups, &eq)) {
+    if (rc == WFM_E_ARG && !h->err.empty()) h->err = "wfm_sites_create: " + h->err;
+    return rc;
+  }
+  eq->eq_only = true;
+  std::unique_ptr<wfm_sites> p(new wfm_sites());
+  p->device = h->device;
+  p->n_bases = n_bases;
+  p->n_groups = n_groups;
+  p->eq = eq;
+  *s = p.release();
+  return WFM_OK;
+}
+
+void wfm_sites_free(wfm_sites_t* s) {
+  if (!s) return;
+  wfm_pav_free(s->eq);
+  DeviceGuard on(s->device);
+  s->work.release();
+  s->tmp.release();
+  if (s->vars) wfm_dfree(s->vars);
+  if (s->alle) wfm_dfree(s->alle);
+  delete s;
+}
+
+int wfm_sites_add_variants(wfm_handle_t* h, wfm_sites_t* s, const wfm_site_var_t* vars, size_t n, const char* alleles, size_t bytes) {
+  if (!h || !s || (n && !vars) || (bytes && !alleles)) return WFM_E_ARG;
+  if (n == 0) return WFM_OK;
+  if (int rc = sites_usable(h, s)) return rc;
+  if (n > SITES_MAX_VARS - s->n) { h->err = "wfm_sites_add_variants: more than 2^31 - 1 variants in one object; nothing was added"; return WFM_E_ARG; }
+  // everything is looked at before anything is added
+  std::vector<SiteVar> mine(n);
+  std::vector<uint64_t> tasks;
+  for (size_t i = 0; i < n; ++i) {
+    const wfm_site_var_t& v = vars[i];
+    if (v.kind > WFM_VAR_DEL) return sites_refuse(h, i, "has kind " + std::to_string(v.kind) + ", not SNV, INS or DEL");
+    const bool fits = v.kind == WFM_VAR_SNV ? (v.ref_len == 1 && v.alt_len == 1)
+                      : v.kind == WFM_VAR_INS ? (v.ref_len == 1 && v.alt_len >= 2)
+                                              : (v.ref_len >= 2 && v.alt_len == 1);
+    if (!fits) return sites_refuse(h, i, "has lengths " + std::to_string(v.ref_len) + " / " + std::to_string(v.alt_len) + " that do not fit its kind (SNV 1/1, INS 1/L+1, DEL L+1/1)");
+    if (v.pos > s->n_bases || v.ref_len > s->n_bases - v.pos) return sites_refuse(h, i, "ends beyond the " + std::to_string(s->n_bases) + " target bases");
+    if (v.group >= s->n_groups) return sites_refuse(h, i, "names group " + std::to_string(v.group) + ", not below " + std::to_string(s->n_groups));
+    const uint64_t len = (uint64_t)v.ref_len + v.alt_len;
+    if (v.off > bytes || len > bytes - v.off) return sites_refuse(h, i, "has alleles outside the " + std::to_string(bytes) + " allele bytes");
+    mine[i] = SiteVar{v.pos, v.kind, v.group, v.ref_len, v.alt_len, v.off + s->bytes};
+    if (len > WFM_SITES_SLICE)
+      for (uint64_t piece = 0; piece * WFM_SITES_TASK < len; ++piece) tasks.push_back((uint64_t)(s->n + i) << 32 | piece);
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  PassTimer tm(h);
+  if (int rc = sites_reserve(h, &s->vars, &s->vcap, s->n, s->n + n, "sites variants")) return rc;
+  if (int rc = sites_reserve(h, &s->alle, &s->acap, s->bytes, s->bytes + bytes, "sites alleles")) return rc;
+  HIPCHK(h, hipMemcpyAsync(s->vars + s->n, mine.data(), n * sizeof(SiteVar), hipMemcpyHostToDevice, h->stream));
+  if (bytes) {
+    HIPCHK(h, hipMemcpyAsync(s->alle + s->bytes, alleles, bytes, hipMemcpyHostToDevice, h->stream));
+    launch_sites_fold(s->alle + s->bytes, bytes, h->stream);
+    HIPCHK(h, hipGetLastError());
+  }
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  s->tasks.insert(s->tasks.end(), tasks.begin(), tasks.end());
+  s->n += n;
+  s->bytes += bytes;
+  s->added += n;
+  if (tm.on)
+    fprintf(stderr, "[wfm] sites add: %zu variants, %zu allele bytes, %zu long-allele tasks, %.3f ms (host clock, ends in a synchronise); the object holds %zu\n", n, bytes,
+            tasks.size(), tm.host_ms(), s->n);
+  return WFM_OK;
+}
+
+int wfm_sites_add_ref(wfm_handle_t* h, wfm_sites_t* s, const wfm_pav_prob_t* probs, size_t n, const uint32_t* runs, size_t n_runs_total, uint32_t* flags_out) {
+  if (!h || !s) return WFM_E_ARG;
+  if (int rc = sites_usable(h, s)) return rc;
+  return wfm_pav_add(h, s->eq, probs, n, runs, n_runs_total, flags_out);
+}
+
+int wfm_sites_table(wfm_handle_t* h, wfm_sites_t* s, wfm_site_t** sites, size_t* n_sites, char** alleles, size_t* bytes, char** gt) {
+  if (!h || !s || !sites || !n_sites || !alleles || !bytes || !gt) return WFM_E_ARG;
+  *sites = nullptr; *n_sites = 0; *alleles = nullptr; *bytes = 0; *gt = nullptr;
+  if (int rc = sites_usable(h, s)) return rc;
+  s->last_sites = s->last_collisions = 0;
+  if (s->n == 0) return WFM_OK;
+  if (int rc = wfm_pav_union(h, s->eq)) return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  PassTimer tm(h);
+  const uint32_t n = (uint32_t)s->n;
+  const size_t G = s->n_groups, sb = (n + WFM_PAV_SCAN_BLOCK - 1) / WFM_PAV_SCAN_BLOCK, n_tasks = s->tasks.size();
+  const int hb = env_num("WFM_SITES_HASH_BITS", 64);
+  const unsigned hash_bits = (unsigned)std::min(64, std::max(0, hb));
+  unsigned k1_bits = 2, g_bits = 0;
+  while (k1_bits < 64 && ((s->n_bases << 2 | 3) >> k1_bits) != 0) ++k1_bits;   // (k1 <= n_bases << 2 | 3)
+  while (g_bits < 32 && ((uint64_t)(G - 1) >> g_bits) != 0) ++g_bits;          // (k3 < n_groups, and n_groups >= 1: a variant names a group)
+  // chunks of whole rows that hold at most WFM_SITES_OUT_MB MiB of the table, and no more cells than one launch takes
+  const size_t cap = (size_t)std::min<unsigned long long>(cap_units("WFM_SITES_OUT_MB", G, 1), std::max<unsigned long long>(1, ((unsigned long long)1 << 30) / G));
+  SitesWork w{};
+  uint64_t* d_tasks;
+  SiteRow* d_rows;
+  uint8_t* d_gt;
+  Carver cv{s->work, "sites table"};
+  cv.piece(&w.k1, n); cv.piece(&w.k2, n); cv.piece(&w.kg, n); cv.piece(&w.ks, n);
+  cv.piece(&w.k3, n); cv.piece(&w.sk3, n); cv.piece(&w.pa, n); cv.piece(&w.pb, n);
+  cv.piece(&w.first, (size_t)n + 1); cv.piece(&w.gfirst, (size_t)n + 1);
+  cv.piece(&w.flag, n); cv.piece(&d_tasks, n_tasks); cv.piece(&w.aux, sb + 2);
+  if (int rc = cv.commit(h)) return rc;
+  w.tasks = (const unsigned long long*)d_tasks;
+  if (n_tasks) HIPCHK(h, hipMemcpyAsync(d_tasks, s->tasks.data(), n_tasks * 8, hipMemcpyHostToDevice, h->stream));
+  launch_sites_keys(s->vars, s->alle, n, w, n_tasks, hash_bits, h->stream);
+  HIPCHK(h, hipGetLastError());
+  // the sorts, least significant word first; cur: the permutation so far, oth: the other block.  Each asks for its own room first
+  uint32_t *cur = w.pa, *oth = w.pb;
+  auto sort64 = [&](const unsigned long long* keys, unsigned bits) -> int {
+    size_t tb = 0;
+    launch_sites_gather64(keys, cur, n, w.kg, h->stream);
+    HIPCHK(h, sites_sort64(nullptr, &tb, w.kg, w.ks, cur, oth, n, bits, h->stream));
+    if (s->tmp.ensure(tb / 8 + 2)) { h->err = "out of device memory (sites sort)"; return WFM_E_NOMEM; }
+    HIPCHK(h, sites_sort64(s->tmp.p, &tb, w.kg, w.ks, cur, oth, n, bits, h->stream));
+    std::swap(cur, oth);
+    return WFM_OK;
+  };
+  if (g_bits) {
+    size_t tb = 0;
+    HIPCHK(h, sites_sort32(nullptr, &tb, w.k3, w.sk3, cur, oth, n, g_bits, h->stream));
+    if (s->tmp.ensure(tb / 8 + 2)) { h->err = "out of device memory (sites sort)"; return WFM_E_NOMEM; }
+    HIPCHK(h, sites_sort32(s->tmp.p, &tb, w.k3, w.sk3, cur, oth, n, g_bits, h->stream));
+    std::swap(cur, oth);
+  }
+  if (hash_bits)
+    if (int rc = sort64(w.k2, hash_bits)) return rc;
+  if (int rc = sort64(w.k1, k1_bits)) return rc;
+  launch_sites_gather64(w.k2, cur, n, w.kg, h->stream);   // (w.ks: the sorted k1; w.kg: the sorted k2)
+  launch_sites_gather32(w.k3, cur, n, w.sk3, h->stream);
+  launch_sites_heads(s->vars, s->alle, n, w, cur, oth, n_tasks, h->stream);
+  HIPCHK(h, hipGetLastError());
+  unsigned long long tot[2] = {0, 0};
+  HIPCHK(h, hipMemcpyAsync(tot, w.aux + sb, 16, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  const size_t S = (size_t)(tot[0] & 0xffffffffull);
+  s->last_collisions = tot[1];
+  if (tot[1]) {
+    h->err = "wfm_sites_table: " + std::to_string(tot[1]) + " neighbours of the sorted list have equal keys (pos, kind, a " + std::to_string(hash_bits) +
+             "-bit hash of the alleles) and different alleles: a hash collision; nothing was written";
+    return WFM_E_INTERNAL;
+  }
+  if (S == 0 || S > n) { h->err = "wfm_sites_table: the heads do not add up"; return WFM_E_INTERNAL; }
+  const double t_join = tm.lap();
+  // the rows' block lies where the keys of the sorts lay (k1, k2: 16 n bytes and S <= n rows of 32 need k1 .. ks, which are read no more)
+  d_rows = (SiteRow*)w.k1;
+  // a chunk of cells: behind everything, in the handle's output block
+  if (h->outblk.ensure(Carver::words64(std::min(S, cap) * G) + 8)) { h->err = "out of device memory (sites cells)"; return WFM_E_NOMEM; }
+  d_gt = (uint8_t*)h->outblk.p;
+  launch_sites_rows(s->vars, cur, w.first, w.gfirst, (uint32_t)S, d_rows, h->stream);
+  HIPCHK(h, hipGetLastError());
+  const bool pinned = cs_pin_pieces(h);
+  std::unique_ptr<wfm_site_t, void (*)(void*)> rows((wfm_site_t*)malloc(S * sizeof(wfm_site_t)), free);
+  std::unique_ptr<char, void (*)(void*)> cells((char*)malloc(std::max<size_t>(S * G, 1)), free);
+  std::vector<char> folded(s->bytes);
+  if (!rows || !cells) { h->err = "out of host memory (sites table)"; return WFM_E_NOMEM; }
+  hipError_t e = cs_copy_down(h, pinned, (char*)rows.get(), (const uint8_t*)d_rows, S * sizeof(wfm_site_t));
+  if (e == hipSuccess) e = cs_copy_down(h, pinned, folded.data(), s->alle, s->bytes);
+  if (e != hipSuccess) { h->err = std::string("wfm_sites_table: ") + hipGetErrorString(e); return WFM_E_HIP; }
+  size_t chunks = 0;
+  for (size_t ra = 0, rb; ra < S && G; ra = rb, ++chunks) {
+    rb = chunk_end(ra, S, cap, [](size_t a, size_t b) { return (unsigned long long)(b - a); });
+    launch_sites_gt(d_rows, w.first, w.sk3, s->eq->ks(), s->eq->ke(), (const unsigned long long*)s->eq->c.p, s->eq->n, ra, rb, s->n_groups, d_gt, h->stream);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = cs_copy_down(h, pinned, cells.get() + ra * G, d_gt, (rb - ra) * G);  // (the block is the next chunk's)
+    if (e != hipSuccess) { h->err = std::string("wfm_sites_table: ") + hipGetErrorString(e); return WFM_E_HIP; }
+  }
+  // one representative's bytes per site, in site order
+  size_t ab = 0;
+  for (size_t i = 0; i < S; ++i) ab += (size_t)rows.get()[i].ref_len + rows.get()[i].alt_len;
+  char* out_alle = (char*)malloc(std::max<size_t>(ab, 1));
+  if (!out_alle) { h->err = "out of host memory (sites alleles)"; return WFM_E_NOMEM; }
+  size_t at = 0;
+  for (size_t i = 0; i < S; ++i) {
+    wfm_site_t& r = rows.get()[i];
+    const size_t len = (size_t)r.ref_len + r.alt_len;
+    memcpy(out_alle + at, folded.data() + r.off, len);
+    r.off = at;
+    at += len;
+  }
+  s->last_sites = S;
+  *sites = rows.release(); *n_sites = S; *alleles = out_alle; *bytes = ab; *gt = cells.release();
+  if (tm.on)
+    fprintf(stderr, "[wfm] sites table: %u variants (%zu long-allele tasks) to %zu sites in %.3f ms (keys, %u + %u + %u sorted bits, heads), %zu x %zu cells over %zu = intervals in %zu chunks, rows and bytes in %.3f ms (host clock)\n",
+            n, n_tasks, S, t_join, g_bits, hash_bits, k1_bits, S, G, s->eq->n, chunks, tm.lap());
+  return WFM_OK;
+}
+
+int wfm_sites_export(wfm_handle_t* h, wfm_sites_t* s, wfm_site_var_t** vars, size_t* n, char** alleles, size_t* bytes, wfm_pav_seg_t** segs, size_t* n_segs) {
+  if (!h || !s || !vars || !n || !alleles || !bytes || !segs || !n_segs) return WFM_E_ARG;
+  *vars = nullptr; *n = 0; *alleles = nullptr; *bytes = 0; *segs = nullptr; *n_segs = 0;
+  if (int rc = sites_usable(h, s)) return rc;
+  if (int rc = wfm_pav_export(h, s->eq, segs, n_segs)) return rc;
+  if (s->n == 0) return WFM_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  wfm_site_var_t* v = (wfm_site_var_t*)malloc(s->n * sizeof(wfm_site_var_t));
+  char* a = (char*)malloc(std::max<size_t>(s->bytes, 1));
+  const bool pinned = cs_pin_pieces(h);
+  hipError_t e = hipSuccess;
+  if (v && a) e = cs_copy_down(h, pinned, (char*)v, (const uint8_t*)s->vars, s->n * sizeof(wfm_site_var_t));
+  if (v && a && e == hipSuccess) e = cs_copy_down(h, pinned, a, s->alle, s->bytes);
+  if (!v || !a || e != hipSuccess) {
+    free(v); free(a); wfm_pav_free_list(*segs);
+    *segs = nullptr; *n_segs = 0;
+    if (e != hipSuccess) { h->err = std::string("wfm_sites_export: ") + hipGetErrorString(e); return WFM_E_HIP; }
+    h->err = "out of host memory (sites list)";
+    return WFM_E_NOMEM;
+  }
+  *vars = v; *n = s->n; *alleles = a; *bytes = s->bytes;
+  return WFM_OK;
+}
+
+int wfm_sites_import(wfm_handle_t* h, wfm_sites_t* s, const wfm_site_var_t* vars, size_t n, const char* alleles, size_t bytes, const wfm_pav_seg_t* segs,
+                     size_t n_segs) {
+  if (!h || !s) return WFM_E_ARG;
+  if (int rc = wfm_sites_add_variants(h, s, vars, n, alleles, bytes)) return rc;
+  return wfm_pav_import(h, s->eq, segs, n_segs);
+}
+
+int wfm_sites_counts(const wfm_sites_t* s, uint64_t out[4]) {
+  if (!s || !out) return WFM_E_ARG;
+  out[0] = s->added; out[1] = s->last_sites; out[2] = s->eq->n_union; out[3] = s->last_collisions;
+  return WFM_OK;
+}
+
+void wfm_sites_free_list(void* p) { free(p); }
 
 // ---- every score proved optimal by a banded DP (wfmash_hip.h; the band: wfa_optband.h; the kernel: wfa_optcheck.hip) ----
 int wfm_check_optimal(wfm_handle_t* h, const wfm_penalties_t* pen, const wfm_seqset_t* s, const wfm_result_t* res, uint64_t max_cells,

@@ -4,7 +4,8 @@
 //
 //   pav_count_kernel      one workgroup per problem.  wfa_scan.h's run_span takes the pattern span; the problem is refused (an empty run,
 //                         a span that leaves [0, n_bases] or does not fit 32 bits, a group that is not below n_groups) BEFORE anything is
-//                         written; then the number of maximal stretches of =/X runs: the segments the problem will write.
+//                         written; then the number of maximal stretches of =/X runs: the segments the problem will write.  (EQ: of = runs
+//                         alone, which is what wfm_sites_add_ref keeps; the write kernel likewise.)
 //   scan_sums_kernel      (wfa_scan.h) ONE workgroup: the counts to their exclusive prefixes over the problems; the blocks' sums likewise.
 //   pav_write_kernel      one workgroup per problem, rounds of 256 runs with three carries (cov_add_kernel's shape): the pattern advance and
 //                         the slot by wfa_scan.h's block_excl, the start of the stretch a run lies in by a running maximum over the heads'
@@ -40,6 +41,11 @@ constexpr int PAV_WAVES = PAV_THREADS / 64;
 constexpr unsigned PAV_SHIFT = 40;
 static_assert(WFM_PAV_SCAN_BLOCK == PAV_THREADS * 4, "a scan block is four segments per lane");
 
+// what a segment is made of: =/X runs (wfm_pav_add) or, EQ, = runs alone (wfm_sites_add_ref)
+template <bool EQ>
+__device__ __forceinline__ bool pav_in(uint32_t op) { return EQ ? op == OP_M : op <= OP_X; }
+
+template <bool EQ>
 __global__ __launch_bounds__(PAV_THREADS) void pav_count_kernel(const uint32_t* __restrict__ runs, const PavProb* __restrict__ probs,
                                                                 unsigned long long n_bases, uint32_t n_groups, uint32_t* __restrict__ flags,
                                                                 unsigned long long* __restrict__ cnt) {
@@ -59,12 +65,13 @@ __global__ __launch_bounds__(PAV_THREADS) void pav_count_kernel(const uint32_t* 
   }
   unsigned long long c = 0;
   for (uint32_t r = (uint32_t)tid; r < n; r += PAV_THREADS)
-    c += WFM_RUN_OP(my[r]) <= OP_X && (r + 1 == n || WFM_RUN_OP(my[r + 1]) > OP_X);
+    c += pav_in<EQ>(WFM_RUN_OP(my[r])) && (r + 1 == n || !pav_in<EQ>(WFM_RUN_OP(my[r + 1])));
   unsigned long long all;
   (void)block_excl<PAV_WAVES>(c, wtot, &all);
   if (tid == 0) { flags[blockIdx.x] = 0; cnt[blockIdx.x] = all; }
 }
 
+template <bool EQ>
 __global__ __launch_bounds__(PAV_THREADS) void pav_write_kernel(const uint32_t* __restrict__ runs, const PavProb* __restrict__ probs,
                                                                 const uint32_t* __restrict__ flags, const unsigned long long* __restrict__ off,
                                                                 unsigned long long* __restrict__ ks, unsigned long long* __restrict__ ke) {
@@ -82,9 +89,9 @@ __global__ __launch_bounds__(PAV_THREADS) void pav_write_kernel(const uint32_t* 
     const bool valid = r < n;
     const uint32_t run = valid ? my[r] : 0u;
     const uint32_t len = WFM_RUN_LEN(run), op = WFM_RUN_OP(run);
-    const bool aligned = valid && op <= OP_X;
-    const bool head = aligned && (r == 0 || WFM_RUN_OP(my[r - 1]) > OP_X);
-    const bool tail = aligned && (r + 1 == n || WFM_RUN_OP(my[r + 1]) > OP_X);
+    const bool aligned = valid && pav_in<EQ>(op);
+    const bool head = aligned && (r == 0 || !pav_in<EQ>(WFM_RUN_OP(my[r - 1])));
+    const bool tail = aligned && (r + 1 == n || !pav_in<EQ>(WFM_RUN_OP(my[r + 1])));
     unsigned long long tp, ts, th;
     const unsigned long long pp = pr.base + carry_p + block_excl<PAV_WAVES>((valid && op != OP_I) ? len : 0u, wtot, &tp);
     const unsigned long long slot = carry_s + block_excl<PAV_WAVES>(tail ? 1u : 0u, wtot, &ts);
@@ -191,16 +198,18 @@ void scan_words(const unsigned long long* words, unsigned long long n, unsigned 
 }  // namespace
 
 void launch_pav_count(const uint32_t* runs, const PavProb* probs, int nprob, unsigned long long n_bases, uint32_t n_groups, uint32_t* flags,
-                      unsigned long long* cnt, unsigned long long* off, hipStream_t st) {
+                      unsigned long long* cnt, unsigned long long* off, bool eq_only, hipStream_t st) {
   if (nprob <= 0) return;
-  hipLaunchKernelGGL(pav_count_kernel, dim3((unsigned)nprob), dim3(PAV_THREADS), 0, st, runs, probs, n_bases, n_groups, flags, cnt);
+  if (eq_only) hipLaunchKernelGGL(pav_count_kernel<true>, dim3((unsigned)nprob), dim3(PAV_THREADS), 0, st, runs, probs, n_bases, n_groups, flags, cnt);
+  else hipLaunchKernelGGL(pav_count_kernel<false>, dim3((unsigned)nprob), dim3(PAV_THREADS), 0, st, runs, probs, n_bases, n_groups, flags, cnt);
   scan_words(cnt, (unsigned long long)nprob, off, st);  // off[i] = the segments of the problems before i, off[nprob] = all of them
 }
 
 void launch_pav_write(const uint32_t* runs, const PavProb* probs, int nprob, const uint32_t* flags, const unsigned long long* off,
-                      unsigned long long* ks, unsigned long long* ke, hipStream_t st) {
+                      unsigned long long* ks, unsigned long long* ke, bool eq_only, hipStream_t st) {
   if (nprob <= 0) return;
-  hipLaunchKernelGGL(pav_write_kernel, dim3((unsigned)nprob), dim3(PAV_THREADS), 0, st, runs, probs, flags, off, ks, ke);
+  if (eq_only) hipLaunchKernelGGL(pav_write_kernel<true>, dim3((unsigned)nprob), dim3(PAV_THREADS), 0, st, runs, probs, flags, off, ks, ke);
+  else hipLaunchKernelGGL(pav_write_kernel<false>, dim3((unsigned)nprob), dim3(PAV_THREADS), 0, st, runs, probs, flags, off, ks, ke);
 }
 
 hipError_t pav_sort(void* tmp, size_t* tmp_bytes, const unsigned long long* ks, unsigned long long* ks2, const unsigned long long* ke,

@@ -4,6 +4,7 @@
 #include "lift_text.hpp"
 #include "chain_text.hpp"
 #include "pav_text.hpp"
+#include "genotype_text.hpp"
 #include "map_queue.hpp"
 #include "parallel.hpp"
 #include "../csrc/wfa_handle.h"
@@ -386,7 +387,8 @@ std::string Aligner::gather_text(Summary& sum, const std::vector<Fetched>& fetch
 std::string Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<std::string>& lines, int threads, Summary& sum, uint64_t first_row,
                                  std::string* vcf, wfm_coverage_t* coverage, const std::vector<uint64_t>* seq_offsets, std::string* lift,
                                  const wfm_liftset_t* liftset, const std::vector<lift::Interval>* lift_intervals, wfm_pav_t* pav,
-                                 const std::vector<uint32_t>* pav_columns, std::string* chain, bool chain_swap) {
+                                 const std::vector<uint32_t>* pav_columns, std::string* chain, bool chain_swap, wfm_sites_t* sites,
+                                 uint32_t sites_groups) {
   const bool dbg = getenv("WFM_DEBUG") != nullptr;
   BatchTimes t;
   std::vector<Fetched> rows = parse_rows(lines, first_row, sum);
@@ -396,9 +398,9 @@ std::string Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<std::stri
   std::vector<Fetched> fetched = fetch_eager(rows, threads, sum);
   if (fetched.empty()) return std::string();
   std::vector<wflign::BiwfaRecord> recs = make_records(fetched);
-  if (coverage || liftset || pav)
+  if (coverage || liftset || pav || sites)
     for (wflign::BiwfaRecord& r : recs) r.target_global = (*seq_offsets)[(size_t)ref->find(r.target_name)];  // (parse_rows has found every name)
-  if (pav)
+  if (pav || sites)
     for (wflign::BiwfaRecord& r : recs) {
       const int qi = query->find(r.query_name);
       r.pav_group = qi >= 0 ? (*pav_columns)[(size_t)qi] : 0xffffffffu;  // (no column: the device flags the record and adds nothing)
@@ -421,6 +423,8 @@ std::string Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<std::stri
   wflign::OutputFormat fmt = format_of(param, threads);
   fmt.coverage = coverage;
   fmt.pav = pav;
+  fmt.sites = sites;
+  fmt.sites_groups = sites_groups;
   fmt.liftset = liftset;
   fmt.lift_intervals = lift_intervals;
   fmt.chain = chain ? (chain_swap ? 2 : 1) : 0;
@@ -596,7 +600,22 @@ struct Aligner::Run {
     pavs.emplace_back(h, p);
     return p;
   }
-  // --coverage, --lift, --pav: where each target sequence begins in the concatenation (nseq + 1 values; empty: all are off).  --coverage: the depth object
+  // --genotypes: the columns (pav_cols, as --pav makes them) and the sites object of every handle the run has used so far, made at the
+  // handle's first batch
+  bool sites_on = false;
+  std::mutex sites_mu;
+  std::vector<std::pair<wfm_handle_t*, wfm_sites_t*>> sites;
+  wfm_sites_t* sites_of(wfm_handle_t* h) {
+    if (!sites_on) return nullptr;
+    std::lock_guard<std::mutex> lk(sites_mu);
+    for (auto& hs : sites) if (hs.first == h) return hs.second;
+    wfm_sites_t* p = nullptr;
+    std::lock_guard<std::mutex> hl(wflign::handle_lock(h));
+    if (wfm_sites_create(h, seq_offsets.back(), (uint32_t)pav_cols.keys.size(), &p) != WFM_OK) throw std::runtime_error(std::string("[wfmash::align] --genotypes: ") + wfm_last_error(h));
+    sites.emplace_back(h, p);
+    return p;
+  }
+  // --coverage, --lift, --pav, --genotypes: where each target sequence begins in the concatenation (nseq + 1 values; empty: all are off).  --coverage: the depth object
   // of every handle the run has used so far, made at the handle's first batch
   std::vector<uint64_t> seq_offsets;
   bool coverage_on = false;
@@ -614,6 +633,10 @@ struct Aligner::Run {
     for (auto& hp : pavs) {
       std::lock_guard<std::mutex> lk(wflign::handle_lock(hp.first));
       wfm_pav_free(hp.second);
+    }
+    for (auto& hs : sites) {
+      std::lock_guard<std::mutex> lk(wflign::handle_lock(hs.first));
+      wfm_sites_free(hs.second);
     }
   }
   wfm_coverage_t* coverage_of(wfm_handle_t* h) {
@@ -716,7 +739,8 @@ void Aligner::run_worker(Run& run, size_t wk) {
       std::string vcf, lifted, chains;
       std::string text = align_batch(run.use[wk], batch, run.threads_each, run.part[wk], first_row, run.vcf_writer ? &vcf : nullptr,
                                      run.coverage_of(run.use[wk]), &run.seq_offsets, run.lift_writer ? &lifted : nullptr, run.liftset_of(run.use[wk]),
-                                     &run.lift_iv, run.pav_of(run.use[wk]), &run.pav_cols.of_seq, run.chain_writer ? &chains : nullptr, run.chain_swap);
+                                     &run.lift_iv, run.pav_of(run.use[wk]), &run.pav_cols.of_seq, run.chain_writer ? &chains : nullptr, run.chain_swap,
+                                     run.sites_of(run.use[wk]), (uint32_t)run.pav_cols.keys.size());
       const double at1 = run.ms();
       run.writer.put((uint64_t)seq, std::move(text));
       if (run.vcf_writer) run.vcf_writer->put((uint64_t)seq, std::move(vcf));
@@ -848,6 +872,56 @@ void Aligner::finish_pav(Run& run, std::ofstream& out, uint64_t bed_skipped) {
             run.pavs.size(), (unsigned long long)counts[0], (unsigned long long)counts[1], n_iv, G, std::chrono::duration<double, std::milli>(t1 - t0).count(), ms_since(t1));
 }
 
+// --genotypes: every other handle's object exported and imported into the first (the table is a set function: the order does not matter),
+// the table of the merged object taken once on the device, the file through genotype_text.hpp
+void Aligner::finish_genotypes(Run& run, std::ofstream& out) {
+  const auto t0 = Clock::now();
+  auto fail = [](wfm_handle_t* h, const char* what) { throw std::runtime_error(std::string("[wfmash::align] --genotypes: ") + what + ": " + wfm_last_error(h)); };
+  const size_t G = run.pav_cols.keys.size();
+  wfm_site_t* rows = nullptr;
+  char *alleles = nullptr, *gt = nullptr;
+  size_t n_sites = 0, bytes = 0;
+  uint64_t counts[4] = {0, 0, 0, 0};
+  if (!run.sites.empty()) {
+    wfm_handle_t* h0 = run.sites.front().first;
+    wfm_sites_t* s0 = run.sites.front().second;
+    for (size_t k = 1; k < run.sites.size(); ++k) {
+      wfm_site_var_t* vars = nullptr;
+      char* a = nullptr;
+      wfm_pav_seg_t* segs = nullptr;
+      size_t n = 0, nb = 0, ns = 0;
+      {
+        std::lock_guard<std::mutex> lk(wflign::handle_lock(run.sites[k].first));
+        if (wfm_sites_export(run.sites[k].first, run.sites[k].second, &vars, &n, &a, &nb, &segs, &ns) != WFM_OK) fail(run.sites[k].first, "export");
+      }
+      std::lock_guard<std::mutex> lk(wflign::handle_lock(h0));
+      const int rc = wfm_sites_import(h0, s0, vars, n, a, nb, segs, ns);
+      wfm_sites_free_list(vars); wfm_sites_free_list(a); wfm_sites_free_list(segs);
+      if (rc != WFM_OK) fail(h0, "import");
+    }
+    std::lock_guard<std::mutex> lk(wflign::handle_lock(h0));
+    if (wfm_sites_table(h0, s0, &rows, &n_sites, &alleles, &bytes, &gt) != WFM_OK) fail(h0, "table");
+    wfm_sites_counts(s0, counts);
+  }
+  const auto t1 = Clock::now();
+  std::vector<std::string> names;
+  std::vector<uint64_t> lengths;
+  for (int i = 0; i < ref->nseq(); ++i) { names.push_back(ref->name(i)); lengths.push_back((uint64_t)ref->length(i)); }
+  std::vector<genotype::Site> sites(n_sites);
+  for (size_t i = 0; i < n_sites; ++i) sites[i] = genotype::Site{rows[i].pos, rows[i].ref_len, rows[i].alt_len, rows[i].off};
+  std::string text = genotype::header(WFMASH_HIP_VERSION, names, lengths, run.pav_cols.keys);
+  for (size_t i : genotype::order(sites, alleles)) {
+    genotype::site_line(text, sites, i, alleles, gt, G, names, run.seq_offsets);
+    if (text.size() >= ((size_t)1 << 20)) { out << text; text.clear(); }
+  }
+  out << text;
+  wfm_sites_free_list(rows); wfm_sites_free_list(alleles); wfm_sites_free_list(gt);
+  wflign::genotypes_finished(counts[0], n_sites);
+  if (getenv("WFM_DEBUG"))
+    fprintf(stderr, "[wfmash::align] genotypes: %zu objects merged, %llu variants, %zu sites x %zu groups, %llu = intervals, merge + table %.1f ms, text %.1f ms\n",
+            run.sites.size(), (unsigned long long)counts[0], n_sites, G, (unsigned long long)counts[2], std::chrono::duration<double, std::milli>(t1 - t0).count(), ms_since(t1));
+}
+
 Summary Aligner::compute() {
   Summary sum;
   const auto t0 = Clock::now();
@@ -897,7 +971,9 @@ Summary Aligner::compute() {
   std::string pav_bed, pav_out;
   uint64_t pav_window = 0, pav_skipped = 0;
   wflign::pav_paths(pav_bed, pav_window, pav_out);
-  if (!cov_path.empty() || !lift_out.empty() || !pav_out.empty()) {
+  std::ofstream gtstream;
+  const std::string gt_path = wflign::genotypes_path();
+  if (!cov_path.empty() || !lift_out.empty() || !pav_out.empty() || !gt_path.empty()) {
     run.seq_offsets.assign(1, 0);
     for (int i = 0; i < ref->nseq(); ++i) run.seq_offsets.push_back(run.seq_offsets.back() + (uint64_t)ref->length(i));
   }
@@ -934,6 +1010,16 @@ Summary Aligner::compute() {
     if (!pavstream.is_open()) throw std::runtime_error("[wfmash::align] Error! Failed to open the pav file: " + pav_out);
     run.pav_on = true;
   }
+  if (!gt_path.empty()) {  // --genotypes: the columns are --pav's; the file is written once the workers are done
+    if (!run.pav_on) {
+      std::vector<std::string> qnames;
+      for (int i = 0; i < query->nseq(); ++i) qnames.push_back(query->name(i));
+      run.pav_cols = pav::columns(qnames);
+    }
+    gtstream.open(gt_path);
+    if (!gtstream.is_open()) throw std::runtime_error("[wfmash::align] Error! Failed to open the genotypes file: " + gt_path);
+    run.sites_on = true;
+  }
   const size_t nworkers = run.plan.nworkers;
   static const bool own_handles = !(getenv("WFM_ALIGN_OWN_HANDLES") && atoi(getenv("WFM_ALIGN_OWN_HANDLES")) == 0);
   static HandlePool pool;
@@ -952,6 +1038,7 @@ Summary Aligner::compute() {
   if (run.failed.load()) throw std::runtime_error(run.first_error);
   if (covstream.is_open()) { finish_coverage(run, covstream); covstream.close(); }
   if (pavstream.is_open()) { finish_pav(run, pavstream, pav_skipped); pavstream.close(); }
+  if (gtstream.is_open()) { finish_genotypes(run, gtstream); gtstream.close(); }
   sum_up(sum, run.part, t0);
   outstream.close();
   if (vcfstream.is_open()) vcfstream.close();

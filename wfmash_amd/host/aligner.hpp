@@ -108,12 +108,13 @@ class Aligner {
   // written are added to, --coverage, with seq_offsets: where each target sequence begins in the concatenation; null: none.  lift: where
   // the lift lines of the records written go, --lift, with the handle's liftset and the intervals in its order; null: nowhere.  pav: the
   // presence object of this handle the records written are added to, --pav, with the column of every query sequence; null: none.  chain:
-  // where the chains of the records written go, without their ids, --chain, swapped or not; null: nowhere)
+  // where the chains of the records written go, without their ids, --chain, swapped or not; null: nowhere.  sites: the sites object of
+  // this handle the variants and = runs of the records written are added to, --genotypes, with pav_columns and the number of groups)
   std::string align_batch(wfm_handle_t* gpu, std::vector<std::string>& lines, int threads, Summary& sum, uint64_t first_row = 0,
                           std::string* vcf = nullptr, wfm_coverage_t* coverage = nullptr, const std::vector<uint64_t>* seq_offsets = nullptr,
                           std::string* lift = nullptr, const wfm_liftset_t* liftset = nullptr, const std::vector<lift::Interval>* lift_intervals = nullptr,
                           wfm_pav_t* pav = nullptr, const std::vector<uint32_t>* pav_columns = nullptr,
-                          std::string* chain = nullptr, bool chain_swap = false);
+                          std::string* chain = nullptr, bool chain_swap = false, wfm_sites_t* sites = nullptr, uint32_t sites_groups = 0);
   std::vector<Fetched> parse_rows(std::vector<std::string>& lines, uint64_t first_row, Summary& sum) const;
   void fetch_windows(Fetched& f) const;
   std::vector<Fetched> fetch_eager(std::vector<Fetched>& rows, int threads, Summary& sum) const;
@@ -129,6 +130,7 @@ class Aligner {
   void run_worker(Run& run, size_t wk);
   void finish_coverage(Run& run, std::ofstream& out);  // --coverage: the handles' depth objects merged into one, its intervals as a bedGraph
   void finish_pav(Run& run, std::ofstream& out, uint64_t bed_skipped);  // --pav: the handles' presence objects merged into one, its table as TSV
+  void finish_genotypes(Run& run, std::ofstream& out);  // --genotypes: the handles' sites objects merged into one, its table as a VCF
   void sum_up(Summary& sum, const std::vector<Summary>& part, std::chrono::steady_clock::time_point t0) const;
   const Parameters& param;
   std::vector<wfm_handle_t*> gpus;

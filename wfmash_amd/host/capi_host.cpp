@@ -16,6 +16,7 @@
 #include "chain_text.hpp"
 #include "lift_text.hpp"
 #include "pav_text.hpp"
+#include "genotype_text.hpp"
 #include "map_stats.hpp"
 
 extern "C" {
@@ -227,6 +228,23 @@ char* wfmh_test_pav_text(const char* const* names, int n_q, const char* const* t
     for (size_t g = 0; g < cells.size(); ++g) cells[g] = (uint32_t)(j + g);
     pav::row(out, tnames[win[j].seq], win[j], cells.data(), cells.size());
   }
+  char* p = (char*)malloc(out.size() + 1);
+  if (p) memcpy(p, out.c_str(), out.size() + 1);
+  return p;
+}
+
+// test hook (no GPU): the text side of --genotypes (genotype_text.hpp): the header, the order of the lines, the lines
+char* wfmh_test_genotype_text(const char* version, const char* const* tnames, const uint64_t* lengths, int n_t, const char* const* keys, int n_groups,
+                              const uint64_t* sites, size_t n_sites, const char* alleles, const char* gt) {
+  if (!version || n_t < 0 || n_groups < 0 || (n_t && (!tnames || !lengths)) || (n_groups && !keys) || (n_sites && (!sites || !alleles || (n_groups && !gt)))) return nullptr;
+  std::vector<std::string> names, cols;
+  std::vector<uint64_t> len, off(1, 0);
+  for (int i = 0; i < n_t; ++i) { names.push_back(tnames[i]); len.push_back(lengths[i]); off.push_back(off.back() + lengths[i]); }
+  for (int g = 0; g < n_groups; ++g) cols.push_back(keys[g]);
+  std::vector<genotype::Site> ss(n_sites);
+  for (size_t i = 0; i < n_sites; ++i) ss[i] = genotype::Site{sites[4 * i], (uint32_t)sites[4 * i + 1], (uint32_t)sites[4 * i + 2], sites[4 * i + 3]};
+  std::string out = genotype::header(version, names, len, cols);
+  for (size_t i : genotype::order(ss, alleles)) genotype::site_line(out, ss, i, alleles, gt, (size_t)n_groups, names, off);
   char* p = (char*)malloc(out.size() + 1);
   if (p) memcpy(p, out.c_str(), out.size() + 1);
   return p;

@@ -87,6 +87,14 @@
 //   --pav-paf IN.paf (--pav IN.bed | --pav-window N) --pav-out FILE target.fa [query.fa]   the same file for an existing aligned PAF: no
 //                                              mapping, no alignment; lines are skipped and counted as --coverage-paf does, and a line whose
 //                                              query is not in the query FASTA; only --device beside it
+//   --genotypes FILE                           the variants of ALL records written merged into one VCF sorted by (sequence, POS, REF, ALT),
+//                                              one line per distinct site and one haploid GT column per group of query sequences (--pav's
+//                                              groups): 1 = a record of the group carries exactly this variant, 0 = the whole REF span lies
+//                                              under = bases of the group's records, . = neither; AC and AN count the row.  The join (a
+//                                              sort, a de-duplication on the allele bytes, the sites x groups table) runs on the device
+//                                              (wfm_sites_*).  It does not imply --left-align: give both, or one indel in a repeat can be two
+//                                              sites.  No output byte of the PAF, SAM or --variants file changes; refused with -m and
+//                                              --verify-paf; off by default
 //   --verify-paf FILE target.fa [query.fa]     the same check on an existing aligned PAF (this build's or the reference's): no mapping,
 //                                              no alignment; exit status 3 if a line fails
 //   --ani-matrix FILE [--ani-only]             the group-by-group ANI table the identity estimate (-p aniN) is made from, as TSV: per
@@ -187,6 +195,7 @@ static void usage() {
           "            --chain-swap  with --chain: the swapped file (query to target), what chainSwap would make of it\n"
           "            --chain-paf FILE with --chain: the chain file of an existing aligned PAF over target.fa, and stop (only --chain-swap and --device beside it)\n"
           "            --pav BED | --pav-window N, --pav-out FILE per target interval and group of query sequences the bases present, from per-group unions on the GPU (not with -m, --verify-paf)\n"
+          "            --genotypes FILE write ONE sorted VCF of the distinct variants of all records with a haploid GT column (0, 1, .) per group of query sequences, joined on the GPU (give --left-align too; not with -m, --verify-paf)\n"
           "            --pav-paf FILE with --pav or --pav-window, --pav-out: the table of an existing aligned PAF over target.fa [query.fa], and stop (only --device beside it)\n"
           "            --verify-paf FILE check an existing aligned PAF against target.fa [query.fa] and stop (exit status 3 if a line fails)\n"
           "  other     --out FILE [stdout]   --device INT [0]   --gpus N|all [1] GPUs of this node, starting at --device\n"
@@ -199,7 +208,7 @@ int main(int argc, char** argv) {
   ap.threads = 1;  // -t, default 1 as in the reference (parse_args.hpp: thread_count); the C ABI default (0) means all cores
   wfmh_map_params_t mp;
   wfmh_map_default_params(&mp);
-  std::string mapping_in, out = "/dev/stdout", target, query, seeds_in, scaffold_out, tmp_base, verify_in, ani_matrix_out, variants_out, coverage_out, coverage_in, lift_bed, lift_out, lift_in, pav_bed, pav_out, pav_in, chain_out, chain_in;
+  std::string mapping_in, out = "/dev/stdout", target, query, seeds_in, scaffold_out, tmp_base, verify_in, ani_matrix_out, variants_out, genotypes_out, coverage_out, coverage_in, lift_bed, lift_out, lift_in, pav_bed, pav_out, pav_in, chain_out, chain_in;
   uint64_t pav_window = 0;
   bool pav_window_set = false;
   bool pav_other = false;      // --pav-paf: anything beside it, --pav, --pav-window, --pav-out, --device and the two FASTAs
@@ -351,6 +360,7 @@ int main(int argc, char** argv) {
     else if (a == "--cs=long") cs_form = 2;
     else if (a.compare(0, 5, "--cs=") == 0) { fprintf(stderr, "[wfmash] ERROR: --cs takes =short or =long, not '%s'\n", a.c_str() + 5); return 1; }
     else if (a == "--variants") variants_out = next("--variants");
+    else if (a == "--genotypes") genotypes_out = next("--genotypes");
     else if (a == "--coverage") coverage_out = next("--coverage");
     else if (a == "--coverage-paf") coverage_in = next("--coverage-paf");
     else if (a == "--lift") lift_bed = next("--lift");
@@ -392,6 +402,8 @@ int main(int argc, char** argv) {
   if (!lift_in.empty() && lift_bed.empty()) { fprintf(stderr, "[wfmash] ERROR: --lift-paf needs --lift IN.bed and --lift-out FILE\n"); return 1; }
   if (!lift_bed.empty() && approx_only) { fprintf(stderr, "[wfmash] ERROR: --lift lifts through alignments: it cannot be combined with -m\n"); return 1; }
   if (!lift_bed.empty() && !verify_in.empty()) { fprintf(stderr, "[wfmash] ERROR: --lift belongs to the align phase: it cannot be combined with --verify-paf\n"); return 1; }
+  if (!genotypes_out.empty() && approx_only) { fprintf(stderr, "[wfmash] ERROR: --genotypes reads alignments: it cannot be combined with -m\n"); return 1; }
+  if (!genotypes_out.empty() && !verify_in.empty()) { fprintf(stderr, "[wfmash] ERROR: --genotypes belongs to the align phase: it cannot be combined with --verify-paf\n"); return 1; }
   if (chain_swap && chain_out.empty()) { fprintf(stderr, "[wfmash] ERROR: --chain-swap needs --chain FILE\n"); return 1; }
   if (!chain_in.empty() && chain_out.empty()) { fprintf(stderr, "[wfmash] ERROR: --chain-paf needs --chain FILE\n"); return 1; }
   if (!chain_out.empty() && approx_only) { fprintf(stderr, "[wfmash] ERROR: --chain writes chains of alignments: it cannot be combined with -m\n"); return 1; }
@@ -576,6 +588,7 @@ int main(int argc, char** argv) {
     if (left_align) wfmh_set_left_align(1);
     if (cs_form) wfmh_set_cs(cs_form);
     if (!variants_out.empty()) wfmh_set_variants(variants_out.c_str());
+    if (!genotypes_out.empty()) wfmh_set_genotypes(genotypes_out.c_str());
     if (!coverage_out.empty()) wfmh_set_coverage(coverage_out.c_str());
     if (!lift_bed.empty()) wfmh_set_lift(lift_bed.c_str(), lift_out.c_str());
     if (!chain_out.empty()) wfmh_set_chain(chain_out.c_str(), chain_swap ? 1 : 0);
@@ -602,6 +615,12 @@ int main(int argc, char** argv) {
       wfmh_variants_counts(vc);
       fprintf(stderr, "[wfmash::variants] %llu records, %llu variants written, %llu SNVs masked, %llu records left alone\n", (unsigned long long)vc[0],
               (unsigned long long)vc[1], (unsigned long long)vc[2], (unsigned long long)vc[3]);
+    }
+    if (!genotypes_out.empty() && rc == WFM_OK) {
+      uint64_t gc[4] = {0, 0, 0, 0};
+      wfmh_genotypes_counts(gc);
+      fprintf(stderr, "[wfmash::genotypes] %llu records added, %llu sites written, %llu variants merged away, %llu records left alone\n", (unsigned long long)gc[0],
+              (unsigned long long)gc[1], (unsigned long long)gc[2], (unsigned long long)gc[3]);
     }
     if (pav_on && rc == WFM_OK) {
       uint64_t pc[4] = {0, 0, 0, 0};

@@ -92,6 +92,13 @@ std::string g_pav_bed, g_pav_out;
 uint64_t g_pav_window = 0;
 std::atomic<uint64_t> g_pav_counts[4];
 
+// --genotypes: the process-wide switch, the file the align phase writes and {records added, sites written, variants merged away, records
+// left alone} since it was set
+std::atomic<bool> g_genotypes{false};
+std::mutex g_genotypes_mu;
+std::string g_genotypes_path;
+std::atomic<uint64_t> g_genotypes_counts[4];
+
 // The problems of one device call, always written by reference (a side without a store id carries its host pointer); without a
 // store they go to the device as plain wfm_problem_t, as they always have.
 struct GpuBatch {
@@ -240,6 +247,15 @@ double ms_between(Clock::time_point a, Clock::time_point b) { return std::chrono
 
 struct WindowSet;  // the records' final runs as device problems (left_align_records, cs_records, variant_records)
 
+// --genotypes: what wfm_call_variants returned for the batch, kept until the filters have spoken (genotype_records)
+struct KeptCalls {
+  wfm_variant_t* vars = nullptr;
+  char* alleles = nullptr;
+  std::vector<wfm_varcall_t> per;  // per part of the window set
+  std::vector<size_t> rec;         // the part's record in the batch
+  ~KeptCalls() { wfm_free_variants(vars, alleles); }
+};
+
 // One call of do_biwfa_alignment_batch: what its stages share.
 struct BiwfaBatch {
   wfm_handle_t* h;
@@ -261,6 +277,7 @@ struct BiwfaBatch {
   std::atomic<uint64_t> n_head{0}, n_tail{0};
   int cs_form = 0;                // --cs as the batch found it: 0 off, 1 short, 2 long
   bool variants = false;          // --variants as the batch found it
+  std::unique_ptr<KeptCalls> calls;  // --genotypes: variant_records' records and alleles, for genotype_records
   std::unique_ptr<WindowSet> windows;  // what left_align_records leaves for cs_records and variant_records, and cs_records for variant_records
   // the handle's message was copied while the handle was still this thread's (another batch may be using it by now)
   int fail(const GpuBatch& g, int rc) const { if (stats) stats->error = g.err; return rc; }
@@ -558,7 +575,8 @@ int cs_records(BiwfaBatch& b) {
 // part is not empty takes part; a part begins and ends with an = or X run, so it has no end gaps and every gap of it is called.  The
 // line's coordinates are the writer's (write_alignment_paf): POS = the target start it writes + p + 1; [QSTART, QEND) = the span
 // [t, t + n) of the line's text -- n = 1 for an SNV, the inserted bases for an INS, 0 for a DEL -- on the query's forward strand.  Masked
-// SNVs are left out and counted.  A record the device flags is a defect: it has no lines and is counted. ----
+// SNVs are left out and counted.  A record the device flags is a defect: it has no lines and is counted.  With --genotypes the records and
+// their alleles stay in the batch (b.calls) for genotype_records; with --genotypes alone no line is spelled. ----
 int variant_records(BiwfaBatch& b) {
   const auto t0 = Clock::now();
   if (!b.windows) b.windows = window_parts(b, 1);
@@ -580,7 +598,7 @@ int variant_records(BiwfaBatch& b) {
   }
   if (rc < 0) return rc;
   const auto t2 = Clock::now();
-  for_each_record(n, b.fmt.threads, [&](size_t j) {
+  if (b.variants) for_each_record(n, b.fmt.threads, [&](size_t j) {
     if (per[j].flags) return;
     const WindowSet::Part& pt = w.parts[j];
     BiwfaRecord& r = b.recs[pt.rec];
@@ -608,7 +626,15 @@ int variant_records(BiwfaBatch& b) {
                                          r.query_is_rev ? '-' : '+'));
     }
   });
-  wfm_free_variants(vars, alleles);
+  if (b.fmt.sites) {
+    b.calls.reset(new KeptCalls());
+    b.calls->vars = vars; b.calls->alleles = alleles;
+    b.calls->per = std::move(per);
+    b.calls->rec.resize(n);
+    for (size_t j = 0; j < n; ++j) b.calls->rec[j] = w.parts[j].rec;
+  } else {
+    wfm_free_variants(vars, alleles);
+  }
   if (getenv("WFM_DEBUG"))
     fprintf(stderr, "[wflign] variants: %zu records, %zu runs, %zu variants, %zu allele bytes, %d flagged, %.1f ms (upload %.1f, device call %.1f, text %.1f)\n",
             n, w.n_cur(), n_vars, bytes, rc, ms_between(t0, Clock::now()), ms_between(t0, t1), ms_between(t1, t2), ms_between(t2, Clock::now()));
@@ -737,6 +763,53 @@ int pav_records(BiwfaBatch& b, const PackedRuns& pk) {
   if (getenv("WFM_DEBUG"))
     fprintf(stderr, "[wflign] pav: %zu records, %zu runs, %d flagged, %.1f ms (runs %.1f, device call %.1f)\n", probs.size(), pk.runs.size(), rc,
             pk.ms + ms_between(t0, Clock::now()), pk.ms + ms_between(t0, t1), ms_between(t1, Clock::now()));
+  return 0;
+}
+// ---- --genotypes: the variants variant_records called for the records WRITTEN (masked SNVs left out), each at its global position --
+// the problem's base + p -- under the column of its query's group, and the same records' runs for the = union: one wfm_sites_add_variants
+// and one wfm_sites_add_ref call per batch.  A record without calls (the device flagged it), without a column or that the device refuses
+// adds nothing, is counted and reported. ----
+int genotype_records(BiwfaBatch& b, const PackedRuns& pk) {
+  const auto t0 = Clock::now();
+  const KeptCalls* kc = b.calls.get();
+  std::vector<size_t> part_of(b.recs.size(), (size_t)-1);
+  if (kc) for (size_t j = 0; j < kc->rec.size(); ++j) part_of[kc->rec[j]] = j;
+  std::vector<wfm_site_var_t> vars;
+  std::string alleles;
+  std::vector<wfm_pav_prob_t> probs;
+  uint64_t alone = pk.unknown;
+  for (size_t j = 0; j < pk.probs.size(); ++j) {
+    const BiwfaRecord& r = b.recs[pk.rec[j]];
+    const size_t part = part_of[pk.rec[j]];
+    if (part == (size_t)-1 || kc->per[part].flags || r.pav_group >= b.fmt.sites_groups) { ++alone; continue; }
+    probs.push_back(wfm_pav_prob_t{pk.probs[j].base, pk.probs[j].runs_off, pk.probs[j].n_runs, r.pav_group});
+    const wfm_varcall_t& pc = kc->per[part];
+    for (uint64_t k = pc.first; k < pc.first + pc.count; ++k) {
+      const wfm_variant_t& v = kc->vars[k];
+      if (v.kind & WFM_VAR_MASKED) continue;
+      vars.push_back(wfm_site_var_t{pk.probs[j].base + v.p, v.kind & 255u, r.pav_group, v.ref_len, v.alt_len, (uint64_t)alleles.size()});
+      alleles.append(kc->alleles + v.off, (size_t)v.ref_len + v.alt_len);
+    }
+  }
+  int rc = WFM_OK;
+  auto t1 = t0;
+  if (!probs.empty()) {
+    std::vector<uint32_t> flags(probs.size());
+    std::lock_guard<std::mutex> lk(handle_lock(b.h));
+    t1 = Clock::now();
+    rc = wfm_sites_add_variants(b.h, b.fmt.sites, vars.data(), vars.size(), alleles.data(), alleles.size());
+    if (rc == WFM_OK) rc = wfm_sites_add_ref(b.h, b.fmt.sites, probs.data(), probs.size(), pk.runs.data(), pk.runs.size(), flags.data());
+    if (rc < 0 && b.stats) b.stats->error = wfm_last_error(b.h);
+  }
+  if (rc < 0) return rc;
+  g_genotypes_counts[0] += probs.size() - (uint64_t)rc;
+  g_genotypes_counts[3] += alone + (uint64_t)rc;
+  if (rc > 0 || alone)
+    fprintf(stderr, "[wflign] genotypes: %llu records of a batch were NOT added (no calls, runs that leave the target or cannot be held, or a query without a column)\n",
+            (unsigned long long)((uint64_t)rc + alone));
+  if (getenv("WFM_DEBUG"))
+    fprintf(stderr, "[wflign] genotypes: %zu records, %zu variants, %zu allele bytes, %zu runs, %d flagged, %.1f ms (host lists %.1f, device calls %.1f)\n", probs.size(),
+            vars.size(), alleles.size(), pk.runs.size(), rc, ms_between(t0, Clock::now()), ms_between(t0, t1), ms_between(t1, Clock::now()));
   return 0;
 }
 // ---- --lift: the BED intervals through the same problems, ONE device call per batch (wfm_lift_runs); the query window is the writer's
@@ -880,6 +953,13 @@ void coverage_finished(uint64_t covered, uint64_t depth_sum, uint64_t intervals)
   g_coverage_counts[1] += covered; g_coverage_counts[2] += depth_sum; g_coverage_counts[3] += intervals;
 }
 
+std::string genotypes_path() {
+  std::lock_guard<std::mutex> lk(g_genotypes_mu);
+  return g_genotypes.load() ? g_genotypes_path : std::string();
+}
+
+void genotypes_finished(uint64_t variants, uint64_t sites) { g_genotypes_counts[1] += sites; g_genotypes_counts[2] += variants - sites; }
+
 std::string variants_path() {
   std::lock_guard<std::mutex> lk(g_variants_mu);
   return g_variants.load() ? g_variants_path : std::string();
@@ -909,21 +989,23 @@ int do_biwfa_alignment_batch(wfm_handle_t* h, std::vector<BiwfaRecord>& recs, co
   const bool left = g_left_align.load();
   b.cs_form = g_cs.load(std::memory_order_relaxed);
   b.variants = g_variants.load(std::memory_order_relaxed);
-  if (left || b.cs_form || b.variants) {  // the two halves with the device calls between them
+  const bool calls = b.variants || fmt.sites;  // (--genotypes takes variant_records' calls, with or without the file of --variants)
+  if (left || b.cs_form || calls) {  // the two halves with the device calls between them
     for_each_record(n, fmt.threads, [&](size_t ri) { swizzle(b, ri); });
-    if (left) rc = left_align_records(b, b.cs_form != 0 || b.variants);
+    if (left) rc = left_align_records(b, b.cs_form != 0 || calls);
     if (rc >= 0 && b.cs_form) rc = cs_records(b);
-    if (rc >= 0 && b.variants) rc = variant_records(b);
+    if (rc >= 0 && calls) rc = variant_records(b);
     release_windows(b);
     if (rc < 0) return rc;
     for_each_record(n, fmt.threads, [&](size_t ri) { write_record(b, ri); });
   } else {
     for_each_record(n, fmt.threads, [&](size_t ri) { swizzle(b, ri); write_record(b, ri); });
   }
-  if (fmt.coverage || fmt.pav || fmt.liftset || fmt.chain) {  // one packing for the stages that are on; each makes its own device call
+  if (fmt.coverage || fmt.pav || fmt.liftset || fmt.chain || fmt.sites) {  // one packing for the stages that are on; each makes its own device call
     const PackedRuns pk = pack_written(b);
     if (fmt.coverage && (rc = coverage_records(b, pk)) < 0) return rc;
     if (fmt.pav && (rc = pav_records(b, pk)) < 0) return rc;
+    if (fmt.sites && (rc = genotype_records(b, pk)) < 0) return rc;
     if (fmt.liftset && (rc = lift_records(b, pk)) < 0) return rc;
     if (fmt.chain && (rc = chain_records(b, pk)) < 0) return rc;
   }
@@ -960,6 +1042,21 @@ void wfmh_set_variants(const char* path_or_null) {
     wflign::g_variants_path = path_or_null ? path_or_null : "";
   }
   wflign::g_variants.store(path_or_null && *path_or_null);
+}
+
+void wfmh_set_genotypes(const char* path_or_null) {
+  for (auto& a : wflign::g_genotypes_counts) a.store(0);
+  {
+    std::lock_guard<std::mutex> lk(wflign::g_genotypes_mu);
+    wflign::g_genotypes_path = path_or_null ? path_or_null : "";
+  }
+  wflign::g_genotypes.store(path_or_null && *path_or_null);
+}
+
+int wfmh_genotypes_counts(uint64_t out[4]) {
+  if (!out) return WFM_E_ARG;
+  for (int q = 0; q < 4; ++q) out[q] = wflign::g_genotypes_counts[q].load();
+  return WFM_OK;
 }
 
 void wfmh_set_coverage(const char* path_or_null) {

@@ -14,13 +14,15 @@
 //   left_align_records --left-align only: every interior gap to its leftmost placement, one wfm_left_align_runs call
 //   cs_records         --cs only: the cs difference string of every record's line, one wfm_cs_strings call (on the windows
 //                      left_align_records uploaded, where both are on)
-//   variant_records    --variants only: the VCF lines of every record's line, one wfm_call_variants call (on the same windows,
-//                      uploaded once whichever of the three switches are on)
+//   variant_records    --variants and --genotypes only: the VCF lines of every record's line, one wfm_call_variants call (on the same
+//                      windows, uploaded once whichever of the switches are on); --genotypes keeps the calls for genotype_records
 //   write_record       PAF / SAM record (+ cs:Z: as its last field)   (wflign.cpp:434-454)
 //   coverage_records   --coverage only: the runs of every record WRITTEN into the handle's depth object, one wfm_coverage_add call
 //                      (nothing is uploaded but runs; whether a record is written is only known behind write_record)
 //   pav_records        --pav only: the runs of every record WRITTEN, with the column of its query's group, into the handle's presence
 //                      object, one wfm_pav_add call (runs alone again)
+//   genotype_records   --genotypes only: the kept calls of every record WRITTEN at their global positions, and the records' runs, into
+//                      the handle's sites object, one wfm_sites_add_variants and one wfm_sites_add_ref call
 //   lift_records       --lift only: the BED intervals lifted through the runs of every record WRITTEN, one wfm_lift_runs call
 //                      (runs alone again), the record's lines into BiwfaRecord::lift
 //   chain_records      --chain only: the runs of every record WRITTEN compacted to the blocks and gaps of a UCSC chain, one
@@ -81,7 +83,7 @@ struct BiwfaRecord {
   uint32_t vcf_masked = 0;           // ... SNVs left out of `vcf` because a base of theirs is not one of ACGT
   uint64_t target_global = 0;        // --coverage, --lift: where the target sequence begins in the concatenation of the target's sequences
   bool written = false;              // the filters let the record's line through (write_record)
-  uint32_t pav_group = 0;            // --pav: the column of the query sequence's group
+  uint32_t pav_group = 0;            // --pav, --genotypes: the column of the query sequence's group
   std::string lift;                  // --lift: the lines of the BED intervals the record's target span overlaps, each with its newline ("" if off or not written)
   std::string chain;                 // --chain: the record's chain without its id (chain_text.hpp; "" if off, not written, refused or without a block)
   uint32_t tags = 0;                 // WFM_PF_* of the main alignment | of the head patch << 8 | of the tail patch << 16 (diagnostics: WFM_RECORD_TAGS)
@@ -124,6 +126,8 @@ struct OutputFormat {
   int threads = 1;                   // host threads for the per-record CIGAR / PAF work of a batch
   wfm_coverage_t* coverage = nullptr;  // --coverage: the depth object of the batch's handle (null: the stage is not run)
   wfm_pav_t* pav = nullptr;            // --pav: the presence object of the batch's handle (null: the stage is not run)
+  wfm_sites_t* sites = nullptr;        // --genotypes: the sites object of the batch's handle (null: the stage is not run) ...
+  uint32_t sites_groups = 0;           // ... and its number of groups
   const wfm_liftset_t* liftset = nullptr;                   // --lift: the intervals on the batch's handle (null: the stage is not run) ...
   const std::vector<lift::Interval>* lift_intervals = nullptr;  // ... and as the BED had them, in the set's order
   int chain = 0;                       // --chain: 1 = the chain of every record written, 2 = the swapped one (0: the stage is not run)
@@ -131,6 +135,11 @@ struct OutputFormat {
 
 // --variants: the file wfmh_set_variants named ("" while the switch is off); the align phase writes the batches' BiwfaRecord::vcf to it
 std::string variants_path();
+
+// --genotypes: the file wfmh_set_genotypes named ("" while the switch is off), and what the align phase adds to the counts once it has
+// the table: the variants the objects held and the sites written
+std::string genotypes_path();
+void genotypes_finished(uint64_t variants, uint64_t sites);
 
 // --coverage: the file wfmh_set_coverage named ("" while the switch is off), and what the align phase adds to the counts once it has
 // the intervals: {target bases with depth >= 1, sum of depth, intervals written}
