@@ -625,6 +625,66 @@ int  wfm_sites_import(wfm_handle_t* h, wfm_sites_t* s, const wfm_site_var_t* var
 int  wfm_sites_counts(const wfm_sites_t* s, uint64_t out[4]);
 void wfm_sites_free_list(void* p);
 
+/* ---- a net across records: which record owns each target base ----
+ * wfm_chain_runs makes one chain per record, overlapping records included.  A net object takes the blocks of many records and answers with
+ * the PIECES of them that are left when every target base is given to the best record over it (wfmash_amd/csrc/wfa_net.hip).
+ *
+ * BLOCKS AND RECORDS.  A record's blocks are those of wfm_chain_runs: its maximal stretches of =/X columns.  Block k has a global target
+ * start t, a query offset q (the text bases between the first base the runs spell and the block, in the direction of the runs) and a size.
+ * D bases belong to no block and are claimed by nobody; I runs advance only q.  Every record carries a score (32 bits) and an order (64
+ * bits, unique in the object).  Record A BEATS record B iff score_A > score_B, or the scores are equal and order_A < order_B.
+ * OWNER AND PIECES.  The owner of a target base is the best record with a block over it; a base under no block has no owner.  A piece is a
+ * maximal stretch of consecutive bases with the same owner inside the same block of that owner (two blocks of one record never abut or
+ * overlap, so "the same block" only matters for the definition): {order, t, q, size}, q = the block's q + (t - the block's t).  The NET is
+ * the list of pieces sorted by (order, t); per record it also gives the number of pieces and the bases won.  The net is a set function of
+ * (blocks, scores, orders): no order of calls, batches, threads or devices changes a byte of it.
+ * Deliberately none of these: chainNet's minSpace, minFill and minScore thresholds; nesting levels or a .net file; joining of records into
+ * one chain; single coverage on the query side.
+ *
+ * wfm_net_create: n_bases >= 2^40 is WFM_E_ARG with a message, as wfm_pav_create.  The object keeps its own device blocks (through the
+ *   block cache), is used with the handle it was made on and freed before it.  Memory follows the blocks, never n_bases.
+ * wfm_net_add: probs[i] = {base, runs_off, n_runs, score, order}, runs as wfm_coverage_add takes them.  score == WFM_NET_SCORE_EQ: the
+ *   problem's = columns, counted on the device.  One record entry per problem and one block per maximal stretch of =/X runs are appended;
+ *   a problem of gap runs only adds a record without blocks.  A problem with an empty run, without runs, or whose pattern or text span
+ *   does not fit 32 bits or leaves [0, n_bases] adds NOTHING and is flagged WFM_NET_SPANS in flags_out[i] (taken before anything is
+ *   written).  The slots are placed by scans, not atomics: two calls give the same list.  A run range that leaves the run buffer is
+ *   WFM_E_ARG with a message, and the handle stays usable.  Returns the number of problems flagged, or WFM_E_*.
+ * wfm_net_table: the net.  With N blocks: the 2 N block ends sorted (rocprim::radix_sort_keys) and compacted to the distinct coordinates
+ *   x[0 .. M], M <= 2 N - 1 elementary intervals; the records ranked by order and, by a second sort, given a dense priority (score
+ *   descending, order ascending); one lane per block finds its leaves [lo, hi) by two binary searches in x and takes a 64-bit integer
+ *   maximum of priority << 32 | block index into the O(log M) canonical nodes of an implicit segment tree over the M leaves (the maximum
+ *   of integers does not depend on the order of arrival); the maxima are pushed down level by level, one launch per level, a gather from
+ *   the parent; leaf k heads a piece iff its winner is non-zero and differs from leaf k - 1's; heads and tails are compacted by prefixes
+ *   of the flags; the pieces, which arrive in t order, are sorted stably by their record's rank in order.  Work is O((N + M) log M)
+ *   whatever the number of blocks that pile on a base.  Pieces come down in chunks of at most WFM_NET_OUT_MB MiB (environment, a decimal,
+ *   read per call, 256; one piece at least).  per[i] = {order, score as used, 0, first, count, bases_won, bases_aligned}, sorted by order,
+ *   locates record i's pieces.  Two records with the same order: WFM_E_ARG with a message, nothing written.  An empty object: WFM_OK, NULLs
+ *   and 0.  Host memory owned by the caller (wfm_net_free_list each).  The object is not changed: more may be added and the table taken again.
+ * wfm_net_export / _import: the raw blocks and record entries, so that the objects of several handles merge.  Import looks at
+ *   everything on the host before anything is added: size >= 1, the block inside [0, n_bases], q + size below 2^32, and every block's
+ *   record among the records given or already in the object; anything else is WFM_E_ARG with a message and nothing is added.  (That the
+ *   blocks of one record do not overlap is the caller's to keep: wfm_net_add's do not.)
+ * wfm_net_counts: out = {records added, blocks added (import included), and of the last table: elementary intervals M, pieces, records
+ *   that won nothing, 0}. */
+typedef struct wfm_net wfm_net_t;
+typedef struct { uint64_t base, runs_off; uint32_t n_runs, score; uint64_t order; } wfm_net_prob_t;   /* 32 bytes */
+typedef struct { uint64_t order, t; uint32_t q, size; } wfm_net_block_t;                               /* 24 bytes: a block, and a piece */
+typedef wfm_net_block_t wfm_net_piece_t;
+typedef struct { uint64_t order; uint32_t score, zero; } wfm_net_rec_t;                                /* 16 bytes */
+typedef struct { uint64_t order; uint32_t score, zero; uint64_t first, count, bases_won, bases_aligned; } wfm_netcall_t;   /* 48 bytes */
+#define WFM_NET_SCORE_EQ 0xffffffffu   /* wfm_net_prob_t::score: take the problem's = columns */
+#define WFM_NET_SPANS 2u               /* as WFM_PAV_SPANS: nothing of the problem is added */
+#define WFM_NET_SCAN_BLOCK 1024        /* elements one workgroup takes in the scans of the table */
+int  wfm_net_create(wfm_handle_t* h, uint64_t n_bases, wfm_net_t** net);
+void wfm_net_free(wfm_net_t* net);
+int  wfm_net_add(wfm_handle_t* h, wfm_net_t* net, const wfm_net_prob_t* probs, size_t n, const uint32_t* runs, size_t n_runs_total,
+                 uint32_t* flags_out);
+int  wfm_net_table(wfm_handle_t* h, wfm_net_t* net, wfm_net_piece_t** pieces, size_t* n_pieces, wfm_netcall_t** per, size_t* n_records);
+int  wfm_net_export(wfm_handle_t* h, wfm_net_t* net, wfm_net_block_t** blocks, size_t* n_blocks, wfm_net_rec_t** recs, size_t* n_recs);
+int  wfm_net_import(wfm_handle_t* h, wfm_net_t* net, const wfm_net_block_t* blocks, size_t n_blocks, const wfm_net_rec_t* recs, size_t n_recs);
+int  wfm_net_counts(const wfm_net_t* net, uint64_t out[6]);
+void wfm_net_free_list(void* p);
+
 /* ---- every score proved optimal by a banded DP ----
  * What wfm_check_runs leaves out.  For every problem of the seqset s whose result claims a score S = res[i].score, a classical
  * minimising gap-affine-2-piece DP over cells (i = pattern index, j = text index) is run on the device, restricted to a band of

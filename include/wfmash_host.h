@@ -234,6 +234,31 @@ int  wfmh_chain_paf(wfm_handle_t* h, const char* target_fasta, const char* align
  * per R line the flags its problem carries under `swap`.  Returns the chain file exactly as the align phase writes it, ids from 1; NULL
  * for a spec it cannot read.  malloc'd, wfmh_free. */
 char* wfmh_test_chain_lines(const char* spec, int swap, uint32_t* flags_out);
+/* ---- single-coverage chain files: a net across the records written (wfm_net_*, wfmash_hip.h) ----
+ * wfmh_set_chain_net(path): from now on every batch of wfmh_align_paf[_multi] runs ONE more device call behind the record writers
+ * (beside wfmh_set_chain's, with or without it): the runs of every record WRITTEN go to the net object of the batch's handle with
+ * score = the record's = columns and order = batch number << 32 | the record's index among the batch's records packed.  No output byte
+ * of the PAF, the SAM or the --chain file changes.  Once all batches are aligned the objects of the handles are merged into the first
+ * (export, import), the net is taken once on the device, and `path` is written: in the order of the PAF's records, ids 1, 2, 3 ..., one
+ * chain per record that won at least one target base, from the PIECES the net left it -- every target base lies under at most one chain,
+ * the chain of the record with the most = columns over it (the earlier record where they are equal).  A chain: the header of
+ * wfmh_set_chain's file with score = the score the record competed with, tStart = the first piece's start, tEnd = the last piece's end,
+ * qStart and qEnd from the first and last pieces on the record's strand; one line "size<TAB>dt<TAB>dq" per piece with the distances to
+ * the next piece on both sides, both of which may be non-zero, the last piece's `size` alone; one empty line.  A record that won nothing
+ * has no chain and is counted.  The file does not depend on the number of devices, handles, threads or the order of the batches.  Not
+ * here: chainNet's thresholds and levels, a .net file, joining records into one chain, single coverage on the query side (a swapped net).
+ * path NULL or "" switches it off.  Every call zeroes the counts.  wfmh_chain_net_counts: out = {records added, chains written, pieces,
+ * records that won nothing} since then.  Off by default; with the switch off nothing new is called and no file is written.
+ * wfmh_chain_net_paf: the same file for an existing aligned PAF, lines read and skipped as wfmh_chain_paf does, order = the number of the
+ * line among those taken; nothing else runs.  out = the same four counts.  Returns 0 or WFM_E_*. */
+void wfmh_set_chain_net(const char* path_or_null);
+int  wfmh_chain_net_counts(uint64_t out[4]);
+int  wfmh_chain_net_paf(wfm_handle_t* h, const char* target_fasta, const char* aligned_paf, const char* out_path, uint64_t out[4]);
+/* Test hook (no GPU): the text side alone (chain_text.hpp's net_body).  spec: lines "R<TAB>qname<TAB>qsize<TAB>qs<TAB>qe<TAB>strand<TAB>tname
+ * <TAB>tsize<TAB>t_offset<TAB>score" (a record as its PAF line has it, where its target sequence begins in the concatenation, the score it
+ * competed with) each followed by its pieces "P<TAB>t<TAB>q<TAB>size" as wfm_net_table gives them (t global).  Returns the file exactly as
+ * the align phase writes it, ids from 1; NULL for a spec it cannot read.  malloc'd, wfmh_free. */
+char* wfmh_test_chain_net_lines(const char* spec);
 
 /* ---- presence of target intervals per group of query sequences (wfm_pav_*, wfmash_hip.h) ----
  * wfmh_set_pav(bed, window, out): from now on every batch of wfmh_align_paf[_multi] runs ONE more device call behind the record writers:

@@ -55,6 +55,7 @@ EXPORTS = [
     "wfm_pav_free_list",
     "wfm_sites_create", "wfm_sites_free", "wfm_sites_add_variants", "wfm_sites_add_ref", "wfm_sites_table", "wfm_sites_export", "wfm_sites_import",
     "wfm_sites_counts", "wfm_sites_free_list",
+    "wfm_net_create", "wfm_net_free", "wfm_net_add", "wfm_net_table", "wfm_net_export", "wfm_net_import", "wfm_net_counts", "wfm_net_free_list",
     "wfm_sketch_intersections",
 ]
 ISECT_LDS_MAX = 4096  # WFM_ISECT_LDS_MAX: the longest column sketch wfm_sketch_intersections searches in LDS
@@ -90,6 +91,10 @@ WFM_PAV_SCAN_BLOCK = 1024
 WFM_SITES_SLICE = 64
 WFM_SITES_TASK = 16384
 WFM_E_ARG, WFM_E_INTERNAL = -3, -7
+# wfm_net_* (include/wfmash_hip.h): "take the = columns" as a problem's score, why a problem added nothing, the elements one workgroup scans
+WFM_NET_SCORE_EQ = 0xffffffff
+WFM_NET_SPANS = 2
+WFM_NET_SCAN_BLOCK = 1024
 # wfm_check_optimal (include/wfmash_hip.h): what a problem's score was flagged for, and the band widths at which the kernel changes form
 WFM_OPT_NOT_CHECKED, WFM_OPT_SKIPPED, WFM_OPT_CHEAPER, WFM_OPT_UNREACHED = 1, 2, 4, 8
 OPT_NAMES = ("NOT_CHECKED", "SKIPPED", "CHEAPER", "UNREACHED")
@@ -210,6 +215,11 @@ CHAINCALL_DTYPE = np.dtype([("flags", "<u4"), ("n_runs", "<u4"), ("first", "<u8"
 
 PAV_PROB_DTYPE = np.dtype([("base", "<u8"), ("runs_off", "<u8"), ("n_runs", "<u4"), ("group", "<u4")])
 PAV_SEG_DTYPE = np.dtype([("start", "<u8"), ("length", "<u4"), ("group", "<u4")])
+NET_PROB_DTYPE = np.dtype([("base", "<u8"), ("runs_off", "<u8"), ("n_runs", "<u4"), ("score", "<u4"), ("order", "<u8")])
+NET_BLOCK_DTYPE = np.dtype([("order", "<u8"), ("t", "<u8"), ("q", "<u4"), ("size", "<u4")])   # wfm_net_block_t, and a piece
+NET_REC_DTYPE = np.dtype([("order", "<u8"), ("score", "<u4"), ("zero", "<u4")])
+NET_CALL_DTYPE = np.dtype([("order", "<u8"), ("score", "<u4"), ("zero", "<u4"), ("first", "<u8"), ("count", "<u8"), ("bases_won", "<u8"),
+                           ("bases_aligned", "<u8")])
 SITE_VAR_DTYPE = np.dtype([("pos", "<u8"), ("kind", "<u4"), ("group", "<u4"), ("ref_len", "<u4"), ("alt_len", "<u4"), ("off", "<u8")])
 SITE_DTYPE = np.dtype([("pos", "<u8"), ("kind", "<u4"), ("n_carrier_groups", "<u4"), ("ref_len", "<u4"), ("alt_len", "<u4"), ("off", "<u8")])
 
@@ -960,6 +970,107 @@ class Sites:
         return tuple(int(v) for v in out)
 
 
+class Net:
+    """wfm_net_t: the blocks of many records, each with a score and a unique order, on the handle's device; .table() gives every target
+    base to the best record over it and returns the pieces that are left (include/wfmash_hip.h).  Close it before its handle."""
+
+    def __init__(self, handle, n_bases):
+        self._h, self._L = handle, handle._L
+        self.n_bases = int(n_bases)
+        self._p = None
+        L = self._L
+        P = C.POINTER
+        L.wfm_net_create.restype = C.c_int
+        L.wfm_net_create.argtypes = [C.c_void_p, C.c_uint64, P(C.c_void_p)]
+        L.wfm_net_free.restype = None
+        L.wfm_net_free.argtypes = [C.c_void_p]
+        L.wfm_net_add.restype = C.c_int
+        L.wfm_net_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.wfm_net_table.restype = C.c_int
+        L.wfm_net_table.argtypes = [C.c_void_p, C.c_void_p, P(C.c_void_p), P(C.c_size_t), P(C.c_void_p), P(C.c_size_t)]
+        L.wfm_net_export.restype = C.c_int
+        L.wfm_net_export.argtypes = [C.c_void_p, C.c_void_p, P(C.c_void_p), P(C.c_size_t), P(C.c_void_p), P(C.c_size_t)]
+        L.wfm_net_import.restype = C.c_int
+        L.wfm_net_import.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
+        L.wfm_net_counts.restype = C.c_int
+        L.wfm_net_counts.argtypes = [C.c_void_p, P(C.c_uint64)]
+        L.wfm_net_free_list.restype = None
+        L.wfm_net_free_list.argtypes = [C.c_void_p]
+        p = C.c_void_p()
+        rc = L.wfm_net_create(handle._p, self.n_bases, C.byref(p))
+        if rc != 0:
+            raise WfmError(f"wfm_net_create failed ({rc}): {handle.last_error()}")
+        self._p = p
+
+    def close(self):
+        if self._p:
+            self._L.wfm_net_free(self._p)
+            self._p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, problems, runs):
+        """wfm_net_add.  problems: a list of (base, runs_off, n_runs, score, order), score WFM_NET_SCORE_EQ for the = columns; runs: the run
+        words ((length << 2) | op).  Returns the problems' flags as a numpy array (WFM_NET_SPANS: nothing of the problem was added)."""
+        probs, probs_p = _run_problems(problems, NET_PROB_DTYPE)
+        runs = np.ascontiguousarray(runs, dtype=np.uint32)
+        flags = np.zeros(max(len(problems), 1), dtype=np.uint32)
+        rc = self._L.wfm_net_add(self._h._p, self._p, probs_p, len(probs), runs.ctypes.data if len(runs) else None, len(runs), flags.ctypes.data)
+        if rc < 0:
+            raise WfmError(f"wfm_net_add failed ({rc}): {self._h.last_error()}")
+        assert rc == int(np.count_nonzero(flags[:len(problems)] & WFM_NET_SPANS))
+        return flags[:len(problems)]
+
+    def _take(self, ptr, nbytes):
+        try:
+            return C.string_at(ptr, nbytes) if nbytes else b""
+        finally:
+            self._L.wfm_net_free_list(ptr)
+
+    def table(self):
+        """wfm_net_table: (the pieces {order, t, q, size} sorted by (order, t), the records {order, score, zero, first, count, bases_won,
+        bases_aligned} sorted by order), two numpy arrays."""
+        pp, rp, n, nr = C.c_void_p(), C.c_void_p(), C.c_size_t(0), C.c_size_t(0)
+        rc = self._L.wfm_net_table(self._h._p, self._p, C.byref(pp), C.byref(n), C.byref(rp), C.byref(nr))
+        if rc != 0:
+            raise WfmError(f"wfm_net_table failed ({rc}): {self._h.last_error()}")
+        if n.value == 0:
+            assert not pp.value
+        if nr.value == 0:
+            assert not rp.value and n.value == 0
+        return (np.frombuffer(self._take(pp, n.value * NET_BLOCK_DTYPE.itemsize), dtype=NET_BLOCK_DTYPE),
+                np.frombuffer(self._take(rp, nr.value * NET_CALL_DTYPE.itemsize), dtype=NET_CALL_DTYPE))
+
+    def export(self):
+        """wfm_net_export: (the raw blocks as an array of wfm_net_block_t, the record entries as an array of wfm_net_rec_t)."""
+        bp, rp, n, nr = C.c_void_p(), C.c_void_p(), C.c_size_t(0), C.c_size_t(0)
+        rc = self._L.wfm_net_export(self._h._p, self._p, C.byref(bp), C.byref(n), C.byref(rp), C.byref(nr))
+        if rc != 0:
+            raise WfmError(f"wfm_net_export failed ({rc}): {self._h.last_error()}")
+        return (np.frombuffer(self._take(bp, n.value * NET_BLOCK_DTYPE.itemsize), dtype=NET_BLOCK_DTYPE),
+                np.frombuffer(self._take(rp, nr.value * NET_REC_DTYPE.itemsize), dtype=NET_REC_DTYPE))
+
+    def import_(self, blocks, recs):
+        """wfm_net_import: what export returned (of another object, of another device), appended."""
+        b = np.ascontiguousarray(blocks, dtype=NET_BLOCK_DTYPE)
+        r = np.ascontiguousarray(recs, dtype=NET_REC_DTYPE)
+        rc = self._L.wfm_net_import(self._h._p, self._p, b.ctypes.data if len(b) else None, len(b), r.ctypes.data if len(r) else None, len(r))
+        if rc != 0:
+            raise WfmError(f"wfm_net_import failed ({rc}): {self._h.last_error()}")
+
+    def counts(self):
+        """wfm_net_counts: (records, blocks, and of the last table: elementary intervals, pieces, records that won nothing)."""
+        out = (C.c_uint64 * 6)()
+        rc = self._L.wfm_net_counts(self._p, out)
+        if rc != 0:
+            raise WfmError(f"wfm_net_counts failed ({rc})")
+        return tuple(int(v) for v in out)[:5]
+
+
 class Handle:
     """One handle per GPU (wfm_create)."""
 
@@ -1279,6 +1390,10 @@ class Handle:
         """wfm_sites_create: a sites object over n_bases target bases and n_groups groups on this handle's device; .add_variants, .add_ref,
         .table, .export, .import_, .counts, .close."""
         return Sites(self, n_bases, n_groups)
+
+    def net(self, n_bases):
+        """A Net on this handle's device over n_bases target bases (wfm_net_create)."""
+        return Net(self, n_bases)
 
     def coverage(self, n_bases):
         """wfm_coverage_create: a depth object over n_bases target bases on this handle's device."""
@@ -1646,6 +1761,7 @@ HOST_EXPORTS = ["wfmh_test_packed_lce", "wfmh_test_is_acgt", "wfmh_align_default
                 "wfmh_set_coverage", "wfmh_coverage_counts", "wfmh_coverage_paf", "wfmh_test_coverage_bedgraph",
                 "wfmh_set_lift", "wfmh_lift_counts", "wfmh_lift_paf", "wfmh_test_lift_lines",
                 "wfmh_set_chain", "wfmh_chain_counts", "wfmh_chain_paf", "wfmh_test_chain_lines",
+                "wfmh_set_chain_net", "wfmh_chain_net_counts", "wfmh_chain_net_paf", "wfmh_test_chain_net_lines",
                 "wfmh_set_pav", "wfmh_pav_counts", "wfmh_pav_paf", "wfmh_test_pav_text",
                 "wfmh_set_genotypes", "wfmh_genotypes_counts", "wfmh_test_genotype_text",
                 "wfmh_ani_matrix", "wfmh_ani_matrix_rows", "wfmh_free_ani_rows", "wfmh_set_ani_matrix", "wfmh_test_ani_tsv"]
@@ -2184,16 +2300,63 @@ def chain_counts():
     return tuple(int(v) for v in out)
 
 
-def chain_paf(handle, target_fasta, aligned_paf, out_path, swap=False):
-    """wfmh_chain_paf: the chain file of an existing aligned PAF; returns (chains written, blocks, records refused, 0)."""
-    f = _host().wfmh_chain_paf
-    f.restype = C.c_int
-    f.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_uint64)]
+def chain_paf(handle, target_fasta, aligned_paf, out_path, swap=False, net_path=None):
+    """wfmh_chain_paf: the chain file of an existing aligned PAF; returns (chains written, blocks, records refused, 0).  net_path: the
+    single-coverage file of the same PAF too (wfmh_chain_net_paf); with out_path None that file alone, and its counts (records added,
+    chains written, pieces, records that won nothing)."""
     out = (C.c_uint64 * 4)()
-    rc = f(handle._p, os.fsencode(target_fasta), os.fsencode(aligned_paf), os.fsencode(out_path), 1 if swap else 0, out)
+    net = (C.c_uint64 * 4)()
+    if out_path is not None:
+        f = _host().wfmh_chain_paf
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_uint64)]
+        rc = f(handle._p, os.fsencode(target_fasta), os.fsencode(aligned_paf), os.fsencode(out_path), 1 if swap else 0, out)
+        if rc != 0:
+            raise WfmError(f"wfmh_chain_paf failed ({rc}): {handle.last_error()}")
+    if net_path is not None:
+        f = _host().wfmh_chain_net_paf
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_uint64)]
+        rc = f(handle._p, os.fsencode(target_fasta), os.fsencode(aligned_paf), os.fsencode(net_path), net)
+        if rc != 0:
+            raise WfmError(f"wfmh_chain_net_paf failed ({rc}): {handle.last_error()}")
+    return tuple(int(v) for v in (out if out_path is not None else net))
+
+
+def set_chain_net(path) -> None:
+    """wfmh_set_chain_net: every later align_paf call of the process adds the blocks of every record it writes to a net object on the
+    device and, once all are aligned, writes the chain of the pieces the net left each record to `path` (None: off): every target base
+    under at most one chain; zeroes the counts."""
+    f = _host().wfmh_set_chain_net
+    f.restype = None
+    f.argtypes = [C.c_char_p]
+    f(os.fsencode(path) if path else None)
+
+
+def chain_net_counts():
+    """wfmh_chain_net_counts: (records added, chains written, pieces, records that won nothing) since wfmh_set_chain_net."""
+    f = _host().wfmh_chain_net_counts
+    f.restype = C.c_int
+    f.argtypes = [C.POINTER(C.c_uint64)]
+    out = (C.c_uint64 * 4)()
+    rc = f(out)
     if rc != 0:
-        raise WfmError(f"wfmh_chain_paf failed ({rc}): {handle.last_error()}")
+        raise WfmError(f"wfmh_chain_net_counts failed ({rc})")
     return tuple(int(v) for v in out)
+
+
+def host_chain_net_lines(spec):
+    """wfmh_test_chain_net_lines (no GPU): the --chain-net file of the records and pieces in `spec` (include/wfmash_host.h) as bytes."""
+    L = _host()
+    f = L.wfmh_test_chain_net_lines
+    f.restype = C.c_void_p
+    f.argtypes = [C.c_char_p]
+    p = f(spec.encode())
+    if not p:
+        raise WfmError("wfmh_test_chain_net_lines cannot read the spec")
+    s = C.string_at(p)
+    L.wfmh_free(p)
+    return s
 
 
 def host_chain_lines(spec, swap=False):

@@ -451,6 +451,73 @@ void launch_sites_rows(const SiteVar* vars, const uint32_t* perm, const uint32_t
 void launch_sites_gt(const SiteRow* rows, const uint32_t* first, const uint32_t* sk3, const unsigned long long* uks, const unsigned long long* uke,
                      const unsigned long long* C, unsigned long long m, unsigned long long ra, unsigned long long rb, uint32_t n_groups, uint8_t* out,
                      hipStream_t st);
+// wfm_net_* (wfa_net.hip).  A problem is wfm_net_prob_t as the caller wrote it, a block wfm_net_block_t, a record entry wfm_net_rec_t.
+struct NetProb {
+  uint64_t base, runs_off;
+  uint32_t n_runs, score;
+  uint64_t order;
+};
+struct NetBlock {
+  uint64_t order, t;
+  uint32_t q, size;
+};
+struct NetRec {
+  uint64_t order;
+  uint32_t score, zero;
+};
+struct NetPer {  // wfm_netcall_t
+  uint64_t order;
+  uint32_t score, zero;
+  uint64_t first, count, won, aligned;
+};
+// flags: nprob; word: nprob, (1 << 32 where the problem is taken) | the blocks it will write; off: nprob + 1, their exclusive prefixes (the
+// records before a problem in the high half, the blocks in the low one); score: nprob, the score each record competes with
+void launch_net_count(const uint32_t* runs, const NetProb* probs, int nprob, unsigned long long n_bases, uint32_t* flags, unsigned long long* word,
+                      unsigned long long* off, uint32_t* score, hipStream_t st);
+// the record entry and the blocks of every problem taken, from slots off[i] >> 32 of recs and off[i] & 0xffffffff of blocks on
+void launch_net_write(const uint32_t* runs, const NetProb* probs, int nprob, const uint32_t* flags, const unsigned long long* off, const uint32_t* score,
+                      NetBlock* blocks, NetRec* recs, hipStream_t st);
+// what the table call has on the device
+struct NetWork {
+  const NetBlock* blocks; unsigned long long n;  // the object's blocks
+  const NetRec* recs; uint32_t r;                // and record entries
+  unsigned long long *e, *e2;          // 2 n: the block ends, and sorted; e then holds x, the m + 1 distinct coordinates
+  unsigned long long* aux;             // the blocks' sums of a scan: 2 n / WFM_NET_SCAN_BLOCK rounded up, + 2
+  uint32_t* brank;                     // n: the rank in order of a block's record
+  unsigned long long *ro, *so;         // r: the orders, and sorted
+  uint32_t *ri, *sp;                   // r: 0, 1, 2, ...; the record at each rank
+  unsigned long long *k2, *k2s;        // r: ~score << 32 | rank, and sorted
+  uint32_t *p2, *prio, *sscore;        // r: the rank at each place of that sort; the priority (1 .. r) and the score by rank
+  unsigned long long *aligned, *won;   // r: by rank
+  uint32_t* bad;                       // 2 words: equal orders; blocks without a record
+  unsigned long long* tree;            // 2 m: node 1 the root, the leaves from m on
+  unsigned long long m;
+  unsigned long long *ps, *pe, *pw;    // p: a piece's start, end and winner
+  uint32_t *key, *val, *sk, *sv;       // p: the winner's rank and 0, 1, 2, ..., and sorted
+  unsigned long long p;
+};
+void launch_net_ends(const NetWork& w, hipStream_t st);
+hipError_t net_sort_keys(void* tmp, size_t* tmp_bytes, const unsigned long long* k, unsigned long long* k2, unsigned long long n, unsigned end_bit, hipStream_t st);
+// the distinct values of the sorted e2 to e; their number to aux[number of scan blocks]
+void launch_net_distinct(const NetWork& w, hipStream_t st);
+// ro = the orders, ri = 0, 1, 2 ...
+void launch_net_rec_keys(const NetWork& w, hipStream_t st);
+// (so, sp) sorted by order: bad[0] where two neighbours are equal, k2 = ~score << 32 | rank, sscore
+void launch_net_rec_rank(const NetWork& w, hipStream_t st);
+// (k2s, p2) sorted: prio[p2[i]] = r - i
+void launch_net_prio(const NetWork& w, hipStream_t st);
+// one lane per block: brank, aligned, and the maxima into the tree's canonical nodes
+void launch_net_fill(const NetWork& w, hipStream_t st);
+// the maxima pushed down, one launch per level
+void launch_net_push(const NetWork& w, hipStream_t st);
+// the number of pieces to aux[number of scan blocks]; then, with room for them, their starts, ends and winners
+void launch_net_heads_count(const NetWork& w, hipStream_t st);
+void launch_net_heads_write(const NetWork& w, hipStream_t st);
+// key = the winner's rank, val = 0, 1, 2 ..., won
+void launch_net_piece_keys(const NetWork& w, hipStream_t st);
+// the pieces at the sorted places [a, b), 24 bytes each
+void launch_net_pieces(const NetWork& w, unsigned long long a, unsigned long long b, NetBlock* out, hipStream_t st);
+void launch_net_per(const NetWork& w, NetPer* per, hipStream_t st);
 // wfm_check_optimal (wfa_optcheck.hip): a problem's forward byte copies, its ends-free allowances (clamped; 0 for the other modes),
 // its band of diagonals (wfa_optband.h) and, for the memory form, where its three row arrays begin in `rows` (32-bit elements)
 struct OptProb {

@@ -1,8 +1,8 @@
 // wfa_passes.hip -- the record passes of the C ABI (see include/wfmash_hip.h): host code that takes the final runs of a batch and
 // produces something from them -- the check against the bases, left-aligned gaps, cs strings, variants, target depth, lifted
-// intervals, the blocks of a chain, presence per group, the sites and genotypes of many records, the proof of optimality.  The kernels are
-// in wfa_check.hip, wfa_leftalign.hip, wfa_cs.hip, wfa_variants.hip, wfa_coverage.hip, wfa_lift.hip, wfa_chain.hip, wfa_pav.hip,
-// wfa_sites.hip and wfa_optcheck.hip.
+// intervals, the blocks of a chain, presence per group, the sites and genotypes of many records, the net across records, the proof of optimality.
+// The kernels are in wfa_check.hip, wfa_leftalign.hip, wfa_cs.hip, wfa_variants.hip, wfa_coverage.hip, wfa_lift.hip, wfa_chain.hip,
+// wfa_pav.hip, wfa_sites.hip, wfa_net.hip and wfa_optcheck.hip.
 //
 // Every pass has the same frame, written once below: it validates the run ranges before anything is launched, carves what the
 // call has on the device out of one block, launches, writes its output in chunks that fit a cap, and waits for the stream before
@@ -1471,6 +1471,309 @@ int wfm_sites_counts(const wfm_sites_t* s, uint64_t out[4]) {
 }
 
 void wfm_sites_free_list(void* p) { free(p); }
+
+// ---- a net across records: which record owns each target base (wfmash_hip.h; the kernels and the sorts: wfa_net.hip) ----
+struct wfm_net {
+  int device = 0;
+  uint64_t n_bases = 0;
+  NetBlock* blocks = nullptr;     // the raw blocks
+  size_t bcap = 0, n = 0;
+  NetRec* recs = nullptr;         // the record entries
+  size_t rcap = 0, r = 0;
+  std::vector<uint64_t> orders;   // the entries' orders once more, on the host: what import looks a block's record up in
+  DevBuf<uint64_t> work;          // an add call's problems, runs, flags, words and offsets; the table's block ends, coordinates and ranks
+  DevBuf<uint64_t> rw;            // the table's record keys, ranks, priorities and rows
+  DevBuf<uint64_t> tree;          // the table's tree
+  DevBuf<uint64_t> pc;            // the table's pieces, their keys and permutations
+  DevBuf<uint64_t> tmp;           // the sorts' own
+  uint64_t last_m = 0, last_pieces = 0, last_lost = 0;
+};
+
+extern "C++" {
+namespace {
+static_assert(sizeof(wfm_net_prob_t) == 32 && sizeof(NetProb) == 32 && sizeof(wfm_net_block_t) == 24 && sizeof(NetBlock) == 24 &&
+              sizeof(wfm_net_rec_t) == 16 && sizeof(NetRec) == 16 && sizeof(wfm_netcall_t) == 48 && sizeof(NetPer) == 48, "wfmash_hip.h states these sizes");
+constexpr size_t NET_MAX = ((size_t)1 << 31) - 1;  // blocks, and records: a winner is priority << 32 | block index
+
+int net_usable(wfm_handle_t* h, const wfm_net_t* net) { return DeviceGuard::usable(h, net->device, "the net object"); }
+unsigned bits_of(uint64_t v) { unsigned b = 0; while (b < 64 && (v >> b) != 0) ++b; return b; }
+}  // namespace
+}  // extern "C++"
+
+int wfm_net_create(wfm_handle_t* h, uint64_t n_bases, wfm_net_t** net) {
+  if (!h || !net) return WFM_E_ARG;
+  *net = nullptr;
+  if (n_bases >= ((uint64_t)1 << 40)) {
+    h->err = "wfm_net_create: " + std::to_string(n_bases) + " target bases: fewer than 2^40, as wfm_pav_create";
+    return WFM_E_ARG;
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  std::unique_ptr<wfm_net> p(new wfm_net());
+  p->device = h->device;
+  p->n_bases = n_bases;
+  *net = p.release();
+  return WFM_OK;
+}
+
+void wfm_net_free(wfm_net_t* net) {
+  if (!net) return;
+  DeviceGuard on(net->device);
+  net->work.release(); net->rw.release(); net->tree.release(); net->pc.release(); net->tmp.release();
+  if (net->blocks) wfm_dfree(net->blocks);
+  if (net->recs) wfm_dfree(net->recs);
+  delete net;
+}
+
+int wfm_net_add(wfm_handle_t* h, wfm_net_t* net, const wfm_net_prob_t* probs, size_t n, const uint32_t* runs, size_t n_runs_total, uint32_t* flags_out) {
+  if (!h || !net || (n && (!probs || !flags_out)) || (n_runs_total && !runs)) return WFM_E_ARG;
+  if (n == 0) return WFM_OK;
+  if (n > (size_t)INT32_MAX || n_runs_total > ((size_t)1 << 31)) { h->err = "wfm_net_add: too many problems or runs for one call"; return WFM_E_ARG; }
+  if (int rc = net_usable(h, net)) return rc;
+  if (int rc = all_runs_inside(h, probs, n, n_runs_total)) return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  PassTimer tm(h);
+  NetProb* d_probs;
+  uint32_t *d_runs, *d_flags, *d_score;
+  unsigned long long *d_word, *d_off;
+  Carver cv{net->work, "net add"};
+  cv.piece(&d_probs, n); cv.piece(&d_runs, n_runs_total); cv.piece(&d_flags, n); cv.piece(&d_score, n); cv.piece(&d_word, n); cv.piece(&d_off, n + 1);
+  if (int rc = cv.commit(h)) return rc;
+  HIPCHK(h, hipMemcpyAsync(d_probs, probs, n * sizeof(NetProb), hipMemcpyHostToDevice, h->stream));
+  if (n_runs_total) HIPCHK(h, hipMemcpyAsync(d_runs, runs, n_runs_total * 4, hipMemcpyHostToDevice, h->stream));
+  launch_net_count(d_runs, d_probs, (int)n, net->n_bases, d_flags, d_word, d_off, d_score, h->stream);
+  HIPCHK(h, hipGetLastError());
+  unsigned long long total = 0;
+  HIPCHK(h, hipMemcpyAsync(flags_out, d_flags, n * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(&total, d_off + n, 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  int spans = 0;
+  for (size_t i = 0; i < n; ++i) spans += (flags_out[i] & WFM_NET_SPANS) != 0;
+  const size_t add_r = (size_t)(total >> 32), add_b = (size_t)(total & 0xffffffffull);
+  if (add_r != n - (size_t)spans) { h->err = "wfm_net_add: the records do not add up"; return WFM_E_INTERNAL; }
+  if (add_r) {
+    if (add_b > NET_MAX - net->n || add_r > NET_MAX - net->r) { h->err = "wfm_net_add: more than 2^31 - 1 blocks or records in one object; nothing was added"; return WFM_E_ARG; }
+    if (int rc = sites_reserve(h, &net->blocks, &net->bcap, net->n, net->n + add_b, "net blocks")) return rc;
+    if (int rc = sites_reserve(h, &net->recs, &net->rcap, net->r, net->r + add_r, "net records")) return rc;
+    launch_net_write(d_runs, d_probs, (int)n, d_flags, d_off, d_score, net->blocks + net->n, net->recs + net->r, h->stream);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    net->n += add_b;
+    net->r += add_r;
+    for (size_t i = 0; i < n; ++i)
+      if (!(flags_out[i] & WFM_NET_SPANS)) net->orders.push_back(probs[i].order);
+  }
+  if (tm.on)
+    fprintf(stderr, "[wfm] net add: %zu problems, %zu runs, %zu blocks, %d flagged, %.3f ms (host clock, ends in a synchronise); the object holds %zu blocks of %zu records\n",
+            n, n_runs_total, add_b, spans, tm.host_ms(), net->n, net->r);
+  return spans;
+}
+
+int wfm_net_table(wfm_handle_t* h, wfm_net_t* net, wfm_net_piece_t** pieces, size_t* n_pieces, wfm_netcall_t** per, size_t* n_records) {
+  if (!h || !net || !pieces || !n_pieces || !per || !n_records) return WFM_E_ARG;
+  *pieces = nullptr; *n_pieces = 0; *per = nullptr; *n_records = 0;
+  if (int rc = net_usable(h, net)) return rc;
+  net->last_m = net->last_pieces = net->last_lost = 0;
+  if (net->r == 0) return WFM_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  PassTimer tm(h);
+  auto lap = [&]() -> double {  // (WFM_DEBUG alone pays for the waits)
+    if (!tm.on) return 0.0;
+    (void)hipStreamSynchronize(h->stream);
+    return tm.lap();
+  };
+  const size_t N = net->n, R = net->r, sb = (2 * N + WFM_NET_SCAN_BLOCK - 1) / WFM_NET_SCAN_BLOCK;
+  NetWork w{};
+  w.blocks = net->blocks; w.n = N; w.recs = net->recs; w.r = (uint32_t)R;
+  NetPer* d_per;
+  {
+    Carver cv{net->rw, "net table: records"};
+    cv.piece(&w.ro, R); cv.piece(&w.so, R); cv.piece(&w.k2, R); cv.piece(&w.k2s, R); cv.piece(&w.aligned, R); cv.piece(&w.won, R);
+    cv.piece(&d_per, R); cv.piece(&w.ri, R); cv.piece(&w.sp, R); cv.piece(&w.p2, R); cv.piece(&w.prio, R); cv.piece(&w.sscore, R); cv.piece(&w.bad, 2);
+    if (int rc = cv.commit(h)) return rc;
+  }
+  {
+    Carver cv{net->work, "net table: blocks"};
+    cv.piece(&w.e, 2 * N); cv.piece(&w.e2, 2 * N); cv.piece(&w.aux, sb + 2); cv.piece(&w.brank, N);
+    if (int rc = cv.commit(h)) return rc;
+  }
+  auto room = [&](size_t bytes) -> int {
+    if (net->tmp.ensure(bytes / 8 + 2)) { h->err = "out of device memory (net sort)"; return WFM_E_NOMEM; }
+    return WFM_OK;
+  };
+  // the records: ranked by order, then by (score descending, order ascending) into the priorities R .. 1
+  HIPCHK(h, hipMemsetAsync(w.aligned, 0, R * 8, h->stream));
+  HIPCHK(h, hipMemsetAsync(w.won, 0, R * 8, h->stream));
+  HIPCHK(h, hipMemsetAsync(w.bad, 0, 8, h->stream));
+  launch_net_rec_keys(w, h->stream);
+  size_t tb = 0;
+  HIPCHK(h, sites_sort64(nullptr, &tb, w.ro, w.so, w.ri, w.sp, (uint32_t)R, 64, h->stream));
+  if (int rc = room(tb)) return rc;
+  HIPCHK(h, sites_sort64(net->tmp.p, &tb, w.ro, w.so, w.ri, w.sp, (uint32_t)R, 64, h->stream));
+  launch_net_rec_rank(w, h->stream);
+  HIPCHK(h, sites_sort64(nullptr, &tb, w.k2, w.k2s, w.ri, w.p2, (uint32_t)R, 64, h->stream));
+  if (int rc = room(tb)) return rc;
+  HIPCHK(h, sites_sort64(net->tmp.p, &tb, w.k2, w.k2s, w.ri, w.p2, (uint32_t)R, 64, h->stream));
+  launch_net_prio(w, h->stream);
+  HIPCHK(h, hipGetLastError());
+  // the block ends, sorted, to the distinct coordinates
+  unsigned long long distinct = 0;
+  uint32_t bad[2] = {0, 0};
+  if (N) {
+    launch_net_ends(w, h->stream);
+    const unsigned end_bit = std::max(1u, bits_of(net->n_bases));  // (an end is n_bases at most)
+    HIPCHK(h, net_sort_keys(nullptr, &tb, w.e, w.e2, 2 * N, end_bit, h->stream));
+    if (int rc = room(tb)) return rc;
+    HIPCHK(h, net_sort_keys(net->tmp.p, &tb, w.e, w.e2, 2 * N, end_bit, h->stream));
+    launch_net_distinct(w, h->stream);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(&distinct, w.aux + sb, 8, hipMemcpyDeviceToHost, h->stream));
+  }
+  HIPCHK(h, hipMemcpyAsync(bad, w.bad, 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (bad[0]) { h->err = "wfm_net_table: two records have the same order; nothing was written"; return WFM_E_ARG; }
+  if (N && (distinct < 2 || distinct > 2 * N)) { h->err = "wfm_net_table: the coordinates do not add up"; return WFM_E_INTERNAL; }
+  const double t_sort = lap();
+  const size_t M = N ? (size_t)distinct - 1 : 0;
+  w.m = M;
+  size_t P = 0;
+  double t_fill = 0, t_push = 0, t_compact = 0;
+  if (M) {
+    if (net->tree.ensure(2 * M + 2)) { h->err = "out of device memory (net table: tree)"; return WFM_E_NOMEM; }
+    w.tree = (unsigned long long*)net->tree.p;
+    HIPCHK(h, hipMemsetAsync(w.tree, 0, 2 * M * 8, h->stream));
+    launch_net_fill(w, h->stream);
+    HIPCHK(h, hipGetLastError());
+    t_fill = lap();
+    launch_net_push(w, h->stream);
+    HIPCHK(h, hipGetLastError());
+    t_push = lap();
+    launch_net_heads_count(w, h->stream);
+    HIPCHK(h, hipGetLastError());
+    unsigned long long heads = 0;
+    const size_t mb = (M + WFM_NET_SCAN_BLOCK - 1) / WFM_NET_SCAN_BLOCK;
+    HIPCHK(h, hipMemcpyAsync(&heads, w.aux + mb, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(bad, w.bad, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (bad[1]) { h->err = "wfm_net_table: a block names a record that is not in the object"; return WFM_E_INTERNAL; }
+    if (heads == 0 || heads > M) { h->err = "wfm_net_table: the heads do not add up"; return WFM_E_INTERNAL; }
+    P = (size_t)heads;
+    w.p = P;
+    Carver cv{net->pc, "net table: pieces"};
+    cv.piece(&w.ps, P); cv.piece(&w.pe, P); cv.piece(&w.pw, P); cv.piece(&w.key, P); cv.piece(&w.val, P); cv.piece(&w.sk, P); cv.piece(&w.sv, P);
+    if (int rc = cv.commit(h)) return rc;
+    launch_net_heads_write(w, h->stream);
+    launch_net_piece_keys(w, h->stream);
+    HIPCHK(h, hipGetLastError());
+    // the pieces arrive in t order: a stable sort by the rank of their record leaves them sorted by (order, t)
+    const unsigned kb = bits_of(R - 1);
+    if (kb) {
+      HIPCHK(h, sites_sort32(nullptr, &tb, w.key, w.sk, w.val, w.sv, (uint32_t)P, kb, h->stream));
+      if (int rc = room(tb)) return rc;
+      HIPCHK(h, sites_sort32(net->tmp.p, &tb, w.key, w.sk, w.val, w.sv, (uint32_t)P, kb, h->stream));
+    } else {
+      w.sk = w.key; w.sv = w.val;
+    }
+    t_compact = lap();
+  }
+  launch_net_per(w, d_per, h->stream);
+  HIPCHK(h, hipGetLastError());
+  // the way down: the rows, then the pieces in chunks of at most WFM_NET_OUT_MB MiB through the handle's output block
+  const size_t cap = (size_t)cap_units("WFM_NET_OUT_MB", sizeof(wfm_net_piece_t), 1);
+  std::unique_ptr<wfm_netcall_t, void (*)(void*)> rows((wfm_netcall_t*)malloc(R * sizeof(wfm_netcall_t)), free);
+  std::unique_ptr<char, void (*)(void*)> out((char*)malloc(std::max<size_t>(P, 1) * sizeof(wfm_net_piece_t)), free);
+  if (!rows || !out) { h->err = "out of host memory (net table)"; return WFM_E_NOMEM; }
+  const bool pinned = cs_pin_pieces(h);
+  hipError_t e = cs_copy_down(h, pinned, (char*)rows.get(), (const uint8_t*)d_per, R * sizeof(wfm_netcall_t));
+  if (e != hipSuccess) { h->err = std::string("wfm_net_table: ") + hipGetErrorString(e); return WFM_E_HIP; }
+  size_t chunks = 0;
+  if (P) {
+    if (h->outblk.ensure(Carver::words64(std::min(P, cap) * sizeof(wfm_net_piece_t)) + 8)) { h->err = "out of device memory (net pieces)"; return WFM_E_NOMEM; }
+    NetBlock* d_out = (NetBlock*)h->outblk.p;
+    for (size_t a = 0, b; a < P; a = b, ++chunks) {
+      b = chunk_end(a, P, cap, [](size_t x, size_t y) { return (unsigned long long)(y - x); });
+      launch_net_pieces(w, a, b, d_out, h->stream);
+      e = hipGetLastError();
+      if (e == hipSuccess) e = cs_copy_down(h, pinned, out.get() + a * sizeof(wfm_net_piece_t), (const uint8_t*)d_out, (b - a) * sizeof(wfm_net_piece_t));  // (the block is the next chunk's)
+      if (e != hipSuccess) { h->err = std::string("wfm_net_table: ") + hipGetErrorString(e); return WFM_E_HIP; }
+    }
+  }
+  uint64_t lost = 0;
+  for (size_t i = 0; i < R; ++i) lost += rows.get()[i].count == 0;
+  net->last_m = M; net->last_pieces = P; net->last_lost = lost;
+  *n_pieces = P; *n_records = R;
+  *per = rows.release();
+  if (P) *pieces = (wfm_net_piece_t*)out.release();
+  if (tm.on)
+    fprintf(stderr, "[wfm] net table: %zu blocks of %zu records, %zu elementary intervals, %zu pieces, %llu records won nothing; sorts %.3f ms, tree fill %.3f ms, push-down %.3f ms, compaction and piece sort %.3f ms, rows and %zu chunks down %.3f ms, the call %.3f ms (host clock)\n",
+            N, R, M, P, (unsigned long long)lost, t_sort, t_fill, t_push, t_compact, chunks, tm.lap(), tm.host_ms());
+  return WFM_OK;
+}
+
+int wfm_net_export(wfm_handle_t* h, wfm_net_t* net, wfm_net_block_t** blocks, size_t* n_blocks, wfm_net_rec_t** recs, size_t* n_recs) {
+  if (!h || !net || !blocks || !n_blocks || !recs || !n_recs) return WFM_E_ARG;
+  *blocks = nullptr; *n_blocks = 0; *recs = nullptr; *n_recs = 0;
+  if (int rc = net_usable(h, net)) return rc;
+  if (net->r == 0) return WFM_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  wfm_net_block_t* b = (wfm_net_block_t*)malloc(std::max<size_t>(net->n, 1) * sizeof(wfm_net_block_t));
+  wfm_net_rec_t* r = (wfm_net_rec_t*)malloc(net->r * sizeof(wfm_net_rec_t));
+  const bool pinned = cs_pin_pieces(h);
+  hipError_t e = hipSuccess;
+  if (b && r) e = cs_copy_down(h, pinned, (char*)b, (const uint8_t*)net->blocks, net->n * sizeof(wfm_net_block_t));
+  if (b && r && e == hipSuccess) e = cs_copy_down(h, pinned, (char*)r, (const uint8_t*)net->recs, net->r * sizeof(wfm_net_rec_t));
+  if (!b || !r || e != hipSuccess) {
+    free(b); free(r);
+    if (e != hipSuccess) { h->err = std::string("wfm_net_export: ") + hipGetErrorString(e); return WFM_E_HIP; }
+    h->err = "out of host memory (net list)";
+    return WFM_E_NOMEM;
+  }
+  if (net->n) { *blocks = b; *n_blocks = net->n; } else free(b);
+  *recs = r; *n_recs = net->r;
+  return WFM_OK;
+}
+
+int wfm_net_import(wfm_handle_t* h, wfm_net_t* net, const wfm_net_block_t* blocks, size_t n_blocks, const wfm_net_rec_t* recs, size_t n_recs) {
+  if (!h || !net || (n_blocks && !blocks) || (n_recs && !recs)) return WFM_E_ARG;
+  if (n_blocks == 0 && n_recs == 0) return WFM_OK;
+  if (int rc = net_usable(h, net)) return rc;
+  if (n_blocks > NET_MAX - net->n || n_recs > NET_MAX - net->r) { h->err = "wfm_net_import: more than 2^31 - 1 blocks or records in one object; nothing was added"; return WFM_E_ARG; }
+  // everything is looked at before anything is added
+  std::vector<uint64_t> known(net->orders);
+  known.reserve(known.size() + n_recs);
+  for (size_t i = 0; i < n_recs; ++i) known.push_back(recs[i].order);
+  std::sort(known.begin(), known.end());
+  for (size_t i = 0; i < n_blocks; ++i) {
+    const wfm_net_block_t& b = blocks[i];
+    if (b.size == 0 || b.t > net->n_bases || b.size > net->n_bases - b.t || (uint64_t)b.q + b.size > 0xffffffffull) {
+      h->err = "wfm_net_import: block " + std::to_string(i) + " is empty, leaves the " + std::to_string(net->n_bases) + " target bases or ends beyond 2^32 query bases; nothing was added";
+      return WFM_E_ARG;
+    }
+    if (!std::binary_search(known.begin(), known.end(), b.order)) {
+      h->err = "wfm_net_import: block " + std::to_string(i) + " names the record of order " + std::to_string(b.order) + ", which is neither given nor in the object; nothing was added";
+      return WFM_E_ARG;
+    }
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  if (int rc = sites_reserve(h, &net->blocks, &net->bcap, net->n, net->n + n_blocks, "net blocks")) return rc;
+  if (int rc = sites_reserve(h, &net->recs, &net->rcap, net->r, net->r + n_recs, "net records")) return rc;
+  std::vector<NetRec> mine(n_recs);
+  for (size_t i = 0; i < n_recs; ++i) mine[i] = NetRec{recs[i].order, recs[i].score, 0u};
+  if (n_blocks) HIPCHK(h, hipMemcpyAsync(net->blocks + net->n, blocks, n_blocks * sizeof(NetBlock), hipMemcpyHostToDevice, h->stream));
+  if (n_recs) HIPCHK(h, hipMemcpyAsync(net->recs + net->r, mine.data(), n_recs * sizeof(NetRec), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  net->n += n_blocks;
+  net->r += n_recs;
+  for (size_t i = 0; i < n_recs; ++i) net->orders.push_back(recs[i].order);
+  return WFM_OK;
+}
+
+int wfm_net_counts(const wfm_net_t* net, uint64_t out[6]) {
+  if (!net || !out) return WFM_E_ARG;
+  out[0] = net->r; out[1] = net->n; out[2] = net->last_m; out[3] = net->last_pieces; out[4] = net->last_lost; out[5] = 0;
+  return WFM_OK;
+}
+
+void wfm_net_free_list(void* p) { free(p); }
 
 // ---- every score proved optimal by a banded DP (wfmash_hip.h; the band: wfa_optband.h; the kernel: wfa_optcheck.hip) ----
 int wfm_check_optimal(wfm_handle_t* h, const wfm_penalties_t* pen, const wfm_seqset_t* s, const wfm_result_t* res, uint64_t max_cells,

@@ -388,7 +388,7 @@ std::string Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<std::stri
                                  std::string* vcf, wfm_coverage_t* coverage, const std::vector<uint64_t>* seq_offsets, std::string* lift,
                                  const wfm_liftset_t* liftset, const std::vector<lift::Interval>* lift_intervals, wfm_pav_t* pav,
                                  const std::vector<uint32_t>* pav_columns, std::string* chain, bool chain_swap, wfm_sites_t* sites,
-                                 uint32_t sites_groups) {
+                                 uint32_t sites_groups, wfm_net_t* net, uint64_t net_batch, std::vector<wflign::NetHead>* net_heads) {
   const bool dbg = getenv("WFM_DEBUG") != nullptr;
   BatchTimes t;
   std::vector<Fetched> rows = parse_rows(lines, first_row, sum);
@@ -398,7 +398,7 @@ std::string Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<std::stri
   std::vector<Fetched> fetched = fetch_eager(rows, threads, sum);
   if (fetched.empty()) return std::string();
   std::vector<wflign::BiwfaRecord> recs = make_records(fetched);
-  if (coverage || liftset || pav || sites)
+  if (coverage || liftset || pav || sites || net)
     for (wflign::BiwfaRecord& r : recs) r.target_global = (*seq_offsets)[(size_t)ref->find(r.target_name)];  // (parse_rows has found every name)
   if (pav || sites)
     for (wflign::BiwfaRecord& r : recs) {
@@ -428,6 +428,9 @@ std::string Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<std::stri
   fmt.liftset = liftset;
   fmt.lift_intervals = lift_intervals;
   fmt.chain = chain ? (chain_swap ? 2 : 1) : 0;
+  fmt.net = net;
+  fmt.net_batch = net_batch;
+  fmt.net_heads = net_heads;
   const int rc = wflign::do_biwfa_alignment_batch(gpu_handle, recs, penalties_of(param), param.disable_chain_patching, filters_of(param), &st,
                                                   fmt, ds ? &resident : nullptr);
   if (rc < 0) throw std::runtime_error(std::string("[wfmash::align] GPU alignment failed: ") + st.error);
@@ -615,7 +618,23 @@ struct Aligner::Run {
     sites.emplace_back(h, p);
     return p;
   }
-  // --coverage, --lift, --pav, --genotypes: where each target sequence begins in the concatenation (nseq + 1 values; empty: all are off).  --coverage: the depth object
+  // --chain-net: the net object of every handle the run has used so far, made at the handle's first batch, and what the chains' headers
+  // need of every record added, in no order (finish_chain_net sorts them by their orders)
+  bool net_on = false;
+  std::mutex net_mu;
+  std::vector<std::pair<wfm_handle_t*, wfm_net_t*>> nets;
+  std::vector<wflign::NetHead> net_heads;
+  wfm_net_t* net_of(wfm_handle_t* h) {
+    if (!net_on) return nullptr;
+    std::lock_guard<std::mutex> lk(net_mu);
+    for (auto& hn : nets) if (hn.first == h) return hn.second;
+    wfm_net_t* p = nullptr;
+    std::lock_guard<std::mutex> hl(wflign::handle_lock(h));
+    if (wfm_net_create(h, seq_offsets.back(), &p) != WFM_OK) throw std::runtime_error(std::string("[wfmash::align] --chain-net: ") + wfm_last_error(h));
+    nets.emplace_back(h, p);
+    return p;
+  }
+  // --coverage, --lift, --pav, --genotypes, --chain-net: where each target sequence begins in the concatenation (nseq + 1 values; empty: all are off).  --coverage: the depth object
   // of every handle the run has used so far, made at the handle's first batch
   std::vector<uint64_t> seq_offsets;
   bool coverage_on = false;
@@ -637,6 +656,10 @@ struct Aligner::Run {
     for (auto& hs : sites) {
       std::lock_guard<std::mutex> lk(wflign::handle_lock(hs.first));
       wfm_sites_free(hs.second);
+    }
+    for (auto& hn : nets) {
+      std::lock_guard<std::mutex> lk(wflign::handle_lock(hn.first));
+      wfm_net_free(hn.second);
     }
   }
   wfm_coverage_t* coverage_of(wfm_handle_t* h) {
@@ -737,10 +760,15 @@ void Aligner::run_worker(Run& run, size_t wk) {
       wfm_set_concurrent_calls(run.use[wk], beside + (more && run.plan.per_gpu > 1 ? 1 : 0));
       struct Leave { std::atomic<int>& a; ~Leave() { a.fetch_sub(1); } } leave{run.in_flight[dev]};
       std::string vcf, lifted, chains;
+      std::vector<wflign::NetHead> heads;
       std::string text = align_batch(run.use[wk], batch, run.threads_each, run.part[wk], first_row, run.vcf_writer ? &vcf : nullptr,
                                      run.coverage_of(run.use[wk]), &run.seq_offsets, run.lift_writer ? &lifted : nullptr, run.liftset_of(run.use[wk]),
                                      &run.lift_iv, run.pav_of(run.use[wk]), &run.pav_cols.of_seq, run.chain_writer ? &chains : nullptr, run.chain_swap,
-                                     run.sites_of(run.use[wk]), (uint32_t)run.pav_cols.keys.size());
+                                     run.sites_of(run.use[wk]), (uint32_t)run.pav_cols.keys.size(), run.net_of(run.use[wk]), (uint64_t)seq, &heads);
+      if (!heads.empty()) {
+        std::lock_guard<std::mutex> lk(run.net_mu);
+        for (auto& hd : heads) run.net_heads.push_back(std::move(hd));
+      }
       const double at1 = run.ms();
       run.writer.put((uint64_t)seq, std::move(text));
       if (run.vcf_writer) run.vcf_writer->put((uint64_t)seq, std::move(vcf));
@@ -922,6 +950,60 @@ void Aligner::finish_genotypes(Run& run, std::ofstream& out) {
             run.sites.size(), (unsigned long long)counts[0], n_sites, G, (unsigned long long)counts[2], std::chrono::duration<double, std::milli>(t1 - t0).count(), ms_since(t1));
 }
 
+// --chain-net: every other handle's object exported and imported into the first (the net is a set function: the order does not matter),
+// the table of the merged object taken once on the device, the file through chain_text.hpp's net_body in the order of the orders, which
+// is the order of the PAF's records
+void Aligner::finish_chain_net(Run& run, std::ofstream& out) {
+  const auto t0 = Clock::now();
+  auto fail = [](wfm_handle_t* h, const char* what) { throw std::runtime_error(std::string("[wfmash::align] --chain-net: ") + what + ": " + wfm_last_error(h)); };
+  wfm_net_piece_t* pieces = nullptr;
+  wfm_netcall_t* per = nullptr;
+  size_t n_pieces = 0, n_rec = 0;
+  uint64_t counts[6] = {0, 0, 0, 0, 0, 0};
+  if (!run.nets.empty()) {
+    wfm_handle_t* h0 = run.nets.front().first;
+    wfm_net_t* n0 = run.nets.front().second;
+    for (size_t k = 1; k < run.nets.size(); ++k) {
+      wfm_net_block_t* blocks = nullptr;
+      wfm_net_rec_t* recs = nullptr;
+      size_t nb = 0, nr = 0;
+      {
+        std::lock_guard<std::mutex> lk(wflign::handle_lock(run.nets[k].first));
+        if (wfm_net_export(run.nets[k].first, run.nets[k].second, &blocks, &nb, &recs, &nr) != WFM_OK) fail(run.nets[k].first, "export");
+      }
+      std::lock_guard<std::mutex> lk(wflign::handle_lock(h0));
+      const int rc = wfm_net_import(h0, n0, blocks, nb, recs, nr);
+      wfm_net_free_list(blocks); wfm_net_free_list(recs);
+      if (rc != WFM_OK) fail(h0, "import");
+    }
+    std::lock_guard<std::mutex> lk(wflign::handle_lock(h0));
+    if (wfm_net_table(h0, n0, &pieces, &n_pieces, &per, &n_rec) != WFM_OK) fail(h0, "table");
+    wfm_net_counts(n0, counts);
+  }
+  const auto t1 = Clock::now();
+  static_assert(sizeof(chain::Piece) == sizeof(wfm_net_piece_t), "chain_text.hpp restates wfm_net_piece_t");
+  std::sort(run.net_heads.begin(), run.net_heads.end(), [](const wflign::NetHead& a, const wflign::NetHead& b) { return a.order < b.order; });
+  if (run.net_heads.size() != n_rec) throw std::runtime_error("[wfmash::align] --chain-net: the table's records are not the records added");
+  std::string body, text;
+  uint64_t next = 1, chains = 0, lost = 0;
+  for (size_t i = 0; i < n_rec; ++i) {  // (per is sorted by order too)
+    const wflign::NetHead& hd = run.net_heads[i];
+    if (hd.order != per[i].order) throw std::runtime_error("[wfmash::align] --chain-net: the table's records are not the records added");
+    if (per[i].count == 0) { ++lost; continue; }
+    chain::net_body(body, hd.rec, hd.t_offset, per[i].score, (const chain::Piece*)pieces + per[i].first, per[i].count);
+    if (body.size() >= ((size_t)1 << 20)) { text.clear(); chains += chain::number(body, &next, text); out << text; body.clear(); }
+  }
+  text.clear();
+  chains += chain::number(body, &next, text);
+  out << text;
+  wfm_net_free_list(pieces); wfm_net_free_list(per);
+  wflign::chain_net_finished(chains, n_pieces, lost);
+  if (getenv("WFM_DEBUG"))
+    fprintf(stderr, "[wfmash::align] chain-net: %zu objects merged, %llu records, %llu blocks, %llu elementary intervals, %zu pieces, %llu chains, %llu records won nothing, merge + table %.1f ms, text %.1f ms\n",
+            run.nets.size(), (unsigned long long)counts[0], (unsigned long long)counts[1], (unsigned long long)counts[2], n_pieces, (unsigned long long)chains,
+            (unsigned long long)lost, std::chrono::duration<double, std::milli>(t1 - t0).count(), ms_since(t1));
+}
+
 Summary Aligner::compute() {
   Summary sum;
   const auto t0 = Clock::now();
@@ -967,13 +1049,20 @@ Summary Aligner::compute() {
     if (!chainstream.is_open()) throw std::runtime_error("[wfmash::align] Error! Failed to open the chain file: " + chain_out);
     run.chain_writer.reset(new skch::OrderedWriter<std::string, ChainSink>(ChainSink{&chainstream}));
   }
+  std::ofstream netstream;
+  const std::string net_out = wflign::chain_net_path();
+  if (!net_out.empty()) {  // --chain-net: the file is opened before anything is aligned, and written once the workers are done
+    netstream.open(net_out);
+    if (!netstream.is_open()) throw std::runtime_error("[wfmash::align] Error! Failed to open the chain-net file: " + net_out);
+    run.net_on = true;
+  }
   std::ofstream pavstream;
   std::string pav_bed, pav_out;
   uint64_t pav_window = 0, pav_skipped = 0;
   wflign::pav_paths(pav_bed, pav_window, pav_out);
   std::ofstream gtstream;
   const std::string gt_path = wflign::genotypes_path();
-  if (!cov_path.empty() || !lift_out.empty() || !pav_out.empty() || !gt_path.empty()) {
+  if (!cov_path.empty() || !lift_out.empty() || !pav_out.empty() || !gt_path.empty() || !net_out.empty()) {
     run.seq_offsets.assign(1, 0);
     for (int i = 0; i < ref->nseq(); ++i) run.seq_offsets.push_back(run.seq_offsets.back() + (uint64_t)ref->length(i));
   }
@@ -1039,6 +1128,7 @@ Summary Aligner::compute() {
   if (covstream.is_open()) { finish_coverage(run, covstream); covstream.close(); }
   if (pavstream.is_open()) { finish_pav(run, pavstream, pav_skipped); pavstream.close(); }
   if (gtstream.is_open()) { finish_genotypes(run, gtstream); gtstream.close(); }
+  if (netstream.is_open()) { finish_chain_net(run, netstream); netstream.close(); }
   sum_up(sum, run.part, t0);
   outstream.close();
   if (vcfstream.is_open()) vcfstream.close();

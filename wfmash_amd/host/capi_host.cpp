@@ -211,6 +211,57 @@ char* wfmh_test_chain_lines(const char* spec, int swap, uint32_t* flags_out) {
   return p;
 }
 
+// test hook (no GPU): the text side of --chain-net (chain_text.hpp's net_body): the file of given records and pieces
+char* wfmh_test_chain_net_lines(const char* spec) {
+  if (!spec) return nullptr;
+  std::string body;
+  chain::Record r;
+  uint64_t t_offset = 0, score = 0;
+  std::vector<chain::Piece> pieces;
+  bool open = false;
+  auto close = [&]() {
+    if (open) chain::net_body(body, r, t_offset, (uint32_t)score, pieces.data(), pieces.size());
+    pieces.clear();
+  };
+  std::istringstream in(spec);
+  std::string line;
+  while (std::getline(in, line)) {
+    if (line.empty()) continue;
+    std::vector<std::string> f;
+    for (size_t at = 0;;) {
+      const size_t tab = line.find('\t', at);
+      f.push_back(line.substr(at, tab == std::string::npos ? std::string::npos : tab - at));
+      if (tab == std::string::npos) break;
+      at = tab + 1;
+    }
+    uint64_t v[3] = {0, 0, 0};
+    if (f[0] == "R" && f.size() == 10) {
+      close();
+      open = true;
+      r = chain::Record();
+      r.qname = f[1]; r.tname = f[6]; r.rev = f[5] == "-";
+      if (!lift::decimal(f[2], 0, f[2].size(), &r.qsize) || !lift::decimal(f[3], 0, f[3].size(), &r.qs) || !lift::decimal(f[4], 0, f[4].size(), &r.qe) ||
+          !lift::decimal(f[7], 0, f[7].size(), &r.tsize) || !lift::decimal(f[8], 0, f[8].size(), &t_offset) || !lift::decimal(f[9], 0, f[9].size(), &score) ||
+          score > 0xffffffffull)
+        return nullptr;
+    } else if (f[0] == "P" && f.size() == 4 && open) {
+      for (int k = 0; k < 3; ++k)
+        if (!lift::decimal(f[(size_t)k + 1], 0, f[(size_t)k + 1].size(), &v[k])) return nullptr;
+      if (v[1] > 0xffffffffull || v[2] > 0xffffffffull) return nullptr;
+      pieces.push_back(chain::Piece{0, v[0], (uint32_t)v[1], (uint32_t)v[2]});
+    } else {
+      return nullptr;
+    }
+  }
+  close();
+  std::string out;
+  uint64_t next = 1;
+  chain::number(body, &next, out);
+  char* p = (char*)malloc(out.size() + 1);
+  if (p) memcpy(p, out.c_str(), out.size() + 1);
+  return p;
+}
+
 // test hook (no GPU): the text side of --pav (pav_text.hpp): the names' keys and columns, the header, the windows' rows
 char* wfmh_test_pav_text(const char* const* names, int n_q, const char* const* tnames, const uint64_t* lengths, int n_t, uint64_t window) {
   if (n_q < 0 || n_t < 0 || (n_q && !names) || (n_t && (!tnames || !lengths))) return nullptr;

@@ -1,6 +1,7 @@
-// chain_text.hpp -- the text side of --chain: which flags a record's device problem carries, the coordinates of the two sides of a UCSC
-// chain and the lines of the chain file.  Pure host code on the standard library alone, so that it can be built on its own
-// (scripts/micro/chain_check.cpp runs it under the address and undefined-behaviour sanitizers).
+// chain_text.hpp -- the text side of --chain and --chain-net: which flags a record's device problem carries, the coordinates of the two
+// sides of a UCSC chain and the lines of the chain file, from a record's blocks (--chain) or from the pieces the net left it
+// (--chain-net).  Pure host code on the standard library alone, so that it can be built on its own (scripts/micro/chain_check.cpp and
+// scripts/micro/chain_net_check.cpp run it under the address and undefined-behaviour sanitizers).
 #pragma once
 
 #include <cstdint>
@@ -50,6 +51,37 @@ inline void chain_body(std::string& out, const Record& r, bool swap, const Ends&
     const Block& b = blocks[k];
     if (k + 1 < n) out.append(num, (size_t)snprintf(num, sizeof num, "%u\t%u\t%u\n", b.size, b.dt, b.dq));
     else out.append(num, (size_t)snprintf(num, sizeof num, "%u\n\n", b.size));
+  }
+}
+
+// a piece as wfm_net_table gives it (wfm_net_piece_t): a global target start, the query offset from the first base the record's runs
+// spell, in the direction of the runs, and a size
+struct Piece { uint64_t order, t; uint32_t q, size; };
+
+// One chain of --chain-net WITHOUT its id, from the n pieces the net left the record, in ascending t (and so ascending q): the header as
+// chain_body's with score = the score the record competed with, tStart = the first piece's t - t_offset (the target sequence's place in
+// the concatenation), tEnd = the last piece's end, qStart and qEnd from the first and last pieces' q behind where chain_body's second
+// side begins (r.qs on +, qsize - r.qe on -: the runs of a - record walk the reverse strand); one line "size<TAB>dt<TAB>dq" per piece
+// with the distances to the next piece on both sides (both may be non-zero: what lay between went to other records), the last piece's
+// `size` alone, one empty line.  Nothing is written for a record that won nothing.
+inline void net_body(std::string& out, const Record& r, uint64_t t_offset, uint32_t score, const Piece* pieces, uint64_t n) {
+  if (n == 0) return;
+  const uint64_t bs = r.rev ? r.qsize - r.qe : r.qs;
+  const Piece &first = pieces[0], &last = pieces[n - 1];
+  char num[200];
+  out.append(num, (size_t)snprintf(num, sizeof num, "chain %u ", score));
+  out += r.tname;
+  out.append(num, (size_t)snprintf(num, sizeof num, " %llu + %llu %llu ", (unsigned long long)r.tsize, (unsigned long long)(first.t - t_offset),
+                                   (unsigned long long)(last.t + last.size - t_offset)));
+  out += r.qname;
+  out.append(num, (size_t)snprintf(num, sizeof num, " %llu %c %llu %llu \n", (unsigned long long)r.qsize, r.rev ? '-' : '+', (unsigned long long)(bs + first.q),
+                                   (unsigned long long)(bs + last.q + last.size)));
+  for (uint64_t k = 0; k < n; ++k) {
+    const Piece& p = pieces[k];
+    if (k + 1 < n)
+      out.append(num, (size_t)snprintf(num, sizeof num, "%u\t%llu\t%llu\n", p.size, (unsigned long long)(pieces[k + 1].t - (p.t + p.size)),
+                                       (unsigned long long)((uint64_t)pieces[k + 1].q - ((uint64_t)p.q + p.size))));
+    else out.append(num, (size_t)snprintf(num, sizeof num, "%u\n\n", p.size));
   }
 }
 

@@ -72,9 +72,17 @@
 //                                              not blastz's score); --chain-swap: the file chainSwap would make of it, from the query to the
 //                                              target; no output byte of the PAF or SAM changes; allowed and refused beside what --lift is;
 //                                              --chain-swap without --chain is an error; off by default
-//   --chain-paf IN.paf --chain FILE [--chain-swap] target.fa [query.fa]   the same file for an existing aligned PAF: no mapping, no
-//                                              alignment; lines are skipped and counted as --coverage-paf does (the query's name and
-//                                              length are the line's: query.fa is not read); only --device beside it
+//   --chain-net FILE                           a single-coverage chain file: the blocks of every record WRITTEN go to a net object on the
+//                                              device (wfm_net_*), which gives every target base to the record with the most = columns over
+//                                              it (the earlier record where they are equal); once all are aligned, one chain per record that
+//                                              won a base, from the pieces left to it, in the order of the PAF's records: an .over.chain for
+//                                              liftOver, CrossMap and bcftools +liftover without chainSort | chainNet | netChainSubset; with
+//                                              or without --chain, whose bytes do not change; refused where --chain is, and with
+//                                              --chain-swap (nets on the query side are not done); off by default
+//   --chain-paf IN.paf [--chain FILE [--chain-swap]] [--chain-net FILE] target.fa [query.fa]   the same file(s) for an existing aligned
+//                                              PAF, one of the two at least: no mapping, no alignment; lines are skipped and counted as
+//                                              --coverage-paf does (the query's name and length are the line's: query.fa is not read);
+//                                              only --device beside it
 //   --pav IN.bed | --pav-window N, --pav-out FILE   which groups of query sequences (haplotypes, samples: the part of the name before its
 //                                              last '#') have each target interval, and how much of it: the runs of every record WRITTEN go
 //                                              into a per-group union of aligned segments on the device (wfm_pav_*; 16 bytes a segment, never
@@ -193,7 +201,8 @@ static void usage() {
           "            --lift-paf FILE with --lift, --lift-out: lift through an existing aligned PAF over target.fa, and stop (only --device beside it)\n"
           "            --chain FILE  write a UCSC chain file (target to query) of every record written, blocks and gaps made on the GPU; score = the = columns (not with -m, --verify-paf)\n"
           "            --chain-swap  with --chain: the swapped file (query to target), what chainSwap would make of it\n"
-          "            --chain-paf FILE with --chain: the chain file of an existing aligned PAF over target.fa, and stop (only --chain-swap and --device beside it)\n"
+          "            --chain-net FILE write a single-coverage chain file: every target base under at most one chain, the best record's, from a net across the records on the GPU (with or without --chain; not with -m, --verify-paf, --chain-swap)\n"
+          "            --chain-paf FILE with --chain and/or --chain-net: the chain file(s) of an existing aligned PAF over target.fa, and stop (only --chain-swap and --device beside it)\n"
           "            --pav BED | --pav-window N, --pav-out FILE per target interval and group of query sequences the bases present, from per-group unions on the GPU (not with -m, --verify-paf)\n"
           "            --genotypes FILE write ONE sorted VCF of the distinct variants of all records with a haploid GT column (0, 1, .) per group of query sequences, joined on the GPU (give --left-align too; not with -m, --verify-paf)\n"
           "            --pav-paf FILE with --pav or --pav-window, --pav-out: the table of an existing aligned PAF over target.fa [query.fa], and stop (only --device beside it)\n"
@@ -208,7 +217,7 @@ int main(int argc, char** argv) {
   ap.threads = 1;  // -t, default 1 as in the reference (parse_args.hpp: thread_count); the C ABI default (0) means all cores
   wfmh_map_params_t mp;
   wfmh_map_default_params(&mp);
-  std::string mapping_in, out = "/dev/stdout", target, query, seeds_in, scaffold_out, tmp_base, verify_in, ani_matrix_out, variants_out, genotypes_out, coverage_out, coverage_in, lift_bed, lift_out, lift_in, pav_bed, pav_out, pav_in, chain_out, chain_in;
+  std::string mapping_in, out = "/dev/stdout", target, query, seeds_in, scaffold_out, tmp_base, verify_in, ani_matrix_out, variants_out, genotypes_out, coverage_out, coverage_in, lift_bed, lift_out, lift_in, pav_bed, pav_out, pav_in, chain_out, chain_in, chain_net_out;
   uint64_t pav_window = 0;
   bool pav_window_set = false;
   bool pav_other = false;      // --pav-paf: anything beside it, --pav, --pav-window, --pav-out, --device and the two FASTAs
@@ -224,7 +233,7 @@ int main(int argc, char** argv) {
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
     if (a[0] == '-' ? (a != "--pav" && a != "--pav-window" && a != "--pav-out" && a != "--pav-paf" && a != "--device" && a != "-h" && a != "--help") : !query.empty()) pav_other = true;
-    if (a[0] == '-' ? (a != "--chain" && a != "--chain-swap" && a != "--chain-paf" && a != "--device" && a != "-h" && a != "--help") : !query.empty()) chain_other = true;
+    if (a[0] == '-' ? (a != "--chain" && a != "--chain-net" && a != "--chain-swap" && a != "--chain-paf" && a != "--device" && a != "-h" && a != "--help") : !query.empty()) chain_other = true;
     if (a[0] == '-' ? (a != "--lift" && a != "--lift-out" && a != "--lift-paf" && a != "--device" && a != "-h" && a != "--help") : !target.empty()) lift_other = true;
     if (a[0] == '-' ? (a != "--coverage" && a != "--coverage-paf" && a != "--device" && a != "-h" && a != "--help") : !target.empty()) other_options = true;
     auto next = [&](const char* name) -> std::string {
@@ -367,6 +376,7 @@ int main(int argc, char** argv) {
     else if (a == "--lift-out") lift_out = next("--lift-out");
     else if (a == "--lift-paf") lift_in = next("--lift-paf");
     else if (a == "--chain") chain_out = next("--chain");
+    else if (a == "--chain-net") chain_net_out = next("--chain-net");
     else if (a == "--chain-swap") chain_swap = true;
     else if (a == "--chain-paf") chain_in = next("--chain-paf");
     else if (a == "--pav") pav_bed = next("--pav");
@@ -404,8 +414,11 @@ int main(int argc, char** argv) {
   if (!lift_bed.empty() && !verify_in.empty()) { fprintf(stderr, "[wfmash] ERROR: --lift belongs to the align phase: it cannot be combined with --verify-paf\n"); return 1; }
   if (!genotypes_out.empty() && approx_only) { fprintf(stderr, "[wfmash] ERROR: --genotypes reads alignments: it cannot be combined with -m\n"); return 1; }
   if (!genotypes_out.empty() && !verify_in.empty()) { fprintf(stderr, "[wfmash] ERROR: --genotypes belongs to the align phase: it cannot be combined with --verify-paf\n"); return 1; }
+  if (!chain_net_out.empty() && chain_swap) { fprintf(stderr, "[wfmash] ERROR: --chain-net cannot be combined with --chain-swap: nets on the query side are not done\n"); return 1; }
   if (chain_swap && chain_out.empty()) { fprintf(stderr, "[wfmash] ERROR: --chain-swap needs --chain FILE\n"); return 1; }
-  if (!chain_in.empty() && chain_out.empty()) { fprintf(stderr, "[wfmash] ERROR: --chain-paf needs --chain FILE\n"); return 1; }
+  if (!chain_in.empty() && chain_out.empty() && chain_net_out.empty()) { fprintf(stderr, "[wfmash] ERROR: --chain-paf needs --chain FILE\n"); return 1; }
+  if (!chain_net_out.empty() && approx_only) { fprintf(stderr, "[wfmash] ERROR: --chain-net writes chains of alignments: it cannot be combined with -m\n"); return 1; }
+  if (!chain_net_out.empty() && !verify_in.empty()) { fprintf(stderr, "[wfmash] ERROR: --chain-net belongs to the align phase: it cannot be combined with --verify-paf\n"); return 1; }
   if (!chain_out.empty() && approx_only) { fprintf(stderr, "[wfmash] ERROR: --chain writes chains of alignments: it cannot be combined with -m\n"); return 1; }
   if (!chain_out.empty() && !verify_in.empty()) { fprintf(stderr, "[wfmash] ERROR: --chain belongs to the align phase: it cannot be combined with --verify-paf\n"); return 1; }
   if (!chain_in.empty() && chain_other) { fprintf(stderr, "[wfmash] ERROR: --chain-paf runs nothing else: besides --chain FILE, --chain-swap and the FASTAs it takes the number of the GPU only\n"); return 1; }
@@ -445,7 +458,8 @@ int main(int argc, char** argv) {
     wfm_handle_t* hc = nullptr;
     if (wfm_create(device, &hc) != WFM_OK) { fprintf(stderr, "[wfmash] ERROR: no usable MI355X device %d (there is no CPU fallback)\n", device); return 2; }
     uint64_t cc[4] = {0, 0, 0, 0};
-    const int crc = wfmh_chain_paf(hc, target.c_str(), chain_in.c_str(), chain_out.c_str(), chain_swap ? 1 : 0, cc);
+    int crc = chain_out.empty() ? WFM_OK : wfmh_chain_paf(hc, target.c_str(), chain_in.c_str(), chain_out.c_str(), chain_swap ? 1 : 0, cc);
+    if (crc == WFM_OK && !chain_net_out.empty()) crc = wfmh_chain_net_paf(hc, target.c_str(), chain_in.c_str(), chain_net_out.c_str(), cc);
     if (crc != WFM_OK) fprintf(stderr, "[wfmash::chain] ERROR: %s\n", wfm_last_error(hc));
     wfm_destroy(hc);
     return crc == WFM_OK ? 0 : 2;
@@ -592,6 +606,7 @@ int main(int argc, char** argv) {
     if (!coverage_out.empty()) wfmh_set_coverage(coverage_out.c_str());
     if (!lift_bed.empty()) wfmh_set_lift(lift_bed.c_str(), lift_out.c_str());
     if (!chain_out.empty()) wfmh_set_chain(chain_out.c_str(), chain_swap ? 1 : 0);
+    if (!chain_net_out.empty()) wfmh_set_chain_net(chain_net_out.c_str());
     if (pav_on) wfmh_set_pav(pav_bed.empty() ? nullptr : pav_bed.c_str(), pav_window, pav_out.c_str());
     rc = wfmh_align_paf_multi(hs.data(), (int)hs.size(), target.c_str(), q, mapping.c_str(), out.c_str(), &ap, &s);
     if (rc == WFM_OK)
@@ -639,6 +654,12 @@ int main(int argc, char** argv) {
       wfmh_chain_counts(hc);
       fprintf(stderr, "[wfmash::chain] %llu chains written, %llu blocks, %llu records refused\n", (unsigned long long)hc[0], (unsigned long long)hc[1],
               (unsigned long long)hc[2]);
+    }
+    if (!chain_net_out.empty() && rc == WFM_OK) {
+      uint64_t nc[4] = {0, 0, 0, 0};
+      wfmh_chain_net_counts(nc);
+      fprintf(stderr, "[wfmash::chain-net] %llu records added, %llu chains written, %llu pieces, %llu records won nothing\n", (unsigned long long)nc[0],
+              (unsigned long long)nc[1], (unsigned long long)nc[2], (unsigned long long)nc[3]);
     }
     if (!coverage_out.empty() && rc == WFM_OK) {
       uint64_t cc[4] = {0, 0, 0, 0};

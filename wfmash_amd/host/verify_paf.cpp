@@ -447,6 +447,80 @@ int wfmh_chain_paf(wfm_handle_t* h, const char* target_fasta, const char* aligne
   }
 }
 
+// --chain-paf with --chain-net: the single-coverage file of an existing aligned PAF.  Lines go to a net object in batches of runs, read and
+// skipped by wfmh_coverage_paf's rules; order = the number of the line among those taken; the table once, at the end.
+int wfmh_chain_net_paf(wfm_handle_t* h, const char* target_fasta, const char* aligned_paf, const char* out_path, uint64_t out[4]) {
+  if (!h || !target_fasta || !aligned_paf || !out_path) return WFM_E_ARG;
+  wfm_net_t* net = nullptr;
+  try {
+    std::shared_ptr<wfmash_host::FastaStore> target = wfmash_host::open_shared(target_fasta);
+    std::ifstream in(aligned_paf);
+    if (!in.is_open()) throw std::runtime_error(std::string("[wfmash::chain-net] cannot open ") + aligned_paf);
+    std::ofstream outstream(out_path);
+    if (!outstream.is_open()) throw std::runtime_error(std::string("[wfmash::chain-net] cannot open ") + out_path);
+    PafRuns pr(h, "chain-net", *target);
+    const uint64_t* skipped = pr.skipped;
+    std::lock_guard<std::mutex> lk(wflign::handle_lock(h));
+    pr.device(wfm_net_create(h, pr.offsets.back(), &net), "create");
+    std::vector<chain::Record> where, kept;   // of the batch; of every line added, in the order of their orders
+    std::vector<uint64_t> kept_off;
+    std::vector<wfm_net_prob_t> probs;
+    std::vector<uint32_t> flags;
+    uint64_t taken = 0;
+    auto flush = [&]() {
+      probs.resize(pr.probs.size());
+      flags.resize(pr.probs.size());
+      for (size_t j = 0; j < probs.size(); ++j) probs[j] = wfm_net_prob_t{pr.probs[j].base, pr.probs[j].runs_off, pr.probs[j].n_runs, WFM_NET_SCORE_EQ, taken + j};
+      const int refused = pr.device(wfm_net_add(h, net, probs.data(), probs.size(), pr.runs.data(), pr.runs.size(), flags.data()), "add");
+      for (size_t j = 0; j < probs.size(); ++j) {
+        if (flags[j]) continue;
+        kept_off.push_back(pr.probs[j].base - where[j].ts);  // (the base is the sequence's offset + the line's target start)
+        kept.push_back(std::move(where[j]));
+      }
+      pr.refused((uint64_t)refused);
+      taken += probs.size();
+      where.clear();
+    };
+    pr.read(in, [&](const verify::Line& l) {
+      chain::Record r;
+      r.qname = l.qname; r.tname = l.tname; r.rev = l.rev;
+      r.qsize = (uint64_t)l.qlen; r.qs = (uint64_t)l.qs; r.qe = (uint64_t)l.qe; r.tsize = (uint64_t)l.tlen; r.ts = (uint64_t)l.ts; r.te = (uint64_t)l.te;
+      where.push_back(std::move(r));
+      return true;
+    }, flush);
+    wfm_net_piece_t* pieces = nullptr;
+    wfm_netcall_t* per = nullptr;
+    size_t n_pieces = 0, n_rec = 0;
+    pr.device(wfm_net_table(h, net, &pieces, &n_pieces, &per, &n_rec), "table");
+    wfm_net_free(net);
+    net = nullptr;
+    static_assert(sizeof(chain::Piece) == sizeof(wfm_net_piece_t), "chain_text.hpp restates wfm_net_piece_t");
+    if (n_rec != kept.size()) { wfm_net_free_list(pieces); wfm_net_free_list(per); throw std::runtime_error("[wfmash::chain-net] the table's records are not the lines added"); }
+    std::string body, text;
+    uint64_t next = 1, chains = 0, lost = 0;
+    for (size_t i = 0; i < n_rec; ++i) {  // (per is sorted by order, as kept is)
+      if (per[i].count == 0) { ++lost; continue; }
+      chain::net_body(body, kept[i], kept_off[i], per[i].score, (const chain::Piece*)pieces + per[i].first, per[i].count);
+      if (body.size() >= ((size_t)1 << 20)) { text.clear(); chains += chain::number(body, &next, text); outstream << text; body.clear(); }
+    }
+    text.clear();
+    chains += chain::number(body, &next, text);
+    outstream << text;
+    wfm_net_free_list(pieces); wfm_net_free_list(per);
+    const uint64_t all_skipped = pr.all_skipped();
+    std::cerr << "[wfmash::chain-net] " << n_rec << " lines added, " << chains << " chains written, " << n_pieces << " pieces, " << lost << " lines won nothing, "
+              << all_skipped << " lines skipped (" << skipped[1] << " without an =XID cg:Z:, " << skipped[2] << " malformed, " << skipped[3]
+              << " with an unknown target, " << skipped[4] << " with another tlen)" << std::endl;
+    if (out) { out[0] = n_rec; out[1] = chains; out[2] = n_pieces; out[3] = lost; }
+    return WFM_OK;
+  } catch (const std::exception& e) {
+    if (net) wfm_net_free(net);
+    std::cerr << e.what() << std::endl;
+    wfm_set_error(h, e.what());
+    return WFM_E_ARG;
+  }
+}
+
 // --pav-paf: the presence table of an existing aligned PAF.  Lines go to the device in batches of runs, read and skipped by
 // wfmh_coverage_paf's rules (coverage::classify_line); a line whose query the query FASTA does not have is skipped and counted too.
 int wfmh_pav_paf(wfm_handle_t* h, const char* target_fasta, const char* query_fasta_or_null, const char* aligned_paf, const char* bed_path_or_null,

@@ -83,6 +83,10 @@ std::atomic<bool> g_chain{false}, g_chain_swap{false};
 std::mutex g_chain_mu;
 std::string g_chain_out;
 std::atomic<uint64_t> g_chain_counts[4];
+std::atomic<bool> g_chain_net{false};
+std::mutex g_chain_net_mu;
+std::string g_chain_net_out;
+std::atomic<uint64_t> g_chain_net_counts[4];
 
 // --pav: the process-wide switch, the BED of target intervals or the window size, the file the align phase writes, and {records added,
 // rows written, union intervals, BED lines skipped} since it was set
@@ -916,7 +920,60 @@ int chain_records(BiwfaBatch& b, const PackedRuns& pk) {
             pk.ms + ms_between(t0, Clock::now()), pk.ms + ms_between(t0, t1), ms_between(t1, t2), ms_between(t2, Clock::now()));
   return 0;
 }
+// ---- --chain-net: the same problems into the net object of the batch's handle, ONE device call per batch (wfm_net_add), each with
+// score = its = columns (counted on the device) and order = batch << 32 | its index among the records packed: the key the ordered
+// writers sort by.  The windows are chain_records'.  A record the device refuses adds nothing, is counted and reported. ----
+int net_records(BiwfaBatch& b, const PackedRuns& pk) {
+  const auto t0 = Clock::now();
+  const size_t n = pk.probs.size();
+  std::vector<wfm_net_prob_t> probs(n);
+  std::vector<NetHead> heads(n);
+  for (size_t j = 0; j < n; ++j) {
+    const BiwfaRecord& r = b.recs[pk.rec[j]];
+    NetHead& hd = heads[j];
+    hd.order = (b.fmt.net_batch << 32) | (uint64_t)j;
+    hd.t_offset = r.target_global;
+    chain::Record& cr = hd.rec;
+    cr.qname = r.query_name; cr.tname = r.target_name; cr.rev = r.query_is_rev;
+    cr.qsize = r.query_total_length; cr.tsize = r.target_total_length;
+    cr.qs = r.query_is_rev ? r.query_offset + (r.query_length - pk.qa[j] - pk.q_len[j]) : r.query_offset + pk.qa[j];
+    cr.qe = cr.qs + pk.q_len[j];
+    cr.ts = r.target_offset + pk.ta[j];
+    cr.te = cr.ts + pk.t_len[j];
+    probs[j] = wfm_net_prob_t{pk.probs[j].base, pk.probs[j].runs_off, pk.probs[j].n_runs, WFM_NET_SCORE_EQ, hd.order};
+  }
+  int rc = WFM_OK;
+  std::vector<uint32_t> flags(n);
+  auto t1 = t0;
+  if (n) {
+    std::lock_guard<std::mutex> lk(handle_lock(b.h));
+    t1 = Clock::now();
+    rc = wfm_net_add(b.h, b.fmt.net, probs.data(), n, pk.runs.data(), pk.runs.size(), flags.data());
+    if (rc < 0 && b.stats) b.stats->error = wfm_last_error(b.h);
+  }
+  if (rc < 0) return rc;
+  if (b.fmt.net_heads)
+    for (size_t j = 0; j < n; ++j)
+      if (!flags[j]) b.fmt.net_heads->push_back(std::move(heads[j]));
+  g_chain_net_counts[0] += n - (uint64_t)rc;
+  if (rc > 0 || pk.unknown)
+    fprintf(stderr, "[wflign] chain-net: %llu records of a batch were NOT added (their runs leave the target or cannot be held)\n",
+            (unsigned long long)((uint64_t)rc + pk.unknown));
+  if (getenv("WFM_DEBUG"))
+    fprintf(stderr, "[wflign] chain-net: %zu records, %zu runs, %d flagged, %.1f ms (runs %.1f, device call %.1f)\n", n, pk.runs.size(), rc,
+            pk.ms + ms_between(t0, Clock::now()), pk.ms + ms_between(t0, t1), ms_between(t1, Clock::now()));
+  return 0;
+}
 }  // namespace
+
+std::string chain_net_path() {
+  std::lock_guard<std::mutex> lk(g_chain_net_mu);
+  return g_chain_net.load() ? g_chain_net_out : std::string();
+}
+
+void chain_net_finished(uint64_t chains, uint64_t pieces, uint64_t lost) {
+  g_chain_net_counts[1] += chains; g_chain_net_counts[2] += pieces; g_chain_net_counts[3] += lost;
+}
 
 void chain_path(std::string& out, bool& swap) {
   std::lock_guard<std::mutex> lk(g_chain_mu);
@@ -1001,13 +1058,14 @@ int do_biwfa_alignment_batch(wfm_handle_t* h, std::vector<BiwfaRecord>& recs, co
   } else {
     for_each_record(n, fmt.threads, [&](size_t ri) { swizzle(b, ri); write_record(b, ri); });
   }
-  if (fmt.coverage || fmt.pav || fmt.liftset || fmt.chain || fmt.sites) {  // one packing for the stages that are on; each makes its own device call
+  if (fmt.coverage || fmt.pav || fmt.liftset || fmt.chain || fmt.sites || fmt.net) {  // one packing for the stages that are on; each makes its own device call
     const PackedRuns pk = pack_written(b);
     if (fmt.coverage && (rc = coverage_records(b, pk)) < 0) return rc;
     if (fmt.pav && (rc = pav_records(b, pk)) < 0) return rc;
     if (fmt.sites && (rc = genotype_records(b, pk)) < 0) return rc;
     if (fmt.liftset && (rc = lift_records(b, pk)) < 0) return rc;
     if (fmt.chain && (rc = chain_records(b, pk)) < 0) return rc;
+    if (fmt.net && (rc = net_records(b, pk)) < 0) return rc;
   }
   if (dbg)
     fprintf(stderr, "[wflign] %zu records: main alignment + runs + scans %.1f ms (incl. waiting for the device), patches %.1f ms (%zu tails scanned after their heads), swizzle + records %.1f ms\n",
@@ -1088,6 +1146,22 @@ void wfmh_set_chain(const char* path_or_null, int swap) {
   }
   wflign::g_chain_swap.store(on && swap != 0);
   wflign::g_chain.store(on);
+}
+
+void wfmh_set_chain_net(const char* path_or_null) {
+  for (auto& a : wflign::g_chain_net_counts) a.store(0);
+  const bool on = path_or_null && *path_or_null;
+  {
+    std::lock_guard<std::mutex> lk(wflign::g_chain_net_mu);
+    wflign::g_chain_net_out = on ? path_or_null : "";
+  }
+  wflign::g_chain_net.store(on);
+}
+
+int wfmh_chain_net_counts(uint64_t out[4]) {
+  if (!out) return WFM_E_ARG;
+  for (int q = 0; q < 4; ++q) out[q] = wflign::g_chain_net_counts[q].load();
+  return WFM_OK;
 }
 
 int wfmh_chain_counts(uint64_t out[4]) {

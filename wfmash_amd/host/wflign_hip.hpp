@@ -27,6 +27,9 @@
 //                      (runs alone again), the record's lines into BiwfaRecord::lift
 //   chain_records      --chain only: the runs of every record WRITTEN compacted to the blocks and gaps of a UCSC chain, one
 //                      wfm_chain_runs call (runs alone again), the record's chain without its id into BiwfaRecord::chain
+//   net_records        --chain-net only: the runs of every record WRITTEN into the handle's net object, one wfm_net_add call (runs alone
+//                      again), each with score = its = columns and order = batch << 32 | its index among the batch's records packed; what
+//                      the chain's header needs stays on the host, keyed by the order
 // and CIGARs are runs (count, op) from the device to the record's text: nothing is expanded to one byte per base.
 #pragma once
 
@@ -39,6 +42,7 @@
 #include <vector>
 
 #include "../../include/wfmash_hip.h"
+#include "chain_text.hpp"
 #include "cigar_ops.hpp"  // CigarOps, the CIGAR helpers, plan_patches, PafParams and the two record writers
 
 namespace lift { struct Interval; }  // lift_text.hpp
@@ -119,6 +123,13 @@ struct ResidentSeqs {
 // A handle runs one call at a time; the mutex every caller of a handle's device entry points holds meanwhile.
 std::mutex& handle_lock(wfm_handle_t* h);
 
+// --chain-net: what a record's chain needs beside its pieces, kept on the host under the order the record went to the net object with
+struct NetHead {
+  uint64_t order = 0;
+  uint64_t t_offset = 0;  // where the target sequence begins in the concatenation
+  chain::Record rec;
+};
+
 struct OutputFormat {
   bool paf_format_else_sam = true;   // wflign.cpp:434
   bool no_seq_in_sam = false;
@@ -131,6 +142,9 @@ struct OutputFormat {
   const wfm_liftset_t* liftset = nullptr;                   // --lift: the intervals on the batch's handle (null: the stage is not run) ...
   const std::vector<lift::Interval>* lift_intervals = nullptr;  // ... and as the BED had them, in the set's order
   int chain = 0;                       // --chain: 1 = the chain of every record written, 2 = the swapped one (0: the stage is not run)
+  wfm_net_t* net = nullptr;            // --chain-net: the net object of the batch's handle (null: the stage is not run) ...
+  uint64_t net_batch = 0;              // ... the batch's number, the high half of its records' orders ...
+  std::vector<NetHead>* net_heads = nullptr;  // ... and where the heads of the records added go
 };
 
 // --variants: the file wfmh_set_variants named ("" while the switch is off); the align phase writes the batches' BiwfaRecord::vcf to it
@@ -153,6 +167,11 @@ void lift_bed_read(uint64_t skipped);
 
 // --chain: the file wfmh_set_chain named ("" while the switch is off) and whether the two sides change places
 void chain_path(std::string& out, bool& swap);
+
+// --chain-net: the file wfmh_set_chain_net named ("" while the switch is off), and what the align phase adds to the counts once it has
+// written the file: the chains written, the pieces, the records that won nothing
+std::string chain_net_path();
+void chain_net_finished(uint64_t chains, uint64_t pieces, uint64_t lost);
 
 // --pav: the BED, the window size and the file wfmh_set_pav named (out "" while the switch is off; one of bed and window is set), and what
 // the align phase adds to the counts once it has written the file: its rows, the union's intervals, the BED lines it skipped
