@@ -685,6 +685,76 @@ int  wfm_net_import(wfm_handle_t* h, wfm_net_t* net, const wfm_net_block_t* bloc
 int  wfm_net_counts(const wfm_net_t* net, uint64_t out[6]);
 void wfm_net_free_list(void* p);
 
+/* ---- transitive lifts: intervals closed over all records, in both directions ----
+ * wfm_lift_runs says where a target interval lies in the query of ONE record.  A trans object keeps the records of a whole run on the
+ * handle's device and answers, per seed interval, with everything the seed reaches through any chain of records, either way
+ * (wfmash_amd/csrc/wfa_trans.hip).
+ *
+ * WORLD.  One coordinate space of n_bases < 2^40: the caller's to lay out (the driver puts the target sequences first, in index order,
+ *   then the query sequences whose names no target has).
+ * RECORD.  {t, q, flags, runs}: t = the world position of the first pattern base the runs spell, q = the world position of the first
+ *   base of the FORWARD query window the runs spell.  WFM_TRANS_REVERSE: the text is the reverse complement of that window, text index i
+ *   is world base q + T - 1 - i (T the text span); otherwise q + i.  P and T, the pattern and text spans, come from the runs.
+ * ARCS.  Every record is TWO arcs: forward, source [t, t + P), destination the query window; back, source [q, q + T), destination the
+ *   target.  A source base is ALIGNED where an = or X column holds it.
+ * HULL.  hull(arc, [a, b)): [a, b) clipped to the arc's source span; where nothing is left or no aligned source base lies inside, the
+ *   arc gives NOTHING (wfm_lift_runs reports an empty lift there).  Otherwise the first and the last aligned source base inside
+ *   (endpoints in a gap run snap inward), the destination bases opposite them, and the half-open world interval from the smaller to the
+ *   larger of the two, inclusive.  Gap runs strictly between two lifted columns are inside it; a gap run before the first or behind the
+ *   last lifted column is not.  On the forward arc it is wfm_lift_runs' [t0, t1) moved to the world.
+ * CLOSURE.  Per seed s: R_0 = {s}; R_(k+1) = R_k united with hull(arc, J) over all arcs and over the MAXIMAL intervals J of R_k
+ *   (abutting and overlapping intervals are merged first, which makes the closure a set function of (records, seed): no order of records,
+ *   calls, objects or devices changes a byte).  depth N >= 1 gives R_N; depth 0 walks until R_(k+1) = R_k (the covered bases are
+ *   compared: R_k is inside R_(k+1)).  Seeds never merge with each other.  A maximal interval of R_k that R_(k-1) had as it is is not
+ *   projected again: its hulls are in R_k.
+ *
+ * wfm_trans_create: n_bases >= 2^40 is WFM_E_ARG with a message.  The object is used with the handle it was made on and freed before it.
+ * wfm_trans_add: probs[i] = {t, q, runs_off, n_runs, flags}, runs as wfm_coverage_add takes them, ONE call per batch.  A problem with an
+ *   empty run, without runs, or whose pattern or text span does not fit 32 bits or leaves the world adds NOTHING and is flagged
+ *   WFM_TRANS_SPANS in flags_out[i] (decided by a first kernel, before anything is written).  A run range that leaves the run buffer or a
+ *   flag bit other than WFM_TRANS_REVERSE is WFM_E_ARG with a message, and the handle stays usable.  Kept per record: its n_runs + 1
+ *   prefix words {pattern, text, = columns, X columns} (16 bytes a run, the totals behind the last; the runs themselves are not kept) and
+ *   two 32-byte arc entries, in blocks of the object's own that grow by half through the device block cache.  Memory follows the records,
+ *   never n_bases.  Where what the object keeps (the sorted copy of the arcs and its running maximum included) would exceed WFM_TRANS_GB
+ *   GiB (environment, a decimal, read per call, 32) the call fails with WFM_E_NOMEM and a message that names the pass, and nothing is
+ *   added.  Returns the number of problems flagged, or WFM_E_*.
+ * wfm_trans_closure: seeds[i] = a half-open world interval, start < end <= n_bases, n_seeds < 2^24, depth >= 0; anything else is
+ *   WFM_E_ARG with a message.  The index is made first where an add or import came since the last one: the arcs sorted by source start
+ *   (rocprim::radix_sort_pairs over the bits n_bases has) and pm = the running maximum of their source ends.  One round: one workgroup
+ *   per interval [a, b) of the list finds its arcs [lo, hi) (lo = the first with pm > a, hi = the first with start >= b) and counts those
+ *   with end > a; the counts become offsets; the host walks the intervals in chunks of at most WFM_TRANS_OUT_MB MiB of pairs
+ *   (environment, a decimal, read per call, 256; one interval at least); one lane per (interval, arc) pair resolves the hull in four
+ *   binary searches over the record's prefix words and writes seed << 40 | lo and seed << 40 | hi (an empty hull writes its interval
+ *   again, which adds nothing); the list and the chunk's pairs are united as wfm_pav_union unites segments (sort, running maximum, heads,
+ *   compaction).  ivs: the result sorted by (seed, start), disjoint and not abutting per seed; per_seed[i] = {first, count, bases} locates
+ *   seed i's.  Host memory owned by the caller (wfm_trans_free_list each; per_seed may be NULL).  The object is not changed: more may be
+ *   added and the closure taken again.
+ * wfm_trans_export / _import: the records {t, q, pre_off, n_runs, flags} and their prefix words (pre_off counts words from the first
+ *   one exported), so that the objects of several handles merge; the two arcs of a record follow from its entry.  Import looks at
+ *   everything on the host before anything is added: every record's words inside the list, the first one zero, every step one run of
+ *   =, X, I or D of length >= 1, the spans inside the world, no unknown flag; anything else is WFM_E_ARG with a message.
+ * wfm_trans_counts: out = {records kept, prefix words kept, arcs, and of the last closure: rounds run, intervals returned, pairs
+ *   projected}. */
+typedef struct wfm_trans wfm_trans_t;
+typedef struct { uint64_t t, q, runs_off; uint32_t n_runs, flags; } wfm_trans_prob_t;   /* 32 bytes */
+typedef struct { uint64_t t, q, pre_off; uint32_t n_runs, flags; } wfm_trans_rec_t;     /* 32 bytes */
+typedef struct { uint32_t p, t, eq, x; } wfm_trans_word_t;                              /* 16 bytes: the exclusive prefixes of one run */
+typedef struct { uint64_t start, end; uint32_t seed, pad_; } wfm_trans_iv_t;            /* 24 bytes */
+typedef struct { uint64_t first, count, bases; } wfm_trans_seed_t;                      /* 24 bytes */
+#define WFM_TRANS_REVERSE 1u        /* wfm_trans_prob_t::flags: the text is the reverse complement of the query window */
+#define WFM_TRANS_SPANS 2u          /* as WFM_NET_SPANS: nothing of the problem is added */
+#define WFM_TRANS_SCAN_BLOCK 1024   /* arcs one workgroup takes in the running maximum */
+int  wfm_trans_create(wfm_handle_t* h, uint64_t n_bases, wfm_trans_t** obj);
+void wfm_trans_free(wfm_trans_t* obj);
+int  wfm_trans_add(wfm_handle_t* h, wfm_trans_t* obj, const wfm_trans_prob_t* probs, size_t n, const uint32_t* runs, size_t n_runs_total,
+                   uint32_t* flags_out);
+int  wfm_trans_closure(wfm_handle_t* h, wfm_trans_t* obj, const wfm_lift_iv_t* seeds, size_t n_seeds, uint32_t depth, wfm_trans_iv_t** ivs,
+                       size_t* n_ivs, wfm_trans_seed_t* per_seed);
+int  wfm_trans_export(wfm_handle_t* h, wfm_trans_t* obj, wfm_trans_rec_t** recs, size_t* n_recs, wfm_trans_word_t** words, size_t* n_words);
+int  wfm_trans_import(wfm_handle_t* h, wfm_trans_t* obj, const wfm_trans_rec_t* recs, size_t n_recs, const wfm_trans_word_t* words, size_t n_words);
+int  wfm_trans_counts(const wfm_trans_t* obj, uint64_t out[6]);
+void wfm_trans_free_list(void* p);
+
 /* ---- every score proved optimal by a banded DP ----
  * What wfm_check_runs leaves out.  For every problem of the seqset s whose result claims a score S = res[i].score, a classical
  * minimising gap-affine-2-piece DP over cells (i = pattern index, j = text index) is run on the device, restricted to a band of

@@ -259,6 +259,31 @@ int  wfmh_chain_net_paf(wfm_handle_t* h, const char* target_fasta, const char* a
  * competed with) each followed by its pieces "P<TAB>t<TAB>q<TAB>size" as wfm_net_table gives them (t global).  Returns the file exactly as
  * the align phase writes it, ids from 1; NULL for a spec it cannot read.  malloc'd, wfmh_free. */
 char* wfmh_test_chain_net_lines(const char* spec);
+/* ---- transitive lifts: seed intervals closed over all records written, both ways (wfm_trans_*, wfmash_hip.h) ----
+ * wfmh_set_transitive(bed, out, depth): from now on every batch of wfmh_align_paf[_multi] runs ONE more device call behind the record
+ * writers: the runs of every record WRITTEN (with wfmh_set_left_align the normalised runs) go to the trans object of the batch's handle,
+ * each with its two places in the WORLD: the target's sequences in index order, then the query's sequences whose names no target has, in
+ * query index order.  No output byte of the PAF, the SAM or another side file changes.  Once all batches are aligned the objects of the
+ * handles are merged into the first (export, import), the closure of the BED's intervals is taken once on the device at `depth` (0: to
+ * the fixed point; the CLI's default is 2) and `out` is written, tab-separated: "seq start end name seed_seq seed_start seed_end", sorted
+ * by (seed in input order, world start), an interval that crosses from one sequence into the next split there, the seed's own interval
+ * among them.  The BED is read as wfmh_set_lift's, names looked up in the world.  The file does not depend on the number of devices,
+ * handles, threads or the order of the batches.  Not here: a minimum length or identity of a hop, the depth or path of an interval, the
+ * query strand of a result, gzip, more than 2^24 - 1 seeds.  bed or out NULL or "" switches it off.  Every call zeroes the counts.
+ * wfmh_transitive_counts: out = {records added, lines written, rounds run, BED lines skipped} since then.  Off by default; with the
+ * switch off nothing new is called and no file is written.
+ * wfmh_transitive_paf: the same file for an existing aligned PAF, lines read and skipped as wfmh_coverage_paf does; a line whose query
+ * neither FASTA has (or whose query window leaves its sequence) is skipped and counted, as wfmh_pav_paf does; nothing else runs.  out =
+ * the same four counts.  Returns 0 or WFM_E_*. */
+void wfmh_set_transitive(const char* bed_path_or_null, const char* out_path_or_null, uint32_t depth);
+int  wfmh_transitive_counts(uint64_t out[4]);
+int  wfmh_transitive_paf(wfm_handle_t* h, const char* target_fasta, const char* query_fasta_or_null, const char* aligned_paf, const char* bed_path,
+                         const char* out_path, uint32_t depth, uint64_t out[4]);
+/* Test hook (no GPU): the text side alone (transitive_text.hpp).  The world of the n_t target and n_q query sequences, what the parser
+ * makes of `bed` in it ("#skipped" and "#iv" lines as wfmh_test_lift_lines spells them, in input order), and per line "I<TAB>seed<TAB>a
+ * <TAB>b" of spec (a world interval of that seed) the file's lines.  NULL for a spec it cannot read.  malloc'd, wfmh_free. */
+char* wfmh_test_transitive_lines(const char* const* tnames, const uint64_t* tlengths, int n_t, const char* const* qnames, const uint64_t* qlengths,
+                                 int n_q, const char* bed, const char* spec);
 
 /* ---- presence of target intervals per group of query sequences (wfm_pav_*, wfmash_hip.h) ----
  * wfmh_set_pav(bed, window, out): from now on every batch of wfmh_align_paf[_multi] runs ONE more device call behind the record writers:

@@ -56,6 +56,8 @@ EXPORTS = [
     "wfm_sites_create", "wfm_sites_free", "wfm_sites_add_variants", "wfm_sites_add_ref", "wfm_sites_table", "wfm_sites_export", "wfm_sites_import",
     "wfm_sites_counts", "wfm_sites_free_list",
     "wfm_net_create", "wfm_net_free", "wfm_net_add", "wfm_net_table", "wfm_net_export", "wfm_net_import", "wfm_net_counts", "wfm_net_free_list",
+    "wfm_trans_create", "wfm_trans_free", "wfm_trans_add", "wfm_trans_closure", "wfm_trans_export", "wfm_trans_import", "wfm_trans_counts",
+    "wfm_trans_free_list",
     "wfm_sketch_intersections",
 ]
 ISECT_LDS_MAX = 4096  # WFM_ISECT_LDS_MAX: the longest column sketch wfm_sketch_intersections searches in LDS
@@ -95,6 +97,11 @@ WFM_E_ARG, WFM_E_INTERNAL = -3, -7
 WFM_NET_SCORE_EQ = 0xffffffff
 WFM_NET_SPANS = 2
 WFM_NET_SCAN_BLOCK = 1024
+# wfm_trans_* (include/wfmash_hip.h): a record's flag, why a problem added nothing, the arcs one workgroup takes in the running maximum
+WFM_TRANS_REVERSE = 1
+WFM_TRANS_SPANS = 2
+WFM_TRANS_SCAN_BLOCK = 1024
+WFM_E_NOMEM = -4
 # wfm_check_optimal (include/wfmash_hip.h): what a problem's score was flagged for, and the band widths at which the kernel changes form
 WFM_OPT_NOT_CHECKED, WFM_OPT_SKIPPED, WFM_OPT_CHEAPER, WFM_OPT_UNREACHED = 1, 2, 4, 8
 OPT_NAMES = ("NOT_CHECKED", "SKIPPED", "CHEAPER", "UNREACHED")
@@ -218,6 +225,11 @@ PAV_SEG_DTYPE = np.dtype([("start", "<u8"), ("length", "<u4"), ("group", "<u4")]
 NET_PROB_DTYPE = np.dtype([("base", "<u8"), ("runs_off", "<u8"), ("n_runs", "<u4"), ("score", "<u4"), ("order", "<u8")])
 NET_BLOCK_DTYPE = np.dtype([("order", "<u8"), ("t", "<u8"), ("q", "<u4"), ("size", "<u4")])   # wfm_net_block_t, and a piece
 NET_REC_DTYPE = np.dtype([("order", "<u8"), ("score", "<u4"), ("zero", "<u4")])
+TRANS_PROB_DTYPE = np.dtype([("t", "<u8"), ("q", "<u8"), ("runs_off", "<u8"), ("n_runs", "<u4"), ("flags", "<u4")])
+TRANS_REC_DTYPE = np.dtype([("t", "<u8"), ("q", "<u8"), ("pre_off", "<u8"), ("n_runs", "<u4"), ("flags", "<u4")])
+TRANS_WORD_DTYPE = np.dtype([("p", "<u4"), ("t", "<u4"), ("eq", "<u4"), ("x", "<u4")])
+TRANS_IV_DTYPE = np.dtype([("start", "<u8"), ("end", "<u8"), ("seed", "<u4"), ("pad_", "<u4")])
+TRANS_SEED_DTYPE = np.dtype([("first", "<u8"), ("count", "<u8"), ("bases", "<u8")])
 NET_CALL_DTYPE = np.dtype([("order", "<u8"), ("score", "<u4"), ("zero", "<u4"), ("first", "<u8"), ("count", "<u8"), ("bases_won", "<u8"),
                            ("bases_aligned", "<u8")])
 SITE_VAR_DTYPE = np.dtype([("pos", "<u8"), ("kind", "<u4"), ("group", "<u4"), ("ref_len", "<u4"), ("alt_len", "<u4"), ("off", "<u8")])
@@ -1071,6 +1083,107 @@ class Net:
         return tuple(int(v) for v in out)[:5]
 
 
+class Transitive:
+    """wfm_trans_t: the records of a run as arcs of one coordinate space, on the handle's device; .closure(seeds, depth) gives per seed
+    interval everything it reaches through any chain of records, either way (include/wfmash_hip.h).  Close it before its handle."""
+
+    def __init__(self, handle, n_bases):
+        self._h, self._L = handle, handle._L
+        self.n_bases = int(n_bases)
+        self._p = None
+        L = self._L
+        P = C.POINTER
+        L.wfm_trans_create.restype = C.c_int
+        L.wfm_trans_create.argtypes = [C.c_void_p, C.c_uint64, P(C.c_void_p)]
+        L.wfm_trans_free.restype = None
+        L.wfm_trans_free.argtypes = [C.c_void_p]
+        L.wfm_trans_add.restype = C.c_int
+        L.wfm_trans_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.wfm_trans_closure.restype = C.c_int
+        L.wfm_trans_closure.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, P(C.c_void_p), P(C.c_size_t), C.c_void_p]
+        L.wfm_trans_export.restype = C.c_int
+        L.wfm_trans_export.argtypes = [C.c_void_p, C.c_void_p, P(C.c_void_p), P(C.c_size_t), P(C.c_void_p), P(C.c_size_t)]
+        L.wfm_trans_import.restype = C.c_int
+        L.wfm_trans_import.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
+        L.wfm_trans_counts.restype = C.c_int
+        L.wfm_trans_counts.argtypes = [C.c_void_p, P(C.c_uint64)]
+        L.wfm_trans_free_list.restype = None
+        L.wfm_trans_free_list.argtypes = [C.c_void_p]
+        p = C.c_void_p()
+        rc = L.wfm_trans_create(handle._p, self.n_bases, C.byref(p))
+        if rc != 0:
+            raise WfmError(f"wfm_trans_create failed ({rc}): {handle.last_error()}")
+        self._p = p
+
+    def close(self):
+        if self._p:
+            self._L.wfm_trans_free(self._p)
+            self._p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, problems, runs):
+        """wfm_trans_add.  problems: a list of (t, q, runs_off, n_runs, flags), flags WFM_TRANS_REVERSE or 0; runs: the run words
+        ((length << 2) | op).  Returns the problems' flags as a numpy array (WFM_TRANS_SPANS: nothing of the problem was added)."""
+        probs, probs_p = _run_problems(problems, TRANS_PROB_DTYPE)
+        runs = np.ascontiguousarray(runs, dtype=np.uint32)
+        flags = np.zeros(max(len(problems), 1), dtype=np.uint32)
+        rc = self._L.wfm_trans_add(self._h._p, self._p, probs_p, len(probs), runs.ctypes.data if len(runs) else None, len(runs), flags.ctypes.data)
+        if rc < 0:
+            raise WfmError(f"wfm_trans_add failed ({rc}): {self._h.last_error()}")
+        assert rc == int(np.count_nonzero(flags[:len(problems)] & WFM_TRANS_SPANS))
+        return flags[:len(problems)]
+
+    def _take(self, ptr, nbytes):
+        try:
+            return C.string_at(ptr, nbytes) if nbytes else b""
+        finally:
+            self._L.wfm_trans_free_list(ptr)
+
+    def closure(self, seeds, depth=2):
+        """wfm_trans_closure: seeds = [(start, end)] in world coordinates; depth 0 walks to the fixed point.  Returns (the intervals {start,
+        end, seed} sorted by (seed, start), per seed {first, count, bases}), two numpy arrays."""
+        iv = np.zeros(len(seeds), dtype=LIFT_IV_DTYPE)
+        for i, (a, b) in enumerate(seeds):
+            iv[i] = (a, b)
+        per = np.zeros(max(len(seeds), 1), dtype=TRANS_SEED_DTYPE)
+        pp, n = C.c_void_p(), C.c_size_t(0)
+        rc = self._L.wfm_trans_closure(self._h._p, self._p, iv.ctypes.data if len(iv) else None, len(iv), int(depth), C.byref(pp), C.byref(n),
+                                       per.ctypes.data)
+        if rc != 0:
+            raise WfmError(f"wfm_trans_closure failed ({rc}): {self._h.last_error()}")
+        return np.frombuffer(self._take(pp, n.value * TRANS_IV_DTYPE.itemsize), dtype=TRANS_IV_DTYPE), per[:len(seeds)]
+
+    def export(self):
+        """wfm_trans_export: (the records as an array of wfm_trans_rec_t, their prefix words as an array of wfm_trans_word_t)."""
+        rp, wp, n, nw = C.c_void_p(), C.c_void_p(), C.c_size_t(0), C.c_size_t(0)
+        rc = self._L.wfm_trans_export(self._h._p, self._p, C.byref(rp), C.byref(n), C.byref(wp), C.byref(nw))
+        if rc != 0:
+            raise WfmError(f"wfm_trans_export failed ({rc}): {self._h.last_error()}")
+        return (np.frombuffer(self._take(rp, n.value * TRANS_REC_DTYPE.itemsize), dtype=TRANS_REC_DTYPE),
+                np.frombuffer(self._take(wp, nw.value * TRANS_WORD_DTYPE.itemsize), dtype=TRANS_WORD_DTYPE))
+
+    def import_(self, recs, words):
+        """wfm_trans_import: what export returned (of another object, of another device), appended."""
+        r = np.ascontiguousarray(recs, dtype=TRANS_REC_DTYPE)
+        w = np.ascontiguousarray(words, dtype=TRANS_WORD_DTYPE)
+        rc = self._L.wfm_trans_import(self._h._p, self._p, r.ctypes.data if len(r) else None, len(r), w.ctypes.data if len(w) else None, len(w))
+        if rc != 0:
+            raise WfmError(f"wfm_trans_import failed ({rc}): {self._h.last_error()}")
+
+    def counts(self):
+        """wfm_trans_counts: (records, prefix words, arcs, and of the last closure: rounds run, intervals returned, pairs projected)."""
+        out = (C.c_uint64 * 6)()
+        rc = self._L.wfm_trans_counts(self._p, out)
+        if rc != 0:
+            raise WfmError(f"wfm_trans_counts failed ({rc})")
+        return tuple(int(v) for v in out)
+
+
 class Handle:
     """One handle per GPU (wfm_create)."""
 
@@ -1394,6 +1507,10 @@ class Handle:
     def net(self, n_bases):
         """A Net on this handle's device over n_bases target bases (wfm_net_create)."""
         return Net(self, n_bases)
+
+    def transitive(self, n_bases):
+        """A Transitive on this handle's device over a world of n_bases bases (wfm_trans_create)."""
+        return Transitive(self, n_bases)
 
     def coverage(self, n_bases):
         """wfm_coverage_create: a depth object over n_bases target bases on this handle's device."""
@@ -1762,6 +1879,7 @@ HOST_EXPORTS = ["wfmh_test_packed_lce", "wfmh_test_is_acgt", "wfmh_align_default
                 "wfmh_set_lift", "wfmh_lift_counts", "wfmh_lift_paf", "wfmh_test_lift_lines",
                 "wfmh_set_chain", "wfmh_chain_counts", "wfmh_chain_paf", "wfmh_test_chain_lines",
                 "wfmh_set_chain_net", "wfmh_chain_net_counts", "wfmh_chain_net_paf", "wfmh_test_chain_net_lines",
+                "wfmh_set_transitive", "wfmh_transitive_counts", "wfmh_transitive_paf", "wfmh_test_transitive_lines",
                 "wfmh_set_pav", "wfmh_pav_counts", "wfmh_pav_paf", "wfmh_test_pav_text",
                 "wfmh_set_genotypes", "wfmh_genotypes_counts", "wfmh_test_genotype_text",
                 "wfmh_ani_matrix", "wfmh_ani_matrix_rows", "wfmh_free_ani_rows", "wfmh_set_ani_matrix", "wfmh_test_ani_tsv"]
@@ -2343,6 +2461,63 @@ def chain_net_counts():
     if rc != 0:
         raise WfmError(f"wfmh_chain_net_counts failed ({rc})")
     return tuple(int(v) for v in out)
+
+
+def set_transitive(bed_path, out_path, depth=2) -> None:
+    """wfmh_set_transitive (include/wfmash_host.h): from now on every align_paf[_multi] adds the records it writes to a trans object per
+    handle and, once all batches are aligned, writes the closure of the BED's intervals to out_path.  None for either switches it off."""
+    L = _host()
+    L.wfmh_set_transitive.restype = None
+    L.wfmh_set_transitive.argtypes = [C.c_char_p, C.c_char_p, C.c_uint32]
+    L.wfmh_set_transitive(os.fsencode(bed_path) if bed_path else None, os.fsencode(out_path) if out_path else None, int(depth))
+
+
+def transitive_counts():
+    """wfmh_transitive_counts: (records added, lines written, rounds run, BED lines skipped) since set_transitive."""
+    L = _host()
+    L.wfmh_transitive_counts.restype = C.c_int
+    L.wfmh_transitive_counts.argtypes = [C.POINTER(C.c_uint64)]
+    out = (C.c_uint64 * 4)()
+    rc = L.wfmh_transitive_counts(out)
+    if rc != 0:
+        raise WfmError(f"wfmh_transitive_counts failed ({rc})")
+    return tuple(int(v) for v in out)
+
+
+def transitive_paf(handle, target_fasta, aligned_paf, bed_path, out_path, depth=2, query_fasta=None):
+    """wfmh_transitive_paf: the --transitive file of an existing aligned PAF.  Returns (lines added, lines written, rounds run, BED lines
+    skipped)."""
+    L = _host()
+    L.wfmh_transitive_paf.restype = C.c_int
+    L.wfmh_transitive_paf.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.POINTER(C.c_uint64)]
+    out = (C.c_uint64 * 4)()
+    rc = L.wfmh_transitive_paf(handle._p, os.fsencode(target_fasta), os.fsencode(query_fasta) if query_fasta else None, os.fsencode(aligned_paf),
+                               os.fsencode(bed_path), os.fsencode(out_path), int(depth), out)
+    if rc != 0:
+        raise WfmError(f"wfmh_transitive_paf failed ({rc}): {handle.last_error()}")
+    return tuple(int(v) for v in out)
+
+
+def host_transitive_lines(tnames, tlengths, qnames, qlengths, bed_text, spec) -> str:
+    """wfmh_test_transitive_lines (no GPU): what the BED parser keeps in the world of the two name lists, and the file's lines of the world
+    intervals in `spec` (include/wfmash_host.h)."""
+    L = _host()
+    f = L.wfmh_test_transitive_lines
+    f.restype = C.c_void_p
+    f.argtypes = [C.POINTER(C.c_char_p), C.POINTER(C.c_uint64), C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_uint64), C.c_int, C.c_char_p, C.c_char_p]
+    tn = (C.c_char_p * max(len(tnames), 1))(*[n.encode() for n in tnames])
+    tl = (C.c_uint64 * max(len(tlengths), 1))(*tlengths)
+    qn = (C.c_char_p * max(len(qnames), 1))(*[n.encode() for n in qnames])
+    ql = (C.c_uint64 * max(len(qlengths), 1))(*qlengths)
+    p = f(tn, tl, len(tnames), qn, ql, len(qnames), bed_text.encode(), spec.encode())
+    if not p:
+        raise WfmError("wfmh_test_transitive_lines cannot read the spec")
+    try:
+        return C.string_at(p).decode()
+    finally:
+        L.wfmh_free.restype = None
+        L.wfmh_free.argtypes = [C.c_void_p]
+        L.wfmh_free(p)
 
 
 def host_chain_net_lines(spec):

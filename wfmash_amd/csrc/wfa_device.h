@@ -518,6 +518,39 @@ void launch_net_piece_keys(const NetWork& w, hipStream_t st);
 // the pieces at the sorted places [a, b), 24 bytes each
 void launch_net_pieces(const NetWork& w, unsigned long long a, unsigned long long b, NetBlock* out, hipStream_t st);
 void launch_net_per(const NetWork& w, NetPer* per, hipStream_t st);
+// wfm_trans_* (wfa_trans.hip).  A problem is wfm_trans_prob_t as the caller wrote it; what trans_span_kernel leaves per problem: its flags
+// and its two spans.  An arc is one direction of a record: its source [s, s + slen) and the start d of its destination in the world, where
+// its record's n_runs + 1 prefix words begin in the object's block (the low 62 bits of pre), whether its source is the query window
+// (TRANS_ARC_BACK) and whether the record's text is the reverse complement of that window (TRANS_ARC_REVERSE).
+struct TransProb {
+  uint64_t t, q, runs_off;
+  uint32_t n_runs, flags;
+};
+struct TransSpan {
+  uint32_t flags, pspan, tspan, pad_;
+};
+struct TransArc {
+  uint64_t s, d, pre;
+  uint32_t slen, n_runs;
+};
+constexpr uint64_t TRANS_ARC_BACK = (uint64_t)1 << 62, TRANS_ARC_REVERSE = (uint64_t)1 << 63, TRANS_ARC_PRE = TRANS_ARC_BACK - 1;
+void launch_trans_span(const uint32_t* runs, const TransProb* probs, int nprob, unsigned long long n_bases, TransSpan* out, hipStream_t st);
+// pre_off: nprob, where each problem's words begin in pre, ~0 for a problem that is not kept
+void launch_trans_pre(const uint32_t* runs, const TransProb* probs, int nprob, const unsigned long long* pre_off, void* pre, hipStream_t st);
+// key[i] = arc i's source start, idx[i] = i: what pav_sort takes
+void launch_trans_keys(const TransArc* arcs, unsigned long long n, unsigned long long* key, unsigned long long* idx, hipStream_t st);
+// sorted[i] = arcs[idx[i]]; pm[i] = the largest source end of sorted[0 .. i]; maxs: n / WFM_TRANS_SCAN_BLOCK rounded up
+void launch_trans_index(const TransArc* arcs, const unsigned long long* idx, unsigned long long n, TransArc* sorted, unsigned long long* maxs,
+                        unsigned long long* pm, hipStream_t st);
+// (ks, ke): the m intervals of the list, keys seed << 40 | position; (pks, pke): the m_prev of the list before; arcs sorted, pm theirs.
+// win: m windows {lo, hi}, 16 bytes each; cnt: m; off: m + 1, the counts' exclusive prefixes
+void launch_trans_count(const unsigned long long* ks, const unsigned long long* ke, unsigned long long m, const unsigned long long* pks,
+                        const unsigned long long* pke, unsigned long long m_prev, const TransArc* arcs, const unsigned long long* pm,
+                        unsigned long long n_arcs, void* win, unsigned long long* cnt, unsigned long long* off, hipStream_t st);
+// the pairs of the intervals [ka, kb) as keys; oks[0] / oke[0] is pair number off[ka] of the round
+void launch_trans_write(const unsigned long long* ks, const unsigned long long* ke, const void* win, const unsigned long long* off,
+                        unsigned long long ka, unsigned long long kb, const TransArc* arcs, const void* pre, unsigned long long* oks,
+                        unsigned long long* oke, hipStream_t st);
 // wfm_check_optimal (wfa_optcheck.hip): a problem's forward byte copies, its ends-free allowances (clamped; 0 for the other modes),
 // its band of diagonals (wfa_optband.h) and, for the memory form, where its three row arrays begin in `rows` (32-bit elements)
 struct OptProb {

@@ -2,7 +2,7 @@
 // produces something from them -- the check against the bases, left-aligned gaps, cs strings, variants, target depth, lifted
 // intervals, the blocks of a chain, presence per group, the sites and genotypes of many records, the net across records, the proof of optimality.
 // The kernels are in wfa_check.hip, wfa_leftalign.hip, wfa_cs.hip, wfa_variants.hip, wfa_coverage.hip, wfa_lift.hip, wfa_chain.hip,
-// wfa_pav.hip, wfa_sites.hip, wfa_net.hip and wfa_optcheck.hip.
+// wfa_pav.hip, wfa_sites.hip, wfa_net.hip, wfa_trans.hip and wfa_optcheck.hip.
 //
 // Every pass has the same frame, written once below: it validates the run ranges before anything is launched, carves what the
 // call has on the device out of one block, launches, writes its output in chunks that fit a cap, and waits for the stream before
@@ -1774,6 +1774,386 @@ int wfm_net_counts(const wfm_net_t* net, uint64_t out[6]) {
 }
 
 void wfm_net_free_list(void* p) { free(p); }
+
+// ---- transitive lifts: intervals closed over all records, both ways (wfmash_hip.h; the kernels: wfa_trans.hip, the union: wfa_pav.hip) ----
+struct wfm_trans {
+  int device = 0;
+  uint64_t n_bases = 0;
+  uint4* pre = nullptr;                 // the records' prefix words, n_runs + 1 each
+  size_t pcap = 0, np = 0;
+  TransArc* arcs = nullptr;             // two per record, as they came
+  size_t acap = 0, na = 0;
+  std::vector<wfm_trans_rec_t> recs;    // the records once more, on the host: what export gives (pre_off: in pre)
+  bool indexed = false;
+  DevBuf<uint64_t> index;               // the arcs sorted by source start (4 words each), then pm and the blocks' maxima
+  DevBuf<unsigned long long> acc, snap, prev;  // a closure's list as it grows, the list a round projects, the list of the round before (ks, then ke)
+  DevBuf<uint64_t> tmp;                 // the sorts' own
+  uint64_t last_rounds = 0, last_ivs = 0, last_pairs = 0;
+  const TransArc* sorted() const { return (const TransArc*)index.p; }
+  const unsigned long long* pm() const { return (const unsigned long long*)(index.p + 4 * na); }
+};
+
+extern "C++" {
+namespace {
+static_assert(sizeof(wfm_trans_prob_t) == 32 && sizeof(wfm_trans_rec_t) == 32 && sizeof(wfm_trans_word_t) == 16 && sizeof(wfm_trans_iv_t) == 24 &&
+              sizeof(wfm_trans_seed_t) == 24, "wfmash_hip.h states these sizes");
+constexpr unsigned TRANS_SHIFT = 40;
+constexpr size_t TRANS_MAX = ((size_t)1 << 31) - 1;  // intervals of a list (one workgroup each), and arcs
+
+int trans_usable(wfm_handle_t* h, const wfm_trans_t* obj) { return DeviceGuard::usable(h, obj->device, "the trans object"); }
+
+// room for add_words more prefix words and add_recs more records, under WFM_TRANS_GB; nothing is changed where it fails
+int trans_reserve(wfm_handle_t* h, wfm_trans_t* obj, const char* who, size_t add_words, size_t add_recs) {
+  if (add_recs > (TRANS_MAX - obj->na) / 2) { h->err = std::string(who) + ": more than 2^31 - 1 arcs in one object; nothing was added"; return WFM_E_ARG; }
+  // (an arc is kept twice, as it came and sorted, with 8 bytes of running maximum)
+  const double gib = env_decimal("WFM_TRANS_GB", 32.0);
+  const double need = ((double)(obj->np + add_words) * 16.0 + (double)(obj->na + 2 * add_recs) * 72.0) / 1073741824.0;
+  if (need > gib) {
+    char msg[240];
+    snprintf(msg, sizeof msg, "%s: the transitive pass would keep %.3f GiB of prefix words and arcs on the device, more than WFM_TRANS_GB = %.3f; nothing was added",
+             who, need, gib);
+    h->err = msg;
+    return WFM_E_NOMEM;
+  }
+  if (int rc = sites_reserve(h, &obj->pre, &obj->pcap, obj->np, obj->np + add_words, "transitive prefix words")) return rc;
+  return sites_reserve(h, &obj->arcs, &obj->acap, obj->na, obj->na + 2 * add_recs, "transitive arcs");
+}
+
+// the two arcs of a record whose words begin at `at` of the object's block
+void trans_arcs_of(const wfm_trans_rec_t& r, uint64_t at, uint32_t pspan, uint32_t tspan, TransArc out[2]) {
+  const uint64_t rev = (r.flags & WFM_TRANS_REVERSE) ? TRANS_ARC_REVERSE : 0;
+  out[0] = TransArc{r.t, r.q, at | rev, pspan, r.n_runs};
+  out[1] = TransArc{r.q, r.t, at | rev | TRANS_ARC_BACK, tspan, r.n_runs};
+}
+
+// the arcs sorted by source start and pm, where something was added since they were made
+int trans_index(wfm_handle_t* h, wfm_trans_t* obj) {
+  if (obj->indexed) return WFM_OK;
+  const size_t n = obj->na, nb = (n + WFM_TRANS_SCAN_BLOCK - 1) / WFM_TRANS_SCAN_BLOCK;
+  if (n) {
+    unsigned long long *key, *idx, *key2, *idx2;
+    Carver cv{h->scratch, "transitive index"};
+    cv.piece(&key, n); cv.piece(&idx, n); cv.piece(&key2, n); cv.piece(&idx2, n);
+    if (int rc = cv.commit(h)) return rc;
+    if (obj->index.ensure(5 * n + nb + 2)) { h->err = "out of device memory (transitive index)"; return WFM_E_NOMEM; }
+    launch_trans_keys(obj->arcs, n, key, idx, h->stream);
+    HIPCHK(h, hipGetLastError());
+    const unsigned end_bit = std::max(1u, bits_of(obj->n_bases));  // (a source start is at most n_bases)
+    size_t tmp_bytes = 0;
+    HIPCHK(h, pav_sort(nullptr, &tmp_bytes, key, key2, idx, idx2, n, end_bit, h->stream));
+    if (obj->tmp.ensure(tmp_bytes / 8 + 2)) { h->err = "out of device memory (transitive sort)"; return WFM_E_NOMEM; }
+    HIPCHK(h, pav_sort(obj->tmp.p, &tmp_bytes, key, key2, idx, idx2, n, end_bit, h->stream));
+    unsigned long long* pm = (unsigned long long*)(obj->index.p + 4 * n);
+    launch_trans_index(obj->arcs, idx2, n, (TransArc*)obj->index.p, pm + n, pm, h->stream);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+  }
+  obj->indexed = true;
+  return WFM_OK;
+}
+
+// acc = the union of acc's m intervals and the c pairs that launch(raw ks tail, raw ke tail) writes; *m = its intervals
+template <class Launch>
+int trans_union(wfm_handle_t* h, wfm_trans_t* obj, size_t* m, size_t c, unsigned end_bit, Launch launch) {
+  const size_t n = *m + c, nb = (n + WFM_PAV_SCAN_BLOCK - 1) / WFM_PAV_SCAN_BLOCK;
+  if (n > TRANS_MAX) { h->err = "wfm_trans_closure: more than 2^31 - 1 intervals in one round; lower WFM_TRANS_OUT_MB or take fewer seeds a call"; return WFM_E_ARG; }
+  unsigned long long *rks, *rke, *sks, *ske, *aux;
+  Carver cv{h->outblk, "transitive union"};
+  cv.piece(&rks, n); cv.piece(&rke, n); cv.piece(&sks, n); cv.piece(&ske, n); cv.piece(&aux, nb + 1);
+  if (int rc = cv.commit(h)) return rc;
+  HIPCHK(h, hipMemcpyAsync(rks, obj->acc.p, *m * 8, hipMemcpyDeviceToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(rke, obj->acc.p + *m, *m * 8, hipMemcpyDeviceToDevice, h->stream));
+  launch(rks + *m, rke + *m);
+  HIPCHK(h, hipGetLastError());
+  size_t tmp_bytes = 0;
+  HIPCHK(h, pav_sort(nullptr, &tmp_bytes, rks, sks, rke, ske, n, end_bit, h->stream));
+  if (obj->tmp.ensure(tmp_bytes / 8 + 2)) { h->err = "out of device memory (transitive sort)"; return WFM_E_NOMEM; }
+  HIPCHK(h, pav_sort(obj->tmp.p, &tmp_bytes, rks, sks, rke, ske, n, end_bit, h->stream));
+  launch_pav_runmax(ske, n, aux, h->stream);
+  HIPCHK(h, hipGetLastError());
+  // (acc's intervals are in the raw copy: the block may be replaced.  A union has no more intervals than the list has segments)
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (obj->acc.ensure(2 * n)) { h->err = "out of device memory (transitive list)"; return WFM_E_NOMEM; }
+  // (the end keys follow the start keys at the union's own length, which is known only now: compact to the raw copy, then move)
+  launch_pav_compact(sks, ske, n, aux, rks, rke, h->stream);
+  HIPCHK(h, hipGetLastError());
+  unsigned long long u = 0;
+  HIPCHK(h, hipMemcpyAsync(&u, aux + nb, 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (u == 0 || u > n) { h->err = "wfm_trans_closure: the union does not add up"; return WFM_E_INTERNAL; }
+  HIPCHK(h, hipMemcpyAsync(obj->acc.p, rks, (size_t)u * 8, hipMemcpyDeviceToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(obj->acc.p + u, rke, (size_t)u * 8, hipMemcpyDeviceToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  *m = (size_t)u;
+  return WFM_OK;
+}
+
+// the bases the m intervals of acc cover
+int trans_bases(wfm_handle_t* h, wfm_trans_t* obj, size_t m, unsigned long long* bases) {
+  const size_t nb = (m + WFM_PAV_SCAN_BLOCK - 1) / WFM_PAV_SCAN_BLOCK;
+  unsigned long long *C, *aux;
+  Carver cv{h->outblk, "transitive prefix"};
+  cv.piece(&C, m + 1); cv.piece(&aux, nb + 1);
+  if (int rc = cv.commit(h)) return rc;
+  launch_pav_prefix(obj->acc.p, obj->acc.p + m, m, aux, C, h->stream);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipMemcpyAsync(bases, C + m, 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return WFM_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int wfm_trans_create(wfm_handle_t* h, uint64_t n_bases, wfm_trans_t** obj) {
+  if (!h || !obj) return WFM_E_ARG;
+  *obj = nullptr;
+  if (n_bases >= ((uint64_t)1 << TRANS_SHIFT)) {
+    h->err = "wfm_trans_create: a world of " + std::to_string(n_bases) + " bases: fewer than 2^40, as wfm_pav_create";
+    return WFM_E_ARG;
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  std::unique_ptr<wfm_trans> p(new wfm_trans());
+  p->device = h->device;
+  p->n_bases = n_bases;
+  *obj = p.release();
+  return WFM_OK;
+}
+
+void wfm_trans_free(wfm_trans_t* obj) {
+  if (!obj) return;
+  DeviceGuard on(obj->device);
+  obj->index.release(); obj->acc.release(); obj->snap.release(); obj->prev.release(); obj->tmp.release();
+  if (obj->pre) wfm_dfree(obj->pre);
+  if (obj->arcs) wfm_dfree(obj->arcs);
+  delete obj;
+}
+
+int wfm_trans_add(wfm_handle_t* h, wfm_trans_t* obj, const wfm_trans_prob_t* probs, size_t n, const uint32_t* runs, size_t n_runs_total, uint32_t* flags_out) {
+  if (!h || !obj || (n && (!probs || !flags_out)) || (n_runs_total && !runs)) return WFM_E_ARG;
+  if (n == 0) return WFM_OK;
+  if (n > (size_t)INT32_MAX || n_runs_total > ((size_t)1 << 31)) { h->err = "wfm_trans_add: too many problems or runs for one call"; return WFM_E_ARG; }
+  if (int rc = trans_usable(h, obj)) return rc;
+  if (int rc = all_runs_inside(h, probs, n, n_runs_total)) return rc;
+  for (size_t i = 0; i < n; ++i)
+    if (probs[i].flags & ~WFM_TRANS_REVERSE) {
+      h->err = "problem " + std::to_string(i) + ": flags " + std::to_string(probs[i].flags) + " hold a bit that is not WFM_TRANS_REVERSE";
+      return WFM_E_ARG;
+    }
+  HIPCHK(h, hipSetDevice(h->device));
+  PassTimer tm(h);
+  TransProb* d_probs;
+  TransSpan* d_span;
+  unsigned long long* d_at;
+  uint32_t* d_runs;
+  Carver cv{h->scratch, "transitive add"};
+  cv.piece(&d_probs, n); cv.piece(&d_span, n); cv.piece(&d_at, n); cv.piece(&d_runs, n_runs_total);
+  if (int rc = cv.commit(h)) return rc;
+  HIPCHK(h, hipMemcpyAsync(d_probs, probs, n * sizeof(TransProb), hipMemcpyHostToDevice, h->stream));
+  if (n_runs_total) HIPCHK(h, hipMemcpyAsync(d_runs, runs, n_runs_total * 4, hipMemcpyHostToDevice, h->stream));
+  launch_trans_span(d_runs, d_probs, (int)n, obj->n_bases, d_span, h->stream);
+  HIPCHK(h, hipGetLastError());
+  std::vector<TransSpan> span(n);
+  HIPCHK(h, hipMemcpyAsync(span.data(), d_span, n * sizeof(TransSpan), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  // what is kept, and where: nothing is written before this is settled
+  std::vector<unsigned long long> at(n, ~0ull);
+  std::vector<TransArc> arcs;
+  std::vector<wfm_trans_rec_t> recs;
+  size_t words = 0;
+  int spans = 0;
+  for (size_t i = 0; i < n; ++i) {
+    flags_out[i] = span[i].flags;
+    if (span[i].flags & WFM_TRANS_SPANS) { ++spans; continue; }
+    at[i] = obj->np + words;
+    recs.push_back(wfm_trans_rec_t{probs[i].t, probs[i].q, at[i], probs[i].n_runs, probs[i].flags});
+    TransArc two[2];
+    trans_arcs_of(recs.back(), at[i], span[i].pspan, span[i].tspan, two);
+    arcs.push_back(two[0]); arcs.push_back(two[1]);
+    words += (size_t)probs[i].n_runs + 1;
+  }
+  if (!recs.empty()) {
+    if (int rc = trans_reserve(h, obj, "wfm_trans_add", words, recs.size())) return rc;
+    HIPCHK(h, hipMemcpyAsync(d_at, at.data(), n * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(obj->arcs + obj->na, arcs.data(), arcs.size() * sizeof(TransArc), hipMemcpyHostToDevice, h->stream));
+    launch_trans_pre(d_runs, d_probs, (int)n, d_at, obj->pre, h->stream);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    obj->np += words;
+    obj->na += arcs.size();
+    obj->recs.insert(obj->recs.end(), recs.begin(), recs.end());
+    obj->indexed = false;
+  }
+  if (tm.on)
+    fprintf(stderr, "[wfm] transitive add: %zu problems, %zu runs, %d flagged, %.3f ms (host clock, ends in a synchronise); the object holds %zu words of %zu records\n",
+            n, n_runs_total, spans, tm.host_ms(), obj->np, obj->recs.size());
+  return spans;
+}
+
+int wfm_trans_closure(wfm_handle_t* h, wfm_trans_t* obj, const wfm_lift_iv_t* seeds, size_t n_seeds, uint32_t depth, wfm_trans_iv_t** ivs, size_t* n_ivs,
+                      wfm_trans_seed_t* per_seed) {
+  if (!h || !obj || !ivs || !n_ivs || (n_seeds && !seeds)) return WFM_E_ARG;
+  *ivs = nullptr; *n_ivs = 0;
+  if (int rc = trans_usable(h, obj)) return rc;
+  if (n_seeds >= ((size_t)1 << 24)) { h->err = "wfm_trans_closure: " + std::to_string(n_seeds) + " seeds in one call: fewer than 2^24 (a key is seed << 40 | position)"; return WFM_E_ARG; }
+  for (size_t i = 0; i < n_seeds; ++i)
+    if (!(seeds[i].start < seeds[i].end && seeds[i].end <= obj->n_bases)) {
+      h->err = "wfm_trans_closure: seed " + std::to_string(i) + " is empty or ends beyond the " + std::to_string(obj->n_bases) + " bases of the world";
+      return WFM_E_ARG;
+    }
+  obj->last_rounds = obj->last_ivs = obj->last_pairs = 0;
+  if (n_seeds == 0) return WFM_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  PassTimer tm(h);
+  if (int rc = trans_index(h, obj)) return rc;
+  const double ms_index = tm.lap();
+  // R_0: one interval per seed, in key order as they are
+  size_t m = n_seeds, m_snap = 0, m_prev = 0;
+  {
+    std::vector<unsigned long long> keys(2 * m);
+    for (size_t i = 0; i < m; ++i) { keys[i] = ((uint64_t)i << TRANS_SHIFT) | seeds[i].start; keys[m + i] = ((uint64_t)i << TRANS_SHIFT) | seeds[i].end; }
+    if (obj->acc.ensure(2 * m)) { h->err = "out of device memory (transitive list)"; return WFM_E_NOMEM; }
+    HIPCHK(h, hipMemcpyAsync(obj->acc.p, keys.data(), 2 * m * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+  }
+  const unsigned end_bit = std::min(64u, TRANS_SHIFT + std::max(1u, bits_of(n_seeds)));
+  const unsigned long long cap = cap_units("WFM_TRANS_OUT_MB", 16, 1);
+  unsigned long long bases = 0, pairs = 0;
+  if (int rc = trans_bases(h, obj, m, &bases)) return rc;
+  uint64_t rounds = 0;
+  size_t chunks = 0;
+  std::vector<unsigned long long> off;
+  while (obj->na && (depth == 0 || rounds < depth)) {
+    // the list this round projects, and the one of the round before
+    std::swap(obj->prev, obj->snap);
+    m_prev = m_snap;
+    if (obj->snap.ensure(2 * m)) { h->err = "out of device memory (transitive list)"; return WFM_E_NOMEM; }
+    HIPCHK(h, hipMemcpyAsync(obj->snap.p, obj->acc.p, 2 * m * 8, hipMemcpyDeviceToDevice, h->stream));
+    m_snap = m;
+    const unsigned long long *ks = obj->snap.p, *ke = obj->snap.p + m_snap;
+    ulonglong2* d_win;
+    unsigned long long *d_cnt, *d_off;
+    Carver cv{h->scratch, "transitive round"};
+    cv.piece(&d_win, m_snap); cv.piece(&d_cnt, m_snap); cv.piece(&d_off, m_snap + 1);
+    if (int rc = cv.commit(h)) return rc;
+    launch_trans_count(ks, ke, m_snap, obj->prev.p, obj->prev.p + m_prev, m_prev, obj->sorted(), obj->pm(), obj->na, d_win, d_cnt, d_off, h->stream);
+    HIPCHK(h, hipGetLastError());
+    off.resize(m_snap + 1);
+    HIPCHK(h, hipMemcpyAsync(off.data(), d_off, (m_snap + 1) * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    ++rounds;
+    pairs += off[m_snap];
+    // chunks of whole intervals that hold at most WFM_TRANS_OUT_MB MiB of pairs; a single interval may exceed that alone
+    for (size_t ka = 0, kb; ka < m_snap; ka = kb) {
+      kb = chunk_end(ka, off, cap);
+      const size_t c = (size_t)(off[kb] - off[ka]);
+      if (c == 0) continue;
+      const int rc = trans_union(h, obj, &m, c, end_bit, [&](unsigned long long* oks, unsigned long long* oke) {
+        launch_trans_write(ks, ke, d_win, d_off, ka, kb, obj->sorted(), obj->pre, oks, oke, h->stream);
+      });
+      if (rc != WFM_OK) return rc;
+      ++chunks;
+    }
+    unsigned long long now = 0;
+    if (int rc = trans_bases(h, obj, m, &now)) return rc;
+    const bool fixed = now == bases;  // (R_k is inside R_k+1: the same bases, the same set)
+    bases = now;
+    if (fixed) break;
+  }
+  // the list, sorted by (seed, start) as the keys are
+  std::vector<unsigned long long> keys(2 * m);
+  const bool pinned = cs_pin_pieces(h);
+  hipError_t e = cs_copy_down(h, pinned, (char*)keys.data(), (const uint8_t*)obj->acc.p, 2 * m * 8);
+  if (e != hipSuccess) { h->err = std::string("wfm_trans_closure: ") + hipGetErrorString(e); return WFM_E_HIP; }
+  wfm_trans_iv_t* out = (wfm_trans_iv_t*)malloc(m * sizeof(wfm_trans_iv_t));
+  if (!out) { h->err = "out of host memory (transitive intervals)"; return WFM_E_NOMEM; }
+  const uint64_t mask = ((uint64_t)1 << TRANS_SHIFT) - 1;
+  if (per_seed) memset(per_seed, 0, n_seeds * sizeof(wfm_trans_seed_t));
+  for (size_t i = 0; i < m; ++i) {
+    const uint32_t s = (uint32_t)(keys[i] >> TRANS_SHIFT);
+    out[i] = wfm_trans_iv_t{keys[i] & mask, keys[m + i] & mask, s, 0u};
+    if (per_seed) {
+      if (per_seed[s].count++ == 0) per_seed[s].first = i;
+      per_seed[s].bases += out[i].end - out[i].start;
+    }
+  }
+  *ivs = out; *n_ivs = m;
+  obj->last_rounds = rounds; obj->last_ivs = m; obj->last_pairs = pairs;
+  if (tm.on)
+    fprintf(stderr, "[wfm] transitive closure: %zu seeds over %zu arcs, depth %u: %llu rounds, %llu pairs in %zu chunks, %zu intervals over %llu bases; index %.3f ms, rounds and copy down %.3f ms (host clock)\n",
+            n_seeds, obj->na, depth, (unsigned long long)rounds, pairs, chunks, m, bases, ms_index, tm.lap());
+  return WFM_OK;
+}
+
+int wfm_trans_export(wfm_handle_t* h, wfm_trans_t* obj, wfm_trans_rec_t** recs, size_t* n_recs, wfm_trans_word_t** words, size_t* n_words) {
+  if (!h || !obj || !recs || !n_recs || !words || !n_words) return WFM_E_ARG;
+  *recs = nullptr; *n_recs = 0; *words = nullptr; *n_words = 0;
+  if (int rc = trans_usable(h, obj)) return rc;
+  if (obj->recs.empty()) return WFM_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  wfm_trans_rec_t* r = (wfm_trans_rec_t*)malloc(obj->recs.size() * sizeof(wfm_trans_rec_t));
+  wfm_trans_word_t* w = (wfm_trans_word_t*)malloc(obj->np * sizeof(wfm_trans_word_t));
+  hipError_t e = hipSuccess;
+  if (r && w) e = cs_copy_down(h, cs_pin_pieces(h), (char*)w, (const uint8_t*)obj->pre, obj->np * sizeof(wfm_trans_word_t));
+  if (!r || !w || e != hipSuccess) {
+    free(r); free(w);
+    if (e != hipSuccess) { h->err = std::string("wfm_trans_export: ") + hipGetErrorString(e); return WFM_E_HIP; }
+    h->err = "out of host memory (transitive list)";
+    return WFM_E_NOMEM;
+  }
+  memcpy(r, obj->recs.data(), obj->recs.size() * sizeof(wfm_trans_rec_t));
+  *recs = r; *n_recs = obj->recs.size();
+  *words = w; *n_words = obj->np;
+  return WFM_OK;
+}
+
+int wfm_trans_import(wfm_handle_t* h, wfm_trans_t* obj, const wfm_trans_rec_t* recs, size_t n_recs, const wfm_trans_word_t* words, size_t n_words) {
+  if (!h || !obj || (n_recs && !recs) || (n_words && !words)) return WFM_E_ARG;
+  if (n_recs == 0) return WFM_OK;
+  if (int rc = trans_usable(h, obj)) return rc;
+  // everything is looked at before anything is added
+  auto refuse = [&](size_t i, const char* why) {
+    h->err = "wfm_trans_import: record " + std::to_string(i) + " " + why + "; nothing was added";
+    return (int)WFM_E_ARG;
+  };
+  std::vector<TransArc> arcs(2 * n_recs);
+  std::vector<wfm_trans_rec_t> mine(recs, recs + n_recs);
+  for (size_t i = 0; i < n_recs; ++i) {
+    const wfm_trans_rec_t& r = recs[i];
+    if (r.flags & ~WFM_TRANS_REVERSE) return refuse(i, "holds a flag bit that is not WFM_TRANS_REVERSE");
+    if (r.n_runs == 0 || r.pre_off > n_words || (uint64_t)r.n_runs + 1 > n_words - r.pre_off) return refuse(i, "has no runs, or its prefix words leave the list");
+    const wfm_trans_word_t* w = words + r.pre_off;
+    if (w[0].p | w[0].t | w[0].eq | w[0].x) return refuse(i, "does not begin at zero");
+    for (uint32_t k = 0; k < r.n_runs; ++k) {
+      const wfm_trans_word_t &a = w[k], &b = w[k + 1];
+      if (b.p < a.p || b.t < a.t || b.eq < a.eq || b.x < a.x) return refuse(i, "has a prefix that falls");
+      const uint32_t dp = b.p - a.p, dt = b.t - a.t, de = b.eq - a.eq, dx = b.x - a.x, len = std::max(dp, dt);
+      const bool run = len && (dp == 0 || dp == len) && (dt == 0 || dt == len) && ((dp == len && dt == len) ? (de + dx == len && (de == 0 || dx == 0)) : (de == 0 && dx == 0));
+      if (!run) return refuse(i, "has a step between two prefix words that is no run of =, X, I or D");
+    }
+    const uint32_t P = w[r.n_runs].p, T = w[r.n_runs].t;
+    if (r.t > obj->n_bases || P > obj->n_bases - r.t || r.q > obj->n_bases || T > obj->n_bases - r.q) return refuse(i, "leaves the world");
+    mine[i].pre_off = obj->np + r.pre_off;
+    trans_arcs_of(mine[i], mine[i].pre_off, P, T, &arcs[2 * i]);
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  if (int rc = trans_reserve(h, obj, "wfm_trans_import", n_words, n_recs)) return rc;
+  HIPCHK(h, hipMemcpyAsync(obj->pre + obj->np, words, n_words * sizeof(wfm_trans_word_t), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(obj->arcs + obj->na, arcs.data(), arcs.size() * sizeof(TransArc), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  obj->np += n_words;
+  obj->na += arcs.size();
+  obj->recs.insert(obj->recs.end(), mine.begin(), mine.end());
+  obj->indexed = false;
+  return WFM_OK;
+}
+
+int wfm_trans_counts(const wfm_trans_t* obj, uint64_t out[6]) {
+  if (!obj || !out) return WFM_E_ARG;
+  out[0] = obj->recs.size(); out[1] = obj->np; out[2] = obj->na; out[3] = obj->last_rounds; out[4] = obj->last_ivs; out[5] = obj->last_pairs;
+  return WFM_OK;
+}
+
+void wfm_trans_free_list(void* p) { free(p); }
 
 // ---- every score proved optimal by a banded DP (wfmash_hip.h; the band: wfa_optband.h; the kernel: wfa_optcheck.hip) ----
 int wfm_check_optimal(wfm_handle_t* h, const wfm_penalties_t* pen, const wfm_seqset_t* s, const wfm_result_t* res, uint64_t max_cells,

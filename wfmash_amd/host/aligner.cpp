@@ -5,6 +5,7 @@
 #include "chain_text.hpp"
 #include "pav_text.hpp"
 #include "genotype_text.hpp"
+#include "transitive_text.hpp"
 #include "map_queue.hpp"
 #include "parallel.hpp"
 #include "../csrc/wfa_handle.h"
@@ -388,7 +389,8 @@ std::string Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<std::stri
                                  std::string* vcf, wfm_coverage_t* coverage, const std::vector<uint64_t>* seq_offsets, std::string* lift,
                                  const wfm_liftset_t* liftset, const std::vector<lift::Interval>* lift_intervals, wfm_pav_t* pav,
                                  const std::vector<uint32_t>* pav_columns, std::string* chain, bool chain_swap, wfm_sites_t* sites,
-                                 uint32_t sites_groups, wfm_net_t* net, uint64_t net_batch, std::vector<wflign::NetHead>* net_heads) {
+                                 uint32_t sites_groups, wfm_net_t* net, uint64_t net_batch, std::vector<wflign::NetHead>* net_heads, wfm_trans_t* trans,
+                                 const std::vector<uint64_t>* query_world) {
   const bool dbg = getenv("WFM_DEBUG") != nullptr;
   BatchTimes t;
   std::vector<Fetched> rows = parse_rows(lines, first_row, sum);
@@ -398,13 +400,15 @@ std::string Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<std::stri
   std::vector<Fetched> fetched = fetch_eager(rows, threads, sum);
   if (fetched.empty()) return std::string();
   std::vector<wflign::BiwfaRecord> recs = make_records(fetched);
-  if (coverage || liftset || pav || sites || net)
+  if (coverage || liftset || pav || sites || net || trans)
     for (wflign::BiwfaRecord& r : recs) r.target_global = (*seq_offsets)[(size_t)ref->find(r.target_name)];  // (parse_rows has found every name)
   if (pav || sites)
     for (wflign::BiwfaRecord& r : recs) {
       const int qi = query->find(r.query_name);
       r.pav_group = qi >= 0 ? (*pav_columns)[(size_t)qi] : 0xffffffffu;  // (no column: the device flags the record and adds nothing)
     }
+  if (trans)
+    for (wflign::BiwfaRecord& r : recs) r.query_global = (*query_world)[(size_t)query->find(r.query_name)];  // (parse_rows has found every name)
   wflign::ResidentSeqs resident;
   if (ds) {
     resident.store = ds->store;
@@ -431,6 +435,7 @@ std::string Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<std::stri
   fmt.net = net;
   fmt.net_batch = net_batch;
   fmt.net_heads = net_heads;
+  fmt.trans = trans;
   const int rc = wflign::do_biwfa_alignment_batch(gpu_handle, recs, penalties_of(param), param.disable_chain_patching, filters_of(param), &st,
                                                   fmt, ds ? &resident : nullptr);
   if (rc < 0) throw std::runtime_error(std::string("[wfmash::align] GPU alignment failed: ") + st.error);
@@ -634,6 +639,25 @@ struct Aligner::Run {
     nets.emplace_back(h, p);
     return p;
   }
+  // --transitive: the world, the seeds in input order, where each query sequence begins in the world, the depth, and the trans object of
+  // every handle the run has used so far, made at the handle's first batch
+  bool trans_on = false;
+  transitive::World world;
+  lift::Bed trans_seeds;
+  std::vector<uint64_t> query_world;
+  uint32_t trans_depth = 2;
+  std::mutex trans_mu;
+  std::vector<std::pair<wfm_handle_t*, wfm_trans_t*>> trans;
+  wfm_trans_t* trans_of(wfm_handle_t* h) {
+    if (!trans_on) return nullptr;
+    std::lock_guard<std::mutex> lk(trans_mu);
+    for (auto& ht : trans) if (ht.first == h) return ht.second;
+    wfm_trans_t* p = nullptr;
+    std::lock_guard<std::mutex> hl(wflign::handle_lock(h));
+    if (wfm_trans_create(h, world.n_bases(), &p) != WFM_OK) throw std::runtime_error(std::string("[wfmash::align] --transitive: ") + wfm_last_error(h));
+    trans.emplace_back(h, p);
+    return p;
+  }
   // --coverage, --lift, --pav, --genotypes, --chain-net: where each target sequence begins in the concatenation (nseq + 1 values; empty: all are off).  --coverage: the depth object
   // of every handle the run has used so far, made at the handle's first batch
   std::vector<uint64_t> seq_offsets;
@@ -660,6 +684,10 @@ struct Aligner::Run {
     for (auto& hn : nets) {
       std::lock_guard<std::mutex> lk(wflign::handle_lock(hn.first));
       wfm_net_free(hn.second);
+    }
+    for (auto& ht : trans) {
+      std::lock_guard<std::mutex> lk(wflign::handle_lock(ht.first));
+      wfm_trans_free(ht.second);
     }
   }
   wfm_coverage_t* coverage_of(wfm_handle_t* h) {
@@ -764,7 +792,8 @@ void Aligner::run_worker(Run& run, size_t wk) {
       std::string text = align_batch(run.use[wk], batch, run.threads_each, run.part[wk], first_row, run.vcf_writer ? &vcf : nullptr,
                                      run.coverage_of(run.use[wk]), &run.seq_offsets, run.lift_writer ? &lifted : nullptr, run.liftset_of(run.use[wk]),
                                      &run.lift_iv, run.pav_of(run.use[wk]), &run.pav_cols.of_seq, run.chain_writer ? &chains : nullptr, run.chain_swap,
-                                     run.sites_of(run.use[wk]), (uint32_t)run.pav_cols.keys.size(), run.net_of(run.use[wk]), (uint64_t)seq, &heads);
+                                     run.sites_of(run.use[wk]), (uint32_t)run.pav_cols.keys.size(), run.net_of(run.use[wk]), (uint64_t)seq, &heads,
+                                     run.trans_of(run.use[wk]), &run.query_world);
       if (!heads.empty()) {
         std::lock_guard<std::mutex> lk(run.net_mu);
         for (auto& hd : heads) run.net_heads.push_back(std::move(hd));
@@ -1004,6 +1033,56 @@ void Aligner::finish_chain_net(Run& run, std::ofstream& out) {
             (unsigned long long)lost, std::chrono::duration<double, std::milli>(t1 - t0).count(), ms_since(t1));
 }
 
+// --transitive: every other handle's object exported and imported into the first (the closure is a set function: the order does not
+// matter), the closure of the seeds taken once on the device, the file through transitive_text.hpp in the order of the BED's lines
+void Aligner::finish_transitive(Run& run, std::ofstream& out) {
+  const auto t0 = Clock::now();
+  auto fail = [](wfm_handle_t* h, const char* what) { throw std::runtime_error(std::string("[wfmash::align] --transitive: ") + what + ": " + wfm_last_error(h)); };
+  const std::vector<lift::Interval>& seeds = run.trans_seeds.iv;
+  wfm_trans_iv_t* ivs = nullptr;
+  size_t n_ivs = 0;
+  std::vector<wfm_trans_seed_t> per(seeds.size());
+  uint64_t counts[6] = {0, 0, 0, 0, 0, 0};
+  if (!run.trans.empty() && !seeds.empty()) {
+    wfm_handle_t* h0 = run.trans.front().first;
+    wfm_trans_t* o0 = run.trans.front().second;
+    for (size_t k = 1; k < run.trans.size(); ++k) {
+      wfm_trans_rec_t* recs = nullptr;
+      wfm_trans_word_t* words = nullptr;
+      size_t nr = 0, nw = 0;
+      {
+        std::lock_guard<std::mutex> lk(wflign::handle_lock(run.trans[k].first));
+        if (wfm_trans_export(run.trans[k].first, run.trans[k].second, &recs, &nr, &words, &nw) != WFM_OK) fail(run.trans[k].first, "export");
+      }
+      std::lock_guard<std::mutex> lk(wflign::handle_lock(h0));
+      const int rc = wfm_trans_import(h0, o0, recs, nr, words, nw);
+      wfm_trans_free_list(recs); wfm_trans_free_list(words);
+      if (rc != WFM_OK) fail(h0, "import");
+    }
+    std::vector<wfm_lift_iv_t> raw(seeds.size());
+    for (size_t i = 0; i < raw.size(); ++i) raw[i] = wfm_lift_iv_t{seeds[i].gstart, seeds[i].gend};
+    std::lock_guard<std::mutex> lk(wflign::handle_lock(h0));
+    if (wfm_trans_closure(h0, o0, raw.data(), raw.size(), run.trans_depth, &ivs, &n_ivs, per.data()) != WFM_OK) fail(h0, "closure");
+    wfm_trans_counts(o0, counts);
+  }
+  const auto t1 = Clock::now();
+  std::string text;
+  uint64_t lines = 0;
+  for (size_t i = 0; i < seeds.size(); ++i) {
+    if (!ivs) lines += transitive::lines(text, run.world, seeds[i], seeds[i].gstart, seeds[i].gend);  // (no record was added: a seed reaches itself)
+    else
+      for (uint64_t k = per[i].first; k < per[i].first + per[i].count; ++k) lines += transitive::lines(text, run.world, seeds[i], ivs[k].start, ivs[k].end);
+    if (text.size() >= ((size_t)1 << 20)) { out << text; text.clear(); }
+  }
+  out << text;
+  wfm_trans_free_list(ivs);
+  wflign::transitive_finished(lines, counts[3], run.trans_seeds.skipped);
+  if (getenv("WFM_DEBUG"))
+    fprintf(stderr, "[wfmash::align] transitive: %zu objects merged, %llu records, %llu prefix words, %zu seeds at depth %u, %llu rounds, %llu pairs, %zu intervals, %llu lines, merge + closure %.1f ms, text %.1f ms\n",
+            run.trans.size(), (unsigned long long)counts[0], (unsigned long long)counts[1], seeds.size(), run.trans_depth, (unsigned long long)counts[3],
+            (unsigned long long)counts[5], n_ivs, (unsigned long long)lines, std::chrono::duration<double, std::milli>(t1 - t0).count(), ms_since(t1));
+}
+
 Summary Aligner::compute() {
   Summary sum;
   const auto t0 = Clock::now();
@@ -1056,13 +1135,16 @@ Summary Aligner::compute() {
     if (!netstream.is_open()) throw std::runtime_error("[wfmash::align] Error! Failed to open the chain-net file: " + net_out);
     run.net_on = true;
   }
+  std::ofstream transstream;
+  std::string trans_bed, trans_out;
+  wflign::transitive_paths(trans_bed, trans_out, run.trans_depth);
   std::ofstream pavstream;
   std::string pav_bed, pav_out;
   uint64_t pav_window = 0, pav_skipped = 0;
   wflign::pav_paths(pav_bed, pav_window, pav_out);
   std::ofstream gtstream;
   const std::string gt_path = wflign::genotypes_path();
-  if (!cov_path.empty() || !lift_out.empty() || !pav_out.empty() || !gt_path.empty() || !net_out.empty()) {
+  if (!cov_path.empty() || !lift_out.empty() || !pav_out.empty() || !gt_path.empty() || !net_out.empty() || !trans_out.empty()) {
     run.seq_offsets.assign(1, 0);
     for (int i = 0; i < ref->nseq(); ++i) run.seq_offsets.push_back(run.seq_offsets.back() + (uint64_t)ref->length(i));
   }
@@ -1078,6 +1160,23 @@ Summary Aligner::compute() {
     liftstream.open(lift_out);
     if (!liftstream.is_open()) throw std::runtime_error("[wfmash::align] Error! Failed to open the lift file: " + lift_out);
     run.lift_writer.reset(new skch::OrderedWriter<std::string, TextSink>(TextSink{&liftstream}));
+  }
+  if (!trans_out.empty()) {  // --transitive: the world and the seeds are known before anything is aligned; the file is written once the workers are done
+    std::vector<std::string> tnames, qnames;
+    std::vector<uint64_t> tlengths, qlengths;
+    for (int i = 0; i < ref->nseq(); ++i) { tnames.push_back(ref->name(i)); tlengths.push_back((uint64_t)ref->length(i)); }
+    for (int i = 0; i < query->nseq(); ++i) { qnames.push_back(query->name(i)); qlengths.push_back((uint64_t)query->length(i)); }
+    run.world = transitive::make_world(tnames, tlengths, qnames, qlengths);
+    if (run.world.n_bases() >= ((uint64_t)1 << 40)) throw std::runtime_error("[wfmash::align] --transitive: the sequences hold 2^40 bases or more");
+    for (const std::string& name : qnames) run.query_world.push_back(run.world.offsets[(size_t)run.world.find(name)]);
+    std::ifstream bed(trans_bed, std::ios::binary);
+    if (!bed.is_open()) throw std::runtime_error("[wfmash::align] Error! Failed to open the BED file of --transitive: " + trans_bed);
+    const std::string text((std::istreambuf_iterator<char>(bed)), std::istreambuf_iterator<char>());
+    run.trans_seeds = transitive::parse_seeds(text, run.world);
+    if (run.trans_seeds.iv.size() >= ((size_t)1 << 24)) throw std::runtime_error("[wfmash::align] --transitive: the BED holds 2^24 seeds or more");
+    transstream.open(trans_out);
+    if (!transstream.is_open()) throw std::runtime_error("[wfmash::align] Error! Failed to open the transitive file: " + trans_out);
+    run.trans_on = true;
   }
   if (!pav_out.empty()) {  // --pav: the intervals and the columns are known before anything is aligned; the file is written once the workers are done
     std::vector<uint64_t> lengths;
@@ -1129,6 +1228,7 @@ Summary Aligner::compute() {
   if (pavstream.is_open()) { finish_pav(run, pavstream, pav_skipped); pavstream.close(); }
   if (gtstream.is_open()) { finish_genotypes(run, gtstream); gtstream.close(); }
   if (netstream.is_open()) { finish_chain_net(run, netstream); netstream.close(); }
+  if (transstream.is_open()) { finish_transitive(run, transstream); transstream.close(); }
   sum_up(sum, run.part, t0);
   outstream.close();
   if (vcfstream.is_open()) vcfstream.close();

@@ -15,6 +15,7 @@
 #include "fasta.hpp"
 #include "chain_text.hpp"
 #include "lift_text.hpp"
+#include "transitive_text.hpp"
 #include "pav_text.hpp"
 #include "genotype_text.hpp"
 #include "map_stats.hpp"
@@ -150,6 +151,37 @@ char* wfmh_test_lift_lines(const char* const* names, const uint64_t* lengths, in
     } else {
       return nullptr;
     }
+  }
+  char* p = (char*)malloc(out.size() + 1);
+  if (p) memcpy(p, out.c_str(), out.size() + 1);
+  return p;
+}
+
+// test hook (no GPU): the text side of --transitive (transitive_text.hpp): the world, the seeds the parser keeps, the lines of given intervals
+char* wfmh_test_transitive_lines(const char* const* tnames, const uint64_t* tlengths, int n_t, const char* const* qnames, const uint64_t* qlengths,
+                                 int n_q, const char* bed, const char* spec) {
+  if (n_t < 0 || n_q < 0 || (n_t && (!tnames || !tlengths)) || (n_q && (!qnames || !qlengths)) || !bed || !spec) return nullptr;
+  std::vector<std::string> tn, qn;
+  std::vector<uint64_t> tl, ql;
+  for (int i = 0; i < n_t; ++i) { tn.push_back(tnames[i]); tl.push_back(tlengths[i]); }
+  for (int i = 0; i < n_q; ++i) { qn.push_back(qnames[i]); ql.push_back(qlengths[i]); }
+  const transitive::World w = transitive::make_world(tn, tl, qn, ql);
+  const lift::Bed seeds = transitive::parse_seeds(std::string(bed), w);
+  std::string out = lift::bed_dump(seeds);
+  std::istringstream in(spec);
+  std::string line;
+  while (std::getline(in, line)) {
+    if (line.empty()) continue;
+    uint64_t v[3] = {0, 0, 0};
+    size_t at = 2;
+    if (line.compare(0, 2, "I\t") != 0) return nullptr;
+    for (int k = 0; k < 3; ++k) {
+      const size_t tab = line.find('\t', at), end = tab == std::string::npos ? line.size() : tab;
+      if (!lift::decimal(line, at, end, &v[k]) || ((tab == std::string::npos) != (k == 2))) return nullptr;
+      at = end + 1;
+    }
+    if (v[0] >= seeds.iv.size() || v[1] > v[2] || v[2] > w.n_bases()) return nullptr;
+    transitive::lines(out, w, seeds.iv[(size_t)v[0]], v[1], v[2]);
   }
   char* p = (char*)malloc(out.size() + 1);
   if (p) memcpy(p, out.c_str(), out.size() + 1);

@@ -79,6 +79,11 @@
 //                                              liftOver, CrossMap and bcftools +liftover without chainSort | chainNet | netChainSubset; with
 //                                              or without --chain, whose bytes do not change; refused where --chain is, and with
 //                                              --chain-swap (nets on the query side are not done); off by default
+//   --transitive IN.bed --transitive-out FILE [--transitive-depth N]   transitive lifts: the runs of every record WRITTEN go to a trans
+//                                              object on the handle's device; after the last batch the BED's intervals are closed over all
+//                                              records, both ways, N rounds deep (default 2, 0 = to the fixed point: include/wfmash_host.h)
+//   --transitive-paf IN.paf --transitive IN.bed --transitive-out FILE [--transitive-depth N] target.fa [query.fa]   the same file for an
+//                                              existing aligned PAF; nothing else runs
 //   --chain-paf IN.paf [--chain FILE [--chain-swap]] [--chain-net FILE] target.fa [query.fa]   the same file(s) for an existing aligned
 //                                              PAF, one of the two at least: no mapping, no alignment; lines are skipped and counted as
 //                                              --coverage-paf does (the query's name and length are the line's: query.fa is not read);
@@ -202,6 +207,8 @@ static void usage() {
           "            --chain FILE  write a UCSC chain file (target to query) of every record written, blocks and gaps made on the GPU; score = the = columns (not with -m, --verify-paf)\n"
           "            --chain-swap  with --chain: the swapped file (query to target), what chainSwap would make of it\n"
           "            --chain-net FILE write a single-coverage chain file: every target base under at most one chain, the best record's, from a net across the records on the GPU (with or without --chain; not with -m, --verify-paf, --chain-swap)\n"
+          "            --transitive IN.bed --transitive-out FILE [--transitive-depth N]  close the BED's intervals over ALL records written, through targets and queries alike, on the GPU: every interval a seed reaches in N rounds (2; 0: to the fixed point) as 'seq start end name seed_seq seed_start seed_end' (not with -m, --verify-paf)\n"
+          "            --transitive-paf FILE with --transitive and --transitive-out: the same file for an existing aligned PAF over target.fa [query.fa], and stop (only --transitive-depth and --device beside it)\n"
           "            --chain-paf FILE with --chain and/or --chain-net: the chain file(s) of an existing aligned PAF over target.fa, and stop (only --chain-swap and --device beside it)\n"
           "            --pav BED | --pav-window N, --pav-out FILE per target interval and group of query sequences the bases present, from per-group unions on the GPU (not with -m, --verify-paf)\n"
           "            --genotypes FILE write ONE sorted VCF of the distinct variants of all records with a haploid GT column (0, 1, .) per group of query sequences, joined on the GPU (give --left-align too; not with -m, --verify-paf)\n"
@@ -217,13 +224,15 @@ int main(int argc, char** argv) {
   ap.threads = 1;  // -t, default 1 as in the reference (parse_args.hpp: thread_count); the C ABI default (0) means all cores
   wfmh_map_params_t mp;
   wfmh_map_default_params(&mp);
-  std::string mapping_in, out = "/dev/stdout", target, query, seeds_in, scaffold_out, tmp_base, verify_in, ani_matrix_out, variants_out, genotypes_out, coverage_out, coverage_in, lift_bed, lift_out, lift_in, pav_bed, pav_out, pav_in, chain_out, chain_in, chain_net_out;
+  std::string mapping_in, out = "/dev/stdout", target, query, seeds_in, scaffold_out, tmp_base, verify_in, ani_matrix_out, variants_out, genotypes_out, coverage_out, coverage_in, lift_bed, lift_out, lift_in, pav_bed, pav_out, pav_in, chain_out, chain_in, chain_net_out, trans_bed, trans_out, trans_in;
+  unsigned long trans_depth = 2;
   uint64_t pav_window = 0;
   bool pav_window_set = false;
   bool pav_other = false;      // --pav-paf: anything beside it, --pav, --pav-window, --pav-out, --device and the two FASTAs
   bool other_options = false;  // --coverage-paf: anything beside it, --coverage, --device and the target
   bool lift_other = false;     // --lift-paf: anything beside it, --lift, --lift-out, --device and the target
   bool chain_other = false;    // --chain-paf: anything beside it, --chain, --chain-swap, --device and the two FASTAs
+  bool trans_other = false;    // --transitive-paf: anything beside it, --transitive, --transitive-out, --transitive-depth, --device and the two FASTAs
   bool chain_swap = false;
   bool verify = false, verify_optimal = false, ani_only = false, left_align = false;
   uint64_t verify_optimal_cells = 0;
@@ -233,6 +242,7 @@ int main(int argc, char** argv) {
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
     if (a[0] == '-' ? (a != "--pav" && a != "--pav-window" && a != "--pav-out" && a != "--pav-paf" && a != "--device" && a != "-h" && a != "--help") : !query.empty()) pav_other = true;
+    if (a[0] == '-' ? (a != "--transitive" && a != "--transitive-out" && a != "--transitive-depth" && a != "--transitive-paf" && a != "--device" && a != "-h" && a != "--help") : !query.empty()) trans_other = true;
     if (a[0] == '-' ? (a != "--chain" && a != "--chain-net" && a != "--chain-swap" && a != "--chain-paf" && a != "--device" && a != "-h" && a != "--help") : !query.empty()) chain_other = true;
     if (a[0] == '-' ? (a != "--lift" && a != "--lift-out" && a != "--lift-paf" && a != "--device" && a != "-h" && a != "--help") : !target.empty()) lift_other = true;
     if (a[0] == '-' ? (a != "--coverage" && a != "--coverage-paf" && a != "--device" && a != "-h" && a != "--help") : !target.empty()) other_options = true;
@@ -377,6 +387,15 @@ int main(int argc, char** argv) {
     else if (a == "--lift-paf") lift_in = next("--lift-paf");
     else if (a == "--chain") chain_out = next("--chain");
     else if (a == "--chain-net") chain_net_out = next("--chain-net");
+    else if (a == "--transitive") trans_bed = next("--transitive");
+    else if (a == "--transitive-out") trans_out = next("--transitive-out");
+    else if (a == "--transitive-paf") trans_in = next("--transitive-paf");
+    else if (a == "--transitive-depth") {
+      const std::string v = next("--transitive-depth");
+      char* end = nullptr;
+      trans_depth = strtoul(v.c_str(), &end, 10);
+      if (v.empty() || *end || v[0] == '-' || trans_depth > 0xfffffffful) { fprintf(stderr, "[wfmash] ERROR: --transitive-depth takes a number of rounds, 0 for the fixed point\n"); return 1; }
+    }
     else if (a == "--chain-swap") chain_swap = true;
     else if (a == "--chain-paf") chain_in = next("--chain-paf");
     else if (a == "--pav") pav_bed = next("--pav");
@@ -414,6 +433,12 @@ int main(int argc, char** argv) {
   if (!lift_bed.empty() && !verify_in.empty()) { fprintf(stderr, "[wfmash] ERROR: --lift belongs to the align phase: it cannot be combined with --verify-paf\n"); return 1; }
   if (!genotypes_out.empty() && approx_only) { fprintf(stderr, "[wfmash] ERROR: --genotypes reads alignments: it cannot be combined with -m\n"); return 1; }
   if (!genotypes_out.empty() && !verify_in.empty()) { fprintf(stderr, "[wfmash] ERROR: --genotypes belongs to the align phase: it cannot be combined with --verify-paf\n"); return 1; }
+  if (!trans_bed.empty() && trans_out.empty()) { fprintf(stderr, "[wfmash] ERROR: --transitive needs --transitive-out FILE\n"); return 1; }
+  if (trans_bed.empty() && !trans_out.empty()) { fprintf(stderr, "[wfmash] ERROR: --transitive-out needs --transitive IN.bed\n"); return 1; }
+  if (!trans_in.empty() && trans_bed.empty()) { fprintf(stderr, "[wfmash] ERROR: --transitive-paf needs --transitive IN.bed and --transitive-out FILE\n"); return 1; }
+  if (!trans_in.empty() && trans_other) { fprintf(stderr, "[wfmash] ERROR: --transitive-paf runs nothing else: besides --transitive IN.bed, --transitive-out FILE, --transitive-depth N and the FASTAs it takes the number of the GPU only\n"); return 1; }
+  if (!trans_bed.empty() && approx_only) { fprintf(stderr, "[wfmash] ERROR: --transitive lifts through alignments: it cannot be combined with -m\n"); return 1; }
+  if (!trans_bed.empty() && !verify_in.empty()) { fprintf(stderr, "[wfmash] ERROR: --transitive belongs to the align phase: it cannot be combined with --verify-paf\n"); return 1; }
   if (!chain_net_out.empty() && chain_swap) { fprintf(stderr, "[wfmash] ERROR: --chain-net cannot be combined with --chain-swap: nets on the query side are not done\n"); return 1; }
   if (chain_swap && chain_out.empty()) { fprintf(stderr, "[wfmash] ERROR: --chain-swap needs --chain FILE\n"); return 1; }
   if (!chain_in.empty() && chain_out.empty() && chain_net_out.empty()) { fprintf(stderr, "[wfmash] ERROR: --chain-paf needs --chain FILE\n"); return 1; }
@@ -463,6 +488,16 @@ int main(int argc, char** argv) {
     if (crc != WFM_OK) fprintf(stderr, "[wfmash::chain] ERROR: %s\n", wfm_last_error(hc));
     wfm_destroy(hc);
     return crc == WFM_OK ? 0 : 2;
+  }
+  if (!trans_in.empty()) {  // the seeds closed over an existing PAF; nothing else runs
+    wfm_handle_t* ht = nullptr;
+    if (wfm_create(device, &ht) != WFM_OK) { fprintf(stderr, "[wfmash] ERROR: no usable MI355X device %d (there is no CPU fallback)\n", device); return 2; }
+    uint64_t tc[4] = {0, 0, 0, 0};
+    const int trc = wfmh_transitive_paf(ht, target.c_str(), query.empty() ? nullptr : query.c_str(), trans_in.c_str(), trans_bed.c_str(), trans_out.c_str(),
+                                        (uint32_t)trans_depth, tc);
+    if (trc != WFM_OK) fprintf(stderr, "[wfmash::transitive] ERROR: %s\n", wfm_last_error(ht));
+    wfm_destroy(ht);
+    return trc == WFM_OK ? 0 : 2;
   }
   if (!lift_in.empty()) {  // the BED through an existing PAF; nothing else runs
     wfm_handle_t* hl = nullptr;
@@ -607,6 +642,7 @@ int main(int argc, char** argv) {
     if (!lift_bed.empty()) wfmh_set_lift(lift_bed.c_str(), lift_out.c_str());
     if (!chain_out.empty()) wfmh_set_chain(chain_out.c_str(), chain_swap ? 1 : 0);
     if (!chain_net_out.empty()) wfmh_set_chain_net(chain_net_out.c_str());
+    if (!trans_bed.empty()) wfmh_set_transitive(trans_bed.c_str(), trans_out.c_str(), (uint32_t)trans_depth);
     if (pav_on) wfmh_set_pav(pav_bed.empty() ? nullptr : pav_bed.c_str(), pav_window, pav_out.c_str());
     rc = wfmh_align_paf_multi(hs.data(), (int)hs.size(), target.c_str(), q, mapping.c_str(), out.c_str(), &ap, &s);
     if (rc == WFM_OK)
@@ -660,6 +696,12 @@ int main(int argc, char** argv) {
       wfmh_chain_net_counts(nc);
       fprintf(stderr, "[wfmash::chain-net] %llu records added, %llu chains written, %llu pieces, %llu records won nothing\n", (unsigned long long)nc[0],
               (unsigned long long)nc[1], (unsigned long long)nc[2], (unsigned long long)nc[3]);
+    }
+    if (!trans_bed.empty() && rc == WFM_OK) {
+      uint64_t tc[4] = {0, 0, 0, 0};
+      wfmh_transitive_counts(tc);
+      fprintf(stderr, "[wfmash::transitive] %llu records added, %llu lines written, %llu rounds, %llu BED lines skipped\n", (unsigned long long)tc[0],
+              (unsigned long long)tc[1], (unsigned long long)tc[2], (unsigned long long)tc[3]);
     }
     if (!coverage_out.empty() && rc == WFM_OK) {
       uint64_t cc[4] = {0, 0, 0, 0};

@@ -17,6 +17,7 @@
 #include "aligner.hpp"
 #include "coverage_text.hpp"
 #include "lift_text.hpp"
+#include "transitive_text.hpp"
 #include "chain_text.hpp"
 #include "pav_text.hpp"
 #include "parallel.hpp"
@@ -595,6 +596,86 @@ int wfmh_pav_paf(wfm_handle_t* h, const char* target_fasta, const char* query_fa
     return WFM_OK;
   } catch (const std::exception& e) {
     if (obj) wfm_pav_free(obj);
+    std::cerr << e.what() << std::endl;
+    wfm_set_error(h, e.what());
+    return WFM_E_ARG;
+  }
+}
+
+// --transitive-paf: the closure of the BED's intervals over an existing aligned PAF.  Lines go to a trans object in batches of runs, read
+// and skipped by wfmh_coverage_paf's rules (coverage::classify_line); a line whose query neither FASTA has is skipped and counted too; the
+// closure once, at the end.
+int wfmh_transitive_paf(wfm_handle_t* h, const char* target_fasta, const char* query_fasta_or_null, const char* aligned_paf, const char* bed_path,
+                        const char* out_path, uint32_t depth, uint64_t out[4]) {
+  if (!h || !target_fasta || !aligned_paf || !bed_path || !out_path) return WFM_E_ARG;
+  wfm_trans_t* obj = nullptr;
+  try {
+    std::shared_ptr<wfmash_host::FastaStore> target = wfmash_host::open_shared(target_fasta);
+    std::shared_ptr<wfmash_host::FastaStore> query = query_fasta_or_null && *query_fasta_or_null ? wfmash_host::open_shared(query_fasta_or_null) : target;
+    std::ifstream in(aligned_paf);
+    if (!in.is_open()) throw std::runtime_error(std::string("[wfmash::transitive] cannot open ") + aligned_paf);
+    std::ifstream bedstream(bed_path, std::ios::binary);
+    if (!bedstream.is_open()) throw std::runtime_error(std::string("[wfmash::transitive] cannot open ") + bed_path);
+    const std::string bed_text((std::istreambuf_iterator<char>(bedstream)), std::istreambuf_iterator<char>());
+    PafRuns pr(h, "transitive", *target);
+    const uint64_t* skipped = pr.skipped;
+    std::vector<std::string> tnames, qnames;
+    std::vector<uint64_t> qlengths;
+    for (int i = 0; i < target->nseq(); ++i) tnames.push_back(target->name(i));
+    for (int i = 0; i < query->nseq(); ++i) { qnames.push_back(query->name(i)); qlengths.push_back((uint64_t)query->length(i)); }
+    const transitive::World world = transitive::make_world(tnames, pr.lengths, qnames, qlengths);
+    if (world.n_bases() >= ((uint64_t)1 << 40)) throw std::runtime_error("[wfmash::transitive] the sequences hold 2^40 bases or more");
+    const lift::Bed seeds = transitive::parse_seeds(bed_text, world);
+    if (seeds.iv.size() >= ((size_t)1 << 24)) throw std::runtime_error("[wfmash::transitive] the BED holds 2^24 seeds or more");
+    std::ofstream outstream(out_path);
+    if (!outstream.is_open()) throw std::runtime_error(std::string("[wfmash::transitive] cannot open ") + out_path);
+    std::lock_guard<std::mutex> lk(wflign::handle_lock(h));
+    pr.device(wfm_trans_create(h, world.n_bases(), &obj), "create");
+    uint64_t added = 0, no_query = 0;
+    std::vector<std::pair<uint64_t, bool>> where;  // of the batch at hand: the world place of the line's forward query window, its strand
+    std::vector<wfm_trans_prob_t> probs;
+    std::vector<uint32_t> flags;
+    pr.read(in, [&](const verify::Line& l) {
+      const int qi = world.find(l.qname);
+      if (qi < 0 || (uint64_t)l.qe > world.lengths[(size_t)qi]) { ++no_query; return false; }
+      where.emplace_back(transitive::query_world(world.offsets[(size_t)qi], (uint64_t)l.qs), l.rev);
+      return true;
+    }, [&]() {
+      probs.resize(pr.probs.size());
+      flags.resize(probs.size());
+      for (size_t j = 0; j < probs.size(); ++j)
+        probs[j] = wfm_trans_prob_t{pr.probs[j].base, where[j].first, pr.probs[j].runs_off, pr.probs[j].n_runs, where[j].second ? WFM_TRANS_REVERSE : 0u};
+      const int refused = pr.device(wfm_trans_add(h, obj, probs.data(), probs.size(), pr.runs.data(), pr.runs.size(), flags.data()), "add");
+      added += probs.size() - (uint64_t)refused;
+      pr.refused((uint64_t)refused);
+      where.clear();
+    });
+    std::vector<wfm_lift_iv_t> raw(seeds.iv.size());
+    for (size_t i = 0; i < raw.size(); ++i) raw[i] = wfm_lift_iv_t{seeds.iv[i].gstart, seeds.iv[i].gend};
+    std::vector<wfm_trans_seed_t> per(raw.size());
+    wfm_trans_iv_t* ivs = nullptr;
+    size_t n_ivs = 0;
+    pr.device(wfm_trans_closure(h, obj, raw.data(), raw.size(), depth, &ivs, &n_ivs, per.data()), "closure");
+    uint64_t counts[6] = {0, 0, 0, 0, 0, 0};
+    wfm_trans_counts(obj, counts);
+    wfm_trans_free(obj);
+    obj = nullptr;
+    std::string text;
+    uint64_t lines = 0;
+    for (size_t i = 0; i < seeds.iv.size(); ++i) {
+      for (uint64_t k = per[i].first; k < per[i].first + per[i].count; ++k) lines += transitive::lines(text, world, seeds.iv[i], ivs[k].start, ivs[k].end);
+      if (text.size() >= ((size_t)1 << 20)) { outstream << text; text.clear(); }
+    }
+    outstream << text;
+    wfm_trans_free_list(ivs);
+    const uint64_t all_skipped = pr.all_skipped() + no_query;
+    std::cerr << "[wfmash::transitive] " << seeds.iv.size() << " seeds (" << seeds.skipped << " BED lines skipped), " << added << " lines added, " << all_skipped
+              << " skipped (" << skipped[1] << " without an =XID cg:Z:, " << skipped[2] << " malformed, " << skipped[3] << " with an unknown target, " << skipped[4]
+              << " with another tlen, " << no_query << " with an unknown query), " << counts[3] << " rounds, " << lines << " lines written" << std::endl;
+    if (out) { out[0] = added; out[1] = lines; out[2] = counts[3]; out[3] = seeds.skipped; }
+    return WFM_OK;
+  } catch (const std::exception& e) {
+    if (obj) wfm_trans_free(obj);
     std::cerr << e.what() << std::endl;
     wfm_set_error(h, e.what());
     return WFM_E_ARG;

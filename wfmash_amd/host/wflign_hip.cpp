@@ -5,6 +5,7 @@
 #include "parallel.hpp"
 #include "lift_text.hpp"
 #include "chain_text.hpp"
+#include "transitive_text.hpp"
 #include "../csrc/wfa_handle.h"
 
 #include <algorithm>
@@ -87,6 +88,14 @@ std::atomic<bool> g_chain_net{false};
 std::mutex g_chain_net_mu;
 std::string g_chain_net_out;
 std::atomic<uint64_t> g_chain_net_counts[4];
+
+// --transitive: the process-wide switch, the BED of seeds, the file the align phase writes and the depth, and {records added, lines
+// written, rounds run, BED lines skipped} since it was set
+std::atomic<bool> g_transitive{false};
+std::mutex g_transitive_mu;
+std::string g_transitive_bed, g_transitive_out;
+uint32_t g_transitive_depth = 2;
+std::atomic<uint64_t> g_transitive_counts[4];
 
 // --pav: the process-wide switch, the BED of target intervals or the window size, the file the align phase writes, and {records added,
 // rows written, union intervals, BED lines skipped} since it was set
@@ -964,7 +973,52 @@ int net_records(BiwfaBatch& b, const PackedRuns& pk) {
             pk.ms + ms_between(t0, Clock::now()), pk.ms + ms_between(t0, t1), ms_between(t1, Clock::now()));
   return 0;
 }
+// ---- --transitive: the same problems into the trans object of the batch's handle, ONE device call per batch (wfm_trans_add), each
+// with the world position of its first target base (the problem's base: the world begins with the target's sequences) and of the first
+// base of its forward query window (chain_records' qs in the query sequence's place in the world).  A record the device refuses adds
+// nothing, is counted and reported. ----
+int trans_records(BiwfaBatch& b, const PackedRuns& pk) {
+  const auto t0 = Clock::now();
+  const size_t n = pk.probs.size();
+  std::vector<wfm_trans_prob_t> probs(n);
+  for (size_t j = 0; j < n; ++j) {
+    const BiwfaRecord& r = b.recs[pk.rec[j]];
+    const uint64_t qs = r.query_is_rev ? r.query_offset + (r.query_length - pk.qa[j] - pk.q_len[j]) : r.query_offset + pk.qa[j];
+    probs[j] = wfm_trans_prob_t{pk.probs[j].base, transitive::query_world(r.query_global, qs), pk.probs[j].runs_off, pk.probs[j].n_runs,
+                                r.query_is_rev ? WFM_TRANS_REVERSE : 0u};
+  }
+  int rc = WFM_OK;
+  std::vector<uint32_t> flags(n);
+  auto t1 = t0;
+  if (n) {
+    std::lock_guard<std::mutex> lk(handle_lock(b.h));
+    t1 = Clock::now();
+    rc = wfm_trans_add(b.h, b.fmt.trans, probs.data(), n, pk.runs.data(), pk.runs.size(), flags.data());
+    if (rc < 0 && b.stats) b.stats->error = wfm_last_error(b.h);
+  }
+  if (rc < 0) return rc;
+  g_transitive_counts[0] += n - (uint64_t)rc;
+  if (rc > 0 || pk.unknown)
+    fprintf(stderr, "[wflign] transitive: %llu records of a batch were NOT added (their runs leave their sequences or cannot be held)\n",
+            (unsigned long long)((uint64_t)rc + pk.unknown));
+  if (getenv("WFM_DEBUG"))
+    fprintf(stderr, "[wflign] transitive: %zu records, %zu runs, %d flagged, %.1f ms (runs %.1f, host %.1f, device call %.1f)\n", n, pk.runs.size(), rc,
+            pk.ms + ms_between(t0, Clock::now()), pk.ms, ms_between(t0, t1), ms_between(t1, Clock::now()));
+  return 0;
+}
 }  // namespace
+
+void transitive_paths(std::string& bed, std::string& out, uint32_t& depth) {
+  std::lock_guard<std::mutex> lk(g_transitive_mu);
+  const bool on = g_transitive.load();
+  bed = on ? g_transitive_bed : std::string();
+  out = on ? g_transitive_out : std::string();
+  depth = g_transitive_depth;
+}
+
+void transitive_finished(uint64_t lines, uint64_t rounds, uint64_t bed_skipped) {
+  g_transitive_counts[1] += lines; g_transitive_counts[2] += rounds; g_transitive_counts[3] += bed_skipped;
+}
 
 std::string chain_net_path() {
   std::lock_guard<std::mutex> lk(g_chain_net_mu);
@@ -1058,7 +1112,7 @@ int do_biwfa_alignment_batch(wfm_handle_t* h, std::vector<BiwfaRecord>& recs, co
   } else {
     for_each_record(n, fmt.threads, [&](size_t ri) { swizzle(b, ri); write_record(b, ri); });
   }
-  if (fmt.coverage || fmt.pav || fmt.liftset || fmt.chain || fmt.sites || fmt.net) {  // one packing for the stages that are on; each makes its own device call
+  if (fmt.coverage || fmt.pav || fmt.liftset || fmt.chain || fmt.sites || fmt.net || fmt.trans) {  // one packing for the stages that are on; each makes its own device call
     const PackedRuns pk = pack_written(b);
     if (fmt.coverage && (rc = coverage_records(b, pk)) < 0) return rc;
     if (fmt.pav && (rc = pav_records(b, pk)) < 0) return rc;
@@ -1066,6 +1120,7 @@ int do_biwfa_alignment_batch(wfm_handle_t* h, std::vector<BiwfaRecord>& recs, co
     if (fmt.liftset && (rc = lift_records(b, pk)) < 0) return rc;
     if (fmt.chain && (rc = chain_records(b, pk)) < 0) return rc;
     if (fmt.net && (rc = net_records(b, pk)) < 0) return rc;
+    if (fmt.trans && (rc = trans_records(b, pk)) < 0) return rc;
   }
   if (dbg)
     fprintf(stderr, "[wflign] %zu records: main alignment + runs + scans %.1f ms (incl. waiting for the device), patches %.1f ms (%zu tails scanned after their heads), swizzle + records %.1f ms\n",
@@ -1156,6 +1211,24 @@ void wfmh_set_chain_net(const char* path_or_null) {
     wflign::g_chain_net_out = on ? path_or_null : "";
   }
   wflign::g_chain_net.store(on);
+}
+
+void wfmh_set_transitive(const char* bed_path_or_null, const char* out_path_or_null, uint32_t depth) {
+  for (auto& a : wflign::g_transitive_counts) a.store(0);
+  const bool on = bed_path_or_null && *bed_path_or_null && out_path_or_null && *out_path_or_null;
+  {
+    std::lock_guard<std::mutex> lk(wflign::g_transitive_mu);
+    wflign::g_transitive_bed = on ? bed_path_or_null : "";
+    wflign::g_transitive_out = on ? out_path_or_null : "";
+    wflign::g_transitive_depth = depth;
+  }
+  wflign::g_transitive.store(on);
+}
+
+int wfmh_transitive_counts(uint64_t out[4]) {
+  if (!out) return WFM_E_ARG;
+  for (int q = 0; q < 4; ++q) out[q] = wflign::g_transitive_counts[q].load();
+  return WFM_OK;
 }
 
 int wfmh_chain_net_counts(uint64_t out[4]) {

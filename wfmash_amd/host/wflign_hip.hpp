@@ -27,6 +27,8 @@
 //                      (runs alone again), the record's lines into BiwfaRecord::lift
 //   chain_records      --chain only: the runs of every record WRITTEN compacted to the blocks and gaps of a UCSC chain, one
 //                      wfm_chain_runs call (runs alone again), the record's chain without its id into BiwfaRecord::chain
+//   trans_records      --transitive only: the runs of every record WRITTEN into the handle's trans object with the record's two places in
+//                      the world, one wfm_trans_add call
 //   net_records        --chain-net only: the runs of every record WRITTEN into the handle's net object, one wfm_net_add call (runs alone
 //                      again), each with score = its = columns and order = batch << 32 | its index among the batch's records packed; what
 //                      the chain's header needs stays on the host, keyed by the order
@@ -88,6 +90,7 @@ struct BiwfaRecord {
   uint64_t target_global = 0;        // --coverage, --lift: where the target sequence begins in the concatenation of the target's sequences
   bool written = false;              // the filters let the record's line through (write_record)
   uint32_t pav_group = 0;            // --pav, --genotypes: the column of the query sequence's group
+  uint64_t query_global = 0;         // --transitive: where the query sequence begins in the world (target_global is the target's place in it)
   std::string lift;                  // --lift: the lines of the BED intervals the record's target span overlaps, each with its newline ("" if off or not written)
   std::string chain;                 // --chain: the record's chain without its id (chain_text.hpp; "" if off, not written, refused or without a block)
   uint32_t tags = 0;                 // WFM_PF_* of the main alignment | of the head patch << 8 | of the tail patch << 16 (diagnostics: WFM_RECORD_TAGS)
@@ -145,6 +148,7 @@ struct OutputFormat {
   wfm_net_t* net = nullptr;            // --chain-net: the net object of the batch's handle (null: the stage is not run) ...
   uint64_t net_batch = 0;              // ... the batch's number, the high half of its records' orders ...
   std::vector<NetHead>* net_heads = nullptr;  // ... and where the heads of the records added go
+  wfm_trans_t* trans = nullptr;        // --transitive: the trans object of the batch's handle (null: the stage is not run)
 };
 
 // --variants: the file wfmh_set_variants named ("" while the switch is off); the align phase writes the batches' BiwfaRecord::vcf to it
@@ -172,6 +176,11 @@ void chain_path(std::string& out, bool& swap);
 // written the file: the chains written, the pieces, the records that won nothing
 std::string chain_net_path();
 void chain_net_finished(uint64_t chains, uint64_t pieces, uint64_t lost);
+
+// --transitive: the BED of seeds, the file and the depth wfmh_set_transitive named (out "" while the switch is off), and what the align
+// phase adds to the counts once it has written the file: the lines written, the rounds run, the BED lines it skipped
+void transitive_paths(std::string& bed, std::string& out, uint32_t& depth);
+void transitive_finished(uint64_t lines, uint64_t rounds, uint64_t bed_skipped);
 
 // --pav: the BED, the window size and the file wfmh_set_pav named (out "" while the switch is off; one of bed and window is set), and what
 // the align phase adds to the counts once it has written the file: its rows, the union's intervals, the BED lines it skipped
