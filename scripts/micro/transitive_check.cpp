@@ -4,9 +4,11 @@
 // skipped line and a known answer, on every prefix of it and on 100000 random mutations of it (whatever is kept lies inside its sequence
 // and the list is in input order); lines() on intervals with known lines, across one, two and all sequence boundaries, at a sequence
 // without bases and at the world's end, and on random intervals (the pieces abut, stay inside their sequences and add up to the interval);
+// file() on the same intervals shared out over the seeds, without a closure (every seed reaches itself) and on more than a MiB of lines;
 // the strand arithmetic of a record's place in the world.
 #include <cstdio>
 #include <cstdlib>
+#include <sstream>
 #include <string>
 #include <vector>
 
@@ -78,6 +80,25 @@ int main() {
               "chrA\t0\t100\t.\thapY\t0\t40\nchrB\t0\t50\t.\thapY\t0\t40\nchrC\t0\t70\t.\thapY\t0\t40\nhapX\t0\t30\t.\thapY\t0\t40\nhapY\t0\t40\t.\thapY\t0\t40\n"
               "hapY\t39\t40\tlast\thapX\t29\t30\n",
               "the lines");
+  // the whole file (file) on the same intervals: seed 0 reaches the first three, seed 1 the whole world, seed 2 the last base, seed 3
+  // nothing -- the lines above in the order of the seeds; without a closure (no record was added) every seed reaches itself
+  {
+    const std::vector<transitive::ClosureIv> ivs = {{10, 20, 0, 0}, {95, 105, 0, 0}, {99, 151, 0, 0}, {0, 290, 1, 0}, {289, 290, 2, 0}};
+    const std::vector<transitive::SeedCall> per = {{0, 3, 72}, {3, 1, 290}, {4, 1, 1}, {0, 0, 0}};
+    std::ostringstream file;
+    expect(transitive::file(file, w, seeds.iv, per.data(), ivs.data()) == 12, "file: the number of lines");
+    expect_text(file.str(), out, "file: the lines");
+    std::ostringstream alone;
+    expect(transitive::file(alone, w, seeds.iv, per.data(), nullptr) == 4, "file without a closure: the number of lines");
+    expect_text(alone.str(), "chrA\t10\t20\tgene1\tchrA\t10\t20\nhapY\t0\t40\t.\thapY\t0\t40\nhapX\t29\t30\tlast\thapX\t29\t30\nchrA\t10\t20\tgene1\tchrA\t10\t20\n",
+                "file without a closure");
+    // more than a MiB: flushed in parts, nothing lost
+    std::vector<transitive::ClosureIv> many(50000, transitive::ClosureIv{10, 20, 0, 0});
+    const std::vector<transitive::SeedCall> all = {{0, many.size(), 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+    std::ostringstream big;
+    expect(transitive::file(big, w, seeds.iv, all.data(), many.data()) == many.size(), "file over a MiB: the number of lines");
+    expect(big.str().size() == many.size() * 28, "file over a MiB: the bytes");
+  }
   for (int it = 0; it < 100000; ++it) {
     uint64_t a = next() % 290, b = a + 1 + next() % (290 - a);
     std::string text;

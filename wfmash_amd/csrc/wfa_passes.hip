@@ -55,6 +55,24 @@ struct Carver {
   }
 };
 
+// room for `need` elements of a block that holds `have`; what it holds moves with it
+template <class T>
+int grow_block(wfm_handle_t* h, T** blk, size_t* cap, size_t have, size_t need, const char* what) {
+  if (need <= *cap) return WFM_OK;
+  const size_t ncap = std::max<size_t>(need + need / 2, 4096);
+  T* nb = nullptr;
+  if (wfm_dmalloc((void**)&nb, ncap * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); h->err = std::string("out of device memory (") + what + ")"; return WFM_E_NOMEM; }
+  if (have) {
+    hipError_t e = hipMemcpyAsync(nb, *blk, have * sizeof(T), hipMemcpyDeviceToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) { wfm_dfree(nb); h->err = std::string("wfm_sites: ") + hipGetErrorString(e); return WFM_E_HIP; }
+  }
+  if (*blk) wfm_dfree(*blk);
+  *blk = nb;
+  *cap = ncap;
+  return WFM_OK;
+}
+
 inline bool runs_inside(uint64_t off, uint64_t n_runs, size_t n_runs_total) { return off <= n_runs_total && n_runs <= n_runs_total - off; }
 int runs_leave(wfm_handle_t* h, size_t i) {
   h->err = "problem " + std::to_string(i) + ": its runs leave the run buffer";
@@ -107,6 +125,52 @@ struct DeviceGuard {
     return WFM_E_ARG;
   }
 };
+
+// What the adds that take runs (wfm_coverage_add, wfm_pav_add, wfm_net_add, wfm_trans_add; fn names the one) open with: the argument and
+// size checks, the object on the handle's device, every problem's runs inside the buffer, the device made current, the problems (DevProb
+// restates P for the kernels) and the runs carved first out of cv's block and uploaded.  more(): what the pass checks and carves beside
+// them, before the block is sized.  Without problems *d_probs stays null and the caller returns.
+template <class DevProb, class P, class More>
+int add_preface(wfm_handle_t* h, const void* obj, int device, const char* what, const char* fn, Carver& cv, const P* probs, size_t n, const uint32_t* runs,
+                size_t n_runs_total, const uint32_t* flags_out, DevProb** d_probs, uint32_t** d_runs, More more) {
+  static_assert(sizeof(DevProb) == sizeof(P), "the kernels' problem restates the header's");
+  *d_probs = nullptr;
+  if (!h || !obj || (n && (!probs || !flags_out)) || (n_runs_total && !runs)) return WFM_E_ARG;
+  if (n == 0) return WFM_OK;
+  if (n > (size_t)INT32_MAX || n_runs_total > ((size_t)1 << 31)) { h->err = std::string(fn) + ": too many problems or runs for one call"; return WFM_E_ARG; }
+  if (int rc = DeviceGuard::usable(h, device, what)) return rc;
+  if (int rc = all_runs_inside(h, probs, n, n_runs_total)) return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  cv.piece(d_probs, n); cv.piece(d_runs, n_runs_total);
+  if (int rc = more()) return rc;
+  if (int rc = cv.commit(h)) return rc;
+  HIPCHK(h, hipMemcpyAsync(*d_probs, probs, n * sizeof(DevProb), hipMemcpyHostToDevice, h->stream));
+  if (n_runs_total) HIPCHK(h, hipMemcpyAsync(*d_runs, runs, n_runs_total * 4, hipMemcpyHostToDevice, h->stream));
+  return WFM_OK;
+}
+inline int count_flagged(const uint32_t* flags, size_t n, uint32_t bit) { return (int)std::count_if(flags, flags + n, [bit](uint32_t f) { return (f & bit) != 0; }); }
+
+// The union of n intervals given by their start keys ks and end keys ke (below 2^end_bit): sorted by start into (sks, ske), the ends to
+// their running maximum, the union's intervals to (uks, uke) and their number to *m, read back behind a wait for the stream.  aux: n /
+// WFM_PAV_SCAN_BLOCK rounded up, + 1; tmp: the sort's own (oom: the text where it cannot grow).  between(): what the caller does once the
+// running maximum is launched, before the compaction.
+template <class Between>
+int interval_union(wfm_handle_t* h, DevBuf<uint64_t>& tmp, const char* oom, const unsigned long long* ks, const unsigned long long* ke, unsigned long long* sks,
+                   unsigned long long* ske, size_t n, unsigned end_bit, unsigned long long* aux, unsigned long long* uks, unsigned long long* uke,
+                   unsigned long long* m, Between between) {
+  size_t tmp_bytes = 0;
+  HIPCHK(h, pav_sort(nullptr, &tmp_bytes, ks, sks, ke, ske, n, end_bit, h->stream));
+  if (tmp.ensure(tmp_bytes / 8 + 2)) { h->err = oom; return WFM_E_NOMEM; }
+  HIPCHK(h, pav_sort(tmp.p, &tmp_bytes, ks, sks, ke, ske, n, end_bit, h->stream));
+  launch_pav_runmax(ske, n, aux, h->stream);
+  HIPCHK(h, hipGetLastError());
+  if (int rc = between()) return rc;
+  launch_pav_compact(sks, ske, n, aux, uks, uke, h->stream);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipMemcpyAsync(m, aux + (n + WFM_PAV_SCAN_BLOCK - 1) / WFM_PAV_SCAN_BLOCK, 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return WFM_OK;
+}
 
 // The times of the [wfm] lines: the host clock from the construction or the last lap(), and the handle's two events around a launch.
 // on: WFM_DEBUG is set; without it nothing is recorded.
@@ -610,26 +674,18 @@ void wfm_coverage_free(wfm_coverage_t* cov) {
 
 int wfm_coverage_add(wfm_handle_t* h, wfm_coverage_t* cov, const wfm_cov_prob_t* probs, size_t n, const uint32_t* runs, size_t n_runs_total,
                      uint32_t* flags_out) {
-  if (!h || !cov || (n && (!probs || !flags_out)) || (n_runs_total && !runs)) return WFM_E_ARG;
-  if (n == 0) return WFM_OK;
-  if (n > (size_t)INT32_MAX || n_runs_total > ((size_t)1 << 31)) { h->err = "wfm_coverage_add: too many problems or runs for one call"; return WFM_E_ARG; }
-  if (int rc = cov_usable(h, cov)) return rc;
-  if (int rc = all_runs_inside(h, probs, n, n_runs_total)) return rc;
-  HIPCHK(h, hipSetDevice(h->device));
+  if (!cov) return WFM_E_ARG;
   CovProb* d_probs;
   uint32_t *d_runs, *d_flags;
   Carver cv{cov->work, "coverage add"};
-  cv.piece(&d_probs, n); cv.piece(&d_runs, n_runs_total); cv.piece(&d_flags, n);
-  if (int rc = cv.commit(h)) return rc;
-  HIPCHK(h, hipMemcpyAsync(d_probs, probs, n * sizeof(CovProb), hipMemcpyHostToDevice, h->stream));
-  if (n_runs_total) HIPCHK(h, hipMemcpyAsync(d_runs, runs, n_runs_total * 4, hipMemcpyHostToDevice, h->stream));
+  const int rc = add_preface(h, cov, cov->device, "the coverage object", "wfm_coverage_add", cv, probs, n, runs, n_runs_total, flags_out, &d_probs, &d_runs,
+                             [&] { cv.piece(&d_flags, n); return WFM_OK; });
+  if (rc || !d_probs) return rc;
   launch_cov_add(d_runs, d_probs, (int)n, cov->d, cov->n_bases, d_flags, h->stream);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipMemcpyAsync(flags_out, d_flags, n * 4, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  int spans = 0;
-  for (size_t i = 0; i < n; ++i) spans += (flags_out[i] & WFM_COV_SPANS) != 0;
-  return spans;
+  return count_flagged(flags_out, n, WFM_COV_SPANS);
 }
 
 int wfm_coverage_export(wfm_handle_t* h, wfm_coverage_t* cov, wfm_cov_entry_t** entries, size_t* n) {
@@ -1015,29 +1071,22 @@ void wfm_pav_free(wfm_pav_t* pav) {
 }
 
 int wfm_pav_add(wfm_handle_t* h, wfm_pav_t* pav, const wfm_pav_prob_t* probs, size_t n, const uint32_t* runs, size_t n_runs_total, uint32_t* flags_out) {
-  if (!h || !pav || (n && (!probs || !flags_out)) || (n_runs_total && !runs)) return WFM_E_ARG;
-  if (n == 0) return WFM_OK;
-  if (n > (size_t)INT32_MAX || n_runs_total > ((size_t)1 << 31)) { h->err = "wfm_pav_add: too many problems or runs for one call"; return WFM_E_ARG; }
-  if (int rc = pav_usable(h, pav)) return rc;
-  if (int rc = all_runs_inside(h, probs, n, n_runs_total)) return rc;
-  HIPCHK(h, hipSetDevice(h->device));
+  if (!pav) return WFM_E_ARG;
   PassTimer tm(h);
   PavProb* d_probs;
   uint32_t *d_runs, *d_flags;
   unsigned long long *d_cnt, *d_off;
   Carver cv{pav->work, "pav add"};
-  cv.piece(&d_probs, n); cv.piece(&d_runs, n_runs_total); cv.piece(&d_flags, n); cv.piece(&d_cnt, n); cv.piece(&d_off, n + 1);
-  if (int rc = cv.commit(h)) return rc;
-  HIPCHK(h, hipMemcpyAsync(d_probs, probs, n * sizeof(PavProb), hipMemcpyHostToDevice, h->stream));
-  if (n_runs_total) HIPCHK(h, hipMemcpyAsync(d_runs, runs, n_runs_total * 4, hipMemcpyHostToDevice, h->stream));
+  const int rc0 = add_preface(h, pav, pav->device, "the pav object", "wfm_pav_add", cv, probs, n, runs, n_runs_total, flags_out, &d_probs, &d_runs,
+                              [&] { cv.piece(&d_flags, n); cv.piece(&d_cnt, n); cv.piece(&d_off, n + 1); return WFM_OK; });
+  if (rc0 || !d_probs) return rc0;
   launch_pav_count(d_runs, d_probs, (int)n, pav->n_bases, pav->n_groups, d_flags, d_cnt, d_off, pav->eq_only, h->stream);
   HIPCHK(h, hipGetLastError());
   unsigned long long total = 0;
   HIPCHK(h, hipMemcpyAsync(flags_out, d_flags, n * 4, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipMemcpyAsync(&total, d_off + n, 8, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  int spans = 0;
-  for (size_t i = 0; i < n; ++i) spans += (flags_out[i] & WFM_PAV_SPANS) != 0;
+  const int spans = count_flagged(flags_out, n, WFM_PAV_SPANS);
   if (total) {
     if (int rc = pav_reserve(h, pav, pav->n + (size_t)total)) return rc;
     launch_pav_write(d_runs, d_probs, (int)n, d_flags, d_off, pav->ks() + pav->n, pav->ke() + pav->n, pav->eq_only, h->stream);
@@ -1068,18 +1117,11 @@ int wfm_pav_union(wfm_handle_t* h, wfm_pav_t* pav) {
   if (int rc = cv.commit(h)) return rc;
   unsigned end_bit = PAV_SHIFT;
   while (end_bit < 64 && ((uint64_t)pav->n_groups >> (end_bit - PAV_SHIFT)) != 0) ++end_bit;  // (keys are below n_groups << 40)
-  size_t tmp_bytes = 0;
-  HIPCHK(h, pav_sort(nullptr, &tmp_bytes, pav->ks(), ks2, pav->ke(), ke2, n, end_bit, h->stream));
-  if (pav->tmp.ensure(tmp_bytes / 8 + 2)) { h->err = "out of device memory (pav sort)"; return WFM_E_NOMEM; }
-  HIPCHK(h, pav_sort(pav->tmp.p, &tmp_bytes, pav->ks(), ks2, pav->ke(), ke2, n, end_bit, h->stream));
-  launch_pav_runmax(ke2, n, aux, h->stream);
-  HIPCHK(h, hipGetLastError());
   // (a union has no more intervals than the list has segments: the block holds it)
-  launch_pav_compact(ks2, ke2, n, aux, pav->ks(), pav->ke(), h->stream);
-  HIPCHK(h, hipGetLastError());
   unsigned long long m = 0;
-  HIPCHK(h, hipMemcpyAsync(&m, aux + nb, 8, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (int rc = interval_union(h, pav->tmp, "out of device memory (pav sort)", pav->ks(), pav->ke(), ks2, ke2, n, end_bit, aux, pav->ks(), pav->ke(), &m,
+                              [] { return (int)WFM_OK; }))
+    return rc;
   if (m > n) { h->err = "wfm_pav_union: the union has more intervals than the list had segments"; return WFM_E_HIP; }
   if (pav->c.ensure((size_t)m + 2)) { h->err = "out of device memory (pav prefix)"; return WFM_E_NOMEM; }
   launch_pav_prefix(pav->ks(), pav->ke(), m, aux, (unsigned long long*)pav->c.p, h->stream);
@@ -1216,24 +1258,6 @@ constexpr size_t SITES_MAX_VARS = ((size_t)1 << 31) - 1;
 
 int sites_usable(wfm_handle_t* h, const wfm_sites_t* s) { return DeviceGuard::usable(h, s->device, "the sites object"); }
 
-// room for `need` elements of a block that holds `have`; what it holds moves with it
-template <class T>
-int sites_reserve(wfm_handle_t* h, T** blk, size_t* cap, size_t have, size_t need, const char* what) {
-  if (need <= *cap) return WFM_OK;
-  const size_t ncap = std::max<size_t>(need + need / 2, 4096);
-  T* nb = nullptr;
-  if (wfm_dmalloc((void**)&nb, ncap * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); h->err = std::string("out of device memory (") + what + ")"; return WFM_E_NOMEM; }
-  if (have) {
-    hipError_t e = hipMemcpyAsync(nb, *blk, have * sizeof(T), hipMemcpyDeviceToDevice, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) { wfm_dfree(nb); h->err = std::string("wfm_sites: ") + hipGetErrorString(e); return WFM_E_HIP; }
-  }
-  if (*blk) wfm_dfree(*blk);
-  *blk = nb;
-  *cap = ncap;
-  return WFM_OK;
-}
-
 int sites_refuse(wfm_handle_t* h, size_t i, const std::string& why) {
   h->err = "wfm_sites_add_variants: variant " + std::to_string(i) + " " + why + "; nothing was added";
   return WFM_E_ARG;
@@ -1295,8 +1319,8 @@ int wfm_sites_add_variants(wfm_handle_t* h, wfm_sites_t* s, const wfm_site_var_t
   }
   HIPCHK(h, hipSetDevice(h->device));
   PassTimer tm(h);
-  if (int rc = sites_reserve(h, &s->vars, &s->vcap, s->n, s->n + n, "sites variants")) return rc;
-  if (int rc = sites_reserve(h, &s->alle, &s->acap, s->bytes, s->bytes + bytes, "sites alleles")) return rc;
+  if (int rc = grow_block(h, &s->vars, &s->vcap, s->n, s->n + n, "sites variants")) return rc;
+  if (int rc = grow_block(h, &s->alle, &s->acap, s->bytes, s->bytes + bytes, "sites alleles")) return rc;
   HIPCHK(h, hipMemcpyAsync(s->vars + s->n, mine.data(), n * sizeof(SiteVar), hipMemcpyHostToDevice, h->stream));
   if (bytes) {
     HIPCHK(h, hipMemcpyAsync(s->alle + s->bytes, alleles, bytes, hipMemcpyHostToDevice, h->stream));
@@ -1525,35 +1549,28 @@ void wfm_net_free(wfm_net_t* net) {
 }
 
 int wfm_net_add(wfm_handle_t* h, wfm_net_t* net, const wfm_net_prob_t* probs, size_t n, const uint32_t* runs, size_t n_runs_total, uint32_t* flags_out) {
-  if (!h || !net || (n && (!probs || !flags_out)) || (n_runs_total && !runs)) return WFM_E_ARG;
-  if (n == 0) return WFM_OK;
-  if (n > (size_t)INT32_MAX || n_runs_total > ((size_t)1 << 31)) { h->err = "wfm_net_add: too many problems or runs for one call"; return WFM_E_ARG; }
-  if (int rc = net_usable(h, net)) return rc;
-  if (int rc = all_runs_inside(h, probs, n, n_runs_total)) return rc;
-  HIPCHK(h, hipSetDevice(h->device));
+  if (!net) return WFM_E_ARG;
   PassTimer tm(h);
   NetProb* d_probs;
   uint32_t *d_runs, *d_flags, *d_score;
   unsigned long long *d_word, *d_off;
   Carver cv{net->work, "net add"};
-  cv.piece(&d_probs, n); cv.piece(&d_runs, n_runs_total); cv.piece(&d_flags, n); cv.piece(&d_score, n); cv.piece(&d_word, n); cv.piece(&d_off, n + 1);
-  if (int rc = cv.commit(h)) return rc;
-  HIPCHK(h, hipMemcpyAsync(d_probs, probs, n * sizeof(NetProb), hipMemcpyHostToDevice, h->stream));
-  if (n_runs_total) HIPCHK(h, hipMemcpyAsync(d_runs, runs, n_runs_total * 4, hipMemcpyHostToDevice, h->stream));
+  const int rc0 = add_preface(h, net, net->device, "the net object", "wfm_net_add", cv, probs, n, runs, n_runs_total, flags_out, &d_probs, &d_runs,
+                              [&] { cv.piece(&d_flags, n); cv.piece(&d_score, n); cv.piece(&d_word, n); cv.piece(&d_off, n + 1); return WFM_OK; });
+  if (rc0 || !d_probs) return rc0;
   launch_net_count(d_runs, d_probs, (int)n, net->n_bases, d_flags, d_word, d_off, d_score, h->stream);
   HIPCHK(h, hipGetLastError());
   unsigned long long total = 0;
   HIPCHK(h, hipMemcpyAsync(flags_out, d_flags, n * 4, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipMemcpyAsync(&total, d_off + n, 8, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  int spans = 0;
-  for (size_t i = 0; i < n; ++i) spans += (flags_out[i] & WFM_NET_SPANS) != 0;
+  const int spans = count_flagged(flags_out, n, WFM_NET_SPANS);
   const size_t add_r = (size_t)(total >> 32), add_b = (size_t)(total & 0xffffffffull);
   if (add_r != n - (size_t)spans) { h->err = "wfm_net_add: the records do not add up"; return WFM_E_INTERNAL; }
   if (add_r) {
     if (add_b > NET_MAX - net->n || add_r > NET_MAX - net->r) { h->err = "wfm_net_add: more than 2^31 - 1 blocks or records in one object; nothing was added"; return WFM_E_ARG; }
-    if (int rc = sites_reserve(h, &net->blocks, &net->bcap, net->n, net->n + add_b, "net blocks")) return rc;
-    if (int rc = sites_reserve(h, &net->recs, &net->rcap, net->r, net->r + add_r, "net records")) return rc;
+    if (int rc = grow_block(h, &net->blocks, &net->bcap, net->n, net->n + add_b, "net blocks")) return rc;
+    if (int rc = grow_block(h, &net->recs, &net->rcap, net->r, net->r + add_r, "net records")) return rc;
     launch_net_write(d_runs, d_probs, (int)n, d_flags, d_off, d_score, net->blocks + net->n, net->recs + net->r, h->stream);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1754,8 +1771,8 @@ int wfm_net_import(wfm_handle_t* h, wfm_net_t* net, const wfm_net_block_t* block
     }
   }
   HIPCHK(h, hipSetDevice(h->device));
-  if (int rc = sites_reserve(h, &net->blocks, &net->bcap, net->n, net->n + n_blocks, "net blocks")) return rc;
-  if (int rc = sites_reserve(h, &net->recs, &net->rcap, net->r, net->r + n_recs, "net records")) return rc;
+  if (int rc = grow_block(h, &net->blocks, &net->bcap, net->n, net->n + n_blocks, "net blocks")) return rc;
+  if (int rc = grow_block(h, &net->recs, &net->rcap, net->r, net->r + n_recs, "net records")) return rc;
   std::vector<NetRec> mine(n_recs);
   for (size_t i = 0; i < n_recs; ++i) mine[i] = NetRec{recs[i].order, recs[i].score, 0u};
   if (n_blocks) HIPCHK(h, hipMemcpyAsync(net->blocks + net->n, blocks, n_blocks * sizeof(NetBlock), hipMemcpyHostToDevice, h->stream));
@@ -1815,8 +1832,8 @@ int trans_reserve(wfm_handle_t* h, wfm_trans_t* obj, const char* who, size_t add
     h->err = msg;
     return WFM_E_NOMEM;
   }
-  if (int rc = sites_reserve(h, &obj->pre, &obj->pcap, obj->np, obj->np + add_words, "transitive prefix words")) return rc;
-  return sites_reserve(h, &obj->arcs, &obj->acap, obj->na, obj->na + 2 * add_recs, "transitive arcs");
+  if (int rc = grow_block(h, &obj->pre, &obj->pcap, obj->np, obj->np + add_words, "transitive prefix words")) return rc;
+  return grow_block(h, &obj->arcs, &obj->acap, obj->na, obj->na + 2 * add_recs, "transitive arcs");
 }
 
 // the two arcs of a record whose words begin at `at` of the object's block
@@ -1865,21 +1882,15 @@ int trans_union(wfm_handle_t* h, wfm_trans_t* obj, size_t* m, size_t c, unsigned
   HIPCHK(h, hipMemcpyAsync(rke, obj->acc.p + *m, *m * 8, hipMemcpyDeviceToDevice, h->stream));
   launch(rks + *m, rke + *m);
   HIPCHK(h, hipGetLastError());
-  size_t tmp_bytes = 0;
-  HIPCHK(h, pav_sort(nullptr, &tmp_bytes, rks, sks, rke, ske, n, end_bit, h->stream));
-  if (obj->tmp.ensure(tmp_bytes / 8 + 2)) { h->err = "out of device memory (transitive sort)"; return WFM_E_NOMEM; }
-  HIPCHK(h, pav_sort(obj->tmp.p, &tmp_bytes, rks, sks, rke, ske, n, end_bit, h->stream));
-  launch_pav_runmax(ske, n, aux, h->stream);
-  HIPCHK(h, hipGetLastError());
-  // (acc's intervals are in the raw copy: the block may be replaced.  A union has no more intervals than the list has segments)
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (obj->acc.ensure(2 * n)) { h->err = "out of device memory (transitive list)"; return WFM_E_NOMEM; }
-  // (the end keys follow the start keys at the union's own length, which is known only now: compact to the raw copy, then move)
-  launch_pav_compact(sks, ske, n, aux, rks, rke, h->stream);
-  HIPCHK(h, hipGetLastError());
+  // (the end keys follow the start keys at the union's own length, which is known only behind the compaction: compact to the raw copy, then move)
   unsigned long long u = 0;
-  HIPCHK(h, hipMemcpyAsync(&u, aux + nb, 8, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  const int rc = interval_union(h, obj->tmp, "out of device memory (transitive sort)", rks, rke, sks, ske, n, end_bit, aux, rks, rke, &u, [&] {
+    // (acc's intervals are in the raw copy: the block may be replaced.  A union has no more intervals than the list has segments)
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (obj->acc.ensure(2 * n)) { h->err = "out of device memory (transitive list)"; return (int)WFM_E_NOMEM; }
+    return (int)WFM_OK;
+  });
+  if (rc != WFM_OK) return rc;
   if (u == 0 || u > n) { h->err = "wfm_trans_closure: the union does not add up"; return WFM_E_INTERNAL; }
   HIPCHK(h, hipMemcpyAsync(obj->acc.p, rks, (size_t)u * 8, hipMemcpyDeviceToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(obj->acc.p + u, rke, (size_t)u * 8, hipMemcpyDeviceToDevice, h->stream));
@@ -1929,27 +1940,23 @@ void wfm_trans_free(wfm_trans_t* obj) {
 }
 
 int wfm_trans_add(wfm_handle_t* h, wfm_trans_t* obj, const wfm_trans_prob_t* probs, size_t n, const uint32_t* runs, size_t n_runs_total, uint32_t* flags_out) {
-  if (!h || !obj || (n && (!probs || !flags_out)) || (n_runs_total && !runs)) return WFM_E_ARG;
-  if (n == 0) return WFM_OK;
-  if (n > (size_t)INT32_MAX || n_runs_total > ((size_t)1 << 31)) { h->err = "wfm_trans_add: too many problems or runs for one call"; return WFM_E_ARG; }
-  if (int rc = trans_usable(h, obj)) return rc;
-  if (int rc = all_runs_inside(h, probs, n, n_runs_total)) return rc;
-  for (size_t i = 0; i < n; ++i)
-    if (probs[i].flags & ~WFM_TRANS_REVERSE) {
-      h->err = "problem " + std::to_string(i) + ": flags " + std::to_string(probs[i].flags) + " hold a bit that is not WFM_TRANS_REVERSE";
-      return WFM_E_ARG;
-    }
-  HIPCHK(h, hipSetDevice(h->device));
+  if (!h || !obj) return WFM_E_ARG;
   PassTimer tm(h);
   TransProb* d_probs;
   TransSpan* d_span;
   unsigned long long* d_at;
   uint32_t* d_runs;
   Carver cv{h->scratch, "transitive add"};
-  cv.piece(&d_probs, n); cv.piece(&d_span, n); cv.piece(&d_at, n); cv.piece(&d_runs, n_runs_total);
-  if (int rc = cv.commit(h)) return rc;
-  HIPCHK(h, hipMemcpyAsync(d_probs, probs, n * sizeof(TransProb), hipMemcpyHostToDevice, h->stream));
-  if (n_runs_total) HIPCHK(h, hipMemcpyAsync(d_runs, runs, n_runs_total * 4, hipMemcpyHostToDevice, h->stream));
+  const int rc0 = add_preface(h, obj, obj->device, "the trans object", "wfm_trans_add", cv, probs, n, runs, n_runs_total, flags_out, &d_probs, &d_runs, [&] {
+    for (size_t i = 0; i < n; ++i)
+      if (probs[i].flags & ~WFM_TRANS_REVERSE) {
+        h->err = "problem " + std::to_string(i) + ": flags " + std::to_string(probs[i].flags) + " hold a bit that is not WFM_TRANS_REVERSE";
+        return (int)WFM_E_ARG;
+      }
+    cv.piece(&d_span, n); cv.piece(&d_at, n);
+    return (int)WFM_OK;
+  });
+  if (rc0 || !d_probs) return rc0;
   launch_trans_span(d_runs, d_probs, (int)n, obj->n_bases, d_span, h->stream);
   HIPCHK(h, hipGetLastError());
   std::vector<TransSpan> span(n);

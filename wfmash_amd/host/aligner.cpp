@@ -385,12 +385,9 @@ std::string Aligner::gather_text(Summary& sum, const std::vector<Fetched>& fetch
   return out;
 }
 
-std::string Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<std::string>& lines, int threads, Summary& sum, uint64_t first_row,
-                                 std::string* vcf, wfm_coverage_t* coverage, const std::vector<uint64_t>* seq_offsets, std::string* lift,
-                                 const wfm_liftset_t* liftset, const std::vector<lift::Interval>* lift_intervals, wfm_pav_t* pav,
-                                 const std::vector<uint32_t>* pav_columns, std::string* chain, bool chain_swap, wfm_sites_t* sites,
-                                 uint32_t sites_groups, wfm_net_t* net, uint64_t net_batch, std::vector<wflign::NetHead>* net_heads, wfm_trans_t* trans,
-                                 const std::vector<uint64_t>* query_world) {
+wflign::BatchTexts Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<std::string>& lines, int threads, Summary& sum, uint64_t first_row,
+                                        const wflign::BatchPasses& passes) {
+  wflign::BatchTexts texts;
   const bool dbg = getenv("WFM_DEBUG") != nullptr;
   BatchTimes t;
   std::vector<Fetched> rows = parse_rows(lines, first_row, sum);
@@ -398,17 +395,16 @@ std::string Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<std::stri
   DeviceStore* ds = param.resident_sequences ? device_store(gpu_handle) : nullptr;
   if (ds) assign_resident_ids(gpu_handle, *ds, rows);
   std::vector<Fetched> fetched = fetch_eager(rows, threads, sum);
-  if (fetched.empty()) return std::string();
+  if (fetched.empty()) return texts;
   std::vector<wflign::BiwfaRecord> recs = make_records(fetched);
-  if (coverage || liftset || pav || sites || net || trans)
-    for (wflign::BiwfaRecord& r : recs) r.target_global = (*seq_offsets)[(size_t)ref->find(r.target_name)];  // (parse_rows has found every name)
-  if (pav || sites)
+  if (const wflign::RunTables* tb = passes.tables)  // (parse_rows has found every name)
     for (wflign::BiwfaRecord& r : recs) {
+      r.target_global = tb->seq_offsets[(size_t)ref->find(r.target_name)];
+      if (tb->columns.of_seq.empty() && tb->query_world.empty()) continue;
       const int qi = query->find(r.query_name);
-      r.pav_group = qi >= 0 ? (*pav_columns)[(size_t)qi] : 0xffffffffu;  // (no column: the device flags the record and adds nothing)
+      if (!tb->columns.of_seq.empty()) r.pav_group = qi >= 0 ? tb->columns.of_seq[(size_t)qi] : 0xffffffffu;  // (no column: the device flags the record and adds nothing)
+      if (!tb->query_world.empty()) r.query_global = tb->query_world[(size_t)qi];
     }
-  if (trans)
-    for (wflign::BiwfaRecord& r : recs) r.query_global = (*query_world)[(size_t)query->find(r.query_name)];  // (parse_rows has found every name)
   wflign::ResidentSeqs resident;
   if (ds) {
     resident.store = ds->store;
@@ -424,30 +420,14 @@ std::string Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<std::stri
   }
   t.fetch = t.lap();
   wflign::BiwfaStats st;
-  wflign::OutputFormat fmt = format_of(param, threads);
-  fmt.coverage = coverage;
-  fmt.pav = pav;
-  fmt.sites = sites;
-  fmt.sites_groups = sites_groups;
-  fmt.liftset = liftset;
-  fmt.lift_intervals = lift_intervals;
-  fmt.chain = chain ? (chain_swap ? 2 : 1) : 0;
-  fmt.net = net;
-  fmt.net_batch = net_batch;
-  fmt.net_heads = net_heads;
-  fmt.trans = trans;
   const int rc = wflign::do_biwfa_alignment_batch(gpu_handle, recs, penalties_of(param), param.disable_chain_patching, filters_of(param), &st,
-                                                  fmt, ds ? &resident : nullptr);
+                                                  format_of(param, threads), ds ? &resident : nullptr, &passes, &texts);
   if (rc < 0) throw std::runtime_error(std::string("[wfmash::align] GPU alignment failed: ") + st.error);
   account(sum, st, resident, fetched, recs);
   t.wflign = t.lap();
-  std::string out = gather_text(sum, fetched, recs);
-  if (vcf)
-    for (const auto& r : recs) *vcf += r.vcf;  // (a record without a line has no VCF lines: write_record)
-  if (lift)
-    for (const auto& r : recs) *lift += r.lift;  // (in the order of the records' lines: gather_text's)
-  if (chain)
-    for (const auto& r : recs) *chain += r.chain;  // (likewise; the ids are the writer's)
+  std::string& out = texts.paf = gather_text(sum, fetched, recs);
+  // (a record without a line has no VCF lines, write_record; lift lines and chains come in the order of the records' lines, and the chains' ids are the writer's)
+  for (const auto& r : recs) { texts.text[wflign::SW_VARIANTS] += r.vcf; texts.text[wflign::SW_LIFT] += r.lift; texts.text[wflign::SW_CHAIN] += r.chain; }
   t.text = t.lap();
   if (verify::enabled() && !param.sam_format) {  // --verify: the finished lines, before they are written (SAM records carry no =/X CIGAR)
     verify::Source src;
@@ -465,7 +445,7 @@ std::string Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<std::stri
   if (dbg)
     fprintf(stderr, "[wfmash::align] batch of %zu records on %d threads: rows %.1f ms, fetch %.1f ms, wflign %.1f ms (device busy %.1f), text %.1f ms\n",
             recs.size(), threads, t.rows, t.fetch, t.wflign, st.ms_gpu, t.text);
-  return out;
+  return texts;
 }
 
 std::string Aligner::align_lines(const std::vector<std::string>& lines, Summary& sum) {
@@ -479,7 +459,7 @@ std::string Aligner::align_lines(const std::vector<std::string>& lines, Summary&
       batch.push_back(lines[i++]);
     }
     const uint64_t first_row = i - batch.size();
-    out += align_batch(gpus.front(), batch, param.threads, sum, first_row);
+    out += align_batch(gpus.front(), batch, param.threads, sum, first_row).paf;
   }
   return out;
 }
@@ -536,24 +516,383 @@ class HandlePool {
   std::map<int, std::vector<std::pair<wfm_handle_t*, bool>>> by_device_;  // handle, in use
 };
 
-// the ordered writer's sink: the output file, flushed once per put
+// the ordered writer's sink: the output file, flushed once per put.  number (--chain): the chains of a batch come without their ids; the
+// writer numbers them 1, 2, 3 ... as it writes them, in file order
 struct TextSink {
   std::ofstream* out;
-  void write(std::string& text) { *out << text; }
-  void flush() { out->flush(); }
-};
-// --chain: the chains of a batch come without their ids; the writer numbers them 1, 2, 3 ... as it writes them, in file order
-struct ChainSink {
-  std::ofstream* out;
+  bool number = false;
   uint64_t next = 1;
   std::string numbered;
   void write(std::string& text) {
+    if (!number) { *out << text; return; }
     numbered.clear();
     chain::number(text, &next, numbered);
     *out << numbered;
   }
   void flush() { out->flush(); }
 };
+using TextWriter = skch::OrderedWriter<std::string, TextSink>;
+
+// what: "output file", "the BED file of --lift", ...
+template <class Stream>
+void open_or_throw(Stream& s, const std::string& path, const char* what, std::ios::openmode mode = std::ios::openmode()) {
+  s.open(path, mode);
+  if (!s.is_open()) throw std::runtime_error(std::string("[wfmash::align] Error! Failed to open ") + what + ": " + path);
+}
+std::string read_whole_file(const std::string& path, const char* what) {
+  std::ifstream f;
+  open_or_throw(f, path, what, std::ios::binary);
+  return std::string((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+}
+std::vector<wfm_lift_iv_t> raw_intervals(const std::vector<lift::Interval>& iv) {
+  std::vector<wfm_lift_iv_t> raw(iv.size());
+  for (size_t i = 0; i < raw.size(); ++i) raw[i] = wfm_lift_iv_t{iv[i].gstart, iv[i].gend};
+  return raw;
+}
+
+// One pass of a run: a switch that is on, and the file it writes -- per batch through an ordered writer keyed by the batches' numbers
+// (--variants, --lift, --chain), or once the workers are done (finish: the others).  A pass with a device object keeps one per handle
+// the run has used so far, made at the handle's first batch; finish merges them into the first handle's.  A pass's constructor reads what
+// it needs before anything is aligned and adds to the run's tables what its stage looks up per record.
+struct Pass {
+  Pass(wflign::SwitchId i, const char* t, bool with_object, wflign::RunTables& tb, const std::string& path, const char* what)
+      : id(i), tag(t), per_handle(with_object), tables(tb) {
+    open_or_throw(out, path, what);
+  }
+  virtual ~Pass() {}
+  const wflign::SwitchId id;
+  const std::string tag;  // "--pav": of the messages
+  const bool per_handle;
+  wflign::RunTables& tables;
+  std::ofstream out;
+  std::unique_ptr<TextWriter> writer;
+  std::mutex mu;  // of objects (and of what a pass gathers from the batches)
+  std::vector<std::pair<wfm_handle_t*, void*>> objects;
+
+  void* object_of(wfm_handle_t* h) {
+    if (!per_handle) return nullptr;
+    std::lock_guard<std::mutex> lk(mu);
+    for (auto& ho : objects) if (ho.first == h) return ho.second;
+    void* o = nullptr;
+    std::lock_guard<std::mutex> hl(wflign::handle_lock(h));
+    if (create(h, &o) != WFM_OK) throw std::runtime_error("[wfmash::align] " + tag + ": " + wfm_last_error(h));
+    objects.emplace_back(h, o);
+    return o;
+  }
+  void free_objects() {
+    for (auto& ho : objects) {
+      std::lock_guard<std::mutex> lk(wflign::handle_lock(ho.first));
+      destroy(ho.second);
+    }
+    objects.clear();
+  }
+  // the batch's share: its text to the ordered writer
+  virtual void take(uint64_t seq, wflign::BatchTexts& t) { if (writer) writer->put(seq, std::move(t.text[id])); }
+  virtual void finish() {}
+
+ protected:
+  virtual int create(wfm_handle_t*, void**) { return WFM_OK; }
+  virtual void destroy(void*) {}
+  // the lists of an object (kept by the pass between the two), into another, freed
+  virtual int export_lists(wfm_handle_t*, void*) { return WFM_OK; }
+  virtual int import_lists(wfm_handle_t*, void*) { return WFM_OK; }
+  virtual void free_lists() {}
+
+  wfm_handle_t* h0() const { return objects.front().first; }
+  template <class T>
+  T* first() const { return static_cast<T*>(objects.front().second); }
+  [[noreturn]] void fail(wfm_handle_t* h, const char* what) const { throw std::runtime_error("[wfmash::align] " + tag + ": " + what + ": " + wfm_last_error(h)); }
+  // every other handle's object exported and imported into the first's (integer adds, unions and set functions: the order does not matter)
+  void merge() {
+    for (size_t k = 1; k < objects.size(); ++k) {
+      {
+        std::lock_guard<std::mutex> lk(wflign::handle_lock(objects[k].first));
+        if (export_lists(objects[k].first, objects[k].second) != WFM_OK) fail(objects[k].first, "export");
+      }
+      std::lock_guard<std::mutex> lk(wflign::handle_lock(h0()));
+      const int rc = import_lists(h0(), objects.front().second);
+      free_lists();
+      if (rc != WFM_OK) fail(h0(), "import");
+    }
+  }
+  void writes_per_batch(bool number = false) { writer.reset(new TextWriter(TextSink{&out, number})); }
+};
+
+// --variants: the header here, the batches' lines through the ordered writer
+struct VariantsPass : Pass {
+  VariantsPass(wflign::RunTables& tb, const wflign::SwitchSetting& s) : Pass(wflign::SW_VARIANTS, "--variants", false, tb, s.out, "the variants file") {
+    out << "##fileformat=VCFv4.2\n##source=wfmash-hip " WFMASH_HIP_VERSION "\n";
+    for (size_t i = 0; i < tb.tnames.size(); ++i) out << "##contig=<ID=" << tb.tnames[i] << ",length=" << tb.tlengths[i] << ">\n";
+    out << "##INFO=<ID=QNAME,Number=1,Type=String,Description=\"Query sequence name\">\n"
+           "##INFO=<ID=QSTART,Number=1,Type=Integer,Description=\"Start of the query bases in ALT, 0-based, forward strand\">\n"
+           "##INFO=<ID=QEND,Number=1,Type=Integer,Description=\"End of the query bases in ALT, exclusive, forward strand\">\n"
+           "##INFO=<ID=QSTRAND,Number=1,Type=String,Description=\"Strand of the query in the alignment\">\n"
+           "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n";
+    writes_per_batch();
+  }
+};
+
+// --coverage: the depth objects; the intervals of their sum taken once on the device, the file through coverage_bedgraph
+struct CoveragePass : Pass {
+  CoveragePass(wflign::RunTables& tb, const wflign::SwitchSetting& s) : Pass(wflign::SW_COVERAGE, "--coverage", true, tb, s.out, "the coverage file") {}
+  wfm_cov_entry_t* list = nullptr;
+  size_t n_list = 0;
+  int create(wfm_handle_t* h, void** o) override {
+    wfm_coverage_t* c = nullptr;
+    const int rc = wfm_coverage_create(h, tables.seq_offsets.back(), &c);
+    *o = c;
+    return rc;
+  }
+  void destroy(void* o) override { wfm_coverage_free((wfm_coverage_t*)o); }
+  int export_lists(wfm_handle_t* h, void* o) override { return wfm_coverage_export(h, (wfm_coverage_t*)o, &list, &n_list); }
+  int import_lists(wfm_handle_t* h, void* o) override { return wfm_coverage_import(h, (wfm_coverage_t*)o, list, n_list); }
+  void free_lists() override { wfm_coverage_free_list(list); }
+  void finish() override {
+    const auto t0 = Clock::now();
+    merge();
+    wfm_cov_interval_t* iv = nullptr;
+    size_t n = 0;
+    uint64_t totals[3] = {0, 0, 0};
+    if (!objects.empty()) {
+      std::lock_guard<std::mutex> lk(wflign::handle_lock(h0()));
+      if (wfm_coverage_intervals(h0(), first<wfm_coverage_t>(), &iv, &n, totals) != WFM_OK) fail(h0(), "intervals");
+    }
+    uint64_t lines = 0;
+    out << coverage::coverage_bedgraph(tables.tnames, tables.tlengths, iv, n, &lines);
+    wfm_coverage_free_list(iv);
+    wflign::switch_finished(id, totals[0], totals[1], lines);
+    if (getenv("WFM_DEBUG"))
+      fprintf(stderr, "[wfmash::align] coverage: %zu objects merged, %zu intervals, %llu lines, %.1f ms\n", objects.size(), n, (unsigned long long)lines, ms_since(t0));
+  }
+};
+
+// --lift: the BED is read once, here, its intervals sorted as the device takes them; a liftset per handle; the batches' lines through the
+// ordered writer
+struct LiftPass : Pass {
+  LiftPass(wflign::RunTables& tb, const wflign::SwitchSetting& s) : Pass(wflign::SW_LIFT, "--lift", true, tb, s.out, "the lift file") {
+    lift::Bed parsed = lift::parse_bed(read_whole_file(s.bed, "the BED file of --lift"), tb.find_target, tb.tlengths, tb.seq_offsets);
+    tb.lift_iv = std::move(parsed.iv);
+    wflign::switch_finished(id, 0, 0, parsed.skipped);
+    writes_per_batch();
+  }
+  int create(wfm_handle_t* h, void** o) override {
+    const std::vector<wfm_lift_iv_t> raw = raw_intervals(tables.lift_iv);
+    wfm_liftset_t* set = nullptr;
+    const int rc = wfm_liftset_create(h, raw.data(), raw.size(), tables.seq_offsets.back(), &set);
+    *o = set;
+    return rc;
+  }
+  void destroy(void* o) override { wfm_liftset_free((wfm_liftset_t*)o); }
+};
+
+// --chain: the batches' chains through the ordered writer, which numbers them
+struct ChainPass : Pass {
+  ChainPass(wflign::RunTables& tb, const wflign::SwitchSetting& s) : Pass(wflign::SW_CHAIN, "--chain", false, tb, s.out, "the chain file") {
+    tb.chain_swap = s.option != 0;
+    writes_per_batch(true);
+  }
+};
+
+// --pav: the intervals of the table in the file's order and the columns are known before anything is aligned; the presence objects; the
+// table of their union taken once on the device, the file through pav_text.hpp
+struct PavPass : Pass {
+  PavPass(wflign::RunTables& tb, const wflign::SwitchSetting& s) : Pass(wflign::SW_PAV, "--pav", true, tb, s.out, "the pav file") {
+    if (!s.bed.empty()) {
+      lift::Bed parsed = lift::parse_bed(read_whole_file(s.bed, "the BED file of --pav"), tb.find_target, tb.tlengths, tb.seq_offsets);
+      iv = std::move(parsed.iv);
+      bed_skipped = parsed.skipped;
+    } else {
+      iv = pav::windows(tb.tlengths, tb.seq_offsets, s.option);
+    }
+    if (tb.columns.of_seq.empty()) tb.columns = pav::columns(tb.qnames);
+  }
+  std::vector<lift::Interval> iv;
+  uint64_t bed_skipped = 0;
+  wfm_pav_seg_t* list = nullptr;
+  size_t n_list = 0;
+  int create(wfm_handle_t* h, void** o) override {
+    wfm_pav_t* p = nullptr;
+    const int rc = wfm_pav_create(h, tables.seq_offsets.back(), (uint32_t)tables.columns.keys.size(), &p);
+    *o = p;
+    return rc;
+  }
+  void destroy(void* o) override { wfm_pav_free((wfm_pav_t*)o); }
+  int export_lists(wfm_handle_t* h, void* o) override { return wfm_pav_export(h, (wfm_pav_t*)o, &list, &n_list); }
+  int import_lists(wfm_handle_t* h, void* o) override { return wfm_pav_import(h, (wfm_pav_t*)o, list, n_list); }
+  void free_lists() override { wfm_pav_free_list(list); }
+  void finish() override {
+    const auto t0 = Clock::now();
+    const size_t G = tables.columns.keys.size();
+    std::vector<uint32_t> cells(G * iv.size(), 0u);
+    uint64_t counts[3] = {0, 0, 0};
+    merge();
+    if (!objects.empty()) {
+      const std::vector<wfm_lift_iv_t> raw = raw_intervals(iv);
+      std::lock_guard<std::mutex> lk(wflign::handle_lock(h0()));
+      if (wfm_pav_matrix(h0(), first<wfm_pav_t>(), raw.data(), raw.size(), cells.data()) != WFM_OK) fail(h0(), "matrix");
+      wfm_pav_counts(first<wfm_pav_t>(), counts);
+    }
+    const auto t1 = Clock::now();
+    pav::table(out, tables.columns.keys, tables.tnames, iv, cells.data());
+    wflign::switch_finished(id, iv.size(), counts[1], bed_skipped);
+    if (getenv("WFM_DEBUG"))
+      fprintf(stderr, "[wfmash::align] pav: %zu objects merged, %llu segments added, %llu union intervals, %zu rows x %zu groups, merge + union + matrix %.1f ms, text %.1f ms\n",
+              objects.size(), (unsigned long long)counts[0], (unsigned long long)counts[1], iv.size(), G, std::chrono::duration<double, std::milli>(t1 - t0).count(), ms_since(t1));
+  }
+};
+
+// --genotypes: the columns are --pav's; the sites objects; the table of their merge taken once on the device, the file through
+// genotype_text.hpp
+struct GenotypesPass : Pass {
+  GenotypesPass(wflign::RunTables& tb, const wflign::SwitchSetting& s) : Pass(wflign::SW_GENOTYPES, "--genotypes", true, tb, s.out, "the genotypes file") {
+    if (tb.columns.of_seq.empty()) tb.columns = pav::columns(tb.qnames);
+  }
+  wfm_site_var_t* vars = nullptr;
+  char* alleles = nullptr;
+  wfm_pav_seg_t* segs = nullptr;
+  size_t n_vars = 0, n_bytes = 0, n_segs = 0;
+  int create(wfm_handle_t* h, void** o) override {
+    wfm_sites_t* p = nullptr;
+    const int rc = wfm_sites_create(h, tables.seq_offsets.back(), (uint32_t)tables.columns.keys.size(), &p);
+    *o = p;
+    return rc;
+  }
+  void destroy(void* o) override { wfm_sites_free((wfm_sites_t*)o); }
+  int export_lists(wfm_handle_t* h, void* o) override { return wfm_sites_export(h, (wfm_sites_t*)o, &vars, &n_vars, &alleles, &n_bytes, &segs, &n_segs); }
+  int import_lists(wfm_handle_t* h, void* o) override { return wfm_sites_import(h, (wfm_sites_t*)o, vars, n_vars, alleles, n_bytes, segs, n_segs); }
+  void free_lists() override { wfm_sites_free_list(vars); wfm_sites_free_list(alleles); wfm_sites_free_list(segs); }
+  void finish() override {
+    const auto t0 = Clock::now();
+    wfm_site_t* rows = nullptr;
+    char *table_alleles = nullptr, *gt = nullptr;
+    size_t n_sites = 0, bytes = 0;
+    uint64_t counts[4] = {0, 0, 0, 0};
+    merge();
+    if (!objects.empty()) {
+      std::lock_guard<std::mutex> lk(wflign::handle_lock(h0()));
+      if (wfm_sites_table(h0(), first<wfm_sites_t>(), &rows, &n_sites, &table_alleles, &bytes, &gt) != WFM_OK) fail(h0(), "table");
+      wfm_sites_counts(first<wfm_sites_t>(), counts);
+    }
+    const auto t1 = Clock::now();
+    genotype::vcf(out, WFMASH_HIP_VERSION, tables.tnames, tables.tlengths, tables.seq_offsets, tables.columns.keys, rows, n_sites, table_alleles, gt);
+    wfm_sites_free_list(rows); wfm_sites_free_list(table_alleles); wfm_sites_free_list(gt);
+    wflign::switch_finished(id, n_sites, counts[0] - n_sites, 0);
+    if (getenv("WFM_DEBUG"))
+      fprintf(stderr, "[wfmash::align] genotypes: %zu objects merged, %llu variants, %zu sites x %zu groups, %llu = intervals, merge + table %.1f ms, text %.1f ms\n",
+              objects.size(), (unsigned long long)counts[0], n_sites, tables.columns.keys.size(), (unsigned long long)counts[2],
+              std::chrono::duration<double, std::milli>(t1 - t0).count(), ms_since(t1));
+  }
+};
+
+// --chain-net: the net objects, and what the chains' headers need of every record added, in no order; the table of the merged object
+// taken once on the device, the file through chain_text.hpp's net_file in the order of the orders, which is the order of the PAF's records
+struct ChainNetPass : Pass {
+  ChainNetPass(wflign::RunTables& tb, const wflign::SwitchSetting& s) : Pass(wflign::SW_CHAIN_NET, "--chain-net", true, tb, s.out, "the chain-net file") {}
+  std::vector<wflign::NetHead> heads;  // (under mu)
+  wfm_net_block_t* blocks = nullptr;
+  wfm_net_rec_t* recs = nullptr;
+  size_t n_blocks = 0, n_recs = 0;
+  void take(uint64_t, wflign::BatchTexts& t) override {
+    if (t.net_heads.empty()) return;
+    std::lock_guard<std::mutex> lk(mu);
+    for (auto& hd : t.net_heads) heads.push_back(std::move(hd));
+  }
+  int create(wfm_handle_t* h, void** o) override {
+    wfm_net_t* p = nullptr;
+    const int rc = wfm_net_create(h, tables.seq_offsets.back(), &p);
+    *o = p;
+    return rc;
+  }
+  void destroy(void* o) override { wfm_net_free((wfm_net_t*)o); }
+  int export_lists(wfm_handle_t* h, void* o) override { return wfm_net_export(h, (wfm_net_t*)o, &blocks, &n_blocks, &recs, &n_recs); }
+  int import_lists(wfm_handle_t* h, void* o) override { return wfm_net_import(h, (wfm_net_t*)o, blocks, n_blocks, recs, n_recs); }
+  void free_lists() override { wfm_net_free_list(blocks); wfm_net_free_list(recs); }
+  void finish() override {
+    const auto t0 = Clock::now();
+    wfm_net_piece_t* pieces = nullptr;
+    wfm_netcall_t* per = nullptr;
+    size_t n_pieces = 0, n_rec = 0;
+    uint64_t counts[6] = {0, 0, 0, 0, 0, 0};
+    merge();
+    if (!objects.empty()) {
+      std::lock_guard<std::mutex> lk(wflign::handle_lock(h0()));
+      if (wfm_net_table(h0(), first<wfm_net_t>(), &pieces, &n_pieces, &per, &n_rec) != WFM_OK) fail(h0(), "table");
+      wfm_net_counts(first<wfm_net_t>(), counts);
+    }
+    const auto t1 = Clock::now();
+    static_assert(sizeof(chain::Piece) == sizeof(wfm_net_piece_t) && sizeof(chain::NetCall) == sizeof(wfm_netcall_t), "chain_text.hpp restates wfm_net_piece_t and wfm_netcall_t");
+    std::sort(heads.begin(), heads.end(), [](const wflign::NetHead& a, const wflign::NetHead& b) { return a.order < b.order; });
+    uint64_t chains = 0, lost = 0;
+    const bool same = chain::net_file(out, heads, (const chain::NetCall*)per, n_rec, (const chain::Piece*)pieces, &chains, &lost);
+    wfm_net_free_list(pieces); wfm_net_free_list(per);
+    if (!same) throw std::runtime_error("[wfmash::align] --chain-net: the table's records are not the records added");
+    wflign::switch_finished(id, chains, n_pieces, lost);
+    if (getenv("WFM_DEBUG"))
+      fprintf(stderr, "[wfmash::align] chain-net: %zu objects merged, %llu records, %llu blocks, %llu elementary intervals, %zu pieces, %llu chains, %llu records won nothing, merge + table %.1f ms, text %.1f ms\n",
+              objects.size(), (unsigned long long)counts[0], (unsigned long long)counts[1], (unsigned long long)counts[2], n_pieces, (unsigned long long)chains,
+              (unsigned long long)lost, std::chrono::duration<double, std::milli>(t1 - t0).count(), ms_since(t1));
+  }
+};
+
+// --transitive: the world and the seeds in input order are known before anything is aligned; the trans objects; the closure of the seeds
+// over their merge taken once on the device, the file through transitive_text.hpp in the order of the BED's lines
+struct TransitivePass : Pass {
+  TransitivePass(wflign::RunTables& tb, const wflign::SwitchSetting& s)
+      : Pass(wflign::SW_TRANSITIVE, "--transitive", true, tb, s.out, "the transitive file"), depth((uint32_t)s.option) {
+    world = transitive::make_world(tb.tnames, tb.tlengths, tb.qnames, tb.qlengths);
+    if (world.n_bases() >= ((uint64_t)1 << 40)) throw std::runtime_error("[wfmash::align] --transitive: the sequences hold 2^40 bases or more");
+    for (const std::string& name : tb.qnames) tb.query_world.push_back(world.offsets[(size_t)world.find(name)]);
+    seeds = transitive::parse_seeds(read_whole_file(s.bed, "the BED file of --transitive"), world);
+    if (seeds.iv.size() >= ((size_t)1 << 24)) throw std::runtime_error("[wfmash::align] --transitive: the BED holds 2^24 seeds or more");
+  }
+  transitive::World world;
+  lift::Bed seeds;
+  const uint32_t depth;
+  wfm_trans_rec_t* recs = nullptr;
+  wfm_trans_word_t* words = nullptr;
+  size_t n_recs = 0, n_words = 0;
+  int create(wfm_handle_t* h, void** o) override {
+    wfm_trans_t* p = nullptr;
+    const int rc = wfm_trans_create(h, world.n_bases(), &p);
+    *o = p;
+    return rc;
+  }
+  void destroy(void* o) override { wfm_trans_free((wfm_trans_t*)o); }
+  int export_lists(wfm_handle_t* h, void* o) override { return wfm_trans_export(h, (wfm_trans_t*)o, &recs, &n_recs, &words, &n_words); }
+  int import_lists(wfm_handle_t* h, void* o) override { return wfm_trans_import(h, (wfm_trans_t*)o, recs, n_recs, words, n_words); }
+  void free_lists() override { wfm_trans_free_list(recs); wfm_trans_free_list(words); }
+  void finish() override {
+    const auto t0 = Clock::now();
+    wfm_trans_iv_t* ivs = nullptr;
+    size_t n_ivs = 0;
+    std::vector<wfm_trans_seed_t> per(seeds.iv.size());
+    uint64_t counts[6] = {0, 0, 0, 0, 0, 0};
+    if (!objects.empty() && !seeds.iv.empty()) {
+      merge();
+      const std::vector<wfm_lift_iv_t> raw = raw_intervals(seeds.iv);
+      std::lock_guard<std::mutex> lk(wflign::handle_lock(h0()));
+      if (wfm_trans_closure(h0(), first<wfm_trans_t>(), raw.data(), raw.size(), depth, &ivs, &n_ivs, per.data()) != WFM_OK) fail(h0(), "closure");
+      wfm_trans_counts(first<wfm_trans_t>(), counts);
+    }
+    const auto t1 = Clock::now();
+    static_assert(sizeof(transitive::ClosureIv) == sizeof(wfm_trans_iv_t) && sizeof(transitive::SeedCall) == sizeof(wfm_trans_seed_t),
+                  "transitive_text.hpp restates wfm_trans_iv_t and wfm_trans_seed_t");
+    const uint64_t lines = transitive::file(out, world, seeds.iv, (const transitive::SeedCall*)per.data(), (const transitive::ClosureIv*)ivs);
+    wfm_trans_free_list(ivs);
+    wflign::switch_finished(id, lines, counts[3], seeds.skipped);
+    if (getenv("WFM_DEBUG"))
+      fprintf(stderr, "[wfmash::align] transitive: %zu objects merged, %llu records, %llu prefix words, %zu seeds at depth %u, %llu rounds, %llu pairs, %zu intervals, %llu lines, merge + closure %.1f ms, text %.1f ms\n",
+              objects.size(), (unsigned long long)counts[0], (unsigned long long)counts[1], seeds.iv.size(), depth, (unsigned long long)counts[3],
+              (unsigned long long)counts[5], n_ivs, (unsigned long long)lines, std::chrono::duration<double, std::milli>(t1 - t0).count(), ms_since(t1));
+  }
+};
+
+// the passes in their order: wflign::SwitchId's first N_PASSES
+template <class P>
+Pass* make_pass(wflign::RunTables& tb, const wflign::SwitchSetting& s) { return new P(tb, s); }
+Pass* (*const kMakePass[wflign::N_PASSES])(wflign::RunTables&, const wflign::SwitchSetting&) = {
+    make_pass<VariantsPass>, make_pass<CoveragePass>, make_pass<LiftPass>,     make_pass<ChainPass>,
+    make_pass<PavPass>,      make_pass<GenotypesPass>, make_pass<ChainNetPass>, make_pass<TransitivePass>};
 }  // namespace
 
 struct Aligner::Run {
@@ -563,142 +902,24 @@ struct Aligner::Run {
     for (auto& a : in_flight) a.store(0);
     for (auto& a : first_taken) a.store(0);
   }
+  ~Run() { for (auto& p : passes) p->free_objects(); }
   const Parameters& param;
   const RunPlan plan;
   const size_t ngpu;
   const Clock::time_point t0;
   std::ifstream& in;
-  skch::OrderedWriter<std::string, TextSink> writer;
-  std::unique_ptr<skch::OrderedWriter<std::string, TextSink>> vcf_writer;  // --variants: the second file, keyed by the same batch numbers
-  // --lift: the third file, keyed by the same batch numbers; the BED's intervals sorted as the device takes them, and the liftset of every
-  // handle the run has used so far, made at the handle's first batch
-  std::unique_ptr<skch::OrderedWriter<std::string, TextSink>> lift_writer;
-  std::vector<lift::Interval> lift_iv;
-  std::mutex lift_mu;
-  std::vector<std::pair<wfm_handle_t*, wfm_liftset_t*>> liftsets;
-  const wfm_liftset_t* liftset_of(wfm_handle_t* h) {
-    if (!lift_writer) return nullptr;
-    std::lock_guard<std::mutex> lk(lift_mu);
-    for (auto& hs : liftsets) if (hs.first == h) return hs.second;
-    std::vector<wfm_lift_iv_t> raw(lift_iv.size());
-    for (size_t i = 0; i < raw.size(); ++i) raw[i] = wfm_lift_iv_t{lift_iv[i].gstart, lift_iv[i].gend};
-    wfm_liftset_t* s = nullptr;
-    std::lock_guard<std::mutex> hl(wflign::handle_lock(h));
-    if (wfm_liftset_create(h, raw.data(), raw.size(), seq_offsets.back(), &s) != WFM_OK) throw std::runtime_error(std::string("[wfmash::align] --lift: ") + wfm_last_error(h));
-    liftsets.emplace_back(h, s);
-    return s;
-  }
-  // --chain: the fourth file, keyed by the same batch numbers
-  std::unique_ptr<skch::OrderedWriter<std::string, ChainSink>> chain_writer;
-  bool chain_swap = false;
-  // --pav: the intervals of the table in the file's order, the columns (and every query sequence's), and the presence object of every
-  // handle the run has used so far, made at the handle's first batch
-  bool pav_on = false;
-  std::vector<lift::Interval> pav_iv;
-  pav::Columns pav_cols;
-  std::mutex pav_mu;
-  std::vector<std::pair<wfm_handle_t*, wfm_pav_t*>> pavs;
-  wfm_pav_t* pav_of(wfm_handle_t* h) {
-    if (!pav_on) return nullptr;
-    std::lock_guard<std::mutex> lk(pav_mu);
-    for (auto& hp : pavs) if (hp.first == h) return hp.second;
-    wfm_pav_t* p = nullptr;
-    std::lock_guard<std::mutex> hl(wflign::handle_lock(h));
-    if (wfm_pav_create(h, seq_offsets.back(), (uint32_t)pav_cols.keys.size(), &p) != WFM_OK) throw std::runtime_error(std::string("[wfmash::align] --pav: ") + wfm_last_error(h));
-    pavs.emplace_back(h, p);
-    return p;
-  }
-  // --genotypes: the columns (pav_cols, as --pav makes them) and the sites object of every handle the run has used so far, made at the
-  // handle's first batch
-  bool sites_on = false;
-  std::mutex sites_mu;
-  std::vector<std::pair<wfm_handle_t*, wfm_sites_t*>> sites;
-  wfm_sites_t* sites_of(wfm_handle_t* h) {
-    if (!sites_on) return nullptr;
-    std::lock_guard<std::mutex> lk(sites_mu);
-    for (auto& hs : sites) if (hs.first == h) return hs.second;
-    wfm_sites_t* p = nullptr;
-    std::lock_guard<std::mutex> hl(wflign::handle_lock(h));
-    if (wfm_sites_create(h, seq_offsets.back(), (uint32_t)pav_cols.keys.size(), &p) != WFM_OK) throw std::runtime_error(std::string("[wfmash::align] --genotypes: ") + wfm_last_error(h));
-    sites.emplace_back(h, p);
-    return p;
-  }
-  // --chain-net: the net object of every handle the run has used so far, made at the handle's first batch, and what the chains' headers
-  // need of every record added, in no order (finish_chain_net sorts them by their orders)
-  bool net_on = false;
-  std::mutex net_mu;
-  std::vector<std::pair<wfm_handle_t*, wfm_net_t*>> nets;
-  std::vector<wflign::NetHead> net_heads;
-  wfm_net_t* net_of(wfm_handle_t* h) {
-    if (!net_on) return nullptr;
-    std::lock_guard<std::mutex> lk(net_mu);
-    for (auto& hn : nets) if (hn.first == h) return hn.second;
-    wfm_net_t* p = nullptr;
-    std::lock_guard<std::mutex> hl(wflign::handle_lock(h));
-    if (wfm_net_create(h, seq_offsets.back(), &p) != WFM_OK) throw std::runtime_error(std::string("[wfmash::align] --chain-net: ") + wfm_last_error(h));
-    nets.emplace_back(h, p);
-    return p;
-  }
-  // --transitive: the world, the seeds in input order, where each query sequence begins in the world, the depth, and the trans object of
-  // every handle the run has used so far, made at the handle's first batch
-  bool trans_on = false;
-  transitive::World world;
-  lift::Bed trans_seeds;
-  std::vector<uint64_t> query_world;
-  uint32_t trans_depth = 2;
-  std::mutex trans_mu;
-  std::vector<std::pair<wfm_handle_t*, wfm_trans_t*>> trans;
-  wfm_trans_t* trans_of(wfm_handle_t* h) {
-    if (!trans_on) return nullptr;
-    std::lock_guard<std::mutex> lk(trans_mu);
-    for (auto& ht : trans) if (ht.first == h) return ht.second;
-    wfm_trans_t* p = nullptr;
-    std::lock_guard<std::mutex> hl(wflign::handle_lock(h));
-    if (wfm_trans_create(h, world.n_bases(), &p) != WFM_OK) throw std::runtime_error(std::string("[wfmash::align] --transitive: ") + wfm_last_error(h));
-    trans.emplace_back(h, p);
-    return p;
-  }
-  // --coverage, --lift, --pav, --genotypes, --chain-net: where each target sequence begins in the concatenation (nseq + 1 values; empty: all are off).  --coverage: the depth object
-  // of every handle the run has used so far, made at the handle's first batch
-  std::vector<uint64_t> seq_offsets;
-  bool coverage_on = false;
-  std::mutex coverage_mu;
-  std::vector<std::pair<wfm_handle_t*, wfm_coverage_t*>> coverage;
-  ~Run() {
-    for (auto& hc : coverage) {
-      std::lock_guard<std::mutex> lk(wflign::handle_lock(hc.first));
-      wfm_coverage_free(hc.second);
-    }
-    for (auto& hs : liftsets) {
-      std::lock_guard<std::mutex> lk(wflign::handle_lock(hs.first));
-      wfm_liftset_free(hs.second);
-    }
-    for (auto& hp : pavs) {
-      std::lock_guard<std::mutex> lk(wflign::handle_lock(hp.first));
-      wfm_pav_free(hp.second);
-    }
-    for (auto& hs : sites) {
-      std::lock_guard<std::mutex> lk(wflign::handle_lock(hs.first));
-      wfm_sites_free(hs.second);
-    }
-    for (auto& hn : nets) {
-      std::lock_guard<std::mutex> lk(wflign::handle_lock(hn.first));
-      wfm_net_free(hn.second);
-    }
-    for (auto& ht : trans) {
-      std::lock_guard<std::mutex> lk(wflign::handle_lock(ht.first));
-      wfm_trans_free(ht.second);
-    }
-  }
-  wfm_coverage_t* coverage_of(wfm_handle_t* h) {
-    if (!coverage_on) return nullptr;
-    std::lock_guard<std::mutex> lk(coverage_mu);
-    for (auto& hc : coverage) if (hc.first == h) return hc.second;
-    wfm_coverage_t* c = nullptr;
-    std::lock_guard<std::mutex> hl(wflign::handle_lock(h));
-    if (wfm_coverage_create(h, seq_offsets.back(), &c) != WFM_OK) throw std::runtime_error(std::string("[wfmash::align] --coverage: ") + wfm_last_error(h));
-    coverage.emplace_back(h, c);
-    return c;
+  TextWriter writer;
+  // the passes that are on, in their order, and the tables they share (filled before the first of them is made)
+  wflign::RunTables tables;
+  std::vector<std::unique_ptr<Pass>> passes;
+  // a batch's view of them: the handle's objects, each made at the handle's first batch
+  wflign::BatchPasses batch_passes(wfm_handle_t* h, uint64_t seq) {
+    wflign::BatchPasses bp;
+    if (passes.empty()) return bp;
+    bp.batch = seq;
+    bp.tables = &tables;
+    for (auto& p : passes) { bp.on[p->id] = true; bp.object[p->id] = p->object_of(h); }
+    return bp;
   }
   std::mutex read_mu;
   uint64_t next_seq = 0;   // (under read_mu) the next batch's number
@@ -787,22 +1008,10 @@ void Aligner::run_worker(Run& run, size_t wk) {
       { std::lock_guard<std::mutex> lk(run.read_mu); more = run.more_rows; beside = run.in_flight[dev].fetch_add(1); }
       wfm_set_concurrent_calls(run.use[wk], beside + (more && run.plan.per_gpu > 1 ? 1 : 0));
       struct Leave { std::atomic<int>& a; ~Leave() { a.fetch_sub(1); } } leave{run.in_flight[dev]};
-      std::string vcf, lifted, chains;
-      std::vector<wflign::NetHead> heads;
-      std::string text = align_batch(run.use[wk], batch, run.threads_each, run.part[wk], first_row, run.vcf_writer ? &vcf : nullptr,
-                                     run.coverage_of(run.use[wk]), &run.seq_offsets, run.lift_writer ? &lifted : nullptr, run.liftset_of(run.use[wk]),
-                                     &run.lift_iv, run.pav_of(run.use[wk]), &run.pav_cols.of_seq, run.chain_writer ? &chains : nullptr, run.chain_swap,
-                                     run.sites_of(run.use[wk]), (uint32_t)run.pav_cols.keys.size(), run.net_of(run.use[wk]), (uint64_t)seq, &heads,
-                                     run.trans_of(run.use[wk]), &run.query_world);
-      if (!heads.empty()) {
-        std::lock_guard<std::mutex> lk(run.net_mu);
-        for (auto& hd : heads) run.net_heads.push_back(std::move(hd));
-      }
+      wflign::BatchTexts texts = align_batch(run.use[wk], batch, run.threads_each, run.part[wk], first_row, run.batch_passes(run.use[wk], (uint64_t)seq));
       const double at1 = run.ms();
-      run.writer.put((uint64_t)seq, std::move(text));
-      if (run.vcf_writer) run.vcf_writer->put((uint64_t)seq, std::move(vcf));
-      if (run.lift_writer) run.lift_writer->put((uint64_t)seq, std::move(lifted));
-      if (run.chain_writer) run.chain_writer->put((uint64_t)seq, std::move(chains));
+      run.writer.put((uint64_t)seq, std::move(texts.paf));
+      for (auto& p : run.passes) p->take((uint64_t)seq, texts);
       if (getenv("WFM_DEBUG"))
         fprintf(stderr, "[wfmash::align] worker %zu: batch %lld from +%.0f ms to +%.0f ms, written at +%.0f ms\n", wk, (long long)seq, at0, at1, run.ms());
     }
@@ -847,367 +1056,40 @@ void Aligner::sum_up(Summary& sum, const std::vector<Summary>& part, std::chrono
   for (const Summary& p : part) sum.ms_gpu = std::max(sum.ms_gpu, p.ms_gpu);
 }
 
-// --coverage: every other handle's object exported and imported into the first (integer adds: the order does not matter), the intervals of
-// the sum taken once on the device, the file through coverage_bedgraph
-void Aligner::finish_coverage(Run& run, std::ofstream& out) {
-  const auto t0 = Clock::now();
-  auto fail = [](wfm_handle_t* h, const char* what) { throw std::runtime_error(std::string("[wfmash::align] --coverage: ") + what + ": " + wfm_last_error(h)); };
-  std::vector<coverage::Interval> iv;
-  uint64_t totals[3] = {0, 0, 0};
-  if (!run.coverage.empty()) {
-    wfm_handle_t* h0 = run.coverage.front().first;
-    wfm_coverage_t* c0 = run.coverage.front().second;
-    for (size_t k = 1; k < run.coverage.size(); ++k) {
-      wfm_cov_entry_t* list = nullptr;
-      size_t n = 0;
-      {
-        std::lock_guard<std::mutex> lk(wflign::handle_lock(run.coverage[k].first));
-        if (wfm_coverage_export(run.coverage[k].first, run.coverage[k].second, &list, &n) != WFM_OK) fail(run.coverage[k].first, "export");
+// the passes whose switches are on, each with its file open and what it reads read; the run's tables before the first of them
+void Aligner::make_passes(Run& run) const {
+  for (int id = 0; id < wflign::N_PASSES; ++id) {
+    const wflign::SwitchSetting s = wflign::switch_setting((wflign::SwitchId)id);
+    if (s.out.empty()) continue;
+    wflign::RunTables& tb = run.tables;
+    if (run.passes.empty()) {
+      tb.seq_offsets.assign(1, 0);
+      for (int i = 0; i < ref->nseq(); ++i) {
+        tb.tnames.push_back(ref->name(i));
+        tb.tlengths.push_back((uint64_t)ref->length(i));
+        tb.seq_offsets.push_back(tb.seq_offsets.back() + tb.tlengths.back());
       }
-      std::lock_guard<std::mutex> lk(wflign::handle_lock(h0));
-      const int rc = wfm_coverage_import(h0, c0, list, n);
-      wfm_coverage_free_list(list);
-      if (rc != WFM_OK) fail(h0, "import");
+      for (int i = 0; i < query->nseq(); ++i) { tb.qnames.push_back(query->name(i)); tb.qlengths.push_back((uint64_t)query->length(i)); }
+      tb.find_target = [this](const std::string& name) { return ref->find(name); };
     }
-    wfm_cov_interval_t* d_iv = nullptr;
-    size_t n = 0;
-    std::lock_guard<std::mutex> lk(wflign::handle_lock(h0));
-    if (wfm_coverage_intervals(h0, c0, &d_iv, &n, totals) != WFM_OK) fail(h0, "intervals");
-    iv.resize(n);
-    for (size_t i = 0; i < n; ++i) iv[i] = coverage::Interval{d_iv[i].start, d_iv[i].depth};
-    wfm_coverage_free_list(d_iv);
+    run.passes.emplace_back(kMakePass[id](tb, s));
   }
-  std::vector<std::string> names;
-  std::vector<uint64_t> lengths;
-  for (int i = 0; i < ref->nseq(); ++i) { names.push_back(ref->name(i)); lengths.push_back((uint64_t)ref->length(i)); }
-  uint64_t lines = 0;
-  out << coverage::coverage_bedgraph(names, lengths, iv, &lines);
-  wflign::coverage_finished(totals[0], totals[1], lines);
-  if (getenv("WFM_DEBUG"))
-    fprintf(stderr, "[wfmash::align] coverage: %zu objects merged, %zu intervals, %llu lines, %.1f ms\n", run.coverage.size(), iv.size(), (unsigned long long)lines, ms_since(t0));
-}
-
-// --pav: every other handle's object exported and imported into the first (a union of unions: the order does not matter), the table of
-// the merged object taken once on the device, the file through pav_text.hpp
-void Aligner::finish_pav(Run& run, std::ofstream& out, uint64_t bed_skipped) {
-  const auto t0 = Clock::now();
-  auto fail = [](wfm_handle_t* h, const char* what) { throw std::runtime_error(std::string("[wfmash::align] --pav: ") + what + ": " + wfm_last_error(h)); };
-  const size_t G = run.pav_cols.keys.size(), n_iv = run.pav_iv.size();
-  std::vector<uint32_t> cells(G * n_iv, 0u);
-  uint64_t counts[3] = {0, 0, 0};
-  if (!run.pavs.empty()) {
-    wfm_handle_t* h0 = run.pavs.front().first;
-    wfm_pav_t* p0 = run.pavs.front().second;
-    for (size_t k = 1; k < run.pavs.size(); ++k) {
-      wfm_pav_seg_t* list = nullptr;
-      size_t n = 0;
-      {
-        std::lock_guard<std::mutex> lk(wflign::handle_lock(run.pavs[k].first));
-        if (wfm_pav_export(run.pavs[k].first, run.pavs[k].second, &list, &n) != WFM_OK) fail(run.pavs[k].first, "export");
-      }
-      std::lock_guard<std::mutex> lk(wflign::handle_lock(h0));
-      const int rc = wfm_pav_import(h0, p0, list, n);
-      wfm_pav_free_list(list);
-      if (rc != WFM_OK) fail(h0, "import");
-    }
-    std::vector<wfm_lift_iv_t> raw(n_iv);
-    for (size_t j = 0; j < n_iv; ++j) raw[j] = wfm_lift_iv_t{run.pav_iv[j].gstart, run.pav_iv[j].gend};
-    std::lock_guard<std::mutex> lk(wflign::handle_lock(h0));
-    if (wfm_pav_matrix(h0, p0, raw.data(), n_iv, cells.data()) != WFM_OK) fail(h0, "matrix");
-    wfm_pav_counts(p0, counts);
-  }
-  const auto t1 = Clock::now();
-  std::string text = pav::header(run.pav_cols.keys);
-  for (size_t j = 0; j < n_iv; ++j) {
-    pav::row(text, ref->name(run.pav_iv[j].seq), run.pav_iv[j], cells.data() + j * G, G);
-    if (text.size() >= ((size_t)1 << 20)) { out << text; text.clear(); }
-  }
-  out << text;
-  wflign::pav_finished(n_iv, counts[1], bed_skipped);
-  if (getenv("WFM_DEBUG"))
-    fprintf(stderr, "[wfmash::align] pav: %zu objects merged, %llu segments added, %llu union intervals, %zu rows x %zu groups, merge + union + matrix %.1f ms, text %.1f ms\n",
-            run.pavs.size(), (unsigned long long)counts[0], (unsigned long long)counts[1], n_iv, G, std::chrono::duration<double, std::milli>(t1 - t0).count(), ms_since(t1));
-}
-
-// --genotypes: every other handle's object exported and imported into the first (the table is a set function: the order does not matter),
-// the table of the merged object taken once on the device, the file through genotype_text.hpp
-void Aligner::finish_genotypes(Run& run, std::ofstream& out) {
-  const auto t0 = Clock::now();
-  auto fail = [](wfm_handle_t* h, const char* what) { throw std::runtime_error(std::string("[wfmash::align] --genotypes: ") + what + ": " + wfm_last_error(h)); };
-  const size_t G = run.pav_cols.keys.size();
-  wfm_site_t* rows = nullptr;
-  char *alleles = nullptr, *gt = nullptr;
-  size_t n_sites = 0, bytes = 0;
-  uint64_t counts[4] = {0, 0, 0, 0};
-  if (!run.sites.empty()) {
-    wfm_handle_t* h0 = run.sites.front().first;
-    wfm_sites_t* s0 = run.sites.front().second;
-    for (size_t k = 1; k < run.sites.size(); ++k) {
-      wfm_site_var_t* vars = nullptr;
-      char* a = nullptr;
-      wfm_pav_seg_t* segs = nullptr;
-      size_t n = 0, nb = 0, ns = 0;
-      {
-        std::lock_guard<std::mutex> lk(wflign::handle_lock(run.sites[k].first));
-        if (wfm_sites_export(run.sites[k].first, run.sites[k].second, &vars, &n, &a, &nb, &segs, &ns) != WFM_OK) fail(run.sites[k].first, "export");
-      }
-      std::lock_guard<std::mutex> lk(wflign::handle_lock(h0));
-      const int rc = wfm_sites_import(h0, s0, vars, n, a, nb, segs, ns);
-      wfm_sites_free_list(vars); wfm_sites_free_list(a); wfm_sites_free_list(segs);
-      if (rc != WFM_OK) fail(h0, "import");
-    }
-    std::lock_guard<std::mutex> lk(wflign::handle_lock(h0));
-    if (wfm_sites_table(h0, s0, &rows, &n_sites, &alleles, &bytes, &gt) != WFM_OK) fail(h0, "table");
-    wfm_sites_counts(s0, counts);
-  }
-  const auto t1 = Clock::now();
-  std::vector<std::string> names;
-  std::vector<uint64_t> lengths;
-  for (int i = 0; i < ref->nseq(); ++i) { names.push_back(ref->name(i)); lengths.push_back((uint64_t)ref->length(i)); }
-  std::vector<genotype::Site> sites(n_sites);
-  for (size_t i = 0; i < n_sites; ++i) sites[i] = genotype::Site{rows[i].pos, rows[i].ref_len, rows[i].alt_len, rows[i].off};
-  std::string text = genotype::header(WFMASH_HIP_VERSION, names, lengths, run.pav_cols.keys);
-  for (size_t i : genotype::order(sites, alleles)) {
-    genotype::site_line(text, sites, i, alleles, gt, G, names, run.seq_offsets);
-    if (text.size() >= ((size_t)1 << 20)) { out << text; text.clear(); }
-  }
-  out << text;
-  wfm_sites_free_list(rows); wfm_sites_free_list(alleles); wfm_sites_free_list(gt);
-  wflign::genotypes_finished(counts[0], n_sites);
-  if (getenv("WFM_DEBUG"))
-    fprintf(stderr, "[wfmash::align] genotypes: %zu objects merged, %llu variants, %zu sites x %zu groups, %llu = intervals, merge + table %.1f ms, text %.1f ms\n",
-            run.sites.size(), (unsigned long long)counts[0], n_sites, G, (unsigned long long)counts[2], std::chrono::duration<double, std::milli>(t1 - t0).count(), ms_since(t1));
-}
-
-// --chain-net: every other handle's object exported and imported into the first (the net is a set function: the order does not matter),
-// the table of the merged object taken once on the device, the file through chain_text.hpp's net_body in the order of the orders, which
-// is the order of the PAF's records
-void Aligner::finish_chain_net(Run& run, std::ofstream& out) {
-  const auto t0 = Clock::now();
-  auto fail = [](wfm_handle_t* h, const char* what) { throw std::runtime_error(std::string("[wfmash::align] --chain-net: ") + what + ": " + wfm_last_error(h)); };
-  wfm_net_piece_t* pieces = nullptr;
-  wfm_netcall_t* per = nullptr;
-  size_t n_pieces = 0, n_rec = 0;
-  uint64_t counts[6] = {0, 0, 0, 0, 0, 0};
-  if (!run.nets.empty()) {
-    wfm_handle_t* h0 = run.nets.front().first;
-    wfm_net_t* n0 = run.nets.front().second;
-    for (size_t k = 1; k < run.nets.size(); ++k) {
-      wfm_net_block_t* blocks = nullptr;
-      wfm_net_rec_t* recs = nullptr;
-      size_t nb = 0, nr = 0;
-      {
-        std::lock_guard<std::mutex> lk(wflign::handle_lock(run.nets[k].first));
-        if (wfm_net_export(run.nets[k].first, run.nets[k].second, &blocks, &nb, &recs, &nr) != WFM_OK) fail(run.nets[k].first, "export");
-      }
-      std::lock_guard<std::mutex> lk(wflign::handle_lock(h0));
-      const int rc = wfm_net_import(h0, n0, blocks, nb, recs, nr);
-      wfm_net_free_list(blocks); wfm_net_free_list(recs);
-      if (rc != WFM_OK) fail(h0, "import");
-    }
-    std::lock_guard<std::mutex> lk(wflign::handle_lock(h0));
-    if (wfm_net_table(h0, n0, &pieces, &n_pieces, &per, &n_rec) != WFM_OK) fail(h0, "table");
-    wfm_net_counts(n0, counts);
-  }
-  const auto t1 = Clock::now();
-  static_assert(sizeof(chain::Piece) == sizeof(wfm_net_piece_t), "chain_text.hpp restates wfm_net_piece_t");
-  std::sort(run.net_heads.begin(), run.net_heads.end(), [](const wflign::NetHead& a, const wflign::NetHead& b) { return a.order < b.order; });
-  if (run.net_heads.size() != n_rec) throw std::runtime_error("[wfmash::align] --chain-net: the table's records are not the records added");
-  std::string body, text;
-  uint64_t next = 1, chains = 0, lost = 0;
-  for (size_t i = 0; i < n_rec; ++i) {  // (per is sorted by order too)
-    const wflign::NetHead& hd = run.net_heads[i];
-    if (hd.order != per[i].order) throw std::runtime_error("[wfmash::align] --chain-net: the table's records are not the records added");
-    if (per[i].count == 0) { ++lost; continue; }
-    chain::net_body(body, hd.rec, hd.t_offset, per[i].score, (const chain::Piece*)pieces + per[i].first, per[i].count);
-    if (body.size() >= ((size_t)1 << 20)) { text.clear(); chains += chain::number(body, &next, text); out << text; body.clear(); }
-  }
-  text.clear();
-  chains += chain::number(body, &next, text);
-  out << text;
-  wfm_net_free_list(pieces); wfm_net_free_list(per);
-  wflign::chain_net_finished(chains, n_pieces, lost);
-  if (getenv("WFM_DEBUG"))
-    fprintf(stderr, "[wfmash::align] chain-net: %zu objects merged, %llu records, %llu blocks, %llu elementary intervals, %zu pieces, %llu chains, %llu records won nothing, merge + table %.1f ms, text %.1f ms\n",
-            run.nets.size(), (unsigned long long)counts[0], (unsigned long long)counts[1], (unsigned long long)counts[2], n_pieces, (unsigned long long)chains,
-            (unsigned long long)lost, std::chrono::duration<double, std::milli>(t1 - t0).count(), ms_since(t1));
-}
-
-// --transitive: every other handle's object exported and imported into the first (the closure is a set function: the order does not
-// matter), the closure of the seeds taken once on the device, the file through transitive_text.hpp in the order of the BED's lines
-void Aligner::finish_transitive(Run& run, std::ofstream& out) {
-  const auto t0 = Clock::now();
-  auto fail = [](wfm_handle_t* h, const char* what) { throw std::runtime_error(std::string("[wfmash::align] --transitive: ") + what + ": " + wfm_last_error(h)); };
-  const std::vector<lift::Interval>& seeds = run.trans_seeds.iv;
-  wfm_trans_iv_t* ivs = nullptr;
-  size_t n_ivs = 0;
-  std::vector<wfm_trans_seed_t> per(seeds.size());
-  uint64_t counts[6] = {0, 0, 0, 0, 0, 0};
-  if (!run.trans.empty() && !seeds.empty()) {
-    wfm_handle_t* h0 = run.trans.front().first;
-    wfm_trans_t* o0 = run.trans.front().second;
-    for (size_t k = 1; k < run.trans.size(); ++k) {
-      wfm_trans_rec_t* recs = nullptr;
-      wfm_trans_word_t* words = nullptr;
-      size_t nr = 0, nw = 0;
-      {
-        std::lock_guard<std::mutex> lk(wflign::handle_lock(run.trans[k].first));
-        if (wfm_trans_export(run.trans[k].first, run.trans[k].second, &recs, &nr, &words, &nw) != WFM_OK) fail(run.trans[k].first, "export");
-      }
-      std::lock_guard<std::mutex> lk(wflign::handle_lock(h0));
-      const int rc = wfm_trans_import(h0, o0, recs, nr, words, nw);
-      wfm_trans_free_list(recs); wfm_trans_free_list(words);
-      if (rc != WFM_OK) fail(h0, "import");
-    }
-    std::vector<wfm_lift_iv_t> raw(seeds.size());
-    for (size_t i = 0; i < raw.size(); ++i) raw[i] = wfm_lift_iv_t{seeds[i].gstart, seeds[i].gend};
-    std::lock_guard<std::mutex> lk(wflign::handle_lock(h0));
-    if (wfm_trans_closure(h0, o0, raw.data(), raw.size(), run.trans_depth, &ivs, &n_ivs, per.data()) != WFM_OK) fail(h0, "closure");
-    wfm_trans_counts(o0, counts);
-  }
-  const auto t1 = Clock::now();
-  std::string text;
-  uint64_t lines = 0;
-  for (size_t i = 0; i < seeds.size(); ++i) {
-    if (!ivs) lines += transitive::lines(text, run.world, seeds[i], seeds[i].gstart, seeds[i].gend);  // (no record was added: a seed reaches itself)
-    else
-      for (uint64_t k = per[i].first; k < per[i].first + per[i].count; ++k) lines += transitive::lines(text, run.world, seeds[i], ivs[k].start, ivs[k].end);
-    if (text.size() >= ((size_t)1 << 20)) { out << text; text.clear(); }
-  }
-  out << text;
-  wfm_trans_free_list(ivs);
-  wflign::transitive_finished(lines, counts[3], run.trans_seeds.skipped);
-  if (getenv("WFM_DEBUG"))
-    fprintf(stderr, "[wfmash::align] transitive: %zu objects merged, %llu records, %llu prefix words, %zu seeds at depth %u, %llu rounds, %llu pairs, %zu intervals, %llu lines, merge + closure %.1f ms, text %.1f ms\n",
-            run.trans.size(), (unsigned long long)counts[0], (unsigned long long)counts[1], seeds.size(), run.trans_depth, (unsigned long long)counts[3],
-            (unsigned long long)counts[5], n_ivs, (unsigned long long)lines, std::chrono::duration<double, std::milli>(t1 - t0).count(), ms_since(t1));
 }
 
 Summary Aligner::compute() {
   Summary sum;
   const auto t0 = Clock::now();
-  std::ifstream in(param.mashmapPafFile);
-  if (!in.is_open()) throw std::runtime_error("[wfmash::align] Error! Failed to open input mapping file: " + param.mashmapPafFile);
-  std::ofstream outstream(param.pafOutputFile);
-  if (!outstream.is_open()) throw std::runtime_error("[wfmash::align] Error! Failed to open output file: " + param.pafOutputFile);
+  std::ifstream in;
+  open_or_throw(in, param.mashmapPafFile, "input mapping file");
+  std::ofstream outstream;
+  open_or_throw(outstream, param.pafOutputFile, "output file");
   if (param.sam_format) {  // write_sam_header (computeAlignments.hpp:725-736)
     for (int i = 0; i < ref->nseq(); ++i) outstream << "@SQ\tSN:" << ref->name(i) << "\tLN:" << ref->length(i) << "\n";
     outstream << "@PG\tID:wfmash\tPN:wfmash\tVN:" WFMASH_HIP_VERSION "\tCL:wfmash\n";
   }
   const size_t ngpu = gpus.size();
   Run run(param, plan_run(in), ngpu, t0, in, outstream);
-  std::ofstream vcfstream;
-  const std::string vcf_path = wflign::variants_path();
-  if (!vcf_path.empty()) {  // --variants: the header here, the batches' lines through a second ordered writer
-    vcfstream.open(vcf_path);
-    if (!vcfstream.is_open()) throw std::runtime_error("[wfmash::align] Error! Failed to open the variants file: " + vcf_path);
-    vcfstream << "##fileformat=VCFv4.2\n##source=wfmash-hip " WFMASH_HIP_VERSION "\n";
-    for (int i = 0; i < ref->nseq(); ++i) vcfstream << "##contig=<ID=" << ref->name(i) << ",length=" << ref->length(i) << ">\n";
-    vcfstream << "##INFO=<ID=QNAME,Number=1,Type=String,Description=\"Query sequence name\">\n"
-                 "##INFO=<ID=QSTART,Number=1,Type=Integer,Description=\"Start of the query bases in ALT, 0-based, forward strand\">\n"
-                 "##INFO=<ID=QEND,Number=1,Type=Integer,Description=\"End of the query bases in ALT, exclusive, forward strand\">\n"
-                 "##INFO=<ID=QSTRAND,Number=1,Type=String,Description=\"Strand of the query in the alignment\">\n"
-                 "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n";
-    run.vcf_writer.reset(new skch::OrderedWriter<std::string, TextSink>(TextSink{&vcfstream}));
-  }
-  std::ofstream covstream;
-  const std::string cov_path = wflign::coverage_path();
-  if (!cov_path.empty()) {  // --coverage: the file is opened before anything is aligned, and written once the workers are done
-    covstream.open(cov_path);
-    if (!covstream.is_open()) throw std::runtime_error("[wfmash::align] Error! Failed to open the coverage file: " + cov_path);
-    run.coverage_on = true;
-  }
-  std::ofstream liftstream;
-  std::string lift_bed, lift_out;
-  wflign::lift_paths(lift_bed, lift_out);
-  std::ofstream chainstream;
-  std::string chain_out;
-  wflign::chain_path(chain_out, run.chain_swap);
-  if (!chain_out.empty()) {  // --chain: the batches' chains go through a fourth ordered writer, which numbers them
-    chainstream.open(chain_out);
-    if (!chainstream.is_open()) throw std::runtime_error("[wfmash::align] Error! Failed to open the chain file: " + chain_out);
-    run.chain_writer.reset(new skch::OrderedWriter<std::string, ChainSink>(ChainSink{&chainstream}));
-  }
-  std::ofstream netstream;
-  const std::string net_out = wflign::chain_net_path();
-  if (!net_out.empty()) {  // --chain-net: the file is opened before anything is aligned, and written once the workers are done
-    netstream.open(net_out);
-    if (!netstream.is_open()) throw std::runtime_error("[wfmash::align] Error! Failed to open the chain-net file: " + net_out);
-    run.net_on = true;
-  }
-  std::ofstream transstream;
-  std::string trans_bed, trans_out;
-  wflign::transitive_paths(trans_bed, trans_out, run.trans_depth);
-  std::ofstream pavstream;
-  std::string pav_bed, pav_out;
-  uint64_t pav_window = 0, pav_skipped = 0;
-  wflign::pav_paths(pav_bed, pav_window, pav_out);
-  std::ofstream gtstream;
-  const std::string gt_path = wflign::genotypes_path();
-  if (!cov_path.empty() || !lift_out.empty() || !pav_out.empty() || !gt_path.empty() || !net_out.empty() || !trans_out.empty()) {
-    run.seq_offsets.assign(1, 0);
-    for (int i = 0; i < ref->nseq(); ++i) run.seq_offsets.push_back(run.seq_offsets.back() + (uint64_t)ref->length(i));
-  }
-  if (!lift_out.empty()) {  // --lift: the BED is read once, here; the batches' lines go through a third ordered writer
-    std::ifstream bed(lift_bed, std::ios::binary);
-    if (!bed.is_open()) throw std::runtime_error("[wfmash::align] Error! Failed to open the BED file of --lift: " + lift_bed);
-    const std::string text((std::istreambuf_iterator<char>(bed)), std::istreambuf_iterator<char>());
-    std::vector<uint64_t> lengths;
-    for (int i = 0; i < ref->nseq(); ++i) lengths.push_back((uint64_t)ref->length(i));
-    lift::Bed parsed = lift::parse_bed(text, [&](const std::string& name) { return ref->find(name); }, lengths, run.seq_offsets);
-    run.lift_iv = std::move(parsed.iv);
-    wflign::lift_bed_read(parsed.skipped);
-    liftstream.open(lift_out);
-    if (!liftstream.is_open()) throw std::runtime_error("[wfmash::align] Error! Failed to open the lift file: " + lift_out);
-    run.lift_writer.reset(new skch::OrderedWriter<std::string, TextSink>(TextSink{&liftstream}));
-  }
-  if (!trans_out.empty()) {  // --transitive: the world and the seeds are known before anything is aligned; the file is written once the workers are done
-    std::vector<std::string> tnames, qnames;
-    std::vector<uint64_t> tlengths, qlengths;
-    for (int i = 0; i < ref->nseq(); ++i) { tnames.push_back(ref->name(i)); tlengths.push_back((uint64_t)ref->length(i)); }
-    for (int i = 0; i < query->nseq(); ++i) { qnames.push_back(query->name(i)); qlengths.push_back((uint64_t)query->length(i)); }
-    run.world = transitive::make_world(tnames, tlengths, qnames, qlengths);
-    if (run.world.n_bases() >= ((uint64_t)1 << 40)) throw std::runtime_error("[wfmash::align] --transitive: the sequences hold 2^40 bases or more");
-    for (const std::string& name : qnames) run.query_world.push_back(run.world.offsets[(size_t)run.world.find(name)]);
-    std::ifstream bed(trans_bed, std::ios::binary);
-    if (!bed.is_open()) throw std::runtime_error("[wfmash::align] Error! Failed to open the BED file of --transitive: " + trans_bed);
-    const std::string text((std::istreambuf_iterator<char>(bed)), std::istreambuf_iterator<char>());
-    run.trans_seeds = transitive::parse_seeds(text, run.world);
-    if (run.trans_seeds.iv.size() >= ((size_t)1 << 24)) throw std::runtime_error("[wfmash::align] --transitive: the BED holds 2^24 seeds or more");
-    transstream.open(trans_out);
-    if (!transstream.is_open()) throw std::runtime_error("[wfmash::align] Error! Failed to open the transitive file: " + trans_out);
-    run.trans_on = true;
-  }
-  if (!pav_out.empty()) {  // --pav: the intervals and the columns are known before anything is aligned; the file is written once the workers are done
-    std::vector<uint64_t> lengths;
-    for (int i = 0; i < ref->nseq(); ++i) lengths.push_back((uint64_t)ref->length(i));
-    if (!pav_bed.empty()) {
-      std::ifstream bed(pav_bed, std::ios::binary);
-      if (!bed.is_open()) throw std::runtime_error("[wfmash::align] Error! Failed to open the BED file of --pav: " + pav_bed);
-      const std::string text((std::istreambuf_iterator<char>(bed)), std::istreambuf_iterator<char>());
-      lift::Bed parsed = lift::parse_bed(text, [&](const std::string& name) { return ref->find(name); }, lengths, run.seq_offsets);
-      run.pav_iv = std::move(parsed.iv);
-      pav_skipped = parsed.skipped;
-    } else {
-      run.pav_iv = pav::windows(lengths, run.seq_offsets, pav_window);
-    }
-    std::vector<std::string> qnames;
-    for (int i = 0; i < query->nseq(); ++i) qnames.push_back(query->name(i));
-    run.pav_cols = pav::columns(qnames);
-    pavstream.open(pav_out);
-    if (!pavstream.is_open()) throw std::runtime_error("[wfmash::align] Error! Failed to open the pav file: " + pav_out);
-    run.pav_on = true;
-  }
-  if (!gt_path.empty()) {  // --genotypes: the columns are --pav's; the file is written once the workers are done
-    if (!run.pav_on) {
-      std::vector<std::string> qnames;
-      for (int i = 0; i < query->nseq(); ++i) qnames.push_back(query->name(i));
-      run.pav_cols = pav::columns(qnames);
-    }
-    gtstream.open(gt_path);
-    if (!gtstream.is_open()) throw std::runtime_error("[wfmash::align] Error! Failed to open the genotypes file: " + gt_path);
-    run.sites_on = true;
-  }
+  make_passes(run);
   const size_t nworkers = run.plan.nworkers;
   static const bool own_handles = !(getenv("WFM_ALIGN_OWN_HANDLES") && atoi(getenv("WFM_ALIGN_OWN_HANDLES")) == 0);
   static HandlePool pool;
@@ -1224,16 +1106,9 @@ Summary Aligner::compute() {
     for (auto& t : threads) t.join();
   }
   if (run.failed.load()) throw std::runtime_error(run.first_error);
-  if (covstream.is_open()) { finish_coverage(run, covstream); covstream.close(); }
-  if (pavstream.is_open()) { finish_pav(run, pavstream, pav_skipped); pavstream.close(); }
-  if (gtstream.is_open()) { finish_genotypes(run, gtstream); gtstream.close(); }
-  if (netstream.is_open()) { finish_chain_net(run, netstream); netstream.close(); }
-  if (transstream.is_open()) { finish_transitive(run, transstream); transstream.close(); }
+  for (auto& p : run.passes) { p->finish(); p->out.close(); }  // (the files the workers did not write, each from its handles' objects merged into one)
   sum_up(sum, run.part, t0);
   outstream.close();
-  if (vcfstream.is_open()) vcfstream.close();
-  if (liftstream.is_open()) liftstream.close();
-  if (chainstream.is_open()) chainstream.close();
   sum.ms_total = ms_since(t0);
   std::cerr << "[wfmash::align] total aligned records = " << sum.records << ", total aligned bp = " << sum.aligned_bp
             << ", completed in " << (uint64_t)(sum.ms_total / 1000.0) << " seconds" << std::endl;

@@ -104,22 +104,10 @@ class Aligner {
   // ---- one batch of mapping rows on one handle (aligner.cpp: align_batch and its stages) ----
   struct Fetched;     // a row, its windows and where its sides are
   struct BatchTimes;  // the stages' times, into the Summary at the end
-  // (vcf: where the VCF lines of the records written go, --variants; null: nowhere.  coverage: the depth object of this handle the records
-  // written are added to, --coverage, with seq_offsets: where each target sequence begins in the concatenation; null: none.  lift: where
-  // the lift lines of the records written go, --lift, with the handle's liftset and the intervals in its order; null: nowhere.  pav: the
-  // presence object of this handle the records written are added to, --pav, with the column of every query sequence; null: none.  chain:
-  // where the chains of the records written go, without their ids, --chain, swapped or not; null: nowhere.  sites: the sites object of
-  // this handle the variants and = runs of the records written are added to, --genotypes, with pav_columns and the number of groups.
-  // net: the net object of this handle the records written are added to, --chain-net, under orders that begin with net_batch, and
-  // net_heads: where what their chains' headers need goes; null: none.  trans: the trans object of this handle the records written are added
-  // to, --transitive, with query_world: where each query sequence begins in the world; null: none)
-  std::string align_batch(wfm_handle_t* gpu, std::vector<std::string>& lines, int threads, Summary& sum, uint64_t first_row = 0,
-                          std::string* vcf = nullptr, wfm_coverage_t* coverage = nullptr, const std::vector<uint64_t>* seq_offsets = nullptr,
-                          std::string* lift = nullptr, const wfm_liftset_t* liftset = nullptr, const std::vector<lift::Interval>* lift_intervals = nullptr,
-                          wfm_pav_t* pav = nullptr, const std::vector<uint32_t>* pav_columns = nullptr,
-                          std::string* chain = nullptr, bool chain_swap = false, wfm_sites_t* sites = nullptr, uint32_t sites_groups = 0,
-                          wfm_net_t* net = nullptr, uint64_t net_batch = 0, std::vector<wflign::NetHead>* net_heads = nullptr,
-                          wfm_trans_t* trans = nullptr, const std::vector<uint64_t>* query_world = nullptr);
+  // (passes: which of the driver's passes are on, this handle's objects for them, the batch's number and the run's tables -- the default:
+  // none.  Returns the batch's text and what the passes leave per batch)
+  wflign::BatchTexts align_batch(wfm_handle_t* gpu, std::vector<std::string>& lines, int threads, Summary& sum, uint64_t first_row = 0,
+                                 const wflign::BatchPasses& passes = wflign::BatchPasses());
   std::vector<Fetched> parse_rows(std::vector<std::string>& lines, uint64_t first_row, Summary& sum) const;
   void fetch_windows(Fetched& f) const;
   std::vector<Fetched> fetch_eager(std::vector<Fetched>& rows, int threads, Summary& sum) const;
@@ -132,12 +120,8 @@ class Aligner {
   struct Run;  // what the workers of one compute() share
   struct RunPlan { size_t per_gpu = 1, nworkers = 1; uint64_t batch_bytes = ~0ull; };
   RunPlan plan_run(std::ifstream& in) const;
+  void make_passes(Run& run) const;  // the across-record outputs whose switches are on (--variants ... --transitive), in their order
   void run_worker(Run& run, size_t wk);
-  void finish_coverage(Run& run, std::ofstream& out);  // --coverage: the handles' depth objects merged into one, its intervals as a bedGraph
-  void finish_pav(Run& run, std::ofstream& out, uint64_t bed_skipped);  // --pav: the handles' presence objects merged into one, its table as TSV
-  void finish_genotypes(Run& run, std::ofstream& out);  // --genotypes: the handles' sites objects merged into one, its table as a VCF
-  void finish_chain_net(Run& run, std::ofstream& out);  // --chain-net: the handles' net objects merged into one, its pieces as a chain file
-  void finish_transitive(Run& run, std::ofstream& out);  // --transitive: the handles' trans objects merged into one, the seeds' closure as text
   void sum_up(Summary& sum, const std::vector<Summary>& part, std::chrono::steady_clock::time_point t0) const;
   const Parameters& param;
   std::vector<wfm_handle_t*> gpus;

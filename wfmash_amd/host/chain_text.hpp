@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <string>
+#include <vector>
 
 namespace chain {
 
@@ -99,6 +100,37 @@ inline uint64_t number(const std::string& text, uint64_t* next, std::string& out
     at = nl + 1;
   }
   return n;
+}
+
+// --chain-net: what a record's chain needs beside its pieces, kept on the host under the order the record went to the net object with
+struct NetHead {
+  uint64_t order = 0;
+  uint64_t t_offset = 0;  // where the target sequence begins in the concatenation
+  Record rec;
+};
+// a record of the table as wfm_net_table gives it (wfm_netcall_t)
+struct NetCall { uint64_t order; uint32_t score, zero; uint64_t first, count, bases_won, bases_aligned; };
+
+// The file of --chain-net from the table of a net object: heads = what was kept of every record added, sorted by order as per[0, n_rec) is;
+// a record's pieces are pieces[first, first + count).  The chains go to `out` (anything that takes << of a string) with their ids, a MiB at
+// a time; *chains = the chains written, *lost = the records that won nothing.  false: the table's records are not the records added.
+template <class Sink>
+inline bool net_file(Sink& out, const std::vector<NetHead>& heads, const NetCall* per, size_t n_rec, const Piece* pieces, uint64_t* chains, uint64_t* lost) {
+  *chains = *lost = 0;
+  if (heads.size() != n_rec) return false;
+  std::string body, text;
+  uint64_t next = 1;
+  for (size_t i = 0; i < n_rec; ++i) {
+    const NetHead& hd = heads[i];
+    if (hd.order != per[i].order) return false;
+    if (per[i].count == 0) { ++*lost; continue; }
+    net_body(body, hd.rec, hd.t_offset, per[i].score, pieces + per[i].first, per[i].count);
+    if (body.size() >= ((size_t)1 << 20)) { text.clear(); *chains += number(body, &next, text); out << text; body.clear(); }
+  }
+  text.clear();
+  *chains += number(body, &next, text);
+  out << text;
+  return true;
 }
 
 }  // namespace chain

@@ -54,6 +54,14 @@ inline std::string coverage_bedgraph(const std::vector<std::string>& names, cons
   return out;
 }
 
+// the same from the intervals as wfm_coverage_intervals gives them (Raw: wfm_cov_interval_t, or anything with its start and depth)
+template <class Raw>
+inline std::string coverage_bedgraph(const std::vector<std::string>& names, const std::vector<uint64_t>& lengths, const Raw* raw, size_t n, uint64_t* lines) {
+  std::vector<Interval> iv(n);
+  for (size_t i = 0; i < n; ++i) iv[i] = Interval{raw[i].start, raw[i].depth};
+  return coverage_bedgraph(names, lengths, iv, lines);
+}
+
 // What --coverage-paf makes of a line.  LINE_ADD: its runs count, at base = the target sequence's offset + ts.  Everything else is
 // skipped and counted: no cg:Z: tag or an op outside =XID, a malformed line (verify::parse_line's rules, or a CIGAR whose target
 // bases are not te - ts), a target name the file does not have, a tlen that is not the file's.

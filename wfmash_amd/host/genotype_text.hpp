@@ -94,4 +94,19 @@ inline void site_line(std::string& out, const std::vector<Site>& sites, size_t i
   line(out, names[c], s.pos - offsets[c] + 1, alleles + s.off, s.ref_len, alleles + s.off + s.ref_len, s.alt_len, gt + i * n_groups, n_groups);
 }
 
+// The file of --genotypes from the table of a sites object (Raw: wfm_site_t, or anything with Site's fields): the header, then the sites'
+// lines in order()'s order; gt: n_sites x keys.size() cells.  The text goes to `out` (anything that takes << of a string) a MiB at a time.
+template <class Sink, class Raw>
+inline void vcf(Sink& out, const std::string& version, const std::vector<std::string>& names, const std::vector<uint64_t>& lengths,
+                const std::vector<uint64_t>& offsets, const std::vector<std::string>& keys, const Raw* rows, size_t n_sites, const char* alleles, const char* gt) {
+  std::vector<Site> sites(n_sites);
+  for (size_t i = 0; i < n_sites; ++i) sites[i] = Site{rows[i].pos, rows[i].ref_len, rows[i].alt_len, rows[i].off};
+  std::string text = header(version, names, lengths, keys);
+  for (size_t i : order(sites, alleles)) {
+    site_line(text, sites, i, alleles, gt, keys.size(), names, offsets);
+    if (text.size() >= ((size_t)1 << 20)) { out << text; text.clear(); }
+  }
+  out << text;
+}
+
 }  // namespace genotype

@@ -81,4 +81,18 @@ inline void row(std::string& out, const std::string& tname, const lift::Interval
   out += '\n';
 }
 
+// The file of --pav: the header, then one row per interval in the order given; cells: n_iv x n_groups, row-major, as wfm_pav_matrix fills
+// them; tnames: the target's sequences.  The text goes to `out` (anything that takes << of a string) a MiB at a time.
+template <class Sink>
+inline void table(Sink& out, const std::vector<std::string>& keys, const std::vector<std::string>& tnames, const std::vector<lift::Interval>& iv,
+                  const uint32_t* cells) {
+  const size_t G = keys.size();
+  std::string text = header(keys);
+  for (size_t j = 0; j < iv.size(); ++j) {
+    row(text, tnames[(size_t)iv[j].seq], iv[j], cells + j * G, G);
+    if (text.size() >= ((size_t)1 << 20)) { out << text; text.clear(); }
+  }
+  out << text;
+}
+
 }  // namespace pav

@@ -75,4 +75,24 @@ inline uint64_t lines(std::string& out, const World& w, const lift::Interval& se
   return n;
 }
 
+// an interval of the closure and a seed's share of them, as wfm_trans_closure gives them (wfm_trans_iv_t, wfm_trans_seed_t)
+struct ClosureIv { uint64_t start, end; uint32_t seed, pad_; };
+struct SeedCall { uint64_t first, count, bases; };
+
+// The file of --transitive: per seed, in the order given, the lines of its intervals ivs[first, first + count).  ivs null: no record was
+// added, and a seed reaches itself.  The text goes to `out` (anything that takes << of a string) a MiB at a time.  Returns the lines written.
+template <class Sink>
+inline uint64_t file(Sink& out, const World& w, const std::vector<lift::Interval>& seeds, const SeedCall* per, const ClosureIv* ivs) {
+  std::string text;
+  uint64_t n = 0;
+  for (size_t i = 0; i < seeds.size(); ++i) {
+    if (!ivs) n += lines(text, w, seeds[i], seeds[i].gstart, seeds[i].gend);
+    else
+      for (uint64_t k = per[i].first; k < per[i].first + per[i].count; ++k) n += lines(text, w, seeds[i], ivs[k].start, ivs[k].end);
+    if (text.size() >= ((size_t)1 << 20)) { out << text; text.clear(); }
+  }
+  out << text;
+  return n;
+}
+
 }  // namespace transitive

@@ -191,6 +191,7 @@ struct PafRuns {
   wfm_handle_t* h;
   const char* tag;                      // "coverage", "lift", "pav": the [wfmash::...] of the texts
   const wfmash_host::FastaStore& target;
+  std::vector<std::string> names;
   std::vector<uint64_t> lengths, offsets;
   uint64_t skipped[5] = {0, 0, 0, 0, 0};  // by coverage::LINE_*
   std::vector<wfm_cov_prob_t> probs;    // the batch at hand: base, runs_off, n_runs of every line
@@ -198,6 +199,7 @@ struct PafRuns {
 
   PafRuns(wfm_handle_t* h_, const char* tag_, const wfmash_host::FastaStore& target_) : h(h_), tag(tag_), target(target_), offsets(1, 0) {
     for (int i = 0; i < target.nseq(); ++i) {
+      names.push_back(target.name(i));
       lengths.push_back((uint64_t)target.length(i));
       offsets.push_back(offsets.back() + lengths.back());
     }
@@ -208,6 +210,13 @@ struct PafRuns {
   }
   void refused(uint64_t n) { skipped[coverage::LINE_MALFORMED] += n; }  // (a span that leaves the target: classify_line lets none through)
   uint64_t all_skipped() const { return skipped[1] + skipped[2] + skipped[3] + skipped[4]; }
+  // "N skipped (... without an =XID cg:Z:, ... malformed, ...)" of the summaries; no_query: the lines the caller left out for their query
+  std::string skipped_clause(const char* noun = "", const uint64_t* no_query = nullptr) const {
+    std::string s = std::to_string(all_skipped() + (no_query ? *no_query : 0)) + " " + noun + "skipped (" + std::to_string(skipped[1]) + " without an =XID cg:Z:, " +
+                    std::to_string(skipped[2]) + " malformed, " + std::to_string(skipped[3]) + " with an unknown target, " + std::to_string(skipped[4]) + " with another tlen";
+    if (no_query) s += ", " + std::to_string(*no_query) + " with an unknown query";
+    return s + ")";
+  }
   // extra(line) -> false: the line is not taken (the caller counts it); flush(): the batch to the device, whatever extra kept given back
   template <class Extra, class Flush>
   void read(std::istream& in, Extra extra, Flush flush) {
@@ -282,11 +291,7 @@ int wfmh_coverage_paf(wfm_handle_t* h, const char* target_fasta, const char* ali
     if (!in.is_open()) throw std::runtime_error(std::string("[wfmash::coverage] cannot open ") + aligned_paf);
     std::ofstream outstream(out_path);
     if (!outstream.is_open()) throw std::runtime_error(std::string("[wfmash::coverage] cannot open ") + out_path);
-    std::vector<std::string> names;
-    for (int i = 0; i < target->nseq(); ++i) names.push_back(target->name(i));
     PafRuns pr(h, "coverage", *target);
-    const std::vector<uint64_t>& lengths = pr.lengths;
-    const uint64_t* skipped = pr.skipped;
     std::lock_guard<std::mutex> lk(wflign::handle_lock(h));
     pr.device(wfm_coverage_create(h, pr.offsets.back(), &cov), "create");
     uint64_t added = 0;
@@ -301,18 +306,14 @@ int wfmh_coverage_paf(wfm_handle_t* h, const char* target_fasta, const char* ali
     size_t n = 0;
     uint64_t totals[3] = {0, 0, 0};
     pr.device(wfm_coverage_intervals(h, cov, &d_iv, &n, totals), "intervals");
-    std::vector<coverage::Interval> iv(n);
-    for (size_t i = 0; i < n; ++i) iv[i] = coverage::Interval{d_iv[i].start, d_iv[i].depth};
-    wfm_coverage_free_list(d_iv);
     wfm_coverage_free(cov);
     cov = nullptr;
     uint64_t lines = 0;
-    outstream << coverage::coverage_bedgraph(names, lengths, iv, &lines);
-    const uint64_t all_skipped = pr.all_skipped();
-    std::cerr << "[wfmash::coverage] " << added << " lines added, " << all_skipped << " skipped (" << skipped[1] << " without an =XID cg:Z:, " << skipped[2]
-              << " malformed, " << skipped[3] << " with an unknown target, " << skipped[4] << " with another tlen), " << totals[0] << " bases covered, sum of depth "
-              << totals[1] << ", max depth " << totals[2] << ", " << lines << " intervals" << std::endl;
-    if (out) { out[0] = added; out[1] = all_skipped; out[2] = totals[0]; out[3] = totals[1]; }
+    outstream << coverage::coverage_bedgraph(pr.names, pr.lengths, d_iv, n, &lines);
+    wfm_coverage_free_list(d_iv);
+    std::cerr << "[wfmash::coverage] " << added << " lines added, " << pr.skipped_clause() << ", " << totals[0] << " bases covered, sum of depth " << totals[1]
+              << ", max depth " << totals[2] << ", " << lines << " intervals" << std::endl;
+    if (out) { out[0] = added; out[1] = pr.all_skipped(); out[2] = totals[0]; out[3] = totals[1]; }
     return WFM_OK;
   } catch (const std::exception& e) {
     if (cov) wfm_coverage_free(cov);
@@ -337,7 +338,6 @@ int wfmh_lift_paf(wfm_handle_t* h, const char* target_fasta, const char* aligned
     std::ofstream outstream(out_path);
     if (!outstream.is_open()) throw std::runtime_error(std::string("[wfmash::lift] cannot open ") + out_path);
     PafRuns pr(h, "lift", *target);
-    const uint64_t* skipped = pr.skipped;
     const lift::Bed bed = lift::parse_bed(bed_text, [&](const std::string& name) { return target->find(name); }, pr.lengths, pr.offsets);
     std::lock_guard<std::mutex> lk(wflign::handle_lock(h));
     {
@@ -377,10 +377,8 @@ int wfmh_lift_paf(wfm_handle_t* h, const char* target_fasta, const char* aligned
     }, flush);
     wfm_liftset_free(set);
     set = nullptr;
-    const uint64_t all_skipped = pr.all_skipped();
-    std::cerr << "[wfmash::lift] " << bed.iv.size() << " intervals (" << bed.skipped << " BED lines skipped), " << lifted << " lines lifted, " << all_skipped
-              << " skipped (" << skipped[1] << " without an =XID cg:Z:, " << skipped[2] << " malformed, " << skipped[3] << " with an unknown target, " << skipped[4]
-              << " with another tlen), " << n_lines << " lifts written, " << empty << " of them empty" << std::endl;
+    std::cerr << "[wfmash::lift] " << bed.iv.size() << " intervals (" << bed.skipped << " BED lines skipped), " << lifted << " lines lifted, " << pr.skipped_clause()
+              << ", " << n_lines << " lifts written, " << empty << " of them empty" << std::endl;
     if (out) { out[0] = lifted; out[1] = n_lines; out[2] = empty; out[3] = bed.skipped; }
     return WFM_OK;
   } catch (const std::exception& e) {
@@ -402,7 +400,6 @@ int wfmh_chain_paf(wfm_handle_t* h, const char* target_fasta, const char* aligne
     std::ofstream outstream(out_path);
     if (!outstream.is_open()) throw std::runtime_error(std::string("[wfmash::chain] cannot open ") + out_path);
     PafRuns pr(h, "chain", *target);
-    const uint64_t* skipped = pr.skipped;
     std::lock_guard<std::mutex> lk(wflign::handle_lock(h));
     uint64_t chains = 0, n_blocks = 0, refused = 0, next = 1;
     std::vector<chain::Record> where;
@@ -436,9 +433,7 @@ int wfmh_chain_paf(wfm_handle_t* h, const char* target_fasta, const char* aligne
       where.push_back(std::move(r));
       return true;
     }, flush);
-    const uint64_t all_skipped = pr.all_skipped();
-    std::cerr << "[wfmash::chain] " << chains << " chains written, " << n_blocks << " blocks, " << all_skipped << " lines skipped (" << skipped[1]
-              << " without an =XID cg:Z:, " << skipped[2] << " malformed, " << skipped[3] << " with an unknown target, " << skipped[4] << " with another tlen)" << std::endl;
+    std::cerr << "[wfmash::chain] " << chains << " chains written, " << n_blocks << " blocks, " << pr.skipped_clause("lines ") << std::endl;
     if (out) { out[0] = chains; out[1] = n_blocks; out[2] = refused; out[3] = 0; }
     return WFM_OK;
   } catch (const std::exception& e) {
@@ -460,11 +455,10 @@ int wfmh_chain_net_paf(wfm_handle_t* h, const char* target_fasta, const char* al
     std::ofstream outstream(out_path);
     if (!outstream.is_open()) throw std::runtime_error(std::string("[wfmash::chain-net] cannot open ") + out_path);
     PafRuns pr(h, "chain-net", *target);
-    const uint64_t* skipped = pr.skipped;
     std::lock_guard<std::mutex> lk(wflign::handle_lock(h));
     pr.device(wfm_net_create(h, pr.offsets.back(), &net), "create");
-    std::vector<chain::Record> where, kept;   // of the batch; of every line added, in the order of their orders
-    std::vector<uint64_t> kept_off;
+    std::vector<chain::Record> where;   // of the batch
+    std::vector<chain::NetHead> kept;   // of every line added, in the order of their orders
     std::vector<wfm_net_prob_t> probs;
     std::vector<uint32_t> flags;
     uint64_t taken = 0;
@@ -475,8 +469,7 @@ int wfmh_chain_net_paf(wfm_handle_t* h, const char* target_fasta, const char* al
       const int refused = pr.device(wfm_net_add(h, net, probs.data(), probs.size(), pr.runs.data(), pr.runs.size(), flags.data()), "add");
       for (size_t j = 0; j < probs.size(); ++j) {
         if (flags[j]) continue;
-        kept_off.push_back(pr.probs[j].base - where[j].ts);  // (the base is the sequence's offset + the line's target start)
-        kept.push_back(std::move(where[j]));
+        kept.push_back(chain::NetHead{probs[j].order, pr.probs[j].base - where[j].ts, std::move(where[j])});  // (the base is the sequence's offset + the line's target start)
       }
       pr.refused((uint64_t)refused);
       taken += probs.size();
@@ -495,23 +488,13 @@ int wfmh_chain_net_paf(wfm_handle_t* h, const char* target_fasta, const char* al
     pr.device(wfm_net_table(h, net, &pieces, &n_pieces, &per, &n_rec), "table");
     wfm_net_free(net);
     net = nullptr;
-    static_assert(sizeof(chain::Piece) == sizeof(wfm_net_piece_t), "chain_text.hpp restates wfm_net_piece_t");
-    if (n_rec != kept.size()) { wfm_net_free_list(pieces); wfm_net_free_list(per); throw std::runtime_error("[wfmash::chain-net] the table's records are not the lines added"); }
-    std::string body, text;
-    uint64_t next = 1, chains = 0, lost = 0;
-    for (size_t i = 0; i < n_rec; ++i) {  // (per is sorted by order, as kept is)
-      if (per[i].count == 0) { ++lost; continue; }
-      chain::net_body(body, kept[i], kept_off[i], per[i].score, (const chain::Piece*)pieces + per[i].first, per[i].count);
-      if (body.size() >= ((size_t)1 << 20)) { text.clear(); chains += chain::number(body, &next, text); outstream << text; body.clear(); }
-    }
-    text.clear();
-    chains += chain::number(body, &next, text);
-    outstream << text;
+    static_assert(sizeof(chain::Piece) == sizeof(wfm_net_piece_t) && sizeof(chain::NetCall) == sizeof(wfm_netcall_t), "chain_text.hpp restates wfm_net_piece_t and wfm_netcall_t");
+    uint64_t chains = 0, lost = 0;
+    const bool same = chain::net_file(outstream, kept, (const chain::NetCall*)per, n_rec, (const chain::Piece*)pieces, &chains, &lost);
     wfm_net_free_list(pieces); wfm_net_free_list(per);
-    const uint64_t all_skipped = pr.all_skipped();
+    if (!same) throw std::runtime_error("[wfmash::chain-net] the table's records are not the lines added");
     std::cerr << "[wfmash::chain-net] " << n_rec << " lines added, " << chains << " chains written, " << n_pieces << " pieces, " << lost << " lines won nothing, "
-              << all_skipped << " lines skipped (" << skipped[1] << " without an =XID cg:Z:, " << skipped[2] << " malformed, " << skipped[3]
-              << " with an unknown target, " << skipped[4] << " with another tlen)" << std::endl;
+              << pr.skipped_clause("lines ") << std::endl;
     if (out) { out[0] = n_rec; out[1] = chains; out[2] = n_pieces; out[3] = lost; }
     return WFM_OK;
   } catch (const std::exception& e) {
@@ -536,7 +519,6 @@ int wfmh_pav_paf(wfm_handle_t* h, const char* target_fasta, const char* query_fa
     if (!in.is_open()) throw std::runtime_error(std::string("[wfmash::pav] cannot open ") + aligned_paf);
     PafRuns pr(h, "pav", *target);
     const std::vector<uint64_t>&lengths = pr.lengths, &offsets = pr.offsets;
-    const uint64_t* skipped = pr.skipped;
     std::vector<lift::Interval> iv;
     uint64_t bed_skipped = 0;
     if (with_bed) {
@@ -582,16 +564,9 @@ int wfmh_pav_paf(wfm_handle_t* h, const char* target_fasta, const char* query_fa
     wfm_pav_counts(obj, counts);
     wfm_pav_free(obj);
     obj = nullptr;
-    std::string text = pav::header(cols.keys);
-    for (size_t j = 0; j < iv.size(); ++j) {
-      pav::row(text, target->name(iv[j].seq), iv[j], cells.data() + j * G, G);
-      if (text.size() >= ((size_t)1 << 20)) { outstream << text; text.clear(); }
-    }
-    outstream << text;
-    const uint64_t all_skipped = pr.all_skipped() + no_query;
-    std::cerr << "[wfmash::pav] " << iv.size() << " intervals (" << bed_skipped << " BED lines skipped) x " << G << " groups, " << added << " lines added, " << all_skipped
-              << " skipped (" << skipped[1] << " without an =XID cg:Z:, " << skipped[2] << " malformed, " << skipped[3] << " with an unknown target, " << skipped[4]
-              << " with another tlen, " << no_query << " with an unknown query), " << counts[1] << " union intervals" << std::endl;
+    pav::table(outstream, cols.keys, pr.names, iv, cells.data());
+    std::cerr << "[wfmash::pav] " << iv.size() << " intervals (" << bed_skipped << " BED lines skipped) x " << G << " groups, " << added << " lines added, "
+              << pr.skipped_clause("", &no_query) << ", " << counts[1] << " union intervals" << std::endl;
     if (out) { out[0] = added; out[1] = iv.size(); out[2] = counts[1]; out[3] = bed_skipped; }
     return WFM_OK;
   } catch (const std::exception& e) {
@@ -618,12 +593,10 @@ int wfmh_transitive_paf(wfm_handle_t* h, const char* target_fasta, const char* q
     if (!bedstream.is_open()) throw std::runtime_error(std::string("[wfmash::transitive] cannot open ") + bed_path);
     const std::string bed_text((std::istreambuf_iterator<char>(bedstream)), std::istreambuf_iterator<char>());
     PafRuns pr(h, "transitive", *target);
-    const uint64_t* skipped = pr.skipped;
-    std::vector<std::string> tnames, qnames;
+    std::vector<std::string> qnames;
     std::vector<uint64_t> qlengths;
-    for (int i = 0; i < target->nseq(); ++i) tnames.push_back(target->name(i));
     for (int i = 0; i < query->nseq(); ++i) { qnames.push_back(query->name(i)); qlengths.push_back((uint64_t)query->length(i)); }
-    const transitive::World world = transitive::make_world(tnames, pr.lengths, qnames, qlengths);
+    const transitive::World world = transitive::make_world(pr.names, pr.lengths, qnames, qlengths);
     if (world.n_bases() >= ((uint64_t)1 << 40)) throw std::runtime_error("[wfmash::transitive] the sequences hold 2^40 bases or more");
     const lift::Bed seeds = transitive::parse_seeds(bed_text, world);
     if (seeds.iv.size() >= ((size_t)1 << 24)) throw std::runtime_error("[wfmash::transitive] the BED holds 2^24 seeds or more");
@@ -660,18 +633,12 @@ int wfmh_transitive_paf(wfm_handle_t* h, const char* target_fasta, const char* q
     wfm_trans_counts(obj, counts);
     wfm_trans_free(obj);
     obj = nullptr;
-    std::string text;
-    uint64_t lines = 0;
-    for (size_t i = 0; i < seeds.iv.size(); ++i) {
-      for (uint64_t k = per[i].first; k < per[i].first + per[i].count; ++k) lines += transitive::lines(text, world, seeds.iv[i], ivs[k].start, ivs[k].end);
-      if (text.size() >= ((size_t)1 << 20)) { outstream << text; text.clear(); }
-    }
-    outstream << text;
+    static_assert(sizeof(transitive::ClosureIv) == sizeof(wfm_trans_iv_t) && sizeof(transitive::SeedCall) == sizeof(wfm_trans_seed_t),
+                  "transitive_text.hpp restates wfm_trans_iv_t and wfm_trans_seed_t");
+    const uint64_t lines = transitive::file(outstream, world, seeds.iv, (const transitive::SeedCall*)per.data(), (const transitive::ClosureIv*)ivs);
     wfm_trans_free_list(ivs);
-    const uint64_t all_skipped = pr.all_skipped() + no_query;
-    std::cerr << "[wfmash::transitive] " << seeds.iv.size() << " seeds (" << seeds.skipped << " BED lines skipped), " << added << " lines added, " << all_skipped
-              << " skipped (" << skipped[1] << " without an =XID cg:Z:, " << skipped[2] << " malformed, " << skipped[3] << " with an unknown target, " << skipped[4]
-              << " with another tlen, " << no_query << " with an unknown query), " << counts[3] << " rounds, " << lines << " lines written" << std::endl;
+    std::cerr << "[wfmash::transitive] " << seeds.iv.size() << " seeds (" << seeds.skipped << " BED lines skipped), " << added << " lines added, "
+              << pr.skipped_clause("", &no_query) << ", " << counts[3] << " rounds, " << lines << " lines written" << std::endl;
     if (out) { out[0] = added; out[1] = lines; out[2] = counts[3]; out[3] = seeds.skipped; }
     return WFM_OK;
   } catch (const std::exception& e) {

@@ -46,71 +46,24 @@ std::mutex& handle_lock(wfm_handle_t* h) {
 }
 namespace {
 
-// --verify-optimal: the process-wide switch, the cap of one problem's DP cells (0: none) and {problems checked (the skipped among them), failed,
-// skipped, cells} since it was set
-std::atomic<bool> g_optimal{false};
-std::atomic<uint64_t> g_optimal_cells{0};
-std::atomic<uint64_t> g_optimal_counts[4];
-
-// --left-align: the process-wide switch and {records handed to the device, their interior gaps, gaps moved, records left alone} since it was set
-std::atomic<bool> g_left_align{false};
-std::atomic<uint64_t> g_left_align_counts[4];
-
-// --cs: the process-wide switch (0 off, 1 short, 2 long) and {records spelled, bytes spelled, records left without a string, 0} since it was set
-std::atomic<int> g_cs{0};
-std::atomic<uint64_t> g_cs_counts[4];
-
-// --variants: the process-wide switch, the file the align phase writes and {records called, variants written, SNVs masked, records left
-// alone} since it was set
-std::atomic<bool> g_variants{false};
-std::mutex g_variants_mu;
-std::string g_variants_path;
-std::atomic<uint64_t> g_variants_counts[4];
-
-// --coverage: the process-wide switch, the file the align phase writes and {records added, target bases with depth >= 1, sum of depth,
-// intervals written} since it was set
-std::atomic<bool> g_coverage{false};
-std::mutex g_coverage_mu;
-std::string g_coverage_path;
-std::atomic<uint64_t> g_coverage_counts[4];
-
-// --lift: the process-wide switch, the BED of target intervals and the file the align phase writes, and {records lifted, lines written,
-// empty lifts, BED lines skipped} since it was set
-std::atomic<bool> g_lift{false};
-std::mutex g_lift_mu;
-std::string g_lift_bed, g_lift_out;
-std::atomic<uint64_t> g_lift_counts[4];
-std::atomic<bool> g_chain{false}, g_chain_swap{false};
-std::mutex g_chain_mu;
-std::string g_chain_out;
-std::atomic<uint64_t> g_chain_counts[4];
-std::atomic<bool> g_chain_net{false};
-std::mutex g_chain_net_mu;
-std::string g_chain_net_out;
-std::atomic<uint64_t> g_chain_net_counts[4];
-
-// --transitive: the process-wide switch, the BED of seeds, the file the align phase writes and the depth, and {records added, lines
-// written, rounds run, BED lines skipped} since it was set
-std::atomic<bool> g_transitive{false};
-std::mutex g_transitive_mu;
-std::string g_transitive_bed, g_transitive_out;
-uint32_t g_transitive_depth = 2;
-std::atomic<uint64_t> g_transitive_counts[4];
-
-// --pav: the process-wide switch, the BED of target intervals or the window size, the file the align phase writes, and {records added,
-// rows written, union intervals, BED lines skipped} since it was set
-std::atomic<bool> g_pav{false};
-std::mutex g_pav_mu;
-std::string g_pav_bed, g_pav_out;
-uint64_t g_pav_window = 0;
-std::atomic<uint64_t> g_pav_counts[4];
-
-// --genotypes: the process-wide switch, the file the align phase writes and {records added, sites written, variants merged away, records
-// left alone} since it was set
-std::atomic<bool> g_genotypes{false};
-std::mutex g_genotypes_mu;
-std::string g_genotypes_path;
-std::atomic<uint64_t> g_genotypes_counts[4];
+// One process-wide switch (wflign_hip.hpp names them): whether it is on, what wfmh_set_* named -- up to two paths under the mutex, one
+// integer -- and four counts since it was set.  The counts: --verify-optimal {problems checked (the skipped among them), failed, skipped,
+// cells}; --left-align {records handed to the device, their interior gaps, gaps moved, records left alone}; --cs {records spelled, bytes
+// spelled, records left without a string, 0}; --variants {records called, variants written, SNVs masked, records left alone}; --coverage
+// {records added, target bases with depth >= 1, sum of depth, intervals written}; --lift {records lifted, lines written, empty lifts, BED
+// lines skipped}; --chain {chains written, blocks, records refused, 0}; --chain-net {records added, chains written, pieces, records that
+// won nothing}; --transitive {records added, lines written, rounds run, BED lines skipped}; --pav {records added, rows written, union
+// intervals, BED lines skipped}; --genotypes {records added, sites written, variants merged away, records left alone}.
+struct Switch {
+  std::atomic<bool> on{false};
+  std::mutex mu;
+  std::string out, bed;
+  std::atomic<uint64_t> option{0};  // --verify-optimal: the cap of one problem's DP cells (0: none); --cs: 1 short, 2 long; SwitchSetting's otherwise
+  std::atomic<uint64_t> counts[4];
+};
+Switch g_switch[N_SWITCHES];
+bool is_on(SwitchId id) { return g_switch[id].on.load(std::memory_order_relaxed); }
+std::atomic<uint64_t>* counts_of(SwitchId id) { return g_switch[id].counts; }
 
 // The problems of one device call, always written by reference (a side without a store id carries its host pointer); without a
 // store they go to the device as plain wfm_problem_t, as they always have.
@@ -134,7 +87,7 @@ struct GpuBatch {
     rc = wfm_align_resident_rle(h, &pen, S, res.data(), &runs, nullptr);
     if (rc >= 0) {
       std::vector<wfm_optcheck_t> oc(probs.size());
-      const int crc = wfm_check_optimal(h, &pen, S, res.data(), g_optimal_cells.load(), oc.data());
+      const int crc = wfm_check_optimal(h, &pen, S, res.data(), g_switch[SW_VERIFY_OPTIMAL].option.load(), oc.data());
       if (crc < 0) rc = crc;
       else report_optimal(oc);
     }
@@ -164,7 +117,8 @@ struct GpuBatch {
       fprintf(stderr, "[wfmash::verify] %s %s (%s, %s, %d x %d bases): claimed score %d, DP score %d\n", (o.flags & WFM_OPT_CHEAPER) ? "NOT OPTIMAL" : "UNREACHED",
               where.c_str(), part, mname, probs[i].plen, probs[i].tlen, res[i].score, o.dp_score);
     }
-    g_optimal_counts[0] += checked; g_optimal_counts[1] += failed; g_optimal_counts[2] += skipped; g_optimal_counts[3] += cells;
+    std::atomic<uint64_t>* c = counts_of(SW_VERIFY_OPTIMAL);
+    c[0] += checked; c[1] += failed; c[2] += skipped; c[3] += cells;
   }
   int run(wfm_handle_t* h, const wfm_penalties_t& pen, BiwfaStats* st) {
     res.assign(probs.size(), wfm_result_t{});
@@ -182,7 +136,7 @@ struct GpuBatch {
                                  r.text_begin_free, r.text_end_free, r.score_hint, 0};
       }
     }
-    if (g_optimal.load()) rc = run_checked(h, pen, plain);  // --verify-optimal: the same call in its parts, the seqset kept for the check
+    if (is_on(SW_VERIFY_OPTIMAL)) rc = run_checked(h, pen, plain);  // --verify-optimal: the same call in its parts, the seqset kept for the check
     else if (store) rc = wfm_align_refs_rle(h, &pen, store, probs.data(), probs.size(), res.data(), &runs, nullptr);
     else rc = wfm_align_batch_rle(h, &pen, plain.data(), plain.size(), res.data(), &runs, nullptr);
     if (rc < 0) err = wfm_last_error(h);
@@ -280,6 +234,8 @@ struct BiwfaBatch {
   const OutputFormat& fmt;
   ResidentSeqs* resident;
   const wfm_seqstore_t* store;
+  const BatchPasses* passes;  // the align driver's passes: which are on, their objects on this handle, the run's tables
+  BatchTexts* texts;          // ... and where what they leave per batch goes (null: nowhere)
   struct Work {
     PatchPlan plan;
     int head_slot = -1, tail_slot = -1;  // problem index in the patch call
@@ -515,7 +471,8 @@ int left_align_records(BiwfaBatch& b, bool keep) {
   const auto t0 = Clock::now();
   b.windows = window_parts(b, keep ? 1 : 3);
   WindowSet& w = *b.windows;
-  g_left_align_counts[0] += w.unknown; g_left_align_counts[3] += w.unknown;
+  std::atomic<uint64_t>* c = counts_of(SW_LEFT_ALIGN);
+  c[0] += w.unknown; c[3] += w.unknown;
   if (w.parts.empty()) return 0;
   const size_t n = w.parts.size();
   std::vector<wfm_leftalign_t> la(n);
@@ -543,7 +500,7 @@ int left_align_records(BiwfaBatch& b, bool keep) {
     all.insert(all.end(), ops.begin() + (long)pt.e, ops.end());
     ops.swap(all);
   });
-  g_left_align_counts[0] += n; g_left_align_counts[1] += gaps.load(); g_left_align_counts[2] += moved.load(); g_left_align_counts[3] += alone.load();
+  c[0] += n; c[1] += gaps.load(); c[2] += moved.load(); c[3] += alone.load();
   if (getenv("WFM_DEBUG"))
     fprintf(stderr, "[wflign] left-align: %zu records, %zu runs, %llu gaps, %llu moved, %llu left alone, %.1f ms (upload, device call, splice)\n", n, w.runs.size(),
             (unsigned long long)gaps.load(), (unsigned long long)moved.load(), (unsigned long long)alone.load(), ms_between(t0, Clock::now()));
@@ -639,7 +596,7 @@ int variant_records(BiwfaBatch& b) {
                                          r.query_is_rev ? '-' : '+'));
     }
   });
-  if (b.fmt.sites) {
+  if (b.passes->on[SW_GENOTYPES]) {
     b.calls.reset(new KeptCalls());
     b.calls->vars = vars; b.calls->alleles = alleles;
     b.calls->per = std::move(per);
@@ -657,9 +614,10 @@ int variant_records(BiwfaBatch& b) {
 // --variants: a record's lines go out with its line or not at all
 void account_variants(BiwfaRecord& r, bool written) {
   if (!written) { r.vcf.clear(); return; }
-  if (!r.vcf_called) { g_variants_counts[3] += 1; return; }  // (flagged by the device, or runs it cannot hold)
-  g_variants_counts[0] += 1; g_variants_counts[2] += r.vcf_masked;
-  g_variants_counts[1] += (uint64_t)std::count(r.vcf.begin(), r.vcf.end(), '\n');
+  std::atomic<uint64_t>* c = counts_of(SW_VARIANTS);
+  if (!r.vcf_called) { c[3] += 1; return; }  // (flagged by the device, or runs it cannot hold)
+  c[0] += 1; c[2] += r.vcf_masked;
+  c[1] += (uint64_t)std::count(r.vcf.begin(), r.vcf.end(), '\n');
 }
 
 // ---- record (wflign.cpp:434-454) ----
@@ -679,16 +637,16 @@ void write_record(BiwfaBatch& b, size_t ri) {
   r.written = written;
   if (b.variants) account_variants(r, written);
   if (!b.cs_form || !written) return;
-  if (r.cs.empty()) { g_cs_counts[2] += 1; return; }  // (flagged by the device, or runs it cannot hold)
+  if (r.cs.empty()) { counts_of(SW_CS)[2] += 1; return; }  // (flagged by the device, or runs it cannot hold)
   // the last field of the line, before its closing newline
   r.paf.pop_back();
   r.paf.reserve(r.paf.size() + r.cs.size() + 7);
   r.paf += "\tcs:Z:";
   r.paf += r.cs;
   r.paf += '\n';
-  g_cs_counts[0] += 1; g_cs_counts[1] += r.cs.size();
+  counts_of(SW_CS)[0] += 1; counts_of(SW_CS)[1] += r.cs.size();
 }
-// ---- the written records of a batch as --coverage, --pav and --lift take them, packed ONCE per batch.  It runs behind write_record, where
+// ---- the written records of a batch as the align driver's passes take them, packed ONCE per batch.  It runs behind write_record, where
 // the filters have spoken.  A record's problem is what its line spells: the ops trimmed of their leading and trailing I and D runs
 // (window_parts' rule, trim_and_filter's), at base = the target sequence's offset in the concatenation + the target start the writer
 // wrote -- variant_records' ts.  Nothing goes up but runs.  A record whose ops the runs cannot hold is a defect: it is in no list, and
@@ -697,14 +655,15 @@ struct PackedRuns {
   std::vector<wfm_cov_prob_t> probs;   // base, runs_off, n_runs of every record packed
   std::vector<uint32_t> runs;          // their trimmed ops as run words
   std::vector<size_t> rec;             // the record's index in the batch
-  std::vector<uint64_t> ta, qa, q_len; // the target and query bases trimmed in front; the query bases the runs spell
-  std::vector<uint64_t> t_len;         // the target bases the runs spell
+  std::vector<chain::Record> where;    // the record as its line has it: the forward windows [qs, qe) and [ts, te) the runs spell (variant_records' qs, qe), sizes,
+                                       // strand, and -- where a pass that writes them is on (--lift, --chain, --chain-net) -- the names
   uint64_t unknown = 0;                // records whose ops the runs cannot hold
   double ms = 0;                       // what the packing took
 };
 PackedRuns pack_written(const BiwfaBatch& b) {
   const auto t0 = Clock::now();
   PackedRuns pk;
+  const bool with_names = b.passes->on[SW_LIFT] || b.passes->on[SW_CHAIN] || b.passes->on[SW_CHAIN_NET];
   for (size_t ri = 0; ri < b.recs.size(); ++ri) {
     const BiwfaRecord& r = b.recs[ri];
     if (!r.ok || !r.written) continue;
@@ -727,64 +686,82 @@ PackedRuns pack_written(const BiwfaBatch& b) {
     if (!known) { pk.runs.resize((size_t)p.runs_off); ++pk.unknown; continue; }
     pk.probs.push_back(p);
     pk.rec.push_back(ri);
-    pk.ta.push_back(ta); pk.qa.push_back(qa); pk.q_len.push_back(q_len); pk.t_len.push_back(t_len);
+    chain::Record cr;
+    if (with_names) { cr.qname = r.query_name; cr.tname = r.target_name; }
+    cr.rev = r.query_is_rev;
+    cr.qsize = r.query_total_length; cr.tsize = r.target_total_length;
+    cr.qs = r.query_is_rev ? r.query_offset + (r.query_length - qa - q_len) : r.query_offset + qa;
+    cr.qe = cr.qs + q_len;
+    cr.ts = r.target_offset + ta;
+    cr.te = cr.ts + t_len;
+    pk.where.push_back(std::move(cr));
   }
   pk.ms = ms_between(t0, Clock::now());
   return pk;
 }
-// ---- --coverage: the packed runs into the depth object of the batch's handle, ONE device call per batch (wfm_coverage_add).  A record
-// the device refuses adds nothing, is counted and reported. ----
-int coverage_records(BiwfaBatch& b, const PackedRuns& pk) {
-  const auto t0 = Clock::now();
-  const std::vector<wfm_cov_prob_t>& probs = pk.probs;
-  int rc = WFM_OK;
-  if (!probs.empty()) {
-    std::vector<uint32_t> flags(probs.size());
-    std::lock_guard<std::mutex> lk(handle_lock(b.h));
-    rc = wfm_coverage_add(b.h, b.fmt.coverage, probs.data(), probs.size(), pk.runs.data(), pk.runs.size(), flags.data());
-    if (rc < 0 && b.stats) b.stats->error = wfm_last_error(b.h);
-  }
+
+// ---- the frame of the stages behind pack_written: ONE device call per batch under the handle's lock (t1: when it was had), its message
+// copied while the handle is still this thread's.  Without problems nothing is called. ----
+template <class Call>
+int device_call(BiwfaBatch& b, size_t n, Clock::time_point& t1, Call call) {
+  if (!n) return WFM_OK;
+  std::lock_guard<std::mutex> lk(handle_lock(b.h));
+  t1 = Clock::now();
+  const int rc = call();
+  if (rc < 0 && b.stats) b.stats->error = wfm_last_error(b.h);
+  return rc;
+}
+// ... and of those that add to the object of the batch's handle: the records added into the switch's count 0, and the warning -- a record
+// the device refuses (the call's return) or that never went to it (alone) adds nothing, is counted and reported.  What differs between
+// them beside that is how a problem is made of a packed record and which wfm_*_add takes them.
+struct AddStage { SwitchId sw; const char* tag; const char* not_added; };
+template <class Call>
+int add_stage(BiwfaBatch& b, const AddStage& s, size_t n, uint64_t alone, Clock::time_point& t1, Call call) {
+  const int rc = device_call(b, n, t1, call);
   if (rc < 0) return rc;
-  g_coverage_counts[0] += probs.size() - (uint64_t)rc;
-  if (rc > 0 || pk.unknown)
-    fprintf(stderr, "[wflign] coverage: %llu records of a batch were NOT added to the depth (their runs leave the target or cannot be held)\n",
-            (unsigned long long)((uint64_t)rc + pk.unknown));
+  counts_of(s.sw)[0] += n - (uint64_t)rc;
+  if (rc > 0 || alone)
+    fprintf(stderr, "[wflign] %s: %llu records of a batch were NOT added%s\n", s.tag, (unsigned long long)((uint64_t)rc + alone), s.not_added);
+  return rc;
+}
+
+// ---- --coverage: the packed runs into the depth object of the batch's handle (wfm_coverage_add) ----
+int coverage_records(BiwfaBatch& b, const PackedRuns& pk) {
+  auto t0 = Clock::now(), t1 = t0;
+  const size_t n = pk.probs.size();
+  std::vector<uint32_t> flags(n);
+  const int rc = add_stage(b, {SW_COVERAGE, "coverage", " to the depth (their runs leave the target or cannot be held)"}, n, pk.unknown, t1, [&] {
+    return wfm_coverage_add(b.h, b.passes->get<wfm_coverage_t>(SW_COVERAGE), pk.probs.data(), n, pk.runs.data(), pk.runs.size(), flags.data());
+  });
+  if (rc < 0) return rc;
   if (getenv("WFM_DEBUG"))
-    fprintf(stderr, "[wflign] coverage: %zu records, %zu runs, %d flagged, %.1f ms\n", probs.size(), pk.runs.size(), rc, pk.ms + ms_between(t0, Clock::now()));
+    fprintf(stderr, "[wflign] coverage: %zu records, %zu runs, %d flagged, %.1f ms\n", n, pk.runs.size(), rc, pk.ms + ms_between(t0, Clock::now()));
   return 0;
 }
-// ---- --pav: the same problems into the presence object of the batch's handle, each with the column of its query's group, ONE device call
-// per batch (wfm_pav_add).  A record the device refuses adds nothing, is counted and reported. ----
+// ---- --pav: the same problems into the presence object of the batch's handle, each with the column of its query's group (wfm_pav_add) ----
 int pav_records(BiwfaBatch& b, const PackedRuns& pk) {
-  const auto t0 = Clock::now();
-  std::vector<wfm_pav_prob_t> probs(pk.probs.size());
-  for (size_t j = 0; j < probs.size(); ++j) probs[j] = wfm_pav_prob_t{pk.probs[j].base, pk.probs[j].runs_off, pk.probs[j].n_runs, b.recs[pk.rec[j]].pav_group};
-  int rc = WFM_OK;
-  auto t1 = t0;
-  if (!probs.empty()) {
-    std::vector<uint32_t> flags(probs.size());
-    std::lock_guard<std::mutex> lk(handle_lock(b.h));
-    t1 = Clock::now();
-    rc = wfm_pav_add(b.h, b.fmt.pav, probs.data(), probs.size(), pk.runs.data(), pk.runs.size(), flags.data());
-    if (rc < 0 && b.stats) b.stats->error = wfm_last_error(b.h);
-  }
+  auto t0 = Clock::now(), t1 = t0;
+  const size_t n = pk.probs.size();
+  std::vector<wfm_pav_prob_t> probs(n);
+  for (size_t j = 0; j < n; ++j) probs[j] = wfm_pav_prob_t{pk.probs[j].base, pk.probs[j].runs_off, pk.probs[j].n_runs, b.recs[pk.rec[j]].pav_group};
+  std::vector<uint32_t> flags(n);
+  const int rc = add_stage(b, {SW_PAV, "pav", " (their runs leave the target or cannot be held, or their query has no column)"}, n, pk.unknown, t1, [&] {
+    return wfm_pav_add(b.h, b.passes->get<wfm_pav_t>(SW_PAV), probs.data(), n, pk.runs.data(), pk.runs.size(), flags.data());
+  });
   if (rc < 0) return rc;
-  g_pav_counts[0] += probs.size() - (uint64_t)rc;
-  if (rc > 0 || pk.unknown)
-    fprintf(stderr, "[wflign] pav: %llu records of a batch were NOT added (their runs leave the target or cannot be held, or their query has no column)\n",
-            (unsigned long long)((uint64_t)rc + pk.unknown));
   if (getenv("WFM_DEBUG"))
-    fprintf(stderr, "[wflign] pav: %zu records, %zu runs, %d flagged, %.1f ms (runs %.1f, device call %.1f)\n", probs.size(), pk.runs.size(), rc,
+    fprintf(stderr, "[wflign] pav: %zu records, %zu runs, %d flagged, %.1f ms (runs %.1f, device call %.1f)\n", n, pk.runs.size(), rc,
             pk.ms + ms_between(t0, Clock::now()), pk.ms + ms_between(t0, t1), ms_between(t1, Clock::now()));
   return 0;
 }
 // ---- --genotypes: the variants variant_records called for the records WRITTEN (masked SNVs left out), each at its global position --
 // the problem's base + p -- under the column of its query's group, and the same records' runs for the = union: one wfm_sites_add_variants
-// and one wfm_sites_add_ref call per batch.  A record without calls (the device flagged it), without a column or that the device refuses
-// adds nothing, is counted and reported. ----
+// and one wfm_sites_add_ref call per batch.  A record without calls (the device flagged it) or without a column never goes to the device. ----
 int genotype_records(BiwfaBatch& b, const PackedRuns& pk) {
-  const auto t0 = Clock::now();
+  auto t0 = Clock::now(), t1 = t0;
   const KeptCalls* kc = b.calls.get();
+  const uint32_t n_groups = (uint32_t)b.passes->tables->columns.keys.size();
+  wfm_sites_t* sites = b.passes->get<wfm_sites_t>(SW_GENOTYPES);
   std::vector<size_t> part_of(b.recs.size(), (size_t)-1);
   if (kc) for (size_t j = 0; j < kc->rec.size(); ++j) part_of[kc->rec[j]] = j;
   std::vector<wfm_site_var_t> vars;
@@ -794,7 +771,7 @@ int genotype_records(BiwfaBatch& b, const PackedRuns& pk) {
   for (size_t j = 0; j < pk.probs.size(); ++j) {
     const BiwfaRecord& r = b.recs[pk.rec[j]];
     const size_t part = part_of[pk.rec[j]];
-    if (part == (size_t)-1 || kc->per[part].flags || r.pav_group >= b.fmt.sites_groups) { ++alone; continue; }
+    if (part == (size_t)-1 || kc->per[part].flags || r.pav_group >= n_groups) { ++alone; continue; }
     probs.push_back(wfm_pav_prob_t{pk.probs[j].base, pk.probs[j].runs_off, pk.probs[j].n_runs, r.pav_group});
     const wfm_varcall_t& pc = kc->per[part];
     for (uint64_t k = pc.first; k < pc.first + pc.count; ++k) {
@@ -804,59 +781,43 @@ int genotype_records(BiwfaBatch& b, const PackedRuns& pk) {
       alleles.append(kc->alleles + v.off, (size_t)v.ref_len + v.alt_len);
     }
   }
-  int rc = WFM_OK;
-  auto t1 = t0;
-  if (!probs.empty()) {
-    std::vector<uint32_t> flags(probs.size());
-    std::lock_guard<std::mutex> lk(handle_lock(b.h));
-    t1 = Clock::now();
-    rc = wfm_sites_add_variants(b.h, b.fmt.sites, vars.data(), vars.size(), alleles.data(), alleles.size());
-    if (rc == WFM_OK) rc = wfm_sites_add_ref(b.h, b.fmt.sites, probs.data(), probs.size(), pk.runs.data(), pk.runs.size(), flags.data());
-    if (rc < 0 && b.stats) b.stats->error = wfm_last_error(b.h);
-  }
+  std::vector<uint32_t> flags(probs.size());
+  const int rc = add_stage(b, {SW_GENOTYPES, "genotypes", " (no calls, runs that leave the target or cannot be held, or a query without a column)"},
+                           probs.size(), alone, t1, [&] {
+    const int rv = wfm_sites_add_variants(b.h, sites, vars.data(), vars.size(), alleles.data(), alleles.size());
+    return rv != WFM_OK ? rv : wfm_sites_add_ref(b.h, sites, probs.data(), probs.size(), pk.runs.data(), pk.runs.size(), flags.data());
+  });
   if (rc < 0) return rc;
-  g_genotypes_counts[0] += probs.size() - (uint64_t)rc;
-  g_genotypes_counts[3] += alone + (uint64_t)rc;
-  if (rc > 0 || alone)
-    fprintf(stderr, "[wflign] genotypes: %llu records of a batch were NOT added (no calls, runs that leave the target or cannot be held, or a query without a column)\n",
-            (unsigned long long)((uint64_t)rc + alone));
+  counts_of(SW_GENOTYPES)[3] += alone + (uint64_t)rc;
   if (getenv("WFM_DEBUG"))
     fprintf(stderr, "[wflign] genotypes: %zu records, %zu variants, %zu allele bytes, %zu runs, %d flagged, %.1f ms (host lists %.1f, device calls %.1f)\n", probs.size(),
             vars.size(), alleles.size(), pk.runs.size(), rc, ms_between(t0, Clock::now()), ms_between(t0, t1), ms_between(t1, Clock::now()));
   return 0;
 }
-// ---- --lift: the BED intervals through the same problems, ONE device call per batch (wfm_lift_runs); the query window is the writer's
-// (variant_records' qs, qe).  The lines of a record go into BiwfaRecord::lift in the order the device gives them: ascending interval.  A
-// record the device refuses has no lines and is reported. ----
+// ---- --lift: the BED intervals through the same problems (wfm_lift_runs).  The lines of a record go into BiwfaRecord::lift in the order
+// the device gives them: ascending interval.  A record the device refuses has no lines and is reported. ----
 int lift_records(BiwfaBatch& b, const PackedRuns& pk) {
-  const auto t0 = Clock::now();
-  const std::vector<wfm_cov_prob_t>& probs = pk.probs;
+  auto t0 = Clock::now(), t1 = t0;
+  const size_t n = pk.probs.size();
   for (BiwfaRecord& r : b.recs) r.lift.clear();
-  std::vector<lift::Record> where(probs.size());
-  for (size_t j = 0; j < probs.size(); ++j) {
-    const BiwfaRecord& r = b.recs[pk.rec[j]];
+  std::vector<lift::Record> where(n);
+  for (size_t j = 0; j < n; ++j) {
+    const chain::Record& cr = pk.where[j];
     lift::Record& lr = where[j];
-    lr.qname = r.query_name; lr.tname = r.target_name; lr.rev = r.query_is_rev;
-    lr.qs = r.query_is_rev ? r.query_offset + (r.query_length - pk.qa[j] - pk.q_len[j]) : r.query_offset + pk.qa[j];
-    lr.qe = lr.qs + pk.q_len[j];
-    lr.ts = r.target_offset + pk.ta[j];
+    lr.qname = cr.qname; lr.tname = cr.tname; lr.rev = cr.rev;
+    lr.qs = cr.qs; lr.qe = cr.qe; lr.ts = cr.ts;
   }
-  int rc = WFM_OK;
   wfm_lift_t* lifts = nullptr;
   size_t n_lifts = 0;
-  std::vector<wfm_liftcall_t> per(probs.size());
-  auto t1 = t0;
-  if (!probs.empty()) {
-    std::lock_guard<std::mutex> lk(handle_lock(b.h));
-    t1 = Clock::now();
-    rc = wfm_lift_runs(b.h, b.fmt.liftset, probs.data(), probs.size(), pk.runs.data(), pk.runs.size(), &lifts, &n_lifts, per.data());
-    if (rc < 0 && b.stats) b.stats->error = wfm_last_error(b.h);
-  }
+  std::vector<wfm_liftcall_t> per(n);
+  const int rc = device_call(b, n, t1, [&] {
+    return wfm_lift_runs(b.h, b.passes->get<const wfm_liftset_t>(SW_LIFT), pk.probs.data(), n, pk.runs.data(), pk.runs.size(), &lifts, &n_lifts, per.data());
+  });
   if (rc < 0) return rc;
   const auto t2 = Clock::now();
-  const std::vector<lift::Interval>& iv = *b.fmt.lift_intervals;
+  const std::vector<lift::Interval>& iv = b.passes->tables->lift_iv;
   std::atomic<uint64_t> lines{0}, empty{0}, refused{0};
-  for_each_record(probs.size(), b.fmt.threads, [&](size_t j) {
+  for_each_record(n, b.fmt.threads, [&](size_t j) {
     if (per[j].flags) { refused += 1; return; }
     std::string& out = b.recs[pk.rec[j]].lift;
     uint64_t e = 0;
@@ -868,48 +829,31 @@ int lift_records(BiwfaBatch& b, const PackedRuns& pk) {
     lines += per[j].count; empty += e;
   });
   wfm_free_lifts(lifts);
-  g_lift_counts[0] += probs.size() - refused.load(); g_lift_counts[1] += lines.load(); g_lift_counts[2] += empty.load();
+  std::atomic<uint64_t>* c = counts_of(SW_LIFT);
+  c[0] += n - refused.load(); c[1] += lines.load(); c[2] += empty.load();
   if (refused.load() || pk.unknown)
     fprintf(stderr, "[wflign] lift: %llu records of a batch were NOT lifted (their runs leave the target or cannot be held)\n",
             (unsigned long long)(refused.load() + pk.unknown));
   if (getenv("WFM_DEBUG"))
-    fprintf(stderr, "[wflign] lift: %zu records, %zu runs, %zu lifts, %.1f ms (runs %.1f, device call %.1f, text %.1f)\n", probs.size(), pk.runs.size(), n_lifts,
+    fprintf(stderr, "[wflign] lift: %zu records, %zu runs, %zu lifts, %.1f ms (runs %.1f, device call %.1f, text %.1f)\n", n, pk.runs.size(), n_lifts,
             pk.ms + ms_between(t0, Clock::now()), pk.ms + ms_between(t0, t1), ms_between(t1, t2), ms_between(t2, Clock::now()));
   return 0;
 }
-// ---- --chain: the same problems compacted to the blocks and gaps of a UCSC chain, ONE device call per batch (wfm_chain_runs); the two
-// windows are the writer's (lift_records' qs, qe and ts).  swap: the query is the chain's first side (chain_text.hpp).  A record's chain goes
-// into BiwfaRecord::chain without its id, which the ordered writer gives it.  A record the device refuses has no chain and is reported. ----
+// ---- --chain: the same problems compacted to the blocks and gaps of a UCSC chain (wfm_chain_runs).  swap: the query is the chain's first
+// side (chain_text.hpp).  A record's chain goes into BiwfaRecord::chain without its id, which the ordered writer gives it.  A record the
+// device refuses has no chain and is reported. ----
 static_assert(sizeof(chain::Block) == sizeof(wfm_chain_block_t), "chain_text.hpp restates wfm_chain_block_t");
 int chain_records(BiwfaBatch& b, const PackedRuns& pk) {
-  const auto t0 = Clock::now();
-  const bool swap = b.fmt.chain == 2;
+  auto t0 = Clock::now(), t1 = t0;
+  const bool swap = b.passes->tables->chain_swap;
   for (BiwfaRecord& r : b.recs) r.chain.clear();
   const size_t n = pk.probs.size();
   std::vector<wfm_chain_prob_t> probs(n);
-  std::vector<chain::Record> where(n);
-  for (size_t j = 0; j < n; ++j) {
-    const BiwfaRecord& r = b.recs[pk.rec[j]];
-    chain::Record& cr = where[j];
-    cr.qname = r.query_name; cr.tname = r.target_name; cr.rev = r.query_is_rev;
-    cr.qsize = r.query_total_length; cr.tsize = r.target_total_length;
-    cr.qs = r.query_is_rev ? r.query_offset + (r.query_length - pk.qa[j] - pk.q_len[j]) : r.query_offset + pk.qa[j];
-    cr.qe = cr.qs + pk.q_len[j];
-    cr.ts = r.target_offset + pk.ta[j];
-    cr.te = cr.ts + pk.t_len[j];
-    probs[j] = wfm_chain_prob_t{pk.probs[j].runs_off, pk.probs[j].n_runs, chain::flags_of(swap, cr.rev)};
-  }
-  int rc = WFM_OK;
+  for (size_t j = 0; j < n; ++j) probs[j] = wfm_chain_prob_t{pk.probs[j].runs_off, pk.probs[j].n_runs, chain::flags_of(swap, pk.where[j].rev)};
   wfm_chain_block_t* blocks = nullptr;
   size_t n_blocks = 0;
   std::vector<wfm_chaincall_t> per(n);
-  auto t1 = t0;
-  if (n) {
-    std::lock_guard<std::mutex> lk(handle_lock(b.h));
-    t1 = Clock::now();
-    rc = wfm_chain_runs(b.h, probs.data(), n, pk.runs.data(), pk.runs.size(), &blocks, &n_blocks, per.data());
-    if (rc < 0 && b.stats) b.stats->error = wfm_last_error(b.h);
-  }
+  const int rc = device_call(b, n, t1, [&] { return wfm_chain_runs(b.h, probs.data(), n, pk.runs.data(), pk.runs.size(), &blocks, &n_blocks, per.data()); });
   if (rc < 0) return rc;
   const auto t2 = Clock::now();
   std::atomic<uint64_t> chains{0}, refused{0};
@@ -917,11 +861,12 @@ int chain_records(BiwfaBatch& b, const PackedRuns& pk) {
     if (per[j].flags) { refused += 1; return; }
     chain::Ends e;
     e.lead_dt = per[j].lead_dt; e.lead_dq = per[j].lead_dq; e.trail_dt = per[j].trail_dt; e.trail_dq = per[j].trail_dq; e.eq = per[j].eq;
-    chain::chain_body(b.recs[pk.rec[j]].chain, where[j], swap, e, (const chain::Block*)blocks + per[j].first, per[j].count);
+    chain::chain_body(b.recs[pk.rec[j]].chain, pk.where[j], swap, e, (const chain::Block*)blocks + per[j].first, per[j].count);
     chains += per[j].count != 0;
   });
   wfm_free_chain(blocks);
-  g_chain_counts[0] += chains.load(); g_chain_counts[1] += n_blocks; g_chain_counts[2] += refused.load();
+  std::atomic<uint64_t>* c = counts_of(SW_CHAIN);
+  c[0] += chains.load(); c[1] += n_blocks; c[2] += refused.load();
   if (refused.load() || pk.unknown)
     fprintf(stderr, "[wflign] chain: %llu records of a batch have NO chain (their runs cannot be held)\n", (unsigned long long)(refused.load() + pk.unknown));
   if (getenv("WFM_DEBUG"))
@@ -929,162 +874,95 @@ int chain_records(BiwfaBatch& b, const PackedRuns& pk) {
             pk.ms + ms_between(t0, Clock::now()), pk.ms + ms_between(t0, t1), ms_between(t1, t2), ms_between(t2, Clock::now()));
   return 0;
 }
-// ---- --chain-net: the same problems into the net object of the batch's handle, ONE device call per batch (wfm_net_add), each with
-// score = its = columns (counted on the device) and order = batch << 32 | its index among the records packed: the key the ordered
-// writers sort by.  The windows are chain_records'.  A record the device refuses adds nothing, is counted and reported. ----
+// ---- --chain-net: the same problems into the net object of the batch's handle (wfm_net_add), each with score = its = columns (counted
+// on the device) and order = batch << 32 | its index among the records packed: the key the ordered writers sort by.  What the chain's
+// header needs of every record added goes to the batch's texts. ----
 int net_records(BiwfaBatch& b, const PackedRuns& pk) {
-  const auto t0 = Clock::now();
+  auto t0 = Clock::now(), t1 = t0;
   const size_t n = pk.probs.size();
   std::vector<wfm_net_prob_t> probs(n);
-  std::vector<NetHead> heads(n);
-  for (size_t j = 0; j < n; ++j) {
-    const BiwfaRecord& r = b.recs[pk.rec[j]];
-    NetHead& hd = heads[j];
-    hd.order = (b.fmt.net_batch << 32) | (uint64_t)j;
-    hd.t_offset = r.target_global;
-    chain::Record& cr = hd.rec;
-    cr.qname = r.query_name; cr.tname = r.target_name; cr.rev = r.query_is_rev;
-    cr.qsize = r.query_total_length; cr.tsize = r.target_total_length;
-    cr.qs = r.query_is_rev ? r.query_offset + (r.query_length - pk.qa[j] - pk.q_len[j]) : r.query_offset + pk.qa[j];
-    cr.qe = cr.qs + pk.q_len[j];
-    cr.ts = r.target_offset + pk.ta[j];
-    cr.te = cr.ts + pk.t_len[j];
-    probs[j] = wfm_net_prob_t{pk.probs[j].base, pk.probs[j].runs_off, pk.probs[j].n_runs, WFM_NET_SCORE_EQ, hd.order};
-  }
-  int rc = WFM_OK;
+  for (size_t j = 0; j < n; ++j)
+    probs[j] = wfm_net_prob_t{pk.probs[j].base, pk.probs[j].runs_off, pk.probs[j].n_runs, WFM_NET_SCORE_EQ, (b.passes->batch << 32) | (uint64_t)j};
   std::vector<uint32_t> flags(n);
-  auto t1 = t0;
-  if (n) {
-    std::lock_guard<std::mutex> lk(handle_lock(b.h));
-    t1 = Clock::now();
-    rc = wfm_net_add(b.h, b.fmt.net, probs.data(), n, pk.runs.data(), pk.runs.size(), flags.data());
-    if (rc < 0 && b.stats) b.stats->error = wfm_last_error(b.h);
-  }
+  const int rc = add_stage(b, {SW_CHAIN_NET, "chain-net", " (their runs leave the target or cannot be held)"}, n, pk.unknown, t1, [&] {
+    return wfm_net_add(b.h, b.passes->get<wfm_net_t>(SW_CHAIN_NET), probs.data(), n, pk.runs.data(), pk.runs.size(), flags.data());
+  });
   if (rc < 0) return rc;
-  if (b.fmt.net_heads)
+  if (b.texts)
     for (size_t j = 0; j < n; ++j)
-      if (!flags[j]) b.fmt.net_heads->push_back(std::move(heads[j]));
-  g_chain_net_counts[0] += n - (uint64_t)rc;
-  if (rc > 0 || pk.unknown)
-    fprintf(stderr, "[wflign] chain-net: %llu records of a batch were NOT added (their runs leave the target or cannot be held)\n",
-            (unsigned long long)((uint64_t)rc + pk.unknown));
+      if (!flags[j]) b.texts->net_heads.push_back(NetHead{probs[j].order, b.recs[pk.rec[j]].target_global, pk.where[j]});
   if (getenv("WFM_DEBUG"))
     fprintf(stderr, "[wflign] chain-net: %zu records, %zu runs, %d flagged, %.1f ms (runs %.1f, device call %.1f)\n", n, pk.runs.size(), rc,
             pk.ms + ms_between(t0, Clock::now()), pk.ms + ms_between(t0, t1), ms_between(t1, Clock::now()));
   return 0;
 }
-// ---- --transitive: the same problems into the trans object of the batch's handle, ONE device call per batch (wfm_trans_add), each
-// with the world position of its first target base (the problem's base: the world begins with the target's sequences) and of the first
-// base of its forward query window (chain_records' qs in the query sequence's place in the world).  A record the device refuses adds
-// nothing, is counted and reported. ----
+// ---- --transitive: the same problems into the trans object of the batch's handle (wfm_trans_add), each with the world position of its
+// first target base (the problem's base: the world begins with the target's sequences) and of the first base of its forward query window
+// (in the query sequence's place in the world). ----
 int trans_records(BiwfaBatch& b, const PackedRuns& pk) {
-  const auto t0 = Clock::now();
+  auto t0 = Clock::now(), t1 = t0;
   const size_t n = pk.probs.size();
   std::vector<wfm_trans_prob_t> probs(n);
-  for (size_t j = 0; j < n; ++j) {
-    const BiwfaRecord& r = b.recs[pk.rec[j]];
-    const uint64_t qs = r.query_is_rev ? r.query_offset + (r.query_length - pk.qa[j] - pk.q_len[j]) : r.query_offset + pk.qa[j];
-    probs[j] = wfm_trans_prob_t{pk.probs[j].base, transitive::query_world(r.query_global, qs), pk.probs[j].runs_off, pk.probs[j].n_runs,
-                                r.query_is_rev ? WFM_TRANS_REVERSE : 0u};
-  }
-  int rc = WFM_OK;
+  for (size_t j = 0; j < n; ++j)
+    probs[j] = wfm_trans_prob_t{pk.probs[j].base, transitive::query_world(b.recs[pk.rec[j]].query_global, pk.where[j].qs), pk.probs[j].runs_off,
+                                pk.probs[j].n_runs, pk.where[j].rev ? WFM_TRANS_REVERSE : 0u};
   std::vector<uint32_t> flags(n);
-  auto t1 = t0;
-  if (n) {
-    std::lock_guard<std::mutex> lk(handle_lock(b.h));
-    t1 = Clock::now();
-    rc = wfm_trans_add(b.h, b.fmt.trans, probs.data(), n, pk.runs.data(), pk.runs.size(), flags.data());
-    if (rc < 0 && b.stats) b.stats->error = wfm_last_error(b.h);
-  }
+  const int rc = add_stage(b, {SW_TRANSITIVE, "transitive", " (their runs leave their sequences or cannot be held)"}, n, pk.unknown, t1, [&] {
+    return wfm_trans_add(b.h, b.passes->get<wfm_trans_t>(SW_TRANSITIVE), probs.data(), n, pk.runs.data(), pk.runs.size(), flags.data());
+  });
   if (rc < 0) return rc;
-  g_transitive_counts[0] += n - (uint64_t)rc;
-  if (rc > 0 || pk.unknown)
-    fprintf(stderr, "[wflign] transitive: %llu records of a batch were NOT added (their runs leave their sequences or cannot be held)\n",
-            (unsigned long long)((uint64_t)rc + pk.unknown));
   if (getenv("WFM_DEBUG"))
     fprintf(stderr, "[wflign] transitive: %zu records, %zu runs, %d flagged, %.1f ms (runs %.1f, host %.1f, device call %.1f)\n", n, pk.runs.size(), rc,
             pk.ms + ms_between(t0, Clock::now()), pk.ms, ms_between(t0, t1), ms_between(t1, Clock::now()));
   return 0;
 }
+
+// the stages behind pack_written, in the order they run
+const struct { SwitchId id; int (*run)(BiwfaBatch&, const PackedRuns&); } kRunStages[] = {
+    {SW_COVERAGE, coverage_records}, {SW_PAV, pav_records},         {SW_GENOTYPES, genotype_records}, {SW_LIFT, lift_records},
+    {SW_CHAIN, chain_records},       {SW_CHAIN_NET, net_records},   {SW_TRANSITIVE, trans_records}};
+
+void set_switch(SwitchId id, bool on, const char* out, const char* bed, uint64_t option) {
+  Switch& s = g_switch[id];
+  for (auto& a : s.counts) a.store(0);
+  {
+    std::lock_guard<std::mutex> lk(s.mu);
+    s.out = on && out ? out : "";
+    s.bed = on && bed ? bed : "";
+    s.option.store(option);
+  }
+  s.on.store(on);
+}
+int switch_counts(SwitchId id, uint64_t out[4]) {
+  if (!out) return WFM_E_ARG;
+  for (int q = 0; q < 4; ++q) out[q] = g_switch[id].counts[q].load();
+  return WFM_OK;
+}
+bool named(const char* path) { return path && *path; }
 }  // namespace
 
-void transitive_paths(std::string& bed, std::string& out, uint32_t& depth) {
-  std::lock_guard<std::mutex> lk(g_transitive_mu);
-  const bool on = g_transitive.load();
-  bed = on ? g_transitive_bed : std::string();
-  out = on ? g_transitive_out : std::string();
-  depth = g_transitive_depth;
+SwitchSetting switch_setting(SwitchId id) {
+  Switch& s = g_switch[id];
+  std::lock_guard<std::mutex> lk(s.mu);
+  const bool on = s.on.load();
+  return SwitchSetting{on ? s.out : std::string(), on ? s.bed : std::string(), s.option.load()};
 }
 
-void transitive_finished(uint64_t lines, uint64_t rounds, uint64_t bed_skipped) {
-  g_transitive_counts[1] += lines; g_transitive_counts[2] += rounds; g_transitive_counts[3] += bed_skipped;
-}
-
-std::string chain_net_path() {
-  std::lock_guard<std::mutex> lk(g_chain_net_mu);
-  return g_chain_net.load() ? g_chain_net_out : std::string();
-}
-
-void chain_net_finished(uint64_t chains, uint64_t pieces, uint64_t lost) {
-  g_chain_net_counts[1] += chains; g_chain_net_counts[2] += pieces; g_chain_net_counts[3] += lost;
-}
-
-void chain_path(std::string& out, bool& swap) {
-  std::lock_guard<std::mutex> lk(g_chain_mu);
-  out = g_chain.load() ? g_chain_out : std::string();
-  swap = g_chain_swap.load();
-}
-
-void lift_paths(std::string& bed, std::string& out) {
-  std::lock_guard<std::mutex> lk(g_lift_mu);
-  bed = g_lift.load() ? g_lift_bed : std::string();
-  out = g_lift.load() ? g_lift_out : std::string();
-}
-
-void lift_bed_read(uint64_t skipped) { g_lift_counts[3] += skipped; }
-
-void pav_paths(std::string& bed, uint64_t& window, std::string& out) {
-  std::lock_guard<std::mutex> lk(g_pav_mu);
-  const bool on = g_pav.load();
-  bed = on ? g_pav_bed : std::string();
-  window = on ? g_pav_window : 0;
-  out = on ? g_pav_out : std::string();
-}
-
-void pav_finished(uint64_t rows, uint64_t union_intervals, uint64_t bed_skipped) {
-  g_pav_counts[1] += rows; g_pav_counts[2] += union_intervals; g_pav_counts[3] += bed_skipped;
-}
-
-std::string coverage_path() {
-  std::lock_guard<std::mutex> lk(g_coverage_mu);
-  return g_coverage.load() ? g_coverage_path : std::string();
-}
-
-void coverage_finished(uint64_t covered, uint64_t depth_sum, uint64_t intervals) {
-  g_coverage_counts[1] += covered; g_coverage_counts[2] += depth_sum; g_coverage_counts[3] += intervals;
-}
-
-std::string genotypes_path() {
-  std::lock_guard<std::mutex> lk(g_genotypes_mu);
-  return g_genotypes.load() ? g_genotypes_path : std::string();
-}
-
-void genotypes_finished(uint64_t variants, uint64_t sites) { g_genotypes_counts[1] += sites; g_genotypes_counts[2] += variants - sites; }
-
-std::string variants_path() {
-  std::lock_guard<std::mutex> lk(g_variants_mu);
-  return g_variants.load() ? g_variants_path : std::string();
+void switch_finished(SwitchId id, uint64_t c1, uint64_t c2, uint64_t c3) {
+  std::atomic<uint64_t>* c = counts_of(id);
+  c[1] += c1; c[2] += c2; c[3] += c3;
 }
 
 int do_biwfa_alignment_batch(wfm_handle_t* h, std::vector<BiwfaRecord>& recs, const wflign_penalties_t& penalties,
                              bool disable_chain_patching, const PafParams& pp, BiwfaStats* stats, const OutputFormat& fmt,
-                             ResidentSeqs* resident) {
+                             ResidentSeqs* resident, const BatchPasses* passes, BatchTexts* texts) {
   const bool dbg = getenv("WFM_DEBUG") != nullptr;
   const auto ts0 = Clock::now();
   const size_t n = recs.size();
+  static const BatchPasses no_passes;
   BiwfaBatch b{h, recs, penalties,
                wfm_penalties_t{penalties.mismatch, penalties.gap_opening1, penalties.gap_extension1, penalties.gap_opening2, penalties.gap_extension2},
-               pp, stats, fmt, resident, resident ? resident->store : nullptr,
+               pp, stats, fmt, resident, resident ? resident->store : nullptr, passes ? passes : &no_passes, texts,
                std::vector<BiwfaBatch::Work>(n), std::vector<char>(n, 0)};
   int rc = align_main(b, !disable_chain_patching);
   if (rc < 0) return rc;
@@ -1097,10 +975,10 @@ int do_biwfa_alignment_batch(wfm_handle_t* h, std::vector<BiwfaRecord>& recs, co
     if (stats) { stats->head_patches += b.n_head.load(); stats->tail_patches += b.n_tail.load(); }
   }
   const auto ts2 = Clock::now();
-  const bool left = g_left_align.load();
-  b.cs_form = g_cs.load(std::memory_order_relaxed);
-  b.variants = g_variants.load(std::memory_order_relaxed);
-  const bool calls = b.variants || fmt.sites;  // (--genotypes takes variant_records' calls, with or without the file of --variants)
+  const bool left = is_on(SW_LEFT_ALIGN);
+  b.cs_form = is_on(SW_CS) ? (int)g_switch[SW_CS].option.load(std::memory_order_relaxed) : 0;
+  b.variants = is_on(SW_VARIANTS);
+  const bool calls = b.variants || b.passes->on[SW_GENOTYPES];  // (--genotypes takes variant_records' calls, with or without the file of --variants)
   if (left || b.cs_form || calls) {  // the two halves with the device calls between them
     for_each_record(n, fmt.threads, [&](size_t ri) { swizzle(b, ri); });
     if (left) rc = left_align_records(b, b.cs_form != 0 || calls);
@@ -1112,15 +990,12 @@ int do_biwfa_alignment_batch(wfm_handle_t* h, std::vector<BiwfaRecord>& recs, co
   } else {
     for_each_record(n, fmt.threads, [&](size_t ri) { swizzle(b, ri); write_record(b, ri); });
   }
-  if (fmt.coverage || fmt.pav || fmt.liftset || fmt.chain || fmt.sites || fmt.net || fmt.trans) {  // one packing for the stages that are on; each makes its own device call
+  bool any = false;
+  for (const auto& s : kRunStages) any = any || b.passes->on[s.id];
+  if (any) {  // one packing for the stages that are on; each makes its own device call
     const PackedRuns pk = pack_written(b);
-    if (fmt.coverage && (rc = coverage_records(b, pk)) < 0) return rc;
-    if (fmt.pav && (rc = pav_records(b, pk)) < 0) return rc;
-    if (fmt.sites && (rc = genotype_records(b, pk)) < 0) return rc;
-    if (fmt.liftset && (rc = lift_records(b, pk)) < 0) return rc;
-    if (fmt.chain && (rc = chain_records(b, pk)) < 0) return rc;
-    if (fmt.net && (rc = net_records(b, pk)) < 0) return rc;
-    if (fmt.trans && (rc = trans_records(b, pk)) < 0) return rc;
+    for (const auto& s : kRunStages)
+      if (b.passes->on[s.id] && (rc = s.run(b, pk)) < 0) return rc;
   }
   if (dbg)
     fprintf(stderr, "[wflign] %zu records: main alignment + runs + scans %.1f ms (incl. waiting for the device), patches %.1f ms (%zu tails scanned after their heads), swizzle + records %.1f ms\n",
@@ -1132,170 +1007,38 @@ int do_biwfa_alignment_batch(wfm_handle_t* h, std::vector<BiwfaRecord>& recs, co
 
 extern "C" {
 
-void wfmh_set_verify_optimal(int on, uint64_t max_cells) {
-  wflign::g_optimal_cells.store(on ? max_cells : 0);
-  for (auto& a : wflign::g_optimal_counts) a.store(0);
-  wflign::g_optimal.store(on != 0);
-}
+using namespace wflign;
 
-void wfmh_set_left_align(int on) {
-  for (auto& a : wflign::g_left_align_counts) a.store(0);
-  wflign::g_left_align.store(on != 0);
-}
-
-void wfmh_set_cs(int form) {
-  for (auto& a : wflign::g_cs_counts) a.store(0);
-  wflign::g_cs.store(form == 1 || form == 2 ? form : 0);
-}
-
-void wfmh_set_variants(const char* path_or_null) {
-  for (auto& a : wflign::g_variants_counts) a.store(0);
-  {
-    std::lock_guard<std::mutex> lk(wflign::g_variants_mu);
-    wflign::g_variants_path = path_or_null ? path_or_null : "";
-  }
-  wflign::g_variants.store(path_or_null && *path_or_null);
-}
-
-void wfmh_set_genotypes(const char* path_or_null) {
-  for (auto& a : wflign::g_genotypes_counts) a.store(0);
-  {
-    std::lock_guard<std::mutex> lk(wflign::g_genotypes_mu);
-    wflign::g_genotypes_path = path_or_null ? path_or_null : "";
-  }
-  wflign::g_genotypes.store(path_or_null && *path_or_null);
-}
-
-int wfmh_genotypes_counts(uint64_t out[4]) {
-  if (!out) return WFM_E_ARG;
-  for (int q = 0; q < 4; ++q) out[q] = wflign::g_genotypes_counts[q].load();
-  return WFM_OK;
-}
-
-void wfmh_set_coverage(const char* path_or_null) {
-  for (auto& a : wflign::g_coverage_counts) a.store(0);
-  {
-    std::lock_guard<std::mutex> lk(wflign::g_coverage_mu);
-    wflign::g_coverage_path = path_or_null ? path_or_null : "";
-  }
-  wflign::g_coverage.store(path_or_null && *path_or_null);
-}
-
+void wfmh_set_verify_optimal(int on, uint64_t max_cells) { set_switch(SW_VERIFY_OPTIMAL, on != 0, nullptr, nullptr, on ? max_cells : 0); }
+void wfmh_set_left_align(int on) { set_switch(SW_LEFT_ALIGN, on != 0, nullptr, nullptr, 0); }
+void wfmh_set_cs(int form) { set_switch(SW_CS, form == 1 || form == 2, nullptr, nullptr, (uint64_t)form); }
+void wfmh_set_variants(const char* path_or_null) { set_switch(SW_VARIANTS, named(path_or_null), path_or_null, nullptr, 0); }
+void wfmh_set_genotypes(const char* path_or_null) { set_switch(SW_GENOTYPES, named(path_or_null), path_or_null, nullptr, 0); }
+void wfmh_set_coverage(const char* path_or_null) { set_switch(SW_COVERAGE, named(path_or_null), path_or_null, nullptr, 0); }
+void wfmh_set_chain_net(const char* path_or_null) { set_switch(SW_CHAIN_NET, named(path_or_null), path_or_null, nullptr, 0); }
 void wfmh_set_lift(const char* bed_path_or_null, const char* out_path_or_null) {
-  for (auto& a : wflign::g_lift_counts) a.store(0);
-  const bool on = bed_path_or_null && *bed_path_or_null && out_path_or_null && *out_path_or_null;
-  {
-    std::lock_guard<std::mutex> lk(wflign::g_lift_mu);
-    wflign::g_lift_bed = on ? bed_path_or_null : "";
-    wflign::g_lift_out = on ? out_path_or_null : "";
-  }
-  wflign::g_lift.store(on);
+  set_switch(SW_LIFT, named(bed_path_or_null) && named(out_path_or_null), out_path_or_null, bed_path_or_null, 0);
 }
-
-void wfmh_set_chain(const char* path_or_null, int swap) {
-  for (auto& a : wflign::g_chain_counts) a.store(0);
-  const bool on = path_or_null && *path_or_null;
-  {
-    std::lock_guard<std::mutex> lk(wflign::g_chain_mu);
-    wflign::g_chain_out = on ? path_or_null : "";
-  }
-  wflign::g_chain_swap.store(on && swap != 0);
-  wflign::g_chain.store(on);
-}
-
-void wfmh_set_chain_net(const char* path_or_null) {
-  for (auto& a : wflign::g_chain_net_counts) a.store(0);
-  const bool on = path_or_null && *path_or_null;
-  {
-    std::lock_guard<std::mutex> lk(wflign::g_chain_net_mu);
-    wflign::g_chain_net_out = on ? path_or_null : "";
-  }
-  wflign::g_chain_net.store(on);
-}
-
+void wfmh_set_chain(const char* path_or_null, int swap) { set_switch(SW_CHAIN, named(path_or_null), path_or_null, nullptr, named(path_or_null) && swap != 0); }
 void wfmh_set_transitive(const char* bed_path_or_null, const char* out_path_or_null, uint32_t depth) {
-  for (auto& a : wflign::g_transitive_counts) a.store(0);
-  const bool on = bed_path_or_null && *bed_path_or_null && out_path_or_null && *out_path_or_null;
-  {
-    std::lock_guard<std::mutex> lk(wflign::g_transitive_mu);
-    wflign::g_transitive_bed = on ? bed_path_or_null : "";
-    wflign::g_transitive_out = on ? out_path_or_null : "";
-    wflign::g_transitive_depth = depth;
-  }
-  wflign::g_transitive.store(on);
+  set_switch(SW_TRANSITIVE, named(bed_path_or_null) && named(out_path_or_null), out_path_or_null, bed_path_or_null, depth);
 }
-
-int wfmh_transitive_counts(uint64_t out[4]) {
-  if (!out) return WFM_E_ARG;
-  for (int q = 0; q < 4; ++q) out[q] = wflign::g_transitive_counts[q].load();
-  return WFM_OK;
-}
-
-int wfmh_chain_net_counts(uint64_t out[4]) {
-  if (!out) return WFM_E_ARG;
-  for (int q = 0; q < 4; ++q) out[q] = wflign::g_chain_net_counts[q].load();
-  return WFM_OK;
-}
-
-int wfmh_chain_counts(uint64_t out[4]) {
-  if (!out) return WFM_E_ARG;
-  for (int q = 0; q < 4; ++q) out[q] = wflign::g_chain_counts[q].load();
-  return WFM_OK;
-}
-
 void wfmh_set_pav(const char* bed_path_or_null, uint64_t window, const char* out_path_or_null) {
-  for (auto& a : wflign::g_pav_counts) a.store(0);
-  const bool bed = bed_path_or_null && *bed_path_or_null;
-  const bool on = out_path_or_null && *out_path_or_null && (bed != (window != 0));  // (one of the two, never both)
-  {
-    std::lock_guard<std::mutex> lk(wflign::g_pav_mu);
-    wflign::g_pav_bed = on && bed ? bed_path_or_null : "";
-    wflign::g_pav_window = on && !bed ? window : 0;
-    wflign::g_pav_out = on ? out_path_or_null : "";
-  }
-  wflign::g_pav.store(on);
+  const bool bed = named(bed_path_or_null);
+  const bool on = named(out_path_or_null) && (bed != (window != 0));  // (one of the two, never both)
+  set_switch(SW_PAV, on, out_path_or_null, bed ? bed_path_or_null : nullptr, on && !bed ? window : 0);
 }
 
-int wfmh_pav_counts(uint64_t out[4]) {
-  if (!out) return WFM_E_ARG;
-  for (int q = 0; q < 4; ++q) out[q] = wflign::g_pav_counts[q].load();
-  return WFM_OK;
-}
-
-int wfmh_lift_counts(uint64_t out[4]) {
-  if (!out) return WFM_E_ARG;
-  for (int q = 0; q < 4; ++q) out[q] = wflign::g_lift_counts[q].load();
-  return WFM_OK;
-}
-
-int wfmh_coverage_counts(uint64_t out[4]) {
-  if (!out) return WFM_E_ARG;
-  for (int q = 0; q < 4; ++q) out[q] = wflign::g_coverage_counts[q].load();
-  return WFM_OK;
-}
-
-int wfmh_variants_counts(uint64_t out[4]) {
-  if (!out) return WFM_E_ARG;
-  for (int q = 0; q < 4; ++q) out[q] = wflign::g_variants_counts[q].load();
-  return WFM_OK;
-}
-
-int wfmh_cs_counts(uint64_t out[4]) {
-  if (!out) return WFM_E_ARG;
-  for (int q = 0; q < 4; ++q) out[q] = wflign::g_cs_counts[q].load();
-  return WFM_OK;
-}
-
-int wfmh_left_align_counts(uint64_t out[4]) {
-  if (!out) return WFM_E_ARG;
-  for (int q = 0; q < 4; ++q) out[q] = wflign::g_left_align_counts[q].load();
-  return WFM_OK;
-}
-
-int wfmh_verify_optimal_counts(uint64_t out[4]) {
-  if (!out) return WFM_E_ARG;
-  for (int q = 0; q < 4; ++q) out[q] = wflign::g_optimal_counts[q].load();
-  return WFM_OK;
-}
+int wfmh_verify_optimal_counts(uint64_t out[4]) { return switch_counts(SW_VERIFY_OPTIMAL, out); }
+int wfmh_left_align_counts(uint64_t out[4]) { return switch_counts(SW_LEFT_ALIGN, out); }
+int wfmh_cs_counts(uint64_t out[4]) { return switch_counts(SW_CS, out); }
+int wfmh_variants_counts(uint64_t out[4]) { return switch_counts(SW_VARIANTS, out); }
+int wfmh_genotypes_counts(uint64_t out[4]) { return switch_counts(SW_GENOTYPES, out); }
+int wfmh_coverage_counts(uint64_t out[4]) { return switch_counts(SW_COVERAGE, out); }
+int wfmh_lift_counts(uint64_t out[4]) { return switch_counts(SW_LIFT, out); }
+int wfmh_chain_counts(uint64_t out[4]) { return switch_counts(SW_CHAIN, out); }
+int wfmh_chain_net_counts(uint64_t out[4]) { return switch_counts(SW_CHAIN_NET, out); }
+int wfmh_transitive_counts(uint64_t out[4]) { return switch_counts(SW_TRANSITIVE, out); }
+int wfmh_pav_counts(uint64_t out[4]) { return switch_counts(SW_PAV, out); }
 
 }  // extern "C"

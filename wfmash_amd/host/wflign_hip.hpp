@@ -35,6 +35,7 @@
 // and CIGARs are runs (count, op) from the device to the record's text: nothing is expanded to one byte per base.
 #pragma once
 
+#include <algorithm>
 #include <atomic>
 #include <cstdint>
 #include <functional>
@@ -46,8 +47,8 @@
 #include "../../include/wfmash_hip.h"
 #include "chain_text.hpp"
 #include "cigar_ops.hpp"  // CigarOps, the CIGAR helpers, plan_patches, PafParams and the two record writers
-
-namespace lift { struct Interval; }  // lift_text.hpp
+#include "lift_text.hpp"
+#include "pav_text.hpp"
 
 namespace wflign {
 
@@ -127,68 +128,66 @@ struct ResidentSeqs {
 std::mutex& handle_lock(wfm_handle_t* h);
 
 // --chain-net: what a record's chain needs beside its pieces, kept on the host under the order the record went to the net object with
-struct NetHead {
-  uint64_t order = 0;
-  uint64_t t_offset = 0;  // where the target sequence begins in the concatenation
-  chain::Record rec;
-};
+using NetHead = chain::NetHead;
 
 struct OutputFormat {
   bool paf_format_else_sam = true;   // wflign.cpp:434
   bool no_seq_in_sam = false;
   bool emit_md_tag = false;
   int threads = 1;                   // host threads for the per-record CIGAR / PAF work of a batch
-  wfm_coverage_t* coverage = nullptr;  // --coverage: the depth object of the batch's handle (null: the stage is not run)
-  wfm_pav_t* pav = nullptr;            // --pav: the presence object of the batch's handle (null: the stage is not run)
-  wfm_sites_t* sites = nullptr;        // --genotypes: the sites object of the batch's handle (null: the stage is not run) ...
-  uint32_t sites_groups = 0;           // ... and its number of groups
-  const wfm_liftset_t* liftset = nullptr;                   // --lift: the intervals on the batch's handle (null: the stage is not run) ...
-  const std::vector<lift::Interval>* lift_intervals = nullptr;  // ... and as the BED had them, in the set's order
-  int chain = 0;                       // --chain: 1 = the chain of every record written, 2 = the swapped one (0: the stage is not run)
-  wfm_net_t* net = nullptr;            // --chain-net: the net object of the batch's handle (null: the stage is not run) ...
-  uint64_t net_batch = 0;              // ... the batch's number, the high half of its records' orders ...
-  std::vector<NetHead>* net_heads = nullptr;  // ... and where the heads of the records added go
-  wfm_trans_t* trans = nullptr;        // --transitive: the trans object of the batch's handle (null: the stage is not run)
 };
 
-// --variants: the file wfmh_set_variants named ("" while the switch is off); the align phase writes the batches' BiwfaRecord::vcf to it
-std::string variants_path();
+// ---- the process-wide switches: one record each (wflign_hip.cpp), named by these ids ----
+enum SwitchId {
+  SW_VARIANTS, SW_COVERAGE, SW_LIFT, SW_CHAIN, SW_PAV, SW_GENOTYPES, SW_CHAIN_NET, SW_TRANSITIVE,  // the align driver's passes, in their order
+  SW_LEFT_ALIGN, SW_CS, SW_VERIFY_OPTIMAL,
+  N_SWITCHES,
+  N_PASSES = SW_TRANSITIVE + 1
+};
 
-// --genotypes: the file wfmh_set_genotypes named ("" while the switch is off), and what the align phase adds to the counts once it has
-// the table: the variants the objects held and the sites written
-std::string genotypes_path();
-void genotypes_finished(uint64_t variants, uint64_t sites);
+// What wfmh_set_* named: the file the align phase writes ("" while the switch is off), the BED it reads ("" while off, or without one) and
+// the switch's integer (--pav: the window size, 0 with a BED; --chain: 1 if the two sides change places; --transitive: the depth)
+struct SwitchSetting {
+  std::string out, bed;
+  uint64_t option = 0;
+};
+SwitchSetting switch_setting(SwitchId id);
+// what the align phase adds to the switch's counts 1, 2 and 3 once it has read a BED or written the file (count 0 is the stages')
+void switch_finished(SwitchId id, uint64_t c1, uint64_t c2, uint64_t c3);
 
-// --coverage: the file wfmh_set_coverage named ("" while the switch is off), and what the align phase adds to the counts once it has
-// the intervals: {target bases with depth >= 1, sum of depth, intervals written}
-std::string coverage_path();
-void coverage_finished(uint64_t covered, uint64_t depth_sum, uint64_t intervals);
-
-// --lift: the BED and the file wfmh_set_lift named (both "" while the switch is off), and what the align phase adds to the counts once it
-// has read the BED: the lines it skipped
-void lift_paths(std::string& bed, std::string& out);
-void lift_bed_read(uint64_t skipped);
-
-// --chain: the file wfmh_set_chain named ("" while the switch is off) and whether the two sides change places
-void chain_path(std::string& out, bool& swap);
-
-// --chain-net: the file wfmh_set_chain_net named ("" while the switch is off), and what the align phase adds to the counts once it has
-// written the file: the chains written, the pieces, the records that won nothing
-std::string chain_net_path();
-void chain_net_finished(uint64_t chains, uint64_t pieces, uint64_t lost);
-
-// --transitive: the BED of seeds, the file and the depth wfmh_set_transitive named (out "" while the switch is off), and what the align
-// phase adds to the counts once it has written the file: the lines written, the rounds run, the BED lines it skipped
-void transitive_paths(std::string& bed, std::string& out, uint32_t& depth);
-void transitive_finished(uint64_t lines, uint64_t rounds, uint64_t bed_skipped);
-
-// --pav: the BED, the window size and the file wfmh_set_pav named (out "" while the switch is off; one of bed and window is set), and what
-// the align phase adds to the counts once it has written the file: its rows, the union's intervals, the BED lines it skipped
-void pav_paths(std::string& bed, uint64_t& window, std::string& out);
-void pav_finished(uint64_t rows, uint64_t union_intervals, uint64_t bed_skipped);
+// ---- the align driver's passes as a batch sees them ----
+// The run's constant tables: the two files' names and lengths, where each target sequence begins in the concatenation (nseq + 1 values),
+// and what single passes look up per record.
+struct RunTables {
+  std::vector<std::string> tnames, qnames;
+  std::vector<uint64_t> tlengths, qlengths, seq_offsets;
+  std::function<int(const std::string&)> find_target;  // a target name's index, or a negative number
+  pav::Columns columns;                 // --pav, --genotypes: the groups and the column of every query sequence
+  std::vector<lift::Interval> lift_iv;   // --lift: the BED's intervals in the order of the handle's liftset
+  bool chain_swap = false;               // --chain: the query is the chain's first side
+  std::vector<uint64_t> query_world;     // --transitive: where each query sequence begins in the world
+};
+// in: which passes are on, the object of the batch's handle for each pass that has one, the batch's number and the tables
+struct BatchPasses {
+  bool on[N_PASSES] = {};
+  void* object[N_PASSES] = {};
+  uint64_t batch = 0;
+  const RunTables* tables = nullptr;
+  template <class T>
+  T* get(SwitchId id) const { return static_cast<T*>(object[id]); }
+  bool any() const { return std::any_of(on, on + N_PASSES, [](bool b) { return b; }); }
+};
+// out: the batch's PAF / SAM text, the text of each pass that writes per batch (--variants, --lift, --chain; in the order of the records'
+// lines), and --chain-net's heads of the records added
+struct BatchTexts {
+  std::string paf;
+  std::string text[N_PASSES];
+  std::vector<NetHead> net_heads;
+};
 
 int do_biwfa_alignment_batch(wfm_handle_t* h, std::vector<BiwfaRecord>& recs, const wflign_penalties_t& penalties,
                              bool disable_chain_patching, const PafParams& pp, BiwfaStats* stats,
-                             const OutputFormat& fmt = OutputFormat(), ResidentSeqs* resident = nullptr);
+                             const OutputFormat& fmt = OutputFormat(), ResidentSeqs* resident = nullptr, const BatchPasses* passes = nullptr,
+                             BatchTexts* texts = nullptr);
 
 }  // namespace wflign
