@@ -755,6 +755,48 @@ int  wfm_trans_import(wfm_handle_t* h, wfm_trans_t* obj, const wfm_trans_rec_t* 
 int  wfm_trans_counts(const wfm_trans_t* obj, uint64_t out[6]);
 void wfm_trans_free_list(void* p);
 
+/* ---- the aligned sequences themselves: the two gapped rows of every problem's runs, as pairwise MAF blocks ----
+ * What `wgatools paf2maf` and its like make of a PAF on one CPU thread with both FASTAs open again.  This call spells the rows on the
+ * device (wfmash_amd/csrc/wfa_maf.hip; forward BYTE copies only, shares nothing with the aligners).  Pattern = target side P, text =
+ * query side T AS ALIGNED (for a `-` record T is the reverse complement of the query window: wfm_cs_strings' convention).  The runs are
+ * read from left to right and every column of a run yields one byte in row P and one byte in row T:
+ *
+ *   run        row P             row T
+ *   = of L     P[p .. p + L)     T[t .. t + L)
+ *   X of L     P[p .. p + L)     T[t .. t + L)
+ *   I of L     L x '-'           T[t .. t + L)
+ *   D of L     P[p .. p + L)     L x '-'
+ *
+ * The bytes are emitted as the device holds them (what --cs=long prints behind `=`: upper-cased by the upload, non-ACGT as the upload left
+ * it, no case change here).  The rows are spelled from the runs, never from a comparison: an = run over different bytes prints both bytes
+ * as they are; whether the runs fit the bases is wfm_check_runs' business.
+ *
+ * Blocks and split.  A gap stretch is a maximal sequence of consecutive I / D runs.  With split = 0 a problem is ONE block of all its
+ * runs.  With split = N >= 1 a gap stretch whose I bases + D bases >= N is a BREAK: none of its columns are written, it ends the block
+ * before it and the next block begins behind it; a block is a maximal run sequence between breaks.  A break at the problem's first or
+ * last run yields no block on that side; a problem that is only a break has count = 0 and no flag.  Where a problem begins and ends with
+ * = / X (the align driver's do) every block begins and ends with an aligned column; through this call a block may have psize == 0 or
+ * tsize == 0, which is legal and reported as it is.
+ *
+ * Per block {off, problem, p, t, psize, tsize, cols, eq, x}: p / t the indices in P and T where the block begins, psize / tsize the
+ * non-gap bytes of each row, cols its columns, eq / x its = and X columns; row P is rows[off .. off + cols), row T is
+ * rows[off + cols .. off + 2 cols).  The blocks are listed in problem order, left to right inside a problem; off is contiguous
+ * (next.off = off + 2 cols) and *bytes = 2 x the sum of cols.  per[i] = {flags, n_runs, first, count}: the problem's blocks are
+ * (*blocks)[first .. first + count).  s, res and runs exactly as for wfm_cs_strings (any order, unused words between the problems).
+ * Returns the number of problems flagged WFM_MAF_SPANS, or a WFM_E_* code; a run range that leaves runs[0 .. n_runs_total) is WFM_E_ARG
+ * with a message, the outputs NULL and the handle usable.  No problems, or no blocks: WFM_OK (or the count), NULL and 0.  Host memory
+ * owned by the caller (wfm_free_maf).  One workgroup writes WFM_MAF_SLICE bytes of the rows whatever blocks or problems they belong to;
+ * the problems are worked in chunks of whole problems whose block table and rows hold at most WFM_MAF_OUT_MB MiB on the device
+ * (environment, a decimal read per call, 256; a single problem may exceed it alone).  No atomics: two calls give the same bytes. */
+#define WFM_MAF_NOT_DONE 1u   /* status != 0, score-only, no runs: count = 0 */
+#define WFM_MAF_SPANS    2u   /* as WFM_CS_SPANS: count = 0, nothing of the problem is spelled */
+typedef struct { uint64_t off; uint32_t problem, p, t, psize, tsize, cols, eq, x; } wfm_maf_block_t;  /* 40 bytes */
+typedef struct { uint32_t flags, n_runs; uint64_t first, count; } wfm_mafcall_t;                      /* 24 bytes */
+#define WFM_MAF_SLICE 16384   /* output bytes one workgroup writes */
+int  wfm_maf_rows(wfm_handle_t* h, const wfm_seqset_t* s, const wfm_result_t* res, const uint32_t* runs, size_t n_runs_total,
+                  uint32_t split, wfm_maf_block_t** blocks, size_t* n_blocks, char** rows, size_t* bytes, wfm_mafcall_t* per);
+void wfm_free_maf(wfm_maf_block_t* blocks, char* rows);
+
 /* ---- every score proved optimal by a banded DP ----
  * What wfm_check_runs leaves out.  For every problem of the seqset s whose result claims a score S = res[i].score, a classical
  * minimising gap-affine-2-piece DP over cells (i = pattern index, j = text index) is run on the device, restricted to a band of

@@ -228,6 +228,29 @@ int  wfmh_lift_paf(wfm_handle_t* h, const char* target_fasta, const char* aligne
 void wfmh_set_chain(const char* path_or_null, int swap);
 int  wfmh_chain_counts(uint64_t out[4]);
 int  wfmh_chain_paf(wfm_handle_t* h, const char* target_fasta, const char* aligned_paf, const char* out_path, int swap, uint64_t out[4]);
+/* ---- the aligned sequences of the records written, as pairwise MAF blocks (wfm_maf_rows, wfmash_hip.h) ----
+ * wfmh_set_maf(path, split): from now on every batch of wfmh_align_paf[_multi] runs ONE more device call between the swizzle (and the
+ * left-alignment, the cs strings and the variants, where they are on: the windows are uploaded once for all of them) and the record
+ * writers: the two gapped rows of every record's runs, on the part of the ops its line spells (with wfmh_set_left_align the normalised
+ * runs), are spelled on the device in blocks -- one per record with split = 0, cut at every gap stretch of split or more gap bases
+ * otherwise (the stretch's columns are not written).  No output byte of the PAF or SAM changes.  The align phase writes `path` through an
+ * ordered writer in the order of the PAF's records: the file does not depend on the number of devices, handles, threads or the order of
+ * the batches.  A record the filters drop has no blocks; a record the device flags has none and is counted.
+ * The file: "##maf version=1", then per block "a score=<eq>", "s <tname> <tstart> <psize> + <tlen> <row P>",
+ * "s <qname> <qstart> <tsize> <+|-> <qlen> <row T>" and one empty line; single spaces, no column padding (readers split on whitespace).
+ * score = the block's = columns (--chain's quantity, not a blastz score); tstart = the line's target start + p; qstart = the line's query
+ * start + t on +, and qlen - the line's query end + t on -: MAF counts a - row on the reverse-complemented source, whose strand row T is.
+ * path NULL or "" switches it off.  Every call zeroes the counts.  wfmh_maf_counts: out = {records written with blocks, blocks, columns,
+ * records left without blocks} since then.  Off by default; with the switch off nothing new is called and no file is written.
+ * wfmh_maf_paf: the same file for an existing aligned PAF; nothing else runs.  Lines are parsed as wfmh_verify_paf parses them and their
+ * windows uploaded as it uploads them; a line without an =XID cg:Z:, a malformed one, one whose sequence its file does not have or has
+ * with another length is skipped and counted.  As in wfmh_verify_paf, a line's target name is looked up in target_fasta and its query
+ * name in query_fasta (target_fasta where that is NULL): with two files, a query that only the target file has counts as unknown.  A cg:Z: that begins or ends with I or D runs is spelled as it is (its first or last block then
+ * begins or ends with gap columns).  One line on stderr has the totals.  out = the same four counts.  Returns 0 or WFM_E_*. */
+void wfmh_set_maf(const char* path_or_null, uint32_t split);
+int  wfmh_maf_counts(uint64_t out[4]);
+int  wfmh_maf_paf(wfm_handle_t* h, const char* target_fasta, const char* query_fasta_or_null, const char* aligned_paf, const char* out_path, uint32_t split,
+                  uint64_t out[4]);
 /* Test hook (no GPU): the text side alone (chain_text.hpp).  spec: lines "R<TAB>qname<TAB>qsize<TAB>qs<TAB>qe<TAB>strand<TAB>tname<TAB>tsize
  * <TAB>ts<TAB>te<TAB>eq<TAB>lead_dt<TAB>lead_dq<TAB>trail_dt<TAB>trail_dq" (a record as its PAF line has it, and what wfm_chain_runs says of
  * its problem beside the blocks) each followed by its blocks "B<TAB>size<TAB>dt<TAB>dq" as the device gives them.  flags_out (or NULL):

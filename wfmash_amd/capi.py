@@ -46,7 +46,7 @@ EXPORTS = [
     "wfm_seqstore_create", "wfm_seqstore_free", "wfm_seqstore_add", "wfm_seqstore_info",
     "wfm_upload_sequence_refs", "wfm_align_refs_rle", "wfm_download_sequences",
     "wfm_check_runs", "wfm_check_optimal", "wfm_left_align_runs", "wfm_cs_strings", "wfm_free_cs",
-    "wfm_call_variants", "wfm_free_variants",
+    "wfm_call_variants", "wfm_free_variants", "wfm_maf_rows", "wfm_free_maf",
     "wfm_coverage_create", "wfm_coverage_free", "wfm_coverage_add", "wfm_coverage_export", "wfm_coverage_import", "wfm_coverage_intervals",
     "wfm_coverage_free_list",
     "wfm_liftset_create", "wfm_liftset_free", "wfm_lift_runs", "wfm_free_lifts",
@@ -71,6 +71,9 @@ WFM_LA_NOT_DONE, WFM_LA_SPANS = 1, 2
 WFM_CS_SHORT, WFM_CS_LONG = 0, 1
 WFM_CS_NOT_DONE, WFM_CS_SPANS = 1, 2
 WFM_CS_SLICE = 16384
+# wfm_maf_rows (include/wfmash_hip.h): why a problem has no blocks, and the output bytes one workgroup writes
+WFM_MAF_NOT_DONE, WFM_MAF_SPANS = 1, 2
+WFM_MAF_SLICE = 16384
 # wfm_call_variants (include/wfmash_hip.h): a record's kind and its MASKED bit, why a problem has no records, the allele bytes one workgroup writes
 WFM_VAR_SNV, WFM_VAR_INS, WFM_VAR_DEL = 0, 1, 2
 WFM_VAR_MASKED = 256
@@ -175,6 +178,21 @@ class VarCall(C.Structure):
     """wfm_varcall_t: where wfm_call_variants put one problem's records, the runs they were called from and the gaps it did not call."""
     _fields_ = [("flags", C.c_uint32), ("n_runs", C.c_uint32), ("first", C.c_uint64), ("count", C.c_uint64),
                 ("end_gaps", C.c_uint32), ("pad_", C.c_uint32)]
+
+
+class MafBlock(C.Structure):
+    """wfm_maf_block_t: one block of wfm_maf_rows; its row P is rows[off : off + cols], its row T the cols bytes behind."""
+    _fields_ = [("off", C.c_uint64), ("problem", C.c_uint32), ("p", C.c_uint32), ("t", C.c_uint32), ("psize", C.c_uint32),
+                ("tsize", C.c_uint32), ("cols", C.c_uint32), ("eq", C.c_uint32), ("x", C.c_uint32)]
+
+
+MAF_BLOCK_DTYPE = np.dtype([("off", "<u8"), ("problem", "<u4"), ("p", "<u4"), ("t", "<u4"), ("psize", "<u4"), ("tsize", "<u4"),
+                            ("cols", "<u4"), ("eq", "<u4"), ("x", "<u4")])
+
+
+class MafCall(C.Structure):
+    """wfm_mafcall_t: where wfm_maf_rows put one problem's blocks, and the runs they were spelled from."""
+    _fields_ = [("flags", C.c_uint32), ("n_runs", C.c_uint32), ("first", C.c_uint64), ("count", C.c_uint64)]
 
 
 class CovProb(C.Structure):
@@ -1466,6 +1484,34 @@ class Handle:
             self._L.wfm_free_variants(recs, alleles)
         return np.frombuffer(raw, dtype=VARIANT_DTYPE), blob, [per[i] for i in range(n)]
 
+    def maf_rows(self, seqset, results, runs, split=0):
+        """wfm_maf_rows: the two gapped rows of every problem's runs in the blocks of a pairwise MAF, spelled on the device.  results and
+        runs as for check_runs; split: 0, or the gap bases from which a gap stretch breaks a block.  Returns (blocks: a numpy structured
+        array with the fields of MafBlock, rows: all row bytes as bytes, [MafCall], one per problem)."""
+        n = seqset.n
+        arr = _result_array(results, n, copy=True)
+        runs = np.ascontiguousarray(runs, dtype=np.uint32)
+        per = (MafCall * max(n, 1))()
+        blocks, rows = C.c_void_p(), C.c_void_p()
+        n_blocks, n_bytes = C.c_size_t(0), C.c_size_t(0)
+        f = self._L.wfm_maf_rows
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                      C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p]
+        self._L.wfm_free_maf.restype = None
+        self._L.wfm_free_maf.argtypes = [C.c_void_p, C.c_void_p]
+        rc = f(self._p, seqset._p, arr, runs.ctypes.data if len(runs) else None, len(runs), int(split), C.byref(blocks), C.byref(n_blocks),
+               C.byref(rows), C.byref(n_bytes), per)
+        if rc < 0:
+            assert not blocks.value and not rows.value and n_blocks.value == 0 and n_bytes.value == 0
+            raise WfmError(f"wfm_maf_rows failed ({rc}): {self.last_error()}")
+        try:
+            raw = C.string_at(blocks, n_blocks.value * C.sizeof(MafBlock)) if n_blocks.value else b""
+            blob = C.string_at(rows, n_bytes.value) if n_bytes.value else b""
+        finally:
+            self._L.wfm_free_maf(blocks, rows)
+        return np.frombuffer(raw, dtype=MAF_BLOCK_DTYPE), blob, [per[i] for i in range(n)]
+
     def chain_runs(self, problems, runs):
         """wfm_chain_runs: the blocks and gaps of a UCSC chain from every problem's runs.  problems: a list of (runs_off, n_runs, flags),
         flags of WFM_CHAIN_SWAP and WFM_CHAIN_REVERSE; runs: the run words ((length << 2) | op).  Returns (the blocks as a numpy array with
@@ -1878,6 +1924,7 @@ HOST_EXPORTS = ["wfmh_test_packed_lce", "wfmh_test_is_acgt", "wfmh_align_default
                 "wfmh_set_coverage", "wfmh_coverage_counts", "wfmh_coverage_paf", "wfmh_test_coverage_bedgraph",
                 "wfmh_set_lift", "wfmh_lift_counts", "wfmh_lift_paf", "wfmh_test_lift_lines",
                 "wfmh_set_chain", "wfmh_chain_counts", "wfmh_chain_paf", "wfmh_test_chain_lines",
+                "wfmh_set_maf", "wfmh_maf_counts", "wfmh_maf_paf",
                 "wfmh_set_chain_net", "wfmh_chain_net_counts", "wfmh_chain_net_paf", "wfmh_test_chain_net_lines",
                 "wfmh_set_transitive", "wfmh_transitive_counts", "wfmh_transitive_paf", "wfmh_test_transitive_lines",
                 "wfmh_set_pav", "wfmh_pav_counts", "wfmh_pav_paf", "wfmh_test_pav_text",
@@ -2439,6 +2486,42 @@ def chain_paf(handle, target_fasta, aligned_paf, out_path, swap=False, net_path=
         if rc != 0:
             raise WfmError(f"wfmh_chain_net_paf failed ({rc}): {handle.last_error()}")
     return tuple(int(v) for v in (out if out_path is not None else net))
+
+
+def set_maf(path, split=0) -> None:
+    """wfmh_set_maf: every later align_paf call of the process writes the aligned sequences of every record it writes as pairwise MAF
+    blocks to `path` (None: off), the rows spelled on the device; split: 0, or the gap bases from which a gap stretch ends a block;
+    zeroes the counts."""
+    f = _host().wfmh_set_maf
+    f.restype = None
+    f.argtypes = [C.c_char_p, C.c_uint32]
+    f(os.fsencode(path) if path else None, int(split))
+
+
+def maf_counts():
+    """wfmh_maf_counts: (records written with blocks, blocks, columns, records left without blocks) since wfmh_set_maf."""
+    f = _host().wfmh_maf_counts
+    f.restype = C.c_int
+    f.argtypes = [C.POINTER(C.c_uint64)]
+    out = (C.c_uint64 * 4)()
+    rc = f(out)
+    if rc != 0:
+        raise WfmError(f"wfmh_maf_counts failed ({rc})")
+    return tuple(int(v) for v in out)
+
+
+def maf_paf(handle, target_fasta, aligned_paf, out_path, split=0, query_fasta=None):
+    """wfmh_maf_paf: the MAF file of an existing aligned PAF; returns (records written with blocks, blocks, columns, records left without
+    blocks)."""
+    out = (C.c_uint64 * 4)()
+    f = _host().wfmh_maf_paf
+    f.restype = C.c_int
+    f.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.POINTER(C.c_uint64)]
+    rc = f(handle._p, os.fsencode(target_fasta), os.fsencode(query_fasta) if query_fasta else None, os.fsencode(aligned_paf), os.fsencode(out_path),
+           int(split), out)
+    if rc != 0:
+        raise WfmError(f"wfmh_maf_paf failed ({rc}): {handle.last_error()}")
+    return tuple(int(v) for v in out)
 
 
 def set_chain_net(path) -> None:

@@ -318,6 +318,17 @@ void launch_cs_index(const uint32_t* runs, const CsProb* probs, int nprob, int f
 // which holds chunk_bytes rounded up to a multiple of WFM_CS_SLICE
 void launch_cs_write(const uint8_t* seq, const CsProb* probs, const void* recs, const unsigned long long* goff, uint32_t ka, uint32_t kb,
                      unsigned long long chunk_bytes, int form, uint8_t* out, hipStream_t st);
+// wfm_maf_rows (wfa_maf.hip): the problems are CsProb as well, but a problem takes n_runs + 1 slots at rec_off (the last holds its totals).
+// recs: one uint4 per slot (pattern index, text index, WRITTEN columns before the run, the run); pre: one uint2 per slot (aligned columns
+// and = columns before the run); nblk / ncols / flags: one per problem (a flagged problem's are 0)
+void launch_maf_index(const uint32_t* runs, const CsProb* probs, int nprob, uint32_t split, void* recs, void* pre, unsigned long long* nblk,
+                      unsigned long long* ncols, uint32_t* flags, hipStream_t st);
+// the problems [ka, kb): their n_blocks = boff[kb] - boff[ka] blocks into blocks (40 bytes each, wfm_maf_block_t) and the chunk_bytes bytes
+// of their rows behind goff[ka] into out, which holds chunk_bytes rounded up to a multiple of WFM_MAF_SLICE and is 16-byte aligned (goff /
+// boff: the n + 1 offsets of the call's rows and blocks)
+void launch_maf_write(const uint8_t* seq, const CsProb* probs, const void* recs, const void* pre, const unsigned long long* nblk,
+                      const unsigned long long* goff, const unsigned long long* boff, uint32_t ka, uint32_t kb, unsigned long long chunk_bytes,
+                      void* blocks, uint32_t n_blocks, uint8_t* out, hipStream_t st);
 // wfm_call_variants (wfa_variants.hip): the problems are CsProb as well.  recs: one uint4 per run of the problems that are not skipped
 // (pattern index, text index, offset of the run's allele bytes in the problem's, the run), rpre: the index of the run's first record in
 // the problem's; tot_bytes / tot_recs / end_gaps / flags: one per problem (a flagged problem's are 0)

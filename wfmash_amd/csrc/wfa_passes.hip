@@ -2,12 +2,13 @@
 // produces something from them -- the check against the bases, left-aligned gaps, cs strings, variants, target depth, lifted
 // intervals, the blocks of a chain, presence per group, the sites and genotypes of many records, the net across records, the proof of optimality.
 // The kernels are in wfa_check.hip, wfa_leftalign.hip, wfa_cs.hip, wfa_variants.hip, wfa_coverage.hip, wfa_lift.hip, wfa_chain.hip,
-// wfa_pav.hip, wfa_sites.hip, wfa_net.hip, wfa_trans.hip and wfa_optcheck.hip.
+// wfa_pav.hip, wfa_sites.hip, wfa_net.hip, wfa_trans.hip, wfa_maf.hip and wfa_optcheck.hip.
 //
 // Every pass has the same frame, written once below: it validates the run ranges before anything is launched, carves what the
 // call has on the device out of one block, launches, writes its output in chunks that fit a cap, and waits for the stream before
 // it returns (so one scratch block and one output block of the handle serve all of them).
 #include <hip/hip_runtime.h>
+#include <sys/mman.h>
 
 #include <algorithm>
 #include <chrono>
@@ -575,6 +576,133 @@ int wfm_call_variants(wfm_handle_t* h, const wfm_seqset_t* s, const wfm_result_t
 }
 
 void wfm_free_variants(wfm_variant_t* vars, char* alleles) { free(vars); free(alleles); }
+
+// ---- the two gapped rows of every problem's runs, in the blocks of a pairwise MAF (wfmash_hip.h; the kernels: wfa_maf.hip) ----
+namespace {
+// The caller's row buffer (released with free, as wfm_free_maf does).  From 8 MiB on it begins on a 2 MiB boundary, is a whole number of such
+// pieces and is advised to huge pages: the rows are written once by memcpy, read once and freed, and a buffer of tens of MB on 4 KiB pages
+// pays for every page on each of the three (profiles/maf.md section 3: 7 ms a call against 2 for 42 MB)
+char* maf_rows_alloc(size_t bytes) {
+  constexpr size_t HUGE = (size_t)2 << 20;
+  if (bytes >= 4 * HUGE) {
+    const size_t whole = (bytes + HUGE - 1) / HUGE * HUGE;
+    if (void* p = aligned_alloc(HUGE, whole)) {
+      (void)madvise(p, whole, MADV_HUGEPAGE);
+      return (char*)p;
+    }
+  }
+  return (char*)malloc(bytes);
+}
+}  // namespace
+
+int wfm_maf_rows(wfm_handle_t* h, const wfm_seqset_t* s, const wfm_result_t* res, const uint32_t* runs, size_t n_runs_total, uint32_t split,
+                 wfm_maf_block_t** blocks, size_t* n_blocks, char** rows, size_t* bytes, wfm_mafcall_t* per) {
+  if (!h || !s || !blocks || !n_blocks || !rows || !bytes || (n_runs_total && !runs)) return WFM_E_ARG;
+  *blocks = nullptr; *rows = nullptr;
+  *n_blocks = 0; *bytes = 0;
+  PassTimer tm(h);
+  const size_t n = s->meta.size();
+  if (n == 0) return WFM_OK;
+  if (!res || !per) return WFM_E_ARG;
+  if (n > (size_t)INT32_MAX || n_runs_total > ((size_t)1 << 31)) { h->err = "wfm_maf_rows: too many problems or runs for one call"; return WFM_E_ARG; }
+  HIPCHK(h, hipSetDevice(h->device));
+  // the problems as wfa_maf.hip sees them: cs_problems' with one more slot per problem, for its totals
+  std::vector<CsProb> probs(n);
+  uint64_t rec_total = 0;
+  size_t run_total = 0;
+  for (size_t i = 0; i < n; ++i) {
+    CsProb& c = probs[i];
+    memset(&c, 0, sizeof(c));
+    fill_prob(c, s->meta[i], res[i], true);
+    if (c.skip) continue;
+    if (!runs_inside(res[i].ops_off, res[i].n_runs, n_runs_total)) return runs_leave(h, i);
+    c.run_off = res[i].ops_off; c.n_runs = res[i].n_runs;
+    c.rec_off = rec_total;
+    rec_total += (uint64_t)c.n_runs + 1;
+    run_total += c.n_runs;
+  }
+  // one block: [run records] 16 and [prefixes] 8 bytes per slot, [offsets of the rows] and [of the blocks] n + 1 each, [blocks] and
+  // [columns] n each of 8 bytes, [problems], [runs], [flags]
+  const size_t nr = n_runs_total;
+  uint4* d_recs;
+  uint2* d_pre;
+  unsigned long long *d_goff, *d_boff, *d_nblk, *d_ncols;
+  CsProb* d_probs;
+  uint32_t *d_runs, *d_flags;
+  Carver cv{h->scratch, "maf"};
+  cv.piece(&d_recs, (size_t)rec_total); cv.piece(&d_pre, (size_t)rec_total); cv.piece(&d_goff, n + 1); cv.piece(&d_boff, n + 1);
+  cv.piece(&d_nblk, n); cv.piece(&d_ncols, n); cv.piece(&d_probs, n); cv.piece(&d_runs, nr); cv.piece(&d_flags, n);
+  if (int rc = cv.commit(h)) return rc;
+  if (nr) HIPCHK(h, hipMemcpyAsync(d_runs, runs, nr * 4, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(d_probs, probs.data(), n * sizeof(CsProb), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, tm.begin());
+  launch_maf_index(d_runs, d_probs, (int)n, split, d_recs, d_pre, d_nblk, d_ncols, d_flags, h->stream);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, tm.end());
+  // the problems' blocks and columns, once: the host sizes the outputs and takes the two prefix sums
+  std::vector<unsigned long long> goff(n + 1), boff(n + 1);
+  std::vector<uint32_t> flags(n);
+  HIPCHK(h, hipMemcpyAsync(goff.data() + 1, d_ncols, n * 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(boff.data() + 1, d_nblk, n * 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(flags.data(), d_flags, n * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  float ms_index = 0, ms_write = 0, ms = 0;
+  (void)tm.event_ms(&ms_index);
+  goff[0] = 0; boff[0] = 0;
+  int spans = 0;
+  for (size_t i = 0; i < n; ++i) {
+    per[i].flags = flags[i]; per[i].n_runs = probs[i].n_runs;
+    per[i].first = boff[i]; per[i].count = boff[i + 1];
+    goff[i + 1] = goff[i] + 2 * goff[i + 1];  // (two rows a column)
+    boff[i + 1] += boff[i];
+    spans += (flags[i] & WFM_MAF_SPANS) != 0;
+  }
+  const unsigned long long total = goff[n], total_blocks = boff[n];
+  if (total_blocks == 0) return spans;  // (a block has columns: no blocks, no bytes)
+  HIPCHK(h, hipMemcpyAsync(d_goff, goff.data(), (n + 1) * 8, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(d_boff, boff.data(), (n + 1) * 8, hipMemcpyHostToDevice, h->stream));
+  char* host = maf_rows_alloc((size_t)total);
+  wfm_maf_block_t* host_blocks = (wfm_maf_block_t*)malloc((size_t)total_blocks * sizeof(wfm_maf_block_t));
+  if (!host || !host_blocks) { (void)hipStreamSynchronize(h->stream); free(host); free(host_blocks); h->err = "out of host memory (maf)"; return WFM_E_NOMEM; }
+  // chunks of whole problems whose blocks and rows fit the output block (a problem larger than that is a chunk of its own)
+  const unsigned long long cap = cap_units("WFM_MAF_OUT_MB", 1, 1);
+  auto cost = [&](size_t ka, size_t kb) { return (goff[kb] - goff[ka]) + (boff[kb] - boff[ka]) * sizeof(wfm_maf_block_t); };
+  const bool pinned = cs_pin_pieces(h);
+  size_t chunks = 0;
+  for (size_t ka = 0, kb; ka < n; ka = kb) {
+    kb = chunk_end(ka, n, cap, cost);
+    const unsigned long long row_bytes = goff[kb] - goff[ka], nb = boff[kb] - boff[ka];
+    if (nb == 0) continue;
+    // the block: the chunk's block table (to a multiple of 16 bytes), then its rows in whole slices
+    const size_t tbl_bytes = ((size_t)nb * sizeof(wfm_maf_block_t) + 15) / 16 * 16;
+    const size_t block = tbl_bytes + (size_t)((row_bytes + WFM_MAF_SLICE - 1) / WFM_MAF_SLICE) * WFM_MAF_SLICE;
+    int rc = WFM_OK;
+    if (nb > 0xffffffffull) { h->err = "wfm_maf_rows: too many blocks in one chunk"; rc = WFM_E_ARG; }
+    if (rc == WFM_OK && h->outblk.ensure(block / 8)) { h->err = "out of device memory (maf output)"; rc = WFM_E_NOMEM; }
+    if (rc == WFM_OK) {
+      uint8_t* d_tbl = (uint8_t*)h->outblk.p;
+      uint8_t* d_rows = d_tbl + tbl_bytes;
+      (void)tm.begin();
+      launch_maf_write(s->d_seq, d_probs, d_recs, d_pre, d_nblk, d_goff, d_boff, (uint32_t)ka, (uint32_t)kb, row_bytes, d_tbl, (uint32_t)nb, d_rows, h->stream);
+      hipError_t e = hipGetLastError();
+      (void)tm.end();
+      if (e == hipSuccess) e = cs_copy_down(h, pinned, (char*)(host_blocks + boff[ka]), d_tbl, (size_t)nb * sizeof(wfm_maf_block_t));
+      if (e == hipSuccess) e = cs_copy_down(h, pinned, host + goff[ka], d_rows, (size_t)row_bytes);  // (the block is the next chunk's)
+      if (e != hipSuccess) { h->err = std::string("wfm_maf_rows: ") + hipGetErrorString(e); rc = WFM_E_HIP; }
+    }
+    if (rc != WFM_OK) { free(host); free(host_blocks); return rc; }
+    if (tm.event_ms(&ms)) ms_write += ms;
+    ++chunks;
+  }
+  *blocks = host_blocks; *n_blocks = (size_t)total_blocks;
+  *rows = host; *bytes = (size_t)total;
+  if (tm.on)
+    fprintf(stderr, "[wfm] maf (split %u): %zu problems, %zu runs, %llu blocks, %llu bytes in %zu chunks, index %.3f ms, blocks + write %.3f ms (device events), the call %.3f ms (host clock)\n",
+            split, n, run_total, total_blocks, total, chunks, ms_index, ms_write, tm.host_ms());
+  return spans;
+}
+
+void wfm_free_maf(wfm_maf_block_t* blocks, char* rows) { free(blocks); free(rows); }
 
 // ---- per-base depth of the target from the runs of many records (wfmash_hip.h; the kernels: wfa_coverage.hip) ----
 struct wfm_coverage {

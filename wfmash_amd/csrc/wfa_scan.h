@@ -1,4 +1,4 @@
-// wfa_scan.h -- what the kernels of the record passes share (wfa_cs.hip, wfa_variants.hip, wfa_coverage.hip, wfa_lift.hip, wfa_chain.hip, wfa_pav.hip):
+// wfa_scan.h -- what the kernels of the record passes share (wfa_cs.hip, wfa_variants.hip, wfa_coverage.hip, wfa_lift.hip, wfa_chain.hip, wfa_pav.hip, wfa_maf.hip):
 // the exclusive prefix and the inclusive running maximum over a workgroup, the two binary searches, the first pass over a problem's runs,
 // and the device-wide scans in the reduce / one-workgroup scan / apply form as templates (the scan of the blocks' sums; the running maximum
 // in three launches).  A workgroup is WAVES x 64 threads; a scan block is four elements per lane.  Device code only.

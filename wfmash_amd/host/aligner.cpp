@@ -3,6 +3,7 @@
 #include "coverage_text.hpp"
 #include "lift_text.hpp"
 #include "chain_text.hpp"
+#include "maf_text.hpp"
 #include "pav_text.hpp"
 #include "genotype_text.hpp"
 #include "transitive_text.hpp"
@@ -427,7 +428,7 @@ wflign::BatchTexts Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<st
   t.wflign = t.lap();
   std::string& out = texts.paf = gather_text(sum, fetched, recs);
   // (a record without a line has no VCF lines, write_record; lift lines and chains come in the order of the records' lines, and the chains' ids are the writer's)
-  for (const auto& r : recs) { texts.text[wflign::SW_VARIANTS] += r.vcf; texts.text[wflign::SW_LIFT] += r.lift; texts.text[wflign::SW_CHAIN] += r.chain; }
+  for (const auto& r : recs) { texts.text[wflign::SW_VARIANTS] += r.vcf; texts.text[wflign::SW_LIFT] += r.lift; texts.text[wflign::SW_CHAIN] += r.chain; texts.text[wflign::SW_MAF] += r.maf; }
   t.text = t.lap();
   if (verify::enabled() && !param.sam_format) {  // --verify: the finished lines, before they are written (SAM records carry no =/X CIGAR)
     verify::Source src;
@@ -693,6 +694,14 @@ struct ChainPass : Pass {
   }
 };
 
+// --maf: the header here, the batches' blocks through the ordered writer (no device object, no merge)
+struct MafPass : Pass {
+  MafPass(wflign::RunTables& tb, const wflign::SwitchSetting& s) : Pass(wflign::SW_MAF, "--maf", false, tb, s.out, "the maf file") {
+    out << maf::header();
+    writes_per_batch();
+  }
+};
+
 // --pav: the intervals of the table in the file's order and the columns are known before anything is aligned; the presence objects; the
 // table of their union taken once on the device, the file through pav_text.hpp
 struct PavPass : Pass {
@@ -892,7 +901,8 @@ template <class P>
 Pass* make_pass(wflign::RunTables& tb, const wflign::SwitchSetting& s) { return new P(tb, s); }
 Pass* (*const kMakePass[wflign::N_PASSES])(wflign::RunTables&, const wflign::SwitchSetting&) = {
     make_pass<VariantsPass>, make_pass<CoveragePass>, make_pass<LiftPass>,     make_pass<ChainPass>,
-    make_pass<PavPass>,      make_pass<GenotypesPass>, make_pass<ChainNetPass>, make_pass<TransitivePass>};
+    make_pass<PavPass>,      make_pass<GenotypesPass>, make_pass<ChainNetPass>, make_pass<TransitivePass>,
+    make_pass<MafPass>};
 }  // namespace
 
 struct Aligner::Run {

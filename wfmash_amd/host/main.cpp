@@ -88,6 +88,18 @@
 //                                              PAF, one of the two at least: no mapping, no alignment; lines are skipped and counted as
 //                                              --coverage-paf does (the query's name and length are the line's: query.fa is not read);
 //                                              only --device beside it
+//   --maf FILE [--maf-split N]                 the aligned sequences of every record WRITTEN as pairwise MAF blocks (what multiz, PHAST,
+//                                              mafTools and wgatools read; `wgatools paf2maf` makes it from a PAF with both FASTAs open
+//                                              again): the two gapped rows are spelled on the device (wfm_maf_rows), one block per record,
+//                                              or cut at every gap stretch of N or more gap bases (N as 5000, 10k; default 0 = never), whose
+//                                              columns are then not written; "a score=" is the block's = columns; fields separated by single
+//                                              spaces, not column-padded; in the order of the PAF's records; works with PAF and -a alike; no
+//                                              output byte of the PAF or SAM changes; refused with -m and --verify-paf; --maf-split without
+//                                              --maf is an error; off by default
+//   --maf-paf IN.paf --maf FILE [--maf-split N] target.fa [query.fa]   the same file for an existing aligned PAF: no mapping, no
+//                                              alignment; a line whose target target.fa does not have, or whose query query.fa (target.fa without it) does not
+//                                              have, is skipped and counted; only --device
+//                                              beside it
 //   --pav IN.bed | --pav-window N, --pav-out FILE   which groups of query sequences (haplotypes, samples: the part of the name before its
 //                                              last '#') have each target interval, and how much of it: the runs of every record WRITTEN go
 //                                              into a per-group union of aligned segments on the device (wfm_pav_*; 16 bytes a segment, never
@@ -205,6 +217,9 @@ static void usage() {
           "            --lift BED --lift-out FILE lift the BED's target intervals through every record written, on the GPU: one line per record and interval (not with -m, --verify-paf)\n"
           "            --lift-paf FILE with --lift, --lift-out: lift through an existing aligned PAF over target.fa, and stop (only --device beside it)\n"
           "            --chain FILE  write a UCSC chain file (target to query) of every record written, blocks and gaps made on the GPU; score = the = columns (not with -m, --verify-paf)\n"
+          "            --maf FILE    write the aligned sequences of every record as pairwise MAF blocks, rows spelled on the GPU (single spaces, no column padding; not with -m, --verify-paf)\n"
+          "            --maf-split N with --maf: end a block at every gap stretch of N or more gap bases (5000, 10k; default 0 = one block per record)\n"
+          "            --maf-paf FILE with --maf: the MAF file of an existing aligned PAF over target.fa [query.fa], and stop (only --maf-split and --device beside it)\n"
           "            --chain-swap  with --chain: the swapped file (query to target), what chainSwap would make of it\n"
           "            --chain-net FILE write a single-coverage chain file: every target base under at most one chain, the best record's, from a net across the records on the GPU (with or without --chain; not with -m, --verify-paf, --chain-swap)\n"
           "            --transitive IN.bed --transitive-out FILE [--transitive-depth N]  close the BED's intervals over ALL records written, through targets and queries alike, on the GPU: every interval a seed reaches in N rounds (2; 0: to the fixed point) as 'seq start end name seed_seq seed_start seed_end' (not with -m, --verify-paf)\n"
@@ -224,7 +239,7 @@ int main(int argc, char** argv) {
   ap.threads = 1;  // -t, default 1 as in the reference (parse_args.hpp: thread_count); the C ABI default (0) means all cores
   wfmh_map_params_t mp;
   wfmh_map_default_params(&mp);
-  std::string mapping_in, out = "/dev/stdout", target, query, seeds_in, scaffold_out, tmp_base, verify_in, ani_matrix_out, variants_out, genotypes_out, coverage_out, coverage_in, lift_bed, lift_out, lift_in, pav_bed, pav_out, pav_in, chain_out, chain_in, chain_net_out, trans_bed, trans_out, trans_in;
+  std::string mapping_in, out = "/dev/stdout", target, query, seeds_in, scaffold_out, tmp_base, verify_in, ani_matrix_out, variants_out, genotypes_out, coverage_out, coverage_in, lift_bed, lift_out, lift_in, pav_bed, pav_out, pav_in, chain_out, chain_in, chain_net_out, trans_bed, trans_out, trans_in, maf_out, maf_in;
   unsigned long trans_depth = 2;
   uint64_t pav_window = 0;
   bool pav_window_set = false;
@@ -234,6 +249,8 @@ int main(int argc, char** argv) {
   bool chain_other = false;    // --chain-paf: anything beside it, --chain, --chain-swap, --device and the two FASTAs
   bool trans_other = false;    // --transitive-paf: anything beside it, --transitive, --transitive-out, --transitive-depth, --device and the two FASTAs
   bool chain_swap = false;
+  bool maf_other = false;      // --maf-paf: anything beside it, --maf, --maf-split, --device and the two FASTAs
+  int64_t maf_split = -1;      // --maf-split: -1 not given
   bool verify = false, verify_optimal = false, ani_only = false, left_align = false;
   uint64_t verify_optimal_cells = 0;
   int cs_form = 0;  // --cs: 0 off, 1 short, 2 long
@@ -244,6 +261,7 @@ int main(int argc, char** argv) {
     if (a[0] == '-' ? (a != "--pav" && a != "--pav-window" && a != "--pav-out" && a != "--pav-paf" && a != "--device" && a != "-h" && a != "--help") : !query.empty()) pav_other = true;
     if (a[0] == '-' ? (a != "--transitive" && a != "--transitive-out" && a != "--transitive-depth" && a != "--transitive-paf" && a != "--device" && a != "-h" && a != "--help") : !query.empty()) trans_other = true;
     if (a[0] == '-' ? (a != "--chain" && a != "--chain-net" && a != "--chain-swap" && a != "--chain-paf" && a != "--device" && a != "-h" && a != "--help") : !query.empty()) chain_other = true;
+    if (a[0] == '-' ? (a != "--maf" && a != "--maf-split" && a != "--maf-paf" && a != "--device" && a != "-h" && a != "--help") : !query.empty()) maf_other = true;
     if (a[0] == '-' ? (a != "--lift" && a != "--lift-out" && a != "--lift-paf" && a != "--device" && a != "-h" && a != "--help") : !target.empty()) lift_other = true;
     if (a[0] == '-' ? (a != "--coverage" && a != "--coverage-paf" && a != "--device" && a != "-h" && a != "--help") : !target.empty()) other_options = true;
     auto next = [&](const char* name) -> std::string {
@@ -397,6 +415,9 @@ int main(int argc, char** argv) {
       if (v.empty() || *end || v[0] == '-' || trans_depth > 0xfffffffful) { fprintf(stderr, "[wfmash] ERROR: --transitive-depth takes a number of rounds, 0 for the fixed point\n"); return 1; }
     }
     else if (a == "--chain-swap") chain_swap = true;
+    else if (a == "--maf") maf_out = next("--maf");
+    else if (a == "--maf-split") maf_split = size("--maf-split");
+    else if (a == "--maf-paf") maf_in = next("--maf-paf");
     else if (a == "--chain-paf") chain_in = next("--chain-paf");
     else if (a == "--pav") pav_bed = next("--pav");
     else if (a == "--pav-out") pav_out = next("--pav-out");
@@ -439,6 +460,12 @@ int main(int argc, char** argv) {
   if (!trans_in.empty() && trans_other) { fprintf(stderr, "[wfmash] ERROR: --transitive-paf runs nothing else: besides --transitive IN.bed, --transitive-out FILE, --transitive-depth N and the FASTAs it takes the number of the GPU only\n"); return 1; }
   if (!trans_bed.empty() && approx_only) { fprintf(stderr, "[wfmash] ERROR: --transitive lifts through alignments: it cannot be combined with -m\n"); return 1; }
   if (!trans_bed.empty() && !verify_in.empty()) { fprintf(stderr, "[wfmash] ERROR: --transitive belongs to the align phase: it cannot be combined with --verify-paf\n"); return 1; }
+  if (maf_split >= 0 && maf_out.empty()) { fprintf(stderr, "[wfmash] ERROR: --maf-split needs --maf FILE\n"); return 1; }
+  if (maf_split > 0xffffffffll) { fprintf(stderr, "[wfmash] ERROR: --maf-split expects a number of gap bases below 2^32\n"); return 1; }
+  if (!maf_in.empty() && maf_out.empty()) { fprintf(stderr, "[wfmash] ERROR: --maf-paf needs --maf FILE\n"); return 1; }
+  if (!maf_out.empty() && approx_only) { fprintf(stderr, "[wfmash] ERROR: --maf spells alignments: it cannot be combined with -m\n"); return 1; }
+  if (!maf_out.empty() && !verify_in.empty()) { fprintf(stderr, "[wfmash] ERROR: --maf belongs to the align phase: it cannot be combined with --verify-paf\n"); return 1; }
+  if (!maf_in.empty() && maf_other) { fprintf(stderr, "[wfmash] ERROR: --maf-paf runs nothing else: besides --maf FILE, --maf-split N and the FASTAs it takes the number of the GPU only\n"); return 1; }
   if (!chain_net_out.empty() && chain_swap) { fprintf(stderr, "[wfmash] ERROR: --chain-net cannot be combined with --chain-swap: nets on the query side are not done\n"); return 1; }
   if (chain_swap && chain_out.empty()) { fprintf(stderr, "[wfmash] ERROR: --chain-swap needs --chain FILE\n"); return 1; }
   if (!chain_in.empty() && chain_out.empty() && chain_net_out.empty()) { fprintf(stderr, "[wfmash] ERROR: --chain-paf needs --chain FILE\n"); return 1; }
@@ -478,6 +505,15 @@ int main(int argc, char** argv) {
     if (prc != WFM_OK) fprintf(stderr, "[wfmash::pav] ERROR: %s\n", wfm_last_error(hp));
     wfm_destroy(hp);
     return prc == WFM_OK ? 0 : 2;
+  }
+  if (!maf_in.empty()) {  // the MAF file of an existing PAF; nothing else runs
+    wfm_handle_t* hm = nullptr;
+    if (wfm_create(device, &hm) != WFM_OK) { fprintf(stderr, "[wfmash] ERROR: no usable MI355X device %d (there is no CPU fallback)\n", device); return 2; }
+    uint64_t mc[4] = {0, 0, 0, 0};
+    const int mrc = wfmh_maf_paf(hm, target.c_str(), query.empty() ? nullptr : query.c_str(), maf_in.c_str(), maf_out.c_str(), (uint32_t)std::max<int64_t>(0, maf_split), mc);
+    if (mrc != WFM_OK) fprintf(stderr, "[wfmash::maf] ERROR: %s\n", wfm_last_error(hm));
+    wfm_destroy(hm);
+    return mrc == WFM_OK ? 0 : 2;
   }
   if (!chain_in.empty()) {  // the chain file of an existing PAF; nothing else runs
     wfm_handle_t* hc = nullptr;
@@ -642,6 +678,7 @@ int main(int argc, char** argv) {
     if (!lift_bed.empty()) wfmh_set_lift(lift_bed.c_str(), lift_out.c_str());
     if (!chain_out.empty()) wfmh_set_chain(chain_out.c_str(), chain_swap ? 1 : 0);
     if (!chain_net_out.empty()) wfmh_set_chain_net(chain_net_out.c_str());
+    if (!maf_out.empty()) wfmh_set_maf(maf_out.c_str(), (uint32_t)std::max<int64_t>(0, maf_split));
     if (!trans_bed.empty()) wfmh_set_transitive(trans_bed.c_str(), trans_out.c_str(), (uint32_t)trans_depth);
     if (pav_on) wfmh_set_pav(pav_bed.empty() ? nullptr : pav_bed.c_str(), pav_window, pav_out.c_str());
     rc = wfmh_align_paf_multi(hs.data(), (int)hs.size(), target.c_str(), q, mapping.c_str(), out.c_str(), &ap, &s);
@@ -696,6 +733,12 @@ int main(int argc, char** argv) {
       wfmh_chain_net_counts(nc);
       fprintf(stderr, "[wfmash::chain-net] %llu records added, %llu chains written, %llu pieces, %llu records won nothing\n", (unsigned long long)nc[0],
               (unsigned long long)nc[1], (unsigned long long)nc[2], (unsigned long long)nc[3]);
+    }
+    if (!maf_out.empty() && rc == WFM_OK) {
+      uint64_t mc[4] = {0, 0, 0, 0};
+      wfmh_maf_counts(mc);
+      fprintf(stderr, "[wfmash::maf] %llu records, %llu blocks, %llu columns, %llu records left without blocks\n", (unsigned long long)mc[0], (unsigned long long)mc[1],
+              (unsigned long long)mc[2], (unsigned long long)mc[3]);
     }
     if (!trans_bed.empty() && rc == WFM_OK) {
       uint64_t tc[4] = {0, 0, 0, 0};

@@ -19,6 +19,7 @@
 #include "lift_text.hpp"
 #include "transitive_text.hpp"
 #include "chain_text.hpp"
+#include "maf_text.hpp"
 #include "pav_text.hpp"
 #include "parallel.hpp"
 #include "wflign_hip.hpp"
@@ -50,14 +51,26 @@ constexpr int64_t MAX_PROBLEM_BASES = (int64_t)1 << 29;   // wfm_upload_sequence
 constexpr int64_t BATCH_BASES = (int64_t)256 << 20;       // bases one device call holds
 constexpr size_t BATCH_LINES = 8192;
 
-// the lines in hand on the device: upload by reference, check, report
-void verify_batch(wfm_handle_t* h, const Source& src, std::vector<Line>& lines, Counts& c) {
-  if (lines.empty()) return;
-  const size_t n = lines.size();
-  std::vector<wfm_problem_ref_t> refs(n);
-  std::vector<wfm_result_t> res(n);
-  std::vector<std::string> pat(n), txt(n);  // the host-pointer sides, normalised
+// The lines in hand as problems by reference -- pattern = target [ts, te), text = query [qs, qe), reverse-complemented for '-' -- with their
+// runs: by id where the source has a store, else by host pointer, fetched and normalised as the align driver's windows are, on the caller's
+// threads.  What verify_batch and maf_batch upload.
+struct LineProblems {
+  std::vector<wfm_problem_ref_t> refs;
+  std::vector<wfm_result_t> res;
+  std::vector<std::string> pat, txt;  // the host-pointer sides, normalised
   std::vector<uint32_t> runs;
+};
+void line_problems(const Source& src, const std::vector<Line>& lines, LineProblems& lp, const char* tag) {
+  const size_t n = lines.size();
+  std::vector<wfm_problem_ref_t>& refs = lp.refs;
+  std::vector<wfm_result_t>& res = lp.res;
+  std::vector<std::string>&pat = lp.pat, &txt = lp.txt;
+  std::vector<uint32_t>& runs = lp.runs;
+  refs.assign(n, wfm_problem_ref_t{});
+  res.assign(n, wfm_result_t{});
+  pat.assign(n, std::string());
+  txt.assign(n, std::string());
+  runs.clear();
   for (size_t i = 0; i < n; ++i) {
     const Line& l = lines[i];
     wfm_problem_ref_t& r = refs[i];
@@ -81,7 +94,6 @@ void verify_batch(wfm_handle_t* h, const Source& src, std::vector<Line>& lines, 
     q.ops_len = (uint32_t)std::min<uint64_t>(ops, 0xffffffffu);
     runs.insert(runs.end(), l.runs.begin(), l.runs.end());
   }
-  // the host-pointer sides, fetched and normalised as the align driver's windows are, on the caller's threads
   std::atomic<bool> fetch_failed{false};
   wfmash_host::parallel_for(n, std::max(1, src.threads), [&](size_t i) {
     const Line& l = lines[i];
@@ -103,7 +115,18 @@ void verify_batch(wfm_handle_t* h, const Source& src, std::vector<Line>& lines, 
       fetch_failed.store(true);
     }
   });
-  if (fetch_failed.load()) throw std::runtime_error("[wfmash::verify] cannot fetch the bases of a line's windows");
+  if (fetch_failed.load()) throw std::runtime_error(std::string("[wfmash::") + tag + "] cannot fetch the bases of a line's windows");
+}
+
+// the lines in hand on the device: upload by reference, check, report
+void verify_batch(wfm_handle_t* h, const Source& src, std::vector<Line>& lines, Counts& c) {
+  if (lines.empty()) return;
+  const size_t n = lines.size();
+  LineProblems lp;
+  line_problems(src, lines, lp, "verify");
+  std::vector<wfm_problem_ref_t>& refs = lp.refs;
+  std::vector<wfm_result_t>& res = lp.res;
+  std::vector<uint32_t>& runs = lp.runs;
   const wfm_penalties_t pen{5, 8, 2, 24, 1};  // (prices nothing that is compared)
   std::vector<wfm_check_t> out(n);
   {
@@ -165,6 +188,74 @@ void verify_text(wfm_handle_t* h, const Source& src, const std::string& text, Co
     if (batch.size() >= BATCH_LINES || bases >= BATCH_BASES) { verify_batch(h, src, batch, c); bases = 0; }
   }
   verify_batch(h, src, batch, c);
+}
+
+// ---- --maf-paf: the lines in hand on the device: upload by reference, ONE wfm_maf_rows call, the blocks' text through maf_text.hpp ----
+namespace {
+void maf_batch(wfm_handle_t* h, const Source& src, std::vector<Line>& lines, uint32_t split, std::ostream& out, uint64_t counts[4]) {
+  if (lines.empty()) return;
+  const size_t n = lines.size();
+  LineProblems lp;
+  line_problems(src, lines, lp, "maf");
+  std::vector<wfm_mafcall_t> per(n);
+  wfm_maf_block_t* blocks = nullptr;
+  char* rows = nullptr;
+  size_t n_blocks = 0, bytes = 0;
+  {
+    std::lock_guard<std::mutex> lk(wflign::handle_lock(h));
+    wfm_seqset_t* S = nullptr;
+    int rc = wfm_upload_sequence_refs(h, src.store, lp.refs.data(), n, &S);
+    if (rc == WFM_OK) {
+      rc = wfm_maf_rows(h, S, lp.res.data(), lp.runs.data(), lp.runs.size(), split, &blocks, &n_blocks, &rows, &bytes, per.data());
+      wfm_free_sequences(h, S);
+    }
+    if (rc < 0) throw std::runtime_error(std::string("[wfmash::maf] device call failed: ") + wfm_last_error(h));
+  }
+  static_assert(sizeof(maf::Block) == sizeof(wfm_maf_block_t), "maf_text.hpp restates wfm_maf_block_t");
+  std::string text;
+  for (size_t i = 0; i < n; ++i) {
+    const Line& l = lines[i];
+    if (per[i].flags || per[i].count == 0) { counts[3]++; continue; }
+    const maf::Line line{&l.tname, (uint64_t)l.ts, (uint64_t)l.tlen, &l.qname, (uint64_t)l.qs, (uint64_t)l.qe, (uint64_t)l.qlen, l.rev};
+    const maf::Block* mine = reinterpret_cast<const maf::Block*>(blocks) + per[i].first;
+    text.clear();
+    text.reserve(maf::record_bytes(line, mine, (size_t)per[i].count));
+    for (uint64_t k = 0; k < per[i].count; ++k) {
+      maf::block(text, line, mine[k], rows);
+      counts[2] += mine[k].cols;
+    }
+    out << text;
+    counts[0]++; counts[1] += per[i].count;
+  }
+  wfm_free_maf(blocks, rows);
+  lines.clear();
+}
+}  // namespace
+
+void maf_text(wfm_handle_t* h, const Source& src, const std::string& text, uint32_t split, std::ostream& out, uint64_t counts[4], uint64_t skipped[4]) {
+  std::vector<Line> batch;
+  int64_t bases = 0;
+  size_t at = 0;
+  while (at < text.size()) {
+    size_t nl = text.find('\n', at);
+    if (nl == std::string::npos) nl = text.size();
+    const std::string line = text.substr(at, nl - at);
+    at = nl + 1;
+    if (line.empty() || line[0] == '@') continue;
+    Line l;
+    const int st = parse_line(line, l, nullptr);
+    if (st == LINE_UNVERIFIABLE) { skipped[0]++; continue; }
+    if (st == LINE_MALFORMED) { skipped[1]++; continue; }
+    // the sequences the line names, as the files have them
+    const int64_t tl = src.target->seq_len(l.tname), ql = src.query->seq_len(l.qname);
+    if (tl < 0 || ql < 0) { skipped[2]++; continue; }
+    if (l.tlen != tl || l.qlen != ql || l.te > tl || l.qe > ql) { skipped[3]++; continue; }
+    if ((l.te - l.ts) + (l.qe - l.qs) > MAX_PROBLEM_BASES) { skipped[1]++; continue; }
+    bases += (l.te - l.ts) + (l.qe - l.qs);
+    batch.push_back(std::move(l));
+    if (batch.size() >= BATCH_LINES || bases >= BATCH_BASES) { maf_batch(h, src, batch, split, out, counts); bases = 0; }
+  }
+  maf_batch(h, src, batch, split, out, counts);
 }
 
 void set_enabled(bool on) {
@@ -273,6 +364,44 @@ int wfmh_verify_paf(wfm_handle_t* h, const char* target_fasta, const char* query
     }
     verify::verify_text(h, src, text, c);
     if (out) { out[0] = c.checked; out[1] = c.failed; out[2] = c.unverifiable; out[3] = c.bases; }
+    return WFM_OK;
+  } catch (const std::exception& e) {
+    std::cerr << e.what() << std::endl;
+    wfm_set_error(h, e.what());
+    return WFM_E_ARG;
+  }
+}
+
+// --maf-paf: the MAF file of an existing aligned PAF, lines parsed as --verify-paf parses them and their windows uploaded as it uploads
+// them; a line whose target the target file does not have, or whose query the query file does not (wfmh_verify_paf's lookup),
+// or that names another length, is skipped and counted.  Nothing else runs.
+int wfmh_maf_paf(wfm_handle_t* h, const char* target_fasta, const char* query_fasta, const char* aligned_paf, const char* out_path, uint32_t split,
+                 uint64_t out[4]) {
+  if (!h || !target_fasta || !aligned_paf || !out_path) return WFM_E_ARG;
+  try {
+    std::shared_ptr<wfmash_host::FastaStore> target = wfmash_host::open_shared(target_fasta), query_own;
+    const std::string qpath = query_fasta ? query_fasta : target_fasta;
+    if (qpath != target_fasta) query_own = wfmash_host::open_shared(qpath);
+    verify::Source src;
+    src.target = target.get();
+    src.query = query_own ? query_own.get() : target.get();
+    src.threads = (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+    std::ifstream in(aligned_paf);
+    if (!in.is_open()) throw std::runtime_error(std::string("[wfmash::maf] cannot open ") + aligned_paf);
+    std::ofstream outstream(out_path);
+    if (!outstream.is_open()) throw std::runtime_error(std::string("[wfmash::maf] cannot open ") + out_path);
+    outstream << maf::header();
+    uint64_t counts[4] = {0, 0, 0, 0}, skipped[4] = {0, 0, 0, 0};
+    std::string text, line;
+    while (std::getline(in, line)) {
+      text += line; text += '\n';
+      if (text.size() >= ((size_t)64 << 20)) { verify::maf_text(h, src, text, split, outstream, counts, skipped); text.clear(); }
+    }
+    verify::maf_text(h, src, text, split, outstream, counts, skipped);
+    std::cerr << "[wfmash::maf] " << counts[0] << " records, " << counts[1] << " blocks, " << counts[2] << " columns, " << counts[3] << " records left without blocks, "
+              << (skipped[0] + skipped[1] + skipped[2] + skipped[3]) << " lines skipped (" << skipped[0] << " without an =XID cg:Z:, " << skipped[1] << " malformed, "
+              << skipped[2] << " with an unknown sequence, " << skipped[3] << " with another length)" << std::endl;
+    if (out) for (int q = 0; q < 4; ++q) out[q] = counts[q];
     return WFM_OK;
   } catch (const std::exception& e) {
     std::cerr << e.what() << std::endl;

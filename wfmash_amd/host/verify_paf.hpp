@@ -8,6 +8,7 @@
 
 #include <cstdint>
 #include <functional>
+#include <ostream>
 #include <string>
 #include <vector>
 
@@ -31,6 +32,11 @@ struct Source {
 // Verifies the lines of `text` (separated by '\n'; empty lines are passed over) on h and adds to `c`; a failure is one line on
 // stderr.  Throws std::runtime_error when a device call fails.
 void verify_text(wfm_handle_t* h, const Source& src, const std::string& text, Counts& c);
+
+// --maf-paf: the MAF blocks (maf_text.hpp; wfm_maf_rows, split as there) of the lines of `text` to `out`, lines parsed and their windows
+// uploaded as verify_text does.  counts += {records written with blocks, blocks, columns, records left without blocks}; skipped +=
+// {lines without an =XID cg:Z:, malformed, with a target the target file or a query the query file does not have, with another length}.  Throws when a device call fails.
+void maf_text(wfm_handle_t* h, const Source& src, const std::string& text, uint32_t split, std::ostream& out, uint64_t counts[4], uint64_t skipped[4]);
 
 // the process-wide switch of --verify and what the runs since it was last set have counted
 void set_enabled(bool on);

@@ -5,6 +5,7 @@
 #include "parallel.hpp"
 #include "lift_text.hpp"
 #include "chain_text.hpp"
+#include "maf_text.hpp"
 #include "transitive_text.hpp"
 #include "../csrc/wfa_handle.h"
 
@@ -212,7 +213,7 @@ wfm_problem_ref_t tail_problem(const BiwfaRecord& r, const Erosion& e) {  // wfl
 using Clock = std::chrono::steady_clock;
 double ms_between(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
 
-struct WindowSet;  // the records' final runs as device problems (left_align_records, cs_records, variant_records)
+struct WindowSet;  // the records' final runs as device problems (left_align_records, cs_records, variant_records, maf_records)
 
 // --genotypes: what wfm_call_variants returned for the batch, kept until the filters have spoken (genotype_records)
 struct KeptCalls {
@@ -246,6 +247,8 @@ struct BiwfaBatch {
   std::atomic<uint64_t> n_head{0}, n_tail{0};
   int cs_form = 0;                // --cs as the batch found it: 0 off, 1 short, 2 long
   bool variants = false;          // --variants as the batch found it
+  bool maf = false;               // --maf as the batch found it
+  uint32_t maf_split = 0;         // ... and --maf-split
   std::unique_ptr<KeptCalls> calls;  // --genotypes: variant_records' records and alleles, for genotype_records
   std::unique_ptr<WindowSet> windows;  // what left_align_records leaves for cs_records and variant_records, and cs_records for variant_records
   // the handle's message was copied while the handle was still this thread's (another batch may be using it by now)
@@ -277,6 +280,8 @@ int align_main(BiwfaBatch& b, bool plan) {
     r.cs.clear();
     r.vcf.clear();
     r.vcf_called = false; r.vcf_masked = 0;
+    r.maf.clear();
+    r.maf_called = false; r.maf_blocks = 0; r.maf_cols = 0;
     r.ops.clear();
     if (!r.ok) return;
     g.ops(i, r.ops);
@@ -611,6 +616,67 @@ int variant_records(BiwfaBatch& b) {
   return 0;
 }
 
+// ---- --maf: the two gapped rows of every record's line in the blocks of a pairwise MAF, ONE device call per batch (wfm_maf_rows) on the
+// runs the line spells -- behind left_align_records the normalised ones -- on the windows the stages before uploaded, if any did.  Every
+// ok record whose trimmed part is not empty takes part; a part begins and ends with an = or X run, so every block begins and ends with an
+// aligned column.  The coordinates are the writer's (variant_records' ts, qs, qe) through maf_text.hpp.  A record the device flags is a
+// defect: it has no blocks and is counted. ----
+static_assert(sizeof(maf::Block) == sizeof(wfm_maf_block_t), "maf_text.hpp restates wfm_maf_block_t");
+int maf_records(BiwfaBatch& b) {
+  const auto t0 = Clock::now();
+  if (!b.windows) b.windows = window_parts(b, 1);
+  WindowSet& w = *b.windows;
+  if (w.parts.empty()) return 0;
+  const size_t n = w.parts.size();
+  std::vector<wfm_mafcall_t> per(n);
+  wfm_maf_block_t* blocks = nullptr;
+  char* rows = nullptr;
+  size_t n_blocks = 0, bytes = 0;
+  int rc = WFM_OK;
+  auto t1 = t0;
+  {
+    std::lock_guard<std::mutex> lk(handle_lock(b.h));
+    if (!w.S) rc = upload_windows(b, w);
+    t1 = Clock::now();
+    if (rc == WFM_OK) rc = wfm_maf_rows(b.h, w.S, w.res.data(), w.cur(), w.n_cur(), b.maf_split, &blocks, &n_blocks, &rows, &bytes, per.data());
+    if (rc < 0 && b.stats) b.stats->error = wfm_last_error(b.h);
+  }
+  if (rc < 0) return rc;
+  const auto t2 = Clock::now();
+  for_each_record(n, b.fmt.threads, [&](size_t j) {
+    if (per[j].flags) return;
+    const WindowSet::Part& pt = w.parts[j];
+    BiwfaRecord& r = b.recs[pt.rec];
+    r.maf_called = true;
+    // where the part begins in the record's windows, as trim_and_filter will find it
+    uint64_t ta = 0, qa = 0;
+    for (size_t k = 0; k < pt.b; ++k) (r.ops[k].second == 'I' ? qa : ta) += (uint64_t)r.ops[k].first;
+    const uint64_t q_len = (uint64_t)w.probs[j].tlen;
+    const uint64_t qs = r.query_is_rev ? r.query_offset + (r.query_length - qa - q_len) : r.query_offset + qa;
+    const maf::Line line{&r.target_name, r.target_offset + ta, r.target_total_length, &r.query_name, qs, qs + q_len, r.query_total_length, r.query_is_rev};
+    const maf::Block* mine = reinterpret_cast<const maf::Block*>(blocks) + per[j].first;
+    r.maf.reserve(maf::record_bytes(line, mine, (size_t)per[j].count));
+    for (uint64_t k = 0; k < per[j].count; ++k) {
+      maf::block(r.maf, line, mine[k], rows);
+      r.maf_cols += mine[k].cols;
+    }
+    r.maf_blocks = (uint32_t)per[j].count;
+  });
+  wfm_free_maf(blocks, rows);
+  if (getenv("WFM_DEBUG"))
+    fprintf(stderr, "[wflign] maf (split %u): %zu records, %zu runs, %zu blocks, %zu row bytes, %d flagged, %.1f ms (upload %.1f, device call %.1f, text %.1f)\n",
+            b.maf_split, n, w.n_cur(), n_blocks, bytes, rc, ms_between(t0, Clock::now()), ms_between(t0, t1), ms_between(t1, t2), ms_between(t2, Clock::now()));
+  return 0;
+}
+
+// --maf: a record's blocks go out with its line or not at all
+void account_maf(BiwfaRecord& r, bool written) {
+  if (!written) { r.maf.clear(); return; }
+  std::atomic<uint64_t>* c = counts_of(SW_MAF);
+  if (!r.maf_called || r.maf_blocks == 0) { c[3] += 1; return; }  // (flagged by the device, or runs it cannot hold)
+  c[0] += 1; c[1] += r.maf_blocks; c[2] += r.maf_cols;
+}
+
 // --variants: a record's lines go out with its line or not at all
 void account_variants(BiwfaRecord& r, bool written) {
   if (!written) { r.vcf.clear(); return; }
@@ -636,6 +702,7 @@ void write_record(BiwfaBatch& b, size_t ri) {
                         r.chain_length, r.chain_pos);
   r.written = written;
   if (b.variants) account_variants(r, written);
+  if (b.maf) account_maf(r, written);
   if (!b.cs_form || !written) return;
   if (r.cs.empty()) { counts_of(SW_CS)[2] += 1; return; }  // (flagged by the device, or runs it cannot hold)
   // the last field of the line, before its closing newline
@@ -979,11 +1046,14 @@ int do_biwfa_alignment_batch(wfm_handle_t* h, std::vector<BiwfaRecord>& recs, co
   b.cs_form = is_on(SW_CS) ? (int)g_switch[SW_CS].option.load(std::memory_order_relaxed) : 0;
   b.variants = is_on(SW_VARIANTS);
   const bool calls = b.variants || b.passes->on[SW_GENOTYPES];  // (--genotypes takes variant_records' calls, with or without the file of --variants)
-  if (left || b.cs_form || calls) {  // the two halves with the device calls between them
+  b.maf = is_on(SW_MAF);
+  b.maf_split = b.maf ? (uint32_t)g_switch[SW_MAF].option.load(std::memory_order_relaxed) : 0;
+  if (left || b.cs_form || calls || b.maf) {  // the two halves with the device calls between them
     for_each_record(n, fmt.threads, [&](size_t ri) { swizzle(b, ri); });
-    if (left) rc = left_align_records(b, b.cs_form != 0 || calls);
+    if (left) rc = left_align_records(b, b.cs_form != 0 || calls || b.maf);
     if (rc >= 0 && b.cs_form) rc = cs_records(b);
     if (rc >= 0 && calls) rc = variant_records(b);
+    if (rc >= 0 && b.maf) rc = maf_records(b);
     release_windows(b);
     if (rc < 0) return rc;
     for_each_record(n, fmt.threads, [&](size_t ri) { write_record(b, ri); });
@@ -1020,6 +1090,7 @@ void wfmh_set_lift(const char* bed_path_or_null, const char* out_path_or_null) {
   set_switch(SW_LIFT, named(bed_path_or_null) && named(out_path_or_null), out_path_or_null, bed_path_or_null, 0);
 }
 void wfmh_set_chain(const char* path_or_null, int swap) { set_switch(SW_CHAIN, named(path_or_null), path_or_null, nullptr, named(path_or_null) && swap != 0); }
+void wfmh_set_maf(const char* path_or_null, uint32_t split) { set_switch(SW_MAF, named(path_or_null), path_or_null, nullptr, named(path_or_null) ? split : 0); }
 void wfmh_set_transitive(const char* bed_path_or_null, const char* out_path_or_null, uint32_t depth) {
   set_switch(SW_TRANSITIVE, named(bed_path_or_null) && named(out_path_or_null), out_path_or_null, bed_path_or_null, depth);
 }
@@ -1040,5 +1111,6 @@ int wfmh_chain_counts(uint64_t out[4]) { return switch_counts(SW_CHAIN, out); }
 int wfmh_chain_net_counts(uint64_t out[4]) { return switch_counts(SW_CHAIN_NET, out); }
 int wfmh_transitive_counts(uint64_t out[4]) { return switch_counts(SW_TRANSITIVE, out); }
 int wfmh_pav_counts(uint64_t out[4]) { return switch_counts(SW_PAV, out); }
+int wfmh_maf_counts(uint64_t out[4]) { return switch_counts(SW_MAF, out); }
 
 }  // extern "C"

@@ -94,6 +94,10 @@ struct BiwfaRecord {
   uint64_t query_global = 0;         // --transitive: where the query sequence begins in the world (target_global is the target's place in it)
   std::string lift;                  // --lift: the lines of the BED intervals the record's target span overlaps, each with its newline ("" if off or not written)
   std::string chain;                 // --chain: the record's chain without its id (chain_text.hpp; "" if off, not written, refused or without a block)
+  std::string maf;                   // --maf: the paragraphs of the record's blocks (maf_text.hpp; "" if off, filtered, or the record has none)
+  bool maf_called = false;           // ... the device spelled the record's rows (false: off, or the record was left alone)
+  uint32_t maf_blocks = 0;           // ... the blocks in `maf`
+  uint64_t maf_cols = 0;             // ... and their columns
   uint32_t tags = 0;                 // WFM_PF_* of the main alignment | of the head patch << 8 | of the tail patch << 16 (diagnostics: WFM_RECORD_TAGS)
 };
 
@@ -139,14 +143,14 @@ struct OutputFormat {
 
 // ---- the process-wide switches: one record each (wflign_hip.cpp), named by these ids ----
 enum SwitchId {
-  SW_VARIANTS, SW_COVERAGE, SW_LIFT, SW_CHAIN, SW_PAV, SW_GENOTYPES, SW_CHAIN_NET, SW_TRANSITIVE,  // the align driver's passes, in their order
+  SW_VARIANTS, SW_COVERAGE, SW_LIFT, SW_CHAIN, SW_PAV, SW_GENOTYPES, SW_CHAIN_NET, SW_TRANSITIVE, SW_MAF,  // the align driver's passes, in their order
   SW_LEFT_ALIGN, SW_CS, SW_VERIFY_OPTIMAL,
   N_SWITCHES,
-  N_PASSES = SW_TRANSITIVE + 1
+  N_PASSES = SW_MAF + 1
 };
 
 // What wfmh_set_* named: the file the align phase writes ("" while the switch is off), the BED it reads ("" while off, or without one) and
-// the switch's integer (--pav: the window size, 0 with a BED; --chain: 1 if the two sides change places; --transitive: the depth)
+// the switch's integer (--pav: the window size, 0 with a BED; --chain: 1 if the two sides change places; --transitive: the depth; --maf: the split)
 struct SwitchSetting {
   std::string out, bed;
   uint64_t option = 0;
@@ -177,7 +181,7 @@ struct BatchPasses {
   T* get(SwitchId id) const { return static_cast<T*>(object[id]); }
   bool any() const { return std::any_of(on, on + N_PASSES, [](bool b) { return b; }); }
 };
-// out: the batch's PAF / SAM text, the text of each pass that writes per batch (--variants, --lift, --chain; in the order of the records'
+// out: the batch's PAF / SAM text, the text of each pass that writes per batch (--variants, --lift, --chain, --maf; in the order of the records'
 // lines), and --chain-net's heads of the records added
 struct BatchTexts {
   std::string paf;
