@@ -317,6 +317,77 @@ class L1Params(C.Structure):
 
 MapParams._fields_ = [("kmer_size", C.c_int32), ("kmer_complexity_threshold", C.c_float), ("l1", L1Params), ("l2", L2Params)]
 
+# The ctypes prototypes of the record passes and the device objects, name -> (restype, argtypes): every name of EXPORTS from wfm_check_runs
+# to wfm_trans_free_list, declared here alone and applied by load()
+_VP, _SZ, _INT, _U32, _U64 = C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.c_uint64
+_PVP, _PSZ, _PU64 = C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)
+_FREE1 = (None, [_VP])
+_FREE2 = (None, [_VP, _VP])
+_ADD = (_INT, [_VP, _VP, _VP, _SZ, _VP, _SZ, _VP])          # handle, object, problems, n, runs, n_runs, flags out
+_LIST1 = (_INT, [_VP, _VP, _PVP, _PSZ])                     # handle, object, a list out
+_LIST2 = (_INT, [_VP, _VP, _PVP, _PSZ, _PVP, _PSZ])         # handle, object, two lists out
+_IMPORT1 = (_INT, [_VP, _VP, _VP, _SZ])
+_IMPORT2 = (_INT, [_VP, _VP, _VP, _SZ, _VP, _SZ])
+_COUNTS = (_INT, [_VP, _PU64])
+PROTOTYPES = {
+    "wfm_check_runs": (_INT, [_VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    "wfm_check_optimal": (_INT, [_VP, _VP, _VP, _VP, _U64, _VP]),
+    "wfm_left_align_runs": (_INT, [_VP, _VP, _VP, _VP, _SZ, C.POINTER(C.POINTER(C.c_uint32)), _PSZ, _VP]),
+    "wfm_cs_strings": (_INT, [_VP, _VP, _VP, _VP, _SZ, _INT, _PVP, _PSZ, _VP]),
+    "wfm_free_cs": _FREE1,
+    "wfm_call_variants": (_INT, [_VP, _VP, _VP, _VP, _SZ, _PVP, _PSZ, _PVP, _PSZ, _VP]),
+    "wfm_free_variants": _FREE2,
+    "wfm_maf_rows": (_INT, [_VP, _VP, _VP, _VP, _SZ, _U32, _PVP, _PSZ, _PVP, _PSZ, _VP]),
+    "wfm_free_maf": _FREE2,
+    "wfm_coverage_create": (_INT, [_VP, _U64, _PVP]),
+    "wfm_coverage_free": _FREE1,
+    "wfm_coverage_add": _ADD,
+    "wfm_coverage_export": _LIST1,
+    "wfm_coverage_import": _IMPORT1,
+    "wfm_coverage_intervals": (_INT, [_VP, _VP, _PVP, _PSZ, _PU64]),
+    "wfm_coverage_free_list": _FREE1,
+    "wfm_liftset_create": (_INT, [_VP, _VP, _SZ, _U64, _PVP]),
+    "wfm_liftset_free": _FREE1,
+    "wfm_lift_runs": (_INT, [_VP, _VP, _VP, _SZ, _VP, _SZ, _PVP, _PSZ, _VP]),
+    "wfm_free_lifts": _FREE1,
+    "wfm_chain_runs": (_INT, [_VP, _VP, _SZ, _VP, _SZ, _PVP, _PSZ, _VP]),
+    "wfm_free_chain": _FREE1,
+    "wfm_pav_create": (_INT, [_VP, _U64, _U32, _PVP]),
+    "wfm_pav_free": _FREE1,
+    "wfm_pav_add": _ADD,
+    "wfm_pav_union": (_INT, [_VP, _VP]),
+    "wfm_pav_export": _LIST1,
+    "wfm_pav_import": _IMPORT1,
+    "wfm_pav_matrix": (_INT, [_VP, _VP, _VP, _SZ, _VP]),
+    "wfm_pav_counts": _COUNTS,
+    "wfm_pav_free_list": _FREE1,
+    "wfm_sites_create": (_INT, [_VP, _U64, _U32, _PVP]),
+    "wfm_sites_free": _FREE1,
+    "wfm_sites_add_variants": (_INT, [_VP, _VP, _VP, _SZ, C.c_char_p, _SZ]),
+    "wfm_sites_add_ref": _ADD,
+    "wfm_sites_table": (_INT, [_VP, _VP, _PVP, _PSZ, _PVP, _PSZ, _PVP]),
+    "wfm_sites_export": (_INT, [_VP, _VP, _PVP, _PSZ, _PVP, _PSZ, _PVP, _PSZ]),
+    "wfm_sites_import": (_INT, [_VP, _VP, _VP, _SZ, C.c_char_p, _SZ, _VP, _SZ]),
+    "wfm_sites_counts": _COUNTS,
+    "wfm_sites_free_list": _FREE1,
+    "wfm_net_create": (_INT, [_VP, _U64, _PVP]),
+    "wfm_net_free": _FREE1,
+    "wfm_net_add": _ADD,
+    "wfm_net_table": _LIST2,
+    "wfm_net_export": _LIST2,
+    "wfm_net_import": _IMPORT2,
+    "wfm_net_counts": _COUNTS,
+    "wfm_net_free_list": _FREE1,
+    "wfm_trans_create": (_INT, [_VP, _U64, _PVP]),
+    "wfm_trans_free": _FREE1,
+    "wfm_trans_add": _ADD,
+    "wfm_trans_closure": (_INT, [_VP, _VP, _VP, _SZ, _U32, _PVP, _PSZ, _VP]),
+    "wfm_trans_export": _LIST2,
+    "wfm_trans_import": _IMPORT2,
+    "wfm_trans_counts": _COUNTS,
+    "wfm_trans_free_list": _FREE1,
+}
+
 _LIB = None
 
 
@@ -361,6 +432,8 @@ def load():
     L.wfm_sketch_fragments.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_size_t, C.c_int, C.c_int, C.c_int32, vp, vp]
     for name in EXPORTS:  # every symbol include/wfmash_hip.h declares must be exported
         getattr(L, name)
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        getattr(L, name).restype, getattr(L, name).argtypes = restype, argtypes
     _LIB = L
     return L
 
@@ -627,37 +700,25 @@ class SeqStore:
             pass
 
 
-class Coverage:
-    """wfm_coverage_t: per-base depth of n_bases target bases, summed on the device over every problem added (include/wfmash_hip.h).
-    Close it before its handle."""
+class _DeviceObject:
+    """What Coverage, LiftSet, Pav, Sites, Net and Transitive share: the handle, the library and the object's pointer; the calls named
+    after _PREFIX (wfm_<prefix>_create / _free / _counts, and _free_list unless _FREE_LIST names another).  Close it before its handle."""
+    _PREFIX = None
+    _FREE_LIST = None
+    _p = None
 
-    def __init__(self, handle, n_bases):
+    def _create(self, handle, *args):
         self._h, self._L = handle, handle._L
-        self.n_bases = int(n_bases)
-        L = self._L
-        L.wfm_coverage_create.restype = C.c_int
-        L.wfm_coverage_create.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]
-        L.wfm_coverage_free.restype = None
-        L.wfm_coverage_free.argtypes = [C.c_void_p]
-        L.wfm_coverage_add.restype = C.c_int
-        L.wfm_coverage_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.wfm_coverage_export.restype = C.c_int
-        L.wfm_coverage_export.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
-        L.wfm_coverage_import.restype = C.c_int
-        L.wfm_coverage_import.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
-        L.wfm_coverage_intervals.restype = C.c_int
-        L.wfm_coverage_intervals.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]
-        L.wfm_coverage_free_list.restype = None
-        L.wfm_coverage_free_list.argtypes = [C.c_void_p]
+        fn = f"wfm_{self._PREFIX}_create"
         p = C.c_void_p()
-        rc = L.wfm_coverage_create(handle._p, self.n_bases, C.byref(p))
+        rc = getattr(self._L, fn)(handle._p, *args, C.byref(p))
         if rc != 0:
-            raise WfmError(f"wfm_coverage_create failed ({rc}): {handle.last_error()}")
+            raise WfmError(f"{fn} failed ({rc}): {handle.last_error()}")
         self._p = p
 
     def close(self):
         if self._p:
-            self._L.wfm_coverage_free(self._p)
+            getattr(self._L, f"wfm_{self._PREFIX}_free")(self._p)
             self._p = None
 
     def __del__(self):
@@ -666,90 +727,102 @@ class Coverage:
         except Exception:
             pass
 
+    def _call(self, fn, *args, counted=False):
+        """fn(handle, object, *args); counted: a positive return value is a count, not an error."""
+        rc = getattr(self._L, fn)(self._h._p, self._p, *args)
+        if rc < 0 or (rc and not counted):
+            raise WfmError(f"{fn} failed ({rc}): {self._h.last_error()}")
+        return rc
+
+    def _add(self, fn, problems, dtype, runs, spans):
+        """An add that takes runs: the problems as `dtype`, the run words, the problems' flags back; the call returns how many hold `spans`."""
+        probs, probs_p = _run_problems(problems, dtype)
+        runs = np.ascontiguousarray(runs, dtype=np.uint32)
+        flags = np.zeros(max(len(problems), 1), dtype=np.uint32)
+        rc = self._call(fn, probs_p, len(probs), runs.ctypes.data if len(runs) else None, len(runs), flags.ctypes.data, counted=True)
+        assert rc == int(np.count_nonzero(flags[:len(problems)] & spans))
+        return flags[:len(problems)]
+
+    def _take(self, ptr, nbytes):
+        try:
+            return C.string_at(ptr, nbytes) if nbytes else b""
+        finally:
+            getattr(self._L, self._FREE_LIST or f"wfm_{self._PREFIX}_free_list")(ptr)
+
+    def _array(self, ptr, n, dtype):
+        """a list the library allocated, as a numpy array; the list is freed"""
+        return np.frombuffer(self._take(ptr, n.value * dtype.itemsize), dtype=dtype)
+
+    def _counts(self, k):
+        fn = f"wfm_{self._PREFIX}_counts"
+        out = (C.c_uint64 * k)()
+        rc = getattr(self._L, fn)(self._p, out)
+        if rc != 0:
+            raise WfmError(f"{fn} failed ({rc})")
+        return tuple(int(v) for v in out)
+
+
+def _interval_array(intervals):
+    """[(start, end)] as an array of wfm_lift_iv_t, and its address (None for an empty list)"""
+    iv = np.zeros(len(intervals), dtype=LIFT_IV_DTYPE)
+    for i, (a, b) in enumerate(intervals):
+        iv[i] = (a, b)
+    return iv, (iv.ctypes.data if len(iv) else None)
+
+
+def _take_lists(free, *lists):
+    """The outputs of an emitting call, each (pointer, bytes), as bytes objects; then free(*pointers)."""
+    try:
+        return [C.string_at(p, nbytes) if nbytes else b"" for p, nbytes in lists]
+    finally:
+        free(*(p for p, _ in lists))
+
+
+class Coverage(_DeviceObject):
+    """wfm_coverage_t: per-base depth of n_bases target bases, summed on the device over every problem added (include/wfmash_hip.h).
+    Close it before its handle."""
+    _PREFIX = "coverage"
+
+    def __init__(self, handle, n_bases):
+        self.n_bases = int(n_bases)
+        self._create(handle, self.n_bases)
+
     def add(self, problems, runs):
         """wfm_coverage_add.  problems: a list of (base, runs_off, n_runs); runs: the run words ((length << 2) | op).  Returns the
         problems' flags as a numpy array (WFM_COV_SPANS: nothing of the problem was added)."""
-        probs, probs_p = _run_problems(problems, COV_PROB_DTYPE)
-        runs = np.ascontiguousarray(runs, dtype=np.uint32)
-        flags = np.zeros(max(len(problems), 1), dtype=np.uint32)
-        rc = self._L.wfm_coverage_add(self._h._p, self._p, probs_p, len(probs),
-                                      runs.ctypes.data if len(runs) else None, len(runs), flags.ctypes.data)
-        if rc < 0:
-            raise WfmError(f"wfm_coverage_add failed ({rc}): {self._h.last_error()}")
-        assert rc == int(np.count_nonzero(flags[:len(problems)] & WFM_COV_SPANS))
-        return flags[:len(problems)]
+        return self._add("wfm_coverage_add", problems, COV_PROB_DTYPE, runs, WFM_COV_SPANS)
 
     def export(self):
         """wfm_coverage_export: the non-zero words of the difference array, ascending, as a numpy array with the fields of CovEntry."""
         ptr, n = C.c_void_p(), C.c_size_t(0)
-        rc = self._L.wfm_coverage_export(self._h._p, self._p, C.byref(ptr), C.byref(n))
-        if rc != 0:
-            raise WfmError(f"wfm_coverage_export failed ({rc}): {self._h.last_error()}")
-        try:
-            raw = C.string_at(ptr, n.value * C.sizeof(CovEntry)) if n.value else b""
-        finally:
-            self._L.wfm_coverage_free_list(ptr)
-        return np.frombuffer(raw, dtype=COV_ENTRY_DTYPE)
+        self._call("wfm_coverage_export", C.byref(ptr), C.byref(n))
+        return self._array(ptr, n, COV_ENTRY_DTYPE)
 
     def import_entries(self, entries):
         """wfm_coverage_import: such a list (of another object, of another device) added into this one."""
         e = np.ascontiguousarray(entries, dtype=COV_ENTRY_DTYPE)
-        rc = self._L.wfm_coverage_import(self._h._p, self._p, e.ctypes.data if len(e) else None, len(e))
-        if rc != 0:
-            raise WfmError(f"wfm_coverage_import failed ({rc}): {self._h.last_error()}")
+        self._call("wfm_coverage_import", e.ctypes.data if len(e) else None, len(e))
 
     def intervals(self):
         """wfm_coverage_intervals: (the maximal intervals of constant depth as a numpy array with the fields of CovInterval,
         (covered bases, sum of depth, max depth))."""
         ptr, n = C.c_void_p(), C.c_size_t(0)
         tot = (C.c_uint64 * 3)()
-        rc = self._L.wfm_coverage_intervals(self._h._p, self._p, C.byref(ptr), C.byref(n), tot)
-        if rc != 0:
-            raise WfmError(f"wfm_coverage_intervals failed ({rc}): {self._h.last_error()}")
-        try:
-            raw = C.string_at(ptr, n.value * C.sizeof(CovInterval)) if n.value else b""
-        finally:
-            self._L.wfm_coverage_free_list(ptr)
-        return np.frombuffer(raw, dtype=COV_INTERVAL_DTYPE), tuple(int(v) for v in tot)
+        self._call("wfm_coverage_intervals", C.byref(ptr), C.byref(n), tot)
+        return self._array(ptr, n, COV_INTERVAL_DTYPE), tuple(int(v) for v in tot)
 
 
-class LiftSet:
+class LiftSet(_DeviceObject):
     """wfm_liftset_t: sorted intervals [(start, end)] over n_bases target bases, on the handle's device (include/wfmash_hip.h).  Close it
     before its handle."""
+    _PREFIX = "liftset"
+    _FREE_LIST = "wfm_free_lifts"
 
     def __init__(self, handle, intervals, n_bases):
-        self._h, self._L = handle, handle._L
         self.n_bases = int(n_bases)
-        L = self._L
-        L.wfm_liftset_create.restype = C.c_int
-        L.wfm_liftset_create.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.POINTER(C.c_void_p)]
-        L.wfm_liftset_free.restype = None
-        L.wfm_liftset_free.argtypes = [C.c_void_p]
-        L.wfm_lift_runs.restype = C.c_int
-        L.wfm_lift_runs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
-                                    C.c_void_p]
-        L.wfm_free_lifts.restype = None
-        L.wfm_free_lifts.argtypes = [C.c_void_p]
-        iv = np.zeros(len(intervals), dtype=LIFT_IV_DTYPE)
-        for i, (a, b) in enumerate(intervals):
-            iv[i] = (a, b)
+        iv, iv_p = _interval_array(intervals)
         self.n = len(iv)
-        p = C.c_void_p()
-        rc = L.wfm_liftset_create(handle._p, iv.ctypes.data if len(iv) else None, len(iv), self.n_bases, C.byref(p))
-        if rc != 0:
-            raise WfmError(f"wfm_liftset_create failed ({rc}): {handle.last_error()}")
-        self._p = p
-
-    def close(self):
-        if self._p:
-            self._L.wfm_liftset_free(self._p)
-            self._p = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(handle, iv_p, len(iv), self.n_bases)
 
     def lift(self, problems, runs):
         """wfm_lift_runs.  problems: a list of (base, runs_off, n_runs); runs: the run words ((length << 2) | op).  Returns (the lifts as
@@ -758,169 +831,68 @@ class LiftSet:
         runs = np.ascontiguousarray(runs, dtype=np.uint32)
         per = np.zeros(max(len(problems), 1), dtype=LIFTCALL_DTYPE)
         ptr, n = C.c_void_p(), C.c_size_t(0)
-        rc = self._L.wfm_lift_runs(self._h._p, self._p, probs_p, len(probs),
-                                   runs.ctypes.data if len(runs) else None, len(runs), C.byref(ptr), C.byref(n), per.ctypes.data)
-        if rc != 0:
-            assert not ptr.value and n.value == 0
-            raise WfmError(f"wfm_lift_runs failed ({rc}): {self._h.last_error()}")
         try:
-            raw = C.string_at(ptr, n.value * C.sizeof(Lift)) if n.value else b""
-        finally:
-            self._L.wfm_free_lifts(ptr)
-        return np.frombuffer(raw, dtype=LIFT_DTYPE), per[:len(problems)]
+            self._call("wfm_lift_runs", probs_p, len(probs), runs.ctypes.data if len(runs) else None, len(runs), C.byref(ptr), C.byref(n), per.ctypes.data)
+        except WfmError:
+            assert not ptr.value and n.value == 0
+            raise
+        return self._array(ptr, n, LIFT_DTYPE), per[:len(problems)]
 
 
-class Pav:
+class Pav(_DeviceObject):
     """wfm_pav_t: per group the union of the aligned bases of every problem added, as segments on the handle's device, over n_bases target
     bases and n_groups groups (include/wfmash_hip.h).  Close it before its handle."""
+    _PREFIX = "pav"
 
     def __init__(self, handle, n_bases, n_groups):
-        self._h, self._L = handle, handle._L
         self.n_bases, self.n_groups = int(n_bases), int(n_groups)
-        self._p = None
-        L = self._L
-        L.wfm_pav_create.restype = C.c_int
-        L.wfm_pav_create.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]
-        L.wfm_pav_free.restype = None
-        L.wfm_pav_free.argtypes = [C.c_void_p]
-        L.wfm_pav_add.restype = C.c_int
-        L.wfm_pav_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.wfm_pav_union.restype = C.c_int
-        L.wfm_pav_union.argtypes = [C.c_void_p, C.c_void_p]
-        L.wfm_pav_export.restype = C.c_int
-        L.wfm_pav_export.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
-        L.wfm_pav_import.restype = C.c_int
-        L.wfm_pav_import.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
-        L.wfm_pav_matrix.restype = C.c_int
-        L.wfm_pav_matrix.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.wfm_pav_counts.restype = C.c_int
-        L.wfm_pav_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
-        L.wfm_pav_free_list.restype = None
-        L.wfm_pav_free_list.argtypes = [C.c_void_p]
         if not 0 <= self.n_groups < (1 << 32):
             raise WfmError(f"wfm_pav_create: {self.n_groups} groups do not fit 32 bits")
-        p = C.c_void_p()
-        rc = L.wfm_pav_create(handle._p, self.n_bases, self.n_groups, C.byref(p))
-        if rc != 0:
-            raise WfmError(f"wfm_pav_create failed ({rc}): {handle.last_error()}")
-        self._p = p
-
-    def close(self):
-        if self._p:
-            self._L.wfm_pav_free(self._p)
-            self._p = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(handle, self.n_bases, self.n_groups)
 
     def add(self, problems, runs):
         """wfm_pav_add.  problems: a list of (base, runs_off, n_runs, group); runs: the run words ((length << 2) | op).  Returns the
         problems' flags as a numpy array (WFM_PAV_SPANS: nothing of the problem was added)."""
-        probs, probs_p = _run_problems(problems, PAV_PROB_DTYPE)
-        runs = np.ascontiguousarray(runs, dtype=np.uint32)
-        flags = np.zeros(max(len(problems), 1), dtype=np.uint32)
-        rc = self._L.wfm_pav_add(self._h._p, self._p, probs_p, len(probs),
-                                 runs.ctypes.data if len(runs) else None, len(runs), flags.ctypes.data)
-        if rc < 0:
-            raise WfmError(f"wfm_pav_add failed ({rc}): {self._h.last_error()}")
-        assert rc == int(np.count_nonzero(flags[:len(problems)] & WFM_PAV_SPANS))
-        return flags[:len(problems)]
+        return self._add("wfm_pav_add", problems, PAV_PROB_DTYPE, runs, WFM_PAV_SPANS)
 
     def union(self):
         """wfm_pav_union: the list becomes the disjoint union per group."""
-        rc = self._L.wfm_pav_union(self._h._p, self._p)
-        if rc != 0:
-            raise WfmError(f"wfm_pav_union failed ({rc}): {self._h.last_error()}")
+        self._call("wfm_pav_union")
 
     def export(self):
         """wfm_pav_export: the union sorted by (group, start) as a numpy array with the fields {start, length, group}."""
         ptr, n = C.c_void_p(), C.c_size_t(0)
-        rc = self._L.wfm_pav_export(self._h._p, self._p, C.byref(ptr), C.byref(n))
-        if rc != 0:
-            raise WfmError(f"wfm_pav_export failed ({rc}): {self._h.last_error()}")
-        try:
-            raw = C.string_at(ptr, n.value * PAV_SEG_DTYPE.itemsize) if n.value else b""
-        finally:
-            self._L.wfm_pav_free_list(ptr)
-        return np.frombuffer(raw, dtype=PAV_SEG_DTYPE)
+        self._call("wfm_pav_export", C.byref(ptr), C.byref(n))
+        return self._array(ptr, n, PAV_SEG_DTYPE)
 
     def import_(self, segs):
         """wfm_pav_import: such a list (of another object, of another device) appended as raw segments."""
         e = np.ascontiguousarray(segs, dtype=PAV_SEG_DTYPE)
-        rc = self._L.wfm_pav_import(self._h._p, self._p, e.ctypes.data if len(e) else None, len(e))
-        if rc != 0:
-            raise WfmError(f"wfm_pav_import failed ({rc}): {self._h.last_error()}")
+        self._call("wfm_pav_import", e.ctypes.data if len(e) else None, len(e))
 
     def matrix(self, intervals):
         """wfm_pav_matrix.  intervals: a list of (start, end), global and half-open.  Returns a numpy array [interval, group] of the
         covered bases."""
-        iv = np.zeros(len(intervals), dtype=LIFT_IV_DTYPE)
-        for i, (a, b) in enumerate(intervals):
-            iv[i] = (a, b)
+        iv, iv_p = _interval_array(intervals)
         out = np.zeros((len(iv), self.n_groups), dtype=np.uint32)
-        rc = self._L.wfm_pav_matrix(self._h._p, self._p, iv.ctypes.data if len(iv) else None, len(iv), out.ctypes.data if out.size else None)
-        if rc != 0:
-            raise WfmError(f"wfm_pav_matrix failed ({rc}): {self._h.last_error()}")
+        self._call("wfm_pav_matrix", iv_p, len(iv), out.ctypes.data if out.size else None)
         return out
 
     def counts(self):
         """wfm_pav_counts: (segments added, union intervals after the last union, unions run)."""
-        out = (C.c_uint64 * 3)()
-        rc = self._L.wfm_pav_counts(self._p, out)
-        if rc != 0:
-            raise WfmError(f"wfm_pav_counts failed ({rc})")
-        return tuple(int(v) for v in out)
+        return self._counts(3)
 
 
-class Sites:
+class Sites(_DeviceObject):
     """wfm_sites_t: the variants of many records (global position, group, alleles) and the = runs of the same records, on the handle's device;
     .table() joins them into distinct sites and a sites x groups table of '0' / '1' / '.' (include/wfmash_hip.h).  Close it before its handle."""
+    _PREFIX = "sites"
 
     def __init__(self, handle, n_bases, n_groups):
-        self._h, self._L = handle, handle._L
         self.n_bases, self.n_groups = int(n_bases), int(n_groups)
-        self._p = None
-        L = self._L
-        P = C.POINTER
-        L.wfm_sites_create.restype = C.c_int
-        L.wfm_sites_create.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, P(C.c_void_p)]
-        L.wfm_sites_free.restype = None
-        L.wfm_sites_free.argtypes = [C.c_void_p]
-        L.wfm_sites_add_variants.restype = C.c_int
-        L.wfm_sites_add_variants.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_char_p, C.c_size_t]
-        L.wfm_sites_add_ref.restype = C.c_int
-        L.wfm_sites_add_ref.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.wfm_sites_table.restype = C.c_int
-        L.wfm_sites_table.argtypes = [C.c_void_p, C.c_void_p, P(C.c_void_p), P(C.c_size_t), P(C.c_void_p), P(C.c_size_t), P(C.c_void_p)]
-        L.wfm_sites_export.restype = C.c_int
-        L.wfm_sites_export.argtypes = [C.c_void_p, C.c_void_p, P(C.c_void_p), P(C.c_size_t), P(C.c_void_p), P(C.c_size_t), P(C.c_void_p), P(C.c_size_t)]
-        L.wfm_sites_import.restype = C.c_int
-        L.wfm_sites_import.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t]
-        L.wfm_sites_counts.restype = C.c_int
-        L.wfm_sites_counts.argtypes = [C.c_void_p, P(C.c_uint64)]
-        L.wfm_sites_free_list.restype = None
-        L.wfm_sites_free_list.argtypes = [C.c_void_p]
         if not 0 <= self.n_groups < (1 << 32):
             raise WfmError(f"wfm_sites_create: {self.n_groups} groups do not fit 32 bits")
-        p = C.c_void_p()
-        rc = L.wfm_sites_create(handle._p, self.n_bases, self.n_groups, C.byref(p))
-        if rc != 0:
-            raise WfmError(f"wfm_sites_create failed ({rc}): {handle.last_error()}")
-        self._p = p
-
-    def close(self):
-        if self._p:
-            self._L.wfm_sites_free(self._p)
-            self._p = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(handle, self.n_bases, self.n_groups)
 
     @staticmethod
     def pack(variants):
@@ -937,37 +909,20 @@ class Sites:
         """wfm_sites_add_variants.  variants: a list of (pos, kind, group, ref bytes, alt bytes), or, with `alleles`, an array of
         wfm_site_var_t whose off point into those bytes."""
         v, a = self.pack(variants) if alleles is None else (np.ascontiguousarray(variants, dtype=SITE_VAR_DTYPE), bytes(alleles))
-        rc = self._L.wfm_sites_add_variants(self._h._p, self._p, v.ctypes.data if len(v) else None, len(v), a if a else None, len(a))
-        if rc != 0:
-            raise WfmError(f"wfm_sites_add_variants failed ({rc}): {self._h.last_error()}")
+        self._call("wfm_sites_add_variants", v.ctypes.data if len(v) else None, len(v), a if a else None, len(a))
 
     def add_ref(self, problems, runs):
         """wfm_sites_add_ref: Pav.add's arguments and flags; the = runs alone make segments."""
-        probs, probs_p = _run_problems(problems, PAV_PROB_DTYPE)
-        runs = np.ascontiguousarray(runs, dtype=np.uint32)
-        flags = np.zeros(max(len(problems), 1), dtype=np.uint32)
-        rc = self._L.wfm_sites_add_ref(self._h._p, self._p, probs_p, len(probs), runs.ctypes.data if len(runs) else None, len(runs), flags.ctypes.data)
-        if rc < 0:
-            raise WfmError(f"wfm_sites_add_ref failed ({rc}): {self._h.last_error()}")
-        assert rc == int(np.count_nonzero(flags[:len(problems)] & WFM_PAV_SPANS))
-        return flags[:len(problems)]
-
-    def _take(self, ptr, nbytes):
-        try:
-            return C.string_at(ptr, nbytes) if nbytes else b""
-        finally:
-            self._L.wfm_sites_free_list(ptr)
+        return self._add("wfm_sites_add_ref", problems, PAV_PROB_DTYPE, runs, WFM_PAV_SPANS)
 
     def table(self):
         """wfm_sites_table: (sites as an array of wfm_site_t in ascending pos, their allele bytes, gt as a uint8 array [site, group] of
         b'0' / b'1' / b'.')."""
         sp, ap, gp, n, nb = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_size_t(0), C.c_size_t(0)
-        rc = self._L.wfm_sites_table(self._h._p, self._p, C.byref(sp), C.byref(n), C.byref(ap), C.byref(nb), C.byref(gp))
-        if rc != 0:
-            raise WfmError(f"wfm_sites_table failed ({rc}): {self._h.last_error()}")
+        self._call("wfm_sites_table", C.byref(sp), C.byref(n), C.byref(ap), C.byref(nb), C.byref(gp))
         if n.value == 0:
             assert not sp.value and not ap.value and not gp.value and nb.value == 0
-        sites = np.frombuffer(self._take(sp, n.value * SITE_DTYPE.itemsize), dtype=SITE_DTYPE)
+        sites = self._array(sp, n, SITE_DTYPE)
         alleles = self._take(ap, nb.value)
         gt = np.frombuffer(self._take(gp, n.value * self.n_groups), dtype=np.uint8).reshape(n.value, self.n_groups)
         return sites, alleles, gt
@@ -975,231 +930,101 @@ class Sites:
     def export(self):
         """wfm_sites_export: (the raw variants as an array of wfm_site_var_t, their folded allele bytes, the = union as Pav.export gives it)."""
         vp, ap, gp, n, nb, ns = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
-        rc = self._L.wfm_sites_export(self._h._p, self._p, C.byref(vp), C.byref(n), C.byref(ap), C.byref(nb), C.byref(gp), C.byref(ns))
-        if rc != 0:
-            raise WfmError(f"wfm_sites_export failed ({rc}): {self._h.last_error()}")
-        return (np.frombuffer(self._take(vp, n.value * SITE_VAR_DTYPE.itemsize), dtype=SITE_VAR_DTYPE), self._take(ap, nb.value),
-                np.frombuffer(self._take(gp, ns.value * PAV_SEG_DTYPE.itemsize), dtype=PAV_SEG_DTYPE))
+        self._call("wfm_sites_export", C.byref(vp), C.byref(n), C.byref(ap), C.byref(nb), C.byref(gp), C.byref(ns))
+        return self._array(vp, n, SITE_VAR_DTYPE), self._take(ap, nb.value), self._array(gp, ns, PAV_SEG_DTYPE)
 
     def import_(self, variants, alleles, segs):
         """wfm_sites_import: what export returned (of another object, of another device), appended."""
         v = np.ascontiguousarray(variants, dtype=SITE_VAR_DTYPE)
         e = np.ascontiguousarray(segs, dtype=PAV_SEG_DTYPE)
         a = bytes(alleles)
-        rc = self._L.wfm_sites_import(self._h._p, self._p, v.ctypes.data if len(v) else None, len(v), a if a else None, len(a),
-                                      e.ctypes.data if len(e) else None, len(e))
-        if rc != 0:
-            raise WfmError(f"wfm_sites_import failed ({rc}): {self._h.last_error()}")
+        self._call("wfm_sites_import", v.ctypes.data if len(v) else None, len(v), a if a else None, len(a), e.ctypes.data if len(e) else None, len(e))
 
     def counts(self):
         """wfm_sites_counts: (variants added, distinct sites of the last table, = union intervals after the last union, collisions of the last table)."""
-        out = (C.c_uint64 * 4)()
-        rc = self._L.wfm_sites_counts(self._p, out)
-        if rc != 0:
-            raise WfmError(f"wfm_sites_counts failed ({rc})")
-        return tuple(int(v) for v in out)
+        return self._counts(4)
 
 
-class Net:
+class Net(_DeviceObject):
     """wfm_net_t: the blocks of many records, each with a score and a unique order, on the handle's device; .table() gives every target
     base to the best record over it and returns the pieces that are left (include/wfmash_hip.h).  Close it before its handle."""
+    _PREFIX = "net"
 
     def __init__(self, handle, n_bases):
-        self._h, self._L = handle, handle._L
         self.n_bases = int(n_bases)
-        self._p = None
-        L = self._L
-        P = C.POINTER
-        L.wfm_net_create.restype = C.c_int
-        L.wfm_net_create.argtypes = [C.c_void_p, C.c_uint64, P(C.c_void_p)]
-        L.wfm_net_free.restype = None
-        L.wfm_net_free.argtypes = [C.c_void_p]
-        L.wfm_net_add.restype = C.c_int
-        L.wfm_net_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.wfm_net_table.restype = C.c_int
-        L.wfm_net_table.argtypes = [C.c_void_p, C.c_void_p, P(C.c_void_p), P(C.c_size_t), P(C.c_void_p), P(C.c_size_t)]
-        L.wfm_net_export.restype = C.c_int
-        L.wfm_net_export.argtypes = [C.c_void_p, C.c_void_p, P(C.c_void_p), P(C.c_size_t), P(C.c_void_p), P(C.c_size_t)]
-        L.wfm_net_import.restype = C.c_int
-        L.wfm_net_import.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
-        L.wfm_net_counts.restype = C.c_int
-        L.wfm_net_counts.argtypes = [C.c_void_p, P(C.c_uint64)]
-        L.wfm_net_free_list.restype = None
-        L.wfm_net_free_list.argtypes = [C.c_void_p]
-        p = C.c_void_p()
-        rc = L.wfm_net_create(handle._p, self.n_bases, C.byref(p))
-        if rc != 0:
-            raise WfmError(f"wfm_net_create failed ({rc}): {handle.last_error()}")
-        self._p = p
-
-    def close(self):
-        if self._p:
-            self._L.wfm_net_free(self._p)
-            self._p = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(handle, self.n_bases)
 
     def add(self, problems, runs):
         """wfm_net_add.  problems: a list of (base, runs_off, n_runs, score, order), score WFM_NET_SCORE_EQ for the = columns; runs: the run
         words ((length << 2) | op).  Returns the problems' flags as a numpy array (WFM_NET_SPANS: nothing of the problem was added)."""
-        probs, probs_p = _run_problems(problems, NET_PROB_DTYPE)
-        runs = np.ascontiguousarray(runs, dtype=np.uint32)
-        flags = np.zeros(max(len(problems), 1), dtype=np.uint32)
-        rc = self._L.wfm_net_add(self._h._p, self._p, probs_p, len(probs), runs.ctypes.data if len(runs) else None, len(runs), flags.ctypes.data)
-        if rc < 0:
-            raise WfmError(f"wfm_net_add failed ({rc}): {self._h.last_error()}")
-        assert rc == int(np.count_nonzero(flags[:len(problems)] & WFM_NET_SPANS))
-        return flags[:len(problems)]
-
-    def _take(self, ptr, nbytes):
-        try:
-            return C.string_at(ptr, nbytes) if nbytes else b""
-        finally:
-            self._L.wfm_net_free_list(ptr)
+        return self._add("wfm_net_add", problems, NET_PROB_DTYPE, runs, WFM_NET_SPANS)
 
     def table(self):
         """wfm_net_table: (the pieces {order, t, q, size} sorted by (order, t), the records {order, score, zero, first, count, bases_won,
         bases_aligned} sorted by order), two numpy arrays."""
         pp, rp, n, nr = C.c_void_p(), C.c_void_p(), C.c_size_t(0), C.c_size_t(0)
-        rc = self._L.wfm_net_table(self._h._p, self._p, C.byref(pp), C.byref(n), C.byref(rp), C.byref(nr))
-        if rc != 0:
-            raise WfmError(f"wfm_net_table failed ({rc}): {self._h.last_error()}")
+        self._call("wfm_net_table", C.byref(pp), C.byref(n), C.byref(rp), C.byref(nr))
         if n.value == 0:
             assert not pp.value
         if nr.value == 0:
             assert not rp.value and n.value == 0
-        return (np.frombuffer(self._take(pp, n.value * NET_BLOCK_DTYPE.itemsize), dtype=NET_BLOCK_DTYPE),
-                np.frombuffer(self._take(rp, nr.value * NET_CALL_DTYPE.itemsize), dtype=NET_CALL_DTYPE))
+        return self._array(pp, n, NET_BLOCK_DTYPE), self._array(rp, nr, NET_CALL_DTYPE)
 
     def export(self):
         """wfm_net_export: (the raw blocks as an array of wfm_net_block_t, the record entries as an array of wfm_net_rec_t)."""
         bp, rp, n, nr = C.c_void_p(), C.c_void_p(), C.c_size_t(0), C.c_size_t(0)
-        rc = self._L.wfm_net_export(self._h._p, self._p, C.byref(bp), C.byref(n), C.byref(rp), C.byref(nr))
-        if rc != 0:
-            raise WfmError(f"wfm_net_export failed ({rc}): {self._h.last_error()}")
-        return (np.frombuffer(self._take(bp, n.value * NET_BLOCK_DTYPE.itemsize), dtype=NET_BLOCK_DTYPE),
-                np.frombuffer(self._take(rp, nr.value * NET_REC_DTYPE.itemsize), dtype=NET_REC_DTYPE))
+        self._call("wfm_net_export", C.byref(bp), C.byref(n), C.byref(rp), C.byref(nr))
+        return self._array(bp, n, NET_BLOCK_DTYPE), self._array(rp, nr, NET_REC_DTYPE)
 
     def import_(self, blocks, recs):
         """wfm_net_import: what export returned (of another object, of another device), appended."""
         b = np.ascontiguousarray(blocks, dtype=NET_BLOCK_DTYPE)
         r = np.ascontiguousarray(recs, dtype=NET_REC_DTYPE)
-        rc = self._L.wfm_net_import(self._h._p, self._p, b.ctypes.data if len(b) else None, len(b), r.ctypes.data if len(r) else None, len(r))
-        if rc != 0:
-            raise WfmError(f"wfm_net_import failed ({rc}): {self._h.last_error()}")
+        self._call("wfm_net_import", b.ctypes.data if len(b) else None, len(b), r.ctypes.data if len(r) else None, len(r))
 
     def counts(self):
         """wfm_net_counts: (records, blocks, and of the last table: elementary intervals, pieces, records that won nothing)."""
-        out = (C.c_uint64 * 6)()
-        rc = self._L.wfm_net_counts(self._p, out)
-        if rc != 0:
-            raise WfmError(f"wfm_net_counts failed ({rc})")
-        return tuple(int(v) for v in out)[:5]
+        return self._counts(6)[:5]
 
 
-class Transitive:
+class Transitive(_DeviceObject):
     """wfm_trans_t: the records of a run as arcs of one coordinate space, on the handle's device; .closure(seeds, depth) gives per seed
     interval everything it reaches through any chain of records, either way (include/wfmash_hip.h).  Close it before its handle."""
+    _PREFIX = "trans"
 
     def __init__(self, handle, n_bases):
-        self._h, self._L = handle, handle._L
         self.n_bases = int(n_bases)
-        self._p = None
-        L = self._L
-        P = C.POINTER
-        L.wfm_trans_create.restype = C.c_int
-        L.wfm_trans_create.argtypes = [C.c_void_p, C.c_uint64, P(C.c_void_p)]
-        L.wfm_trans_free.restype = None
-        L.wfm_trans_free.argtypes = [C.c_void_p]
-        L.wfm_trans_add.restype = C.c_int
-        L.wfm_trans_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.wfm_trans_closure.restype = C.c_int
-        L.wfm_trans_closure.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, P(C.c_void_p), P(C.c_size_t), C.c_void_p]
-        L.wfm_trans_export.restype = C.c_int
-        L.wfm_trans_export.argtypes = [C.c_void_p, C.c_void_p, P(C.c_void_p), P(C.c_size_t), P(C.c_void_p), P(C.c_size_t)]
-        L.wfm_trans_import.restype = C.c_int
-        L.wfm_trans_import.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
-        L.wfm_trans_counts.restype = C.c_int
-        L.wfm_trans_counts.argtypes = [C.c_void_p, P(C.c_uint64)]
-        L.wfm_trans_free_list.restype = None
-        L.wfm_trans_free_list.argtypes = [C.c_void_p]
-        p = C.c_void_p()
-        rc = L.wfm_trans_create(handle._p, self.n_bases, C.byref(p))
-        if rc != 0:
-            raise WfmError(f"wfm_trans_create failed ({rc}): {handle.last_error()}")
-        self._p = p
-
-    def close(self):
-        if self._p:
-            self._L.wfm_trans_free(self._p)
-            self._p = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(handle, self.n_bases)
 
     def add(self, problems, runs):
         """wfm_trans_add.  problems: a list of (t, q, runs_off, n_runs, flags), flags WFM_TRANS_REVERSE or 0; runs: the run words
         ((length << 2) | op).  Returns the problems' flags as a numpy array (WFM_TRANS_SPANS: nothing of the problem was added)."""
-        probs, probs_p = _run_problems(problems, TRANS_PROB_DTYPE)
-        runs = np.ascontiguousarray(runs, dtype=np.uint32)
-        flags = np.zeros(max(len(problems), 1), dtype=np.uint32)
-        rc = self._L.wfm_trans_add(self._h._p, self._p, probs_p, len(probs), runs.ctypes.data if len(runs) else None, len(runs), flags.ctypes.data)
-        if rc < 0:
-            raise WfmError(f"wfm_trans_add failed ({rc}): {self._h.last_error()}")
-        assert rc == int(np.count_nonzero(flags[:len(problems)] & WFM_TRANS_SPANS))
-        return flags[:len(problems)]
-
-    def _take(self, ptr, nbytes):
-        try:
-            return C.string_at(ptr, nbytes) if nbytes else b""
-        finally:
-            self._L.wfm_trans_free_list(ptr)
+        return self._add("wfm_trans_add", problems, TRANS_PROB_DTYPE, runs, WFM_TRANS_SPANS)
 
     def closure(self, seeds, depth=2):
         """wfm_trans_closure: seeds = [(start, end)] in world coordinates; depth 0 walks to the fixed point.  Returns (the intervals {start,
         end, seed} sorted by (seed, start), per seed {first, count, bases}), two numpy arrays."""
-        iv = np.zeros(len(seeds), dtype=LIFT_IV_DTYPE)
-        for i, (a, b) in enumerate(seeds):
-            iv[i] = (a, b)
+        iv, iv_p = _interval_array(seeds)
         per = np.zeros(max(len(seeds), 1), dtype=TRANS_SEED_DTYPE)
         pp, n = C.c_void_p(), C.c_size_t(0)
-        rc = self._L.wfm_trans_closure(self._h._p, self._p, iv.ctypes.data if len(iv) else None, len(iv), int(depth), C.byref(pp), C.byref(n),
-                                       per.ctypes.data)
-        if rc != 0:
-            raise WfmError(f"wfm_trans_closure failed ({rc}): {self._h.last_error()}")
-        return np.frombuffer(self._take(pp, n.value * TRANS_IV_DTYPE.itemsize), dtype=TRANS_IV_DTYPE), per[:len(seeds)]
+        self._call("wfm_trans_closure", iv_p, len(iv), int(depth), C.byref(pp), C.byref(n), per.ctypes.data)
+        return self._array(pp, n, TRANS_IV_DTYPE), per[:len(seeds)]
 
     def export(self):
         """wfm_trans_export: (the records as an array of wfm_trans_rec_t, their prefix words as an array of wfm_trans_word_t)."""
         rp, wp, n, nw = C.c_void_p(), C.c_void_p(), C.c_size_t(0), C.c_size_t(0)
-        rc = self._L.wfm_trans_export(self._h._p, self._p, C.byref(rp), C.byref(n), C.byref(wp), C.byref(nw))
-        if rc != 0:
-            raise WfmError(f"wfm_trans_export failed ({rc}): {self._h.last_error()}")
-        return (np.frombuffer(self._take(rp, n.value * TRANS_REC_DTYPE.itemsize), dtype=TRANS_REC_DTYPE),
-                np.frombuffer(self._take(wp, nw.value * TRANS_WORD_DTYPE.itemsize), dtype=TRANS_WORD_DTYPE))
+        self._call("wfm_trans_export", C.byref(rp), C.byref(n), C.byref(wp), C.byref(nw))
+        return self._array(rp, n, TRANS_REC_DTYPE), self._array(wp, nw, TRANS_WORD_DTYPE)
 
     def import_(self, recs, words):
         """wfm_trans_import: what export returned (of another object, of another device), appended."""
         r = np.ascontiguousarray(recs, dtype=TRANS_REC_DTYPE)
         w = np.ascontiguousarray(words, dtype=TRANS_WORD_DTYPE)
-        rc = self._L.wfm_trans_import(self._h._p, self._p, r.ctypes.data if len(r) else None, len(r), w.ctypes.data if len(w) else None, len(w))
-        if rc != 0:
-            raise WfmError(f"wfm_trans_import failed ({rc}): {self._h.last_error()}")
+        self._call("wfm_trans_import", r.ctypes.data if len(r) else None, len(r), w.ctypes.data if len(w) else None, len(w))
 
     def counts(self):
         """wfm_trans_counts: (records, prefix words, arcs, and of the last closure: rounds run, intervals returned, pairs projected)."""
-        out = (C.c_uint64 * 6)()
-        rc = self._L.wfm_trans_counts(self._p, out)
-        if rc != 0:
-            raise WfmError(f"wfm_trans_counts failed ({rc})")
-        return tuple(int(v) for v in out)
+        return self._counts(6)
 
 
 class Handle:
@@ -1400,10 +1225,7 @@ class Handle:
         runs = np.ascontiguousarray(runs, dtype=np.uint32)
         pn = Penalties(*(pen or DEFAULT_PEN))
         out = (Check * max(n, 1))()
-        f = self._L.wfm_check_runs
-        f.restype = C.c_int
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        rc = f(self._p, C.byref(pn), seqset._p, results, runs.ctypes.data if len(runs) else None, len(runs), out)
+        rc = self._L.wfm_check_runs(self._p, C.byref(pn), seqset._p, results, runs.ctypes.data if len(runs) else None, len(runs), out)
         if rc < 0:
             raise WfmError(f"wfm_check_runs failed ({rc}): {self.last_error()}")
         return rc, [out[i] for i in range(n)]
@@ -1419,12 +1241,9 @@ class Handle:
         out = (LeftAlign * max(n, 1))()
         new = C.POINTER(C.c_uint32)()
         total = C.c_size_t(0)
-        f = self._L.wfm_left_align_runs
-        f.restype = C.c_int
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_size_t), C.c_void_p]
         self._L.wfm_free_runs.restype = None
         self._L.wfm_free_runs.argtypes = [C.POINTER(C.c_uint32)]
-        rc = f(self._p, seqset._p, arr, runs.ctypes.data if len(runs) else None, len(runs), C.byref(new), C.byref(total), out)
+        rc = self._L.wfm_left_align_runs(self._p, seqset._p, arr, runs.ctypes.data if len(runs) else None, len(runs), C.byref(new), C.byref(total), out)
         if rc < 0:
             raise WfmError(f"wfm_left_align_runs failed ({rc}): {self.last_error()}")
         try:
@@ -1443,18 +1262,10 @@ class Handle:
         per = (Cs * max(n, 1))()
         text = C.c_void_p()
         total = C.c_size_t(0)
-        f = self._L.wfm_cs_strings
-        f.restype = C.c_int
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p]
-        self._L.wfm_free_cs.restype = None
-        self._L.wfm_free_cs.argtypes = [C.c_void_p]
-        rc = f(self._p, seqset._p, arr, runs.ctypes.data if len(runs) else None, len(runs), int(form), C.byref(text), C.byref(total), per)
+        rc = self._L.wfm_cs_strings(self._p, seqset._p, arr, runs.ctypes.data if len(runs) else None, len(runs), int(form), C.byref(text), C.byref(total), per)
         if rc < 0:
             raise WfmError(f"wfm_cs_strings failed ({rc}): {self.last_error()}")
-        try:
-            blob = C.string_at(text, total.value) if total.value else b""
-        finally:
-            self._L.wfm_free_cs(text)
+        blob, = _take_lists(self._L.wfm_free_cs, (text, total.value))
         return [blob[per[i].off:per[i].off + per[i].len] for i in range(n)], [per[i] for i in range(n)]
 
     def call_variants(self, seqset, results, runs):
@@ -1467,21 +1278,11 @@ class Handle:
         per = (VarCall * max(n, 1))()
         recs, alleles = C.c_void_p(), C.c_void_p()
         n_recs, n_bytes = C.c_size_t(0), C.c_size_t(0)
-        f = self._L.wfm_call_variants
-        f.restype = C.c_int
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
-                      C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p]
-        self._L.wfm_free_variants.restype = None
-        self._L.wfm_free_variants.argtypes = [C.c_void_p, C.c_void_p]
-        rc = f(self._p, seqset._p, arr, runs.ctypes.data if len(runs) else None, len(runs), C.byref(recs), C.byref(n_recs),
-               C.byref(alleles), C.byref(n_bytes), per)
+        rc = self._L.wfm_call_variants(self._p, seqset._p, arr, runs.ctypes.data if len(runs) else None, len(runs), C.byref(recs), C.byref(n_recs),
+                                       C.byref(alleles), C.byref(n_bytes), per)
         if rc < 0:
             raise WfmError(f"wfm_call_variants failed ({rc}): {self.last_error()}")
-        try:
-            raw = C.string_at(recs, n_recs.value * C.sizeof(Variant)) if n_recs.value else b""
-            blob = C.string_at(alleles, n_bytes.value) if n_bytes.value else b""
-        finally:
-            self._L.wfm_free_variants(recs, alleles)
+        raw, blob = _take_lists(self._L.wfm_free_variants, (recs, n_recs.value * C.sizeof(Variant)), (alleles, n_bytes.value))
         return np.frombuffer(raw, dtype=VARIANT_DTYPE), blob, [per[i] for i in range(n)]
 
     def maf_rows(self, seqset, results, runs, split=0):
@@ -1494,22 +1295,12 @@ class Handle:
         per = (MafCall * max(n, 1))()
         blocks, rows = C.c_void_p(), C.c_void_p()
         n_blocks, n_bytes = C.c_size_t(0), C.c_size_t(0)
-        f = self._L.wfm_maf_rows
-        f.restype = C.c_int
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
-                      C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p]
-        self._L.wfm_free_maf.restype = None
-        self._L.wfm_free_maf.argtypes = [C.c_void_p, C.c_void_p]
-        rc = f(self._p, seqset._p, arr, runs.ctypes.data if len(runs) else None, len(runs), int(split), C.byref(blocks), C.byref(n_blocks),
-               C.byref(rows), C.byref(n_bytes), per)
+        rc = self._L.wfm_maf_rows(self._p, seqset._p, arr, runs.ctypes.data if len(runs) else None, len(runs), int(split), C.byref(blocks), C.byref(n_blocks),
+                                  C.byref(rows), C.byref(n_bytes), per)
         if rc < 0:
             assert not blocks.value and not rows.value and n_blocks.value == 0 and n_bytes.value == 0
             raise WfmError(f"wfm_maf_rows failed ({rc}): {self.last_error()}")
-        try:
-            raw = C.string_at(blocks, n_blocks.value * C.sizeof(MafBlock)) if n_blocks.value else b""
-            blob = C.string_at(rows, n_bytes.value) if n_bytes.value else b""
-        finally:
-            self._L.wfm_free_maf(blocks, rows)
+        raw, blob = _take_lists(self._L.wfm_free_maf, (blocks, n_blocks.value * C.sizeof(MafBlock)), (rows, n_bytes.value))
         return np.frombuffer(raw, dtype=MAF_BLOCK_DTYPE), blob, [per[i] for i in range(n)]
 
     def chain_runs(self, problems, runs):
@@ -1520,19 +1311,11 @@ class Handle:
         runs = np.ascontiguousarray(runs, dtype=np.uint32)
         per = np.zeros(max(len(problems), 1), dtype=CHAINCALL_DTYPE)
         ptr, n = C.c_void_p(), C.c_size_t(0)
-        f = self._L.wfm_chain_runs
-        f.restype = C.c_int
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p]
-        self._L.wfm_free_chain.restype = None
-        self._L.wfm_free_chain.argtypes = [C.c_void_p]
-        rc = f(self._p, probs_p, len(probs), runs.ctypes.data if len(runs) else None, len(runs), C.byref(ptr), C.byref(n), per.ctypes.data)
+        rc = self._L.wfm_chain_runs(self._p, probs_p, len(probs), runs.ctypes.data if len(runs) else None, len(runs), C.byref(ptr), C.byref(n), per.ctypes.data)
         if rc != 0:
             assert not ptr.value and n.value == 0
             raise WfmError(f"wfm_chain_runs failed ({rc}): {self.last_error()}")
-        try:
-            raw = C.string_at(ptr, n.value * CHAIN_BLOCK_DTYPE.itemsize) if n.value else b""
-        finally:
-            self._L.wfm_free_chain(ptr)
+        raw, = _take_lists(self._L.wfm_free_chain, (ptr, n.value * CHAIN_BLOCK_DTYPE.itemsize))
         return np.frombuffer(raw, dtype=CHAIN_BLOCK_DTYPE), per[:len(problems)]
 
     def liftset(self, intervals, n_bases):
@@ -1571,10 +1354,7 @@ class Handle:
             results = _result_array([(r if isinstance(r, tuple) else (0, r)) + (0, 0, 0) for r in results], n)
         pn = Penalties(*(pen or DEFAULT_PEN))
         out = (OptCheck * max(n, 1))()
-        f = self._L.wfm_check_optimal
-        f.restype = C.c_int
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
-        rc = f(self._p, C.byref(pn), seqset._p, results, int(max_cells), out)
+        rc = self._L.wfm_check_optimal(self._p, C.byref(pn), seqset._p, results, int(max_cells), out)
         if rc < 0:
             raise WfmError(f"wfm_check_optimal failed ({rc}): {self.last_error()}")
         return [out[i] for i in range(n)]

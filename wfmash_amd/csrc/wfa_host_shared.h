@@ -148,7 +148,7 @@ struct wfm_handle {
   wfm::DevBuf<int32_t> seqflags;  // wfm_upload_sequences: per problem, nonzero = pure ACGT
   wfm::DevBuf<wfm::SeqRev> flagjobs;
   wfm::DevBuf<wfm::SeqGatherTask> gathertasks;  // wfm_upload_sequence_refs
-  uint8_t* cspin[2] = {nullptr, nullptr};  // the two pinned pieces a chunk's bytes reach the caller's buffer through (CS_PIN_PIECE each)
+  uint8_t* cspin[2] = {nullptr, nullptr};  // the two pinned pieces a chunk's bytes reach the caller's buffer through (PIN_PIECE each)
   wfm::DevBuf<uint64_t> scratch;          // the record passes (wfa_passes.hip): everything a call has on the device, carved out of one block;
   wfm::DevBuf<uint64_t> outblk;           // the output block of one chunk (cs, variants).  A pass waits for the stream before it returns: one of each serves all
   wfm::DevBuf<int32_t> optrows;           // wfm_check_optimal: the rows of the bands too wide for registers

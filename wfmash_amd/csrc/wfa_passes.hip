@@ -1,12 +1,15 @@
 // wfa_passes.hip -- the record passes of the C ABI (see include/wfmash_hip.h): host code that takes the final runs of a batch and
-// produces something from them -- the check against the bases, left-aligned gaps, cs strings, variants, target depth, lifted
-// intervals, the blocks of a chain, presence per group, the sites and genotypes of many records, the net across records, the proof of optimality.
+// produces something from them -- the check against the bases, left-aligned gaps, cs strings, variants, the rows of a MAF, target depth, lifted
+// intervals, the blocks of a chain, presence per group, the sites and genotypes of many records, the net across records, the closure of
+// intervals over all records, the proof of optimality.
 // The kernels are in wfa_check.hip, wfa_leftalign.hip, wfa_cs.hip, wfa_variants.hip, wfa_coverage.hip, wfa_lift.hip, wfa_chain.hip,
 // wfa_pav.hip, wfa_sites.hip, wfa_net.hip, wfa_trans.hip, wfa_maf.hip and wfa_optcheck.hip.
 //
 // Every pass has the same frame, written once below: it validates the run ranges before anything is launched, carves what the
 // call has on the device out of one block, launches, writes its output in chunks that fit a cap, and waits for the stream before
-// it returns (so one scratch block and one output block of the handle serve all of them).
+// it returns (so one scratch block and one output block of the handle serve all of them).  The adds of the accumulating objects open with
+// add_preface; the five passes that emit lists (cs, variants, maf, lift, chain) are callers of emit_lists, which owns the sequence from the
+// carve to the caller's buffers; the chunk plan itself is wfa_emit_plan.h, without a device header.
 #include <hip/hip_runtime.h>
 #include <sys/mman.h>
 
@@ -19,6 +22,7 @@
 #include <string>
 #include <vector>
 
+#include "wfa_emit_plan.h"
 #include "wfa_host_shared.h"
 #include "wfa_optband.h"
 
@@ -66,7 +70,7 @@ int grow_block(wfm_handle_t* h, T** blk, size_t* cap, size_t have, size_t need, 
   if (have) {
     hipError_t e = hipMemcpyAsync(nb, *blk, have * sizeof(T), hipMemcpyDeviceToDevice, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) { wfm_dfree(nb); h->err = std::string("wfm_sites: ") + hipGetErrorString(e); return WFM_E_HIP; }
+    if (e != hipSuccess) { wfm_dfree(nb); h->err = std::string(what) + ": " + hipGetErrorString(e); return WFM_E_HIP; }
   }
   if (*blk) wfm_dfree(*blk);
   *blk = nb;
@@ -97,21 +101,6 @@ template <class P>
 void fill_prob(P& c, const ProbMeta& m, const wfm_result_t& r, bool skip_without_runs) {
   fill_seq(c, m);
   c.skip = (m.score_only() || r.status != 0 || (skip_without_runs && r.n_runs == 0)) ? 1 : 0;
-}
-
-// The largest kb in (ka, n] whose cost(ka, kb) fits the cap, ka + 1 at least (one problem, tile or row larger than the cap is a chunk of its
-// own).  cost grows with kb.
-template <class Cost>
-size_t chunk_end(size_t ka, size_t n, unsigned long long cap, Cost cost) {
-  size_t lo = ka + 1, hi = n;
-  while (lo < hi) {
-    const size_t mid = lo + (hi - lo + 1) / 2;
-    if (cost(ka, mid) <= cap) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-inline size_t chunk_end(size_t ka, const std::vector<unsigned long long>& off, unsigned long long cap) {
-  return chunk_end(ka, off.size() - 1, cap, [&](size_t a, size_t b) { return off[b] - off[a]; });
 }
 
 // An object of a device: usable() refuses a handle of another device; a guard makes the object's device current while it is freed
@@ -180,10 +169,21 @@ struct PassTimer {
   bool on = env_debug() != 0;
   std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now(), t_lap = t0;
   explicit PassTimer(wfm_handle_t* h_) : h(h_) {}
-  hipError_t begin() { return on ? hipEventRecord(h->ev0, h->stream) : hipSuccess; }
+  bool pending = false;  // the events were recorded and not read since
+  hipError_t begin() { pending = on; return on ? hipEventRecord(h->ev0, h->stream) : hipSuccess; }
   hipError_t end() { return on ? hipEventRecord(h->ev1, h->stream) : hipSuccess; }
-  bool event_ms(float* ms) {  // (behind a wait for the stream)
-    if (!on) return false;
+  // launch() between the two events; the first error of the three
+  template <class Launch>
+  hipError_t timed(Launch launch) {
+    hipError_t e = begin();
+    if (e != hipSuccess) return e;
+    launch();
+    e = hipGetLastError();
+    return e != hipSuccess ? e : end();
+  }
+  bool event_ms(float* ms) {  // (behind a wait for the stream; false where nothing was recorded since the last reading)
+    if (!pending) return false;
+    pending = false;
     if (hipEventElapsedTime(ms, h->ev0, h->ev1) == hipSuccess) return true;
     (void)hipGetLastError();
     return false;
@@ -196,6 +196,115 @@ struct PassTimer {
     return ms;
   }
 };
+
+// How a device block reaches the caller's buffer: the chunks of the five emitting passes (emit_lists below), the exports and tables of the
+// accumulating objects and wfm_pav_matrix.
+constexpr size_t PIN_PIECE = (size_t)4 << 20;
+
+// the handle's two pinned pieces, allocated at first use; false: there are none, and a block goes down in one pageable copy
+bool pin_pieces(wfm_handle_t* h) {
+  for (int k = 0; k < 2; ++k)
+    if (!h->cspin[k] && hipHostMalloc((void**)&h->cspin[k], PIN_PIECE, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); h->cspin[k] = nullptr; return false; }
+  return true;
+}
+
+// bytes of the device block src to dst, finished on return.  Down in pieces through the two pinned buffers: piece j + 1 crosses PCIe while
+// piece j is copied to its place (one pageable hipMemcpy of a fresh block took 2 ms for 3.7 MB, and 18 - 28 ms every other call:
+// profiles/cs_tag.md)
+hipError_t copy_down(wfm_handle_t* h, bool pinned, char* dst, const uint8_t* src, size_t bytes) {
+  if (bytes == 0) return hipSuccess;
+  hipError_t e = hipSuccess;
+  const size_t pieces = pinned ? (bytes + PIN_PIECE - 1) / PIN_PIECE : 0;
+  auto piece_len = [&](size_t j) { return std::min<size_t>(PIN_PIECE, bytes - j * PIN_PIECE); };
+  if (!pinned) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream);
+  if (pinned) e = hipMemcpyAsync(h->cspin[0], src, piece_len(0), hipMemcpyDeviceToHost, h->stream);
+  for (size_t j = 0; j < pieces && e == hipSuccess; ++j) {
+    e = hipStreamSynchronize(h->stream);
+    if (e == hipSuccess && j + 1 < pieces)
+      e = hipMemcpyAsync(h->cspin[(j + 1) & 1], src + (j + 1) * PIN_PIECE, piece_len(j + 1), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) memcpy(dst + j * PIN_PIECE, h->cspin[j & 1], piece_len(j));
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  return e;
+}
+
+// ---- the emit frame: the passes that index their problems, learn from the totals how much each one emits, and write lists in chunks
+// (wfm_cs_strings, wfm_call_variants, wfm_maf_rows, wfm_lift_runs, wfm_chain_runs) ----
+
+inline int hip_rc(wfm_handle_t* h, const char* fn, hipError_t e) {
+  if (e == hipSuccess) return WFM_OK;
+  h->err = std::string(fn) + ": " + hipGetErrorString(e);
+  return WFM_E_HIP;
+}
+inline char* plain_alloc(size_t bytes) { return (char*)malloc(bytes); }
+struct FreeHost { void operator()(char* p) const { free(p); } };
+
+// One list a pass emits.  A chunk's part of it lies in the output block behind the streams before it, on `round` bytes of its own
+struct EmitStream {
+  const std::vector<unsigned long long>& off;  // n + 1 offsets in elements: the host's prefix sums, valid once offsets() has run
+  size_t elem;                                 // bytes an element
+  size_t round;                                // its part of the block is a whole number of these
+  char* (*alloc)(size_t);                      // the caller's buffer (released with free)
+  void** out;                                  // where the caller receives it ...
+  size_t* count;                               // ... and its number of elements
+};
+struct EmitSpec {
+  const char* fn;                              // the entry point, in the texts of HIP errors
+  const char *tag, *host_tag, *out_tag;        // what the out-of-memory texts name: the scratch block, the caller's buffers, the output block
+  DevBuf<uint64_t>&scratch, &outblk;
+  unsigned long long cap;                      // bytes of the streams a chunk may hold (one problem may exceed it alone)
+};
+struct EmitStats { size_t chunks = 0; float ms_index = 0, ms_write = 0; };  // (the times: device events, 0 without WFM_DEBUG or where a pass records none)
+
+// carve(cv): the pieces of the scratch block (those read 16 bytes at a time first: Carver aligns to 8).  index(down): the uploads, the index
+// launch, and down(dst, src, bytes) for what the host needs of it; the frame waits for that.  offsets(): the totals to prefix sums and per[],
+// the offsets' upload where there is output; below 0 an error, otherwise what the call returns.  A call without output ends there, its
+// outputs as the caller cleared them.  Otherwise: the caller's buffers, the plan of chunks under the cap, the output block sized once for
+// the widest, and per chunk write(ka, kb, d), which launches with stream s at d[s] and returns WFM_OK or its error, then every stream down
+// to its place.  The buffers are the caller's only when all of it succeeded.  A pass that records no events has no event times.
+template <size_t S, class Carve, class Index, class Offsets, class Write>
+int emit_lists(wfm_handle_t* h, PassTimer& tm, const EmitSpec& sp, size_t n, const EmitStream (&streams)[S], Carve carve, Index index, Offsets offsets,
+               Write write, EmitStats* st) {
+  Carver cv{sp.scratch, sp.tag};
+  carve(cv);
+  if (int rc = cv.commit(h)) return rc;
+  hipError_t e_down = hipSuccess;
+  auto down = [&](void* dst, const void* src, size_t bytes) { if (e_down == hipSuccess) e_down = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream); };
+  if (int rc = index(down)) return rc;
+  if (int rc = hip_rc(h, sp.fn, e_down)) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  (void)tm.event_ms(&st->ms_index);
+  const int ret = offsets();
+  if (ret < 0) return ret;
+  auto bytes_of = [&](size_t s, size_t ka, size_t kb) { return (size_t)(streams[s].off[kb] - streams[s].off[ka]) * streams[s].elem; };
+  auto part_of = [&](size_t s, size_t ka, size_t kb) { return (bytes_of(s, ka, kb) + streams[s].round - 1) / streams[s].round * streams[s].round; };
+  auto cost = [&](size_t ka, size_t kb) { unsigned long long c = 0; for (size_t s = 0; s < S; ++s) c += bytes_of(s, ka, kb); return c; };
+  auto block = [&](size_t ka, size_t kb) { unsigned long long b = 0; for (size_t s = 0; s < S; ++s) b += part_of(s, ka, kb); return b; };
+  if (cost(0, n) == 0) return ret;
+  std::unique_ptr<char, FreeHost> host[S];
+  bool got = true;
+  for (size_t s = 0; s < S; ++s) { host[s].reset(streams[s].alloc(bytes_of(s, 0, n))); got = got && host[s]; }
+  if (!got) { (void)hipStreamSynchronize(h->stream); h->err = std::string("out of host memory (") + sp.host_tag + ")"; return WFM_E_NOMEM; }
+  const EmitPlan plan = emit_plan(n, sp.cap, cost, block);
+  if (sp.outblk.ensure((size_t)(plan.widest + 7) / 8)) { h->err = std::string("out of device memory (") + sp.out_tag + ")"; return WFM_E_NOMEM; }
+  const bool pinned = pin_pieces(h);
+  for (const auto& c : plan.chunks) {
+    const size_t ka = c.first, kb = c.second;
+    uint8_t* d[S];
+    size_t at = 0;
+    for (size_t s = 0; s < S; ++s) { d[s] = (uint8_t*)sp.outblk.p + at; at += part_of(s, ka, kb); }
+    if (int rc = write(ka, kb, d)) return rc;
+    hipError_t e = hipSuccess;
+    for (size_t s = 0; s < S && e == hipSuccess; ++s)  // (the block is the next chunk's)
+      e = copy_down(h, pinned, host[s].get() + streams[s].off[ka] * streams[s].elem, d[s], bytes_of(s, ka, kb));
+    if (int rc = hip_rc(h, sp.fn, e)) return rc;
+    float ms = 0;
+    if (tm.event_ms(&ms)) st->ms_write += ms;
+  }
+  st->chunks = plan.chunks.size();
+  for (size_t s = 0; s < S; ++s) { *streams[s].count = (size_t)streams[s].off[n]; *streams[s].out = host[s].release(); }
+  return ret;
+}
 
 }  // namespace
 
@@ -343,42 +452,10 @@ int wfm_left_align_runs(wfm_handle_t* h, const wfm_seqset_t* s, wfm_result_t* re
   return spans;
 }
 
-// ---- how the output blocks of wfm_cs_strings and wfm_call_variants reach the caller's buffer ----
 namespace {
-constexpr size_t CS_PIN_PIECE = (size_t)4 << 20;
-
-// the handle's two pinned pieces, allocated at first use; false: there are none, and a block goes down in one pageable copy
-bool cs_pin_pieces(wfm_handle_t* h) {
-  for (int k = 0; k < 2; ++k)
-    if (!h->cspin[k] && hipHostMalloc((void**)&h->cspin[k], CS_PIN_PIECE, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); h->cspin[k] = nullptr; return false; }
-  return true;
-}
-
-// bytes of the device block src to dst, finished on return.  Down in pieces through the two pinned buffers: piece j + 1 crosses PCIe while
-// piece j is copied to its place (one pageable hipMemcpy of a fresh block took 2 ms for 3.7 MB, and 18 - 28 ms every other call:
-// profiles/cs_tag.md)
-hipError_t cs_copy_down(wfm_handle_t* h, bool pinned, char* dst, const uint8_t* src, size_t bytes) {
-  if (bytes == 0) return hipSuccess;
-  hipError_t e = hipSuccess;
-  const size_t pieces = pinned ? (bytes + CS_PIN_PIECE - 1) / CS_PIN_PIECE : 0;
-  auto piece_len = [&](size_t j) { return std::min<size_t>(CS_PIN_PIECE, bytes - j * CS_PIN_PIECE); };
-  if (!pinned) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream);
-  if (pinned) e = hipMemcpyAsync(h->cspin[0], src, piece_len(0), hipMemcpyDeviceToHost, h->stream);
-  for (size_t j = 0; j < pieces && e == hipSuccess; ++j) {
-    e = hipStreamSynchronize(h->stream);
-    if (e == hipSuccess && j + 1 < pieces)
-      e = hipMemcpyAsync(h->cspin[(j + 1) & 1], src + (j + 1) * CS_PIN_PIECE, piece_len(j + 1), hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) memcpy(dst + j * CS_PIN_PIECE, h->cspin[j & 1], piece_len(j));
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  return e;
-}
-}  // namespace
-
-namespace {
-// the problems as wfa_cs.hip and wfa_variants.hip see them; the run ranges are validated here, before anything is launched.  The run records
-// lie in problem order whatever order the runs come in
-int cs_problems(wfm_handle_t* h, const wfm_seqset_t* s, const wfm_result_t* res, size_t n_runs_total, std::vector<CsProb>& probs, uint64_t* rec_total) {
+// the problems as wfa_cs.hip, wfa_variants.hip and wfa_maf.hip see them; the run ranges are validated here, before anything is launched.  The
+// run records lie in problem order whatever order the runs come in, `slack` slots behind each problem's (wfa_maf.hip: one, for its totals)
+int cs_problems(wfm_handle_t* h, const wfm_seqset_t* s, const wfm_result_t* res, size_t n_runs_total, unsigned slack, std::vector<CsProb>& probs, uint64_t* rec_total) {
   const size_t n = s->meta.size();
   probs.resize(n);
   for (size_t i = 0; i < n; ++i) {
@@ -389,7 +466,7 @@ int cs_problems(wfm_handle_t* h, const wfm_seqset_t* s, const wfm_result_t* res,
     if (!runs_inside(res[i].ops_off, res[i].n_runs, n_runs_total)) return runs_leave(h, i);
     c.run_off = res[i].ops_off; c.n_runs = res[i].n_runs;
     c.rec_off = *rec_total;
-    *rec_total += c.n_runs;
+    *rec_total += (uint64_t)c.n_runs + slack;
   }
   return WFM_OK;
 }
@@ -410,72 +487,49 @@ int wfm_cs_strings(wfm_handle_t* h, const wfm_seqset_t* s, const wfm_result_t* r
   HIPCHK(h, hipSetDevice(h->device));
   std::vector<CsProb> probs;
   uint64_t rec_total = 0;
-  if (int rc = cs_problems(h, s, res, n_runs_total, probs, &rec_total)) return rc;
+  if (int rc = cs_problems(h, s, res, n_runs_total, 0, probs, &rec_total)) return rc;
   // one block: [records] 16 bytes per run, [offsets] n + 1 and [totals] n of 8 bytes, [problems], [runs], [flags]
   const size_t nr = n_runs_total;
   uint4* d_recs;
   unsigned long long *d_goff, *d_tot;
   CsProb* d_probs;
   uint32_t *d_runs, *d_flags;
-  Carver cv{h->scratch, "cs"};
-  cv.piece(&d_recs, (size_t)rec_total); cv.piece(&d_goff, n + 1); cv.piece(&d_tot, n); cv.piece(&d_probs, n); cv.piece(&d_runs, nr); cv.piece(&d_flags, n);
-  if (int rc = cv.commit(h)) return rc;
-  if (nr) HIPCHK(h, hipMemcpyAsync(d_runs, runs, nr * 4, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(d_probs, probs.data(), n * sizeof(CsProb), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, tm.begin());
-  launch_cs_index(d_runs, d_probs, (int)n, form, d_recs, d_tot, d_flags, h->stream);
-  HIPCHK(h, hipGetLastError());
-  HIPCHK(h, tm.end());
-  // the problems' totals, once: the host sizes the output and takes their prefix sum
   std::vector<unsigned long long> goff(n + 1);
   std::vector<uint32_t> flags(n);
-  HIPCHK(h, hipMemcpyAsync(goff.data() + 1, d_tot, n * 8, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(flags.data(), d_flags, n * 4, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  float ms_index = 0, ms_write = 0, ms = 0;
-  (void)tm.event_ms(&ms_index);
-  goff[0] = 0;
   int spans = 0;
-  for (size_t i = 0; i < n; ++i) {
-    per[i].flags = flags[i]; per[i].n_runs = probs[i].n_runs;
-    per[i].off = goff[i]; per[i].len = goff[i + 1];
-    goff[i + 1] += goff[i];
-    spans += (flags[i] & WFM_CS_SPANS) != 0;
-  }
-  const unsigned long long total = goff[n];
-  if (total == 0) return spans;
-  HIPCHK(h, hipMemcpyAsync(d_goff, goff.data(), (n + 1) * 8, hipMemcpyHostToDevice, h->stream));
-  char* host = (char*)malloc((size_t)total);
-  if (!host) { (void)hipStreamSynchronize(h->stream); h->err = "out of host memory (cs)"; return WFM_E_NOMEM; }
   // chunks of problems whose strings fit the output block (a problem larger than that is a chunk of its own)
-  const unsigned long long cap = (unsigned long long)std::max(1, env_num("WFM_CS_OUT_MB", 256)) << 20;
-  const bool pinned = cs_pin_pieces(h);
-  size_t chunks = 0;
-  for (size_t ka = 0, kb; ka < n; ka = kb) {
-    kb = chunk_end(ka, goff, cap);
-    const unsigned long long bytes = goff[kb] - goff[ka];
-    if (bytes == 0) continue;
-    const size_t block = (size_t)((bytes + WFM_CS_SLICE - 1) / WFM_CS_SLICE) * WFM_CS_SLICE;
-    int rc = WFM_OK;
-    if (h->outblk.ensure(block / 8)) { h->err = "out of device memory (cs output)"; rc = WFM_E_NOMEM; }
-    if (rc == WFM_OK) {
-      (void)tm.begin();
-      launch_cs_write(s->d_seq, d_probs, d_recs, d_goff, (uint32_t)ka, (uint32_t)kb, bytes, form, (uint8_t*)h->outblk.p, h->stream);
-      hipError_t e = hipGetLastError();
-      (void)tm.end();
-      if (e == hipSuccess) e = cs_copy_down(h, pinned, host + goff[ka], (const uint8_t*)h->outblk.p, (size_t)bytes);  // (the block is the next chunk's)
-      if (e != hipSuccess) { h->err = std::string("wfm_cs_strings: ") + hipGetErrorString(e); rc = WFM_E_HIP; }
-    }
-    if (rc != WFM_OK) { free(host); return rc; }
-    if (tm.event_ms(&ms)) ms_write += ms;
-    ++chunks;
-  }
-  *out = host;
-  *out_bytes = (size_t)total;
-  if (tm.on)
+  const EmitSpec sp{"wfm_cs_strings", "cs", "cs", "cs output", h->scratch, h->outblk, (unsigned long long)std::max(1, env_num("WFM_CS_OUT_MB", 256)) << 20};
+  const EmitStream streams[] = {{goff, 1, WFM_CS_SLICE, plain_alloc, (void**)out, out_bytes}};
+  EmitStats st;
+  const int rc = emit_lists(
+      h, tm, sp, n, streams,
+      [&](Carver& cv) { cv.piece(&d_recs, (size_t)rec_total); cv.piece(&d_goff, n + 1); cv.piece(&d_tot, n); cv.piece(&d_probs, n); cv.piece(&d_runs, nr); cv.piece(&d_flags, n); },
+      [&](auto down) {
+        if (nr) HIPCHK(h, hipMemcpyAsync(d_runs, runs, nr * 4, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(d_probs, probs.data(), n * sizeof(CsProb), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, tm.timed([&] { launch_cs_index(d_runs, d_probs, (int)n, form, d_recs, d_tot, d_flags, h->stream); }));
+        down(goff.data() + 1, d_tot, n * 8); down(flags.data(), d_flags, n * 4);
+        return WFM_OK;
+      },
+      [&]() {  // the problems' totals, once: the host takes their prefix sum
+        goff[0] = 0;
+        for (size_t i = 0; i < n; ++i) {
+          per[i].flags = flags[i]; per[i].n_runs = probs[i].n_runs;
+          per[i].off = goff[i]; per[i].len = goff[i + 1];
+          goff[i + 1] += goff[i];
+          spans += (flags[i] & WFM_CS_SPANS) != 0;
+        }
+        if (goff[n]) HIPCHK(h, hipMemcpyAsync(d_goff, goff.data(), (n + 1) * 8, hipMemcpyHostToDevice, h->stream));
+        return spans;
+      },
+      [&](size_t ka, size_t kb, uint8_t* const* d) {
+        return hip_rc(h, sp.fn, tm.timed([&] { launch_cs_write(s->d_seq, d_probs, d_recs, d_goff, (uint32_t)ka, (uint32_t)kb, goff[kb] - goff[ka], form, d[0], h->stream); }));
+      },
+      &st);
+  if (tm.on && st.chunks)
     fprintf(stderr, "[wfm] cs (%s): %zu problems, %zu runs, %llu bytes in %zu chunks, index %.3f ms, write %.3f ms (device events), the call %.3f ms (host clock)\n",
-            form == WFM_CS_LONG ? "long" : "short", n, (size_t)rec_total, total, chunks, ms_index, ms_write, tm.host_ms());
-  return spans;
+            form == WFM_CS_LONG ? "long" : "short", n, (size_t)rec_total, goff[n], st.chunks, st.ms_index, st.ms_write, tm.host_ms());
+  return rc;
 }
 
 void wfm_free_cs(char* p) { free(p); }
@@ -494,7 +548,7 @@ int wfm_call_variants(wfm_handle_t* h, const wfm_seqset_t* s, const wfm_result_t
   HIPCHK(h, hipSetDevice(h->device));
   std::vector<CsProb> probs;
   uint64_t rec_total = 0;
-  if (int rc = cs_problems(h, s, res, n_runs_total, probs, &rec_total)) return rc;
+  if (int rc = cs_problems(h, s, res, n_runs_total, 0, probs, &rec_total)) return rc;
   // one block: [run records] 16 bytes per run, [offsets of the alleles] and [of the records] n + 1 each, [totals of both] n each of 8 bytes,
   // [problems], [runs], [record prefixes] one word per run, [flags], [end gaps]
   const size_t nr = n_runs_total;
@@ -502,77 +556,52 @@ int wfm_call_variants(wfm_handle_t* h, const wfm_seqset_t* s, const wfm_result_t
   unsigned long long *d_goff, *d_voff, *d_totb, *d_totr;
   CsProb* d_probs;
   uint32_t *d_runs, *d_rpre, *d_flags, *d_ends;
-  Carver cv{h->scratch, "variants"};
-  cv.piece(&d_recs, (size_t)rec_total); cv.piece(&d_goff, n + 1); cv.piece(&d_voff, n + 1); cv.piece(&d_totb, n); cv.piece(&d_totr, n);
-  cv.piece(&d_probs, n); cv.piece(&d_runs, nr); cv.piece(&d_rpre, (size_t)rec_total); cv.piece(&d_flags, n); cv.piece(&d_ends, n);
-  if (int rc = cv.commit(h)) return rc;
-  if (nr) HIPCHK(h, hipMemcpyAsync(d_runs, runs, nr * 4, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(d_probs, probs.data(), n * sizeof(CsProb), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, tm.begin());
-  launch_var_index(d_runs, d_probs, (int)n, d_recs, d_rpre, d_totb, d_totr, d_ends, d_flags, h->stream);
-  HIPCHK(h, hipGetLastError());
-  HIPCHK(h, tm.end());
-  // the problems' totals, once: the host sizes the outputs and takes the two prefix sums
   std::vector<unsigned long long> goff(n + 1), voff(n + 1);
   std::vector<uint32_t> flags(n), ends(n);
-  HIPCHK(h, hipMemcpyAsync(goff.data() + 1, d_totb, n * 8, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(voff.data() + 1, d_totr, n * 8, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(flags.data(), d_flags, n * 4, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(ends.data(), d_ends, n * 4, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  float ms_index = 0, ms_write = 0, ms = 0;
-  (void)tm.event_ms(&ms_index);
-  goff[0] = 0; voff[0] = 0;
   int spans = 0;
-  for (size_t i = 0; i < n; ++i) {
-    per[i].flags = flags[i]; per[i].n_runs = probs[i].n_runs;
-    per[i].first = voff[i]; per[i].count = voff[i + 1];
-    per[i].end_gaps = ends[i]; per[i].pad_ = 0;
-    goff[i + 1] += goff[i]; voff[i + 1] += voff[i];
-    spans += (flags[i] & WFM_VAR_SPANS) != 0;
-  }
-  const unsigned long long total = goff[n], total_vars = voff[n];
-  if (total == 0) return spans;  // (a record has allele bytes: no bytes, no records)
-  HIPCHK(h, hipMemcpyAsync(d_goff, goff.data(), (n + 1) * 8, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(d_voff, voff.data(), (n + 1) * 8, hipMemcpyHostToDevice, h->stream));
-  char* host = (char*)malloc((size_t)total);
-  wfm_variant_t* host_vars = (wfm_variant_t*)malloc((size_t)total_vars * sizeof(wfm_variant_t));
-  if (!host || !host_vars) { (void)hipStreamSynchronize(h->stream); free(host); free(host_vars); h->err = "out of host memory (variants)"; return WFM_E_NOMEM; }
-  // chunks of problems whose records and alleles fit the output block (a problem larger than that is a chunk of its own)
-  const unsigned long long cap = (unsigned long long)std::max(1, env_num("WFM_VAR_OUT_MB", 256)) << 20;
-  auto cost = [&](size_t ka, size_t kb) { return (goff[kb] - goff[ka]) + (voff[kb] - voff[ka]) * sizeof(wfm_variant_t); };
-  const bool pinned = cs_pin_pieces(h);
-  size_t chunks = 0;
-  for (size_t ka = 0, kb; ka < n; ka = kb) {
-    kb = chunk_end(ka, n, cap, cost);
-    const unsigned long long bytes = goff[kb] - goff[ka];
-    if (bytes == 0) continue;
-    // the block: the chunk's records, then its alleles in whole slices
-    const size_t rec_bytes = (size_t)(voff[kb] - voff[ka]) * sizeof(wfm_variant_t);
-    const size_t block = rec_bytes + (size_t)((bytes + WFM_VAR_SLICE - 1) / WFM_VAR_SLICE) * WFM_VAR_SLICE;
-    int rc = WFM_OK;
-    if (h->outblk.ensure(block / 8)) { h->err = "out of device memory (variants output)"; rc = WFM_E_NOMEM; }
-    if (rc == WFM_OK) {
-      uint8_t* d_vars = (uint8_t*)h->outblk.p;
-      uint8_t* d_all = d_vars + rec_bytes;
-      (void)tm.begin();
-      launch_var_write(s->d_seq, d_probs, d_recs, d_rpre, d_goff, d_voff, (uint32_t)ka, (uint32_t)kb, bytes, d_all, d_vars, h->stream);
-      hipError_t e = hipGetLastError();
-      (void)tm.end();
-      if (e == hipSuccess) e = cs_copy_down(h, pinned, (char*)(host_vars + voff[ka]), d_vars, rec_bytes);
-      if (e == hipSuccess) e = cs_copy_down(h, pinned, host + goff[ka], d_all, (size_t)bytes);  // (the block is the next chunk's)
-      if (e != hipSuccess) { h->err = std::string("wfm_call_variants: ") + hipGetErrorString(e); rc = WFM_E_HIP; }
-    }
-    if (rc != WFM_OK) { free(host); free(host_vars); return rc; }
-    if (tm.event_ms(&ms)) ms_write += ms;
-    ++chunks;
-  }
-  *vars = host_vars; *n_vars = (size_t)total_vars;
-  *alleles = host; *allele_bytes = (size_t)total;
-  if (tm.on)
+  // chunks of problems whose records and alleles fit the output block (a problem larger than that is a chunk of its own); the block: the
+  // chunk's records, then its alleles in whole slices
+  const EmitSpec sp{"wfm_call_variants", "variants", "variants", "variants output", h->scratch, h->outblk, (unsigned long long)std::max(1, env_num("WFM_VAR_OUT_MB", 256)) << 20};
+  const EmitStream streams[] = {{voff, sizeof(wfm_variant_t), 1, plain_alloc, (void**)vars, n_vars}, {goff, 1, WFM_VAR_SLICE, plain_alloc, (void**)alleles, allele_bytes}};
+  EmitStats st;
+  const int rc = emit_lists(
+      h, tm, sp, n, streams,
+      [&](Carver& cv) {
+        cv.piece(&d_recs, (size_t)rec_total); cv.piece(&d_goff, n + 1); cv.piece(&d_voff, n + 1); cv.piece(&d_totb, n); cv.piece(&d_totr, n);
+        cv.piece(&d_probs, n); cv.piece(&d_runs, nr); cv.piece(&d_rpre, (size_t)rec_total); cv.piece(&d_flags, n); cv.piece(&d_ends, n);
+      },
+      [&](auto down) {
+        if (nr) HIPCHK(h, hipMemcpyAsync(d_runs, runs, nr * 4, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(d_probs, probs.data(), n * sizeof(CsProb), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, tm.timed([&] { launch_var_index(d_runs, d_probs, (int)n, d_recs, d_rpre, d_totb, d_totr, d_ends, d_flags, h->stream); }));
+        down(goff.data() + 1, d_totb, n * 8); down(voff.data() + 1, d_totr, n * 8); down(flags.data(), d_flags, n * 4); down(ends.data(), d_ends, n * 4);
+        return WFM_OK;
+      },
+      [&]() {  // the problems' totals, once: the host takes the two prefix sums
+        goff[0] = 0; voff[0] = 0;
+        for (size_t i = 0; i < n; ++i) {
+          per[i].flags = flags[i]; per[i].n_runs = probs[i].n_runs;
+          per[i].first = voff[i]; per[i].count = voff[i + 1];
+          per[i].end_gaps = ends[i]; per[i].pad_ = 0;
+          goff[i + 1] += goff[i]; voff[i + 1] += voff[i];
+          spans += (flags[i] & WFM_VAR_SPANS) != 0;
+        }
+        if (goff[n]) {  // (a record has allele bytes: no bytes, no records)
+          HIPCHK(h, hipMemcpyAsync(d_goff, goff.data(), (n + 1) * 8, hipMemcpyHostToDevice, h->stream));
+          HIPCHK(h, hipMemcpyAsync(d_voff, voff.data(), (n + 1) * 8, hipMemcpyHostToDevice, h->stream));
+        }
+        return spans;
+      },
+      [&](size_t ka, size_t kb, uint8_t* const* d) {
+        return hip_rc(h, sp.fn, tm.timed([&] {
+          launch_var_write(s->d_seq, d_probs, d_recs, d_rpre, d_goff, d_voff, (uint32_t)ka, (uint32_t)kb, goff[kb] - goff[ka], d[1], d[0], h->stream);
+        }));
+      },
+      &st);
+  if (tm.on && st.chunks)
     fprintf(stderr, "[wfm] variants: %zu problems, %zu runs, %llu records, %llu allele bytes in %zu chunks, index %.3f ms, write %.3f ms (device events), the call %.3f ms (host clock)\n",
-            n, (size_t)rec_total, total_vars, total, chunks, ms_index, ms_write, tm.host_ms());
-  return spans;
+            n, (size_t)rec_total, voff[n], goff[n], st.chunks, st.ms_index, st.ms_write, tm.host_ms());
+  return rc;
 }
 
 void wfm_free_variants(wfm_variant_t* vars, char* alleles) { free(vars); free(alleles); }
@@ -606,21 +635,11 @@ int wfm_maf_rows(wfm_handle_t* h, const wfm_seqset_t* s, const wfm_result_t* res
   if (!res || !per) return WFM_E_ARG;
   if (n > (size_t)INT32_MAX || n_runs_total > ((size_t)1 << 31)) { h->err = "wfm_maf_rows: too many problems or runs for one call"; return WFM_E_ARG; }
   HIPCHK(h, hipSetDevice(h->device));
-  // the problems as wfa_maf.hip sees them: cs_problems' with one more slot per problem, for its totals
-  std::vector<CsProb> probs(n);
+  std::vector<CsProb> probs;
   uint64_t rec_total = 0;
+  if (int rc = cs_problems(h, s, res, n_runs_total, 1, probs, &rec_total)) return rc;
   size_t run_total = 0;
-  for (size_t i = 0; i < n; ++i) {
-    CsProb& c = probs[i];
-    memset(&c, 0, sizeof(c));
-    fill_prob(c, s->meta[i], res[i], true);
-    if (c.skip) continue;
-    if (!runs_inside(res[i].ops_off, res[i].n_runs, n_runs_total)) return runs_leave(h, i);
-    c.run_off = res[i].ops_off; c.n_runs = res[i].n_runs;
-    c.rec_off = rec_total;
-    rec_total += (uint64_t)c.n_runs + 1;
-    run_total += c.n_runs;
-  }
+  for (const CsProb& c : probs) run_total += c.n_runs;
   // one block: [run records] 16 and [prefixes] 8 bytes per slot, [offsets of the rows] and [of the blocks] n + 1 each, [blocks] and
   // [columns] n each of 8 bytes, [problems], [runs], [flags]
   const size_t nr = n_runs_total;
@@ -629,77 +648,54 @@ int wfm_maf_rows(wfm_handle_t* h, const wfm_seqset_t* s, const wfm_result_t* res
   unsigned long long *d_goff, *d_boff, *d_nblk, *d_ncols;
   CsProb* d_probs;
   uint32_t *d_runs, *d_flags;
-  Carver cv{h->scratch, "maf"};
-  cv.piece(&d_recs, (size_t)rec_total); cv.piece(&d_pre, (size_t)rec_total); cv.piece(&d_goff, n + 1); cv.piece(&d_boff, n + 1);
-  cv.piece(&d_nblk, n); cv.piece(&d_ncols, n); cv.piece(&d_probs, n); cv.piece(&d_runs, nr); cv.piece(&d_flags, n);
-  if (int rc = cv.commit(h)) return rc;
-  if (nr) HIPCHK(h, hipMemcpyAsync(d_runs, runs, nr * 4, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(d_probs, probs.data(), n * sizeof(CsProb), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, tm.begin());
-  launch_maf_index(d_runs, d_probs, (int)n, split, d_recs, d_pre, d_nblk, d_ncols, d_flags, h->stream);
-  HIPCHK(h, hipGetLastError());
-  HIPCHK(h, tm.end());
-  // the problems' blocks and columns, once: the host sizes the outputs and takes the two prefix sums
   std::vector<unsigned long long> goff(n + 1), boff(n + 1);
   std::vector<uint32_t> flags(n);
-  HIPCHK(h, hipMemcpyAsync(goff.data() + 1, d_ncols, n * 8, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(boff.data() + 1, d_nblk, n * 8, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(flags.data(), d_flags, n * 4, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  float ms_index = 0, ms_write = 0, ms = 0;
-  (void)tm.event_ms(&ms_index);
-  goff[0] = 0; boff[0] = 0;
   int spans = 0;
-  for (size_t i = 0; i < n; ++i) {
-    per[i].flags = flags[i]; per[i].n_runs = probs[i].n_runs;
-    per[i].first = boff[i]; per[i].count = boff[i + 1];
-    goff[i + 1] = goff[i] + 2 * goff[i + 1];  // (two rows a column)
-    boff[i + 1] += boff[i];
-    spans += (flags[i] & WFM_MAF_SPANS) != 0;
-  }
-  const unsigned long long total = goff[n], total_blocks = boff[n];
-  if (total_blocks == 0) return spans;  // (a block has columns: no blocks, no bytes)
-  HIPCHK(h, hipMemcpyAsync(d_goff, goff.data(), (n + 1) * 8, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(d_boff, boff.data(), (n + 1) * 8, hipMemcpyHostToDevice, h->stream));
-  char* host = maf_rows_alloc((size_t)total);
-  wfm_maf_block_t* host_blocks = (wfm_maf_block_t*)malloc((size_t)total_blocks * sizeof(wfm_maf_block_t));
-  if (!host || !host_blocks) { (void)hipStreamSynchronize(h->stream); free(host); free(host_blocks); h->err = "out of host memory (maf)"; return WFM_E_NOMEM; }
-  // chunks of whole problems whose blocks and rows fit the output block (a problem larger than that is a chunk of its own)
-  const unsigned long long cap = cap_units("WFM_MAF_OUT_MB", 1, 1);
-  auto cost = [&](size_t ka, size_t kb) { return (goff[kb] - goff[ka]) + (boff[kb] - boff[ka]) * sizeof(wfm_maf_block_t); };
-  const bool pinned = cs_pin_pieces(h);
-  size_t chunks = 0;
-  for (size_t ka = 0, kb; ka < n; ka = kb) {
-    kb = chunk_end(ka, n, cap, cost);
-    const unsigned long long row_bytes = goff[kb] - goff[ka], nb = boff[kb] - boff[ka];
-    if (nb == 0) continue;
-    // the block: the chunk's block table (to a multiple of 16 bytes), then its rows in whole slices
-    const size_t tbl_bytes = ((size_t)nb * sizeof(wfm_maf_block_t) + 15) / 16 * 16;
-    const size_t block = tbl_bytes + (size_t)((row_bytes + WFM_MAF_SLICE - 1) / WFM_MAF_SLICE) * WFM_MAF_SLICE;
-    int rc = WFM_OK;
-    if (nb > 0xffffffffull) { h->err = "wfm_maf_rows: too many blocks in one chunk"; rc = WFM_E_ARG; }
-    if (rc == WFM_OK && h->outblk.ensure(block / 8)) { h->err = "out of device memory (maf output)"; rc = WFM_E_NOMEM; }
-    if (rc == WFM_OK) {
-      uint8_t* d_tbl = (uint8_t*)h->outblk.p;
-      uint8_t* d_rows = d_tbl + tbl_bytes;
-      (void)tm.begin();
-      launch_maf_write(s->d_seq, d_probs, d_recs, d_pre, d_nblk, d_goff, d_boff, (uint32_t)ka, (uint32_t)kb, row_bytes, d_tbl, (uint32_t)nb, d_rows, h->stream);
-      hipError_t e = hipGetLastError();
-      (void)tm.end();
-      if (e == hipSuccess) e = cs_copy_down(h, pinned, (char*)(host_blocks + boff[ka]), d_tbl, (size_t)nb * sizeof(wfm_maf_block_t));
-      if (e == hipSuccess) e = cs_copy_down(h, pinned, host + goff[ka], d_rows, (size_t)row_bytes);  // (the block is the next chunk's)
-      if (e != hipSuccess) { h->err = std::string("wfm_maf_rows: ") + hipGetErrorString(e); rc = WFM_E_HIP; }
-    }
-    if (rc != WFM_OK) { free(host); free(host_blocks); return rc; }
-    if (tm.event_ms(&ms)) ms_write += ms;
-    ++chunks;
-  }
-  *blocks = host_blocks; *n_blocks = (size_t)total_blocks;
-  *rows = host; *bytes = (size_t)total;
-  if (tm.on)
+  // chunks of whole problems whose blocks and rows fit the output block (a problem larger than that is a chunk of its own); the block: the
+  // chunk's block table (to a multiple of 16 bytes), then its rows in whole slices
+  const EmitSpec sp{"wfm_maf_rows", "maf", "maf", "maf output", h->scratch, h->outblk, cap_units("WFM_MAF_OUT_MB", 1, 1)};
+  const EmitStream streams[] = {{boff, sizeof(wfm_maf_block_t), 16, plain_alloc, (void**)blocks, n_blocks}, {goff, 1, WFM_MAF_SLICE, maf_rows_alloc, (void**)rows, bytes}};
+  EmitStats st;
+  const int rc = emit_lists(
+      h, tm, sp, n, streams,
+      [&](Carver& cv) {
+        cv.piece(&d_recs, (size_t)rec_total); cv.piece(&d_pre, (size_t)rec_total); cv.piece(&d_goff, n + 1); cv.piece(&d_boff, n + 1);
+        cv.piece(&d_nblk, n); cv.piece(&d_ncols, n); cv.piece(&d_probs, n); cv.piece(&d_runs, nr); cv.piece(&d_flags, n);
+      },
+      [&](auto down) {
+        if (nr) HIPCHK(h, hipMemcpyAsync(d_runs, runs, nr * 4, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(d_probs, probs.data(), n * sizeof(CsProb), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, tm.timed([&] { launch_maf_index(d_runs, d_probs, (int)n, split, d_recs, d_pre, d_nblk, d_ncols, d_flags, h->stream); }));
+        down(goff.data() + 1, d_ncols, n * 8); down(boff.data() + 1, d_nblk, n * 8); down(flags.data(), d_flags, n * 4);
+        return WFM_OK;
+      },
+      [&]() {  // the problems' blocks and columns, once: the host takes the two prefix sums
+        goff[0] = 0; boff[0] = 0;
+        for (size_t i = 0; i < n; ++i) {
+          per[i].flags = flags[i]; per[i].n_runs = probs[i].n_runs;
+          per[i].first = boff[i]; per[i].count = boff[i + 1];
+          goff[i + 1] = goff[i] + 2 * goff[i + 1];  // (two rows a column)
+          boff[i + 1] += boff[i];
+          spans += (flags[i] & WFM_MAF_SPANS) != 0;
+        }
+        if (boff[n]) {  // (a block has columns: no blocks, no bytes)
+          HIPCHK(h, hipMemcpyAsync(d_goff, goff.data(), (n + 1) * 8, hipMemcpyHostToDevice, h->stream));
+          HIPCHK(h, hipMemcpyAsync(d_boff, boff.data(), (n + 1) * 8, hipMemcpyHostToDevice, h->stream));
+        }
+        return spans;
+      },
+      [&](size_t ka, size_t kb, uint8_t* const* d) {
+        const unsigned long long nb = boff[kb] - boff[ka];
+        if (nb > 0xffffffffull) { h->err = "wfm_maf_rows: too many blocks in one chunk"; return (int)WFM_E_ARG; }
+        return hip_rc(h, sp.fn, tm.timed([&] {
+          launch_maf_write(s->d_seq, d_probs, d_recs, d_pre, d_nblk, d_goff, d_boff, (uint32_t)ka, (uint32_t)kb, goff[kb] - goff[ka], d[0], (uint32_t)nb, d[1], h->stream);
+        }));
+      },
+      &st);
+  if (tm.on && st.chunks)
     fprintf(stderr, "[wfm] maf (split %u): %zu problems, %zu runs, %llu blocks, %llu bytes in %zu chunks, index %.3f ms, blocks + write %.3f ms (device events), the call %.3f ms (host clock)\n",
-            split, n, run_total, total_blocks, total, chunks, ms_index, ms_write, tm.host_ms());
-  return spans;
+            split, n, run_total, boff[n], goff[n], st.chunks, st.ms_index, st.ms_write, tm.host_ms());
+  return rc;
 }
 
 void wfm_free_maf(wfm_maf_block_t* blocks, char* rows) { free(blocks); free(rows); }
@@ -829,9 +825,9 @@ int wfm_coverage_export(wfm_handle_t* h, wfm_coverage_t* cov, wfm_cov_entry_t** 
   if (total == 0) return WFM_OK;
   char* host = (char*)malloc((size_t)total * sizeof(wfm_cov_entry_t));
   if (!host) { h->err = "out of host memory (coverage list)"; return WFM_E_NOMEM; }
-  const bool pinned = cs_pin_pieces(h);
+  const bool pinned = pin_pieces(h);
   const int rc = cov_chunks(h, cov, off, 2, [&](const uint8_t* d_ent, unsigned long long first, unsigned long long m, bool) {
-    const hipError_t e = cs_copy_down(h, pinned, host + first * sizeof(wfm_cov_entry_t), d_ent, (size_t)m * sizeof(wfm_cov_entry_t));  // (the block is the next chunk's)
+    const hipError_t e = copy_down(h, pinned, host + first * sizeof(wfm_cov_entry_t), d_ent, (size_t)m * sizeof(wfm_cov_entry_t));  // (the block is the next chunk's)
     if (e != hipSuccess) { h->err = std::string("wfm_coverage_export: ") + hipGetErrorString(e); return (int)WFM_E_HIP; }
     return (int)WFM_OK;
   });
@@ -879,7 +875,7 @@ int wfm_coverage_intervals(wfm_handle_t* h, wfm_coverage_t* cov, wfm_cov_interva
   host[0].start = 0; host[0].depth = 0; host[0].pad_ = 0;
   hipError_t e0 = hipMemsetAsync(cov->cells, 0, 4 * 8, h->stream);
   if (e0 != hipSuccess) { free(host); h->err = std::string("wfm_coverage_intervals: ") + hipGetErrorString(e0); return WFM_E_HIP; }
-  const bool pinned = cs_pin_pieces(h);
+  const bool pinned = pin_pieces(h);
   unsigned long long prev_pos = 0;
   size_t chunks = 0;
   int rc = cov_chunks(h, cov, off, 4, [&](const uint8_t* d_ent, unsigned long long first, unsigned long long m, bool last) {
@@ -887,7 +883,7 @@ int wfm_coverage_intervals(wfm_handle_t* h, wfm_coverage_t* cov, wfm_cov_interva
     unsigned long long* d_sums = (unsigned long long*)(cov->work.p + 4 * (size_t)m);
     launch_cov_intervals(d_ent, m, d_sums, cov->cells, prev_pos, cov->n_bases, last ? 1 : 0, d_iv, cov->cells + 1, h->stream);
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = cs_copy_down(h, pinned, (char*)(host + 1 + first), d_iv, (size_t)m * sizeof(wfm_cov_interval_t));
+    if (e == hipSuccess) e = copy_down(h, pinned, (char*)(host + 1 + first), d_iv, (size_t)m * sizeof(wfm_cov_interval_t));
     if (e != hipSuccess) { h->err = std::string("wfm_coverage_intervals: ") + hipGetErrorString(e); return (int)WFM_E_HIP; }
     prev_pos = host[first + m].start;
     ++chunks;
@@ -991,46 +987,38 @@ int wfm_lift_runs(wfm_handle_t* h, const wfm_liftset_t* s, const wfm_cov_prob_t*
   LiftWin* d_win;
   unsigned long long* d_off;
   uint32_t* d_runs;
-  Carver cv{s->work, "lift"};
-  cv.piece(&d_pre, (size_t)n_pre); cv.piece(&d_probs, n); cv.piece(&d_win, n); cv.piece(&d_off, n + 1); cv.piece(&d_runs, n_runs_total);
-  if (int rc = cv.commit(h)) return rc;
-  HIPCHK(h, hipMemcpyAsync(d_probs, lp.data(), n * sizeof(LiftProb), hipMemcpyHostToDevice, h->stream));
-  if (n_runs_total) HIPCHK(h, hipMemcpyAsync(d_runs, runs, n_runs_total * 4, hipMemcpyHostToDevice, h->stream));
-  launch_lift_index(d_runs, d_probs, (int)n, s->iv, s->pm, s->n, s->n_bases, d_pre, d_win, d_off, h->stream);
-  HIPCHK(h, hipGetLastError());
   std::vector<LiftWin> win(n);
   std::vector<unsigned long long> off(n + 1);
-  HIPCHK(h, hipMemcpyAsync(win.data(), d_win, n * sizeof(LiftWin), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(off.data(), d_off, (n + 1) * 8, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  const double ms_index = tm.lap();
-  for (size_t i = 0; i < n; ++i) per[i] = wfm_liftcall_t{win[i].flags, probs[i].n_runs, off[i], win[i].count};
-  const unsigned long long total = off[n];
-  if (total == 0) return WFM_OK;
+  double ms_index = 0;
   // chunks of whole problems that hold at most WFM_LIFT_OUT_MB MiB of lifts; a single problem may exceed that alone
-  const unsigned long long cap = cap_units("WFM_LIFT_OUT_MB", sizeof(wfm_lift_t), 1);
-  std::vector<std::pair<size_t, size_t>> chunks;
-  unsigned long long widest = 0;
-  for (size_t ka = 0, kb; ka < n; ka = kb) {
-    kb = chunk_end(ka, off, cap);
-    if (off[kb] > off[ka]) { chunks.emplace_back(ka, kb); widest = std::max(widest, off[kb] - off[ka]); }
-  }
-  char* host = (char*)malloc((size_t)total * sizeof(wfm_lift_t));
-  if (!host) { h->err = "out of host memory (lifts)"; return WFM_E_NOMEM; }
-  if (s->out.ensure((size_t)widest * 4)) { free(host); h->err = "out of device memory (lifts)"; return WFM_E_NOMEM; }
-  uint8_t* d_out = (uint8_t*)s->out.p;
-  const bool pinned = cs_pin_pieces(h);
-  for (const auto& c : chunks) {
-    launch_lift_write(d_runs, d_probs, s->iv, d_pre, d_win, d_off, (uint32_t)c.first, (uint32_t)c.second, d_out, h->stream);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = cs_copy_down(h, pinned, host + off[c.first] * sizeof(wfm_lift_t), d_out, (size_t)(off[c.second] - off[c.first]) * sizeof(wfm_lift_t));  // (the block is the next chunk's)
-    if (e != hipSuccess) { free(host); h->err = std::string("wfm_lift_runs: ") + hipGetErrorString(e); return WFM_E_HIP; }
-  }
-  *lifts = (wfm_lift_t*)host; *n_lifts = (size_t)total;
-  if (tm.on)
+  const EmitSpec sp{"wfm_lift_runs", "lift", "lifts", "lifts", s->work, s->out, cap_units("WFM_LIFT_OUT_MB", sizeof(wfm_lift_t), 1) * sizeof(wfm_lift_t)};
+  const EmitStream streams[] = {{off, sizeof(wfm_lift_t), 1, plain_alloc, (void**)lifts, n_lifts}};
+  EmitStats st;
+  const int rc = emit_lists(
+      h, tm, sp, n, streams,
+      [&](Carver& cv) { cv.piece(&d_pre, (size_t)n_pre); cv.piece(&d_probs, n); cv.piece(&d_win, n); cv.piece(&d_off, n + 1); cv.piece(&d_runs, n_runs_total); },
+      [&](auto down) {
+        HIPCHK(h, hipMemcpyAsync(d_probs, lp.data(), n * sizeof(LiftProb), hipMemcpyHostToDevice, h->stream));
+        if (n_runs_total) HIPCHK(h, hipMemcpyAsync(d_runs, runs, n_runs_total * 4, hipMemcpyHostToDevice, h->stream));
+        launch_lift_index(d_runs, d_probs, (int)n, s->iv, s->pm, s->n, s->n_bases, d_pre, d_win, d_off, h->stream);
+        HIPCHK(h, hipGetLastError());
+        down(win.data(), d_win, n * sizeof(LiftWin)); down(off.data(), d_off, (n + 1) * 8);
+        return WFM_OK;
+      },
+      [&]() {  // (the offsets are the device's)
+        ms_index = tm.lap();
+        for (size_t i = 0; i < n; ++i) per[i] = wfm_liftcall_t{win[i].flags, probs[i].n_runs, off[i], win[i].count};
+        return WFM_OK;
+      },
+      [&](size_t ka, size_t kb, uint8_t* const* d) {
+        launch_lift_write(d_runs, d_probs, s->iv, d_pre, d_win, d_off, (uint32_t)ka, (uint32_t)kb, d[0], h->stream);
+        return hip_rc(h, sp.fn, hipGetLastError());
+      },
+      &st);
+  if (tm.on && st.chunks)
     fprintf(stderr, "[wfm] lift: %zu problems, %zu runs, %llu intervals, %llu lifts in %zu chunks, upload + index + count %.3f ms, write + copy down %.3f ms (host clock, each ends in a synchronise)\n",
-            n, n_runs_total, (unsigned long long)s->n, total, chunks.size(), ms_index, tm.lap());
-  return WFM_OK;
+            n, n_runs_total, (unsigned long long)s->n, off[n], st.chunks, ms_index, tm.lap());
+  return rc;
 }
 
 void wfm_free_lifts(wfm_lift_t* p) { free(p); }
@@ -1064,55 +1052,37 @@ int wfm_chain_runs(wfm_handle_t* h, const wfm_chain_prob_t* probs, size_t n, con
   ChainWin* d_win;
   unsigned long long* d_off;
   uint32_t* d_runs;
-  Carver cv{h->scratch, "chain"};
-  cv.piece(&d_pre, (size_t)n_pre); cv.piece(&d_probs, n); cv.piece(&d_win, n); cv.piece(&d_off, n + 1); cv.piece(&d_runs, n_runs_total);
-  if (int rc = cv.commit(h)) return rc;
-  HIPCHK(h, hipMemcpyAsync(d_probs, cp.data(), n * sizeof(ChainProb), hipMemcpyHostToDevice, h->stream));
-  if (n_runs_total) HIPCHK(h, hipMemcpyAsync(d_runs, runs, n_runs_total * 4, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, tm.begin());
-  launch_chain_index(d_runs, d_probs, (int)n, d_pre, d_win, d_off, h->stream);
-  HIPCHK(h, hipGetLastError());
-  HIPCHK(h, tm.end());
   std::vector<ChainWin> win(n);
   std::vector<unsigned long long> off(n + 1);
-  HIPCHK(h, hipMemcpyAsync(win.data(), d_win, n * sizeof(ChainWin), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(off.data(), d_off, (n + 1) * 8, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  float ms_index = 0, ms_write = 0, ms = 0;
-  (void)tm.event_ms(&ms_index);
-  for (size_t i = 0; i < n; ++i) {
-    const ChainWin& w = win[i];
-    per[i] = wfm_chaincall_t{w.flags, probs[i].n_runs, off[i], w.count, w.lead_dt, w.lead_dq, w.trail_dt, w.trail_dq, w.eq, w.x};
-  }
-  const unsigned long long total = off[n];
-  if (total == 0) return WFM_OK;
   // chunks of whole problems that hold at most WFM_CHAIN_OUT_MB MiB of blocks; a single problem may exceed that alone
-  const unsigned long long cap = cap_units("WFM_CHAIN_OUT_MB", sizeof(wfm_chain_block_t), 1);
-  std::vector<std::pair<size_t, size_t>> chunks;
-  unsigned long long widest = 0;
-  for (size_t ka = 0, kb; ka < n; ka = kb) {
-    kb = chunk_end(ka, off, cap);
-    if (off[kb] > off[ka]) { chunks.emplace_back(ka, kb); widest = std::max(widest, off[kb] - off[ka]); }
-  }
-  char* host = (char*)malloc((size_t)total * sizeof(wfm_chain_block_t));
-  if (!host) { h->err = "out of host memory (chain)"; return WFM_E_NOMEM; }
-  if (h->outblk.ensure((size_t)widest * 2)) { free(host); h->err = "out of device memory (chain output)"; return WFM_E_NOMEM; }
-  uint8_t* d_out = (uint8_t*)h->outblk.p;
-  const bool pinned = cs_pin_pieces(h);
-  for (const auto& c : chunks) {
-    (void)tm.begin();
-    launch_chain_write(d_runs, d_probs, d_pre, d_win, d_off, (uint32_t)c.first, (uint32_t)c.second, d_out, h->stream);
-    hipError_t e = hipGetLastError();
-    (void)tm.end();
-    if (e == hipSuccess) e = cs_copy_down(h, pinned, host + off[c.first] * sizeof(wfm_chain_block_t), d_out, (size_t)(off[c.second] - off[c.first]) * sizeof(wfm_chain_block_t));  // (the block is the next chunk's)
-    if (e != hipSuccess) { free(host); h->err = std::string("wfm_chain_runs: ") + hipGetErrorString(e); return WFM_E_HIP; }
-    if (tm.event_ms(&ms)) ms_write += ms;
-  }
-  *blocks = (wfm_chain_block_t*)host; *n_blocks = (size_t)total;
-  if (tm.on)
+  const EmitSpec sp{"wfm_chain_runs", "chain", "chain", "chain output", h->scratch, h->outblk, cap_units("WFM_CHAIN_OUT_MB", sizeof(wfm_chain_block_t), 1) * sizeof(wfm_chain_block_t)};
+  const EmitStream streams[] = {{off, sizeof(wfm_chain_block_t), 1, plain_alloc, (void**)blocks, n_blocks}};
+  EmitStats st;
+  const int rc = emit_lists(
+      h, tm, sp, n, streams,
+      [&](Carver& cv) { cv.piece(&d_pre, (size_t)n_pre); cv.piece(&d_probs, n); cv.piece(&d_win, n); cv.piece(&d_off, n + 1); cv.piece(&d_runs, n_runs_total); },
+      [&](auto down) {
+        HIPCHK(h, hipMemcpyAsync(d_probs, cp.data(), n * sizeof(ChainProb), hipMemcpyHostToDevice, h->stream));
+        if (n_runs_total) HIPCHK(h, hipMemcpyAsync(d_runs, runs, n_runs_total * 4, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, tm.timed([&] { launch_chain_index(d_runs, d_probs, (int)n, d_pre, d_win, d_off, h->stream); }));
+        down(win.data(), d_win, n * sizeof(ChainWin)); down(off.data(), d_off, (n + 1) * 8);
+        return WFM_OK;
+      },
+      [&]() {  // (the offsets are the device's)
+        for (size_t i = 0; i < n; ++i) {
+          const ChainWin& w = win[i];
+          per[i] = wfm_chaincall_t{w.flags, probs[i].n_runs, off[i], w.count, w.lead_dt, w.lead_dq, w.trail_dt, w.trail_dq, w.eq, w.x};
+        }
+        return WFM_OK;
+      },
+      [&](size_t ka, size_t kb, uint8_t* const* d) {
+        return hip_rc(h, sp.fn, tm.timed([&] { launch_chain_write(d_runs, d_probs, d_pre, d_win, d_off, (uint32_t)ka, (uint32_t)kb, d[0], h->stream); }));
+      },
+      &st);
+  if (tm.on && st.chunks)
     fprintf(stderr, "[wfm] chain: %zu problems, %zu runs, %llu blocks in %zu chunks, index %.3f ms, write %.3f ms (device events), the call %.3f ms (host clock)\n",
-            n, n_runs_total, total, chunks.size(), ms_index, ms_write, tm.host_ms());
-  return WFM_OK;
+            n, n_runs_total, off[n], st.chunks, st.ms_index, st.ms_write, tm.host_ms());
+  return rc;
 }
 
 void wfm_free_chain(wfm_chain_block_t* p) { free(p); }
@@ -1274,9 +1244,9 @@ int wfm_pav_export(wfm_handle_t* h, wfm_pav_t* pav, wfm_pav_seg_t** segs, size_t
   if (m == 0) return WFM_OK;
   HIPCHK(h, hipSetDevice(h->device));
   std::vector<unsigned long long> keys(2 * m);
-  const bool pinned = cs_pin_pieces(h);
-  hipError_t e = cs_copy_down(h, pinned, (char*)keys.data(), (const uint8_t*)pav->ks(), m * 8);
-  if (e == hipSuccess) e = cs_copy_down(h, pinned, (char*)(keys.data() + m), (const uint8_t*)pav->ke(), m * 8);
+  const bool pinned = pin_pieces(h);
+  hipError_t e = copy_down(h, pinned, (char*)keys.data(), (const uint8_t*)pav->ks(), m * 8);
+  if (e == hipSuccess) e = copy_down(h, pinned, (char*)(keys.data() + m), (const uint8_t*)pav->ke(), m * 8);
   if (e != hipSuccess) { h->err = std::string("wfm_pav_export: ") + hipGetErrorString(e); return WFM_E_HIP; }
   // a union interval of 2^32 bases or more comes as abutting pieces
   const uint64_t mask = ((uint64_t)1 << PAV_SHIFT) - 1, piece = 0x80000000ull;
@@ -1340,13 +1310,13 @@ int wfm_pav_matrix(wfm_handle_t* h, wfm_pav_t* pav, const wfm_lift_iv_t* iv, siz
   cv.piece(&d_iv, n_iv); cv.piece(&d_out, std::min(n_iv, cap) * G);
   if (int rc = cv.commit(h)) return rc;
   HIPCHK(h, hipMemcpyAsync(d_iv, iv, n_iv * sizeof(wfm_lift_iv_t), hipMemcpyHostToDevice, h->stream));
-  const bool pinned = cs_pin_pieces(h);
+  const bool pinned = pin_pieces(h);
   size_t chunks = 0;
   for (size_t ra = 0, rb; ra < n_iv; ra = rb, ++chunks) {
     rb = chunk_end(ra, n_iv, cap, [](size_t a, size_t b) { return (unsigned long long)(b - a); });
     launch_pav_matrix(pav->ks(), pav->ke(), (const unsigned long long*)pav->c.p, pav->n, d_iv, ra, rb, pav->n_groups, d_out, h->stream);
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = cs_copy_down(h, pinned, (char*)(out + ra * G), (const uint8_t*)d_out, (rb - ra) * G * 4);  // (the block is the next chunk's)
+    if (e == hipSuccess) e = copy_down(h, pinned, (char*)(out + ra * G), (const uint8_t*)d_out, (rb - ra) * G * 4);  // (the block is the next chunk's)
     if (e != hipSuccess) { h->err = std::string("wfm_pav_matrix: ") + hipGetErrorString(e); return WFM_E_HIP; }
   }
   if (tm.on)
@@ -1548,20 +1518,20 @@ int wfm_sites_table(wfm_handle_t* h, wfm_sites_t* s, wfm_site_t** sites, size_t*
   d_gt = (uint8_t*)h->outblk.p;
   launch_sites_rows(s->vars, cur, w.first, w.gfirst, (uint32_t)S, d_rows, h->stream);
   HIPCHK(h, hipGetLastError());
-  const bool pinned = cs_pin_pieces(h);
+  const bool pinned = pin_pieces(h);
   std::unique_ptr<wfm_site_t, void (*)(void*)> rows((wfm_site_t*)malloc(S * sizeof(wfm_site_t)), free);
   std::unique_ptr<char, void (*)(void*)> cells((char*)malloc(std::max<size_t>(S * G, 1)), free);
   std::vector<char> folded(s->bytes);
   if (!rows || !cells) { h->err = "out of host memory (sites table)"; return WFM_E_NOMEM; }
-  hipError_t e = cs_copy_down(h, pinned, (char*)rows.get(), (const uint8_t*)d_rows, S * sizeof(wfm_site_t));
-  if (e == hipSuccess) e = cs_copy_down(h, pinned, folded.data(), s->alle, s->bytes);
+  hipError_t e = copy_down(h, pinned, (char*)rows.get(), (const uint8_t*)d_rows, S * sizeof(wfm_site_t));
+  if (e == hipSuccess) e = copy_down(h, pinned, folded.data(), s->alle, s->bytes);
   if (e != hipSuccess) { h->err = std::string("wfm_sites_table: ") + hipGetErrorString(e); return WFM_E_HIP; }
   size_t chunks = 0;
   for (size_t ra = 0, rb; ra < S && G; ra = rb, ++chunks) {
     rb = chunk_end(ra, S, cap, [](size_t a, size_t b) { return (unsigned long long)(b - a); });
     launch_sites_gt(d_rows, w.first, w.sk3, s->eq->ks(), s->eq->ke(), (const unsigned long long*)s->eq->c.p, s->eq->n, ra, rb, s->n_groups, d_gt, h->stream);
     e = hipGetLastError();
-    if (e == hipSuccess) e = cs_copy_down(h, pinned, cells.get() + ra * G, d_gt, (rb - ra) * G);  // (the block is the next chunk's)
+    if (e == hipSuccess) e = copy_down(h, pinned, cells.get() + ra * G, d_gt, (rb - ra) * G);  // (the block is the next chunk's)
     if (e != hipSuccess) { h->err = std::string("wfm_sites_table: ") + hipGetErrorString(e); return WFM_E_HIP; }
   }
   // one representative's bytes per site, in site order
@@ -1594,10 +1564,10 @@ int wfm_sites_export(wfm_handle_t* h, wfm_sites_t* s, wfm_site_var_t** vars, siz
   HIPCHK(h, hipSetDevice(h->device));
   wfm_site_var_t* v = (wfm_site_var_t*)malloc(s->n * sizeof(wfm_site_var_t));
   char* a = (char*)malloc(std::max<size_t>(s->bytes, 1));
-  const bool pinned = cs_pin_pieces(h);
+  const bool pinned = pin_pieces(h);
   hipError_t e = hipSuccess;
-  if (v && a) e = cs_copy_down(h, pinned, (char*)v, (const uint8_t*)s->vars, s->n * sizeof(wfm_site_var_t));
-  if (v && a && e == hipSuccess) e = cs_copy_down(h, pinned, a, s->alle, s->bytes);
+  if (v && a) e = copy_down(h, pinned, (char*)v, (const uint8_t*)s->vars, s->n * sizeof(wfm_site_var_t));
+  if (v && a && e == hipSuccess) e = copy_down(h, pinned, a, s->alle, s->bytes);
   if (!v || !a || e != hipSuccess) {
     free(v); free(a); wfm_pav_free_list(*segs);
     *segs = nullptr; *n_segs = 0;
@@ -1827,8 +1797,8 @@ int wfm_net_table(wfm_handle_t* h, wfm_net_t* net, wfm_net_piece_t** pieces, siz
   std::unique_ptr<wfm_netcall_t, void (*)(void*)> rows((wfm_netcall_t*)malloc(R * sizeof(wfm_netcall_t)), free);
   std::unique_ptr<char, void (*)(void*)> out((char*)malloc(std::max<size_t>(P, 1) * sizeof(wfm_net_piece_t)), free);
   if (!rows || !out) { h->err = "out of host memory (net table)"; return WFM_E_NOMEM; }
-  const bool pinned = cs_pin_pieces(h);
-  hipError_t e = cs_copy_down(h, pinned, (char*)rows.get(), (const uint8_t*)d_per, R * sizeof(wfm_netcall_t));
+  const bool pinned = pin_pieces(h);
+  hipError_t e = copy_down(h, pinned, (char*)rows.get(), (const uint8_t*)d_per, R * sizeof(wfm_netcall_t));
   if (e != hipSuccess) { h->err = std::string("wfm_net_table: ") + hipGetErrorString(e); return WFM_E_HIP; }
   size_t chunks = 0;
   if (P) {
@@ -1838,7 +1808,7 @@ int wfm_net_table(wfm_handle_t* h, wfm_net_t* net, wfm_net_piece_t** pieces, siz
       b = chunk_end(a, P, cap, [](size_t x, size_t y) { return (unsigned long long)(y - x); });
       launch_net_pieces(w, a, b, d_out, h->stream);
       e = hipGetLastError();
-      if (e == hipSuccess) e = cs_copy_down(h, pinned, out.get() + a * sizeof(wfm_net_piece_t), (const uint8_t*)d_out, (b - a) * sizeof(wfm_net_piece_t));  // (the block is the next chunk's)
+      if (e == hipSuccess) e = copy_down(h, pinned, out.get() + a * sizeof(wfm_net_piece_t), (const uint8_t*)d_out, (b - a) * sizeof(wfm_net_piece_t));  // (the block is the next chunk's)
       if (e != hipSuccess) { h->err = std::string("wfm_net_table: ") + hipGetErrorString(e); return WFM_E_HIP; }
     }
   }
@@ -1862,10 +1832,10 @@ int wfm_net_export(wfm_handle_t* h, wfm_net_t* net, wfm_net_block_t** blocks, si
   HIPCHK(h, hipSetDevice(h->device));
   wfm_net_block_t* b = (wfm_net_block_t*)malloc(std::max<size_t>(net->n, 1) * sizeof(wfm_net_block_t));
   wfm_net_rec_t* r = (wfm_net_rec_t*)malloc(net->r * sizeof(wfm_net_rec_t));
-  const bool pinned = cs_pin_pieces(h);
+  const bool pinned = pin_pieces(h);
   hipError_t e = hipSuccess;
-  if (b && r) e = cs_copy_down(h, pinned, (char*)b, (const uint8_t*)net->blocks, net->n * sizeof(wfm_net_block_t));
-  if (b && r && e == hipSuccess) e = cs_copy_down(h, pinned, (char*)r, (const uint8_t*)net->recs, net->r * sizeof(wfm_net_rec_t));
+  if (b && r) e = copy_down(h, pinned, (char*)b, (const uint8_t*)net->blocks, net->n * sizeof(wfm_net_block_t));
+  if (b && r && e == hipSuccess) e = copy_down(h, pinned, (char*)r, (const uint8_t*)net->recs, net->r * sizeof(wfm_net_rec_t));
   if (!b || !r || e != hipSuccess) {
     free(b); free(r);
     if (e != hipSuccess) { h->err = std::string("wfm_net_export: ") + hipGetErrorString(e); return WFM_E_HIP; }
@@ -2196,8 +2166,8 @@ int wfm_trans_closure(wfm_handle_t* h, wfm_trans_t* obj, const wfm_lift_iv_t* se
   }
   // the list, sorted by (seed, start) as the keys are
   std::vector<unsigned long long> keys(2 * m);
-  const bool pinned = cs_pin_pieces(h);
-  hipError_t e = cs_copy_down(h, pinned, (char*)keys.data(), (const uint8_t*)obj->acc.p, 2 * m * 8);
+  const bool pinned = pin_pieces(h);
+  hipError_t e = copy_down(h, pinned, (char*)keys.data(), (const uint8_t*)obj->acc.p, 2 * m * 8);
   if (e != hipSuccess) { h->err = std::string("wfm_trans_closure: ") + hipGetErrorString(e); return WFM_E_HIP; }
   wfm_trans_iv_t* out = (wfm_trans_iv_t*)malloc(m * sizeof(wfm_trans_iv_t));
   if (!out) { h->err = "out of host memory (transitive intervals)"; return WFM_E_NOMEM; }
@@ -2228,7 +2198,7 @@ int wfm_trans_export(wfm_handle_t* h, wfm_trans_t* obj, wfm_trans_rec_t** recs, 
   wfm_trans_rec_t* r = (wfm_trans_rec_t*)malloc(obj->recs.size() * sizeof(wfm_trans_rec_t));
   wfm_trans_word_t* w = (wfm_trans_word_t*)malloc(obj->np * sizeof(wfm_trans_word_t));
   hipError_t e = hipSuccess;
-  if (r && w) e = cs_copy_down(h, cs_pin_pieces(h), (char*)w, (const uint8_t*)obj->pre, obj->np * sizeof(wfm_trans_word_t));
+  if (r && w) e = copy_down(h, pin_pieces(h), (char*)w, (const uint8_t*)obj->pre, obj->np * sizeof(wfm_trans_word_t));
   if (!r || !w || e != hipSuccess) {
     free(r); free(w);
     if (e != hipSuccess) { h->err = std::string("wfm_trans_export: ") + hipGetErrorString(e); return WFM_E_HIP; }
