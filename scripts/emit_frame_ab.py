@@ -9,7 +9,9 @@ windows on the first sequence.  The switches: --cs=long, --maf, --variants, --co
 --transitive.  Every run is a fresh child process with WFM_LIB_PATH set, under a time limit of its own; a child starts only if the one
 before it exited 0.  Each library is loaded once by a child that is not timed (profiles/driver_passes.md section 2 asks for it); then
 A, B, A, B, ... `--procs` times each.  A child aligns the rows once without a switch, then once with all of them: the second run is the
-timed one.  --debug N: N more children each, alternating, with WFM_DEBUG=1, for the passes' own [wfm] lines."""
+timed one.  Then the child makes the six files an aligned PAF gives (--coverage-paf, --lift-paf, --chain-paf with --chain and with
+--chain-net, --pav-paf, --transitive-paf) from the PAF it has just written, each call timed on the wall clock (profiles/paf_passes.md):
+their md5 and out[4] are compared between the libraries as the run's are, and each is held against the run's own file.  --debug N: N more children each, alternating, with WFM_DEBUG=1, for the passes' own [wfm] lines."""
 import argparse
 import gzip
 import hashlib
@@ -17,6 +19,7 @@ import json
 import os
 import subprocess
 import sys
+import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
@@ -63,10 +66,20 @@ def child(workdir, tag, load_only):
             for n in sw:
                 sw[n][1]()
         files["paf"] = out
+        offline = {"coverage": lambda o: capi.coverage_paf(h, LPA, out, o), "lift": lambda o: capi.lift_paf(h, LPA, out, bed, o),
+                   "chain": lambda o: capi.chain_paf(h, LPA, out, o), "chain_net": lambda o: capi.chain_paf(h, LPA, out, None, net_path=o),
+                   "pav": lambda o: capi.pav_paf(h, LPA, None, out, bed, 0, o), "transitive": lambda o: capi.transitive_paf(h, LPA, out, bed, o, depth=2)}
+        offline_ms = {}
+        for n, call in offline.items():
+            files["offline." + n] = os.path.join(workdir, tag + ".offline." + n)
+            t0 = time.perf_counter()
+            counts["offline." + n] = [int(v) for v in call(files["offline." + n])]
+            offline_ms[n] = round((time.perf_counter() - t0) * 1e3, 2)
         md5 = {n: hashlib.md5(open(p, "rb").read()).hexdigest() for n, p in sorted(files.items())}
         print(json.dumps({"library": capi.LIB_PATH, "ms_total": round(s.ms_total, 2), "ms_wflign": round(s.ms_wflign, 2), "ms_gpu": round(s.ms_gpu, 2),
                           "records": int(s.records), "written": int(s.written), "aligned_bp": int(s.aligned_bp), "batches": int(s.batches),
-                          "md5": md5, "counts": counts}, sort_keys=True), flush=True)
+                          "md5": md5, "counts": counts, "offline_ms": offline_ms,
+                          "offline_is_the_runs_file": all(md5["offline." + n] == md5[n] for n in offline)}, sort_keys=True), flush=True)
     finally:
         h.close()
 
@@ -128,7 +141,14 @@ def main():
     lo, hi = ms["parent"][0], ms["parent"][-1]
     median = ms["branch"][len(ms["branch"]) // 2] if a.procs % 2 else (ms["branch"][a.procs // 2 - 1] + ms["branch"][a.procs // 2]) / 2
     inside = lo - (hi - lo) <= median <= hi + (hi - lo)
-    print(json.dumps({"files_and_counts_identical": same, "parent_ms_total": ms["parent"], "branch_ms_total": ms["branch"], "branch_median": median,
+    for n in first["offline_ms"]:  # the same rule for the wall time of each of the six offline calls
+        pm, bm = sorted(r["offline_ms"][n] for r in runs["parent"]), sorted(r["offline_ms"][n] for r in runs["branch"])
+        med = bm[len(bm) // 2] if a.procs % 2 else (bm[a.procs // 2 - 1] + bm[a.procs // 2]) / 2
+        print(json.dumps({"offline": n, "parent_ms": pm, "branch_ms": bm, "branch_median": med,
+                          "parent_range_widened": [round(2 * pm[0] - pm[-1], 2), round(2 * pm[-1] - pm[0], 2)],
+                          "inside": 2 * pm[0] - pm[-1] <= med <= 2 * pm[-1] - pm[0]}), flush=True)
+    print(json.dumps({"files_and_counts_identical": same, "offline_is_the_runs_file": all(r["offline_is_the_runs_file"] for rs in runs.values() for r in rs),
+                      "parent_ms_total": ms["parent"], "branch_ms_total": ms["branch"], "branch_median": median,
                       "parent_range_widened": [round(lo - (hi - lo), 2), round(hi + (hi - lo), 2)], "inside": inside}), flush=True)
     for k in range(a.debug):
         for label, lib in libs:

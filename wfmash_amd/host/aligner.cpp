@@ -1,13 +1,6 @@
 #include "aligner.hpp"
+#include "run_passes.hpp"
 #include "verify_paf.hpp"
-#include "coverage_text.hpp"
-#include "lift_text.hpp"
-#include "chain_text.hpp"
-#include "maf_text.hpp"
-#include "pav_text.hpp"
-#include "genotype_text.hpp"
-#include "transitive_text.hpp"
-#include "map_queue.hpp"
 #include "parallel.hpp"
 #include "../csrc/wfa_handle.h"
 
@@ -427,8 +420,8 @@ wflign::BatchTexts Aligner::align_batch(wfm_handle_t* gpu_handle, std::vector<st
   account(sum, st, resident, fetched, recs);
   t.wflign = t.lap();
   std::string& out = texts.paf = gather_text(sum, fetched, recs);
-  // (a record without a line has no VCF lines, write_record; lift lines and chains come in the order of the records' lines, and the chains' ids are the writer's)
-  for (const auto& r : recs) { texts.text[wflign::SW_VARIANTS] += r.vcf; texts.text[wflign::SW_LIFT] += r.lift; texts.text[wflign::SW_CHAIN] += r.chain; texts.text[wflign::SW_MAF] += r.maf; }
+  // (a record without a line has no VCF lines, write_record; lift lines and chains are there already, in the order of the records' lines: take_texts)
+  for (const auto& r : recs) { texts.text[wflign::SW_VARIANTS] += r.vcf; texts.text[wflign::SW_MAF] += r.maf; }
   t.text = t.lap();
   if (verify::enabled() && !param.sam_format) {  // --verify: the finished lines, before they are written (SAM records carry no =/X CIGAR)
     verify::Source src;
@@ -517,23 +510,6 @@ class HandlePool {
   std::map<int, std::vector<std::pair<wfm_handle_t*, bool>>> by_device_;  // handle, in use
 };
 
-// the ordered writer's sink: the output file, flushed once per put.  number (--chain): the chains of a batch come without their ids; the
-// writer numbers them 1, 2, 3 ... as it writes them, in file order
-struct TextSink {
-  std::ofstream* out;
-  bool number = false;
-  uint64_t next = 1;
-  std::string numbered;
-  void write(std::string& text) {
-    if (!number) { *out << text; return; }
-    numbered.clear();
-    chain::number(text, &next, numbered);
-    *out << numbered;
-  }
-  void flush() { out->flush(); }
-};
-using TextWriter = skch::OrderedWriter<std::string, TextSink>;
-
 // what: "output file", "the BED file of --lift", ...
 template <class Stream>
 void open_or_throw(Stream& s, const std::string& path, const char* what, std::ios::openmode mode = std::ios::openmode()) {
@@ -545,369 +521,11 @@ std::string read_whole_file(const std::string& path, const char* what) {
   open_or_throw(f, path, what, std::ios::binary);
   return std::string((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
 }
-std::vector<wfm_lift_iv_t> raw_intervals(const std::vector<lift::Interval>& iv) {
-  std::vector<wfm_lift_iv_t> raw(iv.size());
-  for (size_t i = 0; i < raw.size(); ++i) raw[i] = wfm_lift_iv_t{iv[i].gstart, iv[i].gend};
-  return raw;
-}
-
-// One pass of a run: a switch that is on, and the file it writes -- per batch through an ordered writer keyed by the batches' numbers
-// (--variants, --lift, --chain), or once the workers are done (finish: the others).  A pass with a device object keeps one per handle
-// the run has used so far, made at the handle's first batch; finish merges them into the first handle's.  A pass's constructor reads what
-// it needs before anything is aligned and adds to the run's tables what its stage looks up per record.
-struct Pass {
-  Pass(wflign::SwitchId i, const char* t, bool with_object, wflign::RunTables& tb, const std::string& path, const char* what)
-      : id(i), tag(t), per_handle(with_object), tables(tb) {
-    open_or_throw(out, path, what);
-  }
-  virtual ~Pass() {}
-  const wflign::SwitchId id;
-  const std::string tag;  // "--pav": of the messages
-  const bool per_handle;
-  wflign::RunTables& tables;
-  std::ofstream out;
-  std::unique_ptr<TextWriter> writer;
-  std::mutex mu;  // of objects (and of what a pass gathers from the batches)
-  std::vector<std::pair<wfm_handle_t*, void*>> objects;
-
-  void* object_of(wfm_handle_t* h) {
-    if (!per_handle) return nullptr;
-    std::lock_guard<std::mutex> lk(mu);
-    for (auto& ho : objects) if (ho.first == h) return ho.second;
-    void* o = nullptr;
-    std::lock_guard<std::mutex> hl(wflign::handle_lock(h));
-    if (create(h, &o) != WFM_OK) throw std::runtime_error("[wfmash::align] " + tag + ": " + wfm_last_error(h));
-    objects.emplace_back(h, o);
-    return o;
-  }
-  void free_objects() {
-    for (auto& ho : objects) {
-      std::lock_guard<std::mutex> lk(wflign::handle_lock(ho.first));
-      destroy(ho.second);
-    }
-    objects.clear();
-  }
-  // the batch's share: its text to the ordered writer
-  virtual void take(uint64_t seq, wflign::BatchTexts& t) { if (writer) writer->put(seq, std::move(t.text[id])); }
-  virtual void finish() {}
-
- protected:
-  virtual int create(wfm_handle_t*, void**) { return WFM_OK; }
-  virtual void destroy(void*) {}
-  // the lists of an object (kept by the pass between the two), into another, freed
-  virtual int export_lists(wfm_handle_t*, void*) { return WFM_OK; }
-  virtual int import_lists(wfm_handle_t*, void*) { return WFM_OK; }
-  virtual void free_lists() {}
-
-  wfm_handle_t* h0() const { return objects.front().first; }
-  template <class T>
-  T* first() const { return static_cast<T*>(objects.front().second); }
-  [[noreturn]] void fail(wfm_handle_t* h, const char* what) const { throw std::runtime_error("[wfmash::align] " + tag + ": " + what + ": " + wfm_last_error(h)); }
-  // every other handle's object exported and imported into the first's (integer adds, unions and set functions: the order does not matter)
-  void merge() {
-    for (size_t k = 1; k < objects.size(); ++k) {
-      {
-        std::lock_guard<std::mutex> lk(wflign::handle_lock(objects[k].first));
-        if (export_lists(objects[k].first, objects[k].second) != WFM_OK) fail(objects[k].first, "export");
-      }
-      std::lock_guard<std::mutex> lk(wflign::handle_lock(h0()));
-      const int rc = import_lists(h0(), objects.front().second);
-      free_lists();
-      if (rc != WFM_OK) fail(h0(), "import");
-    }
-  }
-  void writes_per_batch(bool number = false) { writer.reset(new TextWriter(TextSink{&out, number})); }
-};
-
-// --variants: the header here, the batches' lines through the ordered writer
-struct VariantsPass : Pass {
-  VariantsPass(wflign::RunTables& tb, const wflign::SwitchSetting& s) : Pass(wflign::SW_VARIANTS, "--variants", false, tb, s.out, "the variants file") {
-    out << "##fileformat=VCFv4.2\n##source=wfmash-hip " WFMASH_HIP_VERSION "\n";
-    for (size_t i = 0; i < tb.tnames.size(); ++i) out << "##contig=<ID=" << tb.tnames[i] << ",length=" << tb.tlengths[i] << ">\n";
-    out << "##INFO=<ID=QNAME,Number=1,Type=String,Description=\"Query sequence name\">\n"
-           "##INFO=<ID=QSTART,Number=1,Type=Integer,Description=\"Start of the query bases in ALT, 0-based, forward strand\">\n"
-           "##INFO=<ID=QEND,Number=1,Type=Integer,Description=\"End of the query bases in ALT, exclusive, forward strand\">\n"
-           "##INFO=<ID=QSTRAND,Number=1,Type=String,Description=\"Strand of the query in the alignment\">\n"
-           "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n";
-    writes_per_batch();
-  }
-};
-
-// --coverage: the depth objects; the intervals of their sum taken once on the device, the file through coverage_bedgraph
-struct CoveragePass : Pass {
-  CoveragePass(wflign::RunTables& tb, const wflign::SwitchSetting& s) : Pass(wflign::SW_COVERAGE, "--coverage", true, tb, s.out, "the coverage file") {}
-  wfm_cov_entry_t* list = nullptr;
-  size_t n_list = 0;
-  int create(wfm_handle_t* h, void** o) override {
-    wfm_coverage_t* c = nullptr;
-    const int rc = wfm_coverage_create(h, tables.seq_offsets.back(), &c);
-    *o = c;
-    return rc;
-  }
-  void destroy(void* o) override { wfm_coverage_free((wfm_coverage_t*)o); }
-  int export_lists(wfm_handle_t* h, void* o) override { return wfm_coverage_export(h, (wfm_coverage_t*)o, &list, &n_list); }
-  int import_lists(wfm_handle_t* h, void* o) override { return wfm_coverage_import(h, (wfm_coverage_t*)o, list, n_list); }
-  void free_lists() override { wfm_coverage_free_list(list); }
-  void finish() override {
-    const auto t0 = Clock::now();
-    merge();
-    wfm_cov_interval_t* iv = nullptr;
-    size_t n = 0;
-    uint64_t totals[3] = {0, 0, 0};
-    if (!objects.empty()) {
-      std::lock_guard<std::mutex> lk(wflign::handle_lock(h0()));
-      if (wfm_coverage_intervals(h0(), first<wfm_coverage_t>(), &iv, &n, totals) != WFM_OK) fail(h0(), "intervals");
-    }
-    uint64_t lines = 0;
-    out << coverage::coverage_bedgraph(tables.tnames, tables.tlengths, iv, n, &lines);
-    wfm_coverage_free_list(iv);
-    wflign::switch_finished(id, totals[0], totals[1], lines);
-    if (getenv("WFM_DEBUG"))
-      fprintf(stderr, "[wfmash::align] coverage: %zu objects merged, %zu intervals, %llu lines, %.1f ms\n", objects.size(), n, (unsigned long long)lines, ms_since(t0));
-  }
-};
-
-// --lift: the BED is read once, here, its intervals sorted as the device takes them; a liftset per handle; the batches' lines through the
-// ordered writer
-struct LiftPass : Pass {
-  LiftPass(wflign::RunTables& tb, const wflign::SwitchSetting& s) : Pass(wflign::SW_LIFT, "--lift", true, tb, s.out, "the lift file") {
-    lift::Bed parsed = lift::parse_bed(read_whole_file(s.bed, "the BED file of --lift"), tb.find_target, tb.tlengths, tb.seq_offsets);
-    tb.lift_iv = std::move(parsed.iv);
-    wflign::switch_finished(id, 0, 0, parsed.skipped);
-    writes_per_batch();
-  }
-  int create(wfm_handle_t* h, void** o) override {
-    const std::vector<wfm_lift_iv_t> raw = raw_intervals(tables.lift_iv);
-    wfm_liftset_t* set = nullptr;
-    const int rc = wfm_liftset_create(h, raw.data(), raw.size(), tables.seq_offsets.back(), &set);
-    *o = set;
-    return rc;
-  }
-  void destroy(void* o) override { wfm_liftset_free((wfm_liftset_t*)o); }
-};
-
-// --chain: the batches' chains through the ordered writer, which numbers them
-struct ChainPass : Pass {
-  ChainPass(wflign::RunTables& tb, const wflign::SwitchSetting& s) : Pass(wflign::SW_CHAIN, "--chain", false, tb, s.out, "the chain file") {
-    tb.chain_swap = s.option != 0;
-    writes_per_batch(true);
-  }
-};
-
-// --maf: the header here, the batches' blocks through the ordered writer (no device object, no merge)
-struct MafPass : Pass {
-  MafPass(wflign::RunTables& tb, const wflign::SwitchSetting& s) : Pass(wflign::SW_MAF, "--maf", false, tb, s.out, "the maf file") {
-    out << maf::header();
-    writes_per_batch();
-  }
-};
-
-// --pav: the intervals of the table in the file's order and the columns are known before anything is aligned; the presence objects; the
-// table of their union taken once on the device, the file through pav_text.hpp
-struct PavPass : Pass {
-  PavPass(wflign::RunTables& tb, const wflign::SwitchSetting& s) : Pass(wflign::SW_PAV, "--pav", true, tb, s.out, "the pav file") {
-    if (!s.bed.empty()) {
-      lift::Bed parsed = lift::parse_bed(read_whole_file(s.bed, "the BED file of --pav"), tb.find_target, tb.tlengths, tb.seq_offsets);
-      iv = std::move(parsed.iv);
-      bed_skipped = parsed.skipped;
-    } else {
-      iv = pav::windows(tb.tlengths, tb.seq_offsets, s.option);
-    }
-    if (tb.columns.of_seq.empty()) tb.columns = pav::columns(tb.qnames);
-  }
-  std::vector<lift::Interval> iv;
-  uint64_t bed_skipped = 0;
-  wfm_pav_seg_t* list = nullptr;
-  size_t n_list = 0;
-  int create(wfm_handle_t* h, void** o) override {
-    wfm_pav_t* p = nullptr;
-    const int rc = wfm_pav_create(h, tables.seq_offsets.back(), (uint32_t)tables.columns.keys.size(), &p);
-    *o = p;
-    return rc;
-  }
-  void destroy(void* o) override { wfm_pav_free((wfm_pav_t*)o); }
-  int export_lists(wfm_handle_t* h, void* o) override { return wfm_pav_export(h, (wfm_pav_t*)o, &list, &n_list); }
-  int import_lists(wfm_handle_t* h, void* o) override { return wfm_pav_import(h, (wfm_pav_t*)o, list, n_list); }
-  void free_lists() override { wfm_pav_free_list(list); }
-  void finish() override {
-    const auto t0 = Clock::now();
-    const size_t G = tables.columns.keys.size();
-    std::vector<uint32_t> cells(G * iv.size(), 0u);
-    uint64_t counts[3] = {0, 0, 0};
-    merge();
-    if (!objects.empty()) {
-      const std::vector<wfm_lift_iv_t> raw = raw_intervals(iv);
-      std::lock_guard<std::mutex> lk(wflign::handle_lock(h0()));
-      if (wfm_pav_matrix(h0(), first<wfm_pav_t>(), raw.data(), raw.size(), cells.data()) != WFM_OK) fail(h0(), "matrix");
-      wfm_pav_counts(first<wfm_pav_t>(), counts);
-    }
-    const auto t1 = Clock::now();
-    pav::table(out, tables.columns.keys, tables.tnames, iv, cells.data());
-    wflign::switch_finished(id, iv.size(), counts[1], bed_skipped);
-    if (getenv("WFM_DEBUG"))
-      fprintf(stderr, "[wfmash::align] pav: %zu objects merged, %llu segments added, %llu union intervals, %zu rows x %zu groups, merge + union + matrix %.1f ms, text %.1f ms\n",
-              objects.size(), (unsigned long long)counts[0], (unsigned long long)counts[1], iv.size(), G, std::chrono::duration<double, std::milli>(t1 - t0).count(), ms_since(t1));
-  }
-};
-
-// --genotypes: the columns are --pav's; the sites objects; the table of their merge taken once on the device, the file through
-// genotype_text.hpp
-struct GenotypesPass : Pass {
-  GenotypesPass(wflign::RunTables& tb, const wflign::SwitchSetting& s) : Pass(wflign::SW_GENOTYPES, "--genotypes", true, tb, s.out, "the genotypes file") {
-    if (tb.columns.of_seq.empty()) tb.columns = pav::columns(tb.qnames);
-  }
-  wfm_site_var_t* vars = nullptr;
-  char* alleles = nullptr;
-  wfm_pav_seg_t* segs = nullptr;
-  size_t n_vars = 0, n_bytes = 0, n_segs = 0;
-  int create(wfm_handle_t* h, void** o) override {
-    wfm_sites_t* p = nullptr;
-    const int rc = wfm_sites_create(h, tables.seq_offsets.back(), (uint32_t)tables.columns.keys.size(), &p);
-    *o = p;
-    return rc;
-  }
-  void destroy(void* o) override { wfm_sites_free((wfm_sites_t*)o); }
-  int export_lists(wfm_handle_t* h, void* o) override { return wfm_sites_export(h, (wfm_sites_t*)o, &vars, &n_vars, &alleles, &n_bytes, &segs, &n_segs); }
-  int import_lists(wfm_handle_t* h, void* o) override { return wfm_sites_import(h, (wfm_sites_t*)o, vars, n_vars, alleles, n_bytes, segs, n_segs); }
-  void free_lists() override { wfm_sites_free_list(vars); wfm_sites_free_list(alleles); wfm_sites_free_list(segs); }
-  void finish() override {
-    const auto t0 = Clock::now();
-    wfm_site_t* rows = nullptr;
-    char *table_alleles = nullptr, *gt = nullptr;
-    size_t n_sites = 0, bytes = 0;
-    uint64_t counts[4] = {0, 0, 0, 0};
-    merge();
-    if (!objects.empty()) {
-      std::lock_guard<std::mutex> lk(wflign::handle_lock(h0()));
-      if (wfm_sites_table(h0(), first<wfm_sites_t>(), &rows, &n_sites, &table_alleles, &bytes, &gt) != WFM_OK) fail(h0(), "table");
-      wfm_sites_counts(first<wfm_sites_t>(), counts);
-    }
-    const auto t1 = Clock::now();
-    genotype::vcf(out, WFMASH_HIP_VERSION, tables.tnames, tables.tlengths, tables.seq_offsets, tables.columns.keys, rows, n_sites, table_alleles, gt);
-    wfm_sites_free_list(rows); wfm_sites_free_list(table_alleles); wfm_sites_free_list(gt);
-    wflign::switch_finished(id, n_sites, counts[0] - n_sites, 0);
-    if (getenv("WFM_DEBUG"))
-      fprintf(stderr, "[wfmash::align] genotypes: %zu objects merged, %llu variants, %zu sites x %zu groups, %llu = intervals, merge + table %.1f ms, text %.1f ms\n",
-              objects.size(), (unsigned long long)counts[0], n_sites, tables.columns.keys.size(), (unsigned long long)counts[2],
-              std::chrono::duration<double, std::milli>(t1 - t0).count(), ms_since(t1));
-  }
-};
-
-// --chain-net: the net objects, and what the chains' headers need of every record added, in no order; the table of the merged object
-// taken once on the device, the file through chain_text.hpp's net_file in the order of the orders, which is the order of the PAF's records
-struct ChainNetPass : Pass {
-  ChainNetPass(wflign::RunTables& tb, const wflign::SwitchSetting& s) : Pass(wflign::SW_CHAIN_NET, "--chain-net", true, tb, s.out, "the chain-net file") {}
-  std::vector<wflign::NetHead> heads;  // (under mu)
-  wfm_net_block_t* blocks = nullptr;
-  wfm_net_rec_t* recs = nullptr;
-  size_t n_blocks = 0, n_recs = 0;
-  void take(uint64_t, wflign::BatchTexts& t) override {
-    if (t.net_heads.empty()) return;
-    std::lock_guard<std::mutex> lk(mu);
-    for (auto& hd : t.net_heads) heads.push_back(std::move(hd));
-  }
-  int create(wfm_handle_t* h, void** o) override {
-    wfm_net_t* p = nullptr;
-    const int rc = wfm_net_create(h, tables.seq_offsets.back(), &p);
-    *o = p;
-    return rc;
-  }
-  void destroy(void* o) override { wfm_net_free((wfm_net_t*)o); }
-  int export_lists(wfm_handle_t* h, void* o) override { return wfm_net_export(h, (wfm_net_t*)o, &blocks, &n_blocks, &recs, &n_recs); }
-  int import_lists(wfm_handle_t* h, void* o) override { return wfm_net_import(h, (wfm_net_t*)o, blocks, n_blocks, recs, n_recs); }
-  void free_lists() override { wfm_net_free_list(blocks); wfm_net_free_list(recs); }
-  void finish() override {
-    const auto t0 = Clock::now();
-    wfm_net_piece_t* pieces = nullptr;
-    wfm_netcall_t* per = nullptr;
-    size_t n_pieces = 0, n_rec = 0;
-    uint64_t counts[6] = {0, 0, 0, 0, 0, 0};
-    merge();
-    if (!objects.empty()) {
-      std::lock_guard<std::mutex> lk(wflign::handle_lock(h0()));
-      if (wfm_net_table(h0(), first<wfm_net_t>(), &pieces, &n_pieces, &per, &n_rec) != WFM_OK) fail(h0(), "table");
-      wfm_net_counts(first<wfm_net_t>(), counts);
-    }
-    const auto t1 = Clock::now();
-    static_assert(sizeof(chain::Piece) == sizeof(wfm_net_piece_t) && sizeof(chain::NetCall) == sizeof(wfm_netcall_t), "chain_text.hpp restates wfm_net_piece_t and wfm_netcall_t");
-    std::sort(heads.begin(), heads.end(), [](const wflign::NetHead& a, const wflign::NetHead& b) { return a.order < b.order; });
-    uint64_t chains = 0, lost = 0;
-    const bool same = chain::net_file(out, heads, (const chain::NetCall*)per, n_rec, (const chain::Piece*)pieces, &chains, &lost);
-    wfm_net_free_list(pieces); wfm_net_free_list(per);
-    if (!same) throw std::runtime_error("[wfmash::align] --chain-net: the table's records are not the records added");
-    wflign::switch_finished(id, chains, n_pieces, lost);
-    if (getenv("WFM_DEBUG"))
-      fprintf(stderr, "[wfmash::align] chain-net: %zu objects merged, %llu records, %llu blocks, %llu elementary intervals, %zu pieces, %llu chains, %llu records won nothing, merge + table %.1f ms, text %.1f ms\n",
-              objects.size(), (unsigned long long)counts[0], (unsigned long long)counts[1], (unsigned long long)counts[2], n_pieces, (unsigned long long)chains,
-              (unsigned long long)lost, std::chrono::duration<double, std::milli>(t1 - t0).count(), ms_since(t1));
-  }
-};
-
-// --transitive: the world and the seeds in input order are known before anything is aligned; the trans objects; the closure of the seeds
-// over their merge taken once on the device, the file through transitive_text.hpp in the order of the BED's lines
-struct TransitivePass : Pass {
-  TransitivePass(wflign::RunTables& tb, const wflign::SwitchSetting& s)
-      : Pass(wflign::SW_TRANSITIVE, "--transitive", true, tb, s.out, "the transitive file"), depth((uint32_t)s.option) {
-    world = transitive::make_world(tb.tnames, tb.tlengths, tb.qnames, tb.qlengths);
-    if (world.n_bases() >= ((uint64_t)1 << 40)) throw std::runtime_error("[wfmash::align] --transitive: the sequences hold 2^40 bases or more");
-    for (const std::string& name : tb.qnames) tb.query_world.push_back(world.offsets[(size_t)world.find(name)]);
-    seeds = transitive::parse_seeds(read_whole_file(s.bed, "the BED file of --transitive"), world);
-    if (seeds.iv.size() >= ((size_t)1 << 24)) throw std::runtime_error("[wfmash::align] --transitive: the BED holds 2^24 seeds or more");
-  }
-  transitive::World world;
-  lift::Bed seeds;
-  const uint32_t depth;
-  wfm_trans_rec_t* recs = nullptr;
-  wfm_trans_word_t* words = nullptr;
-  size_t n_recs = 0, n_words = 0;
-  int create(wfm_handle_t* h, void** o) override {
-    wfm_trans_t* p = nullptr;
-    const int rc = wfm_trans_create(h, world.n_bases(), &p);
-    *o = p;
-    return rc;
-  }
-  void destroy(void* o) override { wfm_trans_free((wfm_trans_t*)o); }
-  int export_lists(wfm_handle_t* h, void* o) override { return wfm_trans_export(h, (wfm_trans_t*)o, &recs, &n_recs, &words, &n_words); }
-  int import_lists(wfm_handle_t* h, void* o) override { return wfm_trans_import(h, (wfm_trans_t*)o, recs, n_recs, words, n_words); }
-  void free_lists() override { wfm_trans_free_list(recs); wfm_trans_free_list(words); }
-  void finish() override {
-    const auto t0 = Clock::now();
-    wfm_trans_iv_t* ivs = nullptr;
-    size_t n_ivs = 0;
-    std::vector<wfm_trans_seed_t> per(seeds.iv.size());
-    uint64_t counts[6] = {0, 0, 0, 0, 0, 0};
-    if (!objects.empty() && !seeds.iv.empty()) {
-      merge();
-      const std::vector<wfm_lift_iv_t> raw = raw_intervals(seeds.iv);
-      std::lock_guard<std::mutex> lk(wflign::handle_lock(h0()));
-      if (wfm_trans_closure(h0(), first<wfm_trans_t>(), raw.data(), raw.size(), depth, &ivs, &n_ivs, per.data()) != WFM_OK) fail(h0(), "closure");
-      wfm_trans_counts(first<wfm_trans_t>(), counts);
-    }
-    const auto t1 = Clock::now();
-    static_assert(sizeof(transitive::ClosureIv) == sizeof(wfm_trans_iv_t) && sizeof(transitive::SeedCall) == sizeof(wfm_trans_seed_t),
-                  "transitive_text.hpp restates wfm_trans_iv_t and wfm_trans_seed_t");
-    const uint64_t lines = transitive::file(out, world, seeds.iv, (const transitive::SeedCall*)per.data(), (const transitive::ClosureIv*)ivs);
-    wfm_trans_free_list(ivs);
-    wflign::switch_finished(id, lines, counts[3], seeds.skipped);
-    if (getenv("WFM_DEBUG"))
-      fprintf(stderr, "[wfmash::align] transitive: %zu objects merged, %llu records, %llu prefix words, %zu seeds at depth %u, %llu rounds, %llu pairs, %zu intervals, %llu lines, merge + closure %.1f ms, text %.1f ms\n",
-              objects.size(), (unsigned long long)counts[0], (unsigned long long)counts[1], seeds.iv.size(), depth, (unsigned long long)counts[3],
-              (unsigned long long)counts[5], n_ivs, (unsigned long long)lines, std::chrono::duration<double, std::milli>(t1 - t0).count(), ms_since(t1));
-  }
-};
-
-// the passes in their order: wflign::SwitchId's first N_PASSES
-template <class P>
-Pass* make_pass(wflign::RunTables& tb, const wflign::SwitchSetting& s) { return new P(tb, s); }
-Pass* (*const kMakePass[wflign::N_PASSES])(wflign::RunTables&, const wflign::SwitchSetting&) = {
-    make_pass<VariantsPass>, make_pass<CoveragePass>, make_pass<LiftPass>,     make_pass<ChainPass>,
-    make_pass<PavPass>,      make_pass<GenotypesPass>, make_pass<ChainNetPass>, make_pass<TransitivePass>,
-    make_pass<MafPass>};
 }  // namespace
 
 struct Aligner::Run {
   Run(const Parameters& p, const RunPlan& pl, size_t n_gpu, Clock::time_point start, std::ifstream& i, std::ofstream& o)
-      : param(p), plan(pl), ngpu(n_gpu), t0(start), in(i), writer(TextSink{&o}), in_flight(n_gpu), first_taken(n_gpu), use(pl.nworkers, nullptr),
+      : param(p), plan(pl), ngpu(n_gpu), t0(start), in(i), writer(wflign::TextSink{&o}), in_flight(n_gpu), first_taken(n_gpu), use(pl.nworkers, nullptr),
         part(pl.nworkers), threads_each(std::max(1, p.threads / (int)pl.nworkers)) {
     for (auto& a : in_flight) a.store(0);
     for (auto& a : first_taken) a.store(0);
@@ -918,10 +536,11 @@ struct Aligner::Run {
   const size_t ngpu;
   const Clock::time_point t0;
   std::ifstream& in;
-  TextWriter writer;
+  wflign::TextWriter writer;
   // the passes that are on, in their order, and the tables they share (filled before the first of them is made)
   wflign::RunTables tables;
-  std::vector<std::unique_ptr<Pass>> passes;
+  std::vector<std::unique_ptr<std::ofstream>> pass_files;  // (each outlives its pass)
+  std::vector<std::unique_ptr<wflign::Pass>> passes;
   // a batch's view of them: the handle's objects, each made at the handle's first batch
   wflign::BatchPasses batch_passes(wfm_handle_t* h, uint64_t seq) {
     wflign::BatchPasses bp;
@@ -1066,23 +685,23 @@ void Aligner::sum_up(Summary& sum, const std::vector<Summary>& part, std::chrono
   for (const Summary& p : part) sum.ms_gpu = std::max(sum.ms_gpu, p.ms_gpu);
 }
 
-// the passes whose switches are on, each with its file open and what it reads read; the run's tables before the first of them
+// the passes whose switches are on, each with its file open and the BED it reads read; the run's tables before the first of them
 void Aligner::make_passes(Run& run) const {
+  static const char* const kNames[wflign::N_PASSES] = {"variants", "coverage", "lift", "chain", "pav", "genotypes", "chain-net", "transitive", "maf"};
   for (int id = 0; id < wflign::N_PASSES; ++id) {
     const wflign::SwitchSetting s = wflign::switch_setting((wflign::SwitchId)id);
     if (s.out.empty()) continue;
-    wflign::RunTables& tb = run.tables;
-    if (run.passes.empty()) {
-      tb.seq_offsets.assign(1, 0);
-      for (int i = 0; i < ref->nseq(); ++i) {
-        tb.tnames.push_back(ref->name(i));
-        tb.tlengths.push_back((uint64_t)ref->length(i));
-        tb.seq_offsets.push_back(tb.seq_offsets.back() + tb.tlengths.back());
-      }
-      for (int i = 0; i < query->nseq(); ++i) { tb.qnames.push_back(query->name(i)); tb.qlengths.push_back((uint64_t)query->length(i)); }
-      tb.find_target = [this](const std::string& name) { return ref->find(name); };
-    }
-    run.passes.emplace_back(kMakePass[id](tb, s));
+    if (run.passes.empty()) wflign::fill_tables(run.tables, *ref, *query);
+    const std::string name = kNames[id];
+    run.pass_files.emplace_back(new std::ofstream());
+    open_or_throw(*run.pass_files.back(), s.out, ("the " + name + " file").c_str());
+    wflign::PassInput in;
+    in.prefix = "[wfmash::align] --" + name + ":";
+    in.out = run.pass_files.back().get();
+    in.has_bed = !s.bed.empty();
+    if (in.has_bed) in.bed = read_whole_file(s.bed, ("the BED file of --" + name).c_str());
+    in.option = s.option;
+    run.passes.push_back(wflign::make_pass((wflign::SwitchId)id, run.tables, in));
   }
 }
 
@@ -1116,7 +735,12 @@ Summary Aligner::compute() {
     for (auto& t : threads) t.join();
   }
   if (run.failed.load()) throw std::runtime_error(run.first_error);
-  for (auto& p : run.passes) { p->finish(); p->out.close(); }  // (the files the workers did not write, each from its handles' objects merged into one)
+  for (size_t k = 0; k < run.passes.size(); ++k) {  // (the files the workers did not write, each from its handles' objects merged into one)
+    const wflign::Pass::Finished end = run.passes[k]->finish();
+    wflign::switch_finished(run.passes[k]->id, end.c[0], end.c[1], end.c[2]);
+    if (!end.debug.empty()) fputs(end.debug.c_str(), stderr);
+    run.pass_files[k]->close();
+  }
   sum_up(sum, run.part, t0);
   outstream.close();
   sum.ms_total = ms_since(t0);

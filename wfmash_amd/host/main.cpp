@@ -233,6 +233,18 @@ static void usage() {
           "            -B DIR directory of the hand-off file [cwd]   -Z keep the hand-off file   --quiet (no effect)\n");
 }
 
+// A mode that works on an existing PAF and runs nothing else: a handle on the device for call(h) -> WFM_*, the handle's message under the
+// mode's tag where that fails.  The exit status: 0, `failed`, or 2 without a device.
+template <class Call>
+static int offline_mode(int device, const char* tag, Call call, int failed = 2) {
+  wfm_handle_t* h = nullptr;
+  if (wfm_create(device, &h) != WFM_OK) { fprintf(stderr, "[wfmash] ERROR: no usable MI355X device %d (there is no CPU fallback)\n", device); return 2; }
+  const int rc = call(h);
+  if (rc != WFM_OK) fprintf(stderr, "[wfmash::%s] ERROR: %s\n", tag, wfm_last_error(h));
+  wfm_destroy(h);
+  return rc == WFM_OK ? 0 : failed;
+}
+
 int main(int argc, char** argv) {
   wfmh_align_params_t ap;
   wfmh_align_default_params(&ap);
@@ -496,73 +508,38 @@ int main(int argc, char** argv) {
     return 1;
   }
   if (!ani_matrix_out.empty() && !verify_in.empty()) { fprintf(stderr, "[wfmash] ERROR: --ani-matrix cannot be combined with --verify-paf\n"); return 1; }
-  if (!pav_in.empty()) {  // the presence table of an existing PAF; nothing else runs
-    wfm_handle_t* hp = nullptr;
-    if (wfm_create(device, &hp) != WFM_OK) { fprintf(stderr, "[wfmash] ERROR: no usable MI355X device %d (there is no CPU fallback)\n", device); return 2; }
-    uint64_t pc[4] = {0, 0, 0, 0};
-    const int prc = wfmh_pav_paf(hp, target.c_str(), query.empty() ? nullptr : query.c_str(), pav_in.c_str(), pav_bed.empty() ? nullptr : pav_bed.c_str(), pav_window,
-                                 pav_out.c_str(), pc);
-    if (prc != WFM_OK) fprintf(stderr, "[wfmash::pav] ERROR: %s\n", wfm_last_error(hp));
-    wfm_destroy(hp);
-    return prc == WFM_OK ? 0 : 2;
-  }
-  if (!maf_in.empty()) {  // the MAF file of an existing PAF; nothing else runs
-    wfm_handle_t* hm = nullptr;
-    if (wfm_create(device, &hm) != WFM_OK) { fprintf(stderr, "[wfmash] ERROR: no usable MI355X device %d (there is no CPU fallback)\n", device); return 2; }
-    uint64_t mc[4] = {0, 0, 0, 0};
-    const int mrc = wfmh_maf_paf(hm, target.c_str(), query.empty() ? nullptr : query.c_str(), maf_in.c_str(), maf_out.c_str(), (uint32_t)std::max<int64_t>(0, maf_split), mc);
-    if (mrc != WFM_OK) fprintf(stderr, "[wfmash::maf] ERROR: %s\n", wfm_last_error(hm));
-    wfm_destroy(hm);
-    return mrc == WFM_OK ? 0 : 2;
-  }
-  if (!chain_in.empty()) {  // the chain file of an existing PAF; nothing else runs
-    wfm_handle_t* hc = nullptr;
-    if (wfm_create(device, &hc) != WFM_OK) { fprintf(stderr, "[wfmash] ERROR: no usable MI355X device %d (there is no CPU fallback)\n", device); return 2; }
-    uint64_t cc[4] = {0, 0, 0, 0};
-    int crc = chain_out.empty() ? WFM_OK : wfmh_chain_paf(hc, target.c_str(), chain_in.c_str(), chain_out.c_str(), chain_swap ? 1 : 0, cc);
-    if (crc == WFM_OK && !chain_net_out.empty()) crc = wfmh_chain_net_paf(hc, target.c_str(), chain_in.c_str(), chain_net_out.c_str(), cc);
-    if (crc != WFM_OK) fprintf(stderr, "[wfmash::chain] ERROR: %s\n", wfm_last_error(hc));
-    wfm_destroy(hc);
-    return crc == WFM_OK ? 0 : 2;
-  }
-  if (!trans_in.empty()) {  // the seeds closed over an existing PAF; nothing else runs
-    wfm_handle_t* ht = nullptr;
-    if (wfm_create(device, &ht) != WFM_OK) { fprintf(stderr, "[wfmash] ERROR: no usable MI355X device %d (there is no CPU fallback)\n", device); return 2; }
-    uint64_t tc[4] = {0, 0, 0, 0};
-    const int trc = wfmh_transitive_paf(ht, target.c_str(), query.empty() ? nullptr : query.c_str(), trans_in.c_str(), trans_bed.c_str(), trans_out.c_str(),
-                                        (uint32_t)trans_depth, tc);
-    if (trc != WFM_OK) fprintf(stderr, "[wfmash::transitive] ERROR: %s\n", wfm_last_error(ht));
-    wfm_destroy(ht);
-    return trc == WFM_OK ? 0 : 2;
-  }
-  if (!lift_in.empty()) {  // the BED through an existing PAF; nothing else runs
-    wfm_handle_t* hl = nullptr;
-    if (wfm_create(device, &hl) != WFM_OK) { fprintf(stderr, "[wfmash] ERROR: no usable MI355X device %d (there is no CPU fallback)\n", device); return 2; }
-    uint64_t lc[4] = {0, 0, 0, 0};
-    const int lrc = wfmh_lift_paf(hl, target.c_str(), lift_in.c_str(), lift_bed.c_str(), lift_out.c_str(), lc);
-    if (lrc != WFM_OK) fprintf(stderr, "[wfmash::lift] ERROR: %s\n", wfm_last_error(hl));
-    wfm_destroy(hl);
-    return lrc == WFM_OK ? 0 : 2;
-  }
-  if (!coverage_in.empty()) {  // the depth of an existing PAF; nothing else runs
-    wfm_handle_t* hc = nullptr;
-    if (wfm_create(device, &hc) != WFM_OK) { fprintf(stderr, "[wfmash] ERROR: no usable MI355X device %d (there is no CPU fallback)\n", device); return 2; }
-    uint64_t cc[4] = {0, 0, 0, 0};
-    const int crc = wfmh_coverage_paf(hc, target.c_str(), coverage_in.c_str(), coverage_out.c_str(), cc);
-    if (crc != WFM_OK) fprintf(stderr, "[wfmash::coverage] ERROR: %s\n", wfm_last_error(hc));
-    wfm_destroy(hc);
-    return crc == WFM_OK ? 0 : 2;
-  }
-  if (!verify_in.empty()) {  // an existing PAF against its sequences; nothing else runs
-    wfm_handle_t* hv = nullptr;
-    if (wfm_create(device, &hv) != WFM_OK) { fprintf(stderr, "[wfmash] ERROR: no usable MI355X device %d (there is no CPU fallback)\n", device); return 2; }
-    uint64_t vc[4] = {0, 0, 0, 0};
-    const int vrc = wfmh_verify_paf(hv, target.c_str(), query.empty() ? nullptr : query.c_str(), verify_in.c_str(), vc);
-    if (vrc != WFM_OK) fprintf(stderr, "[wfmash::verify] ERROR: %s\n", wfm_last_error(hv));
-    else fprintf(stderr, "[wfmash::verify] %llu lines checked, %llu failed, %llu unverifiable, %llu bases compared\n", (unsigned long long)vc[0],
-                 (unsigned long long)vc[1], (unsigned long long)vc[2], (unsigned long long)vc[3]);
-    wfm_destroy(hv);
-    return vrc == WFM_OK && vc[1] == 0 ? 0 : 3;
+  const char* const query_or_null = query.empty() ? nullptr : query.c_str();
+  uint64_t oc[4] = {0, 0, 0, 0};  // (what a mode counted: only --verify-paf reads it)
+  if (!pav_in.empty())  // the presence table of an existing PAF; nothing else runs
+    return offline_mode(device, "pav", [&](wfm_handle_t* h) {
+      return wfmh_pav_paf(h, target.c_str(), query_or_null, pav_in.c_str(), pav_bed.empty() ? nullptr : pav_bed.c_str(), pav_window, pav_out.c_str(), oc);
+    });
+  if (!maf_in.empty())  // the MAF file of an existing PAF; nothing else runs
+    return offline_mode(device, "maf", [&](wfm_handle_t* h) {
+      return wfmh_maf_paf(h, target.c_str(), query_or_null, maf_in.c_str(), maf_out.c_str(), (uint32_t)std::max<int64_t>(0, maf_split), oc);
+    });
+  if (!chain_in.empty())  // the chain file of an existing PAF; nothing else runs
+    return offline_mode(device, "chain", [&](wfm_handle_t* h) {
+      const int rc = chain_out.empty() ? WFM_OK : wfmh_chain_paf(h, target.c_str(), chain_in.c_str(), chain_out.c_str(), chain_swap ? 1 : 0, oc);
+      return rc == WFM_OK && !chain_net_out.empty() ? wfmh_chain_net_paf(h, target.c_str(), chain_in.c_str(), chain_net_out.c_str(), oc) : rc;
+    });
+  if (!trans_in.empty())  // the seeds closed over an existing PAF; nothing else runs
+    return offline_mode(device, "transitive", [&](wfm_handle_t* h) {
+      return wfmh_transitive_paf(h, target.c_str(), query_or_null, trans_in.c_str(), trans_bed.c_str(), trans_out.c_str(), (uint32_t)trans_depth, oc);
+    });
+  if (!lift_in.empty())  // the BED through an existing PAF; nothing else runs
+    return offline_mode(device, "lift", [&](wfm_handle_t* h) { return wfmh_lift_paf(h, target.c_str(), lift_in.c_str(), lift_bed.c_str(), lift_out.c_str(), oc); });
+  if (!coverage_in.empty())  // the depth of an existing PAF; nothing else runs
+    return offline_mode(device, "coverage", [&](wfm_handle_t* h) { return wfmh_coverage_paf(h, target.c_str(), coverage_in.c_str(), coverage_out.c_str(), oc); });
+  if (!verify_in.empty()) {  // an existing PAF against its sequences; nothing else runs: 3 if a line failed or the check could not run
+    const int code = offline_mode(device, "verify", [&](wfm_handle_t* h) {
+      const int rc = wfmh_verify_paf(h, target.c_str(), query_or_null, verify_in.c_str(), oc);
+      if (rc == WFM_OK)
+        fprintf(stderr, "[wfmash::verify] %llu lines checked, %llu failed, %llu unverifiable, %llu bases compared\n", (unsigned long long)oc[0], (unsigned long long)oc[1],
+                (unsigned long long)oc[2], (unsigned long long)oc[3]);
+      return rc;
+    }, 3);
+    return code == 0 && oc[1] != 0 ? 3 : code;
   }
   if (approx_only && !mapping_in.empty()) { fprintf(stderr, "[wfmash] ERROR: -m and -i exclude each other\n"); return 1; }
   if (!seeds_in.empty() && !mapping_in.empty()) { fprintf(stderr, "[wfmash] ERROR: -K (external seeds) and -i (align mappings from a file) exclude each other\n"); return 1; }

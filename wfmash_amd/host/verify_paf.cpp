@@ -16,13 +16,9 @@
 #include "../csrc/wfa_handle.h"
 #include "aligner.hpp"
 #include "coverage_text.hpp"
-#include "lift_text.hpp"
-#include "transitive_text.hpp"
-#include "chain_text.hpp"
 #include "maf_text.hpp"
-#include "pav_text.hpp"
 #include "parallel.hpp"
-#include "wflign_hip.hpp"
+#include "run_passes.hpp"
 
 namespace verify {
 
@@ -275,62 +271,53 @@ Counts total_counts() {
 }  // namespace verify
 
 namespace {
-// What --coverage-paf, --lift-paf and --pav-paf share: the target's offsets in the concatenation, the lines of an aligned PAF read and
-// skipped by one rule (coverage::classify_line), their runs gathered into batches of 65536 problems or 16 Mi runs, and device calls
-// that throw.  An entry point supplies what it keeps per line and what a batch is flushed into.
-struct PafRuns {
-  wfm_handle_t* h;
-  const char* tag;                      // "coverage", "lift", "pav": the [wfmash::...] of the texts
-  const wfmash_host::FastaStore& target;
-  std::vector<std::string> names;
-  std::vector<uint64_t> lengths, offsets;
-  uint64_t skipped[5] = {0, 0, 0, 0, 0};  // by coverage::LINE_*
-  std::vector<wfm_cov_prob_t> probs;    // the batch at hand: base, runs_off, n_runs of every line
-  std::vector<uint32_t> runs;
-
-  PafRuns(wfm_handle_t* h_, const char* tag_, const wfmash_host::FastaStore& target_) : h(h_), tag(tag_), target(target_), offsets(1, 0) {
-    for (int i = 0; i < target.nseq(); ++i) {
-      names.push_back(target.name(i));
-      lengths.push_back((uint64_t)target.length(i));
-      offsets.push_back(offsets.back() + lengths.back());
-    }
+// What --verify-paf and --maf-paf share: the two files (the query's only where it is another), the source of the bases, the PAF open, and
+// its text in chunks of 64 MiB of whole lines.  tag: the [wfmash::...] of "cannot open".
+struct PafText {
+  std::shared_ptr<wfmash_host::FastaStore> target, query_own;
+  verify::Source src;
+  std::ifstream in;
+  PafText(const char* tag, const char* target_fasta, const char* query_fasta, const char* aligned_paf) {
+    target = wfmash_host::open_shared(target_fasta);
+    const std::string qpath = query_fasta ? query_fasta : target_fasta;
+    if (qpath != target_fasta) query_own = wfmash_host::open_shared(qpath);
+    src.target = target.get();
+    src.query = query_own ? query_own.get() : target.get();
+    src.threads = (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+    in.open(aligned_paf);
+    if (!in.is_open()) throw std::runtime_error(std::string("[wfmash::") + tag + "] cannot open " + aligned_paf);
   }
-  int device(int rc, const char* what) const {
-    if (rc < 0) throw std::runtime_error(std::string("[wfmash::") + tag + "] " + what + " failed: " + wfm_last_error(h));
-    return rc;
-  }
-  void refused(uint64_t n) { skipped[coverage::LINE_MALFORMED] += n; }  // (a span that leaves the target: classify_line lets none through)
-  uint64_t all_skipped() const { return skipped[1] + skipped[2] + skipped[3] + skipped[4]; }
-  // "N skipped (... without an =XID cg:Z:, ... malformed, ...)" of the summaries; no_query: the lines the caller left out for their query
-  std::string skipped_clause(const char* noun = "", const uint64_t* no_query = nullptr) const {
-    std::string s = std::to_string(all_skipped() + (no_query ? *no_query : 0)) + " " + noun + "skipped (" + std::to_string(skipped[1]) + " without an =XID cg:Z:, " +
-                    std::to_string(skipped[2]) + " malformed, " + std::to_string(skipped[3]) + " with an unknown target, " + std::to_string(skipped[4]) + " with another tlen";
-    if (no_query) s += ", " + std::to_string(*no_query) + " with an unknown query";
-    return s + ")";
-  }
-  // extra(line) -> false: the line is not taken (the caller counts it); flush(): the batch to the device, whatever extra kept given back
-  template <class Extra, class Flush>
-  void read(std::istream& in, Extra extra, Flush flush) {
-    auto flush_batch = [&]() {
-      if (probs.empty()) return;
-      flush();
-      probs.clear(); runs.clear();
-    };
-    std::string line;
-    verify::Line l;
+  template <class Chunk>
+  void chunks(Chunk chunk) {
+    std::string text, line;
     while (std::getline(in, line)) {
-      if (line.empty() || line[0] == '@') continue;
-      int ti = -1;
-      const int code = coverage::classify_line(line, [&](const std::string& name) { return target.find(name); }, lengths, l, &ti);
-      if (code != coverage::LINE_ADD) { skipped[code]++; continue; }
-      if (!extra(l)) continue;
-      probs.push_back(wfm_cov_prob_t{offsets[(size_t)ti] + (uint64_t)l.ts, (uint64_t)runs.size(), (uint32_t)l.runs.size(), 0u});
-      runs.insert(runs.end(), l.runs.begin(), l.runs.end());
-      if (probs.size() >= 65536 || runs.size() >= ((size_t)16 << 20)) flush_batch();
+      text += line; text += '\n';
+      if (text.size() >= ((size_t)64 << 20)) { chunk(text); text.clear(); }
     }
-    flush_batch();
+    chunk(text);
   }
 };
+
+// a --*-paf entry point's body: what it throws is printed, left as the handle's error and returned as WFM_E_ARG
+template <class Body>
+int guarded(wfm_handle_t* h, Body body) {
+  try {
+    body();
+    return WFM_OK;
+  } catch (const std::exception& e) {
+    std::cerr << e.what() << std::endl;
+    wfm_set_error(h, e.what());
+    return WFM_E_ARG;
+  }
+}
+
+// "N skipped (... without an =XID cg:Z:, ... malformed, ...)" of the summaries; with_query: the lines left out for their query as well
+std::string skipped_clause(const wflign::PafPassResult& r, const char* noun = "", bool with_query = false) {
+  std::string s = std::to_string(r.all_skipped() + r.no_query) + " " + noun + "skipped (" + std::to_string(r.skipped[1]) + " without an =XID cg:Z:, " +
+                  std::to_string(r.skipped[2]) + " malformed, " + std::to_string(r.skipped[3]) + " with an unknown target, " + std::to_string(r.skipped[4]) + " with another tlen";
+  if (with_query) s += ", " + std::to_string(r.no_query) + " with an unknown query";
+  return s + ")";
+}
 }  // namespace
 
 extern "C" {
@@ -346,30 +333,12 @@ int wfmh_verify_counts(uint64_t out[4]) {
 
 int wfmh_verify_paf(wfm_handle_t* h, const char* target_fasta, const char* query_fasta, const char* aligned_paf, uint64_t out[4]) {
   if (!h || !target_fasta || !aligned_paf) return WFM_E_ARG;
-  try {
-    std::shared_ptr<wfmash_host::FastaStore> target = wfmash_host::open_shared(target_fasta), query_own;
-    const std::string qpath = query_fasta ? query_fasta : target_fasta;
-    if (qpath != target_fasta) query_own = wfmash_host::open_shared(qpath);
-    verify::Source src;
-    src.target = target.get();
-    src.query = query_own ? query_own.get() : target.get();
-    src.threads = (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
-    std::ifstream in(aligned_paf);
-    if (!in.is_open()) throw std::runtime_error(std::string("[wfmash::verify] cannot open ") + aligned_paf);
+  return guarded(h, [&] {
+    PafText paf("verify", target_fasta, query_fasta, aligned_paf);
     verify::Counts c;
-    std::string text, line;
-    while (std::getline(in, line)) {
-      text += line; text += '\n';
-      if (text.size() >= ((size_t)64 << 20)) { verify::verify_text(h, src, text, c); text.clear(); }
-    }
-    verify::verify_text(h, src, text, c);
+    paf.chunks([&](const std::string& text) { verify::verify_text(h, paf.src, text, c); });
     if (out) { out[0] = c.checked; out[1] = c.failed; out[2] = c.unverifiable; out[3] = c.bases; }
-    return WFM_OK;
-  } catch (const std::exception& e) {
-    std::cerr << e.what() << std::endl;
-    wfm_set_error(h, e.what());
-    return WFM_E_ARG;
-  }
+  });
 }
 
 // --maf-paf: the MAF file of an existing aligned PAF, lines parsed as --verify-paf parses them and their windows uploaded as it uploads
@@ -378,404 +347,93 @@ int wfmh_verify_paf(wfm_handle_t* h, const char* target_fasta, const char* query
 int wfmh_maf_paf(wfm_handle_t* h, const char* target_fasta, const char* query_fasta, const char* aligned_paf, const char* out_path, uint32_t split,
                  uint64_t out[4]) {
   if (!h || !target_fasta || !aligned_paf || !out_path) return WFM_E_ARG;
-  try {
-    std::shared_ptr<wfmash_host::FastaStore> target = wfmash_host::open_shared(target_fasta), query_own;
-    const std::string qpath = query_fasta ? query_fasta : target_fasta;
-    if (qpath != target_fasta) query_own = wfmash_host::open_shared(qpath);
-    verify::Source src;
-    src.target = target.get();
-    src.query = query_own ? query_own.get() : target.get();
-    src.threads = (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
-    std::ifstream in(aligned_paf);
-    if (!in.is_open()) throw std::runtime_error(std::string("[wfmash::maf] cannot open ") + aligned_paf);
+  return guarded(h, [&] {
+    PafText paf("maf", target_fasta, query_fasta, aligned_paf);
     std::ofstream outstream(out_path);
     if (!outstream.is_open()) throw std::runtime_error(std::string("[wfmash::maf] cannot open ") + out_path);
     outstream << maf::header();
     uint64_t counts[4] = {0, 0, 0, 0}, skipped[4] = {0, 0, 0, 0};
-    std::string text, line;
-    while (std::getline(in, line)) {
-      text += line; text += '\n';
-      if (text.size() >= ((size_t)64 << 20)) { verify::maf_text(h, src, text, split, outstream, counts, skipped); text.clear(); }
-    }
-    verify::maf_text(h, src, text, split, outstream, counts, skipped);
+    paf.chunks([&](const std::string& text) { verify::maf_text(h, paf.src, text, split, outstream, counts, skipped); });
     std::cerr << "[wfmash::maf] " << counts[0] << " records, " << counts[1] << " blocks, " << counts[2] << " columns, " << counts[3] << " records left without blocks, "
               << (skipped[0] + skipped[1] + skipped[2] + skipped[3]) << " lines skipped (" << skipped[0] << " without an =XID cg:Z:, " << skipped[1] << " malformed, "
               << skipped[2] << " with an unknown sequence, " << skipped[3] << " with another length)" << std::endl;
     if (out) for (int q = 0; q < 4; ++q) out[q] = counts[q];
-    return WFM_OK;
-  } catch (const std::exception& e) {
-    std::cerr << e.what() << std::endl;
-    wfm_set_error(h, e.what());
-    return WFM_E_ARG;
-  }
+  });
 }
 
-// --coverage-paf: the depth of an existing aligned PAF.  Lines go to the device in batches of runs; nothing else runs.
+// ---- the modes that make an across-record output of an existing aligned PAF: the lines are the second source of packed runs for the
+// pass and the stage the align driver has (run_passes.hpp: run_paf_pass); nothing else runs.  Here: the argument checks, the summary, out[4]. ----
+using wflign::PafPassCall;
+using wflign::PafPassResult;
+
+// --coverage-paf: the depth of an existing aligned PAF
 int wfmh_coverage_paf(wfm_handle_t* h, const char* target_fasta, const char* aligned_paf, const char* out_path, uint64_t out[4]) {
   if (!h || !target_fasta || !aligned_paf || !out_path) return WFM_E_ARG;
-  wfm_coverage_t* cov = nullptr;
-  try {
-    std::shared_ptr<wfmash_host::FastaStore> target = wfmash_host::open_shared(target_fasta);
-    std::ifstream in(aligned_paf);
-    if (!in.is_open()) throw std::runtime_error(std::string("[wfmash::coverage] cannot open ") + aligned_paf);
-    std::ofstream outstream(out_path);
-    if (!outstream.is_open()) throw std::runtime_error(std::string("[wfmash::coverage] cannot open ") + out_path);
-    PafRuns pr(h, "coverage", *target);
-    std::lock_guard<std::mutex> lk(wflign::handle_lock(h));
-    pr.device(wfm_coverage_create(h, pr.offsets.back(), &cov), "create");
-    uint64_t added = 0;
-    std::vector<uint32_t> flags;
-    pr.read(in, [](const verify::Line&) { return true; }, [&]() {
-      flags.resize(pr.probs.size());
-      const int refused = pr.device(wfm_coverage_add(h, cov, pr.probs.data(), pr.probs.size(), pr.runs.data(), pr.runs.size(), flags.data()), "add");
-      added += pr.probs.size() - (uint64_t)refused;
-      pr.refused((uint64_t)refused);
-    });
-    wfm_cov_interval_t* d_iv = nullptr;
-    size_t n = 0;
-    uint64_t totals[3] = {0, 0, 0};
-    pr.device(wfm_coverage_intervals(h, cov, &d_iv, &n, totals), "intervals");
-    wfm_coverage_free(cov);
-    cov = nullptr;
-    uint64_t lines = 0;
-    outstream << coverage::coverage_bedgraph(pr.names, pr.lengths, d_iv, n, &lines);
-    wfm_coverage_free_list(d_iv);
-    std::cerr << "[wfmash::coverage] " << added << " lines added, " << pr.skipped_clause() << ", " << totals[0] << " bases covered, sum of depth " << totals[1]
-              << ", max depth " << totals[2] << ", " << lines << " intervals" << std::endl;
-    if (out) { out[0] = added; out[1] = pr.all_skipped(); out[2] = totals[0]; out[3] = totals[1]; }
-    return WFM_OK;
-  } catch (const std::exception& e) {
-    if (cov) wfm_coverage_free(cov);
-    std::cerr << e.what() << std::endl;
-    wfm_set_error(h, e.what());
-    return WFM_E_ARG;
-  }
+  return guarded(h, [&] {
+    const PafPassResult r = wflign::run_paf_pass(h, PafPassCall{wflign::SW_COVERAGE, "coverage", target_fasta, nullptr, aligned_paf, nullptr, out_path, 0});
+    std::cerr << "[wfmash::coverage] " << r.counts[0] << " lines added, " << skipped_clause(r) << ", " << r.end.c[0] << " bases covered, sum of depth " << r.end.c[1]
+              << ", max depth " << r.end.extra << ", " << r.end.c[2] << " intervals" << std::endl;
+    if (out) { out[0] = r.counts[0]; out[1] = r.all_skipped(); out[2] = r.end.c[0]; out[3] = r.end.c[1]; }
+  });
 }
 
-// --lift-paf: the BED intervals lifted through an existing aligned PAF.  Lines go to the device in batches of runs, read and skipped by
-// wfmh_coverage_paf's rules (coverage::classify_line); nothing else runs.
+// --lift-paf: the BED intervals lifted through an existing aligned PAF
 int wfmh_lift_paf(wfm_handle_t* h, const char* target_fasta, const char* aligned_paf, const char* bed_path, const char* out_path, uint64_t out[4]) {
   if (!h || !target_fasta || !aligned_paf || !bed_path || !out_path) return WFM_E_ARG;
-  wfm_liftset_t* set = nullptr;
-  try {
-    std::shared_ptr<wfmash_host::FastaStore> target = wfmash_host::open_shared(target_fasta);
-    std::ifstream in(aligned_paf);
-    if (!in.is_open()) throw std::runtime_error(std::string("[wfmash::lift] cannot open ") + aligned_paf);
-    std::ifstream bedstream(bed_path, std::ios::binary);
-    if (!bedstream.is_open()) throw std::runtime_error(std::string("[wfmash::lift] cannot open ") + bed_path);
-    const std::string bed_text((std::istreambuf_iterator<char>(bedstream)), std::istreambuf_iterator<char>());
-    std::ofstream outstream(out_path);
-    if (!outstream.is_open()) throw std::runtime_error(std::string("[wfmash::lift] cannot open ") + out_path);
-    PafRuns pr(h, "lift", *target);
-    const lift::Bed bed = lift::parse_bed(bed_text, [&](const std::string& name) { return target->find(name); }, pr.lengths, pr.offsets);
-    std::lock_guard<std::mutex> lk(wflign::handle_lock(h));
-    {
-      std::vector<wfm_lift_iv_t> raw(bed.iv.size());
-      for (size_t i = 0; i < raw.size(); ++i) raw[i] = wfm_lift_iv_t{bed.iv[i].gstart, bed.iv[i].gend};
-      pr.device(wfm_liftset_create(h, raw.data(), raw.size(), pr.offsets.back(), &set), "create");
-    }
-    uint64_t lifted = 0, n_lines = 0, empty = 0;
-    std::vector<lift::Record> where;
-    std::vector<wfm_liftcall_t> per;
-    std::string text;
-    auto flush = [&]() {
-      per.resize(pr.probs.size());
-      wfm_lift_t* lifts = nullptr;
-      size_t n = 0;
-      pr.device(wfm_lift_runs(h, set, pr.probs.data(), pr.probs.size(), pr.runs.data(), pr.runs.size(), &lifts, &n, per.data()), "lift");
-      text.clear();
-      for (size_t j = 0; j < pr.probs.size(); ++j) {
-        if (per[j].flags) { pr.refused(1); continue; }
-        ++lifted;
-        for (uint64_t k = per[j].first; k < per[j].first + per[j].count; ++k) {
-          const wfm_lift_t& l = lifts[k];
-          lift::lift_line(text, where[j], bed.iv[l.interval], l.p0, l.p1, l.t0, l.t1, l.eq, l.x);
-          empty += l.eq + l.x == 0;
-        }
-        n_lines += per[j].count;
-      }
-      wfm_free_lifts(lifts);
-      outstream << text;
-      where.clear();
-    };
-    pr.read(in, [&](const verify::Line& l) {
-      lift::Record r;
-      r.qname = l.qname; r.tname = l.tname; r.qs = (uint64_t)l.qs; r.qe = (uint64_t)l.qe; r.ts = (uint64_t)l.ts; r.rev = l.rev;
-      where.push_back(std::move(r));
-      return true;
-    }, flush);
-    wfm_liftset_free(set);
-    set = nullptr;
-    std::cerr << "[wfmash::lift] " << bed.iv.size() << " intervals (" << bed.skipped << " BED lines skipped), " << lifted << " lines lifted, " << pr.skipped_clause()
-              << ", " << n_lines << " lifts written, " << empty << " of them empty" << std::endl;
-    if (out) { out[0] = lifted; out[1] = n_lines; out[2] = empty; out[3] = bed.skipped; }
-    return WFM_OK;
-  } catch (const std::exception& e) {
-    if (set) wfm_liftset_free(set);
-    std::cerr << e.what() << std::endl;
-    wfm_set_error(h, e.what());
-    return WFM_E_ARG;
-  }
+  return guarded(h, [&] {
+    const PafPassResult r = wflign::run_paf_pass(h, PafPassCall{wflign::SW_LIFT, "lift", target_fasta, nullptr, aligned_paf, bed_path, out_path, 0});
+    std::cerr << "[wfmash::lift] " << r.end.extra << " intervals (" << r.end.c[2] << " BED lines skipped), " << r.counts[0] << " lines lifted, " << skipped_clause(r)
+              << ", " << r.counts[1] << " lifts written, " << r.counts[2] << " of them empty" << std::endl;
+    if (out) { out[0] = r.counts[0]; out[1] = r.counts[1]; out[2] = r.counts[2]; out[3] = r.end.c[2]; }
+  });
 }
 
-// --chain-paf: the chain file of an existing aligned PAF.  Lines go to the device in batches of runs, read and skipped by
-// wfmh_coverage_paf's rules (coverage::classify_line); nothing else runs.
+// --chain-paf: the chain file of an existing aligned PAF
 int wfmh_chain_paf(wfm_handle_t* h, const char* target_fasta, const char* aligned_paf, const char* out_path, int swap, uint64_t out[4]) {
   if (!h || !target_fasta || !aligned_paf || !out_path) return WFM_E_ARG;
-  try {
-    std::shared_ptr<wfmash_host::FastaStore> target = wfmash_host::open_shared(target_fasta);
-    std::ifstream in(aligned_paf);
-    if (!in.is_open()) throw std::runtime_error(std::string("[wfmash::chain] cannot open ") + aligned_paf);
-    std::ofstream outstream(out_path);
-    if (!outstream.is_open()) throw std::runtime_error(std::string("[wfmash::chain] cannot open ") + out_path);
-    PafRuns pr(h, "chain", *target);
-    std::lock_guard<std::mutex> lk(wflign::handle_lock(h));
-    uint64_t chains = 0, n_blocks = 0, refused = 0, next = 1;
-    std::vector<chain::Record> where;
-    std::vector<wfm_chain_prob_t> probs;
-    std::vector<wfm_chaincall_t> per;
-    std::string body, text;
-    auto flush = [&]() {
-      probs.resize(pr.probs.size());
-      per.resize(pr.probs.size());
-      for (size_t j = 0; j < probs.size(); ++j) probs[j] = wfm_chain_prob_t{pr.probs[j].runs_off, pr.probs[j].n_runs, chain::flags_of(swap != 0, where[j].rev)};
-      wfm_chain_block_t* blocks = nullptr;
-      size_t n = 0;
-      pr.device(wfm_chain_runs(h, probs.data(), probs.size(), pr.runs.data(), pr.runs.size(), &blocks, &n, per.data()), "chain");
-      body.clear(); text.clear();
-      for (size_t j = 0; j < probs.size(); ++j) {
-        if (per[j].flags) { pr.refused(1); ++refused; continue; }
-        chain::Ends e;
-        e.lead_dt = per[j].lead_dt; e.lead_dq = per[j].lead_dq; e.trail_dt = per[j].trail_dt; e.trail_dq = per[j].trail_dq; e.eq = per[j].eq;
-        chain::chain_body(body, where[j], swap != 0, e, (const chain::Block*)blocks + per[j].first, per[j].count);
-      }
-      wfm_free_chain(blocks);
-      chains += chain::number(body, &next, text);
-      n_blocks += n;
-      outstream << text;
-      where.clear();
-    };
-    pr.read(in, [&](const verify::Line& l) {
-      chain::Record r;
-      r.qname = l.qname; r.tname = l.tname; r.rev = l.rev;
-      r.qsize = (uint64_t)l.qlen; r.qs = (uint64_t)l.qs; r.qe = (uint64_t)l.qe; r.tsize = (uint64_t)l.tlen; r.ts = (uint64_t)l.ts; r.te = (uint64_t)l.te;
-      where.push_back(std::move(r));
-      return true;
-    }, flush);
-    std::cerr << "[wfmash::chain] " << chains << " chains written, " << n_blocks << " blocks, " << pr.skipped_clause("lines ") << std::endl;
-    if (out) { out[0] = chains; out[1] = n_blocks; out[2] = refused; out[3] = 0; }
-    return WFM_OK;
-  } catch (const std::exception& e) {
-    std::cerr << e.what() << std::endl;
-    wfm_set_error(h, e.what());
-    return WFM_E_ARG;
-  }
+  return guarded(h, [&] {
+    const PafPassResult r = wflign::run_paf_pass(h, PafPassCall{wflign::SW_CHAIN, "chain", target_fasta, nullptr, aligned_paf, nullptr, out_path, swap != 0});
+    std::cerr << "[wfmash::chain] " << r.counts[0] << " chains written, " << r.counts[1] << " blocks, " << skipped_clause(r, "lines ") << std::endl;
+    if (out) { out[0] = r.counts[0]; out[1] = r.counts[1]; out[2] = r.counts[2]; out[3] = 0; }
+  });
 }
 
-// --chain-paf with --chain-net: the single-coverage file of an existing aligned PAF.  Lines go to a net object in batches of runs, read and
-// skipped by wfmh_coverage_paf's rules; order = the number of the line among those taken; the table once, at the end.
+// --chain-paf with --chain-net: the single-coverage file of an existing aligned PAF; order = the number of the line among those taken
 int wfmh_chain_net_paf(wfm_handle_t* h, const char* target_fasta, const char* aligned_paf, const char* out_path, uint64_t out[4]) {
   if (!h || !target_fasta || !aligned_paf || !out_path) return WFM_E_ARG;
-  wfm_net_t* net = nullptr;
-  try {
-    std::shared_ptr<wfmash_host::FastaStore> target = wfmash_host::open_shared(target_fasta);
-    std::ifstream in(aligned_paf);
-    if (!in.is_open()) throw std::runtime_error(std::string("[wfmash::chain-net] cannot open ") + aligned_paf);
-    std::ofstream outstream(out_path);
-    if (!outstream.is_open()) throw std::runtime_error(std::string("[wfmash::chain-net] cannot open ") + out_path);
-    PafRuns pr(h, "chain-net", *target);
-    std::lock_guard<std::mutex> lk(wflign::handle_lock(h));
-    pr.device(wfm_net_create(h, pr.offsets.back(), &net), "create");
-    std::vector<chain::Record> where;   // of the batch
-    std::vector<chain::NetHead> kept;   // of every line added, in the order of their orders
-    std::vector<wfm_net_prob_t> probs;
-    std::vector<uint32_t> flags;
-    uint64_t taken = 0;
-    auto flush = [&]() {
-      probs.resize(pr.probs.size());
-      flags.resize(pr.probs.size());
-      for (size_t j = 0; j < probs.size(); ++j) probs[j] = wfm_net_prob_t{pr.probs[j].base, pr.probs[j].runs_off, pr.probs[j].n_runs, WFM_NET_SCORE_EQ, taken + j};
-      const int refused = pr.device(wfm_net_add(h, net, probs.data(), probs.size(), pr.runs.data(), pr.runs.size(), flags.data()), "add");
-      for (size_t j = 0; j < probs.size(); ++j) {
-        if (flags[j]) continue;
-        kept.push_back(chain::NetHead{probs[j].order, pr.probs[j].base - where[j].ts, std::move(where[j])});  // (the base is the sequence's offset + the line's target start)
-      }
-      pr.refused((uint64_t)refused);
-      taken += probs.size();
-      where.clear();
-    };
-    pr.read(in, [&](const verify::Line& l) {
-      chain::Record r;
-      r.qname = l.qname; r.tname = l.tname; r.rev = l.rev;
-      r.qsize = (uint64_t)l.qlen; r.qs = (uint64_t)l.qs; r.qe = (uint64_t)l.qe; r.tsize = (uint64_t)l.tlen; r.ts = (uint64_t)l.ts; r.te = (uint64_t)l.te;
-      where.push_back(std::move(r));
-      return true;
-    }, flush);
-    wfm_net_piece_t* pieces = nullptr;
-    wfm_netcall_t* per = nullptr;
-    size_t n_pieces = 0, n_rec = 0;
-    pr.device(wfm_net_table(h, net, &pieces, &n_pieces, &per, &n_rec), "table");
-    wfm_net_free(net);
-    net = nullptr;
-    static_assert(sizeof(chain::Piece) == sizeof(wfm_net_piece_t) && sizeof(chain::NetCall) == sizeof(wfm_netcall_t), "chain_text.hpp restates wfm_net_piece_t and wfm_netcall_t");
-    uint64_t chains = 0, lost = 0;
-    const bool same = chain::net_file(outstream, kept, (const chain::NetCall*)per, n_rec, (const chain::Piece*)pieces, &chains, &lost);
-    wfm_net_free_list(pieces); wfm_net_free_list(per);
-    if (!same) throw std::runtime_error("[wfmash::chain-net] the table's records are not the lines added");
-    std::cerr << "[wfmash::chain-net] " << n_rec << " lines added, " << chains << " chains written, " << n_pieces << " pieces, " << lost << " lines won nothing, "
-              << pr.skipped_clause("lines ") << std::endl;
-    if (out) { out[0] = n_rec; out[1] = chains; out[2] = n_pieces; out[3] = lost; }
-    return WFM_OK;
-  } catch (const std::exception& e) {
-    if (net) wfm_net_free(net);
-    std::cerr << e.what() << std::endl;
-    wfm_set_error(h, e.what());
-    return WFM_E_ARG;
-  }
+  return guarded(h, [&] {
+    const PafPassResult r = wflign::run_paf_pass(h, PafPassCall{wflign::SW_CHAIN_NET, "chain-net", target_fasta, nullptr, aligned_paf, nullptr, out_path, 0});
+    std::cerr << "[wfmash::chain-net] " << r.counts[0] << " lines added, " << r.end.c[0] << " chains written, " << r.end.c[1] << " pieces, " << r.end.c[2]
+              << " lines won nothing, " << skipped_clause(r, "lines ") << std::endl;
+    if (out) { out[0] = r.counts[0]; out[1] = r.end.c[0]; out[2] = r.end.c[1]; out[3] = r.end.c[2]; }
+  });
 }
 
-// --pav-paf: the presence table of an existing aligned PAF.  Lines go to the device in batches of runs, read and skipped by
-// wfmh_coverage_paf's rules (coverage::classify_line); a line whose query the query FASTA does not have is skipped and counted too.
+// --pav-paf: the presence table of an existing aligned PAF; a line whose query the query FASTA does not have is skipped and counted too
 int wfmh_pav_paf(wfm_handle_t* h, const char* target_fasta, const char* query_fasta_or_null, const char* aligned_paf, const char* bed_path_or_null,
                  uint64_t window, const char* out_path, uint64_t out[4]) {
   const bool with_bed = bed_path_or_null && *bed_path_or_null;
   if (!h || !target_fasta || !aligned_paf || !out_path || with_bed == (window != 0)) return WFM_E_ARG;
-  wfm_pav_t* obj = nullptr;
-  try {
-    std::shared_ptr<wfmash_host::FastaStore> target = wfmash_host::open_shared(target_fasta);
-    std::shared_ptr<wfmash_host::FastaStore> query = query_fasta_or_null && *query_fasta_or_null ? wfmash_host::open_shared(query_fasta_or_null) : target;
-    std::ifstream in(aligned_paf);
-    if (!in.is_open()) throw std::runtime_error(std::string("[wfmash::pav] cannot open ") + aligned_paf);
-    PafRuns pr(h, "pav", *target);
-    const std::vector<uint64_t>&lengths = pr.lengths, &offsets = pr.offsets;
-    std::vector<lift::Interval> iv;
-    uint64_t bed_skipped = 0;
-    if (with_bed) {
-      std::ifstream bedstream(bed_path_or_null, std::ios::binary);
-      if (!bedstream.is_open()) throw std::runtime_error(std::string("[wfmash::pav] cannot open ") + bed_path_or_null);
-      const std::string bed_text((std::istreambuf_iterator<char>(bedstream)), std::istreambuf_iterator<char>());
-      lift::Bed bed = lift::parse_bed(bed_text, [&](const std::string& name) { return target->find(name); }, lengths, offsets);
-      iv = std::move(bed.iv);
-      bed_skipped = bed.skipped;
-    } else {
-      iv = pav::windows(lengths, offsets, window);
-    }
-    std::vector<std::string> qnames;
-    for (int i = 0; i < query->nseq(); ++i) qnames.push_back(query->name(i));
-    const pav::Columns cols = pav::columns(qnames);
-    std::ofstream outstream(out_path);
-    if (!outstream.is_open()) throw std::runtime_error(std::string("[wfmash::pav] cannot open ") + out_path);
-    std::lock_guard<std::mutex> lk(wflign::handle_lock(h));
-    pr.device(wfm_pav_create(h, offsets.back(), (uint32_t)cols.keys.size(), &obj), "create");
-    uint64_t added = 0, no_query = 0;
-    std::vector<uint32_t> group, flags;  // the column of every line of the batch at hand
-    std::vector<wfm_pav_prob_t> probs;
-    pr.read(in, [&](const verify::Line& l) {
-      const int qi = query->find(l.qname);
-      if (qi < 0) { ++no_query; return false; }
-      group.push_back(cols.of_seq[(size_t)qi]);
-      return true;
-    }, [&]() {
-      probs.resize(pr.probs.size());
-      for (size_t j = 0; j < probs.size(); ++j) probs[j] = wfm_pav_prob_t{pr.probs[j].base, pr.probs[j].runs_off, pr.probs[j].n_runs, group[j]};
-      flags.resize(probs.size());
-      const int refused = pr.device(wfm_pav_add(h, obj, probs.data(), probs.size(), pr.runs.data(), pr.runs.size(), flags.data()), "add");
-      added += probs.size() - (uint64_t)refused;
-      pr.refused((uint64_t)refused);
-      group.clear();
-    });
-    const size_t G = cols.keys.size();
-    std::vector<uint32_t> cells(G * iv.size(), 0u);
-    std::vector<wfm_lift_iv_t> raw(iv.size());
-    for (size_t j = 0; j < iv.size(); ++j) raw[j] = wfm_lift_iv_t{iv[j].gstart, iv[j].gend};
-    pr.device(wfm_pav_matrix(h, obj, raw.data(), raw.size(), cells.data()), "matrix");
-    uint64_t counts[3] = {0, 0, 0};
-    wfm_pav_counts(obj, counts);
-    wfm_pav_free(obj);
-    obj = nullptr;
-    pav::table(outstream, cols.keys, pr.names, iv, cells.data());
-    std::cerr << "[wfmash::pav] " << iv.size() << " intervals (" << bed_skipped << " BED lines skipped) x " << G << " groups, " << added << " lines added, "
-              << pr.skipped_clause("", &no_query) << ", " << counts[1] << " union intervals" << std::endl;
-    if (out) { out[0] = added; out[1] = iv.size(); out[2] = counts[1]; out[3] = bed_skipped; }
-    return WFM_OK;
-  } catch (const std::exception& e) {
-    if (obj) wfm_pav_free(obj);
-    std::cerr << e.what() << std::endl;
-    wfm_set_error(h, e.what());
-    return WFM_E_ARG;
-  }
+  return guarded(h, [&] {
+    const PafPassResult r = wflign::run_paf_pass(h, PafPassCall{wflign::SW_PAV, "pav", target_fasta, query_fasta_or_null, aligned_paf, bed_path_or_null, out_path, window});
+    std::cerr << "[wfmash::pav] " << r.end.c[0] << " intervals (" << r.end.c[2] << " BED lines skipped) x " << r.groups << " groups, " << r.counts[0] << " lines added, "
+              << skipped_clause(r, "", true) << ", " << r.end.c[1] << " union intervals" << std::endl;
+    if (out) { out[0] = r.counts[0]; out[1] = r.end.c[0]; out[2] = r.end.c[1]; out[3] = r.end.c[2]; }
+  });
 }
 
-// --transitive-paf: the closure of the BED's intervals over an existing aligned PAF.  Lines go to a trans object in batches of runs, read
-// and skipped by wfmh_coverage_paf's rules (coverage::classify_line); a line whose query neither FASTA has is skipped and counted too; the
-// closure once, at the end.
+// --transitive-paf: the closure of the BED's intervals over an existing aligned PAF; a line whose query neither FASTA has is skipped and
+// counted too
 int wfmh_transitive_paf(wfm_handle_t* h, const char* target_fasta, const char* query_fasta_or_null, const char* aligned_paf, const char* bed_path,
                         const char* out_path, uint32_t depth, uint64_t out[4]) {
   if (!h || !target_fasta || !aligned_paf || !bed_path || !out_path) return WFM_E_ARG;
-  wfm_trans_t* obj = nullptr;
-  try {
-    std::shared_ptr<wfmash_host::FastaStore> target = wfmash_host::open_shared(target_fasta);
-    std::shared_ptr<wfmash_host::FastaStore> query = query_fasta_or_null && *query_fasta_or_null ? wfmash_host::open_shared(query_fasta_or_null) : target;
-    std::ifstream in(aligned_paf);
-    if (!in.is_open()) throw std::runtime_error(std::string("[wfmash::transitive] cannot open ") + aligned_paf);
-    std::ifstream bedstream(bed_path, std::ios::binary);
-    if (!bedstream.is_open()) throw std::runtime_error(std::string("[wfmash::transitive] cannot open ") + bed_path);
-    const std::string bed_text((std::istreambuf_iterator<char>(bedstream)), std::istreambuf_iterator<char>());
-    PafRuns pr(h, "transitive", *target);
-    std::vector<std::string> qnames;
-    std::vector<uint64_t> qlengths;
-    for (int i = 0; i < query->nseq(); ++i) { qnames.push_back(query->name(i)); qlengths.push_back((uint64_t)query->length(i)); }
-    const transitive::World world = transitive::make_world(pr.names, pr.lengths, qnames, qlengths);
-    if (world.n_bases() >= ((uint64_t)1 << 40)) throw std::runtime_error("[wfmash::transitive] the sequences hold 2^40 bases or more");
-    const lift::Bed seeds = transitive::parse_seeds(bed_text, world);
-    if (seeds.iv.size() >= ((size_t)1 << 24)) throw std::runtime_error("[wfmash::transitive] the BED holds 2^24 seeds or more");
-    std::ofstream outstream(out_path);
-    if (!outstream.is_open()) throw std::runtime_error(std::string("[wfmash::transitive] cannot open ") + out_path);
-    std::lock_guard<std::mutex> lk(wflign::handle_lock(h));
-    pr.device(wfm_trans_create(h, world.n_bases(), &obj), "create");
-    uint64_t added = 0, no_query = 0;
-    std::vector<std::pair<uint64_t, bool>> where;  // of the batch at hand: the world place of the line's forward query window, its strand
-    std::vector<wfm_trans_prob_t> probs;
-    std::vector<uint32_t> flags;
-    pr.read(in, [&](const verify::Line& l) {
-      const int qi = world.find(l.qname);
-      if (qi < 0 || (uint64_t)l.qe > world.lengths[(size_t)qi]) { ++no_query; return false; }
-      where.emplace_back(transitive::query_world(world.offsets[(size_t)qi], (uint64_t)l.qs), l.rev);
-      return true;
-    }, [&]() {
-      probs.resize(pr.probs.size());
-      flags.resize(probs.size());
-      for (size_t j = 0; j < probs.size(); ++j)
-        probs[j] = wfm_trans_prob_t{pr.probs[j].base, where[j].first, pr.probs[j].runs_off, pr.probs[j].n_runs, where[j].second ? WFM_TRANS_REVERSE : 0u};
-      const int refused = pr.device(wfm_trans_add(h, obj, probs.data(), probs.size(), pr.runs.data(), pr.runs.size(), flags.data()), "add");
-      added += probs.size() - (uint64_t)refused;
-      pr.refused((uint64_t)refused);
-      where.clear();
-    });
-    std::vector<wfm_lift_iv_t> raw(seeds.iv.size());
-    for (size_t i = 0; i < raw.size(); ++i) raw[i] = wfm_lift_iv_t{seeds.iv[i].gstart, seeds.iv[i].gend};
-    std::vector<wfm_trans_seed_t> per(raw.size());
-    wfm_trans_iv_t* ivs = nullptr;
-    size_t n_ivs = 0;
-    pr.device(wfm_trans_closure(h, obj, raw.data(), raw.size(), depth, &ivs, &n_ivs, per.data()), "closure");
-    uint64_t counts[6] = {0, 0, 0, 0, 0, 0};
-    wfm_trans_counts(obj, counts);
-    wfm_trans_free(obj);
-    obj = nullptr;
-    static_assert(sizeof(transitive::ClosureIv) == sizeof(wfm_trans_iv_t) && sizeof(transitive::SeedCall) == sizeof(wfm_trans_seed_t),
-                  "transitive_text.hpp restates wfm_trans_iv_t and wfm_trans_seed_t");
-    const uint64_t lines = transitive::file(outstream, world, seeds.iv, (const transitive::SeedCall*)per.data(), (const transitive::ClosureIv*)ivs);
-    wfm_trans_free_list(ivs);
-    std::cerr << "[wfmash::transitive] " << seeds.iv.size() << " seeds (" << seeds.skipped << " BED lines skipped), " << added << " lines added, "
-              << pr.skipped_clause("", &no_query) << ", " << counts[3] << " rounds, " << lines << " lines written" << std::endl;
-    if (out) { out[0] = added; out[1] = lines; out[2] = counts[3]; out[3] = seeds.skipped; }
-    return WFM_OK;
-  } catch (const std::exception& e) {
-    if (obj) wfm_trans_free(obj);
-    std::cerr << e.what() << std::endl;
-    wfm_set_error(h, e.what());
-    return WFM_E_ARG;
-  }
+  return guarded(h, [&] {
+    const PafPassResult r =
+        wflign::run_paf_pass(h, PafPassCall{wflign::SW_TRANSITIVE, "transitive", target_fasta, query_fasta_or_null, aligned_paf, bed_path, out_path, depth});
+    std::cerr << "[wfmash::transitive] " << r.end.extra << " seeds (" << r.end.c[2] << " BED lines skipped), " << r.counts[0] << " lines added, "
+              << skipped_clause(r, "", true) << ", " << r.end.c[1] << " rounds, " << r.end.c[0] << " lines written" << std::endl;
+    if (out) { out[0] = r.counts[0]; out[1] = r.end.c[0]; out[2] = r.end.c[1]; out[3] = r.end.c[2]; }
+  });
 }
 
 // test hook (no GPU): the bedGraph of n_iv intervals over n_seq sequences, as the align phase writes it.  malloc'd, wfmh_free.

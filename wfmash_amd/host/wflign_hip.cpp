@@ -2,11 +2,8 @@
 // The CIGAR surgery, the patch plan and the record writers are in cigar_ops.hpp; all wavefront arithmetic is done on the GPU
 // through wfm_align_batch (no CPU fallback).
 #include "wflign_hip.hpp"
-#include "parallel.hpp"
-#include "lift_text.hpp"
-#include "chain_text.hpp"
+#include "run_passes.hpp"
 #include "maf_text.hpp"
-#include "transitive_text.hpp"
 #include "../csrc/wfa_handle.h"
 
 #include <algorithm>
@@ -24,19 +21,9 @@ namespace wflign {
 // ---------------------------------------------------------------------------
 // batch pipeline
 // ---------------------------------------------------------------------------
-namespace {
-// fn(i) for i in [0, n) on up to `threads` threads; records are independent of each other (the reference runs one
-// Taskflow task per record, computeAlignments.hpp:391-435)
-template <typename F>
-void for_each_record(size_t n, int threads, F&& fn) {
-  const int nt = (int)std::min<size_t>((size_t)std::max(1, threads), (n + 7) / 8);  // no thread for fewer than 8 records
-  wfmash_host::parallel_for(n, nt, fn);  // (the process's pool: a pass used to start and join its own threads, 2 - 4 ms each -- parallel.hpp)
-}
-
 // A handle runs one batch at a time; several host threads may feed the same GPU (the align driver keeps up to three
 // batches per device in flight so that the host stages of one overlap the device stages of another): calls are
 // serialised here.
-}  // namespace
 std::mutex& handle_lock(wfm_handle_t* h) {
   static std::mutex reg;
   static std::map<wfm_handle_t*, std::unique_ptr<std::mutex>> locks;
@@ -209,9 +196,6 @@ wfm_problem_ref_t tail_problem(const BiwfaRecord& r, const Erosion& e) {  // wfl
   p.text_begin_free = 0; p.text_end_free = (int32_t)e.query_eroded;
   return p;
 }
-
-using Clock = std::chrono::steady_clock;
-double ms_between(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
 
 struct WindowSet;  // the records' final runs as device problems (left_align_records, cs_records, variant_records, maf_records)
 
@@ -713,117 +697,33 @@ void write_record(BiwfaBatch& b, size_t ri) {
   r.paf += '\n';
   counts_of(SW_CS)[0] += 1; counts_of(SW_CS)[1] += r.cs.size();
 }
-// ---- the written records of a batch as the align driver's passes take them, packed ONCE per batch.  It runs behind write_record, where
-// the filters have spoken.  A record's problem is what its line spells: the ops trimmed of their leading and trailing I and D runs
-// (window_parts' rule, trim_and_filter's), at base = the target sequence's offset in the concatenation + the target start the writer
-// wrote -- variant_records' ts.  Nothing goes up but runs.  A record whose ops the runs cannot hold is a defect: it is in no list, and
-// every stage counts and reports it. ----
-struct PackedRuns {
-  std::vector<wfm_cov_prob_t> probs;   // base, runs_off, n_runs of every record packed
-  std::vector<uint32_t> runs;          // their trimmed ops as run words
-  std::vector<size_t> rec;             // the record's index in the batch
-  std::vector<chain::Record> where;    // the record as its line has it: the forward windows [qs, qe) and [ts, te) the runs spell (variant_records' qs, qe), sizes,
-                                       // strand, and -- where a pass that writes them is on (--lift, --chain, --chain-net) -- the names
-  uint64_t unknown = 0;                // records whose ops the runs cannot hold
-  double ms = 0;                       // what the packing took
-};
+// ---- the written records of a batch as the align driver's passes take them, packed ONCE per batch (packed_runs.hpp).  It runs behind
+// write_record, where the filters have spoken.  A record's base = the target sequence's offset in the concatenation + the target start
+// the writer wrote -- variant_records' ts.  A record whose ops the runs cannot hold is a defect: it is in no list, and every stage counts
+// and reports it.  The names go along where a pass that writes them is on (--lift, --chain, --chain-net). ----
 PackedRuns pack_written(const BiwfaBatch& b) {
   const auto t0 = Clock::now();
   PackedRuns pk;
+  pk.order_base = b.passes->batch << 32;
   const bool with_names = b.passes->on[SW_LIFT] || b.passes->on[SW_CHAIN] || b.passes->on[SW_CHAIN_NET];
   for (size_t ri = 0; ri < b.recs.size(); ++ri) {
     const BiwfaRecord& r = b.recs[ri];
     if (!r.ok || !r.written) continue;
-    const CigarOps& ops = r.ops;
-    size_t ob = 0, oe = ops.size();
-    uint64_t ta = 0, qa = 0, q_len = 0, t_len = 0;
-    while (ob < oe && (ops[ob].second == 'I' || ops[ob].second == 'D')) { (ops[ob].second == 'D' ? ta : qa) += (uint64_t)ops[ob].first; ++ob; }
-    while (oe > ob && (ops[oe - 1].second == 'I' || ops[oe - 1].second == 'D')) --oe;
-    if (oe == ob) continue;
-    const wfm_cov_prob_t p{r.target_global + r.target_offset + ta, (uint64_t)pk.runs.size(), (uint32_t)(oe - ob), 0u};
-    bool known = true;
-    for (size_t k = ob; k < oe; ++k) {
-      const char c = ops[k].second;
-      const uint32_t op = c == '=' ? 0u : c == 'X' ? 1u : c == 'I' ? 2u : c == 'D' ? 3u : 4u;
-      if (op > 3u || ops[k].first <= 0 || (uint32_t)ops[k].first >= (1u << 30)) { known = false; break; }
-      pk.runs.push_back(((uint32_t)ops[k].first << 2) | op);
-      if (op != 3u) q_len += (uint64_t)ops[k].first;
-      if (op != 2u) t_len += (uint64_t)ops[k].first;
-    }
-    if (!known) { pk.runs.resize((size_t)p.runs_off); ++pk.unknown; continue; }
-    pk.probs.push_back(p);
-    pk.rec.push_back(ri);
     chain::Record cr;
     if (with_names) { cr.qname = r.query_name; cr.tname = r.target_name; }
     cr.rev = r.query_is_rev;
     cr.qsize = r.query_total_length; cr.tsize = r.target_total_length;
-    cr.qs = r.query_is_rev ? r.query_offset + (r.query_length - qa - q_len) : r.query_offset + qa;
-    cr.qe = cr.qs + q_len;
-    cr.ts = r.target_offset + ta;
-    cr.te = cr.ts + t_len;
-    pk.where.push_back(std::move(cr));
+    cr.qs = r.query_offset; cr.qe = r.query_offset + r.query_length; cr.ts = r.target_offset;
+    if (pack_ops(pk, r.ops, std::move(cr), Place{r.pav_group, r.query_global, r.target_global}) == 1) pk.rec.push_back(ri);
   }
   pk.ms = ms_between(t0, Clock::now());
   return pk;
 }
 
-// ---- the frame of the stages behind pack_written: ONE device call per batch under the handle's lock (t1: when it was had), its message
-// copied while the handle is still this thread's.  Without problems nothing is called. ----
-template <class Call>
-int device_call(BiwfaBatch& b, size_t n, Clock::time_point& t1, Call call) {
-  if (!n) return WFM_OK;
-  std::lock_guard<std::mutex> lk(handle_lock(b.h));
-  t1 = Clock::now();
-  const int rc = call();
-  if (rc < 0 && b.stats) b.stats->error = wfm_last_error(b.h);
-  return rc;
-}
-// ... and of those that add to the object of the batch's handle: the records added into the switch's count 0, and the warning -- a record
-// the device refuses (the call's return) or that never went to it (alone) adds nothing, is counted and reported.  What differs between
-// them beside that is how a problem is made of a packed record and which wfm_*_add takes them.
-struct AddStage { SwitchId sw; const char* tag; const char* not_added; };
-template <class Call>
-int add_stage(BiwfaBatch& b, const AddStage& s, size_t n, uint64_t alone, Clock::time_point& t1, Call call) {
-  const int rc = device_call(b, n, t1, call);
-  if (rc < 0) return rc;
-  counts_of(s.sw)[0] += n - (uint64_t)rc;
-  if (rc > 0 || alone)
-    fprintf(stderr, "[wflign] %s: %llu records of a batch were NOT added%s\n", s.tag, (unsigned long long)((uint64_t)rc + alone), s.not_added);
-  return rc;
-}
-
-// ---- --coverage: the packed runs into the depth object of the batch's handle (wfm_coverage_add) ----
-int coverage_records(BiwfaBatch& b, const PackedRuns& pk) {
-  auto t0 = Clock::now(), t1 = t0;
-  const size_t n = pk.probs.size();
-  std::vector<uint32_t> flags(n);
-  const int rc = add_stage(b, {SW_COVERAGE, "coverage", " to the depth (their runs leave the target or cannot be held)"}, n, pk.unknown, t1, [&] {
-    return wfm_coverage_add(b.h, b.passes->get<wfm_coverage_t>(SW_COVERAGE), pk.probs.data(), n, pk.runs.data(), pk.runs.size(), flags.data());
-  });
-  if (rc < 0) return rc;
-  if (getenv("WFM_DEBUG"))
-    fprintf(stderr, "[wflign] coverage: %zu records, %zu runs, %d flagged, %.1f ms\n", n, pk.runs.size(), rc, pk.ms + ms_between(t0, Clock::now()));
-  return 0;
-}
-// ---- --pav: the same problems into the presence object of the batch's handle, each with the column of its query's group (wfm_pav_add) ----
-int pav_records(BiwfaBatch& b, const PackedRuns& pk) {
-  auto t0 = Clock::now(), t1 = t0;
-  const size_t n = pk.probs.size();
-  std::vector<wfm_pav_prob_t> probs(n);
-  for (size_t j = 0; j < n; ++j) probs[j] = wfm_pav_prob_t{pk.probs[j].base, pk.probs[j].runs_off, pk.probs[j].n_runs, b.recs[pk.rec[j]].pav_group};
-  std::vector<uint32_t> flags(n);
-  const int rc = add_stage(b, {SW_PAV, "pav", " (their runs leave the target or cannot be held, or their query has no column)"}, n, pk.unknown, t1, [&] {
-    return wfm_pav_add(b.h, b.passes->get<wfm_pav_t>(SW_PAV), probs.data(), n, pk.runs.data(), pk.runs.size(), flags.data());
-  });
-  if (rc < 0) return rc;
-  if (getenv("WFM_DEBUG"))
-    fprintf(stderr, "[wflign] pav: %zu records, %zu runs, %d flagged, %.1f ms (runs %.1f, device call %.1f)\n", n, pk.runs.size(), rc,
-            pk.ms + ms_between(t0, Clock::now()), pk.ms + ms_between(t0, t1), ms_between(t1, Clock::now()));
-  return 0;
-}
 // ---- --genotypes: the variants variant_records called for the records WRITTEN (masked SNVs left out), each at its global position --
 // the problem's base + p -- under the column of its query's group, and the same records' runs for the = union: one wfm_sites_add_variants
-// and one wfm_sites_add_ref call per batch.  A record without calls (the device flagged it) or without a column never goes to the device. ----
+// and one wfm_sites_add_ref call per batch.  A record without calls (the device flagged it) or without a column never goes to the device;
+// it adds nothing, is counted and reported, as one the device refuses. ----
 int genotype_records(BiwfaBatch& b, const PackedRuns& pk) {
   auto t0 = Clock::now(), t1 = t0;
   const KeptCalls* kc = b.calls.get();
@@ -836,158 +736,57 @@ int genotype_records(BiwfaBatch& b, const PackedRuns& pk) {
   std::vector<wfm_pav_prob_t> probs;
   uint64_t alone = pk.unknown;
   for (size_t j = 0; j < pk.probs.size(); ++j) {
-    const BiwfaRecord& r = b.recs[pk.rec[j]];
+    const uint32_t group = pk.place[j].group;
     const size_t part = part_of[pk.rec[j]];
-    if (part == (size_t)-1 || kc->per[part].flags || r.pav_group >= n_groups) { ++alone; continue; }
-    probs.push_back(wfm_pav_prob_t{pk.probs[j].base, pk.probs[j].runs_off, pk.probs[j].n_runs, r.pav_group});
+    if (part == (size_t)-1 || kc->per[part].flags || group >= n_groups) { ++alone; continue; }
+    probs.push_back(wfm_pav_prob_t{pk.probs[j].base, pk.probs[j].runs_off, pk.probs[j].n_runs, group});
     const wfm_varcall_t& pc = kc->per[part];
     for (uint64_t k = pc.first; k < pc.first + pc.count; ++k) {
       const wfm_variant_t& v = kc->vars[k];
       if (v.kind & WFM_VAR_MASKED) continue;
-      vars.push_back(wfm_site_var_t{pk.probs[j].base + v.p, v.kind & 255u, r.pav_group, v.ref_len, v.alt_len, (uint64_t)alleles.size()});
+      vars.push_back(wfm_site_var_t{pk.probs[j].base + v.p, v.kind & 255u, group, v.ref_len, v.alt_len, (uint64_t)alleles.size()});
       alleles.append(kc->alleles + v.off, (size_t)v.ref_len + v.alt_len);
     }
   }
   std::vector<uint32_t> flags(probs.size());
-  const int rc = add_stage(b, {SW_GENOTYPES, "genotypes", " (no calls, runs that leave the target or cannot be held, or a query without a column)"},
-                           probs.size(), alone, t1, [&] {
+  std::string error;
+  const int rc = device_call(b.h, probs.size(), t1, error, [&] {
     const int rv = wfm_sites_add_variants(b.h, sites, vars.data(), vars.size(), alleles.data(), alleles.size());
     return rv != WFM_OK ? rv : wfm_sites_add_ref(b.h, sites, probs.data(), probs.size(), pk.runs.data(), pk.runs.size(), flags.data());
   });
-  if (rc < 0) return rc;
-  counts_of(SW_GENOTYPES)[3] += alone + (uint64_t)rc;
+  if (rc < 0) { if (b.stats) b.stats->error = error; return rc; }
+  std::atomic<uint64_t>* c = counts_of(SW_GENOTYPES);
+  c[0] += probs.size() - (uint64_t)rc; c[3] += alone + (uint64_t)rc;
+  if (rc > 0 || alone)
+    fprintf(stderr, "[wflign] genotypes: %llu records of a batch were NOT added (no calls, runs that leave the target or cannot be held, or a query without a column)\n",
+            (unsigned long long)((uint64_t)rc + alone));
   if (getenv("WFM_DEBUG"))
     fprintf(stderr, "[wflign] genotypes: %zu records, %zu variants, %zu allele bytes, %zu runs, %d flagged, %.1f ms (host lists %.1f, device calls %.1f)\n", probs.size(),
             vars.size(), alleles.size(), pk.runs.size(), rc, ms_between(t0, Clock::now()), ms_between(t0, t1), ms_between(t1, Clock::now()));
   return 0;
 }
-// ---- --lift: the BED intervals through the same problems (wfm_lift_runs).  The lines of a record go into BiwfaRecord::lift in the order
-// the device gives them: ascending interval.  A record the device refuses has no lines and is reported. ----
-int lift_records(BiwfaBatch& b, const PackedRuns& pk) {
-  auto t0 = Clock::now(), t1 = t0;
-  const size_t n = pk.probs.size();
-  for (BiwfaRecord& r : b.recs) r.lift.clear();
-  std::vector<lift::Record> where(n);
-  for (size_t j = 0; j < n; ++j) {
-    const chain::Record& cr = pk.where[j];
-    lift::Record& lr = where[j];
-    lr.qname = cr.qname; lr.tname = cr.tname; lr.rev = cr.rev;
-    lr.qs = cr.qs; lr.qe = cr.qe; lr.ts = cr.ts;
-  }
-  wfm_lift_t* lifts = nullptr;
-  size_t n_lifts = 0;
-  std::vector<wfm_liftcall_t> per(n);
-  const int rc = device_call(b, n, t1, [&] {
-    return wfm_lift_runs(b.h, b.passes->get<const wfm_liftset_t>(SW_LIFT), pk.probs.data(), n, pk.runs.data(), pk.runs.size(), &lifts, &n_lifts, per.data());
-  });
-  if (rc < 0) return rc;
-  const auto t2 = Clock::now();
-  const std::vector<lift::Interval>& iv = b.passes->tables->lift_iv;
-  std::atomic<uint64_t> lines{0}, empty{0}, refused{0};
-  for_each_record(n, b.fmt.threads, [&](size_t j) {
-    if (per[j].flags) { refused += 1; return; }
-    std::string& out = b.recs[pk.rec[j]].lift;
-    uint64_t e = 0;
-    for (uint64_t k = per[j].first; k < per[j].first + per[j].count; ++k) {
-      const wfm_lift_t& l = lifts[k];
-      lift::lift_line(out, where[j], iv[l.interval], l.p0, l.p1, l.t0, l.t1, l.eq, l.x);
-      e += l.eq + l.x == 0;
-    }
-    lines += per[j].count; empty += e;
-  });
-  wfm_free_lifts(lifts);
-  std::atomic<uint64_t>* c = counts_of(SW_LIFT);
-  c[0] += n - refused.load(); c[1] += lines.load(); c[2] += empty.load();
-  if (refused.load() || pk.unknown)
-    fprintf(stderr, "[wflign] lift: %llu records of a batch were NOT lifted (their runs leave the target or cannot be held)\n",
-            (unsigned long long)(refused.load() + pk.unknown));
-  if (getenv("WFM_DEBUG"))
-    fprintf(stderr, "[wflign] lift: %zu records, %zu runs, %zu lifts, %.1f ms (runs %.1f, device call %.1f, text %.1f)\n", n, pk.runs.size(), n_lifts,
-            pk.ms + ms_between(t0, Clock::now()), pk.ms + ms_between(t0, t1), ms_between(t1, t2), ms_between(t2, Clock::now()));
-  return 0;
-}
-// ---- --chain: the same problems compacted to the blocks and gaps of a UCSC chain (wfm_chain_runs).  swap: the query is the chain's first
-// side (chain_text.hpp).  A record's chain goes into BiwfaRecord::chain without its id, which the ordered writer gives it.  A record the
-// device refuses has no chain and is reported. ----
-static_assert(sizeof(chain::Block) == sizeof(wfm_chain_block_t), "chain_text.hpp restates wfm_chain_block_t");
-int chain_records(BiwfaBatch& b, const PackedRuns& pk) {
-  auto t0 = Clock::now(), t1 = t0;
-  const bool swap = b.passes->tables->chain_swap;
-  for (BiwfaRecord& r : b.recs) r.chain.clear();
-  const size_t n = pk.probs.size();
-  std::vector<wfm_chain_prob_t> probs(n);
-  for (size_t j = 0; j < n; ++j) probs[j] = wfm_chain_prob_t{pk.probs[j].runs_off, pk.probs[j].n_runs, chain::flags_of(swap, pk.where[j].rev)};
-  wfm_chain_block_t* blocks = nullptr;
-  size_t n_blocks = 0;
-  std::vector<wfm_chaincall_t> per(n);
-  const int rc = device_call(b, n, t1, [&] { return wfm_chain_runs(b.h, probs.data(), n, pk.runs.data(), pk.runs.size(), &blocks, &n_blocks, per.data()); });
-  if (rc < 0) return rc;
-  const auto t2 = Clock::now();
-  std::atomic<uint64_t> chains{0}, refused{0};
-  for_each_record(n, b.fmt.threads, [&](size_t j) {
-    if (per[j].flags) { refused += 1; return; }
-    chain::Ends e;
-    e.lead_dt = per[j].lead_dt; e.lead_dq = per[j].lead_dq; e.trail_dt = per[j].trail_dt; e.trail_dq = per[j].trail_dq; e.eq = per[j].eq;
-    chain::chain_body(b.recs[pk.rec[j]].chain, pk.where[j], swap, e, (const chain::Block*)blocks + per[j].first, per[j].count);
-    chains += per[j].count != 0;
-  });
-  wfm_free_chain(blocks);
-  std::atomic<uint64_t>* c = counts_of(SW_CHAIN);
-  c[0] += chains.load(); c[1] += n_blocks; c[2] += refused.load();
-  if (refused.load() || pk.unknown)
-    fprintf(stderr, "[wflign] chain: %llu records of a batch have NO chain (their runs cannot be held)\n", (unsigned long long)(refused.load() + pk.unknown));
-  if (getenv("WFM_DEBUG"))
-    fprintf(stderr, "[wflign] chain: %zu records, %zu runs, %zu blocks, %.1f ms (runs %.1f, device call %.1f, text %.1f)\n", n, pk.runs.size(), n_blocks,
-            pk.ms + ms_between(t0, Clock::now()), pk.ms + ms_between(t0, t1), ms_between(t1, t2), ms_between(t2, Clock::now()));
-  return 0;
-}
-// ---- --chain-net: the same problems into the net object of the batch's handle (wfm_net_add), each with score = its = columns (counted
-// on the device) and order = batch << 32 | its index among the records packed: the key the ordered writers sort by.  What the chain's
-// header needs of every record added goes to the batch's texts. ----
-int net_records(BiwfaBatch& b, const PackedRuns& pk) {
-  auto t0 = Clock::now(), t1 = t0;
-  const size_t n = pk.probs.size();
-  std::vector<wfm_net_prob_t> probs(n);
-  for (size_t j = 0; j < n; ++j)
-    probs[j] = wfm_net_prob_t{pk.probs[j].base, pk.probs[j].runs_off, pk.probs[j].n_runs, WFM_NET_SCORE_EQ, (b.passes->batch << 32) | (uint64_t)j};
-  std::vector<uint32_t> flags(n);
-  const int rc = add_stage(b, {SW_CHAIN_NET, "chain-net", " (their runs leave the target or cannot be held)"}, n, pk.unknown, t1, [&] {
-    return wfm_net_add(b.h, b.passes->get<wfm_net_t>(SW_CHAIN_NET), probs.data(), n, pk.runs.data(), pk.runs.size(), flags.data());
-  });
-  if (rc < 0) return rc;
-  if (b.texts)
-    for (size_t j = 0; j < n; ++j)
-      if (!flags[j]) b.texts->net_heads.push_back(NetHead{probs[j].order, b.recs[pk.rec[j]].target_global, pk.where[j]});
-  if (getenv("WFM_DEBUG"))
-    fprintf(stderr, "[wflign] chain-net: %zu records, %zu runs, %d flagged, %.1f ms (runs %.1f, device call %.1f)\n", n, pk.runs.size(), rc,
-            pk.ms + ms_between(t0, Clock::now()), pk.ms + ms_between(t0, t1), ms_between(t1, Clock::now()));
-  return 0;
-}
-// ---- --transitive: the same problems into the trans object of the batch's handle (wfm_trans_add), each with the world position of its
-// first target base (the problem's base: the world begins with the target's sequences) and of the first base of its forward query window
-// (in the query sequence's place in the world). ----
-int trans_records(BiwfaBatch& b, const PackedRuns& pk) {
-  auto t0 = Clock::now(), t1 = t0;
-  const size_t n = pk.probs.size();
-  std::vector<wfm_trans_prob_t> probs(n);
-  for (size_t j = 0; j < n; ++j)
-    probs[j] = wfm_trans_prob_t{pk.probs[j].base, transitive::query_world(b.recs[pk.rec[j]].query_global, pk.where[j].qs), pk.probs[j].runs_off,
-                                pk.probs[j].n_runs, pk.where[j].rev ? WFM_TRANS_REVERSE : 0u};
-  std::vector<uint32_t> flags(n);
-  const int rc = add_stage(b, {SW_TRANSITIVE, "transitive", " (their runs leave their sequences or cannot be held)"}, n, pk.unknown, t1, [&] {
-    return wfm_trans_add(b.h, b.passes->get<wfm_trans_t>(SW_TRANSITIVE), probs.data(), n, pk.runs.data(), pk.runs.size(), flags.data());
-  });
-  if (rc < 0) return rc;
-  if (getenv("WFM_DEBUG"))
-    fprintf(stderr, "[wflign] transitive: %zu records, %zu runs, %d flagged, %.1f ms (runs %.1f, host %.1f, device call %.1f)\n", n, pk.runs.size(), rc,
-            pk.ms + ms_between(t0, Clock::now()), pk.ms, ms_between(t0, t1), ms_between(t1, Clock::now()));
-  return 0;
-}
 
-// the stages behind pack_written, in the order they run
-const struct { SwitchId id; int (*run)(BiwfaBatch&, const PackedRuns&); } kRunStages[] = {
-    {SW_COVERAGE, coverage_records}, {SW_PAV, pav_records},         {SW_GENOTYPES, genotype_records}, {SW_LIFT, lift_records},
-    {SW_CHAIN, chain_records},       {SW_CHAIN_NET, net_records},   {SW_TRANSITIVE, trans_records}};
+// the stages behind pack_written, in the order they run, and what the align driver says of the records a stage left out: those the device
+// refused and those that never went to it (pk.unknown)
+const struct { SwitchId id; const char* tag; const char* left_out; } kRunStages[] = {
+    {SW_COVERAGE, "coverage", "were NOT added to the depth (their runs leave the target or cannot be held)"},
+    {SW_PAV, "pav", "were NOT added (their runs leave the target or cannot be held, or their query has no column)"},
+    {SW_GENOTYPES, "genotypes", nullptr},  // (genotype_records: it needs variant_records' kept calls, and reports for itself)
+    {SW_LIFT, "lift", "were NOT lifted (their runs leave the target or cannot be held)"},
+    {SW_CHAIN, "chain", "have NO chain (their runs cannot be held)"},
+    {SW_CHAIN_NET, "chain-net", "were NOT added (their runs leave the target or cannot be held)"},
+    {SW_TRANSITIVE, "transitive", "were NOT added (their runs leave their sequences or cannot be held)"}};
+
+// a stage of run_passes.hpp on the batch, reported the align driver's way: its counts into the switch's, the warning, the WFM_DEBUG line
+int run_stage(BiwfaBatch& b, SwitchId id, const char* tag, const char* left_out, PackedRuns& pk) {
+  const StageOutcome o = stage_of(id)(b.h, b.fmt.threads, *b.passes, pk);
+  if (o.rc < 0) { if (b.stats) b.stats->error = o.error; return o.rc; }
+  std::atomic<uint64_t>* c = counts_of(id);
+  for (int k = 0; k < 3; ++k) c[k] += o.counts[k];
+  if (o.refused || pk.unknown) fprintf(stderr, "[wflign] %s: %llu records of a batch %s\n", tag, (unsigned long long)(o.refused + pk.unknown), left_out);
+  if (!o.debug.empty()) fputs(o.debug.c_str(), stderr);
+  return 0;
+}
 
 void set_switch(SwitchId id, bool on, const char* out, const char* bed, uint64_t option) {
   Switch& s = g_switch[id];
@@ -1063,9 +862,10 @@ int do_biwfa_alignment_batch(wfm_handle_t* h, std::vector<BiwfaRecord>& recs, co
   bool any = false;
   for (const auto& s : kRunStages) any = any || b.passes->on[s.id];
   if (any) {  // one packing for the stages that are on; each makes its own device call
-    const PackedRuns pk = pack_written(b);
+    PackedRuns pk = pack_written(b);
     for (const auto& s : kRunStages)
-      if (b.passes->on[s.id] && (rc = s.run(b, pk)) < 0) return rc;
+      if (b.passes->on[s.id] && (rc = s.left_out ? run_stage(b, s.id, s.tag, s.left_out, pk) : genotype_records(b, pk)) < 0) return rc;
+    if (b.texts) take_texts(pk, *b.texts);
   }
   if (dbg)
     fprintf(stderr, "[wflign] %zu records: main alignment + runs + scans %.1f ms (incl. waiting for the device), patches %.1f ms (%zu tails scanned after their heads), swizzle + records %.1f ms\n",

@@ -17,21 +17,22 @@
 //   variant_records    --variants and --genotypes only: the VCF lines of every record's line, one wfm_call_variants call (on the same
 //                      windows, uploaded once whichever of the switches are on); --genotypes keeps the calls for genotype_records
 //   write_record       PAF / SAM record (+ cs:Z: as its last field)   (wflign.cpp:434-454)
-//   coverage_records   --coverage only: the runs of every record WRITTEN into the handle's depth object, one wfm_coverage_add call
-//                      (nothing is uploaded but runs; whether a record is written is only known behind write_record)
-//   pav_records        --pav only: the runs of every record WRITTEN, with the column of its query's group, into the handle's presence
-//                      object, one wfm_pav_add call (runs alone again)
+//   pack_written      the records WRITTEN as packed runs (packed_runs.hpp), once per batch, for the stages below: nothing goes up but runs, and
+//                      whether a record is written is only known behind write_record
 //   genotype_records   --genotypes only: the kept calls of every record WRITTEN at their global positions, and the records' runs, into
 //                      the handle's sites object, one wfm_sites_add_variants and one wfm_sites_add_ref call
-//   lift_records       --lift only: the BED intervals lifted through the runs of every record WRITTEN, one wfm_lift_runs call
-//                      (runs alone again), the record's lines into BiwfaRecord::lift
-//   chain_records      --chain only: the runs of every record WRITTEN compacted to the blocks and gaps of a UCSC chain, one
-//                      wfm_chain_runs call (runs alone again), the record's chain without its id into BiwfaRecord::chain
-//   trans_records      --transitive only: the runs of every record WRITTEN into the handle's trans object with the record's two places in
-//                      the world, one wfm_trans_add call
-//   net_records        --chain-net only: the runs of every record WRITTEN into the handle's net object, one wfm_net_add call (runs alone
-//                      again), each with score = its = columns and order = batch << 32 | its index among the batch's records packed; what
-//                      the chain's header needs stays on the host, keyed by the order
+//   the stages of run_passes.hpp, which an aligned PAF feeds as well (the --*-paf modes), each wrapped here by what the align driver
+//   reports -- the switch's counts, the warning about records left out, the WFM_DEBUG line:
+//     coverage_records   --coverage: the runs into the handle's depth object, one wfm_coverage_add call
+//     pav_records        --pav: the runs, with the column of the query's group, into the handle's presence object, one wfm_pav_add call
+//     lift_records       --lift: the BED intervals lifted through the runs, one wfm_lift_runs call, the record's lines into PackedRuns::lift
+//     chain_records      --chain: the runs compacted to the blocks and gaps of a UCSC chain, one wfm_chain_runs call, the record's chain
+//                        without its id into PackedRuns::chain
+//     net_records        --chain-net: the runs into the handle's net object, one wfm_net_add call, each with score = its = columns and
+//                        order = batch << 32 | its index among the batch's records packed; what the chain's header needs stays on the
+//                        host, keyed by the order
+//     trans_records      --transitive: the runs into the handle's trans object with the record's two places in the world, one
+//                        wfm_trans_add call
 // and CIGARs are runs (count, op) from the device to the record's text: nothing is expanded to one byte per base.
 #pragma once
 
@@ -49,6 +50,7 @@
 #include "cigar_ops.hpp"  // CigarOps, the CIGAR helpers, plan_patches, PafParams and the two record writers
 #include "lift_text.hpp"
 #include "pav_text.hpp"
+#include "transitive_text.hpp"
 
 namespace wflign {
 
@@ -92,8 +94,6 @@ struct BiwfaRecord {
   bool written = false;              // the filters let the record's line through (write_record)
   uint32_t pav_group = 0;            // --pav, --genotypes: the column of the query sequence's group
   uint64_t query_global = 0;         // --transitive: where the query sequence begins in the world (target_global is the target's place in it)
-  std::string lift;                  // --lift: the lines of the BED intervals the record's target span overlaps, each with its newline ("" if off or not written)
-  std::string chain;                 // --chain: the record's chain without its id (chain_text.hpp; "" if off, not written, refused or without a block)
   std::string maf;                   // --maf: the paragraphs of the record's blocks (maf_text.hpp; "" if off, filtered, or the record has none)
   bool maf_called = false;           // ... the device spelled the record's rows (false: off, or the record was left alone)
   uint32_t maf_blocks = 0;           // ... the blocks in `maf`
@@ -169,7 +169,8 @@ struct RunTables {
   pav::Columns columns;                 // --pav, --genotypes: the groups and the column of every query sequence
   std::vector<lift::Interval> lift_iv;   // --lift: the BED's intervals in the order of the handle's liftset
   bool chain_swap = false;               // --chain: the query is the chain's first side
-  std::vector<uint64_t> query_world;     // --transitive: where each query sequence begins in the world
+  transitive::World world;               // --transitive: the target's sequences, then the query's that no target names
+  std::vector<uint64_t> query_world;     // ... and where each query sequence begins in it
 };
 // in: which passes are on, the object of the batch's handle for each pass that has one, the batch's number and the tables
 struct BatchPasses {
@@ -181,8 +182,8 @@ struct BatchPasses {
   T* get(SwitchId id) const { return static_cast<T*>(object[id]); }
   bool any() const { return std::any_of(on, on + N_PASSES, [](bool b) { return b; }); }
 };
-// out: the batch's PAF / SAM text, the text of each pass that writes per batch (--variants, --lift, --chain, --maf; in the order of the records'
-// lines), and --chain-net's heads of the records added
+// out: the batch's PAF / SAM text (an align batch's), the text of each pass that writes per batch (--variants, --lift, --chain, --maf; in the order
+// of the records' lines), and --chain-net's heads of the records added
 struct BatchTexts {
   std::string paf;
   std::string text[N_PASSES];
